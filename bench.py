@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """bench.py — training throughput of the VRNN hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what takes runs of its own: the
+large-batch sweep and the CPU baseline (VRNN, N = 1).  `--dump-outputs DIR` writes what the last timed step computed (loss,
+metrics, the model's outputs, every parameter after the update and its gradient) as DIR/<name>.npy, at most 64 MB in all.
 
 N > 1: one rank per GPU over RCCL.  Under `python -m torch.distributed.run ... bench.py --gpus N` the ranks come from the
 launcher (RANK / LOCAL_RANK / WORLD_SIZE); run bare, `bench.py --gpus N` starts that launcher itself as a child process BEFORE
@@ -12,12 +16,15 @@ of the N-rank launch.
 A "step" is one full optimisation step of VRNNAudio(DMoL, s=64, h=256, z=256) on a synthetic 16 kHz µ-law batch
 [B,16000] per GPU that is resident in HBM: forward (encoder MLP, recurrent cell over T'=250 steps, decoder MLP, DMoL
 head, KL) + backward (BPTT) + gradient all-reduce (N > 1) + clip-by-value + clip-by-norm + Adam — the loop body of
-the reference's experiments/experiment_vrnn_audio.py:213-232 in fp32.  Rank 0 prints ONE JSON line.
+the reference's experiments/experiment_vrnn_audio.py:213-232 in fp32.  The last timed step restarts from the seeded
+initial weights and a zeroed Adam state, so that what it computes depends on the arguments only (see measure()).  Rank 0
+prints ONE JSON line.
 """
 import argparse
 import json
 import math
 import os
+import re
 import sys
 import time
 
@@ -247,10 +254,15 @@ def model_macs(name, model, B, T, S=64, H=256, Z=256):
     return (S * H + 2 * H * H + 8 * H * H + 2 * H * H + H * 30 * S + 900 * S) * B * (Tp - 1), "LSTMAudio whole train step (matmul FLOPs of embedding + LSTM + decoder + DMoL Linear)"
 
 
-def measure(name, model, B, T, steps, warmup, rank, dev, use_dist, reducer_cls):
+def measure(name, model, B, T, steps, warmup, rank, dev, use_dist, reducer_cls, keep_outputs=False):
     """W untimed + K timed full train steps of `model` on a resident synthetic [B,T] batch.  Returns the wall time of the K
     steps between barrier + synchronize on both sides (MAX over ranks), every step's GPU duration from HIP events on the
-    launching stream, and the HIP-event time of the recurrent-cell calls (the dominant kernels)."""
+    launching stream, and the HIP-event time of the recurrent-cell calls (the dominant kernels).  The last timed step restarts
+    from the weights `model` holds on entry and a zeroed Adam state: the float atomics of the kernels make a step's results
+    differ from run to run in the last bits, and Adam's updates compound that over steps, so only a restarted step has the
+    same inputs in every run with the same arguments, and the same results up to rounding.  The steps before it train on as
+    a training loop does (the step time depends a little on the weights: at the initial ones the forward takes ~0.04 ms more).
+    `keep_outputs`: also the last step's loss, metrics and model outputs (res["last"])."""
     from blvm import _hip, ops
 
     params = list(model.parameters())
@@ -284,6 +296,14 @@ def measure(name, model, B, T, steps, warmup, rank, dev, use_dist, reducer_cls):
     free_nats = {"vrnn": 2.0, "srnn": 2.0, "cwvae": 4.0, "stcn": 4.0}.get(name)  # the experiment scripts' defaults
     bpd_name = {"cwvae": "elbo (bpt)", "stcn": "elbo (bpx)"}.get(name, "bpd")
     last = {}
+    init = [p.detach().clone() for p in params]
+    state = []  # Adam's moments and step counts, once the first step has made them
+
+    def restart():
+        with torch.no_grad():
+            torch._foreach_copy_(params, init)
+            if state:
+                torch._foreach_zero_(state)
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -297,7 +317,11 @@ def measure(name, model, B, T, steps, warmup, rank, dev, use_dist, reducer_cls):
         torch.nn.utils.clip_grad_value_(params, 1000.0)  # experiment_vrnn_audio.py:41-42 defaults
         torch.nn.utils.clip_grad_norm_(params, 3000.0)
         opt.step()
+        if not state:
+            state.extend(t for p in params for t in opt.state[p].values() if torch.is_tensor(t))
         last["metrics"] = metrics
+        if keep_outputs and cur["i"] == steps - 1:  # the last timed step only: earlier steps free their activations as before
+            last["loss"], last["out"] = loss, out
 
     bpd0 = None
     _hip.take_async_errors()  # start from a clean count
@@ -306,6 +330,7 @@ def measure(name, model, B, T, steps, warmup, rank, dev, use_dist, reducer_cls):
         if i == 0:
             torch.cuda.synchronize()
             bpd0 = {m.name: m.value for m in last["metrics"]}[bpd_name]  # forward of the random-init weights
+            restart()  # loads the restart's kernels before the timed region; warm-up trains on from the initial weights
             log(f"{name} [{B},{T}]: first step done")
     torch.cuda.synchronize()
     if use_dist:
@@ -315,6 +340,8 @@ def measure(name, model, B, T, steps, warmup, rank, dev, use_dist, reducer_cls):
     marks[0].record()
     for i in range(steps):
         cur["i"] = i
+        if i == steps - 1:
+            restart()
         step()
         marks[i + 1].record()
     cur["i"] = -1
@@ -346,7 +373,64 @@ def measure(name, model, B, T, steps, warmup, rank, dev, use_dist, reducer_cls):
         res["bwd_ms"] = sorted(c[1] for c in cell)[len(cell) // 2]
     else:  # no hooked recurrent-cell call: whole step against the model's matmul FLOPs
         res["fwd_ms"], res["bwd_ms"] = res["ms_median"] / 3, 2 * res["ms_median"] / 3
+    if keep_outputs:
+        res["last"] = last
     return res
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def step_outputs(model, last):
+    """What a caller of the timed train step receives, as float32 / float64 numpy arrays by name: the loss, the metrics, every
+    floating-point tensor field the model's forward returned (lazily computed fields are not forced), and every parameter after
+    the optimiser's update with the gradient that update used."""
+    import numpy as np
+
+    def arr(t):
+        t = t.detach()
+        return t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+
+    out = {"loss": arr(last["loss"])}
+    for m in last["metrics"]:
+        out["metric." + re.sub(r"\W+", "_", m.name).strip("_")] = np.float64(m.value)  # "kl (bpt)" -> metric.kl_bpt
+    for k, v in vars(last["out"]).items():
+        if isinstance(v, torch.Tensor) and v.is_floating_point():
+            out[f"out.{k}"] = arr(v)
+        elif isinstance(v, (list, tuple)):
+            for i, t in enumerate(v):
+                if isinstance(t, torch.Tensor) and t.is_floating_point():
+                    out[f"out.{k}.{i}"] = arr(t)
+    for k, p in model.named_parameters():
+        out[f"param.{k}"] = arr(p)
+        if p.grad is not None:
+            out[f"grad.{k}"] = arr(p.grad)
+    return out
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write `arrays` as directory/<name>.npy within `limit` bytes in all.  Arrays are taken smallest first and each gets at most
+    an equal share of what is left; one larger than its share is written as a fixed sample (seed 0, sorted flat indices) of as
+    many elements as the share holds, so two builds given the same arguments write the same elements.  Returns {name: (elements
+    written, elements in all)}."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    header = 128  # bytes of an .npy header for these shapes
+    left, n, written = limit - header * len(arrays), len(arrays), {}
+    for name in sorted(arrays, key=lambda k: (np.asarray(arrays[k]).nbytes, k)):
+        a = np.asarray(arrays[name])
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        size = a.size
+        keep = min(size, max(left, 0) // n // a.itemsize)
+        if keep < size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(size, keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written[name] = (keep, size)
+        left -= a.nbytes
+        n -= 1
+    return written
 
 
 def main():
@@ -359,10 +443,12 @@ def main():
     ap.add_argument("--model", default="vrnn", choices=["vrnn", "srnn", "lstm", "wavenet", "cwvae", "stcn"], help="vrnn = BASELINE headline (configs[1])")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"], help="operand type of the matrix products: f32 (headline) or bf16 operands / fp32 "
                     "accumulation for the persistent chains and K6 (the reference's --use_amp regime; a separate mode, never the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own: large-batch sweep and CPU baseline (N=1, vrnn only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=64, help="utterances of the CPU baseline step (default: the GPU's 64; 25 steps of it are ~40 s on 16 cores)")
     ap.add_argument("--cpu-steps", type=int, default=20)
-    ap.add_argument("--no-sweep", action="store_true", help="skip the large-batch sweep (N=1, vrnn only)")
+    ap.add_argument("--no-sweep", action="store_true", help="--full without the large-batch sweep")
     ap.add_argument("--dry-launch", action="store_true", help="CPU rehearsal of the N-rank launch: gloo, no GPU call, no model")
     args = ap.parse_args()
 
@@ -401,9 +487,14 @@ def main():
     Tp = math.ceil(T / S)
     model = build_model(args.model, dev)
     log(f"rank {rank}/{world}: model resident, {args.warmup} warm-up + {args.steps} timed steps")
-    m = measure(args.model, model, B, T, args.steps, args.warmup, rank, dev, use_dist, FlatGradAllReduce)
+    dump = args.dump_outputs is not None and rank == 0
+    m = measure(args.model, model, B, T, args.steps, args.warmup, rank, dev, use_dist, FlatGradAllReduce, keep_outputs=dump)
     log(f"timed {args.steps} steps: mean {m['ms_mean']:.2f} ms/step, median {m['ms_median']:.2f} (min {m['ms_min']:.2f}, max {m['ms_max']:.2f}); "
         f"host enqueue per step: seq_fwd {m['host_fwd_ms']:.2f} ms, seq_bwd {m['host_bwd_ms']:.2f} ms")
+    if dump:  # before the sweep below, which trains the same model further
+        written = dump_outputs(args.dump_outputs, step_outputs(model, m.pop("last")))
+        sampled = [k for k, (w, n) in written.items() if w < n]
+        log(f"dumped {len(written)} arrays of the last timed step to {args.dump_outputs}" + (f" (sampled: {', '.join(sampled)})" if sampled else ""))
     n_ranks = dist.get_world_size() if use_dist else 1
     frames = n_ranks * B * T * args.steps
     macs, kname = model_macs(args.model, model, B, T)
@@ -431,7 +522,7 @@ def main():
             "data": "synthetic",
             "async_errors": 0,  # persistent launches that aborted inside any timed region (filled in below; non-zero = exit 1, no line)
             "bits_per_dim": m["bpd_step0"],
-            "bits_per_dim_note": f"ELBO bits/dim of the first forward (random-init weights, seeded); after {args.warmup + args.steps} Adam updates on this one fixed batch: {m['bpd_last']:.4f}",
+            "bits_per_dim_note": f"ELBO bits/dim of the first forward (random-init weights, seeded); the last timed step restarts from these weights and a fresh Adam state, its forward: {m['bpd_last']:.4f}",
             "config": {
                 "workload": {
                     "cwvae": "experiment_clockwork_audio.py: CWVAEAudio DMoL h=192 z=[128,64,32] strides [64,16,16] 8 blocks/level precision posterior",
@@ -456,7 +547,7 @@ def main():
                 "bwd_ms": m["bwd_ms"],
             },
         }  # fmt: skip
-        if n_ranks == 1 and not use_dist and not args.no_sweep and args.model == "vrnn" and (B, T) == (64, 16000):
+        if args.full and n_ranks == 1 and not use_dist and not args.no_sweep and args.model == "vrnn" and (B, T) == (64, 16000):
             # the large-batch regime of the same kernels (the chain's cost per link does not depend on B until B ~ 256): same
             # model, same step, fewer timed steps.  Not the headline: `value` above stays the B = 64 configuration.
             sweep = [dict(batch_per_gpu=B, ms_per_step=m["ms_median"], frames_per_s=B * T / (m["ms_median"] * 1e-3), roofline_frac=achieved / peak)]
@@ -471,7 +562,7 @@ def main():
                                   async_errors=ms_["async_errors"]))  # fmt: skip
                 log(f"sweep B={Bs}: {ms_['ms_median']:.1f} ms/step, cell {tf:.1f} TF/s")
             res["sweep"] = sweep
-        if n_ranks == 1 and not args.no_cpu_baseline and args.model == "vrnn":
+        if args.full and n_ranks == 1 and not args.no_cpu_baseline and args.model == "vrnn":
             # the box's CPU share for one GPU is 16 cores (more threads than that only thrash the cgroup quota)
             threads = max(1, min(16, os.cpu_count() or 1, len(os.sched_getaffinity(0))))
             res["cpu_baseline"] = cpu_baseline(args.cpu_batch, T, args.cpu_steps, threads, gpu_batch=B)
