@@ -303,43 +303,14 @@ __device__ __forceinline__ void reduce_tiles(const f32x4 (&acc)[G], float* __res
 }
 
 }  // namespace blvm
-#include <functional>
-#include <string>
-namespace blvm {
-// ---- chain graphs (core.hip): an experiment switch, OFF by default (BLVM_GRAPHS=1 enables) ----------------------------------
-// A recurrent sequence is thousands of tiny dependent launches.  What a launch costs (tools/launch_host.hip, graph_chain.hip):
-// the GPU's dependent-dispatch floor is 1.53 us; the HOST pays 0.74 us for a launch without arguments but 2.6-3.1 us for one
-// with arguments (the runtime writes the argument block into device memory per launch; with HIP_FORCE_DEV_KERNARG=0 the host
-// pays 0.9 us and the GPU 3.65 us per kernel fetching arguments from host memory); a captured hipGraph replays a chain of
-// trivial kernels at 1.75 us each.  On the VRNN step a chain launch costs the host ~3 us and the GPU ~4 us per link (DESIGN.md,
-// "Host or GPU?"), so replaying pre-built graphs looked worth having: run_chain() captures a call and replays it, identified by the bytes
-// of ALL its arguments (every pointer, size and flag, the weight / gradient pointer tables included); the first time a key is
-// seen the body runs as plain launches, the second time it is captured (on the library's own stream: the caller's may be the
-// legacy null stream, which cannot capture), afterwards the graph is replayed between two events on the caller's stream.
-// Measured on the real chain (ROCm 7.2): hipGraphLaunch of the 2 260-node forward graph takes 10.9 ms — 4.8 us per node, more
-// than launching them — and the step goes from 21.5 to 26.4 ms.  So it stays off.  (Also tried and removed: argument-less twin
-// kernels that rebuild their arguments from a device table and a step counter — host enqueue falls to 0.6 us per launch, but
-// the table fetch after every kernel boundary and the 10x larger code object put a link at ~5 us on the GPU, 27.3 ms/step.)
-// What is left is fewer launches: several links per launch behind an in-kernel barrier.
-// The body must only enqueue work on the stream it is given and decide nothing from device data.
-struct ChainKey {
-  std::string bytes;
-  explicit ChainKey(const char* tag) : bytes(tag) {}
-  template <class T>
-  ChainKey& add(const T& v) {
-    bytes.append(reinterpret_cast<const char*>(&v), sizeof(T));
-    return *this;
-  }
-};
-int run_chain(const ChainKey& key, hipStream_t user, const std::function<int(hipStream_t)>& body);
 
+namespace blvm {
 // persistent chains (pchain.h): the process-wide control block and a fresh launch epoch (core.hip)
 int pchain_ctl(unsigned** dev, unsigned** host_dev, unsigned* epoch);
 // largest batch the recurrent sequences run as ONE persistent launch for (0 = never; env BLVM_PCHAIN=0 / BLVM_PCHAIN_MAX_B=n, or
 // blvm_pchain_configure).  Beyond it the links are bound by MFMA / operand bytes, not latency, and the 32x32-tile launch-per-link
-// kernels fit better.  pchain_waves(): waves per workgroup of the persistent kernels (8 or 16; env BLVM_PCHAIN_NW).
+// kernels fit better.
 int pchain_max_batch();
-int pchain_waves();
 int pchain_tune();  // placement bits (env BLVM_PCHAIN_TUNE / blvm_pchain_tune): 4 XCD-aware tile placement, 16 canary polls of deferred tiles
 unsigned long long* pchain_profile_buffer();  // diagnostics: null unless blvm_pchain_profile() installed a device buffer
 

@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256) void dmol_kernel(DmolArgs a) {
 //     one wave's MFMAs run under another's exp / log stream.
 constexpr int UNIT_FLOATS = 64 * F_MAX;  // 1920
 // (a compiler-only fence: a release / acquire fence pair, even at wavefront scope, made hipcc wait for ALL outstanding vector
-// memory — the next unit's prefetch included — in front of every image phase)
+// memory in front of every image phase)
 __device__ __forceinline__ void wave_sync() { asm volatile("" ::: "memory"); }
 // a unit in flight from HBM: eight plain vector registers (f32x4 k holds float4 lane + 64 k; k = 7: lanes 0..31).  Separate
 // scalars of an ext-vector type on purpose: an array of HIP's float4 (a struct of unions) passed by reference stayed in scratch.
@@ -447,7 +447,7 @@ __device__ __forceinline__ void mfma_image_30x30(float* __restrict__ lds, const 
   }
 }
 
-template <bool BWD, bool PF>  // PF: the next unit is requested into registers (32 of them) before this one is worked on
+template <bool BWD>
 __global__ __launch_bounds__(256) void dmol_rows_kernel(DmolArgs a, int units, int nchunks) {
   __shared__ __attribute__((aligned(16))) float lds_all[4 * UNIT_FLOATS];
   __shared__ double wsum[4];
@@ -467,7 +467,6 @@ __global__ __launch_bounds__(256) void dmol_rows_kernel(DmolArgs a, int units, i
   };
   UNIT_REGS(nxt);
   int u = u_begin + wave;
-  if (PF && u < u_end) LOAD_UNIT(nxt, a.dec + unit_base(u), lane);  // the first unit travels with the weights
   // the head's Linear for the matrix pipe: forward B operand W^T[k][n] = W[n][k]; backward (d_dec = d_par W) B operand W[k][n]
   float bias_n = 0.f;
   {
@@ -490,9 +489,8 @@ __global__ __launch_bounds__(256) void dmol_rows_kernel(DmolArgs a, int units, i
     const bool valid = tau < len;
     const float yv = valid ? a.y[(size_t)b * a.T + tau] : 0.f;
     wave_sync();  // the previous unit's last image reads (its stores to HBM) are issued
-    if (!PF) LOAD_UNIT(nxt, a.dec + base, lane);
+    LOAD_UNIT(nxt, a.dec + base, lane);
     PUT_UNIT(nxt, lds, lane);
-    if (PF && u + 4 < u_end) LOAD_UNIT(nxt, a.dec + unit_base(u + 4), lane);  // the next unit travels while this one is worked on
     wave_sync();
     if (lin) {
       mfma_image_30x30(lds, wtab, bias_n, lane);  // p = W d + bias, in place
@@ -546,27 +544,24 @@ int launch_dmol(DmolArgs& a, hipStream_t s) {
     BLVM_REQUIRE(units < (1ll << 31), "dmol: too many frames");
     // Few, long-lived workgroups: a wave's prologue (x_sl, 30 weight registers, its first unit: two dependent HBM round trips) is
     // ~4 us, a unit ~1.5 us of its time — at 2 units per wave (2048 workgroups) the waves spent 40 % of their lives parked.  About
-    // three workgroups per CU (what the registers allow), every wave walking its chunk with the next unit in flight.
+    // three workgroups per CU (what the registers allow), every wave walking its chunk.
+    // (Requesting the next unit into 32 registers ahead of time costs a wave of occupancy in both kernels and measured no faster
+    // than one more resident wave per SIMD covering the load — same box: forward 44.8 vs 42.3 us, backward 95.6 vs 92.7.)
     int nchunks = (int)((units + 3) / 4);
-    // PF (the next unit requested into 32 registers ahead of time) costs a wave of occupancy in both kernels and measured no faster
-    // than one more resident wave per SIMD covering the load (same box: forward 44.8 vs 42.3 us, backward 95.6 vs 92.7): off
-    static const int pf = [] { const char* e = getenv("BLVM_DMOL_PF"); return e ? atoi(e) : 0; }();
     static const int wg_env = [] { const char* e = getenv("BLVM_DMOL_WGS"); return e ? atoi(e) : 0; }();
-    static int wg_fill[2] = {0, 0};  // workgroups that fill the chip once: resident workgroups per CU (by registers) x CUs
-    if (wg_fill[pf ? 1 : 0] == 0) {
+    static int wg_fill = 0;  // workgroups that fill the chip once: resident workgroups per CU (by registers) x CUs
+    if (wg_fill == 0) {
       int per_cu = 0, dev = 0, cus = 0;
-      const void* k = pf ? reinterpret_cast<const void*>(&dmol_rows_kernel<BWD, true>) : reinterpret_cast<const void*>(&dmol_rows_kernel<BWD, false>);
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&dmol_rows_kernel<BWD>), 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
       (void)hipGetLastError();
-      wg_fill[pf ? 1 : 0] = per_cu * cus;
+      wg_fill = per_cu * cus;
     }
-    const int wg_target = wg_env > 0 ? wg_env : wg_fill[pf ? 1 : 0];
+    const int wg_target = wg_env > 0 ? wg_env : wg_fill;
     const int cap = (wg_target + a.B - 1) / a.B;
     if (nchunks > cap) nchunks = cap;
     if (nchunks < 1) nchunks = 1;
-    if (pf) hipLaunchKernelGGL((dmol_rows_kernel<BWD, true>), dim3((unsigned)(a.B * nchunks)), dim3(256), 0, s, a, (int)units, nchunks);
-    else hipLaunchKernelGGL((dmol_rows_kernel<BWD, false>), dim3((unsigned)(a.B * nchunks)), dim3(256), 0, s, a, (int)units, nchunks);
+    hipLaunchKernelGGL((dmol_rows_kernel<BWD>), dim3((unsigned)(a.B * nchunks)), dim3(256), 0, s, a, (int)units, nchunks);
   } else {
     const long long blocks = (a.n_frames + FPB - 1) / FPB;
     BLVM_REQUIRE(blocks < (1ll << 31), "dmol: too many frames");

@@ -20,26 +20,12 @@ namespace blvm {
 
 namespace {
 
-// LDS operand reads of the NEXT k-pair issued in front of the current pair's MFMAs (2 = pinned with sched_group_barrier: without the
-// pins the compiler sinks the reads back next to their use; 0 = the plain loop).  Measured r03: VRNN 15.23 -> 15.18, STCN 32.93 -> 32.51,
-// CW-VAE 86.3 -> 85.9 ms/step; the weight-gradient forms +3..4 %, the K = 256 forward forms -1 %.
-#ifndef BLVM_GEMM_PIPE
-#define BLVM_GEMM_PIPE 2
-#endif
-#ifndef BLVM_GEMM_BK64
-#define BLVM_GEMM_BK64 32
-#endif
-#ifndef BLVM_GEMM_BK
-#define BLVM_GEMM_BK 16
-#endif
-constexpr int BK = BLVM_GEMM_BK;  // k-tile depth of the 128-wide tiles (and the unit of the host's split arithmetic)
-constexpr int tile_bk(int bm, int bn) { return (bm == 64 && bn == 64) ? BLVM_GEMM_BK64 : BK; }
+constexpr int BK = 16;    // k-tile depth of the 128-wide tiles (and the unit of the host's split arithmetic)
+constexpr int BK64 = 32;  // k-tile depth of the 64 x 64 tiles (64 deep measured: slower)
+constexpr int tile_bk(int bm, int bn) { return (bm == 64 && bn == 64) ? BK64 : BK; }
 
 constexpr int PAD = 4;
-#ifndef BLVM_GEMM_PAD_T
-#define BLVM_GEMM_PAD_T 2
-#endif
-constexpr int PAD_T = BLVM_GEMM_PAD_T;
+constexpr int PAD_T = 2;
 
 struct GemmArgs {
   const float* A;
@@ -81,7 +67,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
   // by scalar stores whose lanes are 4 k apart (4 rows): with a pad of 2, 4 rows are 8 banks apart and the 32 lanes of a store hit
   // 32 banks (pad 4: 16 banks twice -- SQ_LDS_BANK_CONFLICT was 70 % of the kernel's LDS cycles)
   // (32-deep tiles: 8 lanes per row, a pad of 1 puts 4 rows 4 banks apart)
-  constexpr int PT = BLVM_GEMM_PAD_T >= 0 ? (BK == 32 ? (PAD_T + 1) / 2 : PAD_T) : PAD;
+  constexpr int PT = BK == 32 ? (PAD_T + 1) / 2 : PAD_T;
   constexpr int LDA_S = BM + (OPA == 0 ? PT : PAD), LDB_S = BN + (OPB == 0 ? PT : PAD);
   constexpr int TM = BM / 64, TN = BN / 64;  // 32x32 MFMA tiles per wave in m / n
   constexpr int A_V = BM * BK / 4 / 256;     // float4 per thread per stage
@@ -185,9 +171,11 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
 #pragma unroll
       for (int kk = 0; kk < BK / CS; ++kk) csum += As[(kk * CS + tid / BM) * LDA_S + tid % BM];
     }
-#if BLVM_GEMM_PIPE
     // the operands of k-pair s + 1 are requested from LDS BEFORE the MFMAs of k-pair s are issued (two register sets): the LDS
-    // round trip hides behind TM x TN matrix instructions instead of standing in front of them
+    // round trip hides behind TM x TN matrix instructions instead of standing in front of them.  The order is pinned with
+    // sched_group_barrier: without the pins the compiler sinks the reads back next to their use.  Measured r03 against the plain
+    // loop: VRNN 15.23 -> 15.18, STCN 32.93 -> 32.51, CW-VAE 86.3 -> 85.9 ms/step; the weight-gradient forms +3..4 %, the K = 256
+    // forward forms -1 %.
     float a[2][TM], b[2][TN];
     auto lds_ab = [&](int kk, float (&a_)[TM], float (&b_)[TN]) {
 #pragma unroll
@@ -204,26 +192,9 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
 #pragma unroll
         for (int j = 0; j < TN; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[st & 1][i], b[st & 1][j], acc[i][j], 0, 0, 0);
-#if BLVM_GEMM_PIPE >= 2
       __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);   // the DS reads of the next pair first ...
       __builtin_amdgcn_sched_group_barrier(0x008, TM * TN, 0);   // ... then this pair's MFMAs
-#endif
     }
-#else
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 2) {
-      float a[TM], b[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) a[i] = As[(kk + lh) * LDA_S + wm * (BM / 2) + i * 32 + li];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) b[j] = Bs[(kk + lh) * LDB_S + wn * (BN / 2) + j * 32 + li];
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-#endif
   }
 
   if (do_csum && tid / BM < CS && m0 + tid % BM < g.M) atomicAdd(g.colsum + m0 + tid % BM, csum);

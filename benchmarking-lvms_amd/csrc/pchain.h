@@ -159,12 +159,7 @@ __device__ __forceinline__ void mgemm_trip(const rsrc_t (&ar)[GA], unsigned aoff
 #pragma unroll
   for (int u = 0; u < CH; ++u)
 #pragma unroll
-#ifdef PCHAIN_W_HOT  // timing experiment (garbage results): every weight fragment from the tile's first, cache-resident block —
-                     // an upper bound on what weights kept next to the matrix pipe (LDS / registers) could save
-    for (int g = 0; g < G; ++g) w[g][u] = *reinterpret_cast<const wfrag*>(wp[g] + (size_t)ES * 16 * (size_t)(u & 1));
-#else
     for (int g = 0; g < G; ++g) w[g][u] = *reinterpret_cast<const wfrag*>(wp[g] + (size_t)ES * 16 * (size_t)(kc + u * STEP));
-#endif
   if (!polled) {
 #pragma unroll
     for (int u = 0; u < CH; ++u)
@@ -189,9 +184,6 @@ __device__ __forceinline__ void mgemm_trip(const rsrc_t (&ar)[GA], unsigned aoff
       pl.polls++;
 #endif
       if (!__any(bad && aok) || pl.dead) break;
-#ifdef PCHAIN_NOWAIT  // timing experiment: never wait (results are garbage): what the tiles cost without the hand-offs
-      break;
-#endif
       if (spin_tick(spins, pl.ctl, pl.code, pl.dead)) break;
       pl.sleep();
     }
@@ -272,9 +264,6 @@ __device__ __forceinline__ void poll_words(const rsrc_t (&r)[N], const unsigned 
 #pragma unroll
     for (int i = 0; i < N; ++i) bad |= is_sentinel(v[i]);
     if (!__any(bad && need) || pl.dead) break;
-#ifdef PCHAIN_NOWAIT
-    break;
-#endif
     if (spin_tick(spins, pl.ctl, pl.code, pl.dead)) break;
     pl.sleep();
   }
@@ -327,9 +316,6 @@ __device__ __forceinline__ void canary_wait(const float* A16, int r0, int K, Pol
         bad |= (pr < np) && is_sentinel(v);
       }
       if (!__any(bad) || pl.dead) break;
-#ifdef PCHAIN_NOWAIT
-      break;
-#endif
       if (spin_tick(spins, pl.ctl, pl.code, pl.dead)) break;
       pl.sleep();
     }
@@ -927,9 +913,6 @@ __device__ __forceinline__ void tile_dmol_sample(const float* dec, int ldd, cons
         *reinterpret_cast<f32x4*>(in + rr * rowlen + 4 * cq) = x;
       }
       if (!__any(bad) || pl.dead) break;
-#ifdef PCHAIN_NOWAIT
-      break;
-#endif
       if (spin_tick(spins, pl.ctl, pl.code, pl.dead)) break;
       pl.sleep();
     }
@@ -1081,17 +1064,6 @@ inline Desc& add_linseq(Builder& b, int ct, int wg0, int nwg, int K, bool relu, 
   d.n16[0] = n16; d.i[1] = n; d.i[2] = ldgate; d.f[0] = slope;
   return d;
 }
-// env BLVM_PCHAIN_LINSEQ=0: one descriptor per link (A/B switch)
-// env BLVM_PCHAIN_MERGE=0: the link in front of a run keeps its own descriptor (A/B switch)
-inline bool merge_first_enabled() {
-  static const int v = [] { const char* e = getenv("BLVM_PCHAIN_MERGE"); return e ? atoi(e) : 1; }();
-  return v != 0;
-}
-inline bool linseq_enabled() {
-  static const int v = [] { const char* e = getenv("BLVM_PCHAIN_LINSEQ"); return e ? atoi(e) : 1; }();
-  return v != 0;
-}
-
 // workgroups for `tiles` tiles out of `avail` (a multiple of 8, at least 8): XCD-aware placement deals ranges in eights
 inline int range_for(int tiles, int avail) { return std::max(8, std::min(avail & ~7, (tiles + 7) & ~7)); }
 

@@ -276,7 +276,6 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             }
             if (nt == 0) nx.fetch(ltab, nx_i, nx_s);  // (a visit without tiles)
           } break;
-#ifndef PCHAIN_ONLY_LIN
           case K_HEAD: {
             const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld2 = d.w<RD_LD + 2>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
             (void)ld0; (void)ld1; (void)ld2; (void)ld3; (void)n16;
@@ -402,7 +401,6 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
                                    red0, pl);
             }
           } break;
-#endif
           default: break;
         }
         if (profiled) {
@@ -649,39 +647,35 @@ int pchain_launch(const pchain::Program& prog, hipStream_t stream) {
   }
   BLVM_REQUIRE(prog.s_first >= 0 && prog.s_first < prog.S, "pchain: empty step range [%d, %d)", prog.s_first, prog.S);
   Hdr h{prog.ndesc, prog.s_first, prog.S, prog.B, prog.xcd, prog.prof_wg, prog.lds_products, prog.ctl, prog.prof};
-  const int nw = prog.rt_group > 1 ? 8 : pchain_waves();  // (the row-group kernel is built for 8 waves: 512 threads finish row-tile pairs)
+  const int nw = prog.rt_group > 1 ? 8 : 16;  // (the row-group kernel is built for 8 waves: 512 threads finish row-tile pairs)
   const size_t lds_fixed = sizeof(int) * kDescWords * pchain::kMaxDesc + 32 * sizeof(unsigned long long);
   const size_t lds = lds_fixed + sizeof(float) * 2 * (size_t)prog.lds_products * nw * 256;
   // the dynamic-LDS limit of the kernels is raised once per process and device (the call is far from free), and the launch's
   // residency — every workgroup of the grid must be on a CU at the same time — is checked against the occupancy the runtime
-  // computes for this kernel, block size and LDS size (cached per size)
+  // computes for this kernel, block size and LDS size (cached per kernel and number of products: a train step alternates sizes)
+  constexpr int kMaxProducts = 8;
   static std::mutex attr_mu;
-  static int attr_dev[6] = {-1, -1, -1, -1, -1, -1};
-  static size_t occ_lds[6] = {0, 0, 0, 0, 0, 0};
-  static int occ_blocks[6] = {0, 0, 0, 0, 0, 0};
+  static int attr_dev[3] = {-1, -1, -1};
+  static int occ_blocks[3][kMaxProducts + 1];  // workgroups per CU; 0: not asked yet
   const size_t lds_max = lds_fixed + sizeof(float) * 2 * (prog.rt_group > 1 ? 8 : 4) * (size_t)nw * 256;  // (row groups reduce two row tiles per barrier)
-  BLVM_REQUIRE(lds <= lds_max, "pchain: %d products per tile exceed the reduction scratch", prog.lds_products);
+  BLVM_REQUIRE(prog.lds_products >= 1 && lds <= lds_max, "pchain: %d products per tile do not fit the reduction scratch", prog.lds_products);
   auto go = [&](auto kernel, int slot, int threads) -> int {
     {
       std::lock_guard<std::mutex> lock(attr_mu);
+      int* const occ = occ_blocks[slot];
       if (attr_dev[slot] != dev) {
         BLVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
         attr_dev[slot] = dev;
-        occ_lds[slot] = 0;
+        std::fill(occ, occ + kMaxProducts + 1, 0);
       }
-      if (occ_lds[slot] != lds) {
-        int per_cu = 0;
-        BLVM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds));
-        occ_blocks[slot] = per_cu;
-        occ_lds[slot] = lds;
-      }
-      BLVM_REQUIRE((long)occ_blocks[slot] * cus >= grid,
-                   "pchain: %d workgroups of %d threads + %zu B LDS are not co-resident (%d per CU x %d CUs)", grid, threads, lds, occ_blocks[slot], cus);
+      if (occ[prog.lds_products] == 0) BLVM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[prog.lds_products], kernel, threads, lds));
+      BLVM_REQUIRE((long)occ[prog.lds_products] * cus >= grid,
+                   "pchain: %d workgroups of %d threads + %zu B LDS are not co-resident (%d per CU x %d CUs)", grid, threads, lds, occ[prog.lds_products], cus);
     }
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, stream, (const int*)tab, h);
     return BLVM_OK;
   };
-  BLVM_REQUIRE(prog.rt_group == 1 || prog.rt_group == 2 || prog.rt_group == 4, "pchain: row groups of %d row tiles are not built", prog.rt_group);
+  BLVM_REQUIRE(prog.rt_group == 1 || prog.rt_group == 2, "pchain: row groups of %d row tiles are not built", prog.rt_group);
   if (prog.rt_group > 1) {
     for (int i = 0; i < prog.ndesc; ++i) {
       const int k = prog.d[i].kind;
@@ -690,14 +684,12 @@ int pchain_launch(const pchain::Program& prog, hipStream_t stream) {
       BLVM_REQUIRE(k != pchain::K_DZ || prog.d[i].p[2] == nullptr, "pchain: the row-group dz tile is the single-product form");
     }
     BLVM_REQUIRE(!prog.bf16, "pchain: row groups multiply fp32 operands only");
-    const int rcg = prog.rt_group == 4 ? go(&pchain_rt_kernel<8, false, 4>, 4, 512) : go(&pchain_rt_kernel<8, false, 2>, 5, 512);
+    const int rcg = go(&pchain_rt_kernel<8, false, 2>, 2, 512);
     if (rcg) return rcg;
     BLVM_CHECK_LAUNCH("pchain_launch (row groups)");
     return BLVM_OK;
   }
-  int rc;
-  if (nw == 16) rc = prog.bf16 ? go(&pchain_kernel<16, true>, 3, 1024) : go(&pchain_kernel<16, false>, 1, 1024);
-  else rc = prog.bf16 ? go(&pchain_kernel<8, true>, 2, 512) : go(&pchain_kernel<8, false>, 0, 512);
+  const int rc = prog.bf16 ? go(&pchain_kernel<16, true>, 1, 1024) : go(&pchain_kernel<16, false>, 0, 1024);
   if (rc) return rc;
   BLVM_CHECK_LAUNCH("pchain_launch");
   return BLVM_OK;

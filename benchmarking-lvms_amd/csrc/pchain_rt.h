@@ -14,10 +14,7 @@
 namespace blvm {
 namespace pchain {
 
-#ifndef BLVM_RT_FRAGS
-#define BLVM_RT_FRAGS 16
-#endif
-constexpr int kRtFrags = BLVM_RT_FRAGS;
+constexpr int kRtFrags = 16;
 
 // acc[rt][g] += A[AMap(g)][r0 + 16 rt + i][k] W[g][c0[g] + j][k] for the row tiles rt < RT of a group (mgemm_trip of pchain.h with
 // the activation side repeated per row tile).  rt_off[rt]: byte offset of row tile rt's T16 slab from the group's first (clamped to

@@ -516,7 +516,6 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
   }
   const int nw = pick_nw(kmax, 1);
   const dim3 grid(tiles, (l.B + 15) / 16);
-#ifndef BLVM_NO_LIN1
   if (NSEG == 1 && l.B < 65536 && a.K[0] < 65536 && a.lda[0] < 65536 && a.ldw[0] < 65536 && a.ldadd[0] < 65536 &&
       a.ldgate[0] < 65536 && a.ldo[0] < 65536) {
     const unsigned p0 = (unsigned)a.lda[0] | ((unsigned)a.ldw[0] << 16), p1 = (unsigned)a.K[0] | ((unsigned)l.B << 16);
@@ -526,8 +525,6 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
     else hipLaunchKernelGGL((lin1_stage_kernel<4>), grid, dim3(256), 0, s, a.A[0], a.W[0], a.bias[0], a.add[0], a.gate[0], p0, p1, p2, p3, a.out[0], a.slope);
     return;
   }
-#endif
-#ifndef BLVM_NO_LIN2S
   if (NSEG == 2) {
     const int f = a.flags[0];
     const bool one_operand = (f & LF_ADD) == 0 && ((f & LF_BIAS) == 0 || (f & LF_GATE) == 0);
@@ -547,8 +544,6 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
       return;
     }
   }
-#endif
-#ifndef BLVM_NO_LINP
   if (NSEG == 2) {
     bool fits = l.B < 65536;
     for (int i = 0; i < 2; ++i) fits = fits && a.lda[i % NSEG] < 65536 && a.ldw[i % NSEG] < 65536 && a.K[i % NSEG] < 65536;
@@ -576,7 +571,6 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
       return;
     }
   }
-#endif
   if (nw == 16) hipLaunchKernelGGL((lin_stage_kernel<16, NSEG>), grid, dim3(1024), 0, s, a);
   else if (nw == 8) hipLaunchKernelGGL((lin_stage_kernel<8, NSEG>), grid, dim3(512), 0, s, a);
   else hipLaunchKernelGGL((lin_stage_kernel<4, NSEG>), grid, dim3(256), 0, s, a);

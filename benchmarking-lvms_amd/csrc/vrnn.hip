@@ -137,11 +137,11 @@ __global__ __launch_bounds__(NW * 64) void dh_stage_kernel(const float* DP0, con
 
 // Batches of 65 .. 256 utterances run the VRNN programs on ROW GROUPS of two row tiles (pchain_rt.h: 32-row tiles, the weight
 // fragments fetched once per group).  Measured per train step on one box, [B,16000] fp32: B = 128 22.6 ms (24.7 on 16-row tiles,
-// two per workgroup and link), B = 192 28.7 (36.9 as a launch per link), B = 256 38.6 (40.1).  Groups of FOUR row tiles are slower
-// everywhere (B = 128: 34.8, 256: 40.7): a tile costs ~1.3 us + ~1.1 us per row tile it carries (polled fragments, MFMAs, reduction,
+// two per workgroup and link), B = 192 28.7 (36.9 as a launch per link), B = 256 38.6 (40.1).  Groups of FOUR row tiles were slower
+// everywhere (B = 128: 34.8, 256: 40.7; removed): a tile costs ~1.3 us + ~1.1 us per row tile it carries (polled fragments, MFMAs, reduction,
 // epilogue stores), so fatter tiles only trade workgroups for latency; beyond 256 utterances a link has more 32-row tiles than the
 // chip has workgroups for it and the launch-per-link path on 32 x 32 tiles takes over.  fp32 operands only.
-// env BLVM_PCHAIN_RT_MIN_B / BLVM_PCHAIN_RT_MAX_B: the batch range (default 65 .. 256; MAX_B = 0: never); BLVM_PCHAIN_RT = 2 | 4.
+// env BLVM_PCHAIN_RT_MIN_B / BLVM_PCHAIN_RT_MAX_B: the batch range (default 65 .. 256; MAX_B = 0: never).
 inline int vrnn_rt_max_b() {
   static int v = [] {
     const char* e = getenv("BLVM_PCHAIN_RT_MAX_B");
@@ -151,10 +151,9 @@ inline int vrnn_rt_max_b() {
 }
 inline int vrnn_rt(int B) {
   static const int min_b = [] { const char* e = getenv("BLVM_PCHAIN_RT_MIN_B"); return e ? atoi(e) : 65; }();
-  static const int forced = [] { const char* e = getenv("BLVM_PCHAIN_RT"); return e ? atoi(e) : 0; }();
   if (B < min_b || B > vrnn_rt_max_b() || pchain_max_batch() <= 0 || operand_bf16()) return 0;
   if (B <= kPchainCarveMaxB && B > pchain_max_batch()) return 0;
-  return forced == 4 ? 4 : 2;
+  return 2;
 }
 inline bool vrnn_row_groups(int B) { return vrnn_rt(B) > 0; }
 // SHARED deal of the row-group programs: the gentle link (hidden projection; backward: the hidden-gradient product) owns no range of
@@ -261,37 +260,6 @@ size_t carve_ws(float* base, int Tp, int B, int X, int H, int Z, int R, BwdWs* w
   return off;
 }
 
-// A second stream for work that is independent of the recurrent chain (lazily created, one per process).
-struct SideStream {
-  hipStream_t stream = nullptr;
-  hipEvent_t ready = nullptr, done = nullptr;
-  int ensure() {
-    if (stream) return BLVM_OK;
-    int least = 0, greatest = 0;  // lowest priority: the batched GEMMs must not take dispatch slots from the chain's links
-    BLVM_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    BLVM_HIP(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, least));
-    BLVM_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-    BLVM_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-    return BLVM_OK;
-  }
-};
-inline SideStream& side_stream() {
-  static thread_local SideStream s;
-  return s;
-}
-// Steps per side-stream range; 0 (default) keeps the batched GEMMs behind the chain on the caller's stream.
-// Measured on MI355X at [64,16000]: 24.3 ms/step without overlap, 26.1 / 25.3 / 27.2 ms with ranges of 50 / 25 / 125
-// steps — the big GEMM workgroups take CU slots and memory-pipeline share from the latency-bound chain links, which
-// costs more than the 2.5 ms of GEMMs it hides.  Kept as an experiment switch (env BLVM_WGRAD_OVERLAP_STEPS).
-inline int overlap_chunk_steps() {
-  static int v = [] {
-    const char* e = getenv("BLVM_WGRAD_OVERLAP_STEPS");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-
-
 // a += b + c over n4 float4 (the three partial sums of DPHI[3])
 __global__ __launch_bounds__(256) void add3_kernel(float4* __restrict__ a, const float4* __restrict__ b, const float4* __restrict__ c, size_t n4) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
@@ -300,34 +268,6 @@ __global__ __launch_bounds__(256) void add3_kernel(float4* __restrict__ a, const
     x.x += y.x + z.x; x.y += y.y + z.y; x.z += y.z + z.z; x.w += y.w + z.w;
     a[i] = x;
   }
-}
-
-// parts the persistent backward sequence is cut into so that finished rows' batched GEMMs overlap the rest (1 = no overlap)
-inline int pchain_wgrad_parts() {
-  static int v = [] {
-    const char* e = getenv("BLVM_PCHAIN_WGRAD_PARTS");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-// consecutive links of one shape as ONE descriptor walked inside a visit (K_LINSEQ; env BLVM_PCHAIN_LINSEQ=0: one descriptor per link)
-inline bool pchain_linseq() {
-  static int v = [] {
-    const char* e = getenv("BLVM_PCHAIN_LINSEQ");
-    return e ? atoi(e) : 1;
-  }();
-  return v != 0;
-}
-
-// the link in front of a run of same-shape links joins the run's descriptor visit (K_LINSEQ with its own K for the first link): the
-// first prior / posterior layer (K = R, the posterior's with its x-part addend) in the forward program, the heads' gradient link
-// (K = 2Z) in the backward program -- one visit less per chain and step (~1 us each, tools/probe_engine_chain.py).
-// env BLVM_PCHAIN_MERGE = 0 | 1.
-inline bool vrnn_merge_first(bool groups) {
-  static const int v = [] { const char* e = getenv("BLVM_PCHAIN_MERGE"); return e ? atoi(e) : 1; }();
-  (void)groups;  // (the row-group kernel takes the same descriptors)
-  return v != 0 && pchain_linseq();
 }
 
 // the K = 3R link of the persistent backward as three K = R links (env BLVM_PCHAIN_SPLIT3=0: one link)
@@ -416,11 +356,11 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     const bool groups = vrnn_row_groups(B);
     const int RTG = groups ? vrnn_rt(B) : 1;
     const int tl = (rt + RTG - 1) / RTG;
-    // hidden projection: up to a quarter of the chip (groups of four row tiles: up to half)
+    // hidden projection: up to a quarter of the chip
     // shared deal (row groups, many row tiles): no range of its own for the hidden projection -- it runs on the posterior half after that
     // half's run, in the window where only the prior half works on the heads and the phi_z run
     const bool shared = vrnn_shared_deal(groups, tl);
-    const int def_n = shared ? 0 : range_for(3 * ctR * tl, std::min(RTG >= 4 ? cus / 2 : cus / 4, RTG >= 4 ? 128 : 64));
+    const int def_n = shared ? 0 : range_for(3 * ctR * tl, std::min(cus / 4, 64));
     const int half = range_for(ctH * tl, (cus - def_n) / 2);            // prior | posterior halves of a link
     const int g = 2 * half;
     Builder bld;
@@ -435,12 +375,7 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       bld.ptr(d, 5, orm, rm_step); bld.ptr(d, 6, o16, o16_step);
       d.ld[1] = ldadd; d.ld[3] = ldo; d.n16[0] = n16; d.f[0] = 0.f;
     };
-    // F1: first prior layer | h-half of the first posterior layer | hidden projection
-    const bool merge1 = vrnn_merge_first(groups);  // (then the first prior / posterior layer opens the run below)
-    if (!merge1) {
-      lin(rs.H16, xR, rs.Wp[0], R, w->prior_b[0], nullptr, 0, 0, rs.P[0], sH, H, rs.P16[0], xH, ctH, ctH, 0, half, DF_RELU);
-      lin(rs.H16, xR, rs.Wq[0], R, nullptr, rs.XQ, sH, H, rs.Q[0], sH, H, rs.Q16[0], xH, ctH, ctH, half, half, DF_RELU);
-    }
+    // F1: hidden projection (the first prior layer and the h-half of the first posterior layer open the runs below)
     auto hproj = [&](int wg0, int nwg) {
       lin(rs.H16, xR, rs.Whh, R, w->gru_bhh, nullptr, 0, 0, rs.GHb, s3R, 3 * R, nullptr, 0, 0, 3 * ctR, wg0, nwg,
           DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0));
@@ -459,23 +394,13 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       }
       d.n16[0] = ctH; d.i[1] = n; d.f[0] = 0.f;
     };
-    const bool seq = pchain_linseq();
-    // F2, F3
-    if (seq && merge1) {  // F1 .. F3 of a chain: one visit
+    // F1 .. F3 of a chain: one visit.  The link in front of a run of same-shape links joins the run's descriptor visit (its own K = R,
+    // the posterior's with its x-part addend): one visit less per chain and step (~1 us each, tools/probe_engine_chain.py)
+    {
       const SeqLink lp[3] = {{rs.Wp[0], w->prior_b[0], rs.P[0], sH, H, rs.P16[0]}, {rs.Wp[1], w->prior_b[1], rs.P[1], sH, H, rs.P16[1]}, {rs.Wp[2], w->prior_b[2], rs.P[2], sH, H, rs.P16[2]}};
       const SeqLink lq[3] = {{rs.Wq[0], nullptr, rs.Q[0], sH, H, rs.Q16[0]}, {rs.Wq[1], w->post_b[1], rs.Q[1], sH, H, rs.Q16[1]}, {rs.Wq[2], w->post_b[2], rs.Q[2], sH, H, rs.Q16[2]}};
       linseq(rs.H16, xR, H, 3, lp, 0, half, R);
       linseq(rs.H16, xR, H, 3, lq, half, half, R, rs.XQ, sH, H);
-    } else if (seq) {
-      const SeqLink lp[2] = {{rs.Wp[1], w->prior_b[1], rs.P[1], sH, H, rs.P16[1]}, {rs.Wp[2], w->prior_b[2], rs.P[2], sH, H, rs.P16[2]}};
-      const SeqLink lq[2] = {{rs.Wq[1], w->post_b[1], rs.Q[1], sH, H, rs.Q16[1]}, {rs.Wq[2], w->post_b[2], rs.Q[2], sH, H, rs.Q16[2]}};
-      linseq(rs.P16[0], xH, H, 2, lp, 0, half);
-      linseq(rs.Q16[0], xH, H, 2, lq, half, half);
-    } else {
-      for (int l = 1; l < 3; ++l) {
-        lin(rs.P16[l - 1], xH, rs.Wp[l], H, w->prior_b[l], nullptr, 0, 0, rs.P[l], sH, H, rs.P16[l], xH, ctH, ctH, 0, half, DF_RELU);
-        lin(rs.Q16[l - 1], xH, rs.Wq[l], H, w->post_b[l], nullptr, 0, 0, rs.Q[l], sH, H, rs.Q16[l], xH, ctH, ctH, half, half, DF_RELU);
-      }
     }
     if (shared) hproj(half, half);
     {  // F4: heads + sample
@@ -487,7 +412,7 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       d.ld[3] = Z; d.n16[0] = ctZ; d.i[0] = Z; d.i[1] = residual_posterior; d.f[0] = beta; d.f[1] = 1.f / beta; d.f[2] = sd_eps;
     }
     // F5..F8: phi_z MLP (the last layer writes phi into decin row t)
-    const int first_seq = !seq ? 4 : (Z == H ? 0 : 1);  // (the first layer's K is Z: part of the run only when Z == H)
+    const int first_seq = Z == H ? 0 : 1;  // (the first layer's K is Z: part of the run only when Z == H)
     for (int l = 0; l < first_seq; ++l) {
       const float* A = l == 0 ? rs.Z16 : rs.FZ16[l - 1];
       lin(A, l == 0 ? xZ : xH, rs.Wf[l], l == 0 ? Z : H, w->phi_b[l], nullptr, 0, 0, l == 3 ? decin : rs.FZ[l], l == 3 ? sD : sH, l == 3 ? ldd : H,
@@ -577,13 +502,8 @@ extern "C" int blvm_vrnn_seq_fwd(const BlvmVrnnWeights* w, const float* enc, con
                                  int Tp, int B, int X, int H, int Z, int R, int residual_posterior, float sd_eps,
                                  float* decin, float* mu_q, float* sd_q, float* mu_p, float* sd_p, float* z,
                                  float* reserve, void* stream_) {
-  BLVM_REQUIRE(w != nullptr, "vrnn_fwd: null pointer");
-  ChainKey key("vrnn_fwd");
-  key.add(*w).add(enc).add(h0).add(eps).add(Tp).add(B).add(X).add(H).add(Z).add(R).add(residual_posterior).add(sd_eps);
-  key.add(decin).add(mu_q).add(sd_q).add(mu_p).add(sd_p).add(z).add(reserve);
-  return run_chain(key, static_cast<hipStream_t>(stream_), [&](hipStream_t s) {
-    return vrnn_seq_fwd_impl(w, enc, h0, eps, Tp, B, X, H, Z, R, residual_posterior, sd_eps, decin, mu_q, sd_q, mu_p, sd_p, z, reserve, s);
-  });
+  return vrnn_seq_fwd_impl(w, enc, h0, eps, Tp, B, X, H, Z, R, residual_posterior, sd_eps, decin, mu_q, sd_q, mu_p, sd_p, z, reserve,
+                           static_cast<hipStream_t>(stream_));
 }
 
 static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const float* eps, const float* decin,
@@ -648,18 +568,17 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     }
   };
 
-  // ---- batched, state-independent part: d(enc) and every weight gradient as large MFMA GEMMs over a row range ----
-  // Rows [r0, r0+nr) of every per-step gradient buffer are final once the chain has passed step r0/B, so the range
-  // can be processed on a second stream UNDER the latency-bound BPTT chain (which leaves most CUs idle).
+  // ---- batched, state-independent part: d(enc) and every weight gradient as large MFMA GEMMs over all rows ----
+  // (Running them on a second stream under the latency-bound chain, in ranges of finished steps, measured slower on MI355X at
+  // [64,16000]: 24.3 ms/step without overlap, 26.1 / 25.3 / 27.2 ms with ranges of 50 / 25 / 125 steps -- the big GEMM workgroups take
+  // CU slots and memory-pipeline share from the chain's links; removed.)
   const float* hprev_all = decin + H;  // [n rows, ld = H+R]
-  auto batched = [&](size_t r0, size_t nr, hipStream_t st) -> int {
+  auto batched = [&]() -> int {
     int rc2 = BLVM_OK;
 #define TRY(x) do { rc2 = (x); if (rc2) return rc2; } while (0)
-    const float* DGI = ws.DGI + r0 * 3 * R; const float* DGH = ws.DGH + r0 * 3 * R;
-    const float* encr = enc + r0 * X; const float* decr = decin + r0 * ldd; const float* hpr = hprev_all + r0 * ldd;
     if (d_enc) {
-      TRY(gemm_f32(0, 1, (int)nr, X, H, ws.DQ[0] + r0 * H, H, w->post_w[0] + R, R + X, d_enc + r0 * X, X, nullptr, 0, 0.f, nullptr, 0, 0, 1, st));
-      TRY(gemm_f32(0, 1, (int)nr, X, 3 * R, DGI, 3 * R, w->gru_wih, X + H, d_enc + r0 * X, X, nullptr, 0, 0.f, nullptr, 0, 1, 1, st));
+      TRY(gemm_f32(0, 1, (int)n, X, H, ws.DQ[0], H, w->post_w[0] + R, R + X, d_enc, X, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
+      TRY(gemm_f32(0, 1, (int)n, X, 3 * R, ws.DGI, 3 * R, w->gru_wih, X + H, d_enc, X, nullptr, 0, 0.f, nullptr, 0, 1, 1, s));
     }
     // every weight gradient of the chain as ONE grouped launch (gemm.hip gemm_wgrad_group; D [rows, M] x Act [rows, N] -> dW [M, N], db [M])
     {
@@ -667,21 +586,21 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       auto job = [&](const float* D, int ldd_, int n_out, const float* Act, int lda, int k_in, float* dW, int ldw, float* db = nullptr) {
         grp.add(D, ldd_, n_out, Act, lda, k_in, dW, ldw, db);
       };
-      job(DGI, 3 * R, 3 * R, encr, X, X, gr->gru_wih, X + H, gr->gru_bih);
-      job(DGI, 3 * R, 3 * R, decr, ldd, H, gr->gru_wih ? gr->gru_wih + X : nullptr, X + H);
-      job(DGH, 3 * R, 3 * R, hpr, ldd, R, gr->gru_whh, R, gr->gru_bhh);
-      job(ws.DPHI[0] + r0 * H, H, H, z + r0 * Z, Z, Z, gr->phi_w[0], Z, gr->phi_b[0]);
-      for (int l = 1; l < 4; ++l) job(ws.DPHI[l] + r0 * H, H, H, rs.FZ[l - 1] + r0 * H, H, H, gr->phi_w[l], H, gr->phi_b[l]);
-      job(ws.DPH + r0 * 2 * Z, 2 * Z, 2 * Z, rs.P[2] + r0 * H, H, H, gr->prior_hw, H, gr->prior_hb);
-      job(ws.DQH + r0 * 2 * Z, 2 * Z, 2 * Z, rs.Q[2] + r0 * H, H, H, gr->post_hw, H, gr->post_hb);
+      job(ws.DGI, 3 * R, 3 * R, enc, X, X, gr->gru_wih, X + H, gr->gru_bih);
+      job(ws.DGI, 3 * R, 3 * R, decin, ldd, H, gr->gru_wih ? gr->gru_wih + X : nullptr, X + H);
+      job(ws.DGH, 3 * R, 3 * R, hprev_all, ldd, R, gr->gru_whh, R, gr->gru_bhh);
+      job(ws.DPHI[0], H, H, z, Z, Z, gr->phi_w[0], Z, gr->phi_b[0]);
+      for (int l = 1; l < 4; ++l) job(ws.DPHI[l], H, H, rs.FZ[l - 1], H, H, gr->phi_w[l], H, gr->phi_b[l]);
+      job(ws.DPH, 2 * Z, 2 * Z, rs.P[2], H, H, gr->prior_hw, H, gr->prior_hb);
+      job(ws.DQH, 2 * Z, 2 * Z, rs.Q[2], H, H, gr->post_hw, H, gr->post_hb);
       for (int l = 2; l >= 1; --l) {
-        job(ws.DP[l] + r0 * H, H, H, rs.P[l - 1] + r0 * H, H, H, gr->prior_w[l], H, gr->prior_b[l]);
-        job(ws.DQ[l] + r0 * H, H, H, rs.Q[l - 1] + r0 * H, H, H, gr->post_w[l], H, gr->post_b[l]);
+        job(ws.DP[l], H, H, rs.P[l - 1], H, H, gr->prior_w[l], H, gr->prior_b[l]);
+        job(ws.DQ[l], H, H, rs.Q[l - 1], H, H, gr->post_w[l], H, gr->post_b[l]);
       }
-      job(ws.DP[0] + r0 * H, H, H, hpr, ldd, R, gr->prior_w[0], R, gr->prior_b[0]);
-      job(ws.DQ[0] + r0 * H, H, H, hpr, ldd, R, gr->post_w[0], R + X);
-      job(ws.DQ[0] + r0 * H, H, H, encr, X, X, gr->post_w[0] ? gr->post_w[0] + R : nullptr, R + X, gr->post_b[0]);
-      TRY(grp.run(nr, st));
+      job(ws.DP[0], H, H, hprev_all, ldd, R, gr->prior_w[0], R, gr->prior_b[0]);
+      job(ws.DQ[0], H, H, hprev_all, ldd, R, gr->post_w[0], R + X);
+      job(ws.DQ[0], H, H, enc, X, X, gr->post_w[0] ? gr->post_w[0] + R : nullptr, R + X, gr->post_b[0]);
+      TRY(grp.run(n, s));
     }
 #undef TRY
     return BLVM_OK;
@@ -766,26 +685,14 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       d.n16[0] = ctH; d.i[1] = n; d.i[2] = H; d.f[0] = 0.f;
       return d;
     };
-    const bool seq = pchain_linseq();
-    if (seq) {
-      const SeqLinkB lf[3] = {{ws.fT[3], rs.FZ[2], ws.DPHI[2], ws.DPHI16[2]}, {ws.fT[2], rs.FZ[1], ws.DPHI[1], ws.DPHI16[1]}, {ws.fT[1], rs.FZ[0], ws.DPHI[0], ws.DPHI16[0]}};
-      if (split3) {  // the link that adds the three partial-sum slabs up is a K_LIN of its own (a run's links are plain), the other two a run
-        lin(ws.DPHI16[3], xH, ws.fT[3], H, nullptr, 0, 0, rs.FZ[2], sH, H, ws.DPHI[2], sH, H, ws.DPHI16[2], xH, ctH, ctH, 0, range_for(ctH * tl, wide), DF_A_SUM3);
-        Desc& d = bld.p.d[bld.p.ndesc - 1];
-        bld.ptr(d, 8, ws.DPHI16b + (long)(T - 1) * xH, -xH); bld.ptr(d, 9, ws.DPHI16c + (long)(T - 1) * xH, -xH);
-        linseq_b(ws.DPHI16[2], 2, lf + 1, 0, range_for(ctH * tl, wide), 0);
-      } else {
-        linseq_b(ws.DPHI16[3], 3, lf, 0, range_for(ctH * tl, wide), 0);
-      }
+    const SeqLinkB lf[3] = {{ws.fT[3], rs.FZ[2], ws.DPHI[2], ws.DPHI16[2]}, {ws.fT[2], rs.FZ[1], ws.DPHI[1], ws.DPHI16[1]}, {ws.fT[1], rs.FZ[0], ws.DPHI[0], ws.DPHI16[0]}};
+    if (split3) {  // the link that adds the three partial-sum slabs up is a K_LIN of its own (a run's links are plain), the other two a run
+      lin(ws.DPHI16[3], xH, ws.fT[3], H, nullptr, 0, 0, rs.FZ[2], sH, H, ws.DPHI[2], sH, H, ws.DPHI16[2], xH, ctH, ctH, 0, range_for(ctH * tl, wide), DF_A_SUM3);
+      Desc& d = bld.p.d[bld.p.ndesc - 1];
+      bld.ptr(d, 8, ws.DPHI16b + (long)(T - 1) * xH, -xH); bld.ptr(d, 9, ws.DPHI16c + (long)(T - 1) * xH, -xH);
+      linseq_b(ws.DPHI16[2], 2, lf + 1, 0, range_for(ctH * tl, wide), 0);
     } else {
-      for (int l = 3; l >= 1; --l) {
-        lin(ws.DPHI16[l], xH, ws.fT[l], H, nullptr, 0, 0, rs.FZ[l - 1], sH, H, ws.DPHI[l - 1], sH, H, ws.DPHI16[l - 1], xH, ctH, ctH, 0, range_for(ctH * tl, wide),
-            l == 3 && split3 ? DF_A_SUM3 : 0);
-        if (l == 3 && split3) {
-          Desc& d = bld.p.d[bld.p.ndesc - 1];
-          bld.ptr(d, 8, ws.DPHI16b + (long)(T - 1) * xH, -xH); bld.ptr(d, 9, ws.DPHI16c + (long)(T - 1) * xH, -xH);
-        }
-      }
+      linseq_b(ws.DPHI16[3], 3, lf, 0, range_for(ctH * tl, wide), 0);
     }
     {  // B6: dz and the heads
       Desc& d = bld.add(K_DZ, ctZ, 0, range_for(ctZ * tl, wide), H, 0, 0, T);
@@ -798,83 +705,28 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       d.ld[3] = 2 * Z; d.n16[0] = 2 * ctZ; d.i[0] = Z; d.i[1] = residual_posterior; d.i[2] = stride; d.i[3] = T - 1;
       d.f[0] = fn_floor; d.f[1] = beta; d.f[2] = sd_eps;
     }
-    // B7: heads -> last hidden layers;  B8, B9: hidden layers 2, 1  (prior | posterior)
-    const bool merge1 = vrnn_merge_first(groups);
-    if (seq && merge1) {  // B7 .. B9 of a chain: one visit
+    // B7: heads -> last hidden layers;  B8, B9: hidden layers 2, 1  (prior | posterior).  B7 .. B9 of a chain: one visit (the heads'
+    // gradient link, K = 2Z, joins the run's descriptor visit)
+    {
       const SeqLinkB lp[3] = {{ws.phT, rs.P[2], ws.DP[2], ws.DP16[2]}, {ws.pT[2], rs.P[1], ws.DP[1], ws.DP16[1]}, {ws.pT[1], rs.P[0], ws.DP[0], ws.DP16[0]}};
       const SeqLinkB lq[3] = {{ws.qhT, rs.Q[2], ws.DQ[2], ws.DQ16[2]}, {ws.qT[2], rs.Q[1], ws.DQ[1], ws.DQ16[1]}, {ws.qT[1], rs.Q[0], ws.DQ[0], ws.DQ16[0]}};
       linseq_b(ws.DPH16, 3, lp, 0, half, 0, 2 * Z, x2Z);
       linseq_b(ws.DQH16, 3, lq, half, half, 0, 2 * Z, x2Z);
-    }
-    for (int l = 3; l >= (seq ? 3 : 1) && !(seq && merge1); --l) {
-      lin(l == 3 ? ws.DPH16 : ws.DP16[l], l == 3 ? x2Z : xH, l == 3 ? ws.phT : ws.pT[l], l == 3 ? 2 * Z : H, nullptr, 0, 0, rs.P[l - 1], sH, H, ws.DP[l - 1], sH, H,
-          ws.DP16[l - 1], xH, ctH, ctH, 0, half, 0);
-      lin(l == 3 ? ws.DQH16 : ws.DQ16[l], l == 3 ? x2Z : xH, l == 3 ? ws.qhT : ws.qT[l], l == 3 ? 2 * Z : H, nullptr, 0, 0, rs.Q[l - 1], sH, H, ws.DQ[l - 1], sH, H,
-          ws.DQ16[l - 1], xH, ctH, ctH, half, half, 0);
-    }
-    if (seq && !merge1) {  // B8, B9 of the prior | of the posterior: one visit each
-      const SeqLinkB lp[2] = {{ws.pT[2], rs.P[1], ws.DP[1], ws.DP16[1]}, {ws.pT[1], rs.P[0], ws.DP[0], ws.DP16[0]}};
-      const SeqLinkB lq[2] = {{ws.qT[2], rs.Q[1], ws.DQ[1], ws.DQ16[1]}, {ws.qT[1], rs.Q[0], ws.DQ[0], ws.DQ16[0]}};
-      linseq_b(ws.DP16[2], 2, lp, 0, half, 0);
-      linseq_b(ws.DQ16[2], 2, lq, half, half, 0);
     }
     BLVM_REQUIRE(!bld.overflow, "vrnn_bwd: persistent program overflow");
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
     if (rc) return rc;
     // sentinel-fill what the launch polls: GA, GB (single words) and the T16 copies
     BLVM_HIP(pchain_fill_sentinel(ws.GA, (size_t)(reinterpret_cast<char*>(ws.x16_end) - reinterpret_cast<char*>(ws.GA)), s));
-    // The batched GEMMs of the steps the chain has passed can run UNDER the rest of the chain (which keeps a quarter of the chip
-    // busy): the sequence is cut into `parts` launches, after each the finished rows go to a low-priority side stream.
-    const int parts = std::max(1, std::min(pchain_wgrad_parts(), T / 8));
-    auto add_partials = [&](size_t r0, size_t nr) {  // DPHI[3] rows [r0, r0 + nr) += the two other partial sums
-      if (!split3 || nr == 0) return;
-      const size_t n4 = nr * H / 4;
-      hipLaunchKernelGGL(add3_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, reinterpret_cast<float4*>(ws.DPHI[3] + r0 * H),
-                         reinterpret_cast<const float4*>(ws.DPHI3b + r0 * H), reinterpret_cast<const float4*>(ws.DPHI3c + r0 * H), n4);
-    };
-    if (parts == 1) {
-      rc = pchain_launch(bld.p, s);
-      if (rc) return rc;
-      add_partials(0, n);
-      return batched(0, n, s);
-    }
-    SideStream& sd = side_stream();
-    rc = sd.ensure();
+    rc = pchain_launch(bld.p, s);
     if (rc) return rc;
-    int done_steps = 0;  // steps s < done_steps are finished: rows of t in [T - done_steps, T)
-    for (int k = 0; k < parts; ++k) {
-      const int s_end = k + 1 == parts ? T + 1 : (int)((long)T * (k + 1) / parts);
-      bld.p.s_first = done_steps; bld.p.S = s_end;
-      if (k > 0) {  // a fresh abort epoch per launch
-        rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-        if (rc) return rc;
-      }
-      rc = pchain_launch(bld.p, s);
-      if (rc) return rc;
-      const int fin = std::min(s_end, T);
-      add_partials((size_t)(T - fin) * B, (size_t)(fin - done_steps) * B);
-      // (all ranges on the ONE side stream: two of them accumulating into the same gradient must not run concurrently)
-      BLVM_HIP(hipEventRecord(sd.ready, s));
-      BLVM_HIP(hipStreamWaitEvent(sd.stream, sd.ready, 0));
-      rc = batched((size_t)(T - fin) * B, (size_t)(fin - done_steps) * B, sd.stream);
-      if (rc) return rc;
-      done_steps = fin;
+    if (split3) {  // DPHI[3] += the two other partial sums
+      const size_t n4 = n * H / 4;
+      hipLaunchKernelGGL(add3_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, reinterpret_cast<float4*>(ws.DPHI[3]),
+                         reinterpret_cast<const float4*>(ws.DPHI3b), reinterpret_cast<const float4*>(ws.DPHI3c), n4);
     }
-    BLVM_HIP(hipEventRecord(sd.done, sd.stream));
-    BLVM_HIP(hipStreamWaitEvent(s, sd.done, 0));
-    return BLVM_OK;
+    return batched();
   }
-  const int chunk = overlap_chunk_steps();
-  const bool overlap = chunk > 0 && Tp >= 2 * chunk;
-  SideStream& side = side_stream();
-  if (overlap) {
-    rc = side.ensure();
-    if (rc) return rc;
-    // the side stream must not start before the caller's stream has produced this call's inputs / zeroed grads
-    BLVM_HIP(hipEventRecord(side.ready, s));
-    BLVM_HIP(hipStreamWaitEvent(side.stream, side.ready, 0));
-  }
-  int chunk_hi = Tp;  // steps [chunk_lo, chunk_hi) form the next range handed to the side stream
 
   launch_dh(-1, Tp - 1);  // G(T') = 0: gate derivatives of the last step, G <- d_decin h-part of row T'-1
   for (int t = Tp - 1; t >= 0; --t) {
@@ -917,25 +769,11 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     }
     // B10 (+ gate derivatives of step t-1)
     launch_dh(t, t - 1);
-    if (overlap && (chunk_hi - t >= chunk || t == 0)) {  // every per-step gradient of steps >= t is final now
-      BLVM_HIP(hipEventRecord(side.ready, s));
-      BLVM_HIP(hipStreamWaitEvent(side.stream, side.ready, 0));
-      rc = batched((size_t)t * B, (size_t)(chunk_hi - t) * B, side.stream);
-      if (rc) return rc;
-      chunk_hi = t;
-    }
   }
   BLVM_CHECK_LAUNCH("vrnn_seq_bwd");
   if (d_h0) BLVM_HIP(hipMemcpyAsync(d_h0, ws.G, sizeof(float) * (size_t)B * R, hipMemcpyDeviceToDevice, s));
 
-  if (overlap) {  // join the side stream: everything queued after this call sees the weight gradients
-    BLVM_HIP(hipEventRecord(side.done, side.stream));
-    BLVM_HIP(hipStreamWaitEvent(s, side.done, 0));
-  } else {
-    rc = batched(0, n, s);
-    if (rc) return rc;
-  }
-  return BLVM_OK;
+  return batched();
 }
 
 extern "C" int blvm_vrnn_seq_bwd(const BlvmVrnnWeights* w, const float* enc, const float* eps, const float* decin,
@@ -944,15 +782,6 @@ extern "C" int blvm_vrnn_seq_bwd(const BlvmVrnnWeights* w, const float* enc, con
                                  const float* c_raw, const float* c_fn, int stride, float fn_floor, int Tp, int B, int X, int H, int Z,
                                  int R, int residual_posterior, float sd_eps, float* d_enc, float* d_h0,
                                  const BlvmVrnnGrads* gr, float* workspace, void* stream_) {
-  BLVM_REQUIRE(w != nullptr && gr != nullptr, "vrnn_bwd: null pointer");
-  auto body = [&](hipStream_t s) {
-    return vrnn_seq_bwd_impl(w, enc, eps, decin, mu_q, sd_q, mu_p, sd_p, z, reserve, d_decin, x_sl, c_raw, c_fn, stride, fn_floor, Tp, B, X,
-                             H, Z, R, residual_posterior, sd_eps, d_enc, d_h0, gr, workspace, s);
-  };
-  if (overlap_chunk_steps() > 0) return body(static_cast<hipStream_t>(stream_));  // the side-stream experiment is not capturable
-  ChainKey key("vrnn_bwd");
-  key.add(*w).add(enc).add(eps).add(decin).add(mu_q).add(sd_q).add(mu_p).add(sd_p).add(z).add(reserve).add(d_decin).add(x_sl);
-  key.add(c_raw).add(c_fn).add(stride).add(fn_floor).add(Tp).add(B).add(X).add(H).add(Z).add(R).add(residual_posterior).add(sd_eps);
-  key.add(d_enc).add(d_h0).add(*gr).add(workspace);
-  return run_chain(key, static_cast<hipStream_t>(stream_), body);
+  return vrnn_seq_bwd_impl(w, enc, eps, decin, mu_q, sd_q, mu_p, sd_p, z, reserve, d_decin, x_sl, c_raw, c_fn, stride, fn_floor, Tp, B, X,
+                           H, Z, R, residual_posterior, sd_eps, d_enc, d_h0, gr, workspace, static_cast<hipStream_t>(stream_));
 }

@@ -754,11 +754,7 @@ __global__ __launch_bounds__(256) void wn_ts_wgrad_kernel(TsArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int m = (wave * MW + i) * 16 + 4 * kq + r, n = (j0 + j) * 16 + li;
-#ifdef WN_TS_NOATOMIC  // timing experiment only: wrong results
-          if (a.rows == 1) a.out[((size_t)m * N + n) * a.ostride + (SPLIT ? tap : b)] = acc[b][i][j][r];
-#else
           atomicAdd(a.out + ((size_t)m * N + n) * a.ostride + (SPLIT ? tap : b), acc[b][i][j][r]);
-#endif
         }
   if (do_csum) atomicAdd(a.colsum + tid, csum);
 }

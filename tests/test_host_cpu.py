@@ -29,6 +29,18 @@ def test_library_exports_every_declared_symbol():
     assert _hip.load().blvm_version() >= 100
 
 
+def test_pchain_configure_accepts_only_the_built_wave_count():
+    """The persistent kernels exist for 16 waves per workgroup only: `waves` <= 0 or 16 leaves the configuration as it is, any other
+    count is refused with a message instead of being ignored."""
+    lib = _hip.load()
+    before = lib.blvm_pchain_max_batch()
+    for waves in (-1, 0, 16):
+        assert lib.blvm_pchain_configure(-1, waves) == 0, waves
+    assert lib.blvm_pchain_configure(-1, 8) == -1
+    assert b"16 waves" in lib.blvm_last_error()
+    assert lib.blvm_pchain_max_batch() == before
+
+
 def test_cpu_tensor_is_refused_loudly():
     m = VRNNAudio(likelihood="DMoL", input_size=8, hidden_size=32, latent_size=16)
     x, x_sl = O.synth_batch(2, 32, seed=1)

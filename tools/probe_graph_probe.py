@@ -22,4 +22,4 @@ for bwd in (False, True):
     t_host = time.perf_counter() - t0
     torch.cuda.synchronize()
     t_all = time.perf_counter() - t0
-    print(f"graphs={os.environ.get('BLVM_GRAPHS', '1')} bwd={bwd}: host enqueue {t_host / n * 1e3:.2f} ms/step, total {t_all / n * 1e3:.2f} ms/step", flush=True)
+    print(f"bwd={bwd}: host enqueue {t_host / n * 1e3:.2f} ms/step, total {t_all / n * 1e3:.2f} ms/step", flush=True)
