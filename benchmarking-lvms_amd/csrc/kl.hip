@@ -111,9 +111,9 @@ __global__ __launch_bounds__(256) void kl_bwd_kernel(KlArgs a) {
     const float mq = a.mu_q[base + c], sq = a.sd_q[base + c], mp = a.mu_p[base + c], sp = a.sd_p[base + c];
     float coef = cr;
     if (cf != 0.f) {
-      // d max(kl, floor)/d kl: 1 above the floor, 0 below (ties have measure zero)
+      // d max(kl, floor)/d kl: 1 above the floor, 0 below, 1/2 at a tie (torch.maximum, what the reference differentiates)
       const float k = kl_elem(mq, sq, mp, sp);
-      coef += (!use_fn || k > a.fn_floor) ? cf : 0.f;
+      coef += (!use_fn || k > a.fn_floor) ? cf : (k == a.fn_floor ? 0.5f * cf : 0.f);
     }
     const float d = mq - mp, ip2 = 1.f / (sp * sp);
     a.d_mu_q[base + c] = coef * d * ip2;

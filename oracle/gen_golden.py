@@ -499,6 +499,146 @@ def gen_heads():
     save("heads.npz", **arrays)
 
 
+def _centres(k, bins):
+    """Exact bin centres 2k/(bins-1) - 1 (the values a quantised target takes), rounded once to float32."""
+    return (2.0 * torch.as_tensor(k, dtype=torch.float64) / (bins - 1) - 1.0).float()
+
+
+def _dmol_delta(m, w):
+    """sigmoid(m+w) - sigmoid(m-w) in float64 without cancellation."""
+    return math.sinh(w) / (math.cosh(m) + math.cosh(w))
+
+
+def _dmol_m_for_delta(target, w):
+    """The negative m with delta(m, w) = target (bisection; delta rises monotonically on m < 0)."""
+    lo, hi = -300.0, 0.0
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if _dmol_delta(mid, w) < target else (lo, mid)
+    return 0.5 * (lo + hi)
+
+
+def _dmol_stress_frames(bins, g):
+    """256 crafted DMoL frames [256, 30] (logits | locs | raw log-scales before the -7 clamp) and targets [256] for `bins`
+    bins, four 64-frame waves:
+      0  trained regime: raw log-scales in [-7,-3], some below -7 and some exactly -7.0; |m| = |y-loc|/s from 0 to 1e3
+         (87..104 included: exp(-|m|) is a float32 denormal); edge targets y = +-1 and |y| > 1 - 2/bins among interior ones;
+      1  branch boundaries: a dominant component with delta 2 % above / below 1e-5, and (256 bins) w = half_bin/s 0.1 %
+         either side of 0.25 and from 0.5 to 4;
+      2  extreme logits (spread > 90: some mixture weights underflow) and clamp ties, with edge targets;
+      3  all components far out (|m| 20..1e3, the log-pdf-mid fallback everywhere) and a random trained mix.
+    Every interior target is an exact bin centre."""
+    N, K = 256, 10
+    U = lambda *s: torch.rand(*s, generator=g, dtype=torch.float64)  # noqa: E731
+    half = 1.0 / (bins - 1)
+    y = _centres(torch.randint(1, bins - 1, (N,), generator=g), bins).double()
+    logits = torch.randn(N, K, generator=g, dtype=torch.float64) * 2
+    raw = -7.0 + 4.0 * U(N, K)
+    sgn = torch.where(U(N, K) < 0.5, -1.0, 1.0).double()
+    m = sgn * torch.exp(math.log(1e-3) + U(N, K) * math.log(1e6))  # |m| log-uniform in [1e-3, 1e3]
+    # wave 0
+    w0 = slice(0, 64)
+    raw[w0][U(64, K) < 0.1] = -7.0
+    below = U(64, K) < 0.1
+    raw[w0][below] = -9.0 + 2.0 * U(int(below.sum()))
+    deno = U(64, K) < 0.15
+    m[w0][deno] = sgn[w0][deno] * (87.0 + 17.0 * U(int(deno.sum())))
+    m[0:4, 0] = 0.0
+    y[[3, 17, 40, 41]] = torch.tensor([1.0, -1.0, 1.0 - 1.0 / bins, -1.0 + 1.0 / bins], dtype=torch.float64)
+    # wave 1: component 0 dominates
+    logits[64:128, 0] = 12.0
+    for i in range(64, 128):
+        r = i - 64
+        if bins <= 256 and r >= 32:
+            ws = [0.25 * (1 - 1e-3), 0.25 * (1 + 1e-3), 0.5, 1.0, 1.5, 1.9, 2.5, 4.0]
+            w = ws[r % len(ws)]
+            raw[i, 0] = math.log(half / w)
+            m[i, 0] = float(torch.randn(1, generator=g)) * 1.5 if r % 3 else 0.0
+        else:
+            if bins <= 256 and r % 4 == 0:  # delta boundary with w on either side of 0.25
+                w = 0.25 * (1 + (1e-3 if r % 8 else -1e-3))
+                raw[i, 0] = math.log(half / w)
+            s = math.exp(raw[i, 0])
+            target = 1e-5 * (1.02 if r % 2 else 0.98)
+            m[i, 0] = _dmol_m_for_delta(target, half / s)
+    # wave 2
+    logits[128:192] = -45.0 - 60.0 * U(64, K)
+    logits[128:192, 0] = 50.0
+    logits[128:192, 1] = 48.0
+    raw[128:192][U(64, K) < 0.4] = -7.0
+    y[[130, 150, 191]] = torch.tensor([-1.0, 1.0, -1.0], dtype=torch.float64)
+    deno = U(64, K) < 0.3
+    m[128:192][deno] = sgn[128:192][deno] * (87.0 + 17.0 * U(int(deno.sum())))
+    # wave 3
+    far = slice(192, 224)
+    m[far] = sgn[far] * torch.exp(math.log(20.0) + U(32, K) * math.log(50.0))
+    s = torch.exp(raw.clamp(min=-7.0))
+    locs = (y.unsqueeze(1) - m * s).float()
+    par = torch.cat([logits.float(), locs, raw.float()], 1)
+    return par, y.float()
+
+
+def gen_heads_stress():
+    """Per-frame / per-element fixtures for the likelihood and KL kernels in trained-model regimes: crafted inputs, the
+    reference's float32 values and autograd gradients (tests/test_oracle_golden.py pins the oracle to them,
+    tests/test_gpu_heads.py holds the HIP kernels to the float64 oracle on the same inputs)."""
+    g = torch.Generator().manual_seed(2024)
+    out = {}
+    for bins in (2**16, 256):
+        par, y = _dmol_stress_frames(bins, g)
+        p = par.clone().requires_grad_(True)
+        locs, ls = p[:, 10:20].unsqueeze(1), p[:, 20:].clamp(min=-7.0).unsqueeze(1)  # distributions.py:386
+        ll = RLL.discretized_logistic_mixture_ll(y.unsqueeze(1), p[:, :10], locs, ls, num_bins=bins)
+        ll.sum().backward()
+        out.update({f"dmol{bins}_par": par, f"dmol{bins}_y": y, f"dmol{bins}_ll": ll, f"dmol{bins}_grad": p.grad})
+
+    # Gaussian mixture / single Gaussian heads: sd = softplus_beta(raw) + sd_eps, epsilon 0 in the likelihood
+    N, K, beta, sd_eps = 256, 10, 2.5, 1e-4
+    U = lambda *s: torch.rand(*s, generator=g)  # noqa: E731
+    y = torch.rand(N, generator=g) * 2 - 1
+    logits = torch.randn(N, K, generator=g) * 2
+    logits[192:, 0] = 60.0  # spread > 90
+    logits[192:, 1:] = -40.0 - 20 * U(64, K - 1)
+    raw = torch.randn(N, K, generator=g)
+    raw[0:64] = -40.0 / beta  # sd at the sd_eps floor
+    cross = torch.tensor([19.0, 19.99, 20.0, 20.01, 21.0, 30.0]) / beta  # beta * raw either side of softplus's threshold
+    raw[64:128] = cross[torch.randint(0, len(cross), (64, K), generator=g)]
+    sd = torch.nn.functional.softplus(raw.double(), beta=beta) + sd_eps
+    mu = (y.double().unsqueeze(1) - torch.randn(N, K, generator=g).double() * 3 * sd).float()
+    gpar = torch.cat([logits, mu, raw], 1)
+    p = gpar.clone().requires_grad_(True)
+    sdp = torch.nn.functional.softplus(p[:, 20:], beta=beta) + sd_eps
+    ll = RLL.gaussian_mixture_ll(y.unsqueeze(1), p[:, :10], p[:, 10:20].unsqueeze(1), sdp.unsqueeze(1), epsilon=0)
+    ll.sum().backward()
+    out.update(gmm_par=gpar, gmm_y=y, gmm_ll=ll, gmm_grad=p.grad, gmm_beta=np.float32(beta), gmm_sd_eps=np.float32(sd_eps))
+    gp = torch.stack([mu[:, 0], raw[:, 0]], 1)
+    p = gp.clone().requires_grad_(True)
+    ll = RLL.gaussian_ll(y, p[:, 0], torch.nn.functional.softplus(p[:, 1], beta=beta) + sd_eps, epsilon=0, reduce_dim=None)
+    ll.sum().backward()
+    out.update(gauss_par=gp, gauss_ll=ll, gauss_grad=p.grad)
+
+    # KL + free nats: sq/sp from 1e-3 to 1e3; every 16th element ties the free-nats floor 0.125 exactly (sq = sp = 2^j,
+    # mu_q - mu_p = 2^(j-1): KL = 1/8 in every precision); the fixture's floor is free_nats / Z = 32 / 256
+    R, Z = 16, 256
+    sp = torch.exp(torch.rand(R, Z, generator=g) * 4 - 2)
+    sq = sp * torch.exp(torch.rand(R, Z, generator=g) * 2 * math.log(1e3) - math.log(1e3))
+    mp, mq = torch.randn(R, Z, generator=g), torch.randn(R, Z, generator=g)
+    j = torch.randint(-2, 3, (R, Z // 16), generator=g).float()
+    mp[:, ::16] = torch.randint(-16, 17, (R, Z // 16), generator=g).float() / 8
+    sp[:, ::16] = sq[:, ::16] = torch.exp2(j)
+    mq[:, ::16] = mp[:, ::16] + torch.exp2(j - 1)
+    ins = [t.clone().requires_grad_(True) for t in (mq, sq, mp, sp)]
+    kl = RV.kl_divergence_gaussian(*ins)
+    assert bool((kl.detach()[:, ::16] == 0.125).all())
+    fn = RV.discount_free_nats(kl, 32.0, shared_dims=-1)
+    out.update(kl_mq=mq, kl_sq=sq, kl_mp=mp, kl_sp=sp, kl_out=kl, kl_fn=fn, kl_free_nats=np.float32(32.0))
+    for tag, v in (("kl", kl), ("fn", fn)):
+        grads = torch.autograd.grad(v.sum(), ins, retain_graph=True)
+        for name, gr in zip(("mq", "sq", "mp", "sp"), grads):
+            out[f"kl_grad_{tag}_{name}"] = gr
+    save("heads_stress.npz", **out)
+
+
 def gen_generate():
     """Ancestral sampling: CWVAEAudio.generate with the mode of the observation model (the latents are still sampled; the
     draw order — top level first, one randn(B, z) per step — is replayed into eps)."""
@@ -970,6 +1110,6 @@ def gen_split_eval():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["functions", "vrnn_small", "vrnn_full", "lstm", "srnn", "wavenet", "rssm", "cwvae", "stcn", "heads", "generate", "generate16", "wavenet_stacked", "cwvae_resets", "stcn_bottom_up", "lstm_layers", "data", "split_eval"]
+    which = sys.argv[1:] or ["functions", "vrnn_small", "vrnn_full", "lstm", "srnn", "wavenet", "rssm", "cwvae", "stcn", "heads", "generate", "generate16", "wavenet_stacked", "cwvae_resets", "stcn_bottom_up", "lstm_layers", "data", "split_eval", "heads_stress"]
     for w in which:
         globals()[f"gen_{w}"]()

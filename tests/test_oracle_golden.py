@@ -450,3 +450,62 @@ def test_split_eval_cwvae_host_splits_and_single_split_oracle():
         close(out["z"][l].transpose(0, 1), g[f"cw_one_z{l}"], 1e-5, 1e-6)
         close(out["state_n"][l][0], g[f"cw_one_state_z{l}"], 1e-5, 1e-6)
         close(out["state_n"][l][1], g[f"cw_one_state_h{l}"], 1e-5, 1e-6)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# heads_stress.npz: crafted trained-model regimes of the likelihood and KL functions (oracle/gen_golden.py::gen_heads_stress).
+# The GPU head tests use the float64 oracle as truth on exactly these inputs; here the oracle in float32 must reproduce the
+# reference's float32 values AND autograd gradients on them (256-bin gradient, clamp ties, free-nats ties included).
+# ----------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.fixture(scope="module")
+def hs():
+    return np.load(os.path.join(GOLDEN, "heads_stress.npz"))
+
+
+@pytest.mark.parametrize("bins", [2**16, 256])
+def test_heads_stress_dmol_values_and_gradients(hs, bins):
+    p = T(hs[f"dmol{bins}_par"]).clone().requires_grad_(True)
+    y = T(hs[f"dmol{bins}_y"])
+    lg, lc, ls = O.dmol_head(p, torch.eye(30), torch.zeros(30))
+    ll = O.dmol_ll(y.unsqueeze(1), lg, lc, ls, bins)
+    ll.sum().backward()
+    close(ll.detach(), hs[f"dmol{bins}_ll"], 1e-6, 1e-6)
+    close(p.grad, hs[f"dmol{bins}_grad"], 1e-6, 1e-6)
+    # the crafted regimes are really there: raw log-scales exactly at the clamp, frames with |y| > 1 - 2/bins
+    raw = T(hs[f"dmol{bins}_par"])[:, 20:]
+    assert int((raw == -7.0).sum()) > 50 and int((raw < -7.0).sum()) > 20
+    assert int((y.abs() > 1 - 2 / bins).sum()) >= 7
+
+
+def test_heads_stress_gaussian_heads(hs):
+    beta, eps = float(hs["gmm_beta"]), float(hs["gmm_sd_eps"])
+    p = T(hs["gmm_par"]).clone().requires_grad_(True)
+    y = T(hs["gmm_y"])
+    sd = torch.nn.functional.softplus(p[:, 20:], beta=beta) + eps
+    ll = O.gaussian_mixture_ll(y.unsqueeze(1), p[:, :10], p[:, 10:20].unsqueeze(1), sd.unsqueeze(1), epsilon=0)
+    ll.sum().backward()
+    close(ll.detach(), hs["gmm_ll"], 1e-6, 1e-6)
+    close(p.grad, hs["gmm_grad"], 1e-6, 1e-6)
+    p = T(hs["gauss_par"]).clone().requires_grad_(True)
+    ll = O.gaussian_ll(y, p[:, 0], torch.nn.functional.softplus(p[:, 1], beta=beta) + eps, epsilon=0)
+    ll.sum().backward()
+    close(ll.detach(), hs["gauss_ll"], 1e-6, 1e-6)
+    close(p.grad, hs["gauss_grad"], 1e-6, 1e-6)
+
+
+def test_heads_stress_kl_free_nats_ties(hs):
+    ins = [T(hs[f"kl_{k}"]).clone().requires_grad_(True) for k in ("mq", "sq", "mp", "sp")]
+    kl = O.kl_gaussian(*ins)
+    fn = O.discount_free_nats(kl, float(hs["kl_free_nats"]))
+    close(kl.detach(), hs["kl_out"], 1e-6, 1e-6)
+    close(fn.detach(), hs["kl_fn"], 1e-6, 1e-6)
+    assert bool((kl.detach()[:, ::16] == 0.125).all())  # exact ties with the floor 32 / 256
+    for tag, v in (("kl", kl), ("fn", fn)):
+        grads = torch.autograd.grad(v.sum(), ins, retain_graph=True)
+        for name, gr in zip(("mq", "sq", "mp", "sp"), grads):
+            close(gr, hs[f"kl_grad_{tag}_{name}"], 1e-6, 1e-6)
+    # at a tie d max(kl, floor)/d kl is 1/2 (torch.maximum), so the floored gradient there is half the raw one
+    g_fn, g_kl = T(hs["kl_grad_fn_mq"])[:, ::16], T(hs["kl_grad_kl_mq"])[:, ::16]
+    torch.testing.assert_close(g_fn, 0.5 * g_kl, rtol=0, atol=0)
