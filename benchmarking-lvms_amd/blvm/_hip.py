@@ -83,7 +83,9 @@ _SIGNATURES = {
     "blvm_get_operand_dtype": (c_int, []),
     "blvm_pchain_profile": (c_int, [c_void_p]),
     "blvm_pchain_tune": (c_int, [c_int]),
+    "blvm_pchain_static": (c_int, [c_int]),
     "blvm_pchain_chain_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "blvm_pchain_static_chain_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "blvm_pchain_rows_to_t16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "blvm_gemm_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_void_p, c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),

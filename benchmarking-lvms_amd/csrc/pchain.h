@@ -1074,6 +1074,9 @@ inline int range_for(int tiles, int avail) { return std::max(8, std::min(avail &
 hipError_t pchain_fill_sentinel(void* p, size_t bytes, hipStream_t stream);
 // enqueue the persistent launch of a program (pchain.hip); grid = highest workgroup any descriptor names
 int pchain_launch(const pchain::Program& prog, hipStream_t stream);
+// the VRNN forward / backward program on the static-walk kernels (vrnn_static.hip); 1: not the shape they were compiled for, or
+// blvm_pchain_static(0) — the caller runs pchain_launch
+int vrnn_static_launch(const pchain::Program& prog, bool forward, hipStream_t stream);
 // dst = T16 copy [ceil(B/16)*16, K] of the rows of src [B, K] (row stride ld; null: zeros); rows >= B are left alone (never read).
 // n16 > 0: dst is a slab of n16 blocks per row tile (a concatenation; dst points at this part's first block)
 int pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, hipStream_t stream, int n16 = 0);

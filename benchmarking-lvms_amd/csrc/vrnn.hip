@@ -441,7 +441,8 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     else BLVM_HIP(hipMemset2DAsync(decin + H, sizeof(float) * ldd, 0, sizeof(float) * R, B, s));
     rc = pchain_rows_to_t16(h0, R, B, R, rs.H16, s);
     if (rc) return rc;
-    return pchain_launch(bld.p, s);
+    rc = vrnn_static_launch(bld.p, true, s);
+    return rc == 1 ? pchain_launch(bld.p, s) : rc;
   }
   for (int t = 0; t < Tp; ++t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z, oR = (size_t)t * B * R, o3R = (size_t)t * B * 3 * R;
@@ -718,7 +719,8 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     if (rc) return rc;
     // sentinel-fill what the launch polls: GA, GB (single words) and the T16 copies
     BLVM_HIP(pchain_fill_sentinel(ws.GA, (size_t)(reinterpret_cast<char*>(ws.x16_end) - reinterpret_cast<char*>(ws.GA)), s));
-    rc = pchain_launch(bld.p, s);
+    rc = vrnn_static_launch(bld.p, false, s);
+    if (rc == 1) rc = pchain_launch(bld.p, s);
     if (rc) return rc;
     if (split3) {  // DPHI[3] += the two other partial sums
       const size_t n4 = n * H / 4;

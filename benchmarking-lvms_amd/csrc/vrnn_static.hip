@@ -1,0 +1,561 @@
+// vrnn_static.hip — persistent chains whose walk is fixed at compile time (the "static walk"), against pchain.hip's interpreter.
+//
+// pchain_kernel walks a program of descriptors: every visit of a descriptor extracts its fields with v_readlane, switches on the
+// tile kind and selects flags and pointers — ≈ 350 scalar instructions that all 16 waves of a workgroup execute, ≈ 1 µs per visit
+// against a 1.5–1.7 µs tile.  A static walk knows the kinds, flags, K values and run lengths of its program as
+// constants; only base pointers and per-step strides arrive as kernel arguments (s_load), and a step's address is base + s * stride
+// in scalar registers at the point of use.  The tiles (pchain.h) and the hand-off protocol are the interpreter's, unchanged.
+//
+// The host builds the same pchain::Program as for the interpreter and converts it here; a program of any other shape is "not
+// applicable" (return value 1) and the caller falls back to pchain_launch.
+//
+// Here: the VRNN forward and backward programs of vrnn.hip at B <= 64 on 16-row tiles, fp32, H = Z = 256, R = 512 (the backward in
+// its split3 form), and the gate the design passed first — the dependent linear chain of blvm_pchain_chain_probe as a static walk
+// (blvm_pchain_static_chain_probe), priced per link against the engine and the bare tile loop (tools/probe_static_chain.py).
+// A workgroup picks its role once from its index (prior half, posterior half, gentle range, spare range); each role's step loop
+// is its own branch, a straight sequence of visits, and a visit is skipped when the deal gives the workgroup no tile of the link.
+// blvm_pchain_static(0) sends the VRNN programs to the interpreter (tests compare both paths in one process).
+#include <algorithm>
+#include <mutex>
+
+#include "common.h"
+#include "pchain.h"
+
+namespace blvm {
+namespace {
+using namespace pchain;
+
+// a stepped pointer of a program: element (s, ...) at base + s * stride floats (|stride| < 2^31: checked on the host)
+struct SPtr {
+  float* base;
+  int stride;
+  __device__ __forceinline__ float* at(int s) const { return base + (long)s * stride; }
+};
+
+// A workgroup's tiles of one link, dealt by pchain.h's TileIter exactly as the interpreter deals them: lane k < kMaxTiles of the
+// returned value holds tile k as r0 | column tile << 16 (-1: none), so a tile costs one v_readlane in the step loop.
+constexpr int kMaxTiles = 8;
+__device__ __forceinline__ int tile_lanes(int w, int wg0, int nwg, int rt, int ct, bool xcd) {
+  TileIter it(w, wg0, nwg, rt, ct, xcd);
+  const int lane = threadIdx.x & 63;
+  it.j += lane * it.step;
+  return (lane < kMaxTiles && it.valid()) ? (it.r0() | (it.c() << 16)) : -1;
+}
+__device__ __forceinline__ int tile_count(int lanes) { return __popcll(__ballot(lanes >= 0)); }  // (the valid lanes are 0 .. n-1)
+
+// ---- gate: a linear-only chain ---------------------------------------------------------------------------------------------
+// x_{s+1} = relu(x_s W^T + b) as ONE K_LIN link per step (the program of blvm_pchain_chain_probe), K = 256 or 512 at compile time
+struct LinChainArgs {
+  SPtr a16, orm, o16;
+  const float *W, *bias;
+  int ldo, n16, B, s0, S, wg0, nwg, ct, xcd;
+  Ctl ctl;
+};
+
+template <int NW, int K>
+__global__ __launch_bounds__(NW * 64, 1) void static_lin_chain_kernel(LinChainArgs a) {
+  __shared__ __attribute__((aligned(16))) float red[2][NW * 256];
+  const int w = blockIdx.x, B = a.B;
+  const int tiles = tile_lanes(w, a.wg0, a.nwg, (B + 15) / 16, a.ct, a.xcd != 0);
+  const int nt = tile_count(tiles);
+  if (nt == 0) return;
+  Poll pl{a.ctl, 0u, false, 1};
+  int par = 0;
+  for (int s = a.s0; s < a.S; ++s) {
+    pl.code = (unsigned)s << 4;
+    const float* A = a.a16.at(s);
+    auto late = [&]() { return LinLate{a.bias, nullptr, nullptr, 0, 0, false, true, 0.f, Out{a.orm.at(s), a.ldo, false, a.o16.at(s), a.n16}}; };
+    for (int tk = 0; tk < nt; ++tk) {
+      const int trc = __builtin_amdgcn_readlane(tiles, tk);
+      tile_lin_late<NW, false>(A, 0, true, a.W, K, late, trc & 0xffff, (trc >> 16) * 16, B, red[par], pl);
+      par ^= 1;
+    }
+  }
+}
+
+// ---- the VRNN step programs (vrnn.hip), 16-row tiles, fp32, H = Z = 256, R = 512 ---------------------------------------------
+constexpr int kH = 256, kR = 512;
+
+// K_LIN (pchain.hip's pointer roles): the flags of a link are a template argument, everything else is data
+struct LinArgs {
+  SPtr a, a2, a3, add, gate, orm, o16, o16b;
+  const float *W, *bias;
+  int ld0, ld1, ld2, ld3, n16, n16b, w_width;
+  float slope;
+};
+// K_LINSEQ: a run of N links, link 0 of K0 and the others of K (pointer k of the descriptor: a0 = 0, add0 = 17, W 1+i, aux 5+i,
+// orm 9+i, o16 13+i)
+struct SeqArgs {
+  SPtr a0, add0, aux[4], orm[4], o16[4];
+  const float* W[4];
+  int ld[4], ldadd0, ldgate, n16;
+  float slope;
+};
+struct HeadArgs {
+  SPtr P, Q, eps, mu_p, sd_p, mu_q, sd_q, raw_p, raw_q, muq_raw, z, z16, z16b;
+  const float *Wp, *bp, *Wq, *bq;
+  int ld3, n16, n16b, Z, residual;
+  float beta, inv_beta, sd_eps;
+};
+struct GruArgs {
+  SPtr X, xg, gh, hprev, hrm, h16, h16b, rg, ug, ng;
+  const float *Wih, *bih;
+  int ld0, ld3, n16, n16b, R;
+};
+struct DzArgs {
+  SPtr D, D2, add, mu_q, sd_q, mu_p, sd_p, eps, raw_q, raw_p, muq_raw, dqh, dqh16, dph, dph16;
+  const float *WT, *WT2, *c_raw, *c_fn;
+  const int32_t* x_sl;
+  int ld1, ld3, n16, Z, residual, stride, t0, first_gemm;
+  float fn_floor, beta, sd_eps;
+};
+struct GrubArgs {
+  SPtr D0, D1, g_in, rg, ug, ng, gh, hprev, dd, dgi, dgi16, dgh, dgh16, ga, g_add;
+  const float *W0, *W1, *g_out;
+  int ld0, ld1, ld3, n16, R, first_gemm, end_gates, first_gin;
+};
+// where a link runs: its workgroup range and column tiles (the same TileIter deal as the interpreter), the steps it is active in,
+// and its index in the program (the abort code names it)
+struct Deal {
+  int wg0, nwg, ct, s_begin, s_end, idx;
+};
+
+// one visit = this workgroup's tiles of one link in one step.  `tiles`: tile_lanes of the link.  Every tile alternates the two
+// reduction scratch buffers as pchain_kernel does.
+struct Walk {
+  float* red0;
+  float* red1;
+  int par, B;
+  Poll pl;
+  __device__ __forceinline__ float* red() { par ^= 1; return par ? red0 : red1; }
+  __device__ __forceinline__ void at(const Deal& d, int s, bool gentle, unsigned li = 0) {
+    pl.nap = gentle ? 16 : 1;
+    pl.code = ((unsigned)s << 4) | (unsigned)d.idx | (li << 28);
+  }
+};
+
+template <int NW, int K, int FLAGS>
+__device__ __forceinline__ void visit_lin(const LinArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+  if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
+  constexpr bool sum3 = (FLAGS & DF_A_SUM3) != 0;
+  wk.at(d, s, (FLAGS & DF_GENTLE) != 0);
+  const float* A = q.a.at(s);
+  const float* A2 = sum3 ? q.a2.at(s) : nullptr;
+  const float* A3 = sum3 ? q.a3.at(s) : nullptr;
+  auto late = [&]() {
+    return LinLate{q.bias, q.add.at(s), q.gate.at(s), q.ld1, q.ld2, (FLAGS & DF_ADD_POLLED) != 0, (FLAGS & DF_RELU) != 0, q.slope,
+                   Out{q.orm.at(s), q.ld3, (FLAGS & DF_RM_SC1) != 0, q.o16.at(s), q.n16, q.o16b.at(s), q.n16b}};
+  };
+  for (int tk = 0; tk < nt; ++tk) {
+    const int trc = __builtin_amdgcn_readlane(tiles, tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
+    if constexpr ((FLAGS & DF_CANARY) != 0) canary_wait(A, tr0, K, wk.pl, q.ld0);
+    tile_lin_late<NW, false>(A, q.ld0, true, q.W, K, late, tr0, tc0, wk.B, wk.red(), wk.pl, A2, A3, q.w_width);
+  }
+}
+
+template <int NW, int N, int K0, int K, bool GATED>
+__device__ __forceinline__ void visit_run(const SeqArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+  if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
+  const float* A = q.a0.at(s);
+#pragma unroll
+  for (int li = 0; li < N; ++li) {
+    wk.at(d, s, false, (unsigned)li);
+    auto late = [&]() {
+      const float* aux = q.aux[li].at(s);
+      return LinLate{GATED ? nullptr : aux, li == 0 ? q.add0.at(s) : nullptr, GATED ? aux : nullptr, q.ldadd0, q.ldgate, false, !GATED, q.slope,
+                     Out{q.orm[li].at(s), q.ld[li], false, q.o16[li].at(s), q.n16}};
+    };
+    for (int tk = 0; tk < nt; ++tk) {
+      const int trc = __builtin_amdgcn_readlane(tiles, tk);
+      tile_lin_late<NW, false>(A, 0, true, q.W[li], li == 0 ? K0 : K, late, trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl);
+    }
+    A = q.o16[li].at(s);  // the next link multiplies what this one stored
+  }
+}
+
+template <int NW>
+__device__ __forceinline__ void visit_head(const HeadArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+  if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
+  wk.at(d, s, false);
+  const HeadOut o{q.mu_p.at(s), q.sd_p.at(s), q.mu_q.at(s), q.sd_q.at(s), q.raw_p.at(s), q.raw_q.at(s), q.muq_raw.at(s),
+                  Out{q.z.at(s), q.ld3, false, q.z16.at(s), q.n16, q.z16b.at(s), q.n16b}};
+  for (int tk = 0; tk < nt; ++tk) {
+    const int trc = __builtin_amdgcn_readlane(tiles, tk);
+    tile_head<NW, false>(q.P.at(s), q.Q.at(s), true, q.Wp, q.bp, q.Wq, q.bq, q.eps.at(s), o, kH, q.Z, q.residual, q.beta, q.inv_beta, q.sd_eps,
+                         trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl);
+  }
+}
+
+template <int NW>
+__device__ __forceinline__ void visit_gru(const GruArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+  if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
+  wk.at(d, s, false);
+  const Out o{q.hrm.at(s), q.ld3, true, q.h16.at(s), q.n16, q.h16b.at(s), q.n16b};
+  for (int tk = 0; tk < nt; ++tk) {
+    const int trc = __builtin_amdgcn_readlane(tiles, tk);
+    tile_gru<NW, false>(q.X.at(s), 0, true, q.Wih, kH, q.xg.at(s), q.bih, q.gh.at(s), q.hprev.at(s), q.ld0, q.R, o, q.rg.at(s), q.ug.at(s), q.ng.at(s),
+                        trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl);
+  }
+}
+
+template <int NW>
+__device__ __forceinline__ void visit_dz(const DzArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+  if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
+  wk.at(d, s, false);
+  DzIn z;
+  z.mu_q = q.mu_q.at(s); z.sd_q = q.sd_q.at(s); z.mu_p = q.mu_p.at(s); z.sd_p = q.sd_p.at(s); z.eps = q.eps.at(s); z.raw_q = q.raw_q.at(s);
+  z.raw_p = q.raw_p.at(s); z.muq_raw = q.muq_raw.at(s);
+  z.x_sl = q.x_sl; z.c_raw = q.c_raw; z.c_fn = q.c_fn;
+  z.t = q.t0 - s; z.stride = q.stride; z.residual = q.residual;
+  z.fn_floor = q.fn_floor; z.beta = q.beta; z.sd_eps = q.sd_eps;
+  z.has_gemm = s >= q.first_gemm;
+  const Out oq{q.dqh.at(s), q.ld3, false, q.dqh16.at(s), q.n16}, op{q.dph.at(s), q.ld3, false, q.dph16.at(s), q.n16};
+  for (int tk = 0; tk < nt; ++tk) {
+    const int trc = __builtin_amdgcn_readlane(tiles, tk);
+    tile_dz<NW, false>(q.D.at(s), q.WT, q.D2.at(s), q.WT2, true, q.add.at(s), q.ld1, false, z, oq, op, kH, q.Z, trc & 0xffff, (trc >> 16) * 16, wk.B,
+                       wk.red(), wk.pl);
+  }
+}
+
+template <int NW>
+__device__ __forceinline__ void visit_grub(const GrubArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+  if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
+  wk.at(d, s, false);
+  GrubIn g;
+  g.D0 = q.D0.at(s); g.D1 = q.D1.at(s); g.W0 = q.W0; g.W1 = q.W1; g.g_in = q.g_in.at(s); g.g_add = q.g_add.at(s); g.ld_gadd = q.ld1;
+  g.rg = q.rg.at(s); g.ug = q.ug.at(s); g.ng = q.ng.at(s); g.gh = q.gh.at(s); g.hprev = q.hprev.at(s); g.dd = q.dd.at(s); g.ldh = q.ld0;
+  g.dgi = Out{q.dgi.at(s), q.ld3, false, q.dgi16.at(s), q.n16};
+  g.dgh = Out{q.dgh.at(s), q.ld3, false, q.dgh16.at(s), q.n16};
+  g.ga = q.ga.at(s); g.g_out = const_cast<float*>(q.g_out);
+  g.has_gemm = s >= q.first_gemm; g.has_gates = s < q.end_gates; g.has_gin = s >= q.first_gin;
+  for (int tk = 0; tk < nt; ++tk) {
+    const int trc = __builtin_amdgcn_readlane(tiles, tk);
+    tile_grub<NW, false>(g, kH, q.R, trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl);
+  }
+}
+
+// The kernel's own argument block (offset 0 of the kernarg segment) through a pointer the compiler cannot see through: every visit
+// reads the fields it needs with s_load at its point of use.  Read through the by-value parameter instead, the compiler hoists every
+// pointer of a role's loop into SGPRs for the whole launch and, past 106 of them, parks them in VGPR lanes (forward 514 -> 34,
+// backward 797 -> 110 SGPR spills).
+template <class A>
+__device__ __forceinline__ const A& kargs() {
+  typedef const __attribute__((address_space(4))) char kchar;
+  kchar* p = (kchar*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const A*)p;
+}
+
+// Forward program (vrnn.hip vrnn_seq_fwd_impl, own range for the hidden projection): 0 hidden projection (gentle, K = R), 1 prior
+// run (K = R, H, H), 2 posterior run (the same with the x-part addend), 3 heads, 4 phi_z run of four, 5 GRU.
+struct FwdArgs {
+  LinArgs hproj;
+  SeqArgs run[2];  // prior, posterior
+  HeadArgs head;
+  SeqArgs phi;
+  GruArgs gru;
+  Deal deal[6];
+  int B, s0, S, xcd;
+  Ctl ctl;
+};
+constexpr int kFwdProducts = 4, kBwdProducts = 2;
+
+template <int NW>
+__global__ __launch_bounds__(NW * 64, 1) void vrnn_static_fwd_kernel(FwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds_red[];
+  const int w = blockIdx.x, rt = (a.B + 15) / 16;
+  const bool xcd = a.xcd != 0;
+  Walk wk{lds_red, lds_red + kFwdProducts * NW * 256, 0, a.B, Poll{a.ctl, 0u, false, 1}};
+  // roles, picked once: the gentle range runs the hidden projection alone; a prior or posterior workgroup runs its half's run of
+  // three and whatever tiles of the heads, the phi_z run and the GRU the deal gives it
+  if (w >= a.deal[0].wg0) {
+    const int t0 = tile_lanes(w, a.deal[0].wg0, a.deal[0].nwg, rt, a.deal[0].ct, xcd), n0 = tile_count(t0);
+    if (n0 == 0) return;
+    for (int s = a.s0; s < a.S; ++s) visit_lin<NW, kR, DF_RM_SC1 | DF_GENTLE | DF_CANARY>(kargs<FwdArgs>().hproj, kargs<FwdArgs>().deal[0], s, t0, n0, wk);
+    return;
+  }
+  const int t3 = tile_lanes(w, a.deal[3].wg0, a.deal[3].nwg, rt, a.deal[3].ct, xcd), n3 = tile_count(t3);
+  const int t4 = tile_lanes(w, a.deal[4].wg0, a.deal[4].nwg, rt, a.deal[4].ct, xcd), n4 = tile_count(t4);
+  const int t5 = tile_lanes(w, a.deal[5].wg0, a.deal[5].nwg, rt, a.deal[5].ct, xcd), n5 = tile_count(t5);
+  if (w < a.deal[2].wg0) {
+    const int t1 = tile_lanes(w, a.deal[1].wg0, a.deal[1].nwg, rt, a.deal[1].ct, xcd), n1 = tile_count(t1);
+    for (int s = a.s0; s < a.S; ++s) {
+      visit_run<NW, 3, kR, kH, false>(kargs<FwdArgs>().run[0], kargs<FwdArgs>().deal[1], s, t1, n1, wk);
+      visit_head<NW>(kargs<FwdArgs>().head, kargs<FwdArgs>().deal[3], s, t3, n3, wk);
+      visit_run<NW, 4, kH, kH, false>(kargs<FwdArgs>().phi, kargs<FwdArgs>().deal[4], s, t4, n4, wk);
+      visit_gru<NW>(kargs<FwdArgs>().gru, kargs<FwdArgs>().deal[5], s, t5, n5, wk);
+    }
+  } else {
+    const int t2 = tile_lanes(w, a.deal[2].wg0, a.deal[2].nwg, rt, a.deal[2].ct, xcd), n2 = tile_count(t2);
+    for (int s = a.s0; s < a.S; ++s) {
+      visit_run<NW, 3, kR, kH, false>(kargs<FwdArgs>().run[1], kargs<FwdArgs>().deal[2], s, t2, n2, wk);
+      visit_head<NW>(kargs<FwdArgs>().head, kargs<FwdArgs>().deal[3], s, t3, n3, wk);
+      visit_run<NW, 4, kH, kH, false>(kargs<FwdArgs>().phi, kargs<FwdArgs>().deal[4], s, t4, n4, wk);
+      visit_gru<NW>(kargs<FwdArgs>().gru, kargs<FwdArgs>().deal[5], s, t5, n5, wk);
+    }
+  }
+}
+
+// Backward program (vrnn.hip vrnn_seq_bwd_impl, split3 form): 0 GRU backward (steps 0 .. T'), 1 .. 3 the K = 3R dphi product as
+// three K = R partial-sum links (prior half | posterior half | spare range), 4 GB (gentle, K = 3R), 5 the summing link, 6 phi_z
+// run of two, 7 dz, 8 prior run (K = 2Z, H, H), 9 posterior run.
+struct BwdArgs {
+  GrubArgs grub;
+  LinArgs part[3], gb, sum;
+  SeqArgs phi;
+  DzArgs dz;
+  SeqArgs run[2];
+  Deal deal[10];
+  int B, s0, S, xcd;
+  Ctl ctl;
+};
+
+template <int NW>
+__global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds_red[];
+  const int w = blockIdx.x, rt = (a.B + 15) / 16;
+  const bool xcd = a.xcd != 0;
+  Walk wk{lds_red, lds_red + kBwdProducts * NW * 256, 0, a.B, Poll{a.ctl, 0u, false, 1}};
+  if (w >= a.deal[3].wg0) {  // spare range: the third partial sum alone
+    const int t = tile_lanes(w, a.deal[3].wg0, a.deal[3].nwg, rt, a.deal[3].ct, xcd), n = tile_count(t);
+    if (n == 0) return;
+    for (int s = a.s0; s < a.S; ++s) visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[2], kargs<BwdArgs>().deal[3], s, t, n, wk);
+    return;
+  }
+  if (w >= a.deal[4].wg0) {  // gentle range: GB alone
+    const int t = tile_lanes(w, a.deal[4].wg0, a.deal[4].nwg, rt, a.deal[4].ct, xcd), n = tile_count(t);
+    if (n == 0) return;
+    for (int s = a.s0; s < a.S; ++s) visit_lin<NW, 3 * kR, DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | DF_CANARY>(kargs<BwdArgs>().gb, kargs<BwdArgs>().deal[4], s, t, n, wk);
+    return;
+  }
+  const int t0 = tile_lanes(w, a.deal[0].wg0, a.deal[0].nwg, rt, a.deal[0].ct, xcd), n0 = tile_count(t0);
+  const int t5 = tile_lanes(w, a.deal[5].wg0, a.deal[5].nwg, rt, a.deal[5].ct, xcd), n5 = tile_count(t5);
+  const int t6 = tile_lanes(w, a.deal[6].wg0, a.deal[6].nwg, rt, a.deal[6].ct, xcd), n6 = tile_count(t6);
+  const int t7 = tile_lanes(w, a.deal[7].wg0, a.deal[7].nwg, rt, a.deal[7].ct, xcd), n7 = tile_count(t7);
+  if (w < a.deal[2].wg0) {  // prior half
+    const int t1 = tile_lanes(w, a.deal[1].wg0, a.deal[1].nwg, rt, a.deal[1].ct, xcd), n1 = tile_count(t1);
+    const int t8 = tile_lanes(w, a.deal[8].wg0, a.deal[8].nwg, rt, a.deal[8].ct, xcd), n8 = tile_count(t8);
+    for (int s = a.s0; s < a.S; ++s) {
+      visit_grub<NW>(kargs<BwdArgs>().grub, kargs<BwdArgs>().deal[0], s, t0, n0, wk);
+      visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[0], kargs<BwdArgs>().deal[1], s, t1, n1, wk);
+      visit_lin<NW, kH, DF_A_SUM3>(kargs<BwdArgs>().sum, kargs<BwdArgs>().deal[5], s, t5, n5, wk);
+      visit_run<NW, 2, kH, kH, true>(kargs<BwdArgs>().phi, kargs<BwdArgs>().deal[6], s, t6, n6, wk);
+      visit_dz<NW>(kargs<BwdArgs>().dz, kargs<BwdArgs>().deal[7], s, t7, n7, wk);
+      visit_run<NW, 3, 2 * kH, kH, true>(kargs<BwdArgs>().run[0], kargs<BwdArgs>().deal[8], s, t8, n8, wk);
+    }
+  } else {  // posterior half
+    const int t2 = tile_lanes(w, a.deal[2].wg0, a.deal[2].nwg, rt, a.deal[2].ct, xcd), n2 = tile_count(t2);
+    const int t9 = tile_lanes(w, a.deal[9].wg0, a.deal[9].nwg, rt, a.deal[9].ct, xcd), n9 = tile_count(t9);
+    for (int s = a.s0; s < a.S; ++s) {
+      visit_grub<NW>(kargs<BwdArgs>().grub, kargs<BwdArgs>().deal[0], s, t0, n0, wk);
+      visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[1], kargs<BwdArgs>().deal[2], s, t2, n2, wk);
+      visit_lin<NW, kH, DF_A_SUM3>(kargs<BwdArgs>().sum, kargs<BwdArgs>().deal[5], s, t5, n5, wk);
+      visit_run<NW, 2, kH, kH, true>(kargs<BwdArgs>().phi, kargs<BwdArgs>().deal[6], s, t6, n6, wk);
+      visit_dz<NW>(kargs<BwdArgs>().dz, kargs<BwdArgs>().deal[7], s, t7, n7, wk);
+      visit_run<NW, 3, 2 * kH, kH, true>(kargs<BwdArgs>().run[1], kargs<BwdArgs>().deal[9], s, t9, n9, wk);
+    }
+  }
+}
+
+// the program's pointer k of descriptor d as a stepped pointer
+bool int_strides(const Program& p) {  // SPtr keeps 32-bit strides
+  for (long v : p.stride)
+    if (v < -2147483647L || v > 2147483647L) return false;
+  return true;
+}
+SPtr sptr(const Program& p, const Desc& d, int k) { return SPtr{const_cast<float*>(d.p[k]), (int)p.stride[d.sidx[k]]}; }
+
+// every workgroup of `grid` resident at once (one 16-wave workgroup per CU with `lds` bytes of dynamic LDS), as pchain_launch
+// checks it; the dynamic-LDS limit is raised once per process and device.  slot: 0 forward, 1 backward, 2 the probe's chain
+template <class Kern>
+int static_go(Kern kernel, int slot, int grid, size_t lds, const char* what) {
+  static std::mutex mu;
+  static int attr_dev[3] = {-1, -1, -1}, occ[3] = {0, 0, 0};
+  int dev = 0, cus = 0;
+  BLVM_HIP(hipGetDevice(&dev));
+  BLVM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    if (attr_dev[slot] != dev) {
+      BLVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      BLVM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[slot], kernel, 1024, lds));
+      attr_dev[slot] = dev;
+    }
+    BLVM_REQUIRE((long)occ[slot] * cus >= grid, "%s: %d workgroups are not co-resident (%d per CU x %d CUs)", what, grid, occ[slot], cus);
+  }
+  return BLVM_OK;
+}
+
+// 1: the program is not the linear chain the static kernel was compiled for
+int static_lin_chain_launch(const Program& p, hipStream_t stream) {
+  if (p.ndesc != 1 || p.bf16 || p.rt_group != 1 || !int_strides(p)) return 1;
+  const Desc& d = p.d[0];
+  if (d.kind != K_LIN || d.flags != DF_RELU || d.f[0] != 0.f || (d.K != 256 && d.K != 512) || d.s_begin != 0 || d.s_end != p.S) return 1;
+  if (d.ld[0] != 0 || d.i[0] != 0 || d.p[3] || d.p[4] || d.p[7] || d.p[8] || d.p[9] || d.n16[1] != 0) return 1;
+  const int rt = (p.B + 15) / 16;
+  if (p.xcd ? (((d.ct + 7) / 8) * rt + d.nwg / 8 - 1) / (d.nwg / 8) > kMaxTiles : (d.ct * rt + d.nwg - 1) / d.nwg > kMaxTiles) return 1;
+  LinChainArgs a{sptr(p, d, 0), sptr(p, d, 5), sptr(p, d, 6), d.p[1], d.p[2], d.ld[3], d.n16[0], p.B, p.s_first, p.S, d.wg0, d.nwg, d.ct, p.xcd, p.ctl};
+  const int grid = d.wg0 + d.nwg;
+  auto go = [&](auto kernel) -> int {
+    const int rc = static_go(kernel, 2, grid, 0, "static_lin_chain");
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), 0, stream, a);
+    BLVM_CHECK_LAUNCH("static_lin_chain");
+    return BLVM_OK;
+  };
+  return d.K == 256 ? go(&static_lin_chain_kernel<16, 256>) : go(&static_lin_chain_kernel<16, 512>);
+}
+
+// the selector between the static walk and the interpreter for the VRNN programs (blvm_pchain_static)
+int g_static = 1;
+long g_static_launches = 0;  // VRNN programs launched on the static kernels (blvm_pchain_static(-2))
+bool pchain_static_on() { return g_static != 0; }
+
+// ---- host: the interpreter's program -> the static kernels' arguments -------------------------------------------------------
+SPtr sp(const Program& p, const Desc& d, int k) { return SPtr{const_cast<float*>(d.p[k]), d.p[k] ? (int)p.stride[d.sidx[k]] : 0}; }
+Deal deal_of(const Desc& d, int idx) { return Deal{d.wg0, d.nwg, d.ct, d.s_begin, d.s_end, idx}; }
+bool within(const Desc& d, int lo, int hi) { return d.wg0 >= lo && d.wg0 + d.nwg <= hi; }
+bool few_tiles(const Program& p, const Desc& d) {  // at most kMaxTiles tiles of the link per workgroup (pchain_launch's count)
+  const int rt = (p.B + 15) / 16;
+  if (d.nwg <= 0 || (p.xcd && d.nwg % 8 != 0)) return false;
+  const int per_wg = p.xcd ? (((d.ct + 7) / 8) * rt + d.nwg / 8 - 1) / (d.nwg / 8) : (d.ct * rt + d.nwg - 1) / d.nwg;
+  return per_wg <= kMaxTiles;
+}
+bool shaped(const Desc& d, int kind, int flags, int K) { return d.kind == kind && d.flags == flags && d.K == K; }
+
+LinArgs lin_args(const Program& p, const Desc& d) {
+  return LinArgs{sp(p, d, 0), sp(p, d, 8), sp(p, d, 9), sp(p, d, 3), sp(p, d, 4), sp(p, d, 5), sp(p, d, 6), sp(p, d, 7), d.p[1], d.p[2],
+                 d.ld[0], d.ld[1], d.ld[2], d.ld[3], d.n16[0], d.n16[1], d.i[0], d.f[0]};
+}
+SeqArgs seq_args(const Program& p, const Desc& d) {
+  SeqArgs q{};
+  q.a0 = sp(p, d, 0); q.add0 = sp(p, d, 17);
+  for (int i = 0; i < d.i[1]; ++i) {
+    q.W[i] = d.p[1 + i]; q.aux[i] = sp(p, d, 5 + i); q.orm[i] = sp(p, d, 9 + i); q.o16[i] = sp(p, d, 13 + i); q.ld[i] = d.ld[i];
+  }
+  q.ldadd0 = d.i[0]; q.ldgate = d.i[2]; q.n16 = d.n16[0]; q.slope = d.f[0];
+  return q;
+}
+
+// 1: not the shape the static kernels were compiled for (the caller runs pchain_launch)
+int vrnn_static_check(const Program& p, int ndesc, int products) {
+  if (!pchain_static_on() || p.ndesc != ndesc || p.bf16 || p.rt_group != 1 || p.s_first != 0 || p.B > 64) return 1;
+  if (p.lds_products != products || !int_strides(p)) return 1;  // (the kernels' reduction scratch is sized for `products`)
+  for (int i = 0; i < p.ndesc; ++i)
+    if (!few_tiles(p, p.d[i])) return 1;
+  return 0;
+}
+
+int vrnn_static_fwd(const Program& p, hipStream_t stream) {
+  if (vrnn_static_check(p, 6, kFwdProducts)) return 1;
+  const Desc* d = p.d;
+  const int S = p.S;
+  for (int i = 0; i < 6; ++i)
+    if (d[i].s_begin != 0 || d[i].s_end != S) return 1;
+  if (!shaped(d[0], K_LIN, DF_RM_SC1 | DF_GENTLE | DF_CANARY, kR) || !shaped(d[1], K_LINSEQ, DF_RELU, kH) || !shaped(d[2], K_LINSEQ, DF_RELU, kH) ||
+      !shaped(d[3], K_HEAD, 0, kH) || !shaped(d[4], K_LINSEQ, DF_RELU, kH) || !shaped(d[5], K_GRU, 0, kH))
+    return 1;
+  if (d[1].i[1] != 3 || d[1].i[3] != kR || d[2].i[1] != 3 || d[2].i[3] != kR || d[4].i[1] != 4 || d[4].i[3] != 0) return 1;
+  // roles: prior half [0, d1 end) | posterior half [d2.wg0, d0.wg0) | gentle range [d0.wg0, ...): nothing else there
+  const int half = d[2].wg0, gentle = d[0].wg0;
+  if (d[1].wg0 != 0 || !within(d[1], 0, half) || !within(d[2], half, gentle) || d[0].nwg <= 0) return 1;
+  for (int i = 3; i < 6; ++i)
+    if (!within(d[i], 0, gentle)) return 1;
+  FwdArgs a{};
+  a.hproj = lin_args(p, d[0]);
+  a.run[0] = seq_args(p, d[1]); a.run[1] = seq_args(p, d[2]); a.phi = seq_args(p, d[4]);
+  a.head = HeadArgs{sp(p, d[3], 0), sp(p, d[3], 1), sp(p, d[3], 6), sp(p, d[3], 7), sp(p, d[3], 8), sp(p, d[3], 9), sp(p, d[3], 10), sp(p, d[3], 11),
+                    sp(p, d[3], 12), sp(p, d[3], 13), sp(p, d[3], 14), sp(p, d[3], 15), sp(p, d[3], 16), d[3].p[2], d[3].p[3], d[3].p[4], d[3].p[5],
+                    d[3].ld[3], d[3].n16[0], d[3].n16[1], d[3].i[0], d[3].i[1], d[3].f[0], d[3].f[1], d[3].f[2]};
+  a.gru = GruArgs{sp(p, d[5], 0), sp(p, d[5], 2), sp(p, d[5], 3), sp(p, d[5], 4), sp(p, d[5], 5), sp(p, d[5], 6), sp(p, d[5], 11), sp(p, d[5], 7),
+                  sp(p, d[5], 8), sp(p, d[5], 9), d[5].p[1], d[5].p[10], d[5].ld[0], d[5].ld[3], d[5].n16[0], d[5].n16[1], d[5].i[0]};
+  int grid = 0;
+  for (int i = 0; i < 6; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
+  a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.ctl = p.ctl;
+  const size_t lds = sizeof(float) * 2 * kFwdProducts * 16 * 256;
+  const int rc = static_go(&vrnn_static_fwd_kernel<16>, 0, grid, lds, "vrnn_static_fwd");
+  if (rc) return rc;
+  hipLaunchKernelGGL(vrnn_static_fwd_kernel<16>, dim3(grid), dim3(1024), lds, stream, a);
+  BLVM_CHECK_LAUNCH("vrnn_static_fwd");
+  ++g_static_launches;
+  return BLVM_OK;
+}
+
+int vrnn_static_bwd(const Program& p, hipStream_t stream) {
+  if (vrnn_static_check(p, 10, kBwdProducts)) return 1;
+  const Desc* d = p.d;
+  const int S = p.S;  // T' + 1
+  for (int i = 0; i < 10; ++i)
+    if (d[i].s_begin != 0 || d[i].s_end != (i == 0 ? S : S - 1)) return 1;
+  if (!shaped(d[0], K_GRUB, 0, kH) || !shaped(d[1], K_LIN, 0, kR) || !shaped(d[2], K_LIN, 0, kR) || !shaped(d[3], K_LIN, 0, kR) ||
+      !shaped(d[4], K_LIN, DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | DF_CANARY, 3 * kR) || !shaped(d[5], K_LIN, DF_A_SUM3, kH) ||
+      !shaped(d[6], K_LINSEQ, DF_SEQ_GATE, kH) || !shaped(d[7], K_DZ, 0, kH) || !shaped(d[8], K_LINSEQ, DF_SEQ_GATE, kH) ||
+      !shaped(d[9], K_LINSEQ, DF_SEQ_GATE, kH))
+    return 1;
+  if (d[6].i[1] != 2 || d[6].i[3] != 0 || d[8].i[1] != 3 || d[8].i[3] != 2 * kH || d[9].i[1] != 3 || d[9].i[3] != 2 * kH) return 1;
+  // roles: prior half [0, d2.wg0) | posterior half [d2.wg0, d4.wg0) | gentle range (GB) [d4.wg0, d3.wg0) | spare range [d3.wg0, ...)
+  const int half = d[2].wg0, gentle = d[4].wg0, spare = d[3].wg0;
+  if (!within(d[1], 0, half) || !within(d[8], 0, half) || !within(d[2], half, gentle) || !within(d[9], half, gentle) || !within(d[4], gentle, spare) ||
+      d[3].nwg <= 0)
+    return 1;
+  for (int i : {0, 5, 6, 7})
+    if (!within(d[i], 0, gentle)) return 1;
+  BwdArgs a{};
+  a.grub = GrubArgs{sp(p, d[0], 0), sp(p, d[0], 1), sp(p, d[0], 4), sp(p, d[0], 5), sp(p, d[0], 6), sp(p, d[0], 7), sp(p, d[0], 8), sp(p, d[0], 9),
+                    sp(p, d[0], 10), sp(p, d[0], 11), sp(p, d[0], 12), sp(p, d[0], 13), sp(p, d[0], 14), sp(p, d[0], 15), sp(p, d[0], 17),
+                    d[0].p[2], d[0].p[3], d[0].p[16], d[0].ld[0], d[0].ld[1], d[0].ld[3], d[0].n16[0], d[0].i[0], d[0].i[1], d[0].i[2], d[0].i[3]};
+  for (int k = 0; k < 3; ++k) a.part[k] = lin_args(p, d[1 + k]);
+  a.gb = lin_args(p, d[4]); a.sum = lin_args(p, d[5]);
+  a.phi = seq_args(p, d[6]); a.run[0] = seq_args(p, d[8]); a.run[1] = seq_args(p, d[9]);
+  const Desc& z = d[7];
+  a.dz = DzArgs{sp(p, z, 0), sp(p, z, 2), sp(p, z, 4), sp(p, z, 5), sp(p, z, 6), sp(p, z, 7), sp(p, z, 8), sp(p, z, 9), sp(p, z, 10), sp(p, z, 11),
+                sp(p, z, 12), sp(p, z, 16), sp(p, z, 17), sp(p, z, 18), sp(p, z, 19), z.p[1], z.p[3], z.p[14], z.p[15],
+                reinterpret_cast<const int32_t*>(z.p[13]), z.ld[1], z.ld[3], z.n16[0], z.i[0], z.i[1], z.i[2], z.i[3], (int)z.f[3], z.f[0], z.f[1], z.f[2]};
+  int grid = 0;
+  for (int i = 0; i < 10; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
+  a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.ctl = p.ctl;
+  const size_t lds = sizeof(float) * 2 * kBwdProducts * 16 * 256;
+  const int rc = static_go(&vrnn_static_bwd_kernel<16>, 1, grid, lds, "vrnn_static_bwd");
+  if (rc) return rc;
+  hipLaunchKernelGGL(vrnn_static_bwd_kernel<16>, dim3(grid), dim3(1024), lds, stream, a);
+  BLVM_CHECK_LAUNCH("vrnn_static_bwd");
+  ++g_static_launches;
+  return BLVM_OK;
+}
+
+}  // namespace
+
+int vrnn_static_launch(const pchain::Program& prog, bool forward, hipStream_t stream) {
+  return forward ? vrnn_static_fwd(prog, stream) : vrnn_static_bwd(prog, stream);
+}
+
+}  // namespace blvm
+
+extern "C" int blvm_pchain_static(int mode) {
+  if (mode == -2) return (int)std::min<long>(blvm::g_static_launches, 0x7fffffffL);
+  const int was = blvm::g_static;
+  if (mode >= 0) blvm::g_static = mode != 0;
+  return was;
+}
+
+// blvm_pchain_chain_probe's chain (one K_LIN descriptor per link, the same Builder program) walked by the static kernel.  N = 256 or 512.
+extern "C" int blvm_pchain_static_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream_) {
+  using namespace blvm;
+  using namespace blvm::pchain;
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  BLVM_REQUIRE(W16 && bias && x16 && xs && B > 0 && N > 0 && N % 16 == 0 && L > 0, "pchain_static_chain_probe: bad arguments");
+  const int rt = (B + 15) / 16;
+  const long x = (long)rt * 16 * N, sN = (long)B * N;
+  Builder bld;
+  bld.p.S = L; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 1;
+  const int nw = nwg > 0 ? nwg : range_for((N / 16) * rt, device_cus() & ~7);
+  Desc& d = bld.add(K_LIN, N / 16, 0, nw, N, DF_RELU, 0, L);
+  bld.ptr(d, 0, x16, x); bld.ptr(d, 1, W16); bld.ptr(d, 2, bias); bld.ptr(d, 5, xs, sN); bld.ptr(d, 6, x16 + x, x);
+  d.ld[3] = N; d.n16[0] = N / 16; d.f[0] = 0.f;
+  int rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
+  if (rc) return rc;
+  BLVM_HIP(pchain_fill_sentinel(x16 + x, sizeof(float) * (size_t)x * L, s));
+  rc = static_lin_chain_launch(bld.p, s);
+  BLVM_REQUIRE(rc != 1, "pchain_static_chain_probe: no static kernel for N = %d (256, 512) or this deal", N);
+  return rc;
+}

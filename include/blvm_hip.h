@@ -66,11 +66,19 @@ int blvm_pchain_profile(unsigned long long* device_buffer);
  * column tile's row tiles on one XCD, so every XCD's L2 holds 1/8 of each weight matrix), 16 one-word canary poll in front of the
  * operand polls of tiles off the critical path. */
 int blvm_pchain_tune(int bits);
+/* The VRNN forward / backward programs at B <= 64 (16-row tiles, fp32, H = Z = 256, R = 512) run on static-walk kernels whose walk is
+ * fixed at compile time (mode 1, the default; bit-identical results); mode 0 sends them to the program interpreter, a negative
+ * mode only queries.  Returns the mode in effect before the call; mode -2 returns instead how many VRNN programs the process has
+ * launched on the static kernels so far. */
+int blvm_pchain_static(int mode);
 /* Diagnostics / unit test of the persistent-chain engine on its own: L dependent links x_{s+1} = relu(x_s W^T + b), [B,N] x [N,N],
  * as ONE launch.  W16: W [N,N] in the T16 operand layout (blvm_pchain_rows_to_t16 of W: a weight's rows are the "batch");
  * x16: L+1 T16 slabs of ceil(B/16)*16 x N floats, slab 0 = x_0 in T16 (blvm_pchain_rows_to_t16); xs: L row-major [B,N] outputs.
  * nwg: workgroups (0: one per tile, at most one per CU). */
 int blvm_pchain_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream);
+/* The same chain walked by the static-walk kernel (vrnn_static.hip: kinds, flags and K fixed at compile time, pointers and strides
+ * from kernel arguments).  N = 256 or 512. */
+int blvm_pchain_static_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream);
 /* dst = T16 operand copy [ceil(B/16)*16, K] of the rows of src [B,K] (row stride ld). */
 int blvm_pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, void* stream);
 /* n host integers -> device memory through kernel arguments (asynchronous on `stream`; a pageable hipMemcpy would block the host
