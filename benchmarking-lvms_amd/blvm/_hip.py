@@ -231,20 +231,25 @@ def check_async(what: str = "a persistent recurrent launch", group=None):
         )
 
 
-DTYPES = {"f32": 0, "bf16": 1}
+DTYPES = {"f32": 0, "bf16": 1, "f16": 2}  # BLVM_DTYPE_F32 / _BF16 / _F16 (include/blvm_hip.h)
 
 
 def set_operand_dtype(name: str):
-    """Operand type of the matrix products: "f32" (default) or "bf16" (bf16 operands, fp32 accumulation, for the persistent
-    recurrent chains and the K6 GEMMs) — what the reference's `--use_amp True` selects with torch.autocast
-    (`experiments/experiment_vrnn_audio.py:219-230`).  Process-wide."""
+    """Operand type of the matrix products: "f32" (default), "bf16" or "f16" (16-bit operands rounded to nearest even, fp32
+    accumulation, for the persistent recurrent chains, the sequence and WaveNet block kernels and the K6 GEMMs) — what the reference's
+    `--use_amp True` selects with torch.autocast (`experiments/experiment_vrnn_audio.py:219-230`; autocast's type is fp16, whose
+    gradients need loss scaling: torch.amp.GradScaler).  Process-wide."""
     if name not in DTYPES:
         raise ValueError(f"operand dtype {name!r}: one of {sorted(DTYPES)}")
     check(load().blvm_set_operand_dtype(DTYPES[name]), "blvm_set_operand_dtype")
 
 
 def get_operand_dtype() -> str:
-    return "bf16" if load().blvm_get_operand_dtype() == 1 else "f32"
+    v = load().blvm_get_operand_dtype()
+    for name, code in DTYPES.items():
+        if code == v:
+            return name
+    raise BlvmHipError(f"blvm_get_operand_dtype: unknown operand type {v}")
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)

@@ -321,7 +321,7 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
 int colsum_f32(int M, int N, const float* X, int ldx, float* out, int accumulate, hipStream_t stream);
 // Weight gradients of one reduction length as ONE launch (gemm.hip gemm_group_kernel): dW[M,N] += D^T[M,K] Act[K,N] and, with db,
 // db[M] += column sums of D, for every job with dW (a job without dW only sums its columns).  Falls back to one gemm_f32 per job
-// for bf16 operands, short reductions or more than 20 jobs (env BLVM_WGRAD_GROUP=0: always).
+// for 16-bit operands, short reductions or more than 20 jobs (env BLVM_WGRAD_GROUP=0: always).
 struct WgradJob {
   const float* D; int ldd, M;
   const float* Act; int lda, N;
@@ -330,20 +330,24 @@ struct WgradJob {
 };
 int gemm_wgrad_group(const WgradJob* jobs, int njobs, int K, hipStream_t stream);
 int transpose_f32(int M, int N, const float* X, int ldx, float* out, int ldo, hipStream_t stream);
-// Operand type of the matrix products (core.hip; blvm_set_operand_dtype / env BLVM_DTYPE=bf16): false = fp32 (the default), true =
-// bf16 operands with fp32 accumulation for the persistent chains and K6 — the reference's `--use_amp True` regime
-// (experiments/experiment_vrnn_audio.py:219-230).  Everything stored, every epilogue and every reduction stays fp32.
-bool operand_bf16();
+// Operand type of the matrix products (core.hip; blvm_set_operand_dtype / env BLVM_DTYPE=bf16|f16; values = BLVM_DTYPE_*): OP_F32
+// (the default); OP_BF16 / OP_F16: operands rounded to bf16 / fp16 (nearest even) with fp32 accumulation for the persistent chains,
+// the sequence kernels, the WaveNet block kernels and K6 — the reference's `--use_amp True` regime (experiments/
+// experiment_vrnn_audio.py:219-230; fp16 is its autocast type).  Everything stored, every epilogue and every reduction stays fp32.
+enum OpType { OP_F32 = 0, OP_BF16 = 1, OP_F16 = 2 };
+OpType operand_type();
+inline bool operand_16bit() { return operand_type() != OP_F32; }  // 16-bit operand packs (either type)
 // While one is alive on this thread, t16_pack() calls on `stream` are collected and launched TOGETHER by flush() (or at the scope's
-// end); bf16 = true: the packs are written as bf16 elements (the first half of each dst).
+// end); ot != OP_F32: the packs are written as 16-bit elements of that type (the first half of each dst).
 struct T16PackScope {
-  T16PackScope(bool bf16, hipStream_t stream);
+  T16PackScope(OpType ot, hipStream_t stream);
   ~T16PackScope();
   int flush();
   T16PackScope(const T16PackScope&) = delete;
   T16PackScope& operator=(const T16PackScope&) = delete;
  private:
-  bool prev_, prev_active_;
+  OpType prev_;
+  bool prev_active_;
 };
 // dst = T16 operand layout (see wave_gemm16) of the [R,K] matrix M[r][k] = src[r * rs + k * cs]; R, K multiples of 16.
 int t16_pack(const float* src, long rs, long cs, int R, int K, float* dst, hipStream_t stream);

@@ -84,13 +84,17 @@ int pchain_max_batch() {
   }
   return g_pchain_max_b;
 }
+static_assert(OP_F32 == BLVM_DTYPE_F32 && OP_BF16 == BLVM_DTYPE_BF16 && OP_F16 == BLVM_DTYPE_F16, "operand types are the ABI values");
 static int g_operand_dtype = -1;
-bool operand_bf16() {
+OpType operand_type() {
   if (g_operand_dtype < 0) {
     const char* e = getenv("BLVM_DTYPE");
-    g_operand_dtype = (e && (strcmp(e, "bf16") == 0 || strcmp(e, "1") == 0)) ? 1 : 0;
+    g_operand_dtype = !e ? OP_F32
+                      : (strcmp(e, "bf16") == 0 || strcmp(e, "1") == 0) ? OP_BF16
+                      : (strcmp(e, "f16") == 0 || strcmp(e, "2") == 0)  ? OP_F16
+                                                                          : OP_F32;
   }
-  return g_operand_dtype == 1;
+  return static_cast<OpType>(g_operand_dtype);
 }
 int pchain_tune() {
   if (g_pchain_tune < 0) {
@@ -133,14 +137,14 @@ extern "C" int blvm_pchain_configure(int max_batch, int waves) {
 }
 
 extern "C" int blvm_set_operand_dtype(int dtype) {
-  if (dtype != BLVM_DTYPE_F32 && dtype != BLVM_DTYPE_BF16) {
-    blvm::set_error("blvm_set_operand_dtype: %d is neither BLVM_DTYPE_F32 nor BLVM_DTYPE_BF16", dtype);
+  if (dtype != BLVM_DTYPE_F32 && dtype != BLVM_DTYPE_BF16 && dtype != BLVM_DTYPE_F16) {
+    blvm::set_error("blvm_set_operand_dtype: %d is none of BLVM_DTYPE_F32 (0), BLVM_DTYPE_BF16 (1), BLVM_DTYPE_F16 (2)", dtype);
     return BLVM_EINVAL;
   }
   blvm::g_operand_dtype = dtype;
   return BLVM_OK;
 }
-extern "C" int blvm_get_operand_dtype(void) { return blvm::operand_bf16() ? BLVM_DTYPE_BF16 : BLVM_DTYPE_F32; }
+extern "C" int blvm_get_operand_dtype(void) { return blvm::operand_type(); }
 
 extern "C" int blvm_pchain_max_batch(void) { return std::min(blvm::pchain_max_batch(), 128); }
 

@@ -251,19 +251,25 @@ __global__ __launch_bounds__(256) void gemm_group_kernel(GemmGroup gg) {
   gemm_tile<64, 64, 1, 1>(g, t % tiles_n, t / tiles_n, bz, gg.split);
 }
 
-// ---- bf16-operand variant (operand_bf16(): the reference's --use_amp regime) -----------------------------------------------------
-// Same tiling, arguments and epilogue; the global -> LDS stage rounds both operands to bf16 (nearest even) and lays them out
-// k-group-major — element (m, k) at ((k / 8) * LD + m) * 8 + k % 8 — so that the 8 consecutive k a lane feeds
-// v_mfma_f32_32x32x16_bf16 (gfx950's full-rate form) are one ds_read_b128.  BK = 32: two MFMAs per 32x32 tile and staged k-tile
-// (16x the fp32 pipe's rate, so this kernel is bound by the operand stream: what it buys is the matrix pipe's time).
-// Accumulation and epilogue are fp32.
+// ---- 16-bit operand variant (operand_type() OP_BF16 / OP_F16: the reference's --use_amp regime) ----------------------------------
+// Same tiling, arguments and epilogue; the global -> LDS stage rounds both operands to bf16 / fp16 (OT; nearest even) and lays them
+// out k-group-major — element (m, k) at ((k / 8) * LD + m) * 8 + k % 8 — so that the 8 consecutive k a lane feeds
+// v_mfma_f32_32x32x16_bf16 / _f16 (gfx950's full-rate forms, same cycles) are one ds_read_b128.  BK = 32: two MFMAs per 32x32 tile
+// and staged k-tile (16x the fp32 pipe's rate, so this kernel is bound by the operand stream: what it buys is the matrix pipe's
+// time).  Accumulation and epilogue are fp32.
 constexpr int BKB = 32;
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef float f2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk2(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_convertvector((f2_t){a, b}, b2_t)); }
+typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+template <int OT>  // v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 (nearest even; fp16: |x| >= 65520 -> inf, as torch's .half())
+__device__ __forceinline__ unsigned pk2(float a, float b) {
+  if constexpr (OT == OP_F16) return __builtin_bit_cast(unsigned, __builtin_convertvector((f2_t){a, b}, h2_t));
+  else return __builtin_bit_cast(unsigned, __builtin_convertvector((f2_t){a, b}, b2_t));
+}
 
-template <int BM, int BN, int OPA, int OPB>
+template <int BM, int BN, int OPA, int OPB, int OT>
 __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs g) {
   constexpr int LDA_S = BM + PAD, LDB_S = BN + PAD;
   constexpr int TM = BM / 64, TN = BN / 64;
@@ -318,16 +324,16 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs g) {
         const int id = tid + v * 256;
         const int m = id / KVB, k4 = (id % KVB) * 4;
         uint2 q;
-        q.x = pk2(r[v].x, r[v].y); q.y = pk2(r[v].z, r[v].w);
+        q.x = pk2<OT>(r[v].x, r[v].y); q.y = pk2<OT>(r[v].z, r[v].w);
         *reinterpret_cast<uint2*>(&S[((k4 >> 3) * LD + m) * 8 + (k4 & 7)]) = q;
       } else if ((v & 1) == 0) {
         const int id = tid + (v >> 1) * 256;
         const int k = 2 * (id / (BT / 4)), m4 = (id % (BT / 4)) * 4;
         unsigned short* d = &S[((k >> 3) * LD + m4) * 8 + (k & 7)];
-        *reinterpret_cast<unsigned*>(d + 0) = pk2(r[v].x, r[v + 1].x);
-        *reinterpret_cast<unsigned*>(d + 8) = pk2(r[v].y, r[v + 1].y);
-        *reinterpret_cast<unsigned*>(d + 16) = pk2(r[v].z, r[v + 1].z);
-        *reinterpret_cast<unsigned*>(d + 24) = pk2(r[v].w, r[v + 1].w);
+        *reinterpret_cast<unsigned*>(d + 0) = pk2<OT>(r[v].x, r[v + 1].x);
+        *reinterpret_cast<unsigned*>(d + 8) = pk2<OT>(r[v].y, r[v + 1].y);
+        *reinterpret_cast<unsigned*>(d + 16) = pk2<OT>(r[v].z, r[v + 1].z);
+        *reinterpret_cast<unsigned*>(d + 24) = pk2<OT>(r[v].w, r[v + 1].w);
       }
     }
   };
@@ -359,7 +365,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs g) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < TN; ++j) {
+          if constexpr (OT == OP_F16)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[i]), __builtin_bit_cast(f16x8_t, b[j]), acc[i][j], 0, 0, 0);
+          else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
     }
   }
 
@@ -387,15 +397,18 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs g) {
     }
 }
 
+template <int BM, int BN, int OT>
+void launch_gemm16(const GemmArgs& g, int op_a, int op_b, dim3 grid, hipStream_t s) {
+  if (op_a == 0 && op_b == 0) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 0, 0, OT>), grid, dim3(256), 0, s, g);
+  else if (op_a == 0 && op_b == 1) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 0, 1, OT>), grid, dim3(256), 0, s, g);
+  else if (op_a == 1 && op_b == 0) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 1, 0, OT>), grid, dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 1, 1, OT>), grid, dim3(256), 0, s, g);
+}
+
 template <int BM, int BN>
-void launch_gemm(const GemmArgs& g, int op_a, int op_b, dim3 grid, hipStream_t s, bool bf16) {
-  if (bf16) {
-    if (op_a == 0 && op_b == 0) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 0, 0>), grid, dim3(256), 0, s, g);
-    else if (op_a == 0 && op_b == 1) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 0, 1>), grid, dim3(256), 0, s, g);
-    else if (op_a == 1 && op_b == 0) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 1, 0>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 1, 1>), grid, dim3(256), 0, s, g);
-    return;
-  }
+void launch_gemm(const GemmArgs& g, int op_a, int op_b, dim3 grid, hipStream_t s, OpType ot) {
+  if (ot == OP_BF16) return launch_gemm16<BM, BN, OP_BF16>(g, op_a, op_b, grid, s);
+  if (ot == OP_F16) return launch_gemm16<BM, BN, OP_F16>(g, op_a, op_b, grid, s);
   if (op_a == 0 && op_b == 0) hipLaunchKernelGGL((gemm_kernel<BM, BN, 0, 0>), grid, dim3(256), 0, s, g);
   else if (op_a == 0 && op_b == 1) hipLaunchKernelGGL((gemm_kernel<BM, BN, 0, 1>), grid, dim3(256), 0, s, g);
   else if (op_a == 1 && op_b == 0) hipLaunchKernelGGL((gemm_kernel<BM, BN, 1, 0>), grid, dim3(256), 0, s, g);
@@ -506,9 +519,9 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
   // dgrad unchanged, the VRNN step within noise: not worth a fourth tile shape)
   const int bm = big ? (m192 ? 192 : 128) : 64;
   const int bn = big ? (n192 ? 192 : 128) : 64;
-  const bool bf16 = operand_bf16();
-  const int bk = bf16 ? BKB : tile_bk(bm, bn);
-  if (colsum != nullptr && (bf16 || op_a != 1 || K == 0)) {  // (the bf16 kernel stages ROUNDED operands: the bias gradient stays an fp32 sum)
+  const OpType ot = operand_type();
+  const int bk = ot != OP_F32 ? BKB : tile_bk(bm, bn);
+  if (colsum != nullptr && (ot != OP_F32 || op_a != 1 || K == 0)) {  // (the 16-bit kernel stages ROUNDED operands: the bias gradient stays an fp32 sum)
     const int rc = op_a == 1 ? colsum_f32(K, M, A, lda, colsum, 1, stream) : BLVM_EINVAL;
     if (rc) return rc;
     colsum = nullptr;
@@ -525,10 +538,10 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
   BLVM_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "gemm: grid too large");
   if (split_k > 1 && !accumulate)  // atomic accumulation needs a zeroed destination
     BLVM_HIP(hipMemset2DAsync(C, sizeof(float) * (size_t)ldc, 0, sizeof(float) * (size_t)N, (size_t)M, stream));
-  if (n192) launch_gemm<128, 192>(g, op_a, op_b, grid, stream, bf16);
-  else if (m192) launch_gemm<192, 128>(g, op_a, op_b, grid, stream, bf16);
-  else if (big) launch_gemm<128, 128>(g, op_a, op_b, grid, stream, bf16);
-  else launch_gemm<64, 64>(g, op_a, op_b, grid, stream, bf16);
+  if (n192) launch_gemm<128, 192>(g, op_a, op_b, grid, stream, ot);
+  else if (m192) launch_gemm<192, 128>(g, op_a, op_b, grid, stream, ot);
+  else if (big) launch_gemm<128, 128>(g, op_a, op_b, grid, stream, ot);
+  else launch_gemm<64, 64>(g, op_a, op_b, grid, stream, ot);
   BLVM_CHECK_LAUNCH("gemm_f32");
   return BLVM_OK;
 }
@@ -537,7 +550,7 @@ int gemm_wgrad_group(const WgradJob* jobs, int njobs, int K, hipStream_t stream)
   static const int enabled = [] { const char* e = getenv("BLVM_WGRAD_GROUP"); return e ? atoi(e) : 1; }();
   int live = 0;
   for (int i = 0; i < njobs; ++i) live += jobs[i].dW != nullptr;
-  if (!enabled || operand_bf16() || live < 2 || live > kMaxGroup || K < 1024) {  // one launch per problem (gemm_f32 picks tile and kernel)
+  if (!enabled || operand_16bit() || live < 2 || live > kMaxGroup || K < 1024) {  // one launch per problem (gemm_f32 picks tile and kernel)
     for (int i = 0; i < njobs; ++i) {
       const WgradJob& j = jobs[i];
       const int rc = j.dW ? gemm_f32(1, 1, j.M, j.N, K, j.D, j.ldd, j.Act, j.lda, j.dW, j.ldw, nullptr, 0, 0.f, nullptr, 0, 1, gemm_pick_split(j.M, j.N, K), stream, j.db)
@@ -640,8 +653,10 @@ __global__ __launch_bounds__(256) void t16_pack_kernel(const float* __restrict__
   dst[i] = src[r * rs + (size_t)k * cs];
 }
 
-// the same block order with bf16 elements (two per 32-bit word, round to nearest even): the weights of the bf16-operand chains
-__global__ __launch_bounds__(256) void t16_pack_bf16_kernel(const float* __restrict__ src, long rs, long cs, int KB, size_t n2,
+// the same block order with 16-bit elements H (__bf16 / _Float16: two per 32-bit word, round to nearest even): the weights of the
+// 16-bit operand chains
+template <typename H>
+__global__ __launch_bounds__(256) void t16_pack16_kernel(const float* __restrict__ src, long rs, long cs, int KB, size_t n2,
                                                             unsigned* __restrict__ dst) {
   const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;  // output word = elements 2w, 2w + 1
   if (w >= n2) return;
@@ -653,7 +668,7 @@ __global__ __launch_bounds__(256) void t16_pack_bf16_kernel(const float* __restr
   const size_t r = 16 * t + (lane & 15);
   const int k = 16 * j + 4 * (lane >> 4) + e;
   typedef float f2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+  typedef H b2 __attribute__((ext_vector_type(2)));
   const f2 v = {src[r * rs + (size_t)k * cs], src[r * rs + (size_t)(k + 1) * cs]};
   dst[w] = __builtin_bit_cast(unsigned, __builtin_convertvector(v, b2));
 }
@@ -665,19 +680,21 @@ struct PackJob { const float* src; float* dst; long rs, cs; int KB; unsigned n; 
 struct PackJobs { PackJob j[kPackJobs]; };
 static_assert(sizeof(PackJobs) <= 4000, "kernel argument size");
 
-__global__ __launch_bounds__(256) void t16_pack_jobs_kernel(PackJobs a, int bf16) {
+// half != 0: 16-bit elements H (fp32 packs take the __bf16 instantiation with half = 0)
+template <typename H>
+__global__ __launch_bounds__(256) void t16_pack_jobs_kernel(PackJobs a, int half) {
   const PackJob q = a.j[blockIdx.y];
   for (size_t w = (size_t)blockIdx.x * 256 + threadIdx.x; w < q.n; w += (size_t)gridDim.x * 256) {
-    const size_t i = bf16 ? 2 * w : w;
+    const size_t i = half ? 2 * w : w;
     const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
     const size_t blk = i >> 8;
     const int j = (int)(blk % q.KB);
     const size_t t = blk / q.KB;
     const size_t r = 16 * t + (lane & 15);
     const int k = 16 * j + 4 * (lane >> 4) + e;
-    if (bf16) {
+    if (half) {
       typedef float f2 __attribute__((ext_vector_type(2)));
-      typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+      typedef H b2 __attribute__((ext_vector_type(2)));
       const f2 v = {q.src[r * q.rs + (size_t)k * q.cs], q.src[r * q.rs + (size_t)(k + 1) * q.cs]};
       reinterpret_cast<unsigned*>(q.dst)[w] = __builtin_bit_cast(unsigned, __builtin_convertvector(v, b2));
     } else {
@@ -688,7 +705,8 @@ __global__ __launch_bounds__(256) void t16_pack_jobs_kernel(PackJobs a, int bf16
 
 namespace {
 struct PackState {
-  bool active = false, bf16 = false;
+  bool active = false;
+  OpType ot = OP_F32;
   int n = 0;
   hipStream_t stream = nullptr;
   PackJobs jobs;
@@ -700,14 +718,15 @@ int pack_flush() {
   unsigned most = 0;
   for (int i = 0; i < p.n; ++i) most = std::max(most, p.jobs.j[i].n);
   const unsigned bx = std::min<unsigned>((most + 255) / 256, 512);
-  hipLaunchKernelGGL(t16_pack_jobs_kernel, dim3(bx, (unsigned)p.n), dim3(256), 0, p.stream, p.jobs, p.bf16 ? 1 : 0);
+  if (p.ot == OP_F16) hipLaunchKernelGGL(t16_pack_jobs_kernel<_Float16>, dim3(bx, (unsigned)p.n), dim3(256), 0, p.stream, p.jobs, 1);
+  else hipLaunchKernelGGL(t16_pack_jobs_kernel<__bf16>, dim3(bx, (unsigned)p.n), dim3(256), 0, p.stream, p.jobs, p.ot == OP_BF16 ? 1 : 0);
   p.n = 0;
   BLVM_CHECK_LAUNCH("t16_pack_jobs");
   return BLVM_OK;
 }
 }  // namespace
-T16PackScope::T16PackScope(bool bf16, hipStream_t stream) : prev_(g_pack.bf16), prev_active_(g_pack.active) {
-  g_pack.bf16 = bf16; g_pack.active = true; g_pack.stream = stream;
+T16PackScope::T16PackScope(OpType ot, hipStream_t stream) : prev_(g_pack.ot), prev_active_(g_pack.active) {
+  g_pack.ot = ot; g_pack.active = true; g_pack.stream = stream;
 }
 int T16PackScope::flush() {
   const int rc = pack_flush();
@@ -716,7 +735,7 @@ int T16PackScope::flush() {
 }
 T16PackScope::~T16PackScope() {
   (void)pack_flush();  // (a caller that returned early; an error here resurfaces at the next checked launch)
-  g_pack.bf16 = prev_; g_pack.active = prev_active_;
+  g_pack.ot = prev_; g_pack.active = prev_active_;
 }
 
 int t16_pack(const float* src, long rs, long cs, int R, int K, float* dst, hipStream_t stream) {
@@ -725,12 +744,14 @@ int t16_pack(const float* src, long rs, long cs, int R, int K, float* dst, hipSt
   BLVM_REQUIRE(n < (1ull << 31), "t16_pack: matrix too large");
   if (g_pack.active && g_pack.stream == stream) {  // deferred: one launch for all packs of the scope
     if (g_pack.n == kPackJobs) { const int rc = pack_flush(); if (rc) return rc; }
-    g_pack.jobs.j[g_pack.n++] = PackJob{src, dst, rs, cs, K / 16, (unsigned)(g_pack.bf16 ? n / 2 : n)};
+    g_pack.jobs.j[g_pack.n++] = PackJob{src, dst, rs, cs, K / 16, (unsigned)(g_pack.ot != OP_F32 ? n / 2 : n)};
     return BLVM_OK;
   }
-  if (g_pack.bf16) {
-    hipLaunchKernelGGL(t16_pack_bf16_kernel, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, stream, src, rs, cs, K / 16, n / 2, reinterpret_cast<unsigned*>(dst));
-    BLVM_CHECK_LAUNCH("t16_pack_bf16");
+  if (g_pack.ot != OP_F32) {
+    const dim3 grid((unsigned)((n / 2 + 255) / 256));
+    if (g_pack.ot == OP_F16) hipLaunchKernelGGL(t16_pack16_kernel<_Float16>, grid, dim3(256), 0, stream, src, rs, cs, K / 16, n / 2, reinterpret_cast<unsigned*>(dst));
+    else hipLaunchKernelGGL(t16_pack16_kernel<__bf16>, grid, dim3(256), 0, stream, src, rs, cs, K / 16, n / 2, reinterpret_cast<unsigned*>(dst));
+    BLVM_CHECK_LAUNCH("t16_pack16");
     return BLVM_OK;
   }
   hipLaunchKernelGGL(t16_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, rs, cs, K / 16, n, dst);

@@ -132,28 +132,44 @@ struct NoMid {
   __device__ __forceinline__ void operator()() const {}
 };
 
-// BF (the bf16-operand mode, blvm_set_operand_dtype): the weights were packed as bf16 (same T16 block order, 512 B per block) and the
-// activation fragments are rounded to bf16 in registers — a lane's 4 floats of a chunk ARE the 4 k-values a lane feeds
-// v_mfma_f32_16x16x16_bf16, so one MFMA replaces the four fp32 ones; accumulation, epilogues and everything stored stay fp32.
+// OT (the operand type, blvm_set_operand_dtype): OP_BF16 / OP_F16: the weights were packed as 16-bit elements of that type (same T16
+// block order, 512 B per block) and the activation fragments are rounded to it in registers — a lane's 4 floats of a chunk ARE the
+// 4 k-values a lane feeds v_mfma_f32_16x16x16_bf16 / _f16, so one MFMA replaces the four fp32 ones; accumulation, epilogues and
+// everything stored stay fp32.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned pk_bf16(float a, float b) {  // v_cvt_pk_bf16_f32 (round to nearest even)
   return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
 }
-template <bool BF> struct WFrag { typedef f32x4 type; };
-template <> struct WFrag<true> { typedef u32x2 type; };
+// two floats -> two 16-bit operands of type OT, round to nearest even (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32; fp16: |x| >= 65520 -> inf)
+template <int OT>
+__device__ __forceinline__ unsigned pk16(float a, float b) {
+  if constexpr (OT == OP_F16) return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){a, b}, f16x2_t));
+  else return pk_bf16(a, b);
+}
+// acc += a b over 16 k of 16-bit operands of type OT (4 per lane)
+template <int OT>
+__device__ __forceinline__ f32x4 mfma16(s16x4 a, s16x4 b, f32x4 acc) {
+  if constexpr (OT == OP_F16)
+    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4_t, a), __builtin_bit_cast(f16x4_t, b), acc, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, acc, 0, 0, 0);
+}
+template <int OT> struct WFrag { typedef u32x2 type; };
+template <> struct WFrag<OP_F32> { typedef f32x4 type; };
 
-template <int NW, bool BF, int GA, int G, class AMap, int CH, class Mid>
+template <int NW, int OT, int GA, int G, class AMap, int CH, class Mid>
 __device__ __forceinline__ void mgemm_trip(const rsrc_t (&ar)[GA], unsigned aoff, const float* const (&ap)[GA], const char* const (&wp)[G], int kc,
                                            bool aok, bool polled, f32x4 (&acc)[G], Poll& pl, Mid& mid, bool& mid_pending) {
   // Exactly CH chunks, no per-chunk guards: a guard around each chunk's load and the same guard around its sentinel check are one
   // region to the compiler, which then waits after EVERY chunk's load (one memory round trip per chunk instead of one per trip).
   // Polled operands are T16 slabs read through buffer resources (ar, byte offset aoff + 64 bytes per k), plain ones row-major (ap).
   constexpr int STEP = NW * 16;
-  typedef typename WFrag<BF>::type wfrag;
-  constexpr int ES = BF ? 2 : 4;  // bytes per weight element
+  typedef typename WFrag<OT>::type wfrag;
+  constexpr int ES = OT != OP_F32 ? 2 : 4;  // bytes per weight element
   wfrag w[G][CH];
   f32x4 a[GA][CH];
 #pragma unroll
@@ -197,18 +213,18 @@ __device__ __forceinline__ void mgemm_trip(const rsrc_t (&ar)[GA], unsigned aoff
 #pragma unroll
       for (int ga = 1; ga < GA; ++ga) a[0][u] += a[ga][u];
   }
-  if constexpr (BF) {
+  if constexpr (OT != OP_F32) {
 #pragma unroll
     for (int u = 0; u < CH; ++u) {
       s16x4 ab[GA];
 #pragma unroll
       for (int ga = 0; ga < GA; ++ga) {
         const f32x4 x = a[ga][u];
-        const u32x2 q = {aok ? pk_bf16(x[0], x[1]) : 0u, aok ? pk_bf16(x[2], x[3]) : 0u};
+        const u32x2 q = {aok ? pk16<OT>(x[0], x[1]) : 0u, aok ? pk16<OT>(x[2], x[3]) : 0u};
         ab[ga] = __builtin_bit_cast(s16x4, q);
       }
 #pragma unroll
-      for (int g = 0; g < G; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ab[AMap::of(g)], __builtin_bit_cast(s16x4, w[g][u]), acc[g], 0, 0, 0);
+      for (int g = 0; g < G; ++g) acc[g] = mfma16<OT>(ab[AMap::of(g)], __builtin_bit_cast(s16x4, w[g][u]), acc[g]);
     }
   } else {
 #pragma unroll
@@ -220,7 +236,7 @@ __device__ __forceinline__ void mgemm_trip(const rsrc_t (&ar)[GA], unsigned aoff
   }
 }
 
-template <int NW, bool BF, int GA, int G, class AMap, class Mid = NoMid>
+template <int NW, int OT, int GA, int G, class AMap, class Mid = NoMid>
 __device__ __forceinline__ void mgemm16(const float* const (&A)[GA], const int (&lda)[GA], bool polled, int r0, int nrows,
                                         const float* const (&W)[G], const int (&c0)[G], int K, f32x4 (&acc)[G], Poll& pl, Mid mid = Mid(),
                                         int a_width = 0, int w_width = 0) {  // a_width / w_width: columns of the polled T16 slab / of the packed weight rows when wider than K (the product covers a K-range of them; the pointers start at the range)
@@ -242,14 +258,14 @@ __device__ __forceinline__ void mgemm16(const float* const (&A)[GA], const int (
   }
   const unsigned aoff = 4u * ((unsigned)(r0 >> 4) * 16u * (unsigned)(a_width > 0 ? a_width : K) + 4u * (unsigned)lane);  // T16: row tile's slab + this lane's fragment
 #pragma unroll
-  for (int g = 0; g < G; ++g) wp[g] = reinterpret_cast<const char*>(W[g]) + (BF ? 2 : 4) * ((size_t)c0[g] * (w_width > 0 ? w_width : K) + 4 * lane);
+  for (int g = 0; g < G; ++g) wp[g] = reinterpret_cast<const char*>(W[g]) + (OT != OP_F32 ? 2 : 4) * ((size_t)c0[g] * (w_width > 0 ? w_width : K) + 4 * lane);
   int nch = (K / 16 - wave + NW - 1) / NW;  // chunks wave, wave + NW, ... below K / 16 (wave-uniform)
   int kc = wave * 16;
   bool mid_pending = true;
-  if constexpr (MAXCH >= 6) for (; nch >= 6; nch -= 6, kc += 6 * STEP) mgemm_trip<NW, BF, GA, G, AMap, 6>(ar, aoff, ap, wp, kc, aok, polled, acc, pl, mid, mid_pending);
-  if constexpr (MAXCH >= 4) for (; nch >= 4; nch -= 4, kc += 4 * STEP) mgemm_trip<NW, BF, GA, G, AMap, 4>(ar, aoff, ap, wp, kc, aok, polled, acc, pl, mid, mid_pending);
-  if constexpr (MAXCH >= 2) for (; nch >= 2; nch -= 2, kc += 2 * STEP) mgemm_trip<NW, BF, GA, G, AMap, 2>(ar, aoff, ap, wp, kc, aok, polled, acc, pl, mid, mid_pending);
-  for (; nch >= 1; nch -= 1, kc += STEP) mgemm_trip<NW, BF, GA, G, AMap, 1>(ar, aoff, ap, wp, kc, aok, polled, acc, pl, mid, mid_pending);
+  if constexpr (MAXCH >= 6) for (; nch >= 6; nch -= 6, kc += 6 * STEP) mgemm_trip<NW, OT, GA, G, AMap, 6>(ar, aoff, ap, wp, kc, aok, polled, acc, pl, mid, mid_pending);
+  if constexpr (MAXCH >= 4) for (; nch >= 4; nch -= 4, kc += 4 * STEP) mgemm_trip<NW, OT, GA, G, AMap, 4>(ar, aoff, ap, wp, kc, aok, polled, acc, pl, mid, mid_pending);
+  if constexpr (MAXCH >= 2) for (; nch >= 2; nch -= 2, kc += 2 * STEP) mgemm_trip<NW, OT, GA, G, AMap, 2>(ar, aoff, ap, wp, kc, aok, polled, acc, pl, mid, mid_pending);
+  for (; nch >= 1; nch -= 1, kc += STEP) mgemm_trip<NW, OT, GA, G, AMap, 1>(ar, aoff, ap, wp, kc, aok, polled, acc, pl, mid, mid_pending);
   if (mid_pending) mid();  // a wave without chunks
 }
 
@@ -362,7 +378,7 @@ struct LinLate {
   float slope;
   Out out;
 };
-template <int NW, bool BF, class Late>
+template <int NW, int OT, class Late>
 __device__ __forceinline__ void tile_lin_late(const float* A, int lda, bool a_polled, const float* W, int K, Late& late, int r0, int c0, int B,
                                               float* red, Poll& pl, const float* A2 = nullptr, const float* A3 = nullptr, int w_width = 0) {
   const int t = threadIdx.x & 255;
@@ -386,12 +402,12 @@ __device__ __forceinline__ void tile_lin_late(const float* A, int lda, bool a_po
     const float* const As[3] = {A, A2, A3};
     const float* const Ws[1] = {W};
     const int la[3] = {0, 0, 0}, cs[1] = {c0};
-    mgemm16<NW, BF, 3, 1, MapSum>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch, lda, w_width);
+    mgemm16<NW, OT, 3, 1, MapSum>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch, lda, w_width);
   } else {
     const float* const As[1] = {A};
     const float* const Ws[1] = {W};
     const int la[1] = {lda}, cs[1] = {c0};
-    mgemm16<NW, BF, 1, 1, MapSame>(As, la, a_polled, r0, B, Ws, cs, K, acc, pl, prefetch, a_polled ? lda : 0, w_width);  // polled: lda = slab width (0 = K)
+    mgemm16<NW, OT, 1, 1, MapSame>(As, la, a_polled, r0, B, Ws, cs, K, acc, pl, prefetch, a_polled ? lda : 0, w_width);  // polled: lda = slab width (0 = K)
   }
   float v[1];
   reduce_tiles<1, NW>(acc, red, v);
@@ -419,12 +435,12 @@ __device__ __forceinline__ void tile_lin_late(const float* A, int lda, bool a_po
   if (a_polled && pl.nap == 1) { pl.t_end = wall_clock64(); }
 #endif
 }
-template <int NW, bool BF = false>
+template <int NW, int OT = OP_F32>
 __device__ __forceinline__ void tile_lin(const float* A, int lda, bool a_polled, const float* W, int K, const float* bias,
                                          const float* add, int ldadd, bool add_polled, const float* gate, int ldgate, bool relu,
                                          float slope, const Out& out, int r0, int c0, int B, float* red, Poll& pl) {
   auto late = [&]() { return LinLate{bias, add, gate, ldadd, ldgate, add_polled, relu, slope, out}; };
-  tile_lin_late<NW, BF>(A, lda, a_polled, W, K, late, r0, c0, B, red, pl);
+  tile_lin_late<NW, OT>(A, lda, a_polled, W, K, late, r0, c0, B, red, pl);
 }
 
 // Both Gaussian heads + posterior combination + reparameterised sample (stages.h head_stage_kernel): P, Q [B,H] are the last
@@ -434,7 +450,7 @@ struct HeadOut {
   float *mu_p, *sd_p, *mu_q, *sd_q, *raw_p, *raw_q, *muq_raw;  // [B,Z] slabs of this step; muq_raw may be null
   Out z;
 };
-template <int NW, bool BF = false>
+template <int NW, int OT = OP_F32>
 __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool polled, const float* Wp, const float* bp, const float* Wq,
                                           const float* bq, const float* eps, const HeadOut& o, int H, int Z, int residual, float beta,
                                           float inv_beta, float sd_eps, int r0, int c0, int B, float* red, Poll& pl) {
@@ -451,7 +467,7 @@ __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool p
     const float* const As[2] = {P, Q};
     const float* const Ws[4] = {Wp, Wp, Wq, Wq};
     const int la[2] = {H, H}, cs[4] = {c0, Z + c0, c0, Z + c0};
-    mgemm16<NW, BF, 2, 4, MapPairs>(As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
+    mgemm16<NW, OT, 2, 4, MapPairs>(As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
   }
   float v[4];
   reduce_tiles<4, NW>(acc, red, v);
@@ -482,7 +498,7 @@ __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool p
 // GRU cell update of a [16 x 16] block of the state (vrnn.hip gru_stage_kernel, rssm.hip gru_cell_stage_kernel): gi = X Wih^T
 // (3 products, X [B,K] polled) + xg (state-independent part of the input projection incl. b_ih, computed before the launch) and /
 // or + b_ih ; gh = h_prev Whh^T + b_hh was produced by another link of this launch (polled words), h_prev likewise.  Writes h_new (sc1) and the gates r, u, n (read after the launch).
-template <int NW, bool BF = false>
+template <int NW, int OT = OP_F32>
 __device__ __forceinline__ void tile_gru(const float* X, int ldx, bool polled, const float* Wih, int K, const float* xg, const float* bih,
                                          const float* gh, const float* hprev, int ldh, int R, const Out& hnew, float* rg, float* ug, float* ng,
                                          int r0, int c0, int B, float* red, Poll& pl) {
@@ -511,7 +527,7 @@ __device__ __forceinline__ void tile_gru(const float* X, int ldx, bool polled, c
     const float* const As[1] = {X};
     const float* const Ws[3] = {Wih, Wih, Wih};
     const int la[1] = {ldx}, cs[3] = {c0, R + c0, 2 * R + c0};
-    mgemm16<NW, BF, 1, 3, MapSame>(As, la, polled, r0, B, Ws, cs, K, acc, pl, prefetch);
+    mgemm16<NW, OT, 1, 3, MapSame>(As, la, polled, r0, B, Ws, cs, K, acc, pl, prefetch);
   }
   float v[3];
   reduce_tiles<3, NW>(acc, red, v);
@@ -537,7 +553,7 @@ struct DzIn {
   float fn_floor, beta, sd_eps;
   bool has_gemm = true;  // false: dz = dz_add alone (the last step of a chain whose z only feeds the next step)
 };
-template <int NW, bool BF = false>
+template <int NW, int OT = OP_F32>
 __device__ __forceinline__ void tile_dz(const float* D, const float* WT, const float* D2, const float* WT2, bool polled, const float* dz_add,
                                         int ld_add, bool add_polled, const DzIn& a, const Out& dqh, const Out& dph, int H, int Z, int r0, int c0,
                                         int B, float* red, Poll& pl) {
@@ -565,13 +581,13 @@ __device__ __forceinline__ void tile_dz(const float* D, const float* WT, const f
       const float* const As[2] = {D, D2};
       const float* const Ws[2] = {WT, WT2};
       const int la[2] = {H, H}, cs[2] = {c0, c0};
-      mgemm16<NW, BF, 2, 2, MapId>(As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
+      mgemm16<NW, OT, 2, 2, MapId>(As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
     } else {
       f32x4 a1[1] = {acc[0]};
       const float* const As[1] = {D};
       const float* const Ws[1] = {WT};
       const int la[1] = {H}, cs[1] = {c0};
-      mgemm16<NW, BF, 1, 1, MapSame>(As, la, polled, r0, B, Ws, cs, H, a1, pl, prefetch);
+      mgemm16<NW, OT, 1, 1, MapSame>(As, la, polled, r0, B, Ws, cs, H, a1, pl, prefetch);
       acc[0] = a1[0];
     }
     reduce_tiles<2, NW>(acc, red, v);
@@ -633,7 +649,7 @@ struct GrubIn {
   float *ga, *g_out;
   bool has_gemm, has_gin, has_gates;
 };
-template <int NW, bool BF = false>
+template <int NW, int OT = OP_F32>
 __device__ __forceinline__ void tile_grub(const GrubIn& a, int K, int R, int r0, int c0, int B, float* red, Poll& pl) {
   const int tt = threadIdx.x & 255;
   const int row = r0 + (tt >> 4), col = c0 + (tt & 15);
@@ -659,7 +675,7 @@ __device__ __forceinline__ void tile_grub(const GrubIn& a, int K, int R, int r0,
     const float* const As[2] = {a.D0, a.D1};
     const float* const Ws[2] = {a.W0, a.W1};
     const int la[2] = {0, 0}, cs[2] = {c0, c0};
-    mgemm16<NW, BF, 2, 2, MapId>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch);
+    mgemm16<NW, OT, 2, 2, MapId>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch);
     reduce_tiles<2, NW>(acc, red, v);
   }
   if (threadIdx.x >= 256) return;
@@ -698,7 +714,7 @@ struct GruSeqIn {
   long out_ts;
   int out_ld, j, reverse;
 };
-template <int NW, bool BF = false>
+template <int NW, int OT = OP_F32>
 __device__ __forceinline__ void tile_gru_seq(const GruSeqIn& a, const Out& hnext, int R, int r0, int c0, int B, float* red, Poll& pl) {
   const int t = threadIdx.x & 255;
   const int row = r0 + (t >> 4), col = c0 + (t & 15);
@@ -721,7 +737,7 @@ __device__ __forceinline__ void tile_gru_seq(const GruSeqIn& a, const Out& hnext
     const float* const As[1] = {a.H16};
     const float* const Ws[3] = {a.Whh, a.Whh, a.Whh};
     const int la[1] = {0}, cs[3] = {c0, R + c0, 2 * R + c0};
-    mgemm16<NW, BF, 1, 3, MapSame>(As, la, true, r0, B, Ws, cs, R, acc, pl, prefetch);
+    mgemm16<NW, OT, 1, 3, MapSame>(As, la, true, r0, B, Ws, cs, R, acc, pl, prefetch);
   }
   float v[3];
   reduce_tiles<3, NW>(acc, red, v);
@@ -748,7 +764,7 @@ struct GruSeqBwdIn {
   int out_ld, j, reverse;
   bool has_gemm, has_gates;
 };
-template <int NW, bool BF = false>
+template <int NW, int OT = OP_F32>
 __device__ __forceinline__ void tile_gru_seq_bwd(const GruSeqBwdIn& a, const Out& dgh, int R, int r0, int c0, int B, float* red, Poll& pl) {
   const int t = threadIdx.x & 255;
   const int row = r0 + (t >> 4), col = c0 + (t & 15);
@@ -771,7 +787,7 @@ __device__ __forceinline__ void tile_gru_seq_bwd(const GruSeqBwdIn& a, const Out
     const float* const As[1] = {a.DGHn16};
     const float* const Ws[1] = {a.WhhT};
     const int la[1] = {0}, cs[1] = {c0};
-    mgemm16<NW, BF, 1, 1, MapSame>(As, la, true, r0, B, Ws, cs, 3 * R, acc, pl, prefetch);
+    mgemm16<NW, OT, 1, 1, MapSame>(As, la, true, r0, B, Ws, cs, 3 * R, acc, pl, prefetch);
     reduce_tiles<1, NW>(acc, red, v);
   } else {
     prefetch();
@@ -799,7 +815,7 @@ struct LstmSeqIn {
   float *cnext, *out, *gates;    // [B,H], [B,H] (zero past the row's length), [B,4H] saved i,f,g,o (zero where masked)
   int t;
 };
-template <int NW, bool BF = false>
+template <int NW, int OT = OP_F32>
 __device__ __forceinline__ void tile_lstm_seq(const LstmSeqIn& a, const Out& hnext, int H, int r0, int c0, int B, float* red, Poll& pl) {
   const int tt = threadIdx.x & 255;
   const int row = r0 + (tt >> 4), col = c0 + (tt & 15);
@@ -821,7 +837,7 @@ __device__ __forceinline__ void tile_lstm_seq(const LstmSeqIn& a, const Out& hne
     const float* const As[1] = {a.H16};
     const float* const Ws[4] = {a.Whh, a.Whh, a.Whh, a.Whh};
     const int la[1] = {0}, cs[4] = {c0, H + c0, 2 * H + c0, 3 * H + c0};
-    mgemm16<NW, BF, 1, 4, MapSame>(As, la, true, r0, B, Ws, cs, H, acc, pl, prefetch);
+    mgemm16<NW, OT, 1, 4, MapSame>(As, la, true, r0, B, Ws, cs, H, acc, pl, prefetch);
   }
   float v[4];
   reduce_tiles<4, NW>(acc, red, v);
@@ -845,7 +861,7 @@ struct LstmSeqBwdIn {
   float* dh0;                 // [B,H]: written when has_gates == 0
   bool has_gemm, has_gates;
 };
-template <int NW, bool BF = false>
+template <int NW, int OT = OP_F32>
 __device__ __forceinline__ void tile_lstm_seq_bwd(const LstmSeqBwdIn& a, const Out& dg, int H, int r0, int c0, int B, float* red, Poll& pl) {
   const int tt = threadIdx.x & 255;
   const int row = r0 + (tt >> 4), col = c0 + (tt & 15);
@@ -866,7 +882,7 @@ __device__ __forceinline__ void tile_lstm_seq_bwd(const LstmSeqBwdIn& a, const O
     const float* const As[1] = {a.DGn16};
     const float* const Ws[1] = {a.WhhT};
     const int la[1] = {0}, cs_[1] = {c0};
-    mgemm16<NW, BF, 1, 1, MapSame>(As, la, true, r0, B, Ws, cs_, 4 * H, acc, pl, prefetch);
+    mgemm16<NW, OT, 1, 1, MapSame>(As, la, true, r0, B, Ws, cs_, 4 * H, acc, pl, prefetch);
     reduce_tiles<1, NW>(acc, red, v);
   } else {
     prefetch();
@@ -997,7 +1013,7 @@ struct Desc {
   const float* p[kMaxPtr];        // per kind
 };
 struct Program {
-  int bf16 = 0;  // weights are bf16 T16 packs, products on the bf16 matrix pipe (see mgemm_trip)
+  int ot = OP_F32;  // operand type (OpType): OP_BF16 / OP_F16: weights are 16-bit T16 packs, products on that matrix pipe (see mgemm_trip)
   int rt_group = 1;  // row tiles per tile: 1 = pchain.h's 16-row tiles; 4 = row groups (pchain_rt.h; the VRNN tile kinds only, B > 128)
   int s_first = 0;  // the launch walks steps [s_first, S): a sequence may be cut into several launches (everything a later one needs is in the slabs)
   int ndesc, S, B, xcd;
@@ -1095,7 +1111,8 @@ inline int device_cus() {
 }
 constexpr int kPchainCarveMaxB = 128;  // the persistent kernels' extra buffers are carved for batches up to this size only
 inline bool pchain_applies(int B) { return B <= pchain_max_batch() && B <= kPchainCarveMaxB; }
-// the bf16-operand mode (common.h operand_bf16) of a sequence that runs as a persistent launch: its weights are packed as bf16
-inline bool pchain_bf16(int B) { return operand_bf16() && pchain_applies(B) && device_cus() >= 32; }
+// the operand type (common.h operand_type) of a sequence that runs as a persistent launch: OP_F32 unless the mode is 16-bit and the
+// sequence is persistent, then its weights are packed as 16-bit elements of that type
+inline OpType pchain_optype(int B) { return operand_16bit() && pchain_applies(B) && device_cus() >= 32 ? operand_type() : OP_F32; }
 
 }  // namespace blvm

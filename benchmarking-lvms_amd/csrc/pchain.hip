@@ -150,7 +150,7 @@ struct DescRegs {
   __device__ __forceinline__ int wdyn(int idx) const { return __builtin_amdgcn_readlane(v0, idx); }  // idx < 64
 };
 
-template <int NW, bool BF>
+template <int NW, int OT>
 __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restrict__ tab, Hdr a) {
   extern __shared__ __attribute__((aligned(16))) char lds_all[];  // [descriptors | profile | 2 x (lds_products x NW x 256) floats]
   int* const ltab = reinterpret_cast<int*>(lds_all);
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
               const unsigned long long tq1 = wall_clock64();
               tq[0] += tq1 - tq0;
 #endif
-              tile_lin_late<NW, BF>(A, ld0, a_polled, W, K, late, tr0, tc0, B, red(), pl, A2, A3, w_width);
+              tile_lin_late<NW, OT>(A, ld0, a_polled, W, K, late, tr0, tc0, B, red(), pl, A2, A3, w_width);
 #ifdef PCHAIN_TPROF2
               tq_end = wall_clock64();
               tq[1] += tq_end - tq1;
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
               // VRNN step, used or not, and saves 0.08)
               for (int tk = 0; tk < nt; ++tk) {
                 const int trc = d.tile(tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
-                tile_lin_late<NW, BF>(A, 0, true, W, Kl, late, tr0, tc0, B, red(), pl);
+                tile_lin_late<NW, OT>(A, 0, true, W, Kl, late, tr0, tc0, B, red(), pl);
               }
               A = d.pdyn(13 + li);  // the next link multiplies what this one stored
             }
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             const int Z = d.w<RD_I + 0>(), residual = d.w<RD_I + 1>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_head<NW, BF>(d.p<0>(s), d.p<1>(s), true, d.base<2>(), d.base<3>(), d.base<4>(), d.base<5>(), d.p<6>(s), o, K, Z, residual, d.f<0>(), d.f<1>(),
+              tile_head<NW, OT>(d.p<0>(s), d.p<1>(s), true, d.base<2>(), d.base<3>(), d.base<4>(), d.base<5>(), d.p<6>(s), o, K, Z, residual, d.f<0>(), d.f<1>(),
                             d.f<2>(), trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             const int R = d.w<RD_I + 0>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_gru<NW, BF>(d.p<0>(s), 0, true, d.base<1>(), K, d.p<2>(s), d.base<10>(), d.p<3>(s), d.p<4>(s), ld0, R, o, d.m<7>(s), d.m<8>(s), d.m<9>(s),
+              tile_gru<NW, OT>(d.p<0>(s), 0, true, d.base<1>(), K, d.p<2>(s), d.base<10>(), d.p<3>(s), d.p<4>(s), ld0, R, o, d.m<7>(s), d.m<8>(s), d.m<9>(s),
                            trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             const Out oq{d.m<16>(s), ld3, false, d.m<17>(s), n16}, op{d.m<18>(s), ld3, false, d.m<19>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_dz<NW, BF>(d.p<0>(s), d.base<1>(), d.p<2>(s), d.base<3>(), true, d.p<4>(s), ld1, (flags & DF_ADD_POLLED) != 0, z, oq, op, K, Z, trc & 0xffff,
+              tile_dz<NW, OT>(d.p<0>(s), d.base<1>(), d.p<2>(s), d.base<3>(), true, d.p<4>(s), ld1, (flags & DF_ADD_POLLED) != 0, z, oq, op, K, Z, trc & 0xffff,
                           (trc >> 16) * 16, B, red(), pl);
             }
           } break;
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             const int R = d.w<RD_I + 0>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_grub<NW, BF>(g, K, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
+              tile_grub<NW, OT>(g, K, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_GRUS: {
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             const Out o{d.m<6>(s), ld3, false, d.m<7>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_gru_seq<NW, BF>(g, o, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
+              tile_gru_seq<NW, OT>(g, o, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_GRUSB: {
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             const Out o{d.m<11>(s), ld3, false, d.m<12>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_gru_seq_bwd<NW, BF>(g, o, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
+              tile_gru_seq_bwd<NW, OT>(g, o, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_LSTMS: {
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             const Out o{d.m<6>(s), ld3, false, d.m<7>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_lstm_seq<NW, BF>(g, o, H, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
+              tile_lstm_seq<NW, OT>(g, o, H, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_LSTMSB: {
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             const Out o{d.m<6>(s), ld3, false, d.m<7>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_lstm_seq_bwd<NW, BF>(g, o, H, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
+              tile_lstm_seq_bwd<NW, OT>(g, o, H, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_DMOLS: {
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
 // The same walk on ROW GROUPS (pchain_rt.h): a tile is up to RT row tiles of one column tile, the program's tile lists count
 // groups (rt = row groups here), and only the tile kinds of the VRNN programs exist.  A separate kernel on purpose: the 16-row
 // kernel above is sensitive to every live scalar (tools/probe_engine_chain.py) and must not change when this one does.
-template <int NW, bool BF, int RT>
+template <int NW, int OT, int RT>
 __global__ __launch_bounds__(NW * 64, 1) void pchain_rt_kernel(const int* __restrict__ tab, Hdr a) {
   extern __shared__ __attribute__((aligned(16))) char lds_all[];
   int* const ltab = reinterpret_cast<int*>(lds_all);
@@ -483,7 +483,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_rt_kernel(const int* __rest
               if ((flags & DF_CANARY) && a_polled) {
                 for (int q = 0; q < RT && tr0 + 16 * q < B; ++q) canary_wait(A, tr0 + 16 * q, K, pl, ld0);
               }
-              tile_lin_rt<NW, BF, RT, 1>(A, ld0, a_polled, W, K, late, tr0, tc0, B, red, pl, A2, A3, w_width);
+              tile_lin_rt<NW, OT, RT, 1>(A, ld0, a_polled, W, K, late, tr0, tc0, B, red, pl, A2, A3, w_width);
             }
           } break;
           case K_LINSEQ: {
@@ -503,7 +503,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_rt_kernel(const int* __rest
               };
               for (int tk = 0; tk < nt; ++tk) {
                 const int trc = d.tile(tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
-                tile_lin_rt<NW, BF, RT, 1>(A, 0, true, W, Kl, late, tr0, tc0, B, red, pl);
+                tile_lin_rt<NW, OT, RT, 1>(A, 0, true, W, Kl, late, tr0, tc0, B, red, pl);
               }
               A = d.pdyn(13 + li);
             }
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_rt_kernel(const int* __rest
             const int Z = d.w<RD_I + 0>(), residual = d.w<RD_I + 1>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_head_rt<NW, BF, RT>(d.p<0>(s), d.p<1>(s), true, d.base<2>(), d.base<3>(), d.base<4>(), d.base<5>(), d.p<6>(s), o, K, Z, residual, d.f<0>(),
+              tile_head_rt<NW, OT, RT>(d.p<0>(s), d.p<1>(s), true, d.base<2>(), d.base<3>(), d.base<4>(), d.base<5>(), d.p<6>(s), o, K, Z, residual, d.f<0>(),
                                        d.f<1>(), d.f<2>(), trc & 0xffff, (trc >> 16) * 16, B, red, pl);
             }
           } break;
@@ -523,7 +523,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_rt_kernel(const int* __rest
             const int R = d.w<RD_I + 0>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_gru_rt<NW, BF, RT>(d.p<0>(s), 0, true, d.base<1>(), K, d.p<2>(s), d.base<10>(), d.p<3>(s), d.p<4>(s), ld0, R, o, d.m<7>(s), d.m<8>(s),
+              tile_gru_rt<NW, OT, RT>(d.p<0>(s), 0, true, d.base<1>(), K, d.p<2>(s), d.base<10>(), d.p<3>(s), d.p<4>(s), ld0, R, o, d.m<7>(s), d.m<8>(s),
                                       d.m<9>(s), trc & 0xffff, (trc >> 16) * 16, B, red, pl);
             }
           } break;
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_rt_kernel(const int* __rest
             const Out oq{d.m<16>(s), ld3, false, d.m<17>(s), n16}, op{d.m<18>(s), ld3, false, d.m<19>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_dz_rt<NW, BF, RT>(d.p<0>(s), d.base<1>(), true, d.p<4>(s), ld1, (flags & DF_ADD_POLLED) != 0, z, oq, op, K, Z, trc & 0xffff, (trc >> 16) * 16, B,
+              tile_dz_rt<NW, OT, RT>(d.p<0>(s), d.base<1>(), true, d.p<4>(s), ld1, (flags & DF_ADD_POLLED) != 0, z, oq, op, K, Z, trc & 0xffff, (trc >> 16) * 16, B,
                                      red, pl);
             }
           } break;
@@ -554,7 +554,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_rt_kernel(const int* __rest
             const int R = d.w<RD_I + 0>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_grub_rt<NW, BF, RT>(g, K, R, trc & 0xffff, (trc >> 16) * 16, B, red, pl);
+              tile_grub_rt<NW, OT, RT>(g, K, R, trc & 0xffff, (trc >> 16) * 16, B, red, pl);
             }
           } break;
           default: break;
@@ -655,8 +655,8 @@ int pchain_launch(const pchain::Program& prog, hipStream_t stream) {
   // computes for this kernel, block size and LDS size (cached per kernel and number of products: a train step alternates sizes)
   constexpr int kMaxProducts = 8;
   static std::mutex attr_mu;
-  static int attr_dev[3] = {-1, -1, -1};
-  static int occ_blocks[3][kMaxProducts + 1];  // workgroups per CU; 0: not asked yet
+  static int attr_dev[4] = {-1, -1, -1, -1};
+  static int occ_blocks[4][kMaxProducts + 1];  // workgroups per CU; 0: not asked yet
   const size_t lds_max = lds_fixed + sizeof(float) * 2 * (prog.rt_group > 1 ? 8 : 4) * (size_t)nw * 256;  // (row groups reduce two row tiles per barrier)
   BLVM_REQUIRE(prog.lds_products >= 1 && lds <= lds_max, "pchain: %d products per tile do not fit the reduction scratch", prog.lds_products);
   auto go = [&](auto kernel, int slot, int threads) -> int {
@@ -683,13 +683,15 @@ int pchain_launch(const pchain::Program& prog, hipStream_t stream) {
                    "pchain: tile kind %d has no row-group form", k);
       BLVM_REQUIRE(k != pchain::K_DZ || prog.d[i].p[2] == nullptr, "pchain: the row-group dz tile is the single-product form");
     }
-    BLVM_REQUIRE(!prog.bf16, "pchain: row groups multiply fp32 operands only");
-    const int rcg = go(&pchain_rt_kernel<8, false, 2>, 2, 512);
+    BLVM_REQUIRE(prog.ot == OP_F32, "pchain: row groups multiply fp32 operands only");
+    const int rcg = go(&pchain_rt_kernel<8, OP_F32, 2>, 2, 512);
     if (rcg) return rcg;
     BLVM_CHECK_LAUNCH("pchain_launch (row groups)");
     return BLVM_OK;
   }
-  const int rc = prog.bf16 ? go(&pchain_kernel<16, true>, 1, 1024) : go(&pchain_kernel<16, false>, 0, 1024);
+  const int rc = prog.ot == OP_BF16  ? go(&pchain_kernel<16, OP_BF16>, 1, 1024)
+                 : prog.ot == OP_F16 ? go(&pchain_kernel<16, OP_F16>, 3, 1024)
+                                     : go(&pchain_kernel<16, OP_F32>, 0, 1024);
   if (rc) return rc;
   BLVM_CHECK_LAUNCH("pchain_launch");
   return BLVM_OK;

@@ -19,13 +19,13 @@ constexpr int kRtFrags = 16;
 // acc[rt][g] += A[AMap(g)][r0 + 16 rt + i][k] W[g][c0[g] + j][k] for the row tiles rt < RT of a group (mgemm_trip of pchain.h with
 // the activation side repeated per row tile).  rt_off[rt]: byte offset of row tile rt's T16 slab from the group's first (clamped to
 // the last row tile that exists, so no load leaves the step's slab; aok[rt] is false for every lane of a row tile beyond B).
-template <int NW, bool BF, int RT, int GA, int G, class AMap, int CH, class Mid>
+template <int NW, int OT, int RT, int GA, int G, class AMap, int CH, class Mid>
 __device__ __forceinline__ void mgemm_trip_rt(const rsrc_t (&ar)[GA], unsigned aoff, const unsigned (&rt_off)[RT], const float* const (&ap)[GA],
                                               const size_t (&rt_rows)[RT][GA], const char* const (&wp)[G], int kc, const bool (&aok)[RT], bool polled,
                                               f32x4 (&acc)[RT][G], Poll& pl, Mid& mid, bool& mid_pending) {
   constexpr int STEP = NW * 16;
-  typedef typename WFrag<BF>::type wfrag;
-  constexpr int ES = BF ? 2 : 4;
+  typedef typename WFrag<OT>::type wfrag;
+  constexpr int ES = OT != OP_F32 ? 2 : 4;
   wfrag w[G][CH];
   f32x4 a[RT][GA][CH];
 #pragma unroll
@@ -73,7 +73,7 @@ __device__ __forceinline__ void mgemm_trip_rt(const rsrc_t (&ar)[GA], unsigned a
 #pragma unroll
         for (int ga = 1; ga < GA; ++ga) a[rt][0][u] += a[rt][ga][u];
   }
-  if constexpr (BF) {
+  if constexpr (OT != OP_F32) {
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -82,12 +82,12 @@ __device__ __forceinline__ void mgemm_trip_rt(const rsrc_t (&ar)[GA], unsigned a
 #pragma unroll
         for (int ga = 0; ga < GA; ++ga) {
           const f32x4 x = a[rt][ga][u];
-          const u32x2 q = {aok[rt] ? pk_bf16(x[0], x[1]) : 0u, aok[rt] ? pk_bf16(x[2], x[3]) : 0u};
+          const u32x2 q = {aok[rt] ? pk16<OT>(x[0], x[1]) : 0u, aok[rt] ? pk16<OT>(x[2], x[3]) : 0u};
           ab[ga] = __builtin_bit_cast(s16x4, q);
         }
 #pragma unroll
         for (int g = 0; g < G; ++g)
-          acc[rt][g] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ab[AMap::of(g)], __builtin_bit_cast(s16x4, w[g][u]), acc[rt][g], 0, 0, 0);
+          acc[rt][g] = mfma16<OT>(ab[AMap::of(g)], __builtin_bit_cast(s16x4, w[g][u]), acc[rt][g]);
       }
   } else {
 #pragma unroll
@@ -102,7 +102,7 @@ __device__ __forceinline__ void mgemm_trip_rt(const rsrc_t (&ar)[GA], unsigned a
   }
 }
 
-template <int NW, bool BF, int RT, int GA, int G, class AMap, class Mid = NoMid>
+template <int NW, int OT, int RT, int GA, int G, class AMap, class Mid = NoMid>
 __device__ __forceinline__ void mgemm16_rt(const float* const (&A)[GA], const int (&lda)[GA], bool polled, int r0, int nrows, const float* const (&W)[G],
                                            const int (&c0)[G], int K, f32x4 (&acc)[RT][G], Poll& pl, Mid mid = Mid(), int a_width = 0, int w_width = 0) {
   constexpr int STEP = NW * 16;
@@ -133,14 +133,14 @@ __device__ __forceinline__ void mgemm16_rt(const float* const (&A)[GA], const in
   }
   const unsigned aoff = 4u * ((unsigned)(r0 >> 4) * 16u * (unsigned)width + 4u * (unsigned)lane);
 #pragma unroll
-  for (int g = 0; g < G; ++g) wp[g] = reinterpret_cast<const char*>(W[g]) + (BF ? 2 : 4) * ((size_t)c0[g] * (w_width > 0 ? w_width : K) + 4 * lane);
+  for (int g = 0; g < G; ++g) wp[g] = reinterpret_cast<const char*>(W[g]) + (OT != OP_F32 ? 2 : 4) * ((size_t)c0[g] * (w_width > 0 ? w_width : K) + 4 * lane);
   int nch = (K / 16 - wave + NW - 1) / NW;
   int kc = wave * 16;
   bool mid_pending = true;
-  if constexpr (MAXCH >= 6) for (; nch >= 6; nch -= 6, kc += 6 * STEP) mgemm_trip_rt<NW, BF, RT, GA, G, AMap, 6>(ar, aoff, rt_off, ap, rt_rows, wp, kc, aok, polled, acc, pl, mid, mid_pending);
-  if constexpr (MAXCH >= 4) for (; nch >= 4; nch -= 4, kc += 4 * STEP) mgemm_trip_rt<NW, BF, RT, GA, G, AMap, 4>(ar, aoff, rt_off, ap, rt_rows, wp, kc, aok, polled, acc, pl, mid, mid_pending);
-  if constexpr (MAXCH >= 2) for (; nch >= 2; nch -= 2, kc += 2 * STEP) mgemm_trip_rt<NW, BF, RT, GA, G, AMap, 2>(ar, aoff, rt_off, ap, rt_rows, wp, kc, aok, polled, acc, pl, mid, mid_pending);
-  for (; nch >= 1; nch -= 1, kc += STEP) mgemm_trip_rt<NW, BF, RT, GA, G, AMap, 1>(ar, aoff, rt_off, ap, rt_rows, wp, kc, aok, polled, acc, pl, mid, mid_pending);
+  if constexpr (MAXCH >= 6) for (; nch >= 6; nch -= 6, kc += 6 * STEP) mgemm_trip_rt<NW, OT, RT, GA, G, AMap, 6>(ar, aoff, rt_off, ap, rt_rows, wp, kc, aok, polled, acc, pl, mid, mid_pending);
+  if constexpr (MAXCH >= 4) for (; nch >= 4; nch -= 4, kc += 4 * STEP) mgemm_trip_rt<NW, OT, RT, GA, G, AMap, 4>(ar, aoff, rt_off, ap, rt_rows, wp, kc, aok, polled, acc, pl, mid, mid_pending);
+  if constexpr (MAXCH >= 2) for (; nch >= 2; nch -= 2, kc += 2 * STEP) mgemm_trip_rt<NW, OT, RT, GA, G, AMap, 2>(ar, aoff, rt_off, ap, rt_rows, wp, kc, aok, polled, acc, pl, mid, mid_pending);
+  for (; nch >= 1; nch -= 1, kc += STEP) mgemm_trip_rt<NW, OT, RT, GA, G, AMap, 1>(ar, aoff, rt_off, ap, rt_rows, wp, kc, aok, polled, acc, pl, mid, mid_pending);
   if (mid_pending) mid();
 }
 
@@ -176,7 +176,7 @@ __device__ __forceinline__ void reduce_pair(const f32x4 (&acc0)[G], const f32x4 
 // CT = 1 is instantiated: measured (r03, B = 128 / 192 / 256, same box) a 32-column tile costs twice a 16-column one -- the fp32
 // MFMAs of a tile are ~0.85 us of its ~3.1 us on a CU whose two waves per SIMD share the matrix pipe, the rest scales with the
 // outputs too -- so pairs only halve the tiles a link can be spread over (B = 128: 22.7 -> 28.6 ms/step).
-template <int NW, bool BF, int RT, int CT, class Late, class Red>
+template <int NW, int OT, int RT, int CT, class Late, class Red>
 __device__ __forceinline__ void tile_lin_rt(const float* A, int lda, bool a_polled, const float* W, int K, Late& late, int r0, int c0, int B, Red& red,
                                             Poll& pl, const float* A2 = nullptr, const float* A3 = nullptr, int w_width = 0) {
   const int t = threadIdx.x & 255;
@@ -217,11 +217,11 @@ __device__ __forceinline__ void tile_lin_rt(const float* A, int lda, bool a_poll
   if (A2 != nullptr) {  // (uniform) the operand arrives as three partial-sum slabs
     const float* const As[3] = {A, A2, A3};
     const int la[3] = {0, 0, 0};
-    mgemm16_rt<NW, BF, RT, 3, CT, MapSum>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch, lda, w_width);
+    mgemm16_rt<NW, OT, RT, 3, CT, MapSum>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch, lda, w_width);
   } else {
     const float* const As[1] = {A};
     const int la[1] = {lda};
-    mgemm16_rt<NW, BF, RT, 1, CT, MapSame>(As, la, a_polled, r0, B, Ws, cs, K, acc, pl, prefetch, a_polled ? lda : 0, w_width);
+    mgemm16_rt<NW, OT, RT, 1, CT, MapSame>(As, la, a_polled, r0, B, Ws, cs, K, acc, pl, prefetch, a_polled ? lda : 0, w_width);
   }
   static_assert(RT % 2 == 0 && NW == 8, "row groups are finished in pairs by 512 threads");
 #pragma unroll
@@ -257,7 +257,7 @@ __device__ __forceinline__ void tile_lin_rt(const float* A, int lda, bool a_poll
   }
 }
 
-template <int NW, bool BF, int RT, class Red>
+template <int NW, int OT, int RT, class Red>
 __device__ __forceinline__ void tile_head_rt(const float* P, const float* Q, bool polled, const float* Wp, const float* bp, const float* Wq, const float* bq,
                                              const float* eps, const HeadOut& o, int H, int Z, int residual, float beta, float inv_beta, float sd_eps,
                                              int r0, int c0, int B, Red& red, Poll& pl) {
@@ -285,7 +285,7 @@ __device__ __forceinline__ void tile_head_rt(const float* P, const float* Q, boo
     const float* const As[2] = {P, Q};
     const float* const Ws[4] = {Wp, Wp, Wq, Wq};
     const int la[2] = {H, H}, cs[4] = {c0, Z + c0, c0, Z + c0};
-    mgemm16_rt<NW, BF, RT, 2, 4, MapPairs>(As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
+    mgemm16_rt<NW, OT, RT, 2, 4, MapPairs>(As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
   }
 #pragma unroll
   for (int pr = 0; pr < RT / 2; ++pr) {
@@ -321,7 +321,7 @@ __device__ __forceinline__ void tile_head_rt(const float* P, const float* Q, boo
   }
 }
 
-template <int NW, bool BF, int RT, class Red>
+template <int NW, int OT, int RT, class Red>
 __device__ __forceinline__ void tile_gru_rt(const float* X, int ldx, bool polled, const float* Wih, int K, const float* xg, const float* bih, const float* gh,
                                             const float* hprev, int ldh, int R, const Out& hnew, float* rg, float* ug, float* ng, int r0, int c0, int B,
                                             Red& red, Poll& pl) {
@@ -362,7 +362,7 @@ __device__ __forceinline__ void tile_gru_rt(const float* X, int ldx, bool polled
     const float* const As[1] = {X};
     const float* const Ws[3] = {Wih, Wih, Wih};
     const int la[1] = {ldx}, cs[3] = {c0, R + c0, 2 * R + c0};
-    mgemm16_rt<NW, BF, RT, 1, 3, MapSame>(As, la, polled, r0, B, Ws, cs, K, acc, pl, prefetch);
+    mgemm16_rt<NW, OT, RT, 1, 3, MapSame>(As, la, polled, r0, B, Ws, cs, K, acc, pl, prefetch);
   }
 #pragma unroll
   for (int pr = 0; pr < RT / 2; ++pr) {
@@ -390,7 +390,7 @@ __device__ __forceinline__ void tile_gru_rt(const float* X, int ldx, bool polled
 }
 
 // (single product: the VRNN form, D2 == nullptr)
-template <int NW, bool BF, int RT, class Red>
+template <int NW, int OT, int RT, class Red>
 __device__ __forceinline__ void tile_dz_rt(const float* D, const float* WT, bool polled, const float* dz_add, int ld_add, bool add_polled, const DzIn& a,
                                            const Out& dqh, const Out& dph, int H, int Z, int r0, int c0, int B, Red& red, Poll& pl) {
   const int t = threadIdx.x & 255;
@@ -424,7 +424,7 @@ __device__ __forceinline__ void tile_dz_rt(const float* D, const float* WT, bool
     const float* const As[1] = {D};
     const float* const Ws[1] = {WT};
     const int la[1] = {H}, cs[1] = {c0};
-    mgemm16_rt<NW, BF, RT, 1, 1, MapSame>(As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
+    mgemm16_rt<NW, OT, RT, 1, 1, MapSame>(As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
   } else {
     prefetch();
   }
@@ -482,7 +482,7 @@ __device__ __forceinline__ void tile_dz_rt(const float* D, const float* WT, bool
   }
 }
 
-template <int NW, bool BF, int RT, class Red>
+template <int NW, int OT, int RT, class Red>
 __device__ __forceinline__ void tile_grub_rt(const GrubIn& a, int K, int R, int r0, int c0, int B, Red& red, Poll& pl) {
   const int t = threadIdx.x & 255;
   const int col = c0 + (t & 15);
@@ -516,7 +516,7 @@ __device__ __forceinline__ void tile_grub_rt(const GrubIn& a, int K, int R, int 
     const float* const As[2] = {a.D0, a.D1};
     const float* const Ws[2] = {a.W0, a.W1};
     const int la[2] = {0, 0}, cs[2] = {c0, c0};
-    mgemm16_rt<NW, BF, RT, 2, 2, MapId>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch);
+    mgemm16_rt<NW, OT, RT, 2, 2, MapId>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch);
   }
 #pragma unroll
   for (int pr = 0; pr < RT / 2; ++pr) {

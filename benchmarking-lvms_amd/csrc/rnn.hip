@@ -363,8 +363,8 @@ extern "C" int blvm_lstm_seq_fwd(const float* Wih, const float* Whh, const float
   else BLVM_HIP(hipMemsetAsync(rs.Hs, 0, sizeof(float) * bh, s));
   if (c0) BLVM_HIP(hipMemcpyAsync(rs.Cs, c0, sizeof(float) * bh, hipMemcpyDeviceToDevice, s));
   else BLVM_HIP(hipMemsetAsync(rs.Cs, 0, sizeof(float) * bh, s));
-  const bool bf16_seq = pchain_bf16(B) && seq_persistent(T, B);  // bf16-operand mode of the persistent path
-  T16PackScope pack_scope(bf16_seq, s);
+  const OpType seq_ot = seq_persistent(T, B) ? pchain_optype(B) : OP_F32;  // 16-bit operand mode of the persistent path
+  T16PackScope pack_scope(seq_ot, s);
   rc = t16_pack_rows(Whh, H, 4 * H, H, rs.WhhP, s);  // operand layout of the chain (once per sequence)
   if (rc) return rc;
   rc = pack_scope.flush();
@@ -372,7 +372,7 @@ extern "C" int blvm_lstm_seq_fwd(const float* Wih, const float* Whh, const float
   if (seq_persistent(T, B) && (seq_regs_mask() & 1) && seq_regs_applies(H, 4 * H, H, B, 4)) {
     // one persistent launch with the workgroup's weight slice in registers (seqchain.hip)
     const long xH = (long)((B + 15) / 16) * 16 * H;
-    SeqLstmFwd q{rs.H16, rs.WhhP, bhh, rs.XG, lens, rs.Hs, rs.Cs, out, rs.GATES, T, B, H, bf16_seq ? 1 : 0, {}};
+    SeqLstmFwd q{rs.H16, rs.WhhP, bhh, rs.XG, lens, rs.Hs, rs.Cs, out, rs.GATES, T, B, H, seq_ot, {}};
     rc = pchain_ctl(&q.ctl.dev, &q.ctl.host, &q.ctl.epoch);
     if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(rs.H16 + xH, sizeof(float) * (size_t)T * xH, s));
@@ -390,7 +390,7 @@ extern "C" int blvm_lstm_seq_fwd(const float* Wih, const float* Whh, const float
     const int rt = (B + 15) / 16, ctH = H / 16;
     const long sH = (long)bh, s4H = 4 * sH, xH = (long)rt * 16 * H;
     Builder bld;
-    bld.p.bf16 = bf16_seq; bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 4;
+    bld.p.ot = seq_ot; bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 4;
     bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = 1;
     Desc& d = bld.add(K_LSTMS, ctH, 0, range_for(ctH * rt, device_cus() & ~7), H, 0, 0, T);
     bld.ptr(d, 0, rs.H16, xH); bld.ptr(d, 1, rs.WhhP); bld.ptr(d, 2, bhh); bld.ptr(d, 3, rs.XG, s4H); bld.ptr(d, 4, lens);
@@ -438,8 +438,8 @@ extern "C" int blvm_lstm_seq_bwd(const float* Wih, const float* Whh, const float
   LstmWs ws;
   carve_lstm_ws(workspace, T, B, H, &ws);
   const size_t n = (size_t)T * B, bh = (size_t)B * H;
-  const bool bf16_seq = pchain_bf16(B) && seq_persistent(T, B);  // bf16-operand mode of the persistent path
-  T16PackScope pack_scope(bf16_seq, s);
+  const OpType seq_ot = seq_persistent(T, B) ? pchain_optype(B) : OP_F32;  // 16-bit operand mode of the persistent path
+  T16PackScope pack_scope(seq_ot, s);
   rc = t16_pack_transposed(Whh, H, 4 * H, H, ws.WhhT, s);
   if (rc) return rc;
   rc = pack_scope.flush();
@@ -447,7 +447,7 @@ extern "C" int blvm_lstm_seq_bwd(const float* Wih, const float* Whh, const float
   BLVM_HIP(hipMemsetAsync(ws.DC, 0, sizeof(float) * bh, s));
   if (seq_persistent(T, B) && (seq_regs_mask() & 2) && 4 * H <= kSeqRegsMaxKBwd && seq_regs_applies(H, 4 * H, H, B, 4)) {
     const long x4H = (long)((B + 15) / 16) * 16 * 4 * H;
-    SeqLstmBwd q{ws.DG16, ws.WhhT, d_out, rs.GATES, rs.Cs, ws.DC, ws.DG, d_h0 ? d_h0 : ws.DC, T, B, H, d_h0 ? T + 1 : T, bf16_seq ? 1 : 0, {}};
+    SeqLstmBwd q{ws.DG16, ws.WhhT, d_out, rs.GATES, rs.Cs, ws.DC, ws.DG, d_h0 ? d_h0 : ws.DC, T, B, H, d_h0 ? T + 1 : T, seq_ot, {}};
     rc = pchain_ctl(&q.ctl.dev, &q.ctl.host, &q.ctl.epoch);
     if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(ws.DG16, sizeof(float) * (size_t)T * x4H, s));
@@ -458,7 +458,7 @@ extern "C" int blvm_lstm_seq_bwd(const float* Wih, const float* Whh, const float
     const int rt = (B + 15) / 16, ctH = H / 16;
     const long sH = (long)bh, s4H = 4 * sH, x4H = (long)rt * 16 * 4 * H;
     Builder bld;
-    bld.p.bf16 = bf16_seq; bld.p.S = d_h0 ? T + 1 : T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 1;
+    bld.p.ot = seq_ot; bld.p.S = d_h0 ? T + 1 : T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 1;
     bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = 1;
     Desc& d = bld.add(K_LSTMSB, ctH, 0, range_for(ctH * rt, device_cus() & ~7), 4 * H, 0, 0, T + 1);
     // step s handles t = T-1-s: time-indexed slabs start at the last step and walk backwards; the T16 slabs are indexed by s
@@ -523,15 +523,15 @@ extern "C" int blvm_gru_seq_fwd(const float* Wih, const float* Whh, const float*
   if (rc) return rc;
   if (h0) BLVM_HIP(hipMemcpyAsync(rs.Hs, h0, sizeof(float) * br, hipMemcpyDeviceToDevice, s));
   else BLVM_HIP(hipMemsetAsync(rs.Hs, 0, sizeof(float) * br, s));
-  const bool bf16_seq = pchain_bf16(B) && seq_persistent(T, B);  // bf16-operand mode of the persistent path
-  T16PackScope pack_scope(bf16_seq, s);
+  const OpType seq_ot = seq_persistent(T, B) ? pchain_optype(B) : OP_F32;  // 16-bit operand mode of the persistent path
+  T16PackScope pack_scope(seq_ot, s);
   rc = t16_pack_rows(Whh, R, 3 * R, R, rs.WhhP, s);  // operand layout of the chain (once per sequence)
   if (rc) return rc;
   rc = pack_scope.flush();
   if (rc) return rc;
   if (seq_persistent(T, B) && (seq_regs_mask() & 1) && seq_regs_applies(R, 3 * R, R, B, 3)) {
     const long xR = (long)((B + 15) / 16) * 16 * R;
-    SeqGruFwd q{rs.H16, rs.WhhP, bhh, rs.XG, lens, rs.Hs, out, rs.RG, rs.UG, rs.NG, rs.GHN, (long)out_ts, out_ld, T, B, R, reverse ? 1 : 0, bf16_seq ? 1 : 0, {}};
+    SeqGruFwd q{rs.H16, rs.WhhP, bhh, rs.XG, lens, rs.Hs, out, rs.RG, rs.UG, rs.NG, rs.GHN, (long)out_ts, out_ld, T, B, R, reverse ? 1 : 0, seq_ot, {}};
     rc = pchain_ctl(&q.ctl.dev, &q.ctl.host, &q.ctl.epoch);
     if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(rs.H16 + xR, sizeof(float) * (size_t)T * xR, s));
@@ -548,7 +548,7 @@ extern "C" int blvm_gru_seq_fwd(const float* Wih, const float* Whh, const float*
     const int rt = (B + 15) / 16, ctR = R / 16;
     const long sR = (long)br, xR = (long)rt * 16 * R;
     Builder bld;
-    bld.p.bf16 = bf16_seq; bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 3;
+    bld.p.ot = seq_ot; bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 3;
     bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = 1;
     Desc& d = bld.add(K_GRUS, ctR, 0, range_for(ctR * rt, device_cus() & ~7), R, 0, 0, T);
     bld.ptr(d, 0, rs.H16, xR); bld.ptr(d, 1, rs.WhhP); bld.ptr(d, 2, bhh); bld.ptr(d, 3, rs.XG); bld.ptr(d, 4, lens); bld.ptr(d, 5, rs.Hs, sR);
@@ -596,8 +596,8 @@ extern "C" int blvm_gru_seq_bwd(const float* Wih, const float* Whh, const float*
   GruWs ws;
   carve_gru_ws(workspace, T, B, R, &ws);
   const size_t n = (size_t)T * B, br = (size_t)B * R;
-  const bool bf16_seq = pchain_bf16(B) && seq_persistent(T, B);  // bf16-operand mode of the persistent path
-  T16PackScope pack_scope(bf16_seq, s);
+  const OpType seq_ot = seq_persistent(T, B) ? pchain_optype(B) : OP_F32;  // 16-bit operand mode of the persistent path
+  T16PackScope pack_scope(seq_ot, s);
   rc = t16_pack_transposed(Whh, R, 3 * R, R, ws.WhhT, s);
   if (rc) return rc;
   rc = pack_scope.flush();
@@ -606,7 +606,7 @@ extern "C" int blvm_gru_seq_bwd(const float* Wih, const float* Whh, const float*
   if (seq_persistent(T, B) && (seq_regs_mask() & 2) && 3 * R <= kSeqRegsMaxKBwd && seq_regs_applies(R, 3 * R, R, B, 3)) {
     const long x3R = (long)((B + 15) / 16) * 16 * 3 * R;
     SeqGruBwd q{ws.DGH16, ws.WhhT, d_out, rs.RG, rs.UG, rs.NG, rs.GHN, rs.Hs, lens, ws.G, ws.DGI, ws.DGH, d_h0 ? d_h0 : ws.G, (long)out_ts, out_ld, T, B, R,
-                reverse ? 1 : 0, d_h0 ? T + 1 : T, bf16_seq ? 1 : 0, {}};
+                reverse ? 1 : 0, d_h0 ? T + 1 : T, seq_ot, {}};
     rc = pchain_ctl(&q.ctl.dev, &q.ctl.host, &q.ctl.epoch);
     if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(ws.DGH16, sizeof(float) * (size_t)T * x3R, s));
@@ -618,7 +618,7 @@ extern "C" int blvm_gru_seq_bwd(const float* Wih, const float* Whh, const float*
     const int rt = (B + 15) / 16, ctR = R / 16;
     const long sR = (long)br, s3R = 3 * sR, x3R = (long)rt * 16 * 3 * R;
     Builder bld;
-    bld.p.bf16 = bf16_seq; bld.p.S = d_h0 ? T + 1 : T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 1;
+    bld.p.ot = seq_ot; bld.p.S = d_h0 ? T + 1 : T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 1;
     bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = 1;
     Desc& d = bld.add(K_GRUSB, ctR, 0, range_for(ctR * rt, device_cus() & ~7), 3 * R, 0, 0, T + 1);
     // step s handles recurrence step j = T-1-s: the saves walk backwards from their last slab; the T16 slabs are indexed by s

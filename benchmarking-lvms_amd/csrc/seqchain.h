@@ -18,7 +18,7 @@ struct SeqGruFwd {
   const int32_t* lens;
   float *Hs, *out, *rg, *ug, *ng, *ghn;  // [T+1,B,R] row-major states; time-indexed outputs; per-step saves [T,B,R]
   long out_ts;
-  int out_ld, T, B, R, reverse, bf16;
+  int out_ld, T, B, R, reverse, ot;  // ot: operand type (OpType) of the products; 16-bit: Whh is a 16-bit T16 pack
   pchain::Ctl ctl;
 };
 struct SeqGruBwd {
@@ -26,20 +26,20 @@ struct SeqGruBwd {
   const int32_t* lens;
   float *G, *DGI, *DGH, *dh0;  // G [B,R] in place; DGI [T,B,3R] time indexed; DGH [T,B,3R] step indexed
   long out_ts;
-  int out_ld, T, B, R, reverse, steps, bf16;  // steps = T + 1 when dh0 is wanted
+  int out_ld, T, B, R, reverse, steps, ot;  // steps = T + 1 when dh0 is wanted
   pchain::Ctl ctl;
 };
 struct SeqLstmFwd {
   const float *H16, *Whh, *bhh, *xg;  // xg [T,B,4H]
   const int32_t* lens;
   float *Hs, *Cs, *out, *gates;       // [T+1,B,H] x2, [T,B,H], [T,B,4H]
-  int T, B, H, bf16;
+  int T, B, H, ot;
   pchain::Ctl ctl;
 };
 struct SeqLstmBwd {
   const float *DG16, *WhhT, *dout, *gates, *Cs;
   float *DC, *DG, *dh0;               // DC [B,H] in place; DG [T,B,4H] step indexed
-  int T, B, H, steps, bf16;
+  int T, B, H, steps, ot;
   pchain::Ctl ctl;
 };
 

@@ -8,11 +8,11 @@ constexpr int NW = 8;
 
 // acc[g] += A[r0+i][k] W[g][c0[g]+j][k] over this wave's NCH k-chunks (chunk numbers wave, wave + NW, ...): A polled from a T16 slab
 // (sentinel protocol of pchain.h), W from the registers `w` (loaded once by load_w).  `mid` runs behind the first poll's loads.
-template <bool BF, int G, int NCH>
-__device__ __forceinline__ void load_w(typename WFrag<BF>::type (&w)[G][NCH], const float* W, const int (&c0)[G], int K) {
-  typedef typename WFrag<BF>::type wfrag;
+template <int OT, int G, int NCH>
+__device__ __forceinline__ void load_w(typename WFrag<OT>::type (&w)[G][NCH], const float* W, const int (&c0)[G], int K) {
+  typedef typename WFrag<OT>::type wfrag;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr int ES = BF ? 2 : 4;
+  constexpr int ES = OT != OP_F32 ? 2 : 4;
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const char* base = reinterpret_cast<const char*>(W) + (size_t)ES * ((size_t)c0[g] * K + 4 * lane);
@@ -26,8 +26,8 @@ __device__ __forceinline__ void load_w(typename WFrag<BF>::type (&w)[G][NCH], co
 // brings a line into the XCD's L2, the others hit it, and the fabric carries the slab once per XCD instead of once per tile.  Every
 // word is still validated: a fragment that holds a sentinel (a line cached before its last store landed) is re-read with sc1 loads,
 // which bypass the stale line.
-template <bool BF, int G, int NCH, bool SHARED, class Mid>
-__device__ __forceinline__ void product(const float* A16, int r0, int nrows, int K, const typename WFrag<BF>::type (&w)[G][NCH], f32x4 (&acc)[G], Poll& pl,
+template <int OT, int G, int NCH, bool SHARED, class Mid>
+__device__ __forceinline__ void product(const float* A16, int r0, int nrows, int K, const typename WFrag<OT>::type (&w)[G][NCH], f32x4 (&acc)[G], Poll& pl,
                                         Mid mid) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool aok = (r0 + (lane & 15)) < nrows;
@@ -60,13 +60,13 @@ __device__ __forceinline__ void product(const float* A16, int r0, int nrows, int
     pl.sleep();
   }
 multiply:
-  if constexpr (BF) {
+  if constexpr (OT != OP_F32) {
 #pragma unroll
     for (int u = 0; u < NCH; ++u) {
-      const u32x2 q = {aok ? pk_bf16(a[u][0], a[u][1]) : 0u, aok ? pk_bf16(a[u][2], a[u][3]) : 0u};
+      const u32x2 q = {aok ? pk16<OT>(a[u][0], a[u][1]) : 0u, aok ? pk16<OT>(a[u][2], a[u][3]) : 0u};
       const s16x4 ab = __builtin_bit_cast(s16x4, q);
 #pragma unroll
-      for (int g = 0; g < G; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ab, __builtin_bit_cast(s16x4, w[g][u]), acc[g], 0, 0, 0);
+      for (int g = 0; g < G; ++g) acc[g] = mfma16<OT>(ab, __builtin_bit_cast(s16x4, w[g][u]), acc[g]);
     }
   } else {
 #pragma unroll
@@ -84,7 +84,7 @@ __device__ __forceinline__ TileAt my_tile(int B) {
   return TileAt{(int)(blockIdx.x % rt) * 16, (int)(blockIdx.x / rt) * 16};
 }
 
-template <bool BF, int NCH>
+template <int OT, int NCH>
 __global__ __launch_bounds__(NW * 64, 1) void gru_fwd_kernel(SeqGruFwd a) {
   __shared__ float red[2][3 * NW * 256];
   const TileAt tl = my_tile(a.B);
@@ -93,10 +93,10 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_fwd_kernel(SeqGruFwd a) {
   const bool own = threadIdx.x < 256 && row < B;
   const int rowc = row < B ? row : r0;
   const size_t o = (size_t)rowc * R + col, sR = (size_t)B * R, xR = (size_t)((B + 15) / 16) * 16 * R;
-  typename WFrag<BF>::type w[3][NCH];
+  typename WFrag<OT>::type w[3][NCH];
   {
     const int cs[3] = {c0, R + c0, 2 * R + c0};
-    load_w<BF, 3, NCH>(w, a.Whh, cs, R);
+    load_w<OT, 3, NCH>(w, a.Whh, cs, R);
   }
   const float b0 = a.bhh[col], b1 = a.bhh[R + col], b2 = a.bhh[2 * R + col];
   Poll pl{a.ctl, 0u, false, 1};
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_fwd_kernel(SeqGruFwd a) {
       hp = a.Hs[(size_t)j * sR + o];
     };
     f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    product<BF, 3, NCH, false>(a.H16 + (size_t)j * xR, r0, B, R, w, acc, pl, prefetch);
+    product<OT, 3, NCH, false>(a.H16 + (size_t)j * xR, r0, B, R, w, acc, pl, prefetch);
     float v[3];
     reduce_tiles<3, NW>(acc, red[j & 1], v);
     if (!own) continue;
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_fwd_kernel(SeqGruFwd a) {
   }
 }
 
-template <bool BF, int NCH>
+template <int OT, int NCH>
 __global__ __launch_bounds__(NW * 64, 1) void gru_bwd_kernel(SeqGruBwd a) {
   __shared__ float red[2][NW * 256];
   const TileAt tl = my_tile(a.B);
@@ -139,10 +139,10 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_bwd_kernel(SeqGruBwd a) {
   const bool own = threadIdx.x < 256 && row < B;
   const int rowc = row < B ? row : r0;
   const size_t o = (size_t)rowc * R + col, sR = (size_t)B * R, x3R = (size_t)((B + 15) / 16) * 16 * 3 * R;
-  typename WFrag<BF>::type w[1][NCH];
+  typename WFrag<OT>::type w[1][NCH];
   {
     const int cs[1] = {c0};
-    load_w<BF, 1, NCH>(w, a.WhhT, cs, 3 * R);
+    load_w<OT, 1, NCH>(w, a.WhhT, cs, 3 * R);
   }
   Poll pl{a.ctl, 0u, false, 1};
   float g = own ? a.G[o] : 0.f;  // the running gradient through the u-gate path: this thread's for the whole sequence
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_bwd_kernel(SeqGruBwd a) {
     float v[1] = {0.f};
     if (has_gemm) {  // uniform
       f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
-      product<BF, 1, NCH, (NCH >= 12)>(a.DGH16 + (size_t)(s - 1) * x3R, r0, B, 3 * R, w, acc, pl, prefetch);
+      product<OT, 1, NCH, (NCH >= 12)>(a.DGH16 + (size_t)(s - 1) * x3R, r0, B, 3 * R, w, acc, pl, prefetch);
       reduce_tiles<1, NW>(acc, red[s & 1], v);
     } else {
       prefetch();
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_bwd_kernel(SeqGruBwd a) {
   if (own) a.G[o] = g;
 }
 
-template <bool BF, int NCH>
+template <int OT, int NCH>
 __global__ __launch_bounds__(NW * 64, 1) void lstm_fwd_kernel(SeqLstmFwd a) {
   __shared__ float red[2][4 * NW * 256];
   const TileAt tl = my_tile(a.B);
@@ -194,10 +194,10 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_fwd_kernel(SeqLstmFwd a) {
   const bool own = threadIdx.x < 256 && row < B;
   const int rowc = row < B ? row : r0;
   const size_t o = (size_t)rowc * H + col, o4 = (size_t)rowc * 4 * H + col, sH = (size_t)B * H, xH = (size_t)((B + 15) / 16) * 16 * H;
-  typename WFrag<BF>::type w[4][NCH];
+  typename WFrag<OT>::type w[4][NCH];
   {
     const int cs[4] = {c0, H + c0, 2 * H + c0, 3 * H + c0};
-    load_w<BF, 4, NCH>(w, a.Whh, cs, H);
+    load_w<OT, 4, NCH>(w, a.Whh, cs, H);
   }
   const float b0 = a.bhh[col], b1 = a.bhh[H + col], b2 = a.bhh[2 * H + col], b3 = a.bhh[3 * H + col];
   const int len = a.lens != nullptr ? a.lens[rowc] : a.T;
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_fwd_kernel(SeqLstmFwd a) {
       hp = a.Hs[(size_t)t * sH + o];
     };
     f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    product<BF, 4, NCH, false>(a.H16 + (size_t)t * xH, r0, B, H, w, acc, pl, prefetch);
+    product<OT, 4, NCH, false>(a.H16 + (size_t)t * xH, r0, B, H, w, acc, pl, prefetch);
     float v[4];
     reduce_tiles<4, NW>(acc, red[t & 1], v);
     if (!own) continue;
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_fwd_kernel(SeqLstmFwd a) {
   }
 }
 
-template <bool BF, int NCH>
+template <int OT, int NCH>
 __global__ __launch_bounds__(NW * 64, 1) void lstm_bwd_kernel(SeqLstmBwd a) {
   __shared__ float red[2][NW * 256];
   const TileAt tl = my_tile(a.B);
@@ -239,10 +239,10 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_bwd_kernel(SeqLstmBwd a) {
   const bool own = threadIdx.x < 256 && row < B;
   const int rowc = row < B ? row : r0;
   const size_t o = (size_t)rowc * H + col, o4 = (size_t)rowc * 4 * H + col, sH = (size_t)B * H, x4H = (size_t)((B + 15) / 16) * 16 * 4 * H;
-  typename WFrag<BF>::type w[1][NCH];
+  typename WFrag<OT>::type w[1][NCH];
   {
     const int cs[1] = {c0};
-    load_w<BF, 1, NCH>(w, a.WhhT, cs, 4 * H);
+    load_w<OT, 1, NCH>(w, a.WhhT, cs, 4 * H);
   }
   Poll pl{a.ctl, 0u, false, 1};
   float dc = own ? a.DC[o] : 0.f;  // running gradient wrt the cell state
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_bwd_kernel(SeqLstmBwd a) {
     float v[1] = {0.f};
     if (has_gemm) {  // uniform
       f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
-      product<BF, 1, NCH, (NCH >= 12)>(a.DG16 + (size_t)(s - 1) * x4H, r0, B, 4 * H, w, acc, pl, prefetch);
+      product<OT, 1, NCH, (NCH >= 12)>(a.DG16 + (size_t)(s - 1) * x4H, r0, B, 4 * H, w, acc, pl, prefetch);
       reduce_tiles<1, NW>(acc, red[s & 1], v);
     } else {
       prefetch();
@@ -285,18 +285,22 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_bwd_kernel(SeqLstmBwd a) {
 
 inline bool nch_ok(int nch) { return nch == 1 || nch == 2 || nch == 3 || nch == 4 || nch == 6 || nch == 8 || nch == 12; }
 
-#define SEQ_LAUNCH(kernel, nch, bf, grid, s, args)                                                                                  \
-  do {                                                                                                                              \
-    switch (nch) {                                                                                                                  \
-      case 1: if (bf) hipLaunchKernelGGL((kernel<true, 1>), grid, dim3(NW * 64), 0, s, args); else hipLaunchKernelGGL((kernel<false, 1>), grid, dim3(NW * 64), 0, s, args); break;   \
-      case 2: if (bf) hipLaunchKernelGGL((kernel<true, 2>), grid, dim3(NW * 64), 0, s, args); else hipLaunchKernelGGL((kernel<false, 2>), grid, dim3(NW * 64), 0, s, args); break;   \
-      case 3: if (bf) hipLaunchKernelGGL((kernel<true, 3>), grid, dim3(NW * 64), 0, s, args); else hipLaunchKernelGGL((kernel<false, 3>), grid, dim3(NW * 64), 0, s, args); break;   \
-      case 4: if (bf) hipLaunchKernelGGL((kernel<true, 4>), grid, dim3(NW * 64), 0, s, args); else hipLaunchKernelGGL((kernel<false, 4>), grid, dim3(NW * 64), 0, s, args); break;   \
-      case 6: if (bf) hipLaunchKernelGGL((kernel<true, 6>), grid, dim3(NW * 64), 0, s, args); else hipLaunchKernelGGL((kernel<false, 6>), grid, dim3(NW * 64), 0, s, args); break;   \
-      case 8: if (bf) hipLaunchKernelGGL((kernel<true, 8>), grid, dim3(NW * 64), 0, s, args); else hipLaunchKernelGGL((kernel<false, 8>), grid, dim3(NW * 64), 0, s, args); break;   \
-      case 12: if (bf) hipLaunchKernelGGL((kernel<true, 12>), grid, dim3(NW * 64), 0, s, args); else hipLaunchKernelGGL((kernel<false, 12>), grid, dim3(NW * 64), 0, s, args); break; \
-      default: set_error("seqchain: %d k-chunks per wave are not instantiated", nch); return BLVM_ENOSUP;                           \
-    }                                                                                                                               \
+#define SEQ_LAUNCH_OT(kernel, N, ot, grid, s, args)                                                                  \
+  if ((ot) == OP_BF16) hipLaunchKernelGGL((kernel<OP_BF16, N>), grid, dim3(NW * 64), 0, s, args);                     \
+  else if ((ot) == OP_F16) hipLaunchKernelGGL((kernel<OP_F16, N>), grid, dim3(NW * 64), 0, s, args);                  \
+  else hipLaunchKernelGGL((kernel<OP_F32, N>), grid, dim3(NW * 64), 0, s, args)
+#define SEQ_LAUNCH(kernel, nch, ot, grid, s, args)                                                                     \
+  do {                                                                                                                 \
+    switch (nch) {                                                                                                     \
+      case 1: SEQ_LAUNCH_OT(kernel, 1, ot, grid, s, args); break;                                                      \
+      case 2: SEQ_LAUNCH_OT(kernel, 2, ot, grid, s, args); break;                                                      \
+      case 3: SEQ_LAUNCH_OT(kernel, 3, ot, grid, s, args); break;                                                      \
+      case 4: SEQ_LAUNCH_OT(kernel, 4, ot, grid, s, args); break;                                                      \
+      case 6: SEQ_LAUNCH_OT(kernel, 6, ot, grid, s, args); break;                                                      \
+      case 8: SEQ_LAUNCH_OT(kernel, 8, ot, grid, s, args); break;                                                      \
+      case 12: SEQ_LAUNCH_OT(kernel, 12, ot, grid, s, args); break;                                                    \
+      default: set_error("seqchain: %d k-chunks per wave are not instantiated", nch); return BLVM_ENOSUP;              \
+    }                                                                                                                  \
   } while (0)
 
 }  // namespace
@@ -315,25 +319,25 @@ bool seq_regs_applies(int K_fwd, int K_bwd, int hidden, int B, int gates) {
 
 int seq_gru_fwd(const SeqGruFwd& a, hipStream_t s) {
   const dim3 grid((unsigned)((a.R / 16) * ((a.B + 15) / 16)));
-  SEQ_LAUNCH(gru_fwd_kernel, a.R / (NW * 16), a.bf16 != 0, grid, s, a);
+  SEQ_LAUNCH(gru_fwd_kernel, a.R / (NW * 16), a.ot, grid, s, a);
   BLVM_CHECK_LAUNCH("seq_gru_fwd");
   return BLVM_OK;
 }
 int seq_gru_bwd(const SeqGruBwd& a, hipStream_t s) {
   const dim3 grid((unsigned)((a.R / 16) * ((a.B + 15) / 16)));
-  SEQ_LAUNCH(gru_bwd_kernel, 3 * a.R / (NW * 16), a.bf16 != 0, grid, s, a);
+  SEQ_LAUNCH(gru_bwd_kernel, 3 * a.R / (NW * 16), a.ot, grid, s, a);
   BLVM_CHECK_LAUNCH("seq_gru_bwd");
   return BLVM_OK;
 }
 int seq_lstm_fwd(const SeqLstmFwd& a, hipStream_t s) {
   const dim3 grid((unsigned)((a.H / 16) * ((a.B + 15) / 16)));
-  SEQ_LAUNCH(lstm_fwd_kernel, a.H / (NW * 16), a.bf16 != 0, grid, s, a);
+  SEQ_LAUNCH(lstm_fwd_kernel, a.H / (NW * 16), a.ot, grid, s, a);
   BLVM_CHECK_LAUNCH("seq_lstm_fwd");
   return BLVM_OK;
 }
 int seq_lstm_bwd(const SeqLstmBwd& a, hipStream_t s) {
   const dim3 grid((unsigned)((a.H / 16) * ((a.B + 15) / 16)));
-  SEQ_LAUNCH(lstm_bwd_kernel, 4 * a.H / (NW * 16), a.bf16 != 0, grid, s, a);
+  SEQ_LAUNCH(lstm_bwd_kernel, 4 * a.H / (NW * 16), a.ot, grid, s, a);
   BLVM_CHECK_LAUNCH("seq_lstm_bwd");
   return BLVM_OK;
 }

@@ -75,7 +75,7 @@ extern "C" int blvm_srnn_generate(const BlvmSrnnDecodeWeights* w, const float* x
   const BlvmSrnnWeights* c = w->chain;
   const SdPack p = sd_pack_layout(S, H, Z, R);
   const SdBufs b = sd_layout(p.total, T, B, S, H, Z, R);
-  T16PackScope pack_scope(pchain_bf16(B), s);
+  T16PackScope pack_scope(pchain_optype(B), s);
   int rc;
 #define PACK(dst, src, ld, rows, k)                               \
   do {                                                            \
@@ -99,7 +99,7 @@ extern "C" int blvm_srnn_generate(const BlvmSrnnDecodeWeights* w, const float* x
   const int r_side = range_for(3 * ctR * rt, std::min(cus / 4, 64));  // the hidden projection of the NEXT step: off the critical path
   const int r_main = cus - r_side;
   Builder bld;
-  bld.p.bf16 = pchain_bf16(B);
+  bld.p.ot = pchain_optype(B);
   bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 4;
   bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = r_main;
   // out = leaky(A W^T + bias): A a polled T16 slab of `a_n16` blocks per row tile, outputs: T16 slab(s) and / or row-major (polled words)

@@ -151,7 +151,7 @@ inline int vrnn_rt_max_b() {
 }
 inline int vrnn_rt(int B) {
   static const int min_b = [] { const char* e = getenv("BLVM_PCHAIN_RT_MIN_B"); return e ? atoi(e) : 65; }();
-  if (B < min_b || B > vrnn_rt_max_b() || pchain_max_batch() <= 0 || operand_bf16()) return 0;
+  if (B < min_b || B > vrnn_rt_max_b() || pchain_max_batch() <= 0 || operand_16bit()) return 0;
   if (B <= kPchainCarveMaxB && B > pchain_max_batch()) return 0;
   return 2;
 }
@@ -323,7 +323,7 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   if (rc) return rc;
 
   // T16 operand copies of the chain's weights (once per sequence)
-  T16PackScope pack_scope(pchain_bf16(B), s);  // bf16-operand mode: the persistent launch multiplies bf16 weight packs
+  T16PackScope pack_scope(pchain_optype(B), s);  // 16-bit operand modes: the persistent launch multiplies 16-bit weight packs
   rc = t16_pack_rows(w->prior_w[0], R, H, R, rs.Wp[0], s); if (rc) return rc;
   rc = t16_pack_rows(w->post_w[0], R + X, H, R, rs.Wq[0], s); if (rc) return rc;  // the h columns
   for (int l = 1; l < 3; ++l) {
@@ -364,7 +364,7 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     const int half = range_for(ctH * tl, (cus - def_n) / 2);            // prior | posterior halves of a link
     const int g = 2 * half;
     Builder bld;
-    bld.p.bf16 = pchain_bf16(B);
+    bld.p.ot = pchain_optype(B);
     bld.p.rt_group = RTG;
     bld.p.S = Tp; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = groups ? 8 : 4;
     bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = g;
@@ -528,7 +528,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   const float beta = (float)(0.6931471805599453 / (1.0 - (double)sd_eps));
 
   // transposed T16 operand copies of every weight the chain multiplies from the right
-  T16PackScope pack_scope(pchain_bf16(B), s);  // bf16-operand mode: the persistent launch multiplies bf16 weight packs
+  T16PackScope pack_scope(pchain_optype(B), s);  // 16-bit operand modes: the persistent launch multiplies 16-bit weight packs
   rc = t16_pack_transposed(w->prior_w[0], R, H, R, ws.pT[0], s); if (rc) return rc;
   rc = t16_pack_transposed(w->prior_w[1], H, H, H, ws.pT[1], s); if (rc) return rc;
   rc = t16_pack_transposed(w->prior_w[2], H, H, H, ws.pT[2], s); if (rc) return rc;
@@ -625,7 +625,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     const int half = range_for(ctH * tl, (cus - def_n) / 2), g = 2 * half;
     const int wide = shared ? half : g;  // range of the links between the GRU backward and the heads
     Builder bld;
-    bld.p.bf16 = pchain_bf16(B);
+    bld.p.ot = pchain_optype(B);
     bld.p.rt_group = RTG;
     bld.p.S = T + 1; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = groups ? 8 : 2;
     bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = g;
@@ -655,7 +655,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     const int spare = cus - g - def_n;
     const bool split3 = !shared && spare >= 8 && half >= 8 && pchain_split3();
     if (split3) {
-      const size_t wthird = (size_t)ctR * 256 / (bld.p.bf16 ? 2 : 1);  // the packed weight's k-chunks [ctR * part, ...) (bf16 packs: half the floats)
+      const size_t wthird = (size_t)ctR * 256 / (bld.p.ot != OP_F32 ? 2 : 1);  // the packed weight's k-chunks [ctR * part, ...) (16-bit packs: half the floats)
       float* const orm[3] = {ws.DPHI[3], ws.DPHI3b, ws.DPHI3c};
       float* const o16[3] = {ws.DPHI16[3], ws.DPHI16b, ws.DPHI16c};
       const int wg0s[3] = {0, half, g + def_n}, nwgs[3] = {range_for(ctH * tl, half), range_for(ctH * tl, half), range_for(ctH * tl, spare)};

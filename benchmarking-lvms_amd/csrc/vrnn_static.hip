@@ -388,7 +388,7 @@ int static_go(Kern kernel, int slot, int grid, size_t lds, const char* what) {
 
 // 1: the program is not the linear chain the static kernel was compiled for
 int static_lin_chain_launch(const Program& p, hipStream_t stream) {
-  if (p.ndesc != 1 || p.bf16 || p.rt_group != 1 || !int_strides(p)) return 1;
+  if (p.ndesc != 1 || p.ot != OP_F32 || p.rt_group != 1 || !int_strides(p)) return 1;
   const Desc& d = p.d[0];
   if (d.kind != K_LIN || d.flags != DF_RELU || d.f[0] != 0.f || (d.K != 256 && d.K != 512) || d.s_begin != 0 || d.s_end != p.S) return 1;
   if (d.ld[0] != 0 || d.i[0] != 0 || d.p[3] || d.p[4] || d.p[7] || d.p[8] || d.p[9] || d.n16[1] != 0) return 1;
@@ -439,7 +439,7 @@ SeqArgs seq_args(const Program& p, const Desc& d) {
 
 // 1: not the shape the static kernels were compiled for (the caller runs pchain_launch)
 int vrnn_static_check(const Program& p, int ndesc, int products) {
-  if (!pchain_static_on() || p.ndesc != ndesc || p.bf16 || p.rt_group != 1 || p.s_first != 0 || p.B > 64) return 1;
+  if (!pchain_static_on() || p.ndesc != ndesc || p.ot != OP_F32 || p.rt_group != 1 || p.s_first != 0 || p.B > 64) return 1;
   if (p.lds_products != products || !int_strides(p)) return 1;  // (the kernels' reduction scratch is sized for `products`)
   for (int i = 0; i < p.ndesc; ++i)
     if (!few_tiles(p, p.d[i])) return 1;

@@ -154,23 +154,39 @@ struct FusedFwdArgs {
 __device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // Two interleaved 16x16 products over the 4 k-values a lane holds of each operand (w = weights as the A operand, x = data as the B
-// operand).  fp32: four v_mfma_f32_16x16x4_f32 per product, the two accumulator chains alternating; BF (operand_bf16(), the
-// reference's --use_amp regime, experiments/experiment_wavenet_audio.py): the same 4 k-values rounded to bf16 are exactly one
-// v_mfma_f32_16x16x16_bf16 per product — a quarter of the matrix-pipe time of kernels whose fp32 form is bound by it.
+// operand).  fp32: four v_mfma_f32_16x16x4_f32 per product, the two accumulator chains alternating; OT = OP_BF16 / OP_F16
+// (operand_type(), the reference's --use_amp regime, experiments/experiment_wavenet_audio.py): the same 4 k-values rounded to bf16 /
+// fp16 (nearest even) are exactly one v_mfma_f32_16x16x16_bf16 / _f16 per product — a quarter of the matrix-pipe time of kernels
+// whose fp32 form is bound by it.
 typedef short wn_s16x4 __attribute__((ext_vector_type(4)));
 typedef float wn_f2 __attribute__((ext_vector_type(2)));
 typedef __bf16 wn_b2 __attribute__((ext_vector_type(2)));
+typedef _Float16 wn_h2 __attribute__((ext_vector_type(2)));
+typedef _Float16 wn_h4 __attribute__((ext_vector_type(4)));
 typedef unsigned wn_u2 __attribute__((ext_vector_type(2)));
+template <int OT>
+__device__ __forceinline__ unsigned wn_pk2(float a, float b) {
+  if constexpr (OT == OP_F16) return __builtin_bit_cast(unsigned, __builtin_convertvector((wn_f2){a, b}, wn_h2));
+  else return __builtin_bit_cast(unsigned, __builtin_convertvector((wn_f2){a, b}, wn_b2));
+}
+template <int OT>
 __device__ __forceinline__ wn_s16x4 pk4(float a, float b, float c, float d) {
-  const wn_u2 q = {__builtin_bit_cast(unsigned, __builtin_convertvector((wn_f2){a, b}, wn_b2)), __builtin_bit_cast(unsigned, __builtin_convertvector((wn_f2){c, d}, wn_b2))};
+  const wn_u2 q = {wn_pk2<OT>(a, b), wn_pk2<OT>(c, d)};
   return __builtin_bit_cast(wn_s16x4, q);
 }
-__device__ __forceinline__ wn_s16x4 pk4(const float4& v) { return pk4(v.x, v.y, v.z, v.w); }
-template <bool BF>
+template <int OT>
+__device__ __forceinline__ wn_s16x4 pk4(const float4& v) { return pk4<OT>(v.x, v.y, v.z, v.w); }
+template <int OT>
+__device__ __forceinline__ f32x4 wn_mfma16(wn_s16x4 a, wn_s16x4 b, f32x4 acc) {
+  if constexpr (OT == OP_F16)
+    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(wn_h4, a), __builtin_bit_cast(wn_h4, b), acc, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, acc, 0, 0, 0);
+}
+template <int OT>
 __device__ __forceinline__ void mma4x2(f32x4& a0, const float4& w0, const float4& x0, f32x4& a1, const float4& w1, const float4& x1) {
-  if constexpr (BF) {
-    a0 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pk4(w0), pk4(x0), a0, 0, 0, 0);
-    a1 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pk4(w1), pk4(x1), a1, 0, 0, 0);
+  if constexpr (OT != OP_F32) {
+    a0 = wn_mfma16<OT>(pk4<OT>(w0), pk4<OT>(x0), a0);
+    a1 = wn_mfma16<OT>(pk4<OT>(w1), pk4<OT>(x1), a1);
   } else {
     a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, x0.x, a0, 0, 0, 0);
     a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, x1.x, a1, 0, 0, 0);
@@ -183,7 +199,7 @@ __device__ __forceinline__ void mma4x2(f32x4& a0, const float4& w0, const float4
   }
 }
 
-template <int C, int S, bool BF>
+template <int C, int S, int OT>
 __global__ __launch_bounds__(256, 2) void wn_block_fused_fwd_kernel(FusedFwdArgs a) {
   constexpr int LDX = C + 4, KC = C / 16, NT = C / 16, NR = (C + S) / 16;
   constexpr int WAVE_FLOATS = 16 * 3 * LDX;
@@ -281,8 +297,8 @@ __global__ __launch_bounds__(256, 2) void wn_block_fused_fwd_kernel(FusedFwdArgs
     for (int j = 0; j < JH; ++j) {
       const float4 x0 = *reinterpret_cast<const float4*>(ap0 + 16 * (j0 + j));
       const float4 x1 = *reinterpret_cast<const float4*>(ap1 + 16 * (j0 + j));
-      mma4x2<BF>(aT, F.t0[j], x0, aS, F.s0[j], x0);
-      mma4x2<BF>(aT, F.t1[j], x1, aS, F.s1[j], x1);
+      mma4x2<OT>(aT, F.t0[j], x0, aS, F.s0[j], x0);
+      mma4x2<OT>(aT, F.t1[j], x1, aS, F.s1[j], x1);
     }
     if (j0 + JH < KC) return;
     // weights as the A operand: the accumulator holds data row lane & 15, channels 4 (lane >> 4) + r — 16-byte pieces of a row
@@ -332,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void wn_block_fused_fwd_kernel(FusedFwdArgs
 #pragma unroll
     for (int j = 0; j < KC; ++j) {
       const float4 v = *reinterpret_cast<const float4*>(ap + 16 * j);
-      mma4x2<BF>(c0, G.f0[j], v, c1, G.f1[j], v);
+      mma4x2<OT>(c0, G.f0[j], v, c1, G.f1[j], v);
     }
     if (!live) return;
 #pragma unroll
@@ -370,7 +386,10 @@ template <int C, int S>
 int launch_fused_fwd(const FusedFwdArgs& a, hipStream_t s) {
   constexpr size_t lds = sizeof(float) * 4 * 16 * 3 * (C + 4);
   static_assert(2 * lds <= 160 * 1024, "fused WaveNet block: two workgroups per CU");
-  auto kern = operand_bf16() ? wn_block_fused_fwd_kernel<C, S, true> : wn_block_fused_fwd_kernel<C, S, false>;
+  const OpType ot = operand_type();
+  auto kern = ot == OP_BF16  ? wn_block_fused_fwd_kernel<C, S, OP_BF16>
+              : ot == OP_F16 ? wn_block_fused_fwd_kernel<C, S, OP_F16>
+                             : wn_block_fused_fwd_kernel<C, S, OP_F32>;
   if (lds > 64 * 1024) BLVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const size_t tiles = (a.rows + 63) / 64;
   BLVM_REQUIRE(tiles < (1ull << 31), "wavenet_block_fwd: too many rows");
@@ -402,7 +421,7 @@ struct FusedBwdAArgs {
   float inv_std;
 };
 
-template <int C, int S, bool BF>
+template <int C, int S, int OT>
 __global__ __launch_bounds__(256, 2) void wn_block_fused_bwd_a_kernel(FusedBwdAArgs a) {
   constexpr int W = C + S, LDR = W + 4, KR = W / 16, NT = C / 16, KH = KR / 2;
   constexpr int NP = (16 * W / 4 + 63) / 64;
@@ -461,7 +480,7 @@ __global__ __launch_bounds__(256, 2) void wn_block_fused_bwd_a_kernel(FusedBwdAA
     for (int j = 0; j < KH; ++j) {
       const float4 u = *reinterpret_cast<const float4*>(ap + 16 * j);
       const float4 v = *reinterpret_cast<const float4*>(ap + 16 * (KH + j));
-      mma4x2<BF>(c0, F.f[j], u, c1, F.f[KH + j], v);
+      mma4x2<OT>(c0, F.f[j], u, c1, F.f[KH + j], v);
     }
     // accumulators: data row lane & 15, channels 4 (lane >> 4) + r
     const size_t gr = r0 + rr;
@@ -495,7 +514,7 @@ struct FusedBwdBArgs {
   float inv_std;
 };
 
-template <int C, bool BF>
+template <int C, int OT>
 __global__ __launch_bounds__(256, 2) void wn_block_fused_bwd_b_kernel(FusedBwdBArgs a) {
   constexpr int K2 = 2 * C, LDA = K2 + 4, KR = K2 / 16, NT = C / 16, KH = KR / 2;
   constexpr int NP = (16 * K2 / 4 + 63) / 64;
@@ -539,7 +558,7 @@ __global__ __launch_bounds__(256, 2) void wn_block_fused_bwd_b_kernel(FusedBwdBA
     for (int j = 0; j < KH; ++j) {
       const float4 u = *reinterpret_cast<const float4*>(ap + 16 * j);
       const float4 v = *reinterpret_cast<const float4*>(ap + 16 * (KH + j));
-      mma4x2<BF>(c, F.f[j], u, c1, F.f[KH + j], v);
+      mma4x2<OT>(c, F.f[j], u, c1, F.f[KH + j], v);
     }
     c += c1;
   };
@@ -581,12 +600,16 @@ int launch_fused_bwd(const FusedBwdAArgs& aa, const FusedBwdBArgs& ab, hipStream
   static_assert(2 * lds_a <= 160 * 1024 && 2 * lds_b <= 160 * 1024, "fused WaveNet block backward: two workgroups per CU");
   const size_t ta = (aa.rows + 63) / 64, tb = (ab.rows + ab.shift + 63) / 64;
   BLVM_REQUIRE(tb < (1ull << 31), "wavenet_block_bwd: too many rows");
-  if (operand_bf16()) {
-    hipLaunchKernelGGL((wn_block_fused_bwd_a_kernel<C, S, true>), dim3((unsigned)ta), dim3(256), lds_a, s, aa);
-    hipLaunchKernelGGL((wn_block_fused_bwd_b_kernel<C, true>), dim3((unsigned)tb), dim3(256), lds_b, s, ab);
+  const OpType ot = operand_type();
+  if (ot == OP_BF16) {
+    hipLaunchKernelGGL((wn_block_fused_bwd_a_kernel<C, S, OP_BF16>), dim3((unsigned)ta), dim3(256), lds_a, s, aa);
+    hipLaunchKernelGGL((wn_block_fused_bwd_b_kernel<C, OP_BF16>), dim3((unsigned)tb), dim3(256), lds_b, s, ab);
+  } else if (ot == OP_F16) {
+    hipLaunchKernelGGL((wn_block_fused_bwd_a_kernel<C, S, OP_F16>), dim3((unsigned)ta), dim3(256), lds_a, s, aa);
+    hipLaunchKernelGGL((wn_block_fused_bwd_b_kernel<C, OP_F16>), dim3((unsigned)tb), dim3(256), lds_b, s, ab);
   } else {
-    hipLaunchKernelGGL((wn_block_fused_bwd_a_kernel<C, S, false>), dim3((unsigned)ta), dim3(256), lds_a, s, aa);
-    hipLaunchKernelGGL((wn_block_fused_bwd_b_kernel<C, false>), dim3((unsigned)tb), dim3(256), lds_b, s, ab);
+    hipLaunchKernelGGL((wn_block_fused_bwd_a_kernel<C, S, OP_F32>), dim3((unsigned)ta), dim3(256), lds_a, s, aa);
+    hipLaunchKernelGGL((wn_block_fused_bwd_b_kernel<C, OP_F32>), dim3((unsigned)tb), dim3(256), lds_b, s, ab);
   }
   return BLVM_OK;
 }
@@ -613,7 +636,7 @@ struct TsArgs {
 // output — NSPLIT = taps * (C/16) / NPW workgroups share a slice of rows (all on one XCD, so the slice's A rows come from HBM once)
 // and there are NSPLIT times fewer row slices for the same number of workgroups, i.e. NSPLIT times fewer atomic adds on the same
 // [2C, C(, 2)] words: with 512 slices of 8 chunks each the kernel spent 171 us in 18.9 M contended atomics for 30 us of MFMA.
-template <int C, bool DUAL, bool BF, int NPW>
+template <int C, bool DUAL, int OT, int NPW>
 __global__ __launch_bounds__(256) void wn_ts_wgrad_kernel(TsArgs a) {
   constexpr bool SPLIT = NPW < C / 16;
   constexpr int M = 2 * C, N = C, MT = M / 16, MW = MT / 4;
@@ -711,20 +734,20 @@ __global__ __launch_bounds__(256) void wn_ts_wgrad_kernel(TsArgs a) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) fb[b][j][e] = p[e * LDB];
         }
-      if constexpr (BF) {
+      if constexpr (OT != OP_F32) {
         wn_s16x4 ha[MW], hb[NB][NT];
 #pragma unroll
-        for (int i = 0; i < MW; ++i) ha[i] = pk4(fa[i][0], fa[i][1], fa[i][2], fa[i][3]);
+        for (int i = 0; i < MW; ++i) ha[i] = pk4<OT>(fa[i][0], fa[i][1], fa[i][2], fa[i][3]);
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
-          for (int j = 0; j < NT; ++j) hb[b][j] = pk4(fb[b][j][0], fb[b][j][1], fb[b][j][2], fb[b][j][3]);
+          for (int j = 0; j < NT; ++j) hb[b][j] = pk4<OT>(fb[b][j][0], fb[b][j][1], fb[b][j][2], fb[b][j][3]);
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
           for (int i = 0; i < MW; ++i)
 #pragma unroll
-            for (int j = 0; j < NT; ++j) acc[b][i][j] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ha[i], hb[b][j], acc[b][i][j], 0, 0, 0);
+            for (int j = 0; j < NT; ++j) acc[b][i][j] = wn_mfma16<OT>(ha[i], hb[b][j], acc[b][i][j]);
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -769,8 +792,10 @@ void launch_ts_wgrad_npw(TsArgs a, hipStream_t s) {
   a.chunks_per_wg = (n_chunks + slices - 1) / slices;
   slices = (n_chunks + a.chunks_per_wg - 1) / a.chunks_per_wg;
   const size_t grid = NSPLIT == 1 ? slices : 8 * NSPLIT * ((slices + 7) / 8);  // (slices past the last chunk return at once)
-  if (operand_bf16()) hipLaunchKernelGGL((wn_ts_wgrad_kernel<C, DUAL, true, NPW>), dim3((unsigned)grid), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((wn_ts_wgrad_kernel<C, DUAL, false, NPW>), dim3((unsigned)grid), dim3(256), 0, s, a);
+  const OpType ot = operand_type();
+  if (ot == OP_BF16) hipLaunchKernelGGL((wn_ts_wgrad_kernel<C, DUAL, OP_BF16, NPW>), dim3((unsigned)grid), dim3(256), 0, s, a);
+  else if (ot == OP_F16) hipLaunchKernelGGL((wn_ts_wgrad_kernel<C, DUAL, OP_F16, NPW>), dim3((unsigned)grid), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((wn_ts_wgrad_kernel<C, DUAL, OP_F32, NPW>), dim3((unsigned)grid), dim3(256), 0, s, a);
 }
 
 // column tiles per workgroup: all of them (operands stream exactly once) while every workgroup has >= 64 chunks of 16 rows to
@@ -885,7 +910,7 @@ extern "C" int blvm_wavenet_block_fwd(const float* x, const float* conv_w, const
   if (fused_fwd_enabled() && S == C && (C == 32 || C == 64 || C == 96) && aligned16(skip) && (o == nullptr || aligned16(o))) {
     // operand-layout copies: the two taps straight out of the interleaved Conv1d weight, the 1x1 weight behind them
     float* Wrs = W1 + nk;
-    T16PackScope pack_scope(false, s);  // the three packs in one launch (the block kernels round fp32 packs themselves in the bf16 mode)
+    T16PackScope pack_scope(OP_F32, s);  // the three packs in one launch (the block kernels round fp32 packs themselves in the 16-bit modes)
     int rc = t16_pack(conv_w, 2 * C, 2, 2 * C, C, W0, s); if (rc) return rc;
     rc = t16_pack(conv_w + 1, 2 * C, 2, 2 * C, C, W1, s); if (rc) return rc;
     rc = t16_pack_rows(rs_w, C, C + S, C, Wrs, s); if (rc) return rc;
@@ -935,7 +960,7 @@ extern "C" int blvm_wavenet_block_bwd(const float* x, const float* conv_w, const
     float* WrsT = W0;
     float* W0T = W1;
     float* W1T = dW0;
-    T16PackScope pack_scope(false, s);
+    T16PackScope pack_scope(OP_F32, s);
     rc = t16_pack_transposed(rs_w, C, C + S, C, WrsT, s); if (rc) return rc;
     rc = t16_pack(conv_w, 2, 2 * C, C, 2 * C, W0T, s); if (rc) return rc;
     rc = t16_pack(conv_w + 1, 2, 2 * C, C, 2 * C, W1T, s); if (rc) return rc;

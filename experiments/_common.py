@@ -1,6 +1,6 @@
 """Shared body of the experiment entry points: synthetic length-bucketed data, one process per GPU, and the reference's
 loop order (experiments/experiment_vrnn_audio.py:213-298): forward -> zero_grad -> backward -> [gradient all-reduce] ->
-clip by value -> clip by norm -> optimizer step; lr_scheduler.step() per epoch; evaluation every `test_every` epochs,
+[unscale (fp16 operands: GradScaler)] -> clip by value -> clip by norm -> optimizer step [scaler update]; lr_scheduler.step() per epoch; evaluation every `test_every` epochs,
 optionally on split sequences with carried state; checkpoint when the test metric improves."""
 import math
 import os
@@ -112,13 +112,16 @@ def setup(args):
         dist.init_process_group("nccl", device_id=dev)
     torch.manual_seed(args.seed)  # same weights on every rank
     if args.use_amp:
-        # the reference wraps forward in torch.autocast (experiment_vrnn_audio.py:219-230); here: bf16 operands / fp32 accumulation
-        # for the persistent recurrent chains and the K6 GEMMs, everything else (and everything stored) fp32
+        # the reference wraps forward in torch.autocast (experiment_vrnn_audio.py:219-230); here: bf16 or fp16 (--amp_dtype) operands
+        # with fp32 accumulation for the persistent recurrent chains, the sequence and WaveNet block kernels and the K6 GEMMs,
+        # everything else (and everything stored) fp32.  fp16 also brings the reference's GradScaler (see run)
         from blvm import _hip
 
-        _hip.set_operand_dtype("bf16")
+        amp_dtype = getattr(args, "amp_dtype", "bf16")
+        _hip.set_operand_dtype(amp_dtype)
         if rank == 0:
-            print("note: --use_amp: bf16 matrix operands with fp32 accumulation (libblvm_hip operand dtype bf16)", file=sys.stderr)
+            scaling = " and dynamic loss scaling (GradScaler)" if amp_dtype == "f16" else ""
+            print(f"note: --use_amp: {amp_dtype} matrix operands with fp32 accumulation{scaling} (libblvm_hip operand dtype {amp_dtype})", file=sys.stderr)
     if isinstance(args.batch_len, float):
         args.batch_len = int(16000 * args.batch_len)
     return rank, world, dev
@@ -149,18 +152,39 @@ def cwvae_split_eval(model, x, x_sl, tracker, length):
     return out
 
 
-def clip_and_step(params, optimizer, max_grad_value, max_grad_norm, skip_nonfinite=False):
+def clip_and_step(params, optimizer, max_grad_value, max_grad_norm, skip_nonfinite=False, scaler=None):
     """clip by value -> clip by norm -> optimizer step (experiment_vrnn_audio.py:224-228).  With `skip_nonfinite` a step whose
     gradient norm is NaN / inf is NOT taken (experiment_srnn_audio.py:236-240): parameters and optimizer state stay as they are.
     (Scaling the gradients by a 0/1 flag cannot do this: NaN * 0 is NaN, and `clip_grad_norm_` has already multiplied every
     gradient by a NaN coefficient.)  Like the reference's `if`, the test reads the norm on the host, i.e. waits for backward; in a
-    data-parallel run the norm is that of the all-reduced gradient, so every rank decides alike.  Returns whether it stepped."""
+    data-parallel run the norm is that of the all-reduced gradient, so every rank decides alike.  Returns whether it stepped.
+
+    With a `scaler` (torch.amp.GradScaler; the gradients are those of `scaler.scale(loss)`) the order is the reference's
+    (experiment_vrnn_audio.py:221-230): unscale -> clip the UNSCALED gradients -> scaler.step (skipped when unscale found an inf /
+    NaN) -> scaler.update (halves the scale after a skip).  A skipped step is one whose update lowered the scale; with
+    `skip_nonfinite` a non-finite norm skips the step as before, and is counted once."""
+    if scaler is not None:
+        scaler.unscale_(optimizer)
     torch.nn.utils.clip_grad_value_(params, max_grad_value)
     total_norm = torch.nn.utils.clip_grad_norm_(params, max_grad_norm)
+    if scaler is not None:
+        return scaler_step(scaler, optimizer, skip=skip_nonfinite and not bool(torch.isfinite(total_norm)))
     if skip_nonfinite and not bool(torch.isfinite(total_norm)):
         return False
     optimizer.step()
     return True
+
+
+def scaler_step(scaler, optimizer, skip=False):
+    """scaler.step + scaler.update after `scaler.unscale_(optimizer)`; returns whether the optimizer stepped.  `skip`: do not step
+    whatever the scaler found (the update still backs off if it found an inf / NaN)."""
+    scale = scaler.get_scale()
+    if skip:
+        scaler.update()
+        return False
+    scaler.step(optimizer)
+    scaler.update()
+    return scaler.get_scale() >= scale
 
 
 def run(args, model, forward_train, forward_eval, best_metric, num_bits, split_eval_fn=None, clip=True, skip_nonfinite=False):
@@ -171,6 +195,11 @@ def run(args, model, forward_train, forward_eval, best_metric, num_bits, split_e
     optimizer = getattr(torch.optim, args.optimizer or "Adam")(params, lr=args.lr, **args.optimizer_kwargs)
     scheduler = getattr(torch.optim.lr_scheduler, args.lr_scheduler)(optimizer, **args.lr_scheduler_kwargs)
     reducer = FlatGradAllReduce(params) if world > 1 else None
+    # fp16 operands: the reference's GradScaler (experiment_vrnn_audio.py:198; torch's defaults: init scale 2^16, growth interval
+    # 2000).  An inf / NaN on any rank survives the summed all-reduce, so every rank skips the same steps and the scales stay equal
+    scaler = None
+    if args.use_amp and getattr(args, "amp_dtype", "bf16") == "f16":
+        scaler = torch.amp.GradScaler("cuda", init_scale=2.0**16, growth_interval=2000)
     bs, bl = args.batch_size, (args.batch_len or (0 if args.batch_size else 64 * 16000))
     if args.dataset == "synthetic":
         train = SyntheticUtterances(args.synthetic_utterances, args.synthetic_length, bs, bl, num_bits, args.seed, rank, world)
@@ -186,11 +215,14 @@ def run(args, model, forward_train, forward_eval, best_metric, num_bits, split_e
             x = x.to(dev, non_blocking=True)
             loss, metrics, _ = forward_train(model, x, x_sl)
             optimizer.zero_grad(set_to_none=True)
-            loss.backward()
+            (scaler.scale(loss) if scaler is not None else loss).backward()
             if reducer is not None:
                 reducer(float(x_sl.sum()), status=aborted)
             if clip:
-                skipped += not clip_and_step(params, optimizer, args.max_grad_value, args.max_grad_norm, skip_nonfinite)
+                skipped += not clip_and_step(params, optimizer, args.max_grad_value, args.max_grad_norm, skip_nonfinite, scaler)
+            elif scaler is not None:
+                scaler.unscale_(optimizer)
+                skipped += not scaler_step(scaler, optimizer)
             else:
                 optimizer.step()
             tracker.update(metrics)  # reads this step's sums back: the host has waited for everything enqueued so far
@@ -207,8 +239,9 @@ def run(args, model, forward_train, forward_eval, best_metric, num_bits, split_e
         scheduler.step()
         torch.cuda.synchronize()
         _hip.check_async("training epoch", group=world > 1)  # whatever the last exchange did not carry; collective: all ranks raise together
-        if skipped and rank == 0:
-            print(f"epoch {epoch:4d} | {skipped} step(s) skipped: non-finite gradient norm", flush=True)
+        if (skipped or scaler is not None) and rank == 0:
+            scale = f" (loss scale {scaler.get_scale():g})" if scaler is not None else ""
+            print(f"epoch {epoch:4d} | {skipped} step(s) skipped: non-finite gradient norm{scale}", flush=True)
         tracker.all_reduce("train")
         if rank == 0:
             vals = ", ".join(f"{k} {v:.4f}" for k, v in tracker.values("train").items())
@@ -216,20 +249,22 @@ def run(args, model, forward_train, forward_eval, best_metric, num_bits, split_e
         if (epoch - 1) % args.test_every == 0:
             model.eval()
             # the test ELBO decides about checkpoints and is what runs are compared by: always in fp32 operands, also under --use_amp
-            # (the bf16-operand mode is a training-speed mode whose parity is unpinned)
+            # (the 16-bit operand modes are training modes whose parity is unpinned)
             train_dtype = _hip.get_operand_dtype()
             _hip.set_operand_dtype("f32")
-            with torch.no_grad():
-                for x, x_sl in tracker.steps(test, source="test"):
-                    if x is None:  # this rank's shard of the batch is empty
-                        continue
-                    x = x.to(dev, non_blocking=True)
-                    if split_eval_fn is not None:
-                        split_eval_fn(model, x, x_sl, tracker)
-                    else:
-                        tracker.update(forward_eval(model, x, x_sl)[1])
-            torch.cuda.synchronize()
-            _hip.set_operand_dtype(train_dtype)
+            try:
+                with torch.no_grad():
+                    for x, x_sl in tracker.steps(test, source="test"):
+                        if x is None:  # this rank's shard of the batch is empty
+                            continue
+                        x = x.to(dev, non_blocking=True)
+                        if split_eval_fn is not None:
+                            split_eval_fn(model, x, x_sl, tracker)
+                        else:
+                            tracker.update(forward_eval(model, x, x_sl)[1])
+                torch.cuda.synchronize()
+            finally:
+                _hip.set_operand_dtype(train_dtype)
             _hip.check_async("evaluation", group=world > 1)  # before anyone decides about a checkpoint
             tracker.all_reduce("test")  # the whole test set's value on every rank (rank 0 decides about the checkpoint)
             value = tracker.values("test").get(best_metric)

@@ -52,9 +52,14 @@ int blvm_pchain_max_batch(void); /* the current limit (at most 128) */
  * torch.autocast around forward).  BLVM_DTYPE_F32 (default): fp32 operands, exact fp32 fma chains.  BLVM_DTYPE_BF16: the
  * persistent recurrent chains (K1-K5 with B <= blvm_pchain_max_batch()) and the K6 GEMMs round their operands to bf16 (nearest
  * even) and multiply on the bf16 matrix pipe; accumulation, epilogues, reductions, likelihoods and everything stored stay fp32
- * (autocast keeps bf16 outputs; this mode is at least as precise).  Also settable with env BLVM_DTYPE=bf16 before the first call. */
+ * (autocast keeps bf16 outputs; this mode is at least as precise).  BLVM_DTYPE_F16: the same products with operands rounded to
+ * fp16 (nearest even, |x| >= 65520 -> inf, exactly torch's .half()) on the fp16 matrix pipe — the type the reference's autocast
+ * uses; its gradients need loss scaling (torch.amp.GradScaler), as the reference's do.  Paths that decline the 16-bit modes (row
+ * groups, launch per link, static walks, conv coders) run fp32 in both.  Also settable with env BLVM_DTYPE=bf16 / f16 before the
+ * first call. */
 #define BLVM_DTYPE_F32 0
 #define BLVM_DTYPE_BF16 1
+#define BLVM_DTYPE_F16 2
 int blvm_set_operand_dtype(int dtype);
 int blvm_get_operand_dtype(void);
 /* Diagnostics: while `device_buffer` (64 zero-initialised uint64 in device memory, caller-owned) is installed, the persistent kernels
@@ -116,7 +121,7 @@ int blvm_wgrad_f32(int N_out, int K_in, int rows, const float* D, int ldd, const
  * ldx[i], dW[i], lddw[i], db[i]) — the layers of one MLP chain, the links of one recurrent sequence (reference: autograd's per-layer
  * `grad_weight = dy^T x`, torch/nn/functional.linear backward, called once per nn.Linear of blvm/models/vrnn.py:60-75).  Small
  * outputs (256 x 256) cannot fill the chip alone without a split so fine that the atomics dominate; together they share one coarse
- * split.  dW[i] / db[i] may be NULL.  Falls back to one launch per job for bf16 operands, rows < 1024 or more than 20 jobs. */
+ * split.  dW[i] / db[i] may be NULL.  Falls back to one launch per job for 16-bit operands, rows < 1024 or more than 20 jobs. */
 int blvm_wgrad_group_f32(int n, const int* N_out, const int* K_in, int rows, const float* const* D, const int* ldd, const float* const* X,
                          const int* ldx, float* const* dW, const int* lddw, float* const* db, void* stream);
 
