@@ -319,9 +319,11 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
              int ldc, const float* bias, int act, float slope, const float* gate, int ldg, int accumulate,
              int split_k, hipStream_t stream, float* colsum = nullptr);  // colsum (op_a == 1): [M] += sum over k of A[k][:]
 int colsum_f32(int M, int N, const float* X, int ldx, float* out, int accumulate, hipStream_t stream);
-// Weight gradients of one reduction length as ONE launch (gemm.hip gemm_group_kernel): dW[M,N] += D^T[M,K] Act[K,N] and, with db,
-// db[M] += column sums of D, for every job with dW (a job without dW only sums its columns).  Falls back to one gemm_f32 per job
-// for 16-bit operands, short reductions or more than 20 jobs (env BLVM_WGRAD_GROUP=0: always).
+// Weight gradients of one reduction length as ONE launch: dW[M,N] += D^T[M,K] Act[K,N] and, with db, db[M] += column sums of D, for
+// every job with dW (a job without dW only sums its columns).  Jobs with 16-byte aligned operands, M, N and leading dimensions
+// multiples of 4 and K >= 1024 run together on gemm.hip wgrad_group_kernel (the LDS-DMA 128 x 128 tile), or on gemm_group_kernel
+// (64 x 64) when they would fill under 95 % of their 128 x 128 tile area; a group of one, the other jobs (up to 20 per group) and
+// the 16-bit operand modes go one by one through gemm_f32.
 struct WgradJob {
   const float* D; int ldd, M;
   const float* Act; int lda, N;

@@ -56,7 +56,7 @@ __device__ __forceinline__ float4 ld4(const float* p, int n_valid, bool vec) {
   return v;
 }
 
-// one BM x BN output tile over the k range of split `bz` of `nz` (the body of gemm_kernel and of gemm_group_kernel)
+// one BM x BN output tile over the k range of split `bz` of `nz` (the body of gemm_kernel)
 template <int BM, int BN, int OPA, int OPB>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const int by, const int bz, const int nz) {
   // k-tile depth by tile size: 64 x 64 tiles (8 MFMAs per wave and 16 k, 49 VGPRs at depth 32: still 7 waves per SIMD) run 32 deep --
@@ -228,18 +228,174 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
   gemm_tile<BM, BN, OPA, OPB>(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z);
 }
 
+// ---- weight gradients: dW[M, N] (+)= D^T Act with D [rows, M] and Act [rows, N] both row-major (op_a = op_b = 1) ----------------
+// Both operands keep the reduction (rows) as their slow index, so the k-major LDS image of a 128-wide tile IS the global layout: one
+// contiguous 512-byte row per k.  The tile is filled by LDS-DMA (global_load_lds_dwordx4: no staging VGPRs, no ds_write pass, no
+// transposition) into a ring of WST stages of WBK rows held in ONE __shared__ array (a second LDS object can make hipcc wait for
+// every DMA before the first ds_read of a k-step).  Per k-step: a counted vmcnt retires this wave's DMAs of stage s, a raw s_barrier
+// (no __syncthreads: its fence would drain the DMAs still in flight) makes every wave's stage s visible and retires every read of
+// stage s - 1, then the DMAs of stage s + WST - 1 go into the slot of s - 1 and the MFMAs consume stage s.  Reads are conflict-free
+// ds_read_b32: lanes 0-31 read 32 consecutive floats of row k, lanes 32-63 row k + 1 (the other lane group of the instruction).
+// The MFMA chain per output runs the same k order as gemm_tile, so an unsplit launch matches it bit for bit.
+// Requirements (host-checked; others take gemm_tile): 16-byte aligned operands, M, N, ldd, lda multiples of 4.  Columns past M / N
+// are staged from a clamped (valid) column and never stored; rows past the k range are staged from a clamped row and zeroed at read.
+constexpr int WBM = 128, WBK = 16;         // square tile, k rows per stage
+constexpr int WST = 4;                      // ring depth: 4 x 16 KiB = 64 KiB -> 2 workgroups (2 waves per SIMD) per CU
+                                            // (3 stages, 3 workgroups per CU, measured: chain group 707 -> 774 us)
+constexpr int WDMA = 4;                     // DMA instructions per wave per stage (2 for D, 2 for Act: 2 rows of 512 B each)
+
+template <int N>
+__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"I"(N) : "memory"); }
+__device__ __forceinline__ void ring_barrier() {  // (the LDS reads of the stage before are retired first: its slot is refilled next)
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+__device__ __forceinline__ void wgrad_tile(const GemmArgs& g, const int bx, const int by, const int bz, const int nz) {
+  constexpr int SLOT = 2 * WBK * WBM;  // floats per stage: D rows then Act rows
+  __shared__ __attribute__((aligned(16))) float ring[WST * SLOT];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int m0 = by * WBM, n0 = bx * WBM;
+  const int kbeg = bz * g.k_per_split;
+  const int kend = min(g.K, kbeg + g.k_per_split);
+  const int nst = (kend - kbeg + WBK - 1) / WBK;  // >= 1: the host launches no empty k range
+
+  // DMA source of this lane: column (lane & 31) * 4 of the tile, row 2 r + (lane >> 5) of instruction r (r = 2 wave + j)
+  const int lr = lane >> 5, lc = (lane & 31) * 4;
+  const float* pa = g.A + min(m0 + lc, g.M - 4);
+  const float* pb = g.B + min(n0 + lc, g.N - 4);
+  auto issue = [&](int s) {
+    float* sa = ring + (s % WST) * SLOT;
+    float* sb = sa + WBK * WBM;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int r = (wave * 2 + j) * 2;  // first of the instruction's two k rows (wave-uniform)
+      const size_t k = (size_t)min(kbeg + s * WBK + r + lr, kend - 1);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pa + k * g.lda),
+                                       (__attribute__((address_space(3))) void*)(sa + r * WBM), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pb + k * g.ldb),
+                                       (__attribute__((address_space(3))) void*)(sb + r * WBM), 16, 0, 0);
+    }
+  };
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  const int li = lane & 31, lh = lane >> 5;
+  const bool do_csum = g.colsum != nullptr && bx == 0;  // bias gradient: the first column block also sums its D tiles over k
+  float csum = 0.f;
+
+  // one stage: 8 k-pairs x 2 x 2 MFMAs; the operands of pair p + 1 are requested before the MFMAs of pair p (as in gemm_tile).
+  // MASK: the last stage of a ragged k range — rows >= nv are clamped copies and enter as zeros
+  auto stage = [&](const float* sa, auto mask_tag, int nv) {
+    constexpr bool MASK = decltype(mask_tag)::value;
+    const float* sb = sa + WBK * WBM;
+    if (do_csum) {  // 2 threads per column, 8 rows each
+#pragma unroll
+      for (int kk = 0; kk < WBK / 2; ++kk) {
+        const int k = kk * 2 + (tid >> 7);
+        const float v = sa[k * WBM + (tid & 127)];
+        csum += (!MASK || k < nv) ? v : 0.f;
+      }
+    }
+    float a[2][2], b[2][2];
+    auto lds_ab = [&](int kk, float (&a_)[2], float (&b_)[2]) {
+      const bool ok = !MASK || kk + lh < nv;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const float v = sa[(kk + lh) * WBM + wm * 64 + i * 32 + li];
+        a_[i] = ok ? v : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const float v = sb[(kk + lh) * WBM + wn * 64 + j * 32 + li];
+        b_[j] = ok ? v : 0.f;
+      }
+    };
+    lds_ab(0, a[0], b[0]);
+#pragma unroll
+    for (int p = 0; p < WBK / 2; ++p) {
+      if (p + 1 < WBK / 2) lds_ab(2 * (p + 1), a[(p + 1) & 1], b[(p + 1) & 1]);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[p & 1][i], b[p & 1][j], acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+    }
+  };
+
+#pragma unroll
+  for (int s = 0; s < WST - 1; ++s)
+    if (s < nst) issue(s);
+  auto advance = [&](int s) -> const float* {
+    // this wave's DMAs of stage s have landed once at most WST - 2 younger stages are outstanding (none near the end)
+    if (s + WST - 2 < nst) wait_vm<WDMA * (WST - 2)>();
+    else wait_vm<0>();
+    ring_barrier();  // every wave's stage s is in LDS; every wave has finished reading stage s - 1
+    if (s + WST - 1 < nst) issue(s + WST - 1);  // into the slot of stage s - 1
+    return ring + (s % WST) * SLOT;
+  };
+  // the ragged last stage is peeled: a masked stage inside the loop makes the compiler shuttle the accumulators between register
+  // files on every k-step
+  const int nfull = (kend - kbeg) / WBK;
+  for (int s = 0; s < nfull; ++s) stage(advance(s), std::false_type{}, WBK);
+  if (nfull < nst) stage(advance(nfull), std::true_type{}, kend - kbeg - nfull * WBK);
+
+  if (do_csum && m0 + (tid & 127) < g.M) atomicAdd(g.colsum + m0 + (tid & 127), csum);
+  // epilogue: C/D layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5); rows / columns past M / N are dropped
+  const bool atomic = nz > 1;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int n = n0 + wn * 64 + j * 32 + li;
+      if (n >= g.N) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (m >= g.M) continue;
+        float* cp = g.C + (size_t)m * g.ldc + n;
+        if (atomic) atomicAdd(cp, acc[i][j][r]);
+        else if (g.accumulate) *cp += acc[i][j][r];
+        else *cp = acc[i][j][r];
+      }
+    }
+}
+
 // ---- grouped weight gradients --------------------------------------------------------------------------------------------------
-// Up to kMaxGroup problems dW_p (+)= D_p^T Act_p of ONE reduction length K (the rows of a sequence) as one launch: the small ones
-// (256 x 256 outputs: 16 tiles) cannot fill 256 CUs on their own without a split so fine that a workgroup's k range is ~20 stages
-// and 48 workgroups contend for every output word (tools/gemm_wgrad_sweep.py: 54 TF/s against 81-86 for the 768- and 1920-row
-// forms).  Together they are hundreds of tiles: a coarse split, long k ranges, one launch.  Work item = (problem, tile, split):
-// first[p] = first work item of problem p (first[n] = all); a workgroup finds its problem by scanning that table.
+// Up to kMaxGroup problems dW_p (+)= D_p^T Act_p of ONE reduction length K (the rows of a sequence) as one launch on wgrad_tile: the
+// small ones (256 x 256 outputs: 4 tiles) cannot fill 256 CUs on their own without a split so fine that a workgroup's k range is a
+// few stages and many workgroups contend for every output word.  Together they are ~100 tiles: a coarse split, long k ranges, one
+// launch.  Work item = (problem, split, tile); first[p] = first work item of problem p (first[n] = all); a workgroup finds its
+// problem by scanning that table.
 constexpr int kMaxGroup = 20;
 struct GemmGroup {
   GemmArgs p[kMaxGroup];
   int first[kMaxGroup + 1];
   int n, split;
 };
+__global__ __launch_bounds__(256) void wgrad_group_kernel(GemmGroup gg) {
+  const int item = blockIdx.x;
+  int p = 0;
+  while (p + 1 < gg.n && item >= gg.first[p + 1]) ++p;
+  const GemmArgs g = gg.p[p];
+  const int local = item - gg.first[p];
+  const int tiles_n = (g.N + WBM - 1) / WBM, tiles = tiles_n * ((g.M + WBM - 1) / WBM);
+  const int bz = local / tiles, t = local - bz * tiles;
+  wgrad_tile(g, t % tiles_n, t / tiles_n, bz, gg.split);
+}
+
+// the same work items on the register-staged 64 x 64 tile: groups whose outputs would leave much of a 128 x 128 tile as padding
 __global__ __launch_bounds__(256) void gemm_group_kernel(GemmGroup gg) {
   const int item = blockIdx.x;
   int p = 0;
@@ -250,6 +406,8 @@ __global__ __launch_bounds__(256) void gemm_group_kernel(GemmGroup gg) {
   const int bz = local / tiles, t = local - bz * tiles;
   gemm_tile<64, 64, 1, 1>(g, t % tiles_n, t / tiles_n, bz, gg.split);
 }
+
+__global__ __launch_bounds__(256) void wgrad_kernel(GemmArgs g) { wgrad_tile(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z); }
 
 // ---- 16-bit operand variant (operand_type() OP_BF16 / OP_F16: the reference's --use_amp regime) ----------------------------------
 // Same tiling, arguments and epilogue; the global -> LDS stage rounds both operands to bf16 / fp16 (OT; nearest even) and lays them
@@ -486,6 +644,29 @@ __global__ __launch_bounds__(256) void transpose_kernel(int M, int N, const floa
     if (n0 + i < N && m0 + tx < M) out[(size_t)(n0 + i) * ldo + m0 + tx] = t[tx][i];
 }
 
+// ---- wgrad_tile host side ----
+// operands it can stage by 16-byte DMA (and clamp inside a row), and reductions long enough to pipeline
+bool wgrad_fits(const float* D, int ldd, int M, const float* Act, int lda, int N, int K) {
+  return aligned16(D) && aligned16(Act) && ldd % 4 == 0 && lda % 4 == 0 && M % 4 == 0 && N % 4 == 0 && K >= 1024;
+}
+int wgrad_tiles(int M, int N) { return ((M + WBM - 1) / WBM) * ((N + WBM - 1) / WBM); }
+// k splits over `tiles` output tiles: as many as keep every workgroup in the first wave (the workgroups per CU that the ring's LDS
+// allows: 2 at 64 KiB), k ranges of at least 32 stages (512 rows)
+int wgrad_split(long tiles, int K) {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
+    return n > 0 ? n : 256;
+  }();
+  long split = (160 / (WST * 16)) * (long)cus / std::max(1L, tiles);
+  split = std::min<long>(split, K / (32 * WBK));
+  return (int)std::max(1L, split);
+}
+int wgrad_k_per_split(int K, int split) {
+  const int ksteps = (K + WBK - 1) / WBK;
+  return ((ksteps + split - 1) / split) * WBK;
+}
+
 }  // namespace
 
 int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
@@ -503,11 +684,33 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
   g.a_vec = aligned16(A) && (lda % 4 == 0);
   g.b_vec = aligned16(B) && (ldb % 4 == 0);
   if (split_k < 1) split_k = 1;
-  bool big = (M >= 128 && N >= 128 && (size_t)((M + 127) / 128) * ((N + 127) / 128) * split_k >= 192);
+  // weight-gradient form (both operands [rows, features]) on wgrad_tile where it fits and measured faster than the 64 x 64 tile
+  // (tools/wgrad_tile_bench.py on MI355X, split as the callers request it; us, 64 x 64 -> wgrad_tile):
+  //   1536 x 512 x 16000  257 -> 215      768 x 192 x 393216  1451 -> 1203      384 x 192 x 49152  94.0 -> 88.9
+  //   256 x 256 x 64000  92.5 -> 83.5     256 x 256 x 16000   36.4 -> 44.1      768 x 256 x 16000  72.0 -> 75.7
+  //   192 x 192 x 98304  89.7 -> 108
+  // i.e. large outputs, or long reductions on outputs whose 128-wide tiles are not mostly padding.  split_k == 1 stays unsplit
+  // (deterministic); any other request takes the body's own split.
+  const bool wgrad_wins = (long)M * N >= 512L * 512 || (K >= 32768 && std::max(M, N) >= 256);
+  if (op_a == 1 && op_b == 1 && operand_type() == OP_F32 && act == 0 && gate == nullptr && bias == nullptr && wgrad_wins &&
+      wgrad_fits(A, lda, M, B, ldb, N, K)) {
+    g.colsum = colsum;
+    const int split = split_k == 1 ? 1 : wgrad_split(wgrad_tiles(M, N), K);
+    g.k_per_split = wgrad_k_per_split(K, split);
+    const int nz = (K + g.k_per_split - 1) / g.k_per_split;
+    const dim3 grid((N + WBM - 1) / WBM, (M + WBM - 1) / WBM, nz);
+    if (nz > 1 && !accumulate)  // atomic accumulation needs a zeroed destination
+      BLVM_HIP(hipMemset2DAsync(C, sizeof(float) * (size_t)ldc, 0, sizeof(float) * (size_t)N, (size_t)M, stream));
+    hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, stream, g);
+    BLVM_CHECK_LAUNCH("gemm_f32");
+    return BLVM_OK;
+  }
+  bool big =(M >= 128 && N >= 128 && (size_t)((M + 127) / 128) * ((N + 127) / 128) * split_k >= 192);
   // 192-wide tiles for the conv coders' channel counts (192 = 1.5 x 128 would waste a quarter of a 128-tile pair and
   // re-read the other operand): N % 192 == 0 -> 128x192, else M % 192 == 0 -> 192x128
-  // Measured on MI355X (tools/gemm_bench.py, tools/gemm_cw.py with BLVM_GEMM_TILE forcing each variant): the 64x64 tile wins
-  // for every weight-gradient form (both operands read "transposed": 76 -> 91 TF/s at 768x192x4e5, 71 -> 91 at 1536x512x16000)
+  // Measured on MI355X (tools/gemm_bench.py, tools/gemm_cw.py with BLVM_GEMM_TILE forcing each variant): of the register-staged
+  // tiles the 64x64 one wins for every weight-gradient form (76 -> 91 TF/s at 768x192x4e5, 71 -> 91 at 1536x512x16000; those that
+  // wgrad_tile takes left above)
   // and for short reductions on narrow outputs (K <= 256 and N <= 256: 43 -> 65 TF/s at K = 96, 53 -> 61 at 256x256); the
   // 128-wide tiles win once N >= 512 or K >= 512 (84 vs 74 TF/s at N = 768, K = 192; 114 vs 95 at 4096^3).
   static const int force_tile = [] { const char* e = getenv("BLVM_GEMM_TILE"); return e ? atoi(e) : 0; }();  // experiments only
@@ -547,21 +750,8 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
 }
 
 int gemm_wgrad_group(const WgradJob* jobs, int njobs, int K, hipStream_t stream) {
-  static const int enabled = [] { const char* e = getenv("BLVM_WGRAD_GROUP"); return e ? atoi(e) : 1; }();
-  int live = 0;
-  for (int i = 0; i < njobs; ++i) live += jobs[i].dW != nullptr;
-  if (!enabled || operand_16bit() || live < 2 || live > kMaxGroup || K < 1024) {  // one launch per problem (gemm_f32 picks tile and kernel)
-    for (int i = 0; i < njobs; ++i) {
-      const WgradJob& j = jobs[i];
-      const int rc = j.dW ? gemm_f32(1, 1, j.M, j.N, K, j.D, j.ldd, j.Act, j.lda, j.dW, j.ldw, nullptr, 0, 0.f, nullptr, 0, 1, gemm_pick_split(j.M, j.N, K), stream, j.db)
-                          : (j.db ? colsum_f32(K, j.M, j.D, j.ldd, j.db, 1, stream) : BLVM_OK);
-      if (rc) return rc;
-    }
-    return BLVM_OK;
-  }
-  GemmGroup gg;
-  gg.n = 0;
-  long tiles = 0;
+  // the problems wgrad_tile takes, largest first; the others (unaligned, K < 1024, the 16-bit operand modes) one by one through gemm_f32
+  std::vector<int> take;
   for (int i = 0; i < njobs; ++i) {
     const WgradJob& j = jobs[i];
     if (!j.dW) {
@@ -569,34 +759,63 @@ int gemm_wgrad_group(const WgradJob* jobs, int njobs, int K, hipStream_t stream)
       continue;
     }
     BLVM_REQUIRE(j.D && j.Act && j.M > 0 && j.N > 0 && j.ldd >= j.M && j.lda >= j.N && j.ldw >= j.N, "gemm_wgrad_group: bad job %d", i);
-    GemmArgs& g = gg.p[gg.n];
-    g = GemmArgs{};
-    g.A = j.D; g.B = j.Act; g.C = j.dW; g.bias = nullptr; g.gate = nullptr;
-    g.M = j.M; g.N = j.N; g.K = K; g.lda = j.ldd; g.ldb = j.lda; g.ldc = j.ldw; g.ldg = 0;
-    g.act = 0; g.slope = 0.f; g.accumulate = 1;
-    g.a_vec = aligned16(j.D) && (j.ldd % 4 == 0);
-    g.b_vec = aligned16(j.Act) && (j.lda % 4 == 0);
-    g.colsum = j.db;
-    tiles += (long)((j.M + 63) / 64) * ((j.N + 63) / 64);
-    ++gg.n;
+    if (!operand_16bit() && wgrad_fits(j.D, j.ldd, j.M, j.Act, j.lda, j.N, K) && (int)take.size() < kMaxGroup) {
+      take.push_back(i);
+      continue;
+    }
+    const int rc = gemm_f32(1, 1, j.M, j.N, K, j.D, j.ldd, j.Act, j.lda, j.dW, j.ldw, nullptr, 0, 0.f, nullptr, 0, 1, gemm_pick_split(j.M, j.N, K), stream, j.db);
+    if (rc) return rc;
   }
-  // ~6 workgroups per CU, k ranges of at least 32 stages
-  constexpr int GBK = tile_bk(64, 64);
-  const int ksteps = (K + GBK - 1) / GBK;
-  static const int want = [] { const char* e = getenv("BLVM_WGRAD_GROUP_WGS"); return e ? atoi(e) : 1536; }();
-  int split = (int)((want + tiles - 1) / tiles);
-  split = std::max(1, std::min(split, ksteps / 16));  // k ranges of at least 16 stages (512 rows)
-  const int k_per_split = ((ksteps + split - 1) / split) * GBK;
-  split = (K + k_per_split - 1) / k_per_split;
-  gg.split = split;
+  if (take.size() < 2) {  // a group of one: gemm_f32 picks tile and split (measured: 256 x 256 x 16000 alone 40 us there, 47 in a group)
+    for (const int i : take) {
+      const WgradJob& j = jobs[i];
+      const int rc = gemm_f32(1, 1, j.M, j.N, K, j.D, j.ldd, j.Act, j.lda, j.dW, j.ldw, nullptr, 0, 0.f, nullptr, 0, 1, gemm_pick_split(j.M, j.N, K), stream, j.db);
+      if (rc) return rc;
+    }
+    return BLVM_OK;
+  }
+  std::stable_sort(take.begin(), take.end(), [&](int x, int y) { return (long)jobs[x].M * jobs[x].N > (long)jobs[y].M * jobs[y].N; });
+  GemmGroup gg;
+  gg.n = 0;
+  long tiles = 0;
+  for (const int i : take) {
+    const WgradJob& j = jobs[i];
+    GemmArgs& g = gg.p[gg.n++];
+    g = GemmArgs{};
+    g.A = j.D; g.B = j.Act; g.C = j.dW;
+    g.M = j.M; g.N = j.N; g.K = K; g.lda = j.ldd; g.ldb = j.lda; g.ldc = j.ldw;
+    g.accumulate = 1;
+    g.colsum = j.db;
+    tiles += wgrad_tiles(j.M, j.N);
+  }
+  // wgrad_tile unless its tiles would be mostly padding.  Measured (tools/wgrad_tile_bench.py, us, 64 x 64 group -> wgrad_tile): the
+  // VRNN chain (16 jobs, 164 full tiles) 920 -> 766, a 256 x 512 + 2 x 256 x 256 group 94.5 -> 85.6, but a 256 x 64 + 2 x 256 x 256
+  // group (90 % of its tile area used) 66.2 -> 79.5, and STCN's narrow latent MLPs 31.84 -> 32.32 ms/step
+  long area = 0;
+  for (int p = 0; p < gg.n; ++p) area += (long)gg.p[p].M * gg.p[p].N;
+  const bool dma = area * 100 >= tiles * WBM * WBM * 95L;
+  const int bk = dma ? WBK : tile_bk(64, 64);
+  int split;
+  if (dma) {
+    split = wgrad_split(tiles, K);
+  } else {  // ~6 workgroups per CU, k ranges of at least 16 stages (512 rows)
+    long tiles64 = 0;
+    for (int p = 0; p < gg.n; ++p) tiles64 += (long)((gg.p[p].M + 63) / 64) * ((gg.p[p].N + 63) / 64);
+    split = (int)std::max(1L, std::min<long>((1536 + tiles64 - 1) / tiles64, (K + bk - 1) / bk / 16));
+  }
+  const int ksteps = (K + bk - 1) / bk;
+  const int k_per_split = ((ksteps + split - 1) / split) * bk;
+  gg.split = (K + k_per_split - 1) / k_per_split;
   int first = 0;
   for (int p = 0; p < gg.n; ++p) {
     gg.p[p].k_per_split = k_per_split;
+    gg.p[p].a_vec = 1; gg.p[p].b_vec = 1;  // (wgrad_fits: aligned, leading dimensions multiples of 4)
     gg.first[p] = first;
-    first += ((gg.p[p].M + 63) / 64) * ((gg.p[p].N + 63) / 64) * split;
+    first += (dma ? wgrad_tiles(gg.p[p].M, gg.p[p].N) : ((gg.p[p].M + 63) / 64) * ((gg.p[p].N + 63) / 64)) * gg.split;
   }
   gg.first[gg.n] = first;
-  hipLaunchKernelGGL(gemm_group_kernel, dim3((unsigned)first), dim3(256), 0, stream, gg);
+  if (dma) hipLaunchKernelGGL(wgrad_group_kernel, dim3((unsigned)first), dim3(256), 0, stream, gg);
+  else hipLaunchKernelGGL(gemm_group_kernel, dim3((unsigned)first), dim3(256), 0, stream, gg);
   BLVM_CHECK_LAUNCH("gemm_wgrad_group");
   return BLVM_OK;
 }
