@@ -993,19 +993,66 @@ __device__ __forceinline__ void tile_dmol_sample(const float* dec, int ldd, cons
 // =================================================================================================================================
 enum Kind : int { K_LIN = 0, K_HEAD = 1, K_GRU = 2, K_DZ = 3, K_GRUB = 4, K_DMOLS = 5, K_GRUS = 6, K_GRUSB = 7, K_LSTMS = 8, K_LSTMSB = 9, K_LINSEQ = 10 };
 enum DescFlag : int {
-  DF_RELU = 1,         // K_LIN: leaky ReLU (f[0] = slope) on the result
-  DF_A_PLAIN = 2,      // K_LIN: A is a row-major buffer written before the launch (ld[0]), not a polled T16 copy
+  DF_RELU = 1,         // K_LIN: leaky ReLU (f[LIN_F_SLOPE]) on the result
+  DF_A_PLAIN = 2,      // K_LIN: A is a row-major buffer written before the launch (ld[LIN_LD_A]), not a polled T16 copy
   DF_ADD_POLLED = 4,   // K_LIN: `add` words are produced inside the launch
   DF_RM_SC1 = 8,       // the row-major output is polled word-wise by other workgroups
   DF_GENTLE = 16,      // off the critical path: nap between polls
   DF_CANARY = 32,      // one-word canary wait in front of the operand poll
-  DF_A_SUM3 = 64,      // K_LIN: the polled operand is the sum of three slabs (p[0], p[8], p[9]) of partial sums
+  DF_A_SUM3 = 64,      // K_LIN: the polled operand is the sum of three slabs (LIN_A, LIN_A2, LIN_A3) of partial sums
   DF_SEQ_GATE = 128,   // K_LINSEQ: the per-link auxiliary pointer is the derivative gate (backward chains), not the bias
 };
+// ---- what the slots of a descriptor hold, by tile kind: each enum lists the kind's pointer slots p[] in order, then the indices of
+// the fields it reads: <KIND>_LD_* into ld[], _N16_* into n16[], _I_* into i[], _F_* into f[].  Every kind but K_LINSEQ: ld[LD_OUT] =
+// row stride of its row-major output, n16[N16_OUT] (n16[N16_OUTB]) = 16-column chunks per row of its (second) T16 output.  "T16": in
+// the T16 operand layout; "polled": produced inside the launch.
+enum : int { LD_OUT = 3, N16_OUT = 0, N16_OUTB = 1 };
+// K_LIN: A (T16, polled; ld[LIN_LD_A] = its width when wider than K | row-major when DF_A_PLAIN), W (T16), bias, add, gate, out
+// row-major | T16 | second T16, (DF_A_SUM3) two more slabs of A: the operand is the sum of the three.  i: width of W's packed rows
+// when the product covers a K-range of them.
+enum : int { LIN_A, LIN_W, LIN_BIAS, LIN_ADD, LIN_GATE, LIN_ORM, LIN_O16, LIN_O16B, LIN_A2, LIN_A3, LIN_LD_A = 0, LIN_LD_ADD = 1, LIN_LD_GATE = 2,
+             LIN_I_W_WIDTH = 0, LIN_F_SLOPE = 0 };
+// K_LINSEQ (add_linseq): A_0, then for link l at base + l: W_l, bias_l | gate_l (DF_SEQ_GATE), out_l row-major (ld[LINSEQ_LD_ORM + l])
+// and T16; add0: the first link's row-major addend or null.  i: links in the run, the first link's K when it is not the run's (0: it is).
+enum : int { LINSEQ_A0 = 0, LINSEQ_W = 1, LINSEQ_AUX = 5, LINSEQ_ORM = 9, LINSEQ_O16 = 13, LINSEQ_ADD0 = 17, LINSEQ_LD_ORM = 0,
+             LINSEQ_I_LD_ADD0 = 0, LINSEQ_I_N = 1, LINSEQ_I_LD_GATE = 2, LINSEQ_I_K0 = 3, LINSEQ_F_SLOPE = 0 };
+// K_HEAD (tile_head): P16, Q16 (polled), Wp, bp, Wq, bq, eps, the statistics, z row-major | T16 | second T16
+enum : int { HEAD_P16, HEAD_Q16, HEAD_WP, HEAD_BP, HEAD_WQ, HEAD_BQ, HEAD_EPS, HEAD_MU_P, HEAD_SD_P, HEAD_MU_Q, HEAD_SD_Q, HEAD_RAW_P, HEAD_RAW_Q,
+             HEAD_MUQ_RAW, HEAD_Z, HEAD_Z16, HEAD_Z16B, HEAD_I_Z = 0, HEAD_I_RESIDUAL = 1, HEAD_F_BETA = 0, HEAD_F_INV_BETA = 1, HEAD_F_SD_EPS = 2 };
+// K_GRU (tile_gru): X16, Wih (T16), xg, gh and h_prev (polled words), h_new row-major | T16, gates, b_ih, second h_new T16
+enum : int { GRU_X16, GRU_WIH, GRU_XG, GRU_GH, GRU_HPREV, GRU_HRM, GRU_H16, GRU_RG, GRU_UG, GRU_NG, GRU_BIH, GRU_H16B, GRU_LD_HPREV = 0, GRU_I_R = 0 };
+// K_DZ (tile_dz): D16, WT, D2_16, WT2, dz_add, what the forward saved, x_sl (int32), c_raw, c_fn, dqh and dph row-major | T16 (ld[LD_OUT]
+// = 2Z).  t = i[DZ_I_T0] - s; f[DZ_F_GEMM_FROM]: first step with the product.
+enum : int { DZ_D16, DZ_WT, DZ_D2_16, DZ_WT2, DZ_ADD, DZ_MU_Q, DZ_SD_Q, DZ_MU_P, DZ_SD_P, DZ_EPS, DZ_RAW_Q, DZ_RAW_P, DZ_MUQ_RAW, DZ_X_SL, DZ_C_RAW,
+             DZ_C_FN, DZ_DQH, DZ_DQH16, DZ_DPH, DZ_DPH16, DZ_LD_ADD = 1, DZ_I_Z = 0, DZ_I_RESIDUAL = 1, DZ_I_STRIDE = 2, DZ_I_T0 = 3,
+             DZ_F_FN_FLOOR = 0, DZ_F_BETA = 1, DZ_F_SD_EPS = 2, DZ_F_GEMM_FROM = 3 };
+// K_GRUB (tile_grub): D0_16, D1_16, W0, W1, g_in (polled words), rg, ug, ng, gh, h_prev and dd (ld[GRUB_LD_H]), dgi and dgh row-major |
+// T16 (ld[LD_OUT] = 3R), ga, g_out, g_add.  i: first step with the products | WITHOUT gates | with g_in.
+enum : int { GRUB_D0_16, GRUB_D1_16, GRUB_W0, GRUB_W1, GRUB_G_IN, GRUB_RG, GRUB_UG, GRUB_NG, GRUB_GH, GRUB_HPREV, GRUB_DD, GRUB_DGI, GRUB_DGI16,
+             GRUB_DGH, GRUB_DGH16, GRUB_GA, GRUB_G_OUT, GRUB_G_ADD, GRUB_LD_H = 0, GRUB_LD_GADD = 1, GRUB_I_R = 0, GRUB_I_GEMM_FROM = 1,
+             GRUB_I_GATES_TO = 2, GRUB_I_GIN_FROM = 3 };
+// K_DMOLS (tile_dmol_sample; ct counts tiles of 4 samples): dec (row-major, polled words), head W [F,F], head b, u, v, x row-major | T16
+enum : int { DMOLS_DEC, DMOLS_W, DMOLS_B, DMOLS_U, DMOLS_V, DMOLS_X, DMOLS_X16, DMOLS_LD_DEC = 0, DMOLS_I_S = 0, DMOLS_I_F = 1, DMOLS_I_NMIX = 2,
+             DMOLS_F_LOG_EPS = 0 };
+// K_GRUS (tile_gru_seq; recurrence step j = s): H16 (state entering the step), Whh (T16), b_hh, xg [T,B,3R] (time indexed), lens, h_prev
+// row-major, h_next row-major | T16, out (time indexed), gates, ghn
+enum : int { GRUS_H16, GRUS_WHH, GRUS_BHH, GRUS_XG, GRUS_LENS, GRUS_HPREV, GRUS_HNEXT, GRUS_HNEXT16, GRUS_OUT, GRUS_RG, GRUS_UG, GRUS_NG, GRUS_GHN,
+             GRUS_I_R = 0, GRUS_I_REVERSE = 1, GRUS_I_OUT_TS = 2, GRUS_I_OUT_LD = 3 };
+// K_GRUSB (tile_gru_seq_bwd; j = T-1-s, T = n16[GRUSB_N16_T]; s = 0: no product; s = T: only dh0): DGH16 of step j+1, WhhT (T16), dout
+// (time indexed), saves of step j, lens, G (in place), DGI [T,B,3R] (time indexed), DGH row-major | T16 (ld[LD_OUT] = 3R), dh0
+enum : int { GRUSB_DGH16_IN, GRUSB_WHHT, GRUSB_DOUT, GRUSB_RG, GRUSB_UG, GRUSB_NG, GRUSB_GHN, GRUSB_HPREV, GRUSB_LENS, GRUSB_G, GRUSB_DGI, GRUSB_DGH,
+             GRUSB_DGH16, GRUSB_DH0, GRUSB_N16_T = 1, GRUSB_I_R = 0, GRUSB_I_REVERSE = 1, GRUSB_I_OUT_TS = 2, GRUSB_I_OUT_LD = 3 };
+// K_LSTMS (tile_lstm_seq; t = s): H16, Whh (T16), b_hh, xg of the step [B,4H], lens, h_prev, h_next row-major | T16, c_prev, c_next, out,
+// gates [B,4H]
+enum : int { LSTMS_H16, LSTMS_WHH, LSTMS_BHH, LSTMS_XG, LSTMS_LENS, LSTMS_HPREV, LSTMS_HNEXT, LSTMS_HNEXT16, LSTMS_CPREV, LSTMS_CNEXT, LSTMS_OUT,
+             LSTMS_GATES, LSTMS_I_H = 0 };
+// K_LSTMSB (tile_lstm_seq_bwd; t = T-1-s, T = n16[LSTMSB_N16_T]): DG16 of step t+1, WhhT (T16), dout, gates, c_s (c_{s+1} = one [B,H] slab
+// further), DC (in place), DG row-major | T16 (ld[LD_OUT] = 4H), dh0
+enum : int { LSTMSB_DG16_IN, LSTMSB_WHHT, LSTMSB_DOUT, LSTMSB_GATES, LSTMSB_CS, LSTMSB_DC, LSTMSB_DG, LSTMSB_DG16, LSTMSB_DH0, LSTMSB_N16_T = 1, LSTMSB_I_H = 0 };
 constexpr int kMaxDesc = 24, kMaxPtr = 20;
 struct Desc {
   int kind, ct, wg0, nwg, flags, K, s_begin, s_end;
-  int ld[4];                      // leading dimensions of row-major operands (per kind, see pchain.hip)
+  int ld[4];                      // leading dimensions of row-major operands (per kind, see above)
   int n16[2];                     // 16-column chunks per row of the T16 outputs
   int i[4];                       // per kind
   float f[4];                     // per kind
@@ -1026,6 +1073,10 @@ struct Program {
 // (the program reaches the device through pchain_resolve_kernel, a few descriptors per launch: kernel arguments are limited to 4 KB)
 
 // host-side assembly of a program
+struct Ptr {  // a pointer operand: its value at step 0 and its per-step stride in floats (0: the same at every step)
+  const void* p; long step;
+  Ptr(const void* p_ = nullptr, long step_ = 0) : p(p_), step(step_) {}
+};
 struct Builder {
   Program p{};
   int nstride = 1;
@@ -1047,38 +1098,55 @@ struct Builder {
     d.kind = kind; d.ct = ct; d.wg0 = wg0; d.nwg = nwg; d.K = K; d.flags = flags; d.s_begin = s_begin; d.s_end = s_end;
     return d;
   }
-  void ptr(Desc& d, int k, const void* q, long stride = 0) {
-    d.p[k] = static_cast<const float*>(q);
-    d.sidx[k] = (unsigned char)(q ? stride_index(stride) : 0);
+  void ptr(Desc& d, int k, Ptr q) {  // slot k at step s = q.p + s * q.step floats (strides get table indices in the order of first use)
+    d.p[k] = static_cast<const float*>(q.p);
+    d.sidx[k] = (unsigned char)(q.p ? stride_index(q.step) : 0);
   }
 };
+// slab t0 of a buffer of per-step slabs, walked backwards (a backward program's step s handles t = t0 - s)
+inline Ptr rev(const float* base, long step, long t0) { return Ptr(base ? base + t0 * step : nullptr, -step); }
+
+// A descriptor's operands by slot name (the enums above; null / 0 where left out).  add_desc writes the pointer slots in ascending order,
+// the order in which Builder::ptr hands out stride-table indices, so a call site may fill them in any order.
+struct Operands {
+  Ptr p[kMaxPtr];
+  int ld[4] = {}, n16[2] = {}, i[4] = {}; float f[4] = {};
+};
+inline Desc& add_desc(Builder& b, int kind, int ct, int wg0, int nwg, int K, int flags, int s_begin, int s_end, const Operands& o) {
+  Desc& d = b.add(kind, ct, wg0, nwg, K, flags, s_begin, s_end);
+  for (int k = 0; k < kMaxPtr; ++k) b.ptr(d, k, o.p[k]);
+  std::copy(o.ld, o.ld + 4, d.ld); std::copy(o.n16, o.n16 + 2, d.n16); std::copy(o.i, o.i + 4, d.i); std::copy(o.f, o.f + 4, d.f);
+  return d;
+}
 
 // A run of n <= 4 consecutive links of one shape as ONE K_LINSEQ descriptor (pchain.hip): out_i = act(A_i W_i^T + bias_i) or, with
 // `gated` (backward chains), (A_i W_i^T) masked by the derivative of the activation whose output is gate_i; A_0 = A16, A_i = o16 of
-// link i-1.  Steps of the stepped pointers: a_step (A_0), aux_step (gates), rm_step[i] (row-major outputs), o16_step (T16 outputs).
+// link i-1.  Steps of the stepped pointers: aux_step (gates), rm_step[i] (row-major outputs), o16_step (T16 outputs).
 struct SeqLink {
-  const float* W;
-  const float* aux;  // bias (not stepped) | gate (stepped by aux_step)
+  const float *W, *aux;  // aux: bias (not stepped) | gate (stepped by aux_step)
   float* orm;
   long rm_step;
   int ldo;
   float* o16;
 };
-// K0 / add0: the FIRST link may have its own K (its operand A16 is then [rows, K0]) and a row-major addend [B, ldadd0] stepping by
-// add0_step -- the link in front of a run of same-shape links joins the run's visit (one descriptor walk less per step, ~1 us)
-inline Desc& add_linseq(Builder& b, int ct, int wg0, int nwg, int K, bool relu, bool gated, int s_begin, int s_end, const float* A16, long a_step, int n,
-                        const SeqLink* L, long aux_step, long o16_step, int n16, float slope, int ldgate, int K0 = 0, const float* add0 = nullptr,
-                        long add0_step = 0, int ldadd0 = 0) {
+// K0 / add0: the FIRST link may have its own K (its operand A16 is then [rows, K0]) and a row-major addend [B, ldadd0] -- the link
+// in front of a run of same-shape links joins the run's visit (one descriptor walk less per step, ~1 us)
+inline Desc& add_linseq(Builder& b, int ct, int wg0, int nwg, int K, bool relu, bool gated, int s_begin, int s_end, Ptr A16, int n, const SeqLink* L,
+                        long aux_step, long o16_step, int n16, float slope, int ldgate, int K0 = 0, Ptr add0 = Ptr(), int ldadd0 = 0) {
   Desc& d = b.add(K_LINSEQ, ct, wg0, nwg, K, (relu ? DF_RELU : 0) | (gated ? DF_SEQ_GATE : 0), s_begin, s_end);
-  b.ptr(d, 0, A16, a_step); b.ptr(d, 17, add0, add0_step);
-  d.i[3] = (K0 != 0 && K0 != K) ? K0 : 0; d.i[0] = ldadd0;
+  b.ptr(d, LINSEQ_A0, A16); b.ptr(d, LINSEQ_ADD0, add0);
+  d.i[LINSEQ_I_K0] = (K0 != 0 && K0 != K) ? K0 : 0; d.i[LINSEQ_I_LD_ADD0] = ldadd0;
   for (int i = 0; i < n && i < 4; ++i) {
-    b.ptr(d, 1 + i, L[i].W); b.ptr(d, 5 + i, L[i].aux, gated ? aux_step : 0); b.ptr(d, 9 + i, L[i].orm, L[i].rm_step); b.ptr(d, 13 + i, L[i].o16, o16_step);
-    d.ld[i] = L[i].ldo;
+    b.ptr(d, LINSEQ_W + i, L[i].W); b.ptr(d, LINSEQ_AUX + i, Ptr(L[i].aux, gated ? aux_step : 0)); b.ptr(d, LINSEQ_ORM + i, Ptr(L[i].orm, L[i].rm_step));
+    b.ptr(d, LINSEQ_O16 + i, Ptr(L[i].o16, o16_step)); d.ld[LINSEQ_LD_ORM + i] = L[i].ldo;
   }
   if (n > 4) b.overflow = true;
-  d.n16[0] = n16; d.i[1] = n; d.i[2] = ldgate; d.f[0] = slope;
+  d.n16[N16_OUT] = n16; d.i[LINSEQ_I_N] = n; d.i[LINSEQ_I_LD_GATE] = ldgate; d.f[LINSEQ_F_SLOPE] = slope;
   return d;
+}
+// link of a gated (backward) run walking per-step slabs back from step t0: gate, row-major out [B, ld] slabs of sB floats, T16 out of x16
+inline SeqLink rev_link(const float* W, const float* gate, float* orm, float* o16, long t0, long sB, int ld, long x16) {
+  return SeqLink{W, gate ? gate + t0 * sB : nullptr, orm ? orm + t0 * sB : nullptr, -sB, ld, o16 ? o16 + t0 * x16 : nullptr};
 }
 // workgroups for `tiles` tiles out of `avail` (a multiple of 8, at least 8): XCD-aware placement deals ranges in eights
 inline int range_for(int tiles, int avail) { return std::max(8, std::min(avail & ~7, (tiles + 7) & ~7)); }

@@ -1,37 +1,6 @@
 // pchain.hip — the persistent-chain engine: ONE kernel that executes a host-built program of link descriptors (pchain.h) for a
 // whole recurrent sequence.  Replaces, per model, thousands of dependent launches (VRNN [64,16000]: 4 500 per train step) by one
-// forward and one backward launch.  Pointer roles of a descriptor by tile kind:
-//
-//   K_LIN   p: 0 A (T16 copy, polled, ld[0] = its width when wider than K | row-major when DF_A_PLAIN, ld[0])  1 W (T16)  2 bias  3 add (ld[1])  4 gate (ld[2])
-//              5 out row-major (ld[3])  6 out T16 (n16[0])  7 second out T16 (n16[1])  8, 9 (DF_A_SUM3) two more slabs of A: the
-//              operand is the sum of the three            i: 0 width of W's packed rows when the product covers a K-range of them            f: 0 slope
-//   K_HEAD  p: 0 P16  1 Q16  2 Wp  3 bp  4 Wq  5 bq  6 eps  7 mu_p  8 sd_p  9 mu_q  10 sd_q  11 raw_p  12 raw_q  13 muq_raw
-//              14 z row-major (ld[3])  15 z T16 (n16[0])  16 second z T16 (n16[1])    i: 0 Z  1 residual      f: 0 beta  1 1/beta  2 sd_eps
-//   K_GRU   p: 0 X16  1 Wih (T16)  2 xg  3 gh (polled words)  4 h_prev (polled words, ld[0])  5 h_new row-major (ld[3])
-//              6 h_new T16 (n16[0])  7 rg  8 ug  9 ng  10 b_ih  11 second h_new T16 (n16[1])         i: 0 R
-//   K_DZ    p: 0 D16  1 WT  2 D2_16  3 WT2  4 dz_add (ld[1])  5 mu_q  6 sd_q  7 mu_p  8 sd_p  9 eps  10 raw_q  11 raw_p  12 muq_raw
-//              13 x_sl (int32)  14 c_raw  15 c_fn  16 dqh row-major  17 dqh T16  18 dph row-major  19 dph T16   (ld[3] = 2Z, n16[0])
-//              i: 0 Z  1 residual  2 stride  3 t at s = 0 (t = i[3] - s)   f: 0 fn_floor  1 beta  2 sd_eps  3 first step with the product
-//   K_GRUB  p: 0 D0_16  1 D1_16  2 W0  3 W1  4 g_in (polled words)  5 rg  6 ug  7 ng  8 gh  9 h_prev (ld[0])  10 dd (ld[0])
-//              11 dgi row-major  12 dgi T16  13 dgh row-major  14 dgh T16  (ld[3] = 3R, n16[0])  15 ga  16 g_out  17 g_add (ld[1])
-//              i: 0 R  1 first step with the products  2 first step WITHOUT gates  3 first step with g_in
-//   K_DMOLS p: 0 dec (row-major, polled words, ld[0])  1 head W [F,F]  2 head b  3 u  4 v  5 x row-major (ld[3])  6 x T16 (n16[0])
-//              i: 0 S  1 F  2 num_mix      f: 0 log_eps        (ct counts tiles of 4 samples)
-//   K_LINSEQ  n = i[1] <= 4 CONSECUTIVE links of one shape (K, ct, range) walked inside one visit — out_i = act(A_i W_i^T + bias_i) with
-//              A_0 = p[0] and A_i = the T16 output of link i-1: between them only the pointers change, so the walk of the program
-//              (descriptor fetch, decode, tile list) is paid once per visit instead of once per link
-//              p: 0 A_0  1+i W_i  5+i bias_i | gate_i (DF_SEQ_GATE, ld = i[2])  9+i out_i row-major (ld[i])  13+i out_i T16 (n16[0])
-//              i: 1 n  2 ldgate      f: 0 slope
-//   K_GRUS  p: 0 H16 (state entering the step)  1 Whh (T16)  2 b_hh  3 xg [T,B,3R] (time indexed)  4 lens  5 h_prev row-major
-//              6 h_next row-major (ld[3])  7 h_next T16 (n16[0])  8 out (time indexed)  9 rg  10 ug  11 ng  12 ghn
-//              i: 0 R  1 reverse  2 out_ts  3 out_ld                                   (recurrence step j = s)
-//   K_GRUSB p: 0 DGH16 of step j+1  1 WhhT (T16)  2 dout (time indexed)  3 rg  4 ug  5 ng  6 ghn  7 h_prev  8 lens  9 G (in place)
-//              10 DGI [T,B,3R] (time indexed)  11 DGH row-major (ld[3] = 3R)  12 DGH T16 (n16[0])  13 dh0
-//              i: 0 R  1 reverse  2 out_ts  3 out_ld    n16[1]: T   (j = T-1-s; s = 0: no product; s = T: only dh0)
-//   K_LSTMS p: 0 H16  1 Whh (T16)  2 b_hh  3 xg of the step [B,4H]  4 lens  5 h_prev  6 h_next row-major (ld[3])  7 h_next T16
-//              8 c_prev  9 c_next  10 out  11 gates [B,4H]        i: 0 H                (t = s)
-//   K_LSTMSB p: 0 DG16 of step t+1  1 WhhT (T16)  2 dout  3 gates  4 c_s (c_{s+1} = one [B,H] slab further)  5 DC (in place)
-//              6 DG row-major (ld[3] = 4H)  7 DG T16 (n16[0])  8 dh0       i: 0 H       n16[1]: T   (t = T-1-s)
+// forward and one backward launch.  What the slots of a descriptor hold, by tile kind: pchain.h.
 #include <algorithm>
 #include <mutex>
 
@@ -218,9 +187,9 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             // Only what the operand loads need is taken out of the descriptor here; everything the epilogue needs (and the next
             // descriptor's fetch) is done by `late`, which the tile calls once its first loads are in flight.
             const bool a_polled = !(flags & DF_A_PLAIN);
-            const float *A = d.p<0>(s), *W = d.base<1>();
-            const float *A2 = (flags & DF_A_SUM3) ? d.p<8>(s) : nullptr, *A3 = (flags & DF_A_SUM3) ? d.p<9>(s) : nullptr;
-            const int ld0 = d.w<RD_LD + 0>(), w_width = d.w<RD_I + 0>();
+            const float *A = d.p<LIN_A>(s), *W = d.base<LIN_W>();
+            const float *A2 = (flags & DF_A_SUM3) ? d.p<LIN_A2>(s) : nullptr, *A3 = (flags & DF_A_SUM3) ? d.p<LIN_A3>(s) : nullptr;
+            const int ld0 = d.w<RD_LD + LIN_LD_A>(), w_width = d.w<RD_I + LIN_I_W_WIDTH>();
 #ifdef PCHAIN_TPROF2
             const unsigned long long tqb = wall_clock64();
             tq[4] += tqb - tqa;
@@ -228,8 +197,9 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             auto late = [&]() {
               __builtin_amdgcn_sched_barrier(0);
               nx.fetch(ltab, nx_i, nx_s);  // (per tile: the same lanes again — cheaper than a flag carried through the visit)
-              return LinLate{d.base<2>(), d.p<3>(s), d.p<4>(s), d.w<RD_LD + 1>(), d.w<RD_LD + 2>(), (flags & DF_ADD_POLLED) != 0, (flags & DF_RELU) != 0, d.f<0>(),
-                             Out{d.m<5>(s), d.w<RD_LD + 3>(), (flags & DF_RM_SC1) != 0, d.m<6>(s), d.w<RD_N16>(), d.m<7>(s), d.w<RD_N16 + 1>()}};
+              return LinLate{d.base<LIN_BIAS>(), d.p<LIN_ADD>(s), d.p<LIN_GATE>(s), d.w<RD_LD + LIN_LD_ADD>(), d.w<RD_LD + LIN_LD_GATE>(), (flags & DF_ADD_POLLED) != 0,
+                             (flags & DF_RELU) != 0, d.f<LIN_F_SLOPE>(), Out{d.m<LIN_ORM>(s), d.w<RD_LD + LD_OUT>(), (flags & DF_RM_SC1) != 0, d.m<LIN_O16>(s),
+                                                                             d.w<RD_N16 + N16_OUT>(), d.m<LIN_O16B>(s), d.w<RD_N16 + N16_OUTB>()}};
             };
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
@@ -247,23 +217,24 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             if (nt == 0) nx.fetch(ltab, nx_i, nx_s);  // (a visit without tiles)
           } break;
           case K_LINSEQ: {
-            const int n = d.w<RD_I + 1>();
+            const int n = d.w<RD_I + LINSEQ_I_N>();
             const bool gated = (flags & DF_SEQ_GATE) != 0;
-            const float* A = d.p<0>(s);
-            const int K0 = d.w<RD_I + 3>();  // the FIRST link's K when it is not the run's (0: it is): the link in front of a run joins its visit
+            const float* A = d.p<LINSEQ_A0>(s);
+            const int K0 = d.w<RD_I + LINSEQ_I_K0>();  // the FIRST link's K when it is not the run's (0: it is): the link in front of a run joins its visit
             for (int lq = 0; lq < n; ++lq) {  // (links outside, tiles inside: link li+1 of any tile needs link li of ALL tiles of its row tile)
               int li = lq;
               asm volatile("" : "+s"(li));  // opaque: the five lane indices below are li + constant where they are used, not five more loop counters in SGPRs
               pl.code = ((unsigned)s << 4) | (unsigned)i | ((unsigned)li << 28);
-              const float* W = d.basedyn(1 + li);
+              const float* W = d.basedyn(LINSEQ_W + li);
               const int Kl = (li == 0 && K0 != 0) ? K0 : K;
               auto late = [&]() {
                 __builtin_amdgcn_sched_barrier(0);
                 if (li == 0) nx.fetch(ltab, nx_i, nx_s);  // the next descriptor, once per visit, behind the first link's operand loads (every tile of it: the same lanes again)
-                const float* aux = d.pdyn(5 + li);  // bias (stride 0: the stepped pointer IS the base) | gate (stepped)
-                const float* add0 = li == 0 ? d.p<17>(s) : nullptr;  // the first link's row-major addend [B, i[0]] (null: none)
-                return LinLate{gated ? nullptr : aux, add0, gated ? aux : nullptr, d.w<RD_I + 0>(), d.w<RD_I + 2>(), false, (flags & DF_RELU) != 0, d.f<0>(),
-                               Out{const_cast<float*>(d.pdyn(9 + li)), d.wdyn(RD_LD + li), false, const_cast<float*>(d.pdyn(13 + li)), d.w<RD_N16>()}};
+                const float* aux = d.pdyn(LINSEQ_AUX + li);  // bias (stride 0: the stepped pointer IS the base) | gate (stepped)
+                const float* add0 = li == 0 ? d.p<LINSEQ_ADD0>(s) : nullptr;  // the first link's row-major addend (null: none)
+                return LinLate{gated ? nullptr : aux, add0, gated ? aux : nullptr, d.w<RD_I + LINSEQ_I_LD_ADD0>(), d.w<RD_I + LINSEQ_I_LD_GATE>(), false,
+                               (flags & DF_RELU) != 0, d.f<LINSEQ_F_SLOPE>(), Out{const_cast<float*>(d.pdyn(LINSEQ_ORM + li)), d.wdyn(RD_LD + LINSEQ_LD_ORM + li),
+                                                                                  false, const_cast<float*>(d.pdyn(LINSEQ_O16 + li)), d.w<RD_N16 + N16_OUT>()}};
               };
               // (a run's links are plain: a partial-sum operand or a K-range is a K_LIN in front of the run.  The summing link as a run's first
               // link was built and measured, r03: the three-slab product inlined at this call site costs the WHOLE kernel +0.4 ms per
@@ -272,133 +243,123 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
                 const int trc = d.tile(tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
                 tile_lin_late<NW, OT>(A, 0, true, W, Kl, late, tr0, tc0, B, red(), pl);
               }
-              A = d.pdyn(13 + li);  // the next link multiplies what this one stored
+              A = d.pdyn(LINSEQ_O16 + li);  // the next link multiplies what this one stored
             }
             if (nt == 0) nx.fetch(ltab, nx_i, nx_s);  // (a visit without tiles)
           } break;
           case K_HEAD: {
-            const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld2 = d.w<RD_LD + 2>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
-            (void)ld0; (void)ld1; (void)ld2; (void)ld3; (void)n16;
-            const HeadOut o{d.m<7>(s), d.m<8>(s), d.m<9>(s), d.m<10>(s), d.m<11>(s), d.m<12>(s), d.m<13>(s),
-                            Out{d.m<14>(s), ld3, false, d.m<15>(s), n16, d.m<16>(s), d.w<RD_N16 + 1>()}};
-            const int Z = d.w<RD_I + 0>(), residual = d.w<RD_I + 1>();
+            const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
+            const HeadOut o{d.m<HEAD_MU_P>(s), d.m<HEAD_SD_P>(s), d.m<HEAD_MU_Q>(s), d.m<HEAD_SD_Q>(s), d.m<HEAD_RAW_P>(s), d.m<HEAD_RAW_Q>(s), d.m<HEAD_MUQ_RAW>(s),
+                            Out{d.m<HEAD_Z>(s), ld3, false, d.m<HEAD_Z16>(s), n16, d.m<HEAD_Z16B>(s), d.w<RD_N16 + N16_OUTB>()}};
+            const int Z = d.w<RD_I + HEAD_I_Z>(), residual = d.w<RD_I + HEAD_I_RESIDUAL>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_head<NW, OT>(d.p<0>(s), d.p<1>(s), true, d.base<2>(), d.base<3>(), d.base<4>(), d.base<5>(), d.p<6>(s), o, K, Z, residual, d.f<0>(), d.f<1>(),
-                            d.f<2>(), trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
+              tile_head<NW, OT>(d.p<HEAD_P16>(s), d.p<HEAD_Q16>(s), true, d.base<HEAD_WP>(), d.base<HEAD_BP>(), d.base<HEAD_WQ>(), d.base<HEAD_BQ>(), d.p<HEAD_EPS>(s), o,
+                                K, Z, residual, d.f<HEAD_F_BETA>(), d.f<HEAD_F_INV_BETA>(), d.f<HEAD_F_SD_EPS>(), trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_GRU: {
-            const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld2 = d.w<RD_LD + 2>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
-            (void)ld0; (void)ld1; (void)ld2; (void)ld3; (void)n16;
-            const Out o{d.m<5>(s), ld3, true, d.m<6>(s), n16, d.m<11>(s), d.w<RD_N16 + 1>()};
-            const int R = d.w<RD_I + 0>();
+            const int ld0 = d.w<RD_LD + GRU_LD_HPREV>(), ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
+            const Out o{d.m<GRU_HRM>(s), ld3, true, d.m<GRU_H16>(s), n16, d.m<GRU_H16B>(s), d.w<RD_N16 + N16_OUTB>()};
+            const int R = d.w<RD_I + GRU_I_R>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_gru<NW, OT>(d.p<0>(s), 0, true, d.base<1>(), K, d.p<2>(s), d.base<10>(), d.p<3>(s), d.p<4>(s), ld0, R, o, d.m<7>(s), d.m<8>(s), d.m<9>(s),
-                           trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
+              tile_gru<NW, OT>(d.p<GRU_X16>(s), 0, true, d.base<GRU_WIH>(), K, d.p<GRU_XG>(s), d.base<GRU_BIH>(), d.p<GRU_GH>(s), d.p<GRU_HPREV>(s), ld0, R, o,
+                               d.m<GRU_RG>(s), d.m<GRU_UG>(s), d.m<GRU_NG>(s), trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_DZ: {
-            const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld2 = d.w<RD_LD + 2>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
-            (void)ld0; (void)ld1; (void)ld2; (void)ld3; (void)n16;
+            const int ld1 = d.w<RD_LD + DZ_LD_ADD>(), ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
             DzIn z;
-            z.mu_q = d.p<5>(s); z.sd_q = d.p<6>(s); z.mu_p = d.p<7>(s); z.sd_p = d.p<8>(s); z.eps = d.p<9>(s); z.raw_q = d.p<10>(s); z.raw_p = d.p<11>(s);
-            z.muq_raw = d.p<12>(s);
-            z.x_sl = reinterpret_cast<const int32_t*>(d.base<13>()); z.c_raw = d.base<14>(); z.c_fn = d.base<15>();
-            z.t = d.w<RD_I + 3>() - s; z.stride = d.w<RD_I + 2>(); z.residual = d.w<RD_I + 1>();
-            z.fn_floor = d.f<0>(); z.beta = d.f<1>(); z.sd_eps = d.f<2>();
-            z.has_gemm = s >= (int)d.f<3>();
-            const int Z = d.w<RD_I + 0>();
-            const Out oq{d.m<16>(s), ld3, false, d.m<17>(s), n16}, op{d.m<18>(s), ld3, false, d.m<19>(s), n16};
+            z.mu_q = d.p<DZ_MU_Q>(s); z.sd_q = d.p<DZ_SD_Q>(s); z.mu_p = d.p<DZ_MU_P>(s); z.sd_p = d.p<DZ_SD_P>(s); z.eps = d.p<DZ_EPS>(s); z.raw_q = d.p<DZ_RAW_Q>(s);
+            z.raw_p = d.p<DZ_RAW_P>(s); z.muq_raw = d.p<DZ_MUQ_RAW>(s); z.x_sl = reinterpret_cast<const int32_t*>(d.base<DZ_X_SL>()); z.c_raw = d.base<DZ_C_RAW>();
+            z.c_fn = d.base<DZ_C_FN>(); z.t = d.w<RD_I + DZ_I_T0>() - s; z.stride = d.w<RD_I + DZ_I_STRIDE>(); z.residual = d.w<RD_I + DZ_I_RESIDUAL>();
+            z.fn_floor = d.f<DZ_F_FN_FLOOR>(); z.beta = d.f<DZ_F_BETA>(); z.sd_eps = d.f<DZ_F_SD_EPS>(); z.has_gemm = s >= (int)d.f<DZ_F_GEMM_FROM>();
+            const int Z = d.w<RD_I + DZ_I_Z>();
+            const Out oq{d.m<DZ_DQH>(s), ld3, false, d.m<DZ_DQH16>(s), n16}, op{d.m<DZ_DPH>(s), ld3, false, d.m<DZ_DPH16>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_dz<NW, OT>(d.p<0>(s), d.base<1>(), d.p<2>(s), d.base<3>(), true, d.p<4>(s), ld1, (flags & DF_ADD_POLLED) != 0, z, oq, op, K, Z, trc & 0xffff,
-                          (trc >> 16) * 16, B, red(), pl);
+              tile_dz<NW, OT>(d.p<DZ_D16>(s), d.base<DZ_WT>(), d.p<DZ_D2_16>(s), d.base<DZ_WT2>(), true, d.p<DZ_ADD>(s), ld1, (flags & DF_ADD_POLLED) != 0, z, oq,
+                              op, K, Z, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_GRUB: {
-            const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld2 = d.w<RD_LD + 2>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
-            (void)ld0; (void)ld1; (void)ld2; (void)ld3; (void)n16;
+            const int ld0 = d.w<RD_LD + GRUB_LD_H>(), ld1 = d.w<RD_LD + GRUB_LD_GADD>(), ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
             GrubIn g;
-            g.D0 = d.p<0>(s); g.D1 = d.p<1>(s); g.W0 = d.base<2>(); g.W1 = d.base<3>(); g.g_in = d.p<4>(s); g.g_add = d.p<17>(s); g.ld_gadd = ld1;
-            g.rg = d.p<5>(s); g.ug = d.p<6>(s); g.ng = d.p<7>(s); g.gh = d.p<8>(s); g.hprev = d.p<9>(s); g.dd = d.p<10>(s); g.ldh = ld0;
-            g.dgi = Out{d.m<11>(s), ld3, false, d.m<12>(s), n16};
-            g.dgh = Out{d.m<13>(s), ld3, false, d.m<14>(s), n16};
-            g.ga = d.m<15>(s); g.g_out = const_cast<float*>(d.base<16>());
-            g.has_gemm = s >= d.w<RD_I + 1>(); g.has_gates = s < d.w<RD_I + 2>(); g.has_gin = s >= d.w<RD_I + 3>();
-            const int R = d.w<RD_I + 0>();
+            g.D0 = d.p<GRUB_D0_16>(s); g.D1 = d.p<GRUB_D1_16>(s); g.W0 = d.base<GRUB_W0>(); g.W1 = d.base<GRUB_W1>(); g.g_in = d.p<GRUB_G_IN>(s);
+            g.g_add = d.p<GRUB_G_ADD>(s); g.ld_gadd = ld1; g.rg = d.p<GRUB_RG>(s); g.ug = d.p<GRUB_UG>(s); g.ng = d.p<GRUB_NG>(s); g.gh = d.p<GRUB_GH>(s);
+            g.hprev = d.p<GRUB_HPREV>(s); g.dd = d.p<GRUB_DD>(s); g.ldh = ld0; g.dgi = Out{d.m<GRUB_DGI>(s), ld3, false, d.m<GRUB_DGI16>(s), n16};
+            g.dgh = Out{d.m<GRUB_DGH>(s), ld3, false, d.m<GRUB_DGH16>(s), n16}; g.ga = d.m<GRUB_GA>(s); g.g_out = const_cast<float*>(d.base<GRUB_G_OUT>());
+            g.has_gemm = s >= d.w<RD_I + GRUB_I_GEMM_FROM>(); g.has_gates = s < d.w<RD_I + GRUB_I_GATES_TO>(); g.has_gin = s >= d.w<RD_I + GRUB_I_GIN_FROM>();
+            const int R = d.w<RD_I + GRUB_I_R>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
               tile_grub<NW, OT>(g, K, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_GRUS: {
-            const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld2 = d.w<RD_LD + 2>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
-            (void)ld0; (void)ld1; (void)ld2; (void)ld3; (void)n16;
-            const int R = d.w<RD_I + 0>();
+            const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
+            const int R = d.w<RD_I + GRUS_I_R>();
             GruSeqIn g;
-            g.H16 = d.p<0>(s); g.Whh = d.base<1>(); g.bhh = d.base<2>(); g.xg = d.base<3>(); g.lens = reinterpret_cast<const int32_t*>(d.base<4>());
-            g.hprev = d.p<5>(s); g.out = const_cast<float*>(d.base<8>()); g.rg = d.m<9>(s); g.ug = d.m<10>(s); g.ng = d.m<11>(s); g.ghn = d.m<12>(s);
-            g.out_ts = d.w<RD_I + 2>(); g.out_ld = d.w<RD_I + 3>(); g.j = s; g.reverse = d.w<RD_I + 1>();
-            const Out o{d.m<6>(s), ld3, false, d.m<7>(s), n16};
+            g.H16 = d.p<GRUS_H16>(s); g.Whh = d.base<GRUS_WHH>(); g.bhh = d.base<GRUS_BHH>(); g.xg = d.base<GRUS_XG>();
+            g.lens = reinterpret_cast<const int32_t*>(d.base<GRUS_LENS>()); g.hprev = d.p<GRUS_HPREV>(s); g.out = const_cast<float*>(d.base<GRUS_OUT>());
+            g.rg = d.m<GRUS_RG>(s); g.ug = d.m<GRUS_UG>(s); g.ng = d.m<GRUS_NG>(s); g.ghn = d.m<GRUS_GHN>(s); g.out_ts = d.w<RD_I + GRUS_I_OUT_TS>();
+            g.out_ld = d.w<RD_I + GRUS_I_OUT_LD>(); g.j = s; g.reverse = d.w<RD_I + GRUS_I_REVERSE>();
+            const Out o{d.m<GRUS_HNEXT>(s), ld3, false, d.m<GRUS_HNEXT16>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
               tile_gru_seq<NW, OT>(g, o, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_GRUSB: {
-            const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld2 = d.w<RD_LD + 2>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
-            (void)ld0; (void)ld1; (void)ld2; (void)ld3; (void)n16;
-            const int R = d.w<RD_I + 0>(), T = d.w<RD_N16 + 1>();
+            const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
+            const int R = d.w<RD_I + GRUSB_I_R>(), T = d.w<RD_N16 + GRUSB_N16_T>();
             GruSeqBwdIn g;
-            g.DGHn16 = d.p<0>(s); g.WhhT = d.base<1>(); g.dout = d.base<2>(); g.rg = d.p<3>(s); g.ug = d.p<4>(s); g.ng = d.p<5>(s); g.ghn = d.p<6>(s);
-            g.hprev = d.p<7>(s); g.lens = reinterpret_cast<const int32_t*>(d.base<8>()); g.G = const_cast<float*>(d.base<9>());
-            g.DGI = const_cast<float*>(d.base<10>()); g.dh0 = const_cast<float*>(d.base<13>());
-            g.out_ts = d.w<RD_I + 2>(); g.out_ld = d.w<RD_I + 3>(); g.j = T - 1 - s; g.reverse = d.w<RD_I + 1>();
+            g.DGHn16 = d.p<GRUSB_DGH16_IN>(s); g.WhhT = d.base<GRUSB_WHHT>(); g.dout = d.base<GRUSB_DOUT>(); g.rg = d.p<GRUSB_RG>(s); g.ug = d.p<GRUSB_UG>(s);
+            g.ng = d.p<GRUSB_NG>(s); g.ghn = d.p<GRUSB_GHN>(s); g.hprev = d.p<GRUSB_HPREV>(s); g.lens = reinterpret_cast<const int32_t*>(d.base<GRUSB_LENS>());
+            g.G = const_cast<float*>(d.base<GRUSB_G>()); g.DGI = const_cast<float*>(d.base<GRUSB_DGI>()); g.dh0 = const_cast<float*>(d.base<GRUSB_DH0>());
+            g.out_ts = d.w<RD_I + GRUSB_I_OUT_TS>(); g.out_ld = d.w<RD_I + GRUSB_I_OUT_LD>(); g.j = T - 1 - s; g.reverse = d.w<RD_I + GRUSB_I_REVERSE>();
             g.has_gemm = s >= 1; g.has_gates = s < T;
-            const Out o{d.m<11>(s), ld3, false, d.m<12>(s), n16};
+            const Out o{d.m<GRUSB_DGH>(s), ld3, false, d.m<GRUSB_DGH16>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
               tile_gru_seq_bwd<NW, OT>(g, o, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_LSTMS: {
-            const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld2 = d.w<RD_LD + 2>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
-            (void)ld0; (void)ld1; (void)ld2; (void)ld3; (void)n16;
-            const int H = d.w<RD_I + 0>();
+            const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
+            const int H = d.w<RD_I + LSTMS_I_H>();
             LstmSeqIn g;
-            g.H16 = d.p<0>(s); g.Whh = d.base<1>(); g.bhh = d.base<2>(); g.xg = d.p<3>(s); g.lens = reinterpret_cast<const int32_t*>(d.base<4>());
-            g.hprev = d.p<5>(s); g.cprev = d.p<8>(s); g.cnext = d.m<9>(s); g.out = d.m<10>(s); g.gates = d.m<11>(s); g.t = s;
-            const Out o{d.m<6>(s), ld3, false, d.m<7>(s), n16};
+            g.H16 = d.p<LSTMS_H16>(s); g.Whh = d.base<LSTMS_WHH>(); g.bhh = d.base<LSTMS_BHH>(); g.xg = d.p<LSTMS_XG>(s);
+            g.lens = reinterpret_cast<const int32_t*>(d.base<LSTMS_LENS>()); g.hprev = d.p<LSTMS_HPREV>(s); g.cprev = d.p<LSTMS_CPREV>(s); g.cnext = d.m<LSTMS_CNEXT>(s);
+            g.out = d.m<LSTMS_OUT>(s); g.gates = d.m<LSTMS_GATES>(s); g.t = s;
+            const Out o{d.m<LSTMS_HNEXT>(s), ld3, false, d.m<LSTMS_HNEXT16>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
               tile_lstm_seq<NW, OT>(g, o, H, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_LSTMSB: {
-            const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld2 = d.w<RD_LD + 2>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
-            (void)ld0; (void)ld1; (void)ld2; (void)ld3; (void)n16;
-            const int H = d.w<RD_I + 0>(), T = d.w<RD_N16 + 1>();
+            const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
+            const int H = d.w<RD_I + LSTMSB_I_H>(), T = d.w<RD_N16 + LSTMSB_N16_T>();
             LstmSeqBwdIn g;
-            g.DGn16 = d.p<0>(s); g.WhhT = d.base<1>(); g.dout = d.p<2>(s); g.gates = d.p<3>(s); g.c_s = d.p<4>(s); g.c_s1 = g.c_s + (size_t)B * H;
-            g.DC = const_cast<float*>(d.base<5>()); g.dh0 = const_cast<float*>(d.base<8>());
-            g.has_gemm = s >= 1; g.has_gates = s < T;
-            const Out o{d.m<6>(s), ld3, false, d.m<7>(s), n16};
+            g.DGn16 = d.p<LSTMSB_DG16_IN>(s); g.WhhT = d.base<LSTMSB_WHHT>(); g.dout = d.p<LSTMSB_DOUT>(s); g.gates = d.p<LSTMSB_GATES>(s); g.c_s = d.p<LSTMSB_CS>(s);
+            g.c_s1 = g.c_s + (size_t)B * H; g.DC = const_cast<float*>(d.base<LSTMSB_DC>()); g.dh0 = const_cast<float*>(d.base<LSTMSB_DH0>()); g.has_gemm = s >= 1;
+            g.has_gates = s < T;
+            const Out o{d.m<LSTMSB_DG>(s), ld3, false, d.m<LSTMSB_DG16>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
               tile_lstm_seq_bwd<NW, OT>(g, o, H, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_DMOLS: {
-            const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld2 = d.w<RD_LD + 2>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
-            (void)ld0; (void)ld1; (void)ld2; (void)ld3; (void)n16;
-            const Out o{d.m<5>(s), ld3, false, d.m<6>(s), n16};
-            const int S = d.w<RD_I + 0>(), F = d.w<RD_I + 1>(), nmix = d.w<RD_I + 2>();
+            const int ld0 = d.w<RD_LD + DMOLS_LD_DEC>(), ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
+            const Out o{d.m<DMOLS_X>(s), ld3, false, d.m<DMOLS_X16>(s), n16};
+            const int S = d.w<RD_I + DMOLS_I_S>(), F = d.w<RD_I + DMOLS_I_F>(), nmix = d.w<RD_I + DMOLS_I_NMIX>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_dmol_sample<NW>(d.p<0>(s), ld0, d.base<1>(), d.base<2>(), d.p<3>(s), d.p<4>(s), S, F, nmix, d.f<0>(), o, trc & 0xffff, (trc >> 16) * 4, B,
-                                   red0, pl);
+              tile_dmol_sample<NW>(d.p<DMOLS_DEC>(s), ld0, d.base<DMOLS_W>(), d.base<DMOLS_B>(), d.p<DMOLS_U>(s), d.p<DMOLS_V>(s), S, F, nmix, d.f<DMOLS_F_LOG_EPS>(), o,
+                                   trc & 0xffff, (trc >> 16) * 4, B, red0, pl);
             }
           } break;
           default: break;
@@ -467,16 +428,17 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_rt_kernel(const int* __rest
         const int nt = d.w<RD_NT>();
         pl.nap = (flags & DF_GENTLE) ? 16 : 1;
         pl.code = ((unsigned)s << 4) | (unsigned)i;
-        const int ld0 = d.w<RD_LD + 0>(), ld1 = d.w<RD_LD + 1>(), ld3 = d.w<RD_LD + 3>(), n16 = d.w<RD_N16>();
+        const int ld0 = d.w<RD_LD + LIN_LD_A>(), ld1 = d.w<RD_LD + LIN_LD_ADD>(), ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
+        static_assert(LIN_LD_A == GRU_LD_HPREV && LIN_LD_A == GRUB_LD_H && LIN_LD_ADD == DZ_LD_ADD && LIN_LD_ADD == GRUB_LD_GADD, "ld0, ld1: every kind's");
         switch (kind) {
           case K_LIN: {
             const bool a_polled = !(flags & DF_A_PLAIN);
-            const float *A = d.p<0>(s), *W = d.base<1>();
-            const float *A2 = (flags & DF_A_SUM3) ? d.p<8>(s) : nullptr, *A3 = (flags & DF_A_SUM3) ? d.p<9>(s) : nullptr;
-            const int w_width = d.w<RD_I + 0>();
+            const float *A = d.p<LIN_A>(s), *W = d.base<LIN_W>();
+            const float *A2 = (flags & DF_A_SUM3) ? d.p<LIN_A2>(s) : nullptr, *A3 = (flags & DF_A_SUM3) ? d.p<LIN_A3>(s) : nullptr;
+            const int w_width = d.w<RD_I + LIN_I_W_WIDTH>();
             auto late = [&]() {
-              return LinLate{d.base<2>(), d.p<3>(s), d.p<4>(s), ld1, d.w<RD_LD + 2>(), (flags & DF_ADD_POLLED) != 0, (flags & DF_RELU) != 0, d.f<0>(),
-                             Out{d.m<5>(s), ld3, (flags & DF_RM_SC1) != 0, d.m<6>(s), n16, d.m<7>(s), d.w<RD_N16 + 1>()}};
+              return LinLate{d.base<LIN_BIAS>(), d.p<LIN_ADD>(s), d.p<LIN_GATE>(s), ld1, d.w<RD_LD + LIN_LD_GATE>(), (flags & DF_ADD_POLLED) != 0, (flags & DF_RELU) != 0,
+                             d.f<LIN_F_SLOPE>(), Out{d.m<LIN_ORM>(s), ld3, (flags & DF_RM_SC1) != 0, d.m<LIN_O16>(s), n16, d.m<LIN_O16B>(s), d.w<RD_N16 + N16_OUTB>()}};
             };
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
@@ -487,71 +449,70 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_rt_kernel(const int* __rest
             }
           } break;
           case K_LINSEQ: {
-            const int n = d.w<RD_I + 1>();
+            const int n = d.w<RD_I + LINSEQ_I_N>();
             const bool gated = (flags & DF_SEQ_GATE) != 0;
-            const float* A = d.p<0>(s);
-            const int K0 = d.w<RD_I + 3>();  // the first link's own K (0: the run's), as in pchain_kernel
+            const float* A = d.p<LINSEQ_A0>(s);
+            const int K0 = d.w<RD_I + LINSEQ_I_K0>();  // the first link's own K (0: the run's), as in pchain_kernel
             for (int li = 0; li < n; ++li) {
               pl.code = ((unsigned)s << 4) | (unsigned)i | ((unsigned)li << 28);
-              const float* W = d.basedyn(1 + li);
+              const float* W = d.basedyn(LINSEQ_W + li);
               const int Kl = (li == 0 && K0 != 0) ? K0 : K;
               auto late = [&]() {
-                const float* aux = d.pdyn(5 + li);
-                const float* add0 = li == 0 ? d.p<17>(s) : nullptr;
-                return LinLate{gated ? nullptr : aux, add0, gated ? aux : nullptr, d.w<RD_I + 0>(), d.w<RD_I + 2>(), false, (flags & DF_RELU) != 0, d.f<0>(),
-                               Out{const_cast<float*>(d.pdyn(9 + li)), d.wdyn(RD_LD + li), false, const_cast<float*>(d.pdyn(13 + li)), n16}};
+                const float* aux = d.pdyn(LINSEQ_AUX + li);
+                const float* add0 = li == 0 ? d.p<LINSEQ_ADD0>(s) : nullptr;
+                return LinLate{gated ? nullptr : aux, add0, gated ? aux : nullptr, d.w<RD_I + LINSEQ_I_LD_ADD0>(), d.w<RD_I + LINSEQ_I_LD_GATE>(), false,
+                               (flags & DF_RELU) != 0, d.f<LINSEQ_F_SLOPE>(), Out{const_cast<float*>(d.pdyn(LINSEQ_ORM + li)), d.wdyn(RD_LD + LINSEQ_LD_ORM + li),
+                                                                                  false, const_cast<float*>(d.pdyn(LINSEQ_O16 + li)), n16}};
               };
               for (int tk = 0; tk < nt; ++tk) {
                 const int trc = d.tile(tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
                 tile_lin_rt<NW, OT, RT, 1>(A, 0, true, W, Kl, late, tr0, tc0, B, red, pl);
               }
-              A = d.pdyn(13 + li);
+              A = d.pdyn(LINSEQ_O16 + li);
             }
           } break;
           case K_HEAD: {
-            const HeadOut o{d.m<7>(s), d.m<8>(s), d.m<9>(s), d.m<10>(s), d.m<11>(s), d.m<12>(s), d.m<13>(s),
-                            Out{d.m<14>(s), ld3, false, d.m<15>(s), n16, d.m<16>(s), d.w<RD_N16 + 1>()}};
-            const int Z = d.w<RD_I + 0>(), residual = d.w<RD_I + 1>();
+            const HeadOut o{d.m<HEAD_MU_P>(s), d.m<HEAD_SD_P>(s), d.m<HEAD_MU_Q>(s), d.m<HEAD_SD_Q>(s), d.m<HEAD_RAW_P>(s), d.m<HEAD_RAW_Q>(s), d.m<HEAD_MUQ_RAW>(s),
+                            Out{d.m<HEAD_Z>(s), ld3, false, d.m<HEAD_Z16>(s), n16, d.m<HEAD_Z16B>(s), d.w<RD_N16 + N16_OUTB>()}};
+            const int Z = d.w<RD_I + HEAD_I_Z>(), residual = d.w<RD_I + HEAD_I_RESIDUAL>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_head_rt<NW, OT, RT>(d.p<0>(s), d.p<1>(s), true, d.base<2>(), d.base<3>(), d.base<4>(), d.base<5>(), d.p<6>(s), o, K, Z, residual, d.f<0>(),
-                                       d.f<1>(), d.f<2>(), trc & 0xffff, (trc >> 16) * 16, B, red, pl);
+              tile_head_rt<NW, OT, RT>(d.p<HEAD_P16>(s), d.p<HEAD_Q16>(s), true, d.base<HEAD_WP>(), d.base<HEAD_BP>(), d.base<HEAD_WQ>(), d.base<HEAD_BQ>(),
+                                       d.p<HEAD_EPS>(s), o, K, Z, residual, d.f<HEAD_F_BETA>(), d.f<HEAD_F_INV_BETA>(), d.f<HEAD_F_SD_EPS>(), trc & 0xffff,
+                                       (trc >> 16) * 16, B, red, pl);
             }
           } break;
           case K_GRU: {
-            const Out o{d.m<5>(s), ld3, true, d.m<6>(s), n16, d.m<11>(s), d.w<RD_N16 + 1>()};
-            const int R = d.w<RD_I + 0>();
+            const Out o{d.m<GRU_HRM>(s), ld3, true, d.m<GRU_H16>(s), n16, d.m<GRU_H16B>(s), d.w<RD_N16 + N16_OUTB>()};
+            const int R = d.w<RD_I + GRU_I_R>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_gru_rt<NW, OT, RT>(d.p<0>(s), 0, true, d.base<1>(), K, d.p<2>(s), d.base<10>(), d.p<3>(s), d.p<4>(s), ld0, R, o, d.m<7>(s), d.m<8>(s),
-                                      d.m<9>(s), trc & 0xffff, (trc >> 16) * 16, B, red, pl);
+              tile_gru_rt<NW, OT, RT>(d.p<GRU_X16>(s), 0, true, d.base<GRU_WIH>(), K, d.p<GRU_XG>(s), d.base<GRU_BIH>(), d.p<GRU_GH>(s), d.p<GRU_HPREV>(s), ld0, R, o,
+                                      d.m<GRU_RG>(s), d.m<GRU_UG>(s), d.m<GRU_NG>(s), trc & 0xffff, (trc >> 16) * 16, B, red, pl);
             }
           } break;
           case K_DZ: {
             DzIn z;
-            z.mu_q = d.p<5>(s); z.sd_q = d.p<6>(s); z.mu_p = d.p<7>(s); z.sd_p = d.p<8>(s); z.eps = d.p<9>(s); z.raw_q = d.p<10>(s); z.raw_p = d.p<11>(s);
-            z.muq_raw = d.p<12>(s);
-            z.x_sl = reinterpret_cast<const int32_t*>(d.base<13>()); z.c_raw = d.base<14>(); z.c_fn = d.base<15>();
-            z.t = d.w<RD_I + 3>() - s; z.stride = d.w<RD_I + 2>(); z.residual = d.w<RD_I + 1>();
-            z.fn_floor = d.f<0>(); z.beta = d.f<1>(); z.sd_eps = d.f<2>();
-            z.has_gemm = s >= (int)d.f<3>();
-            const int Z = d.w<RD_I + 0>();
-            const Out oq{d.m<16>(s), ld3, false, d.m<17>(s), n16}, op{d.m<18>(s), ld3, false, d.m<19>(s), n16};
+            z.mu_q = d.p<DZ_MU_Q>(s); z.sd_q = d.p<DZ_SD_Q>(s); z.mu_p = d.p<DZ_MU_P>(s); z.sd_p = d.p<DZ_SD_P>(s); z.eps = d.p<DZ_EPS>(s); z.raw_q = d.p<DZ_RAW_Q>(s);
+            z.raw_p = d.p<DZ_RAW_P>(s); z.muq_raw = d.p<DZ_MUQ_RAW>(s); z.x_sl = reinterpret_cast<const int32_t*>(d.base<DZ_X_SL>()); z.c_raw = d.base<DZ_C_RAW>();
+            z.c_fn = d.base<DZ_C_FN>(); z.t = d.w<RD_I + DZ_I_T0>() - s; z.stride = d.w<RD_I + DZ_I_STRIDE>(); z.residual = d.w<RD_I + DZ_I_RESIDUAL>();
+            z.fn_floor = d.f<DZ_F_FN_FLOOR>(); z.beta = d.f<DZ_F_BETA>(); z.sd_eps = d.f<DZ_F_SD_EPS>(); z.has_gemm = s >= (int)d.f<DZ_F_GEMM_FROM>();
+            const int Z = d.w<RD_I + DZ_I_Z>();
+            const Out oq{d.m<DZ_DQH>(s), ld3, false, d.m<DZ_DQH16>(s), n16}, op{d.m<DZ_DPH>(s), ld3, false, d.m<DZ_DPH16>(s), n16};
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_dz_rt<NW, OT, RT>(d.p<0>(s), d.base<1>(), true, d.p<4>(s), ld1, (flags & DF_ADD_POLLED) != 0, z, oq, op, K, Z, trc & 0xffff, (trc >> 16) * 16, B,
-                                     red, pl);
+              tile_dz_rt<NW, OT, RT>(d.p<DZ_D16>(s), d.base<DZ_WT>(), true, d.p<DZ_ADD>(s), ld1, (flags & DF_ADD_POLLED) != 0, z, oq, op, K, Z, trc & 0xffff,
+                                     (trc >> 16) * 16, B, red, pl);
             }
           } break;
           case K_GRUB: {
             GrubIn g;
-            g.D0 = d.p<0>(s); g.D1 = d.p<1>(s); g.W0 = d.base<2>(); g.W1 = d.base<3>(); g.g_in = d.p<4>(s); g.g_add = d.p<17>(s); g.ld_gadd = ld1;
-            g.rg = d.p<5>(s); g.ug = d.p<6>(s); g.ng = d.p<7>(s); g.gh = d.p<8>(s); g.hprev = d.p<9>(s); g.dd = d.p<10>(s); g.ldh = ld0;
-            g.dgi = Out{d.m<11>(s), ld3, false, d.m<12>(s), n16};
-            g.dgh = Out{d.m<13>(s), ld3, false, d.m<14>(s), n16};
-            g.ga = d.m<15>(s); g.g_out = const_cast<float*>(d.base<16>());
-            g.has_gemm = s >= d.w<RD_I + 1>(); g.has_gates = s < d.w<RD_I + 2>(); g.has_gin = s >= d.w<RD_I + 3>();
-            const int R = d.w<RD_I + 0>();
+            g.D0 = d.p<GRUB_D0_16>(s); g.D1 = d.p<GRUB_D1_16>(s); g.W0 = d.base<GRUB_W0>(); g.W1 = d.base<GRUB_W1>(); g.g_in = d.p<GRUB_G_IN>(s);
+            g.g_add = d.p<GRUB_G_ADD>(s); g.ld_gadd = ld1; g.rg = d.p<GRUB_RG>(s); g.ug = d.p<GRUB_UG>(s); g.ng = d.p<GRUB_NG>(s); g.gh = d.p<GRUB_GH>(s);
+            g.hprev = d.p<GRUB_HPREV>(s); g.dd = d.p<GRUB_DD>(s); g.ldh = ld0; g.dgi = Out{d.m<GRUB_DGI>(s), ld3, false, d.m<GRUB_DGI16>(s), n16};
+            g.dgh = Out{d.m<GRUB_DGH>(s), ld3, false, d.m<GRUB_DGH16>(s), n16}; g.ga = d.m<GRUB_GA>(s); g.g_out = const_cast<float*>(d.base<GRUB_G_OUT>());
+            g.has_gemm = s >= d.w<RD_I + GRUB_I_GEMM_FROM>(); g.has_gates = s < d.w<RD_I + GRUB_I_GATES_TO>(); g.has_gin = s >= d.w<RD_I + GRUB_I_GIN_FROM>();
+            const int R = d.w<RD_I + GRUB_I_R>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
               tile_grub_rt<NW, OT, RT>(g, K, R, trc & 0xffff, (trc >> 16) * 16, B, red, pl);
@@ -718,11 +679,11 @@ extern "C" int blvm_pchain_chain_probe(const float* W16, const float* bias, floa
     bld.p.S = L / run;
     SeqLink lk[4];
     for (int i = 0; i < run; ++i) lk[i] = SeqLink{W16, bias, xs + (long)i * sN, run * sN, N, x16 + (long)(i + 1) * x};
-    add_linseq(bld, N / 16, 0, nw, N, true, false, 0, L / run, x16, run * x, run, lk, 0, run * x, N / 16, 0.f, 0);
+    add_linseq(bld, N / 16, 0, nw, N, true, false, 0, L / run, {x16, run * x}, run, lk, 0, run * x, N / 16, 0.f, 0);
   } else {
-    Desc& d = bld.add(K_LIN, N / 16, 0, nw, N, DF_RELU, 0, L);
-    bld.ptr(d, 0, x16, x); bld.ptr(d, 1, W16); bld.ptr(d, 2, bias); bld.ptr(d, 5, xs, sN); bld.ptr(d, 6, x16 + x, x);
-    d.ld[3] = N; d.n16[0] = N / 16; d.f[0] = 0.f;
+    Operands o;
+    o.p[LIN_A] = {x16, x}; o.p[LIN_W] = W16; o.p[LIN_BIAS] = bias; o.p[LIN_ORM] = {xs, sN}; o.p[LIN_O16] = {x16 + x, x}; o.ld[LD_OUT] = N; o.n16[N16_OUT] = N / 16;
+    add_desc(bld, K_LIN, N / 16, 0, nw, N, DF_RELU, 0, L, o);
   }
   int rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
   if (rc) return rc;

@@ -393,10 +393,10 @@ extern "C" int blvm_lstm_seq_fwd(const float* Wih, const float* Whh, const float
     bld.p.ot = seq_ot; bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 4;
     bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = 1;
     Desc& d = bld.add(K_LSTMS, ctH, 0, range_for(ctH * rt, device_cus() & ~7), H, 0, 0, T);
-    bld.ptr(d, 0, rs.H16, xH); bld.ptr(d, 1, rs.WhhP); bld.ptr(d, 2, bhh); bld.ptr(d, 3, rs.XG, s4H); bld.ptr(d, 4, lens);
-    bld.ptr(d, 5, rs.Hs, sH); bld.ptr(d, 6, rs.Hs + sH, sH); bld.ptr(d, 7, rs.H16 + xH, xH); bld.ptr(d, 8, rs.Cs, sH); bld.ptr(d, 9, rs.Cs + sH, sH);
-    bld.ptr(d, 10, out, sH); bld.ptr(d, 11, rs.GATES, s4H);
-    d.ld[3] = H; d.n16[0] = ctH; d.i[0] = H;
+    bld.ptr(d, LSTMS_H16, {rs.H16, xH}); bld.ptr(d, LSTMS_WHH, rs.WhhP); bld.ptr(d, LSTMS_BHH, bhh); bld.ptr(d, LSTMS_XG, {rs.XG, s4H}); bld.ptr(d, LSTMS_LENS, lens);
+    bld.ptr(d, LSTMS_HPREV, {rs.Hs, sH}); bld.ptr(d, LSTMS_HNEXT, {rs.Hs + sH, sH}); bld.ptr(d, LSTMS_HNEXT16, {rs.H16 + xH, xH}); bld.ptr(d, LSTMS_CPREV, {rs.Cs, sH});
+    bld.ptr(d, LSTMS_CNEXT, {rs.Cs + sH, sH}); bld.ptr(d, LSTMS_OUT, {out, sH}); bld.ptr(d, LSTMS_GATES, {rs.GATES, s4H}); d.ld[LD_OUT] = H; d.n16[N16_OUT] = ctH;
+    d.i[LSTMS_I_H] = H;
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
     if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(rs.H16 + xH, sizeof(float) * (size_t)T * xH, s));
@@ -462,10 +462,10 @@ extern "C" int blvm_lstm_seq_bwd(const float* Wih, const float* Whh, const float
     bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = 1;
     Desc& d = bld.add(K_LSTMSB, ctH, 0, range_for(ctH * rt, device_cus() & ~7), 4 * H, 0, 0, T + 1);
     // step s handles t = T-1-s: time-indexed slabs start at the last step and walk backwards; the T16 slabs are indexed by s
-    bld.ptr(d, 0, ws.DG16 - x4H, x4H); bld.ptr(d, 1, ws.WhhT); bld.ptr(d, 2, d_out + (long)(T - 1) * sH, -sH);
-    bld.ptr(d, 3, rs.GATES + (long)(T - 1) * s4H, -s4H); bld.ptr(d, 4, rs.Cs + (long)(T - 1) * sH, -sH); bld.ptr(d, 5, ws.DC);
-    bld.ptr(d, 6, ws.DG + (long)(T - 1) * s4H, -s4H); bld.ptr(d, 7, ws.DG16, x4H); bld.ptr(d, 8, d_h0 ? d_h0 : ws.DC);
-    d.ld[3] = 4 * H; d.n16[0] = 4 * ctH; d.n16[1] = T; d.i[0] = H;
+    bld.ptr(d, LSTMSB_DG16_IN, {ws.DG16 - x4H, x4H}); bld.ptr(d, LSTMSB_WHHT, ws.WhhT); bld.ptr(d, LSTMSB_DOUT, rev(d_out, sH, T - 1));
+    bld.ptr(d, LSTMSB_GATES, rev(rs.GATES, s4H, T - 1)); bld.ptr(d, LSTMSB_CS, rev(rs.Cs, sH, T - 1)); bld.ptr(d, LSTMSB_DC, ws.DC);
+    bld.ptr(d, LSTMSB_DG, rev(ws.DG, s4H, T - 1)); bld.ptr(d, LSTMSB_DG16, {ws.DG16, x4H}); bld.ptr(d, LSTMSB_DH0, d_h0 ? d_h0 : ws.DC); d.ld[LD_OUT] = 4 * H;
+    d.n16[N16_OUT] = 4 * ctH; d.n16[LSTMSB_N16_T] = T; d.i[LSTMSB_I_H] = H;
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
     if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(ws.DG16, sizeof(float) * (size_t)T * x4H, s));
@@ -551,10 +551,10 @@ extern "C" int blvm_gru_seq_fwd(const float* Wih, const float* Whh, const float*
     bld.p.ot = seq_ot; bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 3;
     bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = 1;
     Desc& d = bld.add(K_GRUS, ctR, 0, range_for(ctR * rt, device_cus() & ~7), R, 0, 0, T);
-    bld.ptr(d, 0, rs.H16, xR); bld.ptr(d, 1, rs.WhhP); bld.ptr(d, 2, bhh); bld.ptr(d, 3, rs.XG); bld.ptr(d, 4, lens); bld.ptr(d, 5, rs.Hs, sR);
-    bld.ptr(d, 6, rs.Hs + sR, sR); bld.ptr(d, 7, rs.H16 + xR, xR); bld.ptr(d, 8, out); bld.ptr(d, 9, rs.RG, sR); bld.ptr(d, 10, rs.UG, sR);
-    bld.ptr(d, 11, rs.NG, sR); bld.ptr(d, 12, rs.GHN, sR);
-    d.ld[3] = R; d.n16[0] = ctR; d.i[0] = R; d.i[1] = reverse ? 1 : 0; d.i[2] = (int)out_ts; d.i[3] = out_ld;
+    bld.ptr(d, GRUS_H16, {rs.H16, xR}); bld.ptr(d, GRUS_WHH, rs.WhhP); bld.ptr(d, GRUS_BHH, bhh); bld.ptr(d, GRUS_XG, rs.XG); bld.ptr(d, GRUS_LENS, lens);
+    bld.ptr(d, GRUS_HPREV, {rs.Hs, sR}); bld.ptr(d, GRUS_HNEXT, {rs.Hs + sR, sR}); bld.ptr(d, GRUS_HNEXT16, {rs.H16 + xR, xR}); bld.ptr(d, GRUS_OUT, out);
+    bld.ptr(d, GRUS_RG, {rs.RG, sR}); bld.ptr(d, GRUS_UG, {rs.UG, sR}); bld.ptr(d, GRUS_NG, {rs.NG, sR}); bld.ptr(d, GRUS_GHN, {rs.GHN, sR}); d.ld[LD_OUT] = R;
+    d.n16[N16_OUT] = ctR; d.i[GRUS_I_R] = R; d.i[GRUS_I_REVERSE] = reverse ? 1 : 0; d.i[GRUS_I_OUT_TS] = (int)out_ts; d.i[GRUS_I_OUT_LD] = out_ld;
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
     if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(rs.H16 + xR, sizeof(float) * (size_t)T * xR, s));
@@ -622,11 +622,12 @@ extern "C" int blvm_gru_seq_bwd(const float* Wih, const float* Whh, const float*
     bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = 1;
     Desc& d = bld.add(K_GRUSB, ctR, 0, range_for(ctR * rt, device_cus() & ~7), 3 * R, 0, 0, T + 1);
     // step s handles recurrence step j = T-1-s: the saves walk backwards from their last slab; the T16 slabs are indexed by s
-    bld.ptr(d, 0, ws.DGH16 - x3R, x3R); bld.ptr(d, 1, ws.WhhT); bld.ptr(d, 2, d_out);
-    bld.ptr(d, 3, rs.RG + (long)(T - 1) * sR, -sR); bld.ptr(d, 4, rs.UG + (long)(T - 1) * sR, -sR); bld.ptr(d, 5, rs.NG + (long)(T - 1) * sR, -sR);
-    bld.ptr(d, 6, rs.GHN + (long)(T - 1) * sR, -sR); bld.ptr(d, 7, rs.Hs + (long)(T - 1) * sR, -sR); bld.ptr(d, 8, lens); bld.ptr(d, 9, ws.G);
-    bld.ptr(d, 10, ws.DGI); bld.ptr(d, 11, ws.DGH + (long)(T - 1) * s3R, -s3R); bld.ptr(d, 12, ws.DGH16, x3R); bld.ptr(d, 13, d_h0 ? d_h0 : ws.G);
-    d.ld[3] = 3 * R; d.n16[0] = 3 * ctR; d.n16[1] = T; d.i[0] = R; d.i[1] = reverse ? 1 : 0; d.i[2] = (int)out_ts; d.i[3] = out_ld;
+    bld.ptr(d, GRUSB_DGH16_IN, {ws.DGH16 - x3R, x3R}); bld.ptr(d, GRUSB_WHHT, ws.WhhT); bld.ptr(d, GRUSB_DOUT, d_out); bld.ptr(d, GRUSB_RG, rev(rs.RG, sR, T - 1));
+    bld.ptr(d, GRUSB_UG, rev(rs.UG, sR, T - 1)); bld.ptr(d, GRUSB_NG, rev(rs.NG, sR, T - 1)); bld.ptr(d, GRUSB_GHN, rev(rs.GHN, sR, T - 1));
+    bld.ptr(d, GRUSB_HPREV, rev(rs.Hs, sR, T - 1)); bld.ptr(d, GRUSB_LENS, lens); bld.ptr(d, GRUSB_G, ws.G); bld.ptr(d, GRUSB_DGI, ws.DGI);
+    bld.ptr(d, GRUSB_DGH, rev(ws.DGH, s3R, T - 1)); bld.ptr(d, GRUSB_DGH16, {ws.DGH16, x3R}); bld.ptr(d, GRUSB_DH0, d_h0 ? d_h0 : ws.G); d.ld[LD_OUT] = 3 * R;
+    d.n16[N16_OUT] = 3 * ctR; d.n16[GRUSB_N16_T] = T; d.i[GRUSB_I_R] = R; d.i[GRUSB_I_REVERSE] = reverse ? 1 : 0; d.i[GRUSB_I_OUT_TS] = (int)out_ts;
+    d.i[GRUSB_I_OUT_LD] = out_ld;
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
     if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(ws.DGH16, sizeof(float) * (size_t)T * x3R, s));

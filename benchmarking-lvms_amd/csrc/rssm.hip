@@ -249,36 +249,35 @@ extern "C" int blvm_rssm_seq_fwd(const BlvmRssmWeights* w, const float* enc, con
     bld.p.ot = pchain_optype(B);
     bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 4;
     bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = r_h;
-    auto lin = [&](const float* A16, long a_step, const float* W, int K, const float* bias, const float* add, long add_step, float* orm, long rm_step,
-                   int ldo, bool rm_sc1, float* o16, long o16_step, int ct, int wg0, int nwg, int flags) {
-      Desc& d = bld.add(K_LIN, ct, wg0, nwg, K, flags | (rm_sc1 ? DF_RM_SC1 : 0), 0, T);
-      bld.ptr(d, 0, A16, a_step); bld.ptr(d, 1, W); bld.ptr(d, 2, bias); bld.ptr(d, 3, add, add_step); bld.ptr(d, 5, orm, rm_step);
-      bld.ptr(d, 6, o16, o16_step);
-      d.ld[1] = H; d.ld[3] = ldo; d.n16[0] = ctH; d.f[0] = 0.f;
-    };
     // L1: GRU input layer (z half; the context half is hoisted) | hidden projection of the GRU
-    lin(rs.Z16, xZ, rs.Wgz, Z, C > 0 ? nullptr : w->gin_b, C > 0 ? rs.XGIN : nullptr, sH, rs.GIN, sH, H, false, rs.GIN16, xH, ctH, 0, r_h, DF_RELU);
-    lin(rs.H16, xH, rs.Whh, H, w->gru_bhh, nullptr, 0, rs.GHb, s3H, 3 * H, true, nullptr, 0, 3 * ctH, r_h, r_gh, 0);
+    Operands gi, gh;
+    gi.p[LIN_A] = {rs.Z16, xZ}; gi.p[LIN_W] = rs.Wgz; gi.p[LIN_BIAS] = C > 0 ? nullptr : w->gin_b; gi.p[LIN_ADD] = {C > 0 ? rs.XGIN : nullptr, sH}; gi.ld[LIN_LD_ADD] = H;
+    gi.p[LIN_ORM] = {rs.GIN, sH}; gi.ld[LD_OUT] = H; gi.p[LIN_O16] = {rs.GIN16, xH}; gi.n16[N16_OUT] = ctH;
+    add_desc(bld, K_LIN, ctH, 0, r_h, Z, DF_RELU, 0, T, gi);
+    gh.p[LIN_A] = {rs.H16, xH}; gh.p[LIN_W] = rs.Whh; gh.p[LIN_BIAS] = w->gru_bhh; gh.ld[LIN_LD_ADD] = H; gh.p[LIN_ORM] = {rs.GHb, s3H}; gh.ld[LD_OUT] = 3 * H;
+    gh.n16[N16_OUT] = ctH;
+    add_desc(bld, K_LIN, 3 * ctH, r_h, r_gh, H, DF_RM_SC1, 0, T, gh);
     {  // L2: GRU
-      Desc& d = bld.add(K_GRU, ctH, 0, r_h, H, 0, 0, T);
-      bld.ptr(d, 0, rs.GIN16, xH); bld.ptr(d, 1, rs.Wih); bld.ptr(d, 2, nullptr); bld.ptr(d, 3, rs.GHb, s3H); bld.ptr(d, 4, hs, sH);
-      bld.ptr(d, 5, hs + sH, sH); bld.ptr(d, 6, rs.H16 + xH, xH); bld.ptr(d, 7, rs.RG, sH); bld.ptr(d, 8, rs.UG, sH); bld.ptr(d, 9, rs.NG, sH);
-      bld.ptr(d, 10, w->gru_bih);
-      d.ld[0] = H; d.ld[3] = H; d.n16[0] = ctH; d.i[0] = H;
+      Operands o;
+      o.p[GRU_X16] = {rs.GIN16, xH}; o.p[GRU_WIH] = rs.Wih; o.p[GRU_GH] = {rs.GHb, s3H}; o.p[GRU_HPREV] = {hs, sH}; o.p[GRU_HRM] = {hs + sH, sH};
+      o.p[GRU_H16] = {rs.H16 + xH, xH}; o.p[GRU_RG] = {rs.RG, sH}; o.p[GRU_UG] = {rs.UG, sH}; o.p[GRU_NG] = {rs.NG, sH}; o.p[GRU_BIH] = w->gru_bih;
+      o.ld[GRU_LD_HPREV] = H; o.ld[LD_OUT] = H; o.n16[N16_OUT] = ctH; o.i[GRU_I_R] = H;
+      add_desc(bld, K_GRU, ctH, 0, r_h, H, 0, 0, T, o);
     }
     {  // L3..L5: posterior | prior MLPs on h_t, one visit per branch and step (the first layer opens the run)
       const SeqLink lq[3] = {{rs.Wq[0], nullptr, rs.Q[0], sH, H, rs.Q16[0]}, {rs.Wq[1], w->post_b[1], rs.Q[1], sH, H, rs.Q16[1]}, {rs.Wq[2], w->post_b[2], rs.Q[2], sH, H, rs.Q16[2]}};
       const SeqLink lp[3] = {{rs.Wp[0], w->prior_b[0], rs.P[0], sH, H, rs.P16[0]}, {rs.Wp[1], w->prior_b[1], rs.P[1], sH, H, rs.P16[1]}, {rs.Wp[2], w->prior_b[2], rs.P[2], sH, H, rs.P16[2]}};
-      add_linseq(bld, ctH, 0, r_h, H, true, false, 0, T, rs.H16 + xH, xH, 3, lq, 0, xH, ctH, 0.f, 0, 0, rs.XQ, sH, H);
-      add_linseq(bld, ctH, r_h, r_h, H, true, false, 0, T, rs.H16 + xH, xH, 3, lp, 0, xH, ctH, 0.f, 0);
+      add_linseq(bld, ctH, 0, r_h, H, true, false, 0, T, {rs.H16 + xH, xH}, 3, lq, 0, xH, ctH, 0.f, 0, 0, {rs.XQ, sH}, H);
+      add_linseq(bld, ctH, r_h, r_h, H, true, false, 0, T, {rs.H16 + xH, xH}, 3, lp, 0, xH, ctH, 0.f, 0);
     }
     {  // L6: heads, combination, sample
-      Desc& d = bld.add(K_HEAD, ctZ, 0, range_for(ctZ * rt, 2 * r_h), H, 0, 0, T);
-      bld.ptr(d, 0, rs.P16[2], xH); bld.ptr(d, 1, rs.Q16[2], xH); bld.ptr(d, 2, rs.Wph); bld.ptr(d, 3, w->prior_hb); bld.ptr(d, 4, rs.Wqh);
-      bld.ptr(d, 5, w->post_hb); bld.ptr(d, 6, eps, sZ); bld.ptr(d, 7, mu_p, sZ); bld.ptr(d, 8, sd_p, sZ); bld.ptr(d, 9, mu_q, sZ);
-      bld.ptr(d, 10, sd_q, sZ); bld.ptr(d, 11, rs.RAWP, sZ); bld.ptr(d, 12, rs.RAWQ, sZ); bld.ptr(d, 13, rs.MUQR, sZ);
-      bld.ptr(d, 14, zs + sZ, sZ); bld.ptr(d, 15, rs.Z16 + xZ, xZ);
-      d.ld[3] = Z; d.n16[0] = ctZ; d.i[0] = Z; d.i[1] = mode; d.f[0] = beta; d.f[1] = 1.f / beta; d.f[2] = sd_eps;
+      Operands o;
+      o.p[HEAD_P16] = {rs.P16[2], xH}; o.p[HEAD_Q16] = {rs.Q16[2], xH}; o.p[HEAD_WP] = rs.Wph; o.p[HEAD_BP] = w->prior_hb; o.p[HEAD_WQ] = rs.Wqh;
+      o.p[HEAD_BQ] = w->post_hb; o.p[HEAD_EPS] = {eps, sZ}; o.p[HEAD_MU_P] = {mu_p, sZ}; o.p[HEAD_SD_P] = {sd_p, sZ}; o.p[HEAD_MU_Q] = {mu_q, sZ};
+      o.p[HEAD_SD_Q] = {sd_q, sZ}; o.p[HEAD_RAW_P] = {rs.RAWP, sZ}; o.p[HEAD_RAW_Q] = {rs.RAWQ, sZ}; o.p[HEAD_MUQ_RAW] = {rs.MUQR, sZ}; o.p[HEAD_Z] = {zs + sZ, sZ};
+      o.p[HEAD_Z16] = {rs.Z16 + xZ, xZ}; o.ld[LD_OUT] = Z; o.n16[N16_OUT] = ctZ; o.i[HEAD_I_Z] = Z; o.i[HEAD_I_RESIDUAL] = mode; o.f[HEAD_F_BETA] = beta;
+      o.f[HEAD_F_INV_BETA] = 1.f / beta; o.f[HEAD_F_SD_EPS] = sd_eps;
+      add_desc(bld, K_HEAD, ctZ, 0, range_for(ctZ * rt, 2 * r_h), H, 0, 0, T, o);
     }
     BLVM_REQUIRE(!bld.overflow, "rssm_fwd: persistent program overflow");
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
@@ -389,58 +388,56 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
     bld.p.ot = pchain_optype(B);
     bld.p.S = T + 1; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 2;
     bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = 2 * r_h;
-    auto at = [&](const float* base, long step, int t0) { return base ? base + (long)t0 * step : nullptr; };  // slab of step t0
-    auto lin = [&](const float* A16, long a_x, int a_t0, const float* W, int K, const float* add, long add_step, int add_t0, int ldadd, bool add_polled,
-                   const float* gate, long gate_step, float* orm, long rm_step, int ldo, bool rm_sc1, float* o16, long o16_x, int n16, int ct, int wg0,
-                   int nwg, int flags, int s0, int s1) {
-      Desc& d = bld.add(K_LIN, ct, wg0, nwg, K, flags | (add_polled ? DF_ADD_POLLED : 0) | (rm_sc1 ? DF_RM_SC1 : 0), s0, s1);
-      bld.ptr(d, 0, at(A16, a_x, a_t0), -a_x); bld.ptr(d, 1, W); bld.ptr(d, 3, at(add, add_step, add_t0), -add_step);
-      bld.ptr(d, 4, at(gate, gate_step, T - 1), -gate_step); bld.ptr(d, 5, rm_step ? at(orm, rm_step, T - 1) : orm, -rm_step);
-      bld.ptr(d, 6, at(o16, o16_x, T - 1), -o16_x);
-      d.ld[1] = ldadd; d.ld[2] = H; d.ld[3] = ldo; d.n16[0] = n16; d.f[0] = 0.f;
-    };
+    auto last = [&](const float* base, long step) { return rev(base, step, T - 1); };  // slab of t = T-1, walked backwards
     {  // B1: dz_t (direct + through the GRU input layer of step t+1), rsample / combination / KL / softplus heads
-      Desc& d = bld.add(K_DZ, ctZ, 0, range_for(ctZ * rt, 2 * r_h), H, 0, 0, T);
-      bld.ptr(d, 0, at(ws.DGIN16, xH, T), -xH); bld.ptr(d, 1, ws.gzT); bld.ptr(d, 4, at(d_zs, sZ, T), -sZ);
-      bld.ptr(d, 5, at(mu_q, sZ, T - 1), -sZ); bld.ptr(d, 6, at(sd_q, sZ, T - 1), -sZ); bld.ptr(d, 7, at(mu_p, sZ, T - 1), -sZ);
-      bld.ptr(d, 8, at(sd_p, sZ, T - 1), -sZ); bld.ptr(d, 9, at(eps, sZ, T - 1), -sZ); bld.ptr(d, 10, at(rs.RAWQ, sZ, T - 1), -sZ);
-      bld.ptr(d, 11, at(rs.RAWP, sZ, T - 1), -sZ); bld.ptr(d, 12, at(rs.MUQR, sZ, T - 1), -sZ);
-      bld.ptr(d, 13, x_sl); bld.ptr(d, 14, c_raw); bld.ptr(d, 15, c_fn);
-      bld.ptr(d, 16, at(ws.DQH, s2Z, T - 1), -s2Z); bld.ptr(d, 17, at(ws.DQH16, x2Z, T - 1), -x2Z); bld.ptr(d, 18, at(ws.DPH, s2Z, T - 1), -s2Z);
-      bld.ptr(d, 19, at(ws.DPH16, x2Z, T - 1), -x2Z);
-      d.ld[1] = Z; d.ld[3] = 2 * Z; d.n16[0] = 2 * ctZ; d.i[0] = Z; d.i[1] = mode; d.i[2] = stride; d.i[3] = T - 1;
-      d.f[0] = fn_floor; d.f[1] = beta; d.f[2] = sd_eps; d.f[3] = 1.f;
+      Operands z;
+      z.p[DZ_D16] = rev(ws.DGIN16, xH, T); z.p[DZ_WT] = ws.gzT; z.p[DZ_ADD] = rev(d_zs, sZ, T); z.ld[DZ_LD_ADD] = Z; z.p[DZ_MU_Q] = last(mu_q, sZ);
+      z.p[DZ_SD_Q] = last(sd_q, sZ); z.p[DZ_MU_P] = last(mu_p, sZ); z.p[DZ_SD_P] = last(sd_p, sZ); z.p[DZ_EPS] = last(eps, sZ); z.p[DZ_RAW_Q] = last(rs.RAWQ, sZ);
+      z.p[DZ_RAW_P] = last(rs.RAWP, sZ); z.p[DZ_MUQ_RAW] = last(rs.MUQR, sZ); z.p[DZ_X_SL] = x_sl; z.p[DZ_C_RAW] = c_raw; z.p[DZ_C_FN] = c_fn;
+      z.p[DZ_DQH] = last(ws.DQH, s2Z); z.p[DZ_DQH16] = last(ws.DQH16, x2Z); z.p[DZ_DPH] = last(ws.DPH, s2Z); z.p[DZ_DPH16] = last(ws.DPH16, x2Z); z.ld[LD_OUT] = 2 * Z;
+      z.n16[N16_OUT] = 2 * ctZ; z.i[DZ_I_Z] = Z; z.i[DZ_I_RESIDUAL] = mode; z.i[DZ_I_STRIDE] = stride; z.i[DZ_I_T0] = T - 1; z.f[DZ_F_FN_FLOOR] = fn_floor;
+      z.f[DZ_F_BETA] = beta; z.f[DZ_F_SD_EPS] = sd_eps; z.f[DZ_F_GEMM_FROM] = 1.f;
+      add_desc(bld, K_DZ, ctZ, 0, range_for(ctZ * rt, 2 * r_h), H, 0, 0, T, z);
     }
     // B2: heads -> third layers (posterior | prior), B3, B4 | GB[t] = GA[t+1] + DGH[t+1] W_hh
-    auto atm = [&](float* base, long step, int t0) { return base ? base + (long)t0 * step : nullptr; };
+    auto blink = [&](const float* W, const float* gate, float* orm, float* o16) { return rev_link(W, gate, orm, o16, T - 1, sH, H, xH); };
     {  // B2 .. B4 of a branch: one visit
-      const SeqLink lq[3] = {{ws.qhT, at(rs.Q[2], sH, T - 1), atm(ws.DQ[2], sH, T - 1), -sH, H, atm(ws.DQ16[2], xH, T - 1)},
-                             {ws.qT[2], at(rs.Q[1], sH, T - 1), atm(ws.DQ[1], sH, T - 1), -sH, H, atm(ws.DQ16[1], xH, T - 1)},
-                             {ws.qT[1], at(rs.Q[0], sH, T - 1), atm(ws.DQ[0], sH, T - 1), -sH, H, atm(ws.DQ16[0], xH, T - 1)}};
-      const SeqLink lp[3] = {{ws.phT, at(rs.P[2], sH, T - 1), atm(ws.DP[2], sH, T - 1), -sH, H, atm(ws.DP16[2], xH, T - 1)},
-                             {ws.pT[2], at(rs.P[1], sH, T - 1), atm(ws.DP[1], sH, T - 1), -sH, H, atm(ws.DP16[1], xH, T - 1)},
-                             {ws.pT[1], at(rs.P[0], sH, T - 1), atm(ws.DP[0], sH, T - 1), -sH, H, atm(ws.DP16[0], xH, T - 1)}};
-      add_linseq(bld, ctH, 0, r_h, H, false, true, 0, T, at(ws.DQH16, x2Z, T - 1), -x2Z, 3, lq, -sH, -xH, ctH, 0.f, H, 2 * Z);
-      add_linseq(bld, ctH, r_h, r_h, H, false, true, 0, T, at(ws.DPH16, x2Z, T - 1), -x2Z, 3, lp, -sH, -xH, ctH, 0.f, H, 2 * Z);
+      const SeqLink lq[3] = {blink(ws.qhT, rs.Q[2], ws.DQ[2], ws.DQ16[2]), blink(ws.qT[2], rs.Q[1], ws.DQ[1], ws.DQ16[1]), blink(ws.qT[1], rs.Q[0], ws.DQ[0], ws.DQ16[0])};
+      const SeqLink lp[3] = {blink(ws.phT, rs.P[2], ws.DP[2], ws.DP16[2]), blink(ws.pT[2], rs.P[1], ws.DP[1], ws.DP16[1]), blink(ws.pT[1], rs.P[0], ws.DP[0], ws.DP16[0])};
+      add_linseq(bld, ctH, 0, r_h, H, false, true, 0, T, last(ws.DQH16, x2Z), 3, lq, -sH, -xH, ctH, 0.f, H, 2 * Z);
+      add_linseq(bld, ctH, r_h, r_h, H, false, true, 0, T, last(ws.DPH16, x2Z), 3, lp, -sH, -xH, ctH, 0.f, H, 2 * Z);
     }
-    lin(ws.DGH16, x3H, T, ws.whhT, 3 * H, ws.GA, sH, T, H, true, nullptr, 0, ws.GB, sH, H, true, nullptr, 0, 0, ctH, 2 * r_h, r_gb, DF_GENTLE, 1, T);
+    Operands gb;  // (also the h0 link below)
+    gb.p[LIN_A] = rev(ws.DGH16, x3H, T); gb.p[LIN_W] = ws.whhT; gb.p[LIN_ADD] = rev(ws.GA, sH, T); gb.ld[LIN_LD_ADD] = H; gb.ld[LIN_LD_GATE] = H;
+    gb.p[LIN_ORM] = last(ws.GB, sH); gb.ld[LD_OUT] = H;
+    add_desc(bld, K_LIN, ctH, 2 * r_h, r_gb, 3 * H, DF_GENTLE | DF_ADD_POLLED | DF_RM_SC1, 1, T, gb);
     {  // B5: complete dL/dh_t, gate derivatives of step t
-      Desc& d = bld.add(K_GRUB, ctH, 0, r_h, H, 0, 0, T);
-      bld.ptr(d, 0, at(ws.DQ16[0], xH, T - 1), -xH); bld.ptr(d, 1, at(ws.DP16[0], xH, T - 1), -xH); bld.ptr(d, 2, ws.qT[0]); bld.ptr(d, 3, ws.pT[0]);
-      bld.ptr(d, 4, at(ws.GB, sH, T - 1), -sH);
-      bld.ptr(d, 5, at(rs.RG, sH, T - 1), -sH); bld.ptr(d, 6, at(rs.UG, sH, T - 1), -sH); bld.ptr(d, 7, at(rs.NG, sH, T - 1), -sH);
-      bld.ptr(d, 8, at(rs.GHb, s3H, T - 1), -s3H); bld.ptr(d, 9, at(hs, sH, T - 1), -sH); bld.ptr(d, 10, nullptr);
-      bld.ptr(d, 11, at(ws.DGI, s3H, T - 1), -s3H); bld.ptr(d, 12, at(ws.DGI16, x3H, T - 1), -x3H); bld.ptr(d, 13, at(ws.DGH, s3H, T - 1), -s3H);
-      bld.ptr(d, 14, at(ws.DGH16, x3H, T - 1), -x3H); bld.ptr(d, 15, at(ws.GA, sH, T - 1), -sH); bld.ptr(d, 16, ws.G);
-      bld.ptr(d, 17, at(d_hs, sH, T), -sH);
-      d.ld[0] = H; d.ld[1] = H; d.ld[3] = 3 * H; d.n16[0] = 3 * ctH; d.i[0] = H; d.i[1] = 0; d.i[2] = T; d.i[3] = 1;
+      Operands o;
+      o.p[GRUB_D0_16] = last(ws.DQ16[0], xH); o.p[GRUB_D1_16] = last(ws.DP16[0], xH); o.p[GRUB_W0] = ws.qT[0]; o.p[GRUB_W1] = ws.pT[0]; o.p[GRUB_G_IN] = last(ws.GB, sH);
+      o.p[GRUB_RG] = last(rs.RG, sH); o.p[GRUB_UG] = last(rs.UG, sH); o.p[GRUB_NG] = last(rs.NG, sH); o.p[GRUB_GH] = last(rs.GHb, s3H); o.p[GRUB_HPREV] = last(hs, sH);
+      o.p[GRUB_DGI] = last(ws.DGI, s3H); o.p[GRUB_DGI16] = last(ws.DGI16, x3H); o.p[GRUB_DGH] = last(ws.DGH, s3H); o.p[GRUB_DGH16] = last(ws.DGH16, x3H);
+      o.p[GRUB_GA] = last(ws.GA, sH); o.p[GRUB_G_OUT] = ws.G; o.p[GRUB_G_ADD] = rev(d_hs, sH, T); o.ld[GRUB_LD_H] = H; o.ld[GRUB_LD_GADD] = H; o.ld[LD_OUT] = 3 * H;
+      o.n16[N16_OUT] = 3 * ctH; o.i[GRUB_I_R] = H; o.i[GRUB_I_GEMM_FROM] = 0; o.i[GRUB_I_GATES_TO] = T; o.i[GRUB_I_GIN_FROM] = 1;
+      add_desc(bld, K_GRUB, ctH, 0, r_h, H, 0, 0, T, o);
     }
-    // B6: through the GRU input projection to the (ReLU) GRU input layer
-    lin(ws.DGI16, x3H, T - 1, ws.wihT, 3 * H, nullptr, 0, 0, 0, false, rs.GIN, sH, ws.DGIN, sH, H, false, ws.DGIN16, xH, ctH, ctH, 0, r_h, 0, 0, T);
+    {  // B6: through the GRU input projection to the (ReLU) GRU input layer
+      Operands o;
+      o.p[LIN_A] = last(ws.DGI16, x3H); o.p[LIN_W] = ws.wihT; o.p[LIN_GATE] = last(rs.GIN, sH); o.ld[LIN_LD_GATE] = H; o.p[LIN_ORM] = last(ws.DGIN, sH); o.ld[LD_OUT] = H;
+      o.p[LIN_O16] = last(ws.DGIN16, xH); o.n16[N16_OUT] = ctH;
+      add_desc(bld, K_LIN, ctH, 0, r_h, 3 * H, 0, 0, T, o);
+    }
     // s = T: gradients wrt the initial state: z0 through the GRU input layer of step 0 (+ its direct gradient), h0 through the GRU
     // of step 0 (the caller adds the direct gradient d_hs[0])
-    if (d_z0) lin(ws.DGIN16, xH, T, ws.gzT, H, d_zs, sZ, T, Z, false, nullptr, 0, d_z0, 0, Z, false, nullptr, 0, 0, ctZ, 0, range_for(ctZ * rt, 2 * r_h), 0, T, T + 1);
-    if (d_h0) lin(ws.DGH16, x3H, T, ws.whhT, 3 * H, ws.GA, sH, T, H, true, nullptr, 0, d_h0, 0, H, false, nullptr, 0, 0, ctH, 2 * r_h, r_gb, 0, T, T + 1);
+    if (d_z0) {
+      Operands o;
+      o.p[LIN_A] = rev(ws.DGIN16, xH, T); o.p[LIN_W] = ws.gzT; o.p[LIN_ADD] = rev(d_zs, sZ, T); o.ld[LIN_LD_ADD] = Z; o.ld[LIN_LD_GATE] = H; o.p[LIN_ORM] = d_z0;
+      o.ld[LD_OUT] = Z;
+      add_desc(bld, K_LIN, ctZ, 0, range_for(ctZ * rt, 2 * r_h), H, 0, T, T + 1, o);
+    }
+    if (d_h0) {
+      gb.p[LIN_ORM] = d_h0;
+      add_desc(bld, K_LIN, ctH, 2 * r_h, r_gb, 3 * H, DF_ADD_POLLED, T, T + 1, gb);
+    }
     BLVM_REQUIRE(!bld.overflow, "rssm_bwd: persistent program overflow");
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
     if (rc) return rc;

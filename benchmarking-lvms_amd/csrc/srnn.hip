@@ -138,16 +138,17 @@ extern "C" int blvm_srnn_latent_fwd(const BlvmSrnnWeights* w, const float* d, co
     {  // the three layers of the prior | posterior MLP: one visit per chain and step (the first layer, K = Z, opens the run)
       const SeqLink lp[3] = {{rs.Wp[0], nullptr, rs.P[0], sH, H, rs.P16[0]}, {rs.Wp[1], w->prior_b[1], rs.P[1], sH, H, rs.P16[1]}, {rs.Wp[2], w->prior_b[2], rs.P[2], sH, H, rs.P16[2]}};
       const SeqLink lq[3] = {{rs.Wq[0], nullptr, rs.Q[0], sH, H, rs.Q16[0]}, {rs.Wq[1], w->post_b[1], rs.Q[1], sH, H, rs.Q16[1]}, {rs.Wq[2], w->post_b[2], rs.Q[2], sH, H, rs.Q16[2]}};
-      add_linseq(bld, ctH, 0, half, H, true, false, 0, Tp, rs.Z16, xZ, 3, lp, 0, xH, ctH, slope, 0, Z, rs.XP, sH, H);
-      add_linseq(bld, ctH, half, half, H, true, false, 0, Tp, rs.Z16, xZ, 3, lq, 0, xH, ctH, slope, 0, Z, rs.XQ, sH, H);
+      add_linseq(bld, ctH, 0, half, H, true, false, 0, Tp, {rs.Z16, xZ}, 3, lp, 0, xH, ctH, slope, 0, Z, {rs.XP, sH}, H);
+      add_linseq(bld, ctH, half, half, H, true, false, 0, Tp, {rs.Z16, xZ}, 3, lq, 0, xH, ctH, slope, 0, Z, {rs.XQ, sH}, H);
     }
     {
-      Desc& d = bld.add(K_HEAD, ctZ, 0, range_for(ctZ * rt, 2 * half), H, 0, 0, Tp);
-      bld.ptr(d, 0, rs.P16[2], xH); bld.ptr(d, 1, rs.Q16[2], xH); bld.ptr(d, 2, rs.Wph); bld.ptr(d, 3, w->prior_hb); bld.ptr(d, 4, rs.Wqh);
-      bld.ptr(d, 5, w->post_hb); bld.ptr(d, 6, eps, sZ); bld.ptr(d, 7, mu_p, sZ); bld.ptr(d, 8, sd_p, sZ); bld.ptr(d, 9, mu_q, sZ);
-      bld.ptr(d, 10, sd_q, sZ); bld.ptr(d, 11, rs.RAWP, sZ); bld.ptr(d, 12, rs.RAWQ, sZ); bld.ptr(d, 13, nullptr);
-      bld.ptr(d, 14, zs + sZ, sZ); bld.ptr(d, 15, rs.Z16 + xZ, xZ);
-      d.ld[3] = Z; d.n16[0] = ctZ; d.i[0] = Z; d.i[1] = residual_posterior; d.f[0] = beta; d.f[1] = 1.f / beta; d.f[2] = sd_eps;
+      Operands o;
+      o.p[HEAD_P16] = {rs.P16[2], xH}; o.p[HEAD_Q16] = {rs.Q16[2], xH}; o.p[HEAD_WP] = rs.Wph; o.p[HEAD_BP] = w->prior_hb; o.p[HEAD_WQ] = rs.Wqh;
+      o.p[HEAD_BQ] = w->post_hb; o.p[HEAD_EPS] = {eps, sZ}; o.p[HEAD_MU_P] = {mu_p, sZ}; o.p[HEAD_SD_P] = {sd_p, sZ}; o.p[HEAD_MU_Q] = {mu_q, sZ};
+      o.p[HEAD_SD_Q] = {sd_q, sZ}; o.p[HEAD_RAW_P] = {rs.RAWP, sZ}; o.p[HEAD_RAW_Q] = {rs.RAWQ, sZ}; o.p[HEAD_Z] = {zs + sZ, sZ}; o.p[HEAD_Z16] = {rs.Z16 + xZ, xZ};
+      o.ld[LD_OUT] = Z; o.n16[N16_OUT] = ctZ; o.i[HEAD_I_Z] = Z; o.i[HEAD_I_RESIDUAL] = residual_posterior; o.f[HEAD_F_BETA] = beta; o.f[HEAD_F_INV_BETA] = 1.f / beta;
+      o.f[HEAD_F_SD_EPS] = sd_eps;
+      add_desc(bld, K_HEAD, ctZ, 0, range_for(ctZ * rt, 2 * half), H, 0, 0, Tp, o);
     }
     BLVM_REQUIRE(!bld.overflow, "srnn_fwd: persistent program overflow");
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
@@ -227,39 +228,32 @@ extern "C" int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, co
     bld.p.ot = pchain_optype(B);
     bld.p.S = T + 1; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 2;
     bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = half;
-    auto at = [&](const float* base, long step, int t0) { return base ? base + (long)t0 * step : nullptr; };
+    auto last = [&](const float* base, long step) { return rev(base, step, T - 1); };  // slab of t = T'-1, walked backwards
     {  // B1: dz_t = decoder gradient + the two first layers of step t+1, then rsample / residual / KL / softplus heads
-      Desc& d = bld.add(K_DZ, ctZ, 0, range_for(ctZ * rt, 2 * half), H, 0, 0, T);
-      bld.ptr(d, 0, at(ws.DP16[0], xH, T), -xH); bld.ptr(d, 1, ws.pzT); bld.ptr(d, 2, at(ws.DQ16[0], xH, T), -xH); bld.ptr(d, 3, ws.qzT);
-      bld.ptr(d, 4, at(d_z, sZ, T - 1), -sZ);
-      bld.ptr(d, 5, at(mu_q, sZ, T - 1), -sZ); bld.ptr(d, 6, at(sd_q, sZ, T - 1), -sZ); bld.ptr(d, 7, at(mu_p, sZ, T - 1), -sZ);
-      bld.ptr(d, 8, at(sd_p, sZ, T - 1), -sZ); bld.ptr(d, 9, at(eps, sZ, T - 1), -sZ); bld.ptr(d, 10, at(rs.RAWQ, sZ, T - 1), -sZ);
-      bld.ptr(d, 11, at(rs.RAWP, sZ, T - 1), -sZ); bld.ptr(d, 12, nullptr); bld.ptr(d, 13, x_sl); bld.ptr(d, 14, c_raw); bld.ptr(d, 15, c_fn);
-      bld.ptr(d, 16, at(ws.DQH, s2Z, T - 1), -s2Z); bld.ptr(d, 17, at(ws.DQH16, x2Z, T - 1), -x2Z); bld.ptr(d, 18, at(ws.DPH, s2Z, T - 1), -s2Z);
-      bld.ptr(d, 19, at(ws.DPH16, x2Z, T - 1), -x2Z);
-      d.ld[1] = Z; d.ld[3] = 2 * Z; d.n16[0] = 2 * ctZ; d.i[0] = Z; d.i[1] = residual_posterior; d.i[2] = stride; d.i[3] = T - 1;
-      d.f[0] = fn_floor; d.f[1] = beta; d.f[2] = sd_eps; d.f[3] = 1.f;
+      Operands z;
+      z.p[DZ_D16] = rev(ws.DP16[0], xH, T); z.p[DZ_WT] = ws.pzT; z.p[DZ_D2_16] = rev(ws.DQ16[0], xH, T); z.p[DZ_WT2] = ws.qzT; z.p[DZ_ADD] = last(d_z, sZ);
+      z.ld[DZ_LD_ADD] = Z; z.p[DZ_MU_Q] = last(mu_q, sZ); z.p[DZ_SD_Q] = last(sd_q, sZ); z.p[DZ_MU_P] = last(mu_p, sZ); z.p[DZ_SD_P] = last(sd_p, sZ);
+      z.p[DZ_EPS] = last(eps, sZ); z.p[DZ_RAW_Q] = last(rs.RAWQ, sZ); z.p[DZ_RAW_P] = last(rs.RAWP, sZ); z.p[DZ_X_SL] = x_sl; z.p[DZ_C_RAW] = c_raw; z.p[DZ_C_FN] = c_fn;
+      z.p[DZ_DQH] = last(ws.DQH, s2Z); z.p[DZ_DQH16] = last(ws.DQH16, x2Z); z.p[DZ_DPH] = last(ws.DPH, s2Z); z.p[DZ_DPH16] = last(ws.DPH16, x2Z); z.ld[LD_OUT] = 2 * Z;
+      z.n16[N16_OUT] = 2 * ctZ; z.i[DZ_I_Z] = Z; z.i[DZ_I_RESIDUAL] = residual_posterior; z.i[DZ_I_STRIDE] = stride; z.i[DZ_I_T0] = T - 1; z.f[DZ_F_FN_FLOOR] = fn_floor;
+      z.f[DZ_F_BETA] = beta; z.f[DZ_F_SD_EPS] = sd_eps; z.f[DZ_F_GEMM_FROM] = 1.f;
+      add_desc(bld, K_DZ, ctZ, 0, range_for(ctZ * rt, 2 * half), H, 0, 0, T, z);
     }
     // B2: heads -> third layers;  B3, B4: down to the first layers (LeakyReLU derivatives fused)
-    auto atm = [&](float* base, long step, int t0) { return base ? base + (long)t0 * step : nullptr; };
+    auto blink = [&](const float* W, const float* gate, float* orm, float* o16) { return rev_link(W, gate, orm, o16, T - 1, sH, H, xH); };
     {  // B2 .. B4 of a chain: one visit
-      const SeqLink lp[3] = {{ws.phT, at(rs.P[2], sH, T - 1), atm(ws.DP[2], sH, T - 1), -sH, H, atm(ws.DP16[2], xH, T - 1)},
-                             {ws.pT[2], at(rs.P[1], sH, T - 1), atm(ws.DP[1], sH, T - 1), -sH, H, atm(ws.DP16[1], xH, T - 1)},
-                             {ws.pT[1], at(rs.P[0], sH, T - 1), atm(ws.DP[0], sH, T - 1), -sH, H, atm(ws.DP16[0], xH, T - 1)}};
-      const SeqLink lq[3] = {{ws.qhT, at(rs.Q[2], sH, T - 1), atm(ws.DQ[2], sH, T - 1), -sH, H, atm(ws.DQ16[2], xH, T - 1)},
-                             {ws.qT[2], at(rs.Q[1], sH, T - 1), atm(ws.DQ[1], sH, T - 1), -sH, H, atm(ws.DQ16[1], xH, T - 1)},
-                             {ws.qT[1], at(rs.Q[0], sH, T - 1), atm(ws.DQ[0], sH, T - 1), -sH, H, atm(ws.DQ16[0], xH, T - 1)}};
-      add_linseq(bld, ctH, 0, half, H, false, true, 0, T, at(ws.DPH16, x2Z, T - 1), -x2Z, 3, lp, -sH, -xH, ctH, slope, H, 2 * Z);
-      add_linseq(bld, ctH, half, half, H, false, true, 0, T, at(ws.DQH16, x2Z, T - 1), -x2Z, 3, lq, -sH, -xH, ctH, slope, H, 2 * Z);
+      const SeqLink lp[3] = {blink(ws.phT, rs.P[2], ws.DP[2], ws.DP16[2]), blink(ws.pT[2], rs.P[1], ws.DP[1], ws.DP16[1]), blink(ws.pT[1], rs.P[0], ws.DP[0], ws.DP16[0])};
+      const SeqLink lq[3] = {blink(ws.qhT, rs.Q[2], ws.DQ[2], ws.DQ16[2]), blink(ws.qT[2], rs.Q[1], ws.DQ[1], ws.DQ16[1]), blink(ws.qT[1], rs.Q[0], ws.DQ[0], ws.DQ16[0])};
+      add_linseq(bld, ctH, 0, half, H, false, true, 0, T, last(ws.DPH16, x2Z), 3, lp, -sH, -xH, ctH, slope, H, 2 * Z);
+      add_linseq(bld, ctH, half, half, H, false, true, 0, T, last(ws.DQH16, x2Z), 3, lq, -sH, -xH, ctH, slope, H, 2 * Z);
     }
     if (d_z0) {  // s = T': gradient wrt the initial latent through both first layers of step 0 (two links: every word written once)
       const int r_z = range_for(ctZ * rt, half);
-      Desc& d1 = bld.add(K_LIN, ctZ, 0, r_z, H, DF_RM_SC1, T, T + 1);
-      bld.ptr(d1, 0, at(ws.DP16[0], xH, T), -xH); bld.ptr(d1, 1, ws.pzT); bld.ptr(d1, 5, ws.DZ0);
-      d1.ld[3] = Z;
-      Desc& d2 = bld.add(K_LIN, ctZ, half, r_z, H, DF_ADD_POLLED, T, T + 1);
-      bld.ptr(d2, 0, at(ws.DQ16[0], xH, T), -xH); bld.ptr(d2, 1, ws.qzT); bld.ptr(d2, 3, ws.DZ0); bld.ptr(d2, 5, d_z0);
-      d2.ld[1] = Z; d2.ld[3] = Z;
+      Operands o;
+      o.p[LIN_A] = rev(ws.DP16[0], xH, T); o.p[LIN_W] = ws.pzT; o.p[LIN_ORM] = ws.DZ0; o.ld[LD_OUT] = Z;
+      add_desc(bld, K_LIN, ctZ, 0, r_z, H, DF_RM_SC1, T, T + 1, o);
+      o.p[LIN_A] = rev(ws.DQ16[0], xH, T); o.p[LIN_W] = ws.qzT; o.p[LIN_ADD] = ws.DZ0; o.ld[LIN_LD_ADD] = Z; o.p[LIN_ORM] = d_z0;
+      add_desc(bld, K_LIN, ctZ, half, r_z, H, DF_ADD_POLLED, T, T + 1, o);
     }
     BLVM_REQUIRE(!bld.overflow, "srnn_bwd: persistent program overflow");
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);

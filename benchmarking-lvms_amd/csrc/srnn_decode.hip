@@ -105,52 +105,53 @@ extern "C" int blvm_srnn_generate(const BlvmSrnnDecodeWeights* w, const float* x
   // out = leaky(A W^T + bias): A a polled T16 slab of `a_n16` blocks per row tile, outputs: T16 slab(s) and / or row-major (polled words)
   auto lin = [&](size_t A16, long a_step, int a_n16, size_t W, int K, const float* bias, int ct, int flags, float* orm, long rm_step, int ldo, size_t o16,
                  long o16_step, int n16, int wg0, int nwg) {
-    Desc& d = bld.add(K_LIN, ct, wg0, nwg, K, flags, 0, T);
-    bld.ptr(d, 0, sc + A16, a_step); bld.ptr(d, 1, sc + W); bld.ptr(d, 2, bias); bld.ptr(d, 5, orm, rm_step);
-    bld.ptr(d, 6, o16 ? sc + o16 : nullptr, o16_step);
-    d.ld[0] = a_n16 * 16; d.ld[3] = ldo; d.n16[0] = n16; d.f[0] = slope;
+    Operands o;
+    o.p[LIN_A] = {sc + A16, a_step}; o.p[LIN_W] = sc + W; o.p[LIN_BIAS] = bias; o.p[LIN_ORM] = {orm, rm_step}; o.p[LIN_O16] = {o16 ? sc + o16 : nullptr, o16_step};
+    o.ld[LIN_LD_A] = a_n16 * 16; o.ld[LD_OUT] = ldo; o.n16[N16_OUT] = n16; o.f[LIN_F_SLOPE] = slope;
+    add_desc(bld, K_LIN, ct, wg0, nwg, K, flags, 0, T, o);
   };
   const int rH = range_for(ctH * rt, r_main);
   // CP slab index: slab 0 = [d_0 | -], slab s + 1 = cat[d_s | z_{s-1}] of step s
   lin(b.X16, xS, ctS, p.enc[0], S, w->enc_b[0], ctH, DF_RELU, nullptr, 0, 0, b.E16[0], xH, ctH, 0, rH);
   {  // the next two layers: one descriptor (K_LINSEQ)
     const SeqLink le[2] = {{sc + p.enc[1], w->enc_b[1], nullptr, 0, 0, sc + b.E16[1]}, {sc + p.enc[2], w->enc_b[2], nullptr, 0, 0, sc + b.ENC16}};
-    add_linseq(bld, ctH, 0, rH, H, true, false, 0, T, sc + b.E16[0], xH, 2, le, 0, xH, ctH, slope, 0);
+    add_linseq(bld, ctH, 0, rH, H, true, false, 0, T, {sc + b.E16[0], xH}, 2, le, 0, xH, ctH, slope, 0);
   }
   // gh_s = d_{s-1} Whh^T + b_hh: reads the d-part of slab s, first needed by the GRU link's epilogue
   lin(b.CP16, xCP, nCP, p.whh, R, w->gru_bhh, 3 * ctR, DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0), sc + b.GHb, s3R, 3 * R, 0, 0, 0, r_main,
       r_side);
   {  // d_s = GRU(enc_s, d_{s-1})
-    Desc& d = bld.add(K_GRU, ctR, 0, range_for(ctR * rt, r_main), H, 0, 0, T);
-    bld.ptr(d, 0, sc + b.ENC16, xH); bld.ptr(d, 1, sc + p.wih); bld.ptr(d, 2, nullptr); bld.ptr(d, 3, sc + b.GHb, s3R); bld.ptr(d, 4, sc + b.DS, sR);
-    bld.ptr(d, 5, sc + b.DS + sR, sR); bld.ptr(d, 6, sc + b.CP16 + xCP, xCP); bld.ptr(d, 7, sc + b.dummyR); bld.ptr(d, 8, sc + b.dummyR);
-    bld.ptr(d, 9, sc + b.dummyR); bld.ptr(d, 10, w->gru_bih); bld.ptr(d, 11, sc + b.DC16 + (size_t)ctZ * 256, xDC);
-    d.ld[0] = R; d.ld[3] = R; d.n16[0] = nCP; d.n16[1] = nDC; d.i[0] = R;
+    Operands o;
+    o.p[GRU_X16] = {sc + b.ENC16, xH}; o.p[GRU_WIH] = sc + p.wih; o.p[GRU_GH] = {sc + b.GHb, s3R}; o.p[GRU_HPREV] = {sc + b.DS, sR}; o.p[GRU_HRM] = {sc + b.DS + sR, sR};
+    o.p[GRU_H16] = {sc + b.CP16 + xCP, xCP}; o.p[GRU_RG] = o.p[GRU_UG] = o.p[GRU_NG] = sc + b.dummyR; o.p[GRU_BIH] = w->gru_bih;
+    o.p[GRU_H16B] = {sc + b.DC16 + (size_t)ctZ * 256, xDC}; o.ld[GRU_LD_HPREV] = R; o.ld[LD_OUT] = R; o.n16[N16_OUT] = nCP; o.n16[N16_OUTB] = nDC; o.i[GRU_I_R] = R;
+    add_desc(bld, K_GRU, ctR, 0, range_for(ctR * rt, r_main), H, 0, 0, T, o);
   }
   // prior(cat[d_s, z_{s-1}])
   lin(b.CP16 + xCP, xCP, nCP, p.prior[0], R + Z, c->prior_b[0], ctH, DF_RELU, nullptr, 0, 0, b.P16[0], xH, ctH, 0, rH);
   {  // the next two prior layers: one descriptor (K_LINSEQ)
     const SeqLink lp[2] = {{sc + p.prior[1], c->prior_b[1], nullptr, 0, 0, sc + b.P16[1]}, {sc + p.prior[2], c->prior_b[2], nullptr, 0, 0, sc + b.P16[2]}};
-    add_linseq(bld, ctH, 0, rH, H, true, false, 0, T, sc + b.P16[0], xH, 2, lp, 0, xH, ctH, slope, 0);
+    add_linseq(bld, ctH, 0, rH, H, true, false, 0, T, {sc + b.P16[0], xH}, 2, lp, 0, xH, ctH, slope, 0);
   }
   {  // z_s ~ prior: into the decoder input and into the NEXT step's prior input
-    Desc& d = bld.add(K_HEAD, ctZ, 0, range_for(ctZ * rt, r_main), H, 0, 0, T);
-    bld.ptr(d, 0, sc + b.P16[2], xH); bld.ptr(d, 1, sc + b.P16[2], xH); bld.ptr(d, 2, sc + p.prior_h); bld.ptr(d, 3, c->prior_hb);
-    bld.ptr(d, 4, sc + p.prior_h); bld.ptr(d, 5, c->prior_hb); bld.ptr(d, 6, eps, sZ);
-    for (int k = 7; k <= 12; ++k) bld.ptr(d, k, sc + b.dummyZ);
-    bld.ptr(d, 13, nullptr); bld.ptr(d, 14, sc + b.ZS, sZ); bld.ptr(d, 15, sc + b.DC16, xDC);
-    bld.ptr(d, 16, sc + b.CP16 + 2 * xCP + (size_t)ctR * 256, xCP);
-    d.ld[3] = Z; d.n16[0] = nDC; d.n16[1] = nCP; d.i[0] = Z; d.i[1] = 3; d.f[0] = beta; d.f[1] = 1.f / beta; d.f[2] = sd_eps;
+    Operands o;
+    o.p[HEAD_P16] = o.p[HEAD_Q16] = {sc + b.P16[2], xH}; o.p[HEAD_WP] = o.p[HEAD_WQ] = sc + p.prior_h; o.p[HEAD_BP] = o.p[HEAD_BQ] = c->prior_hb;
+    o.p[HEAD_EPS] = {eps, sZ}; o.p[HEAD_MU_P] = o.p[HEAD_SD_P] = o.p[HEAD_MU_Q] = o.p[HEAD_SD_Q] = o.p[HEAD_RAW_P] = o.p[HEAD_RAW_Q] = sc + b.dummyZ;
+    o.p[HEAD_Z] = {sc + b.ZS, sZ}; o.p[HEAD_Z16] = {sc + b.DC16, xDC}; o.p[HEAD_Z16B] = {sc + b.CP16 + 2 * xCP + (size_t)ctR * 256, xCP}; o.ld[LD_OUT] = Z;
+    o.n16[N16_OUT] = nDC; o.n16[N16_OUTB] = nCP; o.i[HEAD_I_Z] = Z; o.i[HEAD_I_RESIDUAL] = 3; o.f[HEAD_F_BETA] = beta; o.f[HEAD_F_INV_BETA] = 1.f / beta;
+    o.f[HEAD_F_SD_EPS] = sd_eps;
+    add_desc(bld, K_HEAD, ctZ, 0, range_for(ctZ * rt, r_main), H, 0, 0, T, o);
   }
   // decoder(cat[z_s, d_s]); the last layer (S * F columns) on every workgroup
   lin(b.DC16, xDC, nDC, p.dec[0], Z + R, w->dec_b[0], ctH, DF_RELU, nullptr, 0, 0, b.D16[0], xH, ctH, 0, rH);
   lin(b.D16[0], xH, ctH, p.dec[1], H, w->dec_b[1], ctH, DF_RELU, nullptr, 0, 0, b.D16[1], xH, ctH, 0, rH);
   lin(b.D16[1], xH, ctH, p.dec[2], H, w->dec_b[2], S * SD_F / 16, DF_RELU | DF_RM_SC1, sc + b.DEC, sF, S * SD_F, 0, 0, 0, 0, range_for(S * SD_F / 16 * rt, cus));
   {  // per sample: head Linear -> DMoL draw -> x_{s+1}
-    Desc& d = bld.add(K_DMOLS, S / 4, 0, range_for(S / 4 * rt, r_main), 16, 0, 0, T);
-    bld.ptr(d, 0, sc + b.DEC, sF); bld.ptr(d, 1, w->lik_w); bld.ptr(d, 2, w->lik_b); bld.ptr(d, 3, u, (long)B * S * SD_K); bld.ptr(d, 4, v, (long)B * S);
-    bld.ptr(d, 5, x_out, S); bld.ptr(d, 6, sc + b.X16 + xS, xS);
-    d.ld[0] = S * SD_F; d.ld[3] = T * S; d.n16[0] = ctS; d.i[0] = S; d.i[1] = SD_F; d.i[2] = SD_K; d.f[0] = log_eps;
+    Operands o;
+    o.p[DMOLS_DEC] = {sc + b.DEC, sF}; o.p[DMOLS_W] = w->lik_w; o.p[DMOLS_B] = w->lik_b; o.p[DMOLS_U] = {u, (long)B * S * SD_K}; o.p[DMOLS_V] = {v, (long)B * S};
+    o.p[DMOLS_X] = {x_out, S}; o.p[DMOLS_X16] = {sc + b.X16 + xS, xS}; o.ld[DMOLS_LD_DEC] = S * SD_F; o.ld[LD_OUT] = T * S; o.n16[N16_OUT] = ctS; o.i[DMOLS_I_S] = S;
+    o.i[DMOLS_I_F] = SD_F; o.i[DMOLS_I_NMIX] = SD_K; o.f[DMOLS_F_LOG_EPS] = log_eps;
+    add_desc(bld, K_DMOLS, S / 4, 0, range_for(S / 4 * rt, r_main), 16, 0, 0, T, o);
   }
   BLVM_REQUIRE(!bld.overflow, "srnn_generate: persistent program overflow");
   rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);

@@ -368,67 +368,50 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     bld.p.rt_group = RTG;
     bld.p.S = Tp; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = groups ? 8 : 4;
     bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = g;
-    auto lin = [&](const float* A16, long a_step, const float* W, int K, const float* bias, const float* add, long add_step, int ldadd, float* orm,
-                   long rm_step, int ldo, float* o16, long o16_step, int n16, int ct, int wg0, int nwg, int flags) {
-      Desc& d = bld.add(K_LIN, ct, wg0, nwg, K, flags, 0, Tp);
-      bld.ptr(d, 0, A16, a_step); bld.ptr(d, 1, W); bld.ptr(d, 2, bias); bld.ptr(d, 3, add, add_step);
-      bld.ptr(d, 5, orm, rm_step); bld.ptr(d, 6, o16, o16_step);
-      d.ld[1] = ldadd; d.ld[3] = ldo; d.n16[0] = n16; d.f[0] = 0.f;
-    };
     // F1: hidden projection (the first prior layer and the h-half of the first posterior layer open the runs below)
-    auto hproj = [&](int wg0, int nwg) {
-      lin(rs.H16, xR, rs.Whh, R, w->gru_bhh, nullptr, 0, 0, rs.GHb, s3R, 3 * R, nullptr, 0, 0, 3 * ctR, wg0, nwg,
-          DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0));
-    };
+    Operands hp;
+    hp.p[LIN_A] = {rs.H16, xR}; hp.p[LIN_W] = rs.Whh; hp.p[LIN_BIAS] = w->gru_bhh; hp.p[LIN_ORM] = {rs.GHb, s3R}; hp.ld[LD_OUT] = 3 * R;
+    auto hproj = [&](int wg0, int nwg) { add_desc(bld, K_LIN, 3 * ctR, wg0, nwg, R, DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0), 0, Tp, hp); };
     if (!shared) hproj(g, def_n);
-    // a run of consecutive links of one shape as one descriptor: out_i = relu(A_i W_i^T + b_i), A_{i+1} = out_i
-    struct SeqLink { const float* W; const float* bias; float* orm; long rm_step; int ldo; float* o16; };
-    auto linseq = [&](const float* A16, long a_step, int K, int n, const SeqLink* L, int wg0, int nwg, int K0 = 0, const float* add0 = nullptr,
-                      long add0_step = 0, int ldadd0 = 0) {
-      Desc& d = bld.add(K_LINSEQ, ctH, wg0, nwg, K, DF_RELU, 0, Tp);
-      bld.ptr(d, 0, A16, a_step); bld.ptr(d, 17, add0, add0_step);
-      d.i[3] = K0 != K ? K0 : 0; d.i[0] = ldadd0;
-      for (int i = 0; i < n; ++i) {
-        bld.ptr(d, 1 + i, L[i].W); bld.ptr(d, 5 + i, L[i].bias); bld.ptr(d, 9 + i, L[i].orm, L[i].rm_step); bld.ptr(d, 13 + i, L[i].o16, xH);
-        d.ld[i] = L[i].ldo;
-      }
-      d.n16[0] = ctH; d.i[1] = n; d.f[0] = 0.f;
-    };
     // F1 .. F3 of a chain: one visit.  The link in front of a run of same-shape links joins the run's descriptor visit (its own K = R,
     // the posterior's with its x-part addend): one visit less per chain and step (~1 us each, tools/probe_engine_chain.py)
     {
       const SeqLink lp[3] = {{rs.Wp[0], w->prior_b[0], rs.P[0], sH, H, rs.P16[0]}, {rs.Wp[1], w->prior_b[1], rs.P[1], sH, H, rs.P16[1]}, {rs.Wp[2], w->prior_b[2], rs.P[2], sH, H, rs.P16[2]}};
       const SeqLink lq[3] = {{rs.Wq[0], nullptr, rs.Q[0], sH, H, rs.Q16[0]}, {rs.Wq[1], w->post_b[1], rs.Q[1], sH, H, rs.Q16[1]}, {rs.Wq[2], w->post_b[2], rs.Q[2], sH, H, rs.Q16[2]}};
-      linseq(rs.H16, xR, H, 3, lp, 0, half, R);
-      linseq(rs.H16, xR, H, 3, lq, half, half, R, rs.XQ, sH, H);
+      add_linseq(bld, ctH, 0, half, H, true, false, 0, Tp, {rs.H16, xR}, 3, lp, 0, xH, ctH, 0.f, 0, R);
+      add_linseq(bld, ctH, half, half, H, true, false, 0, Tp, {rs.H16, xR}, 3, lq, 0, xH, ctH, 0.f, 0, R, {rs.XQ, sH}, H);
     }
     if (shared) hproj(half, half);
     {  // F4: heads + sample
-      Desc& d = bld.add(K_HEAD, ctZ, 0, range_for(ctZ * tl, shared ? half : g), H, 0, 0, Tp);
-      bld.ptr(d, 0, rs.P16[2], xH); bld.ptr(d, 1, rs.Q16[2], xH); bld.ptr(d, 2, rs.Wph); bld.ptr(d, 3, w->prior_hb); bld.ptr(d, 4, rs.Wqh);
-      bld.ptr(d, 5, w->post_hb); bld.ptr(d, 6, eps, sZ); bld.ptr(d, 7, mu_p, sZ); bld.ptr(d, 8, sd_p, sZ); bld.ptr(d, 9, mu_q, sZ);
-      bld.ptr(d, 10, sd_q, sZ); bld.ptr(d, 11, rs.RAWP, sZ); bld.ptr(d, 12, rs.RAWQ, sZ); bld.ptr(d, 13, nullptr);
-      bld.ptr(d, 14, z, sZ); bld.ptr(d, 15, rs.Z16, xZ);
-      d.ld[3] = Z; d.n16[0] = ctZ; d.i[0] = Z; d.i[1] = residual_posterior; d.f[0] = beta; d.f[1] = 1.f / beta; d.f[2] = sd_eps;
+      Operands o;
+      o.p[HEAD_P16] = {rs.P16[2], xH}; o.p[HEAD_Q16] = {rs.Q16[2], xH}; o.p[HEAD_WP] = rs.Wph; o.p[HEAD_BP] = w->prior_hb; o.p[HEAD_WQ] = rs.Wqh;
+      o.p[HEAD_BQ] = w->post_hb; o.p[HEAD_EPS] = {eps, sZ}; o.p[HEAD_MU_P] = {mu_p, sZ}; o.p[HEAD_SD_P] = {sd_p, sZ}; o.p[HEAD_MU_Q] = {mu_q, sZ};
+      o.p[HEAD_SD_Q] = {sd_q, sZ}; o.p[HEAD_RAW_P] = {rs.RAWP, sZ}; o.p[HEAD_RAW_Q] = {rs.RAWQ, sZ}; o.p[HEAD_Z] = {z, sZ}; o.p[HEAD_Z16] = {rs.Z16, xZ};
+      o.ld[LD_OUT] = Z; o.n16[N16_OUT] = ctZ; o.i[HEAD_I_Z] = Z; o.i[HEAD_I_RESIDUAL] = residual_posterior; o.f[HEAD_F_BETA] = beta; o.f[HEAD_F_INV_BETA] = 1.f / beta;
+      o.f[HEAD_F_SD_EPS] = sd_eps;
+      add_desc(bld, K_HEAD, ctZ, 0, range_for(ctZ * tl, shared ? half : g), H, 0, 0, Tp, o);
     }
     // F5..F8: phi_z MLP (the last layer writes phi into decin row t)
     const int first_seq = Z == H ? 0 : 1;  // (the first layer's K is Z: part of the run only when Z == H)
-    for (int l = 0; l < first_seq; ++l) {
-      const float* A = l == 0 ? rs.Z16 : rs.FZ16[l - 1];
-      lin(A, l == 0 ? xZ : xH, rs.Wf[l], l == 0 ? Z : H, w->phi_b[l], nullptr, 0, 0, l == 3 ? decin : rs.FZ[l], l == 3 ? sD : sH, l == 3 ? ldd : H,
-          l == 3 ? rs.PHI16 : rs.FZ16[l], xH, ctH, ctH, 0, range_for(ctH * tl, shared ? half : g), DF_RELU);
+    if (first_seq) {
+      Operands o;
+      o.p[LIN_A] = {rs.Z16, xZ}; o.p[LIN_W] = rs.Wf[0]; o.p[LIN_BIAS] = w->phi_b[0]; o.p[LIN_ORM] = {rs.FZ[0], sH}; o.ld[LD_OUT] = H; o.p[LIN_O16] = {rs.FZ16[0], xH};
+      o.n16[N16_OUT] = ctH;
+      add_desc(bld, K_LIN, ctH, 0, range_for(ctH * tl, shared ? half : g), Z, DF_RELU, 0, Tp, o);
     }
-    if (first_seq < 4) {
+    {
       SeqLink lf[4];
       for (int l = first_seq; l < 4; ++l)
         lf[l - first_seq] = SeqLink{rs.Wf[l], w->phi_b[l], l == 3 ? decin : rs.FZ[l], l == 3 ? sD : sH, l == 3 ? ldd : H, l == 3 ? rs.PHI16 : rs.FZ16[l]};
-      linseq(first_seq == 0 ? rs.Z16 : rs.FZ16[first_seq - 1], first_seq == 0 ? xZ : xH, H, 4 - first_seq, lf, 0, range_for(ctH * tl, shared ? half : g));
+      add_linseq(bld, ctH, 0, range_for(ctH * tl, shared ? half : g), H, true, false, 0, Tp, first_seq == 0 ? Ptr(rs.Z16, xZ) : Ptr(rs.FZ16[0], xH), 4 - first_seq,
+                 lf, 0, xH, ctH, 0.f, 0);
     }
     {  // F9: GRU
-      Desc& d = bld.add(K_GRU, ctR, 0, range_for(ctR * tl, g), H, 0, 0, Tp);
-      bld.ptr(d, 0, rs.PHI16, xH); bld.ptr(d, 1, rs.Wih); bld.ptr(d, 2, rs.XG, s3R); bld.ptr(d, 3, rs.GHb, s3R); bld.ptr(d, 4, decin + H, sD);
-      bld.ptr(d, 5, decin + sD + H, sD); bld.ptr(d, 6, rs.H16 + xR, xR); bld.ptr(d, 7, rs.RG, sR); bld.ptr(d, 8, rs.UG, sR); bld.ptr(d, 9, rs.NG, sR);
-      d.ld[0] = ldd; d.ld[3] = ldd; d.n16[0] = ctR; d.i[0] = R;
+      Operands o;
+      o.p[GRU_X16] = {rs.PHI16, xH}; o.p[GRU_WIH] = rs.Wih; o.p[GRU_XG] = {rs.XG, s3R}; o.p[GRU_GH] = {rs.GHb, s3R}; o.p[GRU_HPREV] = {decin + H, sD};
+      o.p[GRU_HRM] = {decin + sD + H, sD}; o.p[GRU_H16] = {rs.H16 + xR, xR}; o.p[GRU_RG] = {rs.RG, sR}; o.p[GRU_UG] = {rs.UG, sR}; o.p[GRU_NG] = {rs.NG, sR};
+      o.ld[GRU_LD_HPREV] = ldd; o.ld[LD_OUT] = ldd; o.n16[N16_OUT] = ctR; o.i[GRU_I_R] = R;
+      add_desc(bld, K_GRU, ctR, 0, range_for(ctR * tl, g), H, 0, 0, Tp, o);
     }
     BLVM_REQUIRE(!bld.overflow, "vrnn_fwd: persistent program overflow");
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
@@ -629,24 +612,17 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     bld.p.rt_group = RTG;
     bld.p.S = T + 1; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = groups ? 8 : 2;
     bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = g;
-    auto last = [&](const float* base, long step) { return base ? base + (long)(T - 1) * step : nullptr; };  // slab of t = T'-1
+    auto last = [&](const float* base, long step) { return rev(base, step, T - 1); };  // slab of t = T'-1, walked backwards
     {  // Ba: complete the gradient wrt h_t, GRU gate derivatives of step t (s = T': only the gradient wrt the initial state)
-      Desc& d = bld.add(K_GRUB, ctR, 0, range_for(ctR * tl, g), H, 0, 0, T + 1);
-      bld.ptr(d, 0, ws.DP16[0] + (long)T * xH, -xH); bld.ptr(d, 1, ws.DQ16[0] + (long)T * xH, -xH); bld.ptr(d, 2, ws.pT[0]); bld.ptr(d, 3, ws.qT[0]);
-      bld.ptr(d, 4, ws.GB + (long)T * sR, -sR);
-      bld.ptr(d, 5, last(rs.RG, sR), -sR); bld.ptr(d, 6, last(rs.UG, sR), -sR); bld.ptr(d, 7, last(rs.NG, sR), -sR); bld.ptr(d, 8, last(rs.GHb, s3R), -s3R);
-      bld.ptr(d, 9, last(decin, sD) + H, -sD); bld.ptr(d, 10, last(d_decin, sD) + H, -sD);
-      bld.ptr(d, 11, last(ws.DGI, s3R), -s3R); bld.ptr(d, 12, last(ws.DGI16, x3R), -x3R); bld.ptr(d, 13, last(ws.DGH, s3R), -s3R);
-      bld.ptr(d, 14, last(ws.DGH16, x3R), -x3R); bld.ptr(d, 15, last(ws.GA, sR), -sR); bld.ptr(d, 16, d_h0 ? d_h0 : ws.G);
-      d.ld[0] = ldd; d.ld[3] = 3 * R; d.n16[0] = 3 * ctR; d.i[0] = R; d.i[1] = 1; d.i[2] = T; d.i[3] = 1;
+      Operands o;
+      o.p[GRUB_D0_16] = rev(ws.DP16[0], xH, T); o.p[GRUB_D1_16] = rev(ws.DQ16[0], xH, T); o.p[GRUB_W0] = ws.pT[0]; o.p[GRUB_W1] = ws.qT[0];
+      o.p[GRUB_G_IN] = rev(ws.GB, sR, T); o.p[GRUB_RG] = last(rs.RG, sR); o.p[GRUB_UG] = last(rs.UG, sR); o.p[GRUB_NG] = last(rs.NG, sR);
+      o.p[GRUB_GH] = last(rs.GHb, s3R); o.p[GRUB_HPREV] = last(decin + H, sD); o.p[GRUB_DD] = last(d_decin + H, sD); o.p[GRUB_DGI] = last(ws.DGI, s3R);
+      o.p[GRUB_DGI16] = last(ws.DGI16, x3R); o.p[GRUB_DGH] = last(ws.DGH, s3R); o.p[GRUB_DGH16] = last(ws.DGH16, x3R); o.p[GRUB_GA] = last(ws.GA, sR);
+      o.p[GRUB_G_OUT] = d_h0 ? d_h0 : ws.G; o.ld[GRUB_LD_H] = ldd; o.ld[LD_OUT] = 3 * R; o.n16[N16_OUT] = 3 * ctR; o.i[GRUB_I_R] = R; o.i[GRUB_I_GEMM_FROM] = 1;
+      o.i[GRUB_I_GATES_TO] = T; o.i[GRUB_I_GIN_FROM] = 1;
+      add_desc(bld, K_GRUB, ctR, 0, range_for(ctR * tl, g), H, 0, 0, T + 1, o);
     }
-    auto lin = [&](const float* A16, long a_x, const float* W, int K, const float* add, long add_step, int ldadd, const float* gate, long gate_step,
-                   int ldgate, float* orm, long rm_step, int ldo, float* o16, long o16_x, int n16, int ct, int wg0, int nwg, int flags) {
-      Desc& d = bld.add(K_LIN, ct, wg0, nwg, K, flags, 0, T);
-      bld.ptr(d, 0, last(A16, a_x), -a_x); bld.ptr(d, 1, W); bld.ptr(d, 3, last(add, add_step), -add_step); bld.ptr(d, 4, last(gate, gate_step), -gate_step);
-      bld.ptr(d, 5, last(orm, rm_step), -rm_step); bld.ptr(d, 6, last(o16, o16_x), -o16_x);
-      d.ld[1] = ldadd; d.ld[2] = ldgate; d.ld[3] = ldo; d.n16[0] = n16; d.f[0] = 0.f;
-    };
     // Bb: dphi through the GRU input projection (+ the decoder's gradient, through phi's ReLU) | GB[t] = GA[t] + DGH[t] W_hh
     // The K = 3R product is the fattest link of the step (96 KB of operands per tile): when a third range of workgroups is free it
     // runs as three K = R links side by side (the r | u | n thirds of DGI and of W_ih^T), each writing a full slab of partial sums
@@ -654,65 +630,55 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     // loads them.
     const int spare = cus - g - def_n;
     const bool split3 = !shared && spare >= 8 && half >= 8 && pchain_split3();
+    Operands o;  // (ld[LIN_LD_A], i[LIN_I_W_WIDTH] of a part: widths of the slab / of the packed rows the K-range is taken from)
+    o.p[LIN_GATE] = last(decin, sD); o.ld[LIN_LD_ADD] = ldd; o.ld[LIN_LD_GATE] = ldd; o.ld[LD_OUT] = H; o.n16[N16_OUT] = ctH;
     if (split3) {
       const size_t wthird = (size_t)ctR * 256 / (bld.p.ot != OP_F32 ? 2 : 1);  // the packed weight's k-chunks [ctR * part, ...) (16-bit packs: half the floats)
       float* const orm[3] = {ws.DPHI[3], ws.DPHI3b, ws.DPHI3c};
       float* const o16[3] = {ws.DPHI16[3], ws.DPHI16b, ws.DPHI16c};
       const int wg0s[3] = {0, half, g + def_n}, nwgs[3] = {range_for(ctH * tl, half), range_for(ctH * tl, half), range_for(ctH * tl, spare)};
+      o.ld[LIN_LD_A] = 3 * R; o.i[LIN_I_W_WIDTH] = 3 * R;
       for (int part = 0; part < 3; ++part) {
-        lin(ws.DGI16 + (size_t)part * ctR * 256, x3R, ws.wihT + part * wthird, R, part == 0 ? d_decin : nullptr, sD, ldd, decin, sD, ldd, orm[part], sH, H, o16[part], xH,
-            ctH, ctH, wg0s[part], nwgs[part], 0);
-        Desc& d = bld.p.d[bld.p.ndesc - 1];
-        d.ld[0] = 3 * R; d.i[0] = 3 * R;  // widths of the slab / of the packed rows the K-range is taken from
+        o.p[LIN_A] = last(ws.DGI16 + (size_t)part * ctR * 256, x3R); o.p[LIN_W] = ws.wihT + part * wthird; o.p[LIN_ADD] = part == 0 ? last(d_decin, sD) : Ptr();
+        o.p[LIN_ORM] = last(orm[part], sH); o.p[LIN_O16] = last(o16[part], xH);
+        add_desc(bld, K_LIN, ctH, wg0s[part], nwgs[part], R, 0, 0, T, o);
       }
     } else {
-      lin(ws.DGI16, x3R, ws.wihT, 3 * R, d_decin, sD, ldd, decin, sD, ldd, ws.DPHI[3], sH, H, ws.DPHI16[3], xH, ctH, ctH, 0, range_for(ctH * tl, wide), 0);
+      o.p[LIN_A] = last(ws.DGI16, x3R); o.p[LIN_W] = ws.wihT; o.p[LIN_ADD] = last(d_decin, sD); o.p[LIN_ORM] = last(ws.DPHI[3], sH);
+      o.p[LIN_O16] = last(ws.DPHI16[3], xH);
+      add_desc(bld, K_LIN, ctH, 0, range_for(ctH * tl, wide), 3 * R, 0, 0, T, o);
     }
-    lin(ws.DGH16, x3R, ws.whhT, 3 * R, ws.GA, sR, R, nullptr, 0, 0, ws.GB, sR, R, nullptr, 0, 0, ctR, shared ? half : g, shared ? half : def_n,
-        DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0));
-    // B3..B5: back through phi_z layers 3, 2, 1
-    // a run of consecutive backward links of one shape as one descriptor (K_LINSEQ): D_{i+1} = (D_i W_i) masked by the saved activation
-    struct SeqLinkB { const float* WT; const float* gate; float* orm; float* o16; };
-    auto linseq_b = [&](const float* A16, int n, const SeqLinkB* L, int wg0, int nwg, int flags, int K0 = 0, long a_x = 0) -> Desc& {
-      Desc& d = bld.add(K_LINSEQ, ctH, wg0, nwg, H, flags | DF_SEQ_GATE, 0, T);
-      if (a_x == 0) a_x = xH;
-      bld.ptr(d, 0, last(A16, a_x), -a_x);
-      d.i[3] = (K0 != 0 && K0 != H) ? K0 : 0;  // (the first link's own K: the link in front of the run, in the run's visit)
-      for (int i = 0; i < n; ++i) {
-        bld.ptr(d, 1 + i, L[i].WT); bld.ptr(d, 5 + i, last(L[i].gate, sH), -sH); bld.ptr(d, 9 + i, last(L[i].orm, sH), -sH);
-        bld.ptr(d, 13 + i, last(L[i].o16, xH), -xH);
-        d.ld[i] = H;
-      }
-      d.n16[0] = ctH; d.i[1] = n; d.i[2] = H; d.f[0] = 0.f;
-      return d;
-    };
-    const SeqLinkB lf[3] = {{ws.fT[3], rs.FZ[2], ws.DPHI[2], ws.DPHI16[2]}, {ws.fT[2], rs.FZ[1], ws.DPHI[1], ws.DPHI16[1]}, {ws.fT[1], rs.FZ[0], ws.DPHI[0], ws.DPHI16[0]}};
+    Operands gb;
+    gb.p[LIN_A] = last(ws.DGH16, x3R); gb.p[LIN_W] = ws.whhT; gb.p[LIN_ADD] = last(ws.GA, sR); gb.ld[LIN_LD_ADD] = R; gb.p[LIN_ORM] = last(ws.GB, sR); gb.ld[LD_OUT] = R;
+    add_desc(bld, K_LIN, ctR, shared ? half : g, shared ? half : def_n, 3 * R, DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0), 0, T, gb);
+    // B3..B5: back through phi_z layers 3, 2, 1: runs of backward links (K_LINSEQ), D_{i+1} = (D_i W_i) masked by the saved activation
+    auto blink = [&](const float* W, const float* gate, float* orm, float* o16) { return rev_link(W, gate, orm, o16, T - 1, sH, H, xH); };
+    const SeqLink lf[3] = {blink(ws.fT[3], rs.FZ[2], ws.DPHI[2], ws.DPHI16[2]), blink(ws.fT[2], rs.FZ[1], ws.DPHI[1], ws.DPHI16[1]),
+                           blink(ws.fT[1], rs.FZ[0], ws.DPHI[0], ws.DPHI16[0])};
     if (split3) {  // the link that adds the three partial-sum slabs up is a K_LIN of its own (a run's links are plain), the other two a run
-      lin(ws.DPHI16[3], xH, ws.fT[3], H, nullptr, 0, 0, rs.FZ[2], sH, H, ws.DPHI[2], sH, H, ws.DPHI16[2], xH, ctH, ctH, 0, range_for(ctH * tl, wide), DF_A_SUM3);
-      Desc& d = bld.p.d[bld.p.ndesc - 1];
-      bld.ptr(d, 8, ws.DPHI16b + (long)(T - 1) * xH, -xH); bld.ptr(d, 9, ws.DPHI16c + (long)(T - 1) * xH, -xH);
-      linseq_b(ws.DPHI16[2], 2, lf + 1, 0, range_for(ctH * tl, wide), 0);
-    } else {
-      linseq_b(ws.DPHI16[3], 3, lf, 0, range_for(ctH * tl, wide), 0);
+      Operands o3;
+      o3.p[LIN_A] = last(ws.DPHI16[3], xH); o3.p[LIN_W] = ws.fT[3]; o3.p[LIN_GATE] = last(rs.FZ[2], sH); o3.ld[LIN_LD_GATE] = H; o3.p[LIN_ORM] = last(ws.DPHI[2], sH);
+      o3.ld[LD_OUT] = H; o3.p[LIN_O16] = last(ws.DPHI16[2], xH); o3.n16[N16_OUT] = ctH; o3.p[LIN_A2] = last(ws.DPHI16b, xH); o3.p[LIN_A3] = last(ws.DPHI16c, xH);
+      add_desc(bld, K_LIN, ctH, 0, range_for(ctH * tl, wide), H, DF_A_SUM3, 0, T, o3);
     }
+    add_linseq(bld, ctH, 0, range_for(ctH * tl, wide), H, false, true, 0, T, last(ws.DPHI16[split3 ? 2 : 3], xH), split3 ? 2 : 3, lf + (split3 ? 1 : 0), -sH,
+               -xH, ctH, 0.f, H);
     {  // B6: dz and the heads
-      Desc& d = bld.add(K_DZ, ctZ, 0, range_for(ctZ * tl, wide), H, 0, 0, T);
-      bld.ptr(d, 0, last(ws.DPHI16[0], xH), -xH); bld.ptr(d, 1, ws.fT[0]); bld.ptr(d, 2, nullptr); bld.ptr(d, 3, nullptr); bld.ptr(d, 4, nullptr);
-      bld.ptr(d, 5, last(mu_q, sZ), -sZ); bld.ptr(d, 6, last(sd_q, sZ), -sZ); bld.ptr(d, 7, last(mu_p, sZ), -sZ); bld.ptr(d, 8, last(sd_p, sZ), -sZ);
-      bld.ptr(d, 9, last(eps, sZ), -sZ); bld.ptr(d, 10, last(rs.RAWQ, sZ), -sZ); bld.ptr(d, 11, last(rs.RAWP, sZ), -sZ); bld.ptr(d, 12, nullptr);
-      bld.ptr(d, 13, x_sl); bld.ptr(d, 14, c_raw); bld.ptr(d, 15, c_fn);
-      bld.ptr(d, 16, last(ws.DQH, s2Z), -s2Z); bld.ptr(d, 17, last(ws.DQH16, x2Z), -x2Z); bld.ptr(d, 18, last(ws.DPH, s2Z), -s2Z);
-      bld.ptr(d, 19, last(ws.DPH16, x2Z), -x2Z);
-      d.ld[3] = 2 * Z; d.n16[0] = 2 * ctZ; d.i[0] = Z; d.i[1] = residual_posterior; d.i[2] = stride; d.i[3] = T - 1;
-      d.f[0] = fn_floor; d.f[1] = beta; d.f[2] = sd_eps;
+      Operands z;
+      z.p[DZ_D16] = last(ws.DPHI16[0], xH); z.p[DZ_WT] = ws.fT[0]; z.p[DZ_MU_Q] = last(mu_q, sZ); z.p[DZ_SD_Q] = last(sd_q, sZ); z.p[DZ_MU_P] = last(mu_p, sZ);
+      z.p[DZ_SD_P] = last(sd_p, sZ); z.p[DZ_EPS] = last(eps, sZ); z.p[DZ_RAW_Q] = last(rs.RAWQ, sZ); z.p[DZ_RAW_P] = last(rs.RAWP, sZ); z.p[DZ_X_SL] = x_sl;
+      z.p[DZ_C_RAW] = c_raw; z.p[DZ_C_FN] = c_fn; z.p[DZ_DQH] = last(ws.DQH, s2Z); z.p[DZ_DQH16] = last(ws.DQH16, x2Z); z.p[DZ_DPH] = last(ws.DPH, s2Z);
+      z.p[DZ_DPH16] = last(ws.DPH16, x2Z); z.ld[LD_OUT] = 2 * Z; z.n16[N16_OUT] = 2 * ctZ; z.i[DZ_I_Z] = Z; z.i[DZ_I_RESIDUAL] = residual_posterior;
+      z.i[DZ_I_STRIDE] = stride; z.i[DZ_I_T0] = T - 1; z.f[DZ_F_FN_FLOOR] = fn_floor; z.f[DZ_F_BETA] = beta; z.f[DZ_F_SD_EPS] = sd_eps;
+      add_desc(bld, K_DZ, ctZ, 0, range_for(ctZ * tl, wide), H, 0, 0, T, z);
     }
     // B7: heads -> last hidden layers;  B8, B9: hidden layers 2, 1  (prior | posterior).  B7 .. B9 of a chain: one visit (the heads'
     // gradient link, K = 2Z, joins the run's descriptor visit)
     {
-      const SeqLinkB lp[3] = {{ws.phT, rs.P[2], ws.DP[2], ws.DP16[2]}, {ws.pT[2], rs.P[1], ws.DP[1], ws.DP16[1]}, {ws.pT[1], rs.P[0], ws.DP[0], ws.DP16[0]}};
-      const SeqLinkB lq[3] = {{ws.qhT, rs.Q[2], ws.DQ[2], ws.DQ16[2]}, {ws.qT[2], rs.Q[1], ws.DQ[1], ws.DQ16[1]}, {ws.qT[1], rs.Q[0], ws.DQ[0], ws.DQ16[0]}};
-      linseq_b(ws.DPH16, 3, lp, 0, half, 0, 2 * Z, x2Z);
-      linseq_b(ws.DQH16, 3, lq, half, half, 0, 2 * Z, x2Z);
+      const SeqLink lp[3] = {blink(ws.phT, rs.P[2], ws.DP[2], ws.DP16[2]), blink(ws.pT[2], rs.P[1], ws.DP[1], ws.DP16[1]), blink(ws.pT[1], rs.P[0], ws.DP[0], ws.DP16[0])};
+      const SeqLink lq[3] = {blink(ws.qhT, rs.Q[2], ws.DQ[2], ws.DQ16[2]), blink(ws.qT[2], rs.Q[1], ws.DQ[1], ws.DQ16[1]), blink(ws.qT[1], rs.Q[0], ws.DQ[0], ws.DQ16[0])};
+      add_linseq(bld, ctH, 0, half, H, false, true, 0, T, last(ws.DPH16, x2Z), 3, lp, -sH, -xH, ctH, 0.f, H, 2 * Z);
+      add_linseq(bld, ctH, half, half, H, false, true, 0, T, last(ws.DQH16, x2Z), 3, lq, -sH, -xH, ctH, 0.f, H, 2 * Z);
     }
     BLVM_REQUIRE(!bld.overflow, "vrnn_bwd: persistent program overflow");
     rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);

@@ -587,11 +587,10 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
   bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = r_main;
   auto lin = [&](size_t A16, long a_step, size_t W, int K, const float* bias, int ct, int flags, float sl, float* orm, long rm_step, int ldo, size_t o16,
                  long o16_step, int n16, size_t o16b, long o16b_step, int n16b, int wg0, int nwg) -> Desc& {
-    Desc& d = bld.add(K_LIN, ct, wg0, nwg, K, flags, 0, T);
-    bld.ptr(d, 0, sc + A16, a_step); bld.ptr(d, 1, sc + W); bld.ptr(d, 2, bias); bld.ptr(d, 5, orm, rm_step);
-    bld.ptr(d, 6, o16 ? sc + o16 : nullptr, o16_step); bld.ptr(d, 7, o16b ? sc + o16b : nullptr, o16b_step);
-    d.ld[3] = ldo; d.n16[0] = n16; d.n16[1] = n16b; d.f[0] = sl;
-    return d;
+    Operands o;
+    o.p[LIN_A] = {sc + A16, a_step}; o.p[LIN_W] = sc + W; o.p[LIN_BIAS] = bias; o.p[LIN_ORM] = {orm, rm_step}; o.p[LIN_O16] = {o16 ? sc + o16 : nullptr, o16_step};
+    o.p[LIN_O16B] = {o16b ? sc + o16b : nullptr, o16b_step}; o.ld[LD_OUT] = ldo; o.n16[N16_OUT] = n16; o.n16[N16_OUTB] = n16b; o.f[LIN_F_SLOPE] = sl;
+    return add_desc(bld, K_LIN, ct, wg0, nwg, K, flags, 0, T, o);
   };
   const int rH = range_for(ctH * rt, r_main);
   // encoder(x_t)
@@ -604,15 +603,15 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
       r_main, r_side);
   {  // the next two prior layers: one descriptor (K_LINSEQ)
     const SeqLink lp[2] = {{sc + p.prior[1], c->prior_b[1], nullptr, 0, 0, sc + b.P16[1]}, {sc + p.prior[2], c->prior_b[2], nullptr, 0, 0, sc + b.P16[2]}};
-    add_linseq(bld, ctH, 0, rH, H, true, false, 0, T, sc + b.P16[0], xH, 2, lp, 0, xH, ctH, 0.f, 0);
+    add_linseq(bld, ctH, 0, rH, H, true, false, 0, T, {sc + b.P16[0], xH}, 2, lp, 0, xH, ctH, 0.f, 0);
   }
   {  // z ~ prior (head in generation mode: the posterior operands are the prior's)
-    Desc& d = bld.add(K_HEAD, ctZ, 0, range_for(ctZ * rt, r_main), H, 0, 0, T);
-    bld.ptr(d, 0, sc + b.P16[2], xH); bld.ptr(d, 1, sc + b.P16[2], xH); bld.ptr(d, 2, sc + p.prior_h); bld.ptr(d, 3, c->prior_hb);
-    bld.ptr(d, 4, sc + p.prior_h); bld.ptr(d, 5, c->prior_hb); bld.ptr(d, 6, eps, sZ);
-    for (int k = 7; k <= 12; ++k) bld.ptr(d, k, sc + b.dummyZ);
-    bld.ptr(d, 13, nullptr); bld.ptr(d, 14, sc + b.dummyZ); bld.ptr(d, 15, sc + b.Z16, xZ);
-    d.ld[3] = Z; d.n16[0] = ctZ; d.i[0] = Z; d.i[1] = 3; d.f[0] = beta; d.f[1] = 1.f / beta; d.f[2] = sd_eps;
+    Operands o;
+    o.p[HEAD_P16] = o.p[HEAD_Q16] = {sc + b.P16[2], xH}; o.p[HEAD_WP] = o.p[HEAD_WQ] = sc + p.prior_h; o.p[HEAD_BP] = o.p[HEAD_BQ] = c->prior_hb;
+    o.p[HEAD_EPS] = {eps, sZ}; o.p[HEAD_MU_P] = o.p[HEAD_SD_P] = o.p[HEAD_MU_Q] = o.p[HEAD_SD_Q] = o.p[HEAD_RAW_P] = o.p[HEAD_RAW_Q] = o.p[HEAD_Z] = sc + b.dummyZ;
+    o.p[HEAD_Z16] = {sc + b.Z16, xZ}; o.ld[LD_OUT] = Z; o.n16[N16_OUT] = ctZ; o.i[HEAD_I_Z] = Z; o.i[HEAD_I_RESIDUAL] = 3; o.f[HEAD_F_BETA] = beta;
+    o.f[HEAD_F_INV_BETA] = 1.f / beta; o.f[HEAD_F_SD_EPS] = sd_eps;
+    add_desc(bld, K_HEAD, ctZ, 0, range_for(ctZ * rt, r_main), H, 0, 0, T, o);
   }
   // phi_z(z): the last layer feeds the GRU input cat[enc, phi] and the decoder input cat[phi, h_new]
   {  // layers 1..3 as one descriptor (K_LINSEQ)
@@ -620,16 +619,17 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
     if (f0) lin(b.Z16, xZ, p.phi[0], Z, c->phi_b[0], ctH, DF_RELU, 0.f, nullptr, 0, 0, b.F16[0], xH, ctH, 0, 0, 0, 0, rH);
     SeqLink lf[3];
     for (int l = f0; l < 3; ++l) lf[l - f0] = SeqLink{sc + p.phi[l], c->phi_b[l], nullptr, 0, 0, sc + b.F16[l]};
-    add_linseq(bld, ctH, 0, rH, H, true, false, 0, T, f0 ? sc + b.F16[0] : sc + b.Z16, f0 ? xH : xZ, 3 - f0, lf, 0, xH, ctH, 0.f, 0);
+    add_linseq(bld, ctH, 0, rH, H, true, false, 0, T, f0 ? Ptr(sc + b.F16[0], xH) : Ptr(sc + b.Z16, xZ), 3 - f0, lf, 0, xH, ctH, 0.f, 0);
   }
   lin(b.F16[2], xH, p.phi[3], H, c->phi_b[3], ctH, DF_RELU, 0.f, nullptr, 0, 0, b.CAT16 + (size_t)(X / 16) * 256, xC, (X + H) / 16, b.DC16, xD,
       (H + R) / 16, 0, rH);
   {  // GRU(cat[enc, phi], h_{t-1}) -> h_t: row-major (polled words of the next step), T16 for the next step, T16 into cat[phi, h_t]
-    Desc& d = bld.add(K_GRU, ctR, 0, range_for(ctR * rt, r_main), X + H, 0, 0, T);
-    bld.ptr(d, 0, sc + b.CAT16, xC); bld.ptr(d, 1, sc + p.wih); bld.ptr(d, 2, nullptr); bld.ptr(d, 3, sc + b.GHb, s3R); bld.ptr(d, 4, sc + b.HS, sR);
-    bld.ptr(d, 5, sc + b.HS + sR, sR); bld.ptr(d, 6, sc + b.H16 + xR, xR); bld.ptr(d, 7, sc + b.dummyR); bld.ptr(d, 8, sc + b.dummyR);
-    bld.ptr(d, 9, sc + b.dummyR); bld.ptr(d, 10, c->gru_bih); bld.ptr(d, 11, sc + b.DC16 + (size_t)(H / 16) * 256, xD);
-    d.ld[0] = R; d.ld[3] = R; d.n16[0] = ctR; d.n16[1] = (H + R) / 16; d.i[0] = R;
+    Operands o;
+    o.p[GRU_X16] = {sc + b.CAT16, xC}; o.p[GRU_WIH] = sc + p.wih; o.p[GRU_GH] = {sc + b.GHb, s3R}; o.p[GRU_HPREV] = {sc + b.HS, sR}; o.p[GRU_HRM] = {sc + b.HS + sR, sR};
+    o.p[GRU_H16] = {sc + b.H16 + xR, xR}; o.p[GRU_RG] = o.p[GRU_UG] = o.p[GRU_NG] = sc + b.dummyR; o.p[GRU_BIH] = c->gru_bih;
+    o.p[GRU_H16B] = {sc + b.DC16 + (size_t)(H / 16) * 256, xD}; o.ld[GRU_LD_HPREV] = R; o.ld[LD_OUT] = R; o.n16[N16_OUT] = ctR; o.n16[N16_OUTB] = (H + R) / 16;
+    o.i[GRU_I_R] = R;
+    add_desc(bld, K_GRU, ctR, 0, range_for(ctR * rt, r_main), X + H, 0, 0, T, o);
   }
   // decoder(cat[phi, h_t]); the last layer (S * F columns) on every workgroup
   lin(b.DC16, xD, p.dec[0], H + R, w->dec_b[0], ctH, DF_RELU, slope, nullptr, 0, 0, b.D16[0], xH, ctH, 0, 0, 0, 0, rH);
@@ -637,10 +637,11 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
   lin(b.D16[1], xH, p.dec[2], H, w->dec_b[2], S * VD_F / 16, DF_RELU | DF_RM_SC1, slope, sc + b.DEC, sF, S * VD_F, 0, 0, 0, 0, 0, 0, 0,
       range_for(S * VD_F / 16 * rt, cus));
   {  // per sample: head Linear -> DMoL draw -> x_{t+1}
-    Desc& d = bld.add(K_DMOLS, S / 4, 0, range_for(S / 4 * rt, r_main), 16, 0, 0, T);
-    bld.ptr(d, 0, sc + b.DEC, sF); bld.ptr(d, 1, w->lik_w); bld.ptr(d, 2, w->lik_b); bld.ptr(d, 3, u, (long)B * S * VD_K); bld.ptr(d, 4, v, (long)B * S);
-    bld.ptr(d, 5, x_out, S); bld.ptr(d, 6, sc + b.X16 + xS, xS);
-    d.ld[0] = S * VD_F; d.ld[3] = T * S; d.n16[0] = ctS; d.i[0] = S; d.i[1] = VD_F; d.i[2] = VD_K; d.f[0] = log_eps;
+    Operands o;
+    o.p[DMOLS_DEC] = {sc + b.DEC, sF}; o.p[DMOLS_W] = w->lik_w; o.p[DMOLS_B] = w->lik_b; o.p[DMOLS_U] = {u, (long)B * S * VD_K}; o.p[DMOLS_V] = {v, (long)B * S};
+    o.p[DMOLS_X] = {x_out, S}; o.p[DMOLS_X16] = {sc + b.X16 + xS, xS}; o.ld[DMOLS_LD_DEC] = S * VD_F; o.ld[LD_OUT] = T * S; o.n16[N16_OUT] = ctS; o.i[DMOLS_I_S] = S;
+    o.i[DMOLS_I_F] = VD_F; o.i[DMOLS_I_NMIX] = VD_K; o.f[DMOLS_F_LOG_EPS] = log_eps;
+    add_desc(bld, K_DMOLS, S / 4, 0, range_for(S / 4 * rt, r_main), 16, 0, 0, T, o);
   }
   BLVM_REQUIRE(!bld.overflow, "vrnn_generate: persistent program overflow");
   rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);

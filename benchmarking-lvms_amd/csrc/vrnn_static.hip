@@ -83,8 +83,7 @@ struct LinArgs {
   int ld0, ld1, ld2, ld3, n16, n16b, w_width;
   float slope;
 };
-// K_LINSEQ: a run of N links, link 0 of K0 and the others of K (pointer k of the descriptor: a0 = 0, add0 = 17, W 1+i, aux 5+i,
-// orm 9+i, o16 13+i)
+// K_LINSEQ: a run of N links, link 0 of K0 and the others of K
 struct SeqArgs {
   SPtr a0, add0, aux[4], orm[4], o16[4];
   const float* W[4];
@@ -390,11 +389,13 @@ int static_go(Kern kernel, int slot, int grid, size_t lds, const char* what) {
 int static_lin_chain_launch(const Program& p, hipStream_t stream) {
   if (p.ndesc != 1 || p.ot != OP_F32 || p.rt_group != 1 || !int_strides(p)) return 1;
   const Desc& d = p.d[0];
-  if (d.kind != K_LIN || d.flags != DF_RELU || d.f[0] != 0.f || (d.K != 256 && d.K != 512) || d.s_begin != 0 || d.s_end != p.S) return 1;
-  if (d.ld[0] != 0 || d.i[0] != 0 || d.p[3] || d.p[4] || d.p[7] || d.p[8] || d.p[9] || d.n16[1] != 0) return 1;
+  if (d.kind != K_LIN || d.flags != DF_RELU || d.f[LIN_F_SLOPE] != 0.f || (d.K != 256 && d.K != 512) || d.s_begin != 0 || d.s_end != p.S) return 1;
+  if (d.ld[LIN_LD_A] != 0 || d.i[LIN_I_W_WIDTH] != 0 || d.p[LIN_ADD] || d.p[LIN_GATE] || d.p[LIN_O16B] || d.p[LIN_A2] || d.p[LIN_A3] || d.n16[N16_OUTB] != 0)
+    return 1;
   const int rt = (p.B + 15) / 16;
   if (p.xcd ? (((d.ct + 7) / 8) * rt + d.nwg / 8 - 1) / (d.nwg / 8) > kMaxTiles : (d.ct * rt + d.nwg - 1) / d.nwg > kMaxTiles) return 1;
-  LinChainArgs a{sptr(p, d, 0), sptr(p, d, 5), sptr(p, d, 6), d.p[1], d.p[2], d.ld[3], d.n16[0], p.B, p.s_first, p.S, d.wg0, d.nwg, d.ct, p.xcd, p.ctl};
+  LinChainArgs a{sptr(p, d, LIN_A), sptr(p, d, LIN_ORM), sptr(p, d, LIN_O16), d.p[LIN_W], d.p[LIN_BIAS], d.ld[LD_OUT], d.n16[N16_OUT], p.B, p.s_first, p.S,
+                 d.wg0, d.nwg, d.ct, p.xcd, p.ctl};
   const int grid = d.wg0 + d.nwg;
   auto go = [&](auto kernel) -> int {
     const int rc = static_go(kernel, 2, grid, 0, "static_lin_chain");
@@ -422,18 +423,21 @@ bool few_tiles(const Program& p, const Desc& d) {  // at most kMaxTiles tiles of
   return per_wg <= kMaxTiles;
 }
 bool shaped(const Desc& d, int kind, int flags, int K) { return d.kind == kind && d.flags == flags && d.K == K; }
+bool run(const Desc& d, int n, int K0) { return d.i[LINSEQ_I_N] == n && d.i[LINSEQ_I_K0] == K0; }  // a K_LINSEQ of n links, first link's K0
 
 LinArgs lin_args(const Program& p, const Desc& d) {
-  return LinArgs{sp(p, d, 0), sp(p, d, 8), sp(p, d, 9), sp(p, d, 3), sp(p, d, 4), sp(p, d, 5), sp(p, d, 6), sp(p, d, 7), d.p[1], d.p[2],
-                 d.ld[0], d.ld[1], d.ld[2], d.ld[3], d.n16[0], d.n16[1], d.i[0], d.f[0]};
+  return LinArgs{sp(p, d, LIN_A), sp(p, d, LIN_A2), sp(p, d, LIN_A3), sp(p, d, LIN_ADD), sp(p, d, LIN_GATE), sp(p, d, LIN_ORM), sp(p, d, LIN_O16),
+                 sp(p, d, LIN_O16B), d.p[LIN_W], d.p[LIN_BIAS], d.ld[LIN_LD_A], d.ld[LIN_LD_ADD], d.ld[LIN_LD_GATE], d.ld[LD_OUT], d.n16[N16_OUT], d.n16[N16_OUTB],
+                 d.i[LIN_I_W_WIDTH], d.f[LIN_F_SLOPE]};
 }
 SeqArgs seq_args(const Program& p, const Desc& d) {
   SeqArgs q{};
-  q.a0 = sp(p, d, 0); q.add0 = sp(p, d, 17);
-  for (int i = 0; i < d.i[1]; ++i) {
-    q.W[i] = d.p[1 + i]; q.aux[i] = sp(p, d, 5 + i); q.orm[i] = sp(p, d, 9 + i); q.o16[i] = sp(p, d, 13 + i); q.ld[i] = d.ld[i];
+  q.a0 = sp(p, d, LINSEQ_A0); q.add0 = sp(p, d, LINSEQ_ADD0);
+  for (int i = 0; i < d.i[LINSEQ_I_N]; ++i) {
+    q.W[i] = d.p[LINSEQ_W + i]; q.aux[i] = sp(p, d, LINSEQ_AUX + i); q.orm[i] = sp(p, d, LINSEQ_ORM + i); q.o16[i] = sp(p, d, LINSEQ_O16 + i);
+    q.ld[i] = d.ld[LINSEQ_LD_ORM + i];
   }
-  q.ldadd0 = d.i[0]; q.ldgate = d.i[2]; q.n16 = d.n16[0]; q.slope = d.f[0];
+  q.ldadd0 = d.i[LINSEQ_I_LD_ADD0]; q.ldgate = d.i[LINSEQ_I_LD_GATE]; q.n16 = d.n16[N16_OUT]; q.slope = d.f[LINSEQ_F_SLOPE];
   return q;
 }
 
@@ -455,7 +459,7 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
   if (!shaped(d[0], K_LIN, DF_RM_SC1 | DF_GENTLE | DF_CANARY, kR) || !shaped(d[1], K_LINSEQ, DF_RELU, kH) || !shaped(d[2], K_LINSEQ, DF_RELU, kH) ||
       !shaped(d[3], K_HEAD, 0, kH) || !shaped(d[4], K_LINSEQ, DF_RELU, kH) || !shaped(d[5], K_GRU, 0, kH))
     return 1;
-  if (d[1].i[1] != 3 || d[1].i[3] != kR || d[2].i[1] != 3 || d[2].i[3] != kR || d[4].i[1] != 4 || d[4].i[3] != 0) return 1;
+  if (!run(d[1], 3, kR) || !run(d[2], 3, kR) || !run(d[4], 4, 0)) return 1;
   // roles: prior half [0, d1 end) | posterior half [d2.wg0, d0.wg0) | gentle range [d0.wg0, ...): nothing else there
   const int half = d[2].wg0, gentle = d[0].wg0;
   if (d[1].wg0 != 0 || !within(d[1], 0, half) || !within(d[2], half, gentle) || d[0].nwg <= 0) return 1;
@@ -464,11 +468,14 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
   FwdArgs a{};
   a.hproj = lin_args(p, d[0]);
   a.run[0] = seq_args(p, d[1]); a.run[1] = seq_args(p, d[2]); a.phi = seq_args(p, d[4]);
-  a.head = HeadArgs{sp(p, d[3], 0), sp(p, d[3], 1), sp(p, d[3], 6), sp(p, d[3], 7), sp(p, d[3], 8), sp(p, d[3], 9), sp(p, d[3], 10), sp(p, d[3], 11),
-                    sp(p, d[3], 12), sp(p, d[3], 13), sp(p, d[3], 14), sp(p, d[3], 15), sp(p, d[3], 16), d[3].p[2], d[3].p[3], d[3].p[4], d[3].p[5],
-                    d[3].ld[3], d[3].n16[0], d[3].n16[1], d[3].i[0], d[3].i[1], d[3].f[0], d[3].f[1], d[3].f[2]};
-  a.gru = GruArgs{sp(p, d[5], 0), sp(p, d[5], 2), sp(p, d[5], 3), sp(p, d[5], 4), sp(p, d[5], 5), sp(p, d[5], 6), sp(p, d[5], 11), sp(p, d[5], 7),
-                  sp(p, d[5], 8), sp(p, d[5], 9), d[5].p[1], d[5].p[10], d[5].ld[0], d[5].ld[3], d[5].n16[0], d[5].n16[1], d[5].i[0]};
+  const Desc &h = d[3], &g = d[5];
+  a.head = HeadArgs{sp(p, h, HEAD_P16), sp(p, h, HEAD_Q16), sp(p, h, HEAD_EPS), sp(p, h, HEAD_MU_P), sp(p, h, HEAD_SD_P), sp(p, h, HEAD_MU_Q),
+                    sp(p, h, HEAD_SD_Q), sp(p, h, HEAD_RAW_P), sp(p, h, HEAD_RAW_Q), sp(p, h, HEAD_MUQ_RAW), sp(p, h, HEAD_Z), sp(p, h, HEAD_Z16),
+                    sp(p, h, HEAD_Z16B), h.p[HEAD_WP], h.p[HEAD_BP], h.p[HEAD_WQ], h.p[HEAD_BQ], h.ld[LD_OUT], h.n16[N16_OUT], h.n16[N16_OUTB],
+                    h.i[HEAD_I_Z], h.i[HEAD_I_RESIDUAL], h.f[HEAD_F_BETA], h.f[HEAD_F_INV_BETA], h.f[HEAD_F_SD_EPS]};
+  a.gru = GruArgs{sp(p, g, GRU_X16), sp(p, g, GRU_XG), sp(p, g, GRU_GH), sp(p, g, GRU_HPREV), sp(p, g, GRU_HRM), sp(p, g, GRU_H16), sp(p, g, GRU_H16B),
+                  sp(p, g, GRU_RG), sp(p, g, GRU_UG), sp(p, g, GRU_NG), g.p[GRU_WIH], g.p[GRU_BIH], g.ld[GRU_LD_HPREV], g.ld[LD_OUT], g.n16[N16_OUT],
+                  g.n16[N16_OUTB], g.i[GRU_I_R]};
   int grid = 0;
   for (int i = 0; i < 6; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.ctl = p.ctl;
@@ -492,7 +499,7 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream) {
       !shaped(d[6], K_LINSEQ, DF_SEQ_GATE, kH) || !shaped(d[7], K_DZ, 0, kH) || !shaped(d[8], K_LINSEQ, DF_SEQ_GATE, kH) ||
       !shaped(d[9], K_LINSEQ, DF_SEQ_GATE, kH))
     return 1;
-  if (d[6].i[1] != 2 || d[6].i[3] != 0 || d[8].i[1] != 3 || d[8].i[3] != 2 * kH || d[9].i[1] != 3 || d[9].i[3] != 2 * kH) return 1;
+  if (!run(d[6], 2, 0) || !run(d[8], 3, 2 * kH) || !run(d[9], 3, 2 * kH)) return 1;
   // roles: prior half [0, d2.wg0) | posterior half [d2.wg0, d4.wg0) | gentle range (GB) [d4.wg0, d3.wg0) | spare range [d3.wg0, ...)
   const int half = d[2].wg0, gentle = d[4].wg0, spare = d[3].wg0;
   if (!within(d[1], 0, half) || !within(d[8], 0, half) || !within(d[2], half, gentle) || !within(d[9], half, gentle) || !within(d[4], gentle, spare) ||
@@ -501,16 +508,20 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream) {
   for (int i : {0, 5, 6, 7})
     if (!within(d[i], 0, gentle)) return 1;
   BwdArgs a{};
-  a.grub = GrubArgs{sp(p, d[0], 0), sp(p, d[0], 1), sp(p, d[0], 4), sp(p, d[0], 5), sp(p, d[0], 6), sp(p, d[0], 7), sp(p, d[0], 8), sp(p, d[0], 9),
-                    sp(p, d[0], 10), sp(p, d[0], 11), sp(p, d[0], 12), sp(p, d[0], 13), sp(p, d[0], 14), sp(p, d[0], 15), sp(p, d[0], 17),
-                    d[0].p[2], d[0].p[3], d[0].p[16], d[0].ld[0], d[0].ld[1], d[0].ld[3], d[0].n16[0], d[0].i[0], d[0].i[1], d[0].i[2], d[0].i[3]};
+  const Desc& g = d[0];
+  a.grub = GrubArgs{sp(p, g, GRUB_D0_16), sp(p, g, GRUB_D1_16), sp(p, g, GRUB_G_IN), sp(p, g, GRUB_RG), sp(p, g, GRUB_UG), sp(p, g, GRUB_NG), sp(p, g, GRUB_GH),
+                    sp(p, g, GRUB_HPREV), sp(p, g, GRUB_DD), sp(p, g, GRUB_DGI), sp(p, g, GRUB_DGI16), sp(p, g, GRUB_DGH), sp(p, g, GRUB_DGH16), sp(p, g, GRUB_GA),
+                    sp(p, g, GRUB_G_ADD), g.p[GRUB_W0], g.p[GRUB_W1], g.p[GRUB_G_OUT], g.ld[GRUB_LD_H], g.ld[GRUB_LD_GADD], g.ld[LD_OUT], g.n16[N16_OUT],
+                    g.i[GRUB_I_R], g.i[GRUB_I_GEMM_FROM], g.i[GRUB_I_GATES_TO], g.i[GRUB_I_GIN_FROM]};
   for (int k = 0; k < 3; ++k) a.part[k] = lin_args(p, d[1 + k]);
   a.gb = lin_args(p, d[4]); a.sum = lin_args(p, d[5]);
   a.phi = seq_args(p, d[6]); a.run[0] = seq_args(p, d[8]); a.run[1] = seq_args(p, d[9]);
   const Desc& z = d[7];
-  a.dz = DzArgs{sp(p, z, 0), sp(p, z, 2), sp(p, z, 4), sp(p, z, 5), sp(p, z, 6), sp(p, z, 7), sp(p, z, 8), sp(p, z, 9), sp(p, z, 10), sp(p, z, 11),
-                sp(p, z, 12), sp(p, z, 16), sp(p, z, 17), sp(p, z, 18), sp(p, z, 19), z.p[1], z.p[3], z.p[14], z.p[15],
-                reinterpret_cast<const int32_t*>(z.p[13]), z.ld[1], z.ld[3], z.n16[0], z.i[0], z.i[1], z.i[2], z.i[3], (int)z.f[3], z.f[0], z.f[1], z.f[2]};
+  a.dz = DzArgs{sp(p, z, DZ_D16), sp(p, z, DZ_D2_16), sp(p, z, DZ_ADD), sp(p, z, DZ_MU_Q), sp(p, z, DZ_SD_Q), sp(p, z, DZ_MU_P), sp(p, z, DZ_SD_P),
+                sp(p, z, DZ_EPS), sp(p, z, DZ_RAW_Q), sp(p, z, DZ_RAW_P), sp(p, z, DZ_MUQ_RAW), sp(p, z, DZ_DQH), sp(p, z, DZ_DQH16), sp(p, z, DZ_DPH),
+                sp(p, z, DZ_DPH16), z.p[DZ_WT], z.p[DZ_WT2], z.p[DZ_C_RAW], z.p[DZ_C_FN], reinterpret_cast<const int32_t*>(z.p[DZ_X_SL]), z.ld[DZ_LD_ADD],
+                z.ld[LD_OUT], z.n16[N16_OUT], z.i[DZ_I_Z], z.i[DZ_I_RESIDUAL], z.i[DZ_I_STRIDE], z.i[DZ_I_T0], (int)z.f[DZ_F_GEMM_FROM], z.f[DZ_F_FN_FLOOR],
+                z.f[DZ_F_BETA], z.f[DZ_F_SD_EPS]};
   int grid = 0;
   for (int i = 0; i < 10; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.ctl = p.ctl;
@@ -549,9 +560,9 @@ extern "C" int blvm_pchain_static_chain_probe(const float* W16, const float* bia
   Builder bld;
   bld.p.S = L; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 1;
   const int nw = nwg > 0 ? nwg : range_for((N / 16) * rt, device_cus() & ~7);
-  Desc& d = bld.add(K_LIN, N / 16, 0, nw, N, DF_RELU, 0, L);
-  bld.ptr(d, 0, x16, x); bld.ptr(d, 1, W16); bld.ptr(d, 2, bias); bld.ptr(d, 5, xs, sN); bld.ptr(d, 6, x16 + x, x);
-  d.ld[3] = N; d.n16[0] = N / 16; d.f[0] = 0.f;
+  Operands o;
+  o.p[LIN_A] = {x16, x}; o.p[LIN_W] = W16; o.p[LIN_BIAS] = bias; o.p[LIN_ORM] = {xs, sN}; o.p[LIN_O16] = {x16 + x, x}; o.ld[LD_OUT] = N; o.n16[N16_OUT] = N / 16;
+  add_desc(bld, K_LIN, N / 16, 0, nw, N, DF_RELU, 0, L, o);
   int rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
   if (rc) return rc;
   BLVM_HIP(pchain_fill_sentinel(x16 + x, sizeof(float) * (size_t)x * L, s));
