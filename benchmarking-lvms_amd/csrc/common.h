@@ -39,7 +39,46 @@ void set_error(const char* fmt, ...);
     }                                                                               \
   } while (0)
 
+// BLVM_TRY(expr): evaluates an int status and returns it from the enclosing function (or int lambda) when it is non-zero
+// (variadic only so that expr may hold the commas of a template argument list)
+#define BLVM_TRY(...)                      \
+  do {                                     \
+    const int rc__ = (__VA_ARGS__);        \
+    if (rc__) return rc__;                 \
+  } while (0)
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// Carves one caller-owned buffer of floats into 16-byte aligned pieces.  A null base gives sizes only (the *_floats exports).
+struct Arena {
+  float* base = nullptr;
+  size_t off = 0;  // floats taken so far
+  size_t take_off(size_t count) { const size_t at = off; off += (count + 3) & ~(size_t)3; return at; }  // the piece as an offset
+  float* take(size_t count) { const size_t at = take_off(count); return base ? base + at : nullptr; }   // take(0): the running end
+  size_t floats() const { return off; }
+  // bytes from p (a piece taken earlier) to the running end: the region a persistent launch polls, sentinel-filled in one go
+  size_t bytes_from(const float* p) const { return base ? sizeof(float) * (size_t)(base + off - p) : 0; }
+};
+
+// initial states: dst = src, or zeros where the caller passes none (contiguous | `rows` rows of `width` bytes at `dpitch`)
+inline hipError_t copy_or_zero(void* dst, const void* src, size_t bytes, hipStream_t s) {
+  return src ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipMemsetAsync(dst, 0, bytes, s);
+}
+inline hipError_t copy_or_zero_2d(void* dst, size_t dpitch, const void* src, size_t width, size_t rows, hipStream_t s) {
+  return src ? hipMemcpy2DAsync(dst, dpitch, src, width, width, rows, hipMemcpyDeviceToDevice, s) : hipMemset2DAsync(dst, dpitch, 0, width, rows, s);
+}
+
+// beta of the Gaussian heads' softplus (softplus_beta below): ln2 / (initial_sd - eps), initial_sd = 1
+inline float softplus_beta_of(float sd_eps) { return (float)(0.6931471805599453 / (1.0 - (double)sd_eps)); }
+
+// kernel<NW> for nw = 16 | 8 | 4 waves (tried, and so instantiated, in that order).  `kernel` is written with NW_ for its wave
+// count: gru_stage_kernel<NW_>, or in parentheses when its template arguments hold a comma: (lin_stage_kernel<NW_, NSEG>)
+#define LAUNCH_NW(kernel, nw, grid, stream, ...)                                                                                  \
+  do {                                                                                                                            \
+    if ((nw) == 16) { constexpr int NW_ = 16; hipLaunchKernelGGL(kernel, grid, dim3(NW_ * 64), 0, stream, __VA_ARGS__); }         \
+    else if ((nw) == 8) { constexpr int NW_ = 8; hipLaunchKernelGGL(kernel, grid, dim3(NW_ * 64), 0, stream, __VA_ARGS__); }      \
+    else { constexpr int NW_ = 4; hipLaunchKernelGGL(kernel, grid, dim3(NW_ * 64), 0, stream, __VA_ARGS__); }                     \
+  } while (0)
 
 // ---- device math -----------------------------------------------------------------------------------------------
 // Accurate libm forms (parity first: ELBO must match the fp32 CPU path to 1e-4 relative over ~1e6 frames).

@@ -551,12 +551,10 @@ static int chan_norm_stats(const float* x, int L, int N, int C, const float* gam
 extern "C" int blvm_chan_norm_stats(const float* x, int L, int N, int C, const float* gamma, const float* beta, float eps,
                                     float* mr, float* scale_shift, double* workspace, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_ln(L, N, C);
-  if (rc) return rc;
+  BLVM_TRY(check_ln(L, N, C));
   BLVM_REQUIRE(x && gamma && beta && mr && scale_shift && workspace, "chan_norm_stats: null pointer");
   BLVM_REQUIRE(aligned16(x), "chan_norm_stats: alignment");
-  rc = chan_norm_stats(x, L, N, C, gamma, beta, eps, mr, scale_shift, workspace, s);
-  if (rc) return rc;
+  BLVM_TRY(chan_norm_stats(x, L, N, C, gamma, beta, eps, mr, scale_shift, workspace, s));
   BLVM_CHECK_LAUNCH("chan_norm_stats");
   return BLVM_OK;
 }
@@ -564,12 +562,10 @@ extern "C" int blvm_chan_norm_stats(const float* x, int L, int N, int C, const f
 extern "C" int blvm_chan_norm_fwd(const float* x, int L, int N, int C, const float* gamma, const float* beta, float eps,
                                   float* y, float* mr, double* workspace, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_ln(L, N, C);
-  if (rc) return rc;
+  BLVM_TRY(check_ln(L, N, C));
   BLVM_REQUIRE(x && gamma && beta && y && mr && workspace, "chan_norm_fwd: null pointer");
   BLVM_REQUIRE(aligned16(x) && aligned16(y) && aligned16(mr) && aligned16(gamma) && aligned16(beta), "chan_norm_fwd: alignment");
-  rc = chan_norm_stats(x, L, N, C, gamma, beta, eps, mr, nullptr, workspace, s);
-  if (rc) return rc;
+  BLVM_TRY(chan_norm_stats(x, L, N, C, gamma, beta, eps, mr, nullptr, workspace, s));
   const int cb = (N / 4 + 63) / 64;
   const int rpb = pick_rows_per_block(L, cb, 32);
   hipLaunchKernelGGL(norm_apply_kernel, dim3(cb, (L + rpb - 1) / rpb), dim3(256), 0, s, x, mr, gamma, beta, L, N, C, rpb, y);
@@ -581,8 +577,7 @@ extern "C" int blvm_chan_norm_bwd(const float* x, const float* dy, const float* 
                                   int relu_mask, float* dx, float* dgamma, float* dbeta, float* dx_chan_sum,
                                   double* workspace, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_ln(L, N, C);
-  if (rc) return rc;
+  BLVM_TRY(check_ln(L, N, C));
   BLVM_REQUIRE(x && dy && mr && gamma && dx && workspace, "chan_norm_bwd: null pointer");
   BLVM_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(mr) && aligned16(gamma), "chan_norm_bwd: alignment");
   BLVM_HIP(hipMemsetAsync(workspace, 0, sizeof(double) * 2 * N, s));
@@ -606,8 +601,7 @@ extern "C" int blvm_dwconv_fwd(const float* x, const float* in_scale, const floa
                                int L_in, int N, int C, int k, int stride, int dilation, int transposed, int relu, float* y,
                                void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_ln(L_in, N, C);
-  if (rc) return rc;
+  BLVM_TRY(check_ln(L_in, N, C));
   BLVM_REQUIRE(x && w && y && k > 0 && k <= 8 && stride > 0 && dilation > 0, "dwconv_fwd: bad arguments");
   BLVM_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "dwconv_fwd: in_scale and in_shift go together");
   const int L_out = dw_len_out(L_in, k, stride, dilation, transposed);
@@ -625,8 +619,7 @@ extern "C" int blvm_dwconv_bwd(const float* x, const float* in_scale, const floa
                                const float* dy, int L_in, int N, int C, int k, int stride, int dilation, int transposed, int relu,
                                float* dx, float* dw, float* dbias, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_ln(L_in, N, C);
-  if (rc) return rc;
+  BLVM_TRY(check_ln(L_in, N, C));
   BLVM_REQUIRE(x && w && dy && k > 0 && k <= 8 && stride > 0 && dilation > 0, "dwconv_bwd: bad arguments");
   BLVM_REQUIRE(!relu || y, "dwconv_bwd: the ReLU mask needs the forward output");
   BLVM_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "dwconv_bwd: in_scale and in_shift go together");

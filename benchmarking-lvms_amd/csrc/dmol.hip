@@ -602,14 +602,12 @@ extern "C" int blvm_dmol_fwd(const float* dec, int layout, const float* W, const
                              const int32_t* x_sl, int B, int T, int Tp, int S, int num_mix, int num_bins,
                              float log_eps, double* log_prob, float* ll_twise, void* stream) {
   using namespace blvm;
-  int rc = check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, num_bins, layout);
-  if (rc) return rc;
+  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, num_bins, layout));
   BLVM_REQUIRE(log_prob != nullptr, "dmol_fwd: log_prob is null");
   DmolArgs a = make_args(dec, layout, W, bias, y, x_sl, B, T, Tp, S, num_bins, log_eps);
   a.log_prob = log_prob;
   a.ll_twise = ll_twise;
-  rc = launch_dmol<false>(a, static_cast<hipStream_t>(stream));
-  if (rc) return rc;
+  BLVM_TRY(launch_dmol<false>(a, static_cast<hipStream_t>(stream)));
   BLVM_CHECK_LAUNCH("dmol_fwd");
   return BLVM_OK;
 }
@@ -618,15 +616,13 @@ extern "C" int blvm_dmol_bwd(const float* dec, int layout, const float* W, const
                              const int32_t* x_sl, const float* g_b, int B, int T, int Tp, int S, int num_mix,
                              int num_bins, float log_eps, float* d_dec, float* d_par, void* stream) {
   using namespace blvm;
-  int rc = check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, num_bins, layout);
-  if (rc) return rc;
+  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, num_bins, layout));
   BLVM_REQUIRE(g_b && d_dec && (d_par || !W), "dmol_bwd: null pointer");
   DmolArgs a = make_args(dec, layout, W, bias, y, x_sl, B, T, Tp, S, num_bins, log_eps);
   a.g_b = g_b;
   a.d_dec = d_dec;
   a.d_par = d_par;
-  rc = launch_dmol<true>(a, static_cast<hipStream_t>(stream));
-  if (rc) return rc;
+  BLVM_TRY(launch_dmol<true>(a, static_cast<hipStream_t>(stream)));
   BLVM_CHECK_LAUNCH("dmol_bwd");
   return BLVM_OK;
 }
@@ -742,15 +738,13 @@ extern "C" int blvm_gauss_head_fwd(const float* dec, int layout, const float* W,
                                    const int32_t* x_sl, int B, int T, int Tp, int S, float sd_beta, float sd_eps,
                                    double* log_prob, float* ll_twise, void* stream) {
   using namespace blvm;
-  int rc = check_common(dec, W, bias, y, x_sl, B, T, Tp, S, NMIX, 2, layout);
-  if (rc) return rc;
+  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, NMIX, 2, layout));
   BLVM_REQUIRE(log_prob != nullptr && sd_beta > 0.f && aligned16(dec), "gauss_head_fwd: bad arguments");
   DmolArgs a = make_args(dec, layout, W, bias, y, x_sl, B, T, Tp, S, 2, 0.f);
   a.kind = 2; a.sd_beta = sd_beta; a.sd_eps = sd_eps;
   a.log_prob = log_prob;
   a.ll_twise = ll_twise;
-  rc = launch_gauss<false>(a, static_cast<hipStream_t>(stream));
-  if (rc) return rc;
+  BLVM_TRY(launch_gauss<false>(a, static_cast<hipStream_t>(stream)));
   BLVM_CHECK_LAUNCH("gauss_head_fwd");
   return BLVM_OK;
 }
@@ -759,16 +753,14 @@ extern "C" int blvm_gauss_head_bwd(const float* dec, int layout, const float* W,
                                    const int32_t* x_sl, const float* g_b, int B, int T, int Tp, int S, float sd_beta,
                                    float sd_eps, float* d_dec, float* d_par, void* stream) {
   using namespace blvm;
-  int rc = check_common(dec, W, bias, y, x_sl, B, T, Tp, S, NMIX, 2, layout);
-  if (rc) return rc;
+  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, NMIX, 2, layout));
   BLVM_REQUIRE(g_b && d_dec && (d_par || !W) && sd_beta > 0.f && aligned16(dec) && aligned16(d_dec), "gauss_head_bwd: bad arguments");
   DmolArgs a = make_args(dec, layout, W, bias, y, x_sl, B, T, Tp, S, 2, 0.f);
   a.kind = 2; a.sd_beta = sd_beta; a.sd_eps = sd_eps;
   a.g_b = g_b;
   a.d_dec = d_dec;
   a.d_par = d_par;
-  rc = launch_gauss<true>(a, static_cast<hipStream_t>(stream));
-  if (rc) return rc;
+  BLVM_TRY(launch_gauss<true>(a, static_cast<hipStream_t>(stream)));
   BLVM_CHECK_LAUNCH("gauss_head_bwd");
   return BLVM_OK;
 }
@@ -777,15 +769,13 @@ extern "C" int blvm_gmm_fwd(const float* dec, int layout, const float* W, const 
                             const int32_t* x_sl, int B, int T, int Tp, int S, int num_mix, float sd_beta, float sd_eps,
                             double* log_prob, float* ll_twise, void* stream) {
   using namespace blvm;
-  int rc = check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, 2, layout);
-  if (rc) return rc;
+  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, 2, layout));
   BLVM_REQUIRE(log_prob != nullptr && sd_beta > 0.f, "gmm_fwd: bad arguments");
   DmolArgs a = make_args(dec, layout, W, bias, y, x_sl, B, T, Tp, S, 2, 0.f);
   a.kind = 1; a.sd_beta = sd_beta; a.sd_eps = sd_eps;
   a.log_prob = log_prob;
   a.ll_twise = ll_twise;
-  rc = launch_dmol<false>(a, static_cast<hipStream_t>(stream));
-  if (rc) return rc;
+  BLVM_TRY(launch_dmol<false>(a, static_cast<hipStream_t>(stream)));
   BLVM_CHECK_LAUNCH("gmm_fwd");
   return BLVM_OK;
 }
@@ -794,16 +784,14 @@ extern "C" int blvm_gmm_bwd(const float* dec, int layout, const float* W, const 
                             const int32_t* x_sl, const float* g_b, int B, int T, int Tp, int S, int num_mix, float sd_beta,
                             float sd_eps, float* d_dec, float* d_par, void* stream) {
   using namespace blvm;
-  int rc = check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, 2, layout);
-  if (rc) return rc;
+  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, 2, layout));
   BLVM_REQUIRE(g_b && d_dec && (d_par || !W) && sd_beta > 0.f, "gmm_bwd: bad arguments");
   DmolArgs a = make_args(dec, layout, W, bias, y, x_sl, B, T, Tp, S, 2, 0.f);
   a.kind = 1; a.sd_beta = sd_beta; a.sd_eps = sd_eps;
   a.g_b = g_b;
   a.d_dec = d_dec;
   a.d_par = d_par;
-  rc = launch_dmol<true>(a, static_cast<hipStream_t>(stream));
-  if (rc) return rc;
+  BLVM_TRY(launch_dmol<true>(a, static_cast<hipStream_t>(stream)));
   BLVM_CHECK_LAUNCH("gmm_bwd");
   return BLVM_OK;
 }

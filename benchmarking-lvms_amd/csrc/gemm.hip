@@ -725,8 +725,7 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
   const OpType ot = operand_type();
   const int bk = ot != OP_F32 ? BKB : tile_bk(bm, bn);
   if (colsum != nullptr && (ot != OP_F32 || op_a != 1 || K == 0)) {  // (the 16-bit kernel stages ROUNDED operands: the bias gradient stays an fp32 sum)
-    const int rc = op_a == 1 ? colsum_f32(K, M, A, lda, colsum, 1, stream) : BLVM_EINVAL;
-    if (rc) return rc;
+    BLVM_TRY(op_a == 1 ? colsum_f32(K, M, A, lda, colsum, 1, stream) : BLVM_EINVAL);
     colsum = nullptr;
   }
   g.colsum = colsum;
@@ -755,7 +754,7 @@ int gemm_wgrad_group(const WgradJob* jobs, int njobs, int K, hipStream_t stream)
   for (int i = 0; i < njobs; ++i) {
     const WgradJob& j = jobs[i];
     if (!j.dW) {
-      if (j.db) { const int rc = colsum_f32(K, j.M, j.D, j.ldd, j.db, 1, stream); if (rc) return rc; }
+      if (j.db) BLVM_TRY(colsum_f32(K, j.M, j.D, j.ldd, j.db, 1, stream));
       continue;
     }
     BLVM_REQUIRE(j.D && j.Act && j.M > 0 && j.N > 0 && j.ldd >= j.M && j.lda >= j.N && j.ldw >= j.N, "gemm_wgrad_group: bad job %d", i);
@@ -763,14 +762,12 @@ int gemm_wgrad_group(const WgradJob* jobs, int njobs, int K, hipStream_t stream)
       take.push_back(i);
       continue;
     }
-    const int rc = gemm_f32(1, 1, j.M, j.N, K, j.D, j.ldd, j.Act, j.lda, j.dW, j.ldw, nullptr, 0, 0.f, nullptr, 0, 1, gemm_pick_split(j.M, j.N, K), stream, j.db);
-    if (rc) return rc;
+    BLVM_TRY(gemm_f32(1, 1, j.M, j.N, K, j.D, j.ldd, j.Act, j.lda, j.dW, j.ldw, nullptr, 0, 0.f, nullptr, 0, 1, gemm_pick_split(j.M, j.N, K), stream, j.db));
   }
   if (take.size() < 2) {  // a group of one: gemm_f32 picks tile and split (measured: 256 x 256 x 16000 alone 40 us there, 47 in a group)
     for (const int i : take) {
       const WgradJob& j = jobs[i];
-      const int rc = gemm_f32(1, 1, j.M, j.N, K, j.D, j.ldd, j.Act, j.lda, j.dW, j.ldw, nullptr, 0, 0.f, nullptr, 0, 1, gemm_pick_split(j.M, j.N, K), stream, j.db);
-      if (rc) return rc;
+      BLVM_TRY(gemm_f32(1, 1, j.M, j.N, K, j.D, j.ldd, j.Act, j.lda, j.dW, j.ldw, nullptr, 0, 0.f, nullptr, 0, 1, gemm_pick_split(j.M, j.N, K), stream, j.db));
     }
     return BLVM_OK;
   }
@@ -962,7 +959,7 @@ int t16_pack(const float* src, long rs, long cs, int R, int K, float* dst, hipSt
   const size_t n = (size_t)R * K;
   BLVM_REQUIRE(n < (1ull << 31), "t16_pack: matrix too large");
   if (g_pack.active && g_pack.stream == stream) {  // deferred: one launch for all packs of the scope
-    if (g_pack.n == kPackJobs) { const int rc = pack_flush(); if (rc) return rc; }
+    if (g_pack.n == kPackJobs) BLVM_TRY(pack_flush());
     g_pack.jobs.j[g_pack.n++] = PackJob{src, dst, rs, cs, K / 16, (unsigned)(g_pack.ot != OP_F32 ? n / 2 : n)};
     return BLVM_OK;
   }

@@ -237,8 +237,7 @@ extern "C" int blvm_kl_fwd(const float* mu_q, const float* sd_q, const float* mu
                            const int32_t* x_sl, int B, int Tp, int Z, int stride, float fn_floor, double* kld,
                            double* kld_fn, void* stream) {
   using namespace blvm;
-  int rc = check(mu_q, sd_q, mu_p, sd_p, layout, x_sl, B, Tp, Z, stride);
-  if (rc) return rc;
+  BLVM_TRY(check(mu_q, sd_q, mu_p, sd_p, layout, x_sl, B, Tp, Z, stride));
   BLVM_REQUIRE(kld && kld_fn, "kl_fwd: null output");
   KlArgs a{};
   a.mu_q = mu_q; a.sd_q = sd_q; a.mu_p = mu_p; a.sd_p = sd_p; a.x_sl = x_sl;
@@ -260,8 +259,7 @@ extern "C" int blvm_kl_bwd(const float* mu_q, const float* sd_q, const float* mu
                            int stride, float fn_floor, float* d_mu_q, float* d_sd_q, float* d_mu_p, float* d_sd_p,
                            void* stream) {
   using namespace blvm;
-  int rc = check(mu_q, sd_q, mu_p, sd_p, layout, x_sl, B, Tp, Z, stride);
-  if (rc) return rc;
+  BLVM_TRY(check(mu_q, sd_q, mu_p, sd_p, layout, x_sl, B, Tp, Z, stride));
   BLVM_REQUIRE(d_mu_q && d_sd_q && d_mu_p && d_sd_p, "kl_bwd: null output");
   KlArgs a{};
   a.mu_q = mu_q; a.sd_q = sd_q; a.mu_p = mu_p; a.sd_p = sd_p; a.x_sl = x_sl;

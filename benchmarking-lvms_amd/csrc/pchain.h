@@ -1081,6 +1081,12 @@ struct Builder {
   Program p{};
   int nstride = 1;
   bool overflow = false;
+  // the program's header: operand type, S steps over B rows, the most products of any tile kind, XCD-aware placement (pchain_tune) and
+  // the profile slot (workgroups 0 and prof_wg; a backward program's ticks go 64 words behind the forward program's)
+  void begin(int ot, int S, int B, int lds_products, bool backward, int prof_wg) {
+    p.ot = ot; p.S = S; p.B = B; p.xcd = (pchain_tune() & 4) ? 1 : 0; p.lds_products = lds_products;
+    p.prof = pchain_profile_buffer() && backward ? pchain_profile_buffer() + 64 : pchain_profile_buffer(); p.prof_wg = prof_wg;
+  }
   int stride_index(long v) {
     if (v == 0) return 0;
     for (int i = 1; i < nstride; ++i)
@@ -1156,11 +1162,21 @@ inline int range_for(int tiles, int avail) { return std::max(8, std::min(avail &
 // sentinel-fill `bytes` (a multiple of 4) at p (4-byte aligned) on `stream`: what hipMemsetAsync(p, 0xFF, bytes) does, as 16-byte
 // stores from 2048 workgroups (the runtime's fill kernel runs 256 workgroups: 72 us for the VRNN backward slabs of [64,16000])
 hipError_t pchain_fill_sentinel(void* p, size_t bytes, hipStream_t stream);
-// enqueue the persistent launch of a program (pchain.hip); grid = highest workgroup any descriptor names
-int pchain_launch(const pchain::Program& prog, hipStream_t stream);
-// the VRNN forward / backward program on the static-walk kernels (vrnn_static.hip); 1: not the shape they were compiled for, or
-// blvm_pchain_static(0) — the caller runs pchain_launch
-int vrnn_static_launch(const pchain::Program& prog, bool forward, hipStream_t stream);
+// The launchers below take the control block themselves (a fresh epoch of the process-wide block, core.hip pchain_ctl): a host-side
+// counter under a mutex, nothing on the stream.  A driver enqueues its sentinel fills first, so only a failing first-time allocation
+// of the block surfaces after them.
+inline int pchain_ctl(pchain::Ctl& c) { return pchain_ctl(&c.dev, &c.host, &c.epoch); }
+// what every launch of a built program starts with: `who` (the caller's name) reports a Builder that ran out of descriptors or strides
+int pchain_prepare(pchain::Builder& bld, const char* who);
+// enqueue the persistent launch of a prepared program (pchain.hip); grid = highest workgroup any descriptor names
+int pchain_run(const pchain::Program& prog, hipStream_t stream);
+inline int pchain_launch(pchain::Builder& bld, const char* who, hipStream_t stream) {
+  BLVM_TRY(pchain_prepare(bld, who));
+  return pchain_run(bld.p, stream);
+}
+// the VRNN forward / backward program on the static-walk kernels (vrnn_static.hip), or on the interpreter when it is not the shape they
+// were compiled for or after blvm_pchain_static(0)
+int vrnn_launch(pchain::Builder& bld, bool forward, const char* who, hipStream_t stream);
 // dst = T16 copy [ceil(B/16)*16, K] of the rows of src [B, K] (row stride ld; null: zeros); rows >= B are left alone (never read).
 // n16 > 0: dst is a slab of n16 blocks per row tile (a concatenation; dst points at this part's first block)
 int pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, hipStream_t stream, int n16 = 0);

@@ -566,7 +566,12 @@ hipError_t pchain_fill_sentinel(void* p, size_t bytes, hipStream_t stream) {
   return hipGetLastError();
 }
 
-int pchain_launch(const pchain::Program& prog, hipStream_t stream) {
+int pchain_prepare(pchain::Builder& bld, const char* who) {
+  BLVM_REQUIRE(!bld.overflow, "%s: persistent program overflow", who);
+  return pchain_ctl(bld.p.ctl);
+}
+
+int pchain_run(const pchain::Program& prog, hipStream_t stream) {
   BLVM_REQUIRE(prog.ndesc > 0 && prog.ndesc <= pchain::kMaxDesc && prog.S > 0 && prog.B > 0, "pchain: bad program (%d descriptors, %d steps)", prog.ndesc, prog.S);
   int grid = 0;
   for (int i = 0; i < prog.ndesc; ++i) {
@@ -645,15 +650,13 @@ int pchain_launch(const pchain::Program& prog, hipStream_t stream) {
       BLVM_REQUIRE(k != pchain::K_DZ || prog.d[i].p[2] == nullptr, "pchain: the row-group dz tile is the single-product form");
     }
     BLVM_REQUIRE(prog.ot == OP_F32, "pchain: row groups multiply fp32 operands only");
-    const int rcg = go(&pchain_rt_kernel<8, OP_F32, 2>, 2, 512);
-    if (rcg) return rcg;
+    BLVM_TRY(go(&pchain_rt_kernel<8, OP_F32, 2>, 2, 512));
     BLVM_CHECK_LAUNCH("pchain_launch (row groups)");
     return BLVM_OK;
   }
-  const int rc = prog.ot == OP_BF16  ? go(&pchain_kernel<16, OP_BF16>, 1, 1024)
-                 : prog.ot == OP_F16 ? go(&pchain_kernel<16, OP_F16>, 3, 1024)
-                                     : go(&pchain_kernel<16, OP_F32>, 0, 1024);
-  if (rc) return rc;
+  BLVM_TRY(prog.ot == OP_BF16  ? go(&pchain_kernel<16, OP_BF16>, 1, 1024)
+           : prog.ot == OP_F16 ? go(&pchain_kernel<16, OP_F16>, 3, 1024)
+                               : go(&pchain_kernel<16, OP_F32>, 0, 1024));
   BLVM_CHECK_LAUNCH("pchain_launch");
   return BLVM_OK;
 }
@@ -671,8 +674,7 @@ extern "C" int blvm_pchain_chain_probe(const float* W16, const float* bias, floa
   const int rt = (B + 15) / 16;
   const long x = (long)rt * 16 * N, sN = (long)B * N;
   Builder bld;
-  bld.p.S = L; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 1;
-  bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = 1;
+  bld.begin(OP_F32, L, B, 1, false, 1);
   static const int run = [] { const char* e = getenv("BLVM_PCHAIN_PROBE_RUN"); return e ? atoi(e) : 1; }();  // links per K_LINSEQ visit
   const int nw = nwg > 0 ? nwg : range_for((N / 16) * rt, device_cus() & ~7);
   if (run >= 2 && run <= 4 && L % run == 0) {  // the same chain as runs of `run` links in one descriptor visit
@@ -685,10 +687,8 @@ extern "C" int blvm_pchain_chain_probe(const float* W16, const float* bias, floa
     o.p[LIN_A] = {x16, x}; o.p[LIN_W] = W16; o.p[LIN_BIAS] = bias; o.p[LIN_ORM] = {xs, sN}; o.p[LIN_O16] = {x16 + x, x}; o.ld[LD_OUT] = N; o.n16[N16_OUT] = N / 16;
     add_desc(bld, K_LIN, N / 16, 0, nw, N, DF_RELU, 0, L, o);
   }
-  int rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-  if (rc) return rc;
   BLVM_HIP(pchain_fill_sentinel(x16 + x, sizeof(float) * (size_t)x * L, s));
-  return pchain_launch(bld.p, s);
+  return pchain_launch(bld, "pchain_chain_probe", s);
 }
 
 extern "C" int blvm_pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, void* stream) {

@@ -15,13 +15,6 @@
 namespace blvm {
 namespace {
 
-#define LAUNCH_NW(kernel, nw, grid, stream, args)                                          \
-  do {                                                                                     \
-    if ((nw) == 16) hipLaunchKernelGGL((kernel<16>), grid, dim3(1024), 0, stream, args);   \
-    else if ((nw) == 8) hipLaunchKernelGGL((kernel<8>), grid, dim3(512), 0, stream, args); \
-    else hipLaunchKernelGGL((kernel<4>), grid, dim3(256), 0, stream, args);                \
-  } while (0)
-
 inline int pick_nw(int K, int groups) {
   const int chunks = (K / 16) * groups;
   if (chunks > 32) return 16;
@@ -158,29 +151,27 @@ inline bool seq_persistent(int T, int B) { return pchain_applies(B) && device_cu
 
 struct LstmReserve { float *XG, *Hs, *Cs, *GATES, *WhhP, *H16; };  // WhhP: T16 copy of Whh; H16: (T+1) T16 slabs of the state
 size_t carve_lstm(float* base, int T, int B, int H, LstmReserve* r) {
-  size_t off = 0;
-  auto take = [&](size_t cnt) { float* p = base ? base + off : nullptr; off += (cnt + 3) & ~(size_t)3; return p; };
+  Arena ar{base};
   LstmReserve t;
-  t.XG = take((size_t)T * B * 4 * H);
-  t.Hs = take((size_t)(T + 1) * B * H);
-  t.Cs = take((size_t)(T + 1) * B * H);
-  t.GATES = take((size_t)T * B * 4 * H);
-  t.WhhP = take((size_t)4 * H * H);
-  t.H16 = B <= kPchainCarveMaxB ? take((size_t)(T + 1) * t16_rows(B) * H) : nullptr;
+  t.XG = ar.take((size_t)T * B * 4 * H);
+  t.Hs = ar.take((size_t)(T + 1) * B * H);
+  t.Cs = ar.take((size_t)(T + 1) * B * H);
+  t.GATES = ar.take((size_t)T * B * 4 * H);
+  t.WhhP = ar.take((size_t)4 * H * H);
+  t.H16 = B <= kPchainCarveMaxB ? ar.take((size_t)(T + 1) * t16_rows(B) * H) : nullptr;
   if (r) *r = t;
-  return off;
+  return ar.floats();
 }
 struct LstmWs { float *WhhT, *DG, *DC, *DG16; };
 size_t carve_lstm_ws(float* base, int T, int B, int H, LstmWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t cnt) { float* p = base ? base + off : nullptr; off += (cnt + 3) & ~(size_t)3; return p; };
+  Arena ar{base};
   LstmWs t;
-  t.WhhT = take((size_t)H * 4 * H);
-  t.DG = take((size_t)T * B * 4 * H);
-  t.DC = take((size_t)B * H);
-  t.DG16 = B <= kPchainCarveMaxB ? take((size_t)(T + 1) * t16_rows(B) * 4 * H) : nullptr;
+  t.WhhT = ar.take((size_t)H * 4 * H);
+  t.DG = ar.take((size_t)T * B * 4 * H);
+  t.DC = ar.take((size_t)B * H);
+  t.DG16 = B <= kPchainCarveMaxB ? ar.take((size_t)(T + 1) * t16_rows(B) * 4 * H) : nullptr;
   if (w) *w = t;
-  return off;
+  return ar.floats();
 }
 
 // ===================================================================================================================
@@ -302,31 +293,29 @@ __global__ __launch_bounds__(NW * 64) void gru_bwd_kernel(const float* DGHn, con
 
 struct GruReserve { float *XG, *Hs, *RG, *UG, *NG, *GHN, *WhhP, *H16; };  // WhhP: T16 copy of Whh; H16: (T+1) T16 slabs of the state
 size_t carve_gru(float* base, int T, int B, int R, GruReserve* r) {
-  size_t off = 0;
-  auto take = [&](size_t cnt) { float* p = base ? base + off : nullptr; off += (cnt + 3) & ~(size_t)3; return p; };
+  Arena ar{base};
   GruReserve t;
   const size_t n = (size_t)T * B;
-  t.XG = take(n * 3 * R);
-  t.Hs = take((size_t)(T + 1) * B * R);
-  t.RG = take(n * R); t.UG = take(n * R); t.NG = take(n * R); t.GHN = take(n * R);
-  t.WhhP = take((size_t)3 * R * R);
-  t.H16 = B <= kPchainCarveMaxB ? take((size_t)(T + 1) * t16_rows(B) * R) : nullptr;
+  t.XG = ar.take(n * 3 * R);
+  t.Hs = ar.take((size_t)(T + 1) * B * R);
+  t.RG = ar.take(n * R); t.UG = ar.take(n * R); t.NG = ar.take(n * R); t.GHN = ar.take(n * R);
+  t.WhhP = ar.take((size_t)3 * R * R);
+  t.H16 = B <= kPchainCarveMaxB ? ar.take((size_t)(T + 1) * t16_rows(B) * R) : nullptr;
   if (r) *r = t;
-  return off;
+  return ar.floats();
 }
 struct GruWs { float *WhhT, *DGI, *DGH, *G, *DGH16; };
 size_t carve_gru_ws(float* base, int T, int B, int R, GruWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t cnt) { float* p = base ? base + off : nullptr; off += (cnt + 3) & ~(size_t)3; return p; };
+  Arena ar{base};
   GruWs t;
   const size_t n = (size_t)T * B;
-  t.WhhT = take((size_t)R * 3 * R);
-  t.DGI = take(n * 3 * R);
-  t.DGH = take(n * 3 * R);
-  t.G = take((size_t)B * R);
-  t.DGH16 = B <= kPchainCarveMaxB ? take((size_t)(T + 1) * t16_rows(B) * 3 * R) : nullptr;
+  t.WhhT = ar.take((size_t)R * 3 * R);
+  t.DGI = ar.take(n * 3 * R);
+  t.DGH = ar.take(n * 3 * R);
+  t.G = ar.take((size_t)B * R);
+  t.DGH16 = B <= kPchainCarveMaxB ? ar.take((size_t)(T + 1) * t16_rows(B) * 3 * R) : nullptr;
   if (w) *w = t;
-  return off;
+  return ar.floats();
 }
 
 int check_rnn(int T, int B, int I, int H) {
@@ -349,74 +338,51 @@ extern "C" int blvm_lstm_seq_fwd(const float* Wih, const float* Whh, const float
                                  const float* h0, const float* c0, const int32_t* lens, int T, int B, int I, int H,
                                  float* out, float* hn, float* cn, float* reserve, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_rnn(T, B, I, H);
-  if (rc) return rc;
+  BLVM_TRY(check_rnn(T, B, I, H));
   BLVM_REQUIRE(Wih && Whh && bih && bhh && in && out && reserve, "lstm_fwd: null pointer");
   BLVM_REQUIRE(aligned16(reserve) && aligned16(Whh), "lstm_fwd: buffers must be 16-byte aligned");
   BLVM_REQUIRE(B < 65536 && H < 65536, "lstm_fwd: B and H must be below 65536 (packed kernel arguments)");
   LstmReserve rs;
   carve_lstm(reserve, T, B, H, &rs);
   const size_t n = (size_t)T * B, bh = (size_t)B * H;
-  rc = gemm_f32(0, 0, (int)n, 4 * H, I, in, I, Wih, I, rs.XG, 4 * H, bih, 0, 0.f, nullptr, 0, 0, 1, s);
-  if (rc) return rc;
-  if (h0) BLVM_HIP(hipMemcpyAsync(rs.Hs, h0, sizeof(float) * bh, hipMemcpyDeviceToDevice, s));
-  else BLVM_HIP(hipMemsetAsync(rs.Hs, 0, sizeof(float) * bh, s));
-  if (c0) BLVM_HIP(hipMemcpyAsync(rs.Cs, c0, sizeof(float) * bh, hipMemcpyDeviceToDevice, s));
-  else BLVM_HIP(hipMemsetAsync(rs.Cs, 0, sizeof(float) * bh, s));
+  BLVM_TRY(gemm_f32(0, 0, (int)n, 4 * H, I, in, I, Wih, I, rs.XG, 4 * H, bih, 0, 0.f, nullptr, 0, 0, 1, s));
+  BLVM_HIP(copy_or_zero(rs.Hs, h0, sizeof(float) * bh, s));
+  BLVM_HIP(copy_or_zero(rs.Cs, c0, sizeof(float) * bh, s));
   const OpType seq_ot = seq_persistent(T, B) ? pchain_optype(B) : OP_F32;  // 16-bit operand mode of the persistent path
   T16PackScope pack_scope(seq_ot, s);
-  rc = t16_pack_rows(Whh, H, 4 * H, H, rs.WhhP, s);  // operand layout of the chain (once per sequence)
-  if (rc) return rc;
-  rc = pack_scope.flush();
-  if (rc) return rc;
+  BLVM_TRY(t16_pack_rows(Whh, H, 4 * H, H, rs.WhhP, s));  // operand layout of the chain (once per sequence)
+  BLVM_TRY(pack_scope.flush());
   if (seq_persistent(T, B) && (seq_regs_mask() & 1) && seq_regs_applies(H, 4 * H, H, B, 4)) {
     // one persistent launch with the workgroup's weight slice in registers (seqchain.hip)
     const long xH = (long)((B + 15) / 16) * 16 * H;
     SeqLstmFwd q{rs.H16, rs.WhhP, bhh, rs.XG, lens, rs.Hs, rs.Cs, out, rs.GATES, T, B, H, seq_ot, {}};
-    rc = pchain_ctl(&q.ctl.dev, &q.ctl.host, &q.ctl.epoch);
-    if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(rs.H16 + xH, sizeof(float) * (size_t)T * xH, s));
-    rc = pchain_rows_to_t16(rs.Hs, H, B, H, rs.H16, s);
-    if (rc) return rc;
-    rc = seq_lstm_fwd(q, s);
-    if (rc) return rc;
-    if (hn) BLVM_HIP(hipMemcpyAsync(hn, rs.Hs + T * bh, sizeof(float) * bh, hipMemcpyDeviceToDevice, s));
-    if (cn) BLVM_HIP(hipMemcpyAsync(cn, rs.Cs + T * bh, sizeof(float) * bh, hipMemcpyDeviceToDevice, s));
-    return BLVM_OK;
-  }
-  if (seq_persistent(T, B)) {
+    BLVM_TRY(pchain_rows_to_t16(rs.Hs, H, B, H, rs.H16, s));
+    BLVM_TRY(seq_lstm_fwd(q, s));
+  } else if (seq_persistent(T, B)) {
     // one persistent launch for the whole sequence (pchain.hip): one link per step — the hidden projection with the gate math
     using namespace pchain;
     const int rt = (B + 15) / 16, ctH = H / 16;
     const long sH = (long)bh, s4H = 4 * sH, xH = (long)rt * 16 * H;
     Builder bld;
-    bld.p.ot = seq_ot; bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 4;
-    bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = 1;
+    bld.begin(seq_ot, T, B, 4, false, 1);
     Desc& d = bld.add(K_LSTMS, ctH, 0, range_for(ctH * rt, device_cus() & ~7), H, 0, 0, T);
     bld.ptr(d, LSTMS_H16, {rs.H16, xH}); bld.ptr(d, LSTMS_WHH, rs.WhhP); bld.ptr(d, LSTMS_BHH, bhh); bld.ptr(d, LSTMS_XG, {rs.XG, s4H}); bld.ptr(d, LSTMS_LENS, lens);
     bld.ptr(d, LSTMS_HPREV, {rs.Hs, sH}); bld.ptr(d, LSTMS_HNEXT, {rs.Hs + sH, sH}); bld.ptr(d, LSTMS_HNEXT16, {rs.H16 + xH, xH}); bld.ptr(d, LSTMS_CPREV, {rs.Cs, sH});
     bld.ptr(d, LSTMS_CNEXT, {rs.Cs + sH, sH}); bld.ptr(d, LSTMS_OUT, {out, sH}); bld.ptr(d, LSTMS_GATES, {rs.GATES, s4H}); d.ld[LD_OUT] = H; d.n16[N16_OUT] = ctH;
     d.i[LSTMS_I_H] = H;
-    rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-    if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(rs.H16 + xH, sizeof(float) * (size_t)T * xH, s));
-    rc = pchain_rows_to_t16(rs.Hs, H, B, H, rs.H16, s);
-    if (rc) return rc;
-    rc = pchain_launch(bld.p, s);
-    if (rc) return rc;
-    if (hn) BLVM_HIP(hipMemcpyAsync(hn, rs.Hs + T * bh, sizeof(float) * bh, hipMemcpyDeviceToDevice, s));
-    if (cn) BLVM_HIP(hipMemcpyAsync(cn, rs.Cs + T * bh, sizeof(float) * bh, hipMemcpyDeviceToDevice, s));
-    return BLVM_OK;
-  }
-  const int nw = pick_nw(H, 4);
-  const dim3 grid(H / 16, (B + 15) / 16);
-  for (int t = 0; t < T; ++t) {
-    const float *hp = rs.Hs + t * bh, *cp = rs.Cs + t * bh, *xg_t = rs.XG + (size_t)t * B * 4 * H;
-    float *hnx = rs.Hs + (t + 1) * bh, *cnx = rs.Cs + (t + 1) * bh, *out_t = out + t * bh, *gates_t = rs.GATES + (size_t)t * B * 4 * H;
-    const unsigned b_h = (unsigned)B | ((unsigned)H << 16);
-    if (nw == 16) hipLaunchKernelGGL((lstm_fwd_kernel<16>), grid, dim3(1024), 0, s, hp, cp, (const float*)rs.WhhP, bhh, xg_t, lens, b_h, t, hnx, cnx, out_t, gates_t);
-    else if (nw == 8) hipLaunchKernelGGL((lstm_fwd_kernel<8>), grid, dim3(512), 0, s, hp, cp, (const float*)rs.WhhP, bhh, xg_t, lens, b_h, t, hnx, cnx, out_t, gates_t);
-    else hipLaunchKernelGGL((lstm_fwd_kernel<4>), grid, dim3(256), 0, s, hp, cp, (const float*)rs.WhhP, bhh, xg_t, lens, b_h, t, hnx, cnx, out_t, gates_t);
+    BLVM_TRY(pchain_rows_to_t16(rs.Hs, H, B, H, rs.H16, s));
+    BLVM_TRY(pchain_launch(bld, "lstm_fwd", s));
+  } else {
+    const int nw = pick_nw(H, 4);
+    const dim3 grid(H / 16, (B + 15) / 16);
+    for (int t = 0; t < T; ++t) {
+      const float *hp = rs.Hs + t * bh, *cp = rs.Cs + t * bh, *xg_t = rs.XG + (size_t)t * B * 4 * H;
+      float *hnx = rs.Hs + (t + 1) * bh, *cnx = rs.Cs + (t + 1) * bh, *out_t = out + t * bh, *gates_t = rs.GATES + (size_t)t * B * 4 * H;
+      const unsigned b_h = (unsigned)B | ((unsigned)H << 16);
+      LAUNCH_NW(lstm_fwd_kernel<NW_>, nw, grid, s, hp, cp, (const float*)rs.WhhP, bhh, xg_t, lens, b_h, t, hnx, cnx, out_t, gates_t);
+    }
   }
   BLVM_CHECK_LAUNCH("lstm_seq_fwd");
   if (hn) BLVM_HIP(hipMemcpyAsync(hn, rs.Hs + T * bh, sizeof(float) * bh, hipMemcpyDeviceToDevice, s));
@@ -428,8 +394,7 @@ extern "C" int blvm_lstm_seq_bwd(const float* Wih, const float* Whh, const float
                                  const float* d_out, int T, int B, int I, int H, float* d_in, float* d_h0, float* d_c0,
                                  float* dWih, float* dWhh, float* dbih, float* dbhh, float* workspace, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_rnn(T, B, I, H);
-  if (rc) return rc;
+  BLVM_TRY(check_rnn(T, B, I, H));
   BLVM_REQUIRE(Wih && Whh && in && reserve && d_out && workspace, "lstm_bwd: null pointer");
   BLVM_REQUIRE(aligned16(reserve) && aligned16(workspace), "lstm_bwd: buffers must be 16-byte aligned");
   BLVM_REQUIRE(B < 65536 && H < 65536, "lstm_bwd: B and H must be below 65536 (packed kernel arguments)");
@@ -440,65 +405,52 @@ extern "C" int blvm_lstm_seq_bwd(const float* Wih, const float* Whh, const float
   const size_t n = (size_t)T * B, bh = (size_t)B * H;
   const OpType seq_ot = seq_persistent(T, B) ? pchain_optype(B) : OP_F32;  // 16-bit operand mode of the persistent path
   T16PackScope pack_scope(seq_ot, s);
-  rc = t16_pack_transposed(Whh, H, 4 * H, H, ws.WhhT, s);
-  if (rc) return rc;
-  rc = pack_scope.flush();
-  if (rc) return rc;
+  BLVM_TRY(t16_pack_transposed(Whh, H, 4 * H, H, ws.WhhT, s));
+  BLVM_TRY(pack_scope.flush());
   BLVM_HIP(hipMemsetAsync(ws.DC, 0, sizeof(float) * bh, s));
   if (seq_persistent(T, B) && (seq_regs_mask() & 2) && 4 * H <= kSeqRegsMaxKBwd && seq_regs_applies(H, 4 * H, H, B, 4)) {
     const long x4H = (long)((B + 15) / 16) * 16 * 4 * H;
     SeqLstmBwd q{ws.DG16, ws.WhhT, d_out, rs.GATES, rs.Cs, ws.DC, ws.DG, d_h0 ? d_h0 : ws.DC, T, B, H, d_h0 ? T + 1 : T, seq_ot, {}};
-    rc = pchain_ctl(&q.ctl.dev, &q.ctl.host, &q.ctl.epoch);
-    if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(ws.DG16, sizeof(float) * (size_t)T * x4H, s));
-    rc = seq_lstm_bwd(q, s);
-    if (rc) return rc;
+    BLVM_TRY(seq_lstm_bwd(q, s));
   } else if (seq_persistent(T, B)) {
     using namespace pchain;
     const int rt = (B + 15) / 16, ctH = H / 16;
     const long sH = (long)bh, s4H = 4 * sH, x4H = (long)rt * 16 * 4 * H;
     Builder bld;
-    bld.p.ot = seq_ot; bld.p.S = d_h0 ? T + 1 : T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 1;
-    bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = 1;
+    bld.begin(seq_ot, d_h0 ? T + 1 : T, B, 1, true, 1);
     Desc& d = bld.add(K_LSTMSB, ctH, 0, range_for(ctH * rt, device_cus() & ~7), 4 * H, 0, 0, T + 1);
     // step s handles t = T-1-s: time-indexed slabs start at the last step and walk backwards; the T16 slabs are indexed by s
     bld.ptr(d, LSTMSB_DG16_IN, {ws.DG16 - x4H, x4H}); bld.ptr(d, LSTMSB_WHHT, ws.WhhT); bld.ptr(d, LSTMSB_DOUT, rev(d_out, sH, T - 1));
     bld.ptr(d, LSTMSB_GATES, rev(rs.GATES, s4H, T - 1)); bld.ptr(d, LSTMSB_CS, rev(rs.Cs, sH, T - 1)); bld.ptr(d, LSTMSB_DC, ws.DC);
     bld.ptr(d, LSTMSB_DG, rev(ws.DG, s4H, T - 1)); bld.ptr(d, LSTMSB_DG16, {ws.DG16, x4H}); bld.ptr(d, LSTMSB_DH0, d_h0 ? d_h0 : ws.DC); d.ld[LD_OUT] = 4 * H;
     d.n16[N16_OUT] = 4 * ctH; d.n16[LSTMSB_N16_T] = T; d.i[LSTMSB_I_H] = H;
-    rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-    if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(ws.DG16, sizeof(float) * (size_t)T * x4H, s));
-    rc = pchain_launch(bld.p, s);
-    if (rc) return rc;
+    BLVM_TRY(pchain_launch(bld, "lstm_bwd", s));
   } else {
-  const int nw = pick_nw(4 * H, 1);
-  const dim3 grid(H / 16, (B + 15) / 16);
-  // scratch for dh0 when the caller does not want it
-  for (int st = T - 1; st >= -1; --st) {
-    const unsigned has = (st < T - 1 ? 1u : 0u) | (st >= 0 ? 2u : 0u);
-    const int sg = st >= 0 ? st : 0;
-    const float* DGn = ws.DG + (size_t)(st + 1 < T ? st + 1 : 0) * B * 4 * H;
-    const float *dout_s = d_out + sg * bh, *gates_s = rs.GATES + (size_t)sg * B * 4 * H, *c_s = rs.Cs + sg * bh;
-    float* DG_s = ws.DG + (size_t)sg * B * 4 * H;
-    const unsigned b_h = (unsigned)B | ((unsigned)H << 16);
-    if (st == -1 && d_h0 == nullptr) break;
-    if (nw == 16) hipLaunchKernelGGL((lstm_bwd_kernel<16>), grid, dim3(1024), 0, s, DGn, (const float*)ws.WhhT, dout_s, gates_s, c_s, ws.DC, b_h, has, DG_s, d_h0);
-    else if (nw == 8) hipLaunchKernelGGL((lstm_bwd_kernel<8>), grid, dim3(512), 0, s, DGn, (const float*)ws.WhhT, dout_s, gates_s, c_s, ws.DC, b_h, has, DG_s, d_h0);
-    else hipLaunchKernelGGL((lstm_bwd_kernel<4>), grid, dim3(256), 0, s, DGn, (const float*)ws.WhhT, dout_s, gates_s, c_s, ws.DC, b_h, has, DG_s, d_h0);
-  }
+    const int nw = pick_nw(4 * H, 1);
+    const dim3 grid(H / 16, (B + 15) / 16);
+    for (int st = T - 1; st >= -1; --st) {
+      const unsigned has = (st < T - 1 ? 1u : 0u) | (st >= 0 ? 2u : 0u);
+      const int sg = st >= 0 ? st : 0;
+      const float* DGn = ws.DG + (size_t)(st + 1 < T ? st + 1 : 0) * B * 4 * H;
+      const float *dout_s = d_out + sg * bh, *gates_s = rs.GATES + (size_t)sg * B * 4 * H, *c_s = rs.Cs + sg * bh;
+      float* DG_s = ws.DG + (size_t)sg * B * 4 * H;
+      const unsigned b_h = (unsigned)B | ((unsigned)H << 16);
+      if (st == -1 && d_h0 == nullptr) break;
+      LAUNCH_NW(lstm_bwd_kernel<NW_>, nw, grid, s, DGn, (const float*)ws.WhhT, dout_s, gates_s, c_s, ws.DC, b_h, has, DG_s, d_h0);
+    }
   }
   BLVM_CHECK_LAUNCH("lstm_seq_bwd");
   if (d_c0) BLVM_HIP(hipMemcpyAsync(d_c0, ws.DC, sizeof(float) * bh, hipMemcpyDeviceToDevice, s));
   if (d_in) {
-    rc = gemm_f32(0, 1, (int)n, I, 4 * H, ws.DG, 4 * H, Wih, I, d_in, I, nullptr, 0, 0.f, nullptr, 0, 0, 1, s);
-    if (rc) return rc;
+    BLVM_TRY(gemm_f32(0, 1, (int)n, I, 4 * H, ws.DG, 4 * H, Wih, I, d_in, I, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
   }
   // weight + bias gradients: the bias sums ride on the weight-gradient GEMMs (gemm.hip: column sums of the staged D tiles)
-  if (dWih) { rc = gemm_f32(1, 1, 4 * H, I, (int)n, ws.DG, 4 * H, in, I, dWih, I, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(4 * H, I, (int)n), s, dbih); if (rc) return rc; }
-  else if (dbih) { rc = colsum_f32((int)n, 4 * H, ws.DG, 4 * H, dbih, 1, s); if (rc) return rc; }
-  if (dWhh) { rc = gemm_f32(1, 1, 4 * H, H, (int)n, ws.DG, 4 * H, rs.Hs, H, dWhh, H, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(4 * H, H, (int)n), s, dbhh); if (rc) return rc; }
-  else if (dbhh) { rc = colsum_f32((int)n, 4 * H, ws.DG, 4 * H, dbhh, 1, s); if (rc) return rc; }
+  if (dWih) BLVM_TRY(gemm_f32(1, 1, 4 * H, I, (int)n, ws.DG, 4 * H, in, I, dWih, I, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(4 * H, I, (int)n), s, dbih));
+  else if (dbih) BLVM_TRY(colsum_f32((int)n, 4 * H, ws.DG, 4 * H, dbih, 1, s));
+  if (dWhh) BLVM_TRY(gemm_f32(1, 1, 4 * H, H, (int)n, ws.DG, 4 * H, rs.Hs, H, dWhh, H, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(4 * H, H, (int)n), s, dbhh));
+  else if (dbhh) BLVM_TRY(colsum_f32((int)n, 4 * H, ws.DG, 4 * H, dbhh, 1, s));
   return BLVM_OK;
 }
 
@@ -510,8 +462,7 @@ extern "C" int blvm_gru_seq_fwd(const float* Wih, const float* Whh, const float*
                                 int ld_in, const float* h0, const int32_t* lens, int reverse, int T, int B, int I, int R,
                                 float* out, long long out_ts, int out_ld, float* hn, float* reserve, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_rnn(T, B, I, R);
-  if (rc) return rc;
+  BLVM_TRY(check_rnn(T, B, I, R));
   BLVM_REQUIRE(Wih && Whh && bih && bhh && in && out && reserve, "gru_fwd: null pointer");
   BLVM_REQUIRE(!reverse || lens, "gru_fwd: reverse needs lens");
   BLVM_REQUIRE(aligned16(reserve) && aligned16(Whh), "gru_fwd: buffers must be 16-byte aligned");
@@ -519,61 +470,42 @@ extern "C" int blvm_gru_seq_fwd(const float* Wih, const float* Whh, const float*
   GruReserve rs;
   carve_gru(reserve, T, B, R, &rs);
   const size_t n = (size_t)T * B, br = (size_t)B * R;
-  rc = gemm_f32(0, 0, (int)n, 3 * R, I, in, ld_in, Wih, I, rs.XG, 3 * R, bih, 0, 0.f, nullptr, 0, 0, 1, s);
-  if (rc) return rc;
-  if (h0) BLVM_HIP(hipMemcpyAsync(rs.Hs, h0, sizeof(float) * br, hipMemcpyDeviceToDevice, s));
-  else BLVM_HIP(hipMemsetAsync(rs.Hs, 0, sizeof(float) * br, s));
+  BLVM_TRY(gemm_f32(0, 0, (int)n, 3 * R, I, in, ld_in, Wih, I, rs.XG, 3 * R, bih, 0, 0.f, nullptr, 0, 0, 1, s));
+  BLVM_HIP(copy_or_zero(rs.Hs, h0, sizeof(float) * br, s));
   const OpType seq_ot = seq_persistent(T, B) ? pchain_optype(B) : OP_F32;  // 16-bit operand mode of the persistent path
   T16PackScope pack_scope(seq_ot, s);
-  rc = t16_pack_rows(Whh, R, 3 * R, R, rs.WhhP, s);  // operand layout of the chain (once per sequence)
-  if (rc) return rc;
-  rc = pack_scope.flush();
-  if (rc) return rc;
+  BLVM_TRY(t16_pack_rows(Whh, R, 3 * R, R, rs.WhhP, s));  // operand layout of the chain (once per sequence)
+  BLVM_TRY(pack_scope.flush());
   if (seq_persistent(T, B) && (seq_regs_mask() & 1) && seq_regs_applies(R, 3 * R, R, B, 3)) {
     const long xR = (long)((B + 15) / 16) * 16 * R;
     SeqGruFwd q{rs.H16, rs.WhhP, bhh, rs.XG, lens, rs.Hs, out, rs.RG, rs.UG, rs.NG, rs.GHN, (long)out_ts, out_ld, T, B, R, reverse ? 1 : 0, seq_ot, {}};
-    rc = pchain_ctl(&q.ctl.dev, &q.ctl.host, &q.ctl.epoch);
-    if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(rs.H16 + xR, sizeof(float) * (size_t)T * xR, s));
-    rc = pchain_rows_to_t16(rs.Hs, R, B, R, rs.H16, s);
-    if (rc) return rc;
-    rc = seq_gru_fwd(q, s);
-    if (rc) return rc;
-    if (hn) BLVM_HIP(hipMemcpyAsync(hn, rs.Hs + T * br, sizeof(float) * br, hipMemcpyDeviceToDevice, s));
-    return BLVM_OK;
-  }
-  if (seq_persistent(T, B)) {
+    BLVM_TRY(pchain_rows_to_t16(rs.Hs, R, B, R, rs.H16, s));
+    BLVM_TRY(seq_gru_fwd(q, s));
+  } else if (seq_persistent(T, B)) {
     using namespace pchain;
     BLVM_REQUIRE(out_ts >= 0 && out_ts < (1ll << 31), "gru_fwd: output step stride out of range");
     const int rt = (B + 15) / 16, ctR = R / 16;
     const long sR = (long)br, xR = (long)rt * 16 * R;
     Builder bld;
-    bld.p.ot = seq_ot; bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 3;
-    bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = 1;
+    bld.begin(seq_ot, T, B, 3, false, 1);
     Desc& d = bld.add(K_GRUS, ctR, 0, range_for(ctR * rt, device_cus() & ~7), R, 0, 0, T);
     bld.ptr(d, GRUS_H16, {rs.H16, xR}); bld.ptr(d, GRUS_WHH, rs.WhhP); bld.ptr(d, GRUS_BHH, bhh); bld.ptr(d, GRUS_XG, rs.XG); bld.ptr(d, GRUS_LENS, lens);
     bld.ptr(d, GRUS_HPREV, {rs.Hs, sR}); bld.ptr(d, GRUS_HNEXT, {rs.Hs + sR, sR}); bld.ptr(d, GRUS_HNEXT16, {rs.H16 + xR, xR}); bld.ptr(d, GRUS_OUT, out);
     bld.ptr(d, GRUS_RG, {rs.RG, sR}); bld.ptr(d, GRUS_UG, {rs.UG, sR}); bld.ptr(d, GRUS_NG, {rs.NG, sR}); bld.ptr(d, GRUS_GHN, {rs.GHN, sR}); d.ld[LD_OUT] = R;
     d.n16[N16_OUT] = ctR; d.i[GRUS_I_R] = R; d.i[GRUS_I_REVERSE] = reverse ? 1 : 0; d.i[GRUS_I_OUT_TS] = (int)out_ts; d.i[GRUS_I_OUT_LD] = out_ld;
-    rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-    if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(rs.H16 + xR, sizeof(float) * (size_t)T * xR, s));
-    rc = pchain_rows_to_t16(rs.Hs, R, B, R, rs.H16, s);
-    if (rc) return rc;
-    rc = pchain_launch(bld.p, s);
-    if (rc) return rc;
-    if (hn) BLVM_HIP(hipMemcpyAsync(hn, rs.Hs + T * br, sizeof(float) * br, hipMemcpyDeviceToDevice, s));
-    return BLVM_OK;
-  }
-  const int nw = pick_nw(R, 3);
-  const dim3 grid(R / 16, (B + 15) / 16);
-  for (int j = 0; j < T; ++j) {
-    const float* hp = rs.Hs + j * br;
-    float *hnx = rs.Hs + (j + 1) * br, *rg_j = rs.RG + j * br, *ug_j = rs.UG + j * br, *ng_j = rs.NG + j * br, *ghn_j = rs.GHN + j * br;
-    const unsigned b_r = (unsigned)B | ((unsigned)R << 16), j_rev = ((unsigned)j << 1) | (reverse ? 1u : 0u);
-    if (nw == 16) hipLaunchKernelGGL((gru_fwd_kernel<16>), grid, dim3(1024), 0, s, hp, (const float*)rs.WhhP, bhh, (const float*)rs.XG, lens, b_r, j_rev, hnx, out, rg_j, ug_j, ng_j, ghn_j, out_ts, out_ld);
-    else if (nw == 8) hipLaunchKernelGGL((gru_fwd_kernel<8>), grid, dim3(512), 0, s, hp, (const float*)rs.WhhP, bhh, (const float*)rs.XG, lens, b_r, j_rev, hnx, out, rg_j, ug_j, ng_j, ghn_j, out_ts, out_ld);
-    else hipLaunchKernelGGL((gru_fwd_kernel<4>), grid, dim3(256), 0, s, hp, (const float*)rs.WhhP, bhh, (const float*)rs.XG, lens, b_r, j_rev, hnx, out, rg_j, ug_j, ng_j, ghn_j, out_ts, out_ld);
+    BLVM_TRY(pchain_rows_to_t16(rs.Hs, R, B, R, rs.H16, s));
+    BLVM_TRY(pchain_launch(bld, "gru_fwd", s));
+  } else {
+    const int nw = pick_nw(R, 3);
+    const dim3 grid(R / 16, (B + 15) / 16);
+    for (int j = 0; j < T; ++j) {
+      const float* hp = rs.Hs + j * br;
+      float *hnx = rs.Hs + (j + 1) * br, *rg_j = rs.RG + j * br, *ug_j = rs.UG + j * br, *ng_j = rs.NG + j * br, *ghn_j = rs.GHN + j * br;
+      const unsigned b_r = (unsigned)B | ((unsigned)R << 16), j_rev = ((unsigned)j << 1) | (reverse ? 1u : 0u);
+      LAUNCH_NW(gru_fwd_kernel<NW_>, nw, grid, s, hp, (const float*)rs.WhhP, bhh, (const float*)rs.XG, lens, b_r, j_rev, hnx, out, rg_j, ug_j, ng_j, ghn_j, out_ts, out_ld);
+    }
   }
   BLVM_CHECK_LAUNCH("gru_seq_fwd");
   if (hn) BLVM_HIP(hipMemcpyAsync(hn, rs.Hs + T * br, sizeof(float) * br, hipMemcpyDeviceToDevice, s));
@@ -585,8 +517,7 @@ extern "C" int blvm_gru_seq_bwd(const float* Wih, const float* Whh, const float*
                                 int T, int B, int I, int R, float* d_in, int ld_din, int accumulate_din, float* d_h0,
                                 float* dWih, float* dWhh, float* dbih, float* dbhh, float* workspace, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_rnn(T, B, I, R);
-  if (rc) return rc;
+  BLVM_TRY(check_rnn(T, B, I, R));
   BLVM_REQUIRE(Wih && Whh && in && reserve && d_out && workspace, "gru_bwd: null pointer");
   BLVM_REQUIRE(!reverse || lens, "gru_bwd: reverse needs lens");
   BLVM_REQUIRE(B < 65536 && R < 65536, "gru_bwd: B and R must be below 65536 (packed kernel arguments)");
@@ -598,28 +529,22 @@ extern "C" int blvm_gru_seq_bwd(const float* Wih, const float* Whh, const float*
   const size_t n = (size_t)T * B, br = (size_t)B * R;
   const OpType seq_ot = seq_persistent(T, B) ? pchain_optype(B) : OP_F32;  // 16-bit operand mode of the persistent path
   T16PackScope pack_scope(seq_ot, s);
-  rc = t16_pack_transposed(Whh, R, 3 * R, R, ws.WhhT, s);
-  if (rc) return rc;
-  rc = pack_scope.flush();
-  if (rc) return rc;
+  BLVM_TRY(t16_pack_transposed(Whh, R, 3 * R, R, ws.WhhT, s));
+  BLVM_TRY(pack_scope.flush());
   BLVM_HIP(hipMemsetAsync(ws.G, 0, sizeof(float) * br, s));
   if (seq_persistent(T, B) && (seq_regs_mask() & 2) && 3 * R <= kSeqRegsMaxKBwd && seq_regs_applies(R, 3 * R, R, B, 3)) {
     const long x3R = (long)((B + 15) / 16) * 16 * 3 * R;
     SeqGruBwd q{ws.DGH16, ws.WhhT, d_out, rs.RG, rs.UG, rs.NG, rs.GHN, rs.Hs, lens, ws.G, ws.DGI, ws.DGH, d_h0 ? d_h0 : ws.G, (long)out_ts, out_ld, T, B, R,
                 reverse ? 1 : 0, d_h0 ? T + 1 : T, seq_ot, {}};
-    rc = pchain_ctl(&q.ctl.dev, &q.ctl.host, &q.ctl.epoch);
-    if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(ws.DGH16, sizeof(float) * (size_t)T * x3R, s));
-    rc = seq_gru_bwd(q, s);
-    if (rc) return rc;
+    BLVM_TRY(seq_gru_bwd(q, s));
   } else if (seq_persistent(T, B)) {
     using namespace pchain;
     BLVM_REQUIRE(out_ts >= 0 && out_ts < (1ll << 31), "gru_bwd: output step stride out of range");
     const int rt = (B + 15) / 16, ctR = R / 16;
     const long sR = (long)br, s3R = 3 * sR, x3R = (long)rt * 16 * 3 * R;
     Builder bld;
-    bld.p.ot = seq_ot; bld.p.S = d_h0 ? T + 1 : T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 1;
-    bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = 1;
+    bld.begin(seq_ot, d_h0 ? T + 1 : T, B, 1, true, 1);
     Desc& d = bld.add(K_GRUSB, ctR, 0, range_for(ctR * rt, device_cus() & ~7), 3 * R, 0, 0, T + 1);
     // step s handles recurrence step j = T-1-s: the saves walk backwards from their last slab; the T16 slabs are indexed by s
     bld.ptr(d, GRUSB_DGH16_IN, {ws.DGH16 - x3R, x3R}); bld.ptr(d, GRUSB_WHHT, ws.WhhT); bld.ptr(d, GRUSB_DOUT, d_out); bld.ptr(d, GRUSB_RG, rev(rs.RG, sR, T - 1));
@@ -628,41 +553,33 @@ extern "C" int blvm_gru_seq_bwd(const float* Wih, const float* Whh, const float*
     bld.ptr(d, GRUSB_DGH, rev(ws.DGH, s3R, T - 1)); bld.ptr(d, GRUSB_DGH16, {ws.DGH16, x3R}); bld.ptr(d, GRUSB_DH0, d_h0 ? d_h0 : ws.G); d.ld[LD_OUT] = 3 * R;
     d.n16[N16_OUT] = 3 * ctR; d.n16[GRUSB_N16_T] = T; d.i[GRUSB_I_R] = R; d.i[GRUSB_I_REVERSE] = reverse ? 1 : 0; d.i[GRUSB_I_OUT_TS] = (int)out_ts;
     d.i[GRUSB_I_OUT_LD] = out_ld;
-    rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-    if (rc) return rc;
     BLVM_HIP(pchain_fill_sentinel(ws.DGH16, sizeof(float) * (size_t)T * x3R, s));
-    rc = pchain_launch(bld.p, s);
-    if (rc) return rc;
+    BLVM_TRY(pchain_launch(bld, "gru_bwd", s));
   } else {
-  const int nw = pick_nw(3 * R, 1);
-  const dim3 grid(R / 16, (B + 15) / 16);
-  for (int j = T - 1; j >= -1; --j) {
-    if (j == -1 && d_h0 == nullptr) break;
-    GruBwdArgs a;
-    a.has_gemm = j < T - 1; a.has_gates = j >= 0;
-    a.DGHn = ws.DGH + (size_t)(j + 1 < T ? j + 1 : 0) * B * 3 * R;
-    a.WhhT = ws.WhhT; a.dout = d_out;
-    const int jg = j >= 0 ? j : 0;
-    a.rg = rs.RG + jg * br; a.ug = rs.UG + jg * br; a.ng = rs.NG + jg * br; a.ghn = rs.GHN + jg * br;
-    a.hprev = rs.Hs + jg * br; a.lens = lens;
-    a.G = ws.G; a.DGI = ws.DGI; a.DGH = ws.DGH + (size_t)jg * B * 3 * R; a.dh0 = d_h0;
-    a.out_ts = out_ts; a.out_ld = out_ld; a.B = B; a.R = R; a.j = jg; a.reverse = reverse;
-    {
+    const int nw = pick_nw(3 * R, 1);
+    const dim3 grid(R / 16, (B + 15) / 16);
+    for (int j = T - 1; j >= -1; --j) {
+      if (j == -1 && d_h0 == nullptr) break;
+      GruBwdArgs a;
+      a.has_gemm = j < T - 1; a.has_gates = j >= 0;
+      a.DGHn = ws.DGH + (size_t)(j + 1 < T ? j + 1 : 0) * B * 3 * R;
+      a.WhhT = ws.WhhT; a.dout = d_out;
+      const int jg = j >= 0 ? j : 0;
+      a.rg = rs.RG + jg * br; a.ug = rs.UG + jg * br; a.ng = rs.NG + jg * br; a.ghn = rs.GHN + jg * br;
+      a.hprev = rs.Hs + jg * br; a.lens = lens;
+      a.G = ws.G; a.DGI = ws.DGI; a.DGH = ws.DGH + (size_t)jg * B * 3 * R; a.dh0 = d_h0;
+      a.out_ts = out_ts; a.out_ld = out_ld; a.B = B; a.R = R; a.j = jg; a.reverse = reverse;
       const unsigned b_r = (unsigned)B | ((unsigned)R << 16), has = (a.has_gemm ? 1u : 0u) | (a.has_gates ? 2u : 0u);
-      if (nw == 16) hipLaunchKernelGGL((gru_bwd_kernel<16>), grid, dim3(1024), 0, s, a.DGHn, a.WhhT, a.G, b_r, has, a);
-      else if (nw == 8) hipLaunchKernelGGL((gru_bwd_kernel<8>), grid, dim3(512), 0, s, a.DGHn, a.WhhT, a.G, b_r, has, a);
-      else hipLaunchKernelGGL((gru_bwd_kernel<4>), grid, dim3(256), 0, s, a.DGHn, a.WhhT, a.G, b_r, has, a);
+      LAUNCH_NW(gru_bwd_kernel<NW_>, nw, grid, s, a.DGHn, a.WhhT, a.G, b_r, has, a);
     }
-  }
   }
   BLVM_CHECK_LAUNCH("gru_seq_bwd");
   if (d_in) {
-    rc = gemm_f32(0, 1, (int)n, I, 3 * R, ws.DGI, 3 * R, Wih, I, d_in, ld_din, nullptr, 0, 0.f, nullptr, 0, accumulate_din, 1, s);
-    if (rc) return rc;
+    BLVM_TRY(gemm_f32(0, 1, (int)n, I, 3 * R, ws.DGI, 3 * R, Wih, I, d_in, ld_din, nullptr, 0, 0.f, nullptr, 0, accumulate_din, 1, s));
   }
-  if (dWih) { rc = gemm_f32(1, 1, 3 * R, I, (int)n, ws.DGI, 3 * R, in, ld_in, dWih, I, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(3 * R, I, (int)n), s, dbih); if (rc) return rc; }
-  else if (dbih) { rc = colsum_f32((int)n, 3 * R, ws.DGI, 3 * R, dbih, 1, s); if (rc) return rc; }
-  if (dWhh) { rc = gemm_f32(1, 1, 3 * R, R, (int)n, ws.DGH, 3 * R, rs.Hs, R, dWhh, R, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(3 * R, R, (int)n), s, dbhh); if (rc) return rc; }
-  else if (dbhh) { rc = colsum_f32((int)n, 3 * R, ws.DGH, 3 * R, dbhh, 1, s); if (rc) return rc; }
+  if (dWih) BLVM_TRY(gemm_f32(1, 1, 3 * R, I, (int)n, ws.DGI, 3 * R, in, ld_in, dWih, I, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(3 * R, I, (int)n), s, dbih));
+  else if (dbih) BLVM_TRY(colsum_f32((int)n, 3 * R, ws.DGI, 3 * R, dbih, 1, s));
+  if (dWhh) BLVM_TRY(gemm_f32(1, 1, 3 * R, R, (int)n, ws.DGH, 3 * R, rs.Hs, R, dWhh, R, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(3 * R, R, (int)n), s, dbhh));
+  else if (dbhh) BLVM_TRY(colsum_f32((int)n, 3 * R, ws.DGH, 3 * R, dbhh, 1, s));
   return BLVM_OK;
 }

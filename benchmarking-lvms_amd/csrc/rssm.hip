@@ -122,62 +122,62 @@ struct RssmReserve {
   float *GIN, *GHb, *RG, *UG, *NG, *Q[3], *P[3], *RAWQ, *RAWP, *MUQR, *XGIN, *XQ;
   float *Wgz, *Wih, *Whh, *Wq[3], *Wp[3], *Wqh, *Wph;  // T16 copies of the weights the forward chain multiplies by
   // persistent forward (B <= kPchainCarveMaxB): T16 copies of every activation a link multiplies, per step [rt*16, width]
-  float *Z16, *H16, *GIN16, *Q16[3], *P16[3], *x16_end;
+  float *Z16, *H16, *GIN16, *Q16[3], *P16[3];
+  size_t x16_bytes;  // from the first piece a launch polls to the end of the T16 copies: sentinel-filled in one go
 };
 size_t carve_rssm(float* base, int T, int B, int H, int Z, RssmReserve* r) {
   const size_t n = (size_t)T * B;
-  size_t off = 0;
-  auto take = [&](size_t cnt) { float* p = base ? base + off : nullptr; off += (cnt + 3) & ~(size_t)3; return p; };
+  Arena ar{base};
   RssmReserve t;
-  t.GIN = take(n * H); t.GHb = take(n * 3 * H);
-  t.RG = take(n * H); t.UG = take(n * H); t.NG = take(n * H);
-  for (int i = 0; i < 3; ++i) t.Q[i] = take(n * H);
-  for (int i = 0; i < 3; ++i) t.P[i] = take(n * H);
-  t.RAWQ = take(n * Z); t.RAWP = take(n * Z); t.MUQR = take(n * Z);
-  t.XGIN = take(n * H); t.XQ = take(n * H);
-  t.Wgz = take((size_t)H * Z); t.Wih = take((size_t)3 * H * H); t.Whh = take((size_t)3 * H * H);
-  for (int i = 0; i < 3; ++i) { t.Wq[i] = take((size_t)H * H); t.Wp[i] = take((size_t)H * H); }
-  t.Wqh = take((size_t)2 * Z * H); t.Wph = take((size_t)2 * Z * H);
+  t.GIN = ar.take(n * H); t.GHb = ar.take(n * 3 * H);
+  t.RG = ar.take(n * H); t.UG = ar.take(n * H); t.NG = ar.take(n * H);
+  for (int i = 0; i < 3; ++i) t.Q[i] = ar.take(n * H);
+  for (int i = 0; i < 3; ++i) t.P[i] = ar.take(n * H);
+  t.RAWQ = ar.take(n * Z); t.RAWP = ar.take(n * Z); t.MUQR = ar.take(n * Z);
+  t.XGIN = ar.take(n * H); t.XQ = ar.take(n * H);
+  t.Wgz = ar.take((size_t)H * Z); t.Wih = ar.take((size_t)3 * H * H); t.Whh = ar.take((size_t)3 * H * H);
+  for (int i = 0; i < 3; ++i) { t.Wq[i] = ar.take((size_t)H * H); t.Wp[i] = ar.take((size_t)H * H); }
+  t.Wqh = ar.take((size_t)2 * Z * H); t.Wph = ar.take((size_t)2 * Z * H);
   t.Z16 = nullptr;
   if (B <= kPchainCarveMaxB) {
     const size_t rows = (size_t)((B + 15) / 16) * 16, m = (size_t)T * rows;
-    t.Z16 = take((m + rows) * Z); t.H16 = take((m + rows) * H); t.GIN16 = take(m * H);
-    for (int i = 0; i < 3; ++i) { t.Q16[i] = take(m * H); t.P16[i] = take(m * H); }
-    t.x16_end = take(0);
+    t.Z16 = ar.take((m + rows) * Z); t.H16 = ar.take((m + rows) * H); t.GIN16 = ar.take(m * H);
+    for (int i = 0; i < 3; ++i) { t.Q16[i] = ar.take(m * H); t.P16[i] = ar.take(m * H); }
+    t.x16_bytes = ar.bytes_from(t.Z16);
   }
   if (r) *r = t;
-  return off;
+  return ar.floats();
 }
 
 struct RssmWs {
   float *gzT, *wihT, *whhT, *qT[3], *pT[3], *qhT, *phT, *DGIN, *DGI, *DGH, *DQH, *DPH, *DQ[3], *DP[3], *G;
   // persistent backward (B <= kPchainCarveMaxB): the running state gradient as per-step slabs [T,B,H] and T16 copies of every
   // gradient a link multiplies, per step [rt*16, width]
-  float *GA, *GB, *DGIN16, *DGI16, *DGH16, *DQH16, *DPH16, *DQ16[3], *DP16[3], *x16_end;
+  float *GA, *GB, *DGIN16, *DGI16, *DGH16, *DQH16, *DPH16, *DQ16[3], *DP16[3];
+  size_t x16_bytes;  // from the first piece a launch polls to the end of the T16 copies: sentinel-filled in one go
 };
 size_t carve_rssm_ws(float* base, int T, int B, int H, int Z, RssmWs* w) {
   const size_t n = (size_t)T * B;
-  size_t off = 0;
-  auto take = [&](size_t cnt) { float* p = base ? base + off : nullptr; off += (cnt + 3) & ~(size_t)3; return p; };
+  Arena ar{base};
   RssmWs t;
-  t.gzT = take((size_t)Z * H); t.wihT = take((size_t)H * 3 * H); t.whhT = take((size_t)H * 3 * H);
-  for (int i = 0; i < 3; ++i) { t.qT[i] = take((size_t)H * H); t.pT[i] = take((size_t)H * H); }
-  t.qhT = take((size_t)H * 2 * Z); t.phT = take((size_t)H * 2 * Z);
-  t.DGIN = take(n * H); t.DGI = take(n * 3 * H); t.DGH = take(n * 3 * H);
-  t.DQH = take(n * 2 * Z); t.DPH = take(n * 2 * Z);
-  for (int i = 0; i < 3; ++i) { t.DQ[i] = take(n * H); t.DP[i] = take(n * H); }
-  t.G = take((size_t)B * H);
+  t.gzT = ar.take((size_t)Z * H); t.wihT = ar.take((size_t)H * 3 * H); t.whhT = ar.take((size_t)H * 3 * H);
+  for (int i = 0; i < 3; ++i) { t.qT[i] = ar.take((size_t)H * H); t.pT[i] = ar.take((size_t)H * H); }
+  t.qhT = ar.take((size_t)H * 2 * Z); t.phT = ar.take((size_t)H * 2 * Z);
+  t.DGIN = ar.take(n * H); t.DGI = ar.take(n * 3 * H); t.DGH = ar.take(n * 3 * H);
+  t.DQH = ar.take(n * 2 * Z); t.DPH = ar.take(n * 2 * Z);
+  for (int i = 0; i < 3; ++i) { t.DQ[i] = ar.take(n * H); t.DP[i] = ar.take(n * H); }
+  t.G = ar.take((size_t)B * H);
   t.GA = nullptr;
   if (B <= kPchainCarveMaxB) {
     const size_t m = (size_t)T * ((B + 15) / 16) * 16;
-    t.GA = take(n * H); t.GB = take(n * H);
-    t.DGIN16 = take(m * H); t.DGI16 = take(m * 3 * H); t.DGH16 = take(m * 3 * H);
-    t.DQH16 = take(m * 2 * Z); t.DPH16 = take(m * 2 * Z);
-    for (int i = 0; i < 3; ++i) { t.DQ16[i] = take(m * H); t.DP16[i] = take(m * H); }
-    t.x16_end = take(0);
+    t.GA = ar.take(n * H); t.GB = ar.take(n * H);
+    t.DGIN16 = ar.take(m * H); t.DGI16 = ar.take(m * 3 * H); t.DGH16 = ar.take(m * 3 * H);
+    t.DQH16 = ar.take(m * 2 * Z); t.DPH16 = ar.take(m * 2 * Z);
+    for (int i = 0; i < 3; ++i) { t.DQ16[i] = ar.take(m * H); t.DP16[i] = ar.take(m * H); }
+    t.x16_bytes = ar.bytes_from(t.GA);
   }
   if (w) *w = t;
-  return off;
+  return ar.floats();
 }
 
 int check_rssm(int T, int B, int H, int Z, int C, int E) {
@@ -201,8 +201,7 @@ extern "C" int blvm_rssm_seq_fwd(const BlvmRssmWeights* w, const float* enc, con
                                  float sd_eps, float* zs, float* hs, float* mu_q, float* sd_q, float* mu_p, float* sd_p,
                                  float* reserve, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_rssm(T, B, H, Z, C, E);
-  if (rc) return rc;
+  BLVM_TRY(check_rssm(T, B, H, Z, C, E));
   BLVM_REQUIRE(w && enc && eps && zs && hs && mu_q && sd_q && mu_p && sd_p && reserve, "rssm_fwd: null pointer");
   BLVM_REQUIRE(C == 0 || ctx != nullptr, "rssm_fwd: context missing");
   BLVM_REQUIRE(mode >= 0 && mode <= 3, "rssm_fwd: mode must be 0 (plain), 1 (residual), 2 (precision-weighted) or 3 (generate: z from the prior)");
@@ -211,32 +210,27 @@ extern "C" int blvm_rssm_seq_fwd(const BlvmRssmWeights* w, const float* enc, con
   carve_rssm(reserve, T, B, H, Z, &rs);
   const size_t n = (size_t)T * B;
   const int ldg = Z + C, ldq = H + E;
-  const float beta = (float)(0.6931471805599453 / (1.0 - (double)sd_eps));
+  const float beta = softplus_beta_of(sd_eps);
   if (C > 0) {
-    rc = gemm_f32(0, 0, (int)n, H, C, ctx, C, w->gin_w + Z, ldg, rs.XGIN, H, w->gin_b, 0, 0.f, nullptr, 0, 0, 1, s);
-    if (rc) return rc;
+    BLVM_TRY(gemm_f32(0, 0, (int)n, H, C, ctx, C, w->gin_w + Z, ldg, rs.XGIN, H, w->gin_b, 0, 0.f, nullptr, 0, 0, 1, s));
   }
-  rc = gemm_f32(0, 0, (int)n, H, E, enc, E, w->post_w[0] + H, ldq, rs.XQ, H, w->post_b[0], 0, 0.f, nullptr, 0, 0, 1, s);
-  if (rc) return rc;
+  BLVM_TRY(gemm_f32(0, 0, (int)n, H, E, enc, E, w->post_w[0] + H, ldq, rs.XQ, H, w->post_b[0], 0, 0.f, nullptr, 0, 0, 1, s));
   // T16 operand copies of the chain's weights (once per sequence): z columns of the GRU input layer, h columns of post_w0
   T16PackScope pack_scope(pchain_optype(B), s);  // 16-bit operand modes: the persistent launch multiplies 16-bit weight packs
-  rc = t16_pack_rows(w->gin_w, ldg, H, Z, rs.Wgz, s); if (rc) return rc;
-  rc = t16_pack_rows(w->gru_wih, H, 3 * H, H, rs.Wih, s); if (rc) return rc;
-  rc = t16_pack_rows(w->gru_whh, H, 3 * H, H, rs.Whh, s); if (rc) return rc;
-  rc = t16_pack_rows(w->post_w[0], ldq, H, H, rs.Wq[0], s); if (rc) return rc;
-  rc = t16_pack_rows(w->prior_w[0], H, H, H, rs.Wp[0], s); if (rc) return rc;
+  BLVM_TRY(t16_pack_rows(w->gin_w, ldg, H, Z, rs.Wgz, s));
+  BLVM_TRY(t16_pack_rows(w->gru_wih, H, 3 * H, H, rs.Wih, s));
+  BLVM_TRY(t16_pack_rows(w->gru_whh, H, 3 * H, H, rs.Whh, s));
+  BLVM_TRY(t16_pack_rows(w->post_w[0], ldq, H, H, rs.Wq[0], s));
+  BLVM_TRY(t16_pack_rows(w->prior_w[0], H, H, H, rs.Wp[0], s));
   for (int k = 1; k < 3; ++k) {
-    rc = t16_pack_rows(w->post_w[k], H, H, H, rs.Wq[k], s); if (rc) return rc;
-    rc = t16_pack_rows(w->prior_w[k], H, H, H, rs.Wp[k], s); if (rc) return rc;
+    BLVM_TRY(t16_pack_rows(w->post_w[k], H, H, H, rs.Wq[k], s));
+    BLVM_TRY(t16_pack_rows(w->prior_w[k], H, H, H, rs.Wp[k], s));
   }
-  rc = t16_pack_rows(w->post_hw, H, 2 * Z, H, rs.Wqh, s); if (rc) return rc;
-  rc = t16_pack_rows(w->prior_hw, H, 2 * Z, H, rs.Wph, s); if (rc) return rc;
-  rc = pack_scope.flush();  // all packs above in one launch
-  if (rc) return rc;
-  if (z0) BLVM_HIP(hipMemcpyAsync(zs, z0, sizeof(float) * (size_t)B * Z, hipMemcpyDeviceToDevice, s));
-  else BLVM_HIP(hipMemsetAsync(zs, 0, sizeof(float) * (size_t)B * Z, s));
-  if (h0) BLVM_HIP(hipMemcpyAsync(hs, h0, sizeof(float) * (size_t)B * H, hipMemcpyDeviceToDevice, s));
-  else BLVM_HIP(hipMemsetAsync(hs, 0, sizeof(float) * (size_t)B * H, s));
+  BLVM_TRY(t16_pack_rows(w->post_hw, H, 2 * Z, H, rs.Wqh, s));
+  BLVM_TRY(t16_pack_rows(w->prior_hw, H, 2 * Z, H, rs.Wph, s));
+  BLVM_TRY(pack_scope.flush());  // all packs above in one launch
+  BLVM_HIP(copy_or_zero(zs, z0, sizeof(float) * (size_t)B * Z, s));
+  BLVM_HIP(copy_or_zero(hs, h0, sizeof(float) * (size_t)B * H, s));
   const int rt = (B + 15) / 16;
   if (pchain_applies(B) && device_cus() >= 32) {
     // Persistent path (pchain.h / pchain.hip): the six links of a step as a program of 10 descriptors, one launch per sequence.
@@ -246,9 +240,7 @@ extern "C" int blvm_rssm_seq_fwd(const BlvmRssmWeights* w, const float* enc, con
     const int r_h = range_for(ctH * rt, cus / 4);              // one H-wide link (or one half of a posterior | prior pair)
     const int r_gh = range_for(3 * ctH * rt, cus - 2 * r_h);   // the hidden projection, beside the GRU input layer
     Builder bld;
-    bld.p.ot = pchain_optype(B);
-    bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 4;
-    bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = r_h;
+    bld.begin(pchain_optype(B), T, B, 4, false, r_h);
     // L1: GRU input layer (z half; the context half is hoisted) | hidden projection of the GRU
     Operands gi, gh;
     gi.p[LIN_A] = {rs.Z16, xZ}; gi.p[LIN_W] = rs.Wgz; gi.p[LIN_BIAS] = C > 0 ? nullptr : w->gin_b; gi.p[LIN_ADD] = {C > 0 ? rs.XGIN : nullptr, sH}; gi.ld[LIN_LD_ADD] = H;
@@ -279,16 +271,13 @@ extern "C" int blvm_rssm_seq_fwd(const BlvmRssmWeights* w, const float* enc, con
       o.f[HEAD_F_INV_BETA] = 1.f / beta; o.f[HEAD_F_SD_EPS] = sd_eps;
       add_desc(bld, K_HEAD, ctZ, 0, range_for(ctZ * rt, 2 * r_h), H, 0, 0, T, o);
     }
-    BLVM_REQUIRE(!bld.overflow, "rssm_fwd: persistent program overflow");
-    rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-    if (rc) return rc;
     // sentinel-fill what the launch polls: the T16 copies, the hidden projection, the states h_1 .. h_T (the GRU link polls words)
-    BLVM_HIP(pchain_fill_sentinel(rs.Z16, (size_t)(reinterpret_cast<char*>(rs.x16_end) - reinterpret_cast<char*>(rs.Z16)), s));
+    BLVM_HIP(pchain_fill_sentinel(rs.Z16, rs.x16_bytes, s));
     BLVM_HIP(pchain_fill_sentinel(rs.GHb, sizeof(float) * n * 3 * H, s));
     BLVM_HIP(pchain_fill_sentinel(hs + sH, sizeof(float) * n * H, s));
-    rc = pchain_rows_to_t16(zs, Z, B, Z, rs.Z16, s); if (rc) return rc;
-    rc = pchain_rows_to_t16(hs, H, B, H, rs.H16, s); if (rc) return rc;
-    return pchain_launch(bld.p, s);
+    BLVM_TRY(pchain_rows_to_t16(zs, Z, B, Z, rs.Z16, s));
+    BLVM_TRY(pchain_rows_to_t16(hs, H, B, H, rs.H16, s));
+    return pchain_launch(bld, "rssm_fwd", s);
   }
   for (int t = 0; t < T; ++t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z, o3 = (size_t)t * B * 3 * H;
@@ -308,9 +297,7 @@ extern "C" int blvm_rssm_seq_fwd(const BlvmRssmWeights* w, const float* enc, con
       const float *gin_t = rs.GIN + oH, *gh_t = rs.GHb + o3;
       float *rg_t = rs.RG + oH, *ug_t = rs.UG + oH, *ng_t = rs.NG + oH;
       const unsigned lda_ldh = (unsigned)H | ((unsigned)H << 16), b_h = (unsigned)B | ((unsigned)H << 16);
-      if (nw == 16) hipLaunchKernelGGL((gru_cell_stage_kernel<16>), grid, dim3(1024), 0, s, gin_t, (const float*)rs.Wih, w->gru_bih, gh_t, hprev, lda_ldh, b_h, H, hnew, H, rg_t, ug_t, ng_t);
-      else if (nw == 8) hipLaunchKernelGGL((gru_cell_stage_kernel<8>), grid, dim3(512), 0, s, gin_t, (const float*)rs.Wih, w->gru_bih, gh_t, hprev, lda_ldh, b_h, H, hnew, H, rg_t, ug_t, ng_t);
-      else hipLaunchKernelGGL((gru_cell_stage_kernel<4>), grid, dim3(256), 0, s, gin_t, (const float*)rs.Wih, w->gru_bih, gh_t, hprev, lda_ldh, b_h, H, hnew, H, rg_t, ug_t, ng_t);
+      LAUNCH_NW(gru_cell_stage_kernel<NW_>, nw, grid, s, gin_t, (const float*)rs.Wih, w->gru_bih, gh_t, hprev, lda_ldh, b_h, H, hnew, H, rg_t, ug_t, ng_t);
     }
     // L3..L5: posterior | prior MLPs on h_t
     l.seg[0] = seg(hnew, H, rs.Wq[0], H, nullptr, rs.XQ + oH, H, nullptr, 0, rs.Q[0] + oH, H, H, H, 1);
@@ -345,8 +332,7 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
                                  float* d_enc, float* d_ctx, float* d_z0, float* d_h0, const BlvmRssmGrads* gr,
                                  float* workspace, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_rssm(T, B, H, Z, C, E);
-  if (rc) return rc;
+  BLVM_TRY(check_rssm(T, B, H, Z, C, E));
   BLVM_REQUIRE(w && enc && eps && zs && hs && mu_q && sd_q && mu_p && sd_p && reserve && d_zs && d_hs && gr && workspace,
                "rssm_bwd: null pointer");
   BLVM_REQUIRE((c_fn == nullptr && c_raw == nullptr) || x_sl != nullptr, "rssm_bwd: KL coefficients need x_sl");
@@ -357,21 +343,20 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
   carve_rssm_ws(workspace, T, B, H, Z, &ws);
   const size_t n = (size_t)T * B, bh = (size_t)B * H, bz = (size_t)B * Z;
   const int ldg = Z + C, ldq = H + E;
-  const float beta = (float)(0.6931471805599453 / (1.0 - (double)sd_eps));
-#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+  const float beta = softplus_beta_of(sd_eps);
   T16PackScope pack_scope(pchain_optype(B), s);  // 16-bit operand modes: the persistent launch multiplies 16-bit weight packs
-  TRY(t16_pack_transposed(w->gin_w, ldg, H, Z, ws.gzT, s));
-  TRY(t16_pack_transposed(w->gru_wih, H, 3 * H, H, ws.wihT, s));
-  TRY(t16_pack_transposed(w->gru_whh, H, 3 * H, H, ws.whhT, s));
-  TRY(t16_pack_transposed(w->post_w[0], ldq, H, H, ws.qT[0], s));
-  TRY(t16_pack_transposed(w->prior_w[0], H, H, H, ws.pT[0], s));
+  BLVM_TRY(t16_pack_transposed(w->gin_w, ldg, H, Z, ws.gzT, s));
+  BLVM_TRY(t16_pack_transposed(w->gru_wih, H, 3 * H, H, ws.wihT, s));
+  BLVM_TRY(t16_pack_transposed(w->gru_whh, H, 3 * H, H, ws.whhT, s));
+  BLVM_TRY(t16_pack_transposed(w->post_w[0], ldq, H, H, ws.qT[0], s));
+  BLVM_TRY(t16_pack_transposed(w->prior_w[0], H, H, H, ws.pT[0], s));
   for (int k = 1; k < 3; ++k) {
-    TRY(t16_pack_transposed(w->post_w[k], H, H, H, ws.qT[k], s));
-    TRY(t16_pack_transposed(w->prior_w[k], H, H, H, ws.pT[k], s));
+    BLVM_TRY(t16_pack_transposed(w->post_w[k], H, H, H, ws.qT[k], s));
+    BLVM_TRY(t16_pack_transposed(w->prior_w[k], H, H, H, ws.pT[k], s));
   }
-  TRY(t16_pack_transposed(w->post_hw, H, 2 * Z, H, ws.qhT, s));
-  TRY(t16_pack_transposed(w->prior_hw, H, 2 * Z, H, ws.phT, s));
-  TRY(pack_scope.flush());
+  BLVM_TRY(t16_pack_transposed(w->post_hw, H, 2 * Z, H, ws.qhT, s));
+  BLVM_TRY(t16_pack_transposed(w->prior_hw, H, 2 * Z, H, ws.phT, s));
+  BLVM_TRY(pack_scope.flush());
   BLVM_HIP(hipMemsetAsync(ws.G, 0, sizeof(float) * bh, s));
   const int rt = (B + 15) / 16;
   const bool persistent = pchain_applies(B) && device_cus() >= 32;
@@ -385,9 +370,7 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
     const long xH = (long)rt * 16 * H, x3H = 3 * xH, x2Z = (long)rt * 16 * 2 * Z;
     const int r_h = range_for(ctH * rt, cus / 4), r_gb = range_for(ctH * rt, cus - 2 * r_h);
     Builder bld;
-    bld.p.ot = pchain_optype(B);
-    bld.p.S = T + 1; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 2;
-    bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = 2 * r_h;
+    bld.begin(pchain_optype(B), T + 1, B, 2, true, 2 * r_h);
     auto last = [&](const float* base, long step) { return rev(base, step, T - 1); };  // slab of t = T-1, walked backwards
     {  // B1: dz_t (direct + through the GRU input layer of step t+1), rsample / combination / KL / softplus heads
       Operands z;
@@ -438,11 +421,8 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
       gb.p[LIN_ORM] = d_h0;
       add_desc(bld, K_LIN, ctH, 2 * r_h, r_gb, 3 * H, DF_ADD_POLLED, T, T + 1, gb);
     }
-    BLVM_REQUIRE(!bld.overflow, "rssm_bwd: persistent program overflow");
-    rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-    if (rc) return rc;
-    BLVM_HIP(pchain_fill_sentinel(ws.GA, (size_t)(reinterpret_cast<char*>(ws.x16_end) - reinterpret_cast<char*>(ws.GA)), s));
-    TRY(pchain_launch(bld.p, s));
+    BLVM_HIP(pchain_fill_sentinel(ws.GA, ws.x16_bytes, s));
+    BLVM_TRY(pchain_launch(bld, "rssm_bwd", s));
   }
   for (int t = T - 1; t >= 0 && !persistent; --t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z, o3 = (size_t)t * B * 3 * H, o2Z = (size_t)t * B * 2 * Z;
@@ -483,9 +463,7 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
       const int nw = pick_nw(H, 2);
       const dim3 grid(H / 16, rt);
       const unsigned b_h = (unsigned)B | ((unsigned)H << 16);
-      if (nw == 16) hipLaunchKernelGGL((rssm_dh_stage_kernel<16>), grid, dim3(1024), 0, s, d.DQ0, d.DP0, d.WqT, d.WpT, d.G, b_h, d);
-      else if (nw == 8) hipLaunchKernelGGL((rssm_dh_stage_kernel<8>), grid, dim3(512), 0, s, d.DQ0, d.DP0, d.WqT, d.WpT, d.G, b_h, d);
-      else hipLaunchKernelGGL((rssm_dh_stage_kernel<4>), grid, dim3(256), 0, s, d.DQ0, d.DP0, d.WqT, d.WpT, d.G, b_h, d);
+      LAUNCH_NW(rssm_dh_stage_kernel<NW_>, nw, grid, s, d.DQ0, d.DP0, d.WqT, d.WpT, d.G, b_h, d);
     }
     // B6: through the GRU input projection to the (ReLU) GRU input layer
     l.nseg = 1;
@@ -510,8 +488,8 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
   BLVM_CHECK_LAUNCH("rssm_seq_bwd tail");
   // batched, state-independent part
   const float* hnew_all = hs + bh;  // h_1..h_T
-  if (d_ctx && C > 0) TRY(gemm_f32(0, 1, (int)n, C, H, ws.DGIN, H, w->gin_w + Z, ldg, d_ctx, C, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
-  if (d_enc) TRY(gemm_f32(0, 1, (int)n, E, H, ws.DQ[0], H, w->post_w[0] + H, ldq, d_enc, E, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
+  if (d_ctx && C > 0) BLVM_TRY(gemm_f32(0, 1, (int)n, C, H, ws.DGIN, H, w->gin_w + Z, ldg, d_ctx, C, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
+  if (d_enc) BLVM_TRY(gemm_f32(0, 1, (int)n, E, H, ws.DQ[0], H, w->post_w[0] + H, ldq, d_enc, E, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
   WgradGroup grp;  // every weight gradient of the sequence: one grouped launch
   grp.add(ws.DGIN, H, H, zs, Z, Z, gr->gin_w, ldg, gr->gin_b);
   if (C > 0) grp.add(ws.DGIN, H, H, ctx, C, C, gr->gin_w ? gr->gin_w + Z : nullptr, ldg);
@@ -526,7 +504,6 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
   }
   grp.add(ws.DQH, 2 * Z, 2 * Z, rs.Q[2], H, H, gr->post_hw, H, gr->post_hb);
   grp.add(ws.DPH, 2 * Z, 2 * Z, rs.P[2], H, H, gr->prior_hw, H, gr->prior_hb);
-  TRY(grp.run(n, s));
-#undef TRY
+  BLVM_TRY(grp.run(n, s));
   return BLVM_OK;
 }

@@ -47,9 +47,10 @@ struct SeqLstmBwd {
 // tile per CU, and a chunk count that was instantiated
 bool seq_regs_applies(int K_fwd, int K_bwd, int hidden, int B, int gates);
 int seq_regs_mask();  // bit 0: forward, bit 1: backward sequences on these kernels
-int seq_gru_fwd(const SeqGruFwd& a, hipStream_t s);
-int seq_gru_bwd(const SeqGruBwd& a, hipStream_t s);
-int seq_lstm_fwd(const SeqLstmFwd& a, hipStream_t s);
-int seq_lstm_bwd(const SeqLstmBwd& a, hipStream_t s);
+// the launchers fill a.ctl themselves (a fresh epoch of the control block, pchain.h pchain_ctl)
+int seq_gru_fwd(SeqGruFwd a, hipStream_t s);
+int seq_gru_bwd(SeqGruBwd a, hipStream_t s);
+int seq_lstm_fwd(SeqLstmFwd a, hipStream_t s);
+int seq_lstm_bwd(SeqLstmBwd a, hipStream_t s);
 
 }  // namespace blvm

@@ -317,25 +317,29 @@ bool seq_regs_applies(int K_fwd, int K_bwd, int hidden, int B, int gates) {
   return (hidden / 16) * ((B + 15) / 16) <= device_cus();
 }
 
-int seq_gru_fwd(const SeqGruFwd& a, hipStream_t s) {
+int seq_gru_fwd(SeqGruFwd a, hipStream_t s) {
+  BLVM_TRY(pchain_ctl(a.ctl));
   const dim3 grid((unsigned)((a.R / 16) * ((a.B + 15) / 16)));
   SEQ_LAUNCH(gru_fwd_kernel, a.R / (NW * 16), a.ot, grid, s, a);
   BLVM_CHECK_LAUNCH("seq_gru_fwd");
   return BLVM_OK;
 }
-int seq_gru_bwd(const SeqGruBwd& a, hipStream_t s) {
+int seq_gru_bwd(SeqGruBwd a, hipStream_t s) {
+  BLVM_TRY(pchain_ctl(a.ctl));
   const dim3 grid((unsigned)((a.R / 16) * ((a.B + 15) / 16)));
   SEQ_LAUNCH(gru_bwd_kernel, 3 * a.R / (NW * 16), a.ot, grid, s, a);
   BLVM_CHECK_LAUNCH("seq_gru_bwd");
   return BLVM_OK;
 }
-int seq_lstm_fwd(const SeqLstmFwd& a, hipStream_t s) {
+int seq_lstm_fwd(SeqLstmFwd a, hipStream_t s) {
+  BLVM_TRY(pchain_ctl(a.ctl));
   const dim3 grid((unsigned)((a.H / 16) * ((a.B + 15) / 16)));
   SEQ_LAUNCH(lstm_fwd_kernel, a.H / (NW * 16), a.ot, grid, s, a);
   BLVM_CHECK_LAUNCH("seq_lstm_fwd");
   return BLVM_OK;
 }
-int seq_lstm_bwd(const SeqLstmBwd& a, hipStream_t s) {
+int seq_lstm_bwd(SeqLstmBwd a, hipStream_t s) {
+  BLVM_TRY(pchain_ctl(a.ctl));
   const dim3 grid((unsigned)((a.H / 16) * ((a.B + 15) / 16)));
   SEQ_LAUNCH(lstm_bwd_kernel, 4 * a.H / (NW * 16), a.ot, grid, s, a);
   BLVM_CHECK_LAUNCH("seq_lstm_bwd");

@@ -17,56 +17,56 @@ namespace {
 
 struct SrnnReserve {
   float *P[3], *Q[3], *XP, *XQ, *RAWP, *RAWQ, *Wp[3], *Wq[3], *Wph, *Wqh;  // W*: T16 weight copies
-  float *Z16, *P16[3], *Q16[3], *x16_end;  // persistent forward (B <= kPchainCarveMaxB): T16 copies of what the links multiply
+  float *Z16, *P16[3], *Q16[3];  // persistent forward (B <= kPchainCarveMaxB): T16 copies of what the links multiply
+  size_t x16_bytes;  // from the first piece a launch polls to the end of the T16 copies: sentinel-filled in one go
 };
 size_t carve_srnn(float* base, int Tp, int B, int H, int Z, SrnnReserve* r) {
   const size_t n = (size_t)Tp * B;
-  size_t off = 0;
-  auto take = [&](size_t cnt) { float* p = base ? base + off : nullptr; off += (cnt + 3) & ~(size_t)3; return p; };
+  Arena ar{base};
   SrnnReserve t;
-  for (int i = 0; i < 3; ++i) t.P[i] = take(n * H);
-  for (int i = 0; i < 3; ++i) t.Q[i] = take(n * H);
-  t.XP = take(n * H); t.XQ = take(n * H);
-  t.RAWP = take(n * Z); t.RAWQ = take(n * Z);
-  t.Wp[0] = take((size_t)H * Z); t.Wq[0] = take((size_t)H * Z);
-  for (int i = 1; i < 3; ++i) { t.Wp[i] = take((size_t)H * H); t.Wq[i] = take((size_t)H * H); }
-  t.Wph = take((size_t)2 * Z * H); t.Wqh = take((size_t)2 * Z * H);
+  for (int i = 0; i < 3; ++i) t.P[i] = ar.take(n * H);
+  for (int i = 0; i < 3; ++i) t.Q[i] = ar.take(n * H);
+  t.XP = ar.take(n * H); t.XQ = ar.take(n * H);
+  t.RAWP = ar.take(n * Z); t.RAWQ = ar.take(n * Z);
+  t.Wp[0] = ar.take((size_t)H * Z); t.Wq[0] = ar.take((size_t)H * Z);
+  for (int i = 1; i < 3; ++i) { t.Wp[i] = ar.take((size_t)H * H); t.Wq[i] = ar.take((size_t)H * H); }
+  t.Wph = ar.take((size_t)2 * Z * H); t.Wqh = ar.take((size_t)2 * Z * H);
   t.Z16 = nullptr;
   if (B <= kPchainCarveMaxB) {
     const size_t rows = (size_t)((B + 15) / 16) * 16, m = (size_t)Tp * rows;
-    t.Z16 = take((m + rows) * Z);
-    for (int i = 0; i < 3; ++i) { t.P16[i] = take(m * H); t.Q16[i] = take(m * H); }
-    t.x16_end = take(0);
+    t.Z16 = ar.take((m + rows) * Z);
+    for (int i = 0; i < 3; ++i) { t.P16[i] = ar.take(m * H); t.Q16[i] = ar.take(m * H); }
+    t.x16_bytes = ar.bytes_from(t.Z16);
   }
   if (r) *r = t;
-  return off;
+  return ar.floats();
 }
 
 struct SrnnWs {
   float *pzT, *qzT, *pT[3], *qT[3], *phT, *qhT, *DPH, *DQH, *DP[3], *DQ[3];
-  float *DZ0, *DPH16, *DQH16, *DP16[3], *DQ16[3], *x16_end;  // persistent backward (B <= kPchainCarveMaxB)
+  float *DZ0, *DPH16, *DQH16, *DP16[3], *DQ16[3];  // persistent backward (B <= kPchainCarveMaxB)
+  size_t x16_bytes;  // from the first piece a launch polls to the end of the T16 copies: sentinel-filled in one go
 };
 size_t carve_srnn_ws(float* base, int Tp, int B, int H, int Z, SrnnWs* w) {
   const size_t n = (size_t)Tp * B;
-  size_t off = 0;
-  auto take = [&](size_t cnt) { float* p = base ? base + off : nullptr; off += (cnt + 3) & ~(size_t)3; return p; };
+  Arena ar{base};
   SrnnWs t;
-  t.pzT = take((size_t)Z * H); t.qzT = take((size_t)Z * H);
+  t.pzT = ar.take((size_t)Z * H); t.qzT = ar.take((size_t)Z * H);
   t.pT[0] = t.qT[0] = nullptr;
-  for (int i = 1; i < 3; ++i) { t.pT[i] = take((size_t)H * H); t.qT[i] = take((size_t)H * H); }
-  t.phT = take((size_t)H * 2 * Z); t.qhT = take((size_t)H * 2 * Z);
-  t.DPH = take(n * 2 * Z); t.DQH = take(n * 2 * Z);
-  for (int i = 0; i < 3; ++i) { t.DP[i] = take(n * H); t.DQ[i] = take(n * H); }
+  for (int i = 1; i < 3; ++i) { t.pT[i] = ar.take((size_t)H * H); t.qT[i] = ar.take((size_t)H * H); }
+  t.phT = ar.take((size_t)H * 2 * Z); t.qhT = ar.take((size_t)H * 2 * Z);
+  t.DPH = ar.take(n * 2 * Z); t.DQH = ar.take(n * 2 * Z);
+  for (int i = 0; i < 3; ++i) { t.DP[i] = ar.take(n * H); t.DQ[i] = ar.take(n * H); }
   t.DZ0 = nullptr;
   if (B <= kPchainCarveMaxB) {
     const size_t m = (size_t)Tp * ((B + 15) / 16) * 16;
-    t.DZ0 = take((size_t)B * Z);
-    t.DPH16 = take(m * 2 * Z); t.DQH16 = take(m * 2 * Z);
-    for (int i = 0; i < 3; ++i) { t.DP16[i] = take(m * H); t.DQ16[i] = take(m * H); }
-    t.x16_end = take(0);
+    t.DZ0 = ar.take((size_t)B * Z);
+    t.DPH16 = ar.take(m * 2 * Z); t.DQH16 = ar.take(m * 2 * Z);
+    for (int i = 0; i < 3; ++i) { t.DP16[i] = ar.take(m * H); t.DQ16[i] = ar.take(m * H); }
+    t.x16_bytes = ar.bytes_from(t.DZ0);
   }
   if (w) *w = t;
-  return off;
+  return ar.floats();
 }
 
 int check_srnn(int Tp, int B, int H, int Z, int R) {
@@ -96,34 +96,29 @@ extern "C" int blvm_srnn_latent_fwd(const BlvmSrnnWeights* w, const float* d, co
                                     float sd_eps, float slope, float* zs, float* mu_q, float* sd_q, float* mu_p,
                                     float* sd_p, float* reserve, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_srnn(Tp, B, H, Z, R);
-  if (rc) return rc;
+  BLVM_TRY(check_srnn(Tp, B, H, Z, R));
   BLVM_REQUIRE(w && d && a && eps && zs && mu_q && sd_q && mu_p && sd_p && reserve, "srnn_fwd: null pointer");
   BLVM_REQUIRE(aligned16(zs) && aligned16(reserve) && aligned16(d) && aligned16(a), "srnn_fwd: buffers must be 16-byte aligned");
   SrnnReserve rs;
   carve_srnn(reserve, Tp, B, H, Z, &rs);
   const size_t n = (size_t)Tp * B;
   const int ldw0 = R + Z;
-  const float beta = (float)(0.6931471805599453 / (1.0 - (double)sd_eps));
+  const float beta = softplus_beta_of(sd_eps);
   // hoisted d / a halves of the two first layers (incl. bias)
-  rc = gemm_f32(0, 0, (int)n, H, R, d, R, w->prior_w[0], ldw0, rs.XP, H, w->prior_b[0], 0, 0.f, nullptr, 0, 0, 1, s);
-  if (rc) return rc;
-  rc = gemm_f32(0, 0, (int)n, H, R, a, R, w->post_w[0], ldw0, rs.XQ, H, w->post_b[0], 0, 0.f, nullptr, 0, 0, 1, s);
-  if (rc) return rc;
+  BLVM_TRY(gemm_f32(0, 0, (int)n, H, R, d, R, w->prior_w[0], ldw0, rs.XP, H, w->prior_b[0], 0, 0.f, nullptr, 0, 0, 1, s));
+  BLVM_TRY(gemm_f32(0, 0, (int)n, H, R, a, R, w->post_w[0], ldw0, rs.XQ, H, w->post_b[0], 0, 0.f, nullptr, 0, 0, 1, s));
   // T16 operand copies of the chain's weights (once per sequence); layer 0: the z columns
   T16PackScope pack_scope(pchain_optype(B), s);  // 16-bit operand modes: the persistent launch multiplies 16-bit weight packs
-  rc = t16_pack_rows(w->prior_w[0] + R, ldw0, H, Z, rs.Wp[0], s); if (rc) return rc;
-  rc = t16_pack_rows(w->post_w[0] + R, ldw0, H, Z, rs.Wq[0], s); if (rc) return rc;
+  BLVM_TRY(t16_pack_rows(w->prior_w[0] + R, ldw0, H, Z, rs.Wp[0], s));
+  BLVM_TRY(t16_pack_rows(w->post_w[0] + R, ldw0, H, Z, rs.Wq[0], s));
   for (int k = 1; k < 3; ++k) {
-    rc = t16_pack_rows(w->prior_w[k], H, H, H, rs.Wp[k], s); if (rc) return rc;
-    rc = t16_pack_rows(w->post_w[k], H, H, H, rs.Wq[k], s); if (rc) return rc;
+    BLVM_TRY(t16_pack_rows(w->prior_w[k], H, H, H, rs.Wp[k], s));
+    BLVM_TRY(t16_pack_rows(w->post_w[k], H, H, H, rs.Wq[k], s));
   }
-  rc = t16_pack_rows(w->prior_hw, H, 2 * Z, H, rs.Wph, s); if (rc) return rc;
-  rc = t16_pack_rows(w->post_hw, H, 2 * Z, H, rs.Wqh, s); if (rc) return rc;
-  rc = pack_scope.flush();  // all packs above in one launch
-  if (rc) return rc;
-  if (z0) BLVM_HIP(hipMemcpyAsync(zs, z0, sizeof(float) * (size_t)B * Z, hipMemcpyDeviceToDevice, s));
-  else BLVM_HIP(hipMemsetAsync(zs, 0, sizeof(float) * (size_t)B * Z, s));
+  BLVM_TRY(t16_pack_rows(w->prior_hw, H, 2 * Z, H, rs.Wph, s));
+  BLVM_TRY(t16_pack_rows(w->post_hw, H, 2 * Z, H, rs.Wqh, s));
+  BLVM_TRY(pack_scope.flush());  // all packs above in one launch
+  BLVM_HIP(copy_or_zero(zs, z0, sizeof(float) * (size_t)B * Z, s));
   const int rt = (B + 15) / 16;
   if (pchain_applies(B) && device_cus() >= 32) {
     // Persistent path (pchain.h / pchain.hip): the four links of a step as a program of 7 descriptors, one launch per sequence
@@ -132,9 +127,7 @@ extern "C" int blvm_srnn_latent_fwd(const BlvmSrnnWeights* w, const float* d, co
     const long sH = (long)B * H, sZ = (long)B * Z, xH = (long)rt * 16 * H, xZ = (long)rt * 16 * Z;
     const int half = range_for(ctH * rt, cus / 2);
     Builder bld;
-    bld.p.ot = pchain_optype(B);
-    bld.p.S = Tp; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 4;
-    bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = half;
+    bld.begin(pchain_optype(B), Tp, B, 4, false, half);
     {  // the three layers of the prior | posterior MLP: one visit per chain and step (the first layer, K = Z, opens the run)
       const SeqLink lp[3] = {{rs.Wp[0], nullptr, rs.P[0], sH, H, rs.P16[0]}, {rs.Wp[1], w->prior_b[1], rs.P[1], sH, H, rs.P16[1]}, {rs.Wp[2], w->prior_b[2], rs.P[2], sH, H, rs.P16[2]}};
       const SeqLink lq[3] = {{rs.Wq[0], nullptr, rs.Q[0], sH, H, rs.Q16[0]}, {rs.Wq[1], w->post_b[1], rs.Q[1], sH, H, rs.Q16[1]}, {rs.Wq[2], w->post_b[2], rs.Q[2], sH, H, rs.Q16[2]}};
@@ -150,13 +143,9 @@ extern "C" int blvm_srnn_latent_fwd(const BlvmSrnnWeights* w, const float* d, co
       o.f[HEAD_F_SD_EPS] = sd_eps;
       add_desc(bld, K_HEAD, ctZ, 0, range_for(ctZ * rt, 2 * half), H, 0, 0, Tp, o);
     }
-    BLVM_REQUIRE(!bld.overflow, "srnn_fwd: persistent program overflow");
-    rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-    if (rc) return rc;
-    BLVM_HIP(pchain_fill_sentinel(rs.Z16, (size_t)(reinterpret_cast<char*>(rs.x16_end) - reinterpret_cast<char*>(rs.Z16)), s));
-    rc = pchain_rows_to_t16(zs, Z, B, Z, rs.Z16, s);
-    if (rc) return rc;
-    return pchain_launch(bld.p, s);
+    BLVM_HIP(pchain_fill_sentinel(rs.Z16, rs.x16_bytes, s));
+    BLVM_TRY(pchain_rows_to_t16(zs, Z, B, Z, rs.Z16, s));
+    return pchain_launch(bld, "srnn_fwd", s);
   }
   for (int t = 0; t < Tp; ++t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z;
@@ -193,8 +182,7 @@ extern "C" int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, co
                                     int H, int Z, int R, int residual_posterior, float sd_eps, float slope, float* d_d,
                                     float* d_a, float* d_z0, const BlvmSrnnGrads* gr, float* workspace, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  int rc = check_srnn(Tp, B, H, Z, R);
-  if (rc) return rc;
+  BLVM_TRY(check_srnn(Tp, B, H, Z, R));
   BLVM_REQUIRE(w && d && a && eps && zs && mu_q && sd_q && mu_p && sd_p && reserve && d_z && workspace && gr, "srnn_bwd: null pointer");
   BLVM_REQUIRE((c_fn == nullptr && c_raw == nullptr) || x_sl != nullptr, "srnn_bwd: KL coefficients need x_sl");
   BLVM_REQUIRE(aligned16(workspace) && aligned16(reserve), "srnn_bwd: buffers must be 16-byte aligned");
@@ -204,18 +192,17 @@ extern "C" int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, co
   carve_srnn_ws(workspace, Tp, B, H, Z, &ws);
   const size_t n = (size_t)Tp * B;
   const int ldw0 = R + Z;
-  const float beta = (float)(0.6931471805599453 / (1.0 - (double)sd_eps));
-#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+  const float beta = softplus_beta_of(sd_eps);
   T16PackScope pack_scope(pchain_optype(B), s);  // 16-bit operand modes: the persistent launch multiplies 16-bit weight packs
-  TRY(t16_pack_transposed(w->prior_w[0] + R, ldw0, H, Z, ws.pzT, s));
-  TRY(t16_pack_transposed(w->post_w[0] + R, ldw0, H, Z, ws.qzT, s));
+  BLVM_TRY(t16_pack_transposed(w->prior_w[0] + R, ldw0, H, Z, ws.pzT, s));
+  BLVM_TRY(t16_pack_transposed(w->post_w[0] + R, ldw0, H, Z, ws.qzT, s));
   for (int k = 1; k < 3; ++k) {
-    TRY(t16_pack_transposed(w->prior_w[k], H, H, H, ws.pT[k], s));
-    TRY(t16_pack_transposed(w->post_w[k], H, H, H, ws.qT[k], s));
+    BLVM_TRY(t16_pack_transposed(w->prior_w[k], H, H, H, ws.pT[k], s));
+    BLVM_TRY(t16_pack_transposed(w->post_w[k], H, H, H, ws.qT[k], s));
   }
-  TRY(t16_pack_transposed(w->prior_hw, H, 2 * Z, H, ws.phT, s));
-  TRY(t16_pack_transposed(w->post_hw, H, 2 * Z, H, ws.qhT, s));
-  TRY(pack_scope.flush());
+  BLVM_TRY(t16_pack_transposed(w->prior_hw, H, 2 * Z, H, ws.phT, s));
+  BLVM_TRY(t16_pack_transposed(w->post_hw, H, 2 * Z, H, ws.qhT, s));
+  BLVM_TRY(pack_scope.flush());
   const int rt = (B + 15) / 16;
   const bool persistent = pchain_applies(B) && device_cus() >= 32;
   if (persistent) {
@@ -225,9 +212,7 @@ extern "C" int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, co
     const long sH = (long)B * H, sZ = (long)B * Z, s2Z = 2 * sZ, xH = (long)rt * 16 * H, x2Z = (long)rt * 16 * 2 * Z;
     const int half = range_for(ctH * rt, cus / 2);
     Builder bld;
-    bld.p.ot = pchain_optype(B);
-    bld.p.S = T + 1; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 2;
-    bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = half;
+    bld.begin(pchain_optype(B), T + 1, B, 2, true, half);
     auto last = [&](const float* base, long step) { return rev(base, step, T - 1); };  // slab of t = T'-1, walked backwards
     {  // B1: dz_t = decoder gradient + the two first layers of step t+1, then rsample / residual / KL / softplus heads
       Operands z;
@@ -255,11 +240,8 @@ extern "C" int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, co
       o.p[LIN_A] = rev(ws.DQ16[0], xH, T); o.p[LIN_W] = ws.qzT; o.p[LIN_ADD] = ws.DZ0; o.ld[LIN_LD_ADD] = Z; o.p[LIN_ORM] = d_z0;
       add_desc(bld, K_LIN, ctZ, half, r_z, H, DF_ADD_POLLED, T, T + 1, o);
     }
-    BLVM_REQUIRE(!bld.overflow, "srnn_bwd: persistent program overflow");
-    rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-    if (rc) return rc;
-    BLVM_HIP(pchain_fill_sentinel(ws.DZ0, (size_t)(reinterpret_cast<char*>(ws.x16_end) - reinterpret_cast<char*>(ws.DZ0)), s));
-    TRY(pchain_launch(bld.p, s));
+    BLVM_HIP(pchain_fill_sentinel(ws.DZ0, ws.x16_bytes, s));
+    BLVM_TRY(pchain_launch(bld, "srnn_bwd", s));
   }
   for (int t = Tp - 1; t >= 0 && !persistent; --t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z, o2Z = (size_t)t * B * 2 * Z;
@@ -298,8 +280,8 @@ extern "C" int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, co
     launch_lin(l, s);
   }
   // batched, state-independent part
-  if (d_d) TRY(gemm_f32(0, 1, (int)n, R, H, ws.DP[0], H, w->prior_w[0], ldw0, d_d, R, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
-  if (d_a) TRY(gemm_f32(0, 1, (int)n, R, H, ws.DQ[0], H, w->post_w[0], ldw0, d_a, R, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
+  if (d_d) BLVM_TRY(gemm_f32(0, 1, (int)n, R, H, ws.DP[0], H, w->prior_w[0], ldw0, d_d, R, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
+  if (d_a) BLVM_TRY(gemm_f32(0, 1, (int)n, R, H, ws.DQ[0], H, w->post_w[0], ldw0, d_a, R, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
   WgradGroup grp;  // every weight gradient of the sequence: one grouped launch
   grp.add(ws.DP[0], H, H, d, R, R, gr->prior_w[0], ldw0);
   grp.add(ws.DP[0], H, H, zs, Z, Z, gr->prior_w[0] ? gr->prior_w[0] + R : nullptr, ldw0, gr->prior_b[0]);
@@ -311,7 +293,6 @@ extern "C" int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, co
   }
   grp.add(ws.DPH, 2 * Z, 2 * Z, rs.P[2], H, H, gr->prior_hw, H, gr->prior_hb);
   grp.add(ws.DQH, 2 * Z, 2 * Z, rs.Q[2], H, H, gr->post_hw, H, gr->post_hb);
-  TRY(grp.run(n, s));
-#undef TRY
+  BLVM_TRY(grp.run(n, s));
   return BLVM_OK;
 }

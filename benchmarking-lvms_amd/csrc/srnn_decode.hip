@@ -17,35 +17,33 @@ constexpr int SD_F = 30, SD_K = 10;  // DMoL head: 3 * num_mix parameters per sa
 struct SdPack { size_t enc[3], wih, whh, prior[3], prior_h, dec[3], total; };
 SdPack sd_pack_layout(int S, int H, int Z, int R) {
   SdPack p;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o += (n + 3) & ~(size_t)3; return at; };
-  p.enc[0] = take((size_t)H * S); p.enc[1] = take((size_t)H * H); p.enc[2] = take((size_t)H * H);
-  p.wih = take((size_t)3 * R * H); p.whh = take((size_t)3 * R * R);
-  p.prior[0] = take((size_t)H * (R + Z)); p.prior[1] = take((size_t)H * H); p.prior[2] = take((size_t)H * H);
-  p.prior_h = take((size_t)2 * Z * H);
-  p.dec[0] = take((size_t)H * (Z + R)); p.dec[1] = take((size_t)H * H); p.dec[2] = take((size_t)S * SD_F * H);
-  p.total = o;
+  Arena ar;
+  p.enc[0] = ar.take_off((size_t)H * S); p.enc[1] = ar.take_off((size_t)H * H); p.enc[2] = ar.take_off((size_t)H * H);
+  p.wih = ar.take_off((size_t)3 * R * H); p.whh = ar.take_off((size_t)3 * R * R);
+  p.prior[0] = ar.take_off((size_t)H * (R + Z)); p.prior[1] = ar.take_off((size_t)H * H); p.prior[2] = ar.take_off((size_t)H * H);
+  p.prior_h = ar.take_off((size_t)2 * Z * H);
+  p.dec[0] = ar.take_off((size_t)H * (Z + R)); p.dec[1] = ar.take_off((size_t)H * H); p.dec[2] = ar.take_off((size_t)S * SD_F * H);
+  p.total = ar.floats();
   return p;
 }
 struct SdBufs { size_t X16, E16[2], ENC16, CP16, DS, GHb, P16[3], DC16, D16[2], DEC, ZS, dummyZ, dummyR, end; };
 SdBufs sd_layout(size_t base, int T, int B, int S, int H, int Z, int R) {
   SdBufs b;
-  size_t o = base;
-  auto take = [&](size_t n) { size_t at = o; o += (n + 3) & ~(size_t)3; return at; };
+  Arena ar{nullptr, base};
   const size_t rows = (size_t)((B + 15) / 16) * 16, m = (size_t)T * rows;
-  b.X16 = take((m + rows) * S);
-  b.E16[0] = take(m * H); b.E16[1] = take(m * H); b.ENC16 = take(m * H);
-  b.CP16 = take((m + 2 * rows) * (R + Z));
-  b.DS = take((size_t)(T + 1) * B * R);
-  b.GHb = take((size_t)T * B * 3 * R);
-  for (int i = 0; i < 3; ++i) b.P16[i] = take(m * H);
-  b.DC16 = take(m * (Z + R));
-  b.D16[0] = take(m * H); b.D16[1] = take(m * H);
-  b.DEC = take((size_t)T * B * S * SD_F);
-  b.ZS = take((size_t)T * B * Z);  // z_t row-major (an output)
-  b.dummyZ = take((size_t)B * Z);
-  b.dummyR = take((size_t)B * R);
-  b.end = o;
+  b.X16 = ar.take_off((m + rows) * S);
+  b.E16[0] = ar.take_off(m * H); b.E16[1] = ar.take_off(m * H); b.ENC16 = ar.take_off(m * H);
+  b.CP16 = ar.take_off((m + 2 * rows) * (R + Z));
+  b.DS = ar.take_off((size_t)(T + 1) * B * R);
+  b.GHb = ar.take_off((size_t)T * B * 3 * R);
+  for (int i = 0; i < 3; ++i) b.P16[i] = ar.take_off(m * H);
+  b.DC16 = ar.take_off(m * (Z + R));
+  b.D16[0] = ar.take_off(m * H); b.D16[1] = ar.take_off(m * H);
+  b.DEC = ar.take_off((size_t)T * B * S * SD_F);
+  b.ZS = ar.take_off((size_t)T * B * Z);  // z_t row-major (an output)
+  b.dummyZ = ar.take_off((size_t)B * Z);
+  b.dummyR = ar.take_off((size_t)B * R);
+  b.end = ar.floats();
   return b;
 }
 }  // namespace
@@ -76,32 +74,24 @@ extern "C" int blvm_srnn_generate(const BlvmSrnnDecodeWeights* w, const float* x
   const SdPack p = sd_pack_layout(S, H, Z, R);
   const SdBufs b = sd_layout(p.total, T, B, S, H, Z, R);
   T16PackScope pack_scope(pchain_optype(B), s);
-  int rc;
-#define PACK(dst, src, ld, rows, k)                               \
-  do {                                                            \
-    rc = t16_pack_rows(src, ld, rows, k, scratch + (dst), s);     \
-    if (rc) return rc;                                            \
-  } while (0)
+#define PACK(dst, src, ld, rows, k) BLVM_TRY(t16_pack_rows(src, ld, rows, k, scratch + (dst), s))
   PACK(p.enc[0], w->enc_w[0], S, H, S); PACK(p.enc[1], w->enc_w[1], H, H, H); PACK(p.enc[2], w->enc_w[2], H, H, H);
   PACK(p.wih, w->gru_wih, H, 3 * R, H); PACK(p.whh, w->gru_whh, R, 3 * R, R);
   PACK(p.prior[0], c->prior_w[0], R + Z, H, R + Z); PACK(p.prior[1], c->prior_w[1], H, H, H); PACK(p.prior[2], c->prior_w[2], H, H, H);
   PACK(p.prior_h, c->prior_hw, H, 2 * Z, H);
   PACK(p.dec[0], w->dec_w[0], Z + R, H, Z + R); PACK(p.dec[1], w->dec_w[1], H, H, H); PACK(p.dec[2], w->dec_w[2], H, S * SD_F, H);
 #undef PACK
-  rc = pack_scope.flush();  // all packs above in one launch
-  if (rc) return rc;
+  BLVM_TRY(pack_scope.flush());  // all packs above in one launch
   const int rt = (B + 15) / 16, ctS = S / 16, ctH = H / 16, ctZ = Z / 16, ctR = R / 16, cus = device_cus() & ~7;
   const int nCP = (R + Z) / 16, nDC = (Z + R) / 16;
   const long rows = (long)rt * 16, xS = rows * S, xH = rows * H, xCP = rows * (R + Z), xDC = rows * (Z + R);
   const long sR = (long)B * R, s3R = 3 * sR, sZ = (long)B * Z, sF = (long)B * S * SD_F;
   float* const sc = scratch;
-  const float beta = (float)(0.6931471805599453 / (1.0 - (double)sd_eps));
+  const float beta = softplus_beta_of(sd_eps);
   const int r_side = range_for(3 * ctR * rt, std::min(cus / 4, 64));  // the hidden projection of the NEXT step: off the critical path
   const int r_main = cus - r_side;
   Builder bld;
-  bld.p.ot = pchain_optype(B);
-  bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 4;
-  bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = r_main;
+  bld.begin(pchain_optype(B), T, B, 4, false, r_main);
   // out = leaky(A W^T + bias): A a polled T16 slab of `a_n16` blocks per row tile, outputs: T16 slab(s) and / or row-major (polled words)
   auto lin = [&](size_t A16, long a_step, int a_n16, size_t W, int K, const float* bias, int ct, int flags, float* orm, long rm_step, int ldo, size_t o16,
                  long o16_step, int n16, int wg0, int nwg) {
@@ -153,18 +143,13 @@ extern "C" int blvm_srnn_generate(const BlvmSrnnDecodeWeights* w, const float* x
     o.i[DMOLS_I_F] = SD_F; o.i[DMOLS_I_NMIX] = SD_K; o.f[DMOLS_F_LOG_EPS] = log_eps;
     add_desc(bld, K_DMOLS, S / 4, 0, range_for(S / 4 * rt, r_main), 16, 0, 0, T, o);
   }
-  BLVM_REQUIRE(!bld.overflow, "srnn_generate: persistent program overflow");
-  rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-  if (rc) return rc;
   // sentinel-fill everything the launch polls, then the initial frame stack and states
   BLVM_HIP(pchain_fill_sentinel(sc + b.X16, sizeof(float) * (b.ZS - b.X16), s));
-  rc = pchain_rows_to_t16(x0, S, B, S, sc + b.X16, s); if (rc) return rc;
-  rc = pchain_rows_to_t16(d0, R, B, R, sc + b.CP16, s, nCP); if (rc) return rc;
-  rc = pchain_rows_to_t16(z0, Z, B, Z, sc + b.CP16 + xCP + (size_t)ctR * 256, s, nCP); if (rc) return rc;
-  if (d0) BLVM_HIP(hipMemcpyAsync(sc + b.DS, d0, sizeof(float) * (size_t)B * R, hipMemcpyDeviceToDevice, s));
-  else BLVM_HIP(hipMemsetAsync(sc + b.DS, 0, sizeof(float) * (size_t)B * R, s));
-  rc = pchain_launch(bld.p, s);
-  if (rc) return rc;
+  BLVM_TRY(pchain_rows_to_t16(x0, S, B, S, sc + b.X16, s));
+  BLVM_TRY(pchain_rows_to_t16(d0, R, B, R, sc + b.CP16, s, nCP));
+  BLVM_TRY(pchain_rows_to_t16(z0, Z, B, Z, sc + b.CP16 + xCP + (size_t)ctR * 256, s, nCP));
+  BLVM_HIP(copy_or_zero(sc + b.DS, d0, sizeof(float) * (size_t)B * R, s));
+  BLVM_TRY(pchain_launch(bld, "srnn_generate", s));
   if (d_out) BLVM_HIP(hipMemcpyAsync(d_out, sc + b.DS + (size_t)T * sR, sizeof(float) * (size_t)B * R, hipMemcpyDeviceToDevice, s));
   if (z_out) BLVM_HIP(hipMemcpyAsync(z_out, sc + b.ZS, sizeof(float) * (size_t)T * B * Z, hipMemcpyDeviceToDevice, s));
   return BLVM_OK;

@@ -327,9 +327,7 @@ __global__ __launch_bounds__(NW * 64) void head_stage_kernel(const float* P, con
 
 inline void launch_head(const HeadArgs& h, int nw, dim3 grid, hipStream_t s) {
   const unsigned b_h = (unsigned)h.B | ((unsigned)h.H << 16);  // callers require B, H < 65536
-  if (nw == 16) hipLaunchKernelGGL((head_stage_kernel<16>), grid, dim3(1024), 0, s, h.P, h.Q, h.Wp, h.Wq, h.bp, h.bq, b_h, h.Z, h);
-  else if (nw == 8) hipLaunchKernelGGL((head_stage_kernel<8>), grid, dim3(512), 0, s, h.P, h.Q, h.Wp, h.Wq, h.bp, h.bq, b_h, h.Z, h);
-  else hipLaunchKernelGGL((head_stage_kernel<4>), grid, dim3(256), 0, s, h.P, h.Q, h.Wp, h.Wq, h.bp, h.bq, b_h, h.Z, h);
+  LAUNCH_NW(head_stage_kernel<NW_>, nw, grid, s, h.P, h.Q, h.Wp, h.Wq, h.bp, h.bq, b_h, h.Z, h);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -431,9 +429,7 @@ __global__ __launch_bounds__(NW * 64) void dz_stage_kernel(const float* D, const
 
 inline void launch_dz(const DzArgs& d, int nw, dim3 grid, hipStream_t s) {
   const unsigned b_h = (unsigned)d.B | ((unsigned)d.H << 16);  // callers require B, H < 65536
-  if (nw == 16) hipLaunchKernelGGL((dz_stage_kernel<16>), grid, dim3(1024), 0, s, d.D, d.WT, d.D2, d.WT2, b_h, d.Z, d.has_gemm, d);
-  else if (nw == 8) hipLaunchKernelGGL((dz_stage_kernel<8>), grid, dim3(512), 0, s, d.D, d.WT, d.D2, d.WT2, b_h, d.Z, d.has_gemm, d);
-  else hipLaunchKernelGGL((dz_stage_kernel<4>), grid, dim3(256), 0, s, d.D, d.WT, d.D2, d.WT2, b_h, d.Z, d.has_gemm, d);
+  LAUNCH_NW(dz_stage_kernel<NW_>, nw, grid, s, d.D, d.WT, d.D2, d.WT2, b_h, d.Z, d.has_gemm, d);
 }
 
 // number of waves for a K-deep reduction.  One product (groups == 1, wave_gemm16): a wave's chunks cost one memory round trip
@@ -449,14 +445,6 @@ inline int pick_nw(int K, int groups) {
     if (trips(nw) < trips(best)) best = nw;
   return best;
 }
-
-#define LAUNCH_NW(kernel, nw, grid, stream, args)                                          \
-  do {                                                                                     \
-    if ((nw) == 16) hipLaunchKernelGGL((kernel<16>), grid, dim3(1024), 0, stream, args);   \
-    else if ((nw) == 8) hipLaunchKernelGGL((kernel<8>), grid, dim3(512), 0, stream, args); \
-    else hipLaunchKernelGGL((kernel<4>), grid, dim3(256), 0, stream, args);                \
-  } while (0)
-
 
 struct LinSegH {  // host-side description of one segment
   const float* A; int lda; const float* W; int ldw; const float* bias; const float* add; int ldadd;
@@ -509,9 +497,7 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
     const int chunks = kmax / 8;
     const int nw32 = chunks > 64 ? 16 : (chunks > 32 ? 8 : 4);
     const dim3 grid32(tiles, (l.B + 31) / 32);
-    if (nw32 == 16) hipLaunchKernelGGL((lin_stage32_kernel<16, NSEG>), grid32, dim3(1024), 0, s, a);
-    else if (nw32 == 8) hipLaunchKernelGGL((lin_stage32_kernel<8, NSEG>), grid32, dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((lin_stage32_kernel<4, NSEG>), grid32, dim3(256), 0, s, a);
+    LAUNCH_NW((lin_stage32_kernel<NW_, NSEG>), nw32, grid32, s, a);
     return;
   }
   const int nw = pick_nw(kmax, 1);
@@ -520,9 +506,7 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
       a.ldgate[0] < 65536 && a.ldo[0] < 65536) {
     const unsigned p0 = (unsigned)a.lda[0] | ((unsigned)a.ldw[0] << 16), p1 = (unsigned)a.K[0] | ((unsigned)l.B << 16);
     const unsigned p2 = (unsigned)a.ldadd[0] | ((unsigned)a.ldgate[0] << 16), p3 = (unsigned)a.ldo[0] | ((unsigned)a.flags[0] << 16);
-    if (nw == 16) hipLaunchKernelGGL((lin1_stage_kernel<16>), grid, dim3(1024), 0, s, a.A[0], a.W[0], a.bias[0], a.add[0], a.gate[0], p0, p1, p2, p3, a.out[0], a.slope);
-    else if (nw == 8) hipLaunchKernelGGL((lin1_stage_kernel<8>), grid, dim3(512), 0, s, a.A[0], a.W[0], a.bias[0], a.add[0], a.gate[0], p0, p1, p2, p3, a.out[0], a.slope);
-    else hipLaunchKernelGGL((lin1_stage_kernel<4>), grid, dim3(256), 0, s, a.A[0], a.W[0], a.bias[0], a.add[0], a.gate[0], p0, p1, p2, p3, a.out[0], a.slope);
+    LAUNCH_NW(lin1_stage_kernel<NW_>, nw, grid, s, a.A[0], a.W[0], a.bias[0], a.add[0], a.gate[0], p0, p1, p2, p3, a.out[0], a.slope);
     return;
   }
   if (NSEG == 2) {
@@ -538,9 +522,7 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
       const unsigned p0 = (unsigned)(a.lda[0] / 16) | ((unsigned)(a.K[0] / 16) << 12) | ((unsigned)f << 24);
       const unsigned p1 = (unsigned)l.B | ((unsigned)a.tiles[0] << 12) | ((unsigned)(lde / 4) << 22);
       const int p2 = a.ldo[0];
-      if (nw == 16) hipLaunchKernelGGL((lin2s_stage_kernel<16>), grid, dim3(1024), 0, s, a.A[0], a.A[1 % NSEG], a.W[0], a.W[1 % NSEG], e0, e1, p0, p1, a.out[0], a.out[1 % NSEG], p2, a.slope);
-      else if (nw == 8) hipLaunchKernelGGL((lin2s_stage_kernel<8>), grid, dim3(512), 0, s, a.A[0], a.A[1 % NSEG], a.W[0], a.W[1 % NSEG], e0, e1, p0, p1, a.out[0], a.out[1 % NSEG], p2, a.slope);
-      else hipLaunchKernelGGL((lin2s_stage_kernel<4>), grid, dim3(256), 0, s, a.A[0], a.A[1 % NSEG], a.W[0], a.W[1 % NSEG], e0, e1, p0, p1, a.out[0], a.out[1 % NSEG], p2, a.slope);
+      LAUNCH_NW(lin2s_stage_kernel<NW_>, nw, grid, s, a.A[0], a.A[1 % NSEG], a.W[0], a.W[1 % NSEG], e0, e1, p0, p1, a.out[0], a.out[1 % NSEG], p2, a.slope);
       return;
     }
   }
@@ -552,9 +534,7 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
       const LinArgs<2>& a2 = reinterpret_cast<const LinArgs<2>&>(a);  // NSEG == 2 here
       const unsigned p0 = (unsigned)a2.lda[0] | ((unsigned)a2.lda[1] << 16), p1 = (unsigned)a2.ldw[0] | ((unsigned)a2.ldw[1] << 16);
       const unsigned p2 = (unsigned)a2.K[0] | ((unsigned)a2.K[1] << 16), p3 = (unsigned)a2.tiles[0] | ((unsigned)l.B << 16);
-      if (nw == 16) hipLaunchKernelGGL((linp2_stage_kernel<16>), grid, dim3(1024), 0, s, a2.A[0], a2.A[1], a2.W[0], a2.W[1], p0, p1, p2, p3, a2);
-      else if (nw == 8) hipLaunchKernelGGL((linp2_stage_kernel<8>), grid, dim3(512), 0, s, a2.A[0], a2.A[1], a2.W[0], a2.W[1], p0, p1, p2, p3, a2);
-      else hipLaunchKernelGGL((linp2_stage_kernel<4>), grid, dim3(256), 0, s, a2.A[0], a2.A[1], a2.W[0], a2.W[1], p0, p1, p2, p3, a2);
+      LAUNCH_NW(linp2_stage_kernel<NW_>, nw, grid, s, a2.A[0], a2.A[1], a2.W[0], a2.W[1], p0, p1, p2, p3, a2);
       return;
     }
   }
@@ -565,15 +545,11 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
     if (fits) {
       const unsigned p0 = (unsigned)a3.lda[0] | ((unsigned)a3.K[0] << 16);
       const unsigned p1 = (unsigned)l.B | ((unsigned)a3.tiles[0] << 12) | ((unsigned)a3.tiles[1] << 22);
-      if (nw == 16) hipLaunchKernelGGL((linp3_stage_kernel<16>), grid, dim3(1024), 0, s, a3.A[0], a3.A[1], a3.A[2], a3.W[0], a3.W[1], a3.W[2], p0, p1, a3);
-      else if (nw == 8) hipLaunchKernelGGL((linp3_stage_kernel<8>), grid, dim3(512), 0, s, a3.A[0], a3.A[1], a3.A[2], a3.W[0], a3.W[1], a3.W[2], p0, p1, a3);
-      else hipLaunchKernelGGL((linp3_stage_kernel<4>), grid, dim3(256), 0, s, a3.A[0], a3.A[1], a3.A[2], a3.W[0], a3.W[1], a3.W[2], p0, p1, a3);
+      LAUNCH_NW(linp3_stage_kernel<NW_>, nw, grid, s, a3.A[0], a3.A[1], a3.A[2], a3.W[0], a3.W[1], a3.W[2], p0, p1, a3);
       return;
     }
   }
-  if (nw == 16) hipLaunchKernelGGL((lin_stage_kernel<16, NSEG>), grid, dim3(1024), 0, s, a);
-  else if (nw == 8) hipLaunchKernelGGL((lin_stage_kernel<8, NSEG>), grid, dim3(512), 0, s, a);
-  else hipLaunchKernelGGL((lin_stage_kernel<4, NSEG>), grid, dim3(256), 0, s, a);
+  LAUNCH_NW((lin_stage_kernel<NW_, NSEG>), nw, grid, s, a);
 }
 
 inline void launch_lin(const LinLaunch& l, hipStream_t s) {

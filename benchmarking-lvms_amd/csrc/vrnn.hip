@@ -178,41 +178,41 @@ struct Reserve {
   float *P[3], *Q[3], *FZ[3], *GHb, *RG, *UG, *NG, *XQ, *XG, *RAWQ, *RAWP;
   float *Wp[3], *Wq[3], *Wph, *Wqh, *Wf[4], *Wih, *Whh;  // T16 copies of the weights the forward chain multiplies by
   // persistent forward (B <= kPchainCarveMaxB): T16 copies of every activation a link multiplies, per step [rt*16, width]
-  float *H16, *P16[3], *Q16[3], *Z16, *FZ16[3], *PHI16, *x16_end;
+  float *H16, *P16[3], *Q16[3], *Z16, *FZ16[3], *PHI16;
+  size_t x16_bytes;  // from the first piece a launch polls to the end of the T16 copies: sentinel-filled in one go
 };
 
 size_t carve_reserve(float* base, int Tp, int B, int H, int Z, int R, Reserve* r) {
   const size_t n = (size_t)Tp * B;
-  size_t off = 0;
-  auto take = [&](size_t cnt) { float* p = base ? base + off : nullptr; off += (cnt + 3) & ~(size_t)3; return p; };
+  Arena ar{base};
   Reserve tmp;
-  for (int i = 0; i < 3; ++i) tmp.P[i] = take(n * H);
-  for (int i = 0; i < 3; ++i) tmp.Q[i] = take(n * H);
-  for (int i = 0; i < 3; ++i) tmp.FZ[i] = take(n * H);
-  tmp.GHb = take(n * 3 * R);
-  tmp.RG = take(n * R); tmp.UG = take(n * R); tmp.NG = take(n * R);
-  tmp.XQ = take(n * H);
-  tmp.XG = take(n * 3 * R);
-  tmp.RAWQ = take(n * Z); tmp.RAWP = take(n * Z);
-  tmp.Wp[0] = take((size_t)H * R); tmp.Wq[0] = take((size_t)H * R);
-  for (int i = 1; i < 3; ++i) { tmp.Wp[i] = take((size_t)H * H); tmp.Wq[i] = take((size_t)H * H); }
-  tmp.Wph = take((size_t)2 * Z * H); tmp.Wqh = take((size_t)2 * Z * H);
-  tmp.Wf[0] = take((size_t)H * Z);
-  for (int i = 1; i < 4; ++i) tmp.Wf[i] = take((size_t)H * H);
-  tmp.Wih = take((size_t)3 * R * H); tmp.Whh = take((size_t)3 * R * R);
+  for (int i = 0; i < 3; ++i) tmp.P[i] = ar.take(n * H);
+  for (int i = 0; i < 3; ++i) tmp.Q[i] = ar.take(n * H);
+  for (int i = 0; i < 3; ++i) tmp.FZ[i] = ar.take(n * H);
+  tmp.GHb = ar.take(n * 3 * R);
+  tmp.RG = ar.take(n * R); tmp.UG = ar.take(n * R); tmp.NG = ar.take(n * R);
+  tmp.XQ = ar.take(n * H);
+  tmp.XG = ar.take(n * 3 * R);
+  tmp.RAWQ = ar.take(n * Z); tmp.RAWP = ar.take(n * Z);
+  tmp.Wp[0] = ar.take((size_t)H * R); tmp.Wq[0] = ar.take((size_t)H * R);
+  for (int i = 1; i < 3; ++i) { tmp.Wp[i] = ar.take((size_t)H * H); tmp.Wq[i] = ar.take((size_t)H * H); }
+  tmp.Wph = ar.take((size_t)2 * Z * H); tmp.Wqh = ar.take((size_t)2 * Z * H);
+  tmp.Wf[0] = ar.take((size_t)H * Z);
+  for (int i = 1; i < 4; ++i) tmp.Wf[i] = ar.take((size_t)H * H);
+  tmp.Wih = ar.take((size_t)3 * R * H); tmp.Whh = ar.take((size_t)3 * R * R);
   tmp.H16 = nullptr;
   if (B <= kPchainCarveMaxB || B <= vrnn_rt_max_b()) {
     const size_t rows = (size_t)((B + 15) / 16) * 16, m = (size_t)Tp * rows;
-    tmp.H16 = take((m + rows) * R);
-    for (int i = 0; i < 3; ++i) tmp.P16[i] = take(m * H);
-    for (int i = 0; i < 3; ++i) tmp.Q16[i] = take(m * H);
-    tmp.Z16 = take(m * Z);
-    for (int i = 0; i < 3; ++i) tmp.FZ16[i] = take(m * H);
-    tmp.PHI16 = take(m * H);
-    tmp.x16_end = take(0);
+    tmp.H16 = ar.take((m + rows) * R);
+    for (int i = 0; i < 3; ++i) tmp.P16[i] = ar.take(m * H);
+    for (int i = 0; i < 3; ++i) tmp.Q16[i] = ar.take(m * H);
+    tmp.Z16 = ar.take(m * Z);
+    for (int i = 0; i < 3; ++i) tmp.FZ16[i] = ar.take(m * H);
+    tmp.PHI16 = ar.take(m * H);
+    tmp.x16_bytes = ar.bytes_from(tmp.H16);
   }
   if (r) *r = tmp;
-  return off;
+  return ar.floats();
 }
 
 struct BwdWs {
@@ -220,44 +220,44 @@ struct BwdWs {
   float *DGI, *DGH, *DPHI[4], *DQH, *DPH, *DP[3], *DQ[3], *G;
   // persistent backward (B <= kPchainCarveMaxB): the running state gradient as per-step slabs (written once each), [T',B,R], and
   // T16 copies of every gradient a link multiplies, per step [rt*16, width]
-  float *GA, *GB, *DP16[3], *DQ16[3], *DGI16, *DGH16, *DPHI16[4], *DPH16, *DQH16, *DPHI16b, *DPHI16c, *x16_end;
+  float *GA, *GB, *DP16[3], *DQ16[3], *DGI16, *DGH16, *DPHI16[4], *DPH16, *DQH16, *DPHI16b, *DPHI16c;
+  size_t x16_bytes;  // from the first piece a launch polls to the end of the T16 copies: sentinel-filled in one go
   float *DPHI3b, *DPHI3c;  // row-major partial sums of DPHI[3] when its K = 3R product is split over three links (added up after the launch)
 };
 
 size_t carve_ws(float* base, int Tp, int B, int X, int H, int Z, int R, BwdWs* w) {
   (void)X;
   const size_t n = (size_t)Tp * B;
-  size_t off = 0;
-  auto take = [&](size_t cnt) { float* p = base ? base + off : nullptr; off += (cnt + 3) & ~(size_t)3; return p; };
+  Arena ar{base};
   BwdWs t;
-  t.pT[0] = take((size_t)R * H); t.pT[1] = take((size_t)H * H); t.pT[2] = take((size_t)H * H);
-  t.phT = take((size_t)H * 2 * Z);
-  t.qT[0] = take((size_t)R * H); t.qT[1] = take((size_t)H * H); t.qT[2] = take((size_t)H * H);
-  t.qhT = take((size_t)H * 2 * Z);
-  t.fT[0] = take((size_t)Z * H);
-  for (int i = 1; i < 4; ++i) t.fT[i] = take((size_t)H * H);
-  t.wihT = take((size_t)H * 3 * R);
-  t.whhT = take((size_t)R * 3 * R);
-  t.DGI = take(n * 3 * R); t.DGH = take(n * 3 * R);
-  for (int i = 0; i < 4; ++i) t.DPHI[i] = take(n * H);
-  t.DQH = take(n * 2 * Z); t.DPH = take(n * 2 * Z);
-  for (int i = 0; i < 3; ++i) t.DP[i] = take(n * H);
-  for (int i = 0; i < 3; ++i) t.DQ[i] = take(n * H);
-  t.G = take((size_t)B * R);
+  t.pT[0] = ar.take((size_t)R * H); t.pT[1] = ar.take((size_t)H * H); t.pT[2] = ar.take((size_t)H * H);
+  t.phT = ar.take((size_t)H * 2 * Z);
+  t.qT[0] = ar.take((size_t)R * H); t.qT[1] = ar.take((size_t)H * H); t.qT[2] = ar.take((size_t)H * H);
+  t.qhT = ar.take((size_t)H * 2 * Z);
+  t.fT[0] = ar.take((size_t)Z * H);
+  for (int i = 1; i < 4; ++i) t.fT[i] = ar.take((size_t)H * H);
+  t.wihT = ar.take((size_t)H * 3 * R);
+  t.whhT = ar.take((size_t)R * 3 * R);
+  t.DGI = ar.take(n * 3 * R); t.DGH = ar.take(n * 3 * R);
+  for (int i = 0; i < 4; ++i) t.DPHI[i] = ar.take(n * H);
+  t.DQH = ar.take(n * 2 * Z); t.DPH = ar.take(n * 2 * Z);
+  for (int i = 0; i < 3; ++i) t.DP[i] = ar.take(n * H);
+  for (int i = 0; i < 3; ++i) t.DQ[i] = ar.take(n * H);
+  t.G = ar.take((size_t)B * R);
   t.GA = nullptr;
   if (B <= kPchainCarveMaxB || B <= vrnn_rt_max_b()) {
     const size_t m = (size_t)Tp * ((B + 15) / 16) * 16;
-    t.GA = take(n * R); t.GB = take(n * R);
-    for (int i = 0; i < 3; ++i) { t.DP16[i] = take(m * H); t.DQ16[i] = take(m * H); }
-    t.DGI16 = take(m * 3 * R); t.DGH16 = take(m * 3 * R);
-    for (int i = 0; i < 4; ++i) t.DPHI16[i] = take(m * H);
-    t.DPH16 = take(m * 2 * Z); t.DQH16 = take(m * 2 * Z);
-    t.DPHI16b = take(m * H); t.DPHI16c = take(m * H);
-    t.x16_end = take(0);
-    t.DPHI3b = take(n * H); t.DPHI3c = take(n * H);
+    t.GA = ar.take(n * R); t.GB = ar.take(n * R);
+    for (int i = 0; i < 3; ++i) { t.DP16[i] = ar.take(m * H); t.DQ16[i] = ar.take(m * H); }
+    t.DGI16 = ar.take(m * 3 * R); t.DGH16 = ar.take(m * 3 * R);
+    for (int i = 0; i < 4; ++i) t.DPHI16[i] = ar.take(m * H);
+    t.DPH16 = ar.take(m * 2 * Z); t.DQH16 = ar.take(m * 2 * Z);
+    t.DPHI16b = ar.take(m * H); t.DPHI16c = ar.take(m * H);
+    t.x16_bytes = ar.bytes_from(t.GA);
+    t.DPHI3b = ar.take(n * H); t.DPHI3c = ar.take(n * H);
   }
   if (w) *w = t;
-  return off;
+  return ar.floats();
 }
 
 // a += b + c over n4 float4 (the three partial sums of DPHI[3])
@@ -305,8 +305,7 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
                              int Tp, int B, int X, int H, int Z, int R, int residual_posterior, float sd_eps,
                              float* decin, float* mu_q, float* sd_q, float* mu_p, float* sd_p, float* z,
                              float* reserve, hipStream_t s) {
-  int rc = check_dims(Tp, B, X, H, Z, R);
-  if (rc) return rc;
+  BLVM_TRY(check_dims(Tp, B, X, H, Z, R));
   BLVM_REQUIRE(w && enc && eps && decin && mu_q && sd_q && mu_p && sd_p && z && reserve, "vrnn_fwd: null pointer");
   BLVM_REQUIRE(aligned16(enc) && aligned16(decin) && aligned16(reserve) && aligned16(z),
                "vrnn_fwd: buffers must be 16-byte aligned");
@@ -314,34 +313,30 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   carve_reserve(reserve, Tp, B, H, Z, R, &rs);
   const size_t n = (size_t)Tp * B;
   const int ldd = H + R;
-  const float beta = (float)(0.6931471805599453 / (1.0 - (double)sd_eps));  // ln2 / (initial_sd - eps), initial_sd = 1
+  const float beta = softplus_beta_of(sd_eps);  // ln2 / (initial_sd - eps), initial_sd = 1
 
   // hoisted, state-independent halves of the two concatenated-input layers
-  rc = gemm_f32(0, 0, (int)n, H, X, enc, X, w->post_w[0] + R, R + X, rs.XQ, H, w->post_b[0], 0, 0.f, nullptr, 0, 0, 1, s);
-  if (rc) return rc;
-  rc = gemm_f32(0, 0, (int)n, 3 * R, X, enc, X, w->gru_wih, X + H, rs.XG, 3 * R, w->gru_bih, 0, 0.f, nullptr, 0, 0, 1, s);
-  if (rc) return rc;
+  BLVM_TRY(gemm_f32(0, 0, (int)n, H, X, enc, X, w->post_w[0] + R, R + X, rs.XQ, H, w->post_b[0], 0, 0.f, nullptr, 0, 0, 1, s));
+  BLVM_TRY(gemm_f32(0, 0, (int)n, 3 * R, X, enc, X, w->gru_wih, X + H, rs.XG, 3 * R, w->gru_bih, 0, 0.f, nullptr, 0, 0, 1, s));
 
   // T16 operand copies of the chain's weights (once per sequence)
   T16PackScope pack_scope(pchain_optype(B), s);  // 16-bit operand modes: the persistent launch multiplies 16-bit weight packs
-  rc = t16_pack_rows(w->prior_w[0], R, H, R, rs.Wp[0], s); if (rc) return rc;
-  rc = t16_pack_rows(w->post_w[0], R + X, H, R, rs.Wq[0], s); if (rc) return rc;  // the h columns
+  BLVM_TRY(t16_pack_rows(w->prior_w[0], R, H, R, rs.Wp[0], s));
+  BLVM_TRY(t16_pack_rows(w->post_w[0], R + X, H, R, rs.Wq[0], s));  // the h columns
   for (int l = 1; l < 3; ++l) {
-    rc = t16_pack_rows(w->prior_w[l], H, H, H, rs.Wp[l], s); if (rc) return rc;
-    rc = t16_pack_rows(w->post_w[l], H, H, H, rs.Wq[l], s); if (rc) return rc;
+    BLVM_TRY(t16_pack_rows(w->prior_w[l], H, H, H, rs.Wp[l], s));
+    BLVM_TRY(t16_pack_rows(w->post_w[l], H, H, H, rs.Wq[l], s));
   }
-  rc = t16_pack_rows(w->prior_hw, H, 2 * Z, H, rs.Wph, s); if (rc) return rc;
-  rc = t16_pack_rows(w->post_hw, H, 2 * Z, H, rs.Wqh, s); if (rc) return rc;
-  rc = t16_pack_rows(w->phi_w[0], Z, H, Z, rs.Wf[0], s); if (rc) return rc;
-  for (int l = 1; l < 4; ++l) { rc = t16_pack_rows(w->phi_w[l], H, H, H, rs.Wf[l], s); if (rc) return rc; }
-  rc = t16_pack_rows(w->gru_wih + X, X + H, 3 * R, H, rs.Wih, s); if (rc) return rc;  // the phi columns
-  rc = t16_pack_rows(w->gru_whh, R, 3 * R, R, rs.Whh, s); if (rc) return rc;
-  rc = pack_scope.flush();  // all packs above in one launch
-  if (rc) return rc;
+  BLVM_TRY(t16_pack_rows(w->prior_hw, H, 2 * Z, H, rs.Wph, s));
+  BLVM_TRY(t16_pack_rows(w->post_hw, H, 2 * Z, H, rs.Wqh, s));
+  BLVM_TRY(t16_pack_rows(w->phi_w[0], Z, H, Z, rs.Wf[0], s));
+  for (int l = 1; l < 4; ++l) BLVM_TRY(t16_pack_rows(w->phi_w[l], H, H, H, rs.Wf[l], s));
+  BLVM_TRY(t16_pack_rows(w->gru_wih + X, X + H, 3 * R, H, rs.Wih, s));  // the phi columns
+  BLVM_TRY(t16_pack_rows(w->gru_whh, R, 3 * R, R, rs.Whh, s));
+  BLVM_TRY(pack_scope.flush());  // all packs above in one launch
 
   // initial state -> h-part of decin row 0
-  if (h0) BLVM_HIP(hipMemcpy2DAsync(decin + H, sizeof(float) * ldd, h0, sizeof(float) * R, sizeof(float) * R, B, hipMemcpyDeviceToDevice, s));
-  else BLVM_HIP(hipMemset2DAsync(decin + H, sizeof(float) * ldd, 0, sizeof(float) * R, B, s));
+  BLVM_HIP(copy_or_zero_2d(decin + H, sizeof(float) * ldd, h0, sizeof(float) * R, B, s));
 
   const int rt = (B + 15) / 16;
   if (vrnn_persistent(B) && device_cus() >= 32) {
@@ -364,10 +359,8 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     const int half = range_for(ctH * tl, (cus - def_n) / 2);            // prior | posterior halves of a link
     const int g = 2 * half;
     Builder bld;
-    bld.p.ot = pchain_optype(B);
+    bld.begin(pchain_optype(B), Tp, B, groups ? 8 : 4, false, g);
     bld.p.rt_group = RTG;
-    bld.p.S = Tp; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = groups ? 8 : 4;
-    bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = g;
     // F1: hidden projection (the first prior layer and the h-half of the first posterior layer open the runs below)
     Operands hp;
     hp.p[LIN_A] = {rs.H16, xR}; hp.p[LIN_W] = rs.Whh; hp.p[LIN_BIAS] = w->gru_bhh; hp.p[LIN_ORM] = {rs.GHb, s3R}; hp.ld[LD_OUT] = 3 * R;
@@ -413,19 +406,13 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       o.ld[GRU_LD_HPREV] = ldd; o.ld[LD_OUT] = ldd; o.n16[N16_OUT] = ctR; o.i[GRU_I_R] = R;
       add_desc(bld, K_GRU, ctR, 0, range_for(ctR * tl, g), H, 0, 0, Tp, o);
     }
-    BLVM_REQUIRE(!bld.overflow, "vrnn_fwd: persistent program overflow");
-    rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-    if (rc) return rc;
     // sentinel-fill what the launch polls: the T16 copies, the hidden projection, and decin (the GRU link polls words of h)
-    BLVM_HIP(pchain_fill_sentinel(rs.H16, (size_t)(reinterpret_cast<char*>(rs.x16_end) - reinterpret_cast<char*>(rs.H16)), s));
+    BLVM_HIP(pchain_fill_sentinel(rs.H16, rs.x16_bytes, s));
     BLVM_HIP(pchain_fill_sentinel(rs.GHb, sizeof(float) * n * 3 * R, s));
     BLVM_HIP(pchain_fill_sentinel(decin, sizeof(float) * n * ldd, s));  // rows 0..T'-1; row T' only receives h_n
-    if (h0) BLVM_HIP(hipMemcpy2DAsync(decin + H, sizeof(float) * ldd, h0, sizeof(float) * R, sizeof(float) * R, B, hipMemcpyDeviceToDevice, s));
-    else BLVM_HIP(hipMemset2DAsync(decin + H, sizeof(float) * ldd, 0, sizeof(float) * R, B, s));
-    rc = pchain_rows_to_t16(h0, R, B, R, rs.H16, s);
-    if (rc) return rc;
-    rc = vrnn_static_launch(bld.p, true, s);
-    return rc == 1 ? pchain_launch(bld.p, s) : rc;
+    BLVM_HIP(copy_or_zero_2d(decin + H, sizeof(float) * ldd, h0, sizeof(float) * R, B, s));
+    BLVM_TRY(pchain_rows_to_t16(h0, R, B, R, rs.H16, s));
+    return vrnn_launch(bld, true, "vrnn_fwd", s);
   }
   for (int t = 0; t < Tp; ++t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z, oR = (size_t)t * B * R, o3R = (size_t)t * B * 3 * R;
@@ -473,9 +460,7 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       const dim3 grid(R / 16, rt);
       const float *xg_t = rs.XG + o3R, *gh_t = rs.GHb + o3R;
       float *rg_t = rs.RG + oR, *ug_t = rs.UG + oR, *ng_t = rs.NG + oR;
-      if (nw == 16) hipLaunchKernelGGL((gru_stage_kernel<16>), grid, dim3(1024), 0, s, dec_t, (const float*)rs.Wih, xg_t, gh_t, B, H, R, dec_n, rg_t, ug_t, ng_t);
-      else if (nw == 8) hipLaunchKernelGGL((gru_stage_kernel<8>), grid, dim3(512), 0, s, dec_t, (const float*)rs.Wih, xg_t, gh_t, B, H, R, dec_n, rg_t, ug_t, ng_t);
-      else hipLaunchKernelGGL((gru_stage_kernel<4>), grid, dim3(256), 0, s, dec_t, (const float*)rs.Wih, xg_t, gh_t, B, H, R, dec_n, rg_t, ug_t, ng_t);
+      LAUNCH_NW(gru_stage_kernel<NW_>, nw, grid, s, dec_t, (const float*)rs.Wih, xg_t, gh_t, B, H, R, dec_n, rg_t, ug_t, ng_t);
     }
   }
   BLVM_CHECK_LAUNCH("vrnn_seq_fwd");
@@ -496,8 +481,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
                              const float* c_raw, const float* c_fn, int stride, float fn_floor, int Tp, int B, int X, int H, int Z,
                              int R, int residual_posterior, float sd_eps, float* d_enc, float* d_h0,
                              const BlvmVrnnGrads* gr, float* workspace, hipStream_t s) {
-  int rc = check_dims(Tp, B, X, H, Z, R);
-  if (rc) return rc;
+  BLVM_TRY(check_dims(Tp, B, X, H, Z, R));
   BLVM_REQUIRE(w && enc && eps && decin && mu_q && sd_q && mu_p && sd_p && z && reserve && d_decin && workspace && gr,
                "vrnn_bwd: null pointer");
   BLVM_REQUIRE((c_fn == nullptr && c_raw == nullptr) || x_sl != nullptr, "vrnn_bwd: KL coefficients need x_sl");
@@ -508,24 +492,23 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   carve_ws(workspace, Tp, B, X, H, Z, R, &ws);
   const size_t n = (size_t)Tp * B;
   const int ldd = H + R;
-  const float beta = (float)(0.6931471805599453 / (1.0 - (double)sd_eps));
+  const float beta = softplus_beta_of(sd_eps);
 
   // transposed T16 operand copies of every weight the chain multiplies from the right
   T16PackScope pack_scope(pchain_optype(B), s);  // 16-bit operand modes: the persistent launch multiplies 16-bit weight packs
-  rc = t16_pack_transposed(w->prior_w[0], R, H, R, ws.pT[0], s); if (rc) return rc;
-  rc = t16_pack_transposed(w->prior_w[1], H, H, H, ws.pT[1], s); if (rc) return rc;
-  rc = t16_pack_transposed(w->prior_w[2], H, H, H, ws.pT[2], s); if (rc) return rc;
-  rc = t16_pack_transposed(w->prior_hw, H, 2 * Z, H, ws.phT, s); if (rc) return rc;
-  rc = t16_pack_transposed(w->post_w[0], R + X, H, R, ws.qT[0], s); if (rc) return rc;
-  rc = t16_pack_transposed(w->post_w[1], H, H, H, ws.qT[1], s); if (rc) return rc;
-  rc = t16_pack_transposed(w->post_w[2], H, H, H, ws.qT[2], s); if (rc) return rc;
-  rc = t16_pack_transposed(w->post_hw, H, 2 * Z, H, ws.qhT, s); if (rc) return rc;
-  rc = t16_pack_transposed(w->phi_w[0], Z, H, Z, ws.fT[0], s); if (rc) return rc;
-  for (int i = 1; i < 4; ++i) { rc = t16_pack_transposed(w->phi_w[i], H, H, H, ws.fT[i], s); if (rc) return rc; }
-  rc = t16_pack_transposed(w->gru_wih + X, X + H, 3 * R, H, ws.wihT, s); if (rc) return rc;
-  rc = t16_pack_transposed(w->gru_whh, R, 3 * R, R, ws.whhT, s); if (rc) return rc;
-  rc = pack_scope.flush();  // all packs above in one launch
-  if (rc) return rc;
+  BLVM_TRY(t16_pack_transposed(w->prior_w[0], R, H, R, ws.pT[0], s));
+  BLVM_TRY(t16_pack_transposed(w->prior_w[1], H, H, H, ws.pT[1], s));
+  BLVM_TRY(t16_pack_transposed(w->prior_w[2], H, H, H, ws.pT[2], s));
+  BLVM_TRY(t16_pack_transposed(w->prior_hw, H, 2 * Z, H, ws.phT, s));
+  BLVM_TRY(t16_pack_transposed(w->post_w[0], R + X, H, R, ws.qT[0], s));
+  BLVM_TRY(t16_pack_transposed(w->post_w[1], H, H, H, ws.qT[1], s));
+  BLVM_TRY(t16_pack_transposed(w->post_w[2], H, H, H, ws.qT[2], s));
+  BLVM_TRY(t16_pack_transposed(w->post_hw, H, 2 * Z, H, ws.qhT, s));
+  BLVM_TRY(t16_pack_transposed(w->phi_w[0], Z, H, Z, ws.fT[0], s));
+  for (int i = 1; i < 4; ++i) BLVM_TRY(t16_pack_transposed(w->phi_w[i], H, H, H, ws.fT[i], s));
+  BLVM_TRY(t16_pack_transposed(w->gru_wih + X, X + H, 3 * R, H, ws.wihT, s));
+  BLVM_TRY(t16_pack_transposed(w->gru_whh, R, 3 * R, R, ws.whhT, s));
+  BLVM_TRY(pack_scope.flush());  // all packs above in one launch
 
   BLVM_HIP(hipMemsetAsync(ws.G, 0, sizeof(float) * (size_t)B * R, s));
   const int rt = (B + 15) / 16;
@@ -546,9 +529,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       const int nw = pick_nw(H, 2);
       const dim3 grid(R / 16, rt);
       const unsigned b_h = (unsigned)B | ((unsigned)H << 16), has = (d.has_gemm ? 1u : 0u) | (d.has_gates ? 2u : 0u);
-      if (nw == 16) hipLaunchKernelGGL((dh_stage_kernel<16>), grid, dim3(1024), 0, s, d.DP0, d.DQ0, d.WpT, d.WqT, d.G, b_h, R, has, d);
-      else if (nw == 8) hipLaunchKernelGGL((dh_stage_kernel<8>), grid, dim3(512), 0, s, d.DP0, d.DQ0, d.WpT, d.WqT, d.G, b_h, R, has, d);
-      else hipLaunchKernelGGL((dh_stage_kernel<4>), grid, dim3(256), 0, s, d.DP0, d.DQ0, d.WpT, d.WqT, d.G, b_h, R, has, d);
+      LAUNCH_NW(dh_stage_kernel<NW_>, nw, grid, s, d.DP0, d.DQ0, d.WpT, d.WqT, d.G, b_h, R, has, d);
     }
   };
 
@@ -558,11 +539,9 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   // CU slots and memory-pipeline share from the chain's links; removed.)
   const float* hprev_all = decin + H;  // [n rows, ld = H+R]
   auto batched = [&]() -> int {
-    int rc2 = BLVM_OK;
-#define TRY(x) do { rc2 = (x); if (rc2) return rc2; } while (0)
     if (d_enc) {
-      TRY(gemm_f32(0, 1, (int)n, X, H, ws.DQ[0], H, w->post_w[0] + R, R + X, d_enc, X, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
-      TRY(gemm_f32(0, 1, (int)n, X, 3 * R, ws.DGI, 3 * R, w->gru_wih, X + H, d_enc, X, nullptr, 0, 0.f, nullptr, 0, 1, 1, s));
+      BLVM_TRY(gemm_f32(0, 1, (int)n, X, H, ws.DQ[0], H, w->post_w[0] + R, R + X, d_enc, X, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
+      BLVM_TRY(gemm_f32(0, 1, (int)n, X, 3 * R, ws.DGI, 3 * R, w->gru_wih, X + H, d_enc, X, nullptr, 0, 0.f, nullptr, 0, 1, 1, s));
     }
     // every weight gradient of the chain as ONE grouped launch (gemm.hip gemm_wgrad_group; D [rows, M] x Act [rows, N] -> dW [M, N], db [M])
     {
@@ -584,9 +563,8 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       job(ws.DP[0], H, H, hprev_all, ldd, R, gr->prior_w[0], R, gr->prior_b[0]);
       job(ws.DQ[0], H, H, hprev_all, ldd, R, gr->post_w[0], R + X);
       job(ws.DQ[0], H, H, enc, X, X, gr->post_w[0] ? gr->post_w[0] + R : nullptr, R + X, gr->post_b[0]);
-      TRY(grp.run(n, s));
+      BLVM_TRY(grp.run(n, s));
     }
-#undef TRY
     return BLVM_OK;
   };
   if (vrnn_persistent(B) && device_cus() >= 32) {
@@ -608,10 +586,8 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     const int half = range_for(ctH * tl, (cus - def_n) / 2), g = 2 * half;
     const int wide = shared ? half : g;  // range of the links between the GRU backward and the heads
     Builder bld;
-    bld.p.ot = pchain_optype(B);
+    bld.begin(pchain_optype(B), T + 1, B, groups ? 8 : 2, true, g);
     bld.p.rt_group = RTG;
-    bld.p.S = T + 1; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = groups ? 8 : 2;
-    bld.p.prof = pchain_profile_buffer() ? pchain_profile_buffer() + 64 : nullptr; bld.p.prof_wg = g;
     auto last = [&](const float* base, long step) { return rev(base, step, T - 1); };  // slab of t = T'-1, walked backwards
     {  // Ba: complete the gradient wrt h_t, GRU gate derivatives of step t (s = T': only the gradient wrt the initial state)
       Operands o;
@@ -680,14 +656,9 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       add_linseq(bld, ctH, 0, half, H, false, true, 0, T, last(ws.DPH16, x2Z), 3, lp, -sH, -xH, ctH, 0.f, H, 2 * Z);
       add_linseq(bld, ctH, half, half, H, false, true, 0, T, last(ws.DQH16, x2Z), 3, lq, -sH, -xH, ctH, 0.f, H, 2 * Z);
     }
-    BLVM_REQUIRE(!bld.overflow, "vrnn_bwd: persistent program overflow");
-    rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-    if (rc) return rc;
     // sentinel-fill what the launch polls: GA, GB (single words) and the T16 copies
-    BLVM_HIP(pchain_fill_sentinel(ws.GA, (size_t)(reinterpret_cast<char*>(ws.x16_end) - reinterpret_cast<char*>(ws.GA)), s));
-    rc = vrnn_static_launch(bld.p, false, s);
-    if (rc == 1) rc = pchain_launch(bld.p, s);
-    if (rc) return rc;
+    BLVM_HIP(pchain_fill_sentinel(ws.GA, ws.x16_bytes, s));
+    BLVM_TRY(vrnn_launch(bld, false, "vrnn_bwd", s));
     if (split3) {  // DPHI[3] += the two other partial sums
       const size_t n4 = n * H / 4;
       hipLaunchKernelGGL(add3_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, reinterpret_cast<float4*>(ws.DPHI[3]),

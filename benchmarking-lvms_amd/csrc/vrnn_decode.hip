@@ -425,16 +425,15 @@ size_t vd_lds_bytes(int S, int H, int Z, int R) {
 struct VdPack { size_t enc[3], prior[3], prior_h, phi[4], wih, whh, dec[3], total; };
 VdPack vd_pack_layout(int S, int H, int Z, int R) {
   VdPack p;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o += (n + 3) & ~(size_t)3; return at; };
-  p.enc[0] = take((size_t)H * S); p.enc[1] = take((size_t)H * H); p.enc[2] = take((size_t)H * H);
-  p.prior[0] = take((size_t)H * R); p.prior[1] = take((size_t)H * H); p.prior[2] = take((size_t)H * H);
-  p.prior_h = take((size_t)2 * Z * H);
-  p.phi[0] = take((size_t)H * Z);
-  for (int i = 1; i < 4; ++i) p.phi[i] = take((size_t)H * H);
-  p.wih = take((size_t)3 * R * 2 * H); p.whh = take((size_t)3 * R * R);
-  p.dec[0] = take((size_t)H * (H + R)); p.dec[1] = take((size_t)H * H); p.dec[2] = take((size_t)S * VD_F * H);
-  p.total = o;
+  Arena ar;
+  p.enc[0] = ar.take_off((size_t)H * S); p.enc[1] = ar.take_off((size_t)H * H); p.enc[2] = ar.take_off((size_t)H * H);
+  p.prior[0] = ar.take_off((size_t)H * R); p.prior[1] = ar.take_off((size_t)H * H); p.prior[2] = ar.take_off((size_t)H * H);
+  p.prior_h = ar.take_off((size_t)2 * Z * H);
+  p.phi[0] = ar.take_off((size_t)H * Z);
+  for (int i = 1; i < 4; ++i) p.phi[i] = ar.take_off((size_t)H * H);
+  p.wih = ar.take_off((size_t)3 * R * 2 * H); p.whh = ar.take_off((size_t)3 * R * R);
+  p.dec[0] = ar.take_off((size_t)H * (H + R)); p.dec[1] = ar.take_off((size_t)H * H); p.dec[2] = ar.take_off((size_t)S * VD_F * H);
+  p.total = ar.floats();
   return p;
 }
 
@@ -467,12 +466,7 @@ extern "C" int blvm_vrnn_decode(const BlvmVrnnDecodeWeights* w, const float* x0,
   const BlvmVrnnWeights* c = w->cell;
   const VdPack p = vd_pack_layout(S, H, Z, R);
   VDArgs a{};
-  int rc;
-#define PACK(dst, src, ld, rows, k)                               \
-  do {                                                            \
-    rc = t16_pack_rows(src, ld, rows, k, scratch + (dst), s);     \
-    if (rc) return rc;                                            \
-  } while (0)
+#define PACK(dst, src, ld, rows, k) BLVM_TRY(t16_pack_rows(src, ld, rows, k, scratch + (dst), s))
   PACK(p.enc[0], w->enc_w[0], S, H, S); PACK(p.enc[1], w->enc_w[1], H, H, H); PACK(p.enc[2], w->enc_w[2], H, H, H);
   PACK(p.prior[0], c->prior_w[0], R, H, R); PACK(p.prior[1], c->prior_w[1], H, H, H); PACK(p.prior[2], c->prior_w[2], H, H, H);
   PACK(p.prior_h, c->prior_hw, H, 2 * Z, H);
@@ -492,7 +486,7 @@ extern "C" int blvm_vrnn_decode(const BlvmVrnnDecodeWeights* w, const float* x0,
   a.lik_w = w->lik_w; a.lik_b = w->lik_b;
   a.x0 = x0; a.h0 = h0; a.eps = eps; a.u = u; a.v = v; a.x_out = x_out; a.h_out = h_out;
   a.T = T; a.B = B; a.S = S; a.H = H; a.Z = Z; a.R = R;
-  a.sd_eps = sd_eps; a.beta = (float)(0.6931471805599453 / (1.0 - (double)sd_eps)); a.slope = slope; a.log_eps = log_eps;
+  a.sd_eps = sd_eps; a.beta = softplus_beta_of(sd_eps); a.slope = slope; a.log_eps = log_eps;
   BLVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(vrnn_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(vrnn_decode_kernel, dim3((unsigned)((B + VD_ROWS - 1) / VD_ROWS)), dim3(VD_NW * 64), lds, s, a);
   BLVM_CHECK_LAUNCH("vrnn_decode");
@@ -512,24 +506,23 @@ struct VgBufs {
 };
 VgBufs vg_layout(size_t base, int T, int B, int S, int H, int Z, int R) {
   VgBufs b;
-  size_t o = base;
-  auto take = [&](size_t n) { size_t at = o; o += (n + 3) & ~(size_t)3; return at; };
+  Arena ar{nullptr, base};
   const size_t rows = (size_t)((B + 15) / 16) * 16, m = (size_t)T * rows, X = H;
-  b.X16 = take((m + rows) * S);
-  b.E16[0] = take(m * H); b.E16[1] = take(m * H);
-  b.CAT16 = take(m * (X + H));
-  b.H16 = take((m + rows) * R);
-  b.HS = take((size_t)(T + 1) * B * R);
-  for (int i = 0; i < 3; ++i) b.P16[i] = take(m * H);
-  b.GHb = take((size_t)T * B * 3 * R);
-  b.Z16 = take(m * Z);
-  for (int i = 0; i < 3; ++i) b.F16[i] = take(m * H);
-  b.DC16 = take(m * (H + R));
-  b.D16[0] = take(m * H); b.D16[1] = take(m * H);
-  b.DEC = take((size_t)T * B * S * VD_F);
-  b.dummyZ = take((size_t)B * Z);
-  b.dummyR = take((size_t)B * R);
-  b.end = o;
+  b.X16 = ar.take_off((m + rows) * S);
+  b.E16[0] = ar.take_off(m * H); b.E16[1] = ar.take_off(m * H);
+  b.CAT16 = ar.take_off(m * (X + H));
+  b.H16 = ar.take_off((m + rows) * R);
+  b.HS = ar.take_off((size_t)(T + 1) * B * R);
+  for (int i = 0; i < 3; ++i) b.P16[i] = ar.take_off(m * H);
+  b.GHb = ar.take_off((size_t)T * B * 3 * R);
+  b.Z16 = ar.take_off(m * Z);
+  for (int i = 0; i < 3; ++i) b.F16[i] = ar.take_off(m * H);
+  b.DC16 = ar.take_off(m * (H + R));
+  b.D16[0] = ar.take_off(m * H); b.D16[1] = ar.take_off(m * H);
+  b.DEC = ar.take_off((size_t)T * B * S * VD_F);
+  b.dummyZ = ar.take_off((size_t)B * Z);
+  b.dummyR = ar.take_off((size_t)B * R);
+  b.end = ar.floats();
   return b;
 }
 }  // namespace
@@ -556,13 +549,8 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
   const BlvmVrnnWeights* c = w->cell;
   const VdPack p = vd_pack_layout(S, H, Z, R);
   const VgBufs b = vg_layout(p.total, T, B, S, H, Z, R);
-  int rc;
   T16PackScope pack_scope(pchain_optype(B), s);
-#define PACK(dst, src, ld, rows, k)                               \
-  do {                                                            \
-    rc = t16_pack_rows(src, ld, rows, k, scratch + (dst), s);     \
-    if (rc) return rc;                                            \
-  } while (0)
+#define PACK(dst, src, ld, rows, k) BLVM_TRY(t16_pack_rows(src, ld, rows, k, scratch + (dst), s))
   PACK(p.enc[0], w->enc_w[0], S, H, S); PACK(p.enc[1], w->enc_w[1], H, H, H); PACK(p.enc[2], w->enc_w[2], H, H, H);
   PACK(p.prior[0], c->prior_w[0], R, H, R); PACK(p.prior[1], c->prior_w[1], H, H, H); PACK(p.prior[2], c->prior_w[2], H, H, H);
   PACK(p.prior_h, c->prior_hw, H, 2 * Z, H);
@@ -571,20 +559,17 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
   PACK(p.wih, c->gru_wih, 2 * H, 3 * R, 2 * H); PACK(p.whh, c->gru_whh, R, 3 * R, R);
   PACK(p.dec[0], w->dec_w[0], H + R, H, H + R); PACK(p.dec[1], w->dec_w[1], H, H, H); PACK(p.dec[2], w->dec_w[2], H, S * VD_F, H);
 #undef PACK
-  rc = pack_scope.flush();  // all packs above in one launch
-  if (rc) return rc;
+  BLVM_TRY(pack_scope.flush());  // all packs above in one launch
   const int rt = (B + 15) / 16, ctS = S / 16, ctH = H / 16, ctZ = Z / 16, ctR = R / 16, X = H, cus = device_cus() & ~7;
   const long rows = (long)rt * 16, xS = rows * S, xH = rows * H, xZ = rows * Z, xR = rows * R, xC = rows * (X + H), xD = rows * (H + R);
   const long sR = (long)B * R, s3R = 3 * sR, sZ = (long)B * Z, sF = (long)B * S * VD_F;
   float* const sc = scratch;
-  const float beta = (float)(0.6931471805599453 / (1.0 - (double)sd_eps));
+  const float beta = softplus_beta_of(sd_eps);
   // ranges: the hidden projection and the wide last decoder layer off to the side of the critical links
   const int r_side = range_for(3 * ctR * rt, std::min(cus / 4, 64));
   const int r_main = range_for(std::max(ctR * rt, ctH * rt), cus - r_side);
   Builder bld;
-    bld.p.ot = pchain_optype(B);
-  bld.p.S = T; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 4;
-  bld.p.prof = pchain_profile_buffer(); bld.p.prof_wg = r_main;
+  bld.begin(pchain_optype(B), T, B, 4, false, r_main);
   auto lin = [&](size_t A16, long a_step, size_t W, int K, const float* bias, int ct, int flags, float sl, float* orm, long rm_step, int ldo, size_t o16,
                  long o16_step, int n16, size_t o16b, long o16b_step, int n16b, int wg0, int nwg) -> Desc& {
     Operands o;
@@ -643,17 +628,12 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
     o.i[DMOLS_I_F] = VD_F; o.i[DMOLS_I_NMIX] = VD_K; o.f[DMOLS_F_LOG_EPS] = log_eps;
     add_desc(bld, K_DMOLS, S / 4, 0, range_for(S / 4 * rt, r_main), 16, 0, 0, T, o);
   }
-  BLVM_REQUIRE(!bld.overflow, "vrnn_generate: persistent program overflow");
-  rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-  if (rc) return rc;
   // sentinel-fill everything the launch polls (all step slabs), then the initial frame stack and state
   BLVM_HIP(pchain_fill_sentinel(sc + b.X16, sizeof(float) * (b.dummyZ - b.X16), s));
-  rc = pchain_rows_to_t16(x0, S, B, S, sc + b.X16, s); if (rc) return rc;
-  rc = pchain_rows_to_t16(h0, R, B, R, sc + b.H16, s); if (rc) return rc;
-  if (h0) BLVM_HIP(hipMemcpyAsync(sc + b.HS, h0, sizeof(float) * (size_t)B * R, hipMemcpyDeviceToDevice, s));
-  else BLVM_HIP(hipMemsetAsync(sc + b.HS, 0, sizeof(float) * (size_t)B * R, s));
-  rc = pchain_launch(bld.p, s);
-  if (rc) return rc;
+  BLVM_TRY(pchain_rows_to_t16(x0, S, B, S, sc + b.X16, s));
+  BLVM_TRY(pchain_rows_to_t16(h0, R, B, R, sc + b.H16, s));
+  BLVM_HIP(copy_or_zero(sc + b.HS, h0, sizeof(float) * (size_t)B * R, s));
+  BLVM_TRY(pchain_launch(bld, "vrnn_generate", s));
   if (h_out) BLVM_HIP(hipMemcpyAsync(h_out, sc + b.HS + (size_t)T * sR, sizeof(float) * (size_t)B * R, hipMemcpyDeviceToDevice, s));
   return BLVM_OK;
 }

@@ -7,7 +7,7 @@
 // in scalar registers at the point of use.  The tiles (pchain.h) and the hand-off protocol are the interpreter's, unchanged.
 //
 // The host builds the same pchain::Program as for the interpreter and converts it here; a program of any other shape is "not
-// applicable" (return value 1) and the caller falls back to pchain_launch.
+// applicable" (return value 1) and vrnn_launch falls back to the interpreter (pchain_run).
 //
 // Here: the VRNN forward and backward programs of vrnn.hip at B <= 64 on 16-row tiles, fp32, H = Z = 256, R = 512 (the backward in
 // its split3 form), and the gate the design passed first — the dependent linear chain of blvm_pchain_chain_probe as a static walk
@@ -364,7 +364,7 @@ bool int_strides(const Program& p) {  // SPtr keeps 32-bit strides
 }
 SPtr sptr(const Program& p, const Desc& d, int k) { return SPtr{const_cast<float*>(d.p[k]), (int)p.stride[d.sidx[k]]}; }
 
-// every workgroup of `grid` resident at once (one 16-wave workgroup per CU with `lds` bytes of dynamic LDS), as pchain_launch
+// every workgroup of `grid` resident at once (one 16-wave workgroup per CU with `lds` bytes of dynamic LDS), as pchain_run
 // checks it; the dynamic-LDS limit is raised once per process and device.  slot: 0 forward, 1 backward, 2 the probe's chain
 template <class Kern>
 int static_go(Kern kernel, int slot, int grid, size_t lds, const char* what) {
@@ -398,8 +398,7 @@ int static_lin_chain_launch(const Program& p, hipStream_t stream) {
                  d.wg0, d.nwg, d.ct, p.xcd, p.ctl};
   const int grid = d.wg0 + d.nwg;
   auto go = [&](auto kernel) -> int {
-    const int rc = static_go(kernel, 2, grid, 0, "static_lin_chain");
-    if (rc) return rc;
+    BLVM_TRY(static_go(kernel, 2, grid, 0, "static_lin_chain"));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), 0, stream, a);
     BLVM_CHECK_LAUNCH("static_lin_chain");
     return BLVM_OK;
@@ -416,7 +415,7 @@ bool pchain_static_on() { return g_static != 0; }
 SPtr sp(const Program& p, const Desc& d, int k) { return SPtr{const_cast<float*>(d.p[k]), d.p[k] ? (int)p.stride[d.sidx[k]] : 0}; }
 Deal deal_of(const Desc& d, int idx) { return Deal{d.wg0, d.nwg, d.ct, d.s_begin, d.s_end, idx}; }
 bool within(const Desc& d, int lo, int hi) { return d.wg0 >= lo && d.wg0 + d.nwg <= hi; }
-bool few_tiles(const Program& p, const Desc& d) {  // at most kMaxTiles tiles of the link per workgroup (pchain_launch's count)
+bool few_tiles(const Program& p, const Desc& d) {  // at most kMaxTiles tiles of the link per workgroup (pchain_run's count)
   const int rt = (p.B + 15) / 16;
   if (d.nwg <= 0 || (p.xcd && d.nwg % 8 != 0)) return false;
   const int per_wg = p.xcd ? (((d.ct + 7) / 8) * rt + d.nwg / 8 - 1) / (d.nwg / 8) : (d.ct * rt + d.nwg - 1) / d.nwg;
@@ -441,7 +440,7 @@ SeqArgs seq_args(const Program& p, const Desc& d) {
   return q;
 }
 
-// 1: not the shape the static kernels were compiled for (the caller runs pchain_launch)
+// 1: not the shape the static kernels were compiled for (vrnn_launch runs the interpreter)
 int vrnn_static_check(const Program& p, int ndesc, int products) {
   if (!pchain_static_on() || p.ndesc != ndesc || p.ot != OP_F32 || p.rt_group != 1 || p.s_first != 0 || p.B > 64) return 1;
   if (p.lds_products != products || !int_strides(p)) return 1;  // (the kernels' reduction scratch is sized for `products`)
@@ -480,8 +479,7 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
   for (int i = 0; i < 6; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.ctl = p.ctl;
   const size_t lds = sizeof(float) * 2 * kFwdProducts * 16 * 256;
-  const int rc = static_go(&vrnn_static_fwd_kernel<16>, 0, grid, lds, "vrnn_static_fwd");
-  if (rc) return rc;
+  BLVM_TRY(static_go(&vrnn_static_fwd_kernel<16>, 0, grid, lds, "vrnn_static_fwd"));
   hipLaunchKernelGGL(vrnn_static_fwd_kernel<16>, dim3(grid), dim3(1024), lds, stream, a);
   BLVM_CHECK_LAUNCH("vrnn_static_fwd");
   ++g_static_launches;
@@ -526,8 +524,7 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream) {
   for (int i = 0; i < 10; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.ctl = p.ctl;
   const size_t lds = sizeof(float) * 2 * kBwdProducts * 16 * 256;
-  const int rc = static_go(&vrnn_static_bwd_kernel<16>, 1, grid, lds, "vrnn_static_bwd");
-  if (rc) return rc;
+  BLVM_TRY(static_go(&vrnn_static_bwd_kernel<16>, 1, grid, lds, "vrnn_static_bwd"));
   hipLaunchKernelGGL(vrnn_static_bwd_kernel<16>, dim3(grid), dim3(1024), lds, stream, a);
   BLVM_CHECK_LAUNCH("vrnn_static_bwd");
   ++g_static_launches;
@@ -536,8 +533,10 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream) {
 
 }  // namespace
 
-int vrnn_static_launch(const pchain::Program& prog, bool forward, hipStream_t stream) {
-  return forward ? vrnn_static_fwd(prog, stream) : vrnn_static_bwd(prog, stream);
+int vrnn_launch(pchain::Builder& bld, bool forward, const char* who, hipStream_t stream) {
+  BLVM_TRY(pchain_prepare(bld, who));
+  const int rc = forward ? vrnn_static_fwd(bld.p, stream) : vrnn_static_bwd(bld.p, stream);
+  return rc == 1 ? pchain_run(bld.p, stream) : rc;
 }
 
 }  // namespace blvm
@@ -558,15 +557,14 @@ extern "C" int blvm_pchain_static_chain_probe(const float* W16, const float* bia
   const int rt = (B + 15) / 16;
   const long x = (long)rt * 16 * N, sN = (long)B * N;
   Builder bld;
-  bld.p.S = L; bld.p.B = B; bld.p.xcd = (pchain_tune() & 4) ? 1 : 0; bld.p.lds_products = 1;
+  bld.begin(OP_F32, L, B, 1, false, 0);
   const int nw = nwg > 0 ? nwg : range_for((N / 16) * rt, device_cus() & ~7);
   Operands o;
   o.p[LIN_A] = {x16, x}; o.p[LIN_W] = W16; o.p[LIN_BIAS] = bias; o.p[LIN_ORM] = {xs, sN}; o.p[LIN_O16] = {x16 + x, x}; o.ld[LD_OUT] = N; o.n16[N16_OUT] = N / 16;
   add_desc(bld, K_LIN, N / 16, 0, nw, N, DF_RELU, 0, L, o);
-  int rc = pchain_ctl(&bld.p.ctl.dev, &bld.p.ctl.host, &bld.p.ctl.epoch);
-  if (rc) return rc;
   BLVM_HIP(pchain_fill_sentinel(x16 + x, sizeof(float) * (size_t)x * L, s));
-  rc = static_lin_chain_launch(bld.p, s);
+  BLVM_TRY(pchain_prepare(bld, "pchain_static_chain_probe"));
+  const int rc = static_lin_chain_launch(bld.p, s);
   BLVM_REQUIRE(rc != 1, "pchain_static_chain_probe: no static kernel for N = %d (256, 512) or this deal", N);
   return rc;
 }

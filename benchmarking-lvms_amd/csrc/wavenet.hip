@@ -821,8 +821,7 @@ struct ConvWs { float *W0, *W1, *dW0, *dW1; };
 // out[L_out*B, N] = x[0:L_out*B] W0^T + x[d*B : d*B + L_out*B] W1^T + bias, with (W0, W1) already split
 static int conv_k2_apply(const float* x, int Cin, const float* W0, const float* W1, const float* bias, size_t rows_out,
                          size_t shift_rows, int N, float* out, hipStream_t s) {
-  int rc = gemm_f32(0, 0, (int)rows_out, N, Cin, x, Cin, W0, Cin, out, N, bias, 0, 0.f, nullptr, 0, 0, 1, s);
-  if (rc) return rc;
+  BLVM_TRY(gemm_f32(0, 0, (int)rows_out, N, Cin, x, Cin, W0, Cin, out, N, bias, 0, 0.f, nullptr, 0, 0, 1, s));
   return gemm_f32(0, 0, (int)rows_out, N, Cin, x + shift_rows * Cin, Cin, W1, Cin, out, N, nullptr, 0, 0.f, nullptr, 0, 1, 1, s);
 }
 
@@ -861,25 +860,20 @@ extern "C" int blvm_conv1d_k2_bwd(const float* x, const float* W, const float* d
   const size_t nk = (size_t)Cin * Cout, nk4 = (nk + 3) & ~(size_t)3;
   float *W0 = workspace, *W1 = W0 + nk4, *dW0 = W1 + nk4, *dW1 = dW0 + nk4;
   const size_t rows = (size_t)(L_in - dilation) * B, shift = (size_t)dilation * B;
-  int rc;
   if (d_x) {
     hipLaunchKernelGGL(split_taps_kernel, ew_grid(nk), dim3(256), 0, s, W, W0, W1, nk);
     BLVM_HIP(hipMemsetAsync(d_x, 0, sizeof(float) * (size_t)L_in * B * Cin, s));
-    rc = gemm_f32(0, 1, (int)rows, Cin, Cout, d_out, Cout, W0, Cin, d_x, Cin, nullptr, 0, 0.f, nullptr, 0, 1, 1, s);
-    if (rc) return rc;
-    rc = gemm_f32(0, 1, (int)rows, Cin, Cout, d_out, Cout, W1, Cin, d_x + shift * Cin, Cin, nullptr, 0, 0.f, nullptr, 0, 1, 1, s);
-    if (rc) return rc;
+    BLVM_TRY(gemm_f32(0, 1, (int)rows, Cin, Cout, d_out, Cout, W0, Cin, d_x, Cin, nullptr, 0, 0.f, nullptr, 0, 1, 1, s));
+    BLVM_TRY(gemm_f32(0, 1, (int)rows, Cin, Cout, d_out, Cout, W1, Cin, d_x + shift * Cin, Cin, nullptr, 0, 0.f, nullptr, 0, 1, 1, s));
   }
   if (dW) {
     BLVM_HIP(hipMemsetAsync(dW0, 0, sizeof(float) * 2 * nk4, s));
     const int sp = pick_split(Cout, Cin, (int)rows);
-    rc = gemm_f32(1, 1, Cout, Cin, (int)rows, d_out, Cout, x, Cin, dW0, Cin, nullptr, 0, 0.f, nullptr, 0, 1, sp, s, db);  // (+ db)
-    if (rc) return rc;
-    rc = gemm_f32(1, 1, Cout, Cin, (int)rows, d_out, Cout, x + shift * Cin, Cin, dW1, Cin, nullptr, 0, 0.f, nullptr, 0, 1, sp, s);
-    if (rc) return rc;
+    BLVM_TRY(gemm_f32(1, 1, Cout, Cin, (int)rows, d_out, Cout, x, Cin, dW0, Cin, nullptr, 0, 0.f, nullptr, 0, 1, sp, s, db));  // (+ db)
+    BLVM_TRY(gemm_f32(1, 1, Cout, Cin, (int)rows, d_out, Cout, x + shift * Cin, Cin, dW1, Cin, nullptr, 0, 0.f, nullptr, 0, 1, sp, s));
     hipLaunchKernelGGL(merge_taps_kernel, ew_grid(nk), dim3(256), 0, s, dW0, dW1, dW, nk);
   }
-  if (db && !dW) { rc = colsum_f32((int)rows, Cout, d_out, Cout, db, 1, s); if (rc) return rc; }
+  if (db && !dW) BLVM_TRY(colsum_f32((int)rows, Cout, d_out, Cout, db, 1, s));
   BLVM_CHECK_LAUNCH("conv1d_k2_bwd");
   return BLVM_OK;
 }
@@ -911,25 +905,22 @@ extern "C" int blvm_wavenet_block_fwd(const float* x, const float* conv_w, const
     // operand-layout copies: the two taps straight out of the interleaved Conv1d weight, the 1x1 weight behind them
     float* Wrs = W1 + nk;
     T16PackScope pack_scope(OP_F32, s);  // the three packs in one launch (the block kernels round fp32 packs themselves in the 16-bit modes)
-    int rc = t16_pack(conv_w, 2 * C, 2, 2 * C, C, W0, s); if (rc) return rc;
-    rc = t16_pack(conv_w + 1, 2 * C, 2, 2 * C, C, W1, s); if (rc) return rc;
-    rc = t16_pack_rows(rs_w, C, C + S, C, Wrs, s); if (rc) return rc;
-    rc = pack_scope.flush(); if (rc) return rc;
+    BLVM_TRY(t16_pack(conv_w, 2 * C, 2, 2 * C, C, W0, s));
+    BLVM_TRY(t16_pack(conv_w + 1, 2 * C, 2, 2 * C, C, W1, s));
+    BLVM_TRY(t16_pack_rows(rs_w, C, C + S, C, Wrs, s));
+    BLVM_TRY(pack_scope.flush());
     FusedFwdArgs a;
     a.x = x; a.W0 = W0; a.W1 = W1; a.Wrs = Wrs; a.conv_b = conv_b; a.rs_b = rs_b;
     a.pre = pre; a.act = act; a.o = o; a.skip = skip;
     a.rows = rows; a.shift = shift; a.off = rows - (size_t)T_skip * B; a.inv_std = inv_std;
-    rc = C == 32 ? launch_fused_fwd<32, 32>(a, s) : C == 64 ? launch_fused_fwd<64, 64>(a, s) : launch_fused_fwd<96, 96>(a, s);
-    if (rc) return rc;
+    BLVM_TRY(C == 32 ? launch_fused_fwd<32, 32>(a, s) : C == 64 ? launch_fused_fwd<64, 64>(a, s) : launch_fused_fwd<96, 96>(a, s));
     BLVM_CHECK_LAUNCH("wavenet_block_fwd (fused)");
     return BLVM_OK;
   }
   hipLaunchKernelGGL(split_taps_kernel, ew_grid(nk), dim3(256), 0, s, conv_w, W0, W1, nk);
-  int rc = conv_k2_apply(x, C, W0, W1, conv_b, rows, shift, 2 * C, pre, s);
-  if (rc) return rc;
+  BLVM_TRY(conv_k2_apply(x, C, W0, W1, conv_b, rows, shift, 2 * C, pre, s));
   hipLaunchKernelGGL(gate_fwd_kernel, ew_grid(rows * (C / 4)), dim3(256), 0, s, pre, act, rows, C);
-  rc = gemm_f32(0, 0, (int)rows, C + S, C, act, C, rs_w, C, rs, C + S, rs_b, 0, 0.f, nullptr, 0, 0, 1, s);
-  if (rc) return rc;
+  BLVM_TRY(gemm_f32(0, 0, (int)rows, C + S, C, act, C, rs_w, C, rs, C + S, rs_b, 0, 0.f, nullptr, 0, 0, 1, s));
   hipLaunchKernelGGL(resskip_fwd_kernel, ew_grid(rows * (C + S)), dim3(256), 0, s, rs, x + shift * C, o, skip, rows,
                      rows - (size_t)T_skip * B, C, S, inv_std);
   BLVM_CHECK_LAUNCH("wavenet_block_fwd");
@@ -952,7 +943,6 @@ extern "C" int blvm_wavenet_block_bwd(const float* x, const float* conv_w, const
   float* d_rs = dW1 + nk + 64;
   float* d_act = d_rs + rows * (C + S);
   float* d_pre = d_act + rows * C;
-  int rc;
   const bool fused = fused_fwd_enabled() && S == C && (C == 32 || C == 64 || C == 96) && (d_o == nullptr || aligned16(d_o)) && aligned16(d_skip);
   if (fused) {
     // operand-layout copies, 2 C^2 floats each: Wrs^T [C, C+S] in the W0 slot, the taps' transposes [C, 2C] in the W1 and
@@ -961,17 +951,16 @@ extern "C" int blvm_wavenet_block_bwd(const float* x, const float* conv_w, const
     float* W0T = W1;
     float* W1T = dW0;
     T16PackScope pack_scope(OP_F32, s);
-    rc = t16_pack_transposed(rs_w, C, C + S, C, WrsT, s); if (rc) return rc;
-    rc = t16_pack(conv_w, 2, 2 * C, C, 2 * C, W0T, s); if (rc) return rc;
-    rc = t16_pack(conv_w + 1, 2, 2 * C, C, 2 * C, W1T, s); if (rc) return rc;
-    rc = pack_scope.flush(); if (rc) return rc;
+    BLVM_TRY(t16_pack_transposed(rs_w, C, C + S, C, WrsT, s));
+    BLVM_TRY(t16_pack(conv_w, 2, 2 * C, C, 2 * C, W0T, s));
+    BLVM_TRY(t16_pack(conv_w + 1, 2, 2 * C, C, 2 * C, W1T, s));
+    BLVM_TRY(pack_scope.flush());
     FusedBwdAArgs aa;
     aa.d_o = d_o; aa.d_skip = d_skip; aa.pre = pre; aa.WrsT = WrsT; aa.d_rs = d_rs; aa.d_pre = d_pre;
     aa.rows = rows; aa.off = rows - (size_t)T_skip * B; aa.inv_std = inv_std;
     FusedBwdBArgs ab;
     ab.d_pre = d_pre; ab.d_o = d_o; ab.W0T = W0T; ab.W1T = W1T; ab.d_x = d_x; ab.rows = rows; ab.shift = shift; ab.inv_std = inv_std;
-    rc = C == 32 ? launch_fused_bwd<32, 32>(aa, ab, s) : C == 64 ? launch_fused_bwd<64, 64>(aa, ab, s) : launch_fused_bwd<96, 96>(aa, ab, s);
-    if (rc) return rc;
+    BLVM_TRY(C == 32 ? launch_fused_bwd<32, 32>(aa, ab, s) : C == 64 ? launch_fused_bwd<64, 64>(aa, ab, s) : launch_fused_bwd<96, 96>(aa, ab, s));
   } else {
     hipLaunchKernelGGL(split_taps_kernel, ew_grid(nk), dim3(256), 0, s, conv_w, W0, W1, nk);
     // d_x: rows [0, d*B) start at zero, rows [d*B, L*B) start with the residual path d_o * inv_std
@@ -979,8 +968,7 @@ extern "C" int blvm_wavenet_block_bwd(const float* x, const float* conv_w, const
     hipLaunchKernelGGL(resskip_bwd_kernel, ew_grid(rows * (C + S)), dim3(256), 0, s, d_o, d_skip, d_rs, d_x + shift * C, rows,
                        rows - (size_t)T_skip * B, C, S, inv_std);
     // 1x1 convolution
-    rc = gemm_f32(0, 1, (int)rows, C, C + S, d_rs, C + S, rs_w, C, d_act, C, nullptr, 0, 0.f, nullptr, 0, 0, 1, s);
-    if (rc) return rc;
+    BLVM_TRY(gemm_f32(0, 1, (int)rows, C, C + S, d_rs, C + S, rs_w, C, d_act, C, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
   }
   if (fused) {
     // weight and bias gradients: the operands stream once (wn_ts_wgrad_kernel); the taps land interleaved in dconv_w
@@ -988,40 +976,34 @@ extern "C" int blvm_wavenet_block_bwd(const float* x, const float* conv_w, const
       TsArgs t{};
       t.A = d_rs; t.B0 = act; t.B1 = nullptr; t.rows = rows; t.out = drs_w; t.ostride = 1; t.colsum = drs_b;
       BLVM_REQUIRE(drs_w != nullptr, "wavenet_block_bwd: drs_b without drs_w");
-      rc = C == 32 ? launch_ts_wgrad<32, false>(t, s) : C == 64 ? launch_ts_wgrad<64, false>(t, s) : launch_ts_wgrad<96, false>(t, s);
-      if (rc) return rc;
+      BLVM_TRY(C == 32 ? launch_ts_wgrad<32, false>(t, s) : C == 64 ? launch_ts_wgrad<64, false>(t, s) : launch_ts_wgrad<96, false>(t, s));
     }
     if (dconv_w || dconv_b) {
       TsArgs t{};
       t.A = d_pre; t.B0 = x; t.B1 = x + shift * C; t.rows = rows; t.out = dconv_w; t.ostride = 2; t.colsum = dconv_b;
       BLVM_REQUIRE(dconv_w != nullptr, "wavenet_block_bwd: dconv_b without dconv_w");
-      rc = C == 32 ? launch_ts_wgrad<32, true>(t, s) : C == 64 ? launch_ts_wgrad<64, true>(t, s) : launch_ts_wgrad<96, true>(t, s);
-      if (rc) return rc;
+      BLVM_TRY(C == 32 ? launch_ts_wgrad<32, true>(t, s) : C == 64 ? launch_ts_wgrad<64, true>(t, s) : launch_ts_wgrad<96, true>(t, s));
     }
     BLVM_CHECK_LAUNCH("wavenet_block_bwd (fused)");
     return BLVM_OK;
   }
   // (bias gradients = column sums of the GEMM's A operand: they ride in its first column block, gemm.hip)
-  if (drs_w) { rc = gemm_f32(1, 1, C + S, C, (int)rows, d_rs, C + S, act, C, drs_w, C, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(C + S, C, (int)rows), s, drs_b); if (rc) return rc; }
-  else if (drs_b) { rc = colsum_f32((int)rows, C + S, d_rs, C + S, drs_b, 1, s); if (rc) return rc; }
+  if (drs_w) BLVM_TRY(gemm_f32(1, 1, C + S, C, (int)rows, d_rs, C + S, act, C, drs_w, C, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(C + S, C, (int)rows), s, drs_b));
+  else if (drs_b) BLVM_TRY(colsum_f32((int)rows, C + S, d_rs, C + S, drs_b, 1, s));
   // gate
   if (!fused) hipLaunchKernelGGL(gate_bwd_kernel, ew_grid(rows * (C / 4)), dim3(256), 0, s, pre, d_act, d_pre, rows, C);
   // dilated convolution: weight gradients of both taps, then the two shifted input gradients
   if (dconv_w) {
     BLVM_HIP(hipMemsetAsync(dW0, 0, sizeof(float) * 2 * nk, s));
     const int sp = pick_split(2 * C, C, (int)rows);
-    rc = gemm_f32(1, 1, 2 * C, C, (int)rows, d_pre, 2 * C, x, C, dW0, C, nullptr, 0, 0.f, nullptr, 0, 1, sp, s, dconv_b);
-    if (rc) return rc;
-    rc = gemm_f32(1, 1, 2 * C, C, (int)rows, d_pre, 2 * C, x + shift * C, C, dW1, C, nullptr, 0, 0.f, nullptr, 0, 1, sp, s);
-    if (rc) return rc;
+    BLVM_TRY(gemm_f32(1, 1, 2 * C, C, (int)rows, d_pre, 2 * C, x, C, dW0, C, nullptr, 0, 0.f, nullptr, 0, 1, sp, s, dconv_b));
+    BLVM_TRY(gemm_f32(1, 1, 2 * C, C, (int)rows, d_pre, 2 * C, x + shift * C, C, dW1, C, nullptr, 0, 0.f, nullptr, 0, 1, sp, s));
     hipLaunchKernelGGL(merge_taps_kernel, ew_grid(nk), dim3(256), 0, s, dW0, dW1, dconv_w, nk);
   }
-  if (dconv_b && !dconv_w) { rc = colsum_f32((int)rows, 2 * C, d_pre, 2 * C, dconv_b, 1, s); if (rc) return rc; }
+  if (dconv_b && !dconv_w) BLVM_TRY(colsum_f32((int)rows, 2 * C, d_pre, 2 * C, dconv_b, 1, s));
   if (!fused) {
-    rc = gemm_f32(0, 1, (int)rows, C, 2 * C, d_pre, 2 * C, W0, C, d_x, C, nullptr, 0, 0.f, nullptr, 0, 1, 1, s);
-    if (rc) return rc;
-    rc = gemm_f32(0, 1, (int)rows, C, 2 * C, d_pre, 2 * C, W1, C, d_x + shift * C, C, nullptr, 0, 0.f, nullptr, 0, 1, 1, s);
-    if (rc) return rc;
+    BLVM_TRY(gemm_f32(0, 1, (int)rows, C, 2 * C, d_pre, 2 * C, W0, C, d_x, C, nullptr, 0, 0.f, nullptr, 0, 1, 1, s));
+    BLVM_TRY(gemm_f32(0, 1, (int)rows, C, 2 * C, d_pre, 2 * C, W1, C, d_x + shift * C, C, nullptr, 0, 0.f, nullptr, 0, 1, 1, s));
   }
   BLVM_CHECK_LAUNCH("wavenet_block_bwd");
   return BLVM_OK;
@@ -1054,8 +1036,7 @@ int stack_layout(int L, int B, int C, const int* dilations, int n, StackLayout& 
 
 extern "C" int blvm_wavenet_stack_floats(int L, int B, int C, const int* dilations, int n_blocks, size_t* acts_floats, size_t* reserve_floats) {
   StackLayout lay;
-  const int rc = stack_layout(L, B, C, dilations, n_blocks, lay);
-  if (rc) return rc;
+  BLVM_TRY(stack_layout(L, B, C, dilations, n_blocks, lay));
   if (acts_floats) *acts_floats = lay.act_off[n_blocks];
   if (reserve_floats) *reserve_floats = lay.res_off[n_blocks];
   return BLVM_OK;
@@ -1066,16 +1047,14 @@ extern "C" int blvm_wavenet_stack_fwd(const float* x, const float* const* params
                                       float* workspace, void* stream) {
   BLVM_REQUIRE(x && params && groups && reserve && workspace && (acts || n_blocks == 1), "wavenet_stack_fwd: null pointer");
   StackLayout lay;
-  int rc = stack_layout(L, B, C, dilations, n_blocks, lay);
-  if (rc) return rc;
+  BLVM_TRY(stack_layout(L, B, C, dilations, n_blocks, lay));
   for (int i = 0; i < n_blocks; ++i) {
     const float* xi = i == 0 ? x : acts + lay.act_off[i - 1];
     float* o = i + 1 < n_blocks ? acts + lay.act_off[i] : nullptr;
     const int Si = groups[i] >= 0 ? S : 0;
     BLVM_REQUIRE(Si == 0 || (skips && skips[groups[i]]), "wavenet_stack_fwd: block %d: no skip tensor %d", i, groups[i]);
-    rc = blvm_wavenet_block_fwd(xi, params[4 * i], params[4 * i + 1], params[4 * i + 2], params[4 * i + 3], lay.L_in[i], B, C, Si, dilations[i],
-                                T_skip, inv_std, o, Si ? skips[groups[i]] : nullptr, reserve + lay.res_off[i], workspace, stream);
-    if (rc) return rc;
+    BLVM_TRY(blvm_wavenet_block_fwd(xi, params[4 * i], params[4 * i + 1], params[4 * i + 2], params[4 * i + 3], lay.L_in[i], B, C, Si, dilations[i],
+                                    T_skip, inv_std, o, Si ? skips[groups[i]] : nullptr, reserve + lay.res_off[i], workspace, stream));
   }
   return BLVM_OK;
 }
@@ -1087,8 +1066,7 @@ extern "C" int blvm_wavenet_stack_bwd(const float* x, const float* const* params
   BLVM_REQUIRE(x && params && groups && reserve && workspace && d_x && grads && (acts || n_blocks == 1) && (d_scratch || n_blocks == 1),
                "wavenet_stack_bwd: null pointer");
   StackLayout lay;
-  int rc = stack_layout(L, B, C, dilations, n_blocks, lay);
-  if (rc) return rc;
+  BLVM_TRY(stack_layout(L, B, C, dilations, n_blocks, lay));
   // input gradients ping-pong between d_x (even blocks; block 0's is the result) and d_scratch (odd blocks), both [L,B,C]
   const float* d_o = nullptr;
   for (int i = n_blocks - 1; i >= 0; --i) {
@@ -1096,10 +1074,9 @@ extern "C" int blvm_wavenet_stack_bwd(const float* x, const float* const* params
     float* d_xi = (i & 1) ? d_scratch : d_x;
     const int Si = groups[i] >= 0 ? S : 0;
     BLVM_REQUIRE(Si == 0 || (d_skips && d_skips[groups[i]]), "wavenet_stack_bwd: block %d: no skip gradient %d", i, groups[i]);
-    rc = blvm_wavenet_block_bwd(xi, params[4 * i], params[4 * i + 2], reserve + lay.res_off[i], d_o, Si ? d_skips[groups[i]] : nullptr, lay.L_in[i],
-                                B, C, Si, dilations[i], T_skip, inv_std, d_xi, grads[4 * i], grads[4 * i + 1], grads[4 * i + 2], grads[4 * i + 3],
-                                workspace, stream);
-    if (rc) return rc;
+    BLVM_TRY(blvm_wavenet_block_bwd(xi, params[4 * i], params[4 * i + 2], reserve + lay.res_off[i], d_o, Si ? d_skips[groups[i]] : nullptr, lay.L_in[i],
+                                    B, C, Si, dilations[i], T_skip, inv_std, d_xi, grads[4 * i], grads[4 * i + 1], grads[4 * i + 2], grads[4 * i + 3],
+                                    workspace, stream));
     d_o = d_xi;
   }
   return BLVM_OK;

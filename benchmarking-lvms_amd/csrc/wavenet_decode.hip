@@ -435,10 +435,8 @@ extern "C" int blvm_wavenet_decode(const float* packed, const int* dilations, in
   for (int i = 0; i < n_blocks; ++i) {
     const float* bw = packed + L.blocks + (size_t)i * L.block_stride;
     float* bt = scratch + (size_t)i * wt_stride;
-    int rc = t16_pack_rows(bw, 2 * C, 2 * C, 2 * C, bt, static_cast<hipStream_t>(stream));
-    if (rc) return rc;
-    rc = t16_pack_rows(bw + L.rs_w, C, C + S, C, bt + (size_t)2 * C * 2 * C, static_cast<hipStream_t>(stream));
-    if (rc) return rc;
+    BLVM_TRY(t16_pack_rows(bw, 2 * C, 2 * C, 2 * C, bt, static_cast<hipStream_t>(stream)));
+    BLVM_TRY(t16_pack_rows(bw + L.rs_w, C, C + S, C, bt + (size_t)2 * C * 2 * C, static_cast<hipStream_t>(stream)));
   }
   a.wt = scratch;
   a.queues = scratch + (size_t)n_blocks * wt_stride;

@@ -281,6 +281,22 @@ def test_persistent_chain_tile_iterator_covers_every_tile_once(tmp_path):
     assert out.returncode == 0 and "0 errors" in out.stdout, out.stdout + out.stderr
 
 
+def test_arena_carves_rounded_pieces_and_polled_regions(tmp_path):
+    """Host-side check of the buffer carving every sequence driver uses (csrc/common.h Arena): a null base gives sizes only, offsets
+    are rounded to 4 floats, take(0) returns the running end, and bytes_from(p) is the sum of the rounded sizes taken since p (the
+    region a persistent launch polls; a wrong length is an out-of-bounds fill on the GPU)."""
+    import shutil
+    import subprocess
+
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = tmp_path / "arena_test"
+    src = os.path.join(ROOT, "tests", "host", "arena_test.hip")
+    inc = [f"-I{os.path.join(ROOT, 'include')}", f"-I{os.path.join(ROOT, 'benchmarking-lvms_amd', 'csrc')}"]
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", *inc, src, "-o", str(exe)], check=True, timeout=600)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "0 errors" in out.stdout, out.stdout + out.stderr
+
+
 def test_wavenet_stack_buffer_layout_is_host_arithmetic():
     """`blvm_wavenet_stack_floats` (the sizes of the two buffers `blvm_wavenet_stack_fwd / _bwd` slice block outputs and reserves
     from) against the per-block sizes it is defined by; a dilation that leaves no output frames is refused.  No GPU call."""
