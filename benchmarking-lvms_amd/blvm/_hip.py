@@ -13,7 +13,7 @@ import torch
 _LIB_PATH = os.environ.get("BLVM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libblvm_hip.so")
 _lib = None
 
-c_int, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+c_int, c_float, c_void_p, c_size_t, c_double = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double
 
 
 class BlvmHipError(RuntimeError):
@@ -97,6 +97,11 @@ _SIGNATURES = {
                               c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "blvm_dmol_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                               c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "blvm_dmol_bwd_fused_workspace_floats": (c_size_t, [c_int] * 3),
+    "blvm_dmol_bwd_fused": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "blvm_elbo_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "blvm_elbo_bwd": (c_int, [c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "blvm_kl_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
                             c_float, c_void_p, c_void_p, c_void_p]),
     "blvm_kl_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -71,12 +71,13 @@ class LSTMAudio(BaseModel):
             out, hn, cn = ops.lstm_sequence(out, h0, c0, lens, *w)
             hns.append(hn)
             cns.append(cn)
-        dec = ops.mlp(out.view(L * B, H), [m for m in self.decoder if isinstance(m, nn.Linear)], ops.ACT_RELU, 0.0)
+        dec_lin = [m for m in self.decoder if isinstance(m, nn.Linear)]
 
         # mask = arange(L*S) < x_sl  (lstm.py:111): lengths are compared with the SHIFTED target axis
         mask_len = ops.upload_i32(x_sl_host.clamp(max=L * S), dev)
-        log_prob = ops.dmol_log_prob(dec, lik.params.weight, lik.params.bias, y, mask_len, ops.LAYOUT_TIME_MAJOR, B, L * S, L,
-                                     S, lik.num_mix, lik.num_bins, lik.log_epsilon).to(torch.float32)  # fmt: skip
+        dec, log_prob = lik.fused_mlp_log_prob(out.view(L * B, H), dec_lin, ops.ACT_RELU, 0.0, y, mask_len, ops.LAYOUT_TIME_MAJOR, B,
+                                               L * S, L, S)  # fmt: skip
+        log_prob = log_prob.to(torch.float32)
         n_frames = float(x_sl_host.sum())
         loss = -log_prob.sum() / n_frames
 

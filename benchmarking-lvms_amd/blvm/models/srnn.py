@@ -20,7 +20,8 @@ from blvm.evaluation import BitsPerDimMetric, DeferredScalars, KLMetric, LatestM
 from blvm.models.base_model import BaseModel
 from blvm.models.vrnn import LIKELIHOOD_HEADS, LazyNamespace, _linears
 from blvm.modules.convenience import View
-from blvm.modules.distributions import DiagonalGaussianDense, DiagonalGaussianMixtureDense, DiscretizedLogisticMixtureDense
+from blvm.modules.distributions import (DiagonalGaussianDense, DiagonalGaussianMixtureDense, DiscretizedLogisticMixtureDense,
+                                        mlp_log_prob)  # fmt: skip
 from blvm.utils.operations import split_sequence
 from blvm.utils.padding import get_modulo_length
 
@@ -132,15 +133,15 @@ class SRNN(nn.Module):
             d, a, z_0, eps, x_sl_dev, self._chain_params(), H, Z, R, self.residual_posterior, stride, free_nats, head.epsilon
         )
         z = zs[1:]
-        dec = ops.mlp(torch.cat([z, d], -1).view(Tp * B, Z + R), dec_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE)
-        log_prob = lik.fused_log_prob(dec, y, x_sl_dev, ops.LAYOUT_TIME_MAJOR, B, T, Tp, S)  # K7 / K7b / K7c
+        dec, log_prob = mlp_log_prob(lik, torch.cat([z, d], -1).view(Tp * B, Z + R), dec_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE, y, x_sl_dev,
+                                     ops.LAYOUT_TIME_MAJOR, B, T, Tp, S)  # K6 + K7 / K7b / K7c; dec detached
 
+        # elbo = log_prob - kld, loss = -(log_prob - beta * kld_fn).sum() / n_frames, in one kernel
         n_frames = float(x_sl_host.sum())
-        elbo = log_prob - kld
-        loss = -(log_prob - beta * kld_fn).sum() / n_frames
+        loss, elbo, sums4 = ops.elbo_assemble(log_prob, kld, kld_fn, beta, n_frames, kl_raw=True)
         kl = kld  # raw KL (srnn.py:156-160)
 
-        sums = DeferredScalars(torch.stack([loss.detach(), elbo.detach().sum(), log_prob.detach().sum(), kl.detach().sum()]))
+        sums = DeferredScalars(sums4)  # (loss, elbo.sum(), log_prob.sum(), kl.sum())
         ln2 = math.log(2)
         metrics = [
             LossMetric(sums[0], weight_by=B),

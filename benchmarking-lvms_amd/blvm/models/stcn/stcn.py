@@ -20,7 +20,7 @@ from blvm.models.vrnn import LazyNamespace
 from blvm.models.wavenet.wavenet_modules import CausalConv1d, ResidualStack
 from blvm.modules.convenience import AddConstant
 from blvm.modules.distributions import (ConditionalDistribution, DiagonalGaussianDense, DiagonalGaussianMixtureDense,
-                                        DiscretizedLogisticMixtureDense)  # fmt: skip
+                                        DiscretizedLogisticMixtureDense, mlp_log_prob)  # fmt: skip
 
 
 class DiagonalGaussianDenseSTCN(ConditionalDistribution):
@@ -201,8 +201,7 @@ class STCN(BaseModel):
         skip_sum = ot.forward_tm(logits_in, T)  # [T,B,C]: sum of the output blocks' skips
         h = ops.scale_act(skip_sum.view(T * B, C), self.inv_std, 1.0)  # * inv_std (slope 1: no activation)
         up = self.out_upsample[0]
-        dec = ops.linear(h, up.weight, up.bias, ops.ACT_RELU)  # [T*B, S*F]
-        log_prob = lik.fused_log_prob(dec, y, mask_len, ops.LAYOUT_TIME_MAJOR, B, T_y, T, S)  # K7 / K7b / K7c
+        dec, log_prob = mlp_log_prob(lik, h, [up], ops.ACT_RELU, 0.0, y, mask_len, ops.LAYOUT_TIME_MAJOR, B, T_y, T, S)  # dec [T*B, S*F]
 
         kld, kld_fn = sum(klds), sum(klds_fn)
         n_frames = float(x_sl_host.sum())

@@ -20,7 +20,7 @@ from blvm.evaluation import BitsPerDimMetric, DeferredScalars, KLMetric, LatestM
 from blvm.models.base_model import BaseModel
 from blvm.modules.convenience import View
 from blvm.modules.distributions import (DiagonalGaussianDense, DiagonalGaussianMixtureDense,
-                                        DiscretizedLogisticMixtureDense)  # fmt: skip
+                                        DiscretizedLogisticMixtureDense, mlp_log_prob)  # fmt: skip
 
 LIKELIHOOD_HEADS = (DiscretizedLogisticMixtureDense, DiagonalGaussianMixtureDense, DiagonalGaussianDense)
 
@@ -198,16 +198,17 @@ class VRNN(nn.Module):
             eps = torch.randn(Tp, B, Z, device=dev, dtype=torch.float32)
         decin, kld, kld_fn, mu_q, sd_q, mu_p, sd_p, z = self.vrnn_cell.sequence(enc, h0, eps, x_sl_dev, stride, free_nats)
 
-        dec = ops.mlp(decin[:Tp].view(Tp * B, H + R), dec_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE)  # [T'*B, S*F]
-        log_prob = lik.fused_log_prob(dec, y, x_sl_dev, ops.LAYOUT_TIME_MAJOR, B, T, Tp, S)  # K7 / K7b / K7c
+        # decoder MLP (K6) + likelihood head (K7 / K7b / K7c); dec [T'*B, S*F] detached
+        dec, log_prob = mlp_log_prob(lik, decin[:Tp].view(Tp * B, H + R), dec_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE, y, x_sl_dev,
+                                     ops.LAYOUT_TIME_MAJOR, B, T, Tp, S)  # fmt: skip
 
-        # ELBO assembly in float64 as the reference does (mask dtype `float`, vrnn.py:266-279)
+        # ELBO assembly in float64 as the reference does (mask dtype `float`, vrnn.py:266-279), one kernel:
+        # elbo = log_prob - kld, loss = -(log_prob - beta * kld_fn).sum() / n_frames
         n_frames = float(x_sl_host.sum())
-        elbo = log_prob - kld
-        loss = -(log_prob - beta * kld_fn).sum() / n_frames
+        loss, elbo, sums4 = ops.elbo_assemble(log_prob, kld, kld_fn, beta, n_frames)
         kl = kld_fn  # the reference returns the free-nats-clamped KL as `kl` (vrnn.py:275-279); == kld when free_nats is 0
 
-        sums = DeferredScalars(torch.stack([loss.detach(), elbo.detach().sum(), log_prob.detach().sum(), kl.detach().sum()]))
+        sums = DeferredScalars(sums4)  # (loss, elbo.sum(), log_prob.sum(), kl.sum())
         ln2 = math.log(2)
         metrics = [
             LossMetric(sums[0], weight_by=B),

@@ -126,7 +126,9 @@ class _MLPFunction(torch.autograd.Function):
     encoders/decoders end in an activation)."""
 
     @staticmethod
-    def forward(ctx, x, act, slope, *params):
+    def forward(ctx, x, act, slope, head_gates, *params):
+        """`head_gates`: the consumer of the output is a fused likelihood head whose backward applies the derivative of the LAST
+        activation itself (`mlp_dmol_log_prob`), so the incoming gradient is already that of the last pre-activation."""
         x = _f32c(x)
         n_layers = len(params) // 2
         acts = [x]
@@ -139,7 +141,7 @@ class _MLPFunction(torch.autograd.Function):
             gemm(0, 0, M, N, K, inp, inp.stride(0), _f32c(W), K, out, N, bias=_f32c(b) if b is not None else None, act=act,
                  slope=slope)
             acts.append(out)
-        ctx.act, ctx.slope, ctx.n_layers = act, slope, n_layers
+        ctx.act, ctx.slope, ctx.n_layers, ctx.head_gates = act, slope, n_layers, bool(head_gates)
         ctx.save_for_backward(*acts, *params)
         return acts[-1]
 
@@ -150,15 +152,15 @@ class _MLPFunction(torch.autograd.Function):
         acts, params = saved[: n + 1], saved[n + 1 :]
         slope = ctx.slope if ctx.act == ACT_LEAKY else 0.0
         dy = _f32c(dy)
-        # derivative of the last activation (no producing GEMM to fuse it into)
-        if ctx.act != ACT_NONE:
+        # derivative of the last activation (no producing GEMM to fuse it into; a fused likelihood head has applied it already)
+        if ctx.act != ACT_NONE and not ctx.head_gates:
             dz = torch.empty_like(dy)
             check(load().blvm_act_bwd_f32(ptr(dy), ptr(acts[n]), slope, ptr(dz), dz.numel(), stream_ptr()), "blvm_act_bwd_f32")
         else:
             dz = dy
         grads: List[Optional[torch.Tensor]] = [None] * (2 * n)
         # every weight / bias gradient of the chain as a view of ONE zero-filled buffer (one fill launch instead of 2n)
-        want = [ctx.needs_input_grad[3 + i] and params[i] is not None for i in range(2 * n)]
+        want = [ctx.needs_input_grad[4 + i] and params[i] is not None for i in range(2 * n)]
         sizes = [(params[i].numel() + 3) // 4 * 4 if want[i] else 0 for i in range(2 * n)]
         flat = torch.zeros(sum(sizes), device=dy.device, dtype=torch.float32)
         views, off = [], 0
@@ -182,19 +184,19 @@ class _MLPFunction(torch.autograd.Function):
                 gemm(0, 1, M, K, N, dz, N, _f32c(W), K, dx, K, slope=slope, gate=gate, ldg=K)
                 dz = dx
         wgrad_group(jobs, acts[0].shape[0])
-        return (dz if ctx.needs_input_grad[0] else None, None, None, *grads)
+        return (dz if ctx.needs_input_grad[0] else None, None, None, None, *grads)
 
 
 def mlp(x2d: torch.Tensor, layers: Sequence[torch.nn.Linear], act: int = ACT_LEAKY, slope: float = LEAKY_SLOPE):
     params = []
     for lin in layers:
         params += [lin.weight, lin.bias]
-    return _MLPFunction.apply(x2d, act, slope, *params)
+    return _MLPFunction.apply(x2d, act, slope, False, *params)
 
 
 def linear(x2d: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, act: int = ACT_NONE, slope: float = 0.0):
     """act(x W^T + b) for a raw [out,in] weight (e.g. a 1x1 Conv1d weight viewed as a matrix)."""
-    return _MLPFunction.apply(x2d, act, slope, weight, bias)
+    return _MLPFunction.apply(x2d, act, slope, False, weight, bias)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -241,9 +243,38 @@ def _head_linear_grads(d_par, dec, W, b, F, n_frames, need_w, need_b):
     return dW, db
 
 
+_F32_TWINS = {}  # data_ptr of a float64 gradient vector written by blvm_elbo_bwd -> (that tensor, its version, its float32 rounding)
+
+
+def _grad_f32(g: torch.Tensor) -> torch.Tensor:
+    """Incoming float64 per-utterance gradient as the contiguous float32 vector the kernels read.  When `g` is the very tensor the ELBO
+    backward kernel wrote (same storage, not modified since), that kernel's own float32 copy is taken instead of a cast launch."""
+    twin = _F32_TWINS.get(g.data_ptr()) if g.dtype == torch.float64 else None
+    if twin is not None and twin[0].shape == g.shape and g.is_contiguous() and g._version == twin[1]:
+        return twin[2]
+    return g.to(torch.float32).contiguous()
+
+
+_DMOL_WS = {}  # (device index, stream) -> workspace of the fused DMoL backward (tickets zero between launches)
+
+
+def _dmol_workspace(device, floats: int) -> torch.Tensor:
+    key = (device.index, stream_ptr())
+    ws = _DMOL_WS.get(key)
+    if ws is None or ws.numel() < floats:
+        ws = _DMOL_WS[key] = torch.zeros(floats, device=device, dtype=torch.float32)
+    return ws
+
+
+BLVM_NOT_APPLICABLE = 1  # include/blvm_hip.h
+
+
 class _DMoLFunction(torch.autograd.Function):
+    """`act_slope` >= 0: `dec` is the output of `_MLPFunction(..., head_gates=True)` with that (leaky) ReLU slope, and the gradient
+    returned for it is that of the last PRE-activation; < 0: the plain gradient of `dec`."""
+
     @staticmethod
-    def forward(ctx, dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, num_bins, log_eps):
+    def forward(ctx, dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, num_bins, log_eps, act_slope):
         dec, y = _f32c(dec), _f32c(y)
         W, b = (_f32c(W), _f32c(b)) if W is not None else (None, None)
         _dmol_check_shapes(dec, W, y, B, T, Tp, S, num_mix)
@@ -255,16 +286,31 @@ class _DMoLFunction(torch.autograd.Function):
         )  # fmt: skip
         ctx.has_linear = W is not None
         ctx.save_for_backward(dec, y, x_sl_dev, *((W, b) if W is not None else ()))
-        ctx.cfg = (layout, B, T, Tp, S, num_mix, num_bins, log_eps)
+        ctx.cfg = (layout, B, T, Tp, S, num_mix, num_bins, log_eps, float(act_slope))
         return log_prob
 
     @staticmethod
     def backward(ctx, g):
         dec, y, x_sl_dev, *lin = ctx.saved_tensors
         W, b = lin if ctx.has_linear else (None, None)
-        layout, B, T, Tp, S, num_mix, num_bins, log_eps = ctx.cfg
-        g32 = g.to(torch.float32).contiguous()
+        layout, B, T, Tp, S, num_mix, num_bins, log_eps, act_slope = ctx.cfg
+        g32 = _grad_f32(g)
         F = 3 * num_mix
+        lib = load()
+        need_w, need_b = ctx.has_linear and ctx.needs_input_grad[1], ctx.has_linear and ctx.needs_input_grad[2]
+        ws_floats = lib.blvm_dmol_bwd_fused_workspace_floats(B, Tp, S) if ctx.has_linear else 0
+        if ws_floats:
+            # one launch: dz (the activation derivative applied), dW and db; d_par is never stored
+            dz = torch.empty_like(dec)
+            dW = torch.empty_like(W) if need_w else None
+            db = torch.empty_like(b) if need_b else None
+            ws = _dmol_workspace(dec.device, ws_floats) if (need_w or need_b) else None
+            rc = lib.blvm_dmol_bwd_fused(ptr(dec), layout, ptr(W), ptr(b), ptr(y), ptr(x_sl_dev), ptr(g32), B, T, Tp, S, num_mix,
+                                         num_bins, log_eps, act_slope, ptr(dz), ptr(dW), ptr(db), ptr(ws), stream_ptr())  # fmt: skip
+            if rc == 0:
+                return (dz if ctx.needs_input_grad[0] else None, dW, db) + (None,) * 11
+            if rc != BLVM_NOT_APPLICABLE:
+                check(rc, "blvm_dmol_bwd_fused")
         d_dec = torch.empty_like(dec)
         d_par = torch.empty_like(dec) if ctx.has_linear else None
         check(
@@ -273,14 +319,34 @@ class _DMoLFunction(torch.autograd.Function):
             "blvm_dmol_bwd",
         )  # fmt: skip
         n_frames = dec.numel() // F
-        dW, db = _head_linear_grads(d_par, dec, W, b, F, n_frames, ctx.has_linear and ctx.needs_input_grad[1], ctx.has_linear and ctx.needs_input_grad[2])
-        return (d_dec if ctx.needs_input_grad[0] else None, dW, db) + (None,) * 10
+        dW, db = _head_linear_grads(d_par, dec, W, b, F, n_frames, need_w, need_b)
+        if act_slope >= 0.0 and ctx.needs_input_grad[0]:
+            dz = torch.empty_like(d_dec)
+            check(lib.blvm_act_bwd_f32(ptr(d_dec), ptr(dec), act_slope, ptr(dz), dz.numel(), stream_ptr()), "blvm_act_bwd_f32")
+            d_dec = dz
+        return (d_dec if ctx.needs_input_grad[0] else None, dW, db) + (None,) * 11
+
+
+def mlp_dmol_log_prob(x2d, layers, W, b, y, x_sl_dev, layout, B, T, Tp, S, act: int = ACT_LEAKY, slope: float = LEAKY_SLOPE,
+                      num_mix=10, num_bins=256, log_eps=-7.0):  # fmt: skip
+    """`mlp(x2d, layers, act, slope)` feeding `dmol_log_prob(., W, b, ...)` as one pair of autograd nodes whose backward never writes
+    d_par or d_dec: the head's backward kernel hands the MLP the gradient of its last pre-activation and accumulates dW / db itself.
+    Returns (dec DETACHED — the activations [rows, S*3*num_mix] for samplers / modes —, log_prob [B] float64)."""
+    if act == ACT_NONE or W is None:
+        dec = mlp(x2d, layers, act, slope)
+        return dec.detach(), dmol_log_prob(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, num_bins, log_eps)
+    params = []
+    for lin in layers:
+        params += [lin.weight, lin.bias]
+    dec = _MLPFunction.apply(x2d, act, slope, True, *params)  # (differentiable ONLY through the head below)
+    gate = slope if act == ACT_LEAKY else 0.0
+    return dec.detach(), _DMoLFunction.apply(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, num_bins, log_eps, gate)
 
 
 def dmol_log_prob(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix=10, num_bins=256, log_eps=-7.0):
     """Per-utterance masked DMoL log-likelihood sums [B] (float64) of targets y [B,T] given decoder activations
     `dec` ([rows, S*3*num_mix], rows ordered by `layout`)."""
-    return _DMoLFunction.apply(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, num_bins, log_eps)
+    return _DMoLFunction.apply(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, num_bins, log_eps, -1.0)
 
 
 class _GaussHeadFunction(torch.autograd.Function):
@@ -411,6 +477,52 @@ def gaussian_kl_sums(mu_q, sd_q, mu_p, sd_p, x_sl_dev, layout, B, Tp, Z, stride,
     """(kld[B], kld_fn[B]) in float64: masked sums of the analytic KL and of max(KL, free_nats/Z)."""
     fn_floor = float(free_nats) / Z if free_nats else 0.0
     return _KLFunction.apply(mu_q, sd_q, mu_p, sd_p, x_sl_dev, layout, B, Tp, Z, stride, fn_floor)
+
+
+class _ELBOFunction(torch.autograd.Function):
+    """(log_prob, kld, kld_fn [B] float64) -> (loss scalar, elbo [B], sums [4]) in one launch; backward one launch (`blvm_elbo_bwd`)."""
+
+    @staticmethod
+    def forward(ctx, log_prob, kld, kld_fn, beta, n_frames, kl_raw):
+        B = log_prob.numel()
+        for t in (log_prob, kld, kld_fn):
+            if t.dtype != torch.float64 or t.shape != (B,):
+                raise _hip.BlvmHipError("elbo_assemble: log_prob, kld and kld_fn must be float64 [B]")
+        log_prob, kld, kld_fn = log_prob.contiguous(), kld.contiguous(), kld_fn.contiguous()
+        f64 = dict(device=log_prob.device, dtype=torch.float64)
+        loss, elbo, sums = torch.empty((), **f64), torch.empty(B, **f64), torch.empty(4, **f64)
+        check(load().blvm_elbo_fwd(ptr(log_prob), ptr(kld), ptr(kld_fn), float(beta), float(n_frames), B, int(kl_raw), ptr(elbo), ptr(loss),
+                                   ptr(sums), stream_ptr()), "blvm_elbo_fwd")  # fmt: skip
+        ctx.cfg = (float(beta), float(n_frames), B)
+        ctx.mark_non_differentiable(sums)
+        ctx.set_materialize_grads(False)
+        return loss, elbo, sums
+
+    @staticmethod
+    def backward(ctx, g_loss, g_elbo, _g_sums):
+        beta, n_frames, B = ctx.cfg
+        if g_loss is None and g_elbo is None:
+            return (None,) * 6
+        dev = g_loss.device if g_loss is not None else g_elbo.device
+        g_loss = g_loss.to(torch.float64).contiguous() if g_loss is not None else None  # (no launch: it is float64 already)
+        g_elbo = g_elbo.to(torch.float64).contiguous() if g_elbo is not None else None
+        g64 = torch.empty(3, B, device=dev, dtype=torch.float64)
+        g32 = torch.empty(3, B, device=dev, dtype=torch.float32)
+        check(load().blvm_elbo_bwd(ptr(g_loss), ptr(g_elbo), beta, n_frames, B, ptr(g64), ptr(g32), stream_ptr()), "blvm_elbo_bwd")
+        _F32_TWINS.clear()  # (the consumers of the previous step's vectors have run)
+        outs = []
+        for i in range(3):
+            v = g64[i]
+            _F32_TWINS[v.data_ptr()] = (v, v._version, g32[i])
+            outs.append(v)
+        d_lp, d_fn, d_raw = outs
+        return d_lp, (d_raw if g_elbo is not None else None), d_fn, None, None, None
+
+
+def elbo_assemble(log_prob, kld, kld_fn, beta: float, n_frames: float, kl_raw: bool = False):
+    """(loss, elbo [B], sums [4]) float64: elbo = log_prob - kld, loss = -(log_prob - beta * kld_fn).sum() / n_frames, sums = (loss,
+    elbo.sum(), log_prob.sum(), kl.sum()) with kl = kld if `kl_raw` else kld_fn — `sums` detached, for `DeferredScalars`."""
+    return _ELBOFunction.apply(log_prob, kld, kld_fn, beta, n_frames, kl_raw)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -558,8 +670,8 @@ class _VRNNSeqFunction(torch.autograd.Function):
         lib = load()
         f32 = dict(device=dev, dtype=torch.float32)
         d_decin = _f32c(d_decin) if d_decin is not None else torch.zeros_like(decin)
-        c_raw = g_kld.to(torch.float32).contiguous() if g_kld is not None else None
-        c_fn = g_kld_fn.to(torch.float32).contiguous() if g_kld_fn is not None else None
+        c_raw = _grad_f32(g_kld) if g_kld is not None else None
+        c_fn = _grad_f32(g_kld_fn) if g_kld_fn is not None else None
         grads = _zeros_like_many(params)
         d_enc = torch.empty_like(enc)
         d_h0 = torch.empty(B, R, **f32) if ctx.has_h0 else None
@@ -791,8 +903,8 @@ class _SRNNLatentFunction(torch.autograd.Function):
         f32 = dict(device=d.device, dtype=torch.float32)
         d_zs = _f32c(d_zs) if d_zs is not None else torch.zeros_like(zs)
         d_z = d_zs[1:]  # rows 1.. are the sampled latents; row 0 is z0 (its direct gradient is added below)
-        c_raw = g_kld.to(torch.float32).contiguous() if g_kld is not None else None
-        c_fn = g_kld_fn.to(torch.float32).contiguous() if g_kld_fn is not None else None
+        c_raw = _grad_f32(g_kld) if g_kld is not None else None
+        c_fn = _grad_f32(g_kld_fn) if g_kld_fn is not None else None
         grads = _zeros_like_many(params)
         d_d, d_a = torch.empty_like(d), torch.empty_like(a)
         d_z0 = torch.empty(B, Z, **f32) if ctx.has_z0 else None

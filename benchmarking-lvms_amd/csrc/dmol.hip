@@ -45,6 +45,11 @@ struct DmolArgs {
   float half_bin, low_edge, high_edge, log_half_bins, log_eps;
   int kind;                 // 0 discretized logistic mixture, 1 Gaussian mixture
   float sd_beta, sd_eps;    // kind 1: sd = softplus_beta(raw) + sd_eps
+  // fused backward only (dmol_rows_kernel<true, 1 or 2>)
+  float act_slope;          // >= 0: `dec` is the output of a (leaky) ReLU with this slope, whose derivative goes into d_dec
+  float* dW;                // [F, F] = d_par^T dec, or NULL
+  float* db;                // [F] = column sums of d_par, or NULL
+  float* ws;                // tickets + per-workgroup / per-group partial tiles (dW or db wanted)
 };
 
 // Stage 256 frames x 30 floats (contiguous in HBM) into LDS [256][31].
@@ -381,6 +386,10 @@ __global__ __launch_bounds__(256) void dmol_kernel(DmolArgs a) {
 // left is arithmetic, not HBM: per unit ~640 vector instructions of mixture math (19 us of a SIMD's time per launch) plus 30 (60)
 // fp32 MFMAs (12.5 us per product pass) that do NOT overlap — SQ_VALU_MFMA_COEXEC_CYCLES is 0: the fp32 matrix instructions share
 // the vector issue — against 20 us (58 us) of HBM time.  Integer divisions are 32-bit and wave-uniform.
+// The fused backward (FUSED 1 / 2, blvm_dmol_bwd_fused) folds the two launches that only re-read this kernel's outputs into it: the
+// derivative of the activation that produced `dec` is applied in the store (dz leaves, d_dec never exists) and the head Linear's dW / db
+// are accumulated on the matrix pipe while d_par is in the image (d_par is never stored): 244 B/frame of HBM instead of 364 + 360 (the
+// activation pass) + 240 (the 30 x 30 weight-gradient GEMM's operands).  DESIGN 8-dt has the registers, occupancy and timings.
 // ---------------------------------------------------------------------------------------------------------------
 // A unit = the 64 frames x 30 floats (7 680 bytes, contiguous and 16-byte aligned in HBM) one wave works on.  Its LDS image is a
 // VERBATIM copy (no padding, no index arithmetic: 480 float4, lane q -> float4 q), private to the wave:
@@ -447,8 +456,69 @@ __device__ __forceinline__ void mfma_image_30x30(float* __restrict__ lds, const 
   }
 }
 
-template <bool BWD>
-__global__ __launch_bounds__(256) void dmol_rows_kernel(DmolArgs a, int units, int nchunks) {
+// the image (d_dec) to HBM times the derivative of the activation that produced `dec` (the unit, read again in the layout of this
+// very store): blvm_act_bwd_f32's rule, element by element
+#define ACT_GATE(v, d, slope)                                                                                       \
+  do {                                                                                                              \
+    v.x = d.x > 0.f ? v.x : v.x * (slope); v.y = d.y > 0.f ? v.y : v.y * (slope);                                   \
+    v.z = d.z > 0.f ? v.z : v.z * (slope); v.w = d.w > 0.f ? v.w : v.w * (slope);                                   \
+  } while (0)
+#define STORE_UNIT_ACT(n, dst, lds, lane, slope)                                                                    \
+  do {                                                                                                              \
+    const f32x4* s4_ = reinterpret_cast<const f32x4*>(lds);                                                         \
+    f32x4* d4_ = reinterpret_cast<f32x4*>(dst);                                                                     \
+    f32x4 v_;                                                                                                       \
+    v_ = s4_[(lane)]; ACT_GATE(v_, n##0, slope); d4_[(lane)] = v_;                                                  \
+    v_ = s4_[(lane) + 64]; ACT_GATE(v_, n##1, slope); d4_[(lane) + 64] = v_;                                        \
+    v_ = s4_[(lane) + 128]; ACT_GATE(v_, n##2, slope); d4_[(lane) + 128] = v_;                                      \
+    v_ = s4_[(lane) + 192]; ACT_GATE(v_, n##3, slope); d4_[(lane) + 192] = v_;                                      \
+    v_ = s4_[(lane) + 256]; ACT_GATE(v_, n##4, slope); d4_[(lane) + 256] = v_;                                      \
+    v_ = s4_[(lane) + 320]; ACT_GATE(v_, n##5, slope); d4_[(lane) + 320] = v_;                                      \
+    v_ = s4_[(lane) + 384]; ACT_GATE(v_, n##6, slope); d4_[(lane) + 384] = v_;                                      \
+    if ((lane) < 32) { v_ = s4_[448 + (lane)]; ACT_GATE(v_, n##7, slope); d4_[448 + (lane)] = v_; }                 \
+  } while (0)
+
+// ---- the head Linear's own gradients, accumulated inside the fused backward ------------------------------------------------------
+// dW[n][k] = sum_f d_par[f][n] dec[f][k] is one 32 x 32 tile per wave (30 x 30 used; column 30 of the B operand is 1.0, so column 30
+// of the tile is db), K = the unit's 64 frames = 32 v_mfma_f32_32x32x2_f32, the accumulator living in registers across the wave's
+// unit loop.  At the end: four wave tiles -> one workgroup tile (LDS, waves in order) -> HBM; the last workgroup of each group of
+// DW_GROUP sums the group's tiles in index order, the last group to finish sums the group tiles in index order and writes dW / db.
+// No float atomics: the result is the same from run to run.  Hand-off (three workgroups per CU, so not the one-per-CU `sc1` row of
+// the measured table: the architectural form): plain stores -> every wave's vmcnt(0) -> workgroup barrier -> one lane's agent
+// release -> ticket (agent-scope add whose returned value names the last arrival) -> that lane's agent acquire -> barrier -> loads.
+constexpr int DW_TILE = 32 * 32;
+constexpr int DW_GROUP = 32;
+constexpr int DW_TICKETS = 256;  // ints at the head of the workspace: [0] the groups' ticket, [1 + g] group g's; zero between launches
+
+__device__ __forceinline__ bool last_arrival(int* ticket, int count, int* flag) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const bool last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == count - 1;
+    if (last) {
+      __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (nobody else touches it again in this launch)
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    *flag = last;
+  }
+  __syncthreads();
+  return *flag != 0;
+}
+
+__device__ __forceinline__ f32x4 sum_tiles(const float* tiles, int n) {  // thread q: float4 q of the sum of n tiles, in index order
+  const f32x4* t4 = reinterpret_cast<const f32x4*>(tiles) + threadIdx.x;
+  f32x4 s = t4[0];
+  for (int i = 1; i < n; ++i) s += t4[(size_t)i * (DW_TILE / 4)];
+  return s;
+}
+
+// FUSED (backward only): 0 the plain backward; 1 the activation derivative folded into the store (dz instead of d_dec, no d_par); 2 that
+// plus the head Linear's dW / db accumulated in the launch.
+template <bool BWD, int FUSED = 0>
+__global__ __launch_bounds__(256, 3) void dmol_rows_kernel(DmolArgs a, int units, int nchunks) {
   __shared__ __attribute__((aligned(16))) float lds_all[4 * UNIT_FLOATS];
   __shared__ double wsum[4];
   __shared__ float wtab[2 * 15 * 64];  // the head's Linear as MFMA B operands per lane: [0] forward (W^T), [1] backward (W)
@@ -482,6 +552,11 @@ __global__ __launch_bounds__(256) void dmol_rows_kernel(DmolArgs a, int units, i
   }
   __syncthreads();
   double acc = 0.0;
+  constexpr bool wgrad = FUSED == 2;
+  const float slope = a.act_slope >= 0.f ? a.act_slope : 1.f;  // (no activation in front of the head: g * 1 either way, exactly g)
+  f32x16 dwacc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) dwacc[r] = 0.f;
   for (; u < u_end; u += 4) {
     const int t = u / upr, j0 = (u - t * upr) * 64;
     const size_t base = unit_base(u);
@@ -517,15 +592,67 @@ __global__ __launch_bounds__(256) void dmol_rows_kernel(DmolArgs a, int units, i
         for (int i = 0; i < F_MAX / 2; ++i) fp[i] = make_float2(p[2 * i] * gv, p[2 * i + 1] * gv);
       }
       wave_sync();
-      if (a.d_par != nullptr) {
+      if (!FUSED && a.d_par != nullptr) {
         store_unit(a.d_par + base, lds, lane);      // d(loss)/d(head output): what the weight / bias gradient GEMM reads
         wave_sync();
+      }
+      // FUSED, dW / db wanted: both operands of dW += d_par^T dec for this unit are requested now — d_par from the image, before the
+      // product below overwrites it; dec once more from L2 (this wave read the unit a microsecond ago), in the operand layout — and
+      // consumed AFTER that product, which covers the round trip.  Keeping dec live across the mixture math instead would cost 32
+      // registers there (137 + 16 accumulators + 32 > the 168 of three waves per SIMD), a second image per wave 30 KB of LDS per
+      // workgroup (69 KB: two workgroups per CU).
+      float bv[32], av[32];
+      if (wgrad) {
+        const int li = lane & 31, lh = lane >> 5, cl = min(li, F_MAX - 1);  // (li >= 30: any in-bounds column; those rows are not stored)
+        const float* drow = a.dec + base + lh * F_MAX + cl;
+        const float* prow = lds + lh * F_MAX + cl;
+#pragma unroll
+        for (int s = 0; s < 32; ++s) bv[s] = drow[s * 2 * F_MAX];
+#pragma unroll
+        for (int s = 0; s < 32; ++s) av[s] = prow[s * 2 * F_MAX];
+        wave_sync();  // (the d_par reads are issued before the product below overwrites the image)
       }
       if (lin) {
         mfma_image_30x30(lds, wtab + 15 * 64, 0.f, lane);  // d_dec = d_par W, in place
         wave_sync();
       }
-      store_unit(a.d_dec + base, lds, lane);
+      if (FUSED) LOAD_UNIT(nxt, a.dec + base, lane);  // the unit in the layout of the store below, for the activation's derivative
+      if (wgrad) {
+        const bool one = (lane & 31) >= F_MAX;  // B column 30 = 1.0: tile column 30 is db
+#pragma unroll
+        for (int s = 0; s < 32; ++s) dwacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], one ? 1.f : bv[s], dwacc, 0, 0, 0);
+      }
+      if (FUSED) STORE_UNIT_ACT(nxt, a.d_dec + base, lds, lane, slope);
+      else store_unit(a.d_dec + base, lds, lane);
+    }
+  }
+  if (wgrad) {
+    __shared__ int last_flag;
+    const int li = lane & 31, lh = lane >> 5;
+    wave_sync();  // the last unit's image reads are issued; the wave's tile goes to the head of its own image
+#pragma unroll
+    for (int r = 0; r < 16; ++r) lds[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + li] = dwacc[r];
+    __syncthreads();
+    const f32x4* t4 = reinterpret_cast<const f32x4*>(lds_all) + threadIdx.x;
+    f32x4 s = t4[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) s += t4[w * (UNIT_FLOATS / 4)];
+    int* tickets = reinterpret_cast<int*>(a.ws);
+    float* parts = a.ws + DW_TICKETS;
+    float* gparts = parts + (size_t)gridDim.x * DW_TILE;
+    const int group = blockIdx.x / DW_GROUP, ngroups = (gridDim.x + DW_GROUP - 1) / DW_GROUP;
+    const int gsize = min(DW_GROUP, (int)gridDim.x - group * DW_GROUP);
+    reinterpret_cast<f32x4*>(parts + (size_t)blockIdx.x * DW_TILE)[threadIdx.x] = s;
+    if (!last_arrival(tickets + 1 + group, gsize, &last_flag)) return;
+    s = sum_tiles(parts + (size_t)group * DW_GROUP * DW_TILE, gsize);
+    reinterpret_cast<f32x4*>(gparts + (size_t)group * DW_TILE)[threadIdx.x] = s;
+    if (!last_arrival(tickets, ngroups, &last_flag)) return;
+    s = sum_tiles(gparts, ngroups);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int e = 4 * threadIdx.x + c, n = e >> 5, k = e & 31;
+      if (n < F_MAX && k < F_MAX && a.dW != nullptr) a.dW[n * F_MAX + k] = s[c];
+      if (n < F_MAX && k == F_MAX && a.db != nullptr) a.db[n] = s[c];
     }
   }
   if (!BWD) {
@@ -537,31 +664,37 @@ __global__ __launch_bounds__(256) void dmol_rows_kernel(DmolArgs a, int units, i
   }
 }
 
+// Workgroups of a rows launch: few and long-lived.  A wave's prologue (x_sl, 30 weight registers, its first unit: two dependent HBM
+// round trips) is ~4 us, a unit ~1.5 us of its time — at 2 units per wave (2048 workgroups) the waves spent 40 % of their lives
+// parked.  About three workgroups per CU (what the registers allow), every wave walking its chunk.
+// (Requesting the next unit into 32 registers ahead of time costs a wave of occupancy in both kernels and measured no faster
+// than one more resident wave per SIMD covering the load — same box: forward 44.8 vs 42.3 us, backward 95.6 vs 92.7.)
+template <bool BWD, int FUSED>
+int rows_nchunks(int B, long long units) {
+  int nchunks = (int)((units + 3) / 4);
+  static const int wg_env = [] { const char* e = getenv("BLVM_DMOL_WGS"); return e ? atoi(e) : 0; }();
+  static int wg_fill = 0;  // workgroups that fill the chip once: resident workgroups per CU (by registers) x CUs
+  if (wg_fill == 0) {
+    int per_cu = 0, dev = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&dmol_rows_kernel<BWD, FUSED>), 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+    (void)hipGetLastError();
+    wg_fill = per_cu * cus;
+  }
+  const int wg_target = wg_env > 0 ? wg_env : wg_fill;
+  const int cap = (wg_target + B - 1) / B;
+  if (nchunks > cap) nchunks = cap;
+  if (nchunks < 1) nchunks = 1;
+  return nchunks;
+}
+
 template <bool BWD>
 int launch_dmol(DmolArgs& a, hipStream_t s) {
   if (a.S % 64 == 0 && aligned16(a.dec) && (!BWD || (aligned16(a.d_dec) && (a.d_par == nullptr || aligned16(a.d_par))))) {
     const long long units = (long long)a.Tp * (a.S / 64);
     BLVM_REQUIRE(units < (1ll << 31), "dmol: too many frames");
-    // Few, long-lived workgroups: a wave's prologue (x_sl, 30 weight registers, its first unit: two dependent HBM round trips) is
-    // ~4 us, a unit ~1.5 us of its time — at 2 units per wave (2048 workgroups) the waves spent 40 % of their lives parked.  About
-    // three workgroups per CU (what the registers allow), every wave walking its chunk.
-    // (Requesting the next unit into 32 registers ahead of time costs a wave of occupancy in both kernels and measured no faster
-    // than one more resident wave per SIMD covering the load — same box: forward 44.8 vs 42.3 us, backward 95.6 vs 92.7.)
-    int nchunks = (int)((units + 3) / 4);
-    static const int wg_env = [] { const char* e = getenv("BLVM_DMOL_WGS"); return e ? atoi(e) : 0; }();
-    static int wg_fill = 0;  // workgroups that fill the chip once: resident workgroups per CU (by registers) x CUs
-    if (wg_fill == 0) {
-      int per_cu = 0, dev = 0, cus = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&dmol_rows_kernel<BWD>), 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-      (void)hipGetLastError();
-      wg_fill = per_cu * cus;
-    }
-    const int wg_target = wg_env > 0 ? wg_env : wg_fill;
-    const int cap = (wg_target + a.B - 1) / a.B;
-    if (nchunks > cap) nchunks = cap;
-    if (nchunks < 1) nchunks = 1;
-    hipLaunchKernelGGL((dmol_rows_kernel<BWD>), dim3((unsigned)(a.B * nchunks)), dim3(256), 0, s, a, (int)units, nchunks);
+    const int nchunks = rows_nchunks<BWD, 0>(a.B, units);
+    hipLaunchKernelGGL((dmol_rows_kernel<BWD, 0>), dim3((unsigned)(a.B * nchunks)), dim3(256), 0, s, a, (int)units, nchunks);
   } else {
     const long long blocks = (a.n_frames + FPB - 1) / FPB;
     BLVM_REQUIRE(blocks < (1ll << 31), "dmol: too many frames");
@@ -569,6 +702,20 @@ int launch_dmol(DmolArgs& a, hipStream_t s) {
   }
   return BLVM_OK;
 }
+
+// The fused backward runs on the rows path only; its grid (0: the shape does not take it).
+long long fused_grid(int B, int Tp, int S, bool wgrad, int* nchunks_out) {
+  if (B <= 0 || Tp <= 0 || S <= 0 || S % 64 != 0) return 0;
+  const long long units = (long long)Tp * (S / 64);
+  if (units >= (1ll << 31)) return 0;
+  const int nchunks = wgrad ? rows_nchunks<true, 2>(B, units) : rows_nchunks<true, 1>(B, units);
+  const long long grid = (long long)B * nchunks;
+  if (grid > (long long)(DW_TICKETS - 1) * DW_GROUP) return 0;
+  if (nchunks_out) *nchunks_out = nchunks;
+  return grid;
+}
+
+size_t fused_ws_floats(long long grid) { return DW_TICKETS + (size_t)(grid + (grid + DW_GROUP - 1) / DW_GROUP) * DW_TILE; }
 
 int check_common(const float* dec, const float* W, const float* bias, const float* y, const int32_t* x_sl, int B,
                  int T, int Tp, int S, int num_mix, int num_bins, int layout) {
@@ -624,6 +771,37 @@ extern "C" int blvm_dmol_bwd(const float* dec, int layout, const float* W, const
   a.d_par = d_par;
   BLVM_TRY(launch_dmol<true>(a, static_cast<hipStream_t>(stream)));
   BLVM_CHECK_LAUNCH("dmol_bwd");
+  return BLVM_OK;
+}
+
+extern "C" size_t blvm_dmol_bwd_fused_workspace_floats(int B, int Tp, int S) {
+  const long long grid = blvm::fused_grid(B, Tp, S, true, nullptr);
+  return grid > 0 ? blvm::fused_ws_floats(grid) : 0;
+}
+
+extern "C" int blvm_dmol_bwd_fused(const float* dec, int layout, const float* W, const float* bias, const float* y,
+                                   const int32_t* x_sl, const float* g_b, int B, int T, int Tp, int S, int num_mix,
+                                   int num_bins, float log_eps, float act_slope, float* dz, float* dW, float* db,
+                                   float* workspace, void* stream) {
+  using namespace blvm;
+  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, num_bins, layout));
+  BLVM_REQUIRE(g_b && dz, "dmol_bwd_fused: null pointer");
+  BLVM_REQUIRE(workspace || (!dW && !db), "dmol_bwd_fused: dW / db need the workspace");
+  int nchunks = 0;
+  const bool wgrad = dW != nullptr || db != nullptr;
+  const long long grid = fused_grid(B, Tp, S, wgrad, &nchunks);
+  if (grid == 0 || W == nullptr || !aligned16(dec) || !aligned16(dz) || (workspace && !aligned16(workspace))) return BLVM_NOT_APPLICABLE;
+  DmolArgs a = make_args(dec, layout, W, bias, y, x_sl, B, T, Tp, S, num_bins, log_eps);
+  a.g_b = g_b;
+  a.d_dec = dz;
+  a.act_slope = act_slope;
+  a.dW = dW;
+  a.db = db;
+  a.ws = wgrad ? workspace : nullptr;
+  const int units = (int)((long long)Tp * (S / 64));
+  if (wgrad) hipLaunchKernelGGL((dmol_rows_kernel<true, 2>), dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream), a, units, nchunks);
+  else hipLaunchKernelGGL((dmol_rows_kernel<true, 1>), dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream), a, units, nchunks);
+  BLVM_CHECK_LAUNCH("dmol_bwd_fused");
   return BLVM_OK;
 }
 

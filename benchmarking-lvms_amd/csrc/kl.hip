@@ -270,3 +270,73 @@ extern "C" int blvm_kl_bwd(const float* mu_q, const float* sd_q, const float* mu
   BLVM_CHECK_LAUNCH("kl_bwd");
   return BLVM_OK;
 }
+
+// ---- ELBO assembly: what the models compute from the per-utterance float64 sums (`VRNN.compute_elbo` blvm/models/vrnn.py:266-279,
+// srnn.py:150-160), one launch each way instead of ~10 single-workgroup ATen launches each way ---------------------------------------
+namespace blvm {
+namespace {
+
+// One wave.  Lane l adds utterances l, l + 64, ... in that order, then a fixed shuffle tree: the sums are the same from run to run.
+__global__ __launch_bounds__(64) void elbo_fwd_kernel(const double* __restrict__ log_prob, const double* __restrict__ kld,
+                                                      const double* __restrict__ kld_fn, double beta, double n_frames, int B,
+                                                      int kl_raw, double* __restrict__ elbo, double* __restrict__ loss,
+                                                      double* __restrict__ sums) {
+  const int lane = threadIdx.x;
+  double s_obj = 0.0, s_elbo = 0.0, s_lp = 0.0, s_kl = 0.0;
+  for (int b = lane; b < B; b += 64) {
+    const double l = log_prob[b], k = kld[b], f = kld_fn[b], e = l - k;
+    elbo[b] = e;
+    s_obj += l - beta * f;
+    s_elbo += e;
+    s_lp += l;
+    s_kl += kl_raw ? k : f;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    s_obj += __shfl_down(s_obj, off, 64);
+    s_elbo += __shfl_down(s_elbo, off, 64);
+    s_lp += __shfl_down(s_lp, off, 64);
+    s_kl += __shfl_down(s_kl, off, 64);
+  }
+  if (lane == 0) {
+    const double v = -s_obj / n_frames;
+    *loss = v;
+    sums[0] = v; sums[1] = s_elbo; sums[2] = s_lp; sums[3] = s_kl;
+  }
+}
+
+// d loss / d log_prob[b] = -(g / n) (+ g_elbo[b]), d loss / d kld_fn[b] = (g / n) beta, d loss / d kld[b] = -g_elbo[b]: the float64
+// values autograd hands on, and their float32 roundings, which is what the likelihood and chain backward kernels read.
+__global__ __launch_bounds__(256) void elbo_bwd_kernel(const double* __restrict__ g_loss, const double* __restrict__ g_elbo, double beta,
+                                                       double n_frames, int B, double* __restrict__ g64, float* __restrict__ g32) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const double t = g_loss != nullptr ? *g_loss / n_frames : 0.0;
+  const double ge = g_elbo != nullptr ? g_elbo[b] : 0.0;
+  const double d_lp = -t + ge, d_fn = t * beta, d_raw = -ge;
+  g64[b] = d_lp; g64[B + b] = d_fn; g64[2 * B + b] = d_raw;
+  g32[b] = (float)d_lp; g32[B + b] = (float)d_fn; g32[2 * B + b] = (float)d_raw;
+}
+
+}  // namespace
+}  // namespace blvm
+
+extern "C" int blvm_elbo_fwd(const double* log_prob, const double* kld, const double* kld_fn, double beta, double n_frames, int B,
+                             int kl_raw, double* elbo, double* loss, double* sums, void* stream) {
+  using namespace blvm;
+  BLVM_REQUIRE(log_prob && kld && kld_fn && elbo && loss && sums && B > 0, "elbo_fwd: bad arguments");
+  hipLaunchKernelGGL(elbo_fwd_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), log_prob, kld, kld_fn, beta, n_frames, B,
+                     kl_raw, elbo, loss, sums);
+  BLVM_CHECK_LAUNCH("elbo_fwd");
+  return BLVM_OK;
+}
+
+extern "C" int blvm_elbo_bwd(const double* g_loss, const double* g_elbo, double beta, double n_frames, int B, double* g64, float* g32,
+                             void* stream) {
+  using namespace blvm;
+  BLVM_REQUIRE(g64 && g32 && B > 0, "elbo_bwd: bad arguments");
+  hipLaunchKernelGGL(elbo_bwd_kernel, dim3((B + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), g_loss, g_elbo, beta,
+                     n_frames, B, g64, g32);
+  BLVM_CHECK_LAUNCH("elbo_bwd");
+  return BLVM_OK;
+}

@@ -27,6 +27,7 @@ extern "C" {
 #define BLVM_EINVAL (-1)  /* bad shape / alignment / null pointer */
 #define BLVM_ELAUNCH (-2) /* HIP launch or runtime error */
 #define BLVM_ENOSUP (-3)  /* configuration not supported by this build */
+#define BLVM_NOT_APPLICABLE 1 /* not an error: the call did nothing because the shape is outside this entry point; take the general one */
 
 int blvm_version(void);
 const char* blvm_last_error(void);
@@ -150,6 +151,18 @@ int blvm_dmol_bwd(const float* dec, int layout, const float* W, const float* bia
                   const int32_t* x_sl, const float* g_b, int B, int T, int Tp, int S, int num_mix, int num_bins,
                   float log_eps, float* d_dec, float* d_par, void* stream);
 
+/*   The same backward with its two consumers folded in (DMoL, rows path: S % 64 == 0, 16-byte aligned buffers, W given; otherwise
+ *   BLVM_NOT_APPLICABLE and nothing is launched).  `dz` = d_dec times the derivative of the activation that produced `dec`
+ *   (act_slope >= 0: dec > 0 ? g : g * act_slope, blvm_act_bwd_f32's rule; act_slope < 0: no activation, dz = d_dec).  dW [F,F] =
+ *   d_par^T dec and db [F] = column sums of d_par are WRITTEN (either may be NULL; both NULL: no accumulation) — d_par itself is
+ *   never stored.  No float atomics: dW and db are identical from run to run.  `workspace`: blvm_dmol_bwd_fused_workspace_floats
+ *   floats (0: the shape does not take this path), needed when dW or db is given; its first 256 words are tickets that must be zero
+ *   before the first launch and are zero again after every launch; launches that share a workspace must be stream-ordered. */
+size_t blvm_dmol_bwd_fused_workspace_floats(int B, int Tp, int S);
+int blvm_dmol_bwd_fused(const float* dec, int layout, const float* W, const float* bias, const float* y,
+                        const int32_t* x_sl, const float* g_b, int B, int T, int Tp, int S, int num_mix, int num_bins,
+                        float log_eps, float act_slope, float* dz, float* dW, float* db, float* workspace, void* stream);
+
 /* K7b / K7c  Gaussian output heads, same calling convention, frame layout, masks and float64 per-utterance sums as K7:
  *   gmm: `DiagonalGaussianMixtureDense.forward` + `.log_prob` (`blvm/modules/distributions.py:153-206`,
  *        `gaussian_mixture_ll` `blvm/utils/log_likelihoods.py:42-60`): dec [rows, S*3*num_mix] -> Linear(30->30) (W NULL:
@@ -192,6 +205,16 @@ int blvm_kl_fwd(const float* mu_q, const float* sd_q, const float* mu_p, const f
 int blvm_kl_bwd(const float* mu_q, const float* sd_q, const float* mu_p, const float* sd_p, int layout,
                 const int32_t* x_sl, const float* c_raw, const float* c_fn, int B, int Tp, int Z, int stride,
                 float fn_floor, float* d_mu_q, float* d_sd_q, float* d_mu_p, float* d_sd_p, void* stream);
+
+/* ELBO assembly from the per-utterance float64 sums (`compute_elbo`, `blvm/models/vrnn.py:266-279`), one launch:
+ *   elbo[b] = log_prob[b] - kld[b];  *loss = -(sum_b log_prob[b] - beta kld_fn[b]) / n_frames;
+ *   sums [4] = (loss, sum elbo, sum log_prob, sum kl) with kl = kld_fn (kl_raw 0) or kld (kl_raw 1); sums in a fixed order over b. */
+int blvm_elbo_fwd(const double* log_prob, const double* kld, const double* kld_fn, double beta, double n_frames, int B,
+                  int kl_raw, double* elbo, double* loss, double* sums, void* stream);
+/*   g_loss: the float64 scalar gradient of loss ON THE DEVICE (NULL = 0), g_elbo [B] that of elbo (NULL = 0).  Writes the gradients
+ *   of (log_prob | kld_fn | kld) as g64 [3,B] float64 and, rounded, as g32 [3,B] float32 (what the backward kernels of K7 / K1 read). */
+int blvm_elbo_bwd(const double* g_loss, const double* g_elbo, double beta, double n_frames, int B, double* g64, float* g32,
+                  void* stream);
 
 /* K8b  Gaussian latent head, elementwise over n = rows*Z: sd = softplus_beta(raw) + sd_eps for prior and posterior
  * (`DiagonalGaussianDenseSTCN.forward`, `blvm/models/stcn/stcn.py:32-76`), posterior combination (mode 0 plain, 1 residual

@@ -30,7 +30,32 @@ def bwd():
     check(lib.blvm_dmol_bwd(ptr(dec), 1, ptr(W), ptr(b), ptr(y), ptr(x_sl), ptr(gb), B, T, Tp, S, 10, 65536, -7.0, ptr(d_dec), ptr(d_par), stream_ptr()), "b")
 
 
-for name, f, bytes_per_frame in (("dmol_fwd", fwd, 124), ("dmol_bwd", bwd, 124 + 240)):
+dW, db = torch.empty_like(W), torch.empty_like(b)
+ws_floats = lib.blvm_dmol_bwd_fused_workspace_floats(B, Tp, S)
+ws = torch.zeros(max(ws_floats, 1), device=dev)
+
+
+def bwd_fused():  # dz (leaky-ReLU derivative applied) + dW + db in the launch; no d_par
+    check(lib.blvm_dmol_bwd_fused(ptr(dec), 1, ptr(W), ptr(b), ptr(y), ptr(x_sl), ptr(gb), B, T, Tp, S, 10, 65536, -7.0, 0.01, ptr(d_dec),
+                                  ptr(dW), ptr(db), ptr(ws), stream_ptr()), "bf")  # fmt: skip
+
+
+def bwd_fused_nograd():  # dz alone (no weight / bias gradient wanted)
+    check(lib.blvm_dmol_bwd_fused(ptr(dec), 1, ptr(W), ptr(b), ptr(y), ptr(x_sl), ptr(gb), B, T, Tp, S, 10, 65536, -7.0, 0.01, ptr(d_dec),
+                                  None, None, None, stream_ptr()), "bf")  # fmt: skip
+
+
+def act_bwd():  # what the fused form replaces beside dmol_bwd: the decoder's last activation derivative ...
+    check(lib.blvm_act_bwd_f32(ptr(d_dec), ptr(dec), 0.01, ptr(d_par), dec.numel(), stream_ptr()), "a")
+
+
+def head_grads():  # ... and the head Linear's weight / bias gradient GEMM
+    ops._head_linear_grads(d_par, dec, W, b, 30, B * T, True, True)
+
+
+for name, f, bytes_per_frame in (("dmol_fwd", fwd, 124), ("dmol_bwd", bwd, 124 + 240), ("dmol_bwd_fused", bwd_fused, 124 + 120),
+                                 ("dmol_bwd_fused (no dW/db)", bwd_fused_nograd, 124 + 120), ("act_bwd", act_bwd, 360),
+                                 ("head_linear_grads", head_grads, 240)):  # fmt: skip
     for _ in range(3):
         f()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
