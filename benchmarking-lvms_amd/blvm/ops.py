@@ -429,7 +429,7 @@ def dmol_ll_twise(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix=10, num_b
     W, b = (_f32c(W), _f32c(b)) if W is not None else (None, None)
     _dmol_check_shapes(dec, W, y, B, T, Tp, S, num_mix)
     lp = torch.zeros(B, device=dec.device, dtype=torch.float64)
-    ll = torch.zeros(B, T, device=dec.device, dtype=torch.float32)
+    ll = torch.zeros(B, T, device=dec.device, dtype=torch.float32)  # (caller zeroes: the kernel writes the unmasked frames only)
     check(
         load().blvm_dmol_fwd(ptr(dec), layout, ptr(W), ptr(b), ptr(y), ptr(x_sl_dev), B, T, Tp, S, num_mix, num_bins,
                              log_eps, ptr(lp), ptr(ll), stream_ptr()),
@@ -635,8 +635,7 @@ class _VRNNSeqFunction(torch.autograd.Function):
         dev = enc.device
         lib = load()
         f32 = dict(device=dev, dtype=torch.float32)
-        decin = torch.empty(Tp + 1, B, H + R, **f32)
-        decin[Tp, :, :H].zero_()  # the phi-part of the extra row is never written by the kernels
+        decin = torch.empty(Tp + 1, B, H + R, **f32)  # (the driver clears the phi-part of the extra row, which no step writes)
         mu_q, sd_q, mu_p, sd_p, z = (torch.empty(Tp, B, Z, **f32) for _ in range(5))
         reserve = torch.empty(lib.blvm_vrnn_reserve_floats(Tp, B, X, H, Z, R), **f32)
         w = _pack_weights(params)

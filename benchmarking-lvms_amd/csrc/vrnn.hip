@@ -337,6 +337,8 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
 
   // initial state -> h-part of decin row 0
   BLVM_HIP(copy_or_zero_2d(decin + H, sizeof(float) * ldd, h0, sizeof(float) * R, B, s));
+  // the phi-part of the extra row T' has no producer (there is no step T'): zeros, so that no word of decin keeps the caller's bytes
+  BLVM_HIP(hipMemset2DAsync(decin + n * ldd, sizeof(float) * ldd, 0, sizeof(float) * H, B, s));
 
   const int rt = (B + 15) / 16;
   if (vrnn_persistent(B) && device_cus() >= 32) {

@@ -9,6 +9,10 @@
  *     float64 (`blvm/models/vrnn.py:266`) are double.
  *   - The caller owns every buffer (inputs, outputs, workspace/reserve); the library never allocates, frees or
  *     retains a pointer past the call.
+ *   - Apart from inputs, from buffers an entry point adds into (marked ACCUMULATED, "+=" or "caller zeroes")
+ *     and from the ticket words of the fused DMoL backward's workspace (zero between launches), no result of
+ *     any entry point depends on what its output, reserve, workspace or scratch buffers held before the call:
+ *     they may be uninitialised.
  *   - All work is enqueued on the caller's `stream` (a hipStream_t passed as void*); no implicit device sync.
  *   - Return value: 0 on success, a negative BLVM_E* code otherwise; text via blvm_last_error() (thread-local).
  *   - Sequence tensors are TIME-MAJOR [T', B, F] (one contiguous slab per recurrent step).
@@ -139,7 +143,8 @@ int blvm_colsum_f32(int M, int N, const float* X, int ldx, float* out, int accum
  *   y        [B, T] targets in [-1,1];  x_sl [B] int32 on device;  frame (b, tau=t*S+j) counts iff tau < x_sl[b]
  *   W [F,F], bias [F]: the likelihood's Linear (both NULL: `dec` already holds the F parameters, e.g. WaveNet's
  *   Linear(C->F) computed by K6);  log_eps: clamp floor of the log-scales (-7)
- *   log_prob [B] double, ACCUMULATED (caller zeroes);  ll_twise optional [B,T] fp32 (masked ll, may be NULL)
+ *   log_prob [B] double, ACCUMULATED (caller zeroes);  ll_twise optional [B,T] fp32 (masked ll, may be NULL):
+ *   only the frames t < x_sl[b] are written (caller zeroes: the masked frames keep what they held)
  * ------------------------------------------------------------------------------------------------------------- */
 int blvm_dmol_fwd(const float* dec, int layout, const float* W, const float* bias, const float* y,
                   const int32_t* x_sl, int B, int T, int Tp, int S, int num_mix, int num_bins, float log_eps,
@@ -288,7 +293,7 @@ size_t blvm_vrnn_bwd_workspace_floats(int Tp, int B, int X, int H, int Z, int R)
 /*   enc [Tp,B,X]; h0 [B,R] (NULL = zeros); eps [Tp,B,Z] standard-normal noise (reference draws it per step,
  *   `blvm/utils/variational.py:141-152`); sd_eps = epsilon of the Gaussian heads (1e-6), initial_sd = 1.
  *   decin [Tp+1,B,H+R]: row t = [phi_t | h_{t-1}] — the decoder input `cat([phi_z, h])` of `vrnn.py:321-324`;
- *     row Tp carries the final state in its h-part.
+ *     row Tp carries the final state in its h-part; its phi-part (there is no step Tp) is written as zeros.
  *   mu_q (residual already added), sd_q, mu_p, sd_p, z: [Tp,B,Z]. */
 int blvm_vrnn_seq_fwd(const BlvmVrnnWeights* w, const float* enc, const float* h0, const float* eps, int Tp, int B,
                       int X, int H, int Z, int R, int residual_posterior, float sd_eps, float* decin,
