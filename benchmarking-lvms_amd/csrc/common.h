@@ -185,7 +185,7 @@ __device__ __forceinline__ f32x4 wave_gemm16(const float* __restrict__ A, int ld
 // results are bit-identical.  The MFMAs of the G products are interleaved, so consecutive MFMAs are independent.
 //
 // `mid` runs once, right after the first trip's operand loads are issued (or at the end for a wave without chunks): a kernel
-// whose operand pointers are preloaded SGPRs (stages.h lin1_stage_kernel) puts there the epilogue prefetches whose pointers
+// whose operand pointers are preloaded SGPRs (stages.h, launch-latency note 4) puts there the epilogue prefetches whose pointers
 // still come by s_load, so the operand loads never wait for the argument fetch.
 template <int NW, int G, bool SAMEA, class Mid = NoMid>
 __device__ __forceinline__ void wave_gemm16_multi(const float* const (&A)[G], const int (&lda)[G], int r0, int nrows,

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(NW * 64) void lstm_fwd_kernel(const float* hprev, c
                                                            const float* bhh, const float* xg, const int32_t* lens, unsigned b_h,
                                                            int t_step, float* hnext, float* cnext, float* out, float* gates) {
   // scalar arguments (LstmFwdArgs documents them): the 6 input pointers, B:16|H:16 and the step are the 14 dwords the command
-  // processor preloads into SGPRs (stages.h lin1_stage_kernel); the outputs come by s_load
+  // processor preloads into SGPRs (stages.h, launch-latency note 4); the outputs come by s_load
   const int B = b_h & 0xffff, H = b_h >> 16;
   __shared__ float red[4 * NW * 256];
   const int r0 = blockIdx.y * 16, c0 = blockIdx.x * 16, wave = threadIdx.x >> 6;
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(NW * 64) void gru_fwd_kernel(const float* hprev, co
                                                           float* hnext, float* out, float* rg, float* ug, float* ng, float* ghn,
                                                           long long out_ts, int out_ld) {
   // scalar arguments (GruFwdArgs documents them): the 5 input pointers, B:16|R:16 and j<<1|reverse are the first 12 dwords,
-  // preloaded into SGPRs (stages.h lin1_stage_kernel); the outputs come by s_load
+  // preloaded into SGPRs (stages.h, launch-latency note 4); the outputs come by s_load
   const int B = b_r & 0xffff, R0 = b_r >> 16, j = j_rev >> 1, reverse = j_rev & 1;
   __shared__ float red[3 * NW * 256];
   const int r0 = blockIdx.y * 16, c0 = blockIdx.x * 16, wave = threadIdx.x >> 6, R = R0;

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(NW * 64) void gru_cell_stage_kernel(const float* A,
                                                                  unsigned b_h, int K, float* hnext, int ldn, float* rg, float* ug,
                                                                  float* ng) {
   // scalar arguments (GruCellArgs documents them; ldw = K for a T16 weight): 5 input pointers, lda:16|ldh:16, B:16|H:16 and K are
-  // the first 13 dwords, preloaded into SGPRs (stages.h lin1_stage_kernel)
+  // the first 13 dwords, preloaded into SGPRs (stages.h, launch-latency note 4)
   const int lda = lda_ldh & 0xffff, ldh = lda_ldh >> 16, B = b_h & 0xffff, H0 = b_h >> 16, ldw = K;
   __shared__ float red[3 * NW * 256];
   const int r0 = blockIdx.y * 16, c0 = blockIdx.x * 16, wave = threadIdx.x >> 6, H = H0;

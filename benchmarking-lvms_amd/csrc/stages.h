@@ -10,13 +10,20 @@
 // dependent scalar load) — segments are selected with scalar selects on values that arrive with the first kernarg
 // fetch; (2) every epilogue operand (bias, addend, gate, saved activations) is loaded BEFORE the K loop so it
 // travels with the operand loads; (3) the K split is as wide as the reduction allows (NW = 4/8/16 waves) so a
-// wave's dependent MFMA chain is <= 24 instructions.
+// wave's dependent MFMA chain is <= 24 instructions; (4) KERNARG PRELOAD: the command processor preloads the first 16
+// argument dwords of a kernel into SGPRs before the wave starts (-mllvm -amdgpu-kernarg-preload-count=16 in the Makefile;
+// 14 dwords remain after the kernarg pointer, and only SCALAR arguments are eligible, never a struct), so loads whose
+// pointers and sizes are leading scalar arguments do not wait for a kernarg fetch from memory (0.16-0.2 us of a ~3 us
+// link, tools/chain_bench.hip "scalar args").  The heads, dz, GRU and LSTM kernels take their operand pointers and packed
+// sizes that way and everything else in a TRAILING struct, which arrives by s_load while the operand loads are in flight:
+// its epilogue prefetches run in the `mid` hook of wave_gemm16 / wave_gemm16_multi (common.h).
 // ---------------------------------------------------------------------------------------------------------------
 
 // EVERY weight operand of the stage kernels (W, Wp, Wq, WT ...) is in the T16 operand layout (common.h: t16_pack /
 // wave_gemm16<NW, true>), packed once per sequence by the host code of the chain; `ldw` is the packed matrix's K.
 //
-// generic multi-segment linear stage:  out = gate( act( A W^T + bias + add ) )
+// The linear link:  out = gate( act( A W^T + bias + add ) )  over 1-3 segments.  It is lin_stage_kernel<NW, NSEG> on 16x16
+// tiles, or lin_stage32_kernel<NW, NSEG> on 32x32 tiles for large batches (launch_lin_n chooses).
 // Struct-of-arrays + scalar selects: every field is a plain kernarg scalar (s_load -> SGPR -> s_cselect); absent
 // operands are replaced on the host by a valid dummy pointer (W) plus a flag bit, so all prefetches are unconditional.
 enum { LF_BIAS = 1, LF_ADD = 2, LF_GATE = 4, LF_RELU = 8 };
@@ -74,136 +81,7 @@ __global__ __launch_bounds__(NW * 64) void lin_stage_kernel(LinArgs<NSEG> a) {
   out[(size_t)row * ldo + col] = x;
 }
 
-// Multi-segment links with the OPERAND side of their arguments as preloaded scalars (see lin1_stage_kernel below) and the rest —
-// epilogue pointers, strides, flags, outputs — in the trailing struct, fetched by s_load while the operand loads are in flight:
-// the epilogue prefetch runs in wave_gemm16's `mid` hook.  Two segments: any shapes (16-bit fields).  Three segments: one shared
-// lda and K (= ldw), which is what VRNN's first link (three products of h_{t-1}) has; the host falls back to lin_stage_kernel.
-template <int NW, int NSEG>
-__device__ __forceinline__ void linp_body(const float* A, const float* W, int lda, int ldw, int K, int B, int ct, int s,
-                                          const LinArgs<NSEG>& a, float* red) {
-  const int r0 = blockIdx.y * 16, c0 = ct * 16;
-  const int t = threadIdx.x & 255;
-  const int row = r0 + (t >> 4), col = c0 + (t & 15);
-  const bool own = threadIdx.x < 256 && row < B;
-  const int rowc = row < B ? row : r0;
-  float e_bias = 0.f, e_add = 0.f, e_gate = 0.f;
-  int flags = 0;
-  auto prefetch = [&]() {
-    const float* bias = PICK(bias);
-    const float* add = PICK(add);
-    const float* gate = PICK(gate);
-    const int ldadd = PICK(ldadd), ldgate = PICK(ldgate);
-    flags = PICK(flags);
-    e_bias = bias[(flags & LF_BIAS) ? col : 0];
-    e_add = add[(flags & LF_ADD) ? (size_t)rowc * ldadd + col : 0];
-    e_gate = gate[(flags & LF_GATE) ? (size_t)rowc * ldgate + col : 0];
-  };
-  f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
-  acc[0] = wave_gemm16<NW, true>(A, lda, r0, B, W, ldw, c0, K, threadIdx.x >> 6, acc[0], prefetch);
-  float v[1];
-  reduce_tiles<1, NW>(acc, red, v);
-  if (!own) return;
-  float* out = PICK(out);
-  const int ldo = PICK(ldo);
-  float x = v[0] + ((flags & LF_BIAS) ? e_bias : 0.f) + ((flags & LF_ADD) ? e_add : 0.f);
-  if (flags & LF_RELU) x = x > 0.f ? x : x * a.slope;
-  if (flags & LF_GATE) x = e_gate > 0.f ? x : x * a.slope;
-  out[(size_t)row * ldo + col] = x;
-}
-
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void linp2_stage_kernel(const float* A0, const float* A1, const float* W0, const float* W1,
-                                                              unsigned lda01, unsigned ldw01, unsigned k01, unsigned tiles0_b,
-                                                              LinArgs<2> a) {
-  __shared__ float red[NW * 256];
-  const int tiles0 = tiles0_b & 0xffff, B = tiles0_b >> 16;
-  const bool s1 = (int)blockIdx.x >= tiles0;  // uniform
-  const int ct = (int)blockIdx.x - (s1 ? tiles0 : 0);
-  linp_body<NW, 2>(s1 ? A1 : A0, s1 ? W1 : W0, s1 ? lda01 >> 16 : lda01 & 0xffff, s1 ? ldw01 >> 16 : ldw01 & 0xffff,
-                   s1 ? k01 >> 16 : k01 & 0xffff, B, ct, s1 ? 1 : 0, a, red);
-}
-
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void linp3_stage_kernel(const float* A0, const float* A1, const float* A2, const float* W0,
-                                                              const float* W1, const float* W2, unsigned lda_k,
-                                                              unsigned b_t0_t1, LinArgs<3> a) {
-  __shared__ float red[NW * 256];
-  const int lda = (lda_k & 0xffff), K = lda_k >> 16;
-  const int B = b_t0_t1 & 0xfff, t0 = (b_t0_t1 >> 12) & 0x3ff, t1 = b_t0_t1 >> 22;
-  const int bx = blockIdx.x;
-  const int s = (bx >= t0 ? 1 : 0) + (bx >= t0 + t1 ? 1 : 0);  // uniform
-  const int ct = bx - (s >= 1 ? t0 : 0) - (s >= 2 ? t1 : 0);
-  linp_body<NW, 3>(s == 0 ? A0 : (s == 1 ? A1 : A2), s == 0 ? W0 : (s == 1 ? W1 : W2), lda, K, K, B, ct, s, a, red);
-}
-
-// Single-segment link with SCALAR arguments: the command processor preloads the first 16 argument dwords into SGPRs before
-// the wave starts (-mllvm -amdgpu-kernarg-preload-count=16; struct arguments are never preloaded), so the operand loads do not
-// wait for a kernarg fetch from memory (0.16-0.2 us of a ~3 us link, tools/chain_bench.hip "scalar args").  Everything the
-// loads need sits in the 14 dwords that are preloaded (16 user SGPRs minus the kernarg pointer): five pointers and the leading
-// dimensions / K / B / flags packed two 16-bit values a dword; `out` and `slope`, needed last, come by s_load.
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void lin1_stage_kernel(const float* A, const float* W, const float* bias,
-                                                             const float* add, const float* gate, unsigned lda_ldw,
-                                                             unsigned k_b, unsigned ldadd_ldgate, unsigned ldo_flags,
-                                                             float* out, float slope) {
-  __shared__ float red[NW * 256];
-  const int lda = lda_ldw & 0xffff, ldw = lda_ldw >> 16, K = k_b & 0xffff, B = k_b >> 16;
-  const int ldadd = ldadd_ldgate & 0xffff, ldgate = ldadd_ldgate >> 16, ldo = ldo_flags & 0xffff, flags = ldo_flags >> 16;
-  const int r0 = blockIdx.y * 16, c0 = blockIdx.x * 16;
-  const int t = threadIdx.x & 255;
-  const int row = r0 + (t >> 4), col = c0 + (t & 15);
-  const bool own = threadIdx.x < 256 && row < B;
-  const int rowc = row < B ? row : r0;
-  const float e_bias = bias[(flags & LF_BIAS) ? col : 0];
-  const float e_add = add[(flags & LF_ADD) ? (size_t)rowc * ldadd + col : 0];
-  const float e_gate = gate[(flags & LF_GATE) ? (size_t)rowc * ldgate + col : 0];
-  f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
-  acc[0] = wave_gemm16<NW, true>(A, lda, r0, B, W, ldw, c0, K, threadIdx.x >> 6, acc[0]);
-  float v[1];
-  reduce_tiles<1, NW>(acc, red, v);
-  if (!own) return;
-  float x = v[0] + ((flags & LF_BIAS) ? e_bias : 0.f) + ((flags & LF_ADD) ? e_add : 0.f);
-  if (flags & LF_RELU) x = x > 0.f ? x : x * slope;
-  if (flags & LF_GATE) x = e_gate > 0.f ? x : x * slope;
-  out[(size_t)row * ldo + col] = x;
-}
-
-// Two SYMMETRIC segments (prior | posterior layer of the same shape, forward with a bias or backward with a gate) with scalar
-// arguments: both segments share lda, K (= ldw, true for every T16 weight that is not a K-slice), ldo, the tile count and the
-// flags, and have at most ONE epilogue operand each (bias or gate), so all that the loads need fits the 14 preloaded dwords:
-// A0 A1 W0 W1 e0 e1 | lda/16:12 K/16:12 flags:4 | B:12 tiles:10 lde/4:10.  out0/out1, ldo, slope come by s_load.
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void lin2s_stage_kernel(const float* A0, const float* A1, const float* W0, const float* W1,
-                                                              const float* e0, const float* e1, unsigned lda_k_flags,
-                                                              unsigned b_tiles_lde, float* out0, float* out1, int ldo,
-                                                              float slope) {
-  __shared__ float red[NW * 256];
-  const int lda = (lda_k_flags & 0xfff) * 16, K = ((lda_k_flags >> 12) & 0xfff) * 16, flags = lda_k_flags >> 24;
-  const int B = b_tiles_lde & 0xfff, tiles = (b_tiles_lde >> 12) & 0x3ff, lde = (b_tiles_lde >> 22) * 4;
-  const bool s1 = (int)blockIdx.x >= tiles;  // uniform
-  const int ct = (int)blockIdx.x - (s1 ? tiles : 0);
-  const float* A = s1 ? A1 : A0;
-  const float* W = s1 ? W1 : W0;
-  const float* e = s1 ? e1 : e0;
-  const int r0 = blockIdx.y * 16, c0 = ct * 16;
-  const int t = threadIdx.x & 255;
-  const int row = r0 + (t >> 4), col = c0 + (t & 15);
-  const bool own = threadIdx.x < 256 && row < B;
-  const int rowc = row < B ? row : r0;
-  // bias: e[col]; gate: e[row * lde + col]; neither: e is a valid dummy
-  const float e_val = e[(flags & LF_GATE) ? (size_t)rowc * lde + col : ((flags & LF_BIAS) ? col : 0)];
-  f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
-  acc[0] = wave_gemm16<NW, true>(A, lda, r0, B, W, K, c0, K, threadIdx.x >> 6, acc[0]);
-  float v[1];
-  reduce_tiles<1, NW>(acc, red, v);
-  if (!own) return;
-  float x = v[0] + ((flags & LF_BIAS) ? e_val : 0.f);
-  if (flags & LF_RELU) x = x > 0.f ? x : x * slope;
-  if (flags & LF_GATE) x = e_val > 0.f ? x : x * slope;
-  (s1 ? out1 : out0)[(size_t)row * ldo + col] = x;
-}
-
-// The same stage on 32x32 tiles for large batches (B >= 128): `tiles` counts 32-column tiles.  The NW partial tiles are
+// The same stage on 32x32 tiles for large batches (B >= LIN32_MIN_BATCH): `tiles` counts 32-column tiles.  The NW partial tiles are
 // combined through LDS (row stride 33: conflict-free); threads 0..255 then own 4 output elements each.
 template <int NW, int NSEG>
 __global__ __launch_bounds__(NW * 64) void lin_stage32_kernel(LinArgs<NSEG> a) {
@@ -462,20 +340,14 @@ struct LinLaunch {
   float slope = 0.f;
 };
 
-// large batches: 32x32 tiles when every segment's width allows it (env BLVM_LIN32_MIN_B overrides the threshold, 0 = never)
-inline int lin32_min_batch() {
-  static int v = [] {
-    const char* e = getenv("BLVM_LIN32_MIN_B");
-    return e ? atoi(e) : 128;
-  }();
-  return v;
-}
+// large batches run the link on 32x32 tiles when every segment's width allows it
+constexpr int LIN32_MIN_BATCH = 128;
 
 template <int NSEG>
 inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
   LinArgs<NSEG> a{};
   int tiles = 0, kmax = 0;
-  bool wide = lin32_min_batch() > 0 && l.B >= lin32_min_batch();
+  bool wide = l.B >= LIN32_MIN_BATCH;
   for (int i = 0; i < NSEG; ++i) wide = wide && (l.seg[i].ncols % 32 == 0) && (l.seg[i].K % 8 == 0);
   const int tw = wide ? 32 : 16;
   for (int i = 0; i < NSEG; ++i) {
@@ -502,53 +374,6 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
   }
   const int nw = pick_nw(kmax, 1);
   const dim3 grid(tiles, (l.B + 15) / 16);
-  if (NSEG == 1 && l.B < 65536 && a.K[0] < 65536 && a.lda[0] < 65536 && a.ldw[0] < 65536 && a.ldadd[0] < 65536 &&
-      a.ldgate[0] < 65536 && a.ldo[0] < 65536) {
-    const unsigned p0 = (unsigned)a.lda[0] | ((unsigned)a.ldw[0] << 16), p1 = (unsigned)a.K[0] | ((unsigned)l.B << 16);
-    const unsigned p2 = (unsigned)a.ldadd[0] | ((unsigned)a.ldgate[0] << 16), p3 = (unsigned)a.ldo[0] | ((unsigned)a.flags[0] << 16);
-    LAUNCH_NW(lin1_stage_kernel<NW_>, nw, grid, s, a.A[0], a.W[0], a.bias[0], a.add[0], a.gate[0], p0, p1, p2, p3, a.out[0], a.slope);
-    return;
-  }
-  if (NSEG == 2) {
-    const int f = a.flags[0];
-    const bool one_operand = (f & LF_ADD) == 0 && ((f & LF_BIAS) == 0 || (f & LF_GATE) == 0);
-    const int lde = (f & LF_GATE) ? a.ldgate[0] : 0;
-    if (one_operand && a.flags[1 % NSEG] == f && a.lda[0] == a.lda[1 % NSEG] && a.K[0] == a.K[1 % NSEG] && a.ldw[0] == a.K[0] &&
-        a.ldw[1 % NSEG] == a.K[0] && a.ldo[0] == a.ldo[1 % NSEG] && a.tiles[0] == a.tiles[1 % NSEG] &&
-        (!(f & LF_GATE) || a.ldgate[1 % NSEG] == lde) && l.B < 4096 && a.lda[0] % 16 == 0 && a.lda[0] < 65536 &&
-        a.K[0] % 16 == 0 && a.K[0] < 65536 && lde % 4 == 0 && lde < 4096 && a.tiles[0] < 1024) {
-      const float* e0 = (f & LF_GATE) ? a.gate[0] : a.bias[0];
-      const float* e1 = (f & LF_GATE) ? a.gate[1 % NSEG] : a.bias[1 % NSEG];
-      const unsigned p0 = (unsigned)(a.lda[0] / 16) | ((unsigned)(a.K[0] / 16) << 12) | ((unsigned)f << 24);
-      const unsigned p1 = (unsigned)l.B | ((unsigned)a.tiles[0] << 12) | ((unsigned)(lde / 4) << 22);
-      const int p2 = a.ldo[0];
-      LAUNCH_NW(lin2s_stage_kernel<NW_>, nw, grid, s, a.A[0], a.A[1 % NSEG], a.W[0], a.W[1 % NSEG], e0, e1, p0, p1, a.out[0], a.out[1 % NSEG], p2, a.slope);
-      return;
-    }
-  }
-  if (NSEG == 2) {
-    bool fits = l.B < 65536;
-    for (int i = 0; i < 2; ++i) fits = fits && a.lda[i % NSEG] < 65536 && a.ldw[i % NSEG] < 65536 && a.K[i % NSEG] < 65536;
-    fits = fits && a.tiles[0] < 65536;
-    if (fits) {
-      const LinArgs<2>& a2 = reinterpret_cast<const LinArgs<2>&>(a);  // NSEG == 2 here
-      const unsigned p0 = (unsigned)a2.lda[0] | ((unsigned)a2.lda[1] << 16), p1 = (unsigned)a2.ldw[0] | ((unsigned)a2.ldw[1] << 16);
-      const unsigned p2 = (unsigned)a2.K[0] | ((unsigned)a2.K[1] << 16), p3 = (unsigned)a2.tiles[0] | ((unsigned)l.B << 16);
-      LAUNCH_NW(linp2_stage_kernel<NW_>, nw, grid, s, a2.A[0], a2.A[1], a2.W[0], a2.W[1], p0, p1, p2, p3, a2);
-      return;
-    }
-  }
-  if (NSEG == 3) {
-    const LinArgs<3>& a3 = reinterpret_cast<const LinArgs<3>&>(a);  // NSEG == 3 here
-    bool fits = l.B < 4096 && a3.tiles[0] < 1024 && a3.tiles[1] < 1024 && a3.lda[0] < 65536 && a3.K[0] < 65536;
-    for (int i = 0; i < 3; ++i) fits = fits && a3.lda[i] == a3.lda[0] && a3.K[i] == a3.K[0] && a3.ldw[i] == a3.K[0];
-    if (fits) {
-      const unsigned p0 = (unsigned)a3.lda[0] | ((unsigned)a3.K[0] << 16);
-      const unsigned p1 = (unsigned)l.B | ((unsigned)a3.tiles[0] << 12) | ((unsigned)a3.tiles[1] << 22);
-      LAUNCH_NW(linp3_stage_kernel<NW_>, nw, grid, s, a3.A[0], a3.A[1], a3.A[2], a3.W[0], a3.W[1], a3.W[2], p0, p1, a3);
-      return;
-    }
-  }
   LAUNCH_NW((lin_stage_kernel<NW_, NSEG>), nw, grid, s, a);
 }
 

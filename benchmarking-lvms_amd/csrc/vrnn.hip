@@ -38,7 +38,7 @@ template <int NW>
 __global__ __launch_bounds__(NW * 64) void gru_stage_kernel(const float* decin_t, const float* Wih, const float* xg,
                                                             const float* gh, int B, int H, int R, float* decin_next,
                                                             float* rg, float* ug, float* ng) {
-  // scalar arguments: the operand pointers and sizes are the first 11 dwords, preloaded into SGPRs (stages.h lin1_stage_kernel)
+  // scalar arguments: the operand pointers and sizes are the first 11 dwords, preloaded into SGPRs (stages.h, launch-latency note 4)
   __shared__ float red[3 * NW * 256];
   const int r0 = blockIdx.y * 16, c0 = blockIdx.x * 16, wave = threadIdx.x >> 6;
   const int ldd = H + R;

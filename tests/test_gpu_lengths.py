@@ -2,8 +2,8 @@
 "TIMIT-length") and SRNN `[16, 196608]` (T' = 3072, "LibriSpeech-length") — which no golden covers: reserve / workspace sizing and
 64-bit offsets at 3-12x the golden-covered sequence length, through size-independent properties (row independence, invariance to
 samples beyond x_sl, the bits/dim window), agreement of the two execution paths of the recurrent chains (one persistent launch vs
-one launch per link), one oracle comparison at T' = 768 on a reduced width, and the struct-argument fallback of the packed
-link kernels (csrc/stages.h) that only shapes outside the packed fields' ranges reach.
+one launch per link), one oracle comparison at T' = 768 on a reduced width, and the launch-per-link path on 16-row tiles
+(csrc/stages.h) at a batch beyond the persistent engine whose widths rule out the 32x32 large-batch kernel.
 Reference lines: blvm/models/vrnn.py:281-369, blvm/models/srnn.py:162-302."""
 import pytest
 import torch
@@ -94,13 +94,16 @@ def test_vrnn_768_steps_vs_oracle_reduced_width():
 
 
 @pytest.mark.parametrize("model", ["vrnn", "srnn"])
-def test_struct_argument_fallback_of_the_packed_link_kernels_vs_oracle(model):
-    """The scalar-argument link kernels pack B, lda, K and tile counts into 12/16-bit fields and fall back to the struct-argument
-    kernels when a value does not fit (csrc/stages.h launch_lin_n).  B = 4100 rows with 48-wide layers (not a multiple of 32, so the
-    32x32 large-batch kernel does not apply either) is out of the 12-bit batch field: the three-segment first link runs on
-    lin_stage_kernel<.., 3>, the symmetric two-segment links on linp2_stage_kernel instead of lin2s.  Same numbers as the oracle."""
+@pytest.mark.parametrize("B,Hd,engine_off", [(4100, 48, False), (5, 96, True), (5, 144, True)])
+def test_launch_per_link_on_16_row_tiles_vs_oracle(model, B, Hd, engine_off):
+    """The launch-per-link path on 16-row tiles (csrc/stages.h lin_stage_kernel<NW, NSEG>) against the oracle.  B = 4100 rows is
+    beyond the persistent engine and beyond any 12-bit batch count (257 row tiles), and its 48-wide layers are not a multiple of
+    32, so the 32x32 large-batch kernel does not apply: every link of the chain runs on 16x16 tiles.
+    The B = 5 cases, with the persistent engine switched off, reach the instantiations that no other test runs (a kernel trace of
+    the suite shows which): the one- and two-segment links reduce over K = hidden, the three-segment link over K = 2 hidden, and
+    pick_nw gives 8 waves at K = 96 and 16 at K = 144 or 192, so hidden = 96 runs <8, 1> and <16, 3>, hidden = 144 runs <16, 1>."""
     torch.manual_seed(8)
-    B, S, Tp, Hd, Z = 4100, 16, 3, 48, 16
+    S, Tp, Z = 16, 3, 16
     T_ = S * Tp - 2
     cls = VRNNAudio if model == "vrnn" else SRNNAudio
     m = cls(likelihood="DMoL", input_size=S, hidden_size=Hd, latent_size=Z, residual_posterior=True)
@@ -111,8 +114,13 @@ def test_struct_argument_fallback_of_the_packed_link_kernels_vs_oracle(model):
     ref = fwd(sd, x, x_sl, eps, beta=0.8, free_nats=1.0, stack=S)
     ref["loss"].backward()
     m.to(DEV)
-    loss, _, out = m(x.to(DEV), x_sl, beta=0.8, free_nats=1.0, eps=eps.to(DEV))
-    loss.backward()
+    if engine_off:
+        _hip.load().blvm_pchain_configure(0, -1)
+    try:
+        loss, _, out = m(x.to(DEV), x_sl, beta=0.8, free_nats=1.0, eps=eps.to(DEV))
+        loss.backward()
+    finally:
+        _hip.load().blvm_pchain_configure(128, -1)
     assert float(loss) == pytest.approx(float(ref["loss"]), rel=1e-5)
     torch.testing.assert_close(out.elbo.cpu(), ref["elbo"].detach(), rtol=1e-5, atol=1e-3)
     for k, p in m.named_parameters():
