@@ -316,6 +316,13 @@ struct TileIter {
   __host__ __device__ __forceinline__ int c() const { return xcd ? x + 8 * (j / rt) : j / rt; }
 };
 
+// (host) the most tiles of a link (rt row tiles x ct column tiles on nwg workgroups) that TileIter deals to one workgroup of its range
+inline int tiles_per_workgroup(int rt, int ct, int nwg, bool xcd) {
+  if (nwg <= 0) return 0;
+  if (xcd) return nwg >= 8 ? (((ct + 7) / 8) * rt + nwg / 8 - 1) / (nwg / 8) : ((ct + 7) / 8) * rt;
+  return (ct * rt + nwg - 1) / nwg;
+}
+
 // Cheap wait in front of a polled product for tiles OFF the critical path: one wave polls ONE word of every 1 KB block of the
 // T16 operand A16[r0 .. r0+15][0 .. K) instead of every wave polling its fragments; the barrier then releases the other waves into
 // the validating operand poll, which normally succeeds at once.  Costs a round trip, saves the fabric most of the idle polling.
@@ -337,6 +344,134 @@ __device__ __forceinline__ void canary_wait(const float* A16, int r0, int K, Pol
     }
   }
   __syncthreads();
+}
+
+// ---- resident weights ---------------------------------------------------------------------------------------------------------
+// A workgroup that owns the same tile of a link in every step of a launch (seqchain.hip's one-link programs, vrnn_static.hip's fixed
+// deal) loads the tile's weight fragments ONCE, in front of its step loop, and keeps them in registers: a visit then issues no
+// weight load at all (per 16-column tile and K = 256: 16 KB a step that neither cross the L1 -> VGPR path nor sit in the wait).
+// A wave's chunks are wave, wave + NW, ...: NCH = K / (16 NW) of them per product, as in mgemm16.
+// Where a tile's weights come from: WMem — the tile's pointer arguments, read every tile; WRegs — the fragments load_w left here.
+struct WMem {
+  static constexpr bool resident = false;
+  static constexpr int products = 0;
+};
+template <int OT, int G, int NCH>
+struct WRegs {
+  static constexpr bool resident = true;
+  static constexpr int products = G;
+  typename WFrag<OT>::type w[G][NCH];
+};
+// w[g][u] <- chunk wave + u NW of the 16 packed rows c0[g] .. c0[g]+15 of W[g] (T16, row length ldw; a K-range of wider rows: the
+// pointer starts at the range, as mgemm16's w_width)
+template <int NW, int OT, int G, int NCH>
+__device__ __forceinline__ void load_w(typename WFrag<OT>::type (&w)[G][NCH], const float* const* W, const int (&c0)[G], int ldw) {
+  typedef typename WFrag<OT>::type wfrag;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr int ES = OT != OP_F32 ? 2 : 4;
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const char* base = reinterpret_cast<const char*>(W[g]) + (size_t)ES * ((size_t)c0[g] * ldw + 4 * lane);
+#pragma unroll
+    for (int u = 0; u < NCH; ++u) w[g][u] = *reinterpret_cast<const wfrag*>(base + (size_t)ES * 256 * (size_t)(wave + u * NW));
+  }
+}
+// acc[g] += A[AMap(g)][r0+i][k] W[g][c0[g]+j][k] over this wave's NCH chunks: the A operands polled from T16 slabs of `width`
+// columns (the sentinel protocol of mgemm16, one poll for all chunks), W from the registers `w`.  The multiply runs in mgemm_trip's
+// order — chunks ascending, the four k of a chunk, the products — so a tile's result is bit-identical to mgemm16's wherever that
+// takes the same chunks in one trip or in consecutive ones.  `mid` runs behind the first poll's loads.
+// SHARED (one operand, wide: K >= 1024): every tile of a row tile reads the same [16, K] slab, and the workgroups of one XCD all belong
+// to the same row tile (blockIdx % 8 fixes blockIdx % rt for rt = 1, 2, 4, 8) — so once one wave has seen the slab's canary words
+// arrive (sc1 polls of word 0 of every 1 KB block), the fragments are read with ORDINARY loads: the first workgroup of the XCD
+// brings a line into the XCD's L2, the others hit it, and the fabric carries the slab once per XCD instead of once per tile.  Every
+// word is still validated: a fragment that holds a sentinel (a line cached before its last store landed) is re-read with sc1 loads,
+// which bypass the stale line.
+template <int NW, int OT, int GA, int G, class AMap, int NCH, bool SHARED, class Mid>
+__device__ __forceinline__ void product_regs(const float* const (&A16)[GA], int r0, int nrows, int width,
+                                             const typename WFrag<OT>::type (&w)[G][NCH], f32x4 (&acc)[G], Poll& pl, Mid mid) {
+  static_assert(!SHARED || GA == 1, "the shared-slab form reads one operand");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool aok = (r0 + (lane & 15)) < nrows;
+  rsrc_t ar[GA];
+#pragma unroll
+  for (int g = 0; g < GA; ++g) ar[g] = make_rsrc(A16[g]);
+  const unsigned aoff = 4u * ((unsigned)(r0 >> 4) * 16u * (unsigned)width + 4u * (unsigned)lane) + 1024u * (unsigned)wave;
+  f32x4 a[GA][NCH];
+  unsigned spins = 0;
+  bool mid_pending = true;
+  if constexpr (SHARED) {
+    canary_wait(A16[0], r0, width, pl);  // (one wave polls; ends in a workgroup barrier)
+    const float* ap = A16[0] + (size_t)(r0 >> 4) * 16 * width + 4 * lane + 256 * wave;
+#pragma unroll
+    for (int u = 0; u < NCH; ++u) a[0][u] = *reinterpret_cast<const f32x4*>(ap + 256 * (size_t)(u * NW));
+    mid();
+    mid_pending = false;
+    bool bad = false;
+#pragma unroll
+    for (int u = 0; u < NCH; ++u) bad |= any_sentinel(a[0][u]);
+    if (!__any(bad && aok)) goto multiply;
+  }
+  for (;;) {
+#pragma unroll
+    for (int u = 0; u < NCH; ++u)
+#pragma unroll
+      for (int g = 0; g < GA; ++g) a[g][u] = ld_sc1_x4(ar[g], aoff + 1024u * (unsigned)(u * NW));
+    if (mid_pending) { mid(); mid_pending = false; }
+    bool bad = false;
+#pragma unroll
+    for (int u = 0; u < NCH; ++u)
+#pragma unroll
+      for (int g = 0; g < GA; ++g) bad |= any_sentinel(a[g][u]);
+    if (!__any(bad && aok) || pl.dead) break;
+    if (spin_tick(spins, pl.ctl, pl.code, pl.dead)) break;
+    pl.sleep();
+  }
+multiply:
+  if constexpr (AMap::sum) {
+#pragma unroll
+    for (int u = 0; u < NCH; ++u)
+#pragma unroll
+      for (int ga = 1; ga < GA; ++ga) a[0][u] += a[ga][u];
+  }
+  if constexpr (OT != OP_F32) {
+#pragma unroll
+    for (int u = 0; u < NCH; ++u) {
+      s16x4 ab[GA];
+#pragma unroll
+      for (int ga = 0; ga < GA; ++ga) {
+        const f32x4 x = a[ga][u];
+        const u32x2 q = {aok ? pk16<OT>(x[0], x[1]) : 0u, aok ? pk16<OT>(x[2], x[3]) : 0u};
+        ab[ga] = __builtin_bit_cast(s16x4, q);
+      }
+#pragma unroll
+      for (int g = 0; g < G; ++g) acc[g] = mfma16<OT>(ab[AMap::of(g)], __builtin_bit_cast(s16x4, w[g][u]), acc[g]);
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < NCH; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(aok ? a[AMap::of(g)][u][e] : 0.f, w[g][u][e], acc[g], 0, 0, 0);
+  }
+}
+
+// a tile's product from either weight source: the arguments of mgemm16 behind the source.
+// CONTRACT of the resident form (nothing checks it at run time; a caller that breaks it reads the wrong memory): the fragments were
+// loaded by load_w for THIS tile's columns, so W, c0 and w_width are ignored; every operand is a polled T16 slab, so `polled` and
+// lda are ignored (a row-major operand would be read as a slab); K is ignored, the product covers the NCH * 16 * NW k the fragments
+// hold.  The callers are the static walks of vrnn_static.hip, which pass polled = true and a K fixed at compile time to match.
+template <int NW, int OT, int GA, int G, class AMap, class Mid = NoMid>
+__device__ __forceinline__ void tile_product(const WMem&, const float* const (&A)[GA], const int (&lda)[GA], bool polled, int r0, int nrows,
+                                             const float* const (&W)[G], const int (&c0)[G], int K, f32x4 (&acc)[G], Poll& pl, Mid mid = Mid(),
+                                             int a_width = 0, int w_width = 0) {
+  mgemm16<NW, OT, GA, G, AMap>(A, lda, polled, r0, nrows, W, c0, K, acc, pl, mid, a_width, w_width);
+}
+template <int NW, int OT, int GA, int G, class AMap, class Mid = NoMid, int NCH>
+__device__ __forceinline__ void tile_product(const WRegs<OT, G, NCH>& ws, const float* const (&A)[GA], const int (&)[GA], bool, int r0, int nrows,
+                                             const float* const (&)[G], const int (&)[G], int, f32x4 (&acc)[G], Poll& pl, Mid mid = Mid(),
+                                             int a_width = 0, int = 0) {
+  product_regs<NW, OT, GA, G, AMap, NCH, false>(A, r0, nrows, a_width > 0 ? a_width : NCH * 16 * NW, ws.w, acc, pl, mid);
 }
 
 // Where a link's [16 x 16] output tile goes: a row-major copy (plain stores; `rm_sc1`: other workgroups poll single words of it)
@@ -378,9 +513,11 @@ struct LinLate {
   float slope;
   Out out;
 };
-template <int NW, int OT, class Late>
+// (ws, here and in the tiles below: the weight source — WMem, the pointer arguments, or a WRegs loaded for this very tile)
+template <int NW, int OT, class Late, class WS = WMem>
 __device__ __forceinline__ void tile_lin_late(const float* A, int lda, bool a_polled, const float* W, int K, Late& late, int r0, int c0, int B,
-                                              float* red, Poll& pl, const float* A2 = nullptr, const float* A3 = nullptr, int w_width = 0) {
+                                              float* red, Poll& pl, const float* A2 = nullptr, const float* A3 = nullptr, int w_width = 0,
+                                              const WS& ws = WS()) {
   const int t = threadIdx.x & 255;
   const int row = r0 + (t >> 4), col = c0 + (t & 15);
   const bool own = threadIdx.x < 256 && row < B;
@@ -402,12 +539,12 @@ __device__ __forceinline__ void tile_lin_late(const float* A, int lda, bool a_po
     const float* const As[3] = {A, A2, A3};
     const float* const Ws[1] = {W};
     const int la[3] = {0, 0, 0}, cs[1] = {c0};
-    mgemm16<NW, OT, 3, 1, MapSum>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch, lda, w_width);
+    tile_product<NW, OT, 3, 1, MapSum>(ws, As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch, lda, w_width);
   } else {
     const float* const As[1] = {A};
     const float* const Ws[1] = {W};
     const int la[1] = {lda}, cs[1] = {c0};
-    mgemm16<NW, OT, 1, 1, MapSame>(As, la, a_polled, r0, B, Ws, cs, K, acc, pl, prefetch, a_polled ? lda : 0, w_width);  // polled: lda = slab width (0 = K)
+    tile_product<NW, OT, 1, 1, MapSame>(ws, As, la, a_polled, r0, B, Ws, cs, K, acc, pl, prefetch, a_polled ? lda : 0, w_width);  // polled: lda = slab width (0 = K)
   }
   float v[1];
   reduce_tiles<1, NW>(acc, red, v);
@@ -450,10 +587,10 @@ struct HeadOut {
   float *mu_p, *sd_p, *mu_q, *sd_q, *raw_p, *raw_q, *muq_raw;  // [B,Z] slabs of this step; muq_raw may be null
   Out z;
 };
-template <int NW, int OT = OP_F32>
+template <int NW, int OT = OP_F32, class WS = WMem>
 __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool polled, const float* Wp, const float* bp, const float* Wq,
                                           const float* bq, const float* eps, const HeadOut& o, int H, int Z, int residual, float beta,
-                                          float inv_beta, float sd_eps, int r0, int c0, int B, float* red, Poll& pl) {
+                                          float inv_beta, float sd_eps, int r0, int c0, int B, float* red, Poll& pl, const WS& ws = WS()) {
   const int t = threadIdx.x & 255;
   const int row = r0 + (t >> 4), col = c0 + (t & 15);
   const bool own = threadIdx.x < 256 && row < B;
@@ -467,7 +604,7 @@ __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool p
     const float* const As[2] = {P, Q};
     const float* const Ws[4] = {Wp, Wp, Wq, Wq};
     const int la[2] = {H, H}, cs[4] = {c0, Z + c0, c0, Z + c0};
-    mgemm16<NW, OT, 2, 4, MapPairs>(As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
+    tile_product<NW, OT, 2, 4, MapPairs>(ws, As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
   }
   float v[4];
   reduce_tiles<4, NW>(acc, red, v);
@@ -498,10 +635,10 @@ __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool p
 // GRU cell update of a [16 x 16] block of the state (vrnn.hip gru_stage_kernel, rssm.hip gru_cell_stage_kernel): gi = X Wih^T
 // (3 products, X [B,K] polled) + xg (state-independent part of the input projection incl. b_ih, computed before the launch) and /
 // or + b_ih ; gh = h_prev Whh^T + b_hh was produced by another link of this launch (polled words), h_prev likewise.  Writes h_new (sc1) and the gates r, u, n (read after the launch).
-template <int NW, int OT = OP_F32>
+template <int NW, int OT = OP_F32, class WS = WMem>
 __device__ __forceinline__ void tile_gru(const float* X, int ldx, bool polled, const float* Wih, int K, const float* xg, const float* bih,
                                          const float* gh, const float* hprev, int ldh, int R, const Out& hnew, float* rg, float* ug, float* ng,
-                                         int r0, int c0, int B, float* red, Poll& pl) {
+                                         int r0, int c0, int B, float* red, Poll& pl, const WS& ws = WS()) {
   const int t = threadIdx.x & 255;
   const int row = r0 + (t >> 4), col = c0 + (t & 15);
   const bool own = threadIdx.x < 256 && row < B;
@@ -527,7 +664,7 @@ __device__ __forceinline__ void tile_gru(const float* X, int ldx, bool polled, c
     const float* const As[1] = {X};
     const float* const Ws[3] = {Wih, Wih, Wih};
     const int la[1] = {ldx}, cs[3] = {c0, R + c0, 2 * R + c0};
-    mgemm16<NW, OT, 1, 3, MapSame>(As, la, polled, r0, B, Ws, cs, K, acc, pl, prefetch);
+    tile_product<NW, OT, 1, 3, MapSame>(ws, As, la, polled, r0, B, Ws, cs, K, acc, pl, prefetch);
   }
   float v[3];
   reduce_tiles<3, NW>(acc, red, v);
@@ -553,10 +690,11 @@ struct DzIn {
   float fn_floor, beta, sd_eps;
   bool has_gemm = true;  // false: dz = dz_add alone (the last step of a chain whose z only feeds the next step)
 };
-template <int NW, int OT = OP_F32>
+// (resident weights: a WRegs of two products for the D, D2 form, of one for D alone — the caller holds the fragments of the form it runs)
+template <int NW, int OT = OP_F32, class WS = WMem>
 __device__ __forceinline__ void tile_dz(const float* D, const float* WT, const float* D2, const float* WT2, bool polled, const float* dz_add,
                                         int ld_add, bool add_polled, const DzIn& a, const Out& dqh, const Out& dph, int H, int Z, int r0, int c0,
-                                        int B, float* red, Poll& pl) {
+                                        int B, float* red, Poll& pl, const WS& ws = WS()) {
   const int t = threadIdx.x & 255;
   const int row = r0 + (t >> 4), col = c0 + (t & 15);
   const bool own = threadIdx.x < 256 && row < B;
@@ -577,18 +715,22 @@ __device__ __forceinline__ void tile_dz(const float* D, const float* WT, const f
     f32x4 acc[2];
     acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f};
     acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (D2 != nullptr) {
-      const float* const As[2] = {D, D2};
-      const float* const Ws[2] = {WT, WT2};
-      const int la[2] = {H, H}, cs[2] = {c0, c0};
-      mgemm16<NW, OT, 2, 2, MapId>(As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
+    if (WS::products != 1 && D2 != nullptr) {
+      if constexpr (WS::products != 1) {
+        const float* const As[2] = {D, D2};
+        const float* const Ws[2] = {WT, WT2};
+        const int la[2] = {H, H}, cs[2] = {c0, c0};
+        tile_product<NW, OT, 2, 2, MapId>(ws, As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
+      }
     } else {
-      f32x4 a1[1] = {acc[0]};
-      const float* const As[1] = {D};
-      const float* const Ws[1] = {WT};
-      const int la[1] = {H}, cs[1] = {c0};
-      mgemm16<NW, OT, 1, 1, MapSame>(As, la, polled, r0, B, Ws, cs, H, a1, pl, prefetch);
-      acc[0] = a1[0];
+      if constexpr (WS::products != 2) {
+        f32x4 a1[1] = {acc[0]};
+        const float* const As[1] = {D};
+        const float* const Ws[1] = {WT};
+        const int la[1] = {H}, cs[1] = {c0};
+        tile_product<NW, OT, 1, 1, MapSame>(ws, As, la, polled, r0, B, Ws, cs, H, a1, pl, prefetch);
+        acc[0] = a1[0];
+      }
     }
     reduce_tiles<2, NW>(acc, red, v);
   } else {
@@ -649,8 +791,8 @@ struct GrubIn {
   float *ga, *g_out;
   bool has_gemm, has_gin, has_gates;
 };
-template <int NW, int OT = OP_F32>
-__device__ __forceinline__ void tile_grub(const GrubIn& a, int K, int R, int r0, int c0, int B, float* red, Poll& pl) {
+template <int NW, int OT = OP_F32, class WS = WMem>
+__device__ __forceinline__ void tile_grub(const GrubIn& a, int K, int R, int r0, int c0, int B, float* red, Poll& pl, const WS& ws = WS()) {
   const int tt = threadIdx.x & 255;
   const int row = r0 + (tt >> 4), col = c0 + (tt & 15);
   const bool own = threadIdx.x < 256 && row < B;
@@ -675,7 +817,7 @@ __device__ __forceinline__ void tile_grub(const GrubIn& a, int K, int R, int r0,
     const float* const As[2] = {a.D0, a.D1};
     const float* const Ws[2] = {a.W0, a.W1};
     const int la[2] = {0, 0}, cs[2] = {c0, c0};
-    mgemm16<NW, OT, 2, 2, MapId>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch);
+    tile_product<NW, OT, 2, 2, MapId>(ws, As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch);
     reduce_tiles<2, NW>(acc, red, v);
   }
   if (threadIdx.x >= 256) return;

@@ -580,7 +580,7 @@ int pchain_run(const pchain::Program& prog, hipStream_t stream) {
     BLVM_REQUIRE(!prog.xcd || d.nwg % 8 == 0, "pchain: XCD-aware placement needs ranges of 8 k workgroups (descriptor %d has %d)", i, d.nwg);
     grid = std::max(grid, d.wg0 + d.nwg);
     const int rt = ((prog.B + 15) / 16 + prog.rt_group - 1) / prog.rt_group;  // row tiles, or row groups
-    const int per_wg = prog.xcd ? (((d.ct + 7) / 8) * rt + d.nwg / 8 - 1) / (d.nwg / 8) : (d.ct * rt + d.nwg - 1) / d.nwg;
+    const int per_wg = pchain::tiles_per_workgroup(rt, d.ct, d.nwg, prog.xcd != 0);
     BLVM_REQUIRE(per_wg <= kMaxTilesPerWg, "pchain: descriptor %d gives a workgroup %d tiles (at most %d)", i, per_wg, kMaxTilesPerWg);
   }
   int dev = 0, cus = 0;

@@ -6,76 +6,19 @@ namespace {
 using namespace pchain;
 constexpr int NW = 8;
 
-// acc[g] += A[r0+i][k] W[g][c0[g]+j][k] over this wave's NCH k-chunks (chunk numbers wave, wave + NW, ...): A polled from a T16 slab
-// (sentinel protocol of pchain.h), W from the registers `w` (loaded once by load_w).  `mid` runs behind the first poll's loads.
+// The resident product is pchain.h's (load_w / product_regs): one operand slab, every product reads it, weights from registers.
 template <int OT, int G, int NCH>
 __device__ __forceinline__ void load_w(typename WFrag<OT>::type (&w)[G][NCH], const float* W, const int (&c0)[G], int K) {
-  typedef typename WFrag<OT>::type wfrag;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr int ES = OT != OP_F32 ? 2 : 4;
+  const float* Ws[G];
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const char* base = reinterpret_cast<const char*>(W) + (size_t)ES * ((size_t)c0[g] * K + 4 * lane);
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) w[g][u] = *reinterpret_cast<const wfrag*>(base + (size_t)ES * 256 * (size_t)(wave + u * NW));
-  }
+  for (int g = 0; g < G; ++g) Ws[g] = W;
+  pchain::load_w<NW, OT, G, NCH>(w, Ws, c0, K);
 }
-// SHARED (wide operands, K >= 1024): every tile of a row tile reads the same [16, K] slab, and the workgroups of one XCD all belong
-// to the same row tile (blockIdx % 8 fixes blockIdx % rt for rt = 1, 2, 4, 8) — so once one wave has seen the slab's canary words
-// arrive (sc1 polls of word 0 of every 1 KB block), the fragments are read with ORDINARY loads: the first workgroup of the XCD
-// brings a line into the XCD's L2, the others hit it, and the fabric carries the slab once per XCD instead of once per tile.  Every
-// word is still validated: a fragment that holds a sentinel (a line cached before its last store landed) is re-read with sc1 loads,
-// which bypass the stale line.
 template <int OT, int G, int NCH, bool SHARED, class Mid>
 __device__ __forceinline__ void product(const float* A16, int r0, int nrows, int K, const typename WFrag<OT>::type (&w)[G][NCH], f32x4 (&acc)[G], Poll& pl,
                                         Mid mid) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool aok = (r0 + (lane & 15)) < nrows;
-  const rsrc_t ar = make_rsrc(A16);
-  const unsigned aoff = 4u * ((unsigned)(r0 >> 4) * 16u * (unsigned)K + 4u * (unsigned)lane) + 1024u * (unsigned)wave;
-  f32x4 a[NCH];
-  unsigned spins = 0;
-  bool mid_pending = true;
-  if constexpr (SHARED) {
-    canary_wait(A16, r0, K, pl);  // (one wave polls; ends in a workgroup barrier)
-    const float* ap = A16 + (size_t)(r0 >> 4) * 16 * K + 4 * lane + 256 * wave;
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) a[u] = *reinterpret_cast<const f32x4*>(ap + 256 * (size_t)(u * NW));
-    mid();
-    mid_pending = false;
-    bool bad = false;
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) bad |= any_sentinel(a[u]);
-    if (!__any(bad && aok)) goto multiply;
-  }
-  for (;;) {
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) a[u] = ld_sc1_x4(ar, aoff + 1024u * (unsigned)(u * NW));
-    if (mid_pending) { mid(); mid_pending = false; }
-    bool bad = false;
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) bad |= any_sentinel(a[u]);
-    if (!__any(bad && aok) || pl.dead) break;
-    if (spin_tick(spins, pl.ctl, pl.code, pl.dead)) break;
-    pl.sleep();
-  }
-multiply:
-  if constexpr (OT != OP_F32) {
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-      const u32x2 q = {aok ? pk16<OT>(a[u][0], a[u][1]) : 0u, aok ? pk16<OT>(a[u][2], a[u][3]) : 0u};
-      const s16x4 ab = __builtin_bit_cast(s16x4, q);
-#pragma unroll
-      for (int g = 0; g < G; ++g) acc[g] = mfma16<OT>(ab, __builtin_bit_cast(s16x4, w[g][u]), acc[g]);
-    }
-  } else {
-#pragma unroll
-    for (int u = 0; u < NCH; ++u)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int g = 0; g < G; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(aok ? a[u][e] : 0.f, w[g][u][e], acc[g], 0, 0, 0);
-  }
+  const float* const As[1] = {A16};
+  product_regs<NW, OT, 1, G, MapSame, NCH, SHARED>(As, r0, nrows, K, w, acc, pl, mid);
 }
 
 struct TileAt { int r0, c0; };

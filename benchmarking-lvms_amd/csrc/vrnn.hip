@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "pchain.h"
+#include "vrnn_static.h"
 
 namespace blvm {
 namespace {
@@ -357,26 +358,24 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     // shared deal (row groups, many row tiles): no range of its own for the hidden projection -- it runs on the posterior half after that
     // half's run, in the window where only the prior half works on the heads and the phi_z run
     const bool shared = vrnn_shared_deal(groups, tl);
-    const int def_n = shared ? 0 : range_for(3 * ctR * tl, std::min(cus / 4, 64));
-    const int half = range_for(ctH * tl, (cus - def_n) / 2);            // prior | posterior halves of a link
-    const int g = 2 * half;
+    const VrnnFwdDeal dl = vrnn_fwd_deal(ctH, ctZ, ctR, tl, cus, shared);  // (vrnn_static.h: the ranges of every link)
     Builder bld;
-    bld.begin(pchain_optype(B), Tp, B, groups ? 8 : 4, false, g);
+    bld.begin(pchain_optype(B), Tp, B, groups ? 8 : 4, false, dl.g);
     bld.p.rt_group = RTG;
     // F1: hidden projection (the first prior layer and the h-half of the first posterior layer open the runs below)
     Operands hp;
     hp.p[LIN_A] = {rs.H16, xR}; hp.p[LIN_W] = rs.Whh; hp.p[LIN_BIAS] = w->gru_bhh; hp.p[LIN_ORM] = {rs.GHb, s3R}; hp.ld[LD_OUT] = 3 * R;
-    auto hproj = [&](int wg0, int nwg) { add_desc(bld, K_LIN, 3 * ctR, wg0, nwg, R, DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0), 0, Tp, hp); };
-    if (!shared) hproj(g, def_n);
+    auto hproj = [&]() { add_desc(bld, K_LIN, dl.hproj.ct, dl.hproj.wg0, dl.hproj.nwg, R, DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0), 0, Tp, hp); };
+    if (!shared) hproj();
     // F1 .. F3 of a chain: one visit.  The link in front of a run of same-shape links joins the run's descriptor visit (its own K = R,
     // the posterior's with its x-part addend): one visit less per chain and step (~1 us each, tools/probe_engine_chain.py)
     {
       const SeqLink lp[3] = {{rs.Wp[0], w->prior_b[0], rs.P[0], sH, H, rs.P16[0]}, {rs.Wp[1], w->prior_b[1], rs.P[1], sH, H, rs.P16[1]}, {rs.Wp[2], w->prior_b[2], rs.P[2], sH, H, rs.P16[2]}};
       const SeqLink lq[3] = {{rs.Wq[0], nullptr, rs.Q[0], sH, H, rs.Q16[0]}, {rs.Wq[1], w->post_b[1], rs.Q[1], sH, H, rs.Q16[1]}, {rs.Wq[2], w->post_b[2], rs.Q[2], sH, H, rs.Q16[2]}};
-      add_linseq(bld, ctH, 0, half, H, true, false, 0, Tp, {rs.H16, xR}, 3, lp, 0, xH, ctH, 0.f, 0, R);
-      add_linseq(bld, ctH, half, half, H, true, false, 0, Tp, {rs.H16, xR}, 3, lq, 0, xH, ctH, 0.f, 0, R, {rs.XQ, sH}, H);
+      add_linseq(bld, ctH, dl.prior.wg0, dl.prior.nwg, H, true, false, 0, Tp, {rs.H16, xR}, 3, lp, 0, xH, ctH, 0.f, 0, R);
+      add_linseq(bld, ctH, dl.post.wg0, dl.post.nwg, H, true, false, 0, Tp, {rs.H16, xR}, 3, lq, 0, xH, ctH, 0.f, 0, R, {rs.XQ, sH}, H);
     }
-    if (shared) hproj(half, half);
+    if (shared) hproj();
     {  // F4: heads + sample
       Operands o;
       o.p[HEAD_P16] = {rs.P16[2], xH}; o.p[HEAD_Q16] = {rs.Q16[2], xH}; o.p[HEAD_WP] = rs.Wph; o.p[HEAD_BP] = w->prior_hb; o.p[HEAD_WQ] = rs.Wqh;
@@ -384,7 +383,7 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       o.p[HEAD_SD_Q] = {sd_q, sZ}; o.p[HEAD_RAW_P] = {rs.RAWP, sZ}; o.p[HEAD_RAW_Q] = {rs.RAWQ, sZ}; o.p[HEAD_Z] = {z, sZ}; o.p[HEAD_Z16] = {rs.Z16, xZ};
       o.ld[LD_OUT] = Z; o.n16[N16_OUT] = ctZ; o.i[HEAD_I_Z] = Z; o.i[HEAD_I_RESIDUAL] = residual_posterior; o.f[HEAD_F_BETA] = beta; o.f[HEAD_F_INV_BETA] = 1.f / beta;
       o.f[HEAD_F_SD_EPS] = sd_eps;
-      add_desc(bld, K_HEAD, ctZ, 0, range_for(ctZ * tl, shared ? half : g), H, 0, 0, Tp, o);
+      add_desc(bld, K_HEAD, ctZ, dl.head.wg0, dl.head.nwg, H, 0, 0, Tp, o);
     }
     // F5..F8: phi_z MLP (the last layer writes phi into decin row t)
     const int first_seq = Z == H ? 0 : 1;  // (the first layer's K is Z: part of the run only when Z == H)
@@ -392,13 +391,13 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       Operands o;
       o.p[LIN_A] = {rs.Z16, xZ}; o.p[LIN_W] = rs.Wf[0]; o.p[LIN_BIAS] = w->phi_b[0]; o.p[LIN_ORM] = {rs.FZ[0], sH}; o.ld[LD_OUT] = H; o.p[LIN_O16] = {rs.FZ16[0], xH};
       o.n16[N16_OUT] = ctH;
-      add_desc(bld, K_LIN, ctH, 0, range_for(ctH * tl, shared ? half : g), Z, DF_RELU, 0, Tp, o);
+      add_desc(bld, K_LIN, ctH, dl.phi.wg0, dl.phi.nwg, Z, DF_RELU, 0, Tp, o);
     }
     {
       SeqLink lf[4];
       for (int l = first_seq; l < 4; ++l)
         lf[l - first_seq] = SeqLink{rs.Wf[l], w->phi_b[l], l == 3 ? decin : rs.FZ[l], l == 3 ? sD : sH, l == 3 ? ldd : H, l == 3 ? rs.PHI16 : rs.FZ16[l]};
-      add_linseq(bld, ctH, 0, range_for(ctH * tl, shared ? half : g), H, true, false, 0, Tp, first_seq == 0 ? Ptr(rs.Z16, xZ) : Ptr(rs.FZ16[0], xH), 4 - first_seq,
+      add_linseq(bld, ctH, dl.phi.wg0, dl.phi.nwg, H, true, false, 0, Tp, first_seq == 0 ? Ptr(rs.Z16, xZ) : Ptr(rs.FZ16[0], xH), 4 - first_seq,
                  lf, 0, xH, ctH, 0.f, 0);
     }
     {  // F9: GRU
@@ -406,7 +405,7 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       o.p[GRU_X16] = {rs.PHI16, xH}; o.p[GRU_WIH] = rs.Wih; o.p[GRU_XG] = {rs.XG, s3R}; o.p[GRU_GH] = {rs.GHb, s3R}; o.p[GRU_HPREV] = {decin + H, sD};
       o.p[GRU_HRM] = {decin + sD + H, sD}; o.p[GRU_H16] = {rs.H16 + xR, xR}; o.p[GRU_RG] = {rs.RG, sR}; o.p[GRU_UG] = {rs.UG, sR}; o.p[GRU_NG] = {rs.NG, sR};
       o.ld[GRU_LD_HPREV] = ldd; o.ld[LD_OUT] = ldd; o.n16[N16_OUT] = ctR; o.i[GRU_I_R] = R;
-      add_desc(bld, K_GRU, ctR, 0, range_for(ctR * tl, g), H, 0, 0, Tp, o);
+      add_desc(bld, K_GRU, ctR, dl.gru.wg0, dl.gru.nwg, H, 0, 0, Tp, o);
     }
     // sentinel-fill what the launch polls: the T16 copies, the hidden projection, and decin (the GRU link polls words of h)
     BLVM_HIP(pchain_fill_sentinel(rs.H16, rs.x16_bytes, s));
@@ -584,11 +583,9 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     // (shared deal: see vrnn_fwd -- here the gentle link is GB, which the posterior half runs while the prior half
     // takes the gradient back through the phi_z run and the heads)
     const bool shared = vrnn_shared_deal(groups, tl);
-    const int def_n = shared ? 0 : range_for(ctR * tl, std::min(cus / 4, 64));  // GB link
-    const int half = range_for(ctH * tl, (cus - def_n) / 2), g = 2 * half;
-    const int wide = shared ? half : g;  // range of the links between the GRU backward and the heads
+    const VrnnBwdDeal dl = vrnn_bwd_deal(ctH, ctZ, ctR, tl, cus, shared, pchain_split3());  // (vrnn_static.h: the ranges of every link)
     Builder bld;
-    bld.begin(pchain_optype(B), T + 1, B, groups ? 8 : 2, true, g);
+    bld.begin(pchain_optype(B), T + 1, B, groups ? 8 : 2, true, dl.g);
     bld.p.rt_group = RTG;
     auto last = [&](const float* base, long step) { return rev(base, step, T - 1); };  // slab of t = T'-1, walked backwards
     {  // Ba: complete the gradient wrt h_t, GRU gate derivatives of step t (s = T': only the gradient wrt the initial state)
@@ -599,36 +596,34 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       o.p[GRUB_DGI16] = last(ws.DGI16, x3R); o.p[GRUB_DGH] = last(ws.DGH, s3R); o.p[GRUB_DGH16] = last(ws.DGH16, x3R); o.p[GRUB_GA] = last(ws.GA, sR);
       o.p[GRUB_G_OUT] = d_h0 ? d_h0 : ws.G; o.ld[GRUB_LD_H] = ldd; o.ld[LD_OUT] = 3 * R; o.n16[N16_OUT] = 3 * ctR; o.i[GRUB_I_R] = R; o.i[GRUB_I_GEMM_FROM] = 1;
       o.i[GRUB_I_GATES_TO] = T; o.i[GRUB_I_GIN_FROM] = 1;
-      add_desc(bld, K_GRUB, ctR, 0, range_for(ctR * tl, g), H, 0, 0, T + 1, o);
+      add_desc(bld, K_GRUB, ctR, dl.grub.wg0, dl.grub.nwg, H, 0, 0, T + 1, o);
     }
     // Bb: dphi through the GRU input projection (+ the decoder's gradient, through phi's ReLU) | GB[t] = GA[t] + DGH[t] W_hh
     // The K = 3R product is the fattest link of the step (96 KB of operands per tile): when a third range of workgroups is free it
     // runs as three K = R links side by side (the r | u | n thirds of DGI and of W_ih^T), each writing a full slab of partial sums
     // (the derivative mask distributes over the sum; the decoder's gradient joins the first), and B3 adds the three slabs up as it
     // loads them.
-    const int spare = cus - g - def_n;
-    const bool split3 = !shared && spare >= 8 && half >= 8 && pchain_split3();
+    const bool split3 = dl.split3;
     Operands o;  // (ld[LIN_LD_A], i[LIN_I_W_WIDTH] of a part: widths of the slab / of the packed rows the K-range is taken from)
     o.p[LIN_GATE] = last(decin, sD); o.ld[LIN_LD_ADD] = ldd; o.ld[LIN_LD_GATE] = ldd; o.ld[LD_OUT] = H; o.n16[N16_OUT] = ctH;
     if (split3) {
       const size_t wthird = (size_t)ctR * 256 / (bld.p.ot != OP_F32 ? 2 : 1);  // the packed weight's k-chunks [ctR * part, ...) (16-bit packs: half the floats)
       float* const orm[3] = {ws.DPHI[3], ws.DPHI3b, ws.DPHI3c};
       float* const o16[3] = {ws.DPHI16[3], ws.DPHI16b, ws.DPHI16c};
-      const int wg0s[3] = {0, half, g + def_n}, nwgs[3] = {range_for(ctH * tl, half), range_for(ctH * tl, half), range_for(ctH * tl, spare)};
       o.ld[LIN_LD_A] = 3 * R; o.i[LIN_I_W_WIDTH] = 3 * R;
       for (int part = 0; part < 3; ++part) {
         o.p[LIN_A] = last(ws.DGI16 + (size_t)part * ctR * 256, x3R); o.p[LIN_W] = ws.wihT + part * wthird; o.p[LIN_ADD] = part == 0 ? last(d_decin, sD) : Ptr();
         o.p[LIN_ORM] = last(orm[part], sH); o.p[LIN_O16] = last(o16[part], xH);
-        add_desc(bld, K_LIN, ctH, wg0s[part], nwgs[part], R, 0, 0, T, o);
+        add_desc(bld, K_LIN, ctH, dl.part[part].wg0, dl.part[part].nwg, R, 0, 0, T, o);
       }
     } else {
       o.p[LIN_A] = last(ws.DGI16, x3R); o.p[LIN_W] = ws.wihT; o.p[LIN_ADD] = last(d_decin, sD); o.p[LIN_ORM] = last(ws.DPHI[3], sH);
       o.p[LIN_O16] = last(ws.DPHI16[3], xH);
-      add_desc(bld, K_LIN, ctH, 0, range_for(ctH * tl, wide), 3 * R, 0, 0, T, o);
+      add_desc(bld, K_LIN, ctH, dl.dphi.wg0, dl.dphi.nwg, 3 * R, 0, 0, T, o);
     }
     Operands gb;
     gb.p[LIN_A] = last(ws.DGH16, x3R); gb.p[LIN_W] = ws.whhT; gb.p[LIN_ADD] = last(ws.GA, sR); gb.ld[LIN_LD_ADD] = R; gb.p[LIN_ORM] = last(ws.GB, sR); gb.ld[LD_OUT] = R;
-    add_desc(bld, K_LIN, ctR, shared ? half : g, shared ? half : def_n, 3 * R, DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0), 0, T, gb);
+    add_desc(bld, K_LIN, ctR, dl.gb.wg0, dl.gb.nwg, 3 * R, DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0), 0, T, gb);
     // B3..B5: back through phi_z layers 3, 2, 1: runs of backward links (K_LINSEQ), D_{i+1} = (D_i W_i) masked by the saved activation
     auto blink = [&](const float* W, const float* gate, float* orm, float* o16) { return rev_link(W, gate, orm, o16, T - 1, sH, H, xH); };
     const SeqLink lf[3] = {blink(ws.fT[3], rs.FZ[2], ws.DPHI[2], ws.DPHI16[2]), blink(ws.fT[2], rs.FZ[1], ws.DPHI[1], ws.DPHI16[1]),
@@ -637,9 +632,9 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       Operands o3;
       o3.p[LIN_A] = last(ws.DPHI16[3], xH); o3.p[LIN_W] = ws.fT[3]; o3.p[LIN_GATE] = last(rs.FZ[2], sH); o3.ld[LIN_LD_GATE] = H; o3.p[LIN_ORM] = last(ws.DPHI[2], sH);
       o3.ld[LD_OUT] = H; o3.p[LIN_O16] = last(ws.DPHI16[2], xH); o3.n16[N16_OUT] = ctH; o3.p[LIN_A2] = last(ws.DPHI16b, xH); o3.p[LIN_A3] = last(ws.DPHI16c, xH);
-      add_desc(bld, K_LIN, ctH, 0, range_for(ctH * tl, wide), H, DF_A_SUM3, 0, T, o3);
+      add_desc(bld, K_LIN, ctH, dl.wide_h.wg0, dl.wide_h.nwg, H, DF_A_SUM3, 0, T, o3);
     }
-    add_linseq(bld, ctH, 0, range_for(ctH * tl, wide), H, false, true, 0, T, last(ws.DPHI16[split3 ? 2 : 3], xH), split3 ? 2 : 3, lf + (split3 ? 1 : 0), -sH,
+    add_linseq(bld, ctH, dl.wide_h.wg0, dl.wide_h.nwg, H, false, true, 0, T, last(ws.DPHI16[split3 ? 2 : 3], xH), split3 ? 2 : 3, lf + (split3 ? 1 : 0), -sH,
                -xH, ctH, 0.f, H);
     {  // B6: dz and the heads
       Operands z;
@@ -648,15 +643,15 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       z.p[DZ_C_RAW] = c_raw; z.p[DZ_C_FN] = c_fn; z.p[DZ_DQH] = last(ws.DQH, s2Z); z.p[DZ_DQH16] = last(ws.DQH16, x2Z); z.p[DZ_DPH] = last(ws.DPH, s2Z);
       z.p[DZ_DPH16] = last(ws.DPH16, x2Z); z.ld[LD_OUT] = 2 * Z; z.n16[N16_OUT] = 2 * ctZ; z.i[DZ_I_Z] = Z; z.i[DZ_I_RESIDUAL] = residual_posterior;
       z.i[DZ_I_STRIDE] = stride; z.i[DZ_I_T0] = T - 1; z.f[DZ_F_FN_FLOOR] = fn_floor; z.f[DZ_F_BETA] = beta; z.f[DZ_F_SD_EPS] = sd_eps;
-      add_desc(bld, K_DZ, ctZ, 0, range_for(ctZ * tl, wide), H, 0, 0, T, z);
+      add_desc(bld, K_DZ, ctZ, dl.dz.wg0, dl.dz.nwg, H, 0, 0, T, z);
     }
     // B7: heads -> last hidden layers;  B8, B9: hidden layers 2, 1  (prior | posterior).  B7 .. B9 of a chain: one visit (the heads'
     // gradient link, K = 2Z, joins the run's descriptor visit)
     {
       const SeqLink lp[3] = {blink(ws.phT, rs.P[2], ws.DP[2], ws.DP16[2]), blink(ws.pT[2], rs.P[1], ws.DP[1], ws.DP16[1]), blink(ws.pT[1], rs.P[0], ws.DP[0], ws.DP16[0])};
       const SeqLink lq[3] = {blink(ws.qhT, rs.Q[2], ws.DQ[2], ws.DQ16[2]), blink(ws.qT[2], rs.Q[1], ws.DQ[1], ws.DQ16[1]), blink(ws.qT[1], rs.Q[0], ws.DQ[0], ws.DQ16[0])};
-      add_linseq(bld, ctH, 0, half, H, false, true, 0, T, last(ws.DPH16, x2Z), 3, lp, -sH, -xH, ctH, 0.f, H, 2 * Z);
-      add_linseq(bld, ctH, half, half, H, false, true, 0, T, last(ws.DQH16, x2Z), 3, lq, -sH, -xH, ctH, 0.f, H, 2 * Z);
+      add_linseq(bld, ctH, dl.prior.wg0, dl.prior.nwg, H, false, true, 0, T, last(ws.DPH16, x2Z), 3, lp, -sH, -xH, ctH, 0.f, H, 2 * Z);
+      add_linseq(bld, ctH, dl.post.wg0, dl.post.nwg, H, false, true, 0, T, last(ws.DQH16, x2Z), 3, lq, -sH, -xH, ctH, 0.f, H, 2 * Z);
     }
     // sentinel-fill what the launch polls: GA, GB (single words) and the T16 copies
     BLVM_HIP(pchain_fill_sentinel(ws.GA, ws.x16_bytes, s));

@@ -14,12 +14,16 @@
 // (blvm_pchain_static_chain_probe), priced per link against the engine and the bare tile loop (tools/probe_static_chain.py).
 // A workgroup picks its role once from its index (prior half, posterior half, gentle range, spare range); each role's step loop
 // is its own branch, a straight sequence of visits, and a visit is skipped when the deal gives the workgroup no tile of the link.
+// The deal is fixed for the launch, so a workgroup owns the same tile of a link in every step: the links of the critical path keep that
+// tile's weight fragments in registers (loaded once in front of the step loop; see "Resident weights" below and pchain.h) and a visit
+// issues no weight load.  The converter refuses a program whose deal gives a workgroup two tiles of such a link.
 // blvm_pchain_static(0) sends the VRNN programs to the interpreter (tests compare both paths in one process).
 #include <algorithm>
 #include <mutex>
 
 #include "common.h"
 #include "pchain.h"
+#include "vrnn_static.h"
 
 namespace blvm {
 namespace {
@@ -52,7 +56,9 @@ struct LinChainArgs {
   Ctl ctl;
 };
 
-template <int NW, int K>
+// RES: the workgroup owns one tile; its weight fragments are loaded once, in front of the step loop (pchain.h "resident weights"),
+// and a step is poll -> MFMA -> reduce -> epilogue.  !RES re-reads them every step (the form the probe prices the resident one against).
+template <int NW, int K, bool RES>
 __global__ __launch_bounds__(NW * 64, 1) void static_lin_chain_kernel(LinChainArgs a) {
   __shared__ __attribute__((aligned(16))) float red[2][NW * 256];
   const int w = blockIdx.x, B = a.B;
@@ -61,6 +67,20 @@ __global__ __launch_bounds__(NW * 64, 1) void static_lin_chain_kernel(LinChainAr
   if (nt == 0) return;
   Poll pl{a.ctl, 0u, false, 1};
   int par = 0;
+  if constexpr (RES) {
+    const int trc = __builtin_amdgcn_readlane(tiles, 0), r0 = trc & 0xffff, c0 = (trc >> 16) * 16;
+    WRegs<OP_F32, 1, K / (16 * NW)> ws;
+    const float* const Ws[1] = {a.W};
+    const int cs[1] = {c0};
+    load_w<NW, OP_F32, 1, K / (16 * NW)>(ws.w, Ws, cs, K);
+    for (int s = a.s0; s < a.S; ++s) {
+      pl.code = (unsigned)s << 4;
+      auto late = [&]() { return LinLate{a.bias, nullptr, nullptr, 0, 0, false, true, 0.f, Out{a.orm.at(s), a.ldo, false, a.o16.at(s), a.n16}}; };
+      tile_lin_late<NW, OP_F32>(a.a16.at(s), 0, true, a.W, K, late, r0, c0, B, red[par], pl, nullptr, nullptr, 0, ws);
+      par ^= 1;
+    }
+    return;
+  }
   for (int s = a.s0; s < a.S; ++s) {
     pl.code = (unsigned)s << 4;
     const float* A = a.a16.at(s);
@@ -102,8 +122,8 @@ struct GruArgs {
   int ld0, ld3, n16, n16b, R;
 };
 struct DzArgs {
-  SPtr D, D2, add, mu_q, sd_q, mu_p, sd_p, eps, raw_q, raw_p, muq_raw, dqh, dqh16, dph, dph16;
-  const float *WT, *WT2, *c_raw, *c_fn;
+  SPtr D, add, mu_q, sd_q, mu_p, sd_p, eps, raw_q, raw_p, muq_raw, dqh, dqh16, dph, dph16;
+  const float *WT, *c_raw, *c_fn;
   const int32_t* x_sl;
   int ld1, ld3, n16, Z, residual, stride, t0, first_gemm;
   float fn_floor, beta, sd_eps;
@@ -133,8 +153,60 @@ struct Walk {
   }
 };
 
-template <int NW, int K, int FLAGS>
-__device__ __forceinline__ void visit_lin(const LinArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+// Resident weights (pchain.h): a link of the critical path deals a workgroup at most ONE tile (the converter refuses any other
+// deal), the same tile in every step, so the role loads that tile's weight fragments once in front of its step loop — load_* below,
+// skipped where the deal gives the workgroup no tile — and a visit issues no weight load.  Per lane, 16 waves: 4 registers per
+// product and 256 k.  The gentle links (several tiles per workgroup, off the critical path) keep reading theirs (WMem).
+template <int K, int G = 1>
+using Res = WRegs<OP_F32, G, K / 256>;
+template <int N, int K0, int K>
+struct RunRes {  // a run of N links, link 0 of K0 and the others of K
+  Res<K0> first;
+  Res<K> rest[N - 1];
+};
+__device__ __forceinline__ int tile_c0(int tiles) { return (__builtin_amdgcn_readlane(tiles, 0) >> 16) * 16; }  // the workgroup's one tile: lane 0
+
+template <int NW, int K>
+__device__ __forceinline__ void load_lin(Res<K>& r, const float* W, int ldw, int tiles, int nt) {
+  if (nt == 0) return;
+  const float* const Ws[1] = {W};
+  const int cs[1] = {tile_c0(tiles)};
+  load_w<NW, OP_F32, 1, K / 256>(r.w, Ws, cs, ldw > 0 ? ldw : K);  // (ldw: the packed rows' length where the link takes a K-range of them)
+}
+template <int NW, int N, int K0, int K>
+__device__ __forceinline__ void load_run(RunRes<N, K0, K>& r, const SeqArgs& q, int tiles, int nt) {
+  load_lin<NW, K0>(r.first, q.W[0], K0, tiles, nt);
+#pragma unroll
+  for (int li = 1; li < N; ++li) load_lin<NW, K>(r.rest[li - 1], q.W[li], K, tiles, nt);
+}
+template <int NW>
+__device__ __forceinline__ void load_head(Res<kH, 4>& r, const HeadArgs& q, int tiles, int nt) {
+  if (nt == 0) return;
+  const int c0 = tile_c0(tiles);
+  const float* const Ws[4] = {q.Wp, q.Wp, q.Wq, q.Wq};
+  const int cs[4] = {c0, q.Z + c0, c0, q.Z + c0};
+  load_w<NW, OP_F32, 4, 1>(r.w, Ws, cs, kH);
+}
+template <int NW>
+__device__ __forceinline__ void load_gru(Res<kH, 3>& r, const GruArgs& q, int tiles, int nt) {
+  if (nt == 0) return;
+  const int c0 = tile_c0(tiles);
+  const float* const Ws[3] = {q.Wih, q.Wih, q.Wih};
+  const int cs[3] = {c0, q.R + c0, 2 * q.R + c0};
+  load_w<NW, OP_F32, 3, 1>(r.w, Ws, cs, kH);
+}
+template <int NW>
+__device__ __forceinline__ void load_grub(Res<kH, 2>& r, const GrubArgs& q, int tiles, int nt) {
+  if (nt == 0) return;
+  const int c0 = tile_c0(tiles);
+  const float* const Ws[2] = {q.W0, q.W1};
+  const int cs[2] = {c0, c0};
+  load_w<NW, OP_F32, 2, 1>(r.w, Ws, cs, kH);
+}
+
+// WS: Res<K> — the link's one tile on resident weights; WMem — every tile the deal gives, weights read per tile
+template <int NW, int K, int FLAGS, class WS>
+__device__ __forceinline__ void visit_lin(const LinArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const WS& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   constexpr bool sum3 = (FLAGS & DF_A_SUM3) != 0;
   wk.at(d, s, (FLAGS & DF_GENTLE) != 0);
@@ -145,16 +217,17 @@ __device__ __forceinline__ void visit_lin(const LinArgs& q, const Deal& d, int s
     return LinLate{q.bias, q.add.at(s), q.gate.at(s), q.ld1, q.ld2, (FLAGS & DF_ADD_POLLED) != 0, (FLAGS & DF_RELU) != 0, q.slope,
                    Out{q.orm.at(s), q.ld3, (FLAGS & DF_RM_SC1) != 0, q.o16.at(s), q.n16, q.o16b.at(s), q.n16b}};
   };
-  for (int tk = 0; tk < nt; ++tk) {
+  for (int tk = 0; tk < (WS::resident ? 1 : nt); ++tk) {
     const int trc = __builtin_amdgcn_readlane(tiles, tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
     if constexpr ((FLAGS & DF_CANARY) != 0) canary_wait(A, tr0, K, wk.pl, q.ld0);
-    tile_lin_late<NW, false>(A, q.ld0, true, q.W, K, late, tr0, tc0, wk.B, wk.red(), wk.pl, A2, A3, q.w_width);
+    tile_lin_late<NW, OP_F32>(A, q.ld0, true, q.W, K, late, tr0, tc0, wk.B, wk.red(), wk.pl, A2, A3, q.w_width, ws);
   }
 }
 
 template <int NW, int N, int K0, int K, bool GATED>
-__device__ __forceinline__ void visit_run(const SeqArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+__device__ __forceinline__ void visit_run(const SeqArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const RunRes<N, K0, K>& rr) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
+  const int trc = __builtin_amdgcn_readlane(tiles, 0), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
   const float* A = q.a0.at(s);
 #pragma unroll
   for (int li = 0; li < N; ++li) {
@@ -164,41 +237,35 @@ __device__ __forceinline__ void visit_run(const SeqArgs& q, const Deal& d, int s
       return LinLate{GATED ? nullptr : aux, li == 0 ? q.add0.at(s) : nullptr, GATED ? aux : nullptr, q.ldadd0, q.ldgate, false, !GATED, q.slope,
                      Out{q.orm[li].at(s), q.ld[li], false, q.o16[li].at(s), q.n16}};
     };
-    for (int tk = 0; tk < nt; ++tk) {
-      const int trc = __builtin_amdgcn_readlane(tiles, tk);
-      tile_lin_late<NW, false>(A, 0, true, q.W[li], li == 0 ? K0 : K, late, trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl);
-    }
+    if (li == 0) tile_lin_late<NW, OP_F32>(A, 0, true, q.W[li], K0, late, tr0, tc0, wk.B, wk.red(), wk.pl, nullptr, nullptr, 0, rr.first);
+    else tile_lin_late<NW, OP_F32>(A, 0, true, q.W[li], K, late, tr0, tc0, wk.B, wk.red(), wk.pl, nullptr, nullptr, 0, rr.rest[li > 0 ? li - 1 : 0]);
     A = q.o16[li].at(s);  // the next link multiplies what this one stored
   }
 }
 
 template <int NW>
-__device__ __forceinline__ void visit_head(const HeadArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+__device__ __forceinline__ void visit_head(const HeadArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const Res<kH, 4>& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   wk.at(d, s, false);
   const HeadOut o{q.mu_p.at(s), q.sd_p.at(s), q.mu_q.at(s), q.sd_q.at(s), q.raw_p.at(s), q.raw_q.at(s), q.muq_raw.at(s),
                   Out{q.z.at(s), q.ld3, false, q.z16.at(s), q.n16, q.z16b.at(s), q.n16b}};
-  for (int tk = 0; tk < nt; ++tk) {
-    const int trc = __builtin_amdgcn_readlane(tiles, tk);
-    tile_head<NW, false>(q.P.at(s), q.Q.at(s), true, q.Wp, q.bp, q.Wq, q.bq, q.eps.at(s), o, kH, q.Z, q.residual, q.beta, q.inv_beta, q.sd_eps,
-                         trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl);
-  }
+  const int trc = __builtin_amdgcn_readlane(tiles, 0);
+  tile_head<NW, OP_F32>(q.P.at(s), q.Q.at(s), true, q.Wp, q.bp, q.Wq, q.bq, q.eps.at(s), o, kH, q.Z, q.residual, q.beta, q.inv_beta, q.sd_eps,
+                        trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl, ws);
 }
 
 template <int NW>
-__device__ __forceinline__ void visit_gru(const GruArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+__device__ __forceinline__ void visit_gru(const GruArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const Res<kH, 3>& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   wk.at(d, s, false);
   const Out o{q.hrm.at(s), q.ld3, true, q.h16.at(s), q.n16, q.h16b.at(s), q.n16b};
-  for (int tk = 0; tk < nt; ++tk) {
-    const int trc = __builtin_amdgcn_readlane(tiles, tk);
-    tile_gru<NW, false>(q.X.at(s), 0, true, q.Wih, kH, q.xg.at(s), q.bih, q.gh.at(s), q.hprev.at(s), q.ld0, q.R, o, q.rg.at(s), q.ug.at(s), q.ng.at(s),
-                        trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl);
-  }
+  const int trc = __builtin_amdgcn_readlane(tiles, 0);
+  tile_gru<NW, OP_F32>(q.X.at(s), 0, true, q.Wih, kH, q.xg.at(s), q.bih, q.gh.at(s), q.hprev.at(s), q.ld0, q.R, o, q.rg.at(s), q.ug.at(s), q.ng.at(s),
+                       trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl, ws);
 }
 
 template <int NW>
-__device__ __forceinline__ void visit_dz(const DzArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+__device__ __forceinline__ void visit_dz(const DzArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const Res<kH>& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   wk.at(d, s, false);
   DzIn z;
@@ -209,15 +276,15 @@ __device__ __forceinline__ void visit_dz(const DzArgs& q, const Deal& d, int s, 
   z.fn_floor = q.fn_floor; z.beta = q.beta; z.sd_eps = q.sd_eps;
   z.has_gemm = s >= q.first_gemm;
   const Out oq{q.dqh.at(s), q.ld3, false, q.dqh16.at(s), q.n16}, op{q.dph.at(s), q.ld3, false, q.dph16.at(s), q.n16};
-  for (int tk = 0; tk < nt; ++tk) {
-    const int trc = __builtin_amdgcn_readlane(tiles, tk);
-    tile_dz<NW, false>(q.D.at(s), q.WT, q.D2.at(s), q.WT2, true, q.add.at(s), q.ld1, false, z, oq, op, kH, q.Z, trc & 0xffff, (trc >> 16) * 16, wk.B,
-                       wk.red(), wk.pl);
-  }
+  const int trc = __builtin_amdgcn_readlane(tiles, 0);
+  tile_dz<NW, OP_F32>(q.D.at(s), q.WT, nullptr, nullptr, true, q.add.at(s), q.ld1, false, z, oq, op, kH, q.Z, trc & 0xffff, (trc >> 16) * 16, wk.B,
+                      wk.red(), wk.pl, ws);
+  // ws holds ONE product's fragments (Res<kH>), so tile_dz runs its single-operand form whatever D2 is: vrnn_static_bwd returns
+  // "not applicable" for a program whose dz descriptor has a second operand (DZ_D2_16 != null).  Keep the two in step.
 }
 
 template <int NW>
-__device__ __forceinline__ void visit_grub(const GrubArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk) {
+__device__ __forceinline__ void visit_grub(const GrubArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const Res<kH, 2>& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   wk.at(d, s, false);
   GrubIn g;
@@ -227,10 +294,8 @@ __device__ __forceinline__ void visit_grub(const GrubArgs& q, const Deal& d, int
   g.dgh = Out{q.dgh.at(s), q.ld3, false, q.dgh16.at(s), q.n16};
   g.ga = q.ga.at(s); g.g_out = const_cast<float*>(q.g_out);
   g.has_gemm = s >= q.first_gemm; g.has_gates = s < q.end_gates; g.has_gin = s >= q.first_gin;
-  for (int tk = 0; tk < nt; ++tk) {
-    const int trc = __builtin_amdgcn_readlane(tiles, tk);
-    tile_grub<NW, false>(g, kH, q.R, trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl);
-  }
+  const int trc = __builtin_amdgcn_readlane(tiles, 0);
+  tile_grub<NW, OP_F32>(g, kH, q.R, trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl, ws);
 }
 
 // The kernel's own argument block (offset 0 of the kernarg segment) through a pointer the compiler cannot see through: every visit
@@ -259,40 +324,45 @@ struct FwdArgs {
 };
 constexpr int kFwdProducts = 4, kBwdProducts = 2;
 
+// a workgroup of the prior (HALF 0) or posterior (1) half: its half's run of three and whatever tile of the heads, the phi_z run and
+// the GRU the deal gives it, all on resident weights
+template <int NW, int HALF>
+__device__ __forceinline__ void fwd_half(const FwdArgs& a, int w, int rt, bool xcd, Walk& wk) {
+  const int t1 = tile_lanes(w, a.deal[1 + HALF].wg0, a.deal[1 + HALF].nwg, rt, a.deal[1 + HALF].ct, xcd), n1 = tile_count(t1);
+  const int t3 = tile_lanes(w, a.deal[3].wg0, a.deal[3].nwg, rt, a.deal[3].ct, xcd), n3 = tile_count(t3);
+  const int t4 = tile_lanes(w, a.deal[4].wg0, a.deal[4].nwg, rt, a.deal[4].ct, xcd), n4 = tile_count(t4);
+  const int t5 = tile_lanes(w, a.deal[5].wg0, a.deal[5].nwg, rt, a.deal[5].ct, xcd), n5 = tile_count(t5);
+  RunRes<3, kR, kH> run;
+  Res<kH, 4> head;
+  RunRes<4, kH, kH> phi;
+  Res<kH, 3> gru;
+  load_run<NW>(run, kargs<FwdArgs>().run[HALF], t1, n1);
+  load_head<NW>(head, kargs<FwdArgs>().head, t3, n3);
+  load_run<NW>(phi, kargs<FwdArgs>().phi, t4, n4);
+  load_gru<NW>(gru, kargs<FwdArgs>().gru, t5, n5);
+  for (int s = a.s0; s < a.S; ++s) {
+    visit_run<NW, 3, kR, kH, false>(kargs<FwdArgs>().run[HALF], kargs<FwdArgs>().deal[1 + HALF], s, t1, n1, wk, run);
+    visit_head<NW>(kargs<FwdArgs>().head, kargs<FwdArgs>().deal[3], s, t3, n3, wk, head);
+    visit_run<NW, 4, kH, kH, false>(kargs<FwdArgs>().phi, kargs<FwdArgs>().deal[4], s, t4, n4, wk, phi);
+    visit_gru<NW>(kargs<FwdArgs>().gru, kargs<FwdArgs>().deal[5], s, t5, n5, wk, gru);
+  }
+}
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_fwd_kernel(FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds_red[];
   const int w = blockIdx.x, rt = (a.B + 15) / 16;
   const bool xcd = a.xcd != 0;
   Walk wk{lds_red, lds_red + kFwdProducts * NW * 256, 0, a.B, Poll{a.ctl, 0u, false, 1}};
-  // roles, picked once: the gentle range runs the hidden projection alone; a prior or posterior workgroup runs its half's run of
-  // three and whatever tiles of the heads, the phi_z run and the GRU the deal gives it
+  // roles, picked once: the gentle range runs the hidden projection alone, the others are a half's workgroups (fwd_half)
   if (w >= a.deal[0].wg0) {
     const int t0 = tile_lanes(w, a.deal[0].wg0, a.deal[0].nwg, rt, a.deal[0].ct, xcd), n0 = tile_count(t0);
     if (n0 == 0) return;
-    for (int s = a.s0; s < a.S; ++s) visit_lin<NW, kR, DF_RM_SC1 | DF_GENTLE | DF_CANARY>(kargs<FwdArgs>().hproj, kargs<FwdArgs>().deal[0], s, t0, n0, wk);
+    for (int s = a.s0; s < a.S; ++s) visit_lin<NW, kR, DF_RM_SC1 | DF_GENTLE | DF_CANARY>(kargs<FwdArgs>().hproj, kargs<FwdArgs>().deal[0], s, t0, n0, wk, WMem());
     return;
   }
-  const int t3 = tile_lanes(w, a.deal[3].wg0, a.deal[3].nwg, rt, a.deal[3].ct, xcd), n3 = tile_count(t3);
-  const int t4 = tile_lanes(w, a.deal[4].wg0, a.deal[4].nwg, rt, a.deal[4].ct, xcd), n4 = tile_count(t4);
-  const int t5 = tile_lanes(w, a.deal[5].wg0, a.deal[5].nwg, rt, a.deal[5].ct, xcd), n5 = tile_count(t5);
-  if (w < a.deal[2].wg0) {
-    const int t1 = tile_lanes(w, a.deal[1].wg0, a.deal[1].nwg, rt, a.deal[1].ct, xcd), n1 = tile_count(t1);
-    for (int s = a.s0; s < a.S; ++s) {
-      visit_run<NW, 3, kR, kH, false>(kargs<FwdArgs>().run[0], kargs<FwdArgs>().deal[1], s, t1, n1, wk);
-      visit_head<NW>(kargs<FwdArgs>().head, kargs<FwdArgs>().deal[3], s, t3, n3, wk);
-      visit_run<NW, 4, kH, kH, false>(kargs<FwdArgs>().phi, kargs<FwdArgs>().deal[4], s, t4, n4, wk);
-      visit_gru<NW>(kargs<FwdArgs>().gru, kargs<FwdArgs>().deal[5], s, t5, n5, wk);
-    }
-  } else {
-    const int t2 = tile_lanes(w, a.deal[2].wg0, a.deal[2].nwg, rt, a.deal[2].ct, xcd), n2 = tile_count(t2);
-    for (int s = a.s0; s < a.S; ++s) {
-      visit_run<NW, 3, kR, kH, false>(kargs<FwdArgs>().run[1], kargs<FwdArgs>().deal[2], s, t2, n2, wk);
-      visit_head<NW>(kargs<FwdArgs>().head, kargs<FwdArgs>().deal[3], s, t3, n3, wk);
-      visit_run<NW, 4, kH, kH, false>(kargs<FwdArgs>().phi, kargs<FwdArgs>().deal[4], s, t4, n4, wk);
-      visit_gru<NW>(kargs<FwdArgs>().gru, kargs<FwdArgs>().deal[5], s, t5, n5, wk);
-    }
-  }
+  if (w < a.deal[2].wg0) fwd_half<NW, 0>(a, w, rt, xcd, wk);
+  else fwd_half<NW, 1>(a, w, rt, xcd, wk);
 }
 
 // Backward program (vrnn.hip vrnn_seq_bwd_impl, split3 form): 0 GRU backward (steps 0 .. T'), 1 .. 3 the K = 3R dphi product as
@@ -309,6 +379,37 @@ struct BwdArgs {
   Ctl ctl;
 };
 
+// a workgroup of the prior (HALF 0) or posterior (1) half: its half's partial sum and run of three and whatever tile of the GRU
+// backward, the summing link, the phi_z run and dz the deal gives it, all on resident weights
+template <int NW, int HALF>
+__device__ __forceinline__ void bwd_half(const BwdArgs& a, int w, int rt, bool xcd, Walk& wk) {
+  const int t0 = tile_lanes(w, a.deal[0].wg0, a.deal[0].nwg, rt, a.deal[0].ct, xcd), n0 = tile_count(t0);
+  const int t1 = tile_lanes(w, a.deal[1 + HALF].wg0, a.deal[1 + HALF].nwg, rt, a.deal[1 + HALF].ct, xcd), n1 = tile_count(t1);
+  const int t5 = tile_lanes(w, a.deal[5].wg0, a.deal[5].nwg, rt, a.deal[5].ct, xcd), n5 = tile_count(t5);
+  const int t6 = tile_lanes(w, a.deal[6].wg0, a.deal[6].nwg, rt, a.deal[6].ct, xcd), n6 = tile_count(t6);
+  const int t7 = tile_lanes(w, a.deal[7].wg0, a.deal[7].nwg, rt, a.deal[7].ct, xcd), n7 = tile_count(t7);
+  const int t8 = tile_lanes(w, a.deal[8 + HALF].wg0, a.deal[8 + HALF].nwg, rt, a.deal[8 + HALF].ct, xcd), n8 = tile_count(t8);
+  Res<kH, 2> grub;
+  Res<kR> part;
+  Res<kH> sum, dz;
+  RunRes<2, kH, kH> phi;
+  RunRes<3, 2 * kH, kH> run;
+  load_grub<NW>(grub, kargs<BwdArgs>().grub, t0, n0);
+  load_lin<NW, kR>(part, kargs<BwdArgs>().part[HALF].W, kargs<BwdArgs>().part[HALF].w_width, t1, n1);
+  load_lin<NW, kH>(sum, kargs<BwdArgs>().sum.W, kH, t5, n5);
+  load_run<NW>(phi, kargs<BwdArgs>().phi, t6, n6);
+  load_lin<NW, kH>(dz, kargs<BwdArgs>().dz.WT, kH, t7, n7);
+  load_run<NW>(run, kargs<BwdArgs>().run[HALF], t8, n8);
+  for (int s = a.s0; s < a.S; ++s) {
+    visit_grub<NW>(kargs<BwdArgs>().grub, kargs<BwdArgs>().deal[0], s, t0, n0, wk, grub);
+    visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[HALF], kargs<BwdArgs>().deal[1 + HALF], s, t1, n1, wk, part);
+    visit_lin<NW, kH, DF_A_SUM3>(kargs<BwdArgs>().sum, kargs<BwdArgs>().deal[5], s, t5, n5, wk, sum);
+    visit_run<NW, 2, kH, kH, true>(kargs<BwdArgs>().phi, kargs<BwdArgs>().deal[6], s, t6, n6, wk, phi);
+    visit_dz<NW>(kargs<BwdArgs>().dz, kargs<BwdArgs>().deal[7], s, t7, n7, wk, dz);
+    visit_run<NW, 3, 2 * kH, kH, true>(kargs<BwdArgs>().run[HALF], kargs<BwdArgs>().deal[8 + HALF], s, t8, n8, wk, run);
+  }
+}
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds_red[];
@@ -318,42 +419,20 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) 
   if (w >= a.deal[3].wg0) {  // spare range: the third partial sum alone
     const int t = tile_lanes(w, a.deal[3].wg0, a.deal[3].nwg, rt, a.deal[3].ct, xcd), n = tile_count(t);
     if (n == 0) return;
-    for (int s = a.s0; s < a.S; ++s) visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[2], kargs<BwdArgs>().deal[3], s, t, n, wk);
+    Res<kR> part;
+    load_lin<NW, kR>(part, kargs<BwdArgs>().part[2].W, kargs<BwdArgs>().part[2].w_width, t, n);
+    for (int s = a.s0; s < a.S; ++s) visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[2], kargs<BwdArgs>().deal[3], s, t, n, wk, part);
     return;
   }
   if (w >= a.deal[4].wg0) {  // gentle range: GB alone
     const int t = tile_lanes(w, a.deal[4].wg0, a.deal[4].nwg, rt, a.deal[4].ct, xcd), n = tile_count(t);
     if (n == 0) return;
-    for (int s = a.s0; s < a.S; ++s) visit_lin<NW, 3 * kR, DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | DF_CANARY>(kargs<BwdArgs>().gb, kargs<BwdArgs>().deal[4], s, t, n, wk);
+    for (int s = a.s0; s < a.S; ++s)
+      visit_lin<NW, 3 * kR, DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | DF_CANARY>(kargs<BwdArgs>().gb, kargs<BwdArgs>().deal[4], s, t, n, wk, WMem());
     return;
   }
-  const int t0 = tile_lanes(w, a.deal[0].wg0, a.deal[0].nwg, rt, a.deal[0].ct, xcd), n0 = tile_count(t0);
-  const int t5 = tile_lanes(w, a.deal[5].wg0, a.deal[5].nwg, rt, a.deal[5].ct, xcd), n5 = tile_count(t5);
-  const int t6 = tile_lanes(w, a.deal[6].wg0, a.deal[6].nwg, rt, a.deal[6].ct, xcd), n6 = tile_count(t6);
-  const int t7 = tile_lanes(w, a.deal[7].wg0, a.deal[7].nwg, rt, a.deal[7].ct, xcd), n7 = tile_count(t7);
-  if (w < a.deal[2].wg0) {  // prior half
-    const int t1 = tile_lanes(w, a.deal[1].wg0, a.deal[1].nwg, rt, a.deal[1].ct, xcd), n1 = tile_count(t1);
-    const int t8 = tile_lanes(w, a.deal[8].wg0, a.deal[8].nwg, rt, a.deal[8].ct, xcd), n8 = tile_count(t8);
-    for (int s = a.s0; s < a.S; ++s) {
-      visit_grub<NW>(kargs<BwdArgs>().grub, kargs<BwdArgs>().deal[0], s, t0, n0, wk);
-      visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[0], kargs<BwdArgs>().deal[1], s, t1, n1, wk);
-      visit_lin<NW, kH, DF_A_SUM3>(kargs<BwdArgs>().sum, kargs<BwdArgs>().deal[5], s, t5, n5, wk);
-      visit_run<NW, 2, kH, kH, true>(kargs<BwdArgs>().phi, kargs<BwdArgs>().deal[6], s, t6, n6, wk);
-      visit_dz<NW>(kargs<BwdArgs>().dz, kargs<BwdArgs>().deal[7], s, t7, n7, wk);
-      visit_run<NW, 3, 2 * kH, kH, true>(kargs<BwdArgs>().run[0], kargs<BwdArgs>().deal[8], s, t8, n8, wk);
-    }
-  } else {  // posterior half
-    const int t2 = tile_lanes(w, a.deal[2].wg0, a.deal[2].nwg, rt, a.deal[2].ct, xcd), n2 = tile_count(t2);
-    const int t9 = tile_lanes(w, a.deal[9].wg0, a.deal[9].nwg, rt, a.deal[9].ct, xcd), n9 = tile_count(t9);
-    for (int s = a.s0; s < a.S; ++s) {
-      visit_grub<NW>(kargs<BwdArgs>().grub, kargs<BwdArgs>().deal[0], s, t0, n0, wk);
-      visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[1], kargs<BwdArgs>().deal[2], s, t2, n2, wk);
-      visit_lin<NW, kH, DF_A_SUM3>(kargs<BwdArgs>().sum, kargs<BwdArgs>().deal[5], s, t5, n5, wk);
-      visit_run<NW, 2, kH, kH, true>(kargs<BwdArgs>().phi, kargs<BwdArgs>().deal[6], s, t6, n6, wk);
-      visit_dz<NW>(kargs<BwdArgs>().dz, kargs<BwdArgs>().deal[7], s, t7, n7, wk);
-      visit_run<NW, 3, 2 * kH, kH, true>(kargs<BwdArgs>().run[1], kargs<BwdArgs>().deal[9], s, t9, n9, wk);
-    }
-  }
+  if (w < a.deal[2].wg0) bwd_half<NW, 0>(a, w, rt, xcd, wk);
+  else bwd_half<NW, 1>(a, w, rt, xcd, wk);
 }
 
 // the program's pointer k of descriptor d as a stepped pointer
@@ -385,15 +464,15 @@ int static_go(Kern kernel, int slot, int grid, size_t lds, const char* what) {
   return BLVM_OK;
 }
 
-// 1: the program is not the linear chain the static kernel was compiled for
-int static_lin_chain_launch(const Program& p, hipStream_t stream) {
+// 1: the program is not the linear chain the static kernel was compiled for (resident: or it deals a workgroup more than one tile)
+int static_lin_chain_launch(const Program& p, hipStream_t stream, bool resident) {
   if (p.ndesc != 1 || p.ot != OP_F32 || p.rt_group != 1 || !int_strides(p)) return 1;
   const Desc& d = p.d[0];
   if (d.kind != K_LIN || d.flags != DF_RELU || d.f[LIN_F_SLOPE] != 0.f || (d.K != 256 && d.K != 512) || d.s_begin != 0 || d.s_end != p.S) return 1;
   if (d.ld[LIN_LD_A] != 0 || d.i[LIN_I_W_WIDTH] != 0 || d.p[LIN_ADD] || d.p[LIN_GATE] || d.p[LIN_O16B] || d.p[LIN_A2] || d.p[LIN_A3] || d.n16[N16_OUTB] != 0)
     return 1;
   const int rt = (p.B + 15) / 16;
-  if (p.xcd ? (((d.ct + 7) / 8) * rt + d.nwg / 8 - 1) / (d.nwg / 8) > kMaxTiles : (d.ct * rt + d.nwg - 1) / d.nwg > kMaxTiles) return 1;
+  if (d.nwg <= 0 || (p.xcd && d.nwg % 8 != 0) || tiles_per_workgroup(rt, d.ct, d.nwg, p.xcd != 0) > (resident ? 1 : kMaxTiles)) return 1;
   LinChainArgs a{sptr(p, d, LIN_A), sptr(p, d, LIN_ORM), sptr(p, d, LIN_O16), d.p[LIN_W], d.p[LIN_BIAS], d.ld[LD_OUT], d.n16[N16_OUT], p.B, p.s_first, p.S,
                  d.wg0, d.nwg, d.ct, p.xcd, p.ctl};
   const int grid = d.wg0 + d.nwg;
@@ -403,7 +482,8 @@ int static_lin_chain_launch(const Program& p, hipStream_t stream) {
     BLVM_CHECK_LAUNCH("static_lin_chain");
     return BLVM_OK;
   };
-  return d.K == 256 ? go(&static_lin_chain_kernel<16, 256>) : go(&static_lin_chain_kernel<16, 512>);
+  if (resident) return d.K == 256 ? go(&static_lin_chain_kernel<16, 256, true>) : go(&static_lin_chain_kernel<16, 512, true>);
+  return d.K == 256 ? go(&static_lin_chain_kernel<16, 256, false>) : go(&static_lin_chain_kernel<16, 512, false>);
 }
 
 // the selector between the static walk and the interpreter for the VRNN programs (blvm_pchain_static)
@@ -416,10 +496,8 @@ SPtr sp(const Program& p, const Desc& d, int k) { return SPtr{const_cast<float*>
 Deal deal_of(const Desc& d, int idx) { return Deal{d.wg0, d.nwg, d.ct, d.s_begin, d.s_end, idx}; }
 bool within(const Desc& d, int lo, int hi) { return d.wg0 >= lo && d.wg0 + d.nwg <= hi; }
 bool few_tiles(const Program& p, const Desc& d) {  // at most kMaxTiles tiles of the link per workgroup (pchain_run's count)
-  const int rt = (p.B + 15) / 16;
   if (d.nwg <= 0 || (p.xcd && d.nwg % 8 != 0)) return false;
-  const int per_wg = p.xcd ? (((d.ct + 7) / 8) * rt + d.nwg / 8 - 1) / (d.nwg / 8) : (d.ct * rt + d.nwg - 1) / d.nwg;
-  return per_wg <= kMaxTiles;
+  return tiles_per_workgroup((p.B + 15) / 16, d.ct, d.nwg, p.xcd != 0) <= kMaxTiles;
 }
 bool shaped(const Desc& d, int kind, int flags, int K) { return d.kind == kind && d.flags == flags && d.K == K; }
 bool run(const Desc& d, int n, int K0) { return d.i[LINSEQ_I_N] == n && d.i[LINSEQ_I_K0] == K0; }  // a K_LINSEQ of n links, first link's K0
@@ -459,6 +537,7 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
       !shaped(d[3], K_HEAD, 0, kH) || !shaped(d[4], K_LINSEQ, DF_RELU, kH) || !shaped(d[5], K_GRU, 0, kH))
     return 1;
   if (!run(d[1], 3, kR) || !run(d[2], 3, kR) || !run(d[4], 4, 0)) return 1;
+  if (!one_tile_each(p, kFwdResident)) return 1;
   // roles: prior half [0, d1 end) | posterior half [d2.wg0, d0.wg0) | gentle range [d0.wg0, ...): nothing else there
   const int half = d[2].wg0, gentle = d[0].wg0;
   if (d[1].wg0 != 0 || !within(d[1], 0, half) || !within(d[2], half, gentle) || d[0].nwg <= 0) return 1;
@@ -498,6 +577,7 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream) {
       !shaped(d[9], K_LINSEQ, DF_SEQ_GATE, kH))
     return 1;
   if (!run(d[6], 2, 0) || !run(d[8], 3, 2 * kH) || !run(d[9], 3, 2 * kH)) return 1;
+  if (!one_tile_each(p, kBwdResident) || d[7].p[DZ_D2_16] != nullptr) return 1;  // (dz holds the fragments of its one product)
   // roles: prior half [0, d2.wg0) | posterior half [d2.wg0, d4.wg0) | gentle range (GB) [d4.wg0, d3.wg0) | spare range [d3.wg0, ...)
   const int half = d[2].wg0, gentle = d[4].wg0, spare = d[3].wg0;
   if (!within(d[1], 0, half) || !within(d[8], 0, half) || !within(d[2], half, gentle) || !within(d[9], half, gentle) || !within(d[4], gentle, spare) ||
@@ -515,9 +595,9 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream) {
   a.gb = lin_args(p, d[4]); a.sum = lin_args(p, d[5]);
   a.phi = seq_args(p, d[6]); a.run[0] = seq_args(p, d[8]); a.run[1] = seq_args(p, d[9]);
   const Desc& z = d[7];
-  a.dz = DzArgs{sp(p, z, DZ_D16), sp(p, z, DZ_D2_16), sp(p, z, DZ_ADD), sp(p, z, DZ_MU_Q), sp(p, z, DZ_SD_Q), sp(p, z, DZ_MU_P), sp(p, z, DZ_SD_P),
+  a.dz = DzArgs{sp(p, z, DZ_D16), sp(p, z, DZ_ADD), sp(p, z, DZ_MU_Q), sp(p, z, DZ_SD_Q), sp(p, z, DZ_MU_P), sp(p, z, DZ_SD_P),
                 sp(p, z, DZ_EPS), sp(p, z, DZ_RAW_Q), sp(p, z, DZ_RAW_P), sp(p, z, DZ_MUQ_RAW), sp(p, z, DZ_DQH), sp(p, z, DZ_DQH16), sp(p, z, DZ_DPH),
-                sp(p, z, DZ_DPH16), z.p[DZ_WT], z.p[DZ_WT2], z.p[DZ_C_RAW], z.p[DZ_C_FN], reinterpret_cast<const int32_t*>(z.p[DZ_X_SL]), z.ld[DZ_LD_ADD],
+                sp(p, z, DZ_DPH16), z.p[DZ_WT], z.p[DZ_C_RAW], z.p[DZ_C_FN], reinterpret_cast<const int32_t*>(z.p[DZ_X_SL]), z.ld[DZ_LD_ADD],
                 z.ld[LD_OUT], z.n16[N16_OUT], z.i[DZ_I_Z], z.i[DZ_I_RESIDUAL], z.i[DZ_I_STRIDE], z.i[DZ_I_T0], (int)z.f[DZ_F_GEMM_FROM], z.f[DZ_F_FN_FLOOR],
                 z.f[DZ_F_BETA], z.f[DZ_F_SD_EPS]};
   int grid = 0;
@@ -549,7 +629,8 @@ extern "C" int blvm_pchain_static(int mode) {
 }
 
 // blvm_pchain_chain_probe's chain (one K_LIN descriptor per link, the same Builder program) walked by the static kernel.  N = 256 or 512.
-extern "C" int blvm_pchain_static_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream_) {
+// resident: the weights stay in registers for the launch (at most one tile per workgroup), else they are re-read every link.
+static int static_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream_, bool resident) {
   using namespace blvm;
   using namespace blvm::pchain;
   hipStream_t s = static_cast<hipStream_t>(stream_);
@@ -564,7 +645,13 @@ extern "C" int blvm_pchain_static_chain_probe(const float* W16, const float* bia
   add_desc(bld, K_LIN, N / 16, 0, nw, N, DF_RELU, 0, L, o);
   BLVM_HIP(pchain_fill_sentinel(x16 + x, sizeof(float) * (size_t)x * L, s));
   BLVM_TRY(pchain_prepare(bld, "pchain_static_chain_probe"));
-  const int rc = static_lin_chain_launch(bld.p, s);
+  const int rc = static_lin_chain_launch(bld.p, s, resident);
   BLVM_REQUIRE(rc != 1, "pchain_static_chain_probe: no static kernel for N = %d (256, 512) or this deal", N);
   return rc;
+}
+extern "C" int blvm_pchain_static_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream) {
+  return static_chain_probe(W16, bias, x16, xs, B, N, L, nwg, stream, true);
+}
+extern "C" int blvm_pchain_static_chain_probe_fetch(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream) {
+  return static_chain_probe(W16, bias, x16, xs, B, N, L, nwg, stream, false);
 }

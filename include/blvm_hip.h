@@ -88,7 +88,9 @@ int blvm_pchain_static(int mode);
 int blvm_pchain_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream);
 /* The same chain walked by the static-walk kernel (vrnn_static.hip: kinds, flags and K fixed at compile time, pointers and strides
  * from kernel arguments).  N = 256 or 512. */
+/* (the weights of a workgroup's tile stay in registers for the launch; _fetch: re-read every link, the form it is priced against) */
 int blvm_pchain_static_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream);
+int blvm_pchain_static_chain_probe_fetch(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream);
 /* dst = T16 operand copy [ceil(B/16)*16, K] of the rows of src [B,K] (row stride ld). */
 int blvm_pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, void* stream);
 /* n host integers -> device memory through kernel arguments (asynchronous on `stream`; a pageable hipMemcpy would block the host

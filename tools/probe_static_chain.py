@@ -1,7 +1,11 @@
 """Gate of the static-walk kernel (csrc/vrnn_static.hip): the dependent [B,N]x[N,N] relu chain of probe_engine_chain.py, per link,
 walked by the interpreter (one descriptor visit per link; BLVM_PCHAIN_PROBE_RUN=4: runs of four links per visit) and by the static
-kernel, alternately in one process.  Both outputs must match bit for bit.  The bare tile loop is tools/pchain_probe.hip."""
-import os, sys
+kernel in its two forms — `fetch`: the weight fragments are re-read every link, `resident`: they are loaded once per launch and stay
+in registers — alternately in one process.  All outputs must match bit for bit.  Per shape: `--repeats` rounds (each figure the best
+of three launches), the spread of the fetch form over the rounds and the median gain of the resident form over it.
+
+--bare PATH: also run the bare tile loop (tools/pchain_probe.hip built to PATH) and print its output beside the rows."""
+import argparse, os, statistics, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "benchmarking-lvms_amd"))
 import torch
@@ -31,12 +35,27 @@ def chain(fn, B, N, L, reps=3):
 
 
 if __name__ == "__main__":
-    L = 2000
-    for B, N in ((64, 256), (8, 256), (64, 512)):
-        for rep in range(2):  # alternate, twice
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--links", type=int, default=2000)
+    ap.add_argument("--bare", default=None, help="the built tools/pchain_probe binary")
+    args = ap.parse_args()
+    L = args.links
+    for B, N in ((64, 256), (8, 256), (64, 512), (8, 512)):
+        fetch, res = [], []
+        for rep in range(args.repeats):  # alternate
             te, xe = chain(lib.blvm_pchain_chain_probe, B, N, L)
-            ts, xs = chain(lib.blvm_pchain_static_chain_probe, B, N, L)
-            same = bool(torch.equal(xe, xs))
-            print(f"B={B} N=K={N} L={L}: engine {te:.3f} us/link, static {ts:.3f} us/link, outputs bit-identical: {same}", flush=True)
+            tf, xf = chain(lib.blvm_pchain_static_chain_probe_fetch, B, N, L)
+            tr, xr = chain(lib.blvm_pchain_static_chain_probe, B, N, L)
+            same = bool(torch.equal(xe, xf)) and bool(torch.equal(xf, xr))
+            print(f"B={B} N=K={N} L={L}: engine {te:.3f} us/link, static fetch {tf:.3f}, static resident {tr:.3f}, outputs bit-identical: {same}", flush=True)
             if not same:
                 sys.exit(1)
+            fetch.append(tf); res.append(tr)
+        print(f"B={B} N=K={N}: fetch median {statistics.median(fetch):.3f} spread {max(fetch) - min(fetch):.3f}, resident median "
+              f"{statistics.median(res):.3f} spread {max(res) - min(res):.3f}, gain {statistics.median(fetch) - statistics.median(res):.3f} us/link", flush=True)
+    if args.bare:
+        print(f"bare tile loop ({args.bare} {L} 1):", flush=True)
+        out = subprocess.run([args.bare, str(L), "1"], capture_output=True, text=True, timeout=300)
+        print(out.stdout + out.stderr, flush=True)
+        sys.exit(out.returncode)
