@@ -12,6 +12,8 @@
 #include "pchain.h"
 #include "seqchain.h"
 
+#include <atomic>
+
 namespace blvm {
 namespace {
 
@@ -318,6 +320,12 @@ size_t carve_gru_ws(float* base, int T, int B, int R, GruWs* w) {
   return ar.floats();
 }
 
+// which implementation each sequence entry point took (blvm_rnn_path_counts): host-side counts, one per call
+enum { RNN_LSTM_FWD = 0, RNN_LSTM_BWD = 1, RNN_GRU_FWD = 2, RNN_GRU_BWD = 3 };
+enum { PATH_REGS = 0, PATH_PROGRAM = 1, PATH_PER_STEP = 2 };
+std::atomic<unsigned long long> g_path_counts[12];
+inline void count_path(int op, int path) { g_path_counts[op * 3 + path].fetch_add(1, std::memory_order_relaxed); }
+
 int check_rnn(int T, int B, int I, int H) {
   BLVM_REQUIRE(T > 0 && B > 0 && I > 0 && H > 0, "rnn: bad shape T=%d B=%d I=%d H=%d", T, B, I, H);
   BLVM_REQUIRE(H % 16 == 0, "rnn: hidden size must be a multiple of 16 (got %d)", H);
@@ -331,6 +339,12 @@ int check_rnn(int T, int B, int I, int H) {
 using namespace blvm;
 
 // --------------------------------------------------------------------------------------------------------------------
+extern "C" int blvm_rnn_path_counts(unsigned long long out[12]) {
+  BLVM_REQUIRE(out, "rnn_path_counts: null pointer");
+  for (int k = 0; k < 12; ++k) out[k] = g_path_counts[k].load(std::memory_order_relaxed);
+  return BLVM_OK;
+}
+
 extern "C" size_t blvm_lstm_reserve_floats(int T, int B, int H) { return carve_lstm(nullptr, T, B, H, nullptr); }
 extern "C" size_t blvm_lstm_bwd_workspace_floats(int T, int B, int H) { return carve_lstm_ws(nullptr, T, B, H, nullptr); }
 
@@ -353,6 +367,7 @@ extern "C" int blvm_lstm_seq_fwd(const float* Wih, const float* Whh, const float
   BLVM_TRY(t16_pack_rows(Whh, H, 4 * H, H, rs.WhhP, s));  // operand layout of the chain (once per sequence)
   BLVM_TRY(pack_scope.flush());
   if (seq_persistent(T, B) && (seq_regs_mask() & 1) && seq_regs_applies(H, 4 * H, H, B, 4)) {
+    count_path(RNN_LSTM_FWD, PATH_REGS);
     // one persistent launch with the workgroup's weight slice in registers (seqchain.hip)
     const long xH = (long)((B + 15) / 16) * 16 * H;
     SeqLstmFwd q{rs.H16, rs.WhhP, bhh, rs.XG, lens, rs.Hs, rs.Cs, out, rs.GATES, T, B, H, seq_ot, {}};
@@ -360,6 +375,7 @@ extern "C" int blvm_lstm_seq_fwd(const float* Wih, const float* Whh, const float
     BLVM_TRY(pchain_rows_to_t16(rs.Hs, H, B, H, rs.H16, s));
     BLVM_TRY(seq_lstm_fwd(q, s));
   } else if (seq_persistent(T, B)) {
+    count_path(RNN_LSTM_FWD, PATH_PROGRAM);
     // one persistent launch for the whole sequence (pchain.hip): one link per step — the hidden projection with the gate math
     using namespace pchain;
     const int rt = (B + 15) / 16, ctH = H / 16;
@@ -375,6 +391,7 @@ extern "C" int blvm_lstm_seq_fwd(const float* Wih, const float* Whh, const float
     BLVM_TRY(pchain_rows_to_t16(rs.Hs, H, B, H, rs.H16, s));
     BLVM_TRY(pchain_launch(bld, "lstm_fwd", s));
   } else {
+    count_path(RNN_LSTM_FWD, PATH_PER_STEP);
     const int nw = pick_nw(H, 4);
     const dim3 grid(H / 16, (B + 15) / 16);
     for (int t = 0; t < T; ++t) {
@@ -409,11 +426,13 @@ extern "C" int blvm_lstm_seq_bwd(const float* Wih, const float* Whh, const float
   BLVM_TRY(pack_scope.flush());
   BLVM_HIP(hipMemsetAsync(ws.DC, 0, sizeof(float) * bh, s));
   if (seq_persistent(T, B) && (seq_regs_mask() & 2) && 4 * H <= kSeqRegsMaxKBwd && seq_regs_applies(H, 4 * H, H, B, 4)) {
+    count_path(RNN_LSTM_BWD, PATH_REGS);
     const long x4H = (long)((B + 15) / 16) * 16 * 4 * H;
     SeqLstmBwd q{ws.DG16, ws.WhhT, d_out, rs.GATES, rs.Cs, ws.DC, ws.DG, d_h0 ? d_h0 : ws.DC, T, B, H, d_h0 ? T + 1 : T, seq_ot, {}};
     BLVM_HIP(pchain_fill_sentinel(ws.DG16, sizeof(float) * (size_t)T * x4H, s));
     BLVM_TRY(seq_lstm_bwd(q, s));
   } else if (seq_persistent(T, B)) {
+    count_path(RNN_LSTM_BWD, PATH_PROGRAM);
     using namespace pchain;
     const int rt = (B + 15) / 16, ctH = H / 16;
     const long sH = (long)bh, s4H = 4 * sH, x4H = (long)rt * 16 * 4 * H;
@@ -428,6 +447,7 @@ extern "C" int blvm_lstm_seq_bwd(const float* Wih, const float* Whh, const float
     BLVM_HIP(pchain_fill_sentinel(ws.DG16, sizeof(float) * (size_t)T * x4H, s));
     BLVM_TRY(pchain_launch(bld, "lstm_bwd", s));
   } else {
+    count_path(RNN_LSTM_BWD, PATH_PER_STEP);
     const int nw = pick_nw(4 * H, 1);
     const dim3 grid(H / 16, (B + 15) / 16);
     for (int st = T - 1; st >= -1; --st) {
@@ -477,12 +497,14 @@ extern "C" int blvm_gru_seq_fwd(const float* Wih, const float* Whh, const float*
   BLVM_TRY(t16_pack_rows(Whh, R, 3 * R, R, rs.WhhP, s));  // operand layout of the chain (once per sequence)
   BLVM_TRY(pack_scope.flush());
   if (seq_persistent(T, B) && (seq_regs_mask() & 1) && seq_regs_applies(R, 3 * R, R, B, 3)) {
+    count_path(RNN_GRU_FWD, PATH_REGS);
     const long xR = (long)((B + 15) / 16) * 16 * R;
     SeqGruFwd q{rs.H16, rs.WhhP, bhh, rs.XG, lens, rs.Hs, out, rs.RG, rs.UG, rs.NG, rs.GHN, (long)out_ts, out_ld, T, B, R, reverse ? 1 : 0, seq_ot, {}};
     BLVM_HIP(pchain_fill_sentinel(rs.H16 + xR, sizeof(float) * (size_t)T * xR, s));
     BLVM_TRY(pchain_rows_to_t16(rs.Hs, R, B, R, rs.H16, s));
     BLVM_TRY(seq_gru_fwd(q, s));
   } else if (seq_persistent(T, B)) {
+    count_path(RNN_GRU_FWD, PATH_PROGRAM);
     using namespace pchain;
     BLVM_REQUIRE(out_ts >= 0 && out_ts < (1ll << 31), "gru_fwd: output step stride out of range");
     const int rt = (B + 15) / 16, ctR = R / 16;
@@ -498,6 +520,7 @@ extern "C" int blvm_gru_seq_fwd(const float* Wih, const float* Whh, const float*
     BLVM_TRY(pchain_rows_to_t16(rs.Hs, R, B, R, rs.H16, s));
     BLVM_TRY(pchain_launch(bld, "gru_fwd", s));
   } else {
+    count_path(RNN_GRU_FWD, PATH_PER_STEP);
     const int nw = pick_nw(R, 3);
     const dim3 grid(R / 16, (B + 15) / 16);
     for (int j = 0; j < T; ++j) {
@@ -533,12 +556,14 @@ extern "C" int blvm_gru_seq_bwd(const float* Wih, const float* Whh, const float*
   BLVM_TRY(pack_scope.flush());
   BLVM_HIP(hipMemsetAsync(ws.G, 0, sizeof(float) * br, s));
   if (seq_persistent(T, B) && (seq_regs_mask() & 2) && 3 * R <= kSeqRegsMaxKBwd && seq_regs_applies(R, 3 * R, R, B, 3)) {
+    count_path(RNN_GRU_BWD, PATH_REGS);
     const long x3R = (long)((B + 15) / 16) * 16 * 3 * R;
     SeqGruBwd q{ws.DGH16, ws.WhhT, d_out, rs.RG, rs.UG, rs.NG, rs.GHN, rs.Hs, lens, ws.G, ws.DGI, ws.DGH, d_h0 ? d_h0 : ws.G, (long)out_ts, out_ld, T, B, R,
                 reverse ? 1 : 0, d_h0 ? T + 1 : T, seq_ot, {}};
     BLVM_HIP(pchain_fill_sentinel(ws.DGH16, sizeof(float) * (size_t)T * x3R, s));
     BLVM_TRY(seq_gru_bwd(q, s));
   } else if (seq_persistent(T, B)) {
+    count_path(RNN_GRU_BWD, PATH_PROGRAM);
     using namespace pchain;
     BLVM_REQUIRE(out_ts >= 0 && out_ts < (1ll << 31), "gru_bwd: output step stride out of range");
     const int rt = (B + 15) / 16, ctR = R / 16;
@@ -556,6 +581,7 @@ extern "C" int blvm_gru_seq_bwd(const float* Wih, const float* Whh, const float*
     BLVM_HIP(pchain_fill_sentinel(ws.DGH16, sizeof(float) * (size_t)T * x3R, s));
     BLVM_TRY(pchain_launch(bld, "gru_bwd", s));
   } else {
+    count_path(RNN_GRU_BWD, PATH_PER_STEP);
     const int nw = pick_nw(3 * R, 1);
     const dim3 grid(R / 16, (B + 15) / 16);
     for (int j = T - 1; j >= -1; --j) {

@@ -81,6 +81,11 @@ int blvm_pchain_tune(int bits);
  * mode only queries.  Returns the mode in effect before the call; mode -2 returns instead how many VRNN programs the process has
  * launched on the static kernels so far. */
 int blvm_pchain_static(int mode);
+/* Diagnostics: which implementation the single-layer sequence entry points (K4 / K2) took so far in this process.  Copies twelve
+ * counters, out[op * 3 + path]: op 0 blvm_lstm_seq_fwd, 1 blvm_lstm_seq_bwd, 2 blvm_gru_seq_fwd, 3 blvm_gru_seq_bwd; path 0 the
+ * register-resident persistent kernel, 1 a program of the persistent-chain interpreter, 2 one launch per step.  One count per call
+ * (not per launch), taken on the host where the call branches; never touches the device. */
+int blvm_rnn_path_counts(unsigned long long out[12]);
 /* Diagnostics / unit test of the persistent-chain engine on its own: L dependent links x_{s+1} = relu(x_s W^T + b), [B,N] x [N,N],
  * as ONE launch.  W16: W [N,N] in the T16 operand layout (blvm_pchain_rows_to_t16 of W: a weight's rows are the "batch");
  * x16: L+1 T16 slabs of ceil(B/16)*16 x N floats, slab 0 = x_0 in T16 (blvm_pchain_rows_to_t16); xs: L row-major [B,N] outputs.

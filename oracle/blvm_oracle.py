@@ -352,6 +352,29 @@ def lstm_packed(emb, lens, w_ih, w_hh, b_ih, b_hh, h0=None, c0=None):
     return torch.stack(outs, 1), h, c
 
 
+def lstm_sequence_ref(x, h0, c0, lens, w_ih, w_hh, b_ih, b_hh):
+    """The contract of `blvm_lstm_seq_fwd` as include/blvm_hip.h states it, as a plain time loop in the dtype it is given:
+    x [T,B,I]; h0, c0 [B,H] or None (zeros); lens [B] integer valid steps per row (any order, 0 allowed) or None (all T).
+    With live = t < lens[b]: a dead row keeps h and c (selected, not blended: bit for bit) and its out is 0.
+    Returns (out [T,B,H], h_n, c_n); differentiable by autograd in every float argument."""
+    T, B, _ = x.shape
+    H = w_hh.size(1)
+    h = torch.zeros(B, H, dtype=x.dtype) if h0 is None else h0
+    c = torch.zeros(B, H, dtype=x.dtype) if c0 is None else c0
+    zero = torch.zeros(B, H, dtype=x.dtype)
+    outs = []
+    for t in range(T):
+        h2, c2 = lstm_cell(x[t], h, c, w_ih, w_hh, b_ih, b_hh)
+        if lens is None:
+            h, c = h2, c2
+            outs.append(h2)
+        else:
+            live = (t < lens).unsqueeze(-1)
+            h, c = torch.where(live, h2, h), torch.where(live, c2, c)
+            outs.append(torch.where(live, h2, zero))
+    return torch.stack(outs, 0), h, c
+
+
 def lstm_audio_forward(sd, x, x_sl, stack=64, num_mix=10, num_bins=256, s_0=None):
     """LSTMAudio.forward: predict stack t+1 from stacks <= t; loss = -sum(ll * [tau < x_sl]) / sum(x_sl) with the
     mask on the SHIFTED target axis (lstm.py:88-115).  fp32 sums (bool mask), unlike VRNN/SRNN."""
