@@ -28,6 +28,18 @@ class InputSizeError(Exception):
         super().__init__(message)
 
 
+class WaveNetDecodeState:
+    """What cached generation needs to go on after `n_frames` samples (a prompt's included): every block's ring buffer of its
+    own input over its last `dilation` frames ([d,B,C], frame tau in slot tau mod d) and the last two samples.
+    `scratch`: the decode kernel's buffer the rings are views into (None on the block-by-block path).  A continued call updates
+    the rings in place: a state is good for ONE continuation."""
+
+    __slots__ = ("scratch", "rings", "samples", "n_frames")
+
+    def __init__(self, scratch, rings, samples, n_frames: int):
+        self.scratch, self.rings, self.samples, self.n_frames = scratch, rings, samples, n_frames
+
+
 class WaveNet(BaseModel):
     def __init__(self, likelihood: nn.Module, in_channels: int = 1, embedding_dim: int = None, num_bins: int = 256,
                  n_layers: int = 10, n_stacks: int = 5, res_channels: int = 512, skip_channels: Optional[int] = None,
@@ -139,7 +151,8 @@ class WaveNet(BaseModel):
         return self.forward(x, x_sl, y=y, pad_causal=True, pad_receptive_field=(i_split == 0))
 
     @torch.no_grad()
-    def generate(self, n_samples: int, n_frames: int = 48000, x=None, uniforms=None, cached: bool = False):
+    def generate(self, n_samples: int, n_frames: int = 48000, x=None, uniforms=None, cached: bool = False, state=None,
+                 return_state: bool = False):  # fmt: skip
         """Sample-by-sample generation from a zero start (wavenet.py:254-293): every frame re-runs the causal conv and the
         whole residual stack over a receptive-field window (no cached sampling, as in the reference), takes the single skip
         output, DIVIDES it by variance_scale (the reference's generate divides where forward multiplies, :274 — kept), applies
@@ -147,16 +160,30 @@ class WaveNet(BaseModel):
         `uniforms[t]` optionally supplies the head sampler's two uniform draws of frame t.
         `cached=True` (the reference's TODO, arXiv:1611.09482): the same samples from per-block queues of past activations —
         one new frame per block per step instead of the whole window; with the DMoL head and widths the decode kernel takes
-        (K10c: every frame in one launch) through `ops.wavenet_decode`, otherwise block by block (`_generate_cached`)."""
+        (K10c: every frame in one launch) through `ops.wavenet_decode`, otherwise block by block (`_generate_cached`).
+        With `cached=True`, `x` [B,P,1] is a prompt: the queues are primed from its last receptive-field samples (`_prime`) and
+        frames P, P+1, ... are drawn.  `return_state=True` returns (x_hat, state); `state=` continues from one (generation in
+        chunks; `uniforms` are indexed from 0 for every call)."""
         lik, C, nsf = self.likelihood, self.res_channels, self.n_stack_frames
         if nsf != 1 and (cached or self.in_channels != 1):
             raise NotImplementedError("libblvm_hip: WaveNet.generate on frame stacks is the window path with in_channels=1 (cached=False)")
+        if not cached and (state is not None or return_state):
+            raise NotImplementedError("libblvm_hip: WaveNet.generate keeps a resumable state on the cached path only (cached=True)")
         if cached:
+            if x is not None and state is not None:
+                raise ValueError("WaveNet.generate: a prompt `x` and a `state` are given; a state already contains its past")
             if x is not None:
-                raise NotImplementedError("libblvm_hip: cached generation starts from the all-zero window")
-            if self._decode_kernel_applies():
-                return self._generate_decode_kernel(n_samples, n_frames, uniforms)
-            return self._generate_cached(n_samples, n_frames, uniforms)
+                if x.size(0) != n_samples:
+                    raise ValueError(f"WaveNet.generate: prompt of {x.size(0)} rows for n_samples = {n_samples}")
+                state = self._prime(x)
+            one_launch = self._decode_kernel_applies()
+            if state is None and not return_state:
+                if one_launch:
+                    return self._generate_decode_kernel(n_samples, n_frames, uniforms)
+                return self._generate_cached(n_samples, n_frames, uniforms)
+            run = self._generate_decode_kernel if one_launch else self._generate_cached
+            x_hat, state = run(n_samples, n_frames, uniforms, state=state, want_state=True)
+            return (x_hat, state) if return_state else x_hat
         dev = self.causal.conv.weight.device
         win = torch.zeros(self.receptive_field, n_samples, self.in_channels * nsf, device=dev) if x is None else x.transpose(0, 1).contiguous()
         x_hat = []
@@ -177,7 +204,28 @@ class WaveNet(BaseModel):
                 and C % 16 == 0 and blk.skip_channels % 16 == 0 and C <= 128 and blk.skip_channels <= 128 and len(self.res_stack.res_blocks) <= 64)  # fmt: skip
 
     @torch.no_grad()
-    def _generate_decode_kernel(self, n_samples: int, n_frames: int, uniforms=None):
+    def _prime(self, x):
+        """Prompt x [B,P,1] (P >= 1) -> the decode state after its P samples.  Only the last receptive_field samples matter; a
+        shorter prompt is left-padded with zeros, which is what the zero start means.  The frame the two newest samples give is
+        the first one generation evaluates, so the window that fills the queues ends one sample earlier: the causal conv drops
+        it (`pad_causal=True`), the in_transform and the time-parallel block kernels give every block's input over the window
+        (`ops.wavenet_prime_rings`), and each ring buffer takes the last `dilation` frames of its block's input."""
+        if self.in_channels != 1 or x.ndim != 3 or x.size(2) != 1 or x.size(1) < 1:
+            raise NotImplementedError("libblvm_hip: cached generation takes a prompt [B,P,1] with P >= 1 (in_channels = 1)")
+        rs, rf, C = self.res_stack, self.receptive_field, self.res_channels
+        dev = self.causal.conv.weight.device
+        B, P = x.size(0), x.size(1)
+        win = x[:, -rf:, 0].to(device=dev, dtype=torch.float32)
+        win = torch.nn.functional.pad(win, (rf - win.size(1), 0))  # [B,rf]
+        out = self.causal.forward_tm(win.t().contiguous().unsqueeze(-1), pad_causal=True)  # [rf-2,B,C]: absolute frames P-rf+2 .. P-1
+        L, t_in, blk = out.size(0), rs.in_transform, rs.res_blocks[0]
+        h0 = ops.linear(out.reshape(L * B, C), t_in.weight.view(t_in.out_channels, C), t_in.bias).view(L, B, C)
+        scratch, rings = ops.wavenet_decode_scratch(rs.dilations, B, C, blk.skip_channels, dev)
+        ops.wavenet_prime_rings(h0, [b.kernel_params() for b in rs.res_blocks], rs.dilations, blk.inv_std, blk.skip_channels, P, rings)
+        return WaveNetDecodeState(scratch, rings, win[:, -2:].contiguous(), P)
+
+    @torch.no_grad()
+    def _generate_decode_kernel(self, n_samples: int, n_frames: int, uniforms=None, state=None, want_state: bool = False):
         lik, rs, B = self.likelihood, self.res_stack, n_samples
         dev = self.causal.conv.weight.device
         if uniforms is None:
@@ -187,19 +235,31 @@ class WaveNet(BaseModel):
             u = torch.stack([a.reshape(B, lik.num_mix) for a, _ in uniforms[:n_frames]]).to(dev)
             v = torch.stack([b.reshape(B) for _, b in uniforms[:n_frames]]).to(dev)
         t_in, blk = rs.in_transform, rs.res_blocks[0]
-        x = ops.wavenet_decode((self.causal.conv.weight, self.causal.conv.bias), (t_in.weight.view(t_in.out_channels, -1), t_in.bias),
-                               [b.kernel_params() for b in rs.res_blocks], rs.dilations,
-                               (self.out_transform.linear.weight, self.out_transform.linear.bias), (lik.params.weight, lik.params.bias),
-                               B, n_frames, blk.inv_std, 1.0 / self.variance_scale, lik.num_mix, lik.log_epsilon, u, v)  # fmt: skip
-        return x.unsqueeze(-1)
+        args = ((self.causal.conv.weight, self.causal.conv.bias), (t_in.weight.view(t_in.out_channels, -1), t_in.bias),
+                [b.kernel_params() for b in rs.res_blocks], rs.dilations,
+                (self.out_transform.linear.weight, self.out_transform.linear.bias), (lik.params.weight, lik.params.bias),
+                B, n_frames, blk.inv_std, 1.0 / self.variance_scale, lik.num_mix, lik.log_epsilon, u, v)  # fmt: skip
+        if state is None and not want_state:
+            return ops.wavenet_decode(*args).unsqueeze(-1)
+        if state is None:  # the zero start, keeping its scratch: the samples in front of frame 0 are zeros
+            x, scratch = ops.wavenet_decode_start(*args)
+            samples = torch.cat([torch.zeros(B, 2, device=dev), x], 1)[:, -2:].contiguous()
+            state = WaveNetDecodeState(scratch, ops.wavenet_ring_views(scratch, rs.dilations, B, self.res_channels, blk.skip_channels), samples, n_frames)
+            return x.unsqueeze(-1), state
+        if state.scratch is None or tuple(state.samples.shape) != (B, 2):
+            raise ValueError("WaveNet.generate: the state does not come from the decode kernel's path at this batch size")
+        # the kernel takes the phase of frame `state.n_frames` in every ring: any t0 equal to it modulo all dilations
+        x, samples = ops.wavenet_decode_resume(*args, state.n_frames % math.lcm(*rs.dilations), state.samples, state.scratch)
+        return x.unsqueeze(-1), WaveNetDecodeState(state.scratch, state.rings, samples, state.n_frames + n_frames)
 
     @torch.no_grad()
-    def _generate_cached(self, n_samples: int, n_frames: int, uniforms=None):
+    def _generate_cached(self, n_samples: int, n_frames: int, uniforms=None, state=None, want_state: bool = False):
         """Queue-based generation.  A window of zeros is an all-zero past, under which every layer sits at a constant
         activation (its response to zero input, biases included); the queues start from those steady states — one chain of
         single-frame block evaluations with both taps on the same vector — and each step then feeds the last two samples
         through the causal conv and ONE frame through every block (tap 0 = the block's input `dilation` steps ago, from its
-        ring buffer; tap 1 = its input now), accumulating the skip branches."""
+        ring buffer; tap 1 = its input now), accumulating the skip branches.
+        `state` (a prompt's, `_prime`, or an earlier call's) replaces the steady-state fill; `want_state` returns (x_hat, state)."""
         lik, C, B = self.likelihood, self.res_channels, n_samples
         dev = self.causal.conv.weight.device
         rs, blocks = self.res_stack, self.res_stack.res_blocks
@@ -221,15 +281,23 @@ class WaveNet(BaseModel):
             return inputs
 
         zero_x = torch.zeros(B, self.in_channels, device=dev)
-        # steady state under an all-zero past: block i's delayed input equals its current input
-        h, steady = causal_pair(zero_x, zero_x), []
-        for i, blk in enumerate(blocks):
-            steady.append(h)
-            if i < len(blocks) - 1:
-                h = ops.wavenet_block_step(torch.stack([h, h], 0), blk.kernel_params(), inv_std, S, torch.zeros(1, B, S, device=dev)).view(B, C)
-        queues = [steady[i].unsqueeze(0).repeat(d, 1, 1) for i, d in enumerate(rs.dilations)]  # ring buffers [d_i,B,C]
-        heads = [0] * len(blocks)
-        x_prev, x_now = zero_x, zero_x
+        if state is None:
+            # steady state under an all-zero past: block i's delayed input equals its current input
+            h, steady = causal_pair(zero_x, zero_x), []
+            for i, blk in enumerate(blocks):
+                steady.append(h)
+                if i < len(blocks) - 1:
+                    h = ops.wavenet_block_step(torch.stack([h, h], 0), blk.kernel_params(), inv_std, S, torch.zeros(1, B, S, device=dev)).view(B, C)
+            queues = [steady[i].unsqueeze(0).repeat(d, 1, 1) for i, d in enumerate(rs.dilations)]  # ring buffers [d_i,B,C]
+            heads = [0] * len(blocks)
+            x_prev, x_now = zero_x, zero_x
+            scratch, frames_before = None, 0
+        else:
+            if tuple(state.samples.shape) != (B, 2) or self.in_channels != 1:
+                raise ValueError("WaveNet.generate: the state does not fit this model and batch size")
+            queues, scratch, frames_before = state.rings, state.scratch, state.n_frames
+            heads = [frames_before % d for d in rs.dilations]  # frame tau lives in slot tau mod d
+            x_prev, x_now = state.samples[:, 0:1].contiguous(), state.samples[:, 1:2].contiguous()
         x_hat = []
         for t in range(n_frames):
             skip = torch.zeros(1, B, S, device=dev)
@@ -243,4 +311,7 @@ class WaveNet(BaseModel):
             pred = lik.sample(parameters) if uniforms is None else lik.sample(parameters, uniforms=uniforms[t])  # [B,1,1]
             x_hat.append(pred)
             x_prev, x_now = x_now, pred.view(B, 1).to(torch.float32)
-        return torch.hstack(x_hat)
+        x_hat = torch.hstack(x_hat)
+        if want_state:
+            return x_hat, WaveNetDecodeState(scratch, queues, torch.cat([x_prev, x_now], 1), frames_before + n_frames)
+        return x_hat

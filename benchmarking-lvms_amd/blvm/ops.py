@@ -1075,11 +1075,8 @@ def wavenet_block_step(x2, params, inv_std: float, S: int, skip_acc, want_output
     return o
 
 
-@torch.no_grad()
-def wavenet_decode(causal, in_transform, blocks_params, dilations, out_linear, head_linear, B: int, n_frames: int, inv_std: float,
-                   skip_scale: float, num_mix: int, log_eps: float, u=None, v=None):
-    """K10c: all frames of B utterances in one launch.  causal / in_transform / out_linear / head_linear = (weight, bias);
-    blocks_params as for wavenet_stack; u [n_frames,B,num_mix], v [n_frames,B] uniform draws (None: the mode).  -> x [B,n_frames]."""
+def _wavenet_decode_pack(causal, in_transform, blocks_params, dilations, out_linear, head_linear, num_mix: int):
+    """The packed weight image of K10c and its sizes: -> (lib, C, S, O, device, packed, dilations as a C array)."""
     import ctypes
 
     lib = load()
@@ -1095,16 +1092,116 @@ def wavenet_decode(causal, in_transform, blocks_params, dilations, out_linear, h
     packed = torch.cat([_f32c(p).reshape(-1) for p in parts])
     if packed.numel() != lib.blvm_wavenet_decode_pack_floats(C, S, O, len(blocks_params)):
         raise ValueError("wavenet_decode: parameter shapes do not match the packed layout")
-    dil = (ctypes.c_int * len(dilations))(*dilations)
-    queues = torch.empty(lib.blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S), device=dev, dtype=torch.float32)
-    x = torch.empty(B, n_frames, device=dev, dtype=torch.float32)
+    return lib, C, S, O, dev, packed, (ctypes.c_int * len(dilations))(*dilations)
+
+
+def _wavenet_decode_draws(u, v, n_frames: int, B: int, num_mix: int):
     if u is not None:
         u, v = _f32c(u), _f32c(v)
         if tuple(u.shape) != (n_frames, B, num_mix) or tuple(v.shape) != (n_frames, B):
             raise ValueError("wavenet_decode: u must be [n_frames,B,num_mix] and v [n_frames,B]")
+    return u, v
+
+
+@torch.no_grad()
+def wavenet_decode_start(causal, in_transform, blocks_params, dilations, out_linear, head_linear, B: int, n_frames: int, inv_std: float,
+                         skip_scale: float, num_mix: int, log_eps: float, u=None, v=None):
+    """`wavenet_decode`, which also hands back its scratch buffer: -> (x [B,n_frames], scratch).  With the last two samples the
+    ring buffers in scratch (`wavenet_ring_views`) are the state after n_frames frames (`wavenet_decode_resume`)."""
+    lib, C, S, O, dev, packed, dil = _wavenet_decode_pack(causal, in_transform, blocks_params, dilations, out_linear, head_linear, num_mix)
+    queues = torch.empty(lib.blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S), device=dev, dtype=torch.float32)
+    x = torch.empty(B, n_frames, device=dev, dtype=torch.float32)
+    u, v = _wavenet_decode_draws(u, v, n_frames, B, num_mix)
     check(lib.blvm_wavenet_decode(ptr(packed), dil, len(dilations), B, C, S, O, num_mix, n_frames, inv_std, skip_scale, log_eps,
                                   ptr(u), ptr(v), ptr(queues), ptr(x), stream_ptr()), "blvm_wavenet_decode")  # fmt: skip
-    return x
+    return x, queues
+
+
+@torch.no_grad()
+def wavenet_decode(causal, in_transform, blocks_params, dilations, out_linear, head_linear, B: int, n_frames: int, inv_std: float,
+                   skip_scale: float, num_mix: int, log_eps: float, u=None, v=None):
+    """K10c: all frames of B utterances in one launch.  causal / in_transform / out_linear / head_linear = (weight, bias);
+    blocks_params as for wavenet_stack; u [n_frames,B,num_mix], v [n_frames,B] uniform draws (None: the mode).  -> x [B,n_frames]."""
+    return wavenet_decode_start(causal, in_transform, blocks_params, dilations, out_linear, head_linear, B, n_frames, inv_std, skip_scale,
+                                num_mix, log_eps, u, v)[0]  # fmt: skip
+
+
+def wavenet_ring_views(scratch, dilations, B: int, C: int, S: int):
+    """The ring buffers inside a K10c scratch buffer: block i's input over its last dilation_i frames as a view [dilation_i,B,C]."""
+    off, views = load().blvm_wavenet_decode_ring_offset_floats(len(dilations), C, S), []
+    for d in dilations:
+        views.append(scratch[off : off + d * B * C].view(d, B, C))
+        off += d * B * C
+    return views
+
+
+def wavenet_decode_scratch(dilations, B: int, C: int, S: int, device):
+    """An uninitialised K10c scratch buffer and its ring views."""
+    import ctypes
+
+    dil = (ctypes.c_int * len(dilations))(*dilations)
+    scratch = torch.empty(load().blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S), device=device, dtype=torch.float32)
+    return scratch, wavenet_ring_views(scratch, dilations, B, C, S)
+
+
+@torch.no_grad()
+def wavenet_ring_fill(h, dilation: int, t0: int, ring):
+    """h [L,B,C] (a block's input, last frame = absolute frame t0 - 1) -> its last `dilation` frames into ring [dilation,B,C],
+    frame tau in slot tau mod dilation."""
+    L, B, C = h.shape
+    if h.dtype != torch.float32 or not h.is_contiguous() or not ring.is_contiguous() or tuple(ring.shape) != (dilation, B, C):
+        raise ValueError("wavenet_ring_fill: h must be contiguous fp32 [L,B,C] and ring contiguous [dilation,B,C]")
+    t0 = t0 % dilation + dilation  # only the phase matters
+    check(load().blvm_wavenet_decode_ring_fill(ptr(h), L, B, C, dilation, t0, ptr(ring), stream_ptr()), "blvm_wavenet_decode_ring_fill")
+
+
+@torch.no_grad()
+def wavenet_prime_rings(h0, blocks_params, dilations, inv_std: float, S: int, t0: int, rings):
+    """Fill every block's ring buffer from a window: h0 [L,B,C] = block 0's input whose last frame is absolute frame t0 - 1,
+    L >= sum(dilations).  The time-parallel block kernel (K10) gives block i+1's input from block i's; each ring takes the
+    tail of its block's input.  Two activation buffers (ping-pong), one reserve and one workspace, whatever the block count."""
+    h0 = _f32c(h0)
+    L, B, C = h0.shape
+    if L < sum(dilations):
+        raise ValueError(f"wavenet_prime_rings: {L} frames for dilations that sum to {sum(dilations)}")
+    lib = load()
+    f32 = dict(device=h0.device, dtype=torch.float32)
+    n, d0 = len(dilations), dilations[0]
+    bufs = [torch.empty(max(L - d0, 1) * B * C, **f32) for _ in range(min(n - 1, 2))]
+    if n > 1:
+        reserve = torch.empty(lib.blvm_wavenet_block_reserve_floats(L, B, C, d0), **f32)
+        ws = torch.empty(lib.blvm_wavenet_block_workspace_floats(L, B, C, S, d0), **f32)
+        skip = torch.zeros(1, B, S, **f32)  # the blocks' skip branch of the newest window frame: not used
+    cur = h0
+    for i, d in enumerate(dilations):
+        wavenet_ring_fill(cur, d, t0, rings[i])
+        if i == n - 1:
+            break
+        cw, cb, rw, rb = (_f32c(p) for p in blocks_params[i])
+        o = bufs[i % 2][: (L - d) * B * C].view(L - d, B, C)
+        check(lib.blvm_wavenet_block_fwd(ptr(cur), ptr(cw), ptr(cb), ptr(rw), ptr(rb), L, B, C, S, d, 1, inv_std, ptr(o), ptr(skip),
+                                         ptr(reserve), ptr(ws), stream_ptr()), "blvm_wavenet_block_fwd")  # fmt: skip
+        cur, L = o, L - d
+
+
+@torch.no_grad()
+def wavenet_decode_resume(causal, in_transform, blocks_params, dilations, out_linear, head_linear, B: int, n_frames: int, inv_std: float,
+                          skip_scale: float, num_mix: int, log_eps: float, u, v, t0: int, samples, scratch):
+    """K10c from a state: `scratch` holds the ring buffers after absolute frame t0 - 1 (`wavenet_prime_rings` or an earlier
+    call; updated in place), samples [B,2] the last two samples.  u, v are indexed from 0.  -> (x [B,n_frames], samples [B,2])."""
+    lib, C, S, O, dev, packed, dil = _wavenet_decode_pack(causal, in_transform, blocks_params, dilations, out_linear, head_linear, num_mix)
+    if scratch.dtype != torch.float32 or scratch.numel() != lib.blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S):
+        raise ValueError("wavenet_decode_resume: the scratch buffer does not belong to these shapes")
+    samples = _f32c(samples)
+    if tuple(samples.shape) != (B, 2):
+        raise ValueError("wavenet_decode_resume: samples must be [B,2]")
+    x = torch.empty(B, n_frames, device=dev, dtype=torch.float32)
+    samples_out = torch.empty(B, 2, device=dev, dtype=torch.float32)
+    u, v = _wavenet_decode_draws(u, v, n_frames, B, num_mix)
+    check(lib.blvm_wavenet_decode_resume(ptr(packed), dil, len(dilations), B, C, S, O, num_mix, n_frames, t0, inv_std, skip_scale,
+                                         log_eps, ptr(u), ptr(v), ptr(samples), ptr(scratch), ptr(x), ptr(samples_out), stream_ptr()),
+          "blvm_wavenet_decode_resume")  # fmt: skip
+    return x, samples_out
 
 
 def wavenet_stack(x, blocks_params, dilations, T_skip: int, inv_std: float, S: int, groups=None):

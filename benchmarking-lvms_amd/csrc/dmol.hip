@@ -868,21 +868,24 @@ namespace {
 // arg-max-logit component (`mode`, distributions.py:359-368).  v [n]: the component's own noise — kind 0: uniform in (0,1),
 // x = loc + exp(max(raw, log_eps)) * (log v - log(1-v)), clamped to [-1,1] (:283-305); kind 1: standard normal,
 // x = mu + (softplus_beta(raw) + eps) * v (sd_beta == 0: the scales are already standard deviations).  NULL: x = the location.
+// K = NMIX: the component count of every audio model, unrolled; K = 0: any count (par [n, 3 num_mix], u [n, num_mix]).
+template <int K>
 __global__ __launch_bounds__(256) void mix_sample_kernel(const float* __restrict__ par, const float* __restrict__ u,
-                                                         const float* __restrict__ v, long long n, int kind, float log_eps,
-                                                         float sd_beta, float sd_eps, float* __restrict__ out) {
+                                                         const float* __restrict__ v, long long n, int num_mix, int kind,
+                                                         float log_eps, float sd_beta, float sd_eps, float* __restrict__ out) {
   const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
   if (f >= n) return;
-  const float* p = par + f * F_MAX;
+  const int nm = K > 0 ? K : num_mix;
+  const float* p = par + f * (3 * nm);
   int best = 0;
   float bv = -INFINITY;
 #pragma unroll
-  for (int m = 0; m < NMIX; ++m) {
+  for (int m = 0; m < nm; ++m) {
     float s = p[m];
-    if (u != nullptr) s -= logf(-logf(u[f * NMIX + m]));
+    if (u != nullptr) s -= logf(-logf(u[f * nm + m]));
     if (s > bv) { bv = s; best = m; }  // first maximum, as torch.argmax
   }
-  const float loc = p[NMIX + best], raw = p[2 * NMIX + best];
+  const float loc = p[nm + best], raw = p[2 * nm + best];
   float x = loc;
   if (v != nullptr) {
     const float vv = v[f];
@@ -902,12 +905,12 @@ __global__ __launch_bounds__(256) void mix_sample_kernel(const float* __restrict
 extern "C" int blvm_mix_sample(const float* par, const float* u, const float* v, long long n, int num_mix, int kind,
                                float log_eps, float sd_beta, float sd_eps, float* out, void* stream) {
   using namespace blvm;
-  BLVM_REQUIRE(par && out && n >= 0 && num_mix == NMIX && (kind == 0 || kind == 1), "mix_sample: bad arguments");
+  BLVM_REQUIRE(par && out && n >= 0 && num_mix >= 1 && num_mix <= 1024 && (kind == 0 || kind == 1), "mix_sample: bad arguments");
   if (n == 0) return BLVM_OK;
   const long long blocks = (n + 255) / 256;
   BLVM_REQUIRE(blocks < (1ll << 31), "mix_sample: too many frames");
-  hipLaunchKernelGGL(mix_sample_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), par, u, v, n, kind,
-                     log_eps, sd_beta, sd_eps, out);
+  hipLaunchKernelGGL(num_mix == NMIX ? mix_sample_kernel<NMIX> : mix_sample_kernel<0>, dim3((unsigned)blocks), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), par, u, v, n, num_mix, kind, log_eps, sd_beta, sd_eps, out);
   BLVM_CHECK_LAUNCH("mix_sample");
   return BLVM_OK;
 }

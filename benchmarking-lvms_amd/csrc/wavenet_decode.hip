@@ -14,6 +14,8 @@
 // A window of zeros is an all-zero past; under it every block input is constant in time (the network's response to zero
 // input, biases included).  The prologue evaluates that steady state once — each block with both taps on the same vector —
 // and fills the ring buffers with it, which makes frame 0 identical to the reference's first window evaluation.
+#include <climits>
+
 #include "common.h"
 
 namespace blvm {
@@ -59,6 +61,10 @@ struct DecodeArgs {
   const float* v;  // [n_frames,B] or NULL
   float* queues;   // block i: [dil_i,B,C] at B*C*sum(dil[:i])
   float* x_out;    // [B,n_frames]
+  // entry from a given state (RESUME): the rings hold every block's input over absolute frames t0 - dil_i .. t0 - 1
+  int t0;             // absolute index of this call's frame 0; frame tau lives in slot tau mod dil_i
+  const float* x_in;  // [B,2] (previous, newest) sample in front of frame t0
+  float* x_state;     // [B,2] the same pair after the last frame
 };
 
 // LDS-only barrier: waits for this wave's LDS traffic, not for its global loads.  No thread of the decoder ever reads
@@ -86,7 +92,10 @@ __device__ __forceinline__ f32x4 tile_from_regs(const float* __restrict__ A, int
 
 // CC, SS > 0: widths known at compile time — the main loop keeps each wave's weight tiles, biases and ring-buffer taps of
 // the NEXT block in registers, loaded while the current block computes.  CC == 0: any width, loads where they are used.
-template <int NW, int CC, int SS>
+// RESUME: no steady-state prologue — rings and the last two samples are the caller's, frame t is absolute frame t0 + t, and
+// the sample pair is handed back; with the rings left in scratch that is the whole state.  A separate instantiation, so the
+// zero-start entry keeps its code.
+template <int NW, int CC, int SS, bool RESUME>
 __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
   extern __shared__ __align__(16) float smem[];
   constexpr int NT = NW * 64;
@@ -107,7 +116,8 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
   const float* w = a.w;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
-  for (int i = tid; i < DEC_ROWS * 2; i += NT) sX[i] = 0.f;
+  const int t0 = RESUME ? a.t0 : 0;
+  for (int i = tid; i < DEC_ROWS * 2; i += NT) sX[i] = (RESUME && b0 + i / 2 < B) ? a.x_in[(size_t)2 * b0 + i] : 0.f;
   __syncthreads();
 
   // causal conv on (previous, newest) sample -> 1x1 in_transform -> sH; clears the skip accumulators
@@ -185,8 +195,8 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
   };
 
   // steady state under an all-zero past
-  front();
-  {
+  if constexpr (!RESUME) {
+    front();
     float* qi = a.queues;
     for (int i = 0; i < a.n_blocks; ++i) {
       block(i, qi, 0, true);
@@ -306,7 +316,7 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
     lds_barrier();
     DEC_TICK(1)
   };
-  if constexpr (CC > 0) load_block(R0, 0, a.queues, 0);
+  if constexpr (CC > 0) load_block(R0, 0, a.queues, t0 % a.dil[0]);
 
   for (int t = 0; t < a.n_frames; ++t) {
     front();
@@ -320,13 +330,13 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
         float* q2 = q1 + (size_t)d1 * B * C;
         const bool last = i + 2 == a.n_blocks;
         const int ni = last ? 0 : i + 2;
-        block_fast(R0, R1, qi, t % d0, i + 1, q1, t % d1);
-        block_fast(R1, R0, q1, t % d1, ni, last ? a.queues : q2, (last ? t + 1 : t) % a.dil[ni]);
+        block_fast(R0, R1, qi, (t0 + t) % d0, i + 1, q1, (t0 + t) % d1);
+        block_fast(R1, R0, q1, (t0 + t) % d1, ni, last ? a.queues : q2, (last ? t0 + t + 1 : t0 + t) % a.dil[ni]);
         qi = q2;
       }
     } else {
       for (int i = 0; i < a.n_blocks; ++i) {
-        block(i, qi, t % a.dil[i], false);
+        block(i, qi, (t0 + t) % a.dil[i], false);
         qi += (size_t)a.dil[i] * B * C;
       }
     }
@@ -377,10 +387,26 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
     }
     __syncthreads();
   }
+  if constexpr (RESUME)
+    for (int i = tid; i < DEC_ROWS * 2; i += NT)
+      if (b0 + i / 2 < B) a.x_state[(size_t)2 * b0 + i] = sX[i];
 #ifdef DEC_PROF
   if (blockIdx.x == 0 && (tid == 0 || tid == NT - 1))
     for (int k = 0; k < 6; ++k) a.x_out[(size_t)B * a.n_frames + (tid ? 6 : 0) + k] = (float)(prof[k] / 1000);
 #endif
+}
+
+// Ring fill for the entry from a state: src = the last d frames [d, B*C/4] (float4) of a block's time-major input, whose frame
+// j is absolute frame t0 - d + j; it goes to slot (t0 - d + j) mod d = (first + j) mod d.  One float4 per thread, both sides
+// contiguous in B*C.
+__global__ __launch_bounds__(256) void wn_ring_fill_kernel(const float4* __restrict__ src, float4* __restrict__ ring, unsigned row4,
+                                                           unsigned d, unsigned first, unsigned n4) {
+  const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+  if (idx >= n4) return;
+  const unsigned j = idx / row4, e = idx - j * row4;
+  unsigned slot = first + j;
+  if (slot >= d) slot -= d;
+  ring[(size_t)slot * row4 + e] = src[idx];
 }
 
 inline size_t decode_lds_bytes(int C, int S, int O) {
@@ -407,18 +433,31 @@ extern "C" size_t blvm_wavenet_decode_scratch_floats(const int* dilations, int n
   return decode_ring_floats(dilations, n_blocks, B, C) + (size_t)n_blocks * ((size_t)2 * C * 2 * C + (size_t)(C + S) * C);
 }
 
-extern "C" int blvm_wavenet_decode(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O,
-                                   int num_mix, int n_frames, float inv_std, float skip_scale, float log_eps,
-                                   const float* u, const float* v, float* scratch, float* x_out, void* stream) {
+extern "C" size_t blvm_wavenet_decode_ring_offset_floats(int n_blocks, int C, int S) {
+  if (n_blocks <= 0 || C <= 0 || S <= 0) return 0;
+  return (size_t)n_blocks * ((size_t)2 * C * 2 * C + (size_t)(C + S) * C);
+}
+
+// resume: the kernel starts from the rings in `scratch` and x_in at absolute frame t0 and hands the sample pair back
+static int decode_run(bool resume, const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int num_mix,
+                      int n_frames, int t0, float inv_std, float skip_scale, float log_eps, const float* u, const float* v,
+                      const float* x_in, float* scratch, float* x_out, float* x_state, void* stream) {
   using namespace blvm;
   BLVM_REQUIRE(packed && dilations && scratch && x_out && aligned16(packed) && aligned16(scratch), "wavenet_decode: NULL or misaligned argument");
   BLVM_REQUIRE(B > 0 && n_frames >= 0 && n_blocks > 0 && n_blocks <= DEC_MAX_BLOCKS, "wavenet_decode: need B > 0, 1 <= n_blocks <= %d", DEC_MAX_BLOCKS);
   BLVM_REQUIRE(C > 0 && S > 0 && O > 0 && C % 16 == 0 && S % 16 == 0 && O % 16 == 0, "wavenet_decode: C, S, O must be multiples of 16");
   BLVM_REQUIRE(num_mix > 0 && 3 * num_mix <= DEC_HEAD_ROWS, "wavenet_decode: num_mix must be in [1, %d]", DEC_HEAD_ROWS / 3);
   BLVM_REQUIRE((u == nullptr) == (v == nullptr), "wavenet_decode: u and v are given together (both NULL: the mode)");
+  if (resume) {
+    BLVM_REQUIRE(x_in && x_state, "wavenet_decode_resume: NULL sample state");
+    BLVM_REQUIRE(t0 >= 0 && n_frames < INT_MAX - t0, "wavenet_decode_resume: t0 = %d, n_frames = %d: need 0 <= t0, t0 + n_frames < 2^31 - 1", t0, n_frames);
+  }
   const size_t lds = decode_lds_bytes(C, S, O);
   BLVM_REQUIRE(lds <= 160 * 1024, "wavenet_decode: C=%d, S=%d, O=%d need %zu bytes of LDS (> 160 KB)", C, S, O, lds);
-  if (n_frames == 0) return BLVM_OK;
+  if (n_frames == 0) {
+    if (resume && x_state != x_in) BLVM_HIP(hipMemcpyAsync(x_state, x_in, sizeof(float) * 2 * B, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return BLVM_OK;
+  }
   DecodeArgs a;
   a.w = packed;
   for (int i = 0; i < n_blocks; ++i) {
@@ -429,6 +468,7 @@ extern "C" int blvm_wavenet_decode(const float* packed, const int* dilations, in
   a.n_blocks = n_blocks; a.B = B; a.C = C; a.S = S; a.O = O; a.n_frames = n_frames; a.num_mix = num_mix;
   a.inv_std = inv_std; a.skip_scale = skip_scale; a.log_eps = log_eps;
   a.u = u; a.v = v; a.x_out = x_out;
+  a.t0 = t0; a.x_in = x_in; a.x_state = x_state;
   // scratch = [T16 operand copies of the blocks' matrices | ring buffers]
   const DecodeLayout L = decode_layout(C, S, O, n_blocks);
   const size_t wt_stride = (size_t)2 * C * 2 * C + (size_t)(C + S) * C;
@@ -441,11 +481,41 @@ extern "C" int blvm_wavenet_decode(const float* packed, const int* dilations, in
   a.wt = scratch;
   a.queues = scratch + (size_t)n_blocks * wt_stride;
   constexpr int NW = 8;
-  auto kern = wn_decode_kernel<NW, 0, 0>;
-  if (n_blocks % 2 == 0 && C == 64 && S == 64) kern = wn_decode_kernel<NW, 64, 64>;
-  else if (n_blocks % 2 == 0 && C == 32 && S == 32) kern = wn_decode_kernel<NW, 32, 32>;
+  const bool even = n_blocks % 2 == 0;
+  auto kern = resume ? wn_decode_kernel<NW, 0, 0, true> : wn_decode_kernel<NW, 0, 0, false>;
+  if (even && C == 64 && S == 64) kern = resume ? wn_decode_kernel<NW, 64, 64, true> : wn_decode_kernel<NW, 64, 64, false>;
+  else if (even && C == 32 && S == 32) kern = resume ? wn_decode_kernel<NW, 32, 32, true> : wn_decode_kernel<NW, 32, 32, false>;
   if (lds > 64 * 1024) BLVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)((B + DEC_ROWS - 1) / DEC_ROWS)), dim3(NW * 64), lds, static_cast<hipStream_t>(stream), a);
   BLVM_CHECK_LAUNCH("wavenet_decode");
+  return BLVM_OK;
+}
+
+extern "C" int blvm_wavenet_decode(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O,
+                                   int num_mix, int n_frames, float inv_std, float skip_scale, float log_eps,
+                                   const float* u, const float* v, float* scratch, float* x_out, void* stream) {
+  return decode_run(false, packed, dilations, n_blocks, B, C, S, O, num_mix, n_frames, 0, inv_std, skip_scale, log_eps, u, v, nullptr,
+                    scratch, x_out, nullptr, stream);
+}
+
+extern "C" int blvm_wavenet_decode_resume(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O,
+                                          int num_mix, int n_frames, int t0, float inv_std, float skip_scale, float log_eps,
+                                          const float* u, const float* v, const float* x_in, float* scratch, float* x_out,
+                                          float* x_state, void* stream) {
+  return decode_run(true, packed, dilations, n_blocks, B, C, S, O, num_mix, n_frames, t0, inv_std, skip_scale, log_eps, u, v, x_in,
+                    scratch, x_out, x_state, stream);
+}
+
+extern "C" int blvm_wavenet_decode_ring_fill(const float* h, int L, int B, int C, int dilation, int t0, float* ring, void* stream) {
+  using namespace blvm;
+  BLVM_REQUIRE(h && ring && aligned16(h) && aligned16(ring), "wavenet_decode_ring_fill: NULL or misaligned argument");
+  BLVM_REQUIRE(B > 0 && C > 0 && C % 4 == 0 && dilation >= 1 && L >= dilation && t0 >= dilation,
+               "wavenet_decode_ring_fill: need B > 0, C a multiple of 4, 1 <= dilation <= min(L, t0) (L %d, dilation %d, t0 %d)", L, dilation, t0);
+  const size_t n4 = (size_t)dilation * B * (C / 4);
+  BLVM_REQUIRE(n4 < (1ull << 31), "wavenet_decode_ring_fill: ring too large");
+  hipLaunchKernelGGL(wn_ring_fill_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const float4*>(h + (size_t)(L - dilation) * B * C), reinterpret_cast<float4*>(ring),
+                     (unsigned)(B * (C / 4)), (unsigned)dilation, (unsigned)((t0 - dilation) % dilation), (unsigned)n4);
+  BLVM_CHECK_LAUNCH("wavenet_decode_ring_fill");
   return BLVM_OK;
 }

@@ -471,6 +471,25 @@ int blvm_wavenet_decode(const float* packed, const int* dilations, int n_blocks,
                         int n_frames, float inv_std, float skip_scale, float log_eps, const float* u, const float* v,
                         float* scratch, float* x_out, void* stream);
 
+/* K10c  The same sampling from a given state: continuing a prompt, or an earlier call (generation in chunks).
+ *   The state after absolute frame t0 - 1 is (a) the ring buffers in scratch: block i's input over frames t0 - dilation_i ..
+ *   t0 - 1 as [dilation_i,B,C], frame tau in slot tau mod dilation_i, block after block from float offset
+ *   blvm_wavenet_decode_ring_offset_floats(n_blocks,C,S) = n_blocks ((2C)^2 + (C+S) C) of scratch, and (b) the last two
+ *   samples x_in [B,2] = (previous, newest).  Frame tau of block 0's input is in_transform(causal conv of samples tau-2, tau-1).
+ *   blvm_wavenet_decode_ring_fill: h [L,B,C] time-major, a block's input whose LAST frame is absolute frame t0 - 1
+ *     (L >= dilation, t0 >= dilation; C a multiple of 4) -> its last `dilation` frames into ring [dilation,B,C]; every slot written.
+ *   blvm_wavenet_decode_resume: arguments as blvm_wavenet_decode; no steady-state fill, frame t of the call is absolute frame
+ *     t0 + t (t0 >= 0; only t0 mod dilation_i matters), u / v are indexed from 0 for the call.  The weight copies at the
+ *     head of scratch are rewritten on every call (the weights may change between calls, the shapes may not); the ring region
+ *     is read and updated in place.  x_state [B,2] (=): the sample pair after the last frame (may be x_in itself); with
+ *     scratch it is the state after t0 + n_frames frames.  After blvm_wavenet_decode (t0 = 0) the rings in its scratch are
+ *     that state too, with x_in = the last two columns of x_out (zeros in front of frame 0). */
+size_t blvm_wavenet_decode_ring_offset_floats(int n_blocks, int C, int S);
+int blvm_wavenet_decode_ring_fill(const float* h, int L, int B, int C, int dilation, int t0, float* ring, void* stream);
+int blvm_wavenet_decode_resume(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int num_mix,
+                               int n_frames, int t0, float inv_std, float skip_scale, float log_eps, const float* u,
+                               const float* v, const float* x_in, float* scratch, float* x_out, float* x_state, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * K5  RSSM cell of the Clockwork-VAE over a sequence (forward + BPTT).  Replaces the per-level time loop
  *     `blvm/models/clockwork_vae/clockwork_vae.py:272-281` over `RSSMCell.forward` (`blvm/modules/rssm.py:79-104`).
