@@ -59,6 +59,16 @@ class SrnnDecodeWeights(ctypes.Structure):
     ]  # fmt: skip
 
 
+class LstmDecodeWeights(ctypes.Structure):
+    """struct BlvmLstmDecodeWeights (wih, whh, bih, bhh: host arrays of num_layers device pointers)."""
+
+    _fields_ = [
+        ("emb_w", c_void_p * 3), ("emb_b", c_void_p * 3), ("wih", ctypes.POINTER(c_void_p)), ("whh", ctypes.POINTER(c_void_p)),
+        ("bih", ctypes.POINTER(c_void_p)), ("bhh", ctypes.POINTER(c_void_p)), ("dec_w", c_void_p * 3), ("dec_b", c_void_p * 3),
+        ("lik_w", c_void_p), ("lik_b", c_void_p),
+    ]  # fmt: skip
+
+
 class RssmWeights(ctypes.Structure):
     """struct BlvmRssmWeights / BlvmRssmGrads."""
 
@@ -112,6 +122,8 @@ _SIGNATURES = {
     "blvm_vrnn_decode": (c_int, [ctypes.POINTER(VrnnDecodeWeights)] + [c_void_p] * 5 + [c_int] * 7 + [c_float] * 3 + [c_void_p] * 4),
     "blvm_srnn_generate_scratch_floats": (c_size_t, [c_int] * 6),
     "blvm_srnn_generate": (c_int, [ctypes.POINTER(SrnnDecodeWeights)] + [c_void_p] * 6 + [c_int] * 7 + [c_float] * 3 + [c_void_p] * 5),
+    "blvm_lstm_generate_scratch_floats": (c_size_t, [c_int] * 5),
+    "blvm_lstm_generate": (c_int, [ctypes.POINTER(LstmDecodeWeights)] + [c_void_p] * 5 + [c_int] * 6 + [c_float] + [c_void_p] * 5),
     "blvm_vrnn_generate_scratch_floats": (c_size_t, [c_int] * 6),
     "blvm_vrnn_generate": (c_int, [ctypes.POINTER(VrnnDecodeWeights)] + [c_void_p] * 5 + [c_int] * 7 + [c_float] * 3 + [c_void_p] * 4),
     "blvm_vrnn_reserve_floats": (c_size_t, [c_int] * 6),

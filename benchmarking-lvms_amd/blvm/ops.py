@@ -751,6 +751,48 @@ def lstm_sequence(inp, h0, c0, lens_dev, Wih, Whh, bih, bhh):
     return _LSTMSeqFunction.apply(inp, h0, c0, lens_dev, Wih, Whh, bih, bhh)
 
 
+def lstm_decode_weights(emb_lin, lstm, dec_lin, lik_lin):
+    """-> (struct BlvmLstmDecodeWeights, what must stay alive while it is used)."""
+    import ctypes
+
+    L = lstm.num_layers
+    keep = [_f32c(t) for lin in (*emb_lin, *dec_lin, lik_lin) for t in (lin.weight, lin.bias)]
+    lk = [[_f32c(getattr(lstm, f"{n}_l{l}")) for l in range(L)] for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    arrays = [(ctypes.c_void_p * L)(*[t.data_ptr() for t in ts]) for ts in lk]  # host arrays of device pointers
+    w = _hip.LstmDecodeWeights()
+    for i in range(3):
+        w.emb_w[i], w.emb_b[i] = ptr(keep[2 * i]), ptr(keep[2 * i + 1])
+        w.dec_w[i], w.dec_b[i] = ptr(keep[6 + 2 * i]), ptr(keep[6 + 2 * i + 1])
+    w.lik_w, w.lik_b = ptr(keep[12]), ptr(keep[13])
+    w.wih, w.whh, w.bih, w.bhh = (ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p)) for a in arrays)
+    return w, (keep, lk, arrays)
+
+
+def lstm_generate(emb_lin, lstm, dec_lin, lik_lin, x0, h0, c0, u, v, S, H, num_mix, log_eps, T=None):
+    """K4c: T = u.shape[0] steps of sampling from LSTMAudio for all B <= 128 utterances in one persistent launch.  emb_lin / dec_lin:
+    3 nn.Linear each; lstm: the nn.LSTM (parameter container, input size H); lik_lin the DMoL head's Linear.  x0 [B,S]; h0, c0
+    [num_layers,B,H] or None (zeros); u [T,B,S,num_mix], v [T,B,S] the sampler's draws (both None: the mode, `T` then says how many
+    steps).  -> (x [B,T,S], h_n, c_n [num_layers,B,H])."""
+    import ctypes
+
+    lib = load()
+    L, B, dev = lstm.num_layers, x0.shape[0], x0.device
+    if (u is None) != (v is None) or (u is None and T is None):
+        raise ValueError("lstm_generate: u and v are given together; the mode (neither) needs T")
+    T = int(T) if u is None else u.shape[0]
+    w, _keep = lstm_decode_weights(emb_lin, lstm, dec_lin, lik_lin)
+    x0 = _f32c(x0)
+    h0 = _f32c(h0) if h0 is not None else None
+    c0 = _f32c(c0) if c0 is not None else None
+    u, v = (None, None) if u is None else (_f32c(u), _f32c(v))
+    f32 = dict(device=dev, dtype=torch.float32)
+    scratch = torch.empty(lib.blvm_lstm_generate_scratch_floats(T, B, S, H, L), **f32)
+    x, hn, cn = torch.empty(B, T, S, **f32), torch.empty(L, B, H, **f32), torch.empty(L, B, H, **f32)
+    check(lib.blvm_lstm_generate(ctypes.byref(w), ptr(x0), ptr(h0), ptr(c0), ptr(u), ptr(v), T, B, S, H, L, num_mix, log_eps, ptr(x), ptr(hn),
+                                 ptr(cn), ptr(scratch), stream_ptr()), "blvm_lstm_generate")  # fmt: skip
+    return x, hn, cn
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # K2: GRU over a sequence, optionally reversed per row (reverse_sequences folded into the kernel's index map)
 # ----------------------------------------------------------------------------------------------------------------------

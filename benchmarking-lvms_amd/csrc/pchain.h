@@ -1043,6 +1043,51 @@ __device__ __forceinline__ void tile_lstm_seq_bwd(const LstmSeqBwdIn& a, const O
   a.DC[o] = dct * fg;
 }
 
+// LSTM cell update of a [16 x 16] block of one layer's state inside a roll-out (lstm_decode.hip), where the input of the step is
+// produced inside the launch: gates = X Wih^T (4 products, X [B,K] a polled T16 slab: the embedding or the layer below) + b_ih + gh,
+// gh = h_prev Whh^T + b_hh [B,4H] produced by a K_LIN link of this launch (polled words, requested under the operand wait as in
+// tile_gru); rows [i|f|g|o]; c' = f c + i g, h' = o tanh(c').  c is read by the thread that wrote it one step earlier (plain: a
+// descriptor's tile list is fixed for the launch, so a tile has the same workgroup and thread in every step) or by the host before
+// the launch; h' goes through `hnew` (row-major: read after the launch; T16: the next link's operand; second T16: the operand of the
+// next step's hidden projection), c' into its per-step [B,H] slab.
+template <int NW, int OT = OP_F32>
+__device__ __forceinline__ void tile_lstm(const float* X, const float* Wih, int K, const float* bih, const float* gh, const float* cprev, float* cnext, int H,
+                                          const Out& hnew, int r0, int c0, int B, float* red, Poll& pl) {
+  const int t = threadIdx.x & 255;
+  const int row = r0 + (t >> 4), col = c0 + (t & 15);
+  const bool own = threadIdx.x < 256 && row < B;
+  const int rowc = row < B ? row : r0;
+  const size_t o = (size_t)rowc * H + col, o4 = (size_t)rowc * 4 * H + col;
+  const rsrc_t rgh = make_rsrc(gh);
+  const rsrc_t ps[4] = {rgh, rgh, rgh, rgh};
+  const unsigned po[4] = {4u * (unsigned)o4, 4u * (unsigned)(o4 + H), 4u * (unsigned)(o4 + 2 * H), 4u * (unsigned)(o4 + 3 * H)};
+  float w[4] = {0.f, 0.f, 0.f, 0.f}, b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f, cp = 0.f;
+  auto prefetch = [&]() {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = ld_sc1(ps[i], po[i]);
+    b0 = bih[col]; b1 = bih[H + col]; b2 = bih[2 * H + col]; b3 = bih[3 * H + col];
+    cp = cprev[o];
+  };
+  f32x4 acc[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  {
+    const float* const As[1] = {X};
+    const float* const Ws[4] = {Wih, Wih, Wih, Wih};
+    const int la[1] = {0}, cs[4] = {c0, H + c0, 2 * H + c0, 3 * H + c0};
+    mgemm16<NW, OT, 1, 4, MapSame>(As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch);
+  }
+  float v[4];
+  reduce_tiles<4, NW>(acc, red, v);
+  if (threadIdx.x >= 256) return;
+  if (__any(own && (is_sentinel(w[0]) | is_sentinel(w[1]) | is_sentinel(w[2]) | is_sentinel(w[3])))) poll_words<4>(ps, po, w, own, pl);
+  if (!own) return;
+  const float i = sigmoidf_(v[0] + b0 + w[0]), f = sigmoidf_(v[1] + b1 + w[1]), g = tanhf(v[2] + b2 + w[2]), og = sigmoidf_(v[3] + b3 + w[3]);
+  const float c2 = f * cp + i * g;
+  cnext[(size_t)row * H + col] = c2;
+  put(hnew, r0, c0, row, col, og * tanhf(c2));
+}
+
 // Sampling from a DMoL head during generation (`VRNN.generate`, blvm/models/vrnn.py:371-434: likelihood(dec) -> sample): a tile =
 // 16 utterances x 4 samples of one frame stack.  dec [B, S*F] (F = 3 * num_mix = 30 head inputs per sample, row-major, polled words:
 // the last decoder layer of this step) -> per sample the head's Linear(F -> F) -> Gumbel-max component pick with u, clamped
@@ -1133,7 +1178,7 @@ __device__ __forceinline__ void tile_dmol_sample(const float* dec, int ldd, cons
 // are its own (TileIter over [wg0, wg0 + nwg)).  A pointer of a descriptor is `p[k] + s * stride[sidx[k]]` (stride table of the
 // program, entry 0 = 0: constants and null pointers); a backward sequence passes its last step's slabs and negative strides.
 // =================================================================================================================================
-enum Kind : int { K_LIN = 0, K_HEAD = 1, K_GRU = 2, K_DZ = 3, K_GRUB = 4, K_DMOLS = 5, K_GRUS = 6, K_GRUSB = 7, K_LSTMS = 8, K_LSTMSB = 9, K_LINSEQ = 10 };
+enum Kind : int { K_LIN = 0, K_HEAD = 1, K_GRU = 2, K_DZ = 3, K_GRUB = 4, K_DMOLS = 5, K_GRUS = 6, K_GRUSB = 7, K_LSTMS = 8, K_LSTMSB = 9, K_LINSEQ = 10, K_LSTM = 11 };
 enum DescFlag : int {
   DF_RELU = 1,         // K_LIN: leaky ReLU (f[LIN_F_SLOPE]) on the result
   DF_A_PLAIN = 2,      // K_LIN: A is a row-major buffer written before the launch (ld[LIN_LD_A]), not a polled T16 copy
@@ -1191,6 +1236,8 @@ enum : int { LSTMS_H16, LSTMS_WHH, LSTMS_BHH, LSTMS_XG, LSTMS_LENS, LSTMS_HPREV,
 // K_LSTMSB (tile_lstm_seq_bwd; t = T-1-s, T = n16[LSTMSB_N16_T]): DG16 of step t+1, WhhT (T16), dout, gates, c_s (c_{s+1} = one [B,H] slab
 // further), DC (in place), DG row-major | T16 (ld[LD_OUT] = 4H), dh0
 enum : int { LSTMSB_DG16_IN, LSTMSB_WHHT, LSTMSB_DOUT, LSTMSB_GATES, LSTMSB_CS, LSTMSB_DC, LSTMSB_DG, LSTMSB_DG16, LSTMSB_DH0, LSTMSB_N16_T = 1, LSTMSB_I_H = 0 };
+// K_LSTM (tile_lstm): X16 (polled), Wih (T16), b_ih, gh (polled words), c_prev, c_next, h_new row-major | T16 | second T16
+enum : int { LSTM_X16, LSTM_WIH, LSTM_BIH, LSTM_GH, LSTM_CPREV, LSTM_CNEXT, LSTM_HRM, LSTM_H16, LSTM_H16B, LSTM_I_H = 0 };
 constexpr int kMaxDesc = 24, kMaxPtr = 20;
 struct Desc {
   int kind, ct, wg0, nwg, flags, K, s_begin, s_end;

@@ -119,7 +119,10 @@ struct DescRegs {
   __device__ __forceinline__ int wdyn(int idx) const { return __builtin_amdgcn_readlane(v0, idx); }  // idx < 64
 };
 
-template <int NW, int OT>
+// ROLL: the instantiation that runs the LSTM roll-out (lstm_decode.hip) — the tile kinds of that program only (K_LIN, K_LINSEQ, K_LSTM,
+// K_DMOLS).  The cell arm inside the shared instantiation cost the fp32 one 4 bytes of scratch per lane, and that kernel
+// is the training kernel: it has every kind but K_LSTM and is the same code with or without the roll-out.
+template <int NW, int OT, bool ROLL = false>
 __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restrict__ tab, Hdr a) {
   extern __shared__ __attribute__((aligned(16))) char lds_all[];  // [descriptors | profile | 2 x (lds_products x NW x 256) floats]
   int* const ltab = reinterpret_cast<int*>(lds_all);
@@ -247,7 +250,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             }
             if (nt == 0) nx.fetch(ltab, nx_i, nx_s);  // (a visit without tiles)
           } break;
-          case K_HEAD: {
+          case K_HEAD: if constexpr (!ROLL) {
             const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
             const HeadOut o{d.m<HEAD_MU_P>(s), d.m<HEAD_SD_P>(s), d.m<HEAD_MU_Q>(s), d.m<HEAD_SD_Q>(s), d.m<HEAD_RAW_P>(s), d.m<HEAD_RAW_Q>(s), d.m<HEAD_MUQ_RAW>(s),
                             Out{d.m<HEAD_Z>(s), ld3, false, d.m<HEAD_Z16>(s), n16, d.m<HEAD_Z16B>(s), d.w<RD_N16 + N16_OUTB>()}};
@@ -258,7 +261,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
                                 K, Z, residual, d.f<HEAD_F_BETA>(), d.f<HEAD_F_INV_BETA>(), d.f<HEAD_F_SD_EPS>(), trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
-          case K_GRU: {
+          case K_GRU: if constexpr (!ROLL) {
             const int ld0 = d.w<RD_LD + GRU_LD_HPREV>(), ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
             const Out o{d.m<GRU_HRM>(s), ld3, true, d.m<GRU_H16>(s), n16, d.m<GRU_H16B>(s), d.w<RD_N16 + N16_OUTB>()};
             const int R = d.w<RD_I + GRU_I_R>();
@@ -268,7 +271,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
                                d.m<GRU_RG>(s), d.m<GRU_UG>(s), d.m<GRU_NG>(s), trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
-          case K_DZ: {
+          case K_DZ: if constexpr (!ROLL) {
             const int ld1 = d.w<RD_LD + DZ_LD_ADD>(), ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
             DzIn z;
             z.mu_q = d.p<DZ_MU_Q>(s); z.sd_q = d.p<DZ_SD_Q>(s); z.mu_p = d.p<DZ_MU_P>(s); z.sd_p = d.p<DZ_SD_P>(s); z.eps = d.p<DZ_EPS>(s); z.raw_q = d.p<DZ_RAW_Q>(s);
@@ -283,7 +286,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
                               op, K, Z, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
-          case K_GRUB: {
+          case K_GRUB: if constexpr (!ROLL) {
             const int ld0 = d.w<RD_LD + GRUB_LD_H>(), ld1 = d.w<RD_LD + GRUB_LD_GADD>(), ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
             GrubIn g;
             g.D0 = d.p<GRUB_D0_16>(s); g.D1 = d.p<GRUB_D1_16>(s); g.W0 = d.base<GRUB_W0>(); g.W1 = d.base<GRUB_W1>(); g.g_in = d.p<GRUB_G_IN>(s);
@@ -297,7 +300,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
               tile_grub<NW, OT>(g, K, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
-          case K_GRUS: {
+          case K_GRUS: if constexpr (!ROLL) {
             const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
             const int R = d.w<RD_I + GRUS_I_R>();
             GruSeqIn g;
@@ -311,7 +314,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
               tile_gru_seq<NW, OT>(g, o, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
-          case K_GRUSB: {
+          case K_GRUSB: if constexpr (!ROLL) {
             const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
             const int R = d.w<RD_I + GRUSB_I_R>(), T = d.w<RD_N16 + GRUSB_N16_T>();
             GruSeqBwdIn g;
@@ -326,7 +329,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
               tile_gru_seq_bwd<NW, OT>(g, o, R, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
-          case K_LSTMS: {
+          case K_LSTMS: if constexpr (!ROLL) {
             const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
             const int H = d.w<RD_I + LSTMS_I_H>();
             LstmSeqIn g;
@@ -339,7 +342,7 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
               tile_lstm_seq<NW, OT>(g, o, H, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
             }
           } break;
-          case K_LSTMSB: {
+          case K_LSTMSB: if constexpr (!ROLL) {
             const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
             const int H = d.w<RD_I + LSTMSB_I_H>(), T = d.w<RD_N16 + LSTMSB_N16_T>();
             LstmSeqBwdIn g;
@@ -350,6 +353,16 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
               tile_lstm_seq_bwd<NW, OT>(g, o, H, trc & 0xffff, (trc >> 16) * 16, B, red(), pl);
+            }
+          } break;
+          case K_LSTM: if constexpr (ROLL) {
+            const int ld3 = d.w<RD_LD + LD_OUT>(), n16 = d.w<RD_N16 + N16_OUT>();
+            const Out o{d.m<LSTM_HRM>(s), ld3, false, d.m<LSTM_H16>(s), n16, d.m<LSTM_H16B>(s), d.w<RD_N16 + N16_OUTB>()};
+            const int H = d.w<RD_I + LSTM_I_H>();
+            for (int tk = 0; tk < nt; ++tk) {
+              const int trc = d.tile(tk);
+              tile_lstm<NW, OT>(d.p<LSTM_X16>(s), d.base<LSTM_WIH>(), K, d.base<LSTM_BIH>(), d.p<LSTM_GH>(s), d.p<LSTM_CPREV>(s), d.m<LSTM_CNEXT>(s), H, o, trc & 0xffff,
+                                (trc >> 16) * 16, B, red(), pl);
             }
           } break;
           case K_DMOLS: {
@@ -621,8 +634,8 @@ int pchain_run(const pchain::Program& prog, hipStream_t stream) {
   // computes for this kernel, block size and LDS size (cached per kernel and number of products: a train step alternates sizes)
   constexpr int kMaxProducts = 8;
   static std::mutex attr_mu;
-  static int attr_dev[4] = {-1, -1, -1, -1};
-  static int occ_blocks[4][kMaxProducts + 1];  // workgroups per CU; 0: not asked yet
+  static int attr_dev[7] = {-1, -1, -1, -1, -1, -1, -1};
+  static int occ_blocks[7][kMaxProducts + 1];  // workgroups per CU; 0: not asked yet
   const size_t lds_max = lds_fixed + sizeof(float) * 2 * (prog.rt_group > 1 ? 8 : 4) * (size_t)nw * 256;  // (row groups reduce two row tiles per barrier)
   BLVM_REQUIRE(prog.lds_products >= 1 && lds <= lds_max, "pchain: %d products per tile do not fit the reduction scratch", prog.lds_products);
   auto go = [&](auto kernel, int slot, int threads) -> int {
@@ -652,6 +665,19 @@ int pchain_run(const pchain::Program& prog, hipStream_t stream) {
     BLVM_REQUIRE(prog.ot == OP_F32, "pchain: row groups multiply fp32 operands only");
     BLVM_TRY(go(&pchain_rt_kernel<8, OP_F32, 2>, 2, 512));
     BLVM_CHECK_LAUNCH("pchain_launch (row groups)");
+    return BLVM_OK;
+  }
+  bool roll = false;
+  for (int i = 0; i < prog.ndesc; ++i) roll |= prog.d[i].kind == pchain::K_LSTM;
+  if (roll) {  // the roll-out's own instantiation
+    for (int i = 0; i < prog.ndesc; ++i) {
+      const int k = prog.d[i].kind;
+      BLVM_REQUIRE(k == pchain::K_LIN || k == pchain::K_LINSEQ || k == pchain::K_LSTM || k == pchain::K_DMOLS, "pchain: tile kind %d is not part of the roll-out kernel", k);
+    }
+    BLVM_TRY(prog.ot == OP_BF16  ? go(&pchain_kernel<16, OP_BF16, true>, 5, 1024)
+             : prog.ot == OP_F16 ? go(&pchain_kernel<16, OP_F16, true>, 6, 1024)
+                                 : go(&pchain_kernel<16, OP_F32, true>, 4, 1024));
+    BLVM_CHECK_LAUNCH("pchain_launch (roll-out)");
     return BLVM_OK;
   }
   BLVM_TRY(prog.ot == OP_BF16  ? go(&pchain_kernel<16, OP_BF16>, 1, 1024)

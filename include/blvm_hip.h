@@ -407,6 +407,26 @@ int blvm_srnn_generate(const BlvmSrnnDecodeWeights* w, const float* x0, const fl
                        const float* u, const float* v, int T, int B, int S, int H, int Z, int R, int num_mix, float sd_eps,
                        float slope, float log_eps, float* x_out, float* d_out, float* z_out, float* scratch, void* stream);
 
+/* K4c  Sampling from LSTMAudio: every step of every utterance in ONE persistent launch (B <= 128).  The loop of `LSTMAudio.generate`
+ *   (`blvm/models/lstm.py`): emb = embedding(x_{t-1}) -> per layer (h, c) = LSTM cell(input, (h, c)) -> decoder(h of the last layer) ->
+ *   DMoL head per sample -> draw -> x_t; 6 + 2 * num_layers links per step dealt over all CUs (csrc/lstm_decode.h).  Weights in
+ *   their PyTorch layouts; embedding / decoder are 3 x (Linear + ReLU), the LSTM's input size is H; wih, whh, bih, bhh are HOST arrays
+ *   of num_layers device pointers.  x0 [B,S] or NULL (zeros); h0, c0 [num_layers,B,H] or NULL (zeros); u [T,B,S,num_mix], v [T,B,S]
+ *   as in blvm_mix_sample (both NULL: the mode).  Outputs: x_out [B,T,S]; h_out, c_out [num_layers,B,H] = the state after step T
+ *   (each may be NULL).  S, H multiples of 16, num_mix = 10, 1 <= num_layers <= 8; T = 0 returns at once.
+ *   scratch: blvm_lstm_generate_scratch_floats(...) floats (weight copies + one slab per step of every activation); results do not
+ *   depend on what scratch or the outputs held before the call. */
+typedef struct BlvmLstmDecodeWeights {
+  const float *emb_w[3], *emb_b[3];                     /* [H,S], [H,H], [H,H] */
+  const float *const *wih, *const *whh, *const *bih, *const *bhh; /* num_layers pointers each: [4H,H], [4H,H], [4H], [4H] */
+  const float *dec_w[3], *dec_b[3];                     /* [H,H], [H,H], [S*3*num_mix,H] */
+  const float *lik_w, *lik_b;                           /* [3*num_mix, 3*num_mix], [3*num_mix] */
+} BlvmLstmDecodeWeights;
+size_t blvm_lstm_generate_scratch_floats(int T, int B, int S, int H, int num_layers);
+int blvm_lstm_generate(const BlvmLstmDecodeWeights* w, const float* x0, const float* h0, const float* c0, const float* u,
+                       const float* v, int T, int B, int S, int H, int num_layers, int num_mix, float log_eps, float* x_out,
+                       float* h_out, float* c_out, float* scratch, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * K10  WaveNet: dilated causal convolution (kernel size 2) and the gated residual block.  Replaces
  *      `CausalConv1d` (`blvm/models/wavenet/wavenet_modules.py:14-50`) and `Conv1dResidualGLU` (`:53-117`).

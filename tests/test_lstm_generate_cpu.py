@@ -1,0 +1,186 @@
+"""`LSTMAudio.generate` on the CPU: the float64 restatement the GPU tests (tests/test_gpu_lstm_generate.py) compare against, the
+properties that make that comparison meaningful, the argument checks, and the host replay of the one-launch program.
+
+The reference cannot generate from its LSTM baseline (its `generate` raises), so there are no reference samples to pin against.
+The oracle is `lstm_audio_generate_f64` below — composed from `blvm_oracle`'s `lstm_cell`, `dmol_head`, `dmol_sample`, `dmol_mode`
+and a ReLU MLP, running freely from x0 — tied to the model's own `forward` by `test_restatement_is_consistent_with_forward`.
+All weights, start values and draws are made in fp32 from fixed seeds and widened exactly.
+
+Comparison rule (as tests/test_wavenet_prompt.py): a Gumbel-max tie would flip a component and every later sample, so ties are
+excluded by construction — `test_cases_have_no_near_ties` asserts for every GPU case that the smallest float64 gap between the
+best and the second-best perturbed logit (plain logit for the mode) over all rows, steps and samples is >= 1e-3; the seeds were
+picked so that it holds.
+"""
+import collections
+import functools
+import os
+import shutil
+import subprocess
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import blvm_oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MIN_GAP = 1e-3
+NUM_MIX = 10
+
+# start: "zeros" (nothing given), "x0" (start stack given), "x0h0" (start stack and state given); seeds: (weights and start, draws)
+Case = collections.namedtuple("Case", "S H L B T start mode seeds")
+CASES = {
+    "a": Case(16, 32, 1, 1, 1, "zeros", False, (0, 100)),    # the smallest shape
+    "b": Case(16, 48, 1, 5, 7, "x0h0", False, (1, 104)),     # three column tiles, a partial row group
+    "c": Case(32, 48, 2, 17, 5, "x0h0", False, (2, 110)),    # two row groups, layer-to-layer hand-off
+    "d": Case(16, 64, 2, 33, 4, "zeros", False, (3, 121)),   # three row groups
+    "e": Case(64, 256, 1, 16, 3, "x0", False, (4, 161)),     # the BASELINE widths
+    "f": Case(16, 48, 1, 5, 4, "zeros", True, (7, 105)),     # use_mode=True
+}
+
+
+def build_model(case):
+    """LSTMAudio on the CPU with its default initialisation from the case's seed; the head's log-scale biases are lowered by 2 so that
+    most draws stay inside (-1, 1) instead of being clamped."""
+    from blvm.models import LSTMAudio
+
+    torch.manual_seed(case.seeds[0])
+    m = LSTMAudio(stack_size=case.S, hidden_size=case.H, num_layers=case.L, num_mix=NUM_MIX)
+    with torch.no_grad():
+        m.likelihood.params.bias[2 * NUM_MIX :] -= 2.0
+    return m.eval()
+
+
+def inputs(case):
+    """(x0 [B,S] | None, (h0, c0) [L,B,H] | None, (u [T,B,S,K], v [T,B,S])) in fp32 from the case's seeds."""
+    g = torch.Generator().manual_seed(case.seeds[0] + 1000)
+    x0 = torch.rand(case.B, case.S, generator=g) - 0.5 if case.start != "zeros" else None
+    s0 = None
+    if case.start == "x0h0":
+        s0 = (0.3 * torch.randn(case.L, case.B, case.H, generator=g), 0.3 * torch.randn(case.L, case.B, case.H, generator=g))
+    g = torch.Generator().manual_seed(case.seeds[1])
+    u = torch.empty(case.T, case.B, case.S, NUM_MIX).uniform_(1e-5, 1.0 - 1e-5, generator=g)
+    v = torch.empty(case.T, case.B, case.S).uniform_(1e-8, 1.0 - 1e-8, generator=g)
+    return x0, s0, (u, v)
+
+
+def relu_mlp(x, sd, prefix):
+    for i in (0, 2, 4):
+        x = F.relu(F.linear(x, sd[f"{prefix}.{i}.weight"], sd[f"{prefix}.{i}.bias"]))
+    return x
+
+
+def lstm_audio_generate_f64(sd, x0, s0, uniforms, T, B, S, H, L, use_mode=False, num_mix=NUM_MIX):
+    """LSTMAudio.generate restated in the dtype of `sd` (float64 here): x_s ~ DMoL(decoder(h^{L-1}_s)), (h^l_s, c^l_s) =
+    lstm_cell(input, (h^l_{s-1}, c^l_{s-1})), input = embedding(x_{s-1}) for l = 0 and h^{l-1}_s above; x_{-1} = x0.
+    -> (x [B,T,S], (h_n, c_n) [L,B,H], smallest gap between the best and the second-best (perturbed) logit)."""
+    dt = sd["embedding.0.weight"].dtype
+    x = torch.zeros(B, S, dtype=dt) if x0 is None else x0.to(dt)
+    h = [torch.zeros(B, H, dtype=dt) if s0 is None else s0[0][l].to(dt) for l in range(L)]
+    c = [torch.zeros(B, H, dtype=dt) if s0 is None else s0[1][l].to(dt) for l in range(L)]
+    out, gap = [], float("inf")
+    for t in range(T):
+        inp = relu_mlp(x, sd, "embedding")
+        for l in range(L):
+            h[l], c[l] = O.lstm_cell(inp, h[l], c[l], *(sd[f"lstm.{k}_l{l}"] for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")))
+            inp = h[l]
+        dec = relu_mlp(inp, sd, "decoder").view(B, S, 3 * num_mix)
+        logits, locs, log_scales = O.dmol_head(dec, sd["likelihood.params.weight"], sd["likelihood.params.bias"], num_mix)
+        if use_mode:
+            score = logits
+            xs = O.dmol_mode(logits, locs)
+        else:
+            u, v = uniforms[0][t].to(dt), uniforms[1][t].to(dt).unsqueeze(-1)
+            score = logits - torch.log(-torch.log(u))
+            xs = O.dmol_sample(logits, locs, log_scales, u, v)
+        top = score.topk(2, dim=-1).values
+        gap = min(gap, float((top[..., 0] - top[..., 1]).min()))
+        x = xs.squeeze(-1)
+        out.append(x)
+    return torch.stack(out, 1), (torch.stack(h), torch.stack(c)), gap
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """(model on the CPU, x0, s0, uniforms, float64 samples [B,T,S], float64 (h_n, c_n), smallest gap) of a case — computed once,
+    never changed."""
+    case = CASES[name]
+    m = build_model(case)
+    x0, s0, uni = inputs(case)
+    sd64 = {k: v.detach().double() for k, v in m.state_dict().items()}
+    x64, s64, gap = lstm_audio_generate_f64(sd64, x0, s0, uni, case.T, case.B, case.S, case.H, case.L, case.mode)
+    return m, x0, s0, uni, x64, s64, gap
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_cases_have_no_near_ties(name):
+    gap = reference(name)[6]
+    assert gap >= MIN_GAP, f"case {name}: (perturbed-)logit gap {gap:.2e}: pick another seed"
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_cases_are_not_vacuous(name):
+    """At least half of the samples lie strictly inside (-1, 1): a comparison of clamped values would show nothing."""
+    x64 = reference(name)[4]
+    assert float((x64.abs() < 1).double().mean()) >= 0.5
+
+
+@pytest.mark.parametrize("name", ["a", "b", "e"])
+def test_restatement_is_consistent_with_forward(name):
+    """Teacher forcing in float64: `lstm_audio_forward` on cat[x0, generated] ends in the restatement's state, and its decoder
+    outputs through the head and `dmol_sample` with the same draws give the generated stacks back (1e-12)."""
+    case = CASES[name]
+    m, x0, s0, (u, v), x64, (h64, c64), _ = reference(name)
+    B, T, S = case.B, case.T, case.S
+    sd64 = {k: v.detach().double() for k, v in m.state_dict().items()}
+    start = torch.zeros(B, 1, S, dtype=torch.float64) if x0 is None else x0.double().view(B, 1, S)
+    x = torch.cat([start, x64], 1).flatten(1)
+    s_0 = None if s0 is None else (s0[0][0].double(), s0[1][0].double())
+    out = O.lstm_audio_forward(sd64, x, torch.full((B,), x.size(1)), stack=S, num_mix=NUM_MIX, s_0=s_0)
+    assert float((out["h_n"] - h64[0]).abs().max()) <= 1e-12 and float((out["c_n"] - c64[0]).abs().max()) <= 1e-12
+    dec = relu_mlp(out["z"], sd64, "decoder").reshape(B, T * S, 3 * NUM_MIX)
+    logits, locs, log_scales = O.dmol_head(dec, sd64["likelihood.params.weight"], sd64["likelihood.params.bias"], NUM_MIX)
+    ub = u.double().permute(1, 0, 2, 3).reshape(B, T * S, NUM_MIX)
+    vb = v.double().permute(1, 0, 2).reshape(B, T * S, 1)
+    again = O.dmol_sample(logits, locs, log_scales, ub, vb).view(B, T, S)
+    assert float((again - x64).abs().max()) <= 1e-12
+
+
+def test_generate_checks_its_arguments_without_a_device():
+    """Wrong x width, h0 that is not a pair of [L,n,H] and uniforms of the wrong shape raise ValueError before any device call (the
+    model sits on the CPU here: a device call would fail differently)."""
+    case = CASES["b"]
+    m = build_model(case)
+    n, T, S, H, L = 3, 2, case.S, case.H, case.L
+    ok_u = (torch.rand(T, n, S, NUM_MIX), torch.rand(T, n, S))
+    bad = [
+        dict(x=torch.zeros(n, S + 1)),
+        dict(x=torch.zeros(n, 2, S)),
+        dict(x=torch.zeros(n + 1, S)),
+        dict(h0=torch.zeros(L, n, H)),
+        dict(h0=(torch.zeros(L, n, H),)),
+        dict(h0=(torch.zeros(L, n, H), torch.zeros(L, n, H + 1))),
+        dict(h0=(torch.zeros(L, n + 1, H), torch.zeros(L, n + 1, H))),
+        dict(uniforms=(ok_u[0],)),
+        dict(uniforms=(ok_u[0][:1], ok_u[1][:1])),
+        dict(uniforms=(ok_u[0][..., :5], ok_u[1])),
+        dict(uniforms=(ok_u[0], ok_u[1][..., :-1])),
+    ]
+    for kw in bad:
+        with pytest.raises(ValueError):
+            m.generate(n_samples=n, max_timesteps=T, **kw)
+    with pytest.raises(ValueError):
+        m.generate(n_samples=0, max_timesteps=T)
+
+
+def test_decode_program_replayed_on_the_host(tmp_path):
+    """tests/host/lstm_decode_plan_test.hip: the program of csrc/lstm_decode.h for B in {1, 16, 17, 128} x {1, 2} layers x T = 3 on
+    256 and 32 CUs, replayed word by word — every polled read prefilled or written by exactly one earlier link, no word written
+    twice, every tile owned once, the layout's regions disjoint; two deliberately miswired programs must be caught.  No GPU call."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = tmp_path / "lstm_decode_plan_test"
+    src = os.path.join(ROOT, "tests", "host", "lstm_decode_plan_test.hip")
+    inc = [f"-I{os.path.join(ROOT, 'include')}", f"-I{os.path.join(ROOT, 'benchmarking-lvms_amd', 'csrc')}"]
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", *inc, src, "-o", str(exe)], check=True, timeout=600)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "32 cases, 0 errors" in out.stdout, out.stdout + out.stderr
