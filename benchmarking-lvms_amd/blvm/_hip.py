@@ -95,6 +95,7 @@ _SIGNATURES = {
     "blvm_pchain_tune": (c_int, [c_int]),
     "blvm_pchain_static": (c_int, [c_int]),
     "blvm_rnn_path_counts": (c_int, [c_void_p]),
+    "blvm_rssm_path_counts": (c_int, [c_void_p]),
     "blvm_pchain_chain_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "blvm_pchain_static_chain_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "blvm_pchain_static_chain_probe_fetch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -8,6 +8,8 @@
 // Six dependent links per step in each direction (stages.h kernels + the two GRU links below); the context / encoding
 // halves of the concatenated-input layers, every weight gradient and d(context), d(enc) are batched MFMA GEMMs
 // outside the loop.  Same design and numerics as vrnn.hip.
+#include <atomic>
+
 #include "common.h"
 #include "pchain.h"
 
@@ -180,6 +182,13 @@ size_t carve_rssm_ws(float* base, int T, int B, int H, int Z, RssmWs* w) {
   return ar.floats();
 }
 
+// which implementation the sequence entry points took and which tiles their per-link loops ran on (blvm_rssm_path_counts):
+// host-side counts, [0..3] one per call, [4..5] one per launch_lin of the launch-per-link loops
+enum { RSSM_FWD_PROGRAM = 0, RSSM_FWD_PER_LINK = 1, RSSM_BWD_PROGRAM = 2, RSSM_BWD_PER_LINK = 3, RSSM_LIN16 = 4, RSSM_LIN32 = 5 };
+std::atomic<unsigned long long> g_rssm_counts[6];
+inline void count_rssm(int k) { g_rssm_counts[k].fetch_add(1, std::memory_order_relaxed); }
+inline void count_lin(int tile_width) { count_rssm(tile_width == 32 ? RSSM_LIN32 : RSSM_LIN16); }
+
 int check_rssm(int T, int B, int H, int Z, int C, int E) {
   BLVM_REQUIRE(T > 0 && B > 0, "rssm: bad T=%d B=%d", T, B);
   BLVM_REQUIRE(H > 0 && Z > 0 && H % 16 == 0 && Z % 16 == 0, "rssm: H, Z must be positive multiples of 16 (got %d, %d)", H, Z);
@@ -192,6 +201,12 @@ int check_rssm(int T, int B, int H, int Z, int C, int E) {
 }  // namespace blvm
 
 using namespace blvm;
+
+extern "C" int blvm_rssm_path_counts(unsigned long long out[6]) {
+  BLVM_REQUIRE(out, "rssm_path_counts: null pointer");
+  for (int k = 0; k < 6; ++k) out[k] = g_rssm_counts[k].load(std::memory_order_relaxed);
+  return BLVM_OK;
+}
 
 extern "C" size_t blvm_rssm_reserve_floats(int T, int B, int H, int Z) { return carve_rssm(nullptr, T, B, H, Z, nullptr); }
 extern "C" size_t blvm_rssm_bwd_workspace_floats(int T, int B, int H, int Z) { return carve_rssm_ws(nullptr, T, B, H, Z, nullptr); }
@@ -235,6 +250,7 @@ extern "C" int blvm_rssm_seq_fwd(const BlvmRssmWeights* w, const float* enc, con
   if (pchain_applies(B) && device_cus() >= 32) {
     // Persistent path (pchain.h / pchain.hip): the six links of a step as a program of 10 descriptors, one launch per sequence.
     using namespace pchain;
+    count_rssm(RSSM_FWD_PROGRAM);
     const int ctH = H / 16, ctZ = Z / 16, cus = device_cus() & ~7;
     const long sH = (long)B * H, sZ = (long)B * Z, s3H = 3 * sH, xH = (long)rt * 16 * H, xZ = (long)rt * 16 * Z;
     const int r_h = range_for(ctH * rt, cus / 4);              // one H-wide link (or one half of a posterior | prior pair)
@@ -279,6 +295,7 @@ extern "C" int blvm_rssm_seq_fwd(const BlvmRssmWeights* w, const float* enc, con
     BLVM_TRY(pchain_rows_to_t16(hs, H, B, H, rs.H16, s));
     return pchain_launch(bld, "rssm_fwd", s);
   }
+  count_rssm(RSSM_FWD_PER_LINK);
   for (int t = 0; t < T; ++t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z, o3 = (size_t)t * B * 3 * H;
     const float* zprev = zs + oZ;
@@ -289,7 +306,7 @@ extern "C" int blvm_rssm_seq_fwd(const BlvmRssmWeights* w, const float* enc, con
     // L1: GRU input layer (z half; context half hoisted) | hidden projection of the GRU
     l.seg[0] = seg(zprev, Z, rs.Wgz, Z, C > 0 ? nullptr : w->gin_b, C > 0 ? rs.XGIN + oH : nullptr, H, nullptr, 0, rs.GIN + oH, H, H, Z, 1);
     l.seg[1] = seg(hprev, H, rs.Whh, H, w->gru_bhh, nullptr, 0, nullptr, 0, rs.GHb + o3, 3 * H, 3 * H, H, 0);
-    launch_lin(l, s);
+    count_lin(launch_lin(l, s));
     // L2: GRU
     {
       const int nw = pick_nw(H, 3);
@@ -302,11 +319,11 @@ extern "C" int blvm_rssm_seq_fwd(const BlvmRssmWeights* w, const float* enc, con
     // L3..L5: posterior | prior MLPs on h_t
     l.seg[0] = seg(hnew, H, rs.Wq[0], H, nullptr, rs.XQ + oH, H, nullptr, 0, rs.Q[0] + oH, H, H, H, 1);
     l.seg[1] = seg(hnew, H, rs.Wp[0], H, w->prior_b[0], nullptr, 0, nullptr, 0, rs.P[0] + oH, H, H, H, 1);
-    launch_lin(l, s);
+    count_lin(launch_lin(l, s));
     for (int k = 1; k < 3; ++k) {
       l.seg[0] = seg(rs.Q[k - 1] + oH, H, rs.Wq[k], H, w->post_b[k], nullptr, 0, nullptr, 0, rs.Q[k] + oH, H, H, H, 1);
       l.seg[1] = seg(rs.P[k - 1] + oH, H, rs.Wp[k], H, w->prior_b[k], nullptr, 0, nullptr, 0, rs.P[k] + oH, H, H, H, 1);
-      launch_lin(l, s);
+      count_lin(launch_lin(l, s));
     }
     // L6: heads, combination, sample
     HeadArgs h;
@@ -360,6 +377,7 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
   BLVM_HIP(hipMemsetAsync(ws.G, 0, sizeof(float) * bh, s));
   const int rt = (B + 15) / 16;
   const bool persistent = pchain_applies(B) && device_cus() >= 32;
+  count_rssm(persistent ? RSSM_BWD_PROGRAM : RSSM_BWD_PER_LINK);
   if (persistent) {
     // Persistent path: the BPTT chain as a program of 12 descriptors walked for s = 0 .. T (t = T-1-s; s = T: the gradients wrt the
     // initial state).  The running gradient wrt h lives in per-step slabs, each written once: GA[t] = g_t * u_t (GRU-backward link),
@@ -445,13 +463,13 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
     l.seg[0] = seg(ws.DQH + o2Z, 2 * Z, ws.qhT, 2 * Z, nullptr, nullptr, 0, rs.Q[2] + oH, H, ws.DQ[2] + oH, H, H, 2 * Z, 0);
     l.seg[1] = seg(ws.DPH + o2Z, 2 * Z, ws.phT, 2 * Z, nullptr, nullptr, 0, rs.P[2] + oH, H, ws.DP[2] + oH, H, H, 2 * Z, 0);
     if (!last) l.seg[2] = seg(ws.DGH + o3 + (size_t)B * 3 * H, 3 * H, ws.whhT, 3 * H, nullptr, ws.G, H, nullptr, 0, ws.G, H, H, 3 * H, 0);
-    launch_lin(l, s);
+    count_lin(launch_lin(l, s));
     // B3, B4
     l.nseg = 2;
     for (int k = 2; k >= 1; --k) {
       l.seg[0] = seg(ws.DQ[k] + oH, H, ws.qT[k], H, nullptr, nullptr, 0, rs.Q[k - 1] + oH, H, ws.DQ[k - 1] + oH, H, H, H, 0);
       l.seg[1] = seg(ws.DP[k] + oH, H, ws.pT[k], H, nullptr, nullptr, 0, rs.P[k - 1] + oH, H, ws.DP[k - 1] + oH, H, H, H, 0);
-      launch_lin(l, s);
+      count_lin(launch_lin(l, s));
     }
     // B5: complete dL/dh_t and the gate derivatives of step t
     RssmDhArgs d;
@@ -468,7 +486,7 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
     // B6: through the GRU input projection to the (ReLU) GRU input layer
     l.nseg = 1;
     l.seg[0] = seg(ws.DGI + o3, 3 * H, ws.wihT, 3 * H, nullptr, nullptr, 0, rs.GIN + oH, H, ws.DGIN + oH, H, H, 3 * H, 0);
-    launch_lin(l, s);
+    count_lin(launch_lin(l, s));
   }
   BLVM_CHECK_LAUNCH("rssm_seq_bwd");
   // gradients wrt the initial state: z0 through the GRU input layer of step 0 (+ its direct gradient), h0 through the
@@ -477,13 +495,13 @@ extern "C" int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, con
     LinLaunch l;
     l.B = B; l.nseg = 1;
     l.seg[0] = seg(ws.DGIN, H, ws.gzT, H, nullptr, d_zs, Z, nullptr, 0, d_z0, Z, Z, H, 0);
-    launch_lin(l, s);
+    count_lin(launch_lin(l, s));
   }
   if (d_h0 && !persistent) {
     LinLaunch l;
     l.B = B; l.nseg = 1;
     l.seg[0] = seg(ws.DGH, 3 * H, ws.whhT, 3 * H, nullptr, ws.G, H, nullptr, 0, d_h0, H, H, 3 * H, 0);
-    launch_lin(l, s);
+    count_lin(launch_lin(l, s));
   }
   BLVM_CHECK_LAUNCH("rssm_seq_bwd tail");
   // batched, state-independent part

@@ -340,11 +340,11 @@ struct LinLaunch {
   float slope = 0.f;
 };
 
-// large batches run the link on 32x32 tiles when every segment's width allows it
+// large batches run the link on 32x32 tiles when every segment's width allows it; launch_lin returns the tile width it chose (16 or 32)
 constexpr int LIN32_MIN_BATCH = 128;
 
 template <int NSEG>
-inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
+inline int launch_lin_n(const LinLaunch& l, hipStream_t s) {
   LinArgs<NSEG> a{};
   int tiles = 0, kmax = 0;
   bool wide = l.B >= LIN32_MIN_BATCH;
@@ -370,17 +370,18 @@ inline void launch_lin_n(const LinLaunch& l, hipStream_t s) {
     const int nw32 = chunks > 64 ? 16 : (chunks > 32 ? 8 : 4);
     const dim3 grid32(tiles, (l.B + 31) / 32);
     LAUNCH_NW((lin_stage32_kernel<NW_, NSEG>), nw32, grid32, s, a);
-    return;
+    return tw;
   }
   const int nw = pick_nw(kmax, 1);
   const dim3 grid(tiles, (l.B + 15) / 16);
   LAUNCH_NW((lin_stage_kernel<NW_, NSEG>), nw, grid, s, a);
+  return tw;
 }
 
-inline void launch_lin(const LinLaunch& l, hipStream_t s) {
-  if (l.nseg == 1) launch_lin_n<1>(l, s);
-  else if (l.nseg == 2) launch_lin_n<2>(l, s);
-  else launch_lin_n<3>(l, s);
+inline int launch_lin(const LinLaunch& l, hipStream_t s) {
+  if (l.nseg == 1) return launch_lin_n<1>(l, s);
+  if (l.nseg == 2) return launch_lin_n<2>(l, s);
+  return launch_lin_n<3>(l, s);
 }
 
 inline int pick_split(int M, int N, int K) { return gemm_pick_split(M, N, K); }

@@ -86,6 +86,11 @@ int blvm_pchain_static(int mode);
  * register-resident persistent kernel, 1 a program of the persistent-chain interpreter, 2 one launch per step.  One count per call
  * (not per launch), taken on the host where the call branches; never touches the device. */
 int blvm_rnn_path_counts(unsigned long long out[12]);
+/* The same for the RSSM sequence entry points (K5).  Copies six counters: out[0] blvm_rssm_seq_fwd calls that ran as one program of
+ * the persistent-chain engine, out[1] those that ran one launch per link and step, out[2] / out[3] the same for blvm_rssm_seq_bwd
+ * (one count per call); out[4] / out[5] the linear-link launches of the launch-per-link loops (the backward's initial-state links
+ * included) that ran on 16x16 / on 32x32 tiles (one count per launch).  Host-side; never touches the device. */
+int blvm_rssm_path_counts(unsigned long long out[6]);
 /* Diagnostics / unit test of the persistent-chain engine on its own: L dependent links x_{s+1} = relu(x_s W^T + b), [B,N] x [N,N],
  * as ONE launch.  W16: W [N,N] in the T16 operand layout (blvm_pchain_rows_to_t16 of W: a weight's rows are the "batch");
  * x16: L+1 T16 slabs of ceil(B/16)*16 x N floats, slab 0 = x_0 in T16 (blvm_pchain_rows_to_t16); xs: L row-major [B,N] outputs.

@@ -39,6 +39,16 @@ def test_rnn_path_counts_is_a_host_side_read():
     assert lib.blvm_rnn_path_counts(None) != 0 and b"null" in lib.blvm_last_error()
 
 
+def test_rssm_path_counts_is_a_host_side_read():
+    """`blvm_rssm_path_counts` copies six host counters (no device needed): all six words are written (two buffers with different
+    prefills come back equal), reading does not change them, and a null pointer is refused."""
+    lib = _hip.load()
+    a, b = (ctypes.c_ulonglong * 6)(*([2**63 + 7] * 6)), (ctypes.c_ulonglong * 6)(*([2**63 + 9] * 6))
+    assert lib.blvm_rssm_path_counts(a) == 0 and lib.blvm_rssm_path_counts(b) == 0
+    assert list(a) == list(b) and max(a) < 2**63
+    assert lib.blvm_rssm_path_counts(None) != 0 and b"null" in lib.blvm_last_error()
+
+
 def test_pchain_configure_accepts_only_the_built_wave_count():
     """The persistent kernels exist for 16 waves per workgroup only: `waves` <= 0 or 16 leaves the configuration as it is, any other
     count is refused with a message instead of being ignored."""
