@@ -487,15 +487,25 @@ struct Out {
 };
 __device__ __forceinline__ Out out_rm(float* p, int ld, bool sc1 = false) { return Out{p, ld, sc1, nullptr, 0}; }
 __device__ __forceinline__ Out out_both(float* p, int ld, float* x16, int n16, bool sc1 = false) { return Out{p, ld, sc1, x16, n16}; }
-__device__ __forceinline__ void put(const Out& o, int r0, int c0, int row, int col, float x) {
+// Store order: the T16 copies first.  A wave's stores leave in program order, and the next link is already polling the T16 words,
+// while the row-major copy is read after the launch (or, with rm_sc1, a link or a step later): a row-major store in front of the
+// T16 store sits between every link and the next one (measured on the static VRNN walk: 0.43 ms of a 12.75 ms train step).  A tile
+// with several outputs issues all its T16 stores (put_t16) before the first row-major one (put_rm).
+__device__ __forceinline__ void put_rm(const Out& o, int row, int col, float x) {
   if (o.rm != nullptr) {
     if (o.rm_sc1) st_sc1(make_rsrc(o.rm), 4u * ((unsigned)row * (unsigned)o.ld + (unsigned)col), x);
     else o.rm[(size_t)row * o.ld + col] = x;
   }
+}
+__device__ __forceinline__ void put_t16(const Out& o, int r0, int c0, int row, int col, float x) {
   const int rr = row - r0, cc = col - c0;
   const unsigned in_block = (unsigned)((rr + 16 * ((cc & 15) >> 2)) * 4 + (cc & 3));
   if (o.x16 != nullptr) st_sc1(make_rsrc(o.x16), 4u * ((((unsigned)(r0 >> 4) * (unsigned)o.n16 + (unsigned)((c0 + cc) >> 4)) << 8) + in_block), x);
   if (o.x16b != nullptr) st_sc1(make_rsrc(o.x16b), 4u * ((((unsigned)(r0 >> 4) * (unsigned)o.n16b + (unsigned)((c0 + cc) >> 4)) << 8) + in_block), x);
+}
+__device__ __forceinline__ void put(const Out& o, int r0, int c0, int row, int col, float x) {
+  put_t16(o, r0, c0, row, col, x);
+  put_rm(o, row, col, x);
 }
 
 // ---- link tiles -------------------------------------------------------------------------------------------------------------
@@ -612,13 +622,24 @@ __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool p
   const size_t oo = (size_t)row * Z + col;
   const float mp = v[0] + b0, rp = v[1] + b1, rq = v[3] + b3;
   float mq = v[2] + b2;
-  const float sp = softplus_beta(rp, beta, inv_beta) + sd_eps;
   const float sq = softplus_beta(rq, beta, inv_beta) + sd_eps;
+  if (residual <= 1) {  // (uniform) z needs neither sd_p nor a store in front of it: the next link polls z, the statistics are read after the launch
+    const float mqr = mq;
+    if (residual == 1) mq += mp;
+    const float z = e * sq + mq;  // randn_like(mu).mul(sd).add(mu)
+    put_t16(o.z, r0, c0, row, col, z);
+    __builtin_amdgcn_sched_barrier(0);  // (the scheduler would interleave the prior's softplus with the posterior's)
+    put_rm(o.z, row, col, z);
+    const float sp = softplus_beta(rp, beta, inv_beta) + sd_eps;
+    if (o.muq_raw != nullptr) o.muq_raw[oo] = mqr;
+    o.mu_p[oo] = mp; o.sd_p[oo] = sp; o.mu_q[oo] = mq; o.sd_q[oo] = sq;
+    o.raw_p[oo] = rp; o.raw_q[oo] = rq;
+    return;
+  }
+  const float sp = softplus_beta(rp, beta, inv_beta) + sd_eps;
   if (o.muq_raw != nullptr) o.muq_raw[oo] = mq;
   float sqc = sq;
-  if (residual == 1) {
-    mq += mp;
-  } else if (residual == 2) {
+  if (residual == 2) {
     const float pq = 1.f / (sq * sq), pp = 1.f / (sp * sp);
     const float var = 1.f / (pq + pp);
     mq = var * (mq * pq + mp * pp);
@@ -771,10 +792,11 @@ __device__ __forceinline__ void tile_dz(const float* D, const float* WT, const f
     g_muq = g_muq * var * pq;
   }
   // [B,2Z]: the mean half at column col, the scale half at Z + col (its T16 blocks follow the mean half's)
-  put(dqh, r0, c0, row, col, g_muq);
-  put(dqh, r0, Z + c0, row, Z + col, g_sdq * sigmoidf_(a.beta * rq));
-  put(dph, r0, c0, row, col, g_mup);
-  put(dph, r0, Z + c0, row, Z + col, g_sdp * sigmoidf_(a.beta * rp));
+  const float g_rq = g_sdq * sigmoidf_(a.beta * rq), g_rp = g_sdp * sigmoidf_(a.beta * rp);
+  put_t16(dqh, r0, c0, row, col, g_muq); put_t16(dqh, r0, Z + c0, row, Z + col, g_rq);
+  put_t16(dph, r0, c0, row, col, g_mup); put_t16(dph, r0, Z + c0, row, Z + col, g_rp);
+  put_rm(dqh, row, col, g_muq); put_rm(dqh, row, Z + col, g_rq);
+  put_rm(dph, row, col, g_mup); put_rm(dph, row, Z + col, g_rp);
 }
 
 // Backward of a GRU state update fused with the products that complete the state gradient (vrnn.hip "B10"):
@@ -834,9 +856,12 @@ __device__ __forceinline__ void tile_grub(const GrubIn& a, int K, int R, int r0,
   const float dn_pre = g * (1.f - u) * (1.f - n * n);
   const float du_pre = g * (hp - n) * u * (1.f - u);
   const float dr_pre = dn_pre * hn * r * (1.f - r);
-  put(a.dgi, r0, c0, row, col, dr_pre); put(a.dgi, r0, R + c0, row, R + col, du_pre); put(a.dgi, r0, 2 * R + c0, row, 2 * R + col, dn_pre);
-  put(a.dgh, r0, c0, row, col, dr_pre); put(a.dgh, r0, R + c0, row, R + col, du_pre); put(a.dgh, r0, 2 * R + c0, row, 2 * R + col, dn_pre * r);
+  const float dnr = dn_pre * r;
+  put_t16(a.dgi, r0, c0, row, col, dr_pre); put_t16(a.dgi, r0, R + c0, row, R + col, du_pre); put_t16(a.dgi, r0, 2 * R + c0, row, 2 * R + col, dn_pre);
+  put_t16(a.dgh, r0, c0, row, col, dr_pre); put_t16(a.dgh, r0, R + c0, row, R + col, du_pre); put_t16(a.dgh, r0, 2 * R + c0, row, 2 * R + col, dnr);
   st_sc1(make_rsrc(a.ga), 4u * ((unsigned)row * (unsigned)R + (unsigned)col), g * u + dd);
+  put_rm(a.dgi, row, col, dr_pre); put_rm(a.dgi, row, R + col, du_pre); put_rm(a.dgi, row, 2 * R + col, dn_pre);
+  put_rm(a.dgh, row, col, dr_pre); put_rm(a.dgh, row, R + col, du_pre); put_rm(a.dgh, row, 2 * R + col, dnr);
 }
 
 // ---- whole GRU / LSTM sequences (rnn.hip: nn.GRU forward / per-row time-reversed, packed nn.LSTM) as one link per step ------------
