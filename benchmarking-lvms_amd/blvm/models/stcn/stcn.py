@@ -7,6 +7,7 @@ The model has no recurrence: everything is time-parallel on time-major channel-l
 """
 import math
 import warnings
+from types import SimpleNamespace
 from typing import List, Optional
 
 import torch
@@ -182,10 +183,7 @@ class STCN(BaseModel):
         n = self.n_latents
         # `d[n_latents - 1 :: n_latents]` (stcn.py:299): every n_latents-th skip connection, the first n_latents of them are
         # used — with n_layers == n_latents (the default) that is the last block of every stack
-        n_blocks = len(self.res_stack.dilations)
-        if n_blocks // n < n:
-            raise IndexError(f"STCN needs n_layers * n_stacks >= n_latents**2 skip connections, got {n_blocks} for {n} latents")
-        groups = [(i // n) if (i % n == n - 1 and i // n < n) else -1 for i in range(n_blocks)]
+        groups = self._skip_groups()
         skips = self.res_stack.forward_tm(out, T + 1, groups=groups)
 
         if eps is None:
@@ -244,5 +242,137 @@ class STCN(BaseModel):
             *[KLMetric(sums[4 + l] / ln2, name=f"kl_{l} (bpx)", reduce_by=nx) for l in range(n)],
         ]
 
-    def generate(self, n_samples: int = 1, max_timesteps: int = 100, use_mode_observations: bool = False, x=None):
-        raise NotImplementedError()
+    def _skip_groups(self):
+        """`d[n_latents - 1 :: n_latents]` (stcn.py:299) as one entry per block: the latent level that reads its skip, or -1."""
+        n, n_blocks = self.n_latents, len(self.res_stack.dilations)
+        if n_blocks // n < n:
+            raise IndexError(f"STCN needs n_layers * n_stacks >= n_latents**2 skip connections, got {n_blocks} for {n} latents")
+        return [(i // n) if (i % n == n - 1 and i // n < n) else -1 for i in range(n_blocks)]
+
+    def _one_launch_applies(self) -> bool:
+        """The structures `blvm_stcn_generate` (K10d) takes: the DMoL head on one input channel and its width rules."""
+        lik, C = self.likelihood_module, self.res_channels
+        return (isinstance(lik, DiscretizedLogisticMixtureDense) and 3 * lik.num_mix <= 32 and self.in_channels == 1 and self.kernel_size == 2
+                and C % 16 == 0 and all(z % 16 == 0 for z in self.latent_size) and self.n_latents <= 8
+                and len(self.res_stack.dilations) <= 64 and self.n_layers <= 64)  # fmt: skip
+
+    def _one_launch_parts(self):
+        """The weight arguments of `ops.stcn_generate` / `ops.stcn_generate_pack`, up to and including `dense`."""
+        rs, ot, up, lik, n = self.res_stack, self.out_transform, self.out_upsample[0], self.likelihood_module, self.n_latents
+        conv1x1 = lambda c: (c.weight.view(c.out_channels, -1), c.bias)  # noqa: E731
+        linears = lambda seq: [seq[0], seq[2], seq[4]]  # noqa: E731
+        order = list(reversed(range(n))) if self.top_down else list(range(n))
+        return ((self.causal.conv.weight, self.causal.conv.bias), conv1x1(rs.in_transform), [b.kernel_params() for b in rs.res_blocks],
+                rs.dilations, self._skip_groups(), [(linears(p.transform_mu), linears(p.transform_sd)) for p in self.prior], order,
+                conv1x1(ot.in_transform), [b.kernel_params() for b in ot.res_blocks], (up.weight, up.bias),
+                (lik.params.weight, lik.params.bias), self.dense)  # fmt: skip
+
+    @torch.no_grad()
+    def generate(self, n_samples: int = 1, max_timesteps: int = 100, use_mode_observations: bool = False, x=None,
+                 eps: Optional[List[torch.Tensor]] = None, uniforms=None, fused: Optional[bool] = None):  # fmt: skip
+        """Ancestral sampling from an all-zero past.  The reference declares `generate` and leaves it unimplemented (stcn.py:435-442);
+        the generative model is the one `forward` / `infer` define (stcn.py:299-326, 389-409).  One model step t gives one stack of
+        S = n_stack_frames samples: the dilated stack on x[<t] gives each level its features d_t[l] (the `d_p` of `infer`), the levels
+        are visited in the model's order and z_t[l] = mu + sd * eps[l][t] is drawn from prior[l](cat[d_t[l], z_t[level visited
+        before]]) — the posterior is not used —, the output stack runs on cat(z_t) (`dense`) or z_t[0] with z_{t-1}, ... as its past
+        (the response to `forward`'s zero padding before step 0), and x_t is drawn from the head (its mode if `use_mode_observations`:
+        the arg-max component's location) and fed back.
+
+        `max_timesteps` counts waveform samples (as `CWVAE.generate`): T' = ceil(max_timesteps / S) steps run and the output is cut.
+        eps[l] [T',n,z_l] supplies the latent noise (otherwise `torch.randn` on the device in the visiting order); uniforms =
+        (u [T',n,S,num_mix], v [T',n,S]) replays the DMoL sampler's draws (otherwise drawn in (1e-5, 1-1e-5) and (1e-8, 1-1e-8)).
+        Returns ((x [n,max_timesteps,1], x_sl = max_timesteps per row), ns(z, prior_mus, prior_sds: per level [n,T',z_l])).
+
+        fused=None takes the one-launch kernel (`ops.stcn_generate`, K10d) when it applies: the DMoL head, res_channels and every
+        latent size multiples of 16, within the kernel's 160 KB of LDS.  fused=True insists.  fused=False, the GMM and Gaussian heads and
+        other widths run step by step on the time-parallel operators over a receptive-field window — an independent second path.
+        Continuing a prompt (`x`) is not implemented: it needs the latent history over the prompt and a resumable state."""
+        n, N, S, C, B = self.n_latents, int(max_timesteps), self.n_stack_frames, self.res_channels, int(n_samples)
+        lik = self.likelihood_module
+        if B < 1 or N < 1:
+            raise ValueError(f"STCN.generate: n_samples and max_timesteps must be positive (got {B}, {N})")
+        if x is not None:
+            raise NotImplementedError("STCN.generate: continuing a prompt is not implemented (x must be None): it needs the latent history "
+                                      "over the prompt and a resumable state")  # fmt: skip
+        if self.in_channels != 1:
+            raise NotImplementedError("STCN.generate: the likelihood heads draw one channel (in_channels must be 1)")
+        Tp = (N + S - 1) // S
+        if eps is not None:
+            if not (isinstance(eps, (tuple, list)) and len(eps) == n
+                    and all(torch.is_tensor(e) and tuple(e.shape) == (Tp, B, z) for e, z in zip(eps, self.latent_size))):  # fmt: skip
+                raise ValueError(f"STCN.generate: eps must hold one [{Tp},{B},z_l] tensor per level, z_l = {self.latent_size}")
+        dmol = isinstance(lik, DiscretizedLogisticMixtureDense)
+        if uniforms is not None:
+            if not dmol:
+                raise ValueError("STCN.generate: uniforms replay the DMoL sampler's draws; this model has another head")
+            K = lik.num_mix
+            if not (isinstance(uniforms, (tuple, list)) and len(uniforms) == 2 and all(torch.is_tensor(t) for t in uniforms)
+                    and tuple(uniforms[0].shape) == (Tp, B, S, K) and tuple(uniforms[1].shape) == (Tp, B, S)):  # fmt: skip
+                raise ValueError(f"STCN.generate: uniforms must be (u [{Tp},{B},{S},{K}], v [{Tp},{B},{S}])")
+        groups = self._skip_groups()
+        dev = self.device
+        if dev.type != "cuda":
+            raise BlvmHipError("blvm HIP kernels were handed a CPU model (no CPU fallback): move the model to a HIP device")
+        f32 = dict(device=dev, dtype=torch.float32)
+        order = list(reversed(range(n))) if self.top_down else list(range(n))
+        if eps is None:
+            eps = [None] * n
+            for l in order:  # the draw order of `forward`
+                eps[l] = torch.randn(Tp, B, self.latent_size[l], **f32)
+        eps = [e.to(**f32).contiguous() for e in eps]
+        u = v = None
+        if dmol and not use_mode_observations:
+            if uniforms is None:
+                u = torch.empty(Tp, B, S, lik.num_mix, **f32).uniform_(1e-5, 1.0 - 1e-5)
+                v = torch.empty(Tp, B, S, **f32).uniform_(1e-8, 1.0 - 1e-8)
+            else:
+                u, v = uniforms[0].to(**f32).contiguous(), uniforms[1].to(**f32).contiguous()
+        x_sl = torch.full((B,), N, dtype=torch.int)
+        rs, ot, up = self.res_stack, self.out_transform, self.out_upsample[0]
+        bt = lambda ts: [t.transpose(0, 1) for t in ts]  # noqa: E731  (reference layout [B,T',Z])
+
+        auto = fused is None
+        if auto:
+            fused = self._one_launch_applies()
+        if fused:
+            if not dmol:
+                raise BlvmHipError("STCN.generate: the one-launch kernel is built for the DMoL head")
+            try:
+                p0 = self.prior[0]
+                xs, z, mu, sd = ops.stcn_generate(*self._one_launch_parts(), B, Tp, S, rs.res_blocks[0].inv_std, self.inv_std, p0.softplus_beta,
+                                                  p0.epsilon, p0.transform_mu[1].negative_slope, lik.num_mix, lik.log_epsilon, eps, u, v)  # fmt: skip
+                return (xs.view(B, Tp * S)[:, :N].unsqueeze(-1), x_sl), SimpleNamespace(z=bt(z), prior_mus=bt(mu), prior_sds=bt(sd))
+            except (BlvmHipError, NotImplementedError):
+                # the library validates before it launches, so nothing has run: only an EXPLICIT fused=True insists
+                if not auto:
+                    raise
+
+        # Step by step: every step re-evaluates its receptive-field window with the time-parallel operators of `forward`.
+        rf, n_out = self.receptive_field, sum(ot.dilations)  # (`forward` pads the output stack's input with at least n_out zero frames)
+        Zin = sum(self.latent_size) if self.dense else self.latent_size[0]
+        xs = torch.zeros(rf + Tp, B, S, **f32)  # rf zero stacks, then the generated ones
+        zin = torch.zeros(n_out + Tp, B, Zin, **f32)  # the output stack's input behind its zero padding
+        zs, mus, sds = ([torch.empty(Tp, B, z, **f32) for z in self.latent_size] for _ in range(3))
+        for t in range(Tp):
+            feats = self.causal.forward_tm(xs[t : t + rf], pad_causal=False)  # [rf - 1,B,C]
+            skips = rs.forward_tm(feats, 1, groups=groups)  # per level [1,B,C]: the features that have seen x[<t]
+            for i, l in enumerate(order):
+                d = skips[l].view(B, C)
+                if i > 0:
+                    d = torch.cat([d, zs[order[i - 1]][t]], -1)
+                mp, sp_raw = self.prior[l].raw(d)
+                beta = self.prior[l].softplus_beta
+                sp, _, _, z_l = ops.gauss_latent(mp, sp_raw, mp, sp_raw, eps[l][t], beta, beta, self.prior[l].epsilon, ops.RSSM_PLAIN)
+                zs[l][t], mus[l][t], sds[l][t] = z_l, mp, sp
+            zin[n_out + t] = torch.cat([z[t] for z in zs], -1) if self.dense else zs[0][t]
+            skip_sum = ot.forward_tm(zin[t : t + n_out + 1], 1)  # [1,B,C]
+            h = ops.scale_act(skip_sum.view(B, C), self.inv_std, 1.0)  # * inv_std (slope 1: no activation)
+            dec = ops.linear(h, up.weight, up.bias, ops.ACT_RELU, 0.0)
+            parameters = lik(dec.view(B, S, lik.out_features))
+            if use_mode_observations:
+                x_t = lik.mode(parameters)
+            else:
+                x_t = lik.sample(parameters, uniforms=(u[t], v[t])) if dmol else lik.sample(parameters)
+            xs[rf + t] = x_t.reshape(B, S)
+        x_out = xs[rf:].permute(1, 0, 2).reshape(B, Tp * S)[:, :N].unsqueeze(-1)
+        return (x_out, x_sl), SimpleNamespace(z=bt(zs), prior_mus=bt(mus), prior_sds=bt(sds))

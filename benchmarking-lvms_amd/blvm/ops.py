@@ -1246,6 +1246,76 @@ def wavenet_decode_resume(causal, in_transform, blocks_params, dilations, out_li
     return x, samples_out
 
 
+def stcn_generate_pack(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear,
+                       head_linear, dense: bool, S: int, num_mix: int):
+    """The packed weight image of K10d (`blvm_stcn_generate`) and the host arrays that travel with it.  causal / in_transform /
+    out_in / up_linear / head_linear = (weight, bias); blocks_params as for wavenet_stack; groups[i] = the latent level that reads
+    block i's skip (or -1); priors[l] = (the three nn.Linear of the mean MLP, those of the sd MLP); order = the levels in visiting
+    order.  -> namespace(lib, packed, C, dil, groups, latent, order, n_blocks, n_out, n, dense, latent_sizes)."""
+    import ctypes
+    from types import SimpleNamespace
+
+    lib = load()
+    C = in_transform[0].shape[0]
+    dev = causal[0].device
+    F = 3 * num_mix
+    hw, hb = head_linear
+    uw, ub = up_linear
+    if tuple(hw.shape) != (F, F) or F > 32 or uw.shape[0] != S * F:
+        raise NotImplementedError("libblvm_hip: stcn_generate needs a [3K,3K] head with 3 * num_mix <= 32 and an up-sampling to S * 3K")
+    if causal[0].numel() != 2 * S * C:
+        raise NotImplementedError("libblvm_hip: stcn_generate is built for in_channels = 1, kernel_size = 2")
+    up_rows = (S * F + 15) // 16 * 16
+    z = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.float32)  # noqa: E731
+    parts = [*causal, *in_transform, *(p for blk in blocks_params for p in blk)]
+    for mu_layers, sd_layers in priors:
+        parts += [t for layers in (mu_layers, sd_layers) for lin in layers for t in (lin.weight, lin.bias)]
+    parts += [*out_in, *(p for blk in out_blocks_params for p in blk)]
+    parts += [uw, z(up_rows - S * F, uw.shape[1]), ub, z(up_rows - S * F)]
+    parts += [torch.nn.functional.pad(hw.detach(), (0, 32 - F, 0, 32 - F)), hb, z(32 - F)]
+    packed = torch.cat([_f32c(p.detach()).reshape(-1) for p in parts])
+    ints = lambda v: (ctypes.c_int * len(v))(*[int(i) for i in v])  # noqa: E731
+    latent_sizes = [int(mu[2].weight.shape[0]) for mu, _ in priors]
+    ns = SimpleNamespace(lib=lib, packed=packed, C=C, dil=ints(dilations), groups=ints(groups), latent=ints(latent_sizes), order=ints(order),
+                         n_blocks=len(dilations), n_out=len(out_blocks_params), n=len(priors), dense=int(bool(dense)), latent_sizes=latent_sizes)  # fmt: skip
+    want = lib.blvm_stcn_generate_pack_floats(C, S, ns.n_blocks, ns.n_out, ns.latent, ns.order, ns.n, ns.dense, num_mix)
+    if want == 0:
+        raise _hip.BlvmHipError("blvm_stcn_generate: " + lib.blvm_last_error().decode(errors="replace"))
+    if packed.numel() != want:
+        raise ValueError("stcn_generate: parameter shapes do not match the packed layout")
+    return ns
+
+
+@torch.no_grad()
+def stcn_generate(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear,
+                  dense: bool, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float, slope: float,
+                  num_mix: int, log_eps: float, eps, u=None, v=None):
+    """K10d: T steps of ancestral sampling from the STCN for B rows in one launch (arguments as `stcn_generate_pack`).  eps[l]
+    [T,B,Z_l]; u [T,B,S,num_mix], v [T,B,S] uniform draws (None: the mode).  -> (x [B,T,S], z, mu, sd: lists of [T,B,Z_l])."""
+    import ctypes
+
+    p = stcn_generate_pack(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear,
+                           head_linear, dense, S, num_mix)  # fmt: skip
+    lib, dev = p.lib, p.packed.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    eps = [_f32c(e) for e in eps]
+    if len(eps) != p.n or any(tuple(e.shape) != (T, B, Z) for e, Z in zip(eps, p.latent_sizes)):
+        raise ValueError("stcn_generate: eps[l] must be [T,B,Z_l] for every level")
+    if u is not None:
+        u, v = _f32c(u), _f32c(v)
+        if tuple(u.shape) != (T, B, S, num_mix) or tuple(v.shape) != (T, B, S):
+            raise ValueError("stcn_generate: u must be [T,B,S,num_mix] and v [T,B,S]")
+    n_scratch = lib.blvm_stcn_generate_scratch_floats(p.dil, p.C, S, p.n_blocks, p.n_out, p.latent, p.order, p.n, p.dense, num_mix, B)
+    scratch = torch.empty(max(int(n_scratch), 4), **f32)
+    x = torch.empty(B, T, S, **f32)
+    zs, mus, sds = ([torch.empty(T, B, Z, **f32) for Z in p.latent_sizes] for _ in range(3))
+    ptrs = lambda ts: (ctypes.c_void_p * len(ts))(*[ptr(t) for t in ts])  # noqa: E731
+    check(lib.blvm_stcn_generate(ptr(p.packed), p.dil, p.groups, p.n_blocks, p.n_out, p.latent, p.order, p.n, p.dense, B, p.C, S, num_mix, T,
+                                 inv_std, out_scale, sd_beta, sd_eps, slope, log_eps, ptrs(eps), ptr(u), ptr(v), ptr(x), ptrs(zs), ptrs(mus),
+                                 ptrs(sds), ptr(scratch), stream_ptr()), "blvm_stcn_generate")  # fmt: skip
+    return x, zs, mus, sds
+
+
 def wavenet_stack(x, blocks_params, dilations, T_skip: int, inv_std: float, S: int, groups=None):
     """x [L,B,C] -> skip output(s) [T_skip,B,S]: the sum over blocks of the last T_skip frames of each block's skip branch
     (groups=None: one sum over all blocks, returned as a tensor; otherwise a tuple, see _WaveNetStackFunction)."""

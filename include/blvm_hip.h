@@ -515,6 +515,37 @@ int blvm_wavenet_decode_resume(const float* packed, const int* dilations, int n_
                                int n_frames, int t0, float inv_std, float skip_scale, float log_eps, const float* u,
                                const float* v, const float* x_in, float* scratch, float* x_out, float* x_state, void* stream);
 
+/* K10d  Ancestral sampling from the STCN: all T steps of all rows in ONE launch, from an all-zero past.  The reference leaves
+ *   `STCN.generate` unimplemented (`blvm/models/stcn/stcn.py:435-442`); this is the generative model its `forward` / `infer` define
+ *   (`stcn.py:299-326, 389-409`) with every latent drawn from its prior.  Per step t: causal conv (kernel 2) of the stacks x_{t-2},
+ *   x_{t-1} -> 1x1 in_transform -> n_blocks gated blocks (ring buffers as K10c), the skip half of block i read by level groups[i]
+ *   (-1: by none; every level reads exactly one block: `d[n-1::n]` of `stcn.py:299`) -> for i = 0 .. n_latents-1, l = order[i]:
+ *   (mu, sd) = prior[l](cat[skip_l, z[order[i-1]]]) (two 3-layer LeakyReLU MLPs of width C, sd = softplus_beta(.) + sd_eps,
+ *   `stcn.py:32-76`), z[l] = mu + sd * eps[l][t] -> the output stack (1x1 in_transform on cat(z) if dense else z[0], n_out gated
+ *   blocks of dilation 1, skips summed; its past before step 0 is the response to `forward`'s zero padding, `stcn.py:389-395`)
+ *   -> * out_scale -> out_upsample Linear + ReLU -> [S, 3 num_mix] -> head Linear per sample -> draw as blvm_mix_sample kind 0 with
+ *   u [T,B,S,num_mix], v [T,B,S] (both NULL: the mode) -> x_out [B,T,S], fed back.
+ *   packed: one image of blvm_stcn_generate_pack_floats(...) floats, row-major PyTorch layouts, in this order: causal conv w [C,S,2],
+ *     b [C]; in_transform w [C,C], b [C]; per block conv w [2C,C,2], b [2C], rs w [2C,C], b [2C]; per level l = 0 .. n-1 the mu then
+ *     the sd MLP, each w0 [C,Kin_l] b0 [C] w1 [C,C] b1 [C] w2 [Z_l,C] b2 [Z_l] (Kin_l = C, + Z of the level visited before l unless l
+ *     is visited first); output in_transform w [C,Zin], b [C]; per output block as above; out_upsample w and b zero-padded to the
+ *     next multiple of 16 rows; head w zero-padded to [32,32], b to [32].
+ *   dilations, groups [n_blocks], latent, order [n_latents]: HOST int arrays; eps, z_out, mu_out, sd_out: HOST arrays of n_latents
+ *     device pointers, each [T,B,Z_l] (z_out, mu_out, sd_out: the draws and the prior parameters of every step).
+ *   C and every Z_l multiples of 16; S >= 1 (any); 3 num_mix <= 32; n_latents <= 8; n_blocks, n_out <= 64; at most 160 KB
+ *     of LDS — anything else is refused before a buffer is touched.
+ *   scratch: blvm_stcn_generate_scratch_floats(...) floats (operand-layout weight copies, the blocks' rings, the selected skips);
+ *     results do not depend on what scratch or the outputs held before the call. */
+size_t blvm_stcn_generate_pack_floats(int C, int S, int n_blocks, int n_out, const int* latent, const int* order, int n_latents,
+                                      int dense, int num_mix);
+size_t blvm_stcn_generate_scratch_floats(const int* dilations, int C, int S, int n_blocks, int n_out, const int* latent,
+                                         const int* order, int n_latents, int dense, int num_mix, int B);
+int blvm_stcn_generate(const float* packed, const int* dilations, const int* groups, int n_blocks, int n_out, const int* latent,
+                       const int* order, int n_latents, int dense, int B, int C, int S, int num_mix, int T, float inv_std,
+                       float out_scale, float sd_beta, float sd_eps, float slope, float log_eps, const float* const* eps,
+                       const float* u, const float* v, float* x_out, float* const* z_out, float* const* mu_out,
+                       float* const* sd_out, float* scratch, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * K5  RSSM cell of the Clockwork-VAE over a sequence (forward + BPTT).  Replaces the per-level time loop
  *     `blvm/models/clockwork_vae/clockwork_vae.py:272-281` over `RSSMCell.forward` (`blvm/modules/rssm.py:79-104`).
