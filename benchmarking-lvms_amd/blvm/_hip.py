@@ -172,6 +172,9 @@ _SIGNATURES = {
     "blvm_stcn_generate_pack_floats": (c_size_t, [c_int] * 4 + [c_void_p] * 2 + [c_int] * 3),
     "blvm_stcn_generate_scratch_floats": (c_size_t, [c_void_p] + [c_int] * 4 + [c_void_p] * 2 + [c_int] * 4),
     "blvm_stcn_generate": (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] * 2 + [c_int] * 7 + [c_float] * 6 + [c_void_p] * 9),
+    "blvm_stcn_generate_ring_offset_floats": (c_size_t, [c_int] * 4 + [c_void_p] * 2 + [c_int] * 3),
+    "blvm_stcn_generate_resume": (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] * 2 + [c_int] * 7 + [c_float] * 6 + [c_void_p] * 8
+                                  + [c_int] + [c_void_p] * 3),
     "blvm_rssm_reserve_floats": (c_size_t, [c_int] * 4),
     "blvm_rssm_bwd_workspace_floats": (c_size_t, [c_int] * 4),
     "blvm_rssm_seq_fwd": (c_int, [ctypes.POINTER(RssmWeights)] + [c_void_p] * 5 + [c_int] * 7 + [c_float] + [c_void_p] * 8),

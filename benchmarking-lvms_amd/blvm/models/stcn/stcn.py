@@ -56,6 +56,25 @@ class DiagonalGaussianDenseSTCN(ConditionalDistribution):
         return out
 
 
+class PromptNeedsDeviceError(BlvmHipError, NotImplementedError):
+    """A prompt handed to `STCN.generate` on a model that is not on a HIP device.  Its latents and the decode state are made by the
+    HIP kernels, so on the CPU continuing a prompt stays what it was before prompts could be continued — not implemented
+    (NotImplementedError) — and it is the CPU hand-off every entry point refuses (BlvmHipError)."""
+
+
+class STCNDecodeState:
+    """What `STCN.generate` needs to go on after `n_steps` model steps (a prompt's included): `x_window` [receptive_field,n,S], the
+    last stacks time-major, and `z_window` [n_layers,n,Zin], the output stack's input (cat(z), or z[0] without `dense`) over the last
+    steps — zero stacks / frames stand in front of step 0.  `scratch`: the one-launch kernel's buffer whose ring region is that
+    kernel's state (None after a prompt or the step-by-step path: the rings are then primed from the windows).  A continued call
+    updates the rings in place: a state is good for ONE continuation."""
+
+    __slots__ = ("n_steps", "x_window", "z_window", "scratch")
+
+    def __init__(self, n_steps: int, x_window, z_window, scratch=None):
+        self.n_steps, self.x_window, self.z_window, self.scratch = n_steps, x_window, z_window, scratch
+
+
 class STCN(BaseModel):
     def __init__(self, likelihood: str = "DMoL", in_channels: int = 1, n_layers: int = 5, n_stacks: Optional[int] = None,
                  latent_size: List[int] = [256, 128, 64, 32, 16], res_channels: int = 256, kernel_size: int = 2,
@@ -267,10 +286,87 @@ class STCN(BaseModel):
                 conv1x1(ot.in_transform), [b.kernel_params() for b in ot.res_blocks], (up.weight, up.bias),
                 (lik.params.weight, lik.params.bias), self.dense)  # fmt: skip
 
+    def _one_launch_shape(self):
+        """The shape arguments of `ops.stcn_ring_views` / `ops.stcn_generate_scratch` between the dilations and B."""
+        n = self.n_latents
+        order = list(reversed(range(n))) if self.top_down else list(range(n))
+        return len(self.out_transform.res_blocks), list(self.latent_size), order, self.dense
+
+    def _latent_pass(self, xt, eps, posterior: bool):
+        """xt [T,B,S] time-major stacks from step 0 -> z per level [T,B,z_l] from ONE time-parallel pass: the posterior's draws exactly
+        as `forward` makes them (the same calls on the same shapes), or each level drawn from its prior given x[<t]."""
+        T, B, S = xt.shape
+        dev, rf, n = xt.device, self.receptive_field, self.n_latents
+        xp = torch.cat([torch.zeros(rf, B, S, device=dev), xt], 0)
+        out = self.causal.forward_tm(xp, pad_causal=False)
+        skips = self.res_stack.forward_tm(out, T + 1, groups=self._skip_groups())
+        if posterior:
+            mask_len = ops.upload_i32(torch.full((B,), T * S, dtype=torch.int64), dev)
+            return self.infer(skips, eps, mask_len, B, T, 0)[4]
+        z = [None] * n
+        order = list(reversed(range(n))) if self.top_down else list(range(n))
+        for i, l in enumerate(order):
+            d = skips[l][:-1]  # the features that have seen x[<t]
+            if i > 0:
+                d = torch.cat([d, z[order[i - 1]]], -1)
+            mp, sp_raw = self.prior[l].raw(d.reshape(T * B, -1))
+            beta = self.prior[l].softplus_beta
+            z[l] = ops.gauss_latent(mp, sp_raw, mp, sp_raw, eps[l].reshape(T * B, -1), beta, beta, self.prior[l].epsilon,
+                                    ops.RSSM_PLAIN)[3].view(T, B, -1)  # fmt: skip
+        return z
+
+    @torch.no_grad()
+    def _prime(self, x, prompt_eps=None, prompt_latents: str = "posterior"):
+        """Prompt x [n,P] (P a positive multiple of S; checked by `generate`) -> (the state after its P' = P / S steps, prompt_z per level
+        [n,P',z_l]).  The latents over the prompt come from one time-parallel pass (`_latent_pass`); the windows take the last
+        receptive_field stacks and the last n_layers frames of the output stack's input, zero-padded on the left."""
+        dev, S, rf, n = self.device, self.n_stack_frames, self.receptive_field, self.n_latents
+        n_out = len(self.out_transform.res_blocks)
+        f32 = dict(device=dev, dtype=torch.float32)
+        x = x.to(**f32)
+        B, Tp = x.size(0), x.size(1) // S
+        xt = x.view(B, Tp, S).transpose(0, 1).contiguous()
+        if prompt_eps is None:
+            prompt_eps = [None] * n
+            for l in (reversed(range(n)) if self.top_down else range(n)):  # the draw order of `forward`
+                prompt_eps[l] = torch.randn(Tp, B, self.latent_size[l], **f32)
+        z = self._latent_pass(xt, [e.to(**f32).contiguous() for e in prompt_eps], prompt_latents == "posterior")
+        zin = torch.cat(z, -1) if self.dense else z[0]
+        x_window = torch.cat([torch.zeros(rf, B, S, **f32), xt], 0)[-rf:].contiguous()
+        z_window = torch.cat([torch.zeros(n_out, B, zin.size(-1), **f32), zin], 0)[-n_out:].contiguous()
+        return STCNDecodeState(Tp, x_window, z_window, None), [t.transpose(0, 1) for t in z]
+
+    @torch.no_grad()
+    def _prime_rings(self, state, num_mix: int):
+        """A fresh one-launch scratch buffer whose rings hold `state`: dilated block i's input over steps t0 - d_i .. t0 - 1, output
+        block j's at step t0 - 1.  Step tau of block 0's input is in_transform(causal conv of the stacks tau-2, tau-1), so the window
+        that fills the rings ends one stack before the newest; `ops.wavenet_prime_rings` runs the time-parallel block kernels over it."""
+        rs, ot, C, S = self.res_stack, self.out_transform, self.res_channels, self.n_stack_frames
+        B, t0, inv_std = state.x_window.size(1), state.n_steps, rs.res_blocks[0].inv_std
+        scratch, (rings, orings) = ops.stcn_generate_scratch(rs.dilations, *self._one_launch_shape(), B, C, S, num_mix, state.x_window.device)
+        feats = self.causal.forward_tm(state.x_window[:-1], pad_causal=False)  # [sum(dilations),B,C]: steps t0 - sum(dilations) .. t0 - 1
+        for stack, frames, dil, views in ((rs, feats, rs.dilations, rings), (ot, state.z_window, [1] * len(ot.res_blocks), orings)):
+            L, t_in = frames.size(0), stack.in_transform
+            h0 = ops.linear(frames.reshape(L * B, -1), t_in.weight.view(t_in.out_channels, -1), t_in.bias).view(L, B, C)
+            ops.wavenet_prime_rings(h0, [b.kernel_params() for b in stack.res_blocks], dil, inv_std, C, t0, views)
+        return scratch
+
+    def _scratch_floats(self, B: int):
+        """Size of the one-launch kernel's scratch buffer at B rows, or None where the kernel does not apply."""
+        if not self._one_launch_applies():
+            return None
+        try:
+            return ops.stcn_generate_scratch_floats(self.res_stack.dilations, *self._one_launch_shape(), B, self.res_channels,
+                                                    self.n_stack_frames, self.likelihood_module.num_mix)  # fmt: skip
+        except BlvmHipError:
+            return None
+
     @torch.no_grad()
     def generate(self, n_samples: int = 1, max_timesteps: int = 100, use_mode_observations: bool = False, x=None,
-                 eps: Optional[List[torch.Tensor]] = None, uniforms=None, fused: Optional[bool] = None):  # fmt: skip
-        """Ancestral sampling from an all-zero past.  The reference declares `generate` and leaves it unimplemented (stcn.py:435-442);
+                 eps: Optional[List[torch.Tensor]] = None, uniforms=None, fused: Optional[bool] = None, prompt_eps=None,
+                 prompt_latents: str = "posterior", state=None, return_state: bool = False):  # fmt: skip
+        """Ancestral sampling from an all-zero past, from a prompt or from an earlier call's state.  The reference declares `generate`
+        and leaves it unimplemented (stcn.py:435-442);
         the generative model is the one `forward` / `infer` define (stcn.py:299-326, 389-409).  One model step t gives one stack of
         S = n_stack_frames samples: the dilated stack on x[<t] gives each level its features d_t[l] (the `d_p` of `infer`), the levels
         are visited in the model's order and z_t[l] = mu + sd * eps[l][t] is drawn from prior[l](cat[d_t[l], z_t[level visited
@@ -283,17 +379,59 @@ class STCN(BaseModel):
         (u [T',n,S,num_mix], v [T',n,S]) replays the DMoL sampler's draws (otherwise drawn in (1e-5, 1-1e-5) and (1e-8, 1-1e-8)).
         Returns ((x [n,max_timesteps,1], x_sl = max_timesteps per row), ns(z, prior_mus, prior_sds: per level [n,T',z_l])).
 
-        fused=None takes the one-launch kernel (`ops.stcn_generate`, K10d) when it applies: the DMoL head, res_channels and every
+        `x` [n,P] or [n,P,1] is a prompt, P a positive multiple of S: steps P' = P / S, P' + 1, ... are drawn (x holds the generated
+        samples only).  The dilated stack sees the prompt's stacks behind the zero past; the output stack needs z over the last
+        n_layers prompt steps, which one time-parallel pass gives: prompt_latents="posterior" exactly the z of `forward(x, x_sl=P,
+        eps=prompt_eps)`, "prior" each level from its prior given x[<t] (what free generation would have drawn).  prompt_eps[l]
+        [P',n,z_l] replays those draws.  The namespace then carries `prompt_z` (per level [n,P',z_l]).  On a model that is not on a
+        HIP device a prompt still raises NotImplementedError (`PromptNeedsDeviceError`, a BlvmHipError too).
+        `return_state=True` adds `state` (an `STCNDecodeState`) to the namespace and `state=` continues from one — generation in
+        chunks; eps and uniforms are indexed from 0 for every call, and max_timesteps must then be a multiple of S.  A continued call
+        updates the state's rings in place: a state is good for ONE continuation.
+
+        fused=None takes the one-launch kernel (`ops.stcn_generate`, K10d; from a state `ops.stcn_generate_resume`, its rings primed
+        from the state's windows when it carries none) when it applies: the DMoL head, res_channels and every
         latent size multiples of 16, within the kernel's 160 KB of LDS.  fused=True insists.  fused=False, the GMM and Gaussian heads and
-        other widths run step by step on the time-parallel operators over a receptive-field window — an independent second path.
-        Continuing a prompt (`x`) is not implemented: it needs the latent history over the prompt and a resumable state."""
+        other widths run step by step on the time-parallel operators over a receptive-field window — an independent second path,
+        which continues from the same state."""
         n, N, S, C, B = self.n_latents, int(max_timesteps), self.n_stack_frames, self.res_channels, int(n_samples)
         lik = self.likelihood_module
         if B < 1 or N < 1:
             raise ValueError(f"STCN.generate: n_samples and max_timesteps must be positive (got {B}, {N})")
+        rf, n_out = self.receptive_field, len(self.out_transform.res_blocks)
+        Zin = sum(self.latent_size) if self.dense else self.latent_size[0]
+        if x is not None and state is not None:
+            raise ValueError("STCN.generate: a prompt `x` and a `state` are given; a state already contains its past")
         if x is not None:
-            raise NotImplementedError("STCN.generate: continuing a prompt is not implemented (x must be None): it needs the latent history "
-                                      "over the prompt and a resumable state")  # fmt: skip
+            if not torch.is_tensor(x) or x.ndim < 1 or x.size(0) != B:
+                raise ValueError(f"STCN.generate: the prompt must be a tensor of n_samples = {B} rows")
+            if x.ndim >= 2 and (x.size(1) < S or x.size(1) % S != 0):
+                raise ValueError(f"STCN.generate: a prompt of {x.size(1)} samples is no positive multiple of n_stack_frames = {S}")
+            if x.ndim not in (2, 3) or (x.ndim == 3 and x.size(2) != 1):
+                raise ValueError(f"STCN.generate: the prompt must be [n,P] or [n,P,1], got {tuple(x.shape)}")
+        if prompt_latents not in ("posterior", "prior"):
+            raise ValueError(f"STCN.generate: prompt_latents must be 'posterior' or 'prior', got {prompt_latents!r}")
+        if prompt_eps is not None:
+            Pp = x.size(1) // S if x is not None else None
+            if not (isinstance(prompt_eps, (tuple, list)) and len(prompt_eps) == n and all(torch.is_tensor(e) for e in prompt_eps)
+                    and all(e.ndim == 3 and e.size(1) == B and e.size(2) == z and (Pp is None or e.size(0) == Pp)
+                            for e, z in zip(prompt_eps, self.latent_size))):  # fmt: skip
+                raise ValueError(f"STCN.generate: prompt_eps must hold one [P',{B},z_l] tensor per level, z_l = {self.latent_size}")
+            if x is None:
+                raise ValueError("STCN.generate: prompt_eps replays the latent draws over a prompt, and there is none (x is None)")
+        stateful = x is not None or state is not None or return_state
+        if (state is not None or return_state) and N % S != 0:
+            raise ValueError(f"STCN.generate: with a state, max_timesteps = {N} must be a multiple of n_stack_frames = {S}: a cut output "
+                             "would lose samples between chunks")  # fmt: skip
+        if state is not None:
+            if not (isinstance(state, STCNDecodeState) and torch.is_tensor(state.x_window) and torch.is_tensor(state.z_window)
+                    and tuple(state.x_window.shape) == (rf, B, S) and tuple(state.z_window.shape) == (n_out, B, Zin)
+                    and int(state.n_steps) >= 0):  # fmt: skip
+                raise ValueError(f"STCN.generate: the state does not fit this model and n_samples = {B}: it needs x_window [{rf},{B},{S}] "
+                                 f"and z_window [{n_out},{B},{Zin}]")  # fmt: skip
+            if state.scratch is not None and not (torch.is_tensor(state.scratch) and state.scratch.dtype == torch.float32
+                                                  and state.scratch.numel() == self._scratch_floats(B)):  # fmt: skip
+                raise ValueError("STCN.generate: the state's scratch buffer does not belong to this model and batch size")
         if self.in_channels != 1:
             raise NotImplementedError("STCN.generate: the likelihood heads draw one channel (in_channels must be 1)")
         Tp = (N + S - 1) // S
@@ -312,6 +450,10 @@ class STCN(BaseModel):
         groups = self._skip_groups()
         dev = self.device
         if dev.type != "cuda":
+            if x is not None:
+                raise PromptNeedsDeviceError("STCN.generate: continuing a prompt is not implemented on the CPU: the latent history over the "
+                                             "prompt and the decode state are made by the HIP kernels (no CPU fallback); move the model to a "
+                                             "HIP device")  # fmt: skip
             raise BlvmHipError("blvm HIP kernels were handed a CPU model (no CPU fallback): move the model to a HIP device")
         f32 = dict(device=dev, dtype=torch.float32)
         order = list(reversed(range(n))) if self.top_down else list(range(n))
@@ -328,6 +470,12 @@ class STCN(BaseModel):
             else:
                 u, v = uniforms[0].to(**f32).contiguous(), uniforms[1].to(**f32).contiguous()
         x_sl = torch.full((B,), N, dtype=torch.int)
+        extra, st = {}, state
+        if x is not None:
+            st, prompt_z = self._prime(x.reshape(B, -1), prompt_eps, prompt_latents)
+            extra["prompt_z"] = prompt_z
+        if st is not None:
+            st.x_window, st.z_window = st.x_window.to(**f32).contiguous(), st.z_window.to(**f32).contiguous()
         rs, ot, up = self.res_stack, self.out_transform, self.out_upsample[0]
         bt = lambda ts: [t.transpose(0, 1) for t in ts]  # noqa: E731  (reference layout [B,T',Z])
 
@@ -339,19 +487,36 @@ class STCN(BaseModel):
                 raise BlvmHipError("STCN.generate: the one-launch kernel is built for the DMoL head")
             try:
                 p0 = self.prior[0]
-                xs, z, mu, sd = ops.stcn_generate(*self._one_launch_parts(), B, Tp, S, rs.res_blocks[0].inv_std, self.inv_std, p0.softplus_beta,
-                                                  p0.epsilon, p0.transform_mu[1].negative_slope, lik.num_mix, lik.log_epsilon, eps, u, v)  # fmt: skip
-                return (xs.view(B, Tp * S)[:, :N].unsqueeze(-1), x_sl), SimpleNamespace(z=bt(z), prior_mus=bt(mu), prior_sds=bt(sd))
+                args = (*self._one_launch_parts(), B, Tp, S, rs.res_blocks[0].inv_std, self.inv_std, p0.softplus_beta, p0.epsilon,
+                        p0.transform_mu[1].negative_slope, lik.num_mix, lik.log_epsilon, eps, u, v)  # fmt: skip
+                if not stateful:
+                    xs, z, mu, sd = ops.stcn_generate(*args)
+                elif st is None:  # the zero start, keeping its scratch
+                    xs, z, mu, sd, scratch = ops.stcn_generate_start(*args)
+                else:
+                    scratch = st.scratch if st.scratch is not None else self._prime_rings(st, lik.num_mix)
+                    # the kernel takes the phase of step `n_steps` in every ring: any t0 equal to it modulo all dilations
+                    xs, z, mu, sd, _ = ops.stcn_generate_resume(*args, st.n_steps % math.lcm(*rs.dilations),
+                                                                st.x_window[-2:].transpose(0, 1).contiguous(), scratch)  # fmt: skip
+                if return_state:
+                    x_old = st.x_window if st is not None else torch.zeros(rf, B, S, **f32)
+                    z_old = st.z_window if st is not None else torch.zeros(n_out, B, Zin, **f32)
+                    z_new = torch.cat(z, -1) if self.dense else z[0]
+                    extra["state"] = STCNDecodeState((st.n_steps if st is not None else 0) + Tp, torch.cat([x_old, xs.transpose(0, 1)], 0)[-rf:].contiguous(),
+                                                     torch.cat([z_old, z_new], 0)[-n_out:].contiguous(), scratch)  # fmt: skip
+                return ((xs.view(B, Tp * S)[:, :N].unsqueeze(-1), x_sl),
+                        SimpleNamespace(z=bt(z), prior_mus=bt(mu), prior_sds=bt(sd), **extra))  # fmt: skip
             except (BlvmHipError, NotImplementedError):
                 # the library validates before it launches, so nothing has run: only an EXPLICIT fused=True insists
                 if not auto:
                     raise
 
         # Step by step: every step re-evaluates its receptive-field window with the time-parallel operators of `forward`.
-        rf, n_out = self.receptive_field, sum(ot.dilations)  # (`forward` pads the output stack's input with at least n_out zero frames)
-        Zin = sum(self.latent_size) if self.dense else self.latent_size[0]
-        xs = torch.zeros(rf + Tp, B, S, **f32)  # rf zero stacks, then the generated ones
-        zin = torch.zeros(n_out + Tp, B, Zin, **f32)  # the output stack's input behind its zero padding
+        # (`forward` pads the output stack's input with at least n_out zero frames)
+        xs = torch.zeros(rf + Tp, B, S, **f32)  # rf zero stacks (or the state's), then the generated ones
+        zin = torch.zeros(n_out + Tp, B, Zin, **f32)  # the output stack's input behind its zero padding (or the state's past)
+        if st is not None:
+            xs[:rf], zin[:n_out] = st.x_window, st.z_window
         zs, mus, sds = ([torch.empty(Tp, B, z, **f32) for z in self.latent_size] for _ in range(3))
         for t in range(Tp):
             feats = self.causal.forward_tm(xs[t : t + rf], pad_causal=False)  # [rf - 1,B,C]
@@ -375,4 +540,6 @@ class STCN(BaseModel):
                 x_t = lik.sample(parameters, uniforms=(u[t], v[t])) if dmol else lik.sample(parameters)
             xs[rf + t] = x_t.reshape(B, S)
         x_out = xs[rf:].permute(1, 0, 2).reshape(B, Tp * S)[:, :N].unsqueeze(-1)
-        return (x_out, x_sl), SimpleNamespace(z=bt(zs), prior_mus=bt(mus), prior_sds=bt(sds))
+        if return_state:
+            extra["state"] = STCNDecodeState((st.n_steps if st is not None else 0) + Tp, xs[-rf:].clone(), zin[-n_out:].clone(), None)
+        return (x_out, x_sl), SimpleNamespace(z=bt(zs), prior_mus=bt(mus), prior_sds=bt(sds), **extra)

@@ -1286,16 +1286,18 @@ def stcn_generate_pack(causal, in_transform, blocks_params, dilations, groups, p
     return ns
 
 
+def _stcn_scratch_floats(p, S: int, num_mix: int, B: int) -> int:
+    return max(int(p.lib.blvm_stcn_generate_scratch_floats(p.dil, p.C, S, p.n_blocks, p.n_out, p.latent, p.order, p.n, p.dense, num_mix, B)), 4)
+
+
 @torch.no_grad()
-def stcn_generate(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear,
-                  dense: bool, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float, slope: float,
-                  num_mix: int, log_eps: float, eps, u=None, v=None):
-    """K10d: T steps of ancestral sampling from the STCN for B rows in one launch (arguments as `stcn_generate_pack`).  eps[l]
-    [T,B,Z_l]; u [T,B,S,num_mix], v [T,B,S] uniform draws (None: the mode).  -> (x [B,T,S], z, mu, sd: lists of [T,B,Z_l])."""
+def _stcn_generate_call(weights, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float, slope: float,
+                        num_mix: int, log_eps: float, eps, u, v, resume=None):
+    """`blvm_stcn_generate`, or `blvm_stcn_generate_resume` with resume = (t0, x_in [B,2,S], scratch).
+    -> (x [B,T,S], z, mu, sd: lists of [T,B,Z_l], scratch, x_state [B,2,S] or None)."""
     import ctypes
 
-    p = stcn_generate_pack(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear,
-                           head_linear, dense, S, num_mix)  # fmt: skip
+    p = stcn_generate_pack(*weights, S, num_mix)
     lib, dev = p.lib, p.packed.device
     f32 = dict(device=dev, dtype=torch.float32)
     eps = [_f32c(e) for e in eps]
@@ -1305,15 +1307,94 @@ def stcn_generate(causal, in_transform, blocks_params, dilations, groups, priors
         u, v = _f32c(u), _f32c(v)
         if tuple(u.shape) != (T, B, S, num_mix) or tuple(v.shape) != (T, B, S):
             raise ValueError("stcn_generate: u must be [T,B,S,num_mix] and v [T,B,S]")
-    n_scratch = lib.blvm_stcn_generate_scratch_floats(p.dil, p.C, S, p.n_blocks, p.n_out, p.latent, p.order, p.n, p.dense, num_mix, B)
-    scratch = torch.empty(max(int(n_scratch), 4), **f32)
+    n_scratch = _stcn_scratch_floats(p, S, num_mix, B)
+    if resume is None:
+        scratch = torch.empty(n_scratch, **f32)
+    else:
+        t0, x_in, scratch = resume
+        if scratch.dtype != torch.float32 or scratch.device != dev or scratch.numel() != n_scratch or not scratch.is_contiguous():
+            raise ValueError("stcn_generate_resume: the scratch buffer does not belong to these shapes")
+        x_in = _f32c(x_in)
+        if tuple(x_in.shape) != (B, 2, S):
+            raise ValueError("stcn_generate_resume: x_in must be [B,2,S]")
     x = torch.empty(B, T, S, **f32)
     zs, mus, sds = ([torch.empty(T, B, Z, **f32) for Z in p.latent_sizes] for _ in range(3))
     ptrs = lambda ts: (ctypes.c_void_p * len(ts))(*[ptr(t) for t in ts])  # noqa: E731
-    check(lib.blvm_stcn_generate(ptr(p.packed), p.dil, p.groups, p.n_blocks, p.n_out, p.latent, p.order, p.n, p.dense, B, p.C, S, num_mix, T,
-                                 inv_std, out_scale, sd_beta, sd_eps, slope, log_eps, ptrs(eps), ptr(u), ptr(v), ptr(x), ptrs(zs), ptrs(mus),
-                                 ptrs(sds), ptr(scratch), stream_ptr()), "blvm_stcn_generate")  # fmt: skip
-    return x, zs, mus, sds
+    args = (ptr(p.packed), p.dil, p.groups, p.n_blocks, p.n_out, p.latent, p.order, p.n, p.dense, B, p.C, S, num_mix, T, inv_std, out_scale,
+            sd_beta, sd_eps, slope, log_eps, ptrs(eps), ptr(u), ptr(v), ptr(x), ptrs(zs), ptrs(mus), ptrs(sds), ptr(scratch))  # fmt: skip
+    if resume is None:
+        check(lib.blvm_stcn_generate(*args, stream_ptr()), "blvm_stcn_generate")
+        return x, zs, mus, sds, scratch, None
+    x_state = torch.empty(B, 2, S, **f32)
+    check(lib.blvm_stcn_generate_resume(*args, int(t0), ptr(x_in), ptr(x_state), stream_ptr()), "blvm_stcn_generate_resume")
+    return x, zs, mus, sds, scratch, x_state
+
+
+def stcn_generate(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear,
+                  dense: bool, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float, slope: float,
+                  num_mix: int, log_eps: float, eps, u=None, v=None):
+    """K10d: T steps of ancestral sampling from the STCN for B rows in one launch (arguments as `stcn_generate_pack`).  eps[l]
+    [T,B,Z_l]; u [T,B,S,num_mix], v [T,B,S] uniform draws (None: the mode).  -> (x [B,T,S], z, mu, sd: lists of [T,B,Z_l])."""
+    weights = (causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear, dense)
+    return _stcn_generate_call(weights, B, T, S, inv_std, out_scale, sd_beta, sd_eps, slope, num_mix, log_eps, eps, u, v)[:4]
+
+
+def stcn_generate_start(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear,
+                        head_linear, dense: bool, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float,
+                        slope: float, num_mix: int, log_eps: float, eps, u=None, v=None):
+    """`stcn_generate`, which also hands back its scratch buffer: -> (x, z, mu, sd, scratch).  With the last two stacks of x (zero
+    stacks in front of step 0) the rings in scratch (`stcn_ring_views`) are the state after T steps (`stcn_generate_resume`)."""
+    weights = (causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear, dense)
+    return _stcn_generate_call(weights, B, T, S, inv_std, out_scale, sd_beta, sd_eps, slope, num_mix, log_eps, eps, u, v)[:5]
+
+
+def stcn_generate_resume(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear,
+                         head_linear, dense: bool, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float,
+                         slope: float, num_mix: int, log_eps: float, eps, u, v, t0: int, x_in, scratch):
+    """K10d from a state: `scratch` holds the rings after absolute step t0 - 1 (primed through `stcn_ring_views`, or an earlier
+    call's; updated in place), x_in [B,2,S] the two newest stacks.  eps, u, v are indexed from 0.
+    -> (x [B,T,S], z, mu, sd: lists of [T,B,Z_l], x_state [B,2,S])."""
+    weights = (causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear, dense)
+    x, zs, mus, sds, _, x_state = _stcn_generate_call(weights, B, T, S, inv_std, out_scale, sd_beta, sd_eps, slope, num_mix, log_eps, eps,
+                                                      u, v, resume=(t0, x_in, scratch))  # fmt: skip
+    return x, zs, mus, sds, x_state
+
+
+def _stcn_ints(v):
+    import ctypes
+
+    return (ctypes.c_int * len(v))(*[int(i) for i in v])
+
+
+def stcn_ring_views(scratch, dilations, n_out: int, latent_sizes, order, dense: bool, B: int, C: int, S: int, num_mix: int):
+    """The state inside a K10d scratch buffer as views: (rings: dilated block i's input over its last dilation_i steps [dilation_i,B,C],
+    orings: output block j's input at the last step [1,B,C])."""
+    off = int(load().blvm_stcn_generate_ring_offset_floats(C, S, len(dilations), n_out, _stcn_ints(latent_sizes), _stcn_ints(order),
+                                                           len(latent_sizes), int(bool(dense)), num_mix))  # fmt: skip
+    if off == 0:
+        raise _hip.BlvmHipError("blvm_stcn_generate: " + load().blvm_last_error().decode(errors="replace"))
+    rings = []
+    for d in [*dilations, *([1] * n_out)]:
+        rings.append(scratch[off : off + d * B * C].view(d, B, C))
+        off += d * B * C
+    return rings[: len(dilations)], rings[len(dilations) :]
+
+
+def stcn_generate_scratch_floats(dilations, n_out: int, latent_sizes, order, dense: bool, B: int, C: int, S: int, num_mix: int) -> int:
+    """Size of a K10d scratch buffer (a host computation: no device needed)."""
+    lib = load()
+    n = lib.blvm_stcn_generate_scratch_floats(_stcn_ints(dilations), C, S, len(dilations), n_out, _stcn_ints(latent_sizes), _stcn_ints(order),
+                                              len(latent_sizes), int(bool(dense)), num_mix, B)  # fmt: skip
+    if n == 0:
+        raise _hip.BlvmHipError("blvm_stcn_generate: " + lib.blvm_last_error().decode(errors="replace"))
+    return max(int(n), 4)
+
+
+def stcn_generate_scratch(dilations, n_out: int, latent_sizes, order, dense: bool, B: int, C: int, S: int, num_mix: int, device):
+    """An uninitialised K10d scratch buffer and its state views: -> (scratch, (rings, orings))."""
+    scratch = torch.empty(stcn_generate_scratch_floats(dilations, n_out, latent_sizes, order, dense, B, C, S, num_mix), device=device,
+                          dtype=torch.float32)  # fmt: skip
+    return scratch, stcn_ring_views(scratch, dilations, n_out, latent_sizes, order, dense, B, C, S, num_mix)
 
 
 def wavenet_stack(x, blocks_params, dilations, T_skip: int, inv_std: float, S: int, groups=None):

@@ -16,6 +16,10 @@
 // windows of the first output.  Under an all-zero past every block input is constant in time, so the prologue evaluates that
 // steady state once per stack (both taps on the same vector) and fills the rings with it.
 //
+// From a state (blvm_stcn_generate_resume: a prompt, or an earlier call): the rings and the two newest stacks ARE the state, so the
+// entry skips that prologue, loads sX from x_in [B,2,S], counts ring slots from t0 and hands sX back in x_state after the last step —
+// one branch, uniform over the grid.  The host primes the rings of a prompt with the time-parallel kernels (contract in the header).
+//
 // Widths: C and every latent size multiples of 16, 3 * num_mix <= 32, n <= 8, n_blocks, n_out <= 64.  S is any
 // positive stack size: the causal convolution is an MFMA product when 2 S is a multiple of 16 and a scalar loop otherwise (S = 1).
 // The packed image carries out_upsample zero-padded to a multiple of 16 rows and the head zero-padded to [32,32]; the kernel
@@ -32,6 +36,8 @@
 //   sUp  [16][8*32+4], sPar [16][8*32] (8 stacked samples per pass) alias it.
 // The n selected skips [16][C] do not fit beside these: they are parked in scratch ([n,B,C]) and read back by the same
 // workgroup after a barrier.
+#include <climits>
+
 #include "common.h"
 
 namespace blvm {
@@ -107,6 +113,10 @@ struct StcnArgs {
   float* rings;   // dilated block i: [dil_i,B,C] at B*C*sum(dil[:i])
   float* orings;  // output block j: [B,C] at j*B*C
   float* dskip;   // [n,B,C] the selected skips of the step
+  // the entry from a state: no steady-state prologue, the rings hold the blocks' inputs up to absolute step t0 - 1
+  int resume, t0;        // t0 reduced modulo every dilation by the host; 0 on the zero start
+  const float* x_in;     // [B,2,S] (previous stack, newest stack)
+  float* x_state;        // [B,2,S] the two newest stacks after the last step (may be x_in)
 };
 
 struct StcnLds {
@@ -158,6 +168,13 @@ __global__ __launch_bounds__(SG_NW * 64) void stcn_decode_kernel(StcnArgs a) {
   for (int i = tid; i < SG_ROWS * ldX; i += NT) sX[i] = 0.f;
   for (int i = tid; i < SG_ROWS * ldZ; i += NT) sZ[i] = 0.f;
   __syncthreads();
+  if (a.resume) {  // uniform over the grid: the two newest stacks of the state, rows >= B stay zero
+    for (int idx = tid; idx < SG_ROWS * 2 * S; idx += NT) {
+      const int r = idx / (2 * S), k = idx - r * 2 * S, tap = k / S, s = k - tap * S;
+      if (b0 + r < B) sX[r * ldX + 2 * s + tap] = a.x_in[(size_t)(b0 + r) * 2 * S + k];
+    }
+    __syncthreads();
+  }
 
   // causal conv on the two previous stacks -> 1x1 in_transform -> sH
   auto front = [&]() {
@@ -255,7 +272,7 @@ __global__ __launch_bounds__(SG_NW * 64) void stcn_decode_kernel(StcnArgs a) {
   };
 
   // ---- steady state under an all-zero past: both stacks
-  {
+  if (!a.resume) {
     front();
     float* qi = a.rings;
     for (int i = 0; i < a.n_blocks; ++i) {
@@ -274,7 +291,7 @@ __global__ __launch_bounds__(SG_NW * 64) void stcn_decode_kernel(StcnArgs a) {
       float* qi = a.rings;
       for (int i = 0; i < a.n_blocks; ++i) {
         const int lvl = a.level[i], d = a.dil[i];
-        block(a.L.blocks + (size_t)i * a.L.block_stride, qi, d, t % d, false, lvl >= 0 ? 2 : 0,
+        block(a.L.blocks + (size_t)i * a.L.block_stride, qi, d, (a.t0 + t) % d, false, lvl >= 0 ? 2 : 0,
               lvl >= 0 ? a.dskip + (size_t)lvl * B * C : nullptr, i + 1 < a.n_blocks);
         qi += (size_t)d * B * C;
       }
@@ -421,6 +438,12 @@ __global__ __launch_bounds__(SG_NW * 64) void stcn_decode_kernel(StcnArgs a) {
       __syncthreads();
     }
   }
+  if (a.resume) {  // the last update of sX is behind the barrier that ends the step
+    for (int idx = tid; idx < SG_ROWS * 2 * S; idx += NT) {
+      const int r = idx / (2 * S), k = idx - r * 2 * S, tap = k / S, s = k - tap * S;
+      if (b0 + r < B) a.x_state[(size_t)(b0 + r) * 2 * S + k] = sX[r * ldX + 2 * s + tap];
+    }
+  }
 }
 
 // Everything the entry points refuse, before anything is touched
@@ -466,11 +489,17 @@ extern "C" size_t blvm_stcn_generate_scratch_floats(const int* dilations, int C,
          (size_t)n_out * B * C + (size_t)n_latents * B * C;
 }
 
-extern "C" int blvm_stcn_generate(const float* packed, const int* dilations, const int* groups, int n_blocks, int n_out, const int* latent,
-                                  const int* order, int n_latents, int dense, int B, int C, int S, int num_mix, int T, float inv_std,
-                                  float out_scale, float sd_beta, float sd_eps, float slope, float log_eps, const float* const* eps,
-                                  const float* u, const float* v, float* x_out, float* const* z_out, float* const* mu_out,
-                                  float* const* sd_out, float* scratch, void* stream) {
+extern "C" size_t blvm_stcn_generate_ring_offset_floats(int C, int S, int n_blocks, int n_out, const int* latent, const int* order,
+                                                        int n_latents, int dense, int num_mix) {
+  return blvm_stcn_generate_pack_floats(C, S, n_blocks, n_out, latent, order, n_latents, dense, num_mix);  // the T16 copies mirror the image
+}
+
+// resume: the kernel starts from the rings in `scratch` and x_in at absolute step t0 and hands the two newest stacks back
+static int stcn_run(bool resume, const float* packed, const int* dilations, const int* groups, int n_blocks, int n_out, const int* latent,
+                    const int* order, int n_latents, int dense, int B, int C, int S, int num_mix, int T, float inv_std, float out_scale,
+                    float sd_beta, float sd_eps, float slope, float log_eps, const float* const* eps, const float* u, const float* v,
+                    float* x_out, float* const* z_out, float* const* mu_out, float* const* sd_out, float* scratch, int t0,
+                    const float* x_in, float* x_state, void* stream) {
   using namespace blvm;
   hipStream_t s = static_cast<hipStream_t>(stream);
   BLVM_REQUIRE(packed && dilations && groups && eps && x_out && z_out && mu_out && sd_out && scratch && aligned16(packed) && aligned16(scratch),
@@ -479,6 +508,10 @@ extern "C" int blvm_stcn_generate(const float* packed, const int* dilations, con
   BLVM_REQUIRE(B > 0 && T >= 0, "stcn_generate: need B > 0, T >= 0");
   BLVM_REQUIRE((u == nullptr) == (v == nullptr), "stcn_generate: u and v are given together (both NULL: the mode)");
   BLVM_REQUIRE(sd_beta > 0.f, "stcn_generate: the softplus beta must be positive");
+  if (resume) {
+    BLVM_REQUIRE(x_in && x_state, "stcn_generate_resume: NULL stack state");
+    BLVM_REQUIRE(t0 >= 0 && T < INT_MAX - t0, "stcn_generate_resume: t0 = %d, T = %d: need 0 <= t0, t0 + T < 2^31 - 1", t0, T);
+  }
   const int n = n_latents;
   StcnArgs a{};
   unsigned selected = 0;
@@ -500,7 +533,10 @@ extern "C" int blvm_stcn_generate(const float* packed, const int* dilations, con
   const StcnLds m = stcn_lds(C, S, a.L.zsum, a.L.zmax);
   const size_t lds = sizeof(float) * m.total;
   BLVM_REQUIRE(lds <= 160 * 1024, "stcn_generate: C=%d, S=%d, %d latent dimensions need %zu bytes of LDS (> 160 KB)", C, S, a.L.zsum, lds);
-  if (T == 0) return BLVM_OK;
+  if (T == 0) {
+    if (resume && x_state != x_in) BLVM_HIP(hipMemcpyAsync(x_state, x_in, sizeof(float) * 2 * S * B, hipMemcpyDeviceToDevice, s));
+    return BLVM_OK;
+  }
 
   a.w = packed;
   a.wt = scratch;
@@ -542,9 +578,29 @@ extern "C" int blvm_stcn_generate(const float* packed, const int* dilations, con
   a.rings = scratch + a.L.total;
   a.orings = a.rings + stcn_ring_floats(dilations, n_blocks, B, C);
   a.dskip = a.orings + (size_t)n_out * B * C;
+  a.resume = resume ? 1 : 0; a.t0 = resume ? t0 : 0; a.x_in = x_in; a.x_state = x_state;
   auto kern = stcn_decode_kernel;
   if (lds > 64 * 1024) BLVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)((B + SG_ROWS - 1) / SG_ROWS)), dim3(SG_NW * 64), lds, s, a);
   BLVM_CHECK_LAUNCH("stcn_generate");
   return BLVM_OK;
+}
+
+extern "C" int blvm_stcn_generate(const float* packed, const int* dilations, const int* groups, int n_blocks, int n_out, const int* latent,
+                                  const int* order, int n_latents, int dense, int B, int C, int S, int num_mix, int T, float inv_std,
+                                  float out_scale, float sd_beta, float sd_eps, float slope, float log_eps, const float* const* eps,
+                                  const float* u, const float* v, float* x_out, float* const* z_out, float* const* mu_out,
+                                  float* const* sd_out, float* scratch, void* stream) {
+  return stcn_run(false, packed, dilations, groups, n_blocks, n_out, latent, order, n_latents, dense, B, C, S, num_mix, T, inv_std, out_scale,
+                  sd_beta, sd_eps, slope, log_eps, eps, u, v, x_out, z_out, mu_out, sd_out, scratch, 0, nullptr, nullptr, stream);
+}
+
+extern "C" int blvm_stcn_generate_resume(const float* packed, const int* dilations, const int* groups, int n_blocks, int n_out,
+                                         const int* latent, const int* order, int n_latents, int dense, int B, int C, int S, int num_mix,
+                                         int T, float inv_std, float out_scale, float sd_beta, float sd_eps, float slope, float log_eps,
+                                         const float* const* eps, const float* u, const float* v, float* x_out, float* const* z_out,
+                                         float* const* mu_out, float* const* sd_out, float* scratch, int t0, const float* x_in,
+                                         float* x_state, void* stream) {
+  return stcn_run(true, packed, dilations, groups, n_blocks, n_out, latent, order, n_latents, dense, B, C, S, num_mix, T, inv_std, out_scale,
+                  sd_beta, sd_eps, slope, log_eps, eps, u, v, x_out, z_out, mu_out, sd_out, scratch, t0, x_in, x_state, stream);
 }

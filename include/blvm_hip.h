@@ -546,6 +546,32 @@ int blvm_stcn_generate(const float* packed, const int* dilations, const int* gro
                        const float* u, const float* v, float* x_out, float* const* z_out, float* const* mu_out,
                        float* const* sd_out, float* scratch, void* stream);
 
+/* K10d  The same sampling from a given state: continuing a prompt, or an earlier call (generation in chunks).
+ *   The state after absolute step t0 - 1 is (a) the rings in scratch, from float offset
+ *   blvm_stcn_generate_ring_offset_floats(...) (= the packed image's size; the operand copies lie below it): dilated block i's input
+ *   over steps t0 - dilation_i .. t0 - 1 as [dilation_i,B,C], step tau in slot tau mod dilation_i, block after block; then output
+ *   block j's input at step t0 - 1 as [B,C], j = 0 .. n_out-1; then the selected skips [n_latents,B,C], which are no state; and
+ *   (b) the two newest stacks x_in [B,2,S] = (x_{t0-2}, x_{t0-1}).  Step tau of dilated block 0's input is in_transform(causal conv
+ *   of the stacks x_{tau-2}, x_{tau-1}); of output block 0's, the output in_transform of cat(z_tau) (dense) or z_tau[0]; stacks and
+ *   latents in front of step 0 are zero.  blvm_wavenet_decode_ring_fill (K10c) serves these rings too: they have its layout.
+ *   blvm_stcn_generate_resume: arguments as blvm_stcn_generate; no steady-state fill, step t of the call is absolute step t0 + t
+ *     (t0 >= 0; only t0 mod dilation_i matters; t0 + T < 2^31 - 1); eps, u, v and every output are indexed from 0 for the call.
+ *     The operand copies at the head of scratch and the selected skips are rewritten on every call (the weights may change between
+ *     calls, the shapes may not; results do not depend on what those regions or the outputs held); the ring region is read and
+ *     updated in place.  x_state [B,2,S] (=): the two newest stacks after the last step (may be x_in itself); with scratch it is the
+ *     state after t0 + T steps.  T = 0: x_in is copied to x_state on the stream and nothing else is launched.  Refuses whatever
+ *     blvm_stcn_generate refuses, NULL x_in / x_state and t0 < 0 — before a buffer is touched.
+ *   After blvm_stcn_generate the rings in its scratch are the state after T steps: t0 = T, x_in = the last two stacks of x_out (zero
+ *     stacks in front of step 0). */
+size_t blvm_stcn_generate_ring_offset_floats(int C, int S, int n_blocks, int n_out, const int* latent, const int* order,
+                                             int n_latents, int dense, int num_mix);
+int blvm_stcn_generate_resume(const float* packed, const int* dilations, const int* groups, int n_blocks, int n_out,
+                              const int* latent, const int* order, int n_latents, int dense, int B, int C, int S, int num_mix,
+                              int T, float inv_std, float out_scale, float sd_beta, float sd_eps, float slope, float log_eps,
+                              const float* const* eps, const float* u, const float* v, float* x_out, float* const* z_out,
+                              float* const* mu_out, float* const* sd_out, float* scratch, int t0, const float* x_in,
+                              float* x_state, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * K5  RSSM cell of the Clockwork-VAE over a sequence (forward + BPTT).  Replaces the per-level time loop
  *     `blvm/models/clockwork_vae/clockwork_vae.py:272-281` over `RSSMCell.forward` (`blvm/modules/rssm.py:79-104`).
