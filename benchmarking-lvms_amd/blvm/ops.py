@@ -4,6 +4,7 @@ hot path, and no CPU fallback (``_hip.ptr`` refuses CPU tensors).
 
 Layout convention: sequence tensors are time-major ``[T', B, F]``.
 """
+import ctypes
 from typing import List, Optional, Sequence
 
 import torch
@@ -24,6 +25,11 @@ seq_timer_hook = None
 def _tick(tag):
     if seq_timer_hook is not None:
         seq_timer_hook(tag)
+
+
+def _c_ints(v):
+    """A host array of C ints from any sequence of integers."""
+    return (ctypes.c_int * len(v))(*[int(i) for i in v])
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -63,8 +69,6 @@ def upload_i32(host, device):
 def wgrad_group(jobs, rows: int):
     """Weight (+ bias) gradients over the same `rows` as ONE launch (blvm_wgrad_group_f32): jobs = [(D [rows, N], X [rows, K], dW [N, K]
     or None, db [N] or None), ...], each dW += D^T X, db += D.sum(0); D and X may be row-strided views."""
-    import ctypes
-
     jobs = [j for j in jobs if j[2] is not None or j[3] is not None]
     if not jobs:
         return
@@ -602,8 +606,6 @@ def vrnn_decode(enc_lin, cell_params, dec_lin, lik_lin, x0, h0, eps, u, v, S, H,
         w.enc_w[i], w.enc_b[i] = ptr(keep[2 * i]), ptr(keep[2 * i + 1])
         w.dec_w[i], w.dec_b[i] = ptr(keep[6 + 2 * i]), ptr(keep[6 + 2 * i + 1])
     w.lik_w, w.lik_b = ptr(keep[12]), ptr(keep[13])
-    import ctypes
-
     w.cell = ctypes.pointer(cw)
     x0, eps = _f32c(x0), _f32c(eps)
     h0 = _f32c(h0) if h0 is not None else None
@@ -753,8 +755,6 @@ def lstm_sequence(inp, h0, c0, lens_dev, Wih, Whh, bih, bhh):
 
 def lstm_decode_weights(emb_lin, lstm, dec_lin, lik_lin):
     """-> (struct BlvmLstmDecodeWeights, what must stay alive while it is used)."""
-    import ctypes
-
     L = lstm.num_layers
     keep = [_f32c(t) for lin in (*emb_lin, *dec_lin, lik_lin) for t in (lin.weight, lin.bias)]
     lk = [[_f32c(getattr(lstm, f"{n}_l{l}")) for l in range(L)] for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
@@ -773,8 +773,6 @@ def lstm_generate(emb_lin, lstm, dec_lin, lik_lin, x0, h0, c0, u, v, S, H, num_m
     3 nn.Linear each; lstm: the nn.LSTM (parameter container, input size H); lik_lin the DMoL head's Linear.  x0 [B,S]; h0, c0
     [num_layers,B,H] or None (zeros); u [T,B,S,num_mix], v [T,B,S] the sampler's draws (both None: the mode, `T` then says how many
     steps).  -> (x [B,T,S], h_n, c_n [num_layers,B,H])."""
-    import ctypes
-
     lib = load()
     L, B, dev = lstm.num_layers, x0.shape[0], x0.device
     if (u is None) != (v is None) or (u is None and T is None):
@@ -872,8 +870,6 @@ def srnn_generate(enc_lin, gru, chain_params, dec_lin, lik_lin, x0, d0, z0, eps,
     enc_lin / dec_lin: 3 nn.Linear each; gru: the forward nn.GRU (parameter container); chain_params in `_SRNN_PARAM_ORDER`;
     lik_lin the DMoL head's Linear.  x0 [B,S]; d0 [B,R], z0 [B,Z] or None; eps [T,B,Z]; u [T,B,S,num_mix] / v [T,B,S] (None: the
     mode).  -> (x [B,T,S], d_T [B,R], z [T,B,Z])."""
-    import ctypes
-
     lib = load()
     T, B = eps.shape[0], x0.shape[0]
     dev = x0.device
@@ -1052,8 +1048,6 @@ class _WaveNetStackFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, dilations, groups, T_skip, inv_std, S, *params):
-        import ctypes
-
         x = _f32c(x)
         params = tuple(_f32c(p) for p in params)
         L, B, C = x.shape
@@ -1079,8 +1073,6 @@ class _WaveNetStackFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *d_skips):
-        import ctypes
-
         dilations, groups, T_skip, inv_std, S, L, B, C, n = ctx.cfg
         x, acts, reserve, *params = ctx.saved_tensors
         lib = load()
@@ -1119,8 +1111,6 @@ def wavenet_block_step(x2, params, inv_std: float, S: int, skip_acc, want_output
 
 def _wavenet_decode_pack(causal, in_transform, blocks_params, dilations, out_linear, head_linear, num_mix: int):
     """The packed weight image of K10c and its sizes: -> (lib, C, S, O, device, packed, dilations as a C array)."""
-    import ctypes
-
     lib = load()
     C, S, O = in_transform[0].shape[0], blocks_params[0][2].shape[0] - in_transform[0].shape[0], out_linear[0].shape[0]
     dev = causal[0].device
@@ -1134,7 +1124,7 @@ def _wavenet_decode_pack(causal, in_transform, blocks_params, dilations, out_lin
     packed = torch.cat([_f32c(p).reshape(-1) for p in parts])
     if packed.numel() != lib.blvm_wavenet_decode_pack_floats(C, S, O, len(blocks_params)):
         raise ValueError("wavenet_decode: parameter shapes do not match the packed layout")
-    return lib, C, S, O, dev, packed, (ctypes.c_int * len(dilations))(*dilations)
+    return lib, C, S, O, dev, packed, _c_ints(dilations)
 
 
 def _wavenet_decode_draws(u, v, n_frames: int, B: int, num_mix: int):
@@ -1179,10 +1169,7 @@ def wavenet_ring_views(scratch, dilations, B: int, C: int, S: int):
 
 def wavenet_decode_scratch(dilations, B: int, C: int, S: int, device):
     """An uninitialised K10c scratch buffer and its ring views."""
-    import ctypes
-
-    dil = (ctypes.c_int * len(dilations))(*dilations)
-    scratch = torch.empty(load().blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S), device=device, dtype=torch.float32)
+    scratch = torch.empty(load().blvm_wavenet_decode_scratch_floats(_c_ints(dilations), len(dilations), B, C, S), device=device, dtype=torch.float32)
     return scratch, wavenet_ring_views(scratch, dilations, B, C, S)
 
 
@@ -1252,7 +1239,6 @@ def stcn_generate_pack(causal, in_transform, blocks_params, dilations, groups, p
     out_in / up_linear / head_linear = (weight, bias); blocks_params as for wavenet_stack; groups[i] = the latent level that reads
     block i's skip (or -1); priors[l] = (the three nn.Linear of the mean MLP, those of the sd MLP); order = the levels in visiting
     order.  -> namespace(lib, packed, C, dil, groups, latent, order, n_blocks, n_out, n, dense, latent_sizes)."""
-    import ctypes
     from types import SimpleNamespace
 
     lib = load()
@@ -1274,9 +1260,9 @@ def stcn_generate_pack(causal, in_transform, blocks_params, dilations, groups, p
     parts += [uw, z(up_rows - S * F, uw.shape[1]), ub, z(up_rows - S * F)]
     parts += [torch.nn.functional.pad(hw.detach(), (0, 32 - F, 0, 32 - F)), hb, z(32 - F)]
     packed = torch.cat([_f32c(p.detach()).reshape(-1) for p in parts])
-    ints = lambda v: (ctypes.c_int * len(v))(*[int(i) for i in v])  # noqa: E731
     latent_sizes = [int(mu[2].weight.shape[0]) for mu, _ in priors]
-    ns = SimpleNamespace(lib=lib, packed=packed, C=C, dil=ints(dilations), groups=ints(groups), latent=ints(latent_sizes), order=ints(order),
+    ns = SimpleNamespace(lib=lib, packed=packed, C=C, dil=_c_ints(dilations), groups=_c_ints(groups), latent=_c_ints(latent_sizes),
+                         order=_c_ints(order),
                          n_blocks=len(dilations), n_out=len(out_blocks_params), n=len(priors), dense=int(bool(dense)), latent_sizes=latent_sizes)  # fmt: skip
     want = lib.blvm_stcn_generate_pack_floats(C, S, ns.n_blocks, ns.n_out, ns.latent, ns.order, ns.n, ns.dense, num_mix)
     if want == 0:
@@ -1295,8 +1281,6 @@ def _stcn_generate_call(weights, B: int, T: int, S: int, inv_std: float, out_sca
                         num_mix: int, log_eps: float, eps, u, v, resume=None):
     """`blvm_stcn_generate`, or `blvm_stcn_generate_resume` with resume = (t0, x_in [B,2,S], scratch).
     -> (x [B,T,S], z, mu, sd: lists of [T,B,Z_l], scratch, x_state [B,2,S] or None)."""
-    import ctypes
-
     p = stcn_generate_pack(*weights, S, num_mix)
     lib, dev = p.lib, p.packed.device
     f32 = dict(device=dev, dtype=torch.float32)
@@ -1360,16 +1344,10 @@ def stcn_generate_resume(causal, in_transform, blocks_params, dilations, groups,
     return x, zs, mus, sds, x_state
 
 
-def _stcn_ints(v):
-    import ctypes
-
-    return (ctypes.c_int * len(v))(*[int(i) for i in v])
-
-
 def stcn_ring_views(scratch, dilations, n_out: int, latent_sizes, order, dense: bool, B: int, C: int, S: int, num_mix: int):
     """The state inside a K10d scratch buffer as views: (rings: dilated block i's input over its last dilation_i steps [dilation_i,B,C],
     orings: output block j's input at the last step [1,B,C])."""
-    off = int(load().blvm_stcn_generate_ring_offset_floats(C, S, len(dilations), n_out, _stcn_ints(latent_sizes), _stcn_ints(order),
+    off = int(load().blvm_stcn_generate_ring_offset_floats(C, S, len(dilations), n_out, _c_ints(latent_sizes), _c_ints(order),
                                                            len(latent_sizes), int(bool(dense)), num_mix))  # fmt: skip
     if off == 0:
         raise _hip.BlvmHipError("blvm_stcn_generate: " + load().blvm_last_error().decode(errors="replace"))
@@ -1383,7 +1361,7 @@ def stcn_ring_views(scratch, dilations, n_out: int, latent_sizes, order, dense: 
 def stcn_generate_scratch_floats(dilations, n_out: int, latent_sizes, order, dense: bool, B: int, C: int, S: int, num_mix: int) -> int:
     """Size of a K10d scratch buffer (a host computation: no device needed)."""
     lib = load()
-    n = lib.blvm_stcn_generate_scratch_floats(_stcn_ints(dilations), C, S, len(dilations), n_out, _stcn_ints(latent_sizes), _stcn_ints(order),
+    n = lib.blvm_stcn_generate_scratch_floats(_c_ints(dilations), C, S, len(dilations), n_out, _c_ints(latent_sizes), _c_ints(order),
                                               len(latent_sizes), int(bool(dense)), num_mix, B)  # fmt: skip
     if n == 0:
         raise _hip.BlvmHipError("blvm_stcn_generate: " + lib.blvm_last_error().decode(errors="replace"))

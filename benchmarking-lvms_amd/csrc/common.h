@@ -1,6 +1,7 @@
 // common.h — shared host/device helpers for libblvm_hip (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -66,6 +67,27 @@ inline hipError_t copy_or_zero(void* dst, const void* src, size_t bytes, hipStre
 }
 inline hipError_t copy_or_zero_2d(void* dst, size_t dpitch, const void* src, size_t width, size_t rows, hipStream_t s) {
   return src ? hipMemcpy2DAsync(dst, dpitch, src, width, width, rows, hipMemcpyDeviceToDevice, s) : hipMemset2DAsync(dst, dpitch, 0, width, rows, s);
+}
+
+// ---- host side of the ring decoders' entry points (wavenet_decode.hip, stcn_decode.hip) ----
+// floats of the rings of n gated blocks: block i keeps its own input over the last dilations[i] frames, [dil_i,B,C]
+inline size_t ring_floats(const int* dilations, int n, int B, int C) {
+  size_t frames = 0;
+  for (int i = 0; i < n; ++i) frames += (size_t)(dilations[i] > 0 ? dilations[i] : 0);
+  return frames * B * C;
+}
+
+// the arguments of an entry from a state: `who` the entry, `state` what x_in / x_state hold, `count` the name of the step count T
+inline int check_resume(const char* who, const char* state, const char* count, int t0, int T, const void* x_in, const void* x_state) {
+  BLVM_REQUIRE(x_in && x_state, "%s: NULL %s state", who, state);
+  BLVM_REQUIRE(t0 >= 0 && T < INT_MAX - t0, "%s: t0 = %d, %s = %d: need 0 <= t0, t0 + %s < 2^31 - 1", who, t0, count, T, count);
+  return BLVM_OK;
+}
+
+// zero steps from a state: the state goes back as it came
+inline int hand_back_state(float* x_state, const float* x_in, size_t floats, hipStream_t s) {
+  if (x_state != x_in) BLVM_HIP(hipMemcpyAsync(x_state, x_in, sizeof(float) * floats, hipMemcpyDeviceToDevice, s));
+  return BLVM_OK;
 }
 
 // beta of the Gaussian heads' softplus (softplus_beta below): ln2 / (initial_sd - eps), initial_sd = 1

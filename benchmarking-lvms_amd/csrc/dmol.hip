@@ -15,6 +15,7 @@
 // belong to one utterance (always true for stack sizes that are multiples of 64) reduces with DPP shuffles and
 // issues ONE fp64 atomic; otherwise lanes fall back to per-lane atomics.
 #include "common.h"
+#include "decode_tiles.h"
 
 namespace blvm {
 namespace {
@@ -877,21 +878,13 @@ __global__ __launch_bounds__(256) void mix_sample_kernel(const float* __restrict
   if (f >= n) return;
   const int nm = K > 0 ? K : num_mix;
   const float* p = par + f * (3 * nm);
-  int best = 0;
-  float bv = -INFINITY;
-#pragma unroll
-  for (int m = 0; m < nm; ++m) {
-    float s = p[m];
-    if (u != nullptr) s -= logf(-logf(u[f * nm + m]));
-    if (s > bv) { bv = s; best = m; }  // first maximum, as torch.argmax
-  }
+  const int best = mix_pick<K>(p, nm, u != nullptr ? u + f * nm : nullptr);  // both kinds pick alike (decode_tiles.h)
   const float loc = p[nm + best], raw = p[2 * nm + best];
   float x = loc;
   if (v != nullptr) {
     const float vv = v[f];
     if (kind == 0) {
-      x = loc + expf(fmaxf(raw, log_eps)) * (logf(vv) - logf(1.f - vv));
-      x = fminf(fmaxf(x, -1.f), 1.f);
+      x = logistic_draw(loc, raw, vv, log_eps);
     } else {
       x = loc + (sd_beta > 0.f ? softplus_beta(raw, sd_beta, 1.f / sd_beta) + sd_eps : raw) * vv;  // sd_beta == 0: raw IS the sd
     }

@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "decode_tiles.h"
 
 namespace blvm {
 namespace pchain {
@@ -1116,7 +1117,7 @@ __device__ __forceinline__ void tile_lstm(const float* X, const float* Wih, int 
 // Sampling from a DMoL head during generation (`VRNN.generate`, blvm/models/vrnn.py:371-434: likelihood(dec) -> sample): a tile =
 // 16 utterances x 4 samples of one frame stack.  dec [B, S*F] (F = 3 * num_mix = 30 head inputs per sample, row-major, polled words:
 // the last decoder layer of this step) -> per sample the head's Linear(F -> F) -> Gumbel-max component pick with u, clamped
-// logistic draw with v (dmol.hip mix_sample_kernel; both null: the mode) -> x [B, ldx] (plain) and the T16 copy the next step's
+// logistic draw with v (decode_tiles.h; both null: the mode) -> x [B, ldx] (plain) and the T16 copy the next step's
 // encoder multiplies.  Wave w computes head outputs 4w .. 4w+3 of all 64 (utterance, sample) pairs (weights wave-uniform); wave 0
 // then draws.  `lds`: >= 16*4*F + 64*32 floats.
 template <int NW>
@@ -1175,20 +1176,9 @@ __device__ __forceinline__ void tile_dmol_sample(const float* dec, int ldd, cons
     if (row < B) {
       const float* p = outp + lane * 32;
       const size_t f = (size_t)row * S + smp;
-      int best = 0;
-      float bv = -INFINITY;
-      for (int m = 0; m < num_mix; ++m) {
-        float sc = p[m];
-        if (u != nullptr) sc -= logf(-logf(u[f * num_mix + m]));
-        if (sc > bv) { bv = sc; best = m; }  // first maximum, as torch.argmax
-      }
-      const float loc = p[num_mix + best], raw = p[2 * num_mix + best];
-      float x = loc;
-      if (v != nullptr) {
-        const float vv = v[f];
-        x = loc + expf(fmaxf(raw, log_eps)) * (logf(vv) - logf(1.f - vv));
-        x = fminf(fmaxf(x, -1.f), 1.f);
-      }
+      const int best = mix_pick(p, num_mix, u != nullptr ? u + f * num_mix : nullptr);
+      float x = p[num_mix + best];
+      if (v != nullptr) x = logistic_draw(x, p[2 * num_mix + best], v[f], log_eps);
       put(xo, r0, s0 & ~15, row, smp, x);
     }
   }

@@ -10,7 +10,8 @@
 // This is a chain of ~2 (n_blocks + n_out) + 3 n dependent small products per step — pure latency — so, as in K10c
 // (wavenet_decode.hip), one workgroup owns 16 rows (the M of v_mfma_f32_16x16x4_f32) and never leaves the kernel: activations
 // in LDS, every block a ring buffer [dil_i,B,C] of its own input in scratch, weights streamed from their T16 operand copies.
-// Rows are independent: no inter-workgroup traffic.
+// Rows are independent: no inter-workgroup traffic.  The gated block, the tile layer and the draw are the ones K10c uses
+// (decode_tiles.h).
 //
 // Zero past: `forward` pads x with receptive_field zero stacks and the output stack's input with n_out zero frames, exactly the
 // windows of the first output.  Under an all-zero past every block input is constant in time, so the prologue evaluates that
@@ -36,9 +37,8 @@
 //   sUp  [16][8*32+4], sPar [16][8*32] (8 stacked samples per pass) alias it.
 // The n selected skips [16][C] do not fit beside these: they are parked in scratch ([n,B,C]) and read back by the same
 // workgroup after a barrier.
-#include <climits>
-
 #include "common.h"
+#include "decode_tiles.h"
 
 namespace blvm {
 namespace {
@@ -158,11 +158,10 @@ __global__ __launch_bounds__(SG_NW * 64) void stcn_decode_kernel(StcnArgs a) {
   float* sUp = smem + m.oR2;
   float* sPar = smem + m.oPar;
 
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, cc = lane & 15;
+  const int tid = threadIdx.x, wave = tid >> 6;
   const int b0 = blockIdx.x * SG_ROWS;
   const float* w = a.w;
   const float* wt = a.wt;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const int CT = C / 16;
 
   for (int i = tid; i < SG_ROWS * ldX; i += NT) sX[i] = 0.f;
@@ -179,13 +178,7 @@ __global__ __launch_bounds__(SG_NW * 64) void stcn_decode_kernel(StcnArgs a) {
   // causal conv on the two previous stacks -> 1x1 in_transform -> sH
   auto front = [&]() {
     if ((2 * S) % 16 == 0) {
-      for (int tile = wave; tile < CT; tile += NW) {
-        const f32x4 acc = wave_gemm16<1, true>(sX, ldX, 0, SG_ROWS, wt + a.L.causal_w, 2 * S, tile * 16, 2 * S, 0, zero4);
-        const int o = tile * 16 + cc;
-        const float bias = w[a.L.causal_b + o];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sAct[(4 * q + r) * ldA + o] = acc[r] + bias;
-      }
+      tile_layer<NW, true>(sX, ldX, wt + a.L.causal_w, 2 * S, 0, CT, w + a.L.causal_b, [&](int row, int o, float val) { sAct[row * ldA + o] = val; });
     } else {
       const float* cw = w + a.L.causal_w;
       for (int idx = tid; idx < SG_ROWS * C; idx += NT) {
@@ -196,79 +189,28 @@ __global__ __launch_bounds__(SG_NW * 64) void stcn_decode_kernel(StcnArgs a) {
       }
     }
     __syncthreads();
-    for (int tile = wave; tile < CT; tile += NW) {
-      const f32x4 acc = wave_gemm16<1, true>(sAct, ldA, 0, SG_ROWS, wt + a.L.in_w, C, tile * 16, C, 0, zero4);
-      const int o = tile * 16 + cc;
-      const float bias = w[a.L.in_b + o];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sH[(4 * q + r) * ldH + o] = acc[r] + bias;
-    }
+    tile_layer<NW, true>(sAct, ldA, wt + a.L.in_w, C, 0, CT, w + a.L.in_b, [&](int row, int o, float val) { sH[row * ldH + o] = val; });
     __syncthreads();
   };
 
   // 1x1 in_transform of the output stack on sZ -> sH
   auto out_in = [&]() {
-    for (int tile = wave; tile < CT; tile += NW) {
-      const f32x4 acc = wave_gemm16<1, true>(sZ, ldZ, 0, SG_ROWS, wt + a.L.oin_w, a.L.zin, tile * 16, a.L.zin, 0, zero4);
-      const int o = tile * 16 + cc;
-      const float bias = w[a.L.oin_b + o];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sH[(4 * q + r) * ldH + o] = acc[r] + bias;
-    }
+    tile_layer<NW, true>(sZ, ldZ, wt + a.L.oin_w, a.L.zin, 0, CT, w + a.L.oin_b, [&](int row, int o, float val) { sH[row * ldH + o] = val; });
     __syncthreads();
   };
 
-  // One gated residual block (packed offset boff) on the frame in sH; its ring qi [d,B,C].  steady: both taps = sH and the ring is
-  // filled with sH.  skip_mode 0: no skip half; 1: added into sSkip; 2: stored to gskip [B,C].  need_res: the residual half.
-  // A ring element is read and rewritten by the same thread.
+  // One gated residual block (decode_tiles.h; packed offset boff) on the frame in sH; its ring qi [d,B,C].  steady: both taps = sH
+  // and the ring is filled with sH.  skip_mode 0: no skip half; 1: added into sSkip; 2: stored to gskip [B,C].  need_res: the
+  // residual half.
+  const GateLds gl = {sH, ldH, sV, ldV, sPre, ldP, sAct, ldA};
   auto block = [&](size_t boff, float* qi, int d, int slot, bool steady, int skip_mode, float* gskip, bool need_res) {
     const float* bw = w + boff;
     const float* bt = wt + boff;
-    for (int idx = tid; idx < SG_ROWS * C; idx += NT) {
-      const int r = idx / C, c = idx - r * C;
-      const float cur = sH[r * ldH + c];
-      float old = cur;
-      if (b0 + r < B) {
-        if (steady) {
-          for (int s = 0; s < d; ++s) qi[((size_t)s * B + b0 + r) * C + c] = cur;
-        } else {
-          float* p = qi + ((size_t)slot * B + b0 + r) * C + c;
-          old = *p;
-          *p = cur;
-        }
-      }
-      sV[r * ldV + 2 * c] = old;
-      sV[r * ldV + 2 * c + 1] = cur;
-    }
-    __syncthreads();
-    for (int tile = wave; tile < 2 * CT; tile += NW) {
-      const f32x4 acc = wave_gemm16<1, true>(sV, ldV, 0, SG_ROWS, bt, 2 * C, tile * 16, 2 * C, 0, zero4);
-      const int o = tile * 16 + cc;
-      const float bias = bw[a.L.conv_b + o];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sPre[(4 * q + r) * ldP + o] = acc[r] + bias;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < SG_ROWS * C; idx += NT) {
-      const int r = idx / C, c = idx - r * C;
-      sAct[r * ldA + c] = tanhf(sPre[r * ldP + c]) * sigmoidf_(sPre[r * ldP + C + c]);
-    }
-    __syncthreads();
-    const int tile_lo = need_res ? 0 : CT, tile_hi = skip_mode ? 2 * CT : CT;
-    for (int tile = tile_lo + wave; tile < tile_hi; tile += NW) {
-      const f32x4 acc = wave_gemm16<1, true>(sAct, ldA, 0, SG_ROWS, bt + a.L.rs_w, C, tile * 16, C, 0, zero4);
-      const int o = tile * 16 + cc;
-      const float bias = bw[a.L.rs_b + o];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 4 * q + r;
-        const float val = acc[r] + bias;
-        if (o < C) sH[row * ldH + o] = (val + sH[row * ldH + o]) * a.inv_std;
-        else if (skip_mode == 1) sSkip[row * ldK + (o - C)] += val;
-        else if (b0 + row < B) gskip[(size_t)(b0 + row) * C + (o - C)] = val;
-      }
-    }
-    __syncthreads();
+    gated_ring_block<NW>(gl, C, bt, bw + a.L.conv_b, bt + a.L.rs_w, bw + a.L.rs_b, qi, d, slot, steady, b0, B, a.inv_std, need_res ? 0 : CT,
+                         skip_mode ? 2 * CT : CT, [&](int row, int j, float val) {
+                           if (skip_mode == 1) sSkip[row * ldK + j] += val;
+                           else if (b0 + row < B) gskip[(size_t)(b0 + row) * C + j] = val;
+                         });
   };
 
   // ---- steady state under an all-zero past: both stacks
@@ -317,39 +259,21 @@ __global__ __launch_bounds__(SG_NW * 64) void stcn_decode_kernel(StcnArgs a) {
       for (int tile = wave; tile < 2 * CT; tile += NW) {  // layer 1 of both branches: sV -> sPre (mu | sd)
         const int br = tile >= CT, tt = tile - br * CT;
         const size_t P = a.L.prior[l] + br * bs;
-        f32x4 acc = wave_gemm16<1, true>(sV, ldV, 0, SG_ROWS, wt + P, kin, tt * 16, kin, 0, zero4);
-        const int o = tt * 16 + cc;
-        const float bias = w[P + o_b0 + o];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float val = acc[r] + bias;
-          sPre[(4 * q + r) * ldP + br * C + o] = val > 0.f ? val : a.slope * val;
-        }
+        tile16<true>(sV, ldV, wt + P, kin, tt, w + P + o_b0, [&](int row, int o, float val) { sPre[row * ldP + br * C + o] = val > 0.f ? val : a.slope * val; });
       }
       __syncthreads();
       for (int tile = wave; tile < 2 * CT; tile += NW) {  // layer 2: sPre -> sAct (mu), sH (sd)
         const int br = tile >= CT, tt = tile - br * CT;
         const size_t P = a.L.prior[l] + br * bs;
-        f32x4 acc = wave_gemm16<1, true>(sPre + br * C, ldP, 0, SG_ROWS, wt + P + o_w1, C, tt * 16, C, 0, zero4);
-        const int o = tt * 16 + cc;
-        const float bias = w[P + o_b1 + o];
         float* dst = br ? sH : sAct;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float val = acc[r] + bias;
-          dst[(4 * q + r) * ldA + o] = val > 0.f ? val : a.slope * val;
-        }
+        tile16<true>(sPre + br * C, ldP, wt + P + o_w1, C, tt, w + P + o_b1, [&](int row, int o, float val) { dst[row * ldA + o] = val > 0.f ? val : a.slope * val; });
       }
       __syncthreads();
       const int ZT = Zl / 16;
       for (int tile = wave; tile < 2 * ZT; tile += NW) {  // layer 3: raw (mu | sd) -> sPre
         const int br = tile >= ZT, tt = tile - br * ZT;
         const size_t P = a.L.prior[l] + br * bs;
-        f32x4 acc = wave_gemm16<1, true>(br ? sH : sAct, ldA, 0, SG_ROWS, wt + P + o_w2, C, tt * 16, C, 0, zero4);
-        const int o = tt * 16 + cc;
-        const float bias = w[P + o_b2 + o];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sPre[(4 * q + r) * ldP + br * Zl + o] = acc[r] + bias;
+        tile16<true>(br ? sH : sAct, ldA, wt + P + o_w2, C, tt, w + P + o_b2, [&](int row, int o, float val) { sPre[row * ldP + br * Zl + o] = val; });
       }
       __syncthreads();
       for (int idx = tid; idx < SG_ROWS * Zl; idx += NT) {
@@ -389,47 +313,27 @@ __global__ __launch_bounds__(SG_NW * 64) void stcn_decode_kernel(StcnArgs a) {
         const int pw = SG_HEAD - F, r = idx / (SG_CHUNK * pw), rem = idx - r * SG_CHUNK * pw;
         sUp[r * ldU + (rem / pw) * SG_HEAD + F + rem % pw] = 0.f;
       }
-      for (int tile = col_lo / 16 + wave; tile < (col_hi + 15) / 16; tile += NW) {
-        const f32x4 acc = wave_gemm16<1, true>(sSkip, ldK, 0, SG_ROWS, wt + a.L.up_w, C, tile * 16, C, 0, zero4);
-        const int col = tile * 16 + cc;
-        if (col >= col_lo && col < col_hi) {
-          const float bias = w[a.L.up_b + col];
-          const int sl = col / F - s0, f = col % F;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) sUp[(4 * q + r) * ldU + sl * SG_HEAD + f] = fmaxf(acc[r] + bias, 0.f);
-        }
-      }
+      // (a tile may straddle the chunk's columns; the bias region is padded to whole tiles like the matrix)
+      tile_layer<NW, true>(sSkip, ldK, wt + a.L.up_w, C, col_lo / 16, (col_hi + 15) / 16, w + a.L.up_b, [&](int row, int col, float val) {
+        if (col >= col_lo && col < col_hi) sUp[row * ldU + (col / F - s0) * SG_HEAD + col % F] = fmaxf(val, 0.f);
+      });
       __syncthreads();
       for (int job = wave; job < ns * (SG_HEAD / 16); job += NW) {
         const int sl = job / (SG_HEAD / 16), ht = job % (SG_HEAD / 16);
-        const f32x4 acc = wave_gemm16<1, true>(sUp + sl * SG_HEAD, ldU, 0, SG_ROWS, wt + a.L.head_w, SG_HEAD, ht * 16, SG_HEAD, 0, zero4);
-        const int o = ht * 16 + cc;
-        const float bias = w[a.L.head_b + o];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sPar[(4 * q + r) * (SG_CHUNK * SG_HEAD) + sl * SG_HEAD + o] = acc[r] + bias;
+        tile16<true>(sUp + sl * SG_HEAD, ldU, wt + a.L.head_w, SG_HEAD, ht, w + a.L.head_b,
+                     [&](int row, int o, float val) { sPar[row * (SG_CHUNK * SG_HEAD) + sl * SG_HEAD + o] = val; });
       }
       __syncthreads();
       if (tid < SG_ROWS * ns) {
-        // Gumbel-max component pick + clamped logistic draw, as mix_sample_kernel (dmol.hip; blvm/utils/variational.py:309-349)
+        // Gumbel-max component pick + clamped logistic draw (decode_tiles.h)
         const int r = tid % SG_ROWS, sl = tid / SG_ROWS, s = s0 + sl;
         float x = 0.f;
         if (b0 + r < B) {
           const float* p = sPar + r * (SG_CHUNK * SG_HEAD) + sl * SG_HEAD;
           const size_t f = ((size_t)t * B + b0 + r) * S + s;
-          int best = 0;
-          float bv = -INFINITY;
-          for (int mm = 0; mm < K; ++mm) {
-            float sc = p[mm];
-            if (a.u != nullptr) sc -= logf(-logf(a.u[f * K + mm]));
-            if (sc > bv) { bv = sc; best = mm; }
-          }
-          const float loc = p[K + best], raw = p[2 * K + best];
-          x = loc;
-          if (a.v != nullptr) {
-            const float vv = a.v[f];
-            x = loc + expf(fmaxf(raw, a.log_eps)) * (logf(vv) - logf(1.f - vv));
-            x = fminf(fmaxf(x, -1.f), 1.f);
-          }
+          const int best = mix_pick(p, K, a.u != nullptr ? a.u + f * K : nullptr);
+          x = p[K + best];
+          if (a.v != nullptr) x = logistic_draw(x, p[2 * K + best], a.v[f], a.log_eps);
           a.x_out[((size_t)(b0 + r) * a.T + t) * S + s] = x;
         }
         sX[r * ldX + 2 * s] = sX[r * ldX + 2 * s + 1];
@@ -474,18 +378,12 @@ extern "C" size_t blvm_stcn_generate_pack_floats(int C, int S, int n_blocks, int
   return stcn_layout(C, S, n_blocks, n_out, latent, order, n_latents, dense, num_mix).total;
 }
 
-static size_t stcn_ring_floats(const int* dilations, int n_blocks, int B, int C) {
-  size_t n = 0;
-  for (int i = 0; i < n_blocks; ++i) n += (size_t)(dilations[i] > 0 ? dilations[i] : 0);
-  return n * B * C;
-}
-
 extern "C" size_t blvm_stcn_generate_scratch_floats(const int* dilations, int C, int S, int n_blocks, int n_out, const int* latent,
                                                     const int* order, int n_latents, int dense, int num_mix, int B) {
   using namespace blvm;
   if (!dilations || B <= 0 || stcn_check_shape(C, S, n_blocks, n_out, latent, order, n_latents, num_mix) != BLVM_OK) return 0;
   // [T16 operand copies | rings of the dilated blocks | rings of the output blocks | the selected skips]
-  return stcn_layout(C, S, n_blocks, n_out, latent, order, n_latents, dense, num_mix).total + stcn_ring_floats(dilations, n_blocks, B, C) +
+  return stcn_layout(C, S, n_blocks, n_out, latent, order, n_latents, dense, num_mix).total + ring_floats(dilations, n_blocks, B, C) +
          (size_t)n_out * B * C + (size_t)n_latents * B * C;
 }
 
@@ -508,10 +406,7 @@ static int stcn_run(bool resume, const float* packed, const int* dilations, cons
   BLVM_REQUIRE(B > 0 && T >= 0, "stcn_generate: need B > 0, T >= 0");
   BLVM_REQUIRE((u == nullptr) == (v == nullptr), "stcn_generate: u and v are given together (both NULL: the mode)");
   BLVM_REQUIRE(sd_beta > 0.f, "stcn_generate: the softplus beta must be positive");
-  if (resume) {
-    BLVM_REQUIRE(x_in && x_state, "stcn_generate_resume: NULL stack state");
-    BLVM_REQUIRE(t0 >= 0 && T < INT_MAX - t0, "stcn_generate_resume: t0 = %d, T = %d: need 0 <= t0, t0 + T < 2^31 - 1", t0, T);
-  }
+  if (resume) BLVM_TRY(check_resume("stcn_generate_resume", "stack", "T", t0, T, x_in, x_state));
   const int n = n_latents;
   StcnArgs a{};
   unsigned selected = 0;
@@ -533,10 +428,7 @@ static int stcn_run(bool resume, const float* packed, const int* dilations, cons
   const StcnLds m = stcn_lds(C, S, a.L.zsum, a.L.zmax);
   const size_t lds = sizeof(float) * m.total;
   BLVM_REQUIRE(lds <= 160 * 1024, "stcn_generate: C=%d, S=%d, %d latent dimensions need %zu bytes of LDS (> 160 KB)", C, S, a.L.zsum, lds);
-  if (T == 0) {
-    if (resume && x_state != x_in) BLVM_HIP(hipMemcpyAsync(x_state, x_in, sizeof(float) * 2 * S * B, hipMemcpyDeviceToDevice, s));
-    return BLVM_OK;
-  }
+  if (T == 0) return resume ? hand_back_state(x_state, x_in, (size_t)2 * S * B, s) : BLVM_OK;
 
   a.w = packed;
   a.wt = scratch;
@@ -576,7 +468,7 @@ static int stcn_run(bool resume, const float* packed, const int* dilations, cons
   a.slope = slope; a.log_eps = log_eps;
   a.u = u; a.v = v; a.x_out = x_out;
   a.rings = scratch + a.L.total;
-  a.orings = a.rings + stcn_ring_floats(dilations, n_blocks, B, C);
+  a.orings = a.rings + ring_floats(dilations, n_blocks, B, C);
   a.dskip = a.orings + (size_t)n_out * B * C;
   a.resume = resume ? 1 : 0; a.t0 = resume ? t0 : 0; a.x_in = x_in; a.x_state = x_state;
   auto kern = stcn_decode_kernel;

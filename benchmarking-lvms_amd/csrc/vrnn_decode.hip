@@ -8,6 +8,7 @@
 // every activation in LDS and walks the layers itself: the only traffic is the weight stream (T16 operand layout: one
 // contiguous 1 KB read per fragment), the noise and the samples — the decode step is bound by how fast one CU ingests weights.
 #include "common.h"
+#include "decode_tiles.h"
 #include "pchain.h"
 
 namespace blvm {
@@ -381,23 +382,14 @@ __global__ __launch_bounds__(VD_NW * 64) void vrnn_decode_kernel(VDArgs a) {
           for (int r = 0; r < 4; ++r) sPar[((4 * q + r) * VD_CHUNK + sm) * 32 + ct * 16 + cc] = c[r] + bv;
         }
         __syncthreads();
-        if (tid < VD_ROWS * VD_CHUNK) {  // Gumbel-max component pick + clamped logistic draw (as mix_sample_kernel, dmol.hip)
+        if (tid < VD_ROWS * VD_CHUNK) {  // Gumbel-max component pick + clamped logistic draw (decode_tiles.h), the draws from registers
           const int r = tid / VD_CHUNK, sm = tid - r * VD_CHUNK, s_idx = ch * VD_CHUNK + sm;
           if (b0 + r < B) {
             const float* p = sPar + tid * 32;
             const size_t f = ((size_t)t * B + b0 + r) * S + s_idx;
-            int best = 0;
-            float bvv = -INFINITY;
-            for (int m = 0; m < VD_K; ++m) {
-              float sc = p[m];
-              if (a.u != nullptr) sc -= logf(-logf(uu[m]));
-              if (sc > bvv) { bvv = sc; best = m; }
-            }
+            const int best = mix_pick_from<VD_K>(p, VD_K, a.u != nullptr, [&](int m) { return uu[m]; });
             float x = p[VD_K + best];
-            if (a.v != nullptr) {
-              x += expf(fmaxf(p[2 * VD_K + best], a.log_eps)) * (logf(vv) - logf(1.f - vv));
-              x = fminf(fmaxf(x, -1.f), 1.f);
-            }
+            if (a.v != nullptr) x = logistic_draw(x, p[2 * VD_K + best], vv, a.log_eps);
             a.x_out[((size_t)(b0 + r) * a.T + t) * S + s_idx] = x;
             sX[r * ldS + s_idx] = x;
           }

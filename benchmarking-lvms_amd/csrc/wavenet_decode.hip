@@ -14,9 +14,11 @@
 // A window of zeros is an all-zero past; under it every block input is constant in time (the network's response to zero
 // input, biases included).  The prologue evaluates that steady state once — each block with both taps on the same vector —
 // and fills the ring buffers with it, which makes frame 0 identical to the reference's first window evaluation.
-#include <climits>
-
+//
+// The any-width block, the tile layers and the draw are the ones K10d (stcn_decode.hip) uses: decode_tiles.h.  The compile-time-
+// width path below (block_fast) is this kernel's own.
 #include "common.h"
+#include "decode_tiles.h"
 
 namespace blvm {
 namespace {
@@ -114,7 +116,6 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
   const int b0 = blockIdx.x * DEC_ROWS;
   const DecodeLayout L = decode_layout(C, S, O, a.n_blocks);
   const float* w = a.w;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
   const int t0 = RESUME ? a.t0 : 0;
   for (int i = tid; i < DEC_ROWS * 2; i += NT) sX[i] = (RESUME && b0 + i / 2 < B) ? a.x_in[(size_t)2 * b0 + i] : 0.f;
@@ -133,65 +134,19 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
       sSkip[r * ldS + (idx - r * S)] = 0.f;
     }
     __syncthreads();
-    for (int tile = wave; tile < C / 16; tile += NW) {
-      const f32x4 acc = wave_gemm16<1>(sAct, ldA, 0, DEC_ROWS, w + L.in_w, C, tile * 16, C, 0, zero4);
-      const int o = tile * 16 + cc;
-      const float bias = w[L.in_b + o];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sH[(4 * q + r) * C + o] = acc[r] + bias;
-    }
+    tile_layer<NW, false>(sAct, ldA, w + L.in_w, C, 0, C / 16, w + L.in_b, [&](int row, int o, float val) { sH[row * C + o] = val; });
     __syncthreads();
   };
 
-  // one gated residual block on the frame in sH.  steady: both taps = sH, ring buffer filled with sH, skip untouched.
+  // one gated residual block (decode_tiles.h) on the frame in sH; the skip half is added into sSkip.  steady: both taps = sH,
+  // ring buffer filled with sH, skip untouched.
   const size_t wt_stride = (size_t)2 * C * 2 * C + (size_t)(C + S) * C;
+  const GateLds gl = {sH, C, sV, ldV, sPre, ldP, sAct, ldA};
   auto block = [&](int i, float* qi, int slot, bool steady) {
     const float* bw = w + L.blocks + (size_t)i * L.block_stride;
     const float* bt = a.wt + (size_t)i * wt_stride;
-    const int d = a.dil[i];
-    for (int idx = tid; idx < DEC_ROWS * C; idx += NT) {
-      const int r = idx / C, c = idx - r * C;
-      const float cur = sH[idx];
-      float old = cur;
-      if (b0 + r < B) {
-        if (steady) {
-          for (int s = 0; s < d; ++s) qi[((size_t)s * B + b0 + r) * C + c] = cur;
-        } else {
-          float* p = qi + ((size_t)slot * B + b0 + r) * C + c;
-          old = *p;
-          *p = cur;
-        }
-      }
-      sV[r * ldV + 2 * c] = old;
-      sV[r * ldV + 2 * c + 1] = cur;
-    }
-    __syncthreads();
-    for (int tile = wave; tile < 2 * C / 16; tile += NW) {
-      const f32x4 acc = wave_gemm16<1, true>(sV, ldV, 0, DEC_ROWS, bt, 2 * C, tile * 16, 2 * C, 0, zero4);
-      const int o = tile * 16 + cc;
-      const float bias = bw[L.conv_b + o];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sPre[(4 * q + r) * ldP + o] = acc[r] + bias;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < DEC_ROWS * C; idx += NT) {
-      const int r = idx / C, c = idx - r * C;
-      sAct[r * ldA + c] = tanhf(sPre[r * ldP + c]) * sigmoidf_(sPre[r * ldP + C + c]);
-    }
-    __syncthreads();
-    for (int tile = wave; tile < (C + S) / 16; tile += NW) {
-      const f32x4 acc = wave_gemm16<1, true>(sAct, ldA, 0, DEC_ROWS, bt + (size_t)2 * C * 2 * C, C, tile * 16, C, 0, zero4);
-      const int o = tile * 16 + cc;
-      const float bias = bw[L.rs_b + o];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 4 * q + r;
-        const float val = acc[r] + bias;
-        if (o < C) sH[row * C + o] = (val + sH[row * C + o]) * a.inv_std;
-        else if (!steady) sSkip[row * ldS + (o - C)] += val;
-      }
-    }
-    __syncthreads();
+    gated_ring_block<NW>(gl, C, bt, bw + L.conv_b, bt + (size_t)2 * C * 2 * C, bw + L.rs_b, qi, a.dil[i], slot, steady, b0, B, a.inv_std, 0,
+                         (steady ? C : C + S) / 16, [&](int row, int j, float val) { sSkip[row * ldS + j] += val; });
   };
 
   // steady state under an all-zero past
@@ -346,41 +301,18 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
       sSkip[r * ldS + c] = fmaxf(sSkip[r * ldS + c] * a.skip_scale, 0.f);
     }
     __syncthreads();
-    for (int tile = wave; tile < O / 16; tile += NW) {
-      const f32x4 acc = wave_gemm16<1>(sSkip, ldS, 0, DEC_ROWS, w + L.out_w, S, tile * 16, S, 0, zero4);
-      const int o = tile * 16 + cc;
-      const float bias = w[L.out_b + o];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sAct[(4 * q + r) * ldA + o] = fmaxf(acc[r] + bias, 0.f);
-    }
+    tile_layer<NW, false>(sSkip, ldS, w + L.out_w, S, 0, O / 16, w + L.out_b, [&](int row, int o, float val) { sAct[row * ldA + o] = fmaxf(val, 0.f); });
     __syncthreads();
-    for (int tile = wave; tile < DEC_HEAD_ROWS / 16; tile += NW) {
-      const f32x4 acc = wave_gemm16<1>(sAct, ldA, 0, DEC_ROWS, w + L.head_w, O, tile * 16, O, 0, zero4);
-      const int o = tile * 16 + cc;
-      const float bias = w[L.head_b + o];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sPar[(4 * q + r) * DEC_HEAD_ROWS + o] = acc[r] + bias;
-    }
+    tile_layer<NW, false>(sAct, ldA, w + L.head_w, O, 0, DEC_HEAD_ROWS / 16, w + L.head_b, [&](int row, int o, float val) { sPar[row * DEC_HEAD_ROWS + o] = val; });
     __syncthreads();
     if (tid < DEC_ROWS && b0 + tid < B) {
-      // Gumbel-max component pick + clamped logistic draw, as mix_sample_kernel (dmol.hip; blvm/utils/variational.py:309-349)
+      // Gumbel-max component pick + clamped logistic draw (decode_tiles.h)
       const float* p = sPar + tid * DEC_HEAD_ROWS;
       const int K = a.num_mix;
       const size_t f = (size_t)t * B + b0 + tid;
-      int best = 0;
-      float bv = -INFINITY;
-      for (int m = 0; m < K; ++m) {
-        float s = p[m];
-        if (a.u != nullptr) s -= logf(-logf(a.u[f * K + m]));
-        if (s > bv) { bv = s; best = m; }
-      }
-      const float loc = p[K + best], raw = p[2 * K + best];
-      float x = loc;
-      if (a.v != nullptr) {
-        const float vv = a.v[f];
-        x = loc + expf(fmaxf(raw, a.log_eps)) * (logf(vv) - logf(1.f - vv));
-        x = fminf(fmaxf(x, -1.f), 1.f);
-      }
+      const int best = mix_pick(p, K, a.u != nullptr ? a.u + f * K : nullptr);
+      float x = p[K + best];
+      if (a.v != nullptr) x = logistic_draw(x, p[2 * K + best], a.v[f], a.log_eps);
       a.x_out[(size_t)(b0 + tid) * a.n_frames + t] = x;
       sX[2 * tid] = sX[2 * tid + 1];
       sX[2 * tid + 1] = x;
@@ -422,15 +354,9 @@ extern "C" size_t blvm_wavenet_decode_pack_floats(int C, int S, int O, int n_blo
   return blvm::decode_layout(C, S, O, n_blocks).total;
 }
 
-static size_t decode_ring_floats(const int* dilations, int n_blocks, int B, int C) {
-  size_t n = 0;
-  for (int i = 0; i < n_blocks; ++i) n += (size_t)(dilations[i] > 0 ? dilations[i] : 0);
-  return n * B * C;
-}
-
 extern "C" size_t blvm_wavenet_decode_scratch_floats(const int* dilations, int n_blocks, int B, int C, int S) {
   if (!dilations || n_blocks <= 0 || B <= 0 || C <= 0 || S <= 0) return 0;
-  return decode_ring_floats(dilations, n_blocks, B, C) + (size_t)n_blocks * ((size_t)2 * C * 2 * C + (size_t)(C + S) * C);
+  return blvm::ring_floats(dilations, n_blocks, B, C) + (size_t)n_blocks * ((size_t)2 * C * 2 * C + (size_t)(C + S) * C);
 }
 
 extern "C" size_t blvm_wavenet_decode_ring_offset_floats(int n_blocks, int C, int S) {
@@ -448,16 +374,10 @@ static int decode_run(bool resume, const float* packed, const int* dilations, in
   BLVM_REQUIRE(C > 0 && S > 0 && O > 0 && C % 16 == 0 && S % 16 == 0 && O % 16 == 0, "wavenet_decode: C, S, O must be multiples of 16");
   BLVM_REQUIRE(num_mix > 0 && 3 * num_mix <= DEC_HEAD_ROWS, "wavenet_decode: num_mix must be in [1, %d]", DEC_HEAD_ROWS / 3);
   BLVM_REQUIRE((u == nullptr) == (v == nullptr), "wavenet_decode: u and v are given together (both NULL: the mode)");
-  if (resume) {
-    BLVM_REQUIRE(x_in && x_state, "wavenet_decode_resume: NULL sample state");
-    BLVM_REQUIRE(t0 >= 0 && n_frames < INT_MAX - t0, "wavenet_decode_resume: t0 = %d, n_frames = %d: need 0 <= t0, t0 + n_frames < 2^31 - 1", t0, n_frames);
-  }
+  if (resume) BLVM_TRY(check_resume("wavenet_decode_resume", "sample", "n_frames", t0, n_frames, x_in, x_state));
   const size_t lds = decode_lds_bytes(C, S, O);
   BLVM_REQUIRE(lds <= 160 * 1024, "wavenet_decode: C=%d, S=%d, O=%d need %zu bytes of LDS (> 160 KB)", C, S, O, lds);
-  if (n_frames == 0) {
-    if (resume && x_state != x_in) BLVM_HIP(hipMemcpyAsync(x_state, x_in, sizeof(float) * 2 * B, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-    return BLVM_OK;
-  }
+  if (n_frames == 0) return resume ? hand_back_state(x_state, x_in, (size_t)2 * B, static_cast<hipStream_t>(stream)) : BLVM_OK;
   DecodeArgs a;
   a.w = packed;
   for (int i = 0; i < n_blocks; ++i) {

@@ -1026,6 +1026,27 @@ def test_wavenet_decode_kernel_matches_window_generation(B, C, layers, stacks):
     assert tuple(free.shape) == (B, 5, 1) and torch.isfinite(free).all() and float(free.abs().max()) <= 1.0
 
 
+def test_wavenet_decode_kernel_with_a_skip_width_of_its_own():
+    """`ops.wavenet_decode` on hand-made parameters with C = 32, S = 16, O = 48 (the model only ever builds S = O = C): the arm of
+    the shared gated block in which the skip width is not the residual width.  Five blocks, so the any-width kernel runs; B = 19 is
+    one full group of 16 rows and a partial one; 12 frames wrap every ring.  Every sample within `TOL` of the float64 restatement
+    of the cached formulation (tests/test_wavenet_prompt.py, which also asserts on the CPU that the case has no near tie)."""
+    import test_wavenet_prompt as WP
+
+    c = WP.SkipCase
+    params, u, v, x64, gap = WP.skip_case_reference()
+    assert gap >= WP.MIN_GAP
+    causal, in_transform, blocks, out_linear, head_linear = ([t.to(DEV) for t in p] if isinstance(p, tuple) else [tuple(t.to(DEV) for t in b) for b in p]
+                                                             for p in params)  # fmt: skip
+    x = ops.wavenet_decode(causal, in_transform, blocks, list(c.dilations), out_linear, head_linear, c.B, c.n_frames, c.inv_std, c.skip_scale,
+                           c.num_mix, c.log_eps, u.to(DEV), v.to(DEV))  # fmt: skip
+    _hip.check_async()
+    assert tuple(x.shape) == (c.B, c.n_frames)
+    err = (x.cpu().double() - x64).abs()
+    print(f"skip width {c.S} != {c.C}: max |diff| {float(err.max()):.3e}, samples beyond {WP.TOL:g}: {int((err > WP.TOL).sum())} of {err.numel()}")
+    assert float(err.max()) <= WP.TOL
+
+
 @pytest.mark.parametrize("C,B,L,dil,T_skip", [(32, 3, 77, (1, 2, 4), 50), (64, 5, 203, (1, 8), 120), (96, 2, 131, (4, 1, 2), 100),
                                               (32, 64, 8300, (2, 1), 8000)])  # fmt: skip
 def test_wavenet_fused_block_kernels_match_torch(C, B, L, dil, T_skip):

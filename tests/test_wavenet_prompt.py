@@ -119,6 +119,84 @@ def reference(name, P):
     return m, prompt, uni, x64, gap
 
 
+# ---- the decode kernel's arm with a skip width other than the residual width ------------------------------------------
+# The model always builds skip_channels = res_channels and an output transform of that width, so this arm is reached with
+# hand-made parameters only (`ops.wavenet_decode` takes the tensors as they are).
+class SkipCase:
+    B, C, S, O, num_mix, n_frames, seed = 19, 32, 16, 48, 10, 12, 9  # one full group of 16 rows and a partial one; S != C != O
+    dilations = (1, 2, 4, 1, 2)  # five blocks: an odd count, so the any-width kernel <8,0,0> runs; 12 frames: every ring wraps
+    inv_std, skip_scale, log_eps = math.sqrt(0.5), 1.0 / math.sqrt(2.5), -7.0  # (skip_scale: five blocks as if in two stacks)
+
+
+def skip_case_parameters():
+    """Hand-made fp32 parameters at torch's default initialisation (uniform in +-1/sqrt(fan_in)), in the regime of `build_model`:
+    the blocks' weights x 2, the output transform's and the head's x 3, the head's log-scale biases -5.
+    -> (causal, in_transform, blocks, out_linear, head_linear) as `ops.wavenet_decode` takes them."""
+    c = SkipCase
+    g = torch.Generator().manual_seed(c.seed)
+
+    def init(fan_in, *shape, gain=1.0):
+        return (torch.rand(*shape, generator=g) * 2 - 1) * (gain / math.sqrt(fan_in))
+
+    causal = (init(2, c.C, 1, 2), init(2, c.C))
+    in_transform = (init(c.C, c.C, c.C), init(c.C, c.C))
+    blocks = [(init(2 * c.C, 2 * c.C, c.C, 2, gain=2.0), init(2 * c.C, 2 * c.C), init(c.C, c.C + c.S, c.C, gain=2.0), init(c.C, c.C + c.S))
+              for _ in c.dilations]  # fmt: skip
+    out_linear = (init(c.S, c.O, c.S, gain=3.0), init(c.S, c.O))
+    head_b = init(c.O, 3 * c.num_mix)
+    head_b[2 * c.num_mix :] = -5.0
+    return causal, in_transform, blocks, out_linear, (init(c.O, 3 * c.num_mix, c.O, gain=3.0), head_b)
+
+
+@functools.lru_cache(maxsize=None)
+def skip_case_reference():
+    """The cached formulation (arXiv:1611.09482) of the hand-made network in float64, restated in plain torch: one ring per block,
+    started from the steady state under an all-zero past.  -> (parameters, u [n,B,K], v [n,B], x64 [B,n], the smallest gap between
+    the best and the second-best perturbed logit) — computed once, never changed."""
+    c = SkipCase
+    params = skip_case_parameters()
+    g = torch.Generator().manual_seed(c.seed + 1)
+    u = torch.empty(c.n_frames, c.B, c.num_mix).uniform_(1e-5, 1 - 1e-5, generator=g)
+    v = torch.empty(c.n_frames, c.B).uniform_(1e-8, 1 - 1e-8, generator=g)
+    f64 = lambda ts: tuple(t.double() for t in ts)  # noqa: E731
+    (cw, cb), (iw, ib), (ow, ob), (hw, hb) = f64(params[0]), f64(params[1]), f64(params[3]), f64(params[4])
+    blocks = [f64(b) for b in params[2]]
+    C, K = c.C, c.num_mix
+
+    def front(x_prev, x_new):  # causal conv (kernel 2) on the two newest samples -> 1x1 in_transform
+        return F.linear(x_prev[:, None] * cw[:, 0, 0] + x_new[:, None] * cw[:, 0, 1] + cb, iw, ib)
+
+    def block(i, old, h):  # -> (the next block's input, the skip half)
+        kw, kb, rw, rb = blocks[i]
+        pre = F.linear(old, kw[:, :, 0]) + F.linear(h, kw[:, :, 1]) + kb
+        rs = F.linear(torch.tanh(pre[:, :C]) * torch.sigmoid(pre[:, C:]), rw, rb)
+        return (rs[:, :C] + h) * c.inv_std, rs[:, C:]
+
+    x_prev = x_new = torch.zeros(c.B, dtype=torch.float64)
+    h, rings = front(x_prev, x_new), []
+    for i, d in enumerate(c.dilations):  # an input constant in time: both taps see it, every slot holds it
+        rings.append(h.repeat(d, 1, 1))
+        h, _ = block(i, h, h)
+    out, gap = [], float("inf")
+    for t in range(c.n_frames):
+        h, skip = front(x_prev, x_new), 0.0
+        for i, d in enumerate(c.dilations):
+            old = rings[i][t % d].clone()
+            rings[i][t % d] = h
+            h, s = block(i, old, h)
+            skip = skip + s
+        par = F.linear(F.relu(F.linear(F.relu(skip * c.skip_scale), ow, ob)), hw, hb)
+        top = (par[:, :K] - torch.log(-torch.log(u[t].double()))).topk(2, dim=-1)
+        gap = min(gap, float((top.values[:, 0] - top.values[:, 1]).min()))
+        best = top.indices[:, :1]
+        loc, raw = par[:, K : 2 * K].gather(1, best)[:, 0], par[:, 2 * K :].gather(1, best)[:, 0]
+        vt = v[t].double()
+        x = (loc + torch.exp(raw.clamp(min=c.log_eps)) * (torch.log(vt) - torch.log(1 - vt))).clamp(-1, 1)
+        out.append(x)
+        x_prev, x_new = x_new, x
+    return params, u, v, torch.stack(out, 1), gap
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # CPU
 # ----------------------------------------------------------------------------------------------------------------------
@@ -152,6 +230,16 @@ def test_cases_have_no_near_ties(name, P):
     if P and (name, 0) in ZERO_STARTS:
         assert float((x64 - reference(name, 0)[3]).abs().max()) > 0.05
     assert float((x64.abs() >= 1).double().mean()) < 0.5
+
+
+def test_skip_width_case_has_no_near_ties():
+    """The precondition of `test_gpu_parity.py::test_wavenet_decode_kernel_with_a_skip_width_of_its_own`, and its regime."""
+    c = SkipCase
+    _, _, _, x64, gap = skip_case_reference()
+    assert tuple(x64.shape) == (c.B, c.n_frames) and bool(torch.isfinite(x64).all())
+    assert gap >= MIN_GAP, f"perturbed-logit gap {gap:.2e}: pick another seed"
+    assert float((x64.abs() >= 1).double().mean()) < 0.5
+    assert float(x64.std()) > 0.05  # (the samples are no constant)
 
 
 def test_prime_and_state_arguments_are_checked_without_a_device():
