@@ -99,6 +99,7 @@ _SIGNATURES = {
     "blvm_pchain_chain_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "blvm_pchain_static_chain_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "blvm_pchain_static_chain_probe_fetch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "blvm_pchain_static_chain_probe_paced": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "blvm_pchain_rows_to_t16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "blvm_gemm_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_void_p, c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -105,6 +105,10 @@ struct Poll {
 #ifdef PCHAIN_TPROF  // variant build: wall-clock anatomy of tile_lin (wave 0): see tile_lin
   unsigned long long t_first = 0, t_ok = 0, t_end = 0, tp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned polls = 0;
+  // resident path (product_regs; tools/probe_static_anatomy.py): first issue of the tile's operand poll, rpolls polls until t_ok,
+  // and the moment this thread had issued the tile's last T16 store (0: it stored nothing)
+  unsigned long long t_issue = 0, t_st = 0;
+  unsigned rpolls = 0;
 #endif
   __device__ __forceinline__ void sleep() const {
     if (nap > 8) __builtin_amdgcn_s_sleep(32);
@@ -347,6 +351,32 @@ __device__ __forceinline__ void canary_wait(const float* A16, int r0, int K, Pol
   __syncthreads();
 }
 
+// ---- poll pacing of the resident tiles ---------------------------------------------------------------------------------------
+// The operand poll of product_regs is serial: issue the fragment loads, wait a round trip (~0.6 us), check, nap, reissue.  A poll
+// that reads memory just before the data lands costs a whole further round trip.  A pacing policy delays the FIRST issue of a tile
+// by a number of s_sleep units (64 clocks each), one value for the waves that leave the previous tile at its barrier (waves
+// 4 .. NW-1: they arrive before the producers have stored) and one for the epilogue waves 0 .. 3 (they arrive right behind their
+// own stores) — for links in lock step with their producers.  The epilogue's own operand loads (`mid`) are issued in front of the
+// delay and land during it.  Protocol, cache bits and layout are unchanged; PaceOff is the plain loop, instruction for instruction.
+// (Two polls in flight per wave — the denser cadence for waiters armed long before their data — has no form the compiler keeps:
+// DESIGN §8-r3, lead (a).)
+struct PaceOff {
+  static constexpr bool paced = false;
+  __device__ __forceinline__ int delay(bool) const { return 0; }
+};
+template <int EARLY, int EPI>  // compile-time constants (the VRNN walks)
+struct PaceK {
+  static constexpr bool paced = EARLY > 0 || EPI > 0;
+  __device__ __forceinline__ int delay(bool epilogue_wave) const { return epilogue_wave ? EPI : EARLY; }
+};
+struct PaceRt {  // delays chosen at run time (the chain probe's sweep)
+  static constexpr bool paced = true;
+  int early, epi;
+  __device__ __forceinline__ int delay(bool epilogue_wave) const { return epilogue_wave ? epi : early; }
+};
+__device__ __forceinline__ void nap_units(int n) {  // n x s_sleep 1 (a scalar instruction: the caller's n is wave-uniform)
+  for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(1);
+}
 // ---- resident weights ---------------------------------------------------------------------------------------------------------
 // A workgroup that owns the same tile of a link in every step of a launch (seqchain.hip's one-link programs, vrnn_static.hip's fixed
 // deal) loads the tile's weight fragments ONCE, in front of its step loop, and keeps them in registers: a visit then issues no
@@ -387,10 +417,11 @@ __device__ __forceinline__ void load_w(typename WFrag<OT>::type (&w)[G][NCH], co
 // brings a line into the XCD's L2, the others hit it, and the fabric carries the slab once per XCD instead of once per tile.  Every
 // word is still validated: a fragment that holds a sentinel (a line cached before its last store landed) is re-read with sc1 loads,
 // which bypass the stale line.
-template <int NW, int OT, int GA, int G, class AMap, int NCH, bool SHARED, class Mid>
+template <int NW, int OT, int GA, int G, class AMap, int NCH, bool SHARED, class Mid, class PC = PaceOff>
 __device__ __forceinline__ void product_regs(const float* const (&A16)[GA], int r0, int nrows, int width,
-                                             const typename WFrag<OT>::type (&w)[G][NCH], f32x4 (&acc)[G], Poll& pl, Mid mid) {
+                                             const typename WFrag<OT>::type (&w)[G][NCH], f32x4 (&acc)[G], Poll& pl, Mid mid, const PC& pace = PC()) {
   static_assert(!SHARED || GA == 1, "the shared-slab form reads one operand");
+  static_assert(!SHARED || !PC::paced, "the shared-slab form is not paced");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool aok = (r0 + (lane & 15)) < nrows;
   rsrc_t ar[GA];
@@ -412,6 +443,18 @@ __device__ __forceinline__ void product_regs(const float* const (&A16)[GA], int 
     for (int u = 0; u < NCH; ++u) bad |= any_sentinel(a[0][u]);
     if (!__any(bad && aok)) goto multiply;
   }
+  if constexpr (PC::paced) {
+    // the epilogue's operand loads first: they land during the delay (nothing waits on them before the first check)
+    const int d = pace.delay(__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) < 4);
+    if (d > 0) {
+      mid();
+      mid_pending = false;
+      nap_units(d);
+    }
+  }
+#ifdef PCHAIN_TPROF
+  pl.t_issue = wall_clock64(); pl.rpolls = 0; pl.t_st = 0;
+#endif
   for (;;) {
 #pragma unroll
     for (int u = 0; u < NCH; ++u)
@@ -423,10 +466,16 @@ __device__ __forceinline__ void product_regs(const float* const (&A16)[GA], int 
     for (int u = 0; u < NCH; ++u)
 #pragma unroll
       for (int g = 0; g < GA; ++g) bad |= any_sentinel(a[g][u]);
+#ifdef PCHAIN_TPROF
+    pl.rpolls++;
+#endif
     if (!__any(bad && aok) || pl.dead) break;
     if (spin_tick(spins, pl.ctl, pl.code, pl.dead)) break;
     pl.sleep();
   }
+#ifdef PCHAIN_TPROF
+  pl.t_ok = wall_clock64();
+#endif
 multiply:
   if constexpr (AMap::sum) {
 #pragma unroll
@@ -462,17 +511,18 @@ multiply:
 // loaded by load_w for THIS tile's columns, so W, c0 and w_width are ignored; every operand is a polled T16 slab, so `polled` and
 // lda are ignored (a row-major operand would be read as a slab); K is ignored, the product covers the NCH * 16 * NW k the fragments
 // hold.  The callers are the static walks of vrnn_static.hip, which pass polled = true and a K fixed at compile time to match.
-template <int NW, int OT, int GA, int G, class AMap, class Mid = NoMid>
+// `pace` (a poll pacing policy, above) applies to the resident form; the form that reads its weights ignores it.
+template <int NW, int OT, int GA, int G, class AMap, class Mid = NoMid, class PC = PaceOff>
 __device__ __forceinline__ void tile_product(const WMem&, const float* const (&A)[GA], const int (&lda)[GA], bool polled, int r0, int nrows,
                                              const float* const (&W)[G], const int (&c0)[G], int K, f32x4 (&acc)[G], Poll& pl, Mid mid = Mid(),
-                                             int a_width = 0, int w_width = 0) {
+                                             int a_width = 0, int w_width = 0, const PC& = PC()) {
   mgemm16<NW, OT, GA, G, AMap>(A, lda, polled, r0, nrows, W, c0, K, acc, pl, mid, a_width, w_width);
 }
-template <int NW, int OT, int GA, int G, class AMap, class Mid = NoMid, int NCH>
+template <int NW, int OT, int GA, int G, class AMap, class Mid = NoMid, class PC = PaceOff, int NCH>
 __device__ __forceinline__ void tile_product(const WRegs<OT, G, NCH>& ws, const float* const (&A)[GA], const int (&)[GA], bool, int r0, int nrows,
                                              const float* const (&)[G], const int (&)[G], int, f32x4 (&acc)[G], Poll& pl, Mid mid = Mid(),
-                                             int a_width = 0, int = 0) {
-  product_regs<NW, OT, GA, G, AMap, NCH, false>(A, r0, nrows, a_width > 0 ? a_width : NCH * 16 * NW, ws.w, acc, pl, mid);
+                                             int a_width = 0, int = 0, const PC& pace = PC()) {
+  product_regs<NW, OT, GA, G, AMap, NCH, false>(A, r0, nrows, a_width > 0 ? a_width : NCH * 16 * NW, ws.w, acc, pl, mid, pace);
 }
 
 // Where a link's [16 x 16] output tile goes: a row-major copy (plain stores; `rm_sc1`: other workgroups poll single words of it)
@@ -525,10 +575,10 @@ struct LinLate {
   Out out;
 };
 // (ws, here and in the tiles below: the weight source — WMem, the pointer arguments, or a WRegs loaded for this very tile)
-template <int NW, int OT, class Late, class WS = WMem>
+template <int NW, int OT, class Late, class WS = WMem, class PC = PaceOff>
 __device__ __forceinline__ void tile_lin_late(const float* A, int lda, bool a_polled, const float* W, int K, Late& late, int r0, int c0, int B,
                                               float* red, Poll& pl, const float* A2 = nullptr, const float* A3 = nullptr, int w_width = 0,
-                                              const WS& ws = WS()) {
+                                              const WS& ws = WS(), const PC& pace = PC()) {
   const int t = threadIdx.x & 255;
   const int row = r0 + (t >> 4), col = c0 + (t & 15);
   const bool own = threadIdx.x < 256 && row < B;
@@ -550,12 +600,12 @@ __device__ __forceinline__ void tile_lin_late(const float* A, int lda, bool a_po
     const float* const As[3] = {A, A2, A3};
     const float* const Ws[1] = {W};
     const int la[3] = {0, 0, 0}, cs[1] = {c0};
-    tile_product<NW, OT, 3, 1, MapSum>(ws, As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch, lda, w_width);
+    tile_product<NW, OT, 3, 1, MapSum>(ws, As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch, lda, w_width, pace);
   } else {
     const float* const As[1] = {A};
     const float* const Ws[1] = {W};
     const int la[1] = {lda}, cs[1] = {c0};
-    tile_product<NW, OT, 1, 1, MapSame>(ws, As, la, a_polled, r0, B, Ws, cs, K, acc, pl, prefetch, a_polled ? lda : 0, w_width);  // polled: lda = slab width (0 = K)
+    tile_product<NW, OT, 1, 1, MapSame>(ws, As, la, a_polled, r0, B, Ws, cs, K, acc, pl, prefetch, a_polled ? lda : 0, w_width, pace);  // polled: lda = slab width (0 = K)
   }
   float v[1];
   reduce_tiles<1, NW>(acc, red, v);
@@ -580,7 +630,7 @@ __device__ __forceinline__ void tile_lin_late(const float* A, int lda, bool a_po
   if (L.gate) x = e_gate > 0.f ? x : x * L.slope;
   put(L.out, r0, c0, row, col, x);
 #ifdef PCHAIN_TPROF
-  if (a_polled && pl.nap == 1) { pl.t_end = wall_clock64(); }
+  if (a_polled && pl.nap == 1) { pl.t_end = wall_clock64(); pl.t_st = pl.t_end; }
 #endif
 }
 template <int NW, int OT = OP_F32>
@@ -598,10 +648,11 @@ struct HeadOut {
   float *mu_p, *sd_p, *mu_q, *sd_q, *raw_p, *raw_q, *muq_raw;  // [B,Z] slabs of this step; muq_raw may be null
   Out z;
 };
-template <int NW, int OT = OP_F32, class WS = WMem>
+template <int NW, int OT = OP_F32, class WS = WMem, class PC = PaceOff>
 __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool polled, const float* Wp, const float* bp, const float* Wq,
                                           const float* bq, const float* eps, const HeadOut& o, int H, int Z, int residual, float beta,
-                                          float inv_beta, float sd_eps, int r0, int c0, int B, float* red, Poll& pl, const WS& ws = WS()) {
+                                          float inv_beta, float sd_eps, int r0, int c0, int B, float* red, Poll& pl, const WS& ws = WS(),
+                                          const PC& pace = PC()) {
   const int t = threadIdx.x & 255;
   const int row = r0 + (t >> 4), col = c0 + (t & 15);
   const bool own = threadIdx.x < 256 && row < B;
@@ -615,7 +666,7 @@ __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool p
     const float* const As[2] = {P, Q};
     const float* const Ws[4] = {Wp, Wp, Wq, Wq};
     const int la[2] = {H, H}, cs[4] = {c0, Z + c0, c0, Z + c0};
-    tile_product<NW, OT, 2, 4, MapPairs>(ws, As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
+    tile_product<NW, OT, 2, 4, MapPairs>(ws, As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch, 0, 0, pace);
   }
   float v[4];
   reduce_tiles<4, NW>(acc, red, v);
@@ -629,6 +680,9 @@ __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool p
     if (residual == 1) mq += mp;
     const float z = e * sq + mq;  // randn_like(mu).mul(sd).add(mu)
     put_t16(o.z, r0, c0, row, col, z);
+#ifdef PCHAIN_TPROF
+    pl.t_st = wall_clock64();
+#endif
     __builtin_amdgcn_sched_barrier(0);  // (the scheduler would interleave the prior's softplus with the posterior's)
     put_rm(o.z, row, col, z);
     const float sp = softplus_beta(rp, beta, inv_beta) + sd_eps;
@@ -657,10 +711,10 @@ __device__ __forceinline__ void tile_head(const float* P, const float* Q, bool p
 // GRU cell update of a [16 x 16] block of the state (vrnn.hip gru_stage_kernel, rssm.hip gru_cell_stage_kernel): gi = X Wih^T
 // (3 products, X [B,K] polled) + xg (state-independent part of the input projection incl. b_ih, computed before the launch) and /
 // or + b_ih ; gh = h_prev Whh^T + b_hh was produced by another link of this launch (polled words), h_prev likewise.  Writes h_new (sc1) and the gates r, u, n (read after the launch).
-template <int NW, int OT = OP_F32, class WS = WMem>
+template <int NW, int OT = OP_F32, class WS = WMem, class PC = PaceOff>
 __device__ __forceinline__ void tile_gru(const float* X, int ldx, bool polled, const float* Wih, int K, const float* xg, const float* bih,
                                          const float* gh, const float* hprev, int ldh, int R, const Out& hnew, float* rg, float* ug, float* ng,
-                                         int r0, int c0, int B, float* red, Poll& pl, const WS& ws = WS()) {
+                                         int r0, int c0, int B, float* red, Poll& pl, const WS& ws = WS(), const PC& pace = PC()) {
   const int t = threadIdx.x & 255;
   const int row = r0 + (t >> 4), col = c0 + (t & 15);
   const bool own = threadIdx.x < 256 && row < B;
@@ -686,7 +740,7 @@ __device__ __forceinline__ void tile_gru(const float* X, int ldx, bool polled, c
     const float* const As[1] = {X};
     const float* const Ws[3] = {Wih, Wih, Wih};
     const int la[1] = {ldx}, cs[3] = {c0, R + c0, 2 * R + c0};
-    tile_product<NW, OT, 1, 3, MapSame>(ws, As, la, polled, r0, B, Ws, cs, K, acc, pl, prefetch);
+    tile_product<NW, OT, 1, 3, MapSame>(ws, As, la, polled, r0, B, Ws, cs, K, acc, pl, prefetch, 0, 0, pace);
   }
   float v[3];
   reduce_tiles<3, NW>(acc, red, v);
@@ -697,6 +751,9 @@ __device__ __forceinline__ void tile_gru(const float* X, int ldx, bool polled, c
   const float u = sigmoidf_(v[1] + x1 + w[1]);
   const float n = tanhf(v[2] + x2 + r * w[2]);
   put(hnew, r0, c0, row, col, (1.f - u) * n + u * w[3]);
+#ifdef PCHAIN_TPROF
+  pl.t_st = wall_clock64();
+#endif
   const size_t o = (size_t)row * R + col;
   rg[o] = r; ug[o] = u; ng[o] = n;
 }
@@ -713,10 +770,10 @@ struct DzIn {
   bool has_gemm = true;  // false: dz = dz_add alone (the last step of a chain whose z only feeds the next step)
 };
 // (resident weights: a WRegs of two products for the D, D2 form, of one for D alone — the caller holds the fragments of the form it runs)
-template <int NW, int OT = OP_F32, class WS = WMem>
+template <int NW, int OT = OP_F32, class WS = WMem, class PC = PaceOff>
 __device__ __forceinline__ void tile_dz(const float* D, const float* WT, const float* D2, const float* WT2, bool polled, const float* dz_add,
                                         int ld_add, bool add_polled, const DzIn& a, const Out& dqh, const Out& dph, int H, int Z, int r0, int c0,
-                                        int B, float* red, Poll& pl, const WS& ws = WS()) {
+                                        int B, float* red, Poll& pl, const WS& ws = WS(), const PC& pace = PC()) {
   const int t = threadIdx.x & 255;
   const int row = r0 + (t >> 4), col = c0 + (t & 15);
   const bool own = threadIdx.x < 256 && row < B;
@@ -742,7 +799,7 @@ __device__ __forceinline__ void tile_dz(const float* D, const float* WT, const f
         const float* const As[2] = {D, D2};
         const float* const Ws[2] = {WT, WT2};
         const int la[2] = {H, H}, cs[2] = {c0, c0};
-        tile_product<NW, OT, 2, 2, MapId>(ws, As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch);
+        tile_product<NW, OT, 2, 2, MapId>(ws, As, la, polled, r0, B, Ws, cs, H, acc, pl, prefetch, 0, 0, pace);
       }
     } else {
       if constexpr (WS::products != 2) {
@@ -750,7 +807,7 @@ __device__ __forceinline__ void tile_dz(const float* D, const float* WT, const f
         const float* const As[1] = {D};
         const float* const Ws[1] = {WT};
         const int la[1] = {H}, cs[1] = {c0};
-        tile_product<NW, OT, 1, 1, MapSame>(ws, As, la, polled, r0, B, Ws, cs, H, a1, pl, prefetch);
+        tile_product<NW, OT, 1, 1, MapSame>(ws, As, la, polled, r0, B, Ws, cs, H, a1, pl, prefetch, 0, 0, pace);
         acc[0] = a1[0];
       }
     }
@@ -796,6 +853,9 @@ __device__ __forceinline__ void tile_dz(const float* D, const float* WT, const f
   const float g_rq = g_sdq * sigmoidf_(a.beta * rq), g_rp = g_sdp * sigmoidf_(a.beta * rp);
   put_t16(dqh, r0, c0, row, col, g_muq); put_t16(dqh, r0, Z + c0, row, Z + col, g_rq);
   put_t16(dph, r0, c0, row, col, g_mup); put_t16(dph, r0, Z + c0, row, Z + col, g_rp);
+#ifdef PCHAIN_TPROF
+  pl.t_st = wall_clock64();
+#endif
   put_rm(dqh, row, col, g_muq); put_rm(dqh, row, Z + col, g_rq);
   put_rm(dph, row, col, g_mup); put_rm(dph, row, Z + col, g_rp);
 }
@@ -814,8 +874,9 @@ struct GrubIn {
   float *ga, *g_out;
   bool has_gemm, has_gin, has_gates;
 };
-template <int NW, int OT = OP_F32, class WS = WMem>
-__device__ __forceinline__ void tile_grub(const GrubIn& a, int K, int R, int r0, int c0, int B, float* red, Poll& pl, const WS& ws = WS()) {
+template <int NW, int OT = OP_F32, class WS = WMem, class PC = PaceOff>
+__device__ __forceinline__ void tile_grub(const GrubIn& a, int K, int R, int r0, int c0, int B, float* red, Poll& pl, const WS& ws = WS(),
+                                          const PC& pace = PC()) {
   const int tt = threadIdx.x & 255;
   const int row = r0 + (tt >> 4), col = c0 + (tt & 15);
   const bool own = threadIdx.x < 256 && row < B;
@@ -840,7 +901,7 @@ __device__ __forceinline__ void tile_grub(const GrubIn& a, int K, int R, int r0,
     const float* const As[2] = {a.D0, a.D1};
     const float* const Ws[2] = {a.W0, a.W1};
     const int la[2] = {0, 0}, cs[2] = {c0, c0};
-    tile_product<NW, OT, 2, 2, MapId>(ws, As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch);
+    tile_product<NW, OT, 2, 2, MapId>(ws, As, la, true, r0, B, Ws, cs, K, acc, pl, prefetch, 0, 0, pace);
     reduce_tiles<2, NW>(acc, red, v);
   }
   if (threadIdx.x >= 256) return;
@@ -861,6 +922,9 @@ __device__ __forceinline__ void tile_grub(const GrubIn& a, int K, int R, int r0,
   put_t16(a.dgi, r0, c0, row, col, dr_pre); put_t16(a.dgi, r0, R + c0, row, R + col, du_pre); put_t16(a.dgi, r0, 2 * R + c0, row, 2 * R + col, dn_pre);
   put_t16(a.dgh, r0, c0, row, col, dr_pre); put_t16(a.dgh, r0, R + c0, row, R + col, du_pre); put_t16(a.dgh, r0, 2 * R + c0, row, 2 * R + col, dnr);
   st_sc1(make_rsrc(a.ga), 4u * ((unsigned)row * (unsigned)R + (unsigned)col), g * u + dd);
+#ifdef PCHAIN_TPROF
+  pl.t_st = wall_clock64();
+#endif
   put_rm(a.dgi, row, col, dr_pre); put_rm(a.dgi, row, R + col, du_pre); put_rm(a.dgi, row, 2 * R + col, dn_pre);
   put_rm(a.dgh, row, col, dr_pre); put_rm(a.dgh, row, R + col, du_pre); put_rm(a.dgh, row, 2 * R + col, dnr);
 }

@@ -47,6 +47,37 @@ __device__ __forceinline__ int tile_lanes(int w, int wg0, int nwg, int rt, int c
 }
 __device__ __forceinline__ int tile_count(int lanes) { return __popcll(__ballot(lanes >= 0)); }  // (the valid lanes are 0 .. n-1)
 
+// ---- anatomy of the resident path (-DPCHAIN_TPROF builds only; tools/probe_static_anatomy.py) ---------------------------------
+// Every wave adds, per visit kind (slot) and wave class (0: the epilogue waves 0 .. 3, 1: waves 4 .. 15), {tiles, polls, ticks from
+// the first issue to the successful poll, ticks from there to the tile's last T16 store (waves that store nothing: to the tile's
+// end)} to a table in LDS; the first workgroup of each role copies its table to the blvm_pchain_profile buffer when it is done:
+// words [kAnatBase + role * kAnatRole + (slot * 2 + class) * 4 + j].  Roles: 0 / 1 forward halves (or the chain probe), 2 / 3
+// backward halves, 4 the backward's spare range.  Slot = 4 * (index of the link in its program) + link of the run.
+constexpr int kAnatBase = 128, kAnatRole = 512, kAnatSlots = 48;
+#ifdef PCHAIN_TPROF
+__device__ __forceinline__ void anat_begin(unsigned* tab) {
+  for (int i = threadIdx.x; i < kAnatSlots * 8; i += blockDim.x) tab[i] = 0u;
+  __syncthreads();
+}
+__device__ __forceinline__ void anat_arm(Poll& pl) { pl.rpolls = 0; pl.t_st = 0; }
+__device__ __forceinline__ void anat_note(unsigned* tab, int slot, const Poll& pl) {
+  const unsigned long long now = wall_clock64();
+  if ((threadIdx.x & 63) == 0 && pl.rpolls != 0) {
+    unsigned* q = tab + (slot * 2 + (threadIdx.x < 256 ? 0 : 1)) * 4;
+    atomicAdd(q, 1u); atomicAdd(q + 1, pl.rpolls); atomicAdd(q + 2, (unsigned)(pl.t_ok - pl.t_issue));
+    atomicAdd(q + 3, (unsigned)((pl.t_st != 0 ? pl.t_st : now) - pl.t_ok));
+  }
+}
+__device__ __forceinline__ void anat_end(const unsigned* tab, unsigned long long* prof, int role, bool chosen) {
+  __syncthreads();
+  if (prof != nullptr && chosen)
+    for (int i = threadIdx.x; i < kAnatSlots * 8; i += blockDim.x) prof[kAnatBase + role * kAnatRole + i] = tab[i];
+}
+#define ANAT(x) x
+#else
+#define ANAT(x)
+#endif
+
 // ---- gate: a linear-only chain ---------------------------------------------------------------------------------------------
 // x_{s+1} = relu(x_s W^T + b) as ONE K_LIN link per step (the program of blvm_pchain_chain_probe), K = 256 or 512 at compile time
 struct LinChainArgs {
@@ -54,13 +85,22 @@ struct LinChainArgs {
   const float *W, *bias;
   int ldo, n16, B, s0, S, wg0, nwg, ct, xcd;
   Ctl ctl;
+  int pace_early, pace_epi;  // the run-time pacing policy's delays (PaceRt; the probe's sweep)
+  ANAT(unsigned long long* prof;)
 };
+template <class PC>
+__device__ __forceinline__ PC chain_pace(const LinChainArgs& a) {
+  if constexpr (PC::paced) return PC{a.pace_early, a.pace_epi};
+  else return PC();
+}
 
 // RES: the workgroup owns one tile; its weight fragments are loaded once, in front of the step loop (pchain.h "resident weights"),
 // and a step is poll -> MFMA -> reduce -> epilogue.  !RES re-reads them every step (the form the probe prices the resident one against).
-template <int NW, int K, bool RES>
+// PC: the poll pacing policy of the resident form (pchain.h): PaceOff, or PaceRt with the delays of the arguments.
+template <int NW, int K, bool RES, class PC = PaceOff>
 __global__ __launch_bounds__(NW * 64, 1) void static_lin_chain_kernel(LinChainArgs a) {
   __shared__ __attribute__((aligned(16))) float red[2][NW * 256];
+  ANAT(__shared__ unsigned anat[kAnatSlots * 8]; anat_begin(anat);)
   const int w = blockIdx.x, B = a.B;
   const int tiles = tile_lanes(w, a.wg0, a.nwg, (B + 15) / 16, a.ct, a.xcd != 0);
   const int nt = tile_count(tiles);
@@ -73,12 +113,16 @@ __global__ __launch_bounds__(NW * 64, 1) void static_lin_chain_kernel(LinChainAr
     const float* const Ws[1] = {a.W};
     const int cs[1] = {c0};
     load_w<NW, OP_F32, 1, K / (16 * NW)>(ws.w, Ws, cs, K);
+    const PC pace = chain_pace<PC>(a);
     for (int s = a.s0; s < a.S; ++s) {
       pl.code = (unsigned)s << 4;
       auto late = [&]() { return LinLate{a.bias, nullptr, nullptr, 0, 0, false, true, 0.f, Out{a.orm.at(s), a.ldo, false, a.o16.at(s), a.n16}}; };
-      tile_lin_late<NW, OP_F32>(a.a16.at(s), 0, true, a.W, K, late, r0, c0, B, red[par], pl, nullptr, nullptr, 0, ws);
+      ANAT(anat_arm(pl);)
+      tile_lin_late<NW, OP_F32>(a.a16.at(s), 0, true, a.W, K, late, r0, c0, B, red[par], pl, nullptr, nullptr, 0, ws, pace);
+      ANAT(anat_note(anat, 0, pl);)
       par ^= 1;
     }
+    ANAT(anat_end(anat, a.prof, 0, w == a.wg0);)
     return;
   }
   for (int s = a.s0; s < a.S; ++s) {
@@ -146,6 +190,7 @@ struct Walk {
   float* red1;
   int par, B;
   Poll pl;
+  ANAT(unsigned* anat;)
   __device__ __forceinline__ float* red() { par ^= 1; return par ? red0 : red1; }
   __device__ __forceinline__ void at(const Deal& d, int s, bool gentle, unsigned li = 0) {
     pl.nap = gentle ? 16 : 1;
@@ -204,8 +249,22 @@ __device__ __forceinline__ void load_grub(Res<kH, 2>& r, const GrubArgs& q, int 
   load_w<NW, OP_F32, 2, 1>(r.w, Ws, cs, kH);
 }
 
+// Poll pacing (pchain.h): a link in lock step with its producers delays its first poll (Paced), by the same amount whatever the
+// producer: longer delays behind the fat tiles (heads, GRU, GRU backward, dz), whose store comes later, measured no better.  Roles
+// that reach a visit links before its operand exists (the posterior half's GRU tile; in the backward the posterior half's run and
+// the spare range's partial sum) are not paced: a delay cannot fix the phase of a poll that started long ago.  The gentle links
+// (WMem) are not paced either.  The values come from tools/probe_static_chain.py --paced, tools/probe_static_anatomy.py and a
+// sweep of bench.py; -D overrides them for such sweeps.
+#ifndef VRNN_PACE_EARLY
+#define VRNN_PACE_EARLY 8  // s_sleep units, the waves that leave the previous tile at its barrier
+#endif
+#ifndef VRNN_PACE_EPI
+#define VRNN_PACE_EPI 4  // the epilogue waves
+#endif
+typedef PaceK<VRNN_PACE_EARLY, VRNN_PACE_EPI> Paced;
+
 // WS: Res<K> — the link's one tile on resident weights; WMem — every tile the deal gives, weights read per tile
-template <int NW, int K, int FLAGS, class WS>
+template <int NW, int K, int FLAGS, class PC = PaceOff, class WS>
 __device__ __forceinline__ void visit_lin(const LinArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const WS& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   constexpr bool sum3 = (FLAGS & DF_A_SUM3) != 0;
@@ -220,11 +279,13 @@ __device__ __forceinline__ void visit_lin(const LinArgs& q, const Deal& d, int s
   for (int tk = 0; tk < (WS::resident ? 1 : nt); ++tk) {
     const int trc = __builtin_amdgcn_readlane(tiles, tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
     if constexpr ((FLAGS & DF_CANARY) != 0) canary_wait(A, tr0, K, wk.pl, q.ld0);
-    tile_lin_late<NW, OP_F32>(A, q.ld0, true, q.W, K, late, tr0, tc0, wk.B, wk.red(), wk.pl, A2, A3, q.w_width, ws);
+    ANAT(anat_arm(wk.pl);)
+    tile_lin_late<NW, OP_F32>(A, q.ld0, true, q.W, K, late, tr0, tc0, wk.B, wk.red(), wk.pl, A2, A3, q.w_width, ws, PC());
+    ANAT(anat_note(wk.anat, 4 * d.idx, wk.pl);)
   }
 }
 
-template <int NW, int N, int K0, int K, bool GATED>
+template <int NW, int N, int K0, int K, bool GATED, class P0 = PaceOff>  // P0: the first link's pacing; the others are Paced
 __device__ __forceinline__ void visit_run(const SeqArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const RunRes<N, K0, K>& rr) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   const int trc = __builtin_amdgcn_readlane(tiles, 0), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
@@ -237,34 +298,40 @@ __device__ __forceinline__ void visit_run(const SeqArgs& q, const Deal& d, int s
       return LinLate{GATED ? nullptr : aux, li == 0 ? q.add0.at(s) : nullptr, GATED ? aux : nullptr, q.ldadd0, q.ldgate, false, !GATED, q.slope,
                      Out{q.orm[li].at(s), q.ld[li], false, q.o16[li].at(s), q.n16}};
     };
-    if (li == 0) tile_lin_late<NW, OP_F32>(A, 0, true, q.W[li], K0, late, tr0, tc0, wk.B, wk.red(), wk.pl, nullptr, nullptr, 0, rr.first);
-    else tile_lin_late<NW, OP_F32>(A, 0, true, q.W[li], K, late, tr0, tc0, wk.B, wk.red(), wk.pl, nullptr, nullptr, 0, rr.rest[li > 0 ? li - 1 : 0]);
+    ANAT(anat_arm(wk.pl);)
+    if (li == 0) tile_lin_late<NW, OP_F32>(A, 0, true, q.W[li], K0, late, tr0, tc0, wk.B, wk.red(), wk.pl, nullptr, nullptr, 0, rr.first, P0());
+    else tile_lin_late<NW, OP_F32>(A, 0, true, q.W[li], K, late, tr0, tc0, wk.B, wk.red(), wk.pl, nullptr, nullptr, 0, rr.rest[li > 0 ? li - 1 : 0], Paced());
+    ANAT(anat_note(wk.anat, 4 * d.idx + li, wk.pl);)
     A = q.o16[li].at(s);  // the next link multiplies what this one stored
   }
 }
 
-template <int NW>
+template <int NW, class PC = PaceOff>
 __device__ __forceinline__ void visit_head(const HeadArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const Res<kH, 4>& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   wk.at(d, s, false);
   const HeadOut o{q.mu_p.at(s), q.sd_p.at(s), q.mu_q.at(s), q.sd_q.at(s), q.raw_p.at(s), q.raw_q.at(s), q.muq_raw.at(s),
                   Out{q.z.at(s), q.ld3, false, q.z16.at(s), q.n16, q.z16b.at(s), q.n16b}};
   const int trc = __builtin_amdgcn_readlane(tiles, 0);
+  ANAT(anat_arm(wk.pl);)
   tile_head<NW, OP_F32>(q.P.at(s), q.Q.at(s), true, q.Wp, q.bp, q.Wq, q.bq, q.eps.at(s), o, kH, q.Z, q.residual, q.beta, q.inv_beta, q.sd_eps,
-                        trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl, ws);
+                        trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl, ws, PC());
+  ANAT(anat_note(wk.anat, 4 * d.idx, wk.pl);)
 }
 
-template <int NW>
+template <int NW, class PC = PaceOff>
 __device__ __forceinline__ void visit_gru(const GruArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const Res<kH, 3>& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   wk.at(d, s, false);
   const Out o{q.hrm.at(s), q.ld3, true, q.h16.at(s), q.n16, q.h16b.at(s), q.n16b};
   const int trc = __builtin_amdgcn_readlane(tiles, 0);
+  ANAT(anat_arm(wk.pl);)
   tile_gru<NW, OP_F32>(q.X.at(s), 0, true, q.Wih, kH, q.xg.at(s), q.bih, q.gh.at(s), q.hprev.at(s), q.ld0, q.R, o, q.rg.at(s), q.ug.at(s), q.ng.at(s),
-                       trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl, ws);
+                       trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl, ws, PC());
+  ANAT(anat_note(wk.anat, 4 * d.idx, wk.pl);)
 }
 
-template <int NW>
+template <int NW, class PC = PaceOff>
 __device__ __forceinline__ void visit_dz(const DzArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const Res<kH>& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   wk.at(d, s, false);
@@ -277,13 +344,15 @@ __device__ __forceinline__ void visit_dz(const DzArgs& q, const Deal& d, int s, 
   z.has_gemm = s >= q.first_gemm;
   const Out oq{q.dqh.at(s), q.ld3, false, q.dqh16.at(s), q.n16}, op{q.dph.at(s), q.ld3, false, q.dph16.at(s), q.n16};
   const int trc = __builtin_amdgcn_readlane(tiles, 0);
+  ANAT(anat_arm(wk.pl);)
   tile_dz<NW, OP_F32>(q.D.at(s), q.WT, nullptr, nullptr, true, q.add.at(s), q.ld1, false, z, oq, op, kH, q.Z, trc & 0xffff, (trc >> 16) * 16, wk.B,
-                      wk.red(), wk.pl, ws);
+                      wk.red(), wk.pl, ws, PC());
+  ANAT(anat_note(wk.anat, 4 * d.idx, wk.pl);)
   // ws holds ONE product's fragments (Res<kH>), so tile_dz runs its single-operand form whatever D2 is: vrnn_static_bwd returns
   // "not applicable" for a program whose dz descriptor has a second operand (DZ_D2_16 != null).  Keep the two in step.
 }
 
-template <int NW>
+template <int NW, class PC = PaceOff>
 __device__ __forceinline__ void visit_grub(const GrubArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const Res<kH, 2>& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   wk.at(d, s, false);
@@ -295,7 +364,9 @@ __device__ __forceinline__ void visit_grub(const GrubArgs& q, const Deal& d, int
   g.ga = q.ga.at(s); g.g_out = const_cast<float*>(q.g_out);
   g.has_gemm = s >= q.first_gemm; g.has_gates = s < q.end_gates; g.has_gin = s >= q.first_gin;
   const int trc = __builtin_amdgcn_readlane(tiles, 0);
-  tile_grub<NW, OP_F32>(g, kH, q.R, trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl, ws);
+  ANAT(anat_arm(wk.pl);)
+  tile_grub<NW, OP_F32>(g, kH, q.R, trc & 0xffff, (trc >> 16) * 16, wk.B, wk.red(), wk.pl, ws, PC());
+  ANAT(anat_note(wk.anat, 4 * d.idx, wk.pl);)
 }
 
 // The kernel's own argument block (offset 0 of the kernarg segment) through a pointer the compiler cannot see through: every visit
@@ -321,6 +392,7 @@ struct FwdArgs {
   Deal deal[6];
   int B, s0, S, xcd;
   Ctl ctl;
+  ANAT(unsigned long long* prof;)
 };
 constexpr int kFwdProducts = 4, kBwdProducts = 2;
 
@@ -341,11 +413,14 @@ __device__ __forceinline__ void fwd_half(const FwdArgs& a, int w, int rt, bool x
   load_run<NW>(phi, kargs<FwdArgs>().phi, t4, n4);
   load_gru<NW>(gru, kargs<FwdArgs>().gru, t5, n5);
   for (int s = a.s0; s < a.S; ++s) {
-    visit_run<NW, 3, kR, kH, false>(kargs<FwdArgs>().run[HALF], kargs<FwdArgs>().deal[1 + HALF], s, t1, n1, wk, run);
-    visit_head<NW>(kargs<FwdArgs>().head, kargs<FwdArgs>().deal[3], s, t3, n3, wk, head);
-    visit_run<NW, 4, kH, kH, false>(kargs<FwdArgs>().phi, kargs<FwdArgs>().deal[4], s, t4, n4, wk, phi);
-    visit_gru<NW>(kargs<FwdArgs>().gru, kargs<FwdArgs>().deal[5], s, t5, n5, wk, gru);
+    visit_run<NW, 3, kR, kH, false, Paced>(kargs<FwdArgs>().run[HALF], kargs<FwdArgs>().deal[1 + HALF], s, t1, n1, wk, run);
+    visit_head<NW, Paced>(kargs<FwdArgs>().head, kargs<FwdArgs>().deal[3], s, t3, n3, wk, head);
+    visit_run<NW, 4, kH, kH, false, Paced>(kargs<FwdArgs>().phi, kargs<FwdArgs>().deal[4], s, t4, n4, wk, phi);
+    // (the posterior half reaches its GRU tile while the prior half still walks the heads and the phi_z run: not paced)
+    if constexpr (HALF == 0) visit_gru<NW, Paced>(kargs<FwdArgs>().gru, kargs<FwdArgs>().deal[5], s, t5, n5, wk, gru);
+    else visit_gru<NW>(kargs<FwdArgs>().gru, kargs<FwdArgs>().deal[5], s, t5, n5, wk, gru);
   }
+  ANAT(anat_end(wk.anat, kargs<FwdArgs>().prof, HALF, w == kargs<FwdArgs>().deal[1 + HALF].wg0);)
 }
 
 template <int NW>
@@ -354,6 +429,7 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_fwd_kernel(FwdArgs a) 
   const int w = blockIdx.x, rt = (a.B + 15) / 16;
   const bool xcd = a.xcd != 0;
   Walk wk{lds_red, lds_red + kFwdProducts * NW * 256, 0, a.B, Poll{a.ctl, 0u, false, 1}};
+  ANAT(__shared__ unsigned anat[kAnatSlots * 8]; anat_begin(anat); wk.anat = anat;)
   // roles, picked once: the gentle range runs the hidden projection alone, the others are a half's workgroups (fwd_half)
   if (w >= a.deal[0].wg0) {
     const int t0 = tile_lanes(w, a.deal[0].wg0, a.deal[0].nwg, rt, a.deal[0].ct, xcd), n0 = tile_count(t0);
@@ -377,6 +453,7 @@ struct BwdArgs {
   Deal deal[10];
   int B, s0, S, xcd;
   Ctl ctl;
+  ANAT(unsigned long long* prof;)
 };
 
 // a workgroup of the prior (HALF 0) or posterior (1) half: its half's partial sum and run of three and whatever tile of the GRU
@@ -401,13 +478,16 @@ __device__ __forceinline__ void bwd_half(const BwdArgs& a, int w, int rt, bool x
   load_lin<NW, kH>(dz, kargs<BwdArgs>().dz.WT, kH, t7, n7);
   load_run<NW>(run, kargs<BwdArgs>().run[HALF], t8, n8);
   for (int s = a.s0; s < a.S; ++s) {
-    visit_grub<NW>(kargs<BwdArgs>().grub, kargs<BwdArgs>().deal[0], s, t0, n0, wk, grub);
-    visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[HALF], kargs<BwdArgs>().deal[1 + HALF], s, t1, n1, wk, part);
-    visit_lin<NW, kH, DF_A_SUM3>(kargs<BwdArgs>().sum, kargs<BwdArgs>().deal[5], s, t5, n5, wk, sum);
-    visit_run<NW, 2, kH, kH, true>(kargs<BwdArgs>().phi, kargs<BwdArgs>().deal[6], s, t6, n6, wk, phi);
-    visit_dz<NW>(kargs<BwdArgs>().dz, kargs<BwdArgs>().deal[7], s, t7, n7, wk, dz);
-    visit_run<NW, 3, 2 * kH, kH, true>(kargs<BwdArgs>().run[HALF], kargs<BwdArgs>().deal[8 + HALF], s, t8, n8, wk, run);
+    visit_grub<NW, Paced>(kargs<BwdArgs>().grub, kargs<BwdArgs>().deal[0], s, t0, n0, wk, grub);
+    visit_lin<NW, kR, 0, Paced>(kargs<BwdArgs>().part[HALF], kargs<BwdArgs>().deal[1 + HALF], s, t1, n1, wk, part);
+    visit_lin<NW, kH, DF_A_SUM3, Paced>(kargs<BwdArgs>().sum, kargs<BwdArgs>().deal[5], s, t5, n5, wk, sum);
+    visit_run<NW, 2, kH, kH, true, Paced>(kargs<BwdArgs>().phi, kargs<BwdArgs>().deal[6], s, t6, n6, wk, phi);
+    visit_dz<NW, Paced>(kargs<BwdArgs>().dz, kargs<BwdArgs>().deal[7], s, t7, n7, wk, dz);
+    // (the posterior half reaches its run while the prior half still walks the summing link, the phi_z run and dz: not paced)
+    if constexpr (HALF == 0) visit_run<NW, 3, 2 * kH, kH, true, Paced>(kargs<BwdArgs>().run[HALF], kargs<BwdArgs>().deal[8 + HALF], s, t8, n8, wk, run);
+    else visit_run<NW, 3, 2 * kH, kH, true>(kargs<BwdArgs>().run[HALF], kargs<BwdArgs>().deal[8 + HALF], s, t8, n8, wk, run);
   }
+  ANAT(anat_end(wk.anat, kargs<BwdArgs>().prof, 2 + HALF, w == kargs<BwdArgs>().deal[1 + HALF].wg0);)
 }
 
 template <int NW>
@@ -416,12 +496,14 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) 
   const int w = blockIdx.x, rt = (a.B + 15) / 16;
   const bool xcd = a.xcd != 0;
   Walk wk{lds_red, lds_red + kBwdProducts * NW * 256, 0, a.B, Poll{a.ctl, 0u, false, 1}};
+  ANAT(__shared__ unsigned anat[kAnatSlots * 8]; anat_begin(anat); wk.anat = anat;)
   if (w >= a.deal[3].wg0) {  // spare range: the third partial sum alone
     const int t = tile_lanes(w, a.deal[3].wg0, a.deal[3].nwg, rt, a.deal[3].ct, xcd), n = tile_count(t);
     if (n == 0) return;
     Res<kR> part;
     load_lin<NW, kR>(part, kargs<BwdArgs>().part[2].W, kargs<BwdArgs>().part[2].w_width, t, n);
     for (int s = a.s0; s < a.S; ++s) visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[2], kargs<BwdArgs>().deal[3], s, t, n, wk, part);
+    ANAT(anat_end(wk.anat, kargs<BwdArgs>().prof, 4, w == kargs<BwdArgs>().deal[3].wg0);)
     return;
   }
   if (w >= a.deal[4].wg0) {  // gentle range: GB alone
@@ -465,7 +547,8 @@ int static_go(Kern kernel, int slot, int grid, size_t lds, const char* what) {
 }
 
 // 1: the program is not the linear chain the static kernel was compiled for (resident: or it deals a workgroup more than one tile)
-int static_lin_chain_launch(const Program& p, hipStream_t stream, bool resident) {
+// pace (resident only): the first-poll delays of early / epi s_sleep units instead of the plain poll loop
+int static_lin_chain_launch(const Program& p, hipStream_t stream, bool resident, bool pace = false, int early = 0, int epi = 0) {
   if (p.ndesc != 1 || p.ot != OP_F32 || p.rt_group != 1 || !int_strides(p)) return 1;
   const Desc& d = p.d[0];
   if (d.kind != K_LIN || d.flags != DF_RELU || d.f[LIN_F_SLOPE] != 0.f || (d.K != 256 && d.K != 512) || d.s_begin != 0 || d.s_end != p.S) return 1;
@@ -474,7 +557,8 @@ int static_lin_chain_launch(const Program& p, hipStream_t stream, bool resident)
   const int rt = (p.B + 15) / 16;
   if (d.nwg <= 0 || (p.xcd && d.nwg % 8 != 0) || tiles_per_workgroup(rt, d.ct, d.nwg, p.xcd != 0) > (resident ? 1 : kMaxTiles)) return 1;
   LinChainArgs a{sptr(p, d, LIN_A), sptr(p, d, LIN_ORM), sptr(p, d, LIN_O16), d.p[LIN_W], d.p[LIN_BIAS], d.ld[LD_OUT], d.n16[N16_OUT], p.B, p.s_first, p.S,
-                 d.wg0, d.nwg, d.ct, p.xcd, p.ctl};
+                 d.wg0, d.nwg, d.ct, p.xcd, p.ctl, early, epi};
+  ANAT(a.prof = pchain_profile_buffer();)
   const int grid = d.wg0 + d.nwg;
   auto go = [&](auto kernel) -> int {
     BLVM_TRY(static_go(kernel, 2, grid, 0, "static_lin_chain"));
@@ -482,6 +566,7 @@ int static_lin_chain_launch(const Program& p, hipStream_t stream, bool resident)
     BLVM_CHECK_LAUNCH("static_lin_chain");
     return BLVM_OK;
   };
+  if (resident && pace) return d.K == 256 ? go(&static_lin_chain_kernel<16, 256, true, PaceRt>) : go(&static_lin_chain_kernel<16, 512, true, PaceRt>);
   if (resident) return d.K == 256 ? go(&static_lin_chain_kernel<16, 256, true>) : go(&static_lin_chain_kernel<16, 512, true>);
   return d.K == 256 ? go(&static_lin_chain_kernel<16, 256, false>) : go(&static_lin_chain_kernel<16, 512, false>);
 }
@@ -557,6 +642,7 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
   int grid = 0;
   for (int i = 0; i < 6; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.ctl = p.ctl;
+  ANAT(a.prof = pchain_profile_buffer();)
   const size_t lds = sizeof(float) * 2 * kFwdProducts * 16 * 256;
   BLVM_TRY(static_go(&vrnn_static_fwd_kernel<16>, 0, grid, lds, "vrnn_static_fwd"));
   hipLaunchKernelGGL(vrnn_static_fwd_kernel<16>, dim3(grid), dim3(1024), lds, stream, a);
@@ -603,6 +689,7 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream) {
   int grid = 0;
   for (int i = 0; i < 10; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.ctl = p.ctl;
+  ANAT(a.prof = pchain_profile_buffer();)
   const size_t lds = sizeof(float) * 2 * kBwdProducts * 16 * 256;
   BLVM_TRY(static_go(&vrnn_static_bwd_kernel<16>, 1, grid, lds, "vrnn_static_bwd"));
   hipLaunchKernelGGL(vrnn_static_bwd_kernel<16>, dim3(grid), dim3(1024), lds, stream, a);
@@ -630,7 +717,8 @@ extern "C" int blvm_pchain_static(int mode) {
 
 // blvm_pchain_chain_probe's chain (one K_LIN descriptor per link, the same Builder program) walked by the static kernel.  N = 256 or 512.
 // resident: the weights stay in registers for the launch (at most one tile per workgroup), else they are re-read every link.
-static int static_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream_, bool resident) {
+static int static_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream_, bool resident,
+                              bool pace = false, int early = 0, int epi = 0) {
   using namespace blvm;
   using namespace blvm::pchain;
   hipStream_t s = static_cast<hipStream_t>(stream_);
@@ -645,7 +733,7 @@ static int static_chain_probe(const float* W16, const float* bias, float* x16, f
   add_desc(bld, K_LIN, N / 16, 0, nw, N, DF_RELU, 0, L, o);
   BLVM_HIP(pchain_fill_sentinel(x16 + x, sizeof(float) * (size_t)x * L, s));
   BLVM_TRY(pchain_prepare(bld, "pchain_static_chain_probe"));
-  const int rc = static_lin_chain_launch(bld.p, s, resident);
+  const int rc = static_lin_chain_launch(bld.p, s, resident, pace, early, epi);
   BLVM_REQUIRE(rc != 1, "pchain_static_chain_probe: no static kernel for N = %d (256, 512) or this deal", N);
   return rc;
 }
@@ -654,4 +742,14 @@ extern "C" int blvm_pchain_static_chain_probe(const float* W16, const float* bia
 }
 extern "C" int blvm_pchain_static_chain_probe_fetch(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream) {
   return static_chain_probe(W16, bias, x16, xs, B, N, L, nwg, stream, false);
+}
+// The resident form under a poll pacing policy (pchain.h): the first poll of a tile waits `early_delay` s_sleep units on the waves that
+// leave the previous tile at its barrier and `epi_delay` on the epilogue waves (0 .. 64 each).  Both zero is
+// blvm_pchain_static_chain_probe's plain loop.  Probe only: the VRNN walks take their pacing at compile time.
+extern "C" int blvm_pchain_static_chain_probe_paced(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg,
+                                                    int early_delay, int epi_delay, void* stream) {
+  using namespace blvm;
+  BLVM_REQUIRE(early_delay >= 0 && early_delay <= 64 && epi_delay >= 0 && epi_delay <= 64,
+               "pchain_static_chain_probe_paced: delays are 0 .. 64 s_sleep units");
+  return static_chain_probe(W16, bias, x16, xs, B, N, L, nwg, stream, true, (early_delay | epi_delay) != 0, early_delay, epi_delay);
 }

@@ -101,6 +101,11 @@ int blvm_pchain_chain_probe(const float* W16, const float* bias, float* x16, flo
 /* (the weights of a workgroup's tile stay in registers for the launch; _fetch: re-read every link, the form it is priced against) */
 int blvm_pchain_static_chain_probe(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream);
 int blvm_pchain_static_chain_probe_fetch(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg, void* stream);
+/* The register-resident form under a poll pacing policy (csrc/pchain.h): the first poll of a tile waits early_delay s_sleep units
+   on the waves that leave the previous tile at its barrier and epi_delay on the epilogue waves (0 .. 64 each).  Both zero is
+   blvm_pchain_static_chain_probe.  Probe only (tools/probe_static_chain.py --paced). */
+int blvm_pchain_static_chain_probe_paced(const float* W16, const float* bias, float* x16, float* xs, int B, int N, int L, int nwg,
+                                         int early_delay, int epi_delay, void* stream);
 /* dst = T16 operand copy [ceil(B/16)*16, K] of the rows of src [B,K] (row stride ld). */
 int blvm_pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, void* stream);
 /* n host integers -> device memory through kernel arguments (asynchronous on `stream`; a pageable hipMemcpy would block the host

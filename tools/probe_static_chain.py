@@ -4,7 +4,12 @@ kernel in its two forms — `fetch`: the weight fragments are re-read every link
 in registers — alternately in one process.  All outputs must match bit for bit.  Per shape: `--repeats` rounds (each figure the best
 of three launches), the spread of the fetch form over the rounds and the median gain of the resident form over it.
 
---bare PATH: also run the bare tile loop (tools/pchain_probe.hip built to PATH) and print its output beside the rows."""
+--bare PATH: also run the bare tile loop (tools/pchain_probe.hip built to PATH) and print its output beside the rows.
+
+--paced E:P[,E:P...]: also run the resident form under each poll pacing setting (csrc/pchain.h "poll pacing"; first-poll delay of E
+s_sleep units on the waves that leave a tile at its barrier and P on the epilogue waves, blvm_pchain_static_chain_probe_paced),
+alternated with the others in every round, checked bit for bit, and print per shape each setting's median, spread and gain over the
+plain resident form."""
 import argparse, os, statistics, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "benchmarking-lvms_amd"))
@@ -12,6 +17,10 @@ import torch
 from blvm import _hip
 from blvm._hip import ptr, stream_ptr, check
 lib = _hip.load(); dev = "cuda:0"
+
+
+def paced(early, epi):
+    return lambda W16, b, x16, xs, B, N, L, nwg, stream: lib.blvm_pchain_static_chain_probe_paced(W16, b, x16, xs, B, N, L, nwg, early, epi, stream)
 
 
 def chain(fn, B, N, L, reps=3):
@@ -39,10 +48,12 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--links", type=int, default=2000)
     ap.add_argument("--bare", default=None, help="the built tools/pchain_probe binary")
+    ap.add_argument("--paced", default="", help="pacing settings EARLY:EPI, comma separated")
     args = ap.parse_args()
     L = args.links
+    settings = [tuple(int(v) for v in item.split(":")) for item in args.paced.split(",") if item]
     for B, N in ((64, 256), (8, 256), (64, 512), (8, 512)):
-        fetch, res = [], []
+        fetch, res, pc = [], [], {st: [] for st in settings}
         for rep in range(args.repeats):  # alternate
             te, xe = chain(lib.blvm_pchain_chain_probe, B, N, L)
             tf, xf = chain(lib.blvm_pchain_static_chain_probe_fetch, B, N, L)
@@ -52,8 +63,18 @@ if __name__ == "__main__":
             if not same:
                 sys.exit(1)
             fetch.append(tf); res.append(tr)
+            for st in settings:
+                tp, xp = chain(paced(*st), B, N, L)
+                ok = bool(torch.equal(xp, xr))
+                print(f"   paced early={st[0]} epi={st[1]}: {tp:.3f} us/link, bit-identical: {ok}", flush=True)
+                if not ok:
+                    sys.exit(1)
+                pc[st].append(tp)
         print(f"B={B} N=K={N}: fetch median {statistics.median(fetch):.3f} spread {max(fetch) - min(fetch):.3f}, resident median "
               f"{statistics.median(res):.3f} spread {max(res) - min(res):.3f}, gain {statistics.median(fetch) - statistics.median(res):.3f} us/link", flush=True)
+        for st in settings:
+            print(f"B={B} N=K={N}: paced early={st[0]} epi={st[1]} median {statistics.median(pc[st]):.3f} spread {max(pc[st]) - min(pc[st]):.3f}, "
+                  f"gain over resident {statistics.median(res) - statistics.median(pc[st]):+.3f} us/link", flush=True)
     if args.bare:
         print(f"bare tile loop ({args.bare} {L} 1):", flush=True)
         out = subprocess.run([args.bare, str(L), "1"], capture_output=True, text=True, timeout=300)
