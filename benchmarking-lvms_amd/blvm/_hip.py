@@ -126,6 +126,7 @@ _SIGNATURES = {
     "blvm_srnn_generate": (c_int, [ctypes.POINTER(SrnnDecodeWeights)] + [c_void_p] * 6 + [c_int] * 7 + [c_float] * 3 + [c_void_p] * 5),
     "blvm_lstm_generate_scratch_floats": (c_size_t, [c_int] * 5),
     "blvm_lstm_generate": (c_int, [ctypes.POINTER(LstmDecodeWeights)] + [c_void_p] * 5 + [c_int] * 6 + [c_float] + [c_void_p] * 5),
+    "blvm_lstm_generate_any_stack": (c_int, [ctypes.POINTER(LstmDecodeWeights)] + [c_void_p] * 5 + [c_int] * 6 + [c_float] + [c_void_p] * 5),
     "blvm_vrnn_generate_scratch_floats": (c_size_t, [c_int] * 6),
     "blvm_vrnn_generate": (c_int, [ctypes.POINTER(VrnnDecodeWeights)] + [c_void_p] * 5 + [c_int] * 7 + [c_float] * 3 + [c_void_p] * 4),
     "blvm_vrnn_reserve_floats": (c_size_t, [c_int] * 6),

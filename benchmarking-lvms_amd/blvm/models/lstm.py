@@ -116,8 +116,8 @@ class LSTMAudio(BaseModel):
         [T,n,S,num_mix], v [T,n,S]) replays the sampler's draws; otherwise they come from the device RNG.
         Returns ((x [n,T,S,1], x_sl = T per row), ns(s_n=(h_n, c_n))), s_n as `forward` returns it.
 
-        fused=None takes the one-launch path (`ops.lstm_generate`) whenever S and H are multiples of 16, num_mix is 10 and
-        0 < n <= blvm_pchain_max_batch(), and falls back to the step-by-step path if the library declines; fused=True insists;
+        fused=None takes the one-launch path (`ops.lstm_generate`) whenever H is a multiple of 16, num_mix is 10 and
+        0 < n <= blvm_pchain_max_batch() (any stack size S >= 1), and falls back to the step-by-step path if the library declines; fused=True insists;
         fused=False runs step by step on the sequence kernels, for any width (hidden sizes that are no multiple of 16 run
         zero-padded), num_mix and batch."""
         S, H, L, lik, n, T = self.stack_size, self.hidden_size, self.num_layers, self.likelihood, int(n_samples), int(max_timesteps)
@@ -158,7 +158,7 @@ class LSTMAudio(BaseModel):
             return (torch.empty(n, 0, S, 1, **f32), x_sl), SimpleNamespace(s_n=s_n)
         auto = fused is None
         if auto:
-            fused = S % 16 == 0 and H % 16 == 0 and K == 10 and 0 < n <= ops.load().blvm_pchain_max_batch()
+            fused = H % 16 == 0 and K == 10 and 0 < n <= ops.load().blvm_pchain_max_batch()
         if fused:
             try:
                 xs, h_n, c_n = ops.lstm_generate(emb_lin, self.lstm, dec_lin, lik.params, x, h, c, u, v, S, H, K, lik.log_epsilon, T=T)

@@ -181,8 +181,9 @@ class SRNN(nn.Module):
         z_t from the prior given cat[d_t, z_{t-1}] (its mean if use_mode), decode cat[z_t, d_t], SAMPLE the next frame stack and
         feed it back.  x [B,1,S] start frames.  Returns ((x [B,T,S,1], x_sl), ns(h_p)).  `eps` [T,B,z] and `uniforms`
         (list of the head sampler's draws per step) optionally supply the randomness.  Every step runs K6 / K2 / K3 at T' = 1;
-        `fused` (DMoL head, no stop value, at most `blvm_pchain_max_batch()` utterances; default: whenever that holds) runs ALL steps
-        in one persistent launch (K3c, `ops.srnn_generate`)."""
+        `fused` (DMoL head, no stop value, at most `blvm_pchain_max_batch()` utterances, hidden / latent / recurrent sizes in multiples
+        of 16, any frame-stack size S >= 1; default: whenever that holds) runs ALL steps in one persistent launch (K3c,
+        `ops.srnn_generate`)."""
         if u is not None or x.size(1) > 1:
             raise NotImplementedError("libblvm_hip: SRNN.generate is built for unconditional generation (x [B,1,S], u=None)")
         S, enc_lin, dec_lin, lik = self._plan()
@@ -190,13 +191,13 @@ class SRNN(nn.Module):
         H, Z, R = self.h_dim, self.z_dim, self.r_dim
         n = n_samples
         can_fuse = (stop_value is None and isinstance(lik, DiscretizedLogisticMixtureDense) and len(enc_lin) == 3 and len(dec_lin) == 3
-                    and 0 < n <= ops.load().blvm_pchain_max_batch() and all(v % 16 == 0 for v in (S, H, Z, R)))  # fmt: skip
+                    and 0 < n <= ops.load().blvm_pchain_max_batch() and all(v % 16 == 0 for v in (H, Z, R)))  # fmt: skip
         if fused is None:
             fused = can_fuse
         if fused:
             if not can_fuse:
                 raise NotImplementedError("libblvm_hip: the one-launch SRNN decoder needs the SRNNAudio(DMoL) structure, no stop value, "
-                                          "dimensions in multiples of 16 and at most blvm_pchain_max_batch() utterances")  # fmt: skip
+                                          "hidden, latent and recurrent sizes in multiples of 16 and at most blvm_pchain_max_batch() utterances")  # fmt: skip
             return self._generate_fused(x, d_0, z_0, n, max_timesteps, use_mode, eps, uniforms, S, enc_lin, dec_lin, lik)
         x_sl = torch.zeros(n)
         d_t = torch.zeros(n, R, device=dev) if d_0 is None else d_0.reshape(n, R).contiguous()

@@ -256,13 +256,15 @@ class VRNN(nn.Module):
         stack, which is sampled (or its mode taken) and fed back.  x [B,S,1] initial frame stack; returns ((x [B,1+T,S], x_sl), ns).
         `eps` [T,B,z] optionally supplies the prior noise, `uniforms` = (u [T,B,S,K], v [T,B,S]) the sampler's draws.  Every step
         runs the K6 / K1 / K7-head kernels at T' = 1; `fused=True` (DMoL head, no stop value) runs ALL steps in one launch (K1c);
-        the default (None) takes the one-launch path whenever the model has that structure."""
+        the default (None) takes the one-launch path whenever the model has that structure: hidden, latent and recurrent sizes in
+        multiples of 16, 10 mixture components, any frame-stack size S >= 1 (up to blvm_pchain_max_batch() utterances; beyond that
+        the per-CU form, which needs S % 16 == 0, or else the step-by-step path)."""
         S, enc_lin, dec_lin, lik = self._plan()
         auto = fused is None
         if auto:
             c = self.vrnn_cell
             fused = (stop_value is None and max_timesteps > 0 and isinstance(lik, DiscretizedLogisticMixtureDense) and len(enc_lin) == 3
-                     and len(dec_lin) == 3 and all(v % 16 == 0 for v in (S, c.h_dim, c.z_dim, c.r_dim)))  # fmt: skip
+                     and len(dec_lin) == 3 and all(v % 16 == 0 for v in (c.h_dim, c.z_dim, c.r_dim)))  # fmt: skip
         if fused:
             try:
                 return self._generate_fused(x, h0, n_samples, max_timesteps, stop_value, use_mode, eps, uniforms)

@@ -586,13 +586,36 @@ def _pack_weights(ts: Sequence[Optional[torch.Tensor]]) -> VrnnWeights:
     return w
 
 
+# The one-launch roll-outs (blvm_vrnn_generate, blvm_srnn_generate, blvm_lstm_generate_any_stack) keep one slab per step of every activation in
+# their scratch: at one sample per step a second of audio is 16 000 steps and gigabytes.  A roll-out whose scratch would exceed this
+# many floats (1 GiB) runs as consecutive launches of as many steps as fit, each starting from the previous one's last stack and state.
+MAX_SCRATCH_FLOATS = 2**28
+
+
+def _steps_per_launch(scratch_floats, T, max_scratch_floats, who):
+    """The most steps n <= T with scratch_floats(n) <= max_scratch_floats (scratch_floats: steps -> floats, increasing)."""
+    bound = MAX_SCRATCH_FLOATS if max_scratch_floats is None else int(max_scratch_floats)
+    if scratch_floats(T) <= bound:
+        return T
+    one = scratch_floats(1)
+    if one > bound:
+        raise ValueError(f"{who}: one step needs {one} floats of scratch, max_scratch_floats is {bound}")
+    n = max(1, min(T, 1 + (bound - one) // max(1, scratch_floats(2) - one)))
+    while n > 1 and scratch_floats(n) > bound:
+        n -= 1
+    return n
+
+
 @torch.no_grad()
-def vrnn_decode(enc_lin, cell_params, dec_lin, lik_lin, x0, h0, eps, u, v, S, H, Z, R, num_mix, sd_eps, slope, log_eps, whole_chip=None):
+def vrnn_decode(enc_lin, cell_params, dec_lin, lik_lin, x0, h0, eps, u, v, S, H, Z, R, num_mix, sd_eps, slope, log_eps, whole_chip=None,
+                max_scratch_floats=None):  # fmt: skip
     """K1c: T = eps.shape[0] steps of ancestral sampling for all B utterances in one launch.  enc_lin / dec_lin: 3 nn.Linear each;
     cell_params in `_VRNN_PARAM_ORDER`; lik_lin the DMoL head's Linear.  x0 [B,S], h0 [B,R] or None, eps [T,B,Z],
     u [T,B,S,num_mix] / v [T,B,S] uniforms (None: the mode).  -> (x [B,T,S], h_n [B,R]).
-    whole_chip: True = `blvm_vrnn_generate` (every layer of a step dealt over all CUs, B <= 128), False = `blvm_vrnn_decode`
-    (16 utterances per CU), None = the former whenever it applies."""
+    whole_chip: True = `blvm_vrnn_generate` (every layer of a step dealt over all CUs, B <= 128, any S >= 1), False =
+    `blvm_vrnn_decode` (16 utterances per CU, S a multiple of 16), None = the former whenever it applies.
+    max_scratch_floats (whole chip; None: MAX_SCRATCH_FLOATS): a roll-out whose scratch would be larger runs as consecutive launches
+    of as many steps as fit — the same samples and state, bit for bit."""
     from ._hip import VrnnDecodeWeights
 
     lib = load()
@@ -616,9 +639,21 @@ def vrnn_decode(enc_lin, cell_params, dec_lin, lik_lin, x0, h0, eps, u, v, S, H,
     x = torch.empty(B, T, S, device=dev, dtype=torch.float32)
     hn = torch.empty(B, R, device=dev, dtype=torch.float32)
     if whole_chip:
-        scratch = torch.empty(lib.blvm_vrnn_generate_scratch_floats(T, B, S, H, Z, R), device=dev, dtype=torch.float32)
-        check(lib.blvm_vrnn_generate(ctypes.byref(w), ptr(x0), ptr(h0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, num_mix, sd_eps,
-                                     slope, log_eps, ptr(x), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_generate")  # fmt: skip
+        floats = lambda n: lib.blvm_vrnn_generate_scratch_floats(n, B, S, H, Z, R)  # noqa: E731
+        n = _steps_per_launch(floats, T, max_scratch_floats, "vrnn_decode") if T > 0 else 0
+        scratch = torch.empty(floats(n), device=dev, dtype=torch.float32)
+        if n == T:
+            check(lib.blvm_vrnn_generate(ctypes.byref(w), ptr(x0), ptr(h0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, num_mix, sd_eps,
+                                         slope, log_eps, ptr(x), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_generate")  # fmt: skip
+            return x, hn
+        for t0 in range(0, T, n):
+            t1 = min(T, t0 + n)
+            xc = torch.empty(B, t1 - t0, S, device=dev, dtype=torch.float32)
+            uc, vc = (None, None) if u is None else (u[t0:t1], v[t0:t1])
+            check(lib.blvm_vrnn_generate(ctypes.byref(w), ptr(x0), ptr(h0), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, num_mix,
+                                         sd_eps, slope, log_eps, ptr(xc), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_generate")  # fmt: skip
+            x[:, t0:t1] = xc
+            x0, h0 = xc[:, -1].contiguous(), hn.clone()
         return x, hn
     scratch = torch.empty(lib.blvm_vrnn_decode_scratch_floats(S, H, Z, R), device=dev, dtype=torch.float32)
     check(lib.blvm_vrnn_decode(ctypes.byref(w), ptr(x0), ptr(h0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, num_mix, sd_eps, slope,
@@ -768,11 +803,13 @@ def lstm_decode_weights(emb_lin, lstm, dec_lin, lik_lin):
     return w, (keep, lk, arrays)
 
 
-def lstm_generate(emb_lin, lstm, dec_lin, lik_lin, x0, h0, c0, u, v, S, H, num_mix, log_eps, T=None):
+def lstm_generate(emb_lin, lstm, dec_lin, lik_lin, x0, h0, c0, u, v, S, H, num_mix, log_eps, T=None, max_scratch_floats=None):
     """K4c: T = u.shape[0] steps of sampling from LSTMAudio for all B <= 128 utterances in one persistent launch.  emb_lin / dec_lin:
     3 nn.Linear each; lstm: the nn.LSTM (parameter container, input size H); lik_lin the DMoL head's Linear.  x0 [B,S]; h0, c0
     [num_layers,B,H] or None (zeros); u [T,B,S,num_mix], v [T,B,S] the sampler's draws (both None: the mode, `T` then says how many
-    steps).  -> (x [B,T,S], h_n, c_n [num_layers,B,H])."""
+    steps).  Any S >= 1; H a multiple of 16.  -> (x [B,T,S], h_n, c_n [num_layers,B,H]).
+    max_scratch_floats (None: MAX_SCRATCH_FLOATS): a roll-out whose scratch would be larger runs as consecutive launches of as many
+    steps as fit — the same samples and states, bit for bit."""
     lib = load()
     L, B, dev = lstm.num_layers, x0.shape[0], x0.device
     if (u is None) != (v is None) or (u is None and T is None):
@@ -784,10 +821,22 @@ def lstm_generate(emb_lin, lstm, dec_lin, lik_lin, x0, h0, c0, u, v, S, H, num_m
     c0 = _f32c(c0) if c0 is not None else None
     u, v = (None, None) if u is None else (_f32c(u), _f32c(v))
     f32 = dict(device=dev, dtype=torch.float32)
-    scratch = torch.empty(lib.blvm_lstm_generate_scratch_floats(T, B, S, H, L), **f32)
+    floats = lambda n: lib.blvm_lstm_generate_scratch_floats(n, B, S, H, L)  # noqa: E731
+    n = _steps_per_launch(floats, T, max_scratch_floats, "lstm_generate") if T > 0 else 0
+    scratch = torch.empty(floats(n), **f32)
     x, hn, cn = torch.empty(B, T, S, **f32), torch.empty(L, B, H, **f32), torch.empty(L, B, H, **f32)
-    check(lib.blvm_lstm_generate(ctypes.byref(w), ptr(x0), ptr(h0), ptr(c0), ptr(u), ptr(v), T, B, S, H, L, num_mix, log_eps, ptr(x), ptr(hn),
-                                 ptr(cn), ptr(scratch), stream_ptr()), "blvm_lstm_generate")  # fmt: skip
+    if n == T:
+        check(lib.blvm_lstm_generate_any_stack(ctypes.byref(w), ptr(x0), ptr(h0), ptr(c0), ptr(u), ptr(v), T, B, S, H, L, num_mix, log_eps, ptr(x), ptr(hn),
+                                     ptr(cn), ptr(scratch), stream_ptr()), "blvm_lstm_generate_any_stack")  # fmt: skip
+        return x, hn, cn
+    for t0 in range(0, T, n):
+        t1 = min(T, t0 + n)
+        xc = torch.empty(B, t1 - t0, S, **f32)
+        uc, vc = (None, None) if u is None else (u[t0:t1], v[t0:t1])
+        check(lib.blvm_lstm_generate_any_stack(ctypes.byref(w), ptr(x0), ptr(h0), ptr(c0), ptr(uc), ptr(vc), t1 - t0, B, S, H, L, num_mix, log_eps, ptr(xc),
+                                     ptr(hn), ptr(cn), ptr(scratch), stream_ptr()), "blvm_lstm_generate_any_stack")  # fmt: skip
+        x[:, t0:t1] = xc
+        x0, h0, c0 = xc[:, -1].contiguous(), hn.clone(), cn.clone()
     return x, hn, cn
 
 
@@ -865,11 +914,14 @@ def _pack_srnn(ts):
     return w
 
 
-def srnn_generate(enc_lin, gru, chain_params, dec_lin, lik_lin, x0, d0, z0, eps, u, v, S, H, Z, R, num_mix, sd_eps, slope, log_eps):
+def srnn_generate(enc_lin, gru, chain_params, dec_lin, lik_lin, x0, d0, z0, eps, u, v, S, H, Z, R, num_mix, sd_eps, slope, log_eps,
+                  max_scratch_floats=None):  # fmt: skip
     """K3c: T = eps.shape[0] steps of ancestral sampling from SRNNAudio for all B <= 128 utterances in one persistent launch.
     enc_lin / dec_lin: 3 nn.Linear each; gru: the forward nn.GRU (parameter container); chain_params in `_SRNN_PARAM_ORDER`;
     lik_lin the DMoL head's Linear.  x0 [B,S]; d0 [B,R], z0 [B,Z] or None; eps [T,B,Z]; u [T,B,S,num_mix] / v [T,B,S] (None: the
-    mode).  -> (x [B,T,S], d_T [B,R], z [T,B,Z])."""
+    mode).  Any S >= 1; H, Z, R multiples of 16.  -> (x [B,T,S], d_T [B,R], z [T,B,Z]).
+    max_scratch_floats (None: MAX_SCRATCH_FLOATS): a roll-out whose scratch would be larger runs as consecutive launches of as many
+    steps as fit — the same samples, latents and state, bit for bit."""
     lib = load()
     T, B = eps.shape[0], x0.shape[0]
     dev = x0.device
@@ -890,10 +942,22 @@ def srnn_generate(enc_lin, gru, chain_params, dec_lin, lik_lin, x0, d0, z0, eps,
     u = _f32c(u) if u is not None else None
     v = _f32c(v) if v is not None else None
     f32 = dict(device=dev, dtype=torch.float32)
-    scratch = torch.empty(lib.blvm_srnn_generate_scratch_floats(T, B, S, H, Z, R), **f32)
+    floats = lambda n: lib.blvm_srnn_generate_scratch_floats(n, B, S, H, Z, R)  # noqa: E731
+    n = _steps_per_launch(floats, T, max_scratch_floats, "srnn_generate") if T > 0 else 0
+    scratch = torch.empty(floats(n), **f32)
     x, dn, zs = torch.empty(B, T, S, **f32), torch.empty(B, R, **f32), torch.empty(T, B, Z, **f32)
-    check(lib.blvm_srnn_generate(ctypes.byref(w), ptr(x0), ptr(d0), ptr(z0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, num_mix, sd_eps,
-                                 slope, log_eps, ptr(x), ptr(dn), ptr(zs), ptr(scratch), stream_ptr()), "blvm_srnn_generate")  # fmt: skip
+    if n == T:
+        check(lib.blvm_srnn_generate(ctypes.byref(w), ptr(x0), ptr(d0), ptr(z0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, num_mix, sd_eps,
+                                     slope, log_eps, ptr(x), ptr(dn), ptr(zs), ptr(scratch), stream_ptr()), "blvm_srnn_generate")  # fmt: skip
+        return x, dn, zs
+    for t0 in range(0, T, n):
+        t1 = min(T, t0 + n)
+        xc = torch.empty(B, t1 - t0, S, **f32)
+        uc, vc = (None, None) if u is None else (u[t0:t1], v[t0:t1])
+        check(lib.blvm_srnn_generate(ctypes.byref(w), ptr(x0), ptr(d0), ptr(z0), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, num_mix,
+                                     sd_eps, slope, log_eps, ptr(xc), ptr(dn), ptr(zs[t0:t1]), ptr(scratch), stream_ptr()), "blvm_srnn_generate")  # fmt: skip
+        x[:, t0:t1] = xc
+        x0, d0, z0 = xc[:, -1].contiguous(), dn.clone(), zs[t1 - 1]
     return x, dn, zs
 
 

@@ -1184,6 +1184,10 @@ __device__ __forceinline__ void tile_lstm(const float* X, const float* Wih, int 
 // logistic draw with v (decode_tiles.h; both null: the mode) -> x [B, ldx] (plain) and the T16 copy the next step's
 // encoder multiplies.  Wave w computes head outputs 4w .. 4w+3 of all 64 (utterance, sample) pairs (weights wave-uniform); wave 0
 // then draws.  `lds`: >= 16*4*F + 64*32 floats.
+// Any S >= 1 (stack_pad below): the tiles cover the operand width Sp = 16 ceil(S / 16), ldd is the padded row length of dec (a
+// multiple of 16 floats, so every 16-byte piece is aligned and lies wholly inside or outside a row).  A sample >= S reads no u, v or
+// head input that is checked, stores no x, and writes 0 into its column of the T16 slab — a consumer polls EVERY word of an operand
+// block, so a pad column left as a sentinel would be a spin until the poll bound.
 template <int NW>
 __device__ __forceinline__ void tile_dmol_sample(const float* dec, int ldd, const float* Wl, const float* bl, const float* u, const float* v, int S, int F,
                                                  int num_mix, float log_eps, const Out& xo, int r0, int s0, int B, float* lds, Poll& pl) {
@@ -1199,9 +1203,9 @@ __device__ __forceinline__ void tile_dmol_sample(const float* dec, int ldd, cons
     for (;;) {
       bool bad = false;
       for (int q = tid; q < pieces; q += NW * 64) {
-        const int rr = q / (rowlen / 4), cq = q % (rowlen / 4);
-        const bool ok = r0 + rr < B;
-        const f32x4 x = ld_sc1_x4(rd, 4u * ((unsigned)(ok ? r0 + rr : r0) * (unsigned)ldd + (unsigned)(s0 * F + 4 * cq)));
+        const int rr = q / (rowlen / 4), cq = q % (rowlen / 4), cd = s0 * F + 4 * cq;
+        const bool ok = r0 + rr < B && cd < ldd;  // a piece past the row's end belongs to samples >= S of a ragged stack: not looked at
+        const f32x4 x = ld_sc1_x4(rd, 4u * (ok ? (unsigned)(r0 + rr) * (unsigned)ldd + (unsigned)cd : (unsigned)r0 * (unsigned)ldd));
         bad |= ok && any_sentinel(x);
         *reinterpret_cast<f32x4*>(in + rr * rowlen + 4 * cq) = x;
       }
@@ -1237,13 +1241,15 @@ __device__ __forceinline__ void tile_dmol_sample(const float* dec, int ldd, cons
   __syncthreads();
   if (wave == 0) {
     const int rr = lane >> 2, ss = lane & 3, row = r0 + rr, smp = s0 + ss;
-    if (row < B) {
+    if (row < B && smp < S) {
       const float* p = outp + lane * 32;
       const size_t f = (size_t)row * S + smp;
       const int best = mix_pick(p, num_mix, u != nullptr ? u + f * num_mix : nullptr);
       float x = p[num_mix + best];
       if (v != nullptr) x = logistic_draw(x, p[2 * num_mix + best], v[f], log_eps);
       put(xo, r0, s0 & ~15, row, smp, x);
+    } else if (row < B) {
+      put_t16(xo, r0, s0 & ~15, row, smp, 0.f);  // a pad column of the operand slab: the next step's first link polls it
     }
   }
   __syncthreads();  // the scratch is reused by the next tile
@@ -1297,7 +1303,8 @@ enum : int { DZ_D16, DZ_WT, DZ_D2_16, DZ_WT2, DZ_ADD, DZ_MU_Q, DZ_SD_Q, DZ_MU_P,
 enum : int { GRUB_D0_16, GRUB_D1_16, GRUB_W0, GRUB_W1, GRUB_G_IN, GRUB_RG, GRUB_UG, GRUB_NG, GRUB_GH, GRUB_HPREV, GRUB_DD, GRUB_DGI, GRUB_DGI16,
              GRUB_DGH, GRUB_DGH16, GRUB_GA, GRUB_G_OUT, GRUB_G_ADD, GRUB_LD_H = 0, GRUB_LD_GADD = 1, GRUB_I_R = 0, GRUB_I_GEMM_FROM = 1,
              GRUB_I_GATES_TO = 2, GRUB_I_GIN_FROM = 3 };
-// K_DMOLS (tile_dmol_sample; ct counts tiles of 4 samples): dec (row-major, polled words), head W [F,F], head b, u, v, x row-major | T16
+// K_DMOLS (tile_dmol_sample; ct counts tiles of 4 samples, Sp / 4 of them): dec (row-major, polled words, ld[DMOLS_LD_DEC] = its padded
+// row length), head W [F,F], head b, u, v, x row-major | T16 (n16 = Sp / 16)
 enum : int { DMOLS_DEC, DMOLS_W, DMOLS_B, DMOLS_U, DMOLS_V, DMOLS_X, DMOLS_X16, DMOLS_LD_DEC = 0, DMOLS_I_S = 0, DMOLS_I_F = 1, DMOLS_I_NMIX = 2,
              DMOLS_F_LOG_EPS = 0 };
 // K_GRUS (tile_gru_seq; recurrence step j = s): H16 (state entering the step), Whh (T16), b_hh, xg [T,B,3R] (time indexed), lens, h_prev
@@ -1447,7 +1454,34 @@ inline int pchain_launch(pchain::Builder& bld, const char* who, hipStream_t stre
 int vrnn_launch(pchain::Builder& bld, bool forward, const char* who, hipStream_t stream);
 // dst = T16 copy [ceil(B/16)*16, K] of the rows of src [B, K] (row stride ld; null: zeros); rows >= B are left alone (never read).
 // n16 > 0: dst is a slab of n16 blocks per row tile (a concatenation; dst points at this part's first block)
-int pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, hipStream_t stream, int n16 = 0);
+// k_src > 0: src has only k_src < K columns, the columns k_src .. K-1 of dst are zeros (a padded frame stack)
+int pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, hipStream_t stream, int n16 = 0, int k_src = 0);
+// ---- frame stacks of any size in the one-launch decoders (vrnn_decode.hip, srnn_decode.hip, lstm_decode.h) -------------------------
+// The caller's S samples per step meet the 16-wide tiles in two places, and both are PADDED rather than guarded, so the link tiles are
+// the ones every other program runs:
+//   the frame-stack operand X16: slabs [rows, Sp], Sp = 16 ceil(S / 16); the first link has K = Sp and a packed weight whose columns
+//     S .. Sp-1 are zero; slab 0's pad columns are zeros from the host prefill, slabs 1 .. T get theirs from the draw tile every step;
+//   the last decoder layer DEC: T slabs [B, Np] row-major, Np = 16 ceil(S F / 16) — a padded leading dimension; the packed weight has
+//     zero rows S F .. Np-1 and the bias a zero-padded copy in the scratch, so the tile writes act(0) = 0 into the pad columns, every step.
+// For S % 16 == 0 nothing is padded: Sp = S, Np = S F, no staging, the layouts and descriptors of the unpadded programs.
+struct StackPad {
+  int S, Sp, N, Np;
+  bool padded() const { return Sp != S; }
+  // floats of the zero-padded row-major copies the packs read (the first layer's weight [H, Sp], the last layer's [Np, H] and bias [Np])
+  size_t stage_in(int H) const { return padded() ? (size_t)H * Sp : 0; }
+  size_t stage_dec(int H) const { return padded() ? (size_t)Np * H : 0; }
+  size_t stage_bias() const { return padded() ? (size_t)Np : 0; }
+};
+inline StackPad stack_pad(int S, int F) {
+  const int Sp = (S + 15) / 16 * 16, N = S * F;
+  return StackPad{S, Sp, N, Sp != S ? (N + 15) / 16 * 16 : N};
+}
+// dst [rows_p, cols_p] = src [rows, cols] (both contiguous) in the top left corner, zeros elsewhere
+inline int pad_copy(float* dst, int rows_p, int cols_p, const float* src, int rows, int cols, hipStream_t s) {
+  BLVM_HIP(hipMemsetAsync(dst, 0, sizeof(float) * (size_t)rows_p * cols_p, s));
+  BLVM_HIP(hipMemcpy2DAsync(dst, sizeof(float) * cols_p, src, sizeof(float) * cols, sizeof(float) * cols, rows, hipMemcpyDeviceToDevice, s));
+  return BLVM_OK;
+}
 inline int device_cus() {
   static int v = [] {
     int dev = 0, n = 0;

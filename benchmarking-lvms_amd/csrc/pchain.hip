@@ -539,18 +539,18 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_rt_kernel(const int* __rest
   }
 }
 
-__global__ void rows_to_t16_kernel(const float* src, int ld, int B, int K, float* dst, int n16) {
+__global__ void rows_to_t16_kernel(const float* src, int ld, int B, int K, float* dst, int n16, int k_src) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * K) return;
   const int row = i / K, k = i % K;
-  dst[((size_t)(row >> 4) * n16 + (k >> 4)) * 256 + ((row & 15) + 16 * ((k & 15) >> 2)) * 4 + (k & 3)] = src ? src[(size_t)row * ld + k] : 0.f;
+  dst[((size_t)(row >> 4) * n16 + (k >> 4)) * 256 + ((row & 15) + 16 * ((k & 15) >> 2)) * 4 + (k & 3)] = src && k < k_src ? src[(size_t)row * ld + k] : 0.f;
 }
 
 }  // namespace
 
-int pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, hipStream_t stream, int n16) {
-  BLVM_REQUIRE(B > 0 && K > 0 && K % 16 == 0 && dst != nullptr && (n16 == 0 || n16 >= K / 16), "pchain_rows_to_t16: bad arguments");
-  hipLaunchKernelGGL(rows_to_t16_kernel, dim3((B * K + 255) / 256), dim3(256), 0, stream, src, ld, B, K, dst, n16 > 0 ? n16 : K / 16);
+int pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, hipStream_t stream, int n16, int k_src) {
+  BLVM_REQUIRE(B > 0 && K > 0 && K % 16 == 0 && dst != nullptr && (n16 == 0 || n16 >= K / 16) && k_src >= 0 && k_src <= K, "pchain_rows_to_t16: bad arguments");
+  hipLaunchKernelGGL(rows_to_t16_kernel, dim3((B * K + 255) / 256), dim3(256), 0, stream, src, ld, B, K, dst, n16 > 0 ? n16 : K / 16, k_src > 0 ? k_src : K);
   BLVM_CHECK_LAUNCH("pchain_rows_to_t16");
   return BLVM_OK;
 }

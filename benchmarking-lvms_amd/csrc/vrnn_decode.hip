@@ -414,17 +414,21 @@ size_t vd_lds_bytes(int S, int H, int Z, int R) {
   return sizeof(float) * ((size_t)VD_ROWS * ((S + 4) + 4 * (H + 4) + (R + 4) + (Z + 4) + (VD_CHUNK * VD_F + 4)) + 1024 + 32 + VD_ROWS * VD_CHUNK * 32 + 32 * 16);  // + the op program
 }
 
-struct VdPack { size_t enc[3], prior[3], prior_h, phi[4], wih, whh, dec[3], total; };
+// (whole-chip form, S % 16 != 0 — pchain.h stack_pad: enc[0] is [H, Sp] and dec[2] [Np, H], packed from zero-padded row-major copies
+// staged behind the packs, and the last decoder layer reads the zero-padded bias dec_b2; the per-CU form takes S % 16 == 0 only)
+struct VdPack { size_t enc[3], prior[3], prior_h, phi[4], wih, whh, dec[3], st_enc0, st_dec2, dec_b2, total; };
 VdPack vd_pack_layout(int S, int H, int Z, int R) {
-  VdPack p;
+  VdPack p{};
   Arena ar;
-  p.enc[0] = ar.take_off((size_t)H * S); p.enc[1] = ar.take_off((size_t)H * H); p.enc[2] = ar.take_off((size_t)H * H);
+  const StackPad sp = stack_pad(S, VD_F);
+  p.enc[0] = ar.take_off((size_t)H * sp.Sp); p.enc[1] = ar.take_off((size_t)H * H); p.enc[2] = ar.take_off((size_t)H * H);
   p.prior[0] = ar.take_off((size_t)H * R); p.prior[1] = ar.take_off((size_t)H * H); p.prior[2] = ar.take_off((size_t)H * H);
   p.prior_h = ar.take_off((size_t)2 * Z * H);
   p.phi[0] = ar.take_off((size_t)H * Z);
   for (int i = 1; i < 4; ++i) p.phi[i] = ar.take_off((size_t)H * H);
   p.wih = ar.take_off((size_t)3 * R * 2 * H); p.whh = ar.take_off((size_t)3 * R * R);
-  p.dec[0] = ar.take_off((size_t)H * (H + R)); p.dec[1] = ar.take_off((size_t)H * H); p.dec[2] = ar.take_off((size_t)S * VD_F * H);
+  p.dec[0] = ar.take_off((size_t)H * (H + R)); p.dec[1] = ar.take_off((size_t)H * H); p.dec[2] = ar.take_off((size_t)sp.Np * H);
+  if (sp.padded()) { p.st_enc0 = ar.take_off(sp.stage_in(H)); p.st_dec2 = ar.take_off(sp.stage_dec(H)); p.dec_b2 = ar.take_off(sp.stage_bias()); }
   p.total = ar.floats();
   return p;
 }
@@ -500,7 +504,8 @@ VgBufs vg_layout(size_t base, int T, int B, int S, int H, int Z, int R) {
   VgBufs b;
   Arena ar{nullptr, base};
   const size_t rows = (size_t)((B + 15) / 16) * 16, m = (size_t)T * rows, X = H;
-  b.X16 = ar.take_off((m + rows) * S);
+  const StackPad sp = stack_pad(S, VD_F);  // X16 slabs [rows, Sp], DEC slabs [B, Np] (padded when S % 16 != 0)
+  b.X16 = ar.take_off((m + rows) * sp.Sp);
   b.E16[0] = ar.take_off(m * H); b.E16[1] = ar.take_off(m * H);
   b.CAT16 = ar.take_off(m * (X + H));
   b.H16 = ar.take_off((m + rows) * R);
@@ -511,7 +516,7 @@ VgBufs vg_layout(size_t base, int T, int B, int S, int H, int Z, int R) {
   for (int i = 0; i < 3; ++i) b.F16[i] = ar.take_off(m * H);
   b.DC16 = ar.take_off(m * (H + R));
   b.D16[0] = ar.take_off(m * H); b.D16[1] = ar.take_off(m * H);
-  b.DEC = ar.take_off((size_t)T * B * S * VD_F);
+  b.DEC = ar.take_off((size_t)T * B * sp.Np);
   b.dummyZ = ar.take_off((size_t)B * Z);
   b.dummyR = ar.take_off((size_t)B * R);
   b.end = ar.floats();
@@ -532,8 +537,8 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
   hipStream_t s = static_cast<hipStream_t>(stream_);
   BLVM_REQUIRE(w && w->cell && x0 && eps && x_out && scratch, "vrnn_generate: null pointer");
   BLVM_REQUIRE(T >= 0 && B > 0 && B <= kPchainCarveMaxB, "vrnn_generate: bad T=%d B=%d (at most %d utterances)", T, B, kPchainCarveMaxB);
-  BLVM_REQUIRE(S % 16 == 0 && H % 16 == 0 && Z % 16 == 0 && R % 16 == 0 && S > 0 && H > 0 && Z > 0 && R > 0,
-               "vrnn_generate: S, H, Z, R must be positive multiples of 16 (got %d, %d, %d, %d)", S, H, Z, R);
+  BLVM_REQUIRE(H % 16 == 0 && Z % 16 == 0 && R % 16 == 0 && S > 0 && H > 0 && Z > 0 && R > 0,
+               "vrnn_generate: S must be positive and H, Z, R positive multiples of 16 (got %d, %d, %d, %d)", S, H, Z, R);
   BLVM_REQUIRE(num_mix == VD_K, "vrnn_generate: the DMoL head has %d components", VD_K);
   BLVM_REQUIRE((u == nullptr) == (v == nullptr), "vrnn_generate: u and v are given together (both NULL: the mode)");
   BLVM_REQUIRE(aligned16(scratch), "vrnn_generate: scratch must be 16-byte aligned");
@@ -541,20 +546,27 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
   const BlvmVrnnWeights* c = w->cell;
   const VdPack p = vd_pack_layout(S, H, Z, R);
   const VgBufs b = vg_layout(p.total, T, B, S, H, Z, R);
+  const StackPad sp = stack_pad(S, VD_F);
+  const int Sp = sp.Sp, Np = sp.Np;
+  if (sp.padded()) {  // the ragged stack's weights and bias, zero-padded to the tile boundaries
+    BLVM_TRY(pad_copy(scratch + p.st_enc0, H, Sp, w->enc_w[0], H, S, s));
+    BLVM_TRY(pad_copy(scratch + p.st_dec2, Np, H, w->dec_w[2], sp.N, H, s));
+    BLVM_TRY(pad_copy(scratch + p.dec_b2, 1, Np, w->dec_b[2], 1, sp.N, s));
+  }
   T16PackScope pack_scope(pchain_optype(B), s);
 #define PACK(dst, src, ld, rows, k) BLVM_TRY(t16_pack_rows(src, ld, rows, k, scratch + (dst), s))
-  PACK(p.enc[0], w->enc_w[0], S, H, S); PACK(p.enc[1], w->enc_w[1], H, H, H); PACK(p.enc[2], w->enc_w[2], H, H, H);
+  PACK(p.enc[0], sp.padded() ? scratch + p.st_enc0 : w->enc_w[0], sp.Sp, H, sp.Sp); PACK(p.enc[1], w->enc_w[1], H, H, H); PACK(p.enc[2], w->enc_w[2], H, H, H);
   PACK(p.prior[0], c->prior_w[0], R, H, R); PACK(p.prior[1], c->prior_w[1], H, H, H); PACK(p.prior[2], c->prior_w[2], H, H, H);
   PACK(p.prior_h, c->prior_hw, H, 2 * Z, H);
   PACK(p.phi[0], c->phi_w[0], Z, H, Z);
   for (int i = 1; i < 4; ++i) PACK(p.phi[i], c->phi_w[i], H, H, H);
   PACK(p.wih, c->gru_wih, 2 * H, 3 * R, 2 * H); PACK(p.whh, c->gru_whh, R, 3 * R, R);
-  PACK(p.dec[0], w->dec_w[0], H + R, H, H + R); PACK(p.dec[1], w->dec_w[1], H, H, H); PACK(p.dec[2], w->dec_w[2], H, S * VD_F, H);
+  PACK(p.dec[0], w->dec_w[0], H + R, H, H + R); PACK(p.dec[1], w->dec_w[1], H, H, H); PACK(p.dec[2], sp.padded() ? scratch + p.st_dec2 : w->dec_w[2], H, sp.Np, H);
 #undef PACK
   BLVM_TRY(pack_scope.flush());  // all packs above in one launch
-  const int rt = (B + 15) / 16, ctS = S / 16, ctH = H / 16, ctZ = Z / 16, ctR = R / 16, X = H, cus = device_cus() & ~7;
-  const long rows = (long)rt * 16, xS = rows * S, xH = rows * H, xZ = rows * Z, xR = rows * R, xC = rows * (X + H), xD = rows * (H + R);
-  const long sR = (long)B * R, s3R = 3 * sR, sZ = (long)B * Z, sF = (long)B * S * VD_F;
+  const int rt = (B + 15) / 16, ctS = Sp / 16, ctH = H / 16, ctZ = Z / 16, ctR = R / 16, X = H, cus = device_cus() & ~7;
+  const long rows = (long)rt * 16, xS = rows * Sp, xH = rows * H, xZ = rows * Z, xR = rows * R, xC = rows * (X + H), xD = rows * (H + R);
+  const long sR = (long)B * R, s3R = 3 * sR, sZ = (long)B * Z, sF = (long)B * Np;
   float* const sc = scratch;
   const float beta = softplus_beta_of(sd_eps);
   // ranges: the hidden projection and the wide last decoder layer off to the side of the critical links
@@ -571,7 +583,7 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
   };
   const int rH = range_for(ctH * rt, r_main);
   // encoder(x_t)
-  lin(b.X16, xS, p.enc[0], S, w->enc_b[0], ctH, DF_RELU, slope, nullptr, 0, 0, b.E16[0], xH, ctH, 0, 0, 0, 0, rH);
+  lin(b.X16, xS, p.enc[0], Sp, w->enc_b[0], ctH, DF_RELU, slope, nullptr, 0, 0, b.E16[0], xH, ctH, 0, 0, 0, 0, rH);
   lin(b.E16[0], xH, p.enc[1], H, w->enc_b[1], ctH, DF_RELU, slope, nullptr, 0, 0, b.E16[1], xH, ctH, 0, 0, 0, 0, rH);
   lin(b.E16[1], xH, p.enc[2], H, w->enc_b[2], ctH, DF_RELU, slope, nullptr, 0, 0, b.CAT16, xC, (X + H) / 16, 0, 0, 0, 0, rH);
   // prior(h_{t-1}) | hidden projection of the GRU
@@ -611,18 +623,18 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
   // decoder(cat[phi, h_t]); the last layer (S * F columns) on every workgroup
   lin(b.DC16, xD, p.dec[0], H + R, w->dec_b[0], ctH, DF_RELU, slope, nullptr, 0, 0, b.D16[0], xH, ctH, 0, 0, 0, 0, rH);
   lin(b.D16[0], xH, p.dec[1], H, w->dec_b[1], ctH, DF_RELU, slope, nullptr, 0, 0, b.D16[1], xH, ctH, 0, 0, 0, 0, rH);
-  lin(b.D16[1], xH, p.dec[2], H, w->dec_b[2], S * VD_F / 16, DF_RELU | DF_RM_SC1, slope, sc + b.DEC, sF, S * VD_F, 0, 0, 0, 0, 0, 0, 0,
-      range_for(S * VD_F / 16 * rt, cus));
+  lin(b.D16[1], xH, p.dec[2], H, sp.padded() ? sc + p.dec_b2 : w->dec_b[2], Np / 16, DF_RELU | DF_RM_SC1, slope, sc + b.DEC, sF, Np, 0, 0, 0, 0, 0, 0, 0,
+      range_for(Np / 16 * rt, cus));
   {  // per sample: head Linear -> DMoL draw -> x_{t+1}
     Operands o;
     o.p[DMOLS_DEC] = {sc + b.DEC, sF}; o.p[DMOLS_W] = w->lik_w; o.p[DMOLS_B] = w->lik_b; o.p[DMOLS_U] = {u, (long)B * S * VD_K}; o.p[DMOLS_V] = {v, (long)B * S};
-    o.p[DMOLS_X] = {x_out, S}; o.p[DMOLS_X16] = {sc + b.X16 + xS, xS}; o.ld[DMOLS_LD_DEC] = S * VD_F; o.ld[LD_OUT] = T * S; o.n16[N16_OUT] = ctS; o.i[DMOLS_I_S] = S;
+    o.p[DMOLS_X] = {x_out, S}; o.p[DMOLS_X16] = {sc + b.X16 + xS, xS}; o.ld[DMOLS_LD_DEC] = Np; o.ld[LD_OUT] = T * S; o.n16[N16_OUT] = ctS; o.i[DMOLS_I_S] = S;
     o.i[DMOLS_I_F] = VD_F; o.i[DMOLS_I_NMIX] = VD_K; o.f[DMOLS_F_LOG_EPS] = log_eps;
-    add_desc(bld, K_DMOLS, S / 4, 0, range_for(S / 4 * rt, r_main), 16, 0, 0, T, o);
+    add_desc(bld, K_DMOLS, Sp / 4, 0, range_for(Sp / 4 * rt, r_main), 16, 0, 0, T, o);
   }
   // sentinel-fill everything the launch polls (all step slabs), then the initial frame stack and state
   BLVM_HIP(pchain_fill_sentinel(sc + b.X16, sizeof(float) * (b.dummyZ - b.X16), s));
-  BLVM_TRY(pchain_rows_to_t16(x0, S, B, S, sc + b.X16, s));
+  BLVM_TRY(pchain_rows_to_t16(x0, S, B, Sp, sc + b.X16, s, 0, S));
   BLVM_TRY(pchain_rows_to_t16(h0, R, B, R, sc + b.H16, s));
   BLVM_HIP(copy_or_zero(sc + b.HS, h0, sizeof(float) * (size_t)B * R, s));
   BLVM_TRY(pchain_launch(bld, "vrnn_generate", s));

@@ -297,7 +297,14 @@ int blvm_vrnn_decode(const BlvmVrnnDecodeWeights* w, const float* x0, const floa
 
 /* K1c on the whole chip: the same sampling loop (same arguments and draws, B <= 128) as ONE persistent launch whose every layer is a
  * link dealt over all CUs (csrc/pchain.hip) instead of 16 utterances per CU: 17 links per step.  scratch:
- * blvm_vrnn_generate_scratch_floats(T, B, ...) floats (weight copies + one slab per step of every activation). */
+ * blvm_vrnn_generate_scratch_floats(T, B, ...) floats (weight copies + one slab per step of every activation).
+ * The frame stack may have any size S >= 1 (H, Z, R multiples of 16, num_mix = 10; blvm_vrnn_decode keeps S % 16 == 0).  When S is no
+ * multiple of 16 the launch works on padded copies inside the scratch, and the *_scratch_floats functions return the padded sizes: the
+ * frame-stack operand is Sp = 16 ceil(S / 16) wide (zero weight columns), the last decoder layer's output rows are Np =
+ * 16 ceil(S 3 num_mix / 16) floats long (zero weight rows, a zero-padded copy of its bias).  x0, x_out, u and v keep width S; nothing
+ * of the caller's is read past its end.  The same rule holds for blvm_srnn_generate and blvm_lstm_generate_any_stack.  The scratch grows with T
+ * and the step program does not depend on T: a long roll-out may be run as consecutive calls, each from the previous call's last frame
+ * stack and state, with bit-identical results (blvm.ops does so above `MAX_SCRATCH_FLOATS`). */
 size_t blvm_vrnn_generate_scratch_floats(int T, int B, int S, int H, int Z, int R);
 int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u,
                        const float* v, int T, int B, int S, int H, int Z, int R, int num_mix, float sd_eps, float slope,
@@ -404,6 +411,7 @@ int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, const float* 
  *   (csrc/pchain.hip).  Weights in their PyTorch layouts; encoder / decoder are 3 x (Linear + LeakyReLU(slope)) as in
  *   `srnn.py:456-474`, x_dim = H.  x0 [B,S]; d0 [B,R], z0 [B,Z] or NULL (zeros); eps [T,B,Z]; u [T,B,S,num_mix], v [T,B,S] as in
  *   blvm_mix_sample (both NULL: the mode).  Outputs: x_out [B,T,S]; d_out [B,R] = d_T and z_out [T,B,Z] (each may be NULL).
+ *   H, Z, R multiples of 16, num_mix = 10, any S >= 1 (padded inside the scratch as described at blvm_vrnn_generate).
  *   scratch: blvm_srnn_generate_scratch_floats(...) floats (weight copies + one slab per step of every activation). */
 typedef struct BlvmSrnnDecodeWeights {
   const float *enc_w[3], *enc_b[3];                    /* [H,S], [H,H], [H,H] */
@@ -423,7 +431,9 @@ int blvm_srnn_generate(const BlvmSrnnDecodeWeights* w, const float* x0, const fl
  *   their PyTorch layouts; embedding / decoder are 3 x (Linear + ReLU), the LSTM's input size is H; wih, whh, bih, bhh are HOST arrays
  *   of num_layers device pointers.  x0 [B,S] or NULL (zeros); h0, c0 [num_layers,B,H] or NULL (zeros); u [T,B,S,num_mix], v [T,B,S]
  *   as in blvm_mix_sample (both NULL: the mode).  Outputs: x_out [B,T,S]; h_out, c_out [num_layers,B,H] = the state after step T
- *   (each may be NULL).  S, H multiples of 16, num_mix = 10, 1 <= num_layers <= 8; T = 0 returns at once.
+ *   (each may be NULL).  H a multiple of 16, any S >= 1 through blvm_lstm_generate_any_stack (padded inside the scratch as described at
+ *   blvm_vrnn_generate; blvm_lstm_generate keeps its published rule, S % 16 == 0, and is otherwise the same call), num_mix = 10,
+ *   1 <= num_layers <= 8; T = 0 returns at once.
  *   scratch: blvm_lstm_generate_scratch_floats(...) floats (weight copies + one slab per step of every activation); results do not
  *   depend on what scratch or the outputs held before the call. */
 typedef struct BlvmLstmDecodeWeights {
@@ -433,6 +443,10 @@ typedef struct BlvmLstmDecodeWeights {
   const float *lik_w, *lik_b;                           /* [3*num_mix, 3*num_mix], [3*num_mix] */
 } BlvmLstmDecodeWeights;
 size_t blvm_lstm_generate_scratch_floats(int T, int B, int S, int H, int num_layers);
+int blvm_lstm_generate_any_stack(const BlvmLstmDecodeWeights* w, const float* x0, const float* h0, const float* c0, const float* u,
+                                 const float* v, int T, int B, int S, int H, int num_layers, int num_mix, float log_eps, float* x_out,
+                                 float* h_out, float* c_out, float* scratch, void* stream);
+/* The same call restricted to S % 16 == 0, as first published: any other S is refused before anything is touched. */
 int blvm_lstm_generate(const BlvmLstmDecodeWeights* w, const float* x0, const float* h0, const float* c0, const float* u,
                        const float* v, int T, int B, int S, int H, int num_layers, int num_mix, float log_eps, float* x_out,
                        float* h_out, float* c_out, float* scratch, void* stream);
