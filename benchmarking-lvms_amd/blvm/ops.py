@@ -606,6 +606,37 @@ def _steps_per_launch(scratch_floats, T, max_scratch_floats, who):
     return n
 
 
+def _rollout(scratch_floats, T, max_scratch_floats, who, x, call, carry):
+    """The driver of the one-launch roll-outs: one launch when the scratch of T steps fits the bound, else consecutive launches of as
+    many steps as fit.  scratch_floats: steps -> floats; x [B,T,S] receives the samples; call(t0, t1, state, x_chunk, scratch) runs
+    steps [t0, t1) from `state` (None: the caller's own start) into x_chunk [B,t1-t0,S]; carry(x_chunk, t1) -> the next chunk's
+    state, taken from what the previous call put out (its last frame stack, copies of its final states)."""
+    n = _steps_per_launch(scratch_floats, T, max_scratch_floats, who) if T > 0 else 0
+    scratch = torch.empty(scratch_floats(n), device=x.device, dtype=torch.float32)
+    if n == T:
+        call(0, T, None, x, scratch)
+        return
+    state = None
+    for t0 in range(0, T, n):
+        t1 = min(T, t0 + n)
+        xc = torch.empty(x.shape[0], t1 - t0, x.shape[2], device=x.device, dtype=torch.float32)
+        call(t0, t1, state, xc, scratch)
+        x[:, t0:t1] = xc
+        state = carry(xc, t1)
+
+
+def _decode_weight_ptrs(w, first, first_lin, dec_lin, lik_lin):
+    """Fills the `first`_w / `first`_b ("enc" | "emb"), dec_w / dec_b and lik_w / lik_b pointers of a decode-weights struct from the
+    3 + 3 + 1 nn.Linear; -> the float32 contiguous tensors, which must stay alive while `w` is used."""
+    keep = [_f32c(t) for lin in (*first_lin, *dec_lin, lik_lin) for t in (lin.weight, lin.bias)]
+    fw, fb = getattr(w, first + "_w"), getattr(w, first + "_b")
+    for i in range(3):
+        fw[i], fb[i] = ptr(keep[2 * i]), ptr(keep[2 * i + 1])
+        w.dec_w[i], w.dec_b[i] = ptr(keep[6 + 2 * i]), ptr(keep[6 + 2 * i + 1])
+    w.lik_w, w.lik_b = ptr(keep[12]), ptr(keep[13])
+    return keep
+
+
 @torch.no_grad()
 def vrnn_decode(enc_lin, cell_params, dec_lin, lik_lin, x0, h0, eps, u, v, S, H, Z, R, num_mix, sd_eps, slope, log_eps, whole_chip=None,
                 max_scratch_floats=None):  # fmt: skip
@@ -621,14 +652,10 @@ def vrnn_decode(enc_lin, cell_params, dec_lin, lik_lin, x0, h0, eps, u, v, S, H,
     lib = load()
     T, B = eps.shape[0], x0.shape[0]
     dev = x0.device
-    keep = [_f32c(t) for lin in (*enc_lin, *dec_lin, lik_lin) for t in (lin.weight, lin.bias)]
     cp = [_f32c(p) for p in cell_params]
     cw = _pack_weights(cp)
     w = VrnnDecodeWeights()
-    for i in range(3):
-        w.enc_w[i], w.enc_b[i] = ptr(keep[2 * i]), ptr(keep[2 * i + 1])
-        w.dec_w[i], w.dec_b[i] = ptr(keep[6 + 2 * i]), ptr(keep[6 + 2 * i + 1])
-    w.lik_w, w.lik_b = ptr(keep[12]), ptr(keep[13])
+    keep = _decode_weight_ptrs(w, "enc", enc_lin, dec_lin, lik_lin)  # noqa: F841  (alive until the calls below are enqueued)
     w.cell = ctypes.pointer(cw)
     x0, eps = _f32c(x0), _f32c(eps)
     h0 = _f32c(h0) if h0 is not None else None
@@ -639,21 +666,15 @@ def vrnn_decode(enc_lin, cell_params, dec_lin, lik_lin, x0, h0, eps, u, v, S, H,
     x = torch.empty(B, T, S, device=dev, dtype=torch.float32)
     hn = torch.empty(B, R, device=dev, dtype=torch.float32)
     if whole_chip:
-        floats = lambda n: lib.blvm_vrnn_generate_scratch_floats(n, B, S, H, Z, R)  # noqa: E731
-        n = _steps_per_launch(floats, T, max_scratch_floats, "vrnn_decode") if T > 0 else 0
-        scratch = torch.empty(floats(n), device=dev, dtype=torch.float32)
-        if n == T:
-            check(lib.blvm_vrnn_generate(ctypes.byref(w), ptr(x0), ptr(h0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, num_mix, sd_eps,
-                                         slope, log_eps, ptr(x), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_generate")  # fmt: skip
-            return x, hn
-        for t0 in range(0, T, n):
-            t1 = min(T, t0 + n)
-            xc = torch.empty(B, t1 - t0, S, device=dev, dtype=torch.float32)
+
+        def call(t0, t1, state, xc, scratch):
+            xs, hs = (x0, h0) if state is None else state
             uc, vc = (None, None) if u is None else (u[t0:t1], v[t0:t1])
-            check(lib.blvm_vrnn_generate(ctypes.byref(w), ptr(x0), ptr(h0), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, num_mix,
+            check(lib.blvm_vrnn_generate(ctypes.byref(w), ptr(xs), ptr(hs), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, num_mix,
                                          sd_eps, slope, log_eps, ptr(xc), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_generate")  # fmt: skip
-            x[:, t0:t1] = xc
-            x0, h0 = xc[:, -1].contiguous(), hn.clone()
+
+        _rollout(lambda n: lib.blvm_vrnn_generate_scratch_floats(n, B, S, H, Z, R), T, max_scratch_floats, "vrnn_decode", x, call,
+                 lambda xc, t1: (xc[:, -1].contiguous(), hn.clone()))  # fmt: skip
         return x, hn
     scratch = torch.empty(lib.blvm_vrnn_decode_scratch_floats(S, H, Z, R), device=dev, dtype=torch.float32)
     check(lib.blvm_vrnn_decode(ctypes.byref(w), ptr(x0), ptr(h0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, num_mix, sd_eps, slope,
@@ -791,14 +812,10 @@ def lstm_sequence(inp, h0, c0, lens_dev, Wih, Whh, bih, bhh):
 def lstm_decode_weights(emb_lin, lstm, dec_lin, lik_lin):
     """-> (struct BlvmLstmDecodeWeights, what must stay alive while it is used)."""
     L = lstm.num_layers
-    keep = [_f32c(t) for lin in (*emb_lin, *dec_lin, lik_lin) for t in (lin.weight, lin.bias)]
     lk = [[_f32c(getattr(lstm, f"{n}_l{l}")) for l in range(L)] for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
     arrays = [(ctypes.c_void_p * L)(*[t.data_ptr() for t in ts]) for ts in lk]  # host arrays of device pointers
     w = _hip.LstmDecodeWeights()
-    for i in range(3):
-        w.emb_w[i], w.emb_b[i] = ptr(keep[2 * i]), ptr(keep[2 * i + 1])
-        w.dec_w[i], w.dec_b[i] = ptr(keep[6 + 2 * i]), ptr(keep[6 + 2 * i + 1])
-    w.lik_w, w.lik_b = ptr(keep[12]), ptr(keep[13])
+    keep = _decode_weight_ptrs(w, "emb", emb_lin, dec_lin, lik_lin)
     w.wih, w.whh, w.bih, w.bhh = (ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p)) for a in arrays)
     return w, (keep, lk, arrays)
 
@@ -821,22 +838,16 @@ def lstm_generate(emb_lin, lstm, dec_lin, lik_lin, x0, h0, c0, u, v, S, H, num_m
     c0 = _f32c(c0) if c0 is not None else None
     u, v = (None, None) if u is None else (_f32c(u), _f32c(v))
     f32 = dict(device=dev, dtype=torch.float32)
-    floats = lambda n: lib.blvm_lstm_generate_scratch_floats(n, B, S, H, L)  # noqa: E731
-    n = _steps_per_launch(floats, T, max_scratch_floats, "lstm_generate") if T > 0 else 0
-    scratch = torch.empty(floats(n), **f32)
     x, hn, cn = torch.empty(B, T, S, **f32), torch.empty(L, B, H, **f32), torch.empty(L, B, H, **f32)
-    if n == T:
-        check(lib.blvm_lstm_generate_any_stack(ctypes.byref(w), ptr(x0), ptr(h0), ptr(c0), ptr(u), ptr(v), T, B, S, H, L, num_mix, log_eps, ptr(x), ptr(hn),
-                                     ptr(cn), ptr(scratch), stream_ptr()), "blvm_lstm_generate_any_stack")  # fmt: skip
-        return x, hn, cn
-    for t0 in range(0, T, n):
-        t1 = min(T, t0 + n)
-        xc = torch.empty(B, t1 - t0, S, **f32)
+
+    def call(t0, t1, state, xc, scratch):
+        xs, hs, cs = (x0, h0, c0) if state is None else state
         uc, vc = (None, None) if u is None else (u[t0:t1], v[t0:t1])
-        check(lib.blvm_lstm_generate_any_stack(ctypes.byref(w), ptr(x0), ptr(h0), ptr(c0), ptr(uc), ptr(vc), t1 - t0, B, S, H, L, num_mix, log_eps, ptr(xc),
-                                     ptr(hn), ptr(cn), ptr(scratch), stream_ptr()), "blvm_lstm_generate_any_stack")  # fmt: skip
-        x[:, t0:t1] = xc
-        x0, h0, c0 = xc[:, -1].contiguous(), hn.clone(), cn.clone()
+        check(lib.blvm_lstm_generate_any_stack(ctypes.byref(w), ptr(xs), ptr(hs), ptr(cs), ptr(uc), ptr(vc), t1 - t0, B, S, H, L, num_mix, log_eps, ptr(xc),
+                                               ptr(hn), ptr(cn), ptr(scratch), stream_ptr()), "blvm_lstm_generate_any_stack")  # fmt: skip
+
+    _rollout(lambda n: lib.blvm_lstm_generate_scratch_floats(n, B, S, H, L), T, max_scratch_floats, "lstm_generate", x, call,
+             lambda xc, t1: (xc[:, -1].contiguous(), hn.clone(), cn.clone()))  # fmt: skip
     return x, hn, cn
 
 
@@ -925,15 +936,11 @@ def srnn_generate(enc_lin, gru, chain_params, dec_lin, lik_lin, x0, d0, z0, eps,
     lib = load()
     T, B = eps.shape[0], x0.shape[0]
     dev = x0.device
-    keep = [_f32c(t) for lin in (*enc_lin, *dec_lin, lik_lin) for t in (lin.weight, lin.bias)]
     gk = [_f32c(t) for t in (gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)]
     cp = [_f32c(p) for p in chain_params]
     cw = _pack_srnn(cp)
     w = _hip.SrnnDecodeWeights()
-    for i in range(3):
-        w.enc_w[i], w.enc_b[i] = ptr(keep[2 * i]), ptr(keep[2 * i + 1])
-        w.dec_w[i], w.dec_b[i] = ptr(keep[6 + 2 * i]), ptr(keep[6 + 2 * i + 1])
-    w.lik_w, w.lik_b = ptr(keep[12]), ptr(keep[13])
+    keep = _decode_weight_ptrs(w, "enc", enc_lin, dec_lin, lik_lin)  # noqa: F841  (alive until the calls below are enqueued)
     w.gru_wih, w.gru_whh, w.gru_bih, w.gru_bhh = (ptr(t) for t in gk)
     w.chain = ctypes.pointer(cw)
     x0, eps = _f32c(x0), _f32c(eps)
@@ -942,22 +949,16 @@ def srnn_generate(enc_lin, gru, chain_params, dec_lin, lik_lin, x0, d0, z0, eps,
     u = _f32c(u) if u is not None else None
     v = _f32c(v) if v is not None else None
     f32 = dict(device=dev, dtype=torch.float32)
-    floats = lambda n: lib.blvm_srnn_generate_scratch_floats(n, B, S, H, Z, R)  # noqa: E731
-    n = _steps_per_launch(floats, T, max_scratch_floats, "srnn_generate") if T > 0 else 0
-    scratch = torch.empty(floats(n), **f32)
     x, dn, zs = torch.empty(B, T, S, **f32), torch.empty(B, R, **f32), torch.empty(T, B, Z, **f32)
-    if n == T:
-        check(lib.blvm_srnn_generate(ctypes.byref(w), ptr(x0), ptr(d0), ptr(z0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, num_mix, sd_eps,
-                                     slope, log_eps, ptr(x), ptr(dn), ptr(zs), ptr(scratch), stream_ptr()), "blvm_srnn_generate")  # fmt: skip
-        return x, dn, zs
-    for t0 in range(0, T, n):
-        t1 = min(T, t0 + n)
-        xc = torch.empty(B, t1 - t0, S, **f32)
+
+    def call(t0, t1, state, xc, scratch):
+        xs, ds, z_prev = (x0, d0, z0) if state is None else state
         uc, vc = (None, None) if u is None else (u[t0:t1], v[t0:t1])
-        check(lib.blvm_srnn_generate(ctypes.byref(w), ptr(x0), ptr(d0), ptr(z0), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, num_mix,
+        check(lib.blvm_srnn_generate(ctypes.byref(w), ptr(xs), ptr(ds), ptr(z_prev), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, num_mix,
                                      sd_eps, slope, log_eps, ptr(xc), ptr(dn), ptr(zs[t0:t1]), ptr(scratch), stream_ptr()), "blvm_srnn_generate")  # fmt: skip
-        x[:, t0:t1] = xc
-        x0, d0, z0 = xc[:, -1].contiguous(), dn.clone(), zs[t1 - 1]
+
+    _rollout(lambda n: lib.blvm_srnn_generate_scratch_floats(n, B, S, H, Z, R), T, max_scratch_floats, "srnn_generate", x, call,
+             lambda xc, t1: (xc[:, -1].contiguous(), dn.clone(), zs[t1 - 1]))  # fmt: skip
     return x, dn, zs
 
 

@@ -1456,7 +1456,7 @@ int vrnn_launch(pchain::Builder& bld, bool forward, const char* who, hipStream_t
 // n16 > 0: dst is a slab of n16 blocks per row tile (a concatenation; dst points at this part's first block)
 // k_src > 0: src has only k_src < K columns, the columns k_src .. K-1 of dst are zeros (a padded frame stack)
 int pchain_rows_to_t16(const float* src, int ld, int B, int K, float* dst, hipStream_t stream, int n16 = 0, int k_src = 0);
-// ---- frame stacks of any size in the one-launch decoders (vrnn_decode.hip, srnn_decode.hip, lstm_decode.h) -------------------------
+// ---- frame stacks of any size in the one-launch decoders (rollout_plan.h, lstm_decode.h) --------------------------------------------
 // The caller's S samples per step meet the 16-wide tiles in two places, and both are PADDED rather than guarded, so the link tiles are
 // the ones every other program runs:
 //   the frame-stack operand X16: slabs [rows, Sp], Sp = 16 ceil(S / 16); the first link has K = Sp and a packed weight whose columns

@@ -9,13 +9,13 @@
 // contiguous 1 KB read per fragment), the noise and the samples — the decode step is bound by how fast one CU ingests weights.
 #include "common.h"
 #include "decode_tiles.h"
-#include "pchain.h"
+#include "rollout_launch.h"
 
 namespace blvm {
 namespace {
 
 constexpr int VD_ROWS = 16, VD_NW = 8, VD_CHUNK = 8;  // utterances per workgroup, waves, samples per decoder chunk
-constexpr int VD_F = 30, VD_K = 10;                   // DMoL head: 3 * num_mix parameters per sample
+constexpr int VD_F = pchain::kDmolF, VD_K = pchain::kDmolK;  // DMoL head: 3 * num_mix parameters per sample
 
 struct VDArgs {
   // T16 operand copies (common.h) and the biases
@@ -414,33 +414,20 @@ size_t vd_lds_bytes(int S, int H, int Z, int R) {
   return sizeof(float) * ((size_t)VD_ROWS * ((S + 4) + 4 * (H + 4) + (R + 4) + (Z + 4) + (VD_CHUNK * VD_F + 4)) + 1024 + 32 + VD_ROWS * VD_CHUNK * 32 + 32 * 16);  // + the op program
 }
 
-// (whole-chip form, S % 16 != 0 — pchain.h stack_pad: enc[0] is [H, Sp] and dec[2] [Np, H], packed from zero-padded row-major copies
-// staged behind the packs, and the last decoder layer reads the zero-padded bias dec_b2; the per-CU form takes S % 16 == 0 only)
-struct VdPack { size_t enc[3], prior[3], prior_h, phi[4], wih, whh, dec[3], st_enc0, st_dec2, dec_b2, total; };
-VdPack vd_pack_layout(int S, int H, int Z, int R) {
-  VdPack p{};
-  Arena ar;
-  const StackPad sp = stack_pad(S, VD_F);
-  p.enc[0] = ar.take_off((size_t)H * sp.Sp); p.enc[1] = ar.take_off((size_t)H * H); p.enc[2] = ar.take_off((size_t)H * H);
-  p.prior[0] = ar.take_off((size_t)H * R); p.prior[1] = ar.take_off((size_t)H * H); p.prior[2] = ar.take_off((size_t)H * H);
-  p.prior_h = ar.take_off((size_t)2 * Z * H);
-  p.phi[0] = ar.take_off((size_t)H * Z);
-  for (int i = 1; i < 4; ++i) p.phi[i] = ar.take_off((size_t)H * H);
-  p.wih = ar.take_off((size_t)3 * R * 2 * H); p.whh = ar.take_off((size_t)3 * R * R);
-  p.dec[0] = ar.take_off((size_t)H * (H + R)); p.dec[1] = ar.take_off((size_t)H * H); p.dec[2] = ar.take_off((size_t)sp.Np * H);
-  if (sp.padded()) { p.st_enc0 = ar.take_off(sp.stage_in(H)); p.st_dec2 = ar.take_off(sp.stage_dec(H)); p.dec_b2 = ar.take_off(sp.stage_bias()); }
-  p.total = ar.floats();
-  return p;
-}
-
 }  // namespace
 }  // namespace blvm
 
 using namespace blvm;
 
+// sizes only: the pack table of no weights
+static pchain::PackTable vd_pack_sizes(int S, int H, int Z, int R) {
+  const BlvmVrnnWeights c{};
+  return pchain::vrnn_pack_table(BlvmVrnnDecodeWeights{}, c, S, H, Z, R);
+}
+
 extern "C" size_t blvm_vrnn_decode_scratch_floats(int S, int H, int Z, int R) {
   if (S <= 0 || H <= 0 || Z <= 0 || R <= 0) return 0;
-  return vd_pack_layout(S, H, Z, R).total;
+  return vd_pack_sizes(S, H, Z, R).total;
 }
 
 extern "C" int blvm_vrnn_decode(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u,
@@ -460,25 +447,18 @@ extern "C" int blvm_vrnn_decode(const BlvmVrnnDecodeWeights* w, const float* x0,
   BLVM_REQUIRE(lds <= 160 * 1024, "vrnn_decode: S=%d H=%d Z=%d R=%d need %zu bytes of LDS (> 160 KB)", S, H, Z, R, lds);
   if (T == 0) return BLVM_OK;
   const BlvmVrnnWeights* c = w->cell;
-  const VdPack p = vd_pack_layout(S, H, Z, R);
+  using namespace pchain;
+  const PackTable p = vrnn_pack_table(*w, *c, S, H, Z, R);  // (S % 16 == 0: nothing staged; each pack its own launch, fp32 operands)
   VDArgs a{};
-#define PACK(dst, src, ld, rows, k) BLVM_TRY(t16_pack_rows(src, ld, rows, k, scratch + (dst), s))
-  PACK(p.enc[0], w->enc_w[0], S, H, S); PACK(p.enc[1], w->enc_w[1], H, H, H); PACK(p.enc[2], w->enc_w[2], H, H, H);
-  PACK(p.prior[0], c->prior_w[0], R, H, R); PACK(p.prior[1], c->prior_w[1], H, H, H); PACK(p.prior[2], c->prior_w[2], H, H, H);
-  PACK(p.prior_h, c->prior_hw, H, 2 * Z, H);
-  PACK(p.phi[0], c->phi_w[0], Z, H, Z);
-  for (int i = 1; i < 4; ++i) PACK(p.phi[i], c->phi_w[i], H, H, H);
-  PACK(p.wih, c->gru_wih, 2 * H, 3 * R, 2 * H); PACK(p.whh, c->gru_whh, R, 3 * R, R);
-  PACK(p.dec[0], w->dec_w[0], H + R, H, H + R); PACK(p.dec[1], w->dec_w[1], H, H, H); PACK(p.dec[2], w->dec_w[2], H, S * VD_F, H);
-#undef PACK
+  for (const PackEntry& e : p.e) BLVM_TRY(t16_pack_rows(e.src, e.ld, e.rows, e.k, scratch + e.off, s));
   for (int i = 0; i < 3; ++i) {
-    a.enc_w[i] = scratch + p.enc[i]; a.enc_b[i] = w->enc_b[i];
-    a.prior_w[i] = scratch + p.prior[i]; a.prior_b[i] = c->prior_b[i];
-    a.dec_w[i] = scratch + p.dec[i]; a.dec_b[i] = w->dec_b[i];
+    a.enc_w[i] = scratch + p.off(VP_ENC0 + i); a.enc_b[i] = w->enc_b[i];
+    a.prior_w[i] = scratch + p.off(VP_PRIOR0 + i); a.prior_b[i] = c->prior_b[i];
+    a.dec_w[i] = scratch + p.off(VP_DEC0 + i); a.dec_b[i] = w->dec_b[i];
   }
-  for (int i = 0; i < 4; ++i) { a.phi_w[i] = scratch + p.phi[i]; a.phi_b[i] = c->phi_b[i]; }
-  a.prior_hw = scratch + p.prior_h; a.prior_hb = c->prior_hb;
-  a.wih = scratch + p.wih; a.whh = scratch + p.whh; a.bih = c->gru_bih; a.bhh = c->gru_bhh;
+  for (int i = 0; i < 4; ++i) { a.phi_w[i] = scratch + p.off(VP_PHI0 + i); a.phi_b[i] = c->phi_b[i]; }
+  a.prior_hw = scratch + p.off(VP_PRIOR_H); a.prior_hb = c->prior_hb;
+  a.wih = scratch + p.off(VP_WIH); a.whh = scratch + p.off(VP_WHH); a.bih = c->gru_bih; a.bhh = c->gru_bhh;
   a.lik_w = w->lik_w; a.lik_b = w->lik_b;
   a.x0 = x0; a.h0 = h0; a.eps = eps; a.u = u; a.v = v; a.x_out = x_out; a.h_out = h_out;
   a.T = T; a.B = B; a.S = S; a.H = H; a.Z = Z; a.R = R;
@@ -493,41 +473,12 @@ extern "C" int blvm_vrnn_decode(const BlvmVrnnDecodeWeights* w, const float* x0,
 // The same sampling loop on the persistent-chain engine (pchain.h / pchain.hip): K1c above keeps 16 utterances on ONE CU (0.37 ms per
 // step at any batch size: the fp32 matrix pipe of one CU); here every layer of a step is a link whose 16x16 tiles are dealt over the
 // whole chip — 17 descriptors per step, the weights (12.5 MB) stay in the L2s, activations travel as sentinel-polled T16 copies.
-// Nothing is kept for a backward pass, but every buffer is still a per-step slab (every word is written once per launch).
+// The pack table (shared with the per-CU form), the layout of the scratch and the descriptor list are in rollout_plan.h, which
+// tests/host/vrnn_generate_plan_test.hip replays on the host.
 // ---------------------------------------------------------------------------------------------------------------------------------
-namespace blvm {
-namespace {
-struct VgBufs {
-  size_t X16, E16[2], CAT16, H16, HS, P16[3], GHb, Z16, F16[3], DC16, D16[2], DEC, dummyZ, dummyR, end;
-};
-VgBufs vg_layout(size_t base, int T, int B, int S, int H, int Z, int R) {
-  VgBufs b;
-  Arena ar{nullptr, base};
-  const size_t rows = (size_t)((B + 15) / 16) * 16, m = (size_t)T * rows, X = H;
-  const StackPad sp = stack_pad(S, VD_F);  // X16 slabs [rows, Sp], DEC slabs [B, Np] (padded when S % 16 != 0)
-  b.X16 = ar.take_off((m + rows) * sp.Sp);
-  b.E16[0] = ar.take_off(m * H); b.E16[1] = ar.take_off(m * H);
-  b.CAT16 = ar.take_off(m * (X + H));
-  b.H16 = ar.take_off((m + rows) * R);
-  b.HS = ar.take_off((size_t)(T + 1) * B * R);
-  for (int i = 0; i < 3; ++i) b.P16[i] = ar.take_off(m * H);
-  b.GHb = ar.take_off((size_t)T * B * 3 * R);
-  b.Z16 = ar.take_off(m * Z);
-  for (int i = 0; i < 3; ++i) b.F16[i] = ar.take_off(m * H);
-  b.DC16 = ar.take_off(m * (H + R));
-  b.D16[0] = ar.take_off(m * H); b.D16[1] = ar.take_off(m * H);
-  b.DEC = ar.take_off((size_t)T * B * sp.Np);
-  b.dummyZ = ar.take_off((size_t)B * Z);
-  b.dummyR = ar.take_off((size_t)B * R);
-  b.end = ar.floats();
-  return b;
-}
-}  // namespace
-}  // namespace blvm
-
 extern "C" size_t blvm_vrnn_generate_scratch_floats(int T, int B, int S, int H, int Z, int R) {
   if (T <= 0 || B <= 0 || S <= 0 || H <= 0 || Z <= 0 || R <= 0) return 0;
-  return vg_layout(vd_pack_layout(S, H, Z, R).total, T, B, S, H, Z, R).end;
+  return pchain::vrnn_generate_layout(vd_pack_sizes(S, H, Z, R).total, T, B, S, H, Z, R).end;
 }
 
 extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u,
@@ -543,101 +494,17 @@ extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x
   BLVM_REQUIRE((u == nullptr) == (v == nullptr), "vrnn_generate: u and v are given together (both NULL: the mode)");
   BLVM_REQUIRE(aligned16(scratch), "vrnn_generate: scratch must be 16-byte aligned");
   if (T == 0) return BLVM_OK;
-  const BlvmVrnnWeights* c = w->cell;
-  const VdPack p = vd_pack_layout(S, H, Z, R);
-  const VgBufs b = vg_layout(p.total, T, B, S, H, Z, R);
-  const StackPad sp = stack_pad(S, VD_F);
-  const int Sp = sp.Sp, Np = sp.Np;
-  if (sp.padded()) {  // the ragged stack's weights and bias, zero-padded to the tile boundaries
-    BLVM_TRY(pad_copy(scratch + p.st_enc0, H, Sp, w->enc_w[0], H, S, s));
-    BLVM_TRY(pad_copy(scratch + p.st_dec2, Np, H, w->dec_w[2], sp.N, H, s));
-    BLVM_TRY(pad_copy(scratch + p.dec_b2, 1, Np, w->dec_b[2], 1, sp.N, s));
-  }
-  T16PackScope pack_scope(pchain_optype(B), s);
-#define PACK(dst, src, ld, rows, k) BLVM_TRY(t16_pack_rows(src, ld, rows, k, scratch + (dst), s))
-  PACK(p.enc[0], sp.padded() ? scratch + p.st_enc0 : w->enc_w[0], sp.Sp, H, sp.Sp); PACK(p.enc[1], w->enc_w[1], H, H, H); PACK(p.enc[2], w->enc_w[2], H, H, H);
-  PACK(p.prior[0], c->prior_w[0], R, H, R); PACK(p.prior[1], c->prior_w[1], H, H, H); PACK(p.prior[2], c->prior_w[2], H, H, H);
-  PACK(p.prior_h, c->prior_hw, H, 2 * Z, H);
-  PACK(p.phi[0], c->phi_w[0], Z, H, Z);
-  for (int i = 1; i < 4; ++i) PACK(p.phi[i], c->phi_w[i], H, H, H);
-  PACK(p.wih, c->gru_wih, 2 * H, 3 * R, 2 * H); PACK(p.whh, c->gru_whh, R, 3 * R, R);
-  PACK(p.dec[0], w->dec_w[0], H + R, H, H + R); PACK(p.dec[1], w->dec_w[1], H, H, H); PACK(p.dec[2], sp.padded() ? scratch + p.st_dec2 : w->dec_w[2], H, sp.Np, H);
-#undef PACK
-  BLVM_TRY(pack_scope.flush());  // all packs above in one launch
-  const int rt = (B + 15) / 16, ctS = Sp / 16, ctH = H / 16, ctZ = Z / 16, ctR = R / 16, X = H, cus = device_cus() & ~7;
-  const long rows = (long)rt * 16, xS = rows * Sp, xH = rows * H, xZ = rows * Z, xR = rows * R, xC = rows * (X + H), xD = rows * (H + R);
-  const long sR = (long)B * R, s3R = 3 * sR, sZ = (long)B * Z, sF = (long)B * Np;
+  // (unlike the SRNN and LSTM roll-outs this entry point never required device_cus() >= 32: kept so)
+  PackTable p = vrnn_pack_table(*w, *w->cell, S, H, Z, R);
+  const VrnnBufs b = vrnn_generate_layout(p.total, T, B, S, H, Z, R);
   float* const sc = scratch;
-  const float beta = softplus_beta_of(sd_eps);
-  // ranges: the hidden projection and the wide last decoder layer off to the side of the critical links
-  const int r_side = range_for(3 * ctR * rt, std::min(cus / 4, 64));
-  const int r_main = range_for(std::max(ctR * rt, ctH * rt), cus - r_side);
+  const OpType ot = pchain_optype(B);
+  BLVM_TRY(stage_and_pack(p, ot, sc, s));
   Builder bld;
-  bld.begin(pchain_optype(B), T, B, 4, false, r_main);
-  auto lin = [&](size_t A16, long a_step, size_t W, int K, const float* bias, int ct, int flags, float sl, float* orm, long rm_step, int ldo, size_t o16,
-                 long o16_step, int n16, size_t o16b, long o16b_step, int n16b, int wg0, int nwg) -> Desc& {
-    Operands o;
-    o.p[LIN_A] = {sc + A16, a_step}; o.p[LIN_W] = sc + W; o.p[LIN_BIAS] = bias; o.p[LIN_ORM] = {orm, rm_step}; o.p[LIN_O16] = {o16 ? sc + o16 : nullptr, o16_step};
-    o.p[LIN_O16B] = {o16b ? sc + o16b : nullptr, o16b_step}; o.ld[LD_OUT] = ldo; o.n16[N16_OUT] = n16; o.n16[N16_OUTB] = n16b; o.f[LIN_F_SLOPE] = sl;
-    return add_desc(bld, K_LIN, ct, wg0, nwg, K, flags, 0, T, o);
-  };
-  const int rH = range_for(ctH * rt, r_main);
-  // encoder(x_t)
-  lin(b.X16, xS, p.enc[0], Sp, w->enc_b[0], ctH, DF_RELU, slope, nullptr, 0, 0, b.E16[0], xH, ctH, 0, 0, 0, 0, rH);
-  lin(b.E16[0], xH, p.enc[1], H, w->enc_b[1], ctH, DF_RELU, slope, nullptr, 0, 0, b.E16[1], xH, ctH, 0, 0, 0, 0, rH);
-  lin(b.E16[1], xH, p.enc[2], H, w->enc_b[2], ctH, DF_RELU, slope, nullptr, 0, 0, b.CAT16, xC, (X + H) / 16, 0, 0, 0, 0, rH);
-  // prior(h_{t-1}) | hidden projection of the GRU
-  lin(b.H16, xR, p.prior[0], R, c->prior_b[0], ctH, DF_RELU, 0.f, nullptr, 0, 0, b.P16[0], xH, ctH, 0, 0, 0, 0, rH);
-  lin(b.H16, xR, p.whh, R, c->gru_bhh, 3 * ctR, DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0), 0.f, sc + b.GHb, s3R, 3 * R, 0, 0, 0, 0, 0, 0,
-      r_main, r_side);
-  {  // the next two prior layers: one descriptor (K_LINSEQ)
-    const SeqLink lp[2] = {{sc + p.prior[1], c->prior_b[1], nullptr, 0, 0, sc + b.P16[1]}, {sc + p.prior[2], c->prior_b[2], nullptr, 0, 0, sc + b.P16[2]}};
-    add_linseq(bld, ctH, 0, rH, H, true, false, 0, T, {sc + b.P16[0], xH}, 2, lp, 0, xH, ctH, 0.f, 0);
-  }
-  {  // z ~ prior (head in generation mode: the posterior operands are the prior's)
-    Operands o;
-    o.p[HEAD_P16] = o.p[HEAD_Q16] = {sc + b.P16[2], xH}; o.p[HEAD_WP] = o.p[HEAD_WQ] = sc + p.prior_h; o.p[HEAD_BP] = o.p[HEAD_BQ] = c->prior_hb;
-    o.p[HEAD_EPS] = {eps, sZ}; o.p[HEAD_MU_P] = o.p[HEAD_SD_P] = o.p[HEAD_MU_Q] = o.p[HEAD_SD_Q] = o.p[HEAD_RAW_P] = o.p[HEAD_RAW_Q] = o.p[HEAD_Z] = sc + b.dummyZ;
-    o.p[HEAD_Z16] = {sc + b.Z16, xZ}; o.ld[LD_OUT] = Z; o.n16[N16_OUT] = ctZ; o.i[HEAD_I_Z] = Z; o.i[HEAD_I_RESIDUAL] = 3; o.f[HEAD_F_BETA] = beta;
-    o.f[HEAD_F_INV_BETA] = 1.f / beta; o.f[HEAD_F_SD_EPS] = sd_eps;
-    add_desc(bld, K_HEAD, ctZ, 0, range_for(ctZ * rt, r_main), H, 0, 0, T, o);
-  }
-  // phi_z(z): the last layer feeds the GRU input cat[enc, phi] and the decoder input cat[phi, h_new]
-  {  // layers 1..3 as one descriptor (K_LINSEQ)
-    const int f0 = Z == H ? 0 : 1;  // (the first layer's K is Z: part of the run only when Z == H)
-    if (f0) lin(b.Z16, xZ, p.phi[0], Z, c->phi_b[0], ctH, DF_RELU, 0.f, nullptr, 0, 0, b.F16[0], xH, ctH, 0, 0, 0, 0, rH);
-    SeqLink lf[3];
-    for (int l = f0; l < 3; ++l) lf[l - f0] = SeqLink{sc + p.phi[l], c->phi_b[l], nullptr, 0, 0, sc + b.F16[l]};
-    add_linseq(bld, ctH, 0, rH, H, true, false, 0, T, f0 ? Ptr(sc + b.F16[0], xH) : Ptr(sc + b.Z16, xZ), 3 - f0, lf, 0, xH, ctH, 0.f, 0);
-  }
-  lin(b.F16[2], xH, p.phi[3], H, c->phi_b[3], ctH, DF_RELU, 0.f, nullptr, 0, 0, b.CAT16 + (size_t)(X / 16) * 256, xC, (X + H) / 16, b.DC16, xD,
-      (H + R) / 16, 0, rH);
-  {  // GRU(cat[enc, phi], h_{t-1}) -> h_t: row-major (polled words of the next step), T16 for the next step, T16 into cat[phi, h_t]
-    Operands o;
-    o.p[GRU_X16] = {sc + b.CAT16, xC}; o.p[GRU_WIH] = sc + p.wih; o.p[GRU_GH] = {sc + b.GHb, s3R}; o.p[GRU_HPREV] = {sc + b.HS, sR}; o.p[GRU_HRM] = {sc + b.HS + sR, sR};
-    o.p[GRU_H16] = {sc + b.H16 + xR, xR}; o.p[GRU_RG] = o.p[GRU_UG] = o.p[GRU_NG] = sc + b.dummyR; o.p[GRU_BIH] = c->gru_bih;
-    o.p[GRU_H16B] = {sc + b.DC16 + (size_t)(H / 16) * 256, xD}; o.ld[GRU_LD_HPREV] = R; o.ld[LD_OUT] = R; o.n16[N16_OUT] = ctR; o.n16[N16_OUTB] = (H + R) / 16;
-    o.i[GRU_I_R] = R;
-    add_desc(bld, K_GRU, ctR, 0, range_for(ctR * rt, r_main), X + H, 0, 0, T, o);
-  }
-  // decoder(cat[phi, h_t]); the last layer (S * F columns) on every workgroup
-  lin(b.DC16, xD, p.dec[0], H + R, w->dec_b[0], ctH, DF_RELU, slope, nullptr, 0, 0, b.D16[0], xH, ctH, 0, 0, 0, 0, rH);
-  lin(b.D16[0], xH, p.dec[1], H, w->dec_b[1], ctH, DF_RELU, slope, nullptr, 0, 0, b.D16[1], xH, ctH, 0, 0, 0, 0, rH);
-  lin(b.D16[1], xH, p.dec[2], H, sp.padded() ? sc + p.dec_b2 : w->dec_b[2], Np / 16, DF_RELU | DF_RM_SC1, slope, sc + b.DEC, sF, Np, 0, 0, 0, 0, 0, 0, 0,
-      range_for(Np / 16 * rt, cus));
-  {  // per sample: head Linear -> DMoL draw -> x_{t+1}
-    Operands o;
-    o.p[DMOLS_DEC] = {sc + b.DEC, sF}; o.p[DMOLS_W] = w->lik_w; o.p[DMOLS_B] = w->lik_b; o.p[DMOLS_U] = {u, (long)B * S * VD_K}; o.p[DMOLS_V] = {v, (long)B * S};
-    o.p[DMOLS_X] = {x_out, S}; o.p[DMOLS_X16] = {sc + b.X16 + xS, xS}; o.ld[DMOLS_LD_DEC] = Np; o.ld[LD_OUT] = T * S; o.n16[N16_OUT] = ctS; o.i[DMOLS_I_S] = S;
-    o.i[DMOLS_I_F] = VD_F; o.i[DMOLS_I_NMIX] = VD_K; o.f[DMOLS_F_LOG_EPS] = log_eps;
-    add_desc(bld, K_DMOLS, Sp / 4, 0, range_for(Sp / 4 * rt, r_main), 16, 0, 0, T, o);
-  }
-  // sentinel-fill everything the launch polls (all step slabs), then the initial frame stack and state
-  BLVM_HIP(pchain_fill_sentinel(sc + b.X16, sizeof(float) * (b.dummyZ - b.X16), s));
-  BLVM_TRY(pchain_rows_to_t16(x0, S, B, Sp, sc + b.X16, s, 0, S));
-  BLVM_TRY(pchain_rows_to_t16(h0, R, B, R, sc + b.H16, s));
-  BLVM_HIP(copy_or_zero(sc + b.HS, h0, sizeof(float) * (size_t)B * R, s));
+  vrnn_generate_program(bld, ot, device_cus(), pchain_tune(), w, p, b, sc, eps, u, v, x_out, T, B, S, H, Z, R, sd_eps, slope, log_eps);
+  const float* const srcs[] = {x0, h0};
+  BLVM_TRY(fill_and_prefill(b.X16, b.polled_end, vrnn_generate_prefills(b, S, R), srcs, B, sc, s));
   BLVM_TRY(pchain_launch(bld, "vrnn_generate", s));
-  if (h_out) BLVM_HIP(hipMemcpyAsync(h_out, sc + b.HS + (size_t)T * sR, sizeof(float) * (size_t)B * R, hipMemcpyDeviceToDevice, s));
+  if (h_out) BLVM_HIP(hipMemcpyAsync(h_out, sc + b.HS + (size_t)T * B * R, sizeof(float) * (size_t)B * R, hipMemcpyDeviceToDevice, s));
   return BLVM_OK;
 }

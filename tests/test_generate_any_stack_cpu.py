@@ -77,7 +77,7 @@ def test_cases_are_not_vacuous(name):
 
 
 def test_padded_program_replayed_on_the_host(tmp_path):
-    """tests/host/lstm_decode_ragged_plan_test.hip: the program of csrc/lstm_decode.h for S in {1, 5, 8, 24} x B in {1, 17} x {1, 2}
+    """tests/host/lstm_decode_ragged_plan_test.hip (on tests/host/rollout_replay.h): the program of csrc/lstm_decode.h for S in {1, 5, 8, 24} x B in {1, 17} x {1, 2}
     layers x T = 3 on 256 and 32 CUs, with and without XCD-aware placement, replayed word by word — every polled word a link reads
     (the pad columns of the frame-stack operand and of the last decoder layer included) prefilled or written by exactly one earlier
     link, no word written twice, x_out complete at width S, no read past the caller's u, v or bias, the regions disjoint; programs

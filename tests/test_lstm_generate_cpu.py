@@ -174,7 +174,7 @@ def test_generate_checks_its_arguments_without_a_device():
 
 
 def test_decode_program_replayed_on_the_host(tmp_path):
-    """tests/host/lstm_decode_plan_test.hip: the program of csrc/lstm_decode.h for B in {1, 16, 17, 128} x {1, 2} layers x T = 3 on
+    """tests/host/lstm_decode_plan_test.hip (on tests/host/rollout_replay.h): the program of csrc/lstm_decode.h for B in {1, 16, 17, 128} x {1, 2} layers x T = 3 on
     256 and 32 CUs, replayed word by word — every polled read prefilled or written by exactly one earlier link, no word written
     twice, every tile owned once, the layout's regions disjoint; two deliberately miswired programs must be caught.  No GPU call."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
