@@ -1108,8 +1108,70 @@ def gen_split_eval():
     save("split_eval.npz", **arrays)
 
 
+STACK_SIZES_FULL_GRAD = 8192  # largest gradient stored whole: the [32, 256] first encoder weight and the [30 * 256] last decoder bias
+
+
+def stack_sizes_case(kind, S):
+    """(B, T, x_sl) of gen_stack_sizes' batch for a model kind and frame-stack size (tests rebuild the inputs from this)."""
+    if S == 256:  # T' = 3, stride ceil(640 / 3) = 214: x_sl = 500 is 3 steps to the KL mask and 2 stacks to the likelihood mask
+        return (3, 896, [896, 700, 300]) if kind == "lstm" else (3, 640, [640, 500, 300])
+    return (4, 37, [37, 30, 21, 2]) if kind == "lstm" else (4, 37, [37, 30, 21, 1])  # (packing: descending, more than one stack each)
+
+
+def gen_stack_sizes():
+    """VRNNAudio, SRNNAudio(smoothing) and LSTMAudio at the frame-stack sizes 1 and 256 of the benchmark table (hidden 32, latent 16).
+    Weights are NOT stored: `torch.manual_seed(S)` + construction order, pinned by per-tensor checksums (as gen_vrnn_full)."""
+    arrays = {}
+    cks = lambda t: np.array([t.double().sum().item(), t.double().abs().sum().item()])  # noqa: E731
+    for kind in ("vrnn", "srnn", "lstm"):
+        for S in (1, 256):
+            tag = f"{kind}{S}"
+            torch.manual_seed(S)
+            if kind == "vrnn":
+                m = RM.VRNNAudio(likelihood="DMoL", input_size=S, hidden_size=32, latent_size=16, residual_posterior=True, num_mix=10, num_bins=2**16)
+            elif kind == "srnn":
+                m = RM.SRNNAudio(likelihood="DMoL", input_size=S, hidden_size=32, latent_size=16, residual_posterior=True, smoothing=True, num_mix=10, num_bins=2**16)
+            else:
+                m = RM.LSTMAudio(stack_size=S, hidden_size=32, num_layers=1, num_mix=10, num_bins=2**16)
+            names = []
+            for k, v in m.state_dict().items():
+                names.append(k)
+                arrays[f"{tag}_cks.{k}"] = np.array([v.double().sum().item(), v.double().abs().sum().item(), *v.shape], dtype=np.float64)
+            arrays[f"{tag}_param_names"] = np.array(names)
+            B, T, lens = stack_sizes_case(kind, S)
+            x, _ = O.synth_batch(B, T, seed=S)
+            x_sl = torch.tensor(lens)
+            x = x * (torch.arange(T).unsqueeze(0) < x_sl.unsqueeze(1))
+            arrays.update({f"{tag}_x_sl": x_sl, f"{tag}_x_cks": cks(x)})
+            if kind == "lstm":
+                torch.manual_seed(5)
+                loss, metrics, o = m(x, x_sl)
+                loss.backward()
+                arrays.update({f"{tag}_loss": loss, f"{tag}_log_prob": o.ll, f"{tag}_h_n": o.s_n[0], f"{tag}_c_n": o.s_n[1], f"{tag}_z_sl": o.z_sl})
+            else:
+                Tp = math.ceil(T / S)
+                eps = replay_eps(123, Tp, B, 16)
+                torch.manual_seed(123)
+                loss, metrics, o = m(x, x_sl, beta=0.8, free_nats=1.0)
+                loss.backward()
+                arrays.update({f"{tag}_eps_cks": cks(eps), f"{tag}_loss": loss, f"{tag}_elbo": o.elbo, f"{tag}_log_prob": o.log_prob,
+                               f"{tag}_kl": o.kl, f"{tag}_z_sl": o.z_sl})
+                if kind == "vrnn":
+                    arrays[f"{tag}_h_n"] = o.h_n
+                else:
+                    arrays.update({f"{tag}_d_n": o.d_n, f"{tag}_a_n": o.a_n, f"{tag}_z_n": o.z_n})
+            arrays[f"{tag}_metric_names"] = np.array([mm.name for mm in metrics])
+            arrays[f"{tag}_metric_values"] = np.array([mm.value for mm in metrics], dtype=np.float64)
+            arrays[f"{tag}_grad_names"] = np.array([k for k, _ in m.named_parameters()])
+            arrays[f"{tag}_grad_norms"] = np.array([p.grad.double().norm().item() for _, p in m.named_parameters()])
+            for k, p in m.named_parameters():
+                if p.numel() <= STACK_SIZES_FULL_GRAD:
+                    arrays[f"{tag}_grad.{k}"] = p.grad
+    save("stack_sizes.npz", **arrays)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["functions", "vrnn_small", "vrnn_full", "lstm", "srnn", "wavenet", "rssm", "cwvae", "stcn", "heads", "generate", "generate16", "wavenet_stacked", "cwvae_resets", "stcn_bottom_up", "lstm_layers", "data", "split_eval", "heads_stress"]
+    which = sys.argv[1:] or ["functions", "vrnn_small", "vrnn_full", "lstm", "srnn", "wavenet", "rssm", "cwvae", "stcn", "heads", "generate", "generate16", "wavenet_stacked", "cwvae_resets", "stcn_bottom_up", "lstm_layers", "data", "split_eval", "heads_stress", "stack_sizes"]
     for w in which:
         globals()[f"gen_{w}"]()

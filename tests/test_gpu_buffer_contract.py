@@ -443,10 +443,10 @@ def test_vrnn_seq_fwd_c_abi_defines_every_word_of_decin(monkeypatch):
 
 
 @gpu
-@pytest.mark.parametrize("S,layout", [(5, 0), (64, 1)], ids=["frame_kernel", "rows_kernel"])
+@pytest.mark.parametrize("S,layout", [(5, 0), (64, 1), (128, 1)], ids=["frame_kernel", "rows_kernel", "rows_kernel_two_units_per_row"])
 def test_dmol_ll_twise_is_a_caller_zeroed_output(S, layout):
-    """ll_twise is the one output found that the header had to mark "caller zeroes": the kernels (S = 5: one lane per frame; S = 64:
-    the 64-frame row units) write it at the frames t < x_sl[b] only, which `test_gpu_heads.py` pins.  What holds, then: `ops` hands
+    """ll_twise is the one output found that the header had to mark "caller zeroes": the kernels (S = 5: one lane per frame; S = 64
+    and 128: the 64-frame row units, one and two per row) write it at the frames t < x_sl[b] only, which `test_gpu_heads.py` pins.  What holds, then: `ops` hands
     the kernel zeros, so the masked frames of what it returns are zeros; the written frames do not depend on what the buffer held
     (a NaN-filled buffer through the C ABI gives the same bits); the per-utterance sums meet the bound of
     `test_dmol_forward_backward_vs_oracle` against the float64 oracle."""

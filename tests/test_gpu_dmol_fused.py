@@ -70,10 +70,17 @@ def _fused(dec, W, b, y, x_sl, gb, B, T, Tp, S, slope, ws, grads=True):
     return rc, dz, dW, db
 
 
-@pytest.mark.parametrize("ragged", [False, True])
-def test_fused_backward_vs_unfused_and_oracle(ragged):
-    """[64,16000], S = 64, time-major: full-length and ragged lengths."""
-    B, T, S, slope = 64, 16000, 64, 0.01
+@pytest.mark.parametrize("B,T,S,ragged", [
+    pytest.param(64, 16000, 64, False, id="False"),
+    pytest.param(64, 16000, 64, True, id="True"),
+    # several 64-frame units per stack row, T ending half a row early: chunk boundaries inside a row, a last unit wholly past T
+    (3, 5 * 128 - 64, 128, True),
+    (3, 3 * 256 - 128, 256, True),
+    (400, 3 * 256 - 128, 256, True),  # the chunk count capped by the chip's fill: 2 chunks of 6 units
+])
+def test_fused_backward_vs_unfused_and_oracle(B, T, S, ragged):
+    """[64,16000], S = 64, time-major: full-length and ragged lengths; S = 128 and 256 (two and four units per row), ragged."""
+    slope = 0.01
     Tp, x, x_sl, dec_bm, W, b, gb = _inputs(B, T, S, ragged, seed=21 + int(ragged))
     dec = dec_bm.view(B, Tp, S * 30).transpose(0, 1).contiguous().view(Tp * B, S * 30).to(DEV)
     Wd, bd, y, xs, gd = W.to(DEV), b.to(DEV), x.to(DEV), x_sl.to(DEV, torch.int32), gb.to(DEV)
@@ -98,7 +105,7 @@ def test_fused_backward_vs_unfused_and_oracle(ragged):
     rW, rb = _oracle_head_grads(torch.float32, dec_bm, W, b, x, x_sl, gb, T)
     for name, got, r32, tr in (("dW", dW, rW, tW), ("db", db, rb, tb)):
         e, e32 = rel_l2(got, tr), rel_l2(r32, tr)
-        print(f"[dmol_fused ragged={ragged}] {name}: rel-L2 vs float64 oracle {e:.3e} (fp32 oracle {e32:.3e}, bar {max(4 * e32, 1e-5):.3e})")
+        print(f"[dmol_fused B={B} T={T} S={S} ragged={ragged}] {name}: rel-L2 vs float64 oracle {e:.3e} (fp32 oracle {e32:.3e}, bar {max(4 * e32, 1e-5):.3e})")
         assert e <= max(4 * e32, 1e-5), (name, e, e32)
 
 
@@ -149,9 +156,11 @@ def _check_pair_equals_separate_nodes(B, T, Tp, S, x, x_sl, W, b, gb, rows_path)
         assert rel_l2(a, c) <= 1e-5
 
 
-def test_autograd_pair_equals_separate_nodes_on_rows_path():
-    """S = 64: MLP(head_gates) + fused head == MLP + head (whose backward is the same kernel without the gate) + blvm_act_bwd_f32."""
-    B, Tp, S = 5, 6, 64
+@pytest.mark.parametrize("S,Tp", [(64, 6), (128, 3), (256, 2)])
+def test_autograd_pair_equals_separate_nodes_on_rows_path(S, Tp):
+    """S % 64 == 0: MLP(head_gates) + fused head == MLP + head (whose backward is the same kernel without the gate) + blvm_act_bwd_f32.
+    T ends 9 frames before the end of the last 64-frame unit."""
+    B = 5
     T = Tp * S - 9
     _, x, x_sl, _, W, b, gb = _inputs(B, T, S, True, seed=6)
     _check_pair_equals_separate_nodes(B, T, Tp, S, x, x_sl, W, b, gb, rows_path=True)

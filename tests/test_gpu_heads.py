@@ -258,9 +258,43 @@ def head_case(hs, kind, bins, B, Tp, S, layout, linear, unaligned=False, seed=0)
     (3, 20, 5, 1, "none", False),   # generic kernel, W = NULL
     (2, 3, 64, 0, "eye", True),     # S = 64 through an unaligned base pointer: generic kernel
     (300, 2, 1, 1, "eye", False),   # B > 256: per-utterance sums by global fp64 atomics
+    # rows kernel with several 64-frame units per stack row (upr = S / 64 > 1)
+    (3, 5, 128, 1, "eye", False),   # upr 2: 10 units in chunks [0,3) [3,6) [6,10), boundaries inside a row; the last row's 2nd unit is past T
+    (3, 5, 128, 0, "eye", False),   # the same, batch-major
+    (3, 5, 192, 1, "none", False),  # upr 3 (odd), W = NULL: 15 units in 4 chunks
+    (2, 3, 256, 1, "eye", False),   # upr 4: chunks coincide with rows (the contrast case)
+    (400, 3, 256, 1, "eye", False),  # the chunk count capped by the chip's fill: 2 chunks of 6 units, the boundary inside row 1
+    (2, 3, 128, 0, "eye", True),    # S = 128 through an unaligned base pointer: generic kernel
 ])
 def test_dmol_per_frame_vs_float64(hs, bins, B, Tp, S, layout, linear, unaligned):
-    head_case(hs, "dmol", bins, B, Tp, S, layout, linear, unaligned, seed=B + S + layout)
+    if S >= 128:
+        # (the unaligned case takes the generic kernel: no chunks; its frames are laid out the same way)
+        rows_units_setup(B, Tp, S, expect_chunks=None if unaligned else {(3, 128): 3, (3, 192): 4, (2, 256): 3, (400, 256): 2}[(B, S)])
+    margins = head_case(hs, "dmol", bins, B, Tp, S, layout, linear, unaligned, seed=B + S + layout)
+    print(f"[heads dmol/{bins} B={B} Tp={Tp} S={S} layout={layout} {linear}{' unaligned' if unaligned else ''}] worst err / bar: "
+          + ", ".join(f"{k} {v:.3g}" for k, v in margins.items()))
+
+
+def rows_units_setup(B, Tp, S, expect_chunks):
+    """What a several-units-per-row case is there for, from the host-side index arithmetic alone (dmol.hip: unit u of an utterance
+    is frames [64 u, 64 u + 64); chunk c walks units [c units / n, (c + 1) units / n), n = min(ceil(units / 4), ceil(fill / B)),
+    fill = resident workgroups per CU x CUs): some unit has no valid frame, some unit is cut by x_sl mid-way, and the chunk split is
+    the one the case names."""
+    _, x_sl, _ = frames_layout(B, Tp, S)
+    units = Tp * (S // 64)
+    start = 64 * torch.arange(units).unsqueeze(0)
+    ln = x_sl.unsqueeze(1)
+    assert bool((start >= ln).any()), "set-up: no unit without a valid frame"
+    assert bool(((start < ln) & (ln < start + 64)).any()), "set-up: no unit that x_sl cuts mid-way"
+    if expect_chunks is None:
+        return
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    for per_cu in (2, 3):  # resident workgroups per CU: 3 by the launch bounds, 2 the library's fallback
+        n = max(1, min((units + 3) // 4, (per_cu * cus + B - 1) // B))
+        assert n == expect_chunks, f"set-up: {n} chunks at {per_cu} workgroups x {cus} CUs (want {expect_chunks})"
+    bounds = [c * units // expect_chunks for c in range(1, expect_chunks)]
+    if S != 256 or B == 400:
+        assert any(bd % (S // 64) for bd in bounds), f"set-up: no chunk boundary inside a stack row ({bounds})"
 
 
 @pytest.mark.parametrize("kind", ["gmm", "gauss"])
@@ -271,10 +305,10 @@ def test_gaussian_heads_per_frame_vs_float64(hs, kind, B, Tp, S, layout, linear)
     head_case(hs, kind, 2**16, B, Tp, S, layout, linear, seed=3 * B + S)
 
 
-@pytest.mark.parametrize("kind,S,layout", [("dmol", 64, 1), ("dmol", 5, 0), ("gmm", 64, 0), ("gmm", 1, 1), ("gauss", 8, 0)])
+@pytest.mark.parametrize("kind,S,layout", [("dmol", 64, 1), ("dmol", 5, 0), ("gmm", 64, 0), ("gmm", 1, 1), ("gauss", 8, 0), ("dmol", 256, 1)])
 def test_heads_random_linear_vs_float64(hs, kind, S, layout):
     """The head's Linear (random W, bias) on the crafted frames' neighbourhood: d_dec, dW, db per element against float64,
-    through the autograd wrappers (rows kernel at S = 64, generic kernel otherwise)."""
+    through the autograd wrappers (rows kernel at S = 64 and, four units per row, at S = 256; generic kernel otherwise)."""
     par, y, _, _ = fixture_frames(hs, kind, 256 if kind == "dmol" else 2**16)
     beta = float(hs["gmm_beta"]) if kind != "dmol" else 1.0
     sd_eps = float(hs["gmm_sd_eps"]) if kind != "dmol" else 0.0

@@ -45,7 +45,10 @@ def rel_l2(a, b):
 
 
 @pytest.mark.parametrize("op_a,op_b", [(0, 0), (0, 1), (1, 0), (1, 1)])
-@pytest.mark.parametrize("M,N,K", [(64, 64, 16), (130, 70, 50), (256, 1920, 768), (1000, 30, 30), (16, 256, 1003)])
+@pytest.mark.parametrize("M,N,K", [(64, 64, 16), (130, 70, 50), (256, 1920, 768), (1000, 30, 30), (16, 256, 1003),
+                                   (185, 32, 1),      # K = 1: a frame-stack of one sample into the first encoder layer (lda = ldb = 1)
+                                   (48, 7680, 32),    # N = 256 * 30: the decoder's last layer at a frame-stack of 256
+                                   (185, 32, 7680)])  # ... and its data gradient (K = 7680)
 def test_gemm_layouts_and_edges(op_a, op_b, M, N, K):
     g = torch.Generator().manual_seed(M * 7 + N * 3 + K + op_a * 2 + op_b)
     A = torch.randn(*((K, M) if op_a else (M, K)), generator=g)
@@ -87,7 +90,8 @@ def test_gemm_192_wide_tiles(op_a, op_b, M, N, K, split):
     assert rel_l2(C, ref + 2) < 3e-6
 
 
-@pytest.mark.parametrize("N,K,rows,split", [(256, 256, 16000, 0), (96, 80, 4099, 16), (1920, 256, 3000, 1), (30, 30, 1000, 0), (384, 200, 20001, 24)])
+@pytest.mark.parametrize("N,K,rows,split", [(256, 256, 16000, 0), (96, 80, 4099, 16), (1920, 256, 3000, 1), (30, 30, 1000, 0), (384, 200, 20001, 24),
+                                            (32, 1, 185, 0), (7680, 32, 48, 0)])  # the frame-stack sizes 1 (K = 1, ldx = 1) and 256 (N = 7680)
 def test_wgrad_with_bias_gradient_in_one_launch(N, K, rows, split):
     """blvm_wgrad_f32: dW += D^T X and db += column sums of D from the same launch (first column block of the GEMM), both accumulating."""
     g = torch.Generator().manual_seed(N + K + rows)
@@ -134,19 +138,26 @@ def test_wgrad_group_one_launch_equals_float64(rows):
             assert rel_l2(db, b) < 3e-6
 
 
-def test_mlp_function_forward_backward_vs_torch():
+@pytest.mark.parametrize("widths,rows", [((24, 64, 64, 48), 300),
+                                         ((1, 32, 32), 185),       # an encoder at a frame-stack of 1: K = 1 forward and weight gradient
+                                         ((48, 32, 7680), 9)],     # a decoder at a frame-stack of 256: N = 7680, data gradient over K = 7680
+                         ids=["24_64_64_48-300", "1_32_32-185", "48_32_7680-9"])
+def test_mlp_function_forward_backward_vs_torch(widths, rows):
+    """ops.mlp against the same layers in float64 on the CPU."""
     torch.manual_seed(3)
-    lins = [torch.nn.Linear(24, 64), torch.nn.Linear(64, 64), torch.nn.Linear(64, 48)]
-    x = torch.randn(300, 24)
-    xr = x.clone().requires_grad_(True)
+    lins = [torch.nn.Linear(i, o) for i, o in zip(widths[:-1], widths[1:])]
+    x = torch.randn(rows, widths[0])
+    xr = x.double().requires_grad_(True)
     y = xr
     for l in lins:
+        l.double()
         y = torch.nn.functional.leaky_relu(l(y))
-    w = torch.randn_like(y)
-    (y * w).sum().backward()
+    w = torch.randn(rows, widths[-1])
+    (y * w.double()).sum().backward()
     ref = [p.grad.clone() for l in lins for p in (l.weight, l.bias)] + [xr.grad.clone()]
     for l in lins:
         l.zero_grad()
+        l.float()
         l.to(DEV)
     xd = x.to(DEV).requires_grad_(True)
     yd = ops.mlp(xd, lins)
@@ -185,7 +196,7 @@ def test_dmol_golden_edge_cases_identity_linear():
         assert float(lp.cpu()) == pytest.approx(float(ref.sum()), rel=1e-5)
 
 
-@pytest.mark.parametrize("layout,S", [(0, 1), (1, 8), (1, 64), (0, 5)])
+@pytest.mark.parametrize("layout,S", [(0, 1), (1, 8), (1, 64), (0, 5), (1, 128), (0, 256)])  # S >= 128: several 64-frame units per row
 def test_dmol_forward_backward_vs_oracle(layout, S):
     g = torch.Generator().manual_seed(11 + S)
     B, Tp = 3, 7

@@ -509,3 +509,110 @@ def test_heads_stress_kl_free_nats_ties(hs):
     # at a tie d max(kl, floor)/d kl is 1/2 (torch.maximum), so the floored gradient there is half the raw one
     g_fn, g_kl = T(hs["kl_grad_fn_mq"])[:, ::16], T(hs["kl_grad_kl_mq"])[:, ::16]
     torch.testing.assert_close(g_fn, 0.5 * g_kl, rtol=0, atol=0)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the recurrent models at the frame-stack sizes 1 and 256 of the reference's benchmark table (tests/golden/stack_sizes.npz)
+# ----------------------------------------------------------------------------------------------------------------------
+
+STACK_SIZES_BETA, STACK_SIZES_FREE_NATS = 0.8, 1.0
+
+
+def stack_sizes_setup(kind, S, cks_rel=1e-12):
+    """The model, batch and noise of gen_stack_sizes for (kind, S), rebuilt from the seeds and checked against the fixture's checksums
+    (the weights are not stored).  Returns (model on the CPU, x, x_sl, eps or None, fixture, key prefix); `test_gpu_stack_sizes.py`
+    starts from the same set-up.  cks_rel: checksum tolerance relative to the sum of magnitudes -- 1e-12 on the host that wrote the
+    fixture; another host's CPU rounds the orthogonal initialisation's QR and the mu-law's float32 log differently in the last place
+    (seen: 2e-7 of a GRU weight's sum, 3e-9 of the batch's), so the GPU tests pass 1e-6: the same tensors to float32 rounding."""
+
+    def same(t, cks, what):
+        s, a = t.double().sum().item(), t.double().abs().sum().item()
+        assert abs(s - cks[0]) <= cks_rel * cks[1] + 1e-9 and abs(a - cks[1]) <= cks_rel * cks[1], (what, s, a, cks[:2])
+
+    from blvm.models import LSTMAudio, SRNNAudio, VRNNAudio
+
+    g = np.load(os.path.join(GOLDEN, "stack_sizes.npz"))
+    tag = f"{kind}{S}"
+    torch.manual_seed(S)
+    if kind == "vrnn":
+        m = VRNNAudio(likelihood="DMoL", input_size=S, hidden_size=32, latent_size=16, residual_posterior=True, num_mix=10, num_bins=2**16)
+    elif kind == "srnn":
+        m = SRNNAudio(likelihood="DMoL", input_size=S, hidden_size=32, latent_size=16, residual_posterior=True, smoothing=True, num_mix=10, num_bins=2**16)
+    else:
+        m = LSTMAudio(stack_size=S, hidden_size=32, num_layers=1, num_mix=10, num_bins=2**16)
+    sd = m.state_dict()
+    assert list(sd.keys()) == g[f"{tag}_param_names"].tolist()
+    for k, v in sd.items():
+        cks = g[f"{tag}_cks.{k}"]
+        assert list(v.shape) == [int(s) for s in cks[2:]], k
+        same(v, cks, k)
+    x_sl = T(g[f"{tag}_x_sl"])
+    B, T_ = x_sl.numel(), int(x_sl.max())
+    x = O.synth_batch(B, T_, seed=S)[0] * (torch.arange(T_).unsqueeze(0) < x_sl.unsqueeze(1))
+    same(x, g[f"{tag}_x_cks"], "x")
+    eps = None
+    if kind != "lstm":
+        torch.manual_seed(123)
+        eps = torch.stack([torch.randn(B, 16) for _ in range(-(-T_ // S))], 0)
+        same(eps, g[f"{tag}_eps_cks"], "eps")
+    return m, x, x_sl, eps, g, tag
+
+
+def stack_sizes_oracle(kind, S, sd, x, x_sl, eps):
+    if kind == "vrnn":
+        return O.vrnn_audio_forward(sd, x, x_sl, eps, beta=STACK_SIZES_BETA, free_nats=STACK_SIZES_FREE_NATS, stack=S)
+    if kind == "srnn":
+        return O.srnn_audio_forward(sd, x, x_sl, eps, beta=STACK_SIZES_BETA, free_nats=STACK_SIZES_FREE_NATS, stack=S)
+    return O.lstm_audio_forward(sd, x, x_sl, stack=S, num_bins=2**16)
+
+
+@pytest.mark.parametrize("S", [1, 256])
+@pytest.mark.parametrize("kind", ["vrnn", "srnn", "lstm"])
+def test_stack_sizes_forward_backward(kind, S):
+    """The fp32 oracle at stack = 1 and 256 against the reference: the bars of the small-model tests above.  At S = 256 the stride
+    ceil(T / T') = 214 is not the stack size, and x_sl = 500 is 3 steps to the KL mask and 2 stacks to the likelihood mask."""
+    m, x, x_sl, eps, g, tag = stack_sizes_setup(kind, S)
+    sd = {k: v.clone().requires_grad_(True) for k, v in m.state_dict().items()}
+    out = stack_sizes_oracle(kind, S, sd, x, x_sl, eps)
+    T_ = x.size(1)
+    stride = -(-T_ // -(-T_ // S))
+    if kind == "lstm":
+        close(out["loss"], g[f"{tag}_loss"], 1e-6, 0)
+        close(out["ll"], g[f"{tag}_log_prob"], 1e-6, 1e-4)
+        close(out["h_n"], g[f"{tag}_h_n"][0], 1e-5, 1e-6)
+        close(out["c_n"], g[f"{tag}_c_n"][0], 1e-5, 1e-6)
+        assert g[f"{tag}_z_sl"].tolist() == [-(-n // S) for n in x_sl.tolist()]
+    else:
+        assert out["loss"].dtype == torch.float64
+        close(out["loss"], g[f"{tag}_loss"], 1e-7, 0)
+        close(out["elbo"], g[f"{tag}_elbo"], 1e-7, 0)
+        close(out["log_prob"], g[f"{tag}_log_prob"], 1e-7, 0)
+        close(out["kl"], g[f"{tag}_kl"], 1e-6, 1e-6)
+        assert g[f"{tag}_z_sl"].tolist() == [-(-n // stride) for n in x_sl.tolist()]
+        if S == 256:
+            assert stride == 214 and any(-(-n // stride) != -(-n // S) for n in x_sl.tolist())
+        if kind == "vrnn":
+            close(out["h_n"], g[f"{tag}_h_n"], 1e-5, 1e-6)
+            mv = O.vrnn_metrics(out, x_sl, STACK_SIZES_BETA, STACK_SIZES_FREE_NATS)
+            for name, val in zip(g[f"{tag}_metric_names"].tolist(), g[f"{tag}_metric_values"].tolist()):
+                assert mv[name] == pytest.approx(val, rel=1e-6, abs=1e-9), name
+        else:
+            close(out["d_n"], g[f"{tag}_d_n"][0], 1e-5, 1e-6)
+            close(out["a_n"], g[f"{tag}_a_n"][0], 1e-5, 1e-6)
+            close(out["z_n"], g[f"{tag}_z_n"], 1e-5, 1e-6)
+    out["loss"].backward()
+    names = g[f"{tag}_grad_names"].tolist()
+    assert names == [k for k, _ in m.named_parameters()]
+    stored = set()
+    for name, norm in zip(names, g[f"{tag}_grad_norms"].tolist()):
+        gr = sd[name].grad
+        assert gr.double().norm().item() == pytest.approx(norm, rel=2e-5), name  # (what the per-tensor bar below implies for a norm)
+        if f"{tag}_grad.{name}" in g.files:
+            ref = T(g[f"{tag}_grad.{name}"])
+            err = (gr - ref).norm() / (ref.norm() + 1e-12)
+            assert err < 2e-5, (name, float(err))
+            stored.add(name)
+        else:
+            assert gr.numel() > 8192, name
+    first, last = ("embedding.0.weight", "decoder.4.bias") if kind == "lstm" else (f"{kind}.encoder.2.weight", f"{kind}.decoder.4.bias")
+    assert {first, last} <= stored and sd[first].shape == (32, S) and sd[last].shape == (30 * S,)
