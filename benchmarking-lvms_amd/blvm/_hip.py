@@ -198,6 +198,9 @@ _SIGNATURES = {
     "blvm_dwconv_bwd": (c_int, [c_void_p] * 6 + [c_int] * 8 + [c_void_p] * 4),
     "blvm_resample_add_fwd": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2),
     "blvm_resample_add_bwd": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2),
+    "blvm_ctc_scratch_floats": (c_size_t, [c_int] * 4),
+    "blvm_ctc_loss": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 5),
+    "blvm_ctc_greedy": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 3),
 }  # fmt: skip
 
 EXPORTS = tuple(_SIGNATURES)

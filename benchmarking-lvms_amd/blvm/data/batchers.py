@@ -23,6 +23,22 @@ class ListBatcher(Batcher):
         return batch, torch.LongTensor([len(b) for b in batch])
 
 
+class TextBatcher(Batcher):
+    """Right-pad lists of token indices to the longest one: LongTensors [B, L_max] and [B] (batchers.py:67-89)."""
+
+    def __init__(self, pad_value: int = 0) -> None:
+        self.pad_value = pad_value
+
+    def collate(self, batch: List[List[int]]):
+        lengths = [len(row) for row in batch]
+        width = max(lengths)
+        return torch.LongTensor([row + [self.pad_value] * (width - n) for row, n in zip(batch, lengths)]), torch.LongTensor(lengths)
+
+    def sort(self, batch, sort_modality_idx: Optional[int] = None):
+        key = (lambda ex: len(ex[0])) if sort_modality_idx is None else (lambda ex: len(ex[0][sort_modality_idx]))
+        return sorted(batch, key=key, reverse=True)
+
+
 class DynamicTensorBatcher(Batcher):
     """Right-pad tensors along one dynamic dimension to the longest example and stack them: [B, *, T_max, *] and the true
     lengths as a LongTensor (batchers.py:113-143); `sort` orders a batch longest first (:145-151)."""

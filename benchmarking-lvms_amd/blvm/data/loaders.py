@@ -51,3 +51,30 @@ class AudioLoader(Loader):
             x, rate = torchaudio.load(path)
         x = x.sum(0) if self.sum_channels else x
         return x, dict(sample_rate=rate, length=x.shape[-1], file=path)
+
+
+class TextLoader(Loader):
+    """The text of `<example>.<extension>` as one string, line breaks turned into spaces (loaders.py:165-181)."""
+
+    def load(self, path: str):
+        with open(path, "r") as f:
+            text = " ".join(f.read().split())
+        return text, dict(length=len(text), word_length=len(text.split()), file=path)
+
+
+class NumpyLoader(Loader):
+    """An array `<example>.<extension>` (.npy, or `key` of an .npz) as a tensor; `length_dim` is its time axis (loaders.py:212-236).
+    The extension may itself hold dots: dumped representations are `<example>.<tag>-z0-n1.npy`."""
+
+    def __init__(self, extension: str, cache: bool = False, length_dim: int = 0, key: str = None, dtype: torch.dtype = None):
+        super().__init__(extension, cache)
+        self.length_dim, self.key, self.dtype = length_dim, key, dtype
+
+    def load(self, path: str):
+        arr = np.load(path)
+        if self.key is not None:
+            arr = arr[self.key]
+        x = torch.from_numpy(np.ascontiguousarray(arr))
+        if self.dtype is not None:
+            x = x.to(self.dtype)
+        return x, dict(length=x.shape[self.length_dim], file=path)

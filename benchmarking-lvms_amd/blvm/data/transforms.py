@@ -23,6 +23,18 @@ class StackTensor(Transform):
         return x
 
 
+class EncodeInteger(Transform):
+    """A string -> the indices of its tokens (transforms.py:66-75)."""
+
+    def __init__(self, tokenizer, token_map):
+        super().__init__()
+        self.tokenizer = tokenizer
+        self.token_map = token_map
+
+    def forward(self, x: str):
+        return self.token_map.encode(self.tokenizer(x))
+
+
 class MuLawEncode(Transform):
     def __init__(self, bits: int = 8):
         super().__init__()

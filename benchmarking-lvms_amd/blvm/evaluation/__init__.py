@@ -2,6 +2,7 @@ from .metrics import (  # noqa: F401
     BitsPerDimMetric,
     DeferredScalars,
     EMAMetric,
+    ErrorRateMetric,
     KLMetric,
     LatestMeanMetric,
     LLMetric,

@@ -107,6 +107,38 @@ def no_value(metrics: List[Metric]):
 GET_BEST = dict(none=no_value, min=min_value, max=max_value)
 
 
+def edit_distance(ref, hyp) -> int:
+    """Levenshtein distance between two token sequences (unit cost for a substitution, an insertion and a deletion)."""
+    ref, hyp = list(ref), list(hyp)
+    row = list(range(len(hyp) + 1))  # distances from the empty reference prefix
+    for i, r in enumerate(ref, 1):
+        diag, row[0] = row[0], i
+        for j, h in enumerate(hyp, 1):
+            diag, row[j] = row[j], min(row[j] + 1, row[j - 1] + 1, diag + (r != h))
+    return row[-1]
+
+
+class ErrorRateMetric(Metric):
+    """Edits / reference length over tokenised strings (blvm/evaluation/metrics.py:68-85): word error rate with `word_tokenizer`,
+    character error rate with `char_tokenizer`.  `update` adds both counts, so the value over an epoch is the pooled rate."""
+
+    def __init__(self, refs, hyps, tokenizer, name="er", tags=None):
+        super().__init__(name=name, tags=tags, get_best="min")
+        self._edits, self._len = 0, 0
+        for ref, hyp in zip(refs, hyps):
+            r, h = tokenizer(ref), tokenizer(hyp)
+            self._edits += edit_distance(r, h)
+            self._len += len(r)
+
+    @property
+    def value(self):
+        return self._edits / self._len if self._len else float("nan")
+
+    def update(self, metric: "ErrorRateMetric"):
+        self._edits += metric._edits
+        self._len += metric._len
+
+
 class LatestMeanMetric(Metric):
     def __init__(self, values, name: str, tags: Set[str] = None, reduce_by=None, get_best: str = None,
                  log_to_console: bool = True, log_to_framework: bool = True):  # fmt: skip

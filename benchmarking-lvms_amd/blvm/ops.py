@@ -1773,3 +1773,88 @@ class _SepBlockFunction(torch.autograd.Function):
 
 def sep_block(x, stride, dilation, transposed, w1, b1, g1, be1, wd, bd, g2, be2, wp, eps: float = 1e-5):
     return _SepBlockFunction.apply(x, (int(stride), int(dilation), bool(transposed), float(eps)), w1, b1, g1, be1, wd, bd, g2, be2, wp)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# K9: CTC loss on un-normalised logits (log-softmax fused) and the greedy CTC decode
+# ----------------------------------------------------------------------------------------------------------------------
+
+
+def _ctc_call(logits, targets, il, tl, blank, d_nll, want_grad):
+    T, B, C = logits.shape
+    Lmax = targets.shape[1]
+    lib = load()
+    f32 = dict(device=logits.device, dtype=torch.float32)
+    nll = torch.empty(B, **f32)
+    d_logits = torch.empty_like(logits) if want_grad else None
+    scratch = torch.empty(lib.blvm_ctc_scratch_floats(T, B, C, Lmax), **f32)
+    check(
+        lib.blvm_ctc_loss(ptr(logits), ptr(targets) if Lmax else None, ptr(il), ptr(tl), T, B, C, Lmax, int(blank), ptr(d_nll), ptr(nll),
+                          ptr(d_logits), ptr(scratch), stream_ptr()),
+        "blvm_ctc_loss",
+    )  # fmt: skip
+    return nll, d_logits
+
+
+class _CTCFunction(torch.autograd.Function):
+    """The forward is the loss-only call (the alpha recursion alone); the backward is the full call with the upstream gradient as d_nll:
+    both recursions run side by side there, so it costs one serial pass as well."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, il, tl, blank):
+        nll, _ = _ctc_call(logits, targets, il, tl, blank, None, False)
+        ctx.blank = blank
+        ctx.save_for_backward(logits, targets, il, tl)
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, targets, il, tl = ctx.saved_tensors
+        _, d_logits = _ctc_call(logits, targets, il, tl, ctx.blank, g.to(torch.float32).contiguous(), True)
+        return d_logits, None, None, None, None
+
+
+def _ctc_lens(v, B, device, what):
+    if torch.is_tensor(v) and v.is_cuda and v.dtype == torch.int32:
+        out = v.contiguous()
+    else:
+        out = upload_i32(torch.as_tensor(v).reshape(-1), device)
+    if out.shape != (B,):
+        raise _hip.BlvmHipError(f"ctc: {what} must hold one length per row, [{B}], got {tuple(out.shape)}")
+    return out
+
+
+def ctc_loss(logits, targets, input_lens, target_lens, blank: int = 0):
+    """nll [B] of `log_softmax(logits, 2)` + `nn.CTCLoss(blank, reduction="none", zero_infinity=False)`, differentiable wrt the
+    UN-normalised time-major logits [T,B,C].  targets [B,Lmax] integers (host or device, right-padded); the lengths are host
+    integers (uploaded like x_sl) or int32 device tensors."""
+    ptr(logits)  # refuses a CPU tensor before anything else is touched
+    if logits.dim() != 3:
+        raise _hip.BlvmHipError(f"ctc_loss: logits must be time-major [T,B,C], got {tuple(logits.shape)}")
+    T, B, C = logits.shape
+    dev = logits.device
+    targets = torch.as_tensor(targets)
+    if targets.dim() != 2 or targets.shape[0] != B:
+        raise _hip.BlvmHipError(f"ctc_loss: targets must be [B={B},Lmax], got {tuple(targets.shape)}")
+    if not (targets.is_cuda and targets.dtype == torch.int32):
+        targets = upload_i32(targets, dev) if not targets.is_cuda else targets.to(torch.int32)
+    il, tl = _ctc_lens(input_lens, B, dev, "input_lens"), _ctc_lens(target_lens, B, dev, "target_lens")
+    logits = _f32c(logits)
+    return _CTCFunction.apply(logits, targets.contiguous(), il, tl, int(blank))
+
+
+def ctc_greedy(logits, input_lens, blank: int = 0):
+    """Greedy CTC decode of time-major logits [T,B,C] on the device: per row the arg-max labels of its first input_lens[b] frames with
+    repeats collapsed and blanks dropped, as a list of lists of ints (`blvm.utils.decoding.greedy_ctc` is the host twin).  Only the
+    [B,T] labels and [B] lengths are copied to the host."""
+    ptr(logits)
+    if logits.dim() != 3:
+        raise _hip.BlvmHipError(f"ctc_greedy: logits must be time-major [T,B,C], got {tuple(logits.shape)}")
+    T, B, C = logits.shape
+    logits = _f32c(logits.detach())
+    il = _ctc_lens(input_lens, B, logits.device, "input_lens")
+    hyp = torch.empty(B, T, device=logits.device, dtype=torch.int32)
+    hyp_lens = torch.empty(B, device=logits.device, dtype=torch.int32)
+    check(load().blvm_ctc_greedy(ptr(logits), ptr(il), T, B, C, int(blank), ptr(hyp), ptr(hyp_lens), stream_ptr()), "blvm_ctc_greedy")
+    hyp, hyp_lens = hyp.cpu().tolist(), hyp_lens.cpu().tolist()
+    return [row[:n] for row, n in zip(hyp, hyp_lens)]

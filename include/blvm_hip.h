@@ -671,6 +671,27 @@ int blvm_dwconv_bwd(const float* x, const float* in_scale, const float* in_shift
 int blvm_resample_add_fwd(const float* y, const float* x, int L_out, int L_in, int N, float* out, void* stream);
 int blvm_resample_add_bwd(const float* dout, int L_out, int L_in, int N, float* dx, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * K9  CTC loss on UN-NORMALISED logits and the greedy CTC decode.  Replaces `logits.log_softmax(2)` + `nn.CTCLoss(blank,
+ *     reduction="none")` and the host `greedy_ctc`, `blvm/models/lstm_asr.py:67-72` + `blvm/utils/decoding.py:5-29`.
+ *   logits [T,B,C] time-major; targets [B,Lmax] int32, right-padded; input_lens, target_lens [B] int32 (device).
+ *   nll [B]: -log p(targets[b,:target_lens[b]] | first input_lens[b] frames), +inf for a row with too few frames for its labels.
+ *   d_logits [T,B,C] or NULL (loss only): d_nll[b] * (softmax_t(c) - occupation_t(c)) for t < input_lens[b], exactly 0 beyond;
+ *   d_nll [B] is the upstream gradient, NULL = ones.  A row with nll = +inf has NaN gradients over its frames (torch's
+ *   zero_infinity=False).  A label outside [0,C) or a length outside [0,T] / [0,Lmax] makes that row's nll and gradient NaN;
+ *   such a value is never used as an index.  No atomics: results are bit-identical from call to call.
+ *   Limits: T, B >= 1, T * B < 2^31, 2 <= C <= 4096, 0 <= Lmax <= 512, 0 <= blank < C.
+ *   scratch: blvm_ctc_scratch_floats(T, B, C, Lmax) floats (the per-step log-sum-exp and alpha, beta [B,T,2 Lmax + 1]).
+ * blvm_ctc_greedy: per row the arg-max of each of the first input_lens[b] frames (lowest index on a tie), repeats collapsed, blanks
+ *   dropped: hyp [B,T] int32 holds hyp_lens[b] labels per row, -1 behind them.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t blvm_ctc_scratch_floats(int T, int B, int C, int Lmax);
+int blvm_ctc_loss(const float* logits, const int32_t* targets, const int32_t* input_lens, const int32_t* target_lens, int T,
+                  int B, int C, int Lmax, int blank, const float* d_nll, float* nll, float* d_logits, float* scratch,
+                  void* stream);
+int blvm_ctc_greedy(const float* logits, const int32_t* input_lens, int T, int B, int C, int blank, int32_t* hyp,
+                    int32_t* hyp_lens, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
