@@ -372,7 +372,8 @@ int pchain_ctl(unsigned** dev, unsigned** host_dev, unsigned* epoch);
 // blvm_pchain_configure).  Beyond it the links are bound by MFMA / operand bytes, not latency, and the 32x32-tile launch-per-link
 // kernels fit better.
 int pchain_max_batch();
-int pchain_tune();  // placement bits (env BLVM_PCHAIN_TUNE / blvm_pchain_tune): 4 XCD-aware tile placement, 16 canary polls of deferred tiles
+int pchain_tune();  // placement bits (env BLVM_PCHAIN_TUNE / blvm_pchain_tune): 4 XCD-aware tile placement, 16 canary polls of deferred tiles,
+                     // 32 / 64 placement of the static walks' launches (vrnn_static.h Place: plain / local where it applies)
 unsigned long long* pchain_profile_buffer();  // diagnostics: null unless blvm_pchain_profile() installed a device buffer
 
 // internal launchers shared between translation units (defined in gemm.hip)

@@ -99,7 +99,7 @@ OpType operand_type() {
 int pchain_tune() {
   if (g_pchain_tune < 0) {
     const char* e = getenv("BLVM_PCHAIN_TUNE");
-    g_pchain_tune = e ? atoi(e) : 20;
+    g_pchain_tune = e ? atoi(e) : 84;  // 4 | 16 | 64: XCD-aware programs, canary polls, the static walks placed locally
   }
   return g_pchain_tune;
 }

@@ -1,5 +1,6 @@
 // vrnn_static.h — the host arithmetic the static walk (vrnn_static.hip) shares with its host test (tests/host/static_plan_test.hip):
-// the deal of the VRNN step programs, and which of their links keep their weights in registers.
+// the deal of the VRNN step programs, which of their links keep their weights in registers, and the placement of a static launch
+// (tests/host/static_place_test.hip).
 #pragma once
 #include <algorithm>
 #include <initializer_list>
@@ -68,10 +69,55 @@ inline VrnnBwdDeal vrnn_bwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, boo
 constexpr std::initializer_list<int> kFwdResident = {1, 2, 3, 4, 5};
 constexpr std::initializer_list<int> kBwdResident = {0, 1, 2, 3, 5, 6, 7, 8, 9};
 // the converter's condition: every resident link deals a workgroup at most one tile (else the interpreter runs the program)
-inline bool one_tile_each(const Program& p, std::initializer_list<int> links) {
+// (xcd: the TileIter mode the kernel will deal with — the program's own, or plain under a placement of the launch, below)
+inline bool one_tile_each(const Program& p, std::initializer_list<int> links, bool xcd) {
   for (int i : links)
-    if (tiles_per_workgroup((p.B + 15) / 16, p.d[i].ct, p.d[i].nwg, p.xcd != 0) > 1) return false;
+    if (tiles_per_workgroup((p.B + 15) / 16, p.d[i].ct, p.d[i].nwg, xcd) > 1) return false;
   return true;
+}
+inline bool one_tile_each(const Program& p, std::initializer_list<int> links) { return one_tile_each(p, links, p.xcd != 0); }
+
+// ---- placement: a property of the static launch, not of the program (the interpreter runs the program as built) -----------------
+// Workgroups are dealt round-robin over the 8 XCDs (observed, as in TileIter: a wrong guess only costs speed), so workgroup p sits
+// on XCD p % 8.  The program's XCD-aware TileIter mode puts column tile c on XCD c % 8 so that an L2 holds 1/8 of every weight
+// matrix; the resident links read no weights in the step loop, and what that mode costs them is that the 16 producers of every
+// [16, K] slab sit on all eight XCDs.  Plain TileIter on ranges that start at multiples of 8 gives workgroup w row tile w % rt:
+// with rt = 4 a row tile lives on XCDs r and r + 4.  kPlaceLocal adds a bijection of the block index on top (place_wg) that
+// gathers the prior half of row tile r on XCD r and the posterior half on XCD r + 4.  Which workgroup computes a tile changes no
+// operand and no summation order: results do not depend on the placement.
+enum Place {
+  kPlaceProgram = 0,  // the program's TileIter mode, identity block index
+  kPlacePlain = 1,    // plain TileIter, identity block index
+  kPlaceLocal = 2,    // plain TileIter, workgroup = place_wg(block index)
+};
+constexpr int kPlaceSpan = 128;  // place_wg permutes the block indices below it
+// block index -> workgroup of the deal.  Block p < 128 on XCD x = p % 8: x < 4 -> workgroup 4 (p / 8) + x of [0, 64), row tile x;
+// x >= 4 -> workgroup 64 + 4 (p / 8) + x - 4 of [64, 128), row tile x - 4.
+__host__ __device__ __forceinline__ int place_wg(int p) { return p < kPlaceSpan ? 64 * ((p & 7) >> 2) + 4 * (p >> 3) + (p & 3) : p; }
+// place_wg is a bijection of [0, grid) for any grid >= 128: it permutes the blocks of the two halves among themselves and leaves
+// the gentle and spare ranges behind them alone, so every workgroup of the deal still runs on exactly one block.  kPlaceLocal
+// applies to a program when the halves are what the permutation was made for and every range it touches deals row tile (w % 4):
+// rt = 4, the links `prior` and `post` on [0, 64) and [64, 128), and every other link on one of those, on their union, or past them.
+inline bool place_local_applies(const Program& p, int prior, int post, int grid) {
+  if ((p.B + 15) / 16 != 4 || grid < kPlaceSpan) return false;
+  if (p.d[prior].wg0 != 0 || p.d[prior].nwg != 64 || p.d[post].wg0 != 64 || p.d[post].nwg != 64) return false;
+  for (int i = 0; i < p.ndesc; ++i) {
+    const int lo = p.d[i].wg0, hi = lo + p.d[i].nwg;
+    const bool kept = (lo == 0 && (hi == 64 || hi == kPlaceSpan)) || (lo == 64 && hi == kPlaceSpan) || lo >= kPlaceSpan;
+    if (!kept) return false;
+  }
+  return true;
+}
+// the placement a launch runs with: kPlaceLocal falls back to `fallback` (kPlacePlain or kPlaceProgram) where it does not apply
+inline int place_for(int want, int fallback, const Program& p, int prior, int post, int grid) {
+  if (want == kPlaceLocal) return place_local_applies(p, prior, post, grid) ? kPlaceLocal : (fallback == kPlacePlain ? kPlacePlain : kPlaceProgram);
+  return want == kPlacePlain ? kPlacePlain : kPlaceProgram;
+}
+inline bool place_xcd(int place, const Program& p) { return place == kPlaceProgram && p.xcd != 0; }  // the TileIter mode of a launch
+inline int grid_of(const Program& p) {
+  int g = 0;
+  for (int i = 0; i < p.ndesc; ++i) g = std::max(g, p.d[i].wg0 + p.d[i].nwg);
+  return g;
 }
 
 }  // namespace pchain

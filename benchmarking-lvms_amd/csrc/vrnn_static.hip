@@ -39,6 +39,8 @@ struct SPtr {
 // A workgroup's tiles of one link, dealt by pchain.h's TileIter exactly as the interpreter deals them: lane k < kMaxTiles of the
 // returned value holds tile k as r0 | column tile << 16 (-1: none), so a tile costs one v_readlane in the step loop.
 constexpr int kMaxTiles = 8;
+// the workgroup of the deal this block is under the launch's placement (vrnn_static.h)
+__device__ __forceinline__ int placed_wg(int place) { return place == kPlaceLocal ? place_wg((int)blockIdx.x) : (int)blockIdx.x; }
 __device__ __forceinline__ int tile_lanes(int w, int wg0, int nwg, int rt, int ct, bool xcd) {
   TileIter it(w, wg0, nwg, rt, ct, xcd);
   const int lane = threadIdx.x & 63;
@@ -83,7 +85,7 @@ __device__ __forceinline__ void anat_end(const unsigned* tab, unsigned long long
 struct LinChainArgs {
   SPtr a16, orm, o16;
   const float *W, *bias;
-  int ldo, n16, B, s0, S, wg0, nwg, ct, xcd;
+  int ldo, n16, B, s0, S, wg0, nwg, ct, xcd, place;  // place: vrnn_static.h Place
   Ctl ctl;
   int pace_early, pace_epi;  // the run-time pacing policy's delays (PaceRt; the probe's sweep)
   ANAT(unsigned long long* prof;)
@@ -101,8 +103,8 @@ template <int NW, int K, bool RES, class PC = PaceOff>
 __global__ __launch_bounds__(NW * 64, 1) void static_lin_chain_kernel(LinChainArgs a) {
   __shared__ __attribute__((aligned(16))) float red[2][NW * 256];
   ANAT(__shared__ unsigned anat[kAnatSlots * 8]; anat_begin(anat);)
-  const int w = blockIdx.x, B = a.B;
-  const int tiles = tile_lanes(w, a.wg0, a.nwg, (B + 15) / 16, a.ct, a.xcd != 0);
+  const int w = placed_wg(a.place), B = a.B;
+  const int tiles = tile_lanes(w, a.wg0, a.nwg, (B + 15) / 16, a.ct, a.place == kPlaceProgram && a.xcd != 0);
   const int nt = tile_count(tiles);
   if (nt == 0) return;
   Poll pl{a.ctl, 0u, false, 1};
@@ -390,7 +392,7 @@ struct FwdArgs {
   SeqArgs phi;
   GruArgs gru;
   Deal deal[6];
-  int B, s0, S, xcd;
+  int B, s0, S, xcd, place;  // place: vrnn_static.h Place
   Ctl ctl;
   ANAT(unsigned long long* prof;)
 };
@@ -426,8 +428,8 @@ __device__ __forceinline__ void fwd_half(const FwdArgs& a, int w, int rt, bool x
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_fwd_kernel(FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds_red[];
-  const int w = blockIdx.x, rt = (a.B + 15) / 16;
-  const bool xcd = a.xcd != 0;
+  const int w = placed_wg(a.place), rt = (a.B + 15) / 16;
+  const bool xcd = a.place == kPlaceProgram && a.xcd != 0;
   Walk wk{lds_red, lds_red + kFwdProducts * NW * 256, 0, a.B, Poll{a.ctl, 0u, false, 1}};
   ANAT(__shared__ unsigned anat[kAnatSlots * 8]; anat_begin(anat); wk.anat = anat;)
   // roles, picked once: the gentle range runs the hidden projection alone, the others are a half's workgroups (fwd_half)
@@ -451,7 +453,7 @@ struct BwdArgs {
   DzArgs dz;
   SeqArgs run[2];
   Deal deal[10];
-  int B, s0, S, xcd;
+  int B, s0, S, xcd, place;  // place: vrnn_static.h Place
   Ctl ctl;
   ANAT(unsigned long long* prof;)
 };
@@ -493,8 +495,8 @@ __device__ __forceinline__ void bwd_half(const BwdArgs& a, int w, int rt, bool x
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds_red[];
-  const int w = blockIdx.x, rt = (a.B + 15) / 16;
-  const bool xcd = a.xcd != 0;
+  const int w = placed_wg(a.place), rt = (a.B + 15) / 16;
+  const bool xcd = a.place == kPlaceProgram && a.xcd != 0;
   Walk wk{lds_red, lds_red + kBwdProducts * NW * 256, 0, a.B, Poll{a.ctl, 0u, false, 1}};
   ANAT(__shared__ unsigned anat[kAnatSlots * 8]; anat_begin(anat); wk.anat = anat;)
   if (w >= a.deal[3].wg0) {  // spare range: the third partial sum alone
@@ -516,6 +518,12 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) 
   if (w < a.deal[2].wg0) bwd_half<NW, 0>(a, w, rt, xcd, wk);
   else bwd_half<NW, 1>(a, w, rt, xcd, wk);
 }
+
+// the placement the static launches ask for (vrnn_static.h Place): bits 32 (plain) and 64 (local) of pchain_tune; neither: the
+// program's TileIter mode.  Where the local placement does not apply the launch falls back to the plain one if bit 32 is set too,
+// else to the program's mode: plain alone measured slower than that at B = 32 and 64.
+int static_place_fallback() { return (pchain_tune() & 32) ? kPlacePlain : kPlaceProgram; }
+int static_place_wanted() { return (pchain_tune() & 64) ? kPlaceLocal : static_place_fallback(); }
 
 // the program's pointer k of descriptor d as a stepped pointer
 bool int_strides(const Program& p) {  // SPtr keeps 32-bit strides
@@ -555,11 +563,17 @@ int static_lin_chain_launch(const Program& p, hipStream_t stream, bool resident,
   if (d.ld[LIN_LD_A] != 0 || d.i[LIN_I_W_WIDTH] != 0 || d.p[LIN_ADD] || d.p[LIN_GATE] || d.p[LIN_O16B] || d.p[LIN_A2] || d.p[LIN_A3] || d.n16[N16_OUTB] != 0)
     return 1;
   const int rt = (p.B + 15) / 16;
-  if (d.nwg <= 0 || (p.xcd && d.nwg % 8 != 0) || tiles_per_workgroup(rt, d.ct, d.nwg, p.xcd != 0) > (resident ? 1 : kMaxTiles)) return 1;
+  // placement (vrnn_static.h): the chain's one range [0, 64) or [0, 128) on four row tiles is one place_wg keeps — row tile r on
+  // XCD r (64 tiles; the blocks of XCDs 4 .. 7 get none) or on XCDs r and r + 4 (128 tiles, as plain).  The resident form only: the
+  // fetch form reads its weights through L2 every link, which is what the program's mode places for.
+  int place = resident ? static_place_wanted() : kPlaceProgram;
+  if (place == kPlaceLocal && !(rt == 4 && d.wg0 == 0 && (d.nwg == 64 || d.nwg == kPlaceSpan) && device_cus() >= kPlaceSpan)) place = static_place_fallback();
+  const bool xcd = place == kPlaceProgram && p.xcd != 0;
+  if (d.nwg <= 0 || (p.xcd && d.nwg % 8 != 0) || tiles_per_workgroup(rt, d.ct, d.nwg, xcd) > (resident ? 1 : kMaxTiles)) return 1;
   LinChainArgs a{sptr(p, d, LIN_A), sptr(p, d, LIN_ORM), sptr(p, d, LIN_O16), d.p[LIN_W], d.p[LIN_BIAS], d.ld[LD_OUT], d.n16[N16_OUT], p.B, p.s_first, p.S,
-                 d.wg0, d.nwg, d.ct, p.xcd, p.ctl, early, epi};
+                 d.wg0, d.nwg, d.ct, p.xcd, place, p.ctl, early, epi};
   ANAT(a.prof = pchain_profile_buffer();)
-  const int grid = d.wg0 + d.nwg;
+  const int grid = place == kPlaceLocal ? kPlaceSpan : d.wg0 + d.nwg;
   auto go = [&](auto kernel) -> int {
     BLVM_TRY(static_go(kernel, 2, grid, 0, "static_lin_chain"));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), 0, stream, a);
@@ -580,9 +594,9 @@ bool pchain_static_on() { return g_static != 0; }
 SPtr sp(const Program& p, const Desc& d, int k) { return SPtr{const_cast<float*>(d.p[k]), d.p[k] ? (int)p.stride[d.sidx[k]] : 0}; }
 Deal deal_of(const Desc& d, int idx) { return Deal{d.wg0, d.nwg, d.ct, d.s_begin, d.s_end, idx}; }
 bool within(const Desc& d, int lo, int hi) { return d.wg0 >= lo && d.wg0 + d.nwg <= hi; }
-bool few_tiles(const Program& p, const Desc& d) {  // at most kMaxTiles tiles of the link per workgroup (pchain_run's count)
+bool few_tiles(const Program& p, const Desc& d, bool xcd) {  // at most kMaxTiles tiles of the link per workgroup in the launch's TileIter mode
   if (d.nwg <= 0 || (p.xcd && d.nwg % 8 != 0)) return false;
-  return tiles_per_workgroup((p.B + 15) / 16, d.ct, d.nwg, p.xcd != 0) <= kMaxTiles;
+  return tiles_per_workgroup((p.B + 15) / 16, d.ct, d.nwg, xcd) <= kMaxTiles;
 }
 bool shaped(const Desc& d, int kind, int flags, int K) { return d.kind == kind && d.flags == flags && d.K == K; }
 bool run(const Desc& d, int n, int K0) { return d.i[LINSEQ_I_N] == n && d.i[LINSEQ_I_K0] == K0; }  // a K_LINSEQ of n links, first link's K0
@@ -603,17 +617,20 @@ SeqArgs seq_args(const Program& p, const Desc& d) {
   return q;
 }
 
-// 1: not the shape the static kernels were compiled for (vrnn_launch runs the interpreter)
-int vrnn_static_check(const Program& p, int ndesc, int products) {
+// 1: not the shape the static kernels were compiled for (vrnn_launch runs the interpreter).  *place: the launch's placement
+// (prior, post: the descriptors of the two halves' runs); every count of tiles is taken in the TileIter mode that placement deals with
+int vrnn_static_check(const Program& p, int ndesc, int products, int prior, int post, int* place) {
   if (!pchain_static_on() || p.ndesc != ndesc || p.ot != OP_F32 || p.rt_group != 1 || p.s_first != 0 || p.B > 64) return 1;
   if (p.lds_products != products || !int_strides(p)) return 1;  // (the kernels' reduction scratch is sized for `products`)
+  *place = place_for(static_place_wanted(), static_place_fallback(), p, prior, post, grid_of(p));
   for (int i = 0; i < p.ndesc; ++i)
-    if (!few_tiles(p, p.d[i])) return 1;
+    if (!few_tiles(p, p.d[i], place_xcd(*place, p))) return 1;
   return 0;
 }
 
 int vrnn_static_fwd(const Program& p, hipStream_t stream) {
-  if (vrnn_static_check(p, 6, kFwdProducts)) return 1;
+  int place = kPlaceProgram;
+  if (vrnn_static_check(p, 6, kFwdProducts, 1, 2, &place)) return 1;
   const Desc* d = p.d;
   const int S = p.S;
   for (int i = 0; i < 6; ++i)
@@ -622,7 +639,7 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
       !shaped(d[3], K_HEAD, 0, kH) || !shaped(d[4], K_LINSEQ, DF_RELU, kH) || !shaped(d[5], K_GRU, 0, kH))
     return 1;
   if (!run(d[1], 3, kR) || !run(d[2], 3, kR) || !run(d[4], 4, 0)) return 1;
-  if (!one_tile_each(p, kFwdResident)) return 1;
+  if (!one_tile_each(p, kFwdResident, place_xcd(place, p))) return 1;
   // roles: prior half [0, d1 end) | posterior half [d2.wg0, d0.wg0) | gentle range [d0.wg0, ...): nothing else there
   const int half = d[2].wg0, gentle = d[0].wg0;
   if (d[1].wg0 != 0 || !within(d[1], 0, half) || !within(d[2], half, gentle) || d[0].nwg <= 0) return 1;
@@ -641,7 +658,7 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
                   g.n16[N16_OUTB], g.i[GRU_I_R]};
   int grid = 0;
   for (int i = 0; i < 6; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
-  a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.ctl = p.ctl;
+  a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.place = place; a.ctl = p.ctl;
   ANAT(a.prof = pchain_profile_buffer();)
   const size_t lds = sizeof(float) * 2 * kFwdProducts * 16 * 256;
   BLVM_TRY(static_go(&vrnn_static_fwd_kernel<16>, 0, grid, lds, "vrnn_static_fwd"));
@@ -652,7 +669,8 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
 }
 
 int vrnn_static_bwd(const Program& p, hipStream_t stream) {
-  if (vrnn_static_check(p, 10, kBwdProducts)) return 1;
+  int place = kPlaceProgram;
+  if (vrnn_static_check(p, 10, kBwdProducts, 8, 9, &place)) return 1;
   const Desc* d = p.d;
   const int S = p.S;  // T' + 1
   for (int i = 0; i < 10; ++i)
@@ -663,7 +681,7 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream) {
       !shaped(d[9], K_LINSEQ, DF_SEQ_GATE, kH))
     return 1;
   if (!run(d[6], 2, 0) || !run(d[8], 3, 2 * kH) || !run(d[9], 3, 2 * kH)) return 1;
-  if (!one_tile_each(p, kBwdResident) || d[7].p[DZ_D2_16] != nullptr) return 1;  // (dz holds the fragments of its one product)
+  if (!one_tile_each(p, kBwdResident, place_xcd(place, p)) || d[7].p[DZ_D2_16] != nullptr) return 1;  // (dz holds the fragments of its one product)
   // roles: prior half [0, d2.wg0) | posterior half [d2.wg0, d4.wg0) | gentle range (GB) [d4.wg0, d3.wg0) | spare range [d3.wg0, ...)
   const int half = d[2].wg0, gentle = d[4].wg0, spare = d[3].wg0;
   if (!within(d[1], 0, half) || !within(d[8], 0, half) || !within(d[2], half, gentle) || !within(d[9], half, gentle) || !within(d[4], gentle, spare) ||
@@ -688,7 +706,7 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream) {
                 z.f[DZ_F_BETA], z.f[DZ_F_SD_EPS]};
   int grid = 0;
   for (int i = 0; i < 10; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
-  a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.ctl = p.ctl;
+  a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.place = place; a.ctl = p.ctl;
   ANAT(a.prof = pchain_profile_buffer();)
   const size_t lds = sizeof(float) * 2 * kBwdProducts * 16 * 256;
   BLVM_TRY(static_go(&vrnn_static_bwd_kernel<16>, 1, grid, lds, "vrnn_static_bwd"));

@@ -72,9 +72,12 @@ int blvm_get_operand_dtype(void);
  * [0..31] workgroup 0 (critical path), [32..55] the first workgroup of the deferred range ([64..127]: the same for backward
  * programs; pass 128 words).  NULL uninstalls. */
 int blvm_pchain_profile(unsigned long long* device_buffer);
-/* Diagnostics: placement bits of the persistent programs (results unchanged; default 20): 4 XCD-aware column-tile placement (a
+/* Diagnostics: placement bits of the persistent programs (results unchanged; default 84 = 4 | 16 | 64): 4 XCD-aware column-tile placement (a
  * column tile's row tiles on one XCD, so every XCD's L2 holds 1/8 of each weight matrix), 16 one-word canary poll in front of the
- * operand polls of tiles off the critical path. */
+ * operand polls of tiles off the critical path.  Bits 32 and 64 place the static-walk launches only (the interpreter runs a program as
+ * built): 32 deals their tiles without the column-tile placement of bit 4 (with four row tiles, row tile r on XCDs r and r + 4), 64
+ * permutes the block index as well, so that the prior half of row tile r sits on XCD r and the posterior half on XCD r + 4; where
+ * the deal is not the one the permutation was made for (it needs four row tiles on 256 CUs) a launch is placed as bit 32 says. */
 int blvm_pchain_tune(int bits);
 /* The VRNN forward / backward programs at B <= 64 (16-row tiles, fp32, H = Z = 256, R = 512) run on static-walk kernels whose walk is
  * fixed at compile time (mode 1, the default; bit-identical results); mode 0 sends them to the program interpreter, a negative

@@ -9,7 +9,11 @@ of three launches), the spread of the fetch form over the rounds and the median 
 --paced E:P[,E:P...]: also run the resident form under each poll pacing setting (csrc/pchain.h "poll pacing"; first-poll delay of E
 s_sleep units on the waves that leave a tile at its barrier and P on the epilogue waves, blvm_pchain_static_chain_probe_paced),
 alternated with the others in every round, checked bit for bit, and print per shape each setting's median, spread and gain over the
-plain resident form."""
+plain resident form.
+
+--places P[,P...]: run the resident and paced forms under each placement of the static launch (csrc/vrnn_static.h Place: 0 the
+program's TileIter mode, 1 plain TileIter, 2 plain behind the block-index permutation; bits 32 / 64 of blvm_pchain_tune), alternated
+in every round."""
 import argparse, os, statistics, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "benchmarking-lvms_amd"))
@@ -49,32 +53,51 @@ if __name__ == "__main__":
     ap.add_argument("--links", type=int, default=2000)
     ap.add_argument("--bare", default=None, help="the built tools/pchain_probe binary")
     ap.add_argument("--paced", default="", help="pacing settings EARLY:EPI, comma separated")
+    ap.add_argument("--places", default="", help="placements of the static launch (0, 1, 2), comma separated; empty: the tune bits as they are")
+    ap.add_argument("--shapes", default="64:256,8:256,64:512,8:512", help="B:N, comma separated")
     args = ap.parse_args()
     L = args.links
     settings = [tuple(int(v) for v in item.split(":")) for item in args.paced.split(",") if item]
-    for B, N in ((64, 256), (8, 256), (64, 512), (8, 512)):
-        fetch, res, pc = [], [], {st: [] for st in settings}
+    places = [int(v) for v in args.places.split(",") if v] or [None]
+    base = int(os.environ.get("BLVM_PCHAIN_TUNE", "84")) & ~96  # the program's own bits; 32 / 64 select the placement
+    tag = lambda pl: "" if pl is None else f" place={pl}"
+    for B, N in (tuple(int(v) for v in item.split(":")) for item in args.shapes.split(",")):
+        fetch, res, pc = [], {pl: [] for pl in places}, {(pl, st): [] for pl in places for st in settings}
         for rep in range(args.repeats):  # alternate
             te, xe = chain(lib.blvm_pchain_chain_probe, B, N, L)
             tf, xf = chain(lib.blvm_pchain_static_chain_probe_fetch, B, N, L)
-            tr, xr = chain(lib.blvm_pchain_static_chain_probe, B, N, L)
-            same = bool(torch.equal(xe, xf)) and bool(torch.equal(xf, xr))
-            print(f"B={B} N=K={N} L={L}: engine {te:.3f} us/link, static fetch {tf:.3f}, static resident {tr:.3f}, outputs bit-identical: {same}", flush=True)
+            same = bool(torch.equal(xe, xf))
+            print(f"B={B} N=K={N} L={L}: engine {te:.3f} us/link, static fetch {tf:.3f}, outputs bit-identical: {same}", flush=True)
             if not same:
                 sys.exit(1)
-            fetch.append(tf); res.append(tr)
-            for st in settings:
-                tp, xp = chain(paced(*st), B, N, L)
-                ok = bool(torch.equal(xp, xr))
-                print(f"   paced early={st[0]} epi={st[1]}: {tp:.3f} us/link, bit-identical: {ok}", flush=True)
-                if not ok:
+            fetch.append(tf)
+            for pl in places:
+                if pl is not None:
+                    lib.blvm_pchain_tune(base | (0, 32, 96)[pl])
+                tr, xr = chain(lib.blvm_pchain_static_chain_probe, B, N, L)
+                same = bool(torch.equal(xe, xr))
+                print(f"  {tag(pl)} static resident {tr:.3f} us/link, bit-identical to the engine: {same}", flush=True)
+                if not same:
                     sys.exit(1)
-                pc[st].append(tp)
-        print(f"B={B} N=K={N}: fetch median {statistics.median(fetch):.3f} spread {max(fetch) - min(fetch):.3f}, resident median "
-              f"{statistics.median(res):.3f} spread {max(res) - min(res):.3f}, gain {statistics.median(fetch) - statistics.median(res):.3f} us/link", flush=True)
-        for st in settings:
-            print(f"B={B} N=K={N}: paced early={st[0]} epi={st[1]} median {statistics.median(pc[st]):.3f} spread {max(pc[st]) - min(pc[st]):.3f}, "
-                  f"gain over resident {statistics.median(res) - statistics.median(pc[st]):+.3f} us/link", flush=True)
+                res[pl].append(tr)
+                for st in settings:
+                    tp, xp = chain(paced(*st), B, N, L)
+                    ok = bool(torch.equal(xp, xe))
+                    print(f"  {tag(pl)} paced early={st[0]} epi={st[1]}: {tp:.3f} us/link, bit-identical to the engine: {ok}", flush=True)
+                    if not ok:
+                        sys.exit(1)
+                    pc[pl, st].append(tp)
+                if pl is not None:
+                    lib.blvm_pchain_tune(-1)  # (the engine and the fetch form run with the bits of the environment)
+        med = statistics.median
+        print(f"B={B} N=K={N}: fetch median {med(fetch):.3f} spread {max(fetch) - min(fetch):.3f}", flush=True)
+        for pl in places:
+            print(f"B={B} N=K={N}{tag(pl)}: resident median {med(res[pl]):.3f} spread {max(res[pl]) - min(res[pl]):.3f}, "
+                  f"gain over fetch {med(fetch) - med(res[pl]):.3f} us/link", flush=True)
+            for st in settings:
+                v = pc[pl, st]
+                print(f"B={B} N=K={N}{tag(pl)}: paced early={st[0]} epi={st[1]} median {med(v):.3f} spread {max(v) - min(v):.3f}, "
+                      f"gain over resident {med(res[pl]) - med(v):+.3f} us/link", flush=True)
     if args.bare:
         print(f"bare tile loop ({args.bare} {L} 1):", flush=True)
         out = subprocess.run([args.bare, str(L), "1"], capture_output=True, text=True, timeout=300)
