@@ -1,9 +1,13 @@
-"""The two transforms on the hot path (reference: blvm/data/transforms.py:90-98 StackTensor, :192-215 µ-law)."""
+"""The transforms on the hot path (reference: blvm/data/transforms.py:90-98 StackTensor, :192-215 µ-law) and the probe's log-mel
+front end (:113-166), which runs on the device."""
 import math
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
+from blvm import ops
+from blvm._hip import BlvmHipError, ptr
 from blvm.utils.operations import stack_tensor
 
 
@@ -81,6 +85,37 @@ class RandomSegment(Transform):
     def forward(self, x):
         start = int(torch.randint(low=0, high=max(x.size(0) - self.length, 1), size=(1,)))
         return x[start : start + self.length]
+
+
+class LogMelSpectrogram(Transform):
+    """Log-mel spectrogram in dB, normalised per utterance and mel bin (transforms.py:113-166), computed on the device by the fused
+    front end (`ops.log_mel_spectrogram`): one call per BATCH of waveforms, where the reference runs torchaudio per example in the
+    loader's workers.  `forward(waveform)` takes [time] or [B, time] of full-length rows and returns [..., n_mels, T];
+    `forward(waveform, lengths)` takes a right-padded batch with its lengths and returns (features [B, n_mels, T_max], feature
+    lengths [B] int32 on the device), T = 1 + time // hop_length.  A CPU tensor raises BlvmHipError."""
+
+    def __init__(self, sample_rate: int = 16000, n_fft: int = 400, win_length: Optional[int] = None, hop_length: Optional[int] = None,
+                 n_mels: int = 80, normalize_frq_bins: bool = True):  # fmt: skip
+        super().__init__()
+        self.sample_rate = sample_rate
+        self.n_fft = n_fft
+        self.win_length = win_length if win_length is not None else n_fft
+        self.hop_length = hop_length if hop_length is not None else self.win_length // 2
+        self.n_mels = n_mels
+        self.normalize_frq_bins = normalize_frq_bins
+        ops.logmel_check_geometry(self.n_fft, self.win_length, self.hop_length, self.n_mels)
+
+    def forward(self, waveform: torch.Tensor, lengths=None):
+        ptr(waveform)
+        if waveform.dim() not in (1, 2):
+            raise BlvmHipError(f"LogMelSpectrogram: waveform must be [time] or [B, time], got {tuple(waveform.shape)}")
+        batch = waveform.reshape(-1, waveform.size(-1))
+        features, feature_lens = ops.log_mel_spectrogram(
+            batch, lengths if lengths is not None else [batch.size(1)] * batch.size(0), self.sample_rate, self.n_fft, self.win_length,
+            self.hop_length, self.n_mels, self.normalize_frq_bins)  # fmt: skip
+        if lengths is not None:
+            return features, feature_lens
+        return features[0] if waveform.dim() == 1 else features
 
 
 class Normalize(Transform):

@@ -1858,3 +1858,115 @@ def ctc_greedy(logits, input_lens, blank: int = 0):
     check(load().blvm_ctc_greedy(ptr(logits), ptr(il), T, B, C, int(blank), ptr(hyp), ptr(hyp_lens), stream_ptr()), "blvm_ctc_greedy")
     hyp, hyp_lens = hyp.cpu().tolist(), hyp_lens.cpu().tolist()
     return [row[:n] for row, n in zip(hyp, hyp_lens)]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# K10: log-mel spectrogram front end
+# ----------------------------------------------------------------------------------------------------------------------
+
+
+def logmel_check_geometry(n_fft: int, win_length: int, hop_length: int, n_mels: int):
+    """The range blvm_logmel takes (the library checks it again): raises BlvmHipError with the offending value."""
+    if not (n_fft % 2 == 0 and 2 <= n_fft <= 1024):
+        raise _hip.BlvmHipError(f"log_mel_spectrogram: n_fft = {n_fft}: need an even n_fft of at most 1024")
+    if not 16 <= win_length <= n_fft:
+        raise _hip.BlvmHipError(f"log_mel_spectrogram: win_length = {win_length}: need 16 <= win_length <= n_fft = {n_fft}")
+    if hop_length < 1:
+        raise _hip.BlvmHipError(f"log_mel_spectrogram: hop_length = {hop_length}: need hop_length >= 1")
+    if not 1 <= n_mels <= 128:
+        raise _hip.BlvmHipError(f"log_mel_spectrogram: n_mels = {n_mels}: need 1 <= n_mels <= 128")
+
+
+def logmel_check_lengths(lengths, n_fft: int, Lmax: int):
+    """Host lengths of the rows of a [B,Lmax] batch: every row needs more than n_fft // 2 samples (one reflection about its own
+    ends must reach every tap of its first and last frame, as in torch.stft) and no more than the batch holds."""
+    for b, v in enumerate(lengths):
+        if not n_fft // 2 < int(v) <= Lmax:
+            raise _hip.BlvmHipError(f"log_mel_spectrogram: row {b} has {int(v)} samples: every row needs more than n_fft // 2 = "
+                                    f"{n_fft // 2} (reflect padding) and at most Lmax = {Lmax}")
+
+
+def logmel_frames(length: int, hop_length: int) -> int:
+    """Frames of an utterance of `length` samples: centred frames, one per hop, the last one centred at or before the end."""
+    return 1 + int(length) // int(hop_length)
+
+
+def logmel_basis(n_fft: int, win_length: int) -> torch.Tensor:
+    """float64 [win_length, 2, n_fft // 2 + 1]: the windowed DFT of the win_length non-zero taps of a frame.  [n, 0, k] =
+    w[n] cos(2 pi k (left + n) / n_fft), [n, 1, k] = w[n] sin(same), w the periodic Hann window of win_length and left =
+    (n_fft - win_length) // 2 the zero taps in front of it.  The phase is reduced in integers before it is scaled."""
+    n = torch.arange(win_length, dtype=torch.int64)
+    k = torch.arange(n_fft // 2 + 1, dtype=torch.int64)
+    left = (n_fft - win_length) // 2
+    w = 0.5 - 0.5 * torch.cos(2.0 * torch.pi * n.double() / win_length)
+    phase = ((left + n)[:, None] * k[None, :] % n_fft).double() * (2.0 * torch.pi / n_fft)
+    return torch.stack([w[:, None] * torch.cos(phase), w[:, None] * torch.sin(phase)], dim=1)
+
+
+def logmel_filterbank(sample_rate: int, n_fft: int, n_mels: int) -> torch.Tensor:
+    """float64 [n_fft // 2 + 1, n_mels]: triangular filters on the HTK mel scale from 0 to sample_rate / 2, not normalised
+    (torchaudio's `melscale_fbanks(norm=None, mel_scale="htk")`)."""
+    all_freqs = torch.linspace(0, sample_rate // 2, n_fft // 2 + 1, dtype=torch.float64)
+    m_max = 2595.0 * torch.log10(torch.tensor(1.0 + (sample_rate / 2) / 700.0, dtype=torch.float64))
+    m_pts = torch.linspace(0.0, float(m_max), n_mels + 2, dtype=torch.float64)
+    f_pts = 700.0 * (10.0 ** (m_pts / 2595.0) - 1.0)
+    f_diff = f_pts[1:] - f_pts[:-1]
+    slopes = f_pts[None, :] - all_freqs[:, None]
+    down, up = -slopes[:, :-2] / f_diff[:-1], slopes[:, 2:] / f_diff[1:]
+    return torch.clamp_min(torch.minimum(down, up), 0.0)
+
+
+_logmel_operands_cache = {}
+
+
+def _round_up(v: int, m: int) -> int:
+    return (v + m - 1) // m * m
+
+
+def _logmel_operands(device, sample_rate: int, n_fft: int, win_length: int, n_mels: int):
+    """(basis [WP,2,NBP], fbank [NBP,NMP]) in fp32 on `device`, zero-padded as blvm_logmel reads them; built once per geometry."""
+    key = (str(device), sample_rate, n_fft, win_length, n_mels)
+    hit = _logmel_operands_cache.get(key)
+    if hit is None:
+        n_bins = n_fft // 2 + 1
+        WP, NBP, NMP = _round_up(win_length, 8), _round_up(n_bins, 32), _round_up(n_mels, 32)
+        basis = torch.zeros(WP, 2, NBP, dtype=torch.float32)
+        basis[:win_length, :, :n_bins] = logmel_basis(n_fft, win_length).to(torch.float32)
+        fbank = torch.zeros(NBP, NMP, dtype=torch.float32)
+        fbank[:n_bins, :n_mels] = logmel_filterbank(sample_rate, n_fft, n_mels).to(torch.float32)
+        hit = _logmel_operands_cache[key] = (basis.to(device), fbank.to(device))
+    return hit
+
+
+def log_mel_spectrogram(wave, lens, sample_rate: int, n_fft: int, win_length: int, hop_length: int, n_mels: int, normalize: bool = True):
+    """(features [B,n_mels,T_max], feature_lens [B] int32 on the device) of a batch of right-padded waveforms [B,Lmax]: power
+    spectrogram of centred, reflect-padded frames (periodic Hann of win_length) -> HTK mel filters -> 10 log10(max(., 1e-10)) and,
+    with `normalize`, per utterance and mel bin (x - mean) / (std + 1e-10) over the utterance's own T_b = 1 + L_b // hop_length
+    frames (unbiased std: an utterance of a single frame normalises to NaN, as torch.std gives).  Columns behind T_b are 0.
+    `lens` are host integers (checked here: every row needs more than n_fft // 2 samples, as torch.stft's reflect padding does) or
+    an int32 device tensor (not read back: a row with a length outside (n_fft // 2, Lmax] comes out NaN with feature length 0)."""
+    ptr(wave)  # refuses a CPU tensor before anything else is touched
+    if wave.dim() != 2:
+        raise _hip.BlvmHipError(f"log_mel_spectrogram: wave must be [B,Lmax], got {tuple(wave.shape)}")
+    n_fft, win_length, hop_length, n_mels = int(n_fft), int(win_length), int(hop_length), int(n_mels)
+    logmel_check_geometry(n_fft, win_length, hop_length, n_mels)
+    B, Lmax = wave.shape
+    dev = wave.device
+    if torch.is_tensor(lens) and lens.is_cuda and lens.dtype == torch.int32:
+        lens_dev = lens.contiguous()
+    else:
+        host = torch.as_tensor(lens).reshape(-1).to(torch.int64)
+        logmel_check_lengths(host.tolist(), n_fft, Lmax)
+        lens_dev = upload_i32(host, dev)
+    if lens_dev.shape != (B,):
+        raise _hip.BlvmHipError(f"log_mel_spectrogram: lens must hold one length per row, [{B}], got {tuple(lens_dev.shape)}")
+    wave = _f32c(wave.detach())
+    basis, fbank = _logmel_operands(dev, int(sample_rate), n_fft, win_length, n_mels)
+    out = torch.empty(B, n_mels, logmel_frames(Lmax, hop_length), device=dev, dtype=torch.float32)
+    out_lens = torch.empty(B, device=dev, dtype=torch.int32)
+    check(
+        load().blvm_logmel(ptr(wave), ptr(lens_dev), B, Lmax, n_fft, win_length, hop_length, n_mels, ptr(basis), ptr(fbank),
+                           int(bool(normalize)), ptr(out), ptr(out_lens), stream_ptr()),
+        "blvm_logmel",
+    )  # fmt: skip
+    return out, out_lens

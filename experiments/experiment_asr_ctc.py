@@ -4,9 +4,12 @@ point with the reference's model flags and defaults (experiments/experiment_asr_
 
   --dataset synthetic            random features with feasible random label sequences (no files needed: the smoke path)
   --dataset train.csv            a source CSV (`filename,length...`); per example `<filename>.<data_type>` holds a [T,D] array
-      --data_type EXT            (.npy; the dumps of dump_representations.py are `<tag>-z0-n1.npy`) or, with `--data_type waveform`,
-      --text_ext EXT             `<filename>.<audio_ext>` is cut into frames of --hop_length samples; `<filename>.<text_ext>` holds the
-      --tokens FILE              space-separated labels, and FILE lists the tokens, one per line (the project ships no phoneme list)
+      --data_type EXT            (.npy; the dumps of dump_representations.py are `<tag>-z0-n1.npy`); with `--data_type waveform`
+      --text_ext EXT             `<filename>.<audio_ext>` is cut into frames of --hop_length samples; with `--data_type spectrogram`
+      --tokens FILE              (the default: the baseline every representation is compared against) each batch of waveforms becomes
+                                 log-mel features on the device (--n_fft, --win_length, --hop_length, --n_mels).
+                                 `<filename>.<text_ext>` holds the space-separated labels, and FILE lists the tokens, one per line
+                                 (the project ships no phoneme list)
 """
 import sys
 import time
@@ -30,7 +33,10 @@ g.add_argument("--text_type", default="phon", choices=["word", "char", "phon"], 
 g.add_argument("--text_ext", default="PHN", type=str, help="extension of the per-example label files")
 g.add_argument("--tokens", default=None, type=str, help="file with one token per line (the blank is added)")
 g.add_argument("--sample_rate", default=16000, type=int)
-g.add_argument("--hop_length", default=64, type=int, help="frame size in samples of --data_type waveform")
+g.add_argument("--n_fft", default=512, type=int, help="FFT size of --data_type spectrogram")
+g.add_argument("--win_length", default=128, type=int, help="window size in samples of --data_type spectrogram")
+g.add_argument("--hop_length", default=64, type=int, help="frame size in samples of --data_type waveform, hop of --data_type spectrogram")
+g.add_argument("--n_mels", default=80, type=int, help="mel bins of --data_type spectrogram")
 g.add_argument("--hidden_size", default=128, type=int, help="size of the LSTM layers")
 g.add_argument("--num_layers", default=1, type=int, help="number of LSTM layers")
 g.add_argument("--bidirectional", default=False, type=str2bool, help="bidirectional LSTM layers")
@@ -80,10 +86,9 @@ def real_loaders(args, token_map):
     from blvm.data.transforms import Compose, EncodeInteger, StackTensor
     from blvm.modules.convenience import Permute
 
-    if args.data_type == "spectrogram":
-        raise SystemExit("--data_type spectrogram: log-mel spectrograms need torchaudio, which this build does not use; compute them "
-                         "offline into per-example [T,n_mels] .npy files and pass their extension as --data_type, or use --data_type waveform")
-    if args.data_type == "waveform":
+    if args.data_type == "spectrogram":  # padded waveforms [B,Lmax]: main() turns each batch into log-mel features on the device
+        features = (AudioLoader(args.audio_ext), None, DynamicTensorBatcher())
+    elif args.data_type == "waveform":
         features = (AudioLoader(args.audio_ext), Compose(StackTensor(args.hop_length), Permute(1, 0)), DynamicTensorBatcher())
     else:
         features = (NumpyLoader(args.data_type, dtype=torch.float32), Permute(1, 0), DynamicTensorBatcher())  # [T,D] -> [D,T]
@@ -108,6 +113,7 @@ def main():
     if args.use_amp:
         raise SystemExit("--use_amp True: the CTC probe runs in fp32 (the 16-bit operand modes do not cover it)")
     _, _, dev = setup(args)
+    front_end = None
     if args.dataset == "synthetic":
         token_map = TokenMap([f"t{i:02d}" for i in range(args.synthetic_tokens)], add_blank=True)
         bs = args.batch_size or 16
@@ -122,8 +128,14 @@ def main():
         with open(args.tokens) as f:
             token_map = TokenMap([line.rstrip("\n") for line in f if line.strip()], add_blank=True)
         train, test = real_loaders(args, token_map)
-        ((x, _), _), _ = next(iter(test))
-        input_size = x.size(1)
+        if args.data_type == "spectrogram":
+            from blvm.data.transforms import LogMelSpectrogram
+
+            front_end = LogMelSpectrogram(args.sample_rate, args.n_fft, args.win_length, args.hop_length, args.n_mels)
+            input_size = args.n_mels
+        else:
+            ((x, _), _), _ = next(iter(test))
+            input_size = x.size(1)
     model = SimpleLSTMASR(token_map=token_map, input_size=input_size, hidden_size=args.hidden_size, num_layers=args.num_layers,
                           bidirectional=args.bidirectional, sum_directions=args.sum_directions, dropout_prob=args.dropout_prob,
                           temporal_dropout=args.temporal_dropout).to(dev)  # fmt: skip
@@ -136,12 +148,22 @@ def main():
         for item in loader:
             yield item if args.dataset == "synthetic" else item[0]
 
+    def features_of(x, x_sl):
+        """The model's input on the device.  Spectrogram: the batch of waveforms becomes log-mel features there; their lengths
+        1 + samples // hop_length are monotone in the sample lengths, so the samplers' longest-first order survives."""
+        x = x.to(dev, non_blocking=True)
+        if front_end is None:
+            return x, x_sl
+        x, _ = front_end(x, x_sl)
+        return x, 1 + x_sl // args.hop_length
+
     tracker, best = Tracker(), None
     for epoch in tracker.epochs(args.epochs):
         model.train()
         t0, frames, skipped = time.time(), 0, 0
         for (x, x_sl), (y, y_sl) in tracker.steps(batches(train), source="train"):
-            loss, metrics, _ = model(x.to(dev, non_blocking=True), x_sl, y.to(dev, non_blocking=True), y_sl)
+            x, x_sl = features_of(x, x_sl)
+            loss, metrics, _ = model(x, x_sl, y.to(dev, non_blocking=True), y_sl)
             optimizer.zero_grad(set_to_none=True)
             loss.backward()
             # an infeasible row makes the loss +inf and its gradients NaN: that step is not taken
@@ -159,7 +181,8 @@ def main():
             out = None
             with torch.no_grad():
                 for (x, x_sl), (y, y_sl) in tracker.steps(batches(test), source="test"):
-                    _, metrics, out = model(x.to(dev, non_blocking=True), x_sl, y.to(dev, non_blocking=True), y_sl)
+                    x, x_sl = features_of(x, x_sl)
+                    _, metrics, out = model(x, x_sl, y.to(dev, non_blocking=True), y_sl)
                     tracker.update(metrics)
             vals = tracker.values("test")
             print("           test " + ", ".join(f"{k} {v:.4f}" for k, v in vals.items()), flush=True)

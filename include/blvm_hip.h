@@ -695,6 +695,27 @@ int blvm_ctc_loss(const float* logits, const int32_t* targets, const int32_t* in
 int blvm_ctc_greedy(const float* logits, const int32_t* input_lens, int T, int B, int C, int blank, int32_t* hyp,
                     int32_t* hyp_lens, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * K10 Log-mel spectrogram front end of the probe, on the device and per batch.  Replaces the loader-side
+ *     `torchaudio.transforms.MelSpectrogram` (its defaults: centred frames, reflect padding, periodic Hann, power 2, HTK mel
+ *     scale, no filter norm) + `10 log10(clamp_min(., 1e-10))` + per-bin mean / std, `blvm/data/transforms.py:113-166`.
+ *   wave [B,Lmax] right-padded; lens [B] int32 (device): L_b valid samples, n_fft / 2 < L_b <= Lmax.  Frame t of row b is centred
+ *   on sample t * hop_length; samples outside [0, L_b) are reflected about the row's OWN ends.  T_b = 1 + L_b / hop_length.
+ *   basis [WP,2,NBP]: basis[n,0,k] = w[n] cos(2 pi k (left + n) / n_fft), basis[n,1,k] = the sine, w the periodic Hann window of
+ *   win_length, left = (n_fft - win_length) / 2, k < n_bins = n_fft / 2 + 1; rows n >= win_length and columns k >= n_bins are 0.
+ *   fbank [NBP,NMP]: the mel filters, zero-padded.  WP = win_length rounded up to 8; NBP, NMP = n_bins, n_mels rounded up to 32.
+ *   out [B,n_mels,T_max], T_max = 1 + Lmax / hop_length: 10 log10(max(mel power, 1e-10)); with normalize = 1 every (b, mel) row
+ *   then has its mean over its T_b frames subtracted and is divided by (unbiased standard deviation + 1e-10): a constant row comes
+ *   out exactly 0, a row of one frame NaN (as torch.std).  Columns t >= T_b are written as 0 and out_lens[b] = T_b on every call;
+ *   nothing depends on the buffers' earlier contents.  A row whose length is outside (n_fft / 2, Lmax] is NaN throughout with
+ *   out_lens[b] = 0; such a length is never used as an index.  No atomics: bit-identical from call to call, and a row's result
+ *   does not depend on the other rows of the batch.
+ *   Limits: n_fft even, 16 <= win_length <= n_fft <= 1024, hop_length >= 1, 1 <= n_mels <= 128, Lmax > n_fft / 2,
+ *   B * T_max < 2^31, B * n_mels < 2^31.
+ * ------------------------------------------------------------------------------------------------------------- */
+int blvm_logmel(const float* wave, const int32_t* lens, int B, int Lmax, int n_fft, int win_length, int hop_length, int n_mels,
+                const float* basis, const float* fbank, int normalize, float* out, int32_t* out_lens, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
