@@ -103,6 +103,9 @@ _SIGNATURES = {
     "blvm_pchain_rows_to_t16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "blvm_gemm_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_void_p, c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "blvm_gemm_ws_route": (c_int, [c_int, c_int, c_int, c_int, c_size_t, c_int, c_int, c_int, c_int, c_int]),
+    "blvm_gemm_ws_min_rows": (c_int, [c_int]),
+    "blvm_gemm_path_counts": (c_int, [c_void_p]),
     "blvm_act_bwd_f32": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_size_t, c_void_p]),
     "blvm_colsum_f32": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "blvm_wgrad_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),

@@ -380,6 +380,13 @@ unsigned long long* pchain_profile_buffer();  // diagnostics: null unless blvm_p
 int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
              int ldc, const float* bias, int act, float slope, const float* gate, int ldg, int accumulate,
              int split_k, hipStream_t stream, float* colsum = nullptr);  // colsum (op_a == 1): [M] += sum over k of A[k][:]
+// the weight-stationary forward / data-gradient path (gemm_ws.hip): its routing predicate (host arithmetic only), the row threshold
+// in force (blvm_gemm_ws_min_rows), the launcher gemm_f32 hands such a product to, and gemm_f32's per-path launch counter
+bool gemm_ws_route(int op_a, int M, int N, int K, uintptr_t a_addr, int lda, int split_k, bool has_colsum, int operand, int min_rows);
+int gemm_ws_min_rows();
+int gemm_ws_f32(int op_b, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias,
+                int act, float slope, const float* gate, int ldg, int accumulate, hipStream_t stream);
+void gemm_count_path(int path);  // 0: the staged tiles of gemm.hip, 1: gemm_ws.hip
 int colsum_f32(int M, int N, const float* X, int ldx, float* out, int accumulate, hipStream_t stream);
 // Weight gradients of one reduction length as ONE launch: dW[M,N] += D^T[M,K] Act[K,N] and, with db, db[M] += column sums of D, for
 // every job with dW (a job without dW only sums its columns).  Jobs with 16-byte aligned operands, M, N and leading dimensions

@@ -705,6 +705,15 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
     BLVM_CHECK_LAUNCH("gemm_f32");
     return BLVM_OK;
   }
+  static const int force_tile = [] { const char* e = getenv("BLVM_GEMM_TILE"); return e ? atoi(e) : 0; }();  // experiments only
+  // forward / data-gradient forms with a short reduction and many rows: the weight-stationary path (gemm_ws.hip; the routing
+  // table is at gemm_ws_route).  BLVM_GEMM_TILE=3 keeps them on the staged tiles (A/B runs of one library).
+  if (force_tile != 3 && gemm_ws_route(op_a, M, N, K, reinterpret_cast<uintptr_t>(A), lda, split_k, colsum != nullptr, operand_type(),
+                                       gemm_ws_min_rows())) {
+    gemm_count_path(1);
+    return gemm_ws_f32(op_b, M, N, K, A, lda, B, ldb, C, ldc, bias, act, slope, gate, ldg, accumulate, stream);
+  }
+  gemm_count_path(0);
   bool big =(M >= 128 && N >= 128 && (size_t)((M + 127) / 128) * ((N + 127) / 128) * split_k >= 192);
   // 192-wide tiles for the conv coders' channel counts (192 = 1.5 x 128 would waste a quarter of a 128-tile pair and
   // re-read the other operand): N % 192 == 0 -> 128x192, else M % 192 == 0 -> 192x128
@@ -713,7 +722,6 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
   // wgrad_tile takes left above)
   // and for short reductions on narrow outputs (K <= 256 and N <= 256: 43 -> 65 TF/s at K = 96, 53 -> 61 at 256x256); the
   // 128-wide tiles win once N >= 512 or K >= 512 (84 vs 74 TF/s at N = 768, K = 192; 114 vs 95 at 4096^3).
-  static const int force_tile = [] { const char* e = getenv("BLVM_GEMM_TILE"); return e ? atoi(e) : 0; }();  // experiments only
   if ((op_a == 1 && op_b == 1) || (K <= 256 && N <= 256)) big = false;
   if (force_tile == 1) big = false;
   const bool n192 = big && N % 192 == 0 && N % 128 != 0 && force_tile != 2;

@@ -130,6 +130,22 @@ int blvm_gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int l
                   float* C, int ldc, const float* bias, int act, float slope, const float* gate, int ldg,
                   int accumulate, int split_k, void* stream);
 
+/* Which kernel family a product takes.  Forward / data-gradient forms with a short reduction and many rows run weight-stationary
+ * (csrc/gemm_ws.hip: a wave keeps a 16-column slab of B in registers and streams 16-row blocks of A through the matrix pipe, no LDS);
+ * every other product runs on the LDS-staged tiles.  The weight-stationary path is taken when ALL of these hold:
+ *   fp32 operands (BLVM_DTYPE_F32), op_a == 0, split_k == 1, no column sums riding along, K % 16 == 0 and 0 < K <= 256, N % 16 == 0,
+ *   A 16-byte aligned with lda % 4 == 0, M >= the row threshold.
+ * Both paths sum every output as one fp32 fma chain in ascending k: the same product gives the same bits on either.
+ *
+ * The routing predicate itself, pure host arithmetic (1: weight-stationary, 0: staged tiles): a_addr is A as an integer, has_colsum
+ * whether a bias gradient rides on the product, operand a BLVM_DTYPE_* value, min_rows the row threshold to apply. */
+int blvm_gemm_ws_route(int op_a, int M, int N, int K, size_t a_addr, int lda, int split_k, int has_colsum, int operand, int min_rows);
+/* Sets the row threshold of the process (rows < 0: the built-in value) and returns the one it replaces.  For tests and experiments. */
+int blvm_gemm_ws_min_rows(int rows);
+/* out[0] = products launched on the staged tiles, out[1] = on the weight-stationary path, since the library was loaded (host
+ * counters, no device needed; products that the weight-gradient ring takes are counted in neither). */
+int blvm_gemm_path_counts(unsigned long long* out);
+
 /* dz[i] = dy[i] * (y[i] > 0 ? 1 : slope) over n contiguous floats: derivative of ReLU / LeakyReLU from its OUTPUT y
  * (used where no producing GEMM exists to fuse it into, e.g. behind the DMoL head).  dz may alias dy. */
 int blvm_act_bwd_f32(const float* dy, const float* y, float slope, float* dz, size_t n, void* stream);
