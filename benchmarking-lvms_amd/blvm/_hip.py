@@ -204,6 +204,7 @@ _SIGNATURES = {
     "blvm_ctc_scratch_floats": (c_size_t, [c_int] * 4),
     "blvm_ctc_loss": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 5),
     "blvm_ctc_greedy": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 3),
+    "blvm_edit_distance": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 3 + [c_int] + [c_void_p] * 4),
     "blvm_logmel": (c_int, [c_void_p] * 2 + [c_int] * 6 + [c_void_p] * 2 + [c_int] + [c_void_p] * 3),
 }  # fmt: skip
 

@@ -18,6 +18,37 @@ def char_tokenizer(string: str) -> List[str]:
     return list(string)
 
 
+class UnitTable:
+    """token index -> list of integer units, in CSR form (the layout `ops.edit_distance` uploads): token v stands for
+    units[offsets[v]:offsets[v + 1]], possibly none; `separator` >= 0 goes between every two consecutive tokens of a sequence (not
+    before the first, not after the last), < 0: no separator."""
+
+    def __init__(self, unit_lists: Iterable[Iterable[int]], separator: int = -1):
+        self.offsets, self.units = [0], []
+        for row in unit_lists:
+            self.units.extend(int(u) for u in row)
+            self.offsets.append(len(self.units))
+        self.separator = int(separator)
+        self.max_units = max((b - a for a, b in zip(self.offsets, self.offsets[1:])), default=0)
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+
+def expand_units(indices: Iterable[int], table: UnitTable) -> List[int]:
+    """The unit sequence that `table` makes of a token index sequence: the host twin of the expansion in `ops.edit_distance`."""
+    if isinstance(indices, torch.Tensor):
+        indices = indices.tolist()
+    out = []
+    for n, v in enumerate(indices):
+        if not 0 <= v < len(table):
+            raise ValueError(f"expand_units: token index {v} is outside [0, {len(table)})")
+        if n and table.separator >= 0:
+            out.append(table.separator)
+        out.extend(table.units[table.offsets[v] : table.offsets[v + 1]])
+    return out
+
+
 class TokenMap:
     """tokens are SORTED, then `add_blank` puts the blank at index 0."""
 
@@ -56,6 +87,25 @@ class TokenMap:
         if len(indices_batch) != len(sl):
             raise ValueError("TokenMap.decode_batch: `indices_batch` is batch-first and needs one length per row")
         return [self.decode(row[:n], join_separator) for row, n in zip(indices_batch, sl)]
+
+    def unit_tables(self):
+        """(word table, character table): the two `UnitTable`s under which the edit distance between expanded INDEX sequences equals
+        the error-rate metrics' distance between tokenised STRINGS, `word_tokenizer(" ".join(tokens))` and
+        `char_tokenizer(" ".join(tokens))`.  The joining space isolates the tokens, so the words of the joined string are the
+        tokens' own `split()` words in order (none for a whitespace-only token; word ids are interned over the map, no separator),
+        and its characters are the tokens' characters with one " " between consecutive tokens (units `ord(c)`, separator
+        `ord(" ")`).  The character side needs non-empty tokens (an empty first, last or only token leaves a space in the joined
+        string where the separator rule puts none): a map with an empty token has no tables and this returns None, the caller keeps
+        to the strings.  Built once per map."""
+        if not hasattr(self, "_unit_tables"):
+            if any(t == "" for t in self.tokens):
+                self._unit_tables = None
+            else:
+                ids = {}
+                words = [[ids.setdefault(w, len(ids)) for w in t.split()] for t in self.tokens]
+                chars = [[ord(c) for c in t] for t in self.tokens]
+                self._unit_tables = (UnitTable(words), UnitTable(chars, separator=ord(" ")))
+        return self._unit_tables
 
     def __getitem__(self, index: int) -> str:
         return self.get_token(index)

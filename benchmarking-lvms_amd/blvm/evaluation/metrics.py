@@ -120,23 +120,50 @@ def edit_distance(ref, hyp) -> int:
 
 class ErrorRateMetric(Metric):
     """Edits / reference length over tokenised strings (blvm/evaluation/metrics.py:68-85): word error rate with `word_tokenizer`,
-    character error rate with `char_tokenizer`.  `update` adds both counts, so the value over an epoch is the pooled rate."""
+    character error rate with `char_tokenizer`.  `update` adds both counts, so the value over an epoch is the pooled rate.
+
+    `from_counts` takes the two counts ready-made, as deferred device scalars (`ops.ctc_error_counts`): they stay pending, through
+    `update` too, until a value is read, so a training step transfers nothing."""
 
     def __init__(self, refs, hyps, tokenizer, name="er", tags=None):
         super().__init__(name=name, tags=tags, get_best="min")
         self._edits, self._len = 0, 0
+        self._pending = []  # (edits, reference length, refused rows or None): float-convertibles not yet read
         for ref, hyp in zip(refs, hyps):
             r, h = tokenizer(ref), tokenizer(hyp)
             self._edits += edit_distance(r, h)
             self._len += len(r)
 
+    @classmethod
+    def from_counts(cls, counts, name="er", tags=None, invalid=None):
+        """counts: (edits, reference length), each int- or float-convertible (a `DeferredScalars` element, a number); invalid: the
+        number of rows the device refused (a label outside the token map), or None.  A negative count or invalid > 0 raises
+        ValueError when the metric is resolved."""
+        self = cls((), (), None, name=name, tags=tags)
+        edits, length = counts
+        self._pending.append((edits, length, invalid))
+        return self
+
+    def _resolve(self):
+        while self._pending:  # an entry that raises stays pending: the metric keeps raising
+            edits, length, invalid = self._pending[0]
+            edits, length, invalid = int(float(edits)), int(float(length)), 0 if invalid is None else int(float(invalid))
+            if edits < 0 or length < 0 or invalid > 0:
+                raise ValueError(f"ErrorRateMetric {self.name!r}: {max(invalid, 1)} row(s) of a batch held a label outside the token "
+                                 f"map or a length outside its row (edits = {edits}, reference length = {length})")
+            self._pending.pop(0)
+            self._edits += edits
+            self._len += length
+
     @property
     def value(self):
+        self._resolve()
         return self._edits / self._len if self._len else float("nan")
 
     def update(self, metric: "ErrorRateMetric"):
         self._edits += metric._edits
         self._len += metric._len
+        self._pending.extend(metric._pending)
 
 
 class LatestMeanMetric(Metric):

@@ -1843,10 +1843,9 @@ def ctc_loss(logits, targets, input_lens, target_lens, blank: int = 0):
     return _CTCFunction.apply(logits, targets.contiguous(), il, tl, int(blank))
 
 
-def ctc_greedy(logits, input_lens, blank: int = 0):
-    """Greedy CTC decode of time-major logits [T,B,C] on the device: per row the arg-max labels of its first input_lens[b] frames with
-    repeats collapsed and blanks dropped, as a list of lists of ints (`blvm.utils.decoding.greedy_ctc` is the host twin).  Only the
-    [B,T] labels and [B] lengths are copied to the host."""
+def ctc_greedy_device(logits, input_lens, blank: int = 0):
+    """Greedy CTC decode of time-major logits [T,B,C], kept on the device: (hyp [B,T] int32, hyp_lens [B] int32).  Row b holds the
+    arg-max labels of its first input_lens[b] frames with repeats collapsed and blanks dropped, hyp_lens[b] of them, -1 behind."""
     ptr(logits)
     if logits.dim() != 3:
         raise _hip.BlvmHipError(f"ctc_greedy: logits must be time-major [T,B,C], got {tuple(logits.shape)}")
@@ -1856,8 +1855,117 @@ def ctc_greedy(logits, input_lens, blank: int = 0):
     hyp = torch.empty(B, T, device=logits.device, dtype=torch.int32)
     hyp_lens = torch.empty(B, device=logits.device, dtype=torch.int32)
     check(load().blvm_ctc_greedy(ptr(logits), ptr(il), T, B, C, int(blank), ptr(hyp), ptr(hyp_lens), stream_ptr()), "blvm_ctc_greedy")
+    return hyp, hyp_lens
+
+
+def ctc_greedy(logits, input_lens, blank: int = 0):
+    """Greedy CTC decode of time-major logits [T,B,C] on the device: per row the arg-max labels of its first input_lens[b] frames with
+    repeats collapsed and blanks dropped, as a list of lists of ints (`blvm.utils.decoding.greedy_ctc` is the host twin).  Only the
+    [B,T] labels and [B] lengths are copied to the host."""
+    hyp, hyp_lens = ctc_greedy_device(logits, input_lens, blank)
     hyp, hyp_lens = hyp.cpu().tolist(), hyp_lens.cpu().tolist()
     return [row[:n] for row, n in zip(hyp, hyp_lens)]
+
+
+EDIT_MAX_REF_UNITS = 8192  # blvm_edit_distance: the expanded reference of a row (EDIT_MAX_REF, csrc/editdist.hip)
+EDIT_STRIP_UNITS = 512  # hypothesis units the kernel walks per strip (EDIT_STRIP)
+_edit_tables_cache = {}
+
+
+def _edit_tables(tables, device):
+    """(unit_offsets [n,V + 1], units, separators [n]) int32 on `device` for a tuple of `blvm.data.token_map.UnitTable`s over the same
+    V tokens, the offsets shifted into one shared `units` array; uploaded once per tuple of tables and device."""
+    key = (tuple(id(t) for t in tables), str(device))
+    hit = _edit_tables_cache.get(key)
+    if hit is None:
+        V = len(tables[0])
+        if V < 1 or any(len(t) != V for t in tables):
+            raise _hip.BlvmHipError(f"edit_distance: the tables must share one V >= 1, got {[len(t) for t in tables]}")
+        offsets, units = [], []
+        for t in tables:
+            offsets.append([len(units) + o for o in t.offsets])
+            units.extend(t.units)
+        i32 = dict(dtype=torch.int32, device=device)
+        hit = (torch.tensor(offsets, **i32), torch.tensor(units or [0], **i32), torch.tensor([t.separator for t in tables], **i32),
+               tuple(tables))  # the tables themselves: their ids stay taken while the entry lives
+        _edit_tables_cache[key] = hit
+    return hit[:3]
+
+
+def edit_distance_fits(ref_stride: int, tables=None) -> bool:
+    """Whether reference rows of `ref_stride` tokens are within blvm_edit_distance's limit under `tables` (None: compared as they
+    are): the bound of a row's expansion, every token at its table's longest and a separator after all but the last."""
+    if not tables:
+        return ref_stride <= EDIT_MAX_REF_UNITS
+    return ref_stride * (max(t.max_units for t in tables) + 1) - 1 <= EDIT_MAX_REF_UNITS
+
+
+def _edit_seq(v, device, what):
+    v = torch.as_tensor(v)
+    if v.dim() != 2:
+        raise _hip.BlvmHipError(f"edit_distance: {what} must be [B,stride], got {tuple(v.shape)}")
+    if not (v.is_cuda and v.dtype == torch.int32):
+        v = upload_i32(v, device) if not v.is_cuda else v.to(torch.int32)
+    return v.contiguous()
+
+
+def _edit_call(ref, ref_lens, hyp, hyp_lens, tables, want_totals):
+    hyp = torch.as_tensor(hyp)
+    if not hyp.is_cuda:
+        ptr(hyp)  # refuses a CPU tensor before anything else is touched: the hypotheses name the device
+    dev = hyp.device
+    hyp, ref = _edit_seq(hyp, dev, "hyp"), _edit_seq(ref, dev, "ref")
+    B = hyp.shape[0]
+    if ref.shape[0] != B:
+        raise _hip.BlvmHipError(f"edit_distance: ref has {ref.shape[0]} rows, hyp {B}")
+    rl, hl = _ctc_lens(ref_lens, B, dev, "ref_lens"), _ctc_lens(hyp_lens, B, dev, "hyp_lens")
+    n = len(tables)
+    off, units, seps = _edit_tables(tables, dev) if n else (None, None, None)
+    i32 = dict(device=dev, dtype=torch.int32)
+    edits, ref_units = torch.empty(max(n, 1), B, **i32), torch.empty(max(n, 1), B, **i32)
+    totals = torch.empty(max(n, 1), 3, **i32) if want_totals else None
+    check(
+        load().blvm_edit_distance(ptr(ref) if ref.shape[1] else None, ptr(rl), ref.shape[1], ptr(hyp) if hyp.shape[1] else None, ptr(hl),
+                                  hyp.shape[1], B, n, len(tables[0]) if n else 0, ptr(off), ptr(units), ptr(seps),
+                                  max(t.max_units for t in tables) if n else 0, ptr(edits), ptr(ref_units), ptr(totals), stream_ptr()),
+        "blvm_edit_distance",
+    )  # fmt: skip
+    return edits, ref_units, totals
+
+
+def edit_distance(ref, ref_lens, hyp, hyp_lens, table=None):
+    """Levenshtein distance (unit-cost substitutions, insertions, deletions) per row between ref[b,:ref_lens[b]] and
+    hyp[b,:hyp_lens[b]] -> (edits, ref_units) int32 device tensors.  `hyp` [B,stride] is a device tensor of integers (as
+    `ctc_greedy_device` gives it; what lies behind a row's length is never read); `ref` [B,stride] may be host or device integers,
+    the lengths host integers or int32 device tensors.  table: None compares the sequences as they are; a
+    `blvm.data.token_map.UnitTable` expands every token to its units first (`expand_units` is the host twin) and gives [B]
+    results; a list or tuple of tables over the same tokens is served by ONE launch and gives [n_tables,B].  ref_units is the
+    expanded reference's length.  A row with a token outside the table or a length outside its stride gets -1 in both."""
+    single = table is None or not isinstance(table, (list, tuple))
+    tables = () if table is None else ((table,) if single else tuple(table))
+    edits, ref_units, _ = _edit_call(ref, ref_lens, hyp, hyp_lens, tables, False)
+    return (edits[0], ref_units[0]) if single else (edits, ref_units)
+
+
+def ctc_error_totals(logits, input_lens, targets, target_lens, tables, blank: int = 0):
+    """The greedy decode of time-major logits [T,B,C] and its edit distances to the targets under each of `tables`
+    (`blvm.data.token_map.UnitTable`s, e.g. `TokenMap.unit_tables()`), with nothing copied to the host -> (totals [n_tables,3] int32,
+    hyp [B,T] int32, hyp_lens [B] int32).  totals[k] = (sum of edits, sum of reference units, number of refused rows) under table k;
+    refused rows (a label outside the table, a length outside its row) add to neither sum.  Three launches: the decode, the
+    distances of every (row, table), and the batch sums, a one-wave kernel per table that adds in a fixed order (no atomics)."""
+    hyp, hyp_lens = ctc_greedy_device(logits, input_lens, blank)
+    tables = tuple(tables)
+    if not tables:
+        raise _hip.BlvmHipError("ctc_error_counts: needs at least one unit table")
+    _, _, totals = _edit_call(targets, target_lens, hyp, hyp_lens, tables, True)
+    return totals, hyp, hyp_lens
+
+
+def ctc_error_counts(logits, input_lens, targets, target_lens, tables, blank: int = 0):
+    """`ctc_error_totals` as (counts [n_tables,2] int32: the sum of edits and of reference units over the batch's accepted rows,
+    invalid [n_tables] int32: the number of refused rows), both views of one device tensor."""
+    totals, _, _ = ctc_error_totals(logits, input_lens, targets, target_lens, tables, blank)
+    return totals[:, :2], totals[:, 2]
 
 
 # ----------------------------------------------------------------------------------------------------------------------

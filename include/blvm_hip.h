@@ -712,7 +712,30 @@ int blvm_ctc_greedy(const float* logits, const int32_t* input_lens, int T, int B
                     int32_t* hyp_lens, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
- * K10 Log-mel spectrogram front end of the probe, on the device and per batch.  Replaces the loader-side
+ * K9  Batched Levenshtein distance (unit-cost substitutions, insertions, deletions) between integer sequences, with an optional
+ *     token -> unit expansion.  Replaces the host `edit_distance` of the error-rate metrics, `blvm/evaluation/metrics.py:68-85`.
+ *   ref [B,ref_stride], hyp [B,hyp_stride] int32 with ref_len, hyp_len [B] int32 (device): only the first len entries of a row are
+ *   read, whatever lies behind them (the -1 padding of blvm_ctc_greedy included).
+ *   n_tables = 0: the sequences are compared as they are; unit_offsets, units, separators, V and max_units are ignored.
+ *   n_tables >= 1: ONE launch serves every table over the same sequences (grid B x n_tables).  unit_offsets [n_tables,V + 1] are
+ *   CSR offsets into the shared array `units`: under table k token v stands for units[unit_offsets[k][v] .. unit_offsets[k][v + 1]),
+ *   possibly none; separators[k] >= 0 is inserted between every two consecutive tokens (not before the first, not after the
+ *   last), < 0: no separator.  max_units: the longest unit list of any token (host side; it sizes the kernel's LDS).
+ *   edits, ref_units [max(n_tables,1),B]: the distance between the expanded sequences and the expanded reference's length.  A token
+ *   outside [0,V) inside a row's length (tables only) or a length outside [0,stride] makes edits = ref_units = -1 for that row and
+ *   table alone; such a value is never used as an index.  totals [max(n_tables,1),3] or NULL: per table the sum of edits and of
+ *   ref_units over the accepted rows and the number of refused rows, summed in a fixed order by a second small launch.
+ *   No atomics; every element is written on every call: bit-identical from call to call, whatever the buffers held.
+ *   Limits: an expanded reference row of at most 8192 units, judged by its bound ref_stride * (max_units + 1) - 1 (ref_stride
+ *   without tables); hyp_stride * (max_units + 1) < 2^30 (any hypothesis length: it is walked in strips of 512 units);
+ *   n_tables <= 65535.
+ * ------------------------------------------------------------------------------------------------------------- */
+int blvm_edit_distance(const int32_t* ref, const int32_t* ref_len, int ref_stride, const int32_t* hyp, const int32_t* hyp_len,
+                       int hyp_stride, int B, int n_tables, int V, const int32_t* unit_offsets, const int32_t* units,
+                       const int32_t* separators, int max_units, int32_t* edits, int32_t* ref_units, int32_t* totals, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * K10Log-mel spectrogram front end of the probe, on the device and per batch.  Replaces the loader-side
  *     `torchaudio.transforms.MelSpectrogram` (its defaults: centred frames, reflect padding, periodic Hann, power 2, HTK mel
  *     scale, no filter norm) + `10 log10(clamp_min(., 1e-10))` + per-bin mean / std, `blvm/data/transforms.py:113-166`.
  *   wave [B,Lmax] right-padded; lens [B] int32 (device): L_b valid samples, n_fft / 2 < L_b <= Lmax.  Frame t of row b is centred
