@@ -5,7 +5,9 @@ the stream as the current torch HIP stream handle.  There is NO CPU fallback: ev
 is missing or if it is handed a tensor that does not live on a HIP device.
 """
 import ctypes
+import functools
 import os
+import re
 
 import torch
 
@@ -13,202 +15,131 @@ import torch
 _LIB_PATH = os.environ.get("BLVM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libblvm_hip.so")
 _lib = None
 
-c_int, c_float, c_void_p, c_size_t, c_double = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double
-
 
 class BlvmHipError(RuntimeError):
     pass
 
 
-class VrnnWeights(ctypes.Structure):
-    """struct BlvmVrnnWeights / BlvmVrnnGrads (identical field order)."""
+# The header is the one declaration of the ABI: prototypes, structs and constants are read from it at import (pure text: no
+# library, no GPU).  Found the way the Makefile's -I finds it.
+_HEADER_PATH = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "include", "blvm_hip.h"))
 
-    _fields_ = [
-        ("prior_w", c_void_p * 3), ("prior_b", c_void_p * 3), ("prior_hw", c_void_p), ("prior_hb", c_void_p),
-        ("post_w", c_void_p * 3), ("post_b", c_void_p * 3), ("post_hw", c_void_p), ("post_hb", c_void_p),
-        ("phi_w", c_void_p * 4), ("phi_b", c_void_p * 4),
-        ("gru_wih", c_void_p), ("gru_whh", c_void_p), ("gru_bih", c_void_p), ("gru_bhh", c_void_p),
-    ]  # fmt: skip
-
-
-class VrnnDecodeWeights(ctypes.Structure):
-    """struct BlvmVrnnDecodeWeights."""
-
-    _fields_ = [
-        ("enc_w", c_void_p * 3), ("enc_b", c_void_p * 3), ("cell", ctypes.POINTER(VrnnWeights)),
-        ("dec_w", c_void_p * 3), ("dec_b", c_void_p * 3), ("lik_w", c_void_p), ("lik_b", c_void_p),
-    ]  # fmt: skip
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t}  # and const char*
+_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t, "long long": ctypes.c_longlong, "int32_t": ctypes.c_int32}  # fmt: skip
+_POINTEE_WORDS = {"void", "char", "int", "unsigned", "long", "float", "double", "size_t", "int32_t"}
+_STARS = r"((?:\*\s*(?:const\b\s*)?)*)"
+_PROTOTYPE = re.compile(r"(int|size_t|const\s+char\s*\*)\s*(blvm_\w+)\s*\(([^()]*)\)")
+_PARAM = re.compile(rf"(?:const\s+)?(\w+(?:\s+\w+)*?)\s*{_STARS}(\w+)\s*(\[\d*\])?")  # type words, stars, name, array
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_MEMBERS = re.compile(r"(?:const\s+)?(\w+)\s*(\*.*)")  # pointee, declarators
+_DECLARATOR = re.compile(rf"{_STARS}(\w+)\s*(?:\[(\d+)\])?")  # stars, name, array length
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(BLVM_\w+)[ \t]+(?:\((-?\d+)\)|(-?\d+))(?!\w)", re.M)
 
 
-class SrnnWeights(ctypes.Structure):
-    """struct BlvmSrnnWeights / BlvmSrnnGrads."""
+def parse_header(text):
+    """The subset of C that include/blvm_hip.h is written in -> (structs {name: ctypes.Structure class}, signatures
+    {name: (restype, argtypes)}, constants {name: int}).  Every pointer is a void* except a pointer to one of the header's structs.
+    Anything outside the subset raises BlvmHipError quoting the declaration: nothing is guessed and nothing is skipped."""
+    constants = {name: int(a or b) for name, a, b in _DEFINE.findall(text)}
+    body = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    body = re.sub(r"^[ \t]*#.*$", "", body, flags=re.M)
+    structs, signatures = {}, {}
 
-    _fields_ = [
-        ("prior_w", c_void_p * 3), ("prior_b", c_void_p * 3), ("prior_hw", c_void_p), ("prior_hb", c_void_p),
-        ("post_w", c_void_p * 3), ("post_b", c_void_p * 3), ("post_hw", c_void_p), ("post_hb", c_void_p),
-    ]  # fmt: skip
+    def bad(why, decl):
+        return BlvmHipError(f"blvm_hip.h: {why}: {decl}")
+
+    def pointer(words, stars, decl):
+        if words in structs:
+            return ctypes.POINTER(structs[words]) if stars == 1 else ctypes.c_void_p
+        if not set(words.split()) <= _POINTEE_WORDS:
+            raise bad(f"pointer to the unknown type {words!r}", decl)
+        return ctypes.c_void_p
+
+    def struct(m):
+        decl = " ".join(m.group(0).split())
+        name, members, alias = m.groups()
+        if name != alias:
+            raise bad("struct tag and typedef name differ", decl)
+        fields = []
+        for line in filter(None, (" ".join(s.split()) for s in members.split(";"))):
+            mm = _MEMBERS.fullmatch(line)
+            dms = [_DECLARATOR.fullmatch(d.strip()) for d in mm.group(2).split(",")] if mm else [None]
+            if not all(dm and dm.group(1) for dm in dms) or (mm.group(1) != "float" and mm.group(1) not in structs):
+                raise bad(f"member `{line}` is not pointers to float or to an earlier struct", decl)
+            for stars, member, length in (dm.groups() for dm in dms):
+                # a host array of device pointers (float *const *) keeps its pointee type
+                t = ctypes.POINTER(ctypes.c_void_p) if stars.count("*") == 2 else pointer(mm.group(1), stars.count("*"), decl)
+                fields.append((member, t * int(length) if length else t))
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+        return " "
+
+    body = _STRUCT.sub(struct, body)
+    body = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", body, flags=re.S)
+    *decls, tail = (" ".join(s.split()) for s in body.split(";"))
+    if tail:
+        raise bad("a declaration without its `;`", tail)
+    for decl in filter(None, decls):
+        m = _PROTOTYPE.fullmatch(decl)
+        if not m:
+            raise bad("not `int | size_t | const char* blvm_name(parameters);` or `typedef struct Name {members} Name;`", decl)
+        ret, name, params = m.groups()
+        argtypes = []
+        for p in [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]:
+            pm = _PARAM.fullmatch(p)
+            if not pm:
+                raise bad(f"parameter `{p}` is not `type name`", decl)
+            words, stars = pm.group(1), pm.group(2).count("*") + bool(pm.group(4))
+            if stars:
+                argtypes.append(pointer(words, stars, decl))
+            elif words in _SCALARS:
+                argtypes.append(_SCALARS[words])
+            else:
+                raise bad(f"parameter `{p}` is passed by value and its type is none of {sorted(_SCALARS)}", decl)
+        signatures[name] = (_RETURNS.get(ret, ctypes.c_char_p), argtypes)
+    return structs, signatures, constants
 
 
-class SrnnDecodeWeights(ctypes.Structure):
-    """struct BlvmSrnnDecodeWeights."""
+try:
+    with open(_HEADER_PATH) as _f:
+        STRUCTS, SIGNATURES, CONSTANTS = parse_header(_f.read())
+except OSError as e:
+    raise BlvmHipError(f"the ABI header could not be read at {_HEADER_PATH}: {e}") from e
 
-    _fields_ = [
-        ("enc_w", c_void_p * 3), ("enc_b", c_void_p * 3), ("gru_wih", c_void_p), ("gru_whh", c_void_p), ("gru_bih", c_void_p),
-        ("gru_bhh", c_void_p), ("chain", ctypes.POINTER(SrnnWeights)), ("dec_w", c_void_p * 3), ("dec_b", c_void_p * 3),
-        ("lik_w", c_void_p), ("lik_b", c_void_p),
-    ]  # fmt: skip
+for _name, _cls in STRUCTS.items():  # a *Grads struct is filled in the Python-side order of its *Weights twin
+    if _name.endswith("Grads") and _cls._fields_ != STRUCTS[_name[:-5] + "Weights"]._fields_:
+        raise BlvmHipError(f"{_HEADER_PATH}: the members of {_name} differ from those of {_name[:-5]}Weights")
 
-
-class LstmDecodeWeights(ctypes.Structure):
-    """struct BlvmLstmDecodeWeights (wih, whh, bih, bhh: host arrays of num_layers device pointers)."""
-
-    _fields_ = [
-        ("emb_w", c_void_p * 3), ("emb_b", c_void_p * 3), ("wih", ctypes.POINTER(c_void_p)), ("whh", ctypes.POINTER(c_void_p)),
-        ("bih", ctypes.POINTER(c_void_p)), ("bhh", ctypes.POINTER(c_void_p)), ("dec_w", c_void_p * 3), ("dec_b", c_void_p * 3),
-        ("lik_w", c_void_p), ("lik_b", c_void_p),
-    ]  # fmt: skip
+VrnnWeights, VrnnGrads, VrnnDecodeWeights = STRUCTS["BlvmVrnnWeights"], STRUCTS["BlvmVrnnGrads"], STRUCTS["BlvmVrnnDecodeWeights"]
+SrnnWeights, SrnnGrads, SrnnDecodeWeights = STRUCTS["BlvmSrnnWeights"], STRUCTS["BlvmSrnnGrads"], STRUCTS["BlvmSrnnDecodeWeights"]
+RssmWeights, RssmGrads, LstmDecodeWeights = STRUCTS["BlvmRssmWeights"], STRUCTS["BlvmRssmGrads"], STRUCTS["BlvmLstmDecodeWeights"]
 
 
-class RssmWeights(ctypes.Structure):
-    """struct BlvmRssmWeights / BlvmRssmGrads."""
+@functools.lru_cache(maxsize=None)
+def _slots(cls):
+    """{slot name: (member, index)} of a struct class: a member under its own name (index None), every slot of an array member under
+    the member's name followed by the decimal index (`prior_w2` is prior_w[2])."""
+    slots = {}
+    for member, t in cls._fields_:
+        slots[member] = (member, None)
+        for i in range(getattr(t, "_length_", 0)):
+            slots[f"{member}{i}"] = (member, i)
+    return slots
 
-    _fields_ = [
-        ("gin_w", c_void_p), ("gin_b", c_void_p), ("gru_wih", c_void_p), ("gru_whh", c_void_p), ("gru_bih", c_void_p),
-        ("gru_bhh", c_void_p),
-        ("prior_w", c_void_p * 3), ("prior_b", c_void_p * 3), ("prior_hw", c_void_p), ("prior_hb", c_void_p),
-        ("post_w", c_void_p * 3), ("post_b", c_void_p * 3), ("post_hw", c_void_p), ("post_hb", c_void_p),
-    ]  # fmt: skip
 
-
-_SIGNATURES = {
-    "blvm_upload_i32": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
-    "blvm_version": (c_int, []),
-    "blvm_last_error": (ctypes.c_char_p, []),
-    "blvm_device_ok": (c_int, []),
-    "blvm_async_errors": (c_int, [c_void_p]),
-    "blvm_async_errors_take": (c_int, [c_void_p]),
-    "blvm_pchain_configure": (c_int, [c_int, c_int]),
-    "blvm_pchain_max_batch": (c_int, []),
-    "blvm_set_operand_dtype": (c_int, [c_int]),
-    "blvm_get_operand_dtype": (c_int, []),
-    "blvm_pchain_profile": (c_int, [c_void_p]),
-    "blvm_pchain_tune": (c_int, [c_int]),
-    "blvm_pchain_static": (c_int, [c_int]),
-    "blvm_rnn_path_counts": (c_int, [c_void_p]),
-    "blvm_rssm_path_counts": (c_int, [c_void_p]),
-    "blvm_pchain_chain_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "blvm_pchain_static_chain_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "blvm_pchain_static_chain_probe_fetch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "blvm_pchain_static_chain_probe_paced": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
-    "blvm_pchain_rows_to_t16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "blvm_gemm_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                              c_void_p, c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "blvm_gemm_ws_route": (c_int, [c_int, c_int, c_int, c_int, c_size_t, c_int, c_int, c_int, c_int, c_int]),
-    "blvm_gemm_ws_min_rows": (c_int, [c_int]),
-    "blvm_gemm_path_counts": (c_int, [c_void_p]),
-    "blvm_act_bwd_f32": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_size_t, c_void_p]),
-    "blvm_colsum_f32": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
-    "blvm_wgrad_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
-    "blvm_wgrad_group_f32": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "blvm_dmol_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                              c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-    "blvm_dmol_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                              c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-    "blvm_dmol_bwd_fused_workspace_floats": (c_size_t, [c_int] * 3),
-    "blvm_dmol_bwd_fused": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                    c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "blvm_elbo_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "blvm_elbo_bwd": (c_int, [c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p]),
-    "blvm_kl_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
-                            c_float, c_void_p, c_void_p, c_void_p]),
-    "blvm_kl_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                            c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "blvm_vrnn_decode_scratch_floats": (c_size_t, [c_int] * 4),
-    "blvm_vrnn_decode": (c_int, [ctypes.POINTER(VrnnDecodeWeights)] + [c_void_p] * 5 + [c_int] * 7 + [c_float] * 3 + [c_void_p] * 4),
-    "blvm_srnn_generate_scratch_floats": (c_size_t, [c_int] * 6),
-    "blvm_srnn_generate": (c_int, [ctypes.POINTER(SrnnDecodeWeights)] + [c_void_p] * 6 + [c_int] * 7 + [c_float] * 3 + [c_void_p] * 5),
-    "blvm_lstm_generate_scratch_floats": (c_size_t, [c_int] * 5),
-    "blvm_lstm_generate": (c_int, [ctypes.POINTER(LstmDecodeWeights)] + [c_void_p] * 5 + [c_int] * 6 + [c_float] + [c_void_p] * 5),
-    "blvm_lstm_generate_any_stack": (c_int, [ctypes.POINTER(LstmDecodeWeights)] + [c_void_p] * 5 + [c_int] * 6 + [c_float] + [c_void_p] * 5),
-    "blvm_vrnn_generate_scratch_floats": (c_size_t, [c_int] * 6),
-    "blvm_vrnn_generate": (c_int, [ctypes.POINTER(VrnnDecodeWeights)] + [c_void_p] * 5 + [c_int] * 7 + [c_float] * 3 + [c_void_p] * 4),
-    "blvm_vrnn_reserve_floats": (c_size_t, [c_int] * 6),
-    "blvm_vrnn_bwd_workspace_floats": (c_size_t, [c_int] * 6),
-    "blvm_vrnn_seq_fwd": (c_int, [ctypes.POINTER(VrnnWeights), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                  c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_void_p]),
-    "blvm_vrnn_seq_bwd": (c_int, [ctypes.POINTER(VrnnWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                                  c_void_p, ctypes.POINTER(VrnnWeights), c_void_p, c_void_p]),
-    "blvm_lstm_reserve_floats": (c_size_t, [c_int] * 3),
-    "blvm_lstm_bwd_workspace_floats": (c_size_t, [c_int] * 3),
-    "blvm_lstm_seq_fwd": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p] * 5),
-    "blvm_lstm_seq_bwd": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 9),
-    "blvm_gru_reserve_floats": (c_size_t, [c_int] * 3),
-    "blvm_gru_bwd_workspace_floats": (c_size_t, [c_int] * 3),
-    "blvm_gru_seq_fwd": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, ctypes.c_longlong, c_int]
-                         + [c_void_p] * 3),
-    "blvm_gru_seq_bwd": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_int]
-                         + [c_int] * 4 + [c_void_p, c_int, c_int] + [c_void_p] * 7),
-    "blvm_srnn_reserve_floats": (c_size_t, [c_int] * 5),
-    "blvm_srnn_bwd_workspace_floats": (c_size_t, [c_int] * 5),
-    "blvm_srnn_latent_fwd": (c_int, [ctypes.POINTER(SrnnWeights)] + [c_void_p] * 4 + [c_int] * 6 + [c_float, c_float]
-                             + [c_void_p] * 7),
-    "blvm_srnn_latent_bwd": (c_int, [ctypes.POINTER(SrnnWeights)] + [c_void_p] * 13 + [c_int, c_float] + [c_int] * 6
-                             + [c_float, c_float] + [c_void_p] * 3 + [ctypes.POINTER(SrnnWeights), c_void_p, c_void_p]),
-    "blvm_scale_act_f32": (c_int, [c_void_p, c_float, c_float, c_void_p, c_size_t, c_void_p]),
-    "blvm_conv1d_k2_workspace_floats": (c_size_t, [c_int] * 2),
-    "blvm_conv1d_k2_fwd": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 3),
-    "blvm_conv1d_k2_bwd": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 5),
-    "blvm_wavenet_block_reserve_floats": (c_size_t, [c_int] * 4),
-    "blvm_wavenet_block_workspace_floats": (c_size_t, [c_int] * 5),
-    "blvm_wavenet_block_fwd": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_float] + [c_void_p] * 5),
-    "blvm_wavenet_block_bwd": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_float] + [c_void_p] * 7),
-    "blvm_wavenet_stack_floats": (c_int, [c_int] * 3 + [c_void_p, c_int, c_void_p, c_void_p]),
-    "blvm_wavenet_stack_fwd": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_float] + [c_void_p] * 5),
-    "blvm_wavenet_stack_bwd": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_float] + [c_void_p] * 8),
-    "blvm_wavenet_decode_pack_floats": (c_size_t, [c_int] * 4),
-    "blvm_wavenet_decode_scratch_floats": (c_size_t, [c_void_p] + [c_int] * 4),
-    "blvm_wavenet_decode": (c_int, [c_void_p] * 2 + [c_int] * 7 + [c_float] * 3 + [c_void_p] * 5),
-    "blvm_wavenet_decode_ring_offset_floats": (c_size_t, [c_int] * 3),
-    "blvm_wavenet_decode_ring_fill": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p] * 2),
-    "blvm_wavenet_decode_resume": (c_int, [c_void_p] * 2 + [c_int] * 8 + [c_float] * 3 + [c_void_p] * 7),
-    "blvm_stcn_generate_pack_floats": (c_size_t, [c_int] * 4 + [c_void_p] * 2 + [c_int] * 3),
-    "blvm_stcn_generate_scratch_floats": (c_size_t, [c_void_p] + [c_int] * 4 + [c_void_p] * 2 + [c_int] * 4),
-    "blvm_stcn_generate": (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] * 2 + [c_int] * 7 + [c_float] * 6 + [c_void_p] * 9),
-    "blvm_stcn_generate_ring_offset_floats": (c_size_t, [c_int] * 4 + [c_void_p] * 2 + [c_int] * 3),
-    "blvm_stcn_generate_resume": (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] * 2 + [c_int] * 7 + [c_float] * 6 + [c_void_p] * 8
-                                  + [c_int] + [c_void_p] * 3),
-    "blvm_rssm_reserve_floats": (c_size_t, [c_int] * 4),
-    "blvm_rssm_bwd_workspace_floats": (c_size_t, [c_int] * 4),
-    "blvm_rssm_seq_fwd": (c_int, [ctypes.POINTER(RssmWeights)] + [c_void_p] * 5 + [c_int] * 7 + [c_float] + [c_void_p] * 8),
-    "blvm_rssm_seq_bwd": (c_int, [ctypes.POINTER(RssmWeights)] + [c_void_p] * 15 + [c_int, c_float] + [c_int] * 7 + [c_float]
-                          + [c_void_p] * 4 + [ctypes.POINTER(RssmWeights), c_void_p, c_void_p]),
-    "blvm_gmm_fwd": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 3),
-    "blvm_gmm_bwd": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 3),
-    "blvm_gauss_head_fwd": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 4 + [c_float] * 2 + [c_void_p] * 3),
-    "blvm_gauss_head_bwd": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 4 + [c_float] * 2 + [c_void_p] * 3),
-    "blvm_mix_sample": (c_int, [c_void_p] * 3 + [ctypes.c_longlong] + [c_int] * 2 + [c_float] * 3 + [c_void_p] * 2),
-    "blvm_gauss_latent_fwd": (c_int, [c_void_p] * 5 + [c_size_t] + [c_float] * 3 + [c_int] + [c_void_p] * 5),
-    "blvm_gauss_latent_bwd": (c_int, [c_void_p] * 9 + [c_size_t] + [c_float] * 3 + [c_int] + [c_void_p] * 5),
-    "blvm_chan_norm_workspace_doubles": (c_size_t, [c_int]),
-    "blvm_chan_norm_stats": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2 + [c_float] + [c_void_p] * 4),
-    "blvm_chan_norm_fwd": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2 + [c_float] + [c_void_p] * 4),
-    "blvm_chan_norm_bwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6),
-    "blvm_dwconv_out_length": (c_int, [c_int] * 5),
-    "blvm_dwconv_fwd": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p] * 2),
-    "blvm_dwconv_bwd": (c_int, [c_void_p] * 6 + [c_int] * 8 + [c_void_p] * 4),
-    "blvm_resample_add_fwd": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2),
-    "blvm_resample_add_bwd": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2),
-    "blvm_ctc_scratch_floats": (c_size_t, [c_int] * 4),
-    "blvm_ctc_loss": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 5),
-    "blvm_ctc_greedy": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 3),
-    "blvm_edit_distance": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 3 + [c_int] + [c_void_p] * 4),
-    "blvm_logmel": (c_int, [c_void_p] * 2 + [c_int] * 6 + [c_void_p] * 2 + [c_int] + [c_void_p] * 3),
-}  # fmt: skip
-
-EXPORTS = tuple(_SIGNATURES)
+def fill(struct, names, addresses):
+    """struct.<slot> = address for every (name, address) pair, slots named as in `_slots`.  None stays NULL.  A name that is no slot
+    of the struct (an index past an array's end included) raises.  -> struct."""
+    slots = _slots(type(struct))
+    for name, address in zip(names, addresses, strict=True):
+        if name not in slots:
+            raise BlvmHipError(f"struct {type(struct).__name__} has no slot {name!r}")
+        member, i = slots[name]
+        if i is None:
+            setattr(struct, member, address)
+        else:
+            getattr(struct, member)[i] = address
+    return struct
 
 
 def lib_path() -> str:
@@ -225,7 +156,7 @@ def load():
                 "(or __graft_entry__.build()).  There is no CPU/PyTorch fallback for the blvm hot path."
             )
         lib = ctypes.CDLL(_LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -270,7 +201,7 @@ def check_async(what: str = "a persistent recurrent launch", group=None):
         )
 
 
-DTYPES = {"f32": 0, "bf16": 1, "f16": 2}  # BLVM_DTYPE_F32 / _BF16 / _F16 (include/blvm_hip.h)
+DTYPES = {"f32": CONSTANTS["BLVM_DTYPE_F32"], "bf16": CONSTANTS["BLVM_DTYPE_BF16"], "f16": CONSTANTS["BLVM_DTYPE_F16"]}
 
 
 def set_operand_dtype(name: str):

@@ -270,7 +270,7 @@ def _dmol_workspace(device, floats: int) -> torch.Tensor:
     return ws
 
 
-BLVM_NOT_APPLICABLE = 1  # include/blvm_hip.h
+BLVM_NOT_APPLICABLE = _hip.CONSTANTS["BLVM_NOT_APPLICABLE"]
 
 
 class _DMoLFunction(torch.autograd.Function):
@@ -572,18 +572,13 @@ def gauss_latent(mu_p, sd_p_raw, mu_q_raw, sd_q_raw, eps, beta_p: float, beta_q:
     return _GaussLatentFunction.apply(mu_p, sd_p_raw, mu_q_raw, sd_q_raw, eps, (float(beta_p), float(beta_q), float(sd_eps), int(mode)))
 
 
-def _pack_weights(ts: Sequence[Optional[torch.Tensor]]) -> VrnnWeights:
-    d = dict(zip(_VRNN_PARAM_ORDER, ts))
-    p = lambda k: ptr(d[k]) if d[k] is not None else None  # noqa: E731
-    w = VrnnWeights()
-    for i in range(3):
-        w.prior_w[i], w.prior_b[i] = p(f"prior_w{i}"), p(f"prior_b{i}")
-        w.post_w[i], w.post_b[i] = p(f"post_w{i}"), p(f"post_b{i}")
-    for i in range(4):
-        w.phi_w[i], w.phi_b[i] = p(f"phi_w{i}"), p(f"phi_b{i}")
-    w.prior_hw, w.prior_hb, w.post_hw, w.post_hb = p("prior_hw"), p("prior_hb"), p("post_hw"), p("post_hb")
-    w.gru_wih, w.gru_whh, w.gru_bih, w.gru_bhh = p("gru_wih"), p("gru_whh"), p("gru_bih"), p("gru_bhh")
-    return w
+def _pack(struct, order, ts: Sequence[Optional[torch.Tensor]]):
+    """A weights or grads struct of the C ABI from tensors in the Python-side parameter order (None -> NULL)."""
+    return _hip.fill(struct(), order, [ptr(t) for t in ts])
+
+
+def _pack_weights(ts, struct=VrnnWeights):
+    return _pack(struct, _VRNN_PARAM_ORDER, ts)
 
 
 # The one-launch roll-outs (blvm_vrnn_generate, blvm_srnn_generate, blvm_lstm_generate_any_stack) keep one slab per step of every activation in
@@ -629,11 +624,8 @@ def _decode_weight_ptrs(w, first, first_lin, dec_lin, lik_lin):
     """Fills the `first`_w / `first`_b ("enc" | "emb"), dec_w / dec_b and lik_w / lik_b pointers of a decode-weights struct from the
     3 + 3 + 1 nn.Linear; -> the float32 contiguous tensors, which must stay alive while `w` is used."""
     keep = [_f32c(t) for lin in (*first_lin, *dec_lin, lik_lin) for t in (lin.weight, lin.bias)]
-    fw, fb = getattr(w, first + "_w"), getattr(w, first + "_b")
-    for i in range(3):
-        fw[i], fb[i] = ptr(keep[2 * i]), ptr(keep[2 * i + 1])
-        w.dec_w[i], w.dec_b[i] = ptr(keep[6 + 2 * i]), ptr(keep[6 + 2 * i + 1])
-    w.lik_w, w.lik_b = ptr(keep[12]), ptr(keep[13])
+    names = [f"{part}_{k}{i}" for part in (first, "dec") for i in range(3) for k in "wb"] + ["lik_w", "lik_b"]
+    _hip.fill(w, names, [ptr(t) for t in keep])
     return keep
 
 
@@ -733,7 +725,7 @@ class _VRNNSeqFunction(torch.autograd.Function):
         d_enc = torch.empty_like(enc)
         d_h0 = torch.empty(B, R, **f32) if ctx.has_h0 else None
         ws = torch.empty(lib.blvm_vrnn_bwd_workspace_floats(Tp, B, X, H, Z, R), **f32)
-        w, g = _pack_weights(params), _pack_weights(grads)
+        w, g = _pack_weights(params), _pack_weights(grads, _hip.VrnnGrads)
         _tick("bwd_begin")
         check(
             lib.blvm_vrnn_seq_bwd(w, ptr(enc), ptr(eps), ptr(decin), ptr(mu_q), ptr(sd_q), ptr(mu_p), ptr(sd_p), ptr(z),
@@ -915,16 +907,6 @@ _SRNN_PARAM_ORDER = (
 )
 
 
-def _pack_srnn(ts):
-    d = dict(zip(_SRNN_PARAM_ORDER, ts))
-    w = _hip.SrnnWeights()
-    for i in range(3):
-        w.prior_w[i], w.prior_b[i] = ptr(d[f"prior_w{i}"]), ptr(d[f"prior_b{i}"])
-        w.post_w[i], w.post_b[i] = ptr(d[f"post_w{i}"]), ptr(d[f"post_b{i}"])
-    w.prior_hw, w.prior_hb, w.post_hw, w.post_hb = ptr(d["prior_hw"]), ptr(d["prior_hb"]), ptr(d["post_hw"]), ptr(d["post_hb"])
-    return w
-
-
 def srnn_generate(enc_lin, gru, chain_params, dec_lin, lik_lin, x0, d0, z0, eps, u, v, S, H, Z, R, num_mix, sd_eps, slope, log_eps,
                   max_scratch_floats=None):  # fmt: skip
     """K3c: T = eps.shape[0] steps of ancestral sampling from SRNNAudio for all B <= 128 utterances in one persistent launch.
@@ -938,7 +920,7 @@ def srnn_generate(enc_lin, gru, chain_params, dec_lin, lik_lin, x0, d0, z0, eps,
     dev = x0.device
     gk = [_f32c(t) for t in (gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)]
     cp = [_f32c(p) for p in chain_params]
-    cw = _pack_srnn(cp)
+    cw = _pack(_hip.SrnnWeights, _SRNN_PARAM_ORDER, cp)
     w = _hip.SrnnDecodeWeights()
     keep = _decode_weight_ptrs(w, "enc", enc_lin, dec_lin, lik_lin)  # noqa: F841  (alive until the calls below are enqueued)
     w.gru_wih, w.gru_whh, w.gru_bih, w.gru_bhh = (ptr(t) for t in gk)
@@ -975,9 +957,10 @@ class _SRNNLatentFunction(torch.autograd.Function):
         zs = torch.empty(Tp + 1, B, Z, **f32)
         mu_q, sd_q, mu_p, sd_p = (torch.empty(Tp, B, Z, **f32) for _ in range(4))
         reserve = torch.empty(lib.blvm_srnn_reserve_floats(Tp, B, H, Z, R), **f32)
+        w = _pack(_hip.SrnnWeights, _SRNN_PARAM_ORDER, params)
         _tick("fwd_begin")
         check(
-            lib.blvm_srnn_latent_fwd(_pack_srnn(params), ptr(d), ptr(a), ptr(_f32c(z0)) if z0 is not None else None, ptr(eps),
+            lib.blvm_srnn_latent_fwd(w, ptr(d), ptr(a), ptr(_f32c(z0)) if z0 is not None else None, ptr(eps),
                                      Tp, B, H, Z, R, int(residual), sd_eps, slope, ptr(zs), ptr(mu_q), ptr(sd_q), ptr(mu_p),
                                      ptr(sd_p), ptr(reserve), stream_ptr()),
             "blvm_srnn_latent_fwd",
@@ -1011,12 +994,13 @@ class _SRNNLatentFunction(torch.autograd.Function):
         d_d, d_a = torch.empty_like(d), torch.empty_like(a)
         d_z0 = torch.empty(B, Z, **f32) if ctx.has_z0 else None
         ws = torch.empty(lib.blvm_srnn_bwd_workspace_floats(Tp, B, H, Z, R), **f32)
+        w, g = _pack(_hip.SrnnWeights, _SRNN_PARAM_ORDER, params), _pack(_hip.SrnnGrads, _SRNN_PARAM_ORDER, grads)
         _tick("bwd_begin")
         check(
-            lib.blvm_srnn_latent_bwd(_pack_srnn(params), ptr(d), ptr(a), ptr(eps), ptr(zs), ptr(mu_q), ptr(sd_q), ptr(mu_p),
+            lib.blvm_srnn_latent_bwd(w, ptr(d), ptr(a), ptr(eps), ptr(zs), ptr(mu_q), ptr(sd_q), ptr(mu_p),
                                      ptr(sd_p), ptr(reserve), ptr(d_z), ptr(x_sl_dev), ptr(c_raw), ptr(c_fn), stride, fn_floor,
                                      Tp, B, H, Z, R, int(residual), sd_eps, slope, ptr(d_d), ptr(d_a), ptr(d_z0),
-                                     _pack_srnn(grads), ptr(ws), stream_ptr()),
+                                     g, ptr(ws), stream_ptr()),
             "blvm_srnn_latent_bwd",
         )  # fmt: skip
         _tick("bwd_end")
@@ -1461,17 +1445,6 @@ _RSSM_PARAM_ORDER = (
 RSSM_PLAIN, RSSM_RESIDUAL, RSSM_PRECISION, RSSM_GENERATE = 0, 1, 2, 3  # 3: z drawn from the prior (generation)
 
 
-def _pack_rssm(ts):
-    d = dict(zip(_RSSM_PARAM_ORDER, ts))
-    w = _hip.RssmWeights()
-    for k in ("gin_w", "gin_b", "gru_wih", "gru_whh", "gru_bih", "gru_bhh", "prior_hw", "prior_hb", "post_hw", "post_hb"):
-        setattr(w, k, ptr(d[k]))
-    for i in range(3):
-        w.prior_w[i], w.prior_b[i] = ptr(d[f"prior_w{i}"]), ptr(d[f"prior_b{i}"])
-        w.post_w[i], w.post_b[i] = ptr(d[f"post_w{i}"]), ptr(d[f"post_b{i}"])
-    return w
-
-
 class _RSSMSeqFunction(torch.autograd.Function):
     """(enc, ctx, z0, h0, eps, 22 params) -> zs [T+1,B,Z], hs [T+1,B,H], kld [B], kld_fn [B] (+ non-diff. mu/sd)."""
 
@@ -1486,8 +1459,9 @@ class _RSSMSeqFunction(torch.autograd.Function):
         zs, hs = torch.empty(T + 1, B, Z, **f32), torch.empty(T + 1, B, H, **f32)
         mu_q, sd_q, mu_p, sd_p = (torch.empty(T, B, Z, **f32) for _ in range(4))
         reserve = torch.empty(lib.blvm_rssm_reserve_floats(T, B, H, Z), **f32)
+        w = _pack(_hip.RssmWeights, _RSSM_PARAM_ORDER, params)
         check(
-            lib.blvm_rssm_seq_fwd(_pack_rssm(params), ptr(enc), ptr(ctx), ptr(_f32c(z0)) if z0 is not None else None,
+            lib.blvm_rssm_seq_fwd(w, ptr(enc), ptr(ctx), ptr(_f32c(z0)) if z0 is not None else None,
                                   ptr(_f32c(h0)) if h0 is not None else None, ptr(eps), T, B, H, Z, C, E, mode, sd_eps, ptr(zs),
                                   ptr(hs), ptr(mu_q), ptr(sd_q), ptr(mu_p), ptr(sd_p), ptr(reserve), stream_ptr()),
             "blvm_rssm_seq_fwd",
@@ -1528,11 +1502,12 @@ class _RSSMSeqFunction(torch.autograd.Function):
         d_z0 = torch.empty(B, Z, **f32) if has_z0 else None
         d_h0 = torch.empty(B, H, **f32) if has_h0 else None
         ws = torch.empty(lib.blvm_rssm_bwd_workspace_floats(T, B, H, Z), **f32)
+        w, g = _pack(_hip.RssmWeights, _RSSM_PARAM_ORDER, params), _pack(_hip.RssmGrads, _RSSM_PARAM_ORDER, grads)
         check(
-            lib.blvm_rssm_seq_bwd(_pack_rssm(params), ptr(enc), ptr(ctx), ptr(eps), ptr(zs), ptr(hs), ptr(mu_q), ptr(sd_q),
+            lib.blvm_rssm_seq_bwd(w, ptr(enc), ptr(ctx), ptr(eps), ptr(zs), ptr(hs), ptr(mu_q), ptr(sd_q),
                                   ptr(mu_p), ptr(sd_p), ptr(reserve), ptr(d_zs), ptr(d_hs), ptr(x_sl_dev), ptr(c_raw), ptr(c_fn),
                                   stride, fn_floor, T, B, H, Z, C, E, mode, sd_eps, ptr(d_enc), ptr(d_ctx), ptr(d_z0), ptr(d_h0),
-                                  _pack_rssm(grads), ptr(ws), stream_ptr()),
+                                  g, ptr(ws), stream_ptr()),
             "blvm_rssm_seq_bwd",
         )  # fmt: skip
         if d_h0 is not None:

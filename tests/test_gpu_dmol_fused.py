@@ -15,7 +15,7 @@ from blvm import _hip, ops
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-NOT_APPLICABLE = 1  # BLVM_NOT_APPLICABLE (include/blvm_hip.h)
+NOT_APPLICABLE = _hip.CONSTANTS["BLVM_NOT_APPLICABLE"]
 BINS = 2**16
 
 

@@ -2,16 +2,16 @@
 import ctypes, hashlib, json, sys
 import torch
 sys.path.insert(0, "benchmarking-lvms_amd")
+from blvm import _hip
 from blvm.models import WaveNet
 from blvm.modules.distributions import DiscretizedLogisticMixtureDense
 
 path, tag = sys.argv[1], sys.argv[2]
 lib = ctypes.CDLL(path)
-vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-lib.blvm_wavenet_decode_scratch_floats.restype = ctypes.c_size_t
-lib.blvm_wavenet_decode_scratch_floats.argtypes = [vp] + [ci] * 4
-lib.blvm_wavenet_decode.restype = ci
-lib.blvm_wavenet_decode.argtypes = [vp] * 2 + [ci] * 7 + [cf] * 3 + [vp] * 5
+ci = ctypes.c_int
+for name in ("blvm_wavenet_decode_scratch_floats", "blvm_wavenet_decode"):
+    fn = getattr(lib, name)
+    fn.restype, fn.argtypes = _hip.SIGNATURES[name]
 torch.manual_seed(0)
 C, B, N = 64, 16, 2000
 m = WaveNet(likelihood=DiscretizedLogisticMixtureDense(C, 1, num_mix=10, num_bins=2**16), n_layers=10, n_stacks=5, res_channels=C).cuda()
