@@ -7,7 +7,9 @@ hot path of JakobHavtorn/benchmarking-lvms (`blvm`).  Only `tests/`, `__graft_en
 Parity status: PINNED.  Every function here is checked in `tests/test_oracle_golden.py` against golden
 vectors in `tests/golden/` that were produced by importing the unmodified reference in the build container
 (`oracle/gen_golden.py`).  The reference's own tests pin only `reverse_sequences` and `CausalConv1d`
-(SURVEY.md §4); those known-answer vectors are restated in the tests as well.
+(SURVEY.md §4); those known-answer vectors are restated in the tests as well.  The last section (`rounded_linear` and the
+`*_rounded_ref` time loops: the contract of the 16-bit operand modes, which the reference has no CPU form of) is pinned in
+`tests/test_rounded_oracle_cpu.py` against `F.linear`, the explicit formulas and the unrounded functions above.
 
 All citations are `path:line` relative to the reference checkout.  Everything is functional: models take a
 `state_dict` with the reference's key names and explicit noise `eps` instead of drawing from
@@ -918,3 +920,228 @@ def wavenet_generate(sd, n_samples, n_frames, n_layers, n_stacks, uniforms, num_
         out.append(pred)
         x = torch.cat([x[:, :, 1:], pred], dim=2)
     return torch.hstack(out)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the 16-bit operand modes: the contract of one product, and the sequence kernels link by link
+# ----------------------------------------------------------------------------------------------------------------------
+
+
+def operand_rounding(mode):
+    """`rnd` of an operand mode: "f32" / None -> the identity; "bf16" / "f16" -> t.to(float32).to(that type).to(t.dtype), torch's
+    nearest-even conversion (fp16: |x| >= 65520 -> inf, subnormals kept).  A value that is exact in fp32 gives the bits the
+    kernels' `v_cvt_pk_*` gives for it."""
+    if mode in (None, "f32"):
+        return lambda t: t
+    dt = {"bf16": torch.bfloat16, "f16": torch.float16}[mode]
+    return lambda t: t.to(torch.float32).to(dt).to(t.dtype)
+
+
+class _RoundedLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, W, b, rnd, rnd_wgrad):
+        xr, Wr = rnd(x), rnd(W)
+        ctx.rnd, ctx.rnd_wgrad = rnd, rnd_wgrad
+        ctx.save_for_backward(Wr, xr if rnd_wgrad is rnd else rnd_wgrad(x))
+        return F.linear(xr, Wr, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        Wr, xw = ctx.saved_tensors
+        dx = dW = db = None
+        if ctx.needs_input_grad[0]:
+            dx = ctx.rnd(dy).mm(Wr)
+        if ctx.needs_input_grad[1]:
+            dW = ctx.rnd_wgrad(dy).t().mm(xw)
+        if ctx.needs_input_grad[2]:
+            db = dy.sum(0)
+        return dx, dW, db, None, None
+
+
+def rounded_linear(x, W, b, rnd, rnd_wgrad=None):
+    """One product of a 16-bit operand mode, in the dtype it is given: x [n, K], W [N, K], b [N] or None.
+        forward   rnd(x) @ rnd(W).T + b
+        backward  dx = rnd(dy) @ rnd(W);  dW = rnd(dy).T @ rnd(x) (what the K6 weight-gradient GEMMs multiply);
+                  db = dy.sum(0) of the UNROUNDED dy (§3f: the bias sums stay fp32 sums of the unrounded operands).
+    `rnd_wgrad` (default: rnd) rounds the two operands of dW instead: a launch-per-step arm multiplies its recurrent product in
+    fp32 (rnd the identity) while its hoisted weight-gradient GEMM still runs in the mode.  With both the identity this is
+    F.linear and its autograd, bit for bit."""
+    return _RoundedLinear.apply(x, W, b, rnd, rnd if rnd_wgrad is None else rnd_wgrad)
+
+
+def _forced(value, own):
+    """Teacher forcing that keeps autograd connected: the VALUE is `value` (what the kernel stored), the gradient path is `own`'s."""
+    return value.to(own.dtype) + (own - own.detach())
+
+
+def lstm_sequence_rounded_ref(x, h0, c0, lens, w_ih, w_hh, b_ih, b_hh, rnd, recurrent_rounded=True, forced_out=None):
+    """`lstm_sequence_ref` in a 16-bit operand mode, as csrc/rnn.hip runs it: the input projection (one hoisted GEMM over all
+    steps) and both weight-gradient GEMMs are rounded in every arm; the recurrent product h @ Whh.T and its data gradient are
+    rounded where `recurrent_rounded` (the persistent arms; one launch per step multiplies them in fp32).  The cell state and the
+    gate math are never rounded.
+    forced_out [T,B,H]: the kernel's own `out`.  The h that enters step t + 1 then has the VALUE the kernel stored (out[t] for a
+    live row, the held state for a dead one; step 0 takes h0 itself), so every step is one product deep from public fp32 values;
+    its gradient path stays this function's."""
+    T, B, I = x.shape
+    H = w_hh.size(1)
+    ident = lambda t: t  # noqa: E731
+    h = torch.zeros(B, H, dtype=x.dtype) if h0 is None else h0
+    c = torch.zeros(B, H, dtype=x.dtype) if c0 is None else c0
+    zero = torch.zeros(B, H, dtype=x.dtype)
+    xg = rounded_linear(x.reshape(T * B, I), w_ih, b_ih, rnd).reshape(T, B, 4 * H)
+    outs = []
+    for t in range(T):
+        g = xg[t] + rounded_linear(h, w_hh, b_hh, rnd if recurrent_rounded else ident, rnd)
+        i, f, gg, o = g.chunk(4, -1)
+        c2 = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
+        h2 = torch.sigmoid(o) * torch.tanh(c2)
+        live = torch.ones(B, 1, dtype=torch.bool) if lens is None else (t < lens).unsqueeze(-1)
+        h_own, c = torch.where(live, h2, h), torch.where(live, c2, c)
+        outs.append(torch.where(live, h2, zero))
+        h = h_own if forced_out is None else _forced(torch.where(live, forced_out[t].to(x.dtype), h.detach()), h_own)
+    return torch.stack(outs, 0), h_own, c
+
+
+def gru_sequence_rounded_ref(x, h0, w_ih, w_hh, b_ih, b_hh, rnd, recurrent_rounded=True, forced_out=None):
+    """`gru_sequence` (nn.GRU over [T,B,I], no lengths) in a 16-bit operand mode, with the flags and the teacher forcing of
+    `lstm_sequence_rounded_ref`: forced_out[t] is the value of the h that enters step t + 1.  The reversed form is this function
+    between two `reverse_sequences`, of x and forced_out going in and of out coming back."""
+    T, B, I = x.shape
+    R = w_hh.size(1)
+    ident = lambda t: t  # noqa: E731
+    xg = rounded_linear(x.reshape(T * B, I), w_ih, b_ih, rnd).reshape(T, B, 3 * R)
+    h, outs = h0, []
+    for t in range(T):
+        gh = rounded_linear(h, w_hh, b_hh, rnd if recurrent_rounded else ident, rnd)
+        i_r, i_z, i_n = xg[t].chunk(3, -1)
+        h_r, h_z, h_n = gh.chunk(3, -1)
+        r = torch.sigmoid(i_r + h_r)
+        z = torch.sigmoid(i_z + h_z)
+        n = torch.tanh(i_n + r * h_n)
+        h_own = (1 - z) * n + z * h
+        outs.append(h_own)
+        h = h_own if forced_out is None else _forced(forced_out[t], h_own)
+    return torch.stack(outs, 0), h_own
+
+
+def wavenet_block_rounded_ref(x, conv_w, conv_b, rs_w, rs_b, dilation, T_skip, rnd):
+    """The skip output [T_skip,B,S] of ONE gated residual block (csrc/wavenet.hip, the fused block kernels) in a 16-bit operand mode:
+    x [L,B,C]; conv_w [2C,C,2] (tap 0 meets the frame `dilation` steps back), conv_b [2C]; rs_w [C+S,C], rs_b [C+S] (rows C.. are the
+    skip branch; a single block has no residual output, so rows ..C reach nothing).  Two products per row r = (l, b): the dilated
+    convolution as one product over both taps, pre = rnd([x[l], x[l + dilation]]) @ rnd([W0 | W1]).T + conv_b, and the 1x1
+    convolution of the gate output, rnd(tanh(pre[:C]) * sigmoid(pre[C:])) @ rnd(Wskip).T + b: that rounding of the fp32 gate output
+    is the only one of a hidden value."""
+    L, B, C = x.shape
+    rows = (L - dilation) * B
+    xcat = torch.cat([x[: L - dilation], x[dilation:]], -1).reshape(rows, 2 * C)
+    wcat = torch.cat([conv_w[:, :, 0], conv_w[:, :, 1]], 1)
+    pre = rounded_linear(xcat, wcat, conv_b, rnd)
+    act = torch.tanh(pre[:, :C]) * torch.sigmoid(pre[:, C:])
+    skip = rounded_linear(act[rows - T_skip * B:], rs_w[C:], rs_b[C:], rnd)
+    return skip.reshape(T_skip, B, -1)
+
+
+SRNN_CHAIN_PARAMS = tuple(f"{c}_{n}" for c in ("prior", "post") for n in ("w0", "b0", "w1", "b1", "w2", "b2", "hw", "hb"))
+
+
+def srnn_latent_rounded_ref(d, a, z0, eps, p, residual_posterior, rnd, recurrent_rounded=True, forced_zs=None, sd_eps=1e-6, slope=0.01, pre_out=None):
+    """The SRNN latent chain (csrc/srnn.hip; srnn.py:224-253) in a 16-bit operand mode.  d, a [T',B,R]; z0 [B,Z] or None (zeros);
+    eps [T',B,Z]; p: dict over SRNN_CHAIN_PARAMS (w0 [H,R+Z]: columns [:R] meet d / a, [R:] meet z_{t-1}).  Per step and chain
+    (prior from d, posterior from a): three Linear + LeakyReLU and a Gaussian head, then mu_q += mu_p (residual posterior) and
+    z_t = mu_q + sd_q * eps_t.  The d / a halves of the first layers are hoisted GEMMs over all steps and, like every weight
+    gradient, rounded in every arm; the products inside the step (z half of the first layer, layers two and three, the heads) and
+    their data gradients are rounded where `recurrent_rounded` (the persistent launch; the launch-per-link arm multiplies in fp32).
+    forced_zs [T'+1,B,Z]: the kernel's own zs; the z that enters step t then has the value zs[t] (zs[0] = z0 itself), so a step is
+    four products deep from public fp32 values, the activations between its layers being the hidden rounded ones.
+    pre_out: a list that receives every hidden pre-activation [B,H] (what the LeakyReLUs see), in order of evaluation.
+    -> zs [T'+1,B,Z], mu_q, sd_q, mu_p, sd_p [T',B,Z]"""
+    Tp, B, R = d.shape
+    Z = eps.shape[-1]
+    ident = lambda t: t  # noqa: E731
+    rr = rnd if recurrent_rounded else ident
+    beta = LN2 / (1.0 - sd_eps)
+    xs = {"prior": rounded_linear(d.reshape(Tp * B, R), p["prior_w0"][:, :R], p["prior_b0"], rnd).reshape(Tp, B, -1),
+          "post": rounded_linear(a.reshape(Tp * B, R), p["post_w0"][:, :R], p["post_b0"], rnd).reshape(Tp, B, -1)}
+    z = torch.zeros(B, Z, dtype=d.dtype) if z0 is None else z0
+    zs, out = [z], {k: [] for k in ("mu_q", "sd_q", "mu_p", "sd_p")}
+    for t in range(Tp):
+        st = {}
+        for c in ("prior", "post"):
+            pre = xs[c][t] + rounded_linear(z, p[f"{c}_w0"][:, R:], None, rr, rnd)
+            for k in (1, 2, 3):
+                if pre_out is not None:
+                    pre_out.append(pre.detach())
+                h = F.leaky_relu(pre, slope)
+                if k < 3:
+                    pre = rounded_linear(h, p[f"{c}_w{k}"], p[f"{c}_b{k}"], rr, rnd)
+            mu, s = rounded_linear(h, p[f"{c}_hw"], p[f"{c}_hb"], rr, rnd).chunk(2, -1)
+            st[c] = (mu, F.softplus(s, beta=beta) + sd_eps)
+        (mu_p, sd_p), (mu_q, sd_q) = st["prior"], st["post"]
+        if residual_posterior:
+            mu_q = mu_q + mu_p
+        z_own = mu_q + sd_q * eps[t]
+        zs.append(z_own)
+        for k, v in (("mu_q", mu_q), ("sd_q", sd_q), ("mu_p", mu_p), ("sd_p", sd_p)):
+            out[k].append(v)
+        z = z_own if forced_zs is None else _forced(forced_zs[t + 1], z_own)
+    return (torch.stack(zs, 0),) + tuple(torch.stack(out[k], 0) for k in ("mu_q", "sd_q", "mu_p", "sd_p"))
+
+
+VRNN_SEQ_PARAMS = (SRNN_CHAIN_PARAMS + tuple(f"phi_{n}{k}" for k in range(4) for n in ("w", "b")) + ("gru_wih", "gru_whh", "gru_bih", "gru_bhh"))
+
+
+def _relu_seen(pre, pre_out):
+    if pre_out is not None:
+        pre_out.append(pre.detach())
+    return F.relu(pre)
+
+
+def vrnn_sequence_rounded_ref(enc, h0, eps, p, residual_posterior, rnd, recurrent_rounded=True, forced=None, sd_eps=1e-6, pre_out=None):
+    """The VRNN cell over a sequence (csrc/vrnn.hip; vrnn.py:109-141) in a 16-bit operand mode.  enc [T',B,X]; h0 [B,R] or None; eps
+    [T',B,Z]; p: dict over VRNN_SEQ_PARAMS (post_w0 [H,R+X]: columns [:R] meet h, [R:] meet enc; gru_wih [3R,X+H]: columns [:X] meet
+    enc, [X:] meet phi).  The enc halves are hoisted GEMMs, rounded in every arm like every weight gradient; the products of a step
+    are rounded where `recurrent_rounded`.  A step has three pieces, and `forced` = dict(decin, z), the kernel's own stores, gives
+    each its input VALUES: h_{t-1} (decin[t, :, H:]) -> prior / posterior MLPs (ReLU) and heads -> z_t;  z_t -> the four phi_z layers
+    -> phi_t (decin[t, :, :H]);  (enc_t, phi_t, h_{t-1}) -> the GRU cell -> h_t (decin[t + 1, :, H:]), one product deep.
+    pre_out: a list that receives every hidden pre-activation [B,H] (what the ReLUs see), in order of evaluation.
+    -> decin [T'+1,B,H+R] (the phi part of row T' is zero), mu_q, sd_q, mu_p, sd_p, z [T',B,Z]"""
+    Tp, B, X = enc.shape
+    R, H = p["gru_whh"].shape[1], p["phi_w3"].shape[0]
+    ident = lambda t: t  # noqa: E731
+    rr = rnd if recurrent_rounded else ident
+    beta = LN2 / (1.0 - sd_eps)
+    e2 = enc.reshape(Tp * B, X)
+    xq = rounded_linear(e2, p["post_w0"][:, R:], p["post_b0"], rnd).reshape(Tp, B, -1)
+    xg = rounded_linear(e2, p["gru_wih"][:, :X], p["gru_bih"], rnd).reshape(Tp, B, -1)
+    h = torch.zeros(B, R, dtype=enc.dtype) if h0 is None else h0
+    h_own = h  # what this function computed for the h part of a row: compared with the kernel's, never the forced value itself
+    rows, out = [], {k: [] for k in ("mu_q", "sd_q", "mu_p", "sd_p", "z")}
+    for t in range(Tp):
+        st = {}
+        for c in ("prior", "post"):
+            a = rounded_linear(h, p[f"{c}_w0"][:, :R], p["prior_b0"] if c == "prior" else None, rr, rnd)
+            a = _relu_seen(a + xq[t] if c == "post" else a, pre_out)
+            for k in (1, 2):
+                a = _relu_seen(rounded_linear(a, p[f"{c}_w{k}"], p[f"{c}_b{k}"], rr, rnd), pre_out)
+            mu, s = rounded_linear(a, p[f"{c}_hw"], p[f"{c}_hb"], rr, rnd).chunk(2, -1)
+            st[c] = (mu, F.softplus(s, beta=beta) + sd_eps)
+        (mu_p, sd_p), (mu_q, sd_q) = st["prior"], st["post"]
+        if residual_posterior:
+            mu_q = mu_q + mu_p
+        z_own = mu_q + sd_q * eps[t]
+        z = z_own if forced is None else _forced(forced["z"][t], z_own)
+        phi_own = z
+        for k in range(4):
+            phi_own = _relu_seen(rounded_linear(phi_own, p[f"phi_w{k}"], p[f"phi_b{k}"], rr, rnd), pre_out)
+        phi = phi_own if forced is None else _forced(forced["decin"][t, :, :H], phi_own)
+        gi = xg[t] + rounded_linear(phi, p["gru_wih"][:, X:], None, rr, rnd)
+        gh = rounded_linear(h, p["gru_whh"], p["gru_bhh"], rr, rnd)
+        (i_r, i_u, i_n), (h_r, h_u, h_n) = gi.chunk(3, -1), gh.chunk(3, -1)
+        u = torch.sigmoid(i_u + h_u)
+        rows.append(torch.cat([phi_own, h_own], -1))
+        h_own = (1 - u) * torch.tanh(i_n + torch.sigmoid(i_r + h_r) * h_n) + u * h
+        for k, v in (("mu_q", mu_q), ("sd_q", sd_q), ("mu_p", mu_p), ("sd_p", sd_p), ("z", z_own)):
+            out[k].append(v)
+        h = h_own if forced is None else _forced(forced["decin"][t + 1, :, H:], h_own)
+    rows.append(torch.cat([torch.zeros(B, H, dtype=enc.dtype), h_own], -1))
+    return (torch.stack(rows, 0),) + tuple(torch.stack(out[k], 0) for k in ("mu_q", "sd_q", "mu_p", "sd_p", "z"))

@@ -101,6 +101,29 @@ def test_gemm_f16_operands_fp32_accumulate(op_a, op_b, M, N, K):
     assert e16 < ebf / 4, (e16, ebf)
 
 
+@pytest.mark.parametrize("op_a,op_b", [(0, 0), (0, 1), (1, 0), (1, 1)])
+@pytest.mark.parametrize("M,N,K", [(64, 64, 32), (130, 70, 50)])
+def test_gemm_f16_subnormal_operands_are_halfs(op_a, op_b, M, N, K):
+    """Operands below fp16's smallest normal number (6.1e-5), which randn almost never draws: log-uniform in [1e-7, 6e-5] with a
+    random sign.  .half() keeps them as subnormals (multiples of 2^-24); so must the conversion and the fp16 matrix pipe."""
+    g = torch.Generator().manual_seed(M + N + K + op_a * 2 + op_b)
+
+    def draw(*shape):
+        lo, hi = np.log(1e-7), np.log(6e-5)
+        mag = torch.exp(torch.rand(*shape, generator=g) * (hi - lo) + lo)
+        return mag * (torch.randint(0, 2, shape, generator=g) * 2 - 1)
+
+    A, Bm = draw(*((K, M) if op_a else (M, K))), draw(*((K, N) if op_b else (N, K)))
+    assert float(A.abs().max()) < FP16_TINY and float(Bm.abs().max()) < FP16_TINY
+    ref = _gemm_ref(A, Bm, op_a, op_b, rh)
+    C = torch.empty(M, N, device=DEV)
+    ops.gemm(op_a, op_b, M, N, K, A.to(DEV), A.shape[1], Bm.to(DEV), Bm.shape[1], C, N)
+    flushed = _gemm_ref(A, Bm, op_a, op_b, lambda t: torch.where(t.abs() < 2.0**-14, torch.zeros_like(t), t).half().double())
+    print(f"subnormal operands: vs .half() {rel_l2(C, ref):.3e}; |C| max {float(C.abs().max()):.3e}, |ref| max {float(ref.abs().max()):.3e}, flushed |ref| max {float(flushed.abs().max()):.3e}")
+    assert rel_l2(C, ref) < 2e-6
+    assert float(flushed.abs().max()) == 0.0 and float(C.abs().max()) > 1e-9  # flushed operands would give a zero product
+
+
 @pytest.mark.parametrize("op_a,op_b,M,N,K,split", [(1, 1, 192, 768, 30000, 40), (1, 0, 384, 130, 20001, 24), (0, 1, 16385, 576, 192, 1), (1, 1, 96, 80, 4096, 16)])
 def test_gemm_f16_split_k_wide_tiles_accumulate(op_a, op_b, M, N, K, split):
     g = torch.Generator().manual_seed(M + N + K)

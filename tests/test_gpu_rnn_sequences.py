@@ -26,12 +26,12 @@ import torch
 
 import blvm_oracle as O
 from blvm import _hip, ops
+from rnn_arms import PER_STEP, PROGRAM, REGS, sorted_lens, unsorted_lens, zero_row
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 BAR_VALUE, BAR_GRAD = 1e-5, 2e-5
-REGS, PROGRAM, PER_STEP = 0, 1, 2
 ARM_NAMES = ("register-resident", "interpreter program", "one launch per step")
 LSTM_FWD, LSTM_BWD, GRU_FWD, GRU_BWD = 0, 1, 2, 3
 
@@ -120,32 +120,6 @@ class Checks:
 # ----------------------------------------------------------------------------------------------------------------------
 # lengths
 # ----------------------------------------------------------------------------------------------------------------------
-
-
-def sorted_lens(T_, B):
-    """Descending, >= 1, the first row full: what pack_padded_sequence accepts."""
-    return torch.tensor([max(1, T_ - (k * T_) // B) for k in range(B)], dtype=torch.int64)
-
-
-def zero_row(B):
-    """The row of length 0 of `unsorted_lens`: the middle of the last row tile (the partial one when B is no multiple of 16)."""
-    r0 = 16 * ((B - 1) // 16)
-    return r0 + (B - 1 - r0) // 2
-
-
-def unsorted_lens(T_, B, with_zero=True):
-    """What LSTMAudio produces, `(x_sl_stack - 1).clamp(min=0)`: unsorted; lens[0] = T; one row of length 1; with_zero: one row of
-    length 0 inside the last row tile (B = 1 has room for the full row only)."""
-    lens = torch.tensor([1 + (7 * b + 3) % T_ for b in range(B)], dtype=torch.int64)
-    lens[0] = T_
-    if B == 1:
-        return lens
-    z = zero_row(B) if with_zero and B >= 3 else -1
-    one = B - 1 if B - 1 != z else 1
-    lens[one] = 1
-    if z >= 0:
-        lens[z] = 0
-    return lens
 
 
 def test_length_patterns():
