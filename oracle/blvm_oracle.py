@@ -878,6 +878,67 @@ def dmol_sample(logits, locs, log_scales, u, u2):
     return (loc + torch.exp(ls) * (torch.log(u2) - torch.log(1 - u2))).clamp(-1, 1)
 
 
+def gmm_sample(logits, mu, sd, u, n):
+    """rsample_gaussian_mixture (variational.py:156-195) with its draws made explicit: u [*,K] in (1e-6, 1-1e-6) -> Gumbel-max
+    component pick (:183-184); n [*,1] standard normal -> mu + sd * n of the picked component (:190-194, :152).  No clamp."""
+    idx = (logits - torch.log(-torch.log(u))).argmax(-1, keepdim=True).unsqueeze(-1)
+    return torch.gather(mu, -1, idx).squeeze(-1) + torch.gather(sd, -1, idx).squeeze(-1) * n
+
+
+def mix_mode(logits, locs):
+    """`mode` of both mixture heads (distributions.py:173-186 GMM, :359-368 DMoL): the location of the arg-max-logit component,
+    first maximum (torch.argmax), NOT clamped.  logits [*,K], locs [*,D,K] -> [*,D]."""
+    return dmol_mode(logits, locs)
+
+
+def softplus_beta64(raw, beta, threshold=20.0):
+    """nn.Softplus(beta) in float64: log1p(exp(beta x)) / beta, x itself where beta x > threshold (distributions.py:168-171)."""
+    z = raw.double() * beta
+    return torch.where(z > threshold, raw.double(), torch.log1p(torch.exp(torch.clamp(z, max=threshold))) / beta)
+
+
+def mix_draw_detail(par, u=None, v=None, kind=0, log_eps=-7.0, sd_beta=0.0, sd_eps=0.0, floor=True):
+    """One draw per row of packed head outputs par [N,3K] (logits | locations | raw scales), everything in float64 on the float32
+    inputs cast up.  The pick is variational.py:337-338 / :183-184 (scores s_m = p_m - log(-log u_m), first maximum); u None: the
+    mode's pick (distributions.py:183, :365; Gumbel terms 0).  The value is, kind 0: loc + exp(max(raw, log_eps)) * (log v -
+    log(1 - v)) (distributions.py:386 + variational.py:291-292), clamped to [-1, 1] (:305); kind 1: mu + sd * v (variational.py:152)
+    with sd = raw (sd_beta == 0) or softplus_beta(raw) + sd_eps (distributions.py:168-171, 203); v None: the location itself.
+    floor=False drops the max(raw, log_eps) (used only to show that a test input reaches the floor).
+    Returns a dict of [N] tensors: best, runner (the first maximum among the others; = best for K == 1), s_best, s_runner, g_best,
+    g_runner (Gumbel terms), p_best, p_runner (logits), loc, sd, pre (the value BEFORE the clamp), x (after it), and
+    pre_runner, x_runner: the same value had the runner-up been picked."""
+    par = par.double()
+    N, K = par.shape[0], par.shape[1] // 3
+    logits, locs, raws = par[:, :K], par[:, K:2 * K], par[:, 2 * K:]
+    G = torch.zeros_like(logits) if u is None else -torch.log(-torch.log(u.double().reshape(N, K)))
+    s = logits + G
+    best = s.argmax(-1)
+    rows = torch.arange(N)
+    if K > 1:
+        masked = s.clone()
+        masked[rows, best] = -float("inf")
+        runner = masked.argmax(-1)
+        dup = masked[rows, runner] == -float("inf")  # every other score is -inf as well: argmax returned index 0
+        runner = torch.where(dup & (best == 0), torch.ones_like(runner), runner)
+    else:
+        runner = best.clone()
+
+    def value(c):
+        loc, raw = locs[rows, c], raws[rows, c]
+        if kind == 0:
+            sd = torch.exp(raw.clamp(min=log_eps) if floor else raw)
+            pre = loc if v is None else loc + sd * (torch.log(v.double().reshape(N)) - torch.log(1 - v.double().reshape(N)))
+            return loc, sd, pre, pre.clamp(-1, 1) if v is not None else pre  # the mode is NOT clamped (distributions.py:363-368)
+        sd = softplus_beta64(raw, sd_beta) + sd_eps if sd_beta > 0 else raw
+        pre = loc if v is None else loc + sd * v.double().reshape(N)
+        return loc, sd, pre, pre
+
+    loc, sd, pre, x = value(best)
+    _, _, pre_r, x_r = value(runner)
+    return dict(best=best, runner=runner, s_best=s[rows, best], s_runner=s[rows, runner], g_best=G[rows, best], g_runner=G[rows, runner],
+                p_best=logits[rows, best], p_runner=logits[rows, runner], loc=loc, sd=sd, pre=pre, x=x, pre_runner=pre_r, x_runner=x_r)
+
+
 def srnn_audio_generate(sd, n_samples, max_timesteps, stack, eps, uniforms, num_mix=10, prefix="srnn"):
     """SRNNAudio.generate, unconditional (srnn.py:304-403, 515-535): d_t = GRU(encoder(x_{t-1}), d_{t-1}); z_t ~ prior(cat[d_t, z_{t-1}])
     (Elman transfer); x_t ~ DMoL(decoder(cat[z_t, d_t])) — always SAMPLED — fed back.  eps [T,B,z]; uniforms[t] = (u, u2).

@@ -25,7 +25,7 @@ sys.path.insert(0, HERE)
 import blvm  # noqa: E402  (the reference, from /root/reference via PYTHONPATH)
 import blvm.models as RM  # noqa: E402
 from blvm.data.transforms import MuLawEncode  # noqa: E402
-from blvm.modules.distributions import DiagonalGaussianDense, DiscretizedLogisticMixtureDense  # noqa: E402
+from blvm.modules.distributions import DiagonalGaussianDense, DiagonalGaussianMixtureDense, DiscretizedLogisticMixtureDense  # noqa: E402
 from blvm.training.annealers import CosineAnnealer  # noqa: E402
 from blvm.utils import log_likelihoods as RLL  # noqa: E402
 from blvm.utils import operations as ROP  # noqa: E402
@@ -1170,8 +1170,60 @@ def gen_stack_sizes():
     save("stack_sizes.npz", **arrays)
 
 
+def gen_samplers():
+    """The mixture samplers draw by draw (tests/draw_cases.py holds the regimes and the rule): parameter rows from heads_stress.npz
+    and the crafted ones, and what the reference draws and returns on them.  Per regime: seed, call the reference, re-seed and
+    replay its draws in its own order: uniform_(1e-5, 1-1e-5) over [N,K] then uniform_(1e-8, 1-1e-8) over [N,1]
+    (variational.py:337, :291); Gaussian mixture: uniform_(1e-6, 1-1e-6) over [N,K] then randn over [N,1] (:183, :152).  A regime
+    that crafts its own u or v keeps the reference's draws beside them as ref_u / ref_v; ref_x always belongs to the reference's."""
+    sys.path.insert(0, os.path.join(HERE, "..", "tests"))
+    import draw_cases as DC
+
+    hs = np.load(os.path.join(OUT, "heads_stress.npz"))
+    regs, out, K = DC.build(hs), {}, DC.K0
+    dmol = DiscretizedLogisticMixtureDense(4, 1, num_mix=K, num_bins=2**16)
+    gmm = DiagonalGaussianMixtureDense(4, 1, num_mix=K)
+    for i, (name, r) in enumerate(regs.items()):
+        par = r["par"]
+        N = par.shape[0]
+        logits, a, b = par[:, :K], par[:, K:2 * K].unsqueeze(1), par[:, 2 * K:].unsqueeze(1)
+        seed = 700 + i
+        if name in DC.GMM_REGIMES:
+            sd = b if name == "gmm_sd0" else torch.nn.functional.softplus(b, beta=float(hs["gmm_beta"])) + float(hs["gmm_sd_eps"])
+            torch.manual_seed(seed)
+            x = gmm.sample((logits, a, sd))
+            torch.manual_seed(seed)
+            ref_u, ref_v = torch.empty(N, K).uniform_(1e-6, 1 - 1e-6), torch.randn(N, 1)
+            out[f"{name}_n"] = ref_v.squeeze(1)
+            mode = gmm.mode((logits, a, sd))
+        else:
+            ls = b.clamp(min=dmol.log_epsilon)  # distributions.py:386
+            torch.manual_seed(seed)
+            x = dmol.sample((logits, a, ls))
+            torch.manual_seed(seed)
+            ref_u, ref_v = torch.empty(N, K).uniform_(1e-5, 1 - 1e-5), torch.empty(N, 1).uniform_(1e-8, 1 - 1e-8)
+            out[f"{name}_v"] = r.get("v", ref_v.squeeze(1))
+            out[f"{name}_n"] = r["n"]
+            if "v" in r:
+                out[f"{name}_ref_v"] = ref_v.squeeze(1)
+            mode = dmol.mode((logits, a, ls))
+        # the replay is the reference's own arithmetic on the replayed draws: it must reproduce the reference's samples bit for bit
+        pick = (logits - torch.log(-torch.log(ref_u))).argmax(-1, keepdim=True)
+        if name in DC.GMM_REGIMES:
+            again = a.squeeze(1).gather(1, pick) + sd.squeeze(1).gather(1, pick) * ref_v
+        else:
+            again = (a.squeeze(1).gather(1, pick) + torch.exp(ls.squeeze(1).gather(1, pick)) * (torch.log(ref_v) - torch.log(1 - ref_v))).clamp(-1, 1)
+        assert torch.equal(again, x), f"{name}: the replayed draws do not reproduce the reference's samples"
+        out[f"{name}_par"], out[f"{name}_u"] = par, r.get("u", ref_u)
+        if "u" in r:
+            out[f"{name}_ref_u"] = ref_u
+        out[f"{name}_ref_x"], out[f"{name}_ref_mode"] = x.squeeze(1), mode.squeeze(1)
+    out.update(gmm_beta=hs["gmm_beta"], gmm_sd_eps=hs["gmm_sd_eps"])
+    save("samplers.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["functions", "vrnn_small", "vrnn_full", "lstm", "srnn", "wavenet", "rssm", "cwvae", "stcn", "heads", "generate", "generate16", "wavenet_stacked", "cwvae_resets", "stcn_bottom_up", "lstm_layers", "data", "split_eval", "heads_stress", "stack_sizes"]
+    which = sys.argv[1:] or ["functions", "vrnn_small", "vrnn_full", "lstm", "srnn", "wavenet", "rssm", "cwvae", "stcn", "heads", "generate", "generate16", "wavenet_stacked", "cwvae_resets", "stcn_bottom_up", "lstm_layers", "data", "split_eval", "heads_stress", "stack_sizes", "samplers"]
     for w in which:
         globals()[f"gen_{w}"]()

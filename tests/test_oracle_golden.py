@@ -512,6 +512,57 @@ def test_heads_stress_kl_free_nats_ties(hs):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# samplers.npz: what the unmodified reference draws and returns on the sampler regimes (oracle/gen_golden.py::gen_samplers).  The
+# float32 oracle on the recorded draws must give the reference's samples bit for bit (same torch ops in the same order); the
+# float64 detail helper, which is the truth of tests/test_gpu_samplers.py, must hold the reference's samples to the rule of
+# tests/draw_cases.py: decided draws at fp32 accuracy, the caps on undecided ones kept by the reference's own draws.
+# ----------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.fixture(scope="module")
+def smp():
+    import draw_cases as DC
+
+    return DC, DC.load(GOLDEN)
+
+
+def _ref_draws(fx, name):
+    pick = lambda k: T(fx[f"{name}_ref_{k}"] if f"{name}_ref_{k}" in fx else fx[f"{name}_{k}"])  # noqa: E731
+    return pick("u"), pick("v")
+
+
+def test_samplers_dmol_sample_and_mode_match_reference(smp):
+    DC, (regs, fx) = smp
+    for name in DC.DMOL_REGIMES:
+        par, (u, v) = regs[name]["par"], _ref_draws(fx, name)
+        logits, locs, ls = O.dmol_head(par, torch.eye(30), torch.zeros(30))
+        assert torch.equal(O.dmol_sample(logits, locs, ls, u, v.unsqueeze(1)).squeeze(1), T(fx[f"{name}_ref_x"])), name
+        assert torch.equal(O.mix_mode(logits, locs).squeeze(1), T(fx[f"{name}_ref_mode"])), name
+        res = DC.judge(name, T(fx[f"{name}_ref_x"]), par, u, v, 0, *DC.head_constants(name, 0, fx))
+        DC.report(f"reference fp32 {name}", res)
+        d = O.mix_draw_detail(par, None, None, 0)
+        assert torch.equal(d["x"].float(), T(fx[f"{name}_ref_mode"])), name  # the mode: first maximum, location NOT clamped
+    mode = T(fx["saturation_ref_mode"])
+    assert int((mode.abs() > 1).sum()) > 100  # the reference's mode leaves |loc| > 1 as it is (distributions.py:363-368)
+    ties = T(fx["ties_ref_mode"])
+    assert torch.equal(ties[64:128], regs["ties"]["par"][64:128, 13]) and torch.equal(ties[128:], regs["ties"]["par"][128:, 10])
+
+
+def test_samplers_gmm_sample_and_mode_match_reference(smp):
+    DC, (regs, fx) = smp
+    beta, eps = float(fx["gmm_beta"]), float(fx["gmm_sd_eps"])
+    for name in DC.GMM_REGIMES:
+        par, u, n = regs[name]["par"], regs[name]["u"], regs[name]["n"]
+        logits, mu, raw = par[:, :10], par[:, 10:20].unsqueeze(1), par[:, 20:].unsqueeze(1)
+        sd = raw if name == "gmm_sd0" else torch.nn.functional.softplus(raw, beta=beta) + eps
+        assert torch.equal(O.gmm_sample(logits, mu, sd, u, n.unsqueeze(1)).squeeze(1), T(fx[f"{name}_ref_x"])), name
+        assert torch.equal(O.mix_mode(logits, mu).squeeze(1), T(fx[f"{name}_ref_mode"])), name
+        res = DC.judge(name, T(fx[f"{name}_ref_x"]), par, u, n, 1, *DC.head_constants(name, 1, fx))
+        DC.report(f"reference fp32 {name}", res)
+        assert torch.equal(O.mix_draw_detail(par, None, None, 1)["x"].float(), T(fx[f"{name}_ref_mode"])), name
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # the recurrent models at the frame-stack sizes 1 and 256 of the reference's benchmark table (tests/golden/stack_sizes.npz)
 # ----------------------------------------------------------------------------------------------------------------------
 
