@@ -87,8 +87,9 @@ class VRNNCell(nn.Module):
         out += [g.weight_ih, g.weight_hh, g.bias_ih, g.bias_hh]
         return out
 
-    def sequence(self, enc, h0, eps, x_sl_dev, stride: int, free_nats: float = 0.0, generate: bool = False):
-        """`generate=True`: z is drawn from the prior instead of the posterior (`VRNNCell.generate`, vrnn.py:143-164)."""
+    def sequence(self, enc, h0, eps, x_sl_dev, stride: int, free_nats: float = 0.0, generate: bool = False, decoder=None):
+        """`generate=True`: z is drawn from the prior instead of the posterior (`VRNNCell.generate`, vrnn.py:143-164).
+        `decoder`: an `ops.DecoderFold` (see `ops.vrnn_sequence`)."""
         if not self.condition_h_on_x:
             raise NotImplementedError("libblvm_hip: VRNN cell kernels implement condition_h_on_x=True (the VRNNAudio form)")
         head = self.prior[6]
@@ -96,7 +97,7 @@ class VRNNCell(nn.Module):
             raise NotImplementedError("libblvm_hip: Gaussian heads with initial_sd != 1 are not supported")
         mode = 3 if generate else int(self.residual_posterior)
         return ops.vrnn_sequence(enc, h0, eps, x_sl_dev, self.kernel_params(), self.x_dim, self.h_dim, self.z_dim,
-                                 self.r_dim, mode, stride, free_nats, head.epsilon)  # fmt: skip
+                                 self.r_dim, mode, stride, free_nats, head.epsilon, decoder=decoder)  # fmt: skip
 
     @torch.no_grad()
     def generate(self, x: torch.Tensor, h: torch.Tensor, use_mode: bool = False, eps: Optional[torch.Tensor] = None):
@@ -196,11 +197,17 @@ class VRNN(nn.Module):
 
         if eps is None:
             eps = torch.randn(Tp, B, Z, device=dev, dtype=torch.float32)
-        decin, kld, kld_fn, mu_q, sd_q, mu_p, sd_p, z = self.vrnn_cell.sequence(enc, h0, eps, x_sl_dev, stride, free_nats)
+        # a decoder of three Linear + LeakyReLU goes down with the cell: the forward launch runs it on its spare workgroups where it
+        # has them (`given`: its activations; None: not folded, the decoder runs as K6 below)
+        widths = [(lin.in_features, lin.out_features) for lin in dec_lin]
+        chained = len(dec_lin) == 3 and widths[0] == (H + R, widths[1][0]) and widths[1][1] == widths[1][0] == widths[2][0]
+        fold = ops.DecoderFold(dec_lin, ops.LEAKY_SLOPE) if chained and all(lin.bias is not None for lin in dec_lin) else None
+        decin, kld, kld_fn, mu_q, sd_q, mu_p, sd_p, z = self.vrnn_cell.sequence(enc, h0, eps, x_sl_dev, stride, free_nats, decoder=fold)
+        given = fold.given if fold is not None else None
 
-        # decoder MLP (K6) + likelihood head (K7 / K7b / K7c); dec [T'*B, S*F] detached
+        # decoder MLP (K6, or its node alone) + likelihood head (K7 / K7b / K7c); dec [T'*B, S*F] detached
         dec, log_prob = mlp_log_prob(lik, decin[:Tp].view(Tp * B, H + R), dec_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE, y, x_sl_dev,
-                                     ops.LAYOUT_TIME_MAJOR, B, T, Tp, S)  # fmt: skip
+                                     ops.LAYOUT_TIME_MAJOR, B, T, Tp, S, given=given)  # fmt: skip
 
         # ELBO assembly in float64 as the reference does (mask dtype `float`, vrnn.py:266-279), one kernel:
         # elbo = log_prob - kld, loss = -(log_prob - beta * kld_fn).sum() / n_frames

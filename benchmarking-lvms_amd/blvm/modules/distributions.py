@@ -80,11 +80,12 @@ class DiscretizedLogisticMixtureDense(ConditionalDistribution):
         W, b = (self.params.weight, self.params.bias) if fused_linear else (None, None)
         return ops.dmol_log_prob(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, self.num_mix, self.num_bins, self.log_epsilon)
 
-    def fused_mlp_log_prob(self, x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S):
+    def fused_mlp_log_prob(self, x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given=None):
         """The decoder MLP `layers` (activation after every layer) and this head on its output: (activations DETACHED, log_prob [B]).
-        The head's backward hands the MLP the gradient of its last pre-activation and the head Linear's own gradients (K7 fused)."""
+        The head's backward hands the MLP the gradient of its last pre-activation and the head Linear's own gradients (K7 fused).
+        `given`: the MLP's activations where they were computed already (`ops.mlp_given`)."""
         return ops.mlp_dmol_log_prob(x2d, layers, self.params.weight, self.params.bias, y, x_sl_dev, layout, B, T, Tp, S, act, slope,
-                                     self.num_mix, self.num_bins, self.log_epsilon)  # fmt: skip
+                                     self.num_mix, self.num_bins, self.log_epsilon, given)  # fmt: skip
 
     @staticmethod
     def _pack(params):
@@ -153,10 +154,11 @@ class DiagonalGaussianMixtureDense(ConditionalDistribution):
         return ops.mix_sample(DiscretizedLogisticMixtureDense._pack(params), u, nrm, 1, sd_beta=0.0).unsqueeze(-1)
 
 
-def mlp_log_prob(lik, x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S):
+def mlp_log_prob(lik, x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given=None):
     """Decoder MLP + likelihood head `lik` on its output: (decoder activations DETACHED, masked per-utterance log-likelihood sums [B]).
-    The DMoL head takes its fused form; the Gaussian heads run the MLP and `fused_log_prob` as separate nodes."""
+    The DMoL head takes its fused form; the Gaussian heads run the MLP and `fused_log_prob` as separate nodes.
+    `given`: the MLP's activations, one tensor per layer, where they were computed already (the VRNN forward launch)."""
     if isinstance(lik, DiscretizedLogisticMixtureDense):
-        return lik.fused_mlp_log_prob(x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S)
-    dec = ops.mlp(x2d, layers, act, slope)
+        return lik.fused_mlp_log_prob(x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given)
+    dec = ops.mlp(x2d, layers, act, slope) if given is None else ops.mlp_given(x2d, layers, given, act, slope)
     return dec.detach(), lik.fused_log_prob(dec, y, x_sl_dev, layout, B, T, Tp, S)

@@ -151,6 +151,11 @@ class _MLPFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        return _MLPFunction._backward(ctx, dy, 4)
+
+    @staticmethod
+    def _backward(ctx, dy, first_param):
+        """`first_param`: position of the first weight among the node's inputs (what `ctx.needs_input_grad` is indexed by)."""
         n = ctx.n_layers
         saved = ctx.saved_tensors
         acts, params = saved[: n + 1], saved[n + 1 :]
@@ -164,7 +169,7 @@ class _MLPFunction(torch.autograd.Function):
             dz = dy
         grads: List[Optional[torch.Tensor]] = [None] * (2 * n)
         # every weight / bias gradient of the chain as a view of ONE zero-filled buffer (one fill launch instead of 2n)
-        want = [ctx.needs_input_grad[4 + i] and params[i] is not None for i in range(2 * n)]
+        want = [ctx.needs_input_grad[first_param + i] and params[i] is not None for i in range(2 * n)]
         sizes = [(params[i].numel() + 3) // 4 * 4 if want[i] else 0 for i in range(2 * n)]
         flat = torch.zeros(sum(sizes), device=dy.device, dtype=torch.float32)
         views, off = [], 0
@@ -188,7 +193,33 @@ class _MLPFunction(torch.autograd.Function):
                 gemm(0, 1, M, K, N, dz, N, _f32c(W), K, dx, K, slope=slope, gate=gate, ldg=K)
                 dz = dx
         wgrad_group(jobs, acts[0].shape[0])
-        return (dz if ctx.needs_input_grad[0] else None, None, None, None, *grads)
+        return (dz if ctx.needs_input_grad[0] else None, *(None,) * (first_param - 1), *grads)
+
+
+class _MLPGivenFunction(torch.autograd.Function):
+    """`_MLPFunction` whose forward was already computed elsewhere (the VRNN forward launch runs its decoder as a follower of the
+    recurrent chain): `given` = the activations of `x`, one per layer, of the first layers or of all of them.  The remaining layers run
+    here; the backward is `_MLPFunction`'s."""
+
+    @staticmethod
+    def forward(ctx, x, act, slope, head_gates, given, *params):
+        x = _f32c(x)
+        n_layers = len(params) // 2
+        acts = [x, *given]
+        for l in range(len(given), n_layers):  # the layers that were not: K6, as `_MLPFunction` runs them
+            W, b = params[2 * l], params[2 * l + 1]
+            inp = acts[-1]
+            out = torch.empty(inp.shape[0], W.shape[0], device=x.device, dtype=torch.float32)
+            gemm(0, 0, inp.shape[0], W.shape[0], inp.shape[1], inp, inp.stride(0), _f32c(W), inp.shape[1], out, W.shape[0],
+                 bias=_f32c(b) if b is not None else None, act=act, slope=slope)
+            acts.append(out)
+        ctx.act, ctx.slope, ctx.n_layers, ctx.head_gates = act, slope, n_layers, bool(head_gates)
+        ctx.save_for_backward(*acts, *params)
+        return acts[-1]
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _MLPFunction._backward(ctx, dy, 5)
 
 
 def mlp(x2d: torch.Tensor, layers: Sequence[torch.nn.Linear], act: int = ACT_LEAKY, slope: float = LEAKY_SLOPE):
@@ -331,18 +362,27 @@ class _DMoLFunction(torch.autograd.Function):
         return (d_dec if ctx.needs_input_grad[0] else None, dW, db) + (None,) * 11
 
 
+def mlp_given(x2d, layers, given, act: int = ACT_LEAKY, slope: float = LEAKY_SLOPE, head_gates: bool = False):
+    """`mlp(x2d, layers, act, slope)` whose activations `given` (one tensor per layer) were computed already."""
+    params = []
+    for lin in layers:
+        params += [lin.weight, lin.bias]
+    return _MLPGivenFunction.apply(x2d, act, slope, head_gates, tuple(given), *params)
+
+
 def mlp_dmol_log_prob(x2d, layers, W, b, y, x_sl_dev, layout, B, T, Tp, S, act: int = ACT_LEAKY, slope: float = LEAKY_SLOPE,
-                      num_mix=10, num_bins=256, log_eps=-7.0):  # fmt: skip
+                      num_mix=10, num_bins=256, log_eps=-7.0, given=None):  # fmt: skip
     """`mlp(x2d, layers, act, slope)` feeding `dmol_log_prob(., W, b, ...)` as one pair of autograd nodes whose backward never writes
     d_par or d_dec: the head's backward kernel hands the MLP the gradient of its last pre-activation and accumulates dW / db itself.
     Returns (dec DETACHED — the activations [rows, S*3*num_mix] for samplers / modes —, log_prob [B] float64)."""
     if act == ACT_NONE or W is None:
-        dec = mlp(x2d, layers, act, slope)
+        dec = mlp(x2d, layers, act, slope) if given is None else mlp_given(x2d, layers, given, act, slope)
         return dec.detach(), dmol_log_prob(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, num_bins, log_eps)
     params = []
     for lin in layers:
         params += [lin.weight, lin.bias]
-    dec = _MLPFunction.apply(x2d, act, slope, True, *params)  # (differentiable ONLY through the head below)
+    # (differentiable ONLY through the head below; `given`: the activations, computed already)
+    dec = _MLPFunction.apply(x2d, act, slope, True, *params) if given is None else mlp_given(x2d, layers, given, act, slope, True)
     gate = slope if act == ACT_LEAKY else 0.0
     return dec.detach(), _DMoLFunction.apply(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, num_bins, log_eps, gate)
 
@@ -678,7 +718,9 @@ class _VRNNSeqFunction(torch.autograd.Function):
     """(enc, h0, eps, 28 params) -> decin [T'+1,B,H+R], kld [B], kld_fn [B]  (+ non-differentiable mu/sd/z)."""
 
     @staticmethod
-    def forward(ctx, enc, h0, eps, x_sl_dev, cfg, *params):
+    def forward(ctx, enc, h0, eps, x_sl_dev, cfg, dec, *params):
+        """`dec`: None or a `DecoderFold`: the decoder is handed down and, where the launch folds it (blvm_vrnn_seq_fwd_dec), its
+        three activations are left in `dec.given`."""
         Tp, B, X, H, Z, R, residual, sd_eps, stride, fn_floor = cfg
         enc, eps = _f32c(enc), _f32c(eps)
         params = tuple(_f32c(p) for p in params)
@@ -687,15 +729,32 @@ class _VRNNSeqFunction(torch.autograd.Function):
         f32 = dict(device=dev, dtype=torch.float32)
         decin = torch.empty(Tp + 1, B, H + R, **f32)  # (the driver clears the phi-part of the extra row, which no step writes)
         mu_q, sd_q, mu_p, sd_p, z = (torch.empty(Tp, B, Z, **f32) for _ in range(5))
-        reserve = torch.empty(lib.blvm_vrnn_reserve_floats(Tp, B, X, H, Z, R), **f32)
         w = _pack_weights(params)
-        _tick("fwd_begin")
-        check(
-            lib.blvm_vrnn_seq_fwd(w, ptr(enc), ptr(_f32c(h0)) if h0 is not None else None, ptr(eps), Tp, B, X, H, Z, R,
-                                  int(residual), sd_eps, ptr(decin), ptr(mu_q), ptr(sd_q), ptr(mu_p), ptr(sd_p), ptr(z),
-                                  ptr(reserve), stream_ptr()),
-            "blvm_vrnn_seq_fwd",
-        )  # fmt: skip
+        if dec is None:
+            reserve = torch.empty(lib.blvm_vrnn_reserve_floats(Tp, B, X, H, Z, R), **f32)
+            _tick("fwd_begin")
+            check(
+                lib.blvm_vrnn_seq_fwd(w, ptr(enc), ptr(_f32c(h0)) if h0 is not None else None, ptr(eps), Tp, B, X, H, Z, R,
+                                      int(residual), sd_eps, ptr(decin), ptr(mu_q), ptr(sd_q), ptr(mu_p), ptr(sd_p), ptr(z),
+                                      ptr(reserve), stream_ptr()),
+                "blvm_vrnn_seq_fwd",
+            )  # fmt: skip
+        else:
+            keep = [_f32c(t.detach()) for lin in dec.layers for t in (lin.weight, lin.bias)]
+            DH, SF = keep[0].shape[0], keep[4].shape[0]
+            ys = [torch.empty(Tp * B, n, **f32) for n in (DH, DH, SF)]
+            three = ctypes.c_void_p * 3  # host arrays of device pointers: weights, biases, activations
+            dw, db, dy = three(*(ptr(t) for t in keep[0::2])), three(*(ptr(t) for t in keep[1::2])), three(*(ptr(t) for t in ys))
+            reserve = torch.empty(lib.blvm_vrnn_fwd_reserve_floats(Tp, B, X, H, Z, R, DH, SF), **f32)
+            folded = ctypes.c_int(0)
+            _tick("fwd_begin")
+            check(
+                lib.blvm_vrnn_seq_fwd_dec(w, ptr(enc), ptr(_f32c(h0)) if h0 is not None else None, ptr(eps), Tp, B, X, H, Z, R,
+                                          int(residual), sd_eps, ptr(decin), ptr(mu_q), ptr(sd_q), ptr(mu_p), ptr(sd_p), ptr(z),
+                                          ptr(reserve), dw, db, dy, DH, SF, dec.slope, ctypes.byref(folded), stream_ptr()),
+                "blvm_vrnn_seq_fwd_dec",
+            )  # fmt: skip
+            dec.given = tuple(ys[: folded.value]) if folded.value else None  # (2: the last layer is left to the caller)
         _tick("fwd_end")
         kld = torch.zeros(B, device=dev, dtype=torch.float64)
         kld_fn = torch.zeros(B, device=dev, dtype=torch.float64)
@@ -734,17 +793,31 @@ class _VRNNSeqFunction(torch.autograd.Function):
             "blvm_vrnn_seq_bwd",
         )  # fmt: skip
         _tick("bwd_end")
-        return (d_enc, d_h0, None, None, None, *grads)
+        return (d_enc, d_h0, None, None, None, None, *grads)
 
 
 def vrnn_sequence(enc, h0, eps, x_sl_dev, params: Sequence[torch.Tensor], X, H, Z, R, residual_posterior, stride,
-                  free_nats=0.0, sd_eps=1e-6):  # fmt: skip
+                  free_nats=0.0, sd_eps=1e-6, decoder=None):  # fmt: skip
     """Run the VRNN cell over enc [T',B,X].  `params` in `_VRNN_PARAM_ORDER`.  Returns
-    (decin [T'+1,B,H+R], kld [B] f64, kld_fn [B] f64, mu_q, sd_q, mu_p, sd_p, z)."""
+    (decin [T'+1,B,H+R], kld [B] f64, kld_fn [B] f64, mu_q, sd_q, mu_p, sd_p, z).
+    `decoder`: a `DecoderFold` — the decoder MLP on decin[:T'] handed down so that the forward launch can run it on its spare
+    workgroups; its `given` is set to the three activations [T'*B, .], or to None where the launch did not fold the decoder."""
     Tp, B, _ = enc.shape
     fn_floor = float(free_nats) / Z if free_nats else 0.0
     cfg = (Tp, B, X, H, Z, R, int(residual_posterior), float(sd_eps), int(stride), fn_floor)  # 0 plain, 1 residual, 3 generate
-    return _VRNNSeqFunction.apply(enc, h0, eps, x_sl_dev, cfg, *params)
+    if decoder is None:
+        return _VRNNSeqFunction.apply(enc, h0, eps, x_sl_dev, cfg, None, *params)
+    decoder.given = None
+    return _VRNNSeqFunction.apply(enc, h0, eps, x_sl_dev, cfg, decoder, *params)
+
+
+class DecoderFold:
+    """The VRNN decoder MLP handed down to the cell's forward (`vrnn_sequence`): `layers` = its three nn.Linear, LeakyReLU(`slope`)
+    after each.  After the call `given` holds the three activations (plain tensors outside the graph; `mlp_given` builds the decoder's
+    autograd node from them) where the launch computed them, else None."""
+
+    def __init__(self, layers, slope: float = LEAKY_SLOPE):
+        self.layers, self.slope, self.given = list(layers), float(slope), None
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -180,10 +180,14 @@ struct Reserve {
   float *Wp[3], *Wq[3], *Wph, *Wqh, *Wf[4], *Wih, *Whh;  // T16 copies of the weights the forward chain multiplies by
   // persistent forward (B <= kPchainCarveMaxB): T16 copies of every activation a link multiplies, per step [rt*16, width]
   float *H16, *P16[3], *Q16[3], *Z16, *FZ16[3], *PHI16;
+  // decoder range of the forward launch (SF > 0; vrnn_static.h): the hand-off slabs of the decoder's first two layers, the polled
+  // row-major partial sum of the first, and T16 copies of the three weights.  Carved behind everything else, so the pieces above
+  // sit where the backward (which carves with SF = 0) looks for them.
+  float *Y116, *Y216, *Y1P, *Wd[3];
   size_t x16_bytes;  // from the first piece a launch polls to the end of the T16 copies: sentinel-filled in one go
 };
 
-size_t carve_reserve(float* base, int Tp, int B, int H, int Z, int R, Reserve* r) {
+size_t carve_reserve(float* base, int Tp, int B, int H, int Z, int R, Reserve* r, int SF = 0) {
   const size_t n = (size_t)Tp * B;
   Arena ar{base};
   Reserve tmp;
@@ -210,7 +214,10 @@ size_t carve_reserve(float* base, int Tp, int B, int H, int Z, int R, Reserve* r
     tmp.Z16 = ar.take(m * Z);
     for (int i = 0; i < 3; ++i) tmp.FZ16[i] = ar.take(m * H);
     tmp.PHI16 = ar.take(m * H);
+    tmp.Y116 = tmp.Y216 = tmp.Y1P = nullptr;
+    if (SF > 0) { tmp.Y116 = ar.take(m * H); tmp.Y216 = ar.take(m * H); tmp.Y1P = ar.take(n * H); }
     tmp.x16_bytes = ar.bytes_from(tmp.H16);
+    if (SF > 0) { tmp.Wd[0] = ar.take((size_t)H * (H + R)); tmp.Wd[1] = ar.take((size_t)H * H); tmp.Wd[2] = ar.take((size_t)SF * H); }
   }
   if (r) *r = tmp;
   return ar.floats();
@@ -280,6 +287,26 @@ inline bool pchain_split3() {
   return v != 0;
 }
 
+struct VrnnDecoder {  // blvm_vrnn_seq_fwd_dec's three layers and the activations it writes
+  const float *w[3], *b[3];
+  float* y[3];
+};
+// the decoder MLP inside the forward launch (blvm_vrnn_seq_fwd_dec; blvm_vrnn_dec_fold; env BLVM_VRNN_DEC_FOLD=0: never)
+// 0: never; 1: all three layers; 2: the first two only (the last layer stays a K6 launch of the caller's)
+int g_dec_fold = [] { const char* e = getenv("BLVM_VRNN_DEC_FOLD"); const int v = e ? atoi(e) : 1; return v >= 0 && v <= 2 ? v : 1; }();
+long g_dec_folded = 0;  // forward calls that computed the decoder inside the launch
+// How many layers of the decoder a forward call folds (0 | 2 | 3; the deal it then runs on is dec_ct's).  Needed: fp32 operands,
+// 16-row tiles without row groups, the own-range deal, Z == H (the phi_z run is one descriptor), a decoder of hidden width H whose
+// output is whole 16-column tiles, and a decoder range in which every link fits (vrnn_static.h).
+int dec_ct(int layers, int SF) { return layers == 3 ? SF / 16 : layers == 2 ? 1 : 0; }  // vrnn_fwd_deal's ctD (two layers: dec[3] is not used)
+int vrnn_dec_folds(int B, int H, int Z, int R, int DH, int SF) {
+  if (!g_dec_fold || !vrnn_persistent(B) || device_cus() < 32 || operand_16bit() || pchain_optype(B) != OP_F32) return 0;
+  if (B > 64 || vrnn_row_groups(B) || Z != H || DH != H || SF <= 0 || SF % 16 != 0) return 0;
+  const int tl = (B + 15) / 16, layers = g_dec_fold == 2 ? 2 : 3;
+  const bool fits = pchain::vrnn_fwd_deal(H / 16, Z / 16, R / 16, tl, device_cus() & ~7, vrnn_shared_deal(false, tl), dec_ct(layers, SF)).dec[0].nwg > 0;
+  return fits ? layers : 0;
+}
+
 int check_dims(int Tp, int B, int X, int H, int Z, int R) {
   BLVM_REQUIRE(Tp > 0 && B > 0, "vrnn: bad Tp=%d B=%d", Tp, B);
   BLVM_REQUIRE(X > 0 && H > 0 && Z > 0 && R > 0 && X % 16 == 0 && H % 16 == 0 && Z % 16 == 0 && R % 16 == 0,
@@ -297,6 +324,16 @@ extern "C" size_t blvm_vrnn_reserve_floats(int Tp, int B, int X, int H, int Z, i
   (void)X;
   return carve_reserve(nullptr, Tp, B, H, Z, R, nullptr);
 }
+extern "C" size_t blvm_vrnn_fwd_reserve_floats(int Tp, int B, int X, int H, int Z, int R, int DH, int SF) {
+  (void)X;
+  return carve_reserve(nullptr, Tp, B, H, Z, R, nullptr, vrnn_dec_folds(B, H, Z, R, DH, SF) ? SF : 0);  // (grown only where the call folds)
+}
+extern "C" int blvm_vrnn_dec_fold(int mode) {
+  if (mode == -2) return (int)std::min<long>(g_dec_folded, 0x7fffffffL);
+  const int was = g_dec_fold;
+  if (mode >= 0) g_dec_fold = mode <= 2 ? mode : 1;
+  return was;
+}
 
 extern "C" size_t blvm_vrnn_bwd_workspace_floats(int Tp, int B, int X, int H, int Z, int R) {
   return carve_ws(nullptr, Tp, B, X, H, Z, R, nullptr);
@@ -305,13 +342,17 @@ extern "C" size_t blvm_vrnn_bwd_workspace_floats(int Tp, int B, int X, int H, in
 static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const float* h0, const float* eps,
                              int Tp, int B, int X, int H, int Z, int R, int residual_posterior, float sd_eps,
                              float* decin, float* mu_q, float* sd_q, float* mu_p, float* sd_p, float* z,
-                             float* reserve, hipStream_t s) {
+                             float* reserve, hipStream_t s, const VrnnDecoder* dec = nullptr, int DH = 0, int SF = 0,
+                             float dec_slope = 0.f, int* folded = nullptr) {
   BLVM_TRY(check_dims(Tp, B, X, H, Z, R));
   BLVM_REQUIRE(w && enc && eps && decin && mu_q && sd_q && mu_p && sd_p && z && reserve, "vrnn_fwd: null pointer");
   BLVM_REQUIRE(aligned16(enc) && aligned16(decin) && aligned16(reserve) && aligned16(z),
                "vrnn_fwd: buffers must be 16-byte aligned");
+  if (folded) *folded = 0;
+  // dec != null: the reserve is blvm_vrnn_fwd_reserve_floats(..., DH, SF) floats; the decoder runs inside the launch where that applies
+  const int fold = dec != nullptr ? vrnn_dec_folds(B, H, Z, R, DH, SF) : 0;  // layers of the decoder inside the launch
   Reserve rs;
-  carve_reserve(reserve, Tp, B, H, Z, R, &rs);
+  carve_reserve(reserve, Tp, B, H, Z, R, &rs, fold ? SF : 0);
   const size_t n = (size_t)Tp * B;
   const int ldd = H + R;
   const float beta = softplus_beta_of(sd_eps);  // ln2 / (initial_sd - eps), initial_sd = 1
@@ -334,6 +375,11 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   for (int l = 1; l < 4; ++l) BLVM_TRY(t16_pack_rows(w->phi_w[l], H, H, H, rs.Wf[l], s));
   BLVM_TRY(t16_pack_rows(w->gru_wih + X, X + H, 3 * R, H, rs.Wih, s));  // the phi columns
   BLVM_TRY(t16_pack_rows(w->gru_whh, R, 3 * R, R, rs.Whh, s));
+  if (fold) {
+    BLVM_TRY(t16_pack_rows(dec->w[0], H + R, H, H + R, rs.Wd[0], s));
+    BLVM_TRY(t16_pack_rows(dec->w[1], H, H, H, rs.Wd[1], s));
+    if (fold == 3) BLVM_TRY(t16_pack_rows(dec->w[2], H, SF, H, rs.Wd[2], s));
+  }
   BLVM_TRY(pack_scope.flush());  // all packs above in one launch
 
   // initial state -> h-part of decin row 0
@@ -358,7 +404,7 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     // shared deal (row groups, many row tiles): no range of its own for the hidden projection -- it runs on the posterior half after that
     // half's run, in the window where only the prior half works on the heads and the phi_z run
     const bool shared = vrnn_shared_deal(groups, tl);
-    const VrnnFwdDeal dl = vrnn_fwd_deal(ctH, ctZ, ctR, tl, cus, shared);  // (vrnn_static.h: the ranges of every link)
+    const VrnnFwdDeal dl = vrnn_fwd_deal(ctH, ctZ, ctR, tl, cus, shared, dec_ct(fold, SF));  // (vrnn_static.h: the ranges of every link)
     Builder bld;
     bld.begin(pchain_optype(B), Tp, B, groups ? 8 : 4, false, dl.g);
     bld.p.rt_group = RTG;
@@ -407,13 +453,41 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       o.ld[GRU_LD_HPREV] = ldd; o.ld[LD_OUT] = ldd; o.n16[N16_OUT] = ctR; o.i[GRU_I_R] = R;
       add_desc(bld, K_GRU, ctR, dl.gru.wg0, dl.gru.nwg, H, 0, 0, Tp, o);
     }
+    if (fold) {
+      // The decoder of step t behind the chain, on the workgroups the deal leaves free (vrnn_static.h): row t of decin = [phi_t | h_t]
+      // arrives as the slabs PHI16[t] and H16[t].  The first layer's K = H + R product is two links over the two K-ranges of its packed
+      // rows: the h-part (with the bias) can run as soon as the step begins, the phi-part adds it in its epilogue.  Every layer ends in
+      // the activation, as the K6 chain's does.  Outputs: the activations the decoder's backward reads (y[0], y[1], y[2] row-major).
+      const long sF = (long)B * SF;
+      const int canary = (pchain_tune() & 16) ? DF_CANARY : 0, ldw = H + R;
+      Operands o;
+      o.p[LIN_A] = {rs.H16, xR}; o.p[LIN_W] = rs.Wd[0] + (size_t)ctH * 256; o.i[LIN_I_W_WIDTH] = ldw; o.p[LIN_BIAS] = dec->b[0];
+      o.p[LIN_ORM] = {rs.Y1P, sH}; o.ld[LD_OUT] = H;
+      add_desc(bld, K_LIN, dl.dec[0].ct, dl.dec[0].wg0, dl.dec[0].nwg, R, DF_RM_SC1 | DF_GENTLE | canary, 0, Tp, o);
+      o = Operands();
+      o.p[LIN_A] = {rs.PHI16, xH}; o.p[LIN_W] = rs.Wd[0]; o.i[LIN_I_W_WIDTH] = ldw; o.p[LIN_ADD] = {rs.Y1P, sH}; o.ld[LIN_LD_ADD] = H;
+      o.p[LIN_ORM] = {dec->y[0], sH}; o.ld[LD_OUT] = H; o.p[LIN_O16] = {rs.Y116, xH}; o.n16[N16_OUT] = ctH; o.f[LIN_F_SLOPE] = dec_slope;
+      add_desc(bld, K_LIN, dl.dec[1].ct, dl.dec[1].wg0, dl.dec[1].nwg, H, DF_ADD_POLLED | DF_RELU | DF_GENTLE | canary, 0, Tp, o);
+      o = Operands();
+      o.p[LIN_A] = {rs.Y116, xH}; o.p[LIN_W] = rs.Wd[1]; o.p[LIN_BIAS] = dec->b[1]; o.p[LIN_ORM] = {dec->y[1], sH}; o.ld[LD_OUT] = H;
+      o.p[LIN_O16] = {rs.Y216, xH}; o.n16[N16_OUT] = ctH; o.f[LIN_F_SLOPE] = dec_slope;
+      add_desc(bld, K_LIN, dl.dec[2].ct, dl.dec[2].wg0, dl.dec[2].nwg, H, DF_RELU | DF_GENTLE | canary, 0, Tp, o);
+      if (fold == 3) {  // (2: the last layer stays the caller's K6 launch on y[1])
+        o = Operands();
+        o.p[LIN_A] = {rs.Y216, xH}; o.p[LIN_W] = rs.Wd[2]; o.p[LIN_BIAS] = dec->b[2]; o.p[LIN_ORM] = {dec->y[2], sF}; o.ld[LD_OUT] = SF;
+        o.f[LIN_F_SLOPE] = dec_slope;
+        add_desc(bld, K_LIN, dl.dec[3].ct, dl.dec[3].wg0, dl.dec[3].nwg, H, DF_RELU | DF_GENTLE | canary, 0, Tp, o);
+      }
+    }
     // sentinel-fill what the launch polls: the T16 copies, the hidden projection, and decin (the GRU link polls words of h)
     BLVM_HIP(pchain_fill_sentinel(rs.H16, rs.x16_bytes, s));
     BLVM_HIP(pchain_fill_sentinel(rs.GHb, sizeof(float) * n * 3 * R, s));
     BLVM_HIP(pchain_fill_sentinel(decin, sizeof(float) * n * ldd, s));  // rows 0..T'-1; row T' only receives h_n
     BLVM_HIP(copy_or_zero_2d(decin + H, sizeof(float) * ldd, h0, sizeof(float) * R, B, s));
     BLVM_TRY(pchain_rows_to_t16(h0, R, B, R, rs.H16, s));
-    return vrnn_launch(bld, true, "vrnn_fwd", s);
+    BLVM_TRY(vrnn_launch(bld, true, "vrnn_fwd", s));
+    if (fold) { ++g_dec_folded; if (folded) *folded = fold; }
+    return BLVM_OK;
   }
   for (int t = 0; t < Tp; ++t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z, oR = (size_t)t * B * R, o3R = (size_t)t * B * 3 * R;
@@ -474,6 +548,22 @@ extern "C" int blvm_vrnn_seq_fwd(const BlvmVrnnWeights* w, const float* enc, con
                                  float* reserve, void* stream_) {
   return vrnn_seq_fwd_impl(w, enc, h0, eps, Tp, B, X, H, Z, R, residual_posterior, sd_eps, decin, mu_q, sd_q, mu_p, sd_p, z, reserve,
                            static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int blvm_vrnn_seq_fwd_dec(const BlvmVrnnWeights* w, const float* enc, const float* h0, const float* eps,
+                                     int Tp, int B, int X, int H, int Z, int R, int residual_posterior, float sd_eps,
+                                     float* decin, float* mu_q, float* sd_q, float* mu_p, float* sd_p, float* z,
+                                     float* reserve, const float* const* dec_w, const float* const* dec_b, float* const* dec_y,
+                                     int DH, int SF, float slope, int* folded, void* stream_) {
+  BLVM_REQUIRE(dec_w && dec_b && dec_y && folded, "vrnn_seq_fwd_dec: null pointer");
+  VrnnDecoder d;
+  for (int l = 0; l < 3; ++l) {
+    d.w[l] = dec_w[l]; d.b[l] = dec_b[l]; d.y[l] = dec_y[l];
+    BLVM_REQUIRE(d.w[l] && d.b[l] && d.y[l] && aligned16(d.y[l]), "vrnn_seq_fwd_dec: decoder layer %d: null or unaligned pointer", l);
+  }
+  BLVM_REQUIRE(DH > 0 && SF > 0, "vrnn_seq_fwd_dec: bad decoder widths %d, %d", DH, SF);
+  return vrnn_seq_fwd_impl(w, enc, h0, eps, Tp, B, X, H, Z, R, residual_posterior, sd_eps, decin, mu_q, sd_q, mu_p, sd_p, z, reserve,
+                           static_cast<hipStream_t>(stream_), &d, DH, SF, slope, folded);
 }
 
 static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const float* eps, const float* decin,

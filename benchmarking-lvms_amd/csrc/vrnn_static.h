@@ -18,11 +18,21 @@ struct LinkRange {
 };
 // forward: the hidden projection (gentle: up to a quarter of the chip behind the halves, or with `shared` the posterior half), the
 // prior | posterior runs on a half each, heads, phi_z links and GRU from workgroup 0
+// forward, decoder range (ctD > 0: the decoder MLP's last layer has ctD column tiles): the workgroups the deal leaves free behind
+// the gentle range run the decoder of step t as a follower of the chain, four gentle links from workgroup g + def_n:
+//   dec[0]  Y1P = h_t Wd1[:, H:]^T + b1          (K = R; h_t enters step t, so this link runs ahead of the step's phi)
+//   dec[1]  Y1  = act(phi_t Wd1[:, :H]^T + Y1P)  (K = H, polled addend: the two column ranges of the first layer's K = H + R product)
+//   dec[2]  Y2  = act(Y1 Wd2^T + b2)             (K = H)
+//   dec[3]  dec = act(Y2 Wd3^T + b3)             (K = H, ctD column tiles)
+// dec[0 .. 2] keep their weights in registers and need one tile per workgroup; dec[3] reads its weights per tile, at most kMaxTiles
+// tiles per workgroup (checked in both TileIter modes: a launch's placement picks one).  The range is empty (nwg = 0 in all four)
+// when fewer than 8 workgroups are free, with the shared deal, or when a link does not fit.
+constexpr int kMaxTiles = 8;  // most tiles of a link the static walk deals one workgroup (vrnn_static.hip tile_lanes)
 struct VrnnFwdDeal {
-  int def_n, half, g;
-  LinkRange hproj, prior, post, head, phi, gru;
+  int def_n, half, g, spare;
+  LinkRange hproj, prior, post, head, phi, gru, dec[4];
 };
-inline VrnnFwdDeal vrnn_fwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, bool shared) {
+inline VrnnFwdDeal vrnn_fwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, bool shared, int ctD = 0) {
   VrnnFwdDeal d;
   d.def_n = shared ? 0 : range_for(3 * ctR * tl, std::min(cus / 4, 64));
   d.half = range_for(ctH * tl, (cus - d.def_n) / 2);  // prior | posterior halves of a link
@@ -34,6 +44,18 @@ inline VrnnFwdDeal vrnn_fwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, boo
   d.head = LinkRange{ctZ, 0, range_for(ctZ * tl, wide)};
   d.phi = LinkRange{ctH, 0, range_for(ctH * tl, wide)};
   d.gru = LinkRange{ctR, 0, range_for(ctR * tl, d.g)};
+  d.spare = shared ? 0 : cus - d.g - d.def_n;
+  for (LinkRange& r : d.dec) r = LinkRange{0, 0, 0};
+  if (ctD > 0 && d.spare >= 8) {
+    const int w0 = d.g + d.def_n, n12 = range_for(ctH * tl, d.spare), n3 = range_for(ctD * tl, d.spare);
+    bool fits = true;
+    for (bool xcd : {false, true})
+      fits = fits && tiles_per_workgroup(tl, ctH, n12, xcd) <= 1 && tiles_per_workgroup(tl, ctD, n3, xcd) <= kMaxTiles;
+    if (fits) {
+      d.dec[0] = d.dec[1] = d.dec[2] = LinkRange{ctH, w0, n12};
+      d.dec[3] = LinkRange{ctD, w0, n3};
+    }
+  }
   return d;
 }
 // backward: GRU backward; dphi as one link or (split3: a third range is free) three K = R partial-sum links side by side; GB
@@ -68,6 +90,9 @@ inline VrnnBwdDeal vrnn_bwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, boo
 // The gentle links (forward 0: hidden projection; backward 4: GB) deal several tiles per workgroup and read theirs per tile.
 constexpr std::initializer_list<int> kFwdResident = {1, 2, 3, 4, 5};
 constexpr std::initializer_list<int> kBwdResident = {0, 1, 2, 3, 5, 6, 7, 8, 9};
+// the forward program with the decoder range: descriptors 6 .. 9 are dec[0 .. 3] of the deal; the first three are resident too
+constexpr int kFwdDesc = 6, kFwdDecDesc = 10;
+constexpr std::initializer_list<int> kFwdDecResident = {6, 7, 8};
 // the converter's condition: every resident link deals a workgroup at most one tile (else the interpreter runs the program)
 // (xcd: the TileIter mode the kernel will deal with — the program's own, or plain under a placement of the launch, below)
 inline bool one_tile_each(const Program& p, std::initializer_list<int> links, bool xcd) {

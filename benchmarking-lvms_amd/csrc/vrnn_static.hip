@@ -38,7 +38,7 @@ struct SPtr {
 
 // A workgroup's tiles of one link, dealt by pchain.h's TileIter exactly as the interpreter deals them: lane k < kMaxTiles of the
 // returned value holds tile k as r0 | column tile << 16 (-1: none), so a tile costs one v_readlane in the step loop.
-constexpr int kMaxTiles = 8;
+// (kMaxTiles: vrnn_static.h)
 // the workgroup of the deal this block is under the launch's placement (vrnn_static.h)
 __device__ __forceinline__ int placed_wg(int place) { return place == kPlaceLocal ? place_wg((int)blockIdx.x) : (int)blockIdx.x; }
 __device__ __forceinline__ int tile_lanes(int w, int wg0, int nwg, int rt, int ct, bool xcd) {
@@ -266,7 +266,10 @@ __device__ __forceinline__ void load_grub(Res<kH, 2>& r, const GrubArgs& q, int 
 typedef PaceK<VRNN_PACE_EARLY, VRNN_PACE_EPI> Paced;
 
 // WS: Res<K> — the link's one tile on resident weights; WMem — every tile the deal gives, weights read per tile
-template <int NW, int K, int FLAGS, class PC = PaceOff, class WS>
+// ROW_ONCE: the canary wait only in front of the first tile of a row tile.  A workgroup's tiles of a visit that share their row tile
+// read the same [16, K] slab (with four row tiles on a range of 8 k workgroups: all of them), and once its canary words have arrived
+// the later tiles' operand polls succeed at once; a canary per tile is a round trip and a barrier each for nothing.
+template <int NW, int K, int FLAGS, class PC = PaceOff, bool ROW_ONCE = false, class WS>
 __device__ __forceinline__ void visit_lin(const LinArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const WS& ws) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
   constexpr bool sum3 = (FLAGS & DF_A_SUM3) != 0;
@@ -278,9 +281,13 @@ __device__ __forceinline__ void visit_lin(const LinArgs& q, const Deal& d, int s
     return LinLate{q.bias, q.add.at(s), q.gate.at(s), q.ld1, q.ld2, (FLAGS & DF_ADD_POLLED) != 0, (FLAGS & DF_RELU) != 0, q.slope,
                    Out{q.orm.at(s), q.ld3, (FLAGS & DF_RM_SC1) != 0, q.o16.at(s), q.n16, q.o16b.at(s), q.n16b}};
   };
+  int seen_r0 = -1;  // (wave-uniform, as tr0: the branch around the canary's barrier is uniform)
   for (int tk = 0; tk < (WS::resident ? 1 : nt); ++tk) {
     const int trc = __builtin_amdgcn_readlane(tiles, tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
-    if constexpr ((FLAGS & DF_CANARY) != 0) canary_wait(A, tr0, K, wk.pl, q.ld0);
+    if constexpr ((FLAGS & DF_CANARY) != 0) {
+      if (!ROW_ONCE || tr0 != seen_r0) canary_wait(A, tr0, K, wk.pl, q.ld0);
+      seen_r0 = tr0;
+    }
     ANAT(anat_arm(wk.pl);)
     tile_lin_late<NW, OP_F32>(A, q.ld0, true, q.W, K, late, tr0, tc0, wk.B, wk.red(), wk.pl, A2, A3, q.w_width, ws, PC());
     ANAT(anat_note(wk.anat, 4 * d.idx, wk.pl);)
@@ -384,14 +391,17 @@ __device__ __forceinline__ const A& kargs() {
 }
 
 // Forward program (vrnn.hip vrnn_seq_fwd_impl, own range for the hidden projection): 0 hidden projection (gentle, K = R), 1 prior
-// run (K = R, H, H), 2 posterior run (the same with the x-part addend), 3 heads, 4 phi_z run of four, 5 GRU.
+// run (K = R, H, H), 2 posterior run (the same with the x-part addend), 3 heads, 4 phi_z run of four, 5 GRU; with the decoder range
+// (ndec = 4, vrnn_static.h) 6 .. 9 the decoder MLP's four gentle links behind the gentle range.
 struct FwdArgs {
   LinArgs hproj;
   SeqArgs run[2];  // prior, posterior
   HeadArgs head;
   SeqArgs phi;
   GruArgs gru;
-  Deal deal[6];
+  LinArgs dec[4];
+  Deal deal[kFwdDecDesc];
+  int ndec;  // 0 | 3 | 4 (the last layer's Deal stays empty)
   int B, s0, S, xcd, place;  // place: vrnn_static.h Place
   Ctl ctl;
   ANAT(unsigned long long* prof;)
@@ -425,6 +435,30 @@ __device__ __forceinline__ void fwd_half(const FwdArgs& a, int w, int rt, bool x
   ANAT(anat_end(wk.anat, kargs<FwdArgs>().prof, HALF, w == kargs<FwdArgs>().deal[1 + HALF].wg0);)
 }
 
+// a workgroup of the decoder range: a follower of the chain.  Step t's decoder row needs [phi_t | h_t] only, so nothing the critical
+// roles poll is written here.  The first layer's two column ranges and the second layer run on resident weights (one tile each: the
+// converter checks it), the last layer's up to kMaxTiles tiles read theirs per tile.
+constexpr int kDecFlags = DF_RELU | DF_GENTLE | DF_CANARY;
+template <int NW>
+__device__ __forceinline__ void fwd_dec(const FwdArgs& a, int w, int rt, bool xcd, Walk& wk) {
+  const int t6 = tile_lanes(w, a.deal[6].wg0, a.deal[6].nwg, rt, a.deal[6].ct, xcd), n6 = tile_count(t6);
+  const int t7 = tile_lanes(w, a.deal[7].wg0, a.deal[7].nwg, rt, a.deal[7].ct, xcd), n7 = tile_count(t7);
+  const int t8 = tile_lanes(w, a.deal[8].wg0, a.deal[8].nwg, rt, a.deal[8].ct, xcd), n8 = tile_count(t8);
+  const int t9 = tile_lanes(w, a.deal[9].wg0, a.deal[9].nwg, rt, a.deal[9].ct, xcd), n9 = tile_count(t9);
+  if ((n6 | n7 | n8 | n9) == 0) return;
+  Res<kR> w1h;
+  Res<kH> w1p, w2;
+  load_lin<NW, kR>(w1h, kargs<FwdArgs>().dec[0].W, kargs<FwdArgs>().dec[0].w_width, t6, n6);
+  load_lin<NW, kH>(w1p, kargs<FwdArgs>().dec[1].W, kargs<FwdArgs>().dec[1].w_width, t7, n7);
+  load_lin<NW, kH>(w2, kargs<FwdArgs>().dec[2].W, kH, t8, n8);
+  for (int s = a.s0; s < a.S; ++s) {
+    visit_lin<NW, kR, DF_RM_SC1 | DF_GENTLE | DF_CANARY>(kargs<FwdArgs>().dec[0], kargs<FwdArgs>().deal[6], s, t6, n6, wk, w1h);
+    visit_lin<NW, kH, DF_ADD_POLLED | kDecFlags>(kargs<FwdArgs>().dec[1], kargs<FwdArgs>().deal[7], s, t7, n7, wk, w1p);
+    visit_lin<NW, kH, kDecFlags>(kargs<FwdArgs>().dec[2], kargs<FwdArgs>().deal[8], s, t8, n8, wk, w2);
+    visit_lin<NW, kH, kDecFlags, PaceOff, true>(kargs<FwdArgs>().dec[3], kargs<FwdArgs>().deal[9], s, t9, n9, wk, WMem());
+  }
+}
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_fwd_kernel(FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds_red[];
@@ -432,7 +466,12 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_fwd_kernel(FwdArgs a) 
   const bool xcd = a.place == kPlaceProgram && a.xcd != 0;
   Walk wk{lds_red, lds_red + kFwdProducts * NW * 256, 0, a.B, Poll{a.ctl, 0u, false, 1}};
   ANAT(__shared__ unsigned anat[kAnatSlots * 8]; anat_begin(anat); wk.anat = anat;)
-  // roles, picked once: the gentle range runs the hidden projection alone, the others are a half's workgroups (fwd_half)
+  // roles, picked once: the decoder range (if any) follows the chain, the gentle range runs the hidden projection alone, the others
+  // are a half's workgroups (fwd_half)
+  if (a.ndec != 0 && w >= a.deal[6].wg0) {
+    fwd_dec<NW>(a, w, rt, xcd, wk);
+    return;
+  }
   if (w >= a.deal[0].wg0) {
     const int t0 = tile_lanes(w, a.deal[0].wg0, a.deal[0].nwg, rt, a.deal[0].ct, xcd), n0 = tile_count(t0);
     if (n0 == 0) return;
@@ -630,10 +669,11 @@ int vrnn_static_check(const Program& p, int ndesc, int products, int prior, int 
 
 int vrnn_static_fwd(const Program& p, hipStream_t stream) {
   int place = kPlaceProgram;
-  if (vrnn_static_check(p, 6, kFwdProducts, 1, 2, &place)) return 1;
+  const bool dec = p.ndesc == kFwdDecDesc || p.ndesc == kFwdDecDesc - 1;  // with the decoder range (all three layers | the first two)
+  if (vrnn_static_check(p, dec ? p.ndesc : kFwdDesc, kFwdProducts, 1, 2, &place)) return 1;
   const Desc* d = p.d;
   const int S = p.S;
-  for (int i = 0; i < 6; ++i)
+  for (int i = 0; i < p.ndesc; ++i)
     if (d[i].s_begin != 0 || d[i].s_end != S) return 1;
   if (!shaped(d[0], K_LIN, DF_RM_SC1 | DF_GENTLE | DF_CANARY, kR) || !shaped(d[1], K_LINSEQ, DF_RELU, kH) || !shaped(d[2], K_LINSEQ, DF_RELU, kH) ||
       !shaped(d[3], K_HEAD, 0, kH) || !shaped(d[4], K_LINSEQ, DF_RELU, kH) || !shaped(d[5], K_GRU, 0, kH))
@@ -643,8 +683,22 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
   // roles: prior half [0, d1 end) | posterior half [d2.wg0, d0.wg0) | gentle range [d0.wg0, ...): nothing else there
   const int half = d[2].wg0, gentle = d[0].wg0;
   if (d[1].wg0 != 0 || !within(d[1], 0, half) || !within(d[2], half, gentle) || d[0].nwg <= 0) return 1;
+  if (dec && !within(d[0], gentle, d[6].wg0)) return 1;
   for (int i = 3; i < 6; ++i)
     if (!within(d[i], 0, gentle)) return 1;
+  if (dec) {
+    // the decoder's links: plain single-operand K_LIN, the first layer as the two K-ranges of rows kH + kR wide, all from the first
+    // workgroup behind the gentle range, the resident three on one tile per workgroup
+    const int from = gentle + d[0].nwg;
+    if (!shaped(d[6], K_LIN, DF_RM_SC1 | DF_GENTLE | DF_CANARY, kR) || !shaped(d[7], K_LIN, DF_ADD_POLLED | kDecFlags, kH) ||
+        !shaped(d[8], K_LIN, kDecFlags, kH) || (p.ndesc == kFwdDecDesc && !shaped(d[9], K_LIN, kDecFlags, kH)))
+      return 1;
+    for (int i = 6; i < p.ndesc; ++i) {
+      if (d[i].wg0 != from || d[i].ld[LIN_LD_A] != 0 || d[i].p[LIN_A2] || d[i].p[LIN_A3] || d[i].p[LIN_O16B] || d[i].p[LIN_GATE]) return 1;
+      if (d[i].i[LIN_I_W_WIDTH] != (i < 8 ? kH + kR : 0)) return 1;
+    }
+    if (!one_tile_each(p, kFwdDecResident, place_xcd(place, p))) return 1;
+  }
   FwdArgs a{};
   a.hproj = lin_args(p, d[0]);
   a.run[0] = seq_args(p, d[1]); a.run[1] = seq_args(p, d[2]); a.phi = seq_args(p, d[4]);
@@ -656,8 +710,10 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
   a.gru = GruArgs{sp(p, g, GRU_X16), sp(p, g, GRU_XG), sp(p, g, GRU_GH), sp(p, g, GRU_HPREV), sp(p, g, GRU_HRM), sp(p, g, GRU_H16), sp(p, g, GRU_H16B),
                   sp(p, g, GRU_RG), sp(p, g, GRU_UG), sp(p, g, GRU_NG), g.p[GRU_WIH], g.p[GRU_BIH], g.ld[GRU_LD_HPREV], g.ld[LD_OUT], g.n16[N16_OUT],
                   g.n16[N16_OUTB], g.i[GRU_I_R]};
+  a.ndec = dec ? p.ndesc - kFwdDesc : 0;
+  for (int k = 0; k < a.ndec; ++k) a.dec[k] = lin_args(p, d[6 + k]);
   int grid = 0;
-  for (int i = 0; i < 6; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
+  for (int i = 0; i < p.ndesc; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.place = place; a.ctl = p.ctl;
   ANAT(a.prof = pchain_profile_buffer();)
   const size_t lds = sizeof(float) * 2 * kFwdProducts * 16 * 256;

@@ -342,6 +342,27 @@ int blvm_vrnn_seq_fwd(const BlvmVrnnWeights* w, const float* enc, const float* h
                       int X, int H, int Z, int R, int residual_posterior, float sd_eps, float* decin,
                       float* mu_q, float* sd_q, float* mu_p, float* sd_p, float* z, float* reserve, void* stream);
 
+/* The same forward with the decoder MLP of `vrnn.py:321-324` (3 x (Linear + LeakyReLU(slope)) on decin rows 0 .. Tp-1) handed down:
+ * where the launch has workgroups to spare (fp32 operands, B <= 64 on 16-row tiles, Z == H, DH == H, SF a multiple of 16, and the
+ * deal of csrc/vrnn_static.h leaves a decoder range) the three layers run inside the persistent forward launch as a follower of the
+ * chain and *folded = 3: dec_y[0] [Tp*B,DH], dec_y[1] [Tp*B,DH] and dec_y[2] [Tp*B,SF] then hold the three activations.  Otherwise
+ * *folded = 0, they are not written and the caller runs the decoder itself (K6).  Everything else is computed exactly as by
+ * blvm_vrnn_seq_fwd.  dec_w, dec_b, dec_y: host arrays of three device pointers each.
+ *   dec_w[0] [DH,H+R] (input order cat[phi_z, h]), dec_w[1] [DH,DH], dec_w[2] [SF,DH]; SF = S * (the head's features per sample).
+ *   reserve: blvm_vrnn_fwd_reserve_floats(..., DH, SF) floats, asked for under the same blvm_vrnn_dec_fold mode as the call (more than
+ *   blvm_vrnn_reserve_floats only where the call folds); blvm_vrnn_seq_bwd reads it as it reads blvm_vrnn_seq_fwd's.
+ * *folded = 2: the first two layers only (dec_y[2] is not written; the caller runs the last layer on dec_y[1]).
+ * blvm_vrnn_dec_fold(mode): 0 never folds, 1 (default; env BLVM_VRNN_DEC_FOLD) folds where it applies, 2 folds the first two layers
+ * only, negative only queries;
+ * returns the mode in effect before the call, mode -2 instead the number of forward calls that folded so far. */
+size_t blvm_vrnn_fwd_reserve_floats(int Tp, int B, int X, int H, int Z, int R, int DH, int SF);
+int blvm_vrnn_seq_fwd_dec(const BlvmVrnnWeights* w, const float* enc, const float* h0, const float* eps, int Tp, int B,
+                          int X, int H, int Z, int R, int residual_posterior, float sd_eps, float* decin,
+                          float* mu_q, float* sd_q, float* mu_p, float* sd_p, float* z, float* reserve,
+                          const float* const* dec_w, const float* const* dec_b, float* const* dec_y, int DH, int SF, float slope,
+                          int* folded, void* stream);
+int blvm_vrnn_dec_fold(int mode);
+
 /*   d_decin [Tp+1,B,H+R]: gradient wrt decin (row Tp ignored).  KL term folded in: loss += sum_b (c_raw[b] *
  *   kld[b] + c_fn[b] * kld_fn[b]) with the mask t*stride < x_sl[b] and floor fn_floor (see blvm_kl_fwd);
  *   c_raw / c_fn may be NULL (= 0).
