@@ -1,9 +1,12 @@
 """LSTMBlock: consecutive (bi)directional LSTM layers with the reference's arguments and state_dict (blvm/modules/lstm_block.py:9-82).
 
-Every direction of every layer is one K4 sequence call (`ops.lstm_sequence`, packed-sequence semantics through the lengths: zeros past
-a row's length).  The backward direction is the per-row time reversal that leaves right padding in place
-(`utils.operations.reverse_sequences`) applied before and after an unchanged K4 call.  The reversal, the concatenation or sum of
-the directions and the dropout scale are torch ops (a gather, a cat / add and a multiply per layer): no fused kernel for them yet.
+A bidirectional layer is ONE K4b call (`ops.lstm_bidir_sequence`): both directions' chains run side by side in one persistent launch
+that writes [forward | reverse] straight into the layer's [T,N,2H] output (packed-sequence semantics through the lengths: zeros past a
+row's length); the reverse direction is the per-row time reversal that leaves right padding in place
+(`utils.operations.reverse_sequences`) folded into the kernel's indexing.  `sum_directions` adds the two halves.  Shapes outside that
+call (hidden size not 128 / 256 / 384, T < 4, more tiles than the device has CUs) and unidirectional layers take one K4 sequence call
+(`ops.lstm_sequence`) per direction, the reverse one between two `reverse_sequences` gathers, joined by a cat / add.  The dropout
+scale is a torch multiply per layer.
 
 Dropout is a scale on the layer's output: `temporal_dropout=True` draws one [1,F] scale per layer and call, `(rand > p) / (1 - p)`,
 shared by every frame and row (the reference's 1-d dropout on packed data); False draws it per element.  Training mode only.
@@ -61,15 +64,23 @@ class LSTMBlock(nn.Module):
         rev_lens = sl_host  # on the host: reverse_sequences builds its index map from it without a device read-back
         x, outputs = input, []
         for i, lstm in enumerate(self.lstm_layers):
-            fwd = ops.lstm_sequence(x, None, None, lens, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)[0]
+            both = None
             if self.bidirectional:
+                both = ops.lstm_bidir_sequence(
+                    x, lens, (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0),
+                    (lstm.weight_ih_l0_reverse, lstm.weight_hh_l0_reverse, lstm.bias_ih_l0_reverse, lstm.bias_hh_l0_reverse))  # fmt: skip
+            if both is not None:
+                H = self.hidden_size
+                x = both[..., :H] + both[..., H:] if self.sum_directions else both
+            elif self.bidirectional:
+                fwd = ops.lstm_sequence(x, None, None, lens, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)[0]
                 xr = _reverse(x, rev_lens)
                 bwd = ops.lstm_sequence(xr, None, None, lens, lstm.weight_ih_l0_reverse, lstm.weight_hh_l0_reverse,
                                         lstm.bias_ih_l0_reverse, lstm.bias_hh_l0_reverse)[0]  # fmt: skip
                 bwd = _reverse(bwd, rev_lens)
                 x = fwd + bwd if self.sum_directions else torch.cat([fwd, bwd], dim=2)
             else:
-                x = fwd
+                x = ops.lstm_sequence(x, None, None, lens, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)[0]
             scale = self._scale(x, None if dropout_masks is None else dropout_masks[i])
             if scale is not None:
                 x = x * scale

@@ -874,6 +874,59 @@ def lstm_sequence(inp, h0, c0, lens_dev, Wih, Whh, bih, bhh):
     return _LSTMSeqFunction.apply(inp, h0, c0, lens_dev, Wih, Whh, bih, bhh)
 
 
+class _LSTMBidirSeqFunction(torch.autograd.Function):
+    """K4b: both directions of one bidirectional layer in one launch.  forward returns None where the call does not apply."""
+
+    @staticmethod
+    def forward(ctx, inp, lens_dev, Wih_f, Whh_f, bih_f, bhh_f, Wih_r, Whh_r, bih_r, bhh_r):
+        inp, *params = (_f32c(t) for t in (inp, Wih_f, Whh_f, bih_f, bhh_f, Wih_r, Whh_r, bih_r, bhh_r))
+        T, B, I = inp.shape
+        H = params[1].shape[1]
+        lib = load()
+        if not lib.blvm_lstm_bidir_applies(T, B, H):  # asked first: nothing is allocated for a call that would be refused
+            return None
+        f32 = dict(device=inp.device, dtype=torch.float32)
+        out = torch.empty(T, B, 2 * H, **f32)
+        reserve = torch.empty(lib.blvm_lstm_bidir_reserve_floats(T, B, H), **f32)
+        rc = lib.blvm_lstm_bidir_fwd(*(ptr(p) for p in params), ptr(inp), ptr(lens_dev), T, B, I, H, ptr(out), ptr(reserve), stream_ptr())
+        if rc == BLVM_NOT_APPLICABLE:
+            return None
+        check(rc, "blvm_lstm_bidir_fwd")
+        ctx.dims = (T, B, I, H)
+        ctx.save_for_backward(inp, lens_dev, reserve, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        T, B, I, H = ctx.dims
+        inp, lens_dev, reserve, Wih_f, Whh_f, bih_f, bhh_f, Wih_r, Whh_r, bih_r, bhh_r = ctx.saved_tensors
+        lib = load()
+        d_out = _f32c(d_out)
+        d_in = torch.empty_like(inp) if ctx.needs_input_grad[0] else None
+        grads = [torch.zeros_like(p) for p in (Wih_f, Whh_f, bih_f, bhh_f, Wih_r, Whh_r, bih_r, bhh_r)]
+        ws = torch.empty(lib.blvm_lstm_bidir_bwd_workspace_floats(T, B, H), device=inp.device, dtype=torch.float32)
+        check(
+            lib.blvm_lstm_bidir_bwd(ptr(Wih_f), ptr(Whh_f), ptr(Wih_r), ptr(Whh_r), ptr(inp), ptr(lens_dev), ptr(reserve), ptr(d_out),
+                                    T, B, I, H, ptr(d_in), *(ptr(g) for g in grads), ptr(ws), stream_ptr()),
+            "blvm_lstm_bidir_bwd",
+        )  # fmt: skip
+        return (d_in, None, *grads)
+
+
+def lstm_bidir_sequence(inp, lens_dev, fwd_params, rev_params):
+    """inp [T,B,I], lens_dev [B] int32 on the device, each params = (Wih [4H,I], Whh [4H,H], bih [4H], bhh [4H]) of one direction
+    -> out [T,B,2H] (forward | reverse halves, zeros past each row's length), both directions in one launch; or None where the
+    one-launch form does not take the shape (nothing was launched: run two `lstm_sequence` calls)."""
+    return _LSTMBidirSeqFunction.apply(inp, lens_dev, *fwd_params, *rev_params)
+
+
+def lstm_bidir_path_counts():
+    """(forward, backward) calls of this process that ran the one-launch bidirectional kernels."""
+    out = (ctypes.c_ulonglong * 2)()
+    check(load().blvm_lstm_bidir_path_counts(out), "blvm_lstm_bidir_path_counts")
+    return int(out[0]), int(out[1])
+
+
 def lstm_decode_weights(emb_lin, lstm, dec_lin, lik_lin):
     """-> (struct BlvmLstmDecodeWeights, what must stay alive while it is used)."""
     L = lstm.num_layers

@@ -475,6 +475,123 @@ extern "C" int blvm_lstm_seq_bwd(const float* Wih, const float* Whh, const float
 }
 
 // --------------------------------------------------------------------------------------------------------------------
+// Bidirectional LSTM layer, both directions in one launch (seqchain.hip lstm_bidir_*_kernel).  Each direction owns one LstmReserve /
+// LstmWs carve plus its leaving cell states; of the carve, Hs and Cs hold the states ENTERING the step of each time index (their first
+// T slabs), and DC is unused (the running cell gradient starts at zero in a register).
+namespace blvm {
+namespace {
+struct LstmBidirReserve { LstmReserve d[2]; float* Cout[2]; };
+size_t carve_lstm_bidir(float* base, int T, int B, int H, LstmBidirReserve* r) {
+  Arena ar{base};
+  LstmBidirReserve t;
+  for (int k = 0; k < 2; ++k) {
+    float* at = ar.take(carve_lstm(nullptr, T, B, H, nullptr));
+    carve_lstm(at, T, B, H, &t.d[k]);
+    t.Cout[k] = ar.take((size_t)T * B * H);
+  }
+  if (r) *r = t;
+  return ar.floats();
+}
+size_t carve_lstm_bidir_ws(float* base, int T, int B, int H, LstmWs (*w)[2]) {
+  Arena ar{base};
+  for (int k = 0; k < 2; ++k) {
+    float* at = ar.take(carve_lstm_ws(nullptr, T, B, H, nullptr));
+    if (w) carve_lstm_ws(at, T, B, H, &(*w)[k]);
+  }
+  return ar.floats();
+}
+// The one-launch form: the register-resident forward AND backward kernels take the shape (H in {128, 256, 384}), and BOTH directions'
+// tiles are resident at once — a workgroup that was never scheduled would leave the polling ones spinning.
+inline bool lstm_bidir_applies(int T, int B, int H) {
+  return seq_persistent(T, B) && (seq_regs_mask() & 3) == 3 && 4 * H <= kSeqRegsMaxKBwd && seq_regs_applies(H, 4 * H, H, B, 4) &&
+         2 * (H / 16) * ((B + 15) / 16) <= device_cus();
+}
+std::atomic<unsigned long long> g_bidir_counts[2];
+}  // namespace
+}  // namespace blvm
+
+extern "C" size_t blvm_lstm_bidir_reserve_floats(int T, int B, int H) { return carve_lstm_bidir(nullptr, T, B, H, nullptr); }
+extern "C" size_t blvm_lstm_bidir_bwd_workspace_floats(int T, int B, int H) { return carve_lstm_bidir_ws(nullptr, T, B, H, nullptr); }
+
+extern "C" int blvm_lstm_bidir_applies(int T, int B, int H) { return T > 0 && B > 0 && H > 0 && lstm_bidir_applies(T, B, H) ? 1 : 0; }
+
+extern "C" int blvm_lstm_bidir_path_counts(unsigned long long out[2]) {
+  BLVM_REQUIRE(out, "lstm_bidir_path_counts: null pointer");
+  for (int k = 0; k < 2; ++k) out[k] = g_bidir_counts[k].load(std::memory_order_relaxed);
+  return BLVM_OK;
+}
+
+extern "C" int blvm_lstm_bidir_fwd(const float* Wih_f, const float* Whh_f, const float* bih_f, const float* bhh_f, const float* Wih_r,
+                                   const float* Whh_r, const float* bih_r, const float* bhh_r, const float* in, const int32_t* lens,
+                                   int T, int B, int I, int H, float* out, float* reserve, void* stream_) {
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  BLVM_TRY(check_rnn(T, B, I, H));
+  BLVM_REQUIRE(Wih_f && Whh_f && bih_f && bhh_f && Wih_r && Whh_r && bih_r && bhh_r && in && lens && out && reserve, "lstm_bidir_fwd: null pointer");
+  BLVM_REQUIRE(aligned16(reserve) && aligned16(Whh_f) && aligned16(Whh_r), "lstm_bidir_fwd: buffers must be 16-byte aligned");
+  if (!lstm_bidir_applies(T, B, H)) return BLVM_NOT_APPLICABLE;
+  LstmBidirReserve rs;
+  carve_lstm_bidir(reserve, T, B, H, &rs);
+  const float *Wih[2] = {Wih_f, Wih_r}, *Whh[2] = {Whh_f, Whh_r}, *bih[2] = {bih_f, bih_r}, *bhh[2] = {bhh_f, bhh_r};
+  const size_t n = (size_t)T * B;
+  const long xH = (long)t16_rows(B) * H;
+  for (int k = 0; k < 2; ++k) BLVM_TRY(gemm_f32(0, 0, (int)n, 4 * H, I, in, I, Wih[k], I, rs.d[k].XG, 4 * H, bih[k], 0, 0.f, nullptr, 0, 0, 1, s));
+  const OpType seq_ot = pchain_optype(B);
+  T16PackScope pack_scope(seq_ot, s);
+  for (int k = 0; k < 2; ++k) BLVM_TRY(t16_pack_rows(Whh[k], H, 4 * H, H, rs.d[k].WhhP, s));
+  BLVM_TRY(pack_scope.flush());
+  SeqLstmBidirFwd q{};
+  for (int k = 0; k < 2; ++k) {
+    q.d[k] = SeqLstmBidirFwdDir{rs.d[k].H16, rs.d[k].WhhP, bhh[k], rs.d[k].XG, rs.d[k].Hs, rs.d[k].Cs, rs.Cout[k], rs.d[k].GATES};
+    BLVM_HIP(pchain_fill_sentinel(rs.d[k].H16 + xH, sizeof(float) * (size_t)T * xH, s));
+    BLVM_TRY(pchain_rows_to_t16(nullptr, H, B, H, rs.d[k].H16, s));  // zero initial state
+  }
+  q.lens = lens; q.out = out; q.T = T; q.B = B; q.H = H; q.ot = seq_ot;
+  BLVM_TRY(seq_lstm_bidir_fwd(q, s));
+  g_bidir_counts[0].fetch_add(1, std::memory_order_relaxed);
+  return BLVM_OK;
+}
+
+extern "C" int blvm_lstm_bidir_bwd(const float* Wih_f, const float* Whh_f, const float* Wih_r, const float* Whh_r, const float* in,
+                                   const int32_t* lens, const float* reserve, const float* d_out, int T, int B, int I, int H,
+                                   float* d_in, float* dWih_f, float* dWhh_f, float* dbih_f, float* dbhh_f, float* dWih_r,
+                                   float* dWhh_r, float* dbih_r, float* dbhh_r, float* workspace, void* stream_) {
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  BLVM_TRY(check_rnn(T, B, I, H));
+  BLVM_REQUIRE(Wih_f && Whh_f && Wih_r && Whh_r && in && lens && reserve && d_out && workspace, "lstm_bidir_bwd: null pointer");
+  BLVM_REQUIRE(aligned16(reserve) && aligned16(workspace), "lstm_bidir_bwd: buffers must be 16-byte aligned");
+  if (!lstm_bidir_applies(T, B, H)) return BLVM_NOT_APPLICABLE;
+  LstmBidirReserve rs;
+  carve_lstm_bidir(const_cast<float*>(reserve), T, B, H, &rs);
+  LstmWs ws[2];
+  carve_lstm_bidir_ws(workspace, T, B, H, &ws);
+  const float *Wih[2] = {Wih_f, Wih_r}, *Whh[2] = {Whh_f, Whh_r};
+  float *dWih[2] = {dWih_f, dWih_r}, *dWhh[2] = {dWhh_f, dWhh_r}, *dbih[2] = {dbih_f, dbih_r}, *dbhh[2] = {dbhh_f, dbhh_r};
+  const size_t n = (size_t)T * B;
+  const long x4H = (long)t16_rows(B) * 4 * H;
+  const OpType seq_ot = pchain_optype(B);
+  T16PackScope pack_scope(seq_ot, s);
+  for (int k = 0; k < 2; ++k) BLVM_TRY(t16_pack_transposed(Whh[k], H, 4 * H, H, ws[k].WhhT, s));
+  BLVM_TRY(pack_scope.flush());
+  SeqLstmBidirBwd q{};
+  for (int k = 0; k < 2; ++k) {
+    q.d[k] = SeqLstmBidirBwdDir{ws[k].DG16, ws[k].WhhT, rs.d[k].GATES, rs.d[k].Cs, rs.Cout[k], ws[k].DG};
+    BLVM_HIP(pchain_fill_sentinel(ws[k].DG16, sizeof(float) * (size_t)T * x4H, s));
+  }
+  q.lens = lens; q.dout = d_out; q.T = T; q.B = B; q.H = H; q.ot = seq_ot;
+  BLVM_TRY(seq_lstm_bidir_bwd(q, s));
+  g_bidir_counts[1].fetch_add(1, std::memory_order_relaxed);
+  // DG, Hs (the entering states) and `in` are all TIME indexed: the unidirectional driver's GEMMs, once per direction
+  for (int k = 0; k < 2; ++k) {
+    if (d_in) BLVM_TRY(gemm_f32(0, 1, (int)n, I, 4 * H, ws[k].DG, 4 * H, Wih[k], I, d_in, I, nullptr, 0, 0.f, nullptr, 0, k, 1, s));
+    if (dWih[k]) BLVM_TRY(gemm_f32(1, 1, 4 * H, I, (int)n, ws[k].DG, 4 * H, in, I, dWih[k], I, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(4 * H, I, (int)n), s, dbih[k]));
+    else if (dbih[k]) BLVM_TRY(colsum_f32((int)n, 4 * H, ws[k].DG, 4 * H, dbih[k], 1, s));
+    if (dWhh[k]) BLVM_TRY(gemm_f32(1, 1, 4 * H, H, (int)n, ws[k].DG, 4 * H, rs.d[k].Hs, H, dWhh[k], H, nullptr, 0, 0.f, nullptr, 0, 1, pick_split(4 * H, H, (int)n), s, dbhh[k]));
+    else if (dbhh[k]) BLVM_TRY(colsum_f32((int)n, 4 * H, ws[k].DG, 4 * H, dbhh[k], 1, s));
+  }
+  return BLVM_OK;
+}
+
+// --------------------------------------------------------------------------------------------------------------------
 extern "C" size_t blvm_gru_reserve_floats(int T, int B, int R) { return carve_gru(nullptr, T, B, R, nullptr); }
 extern "C" size_t blvm_gru_bwd_workspace_floats(int T, int B, int R) { return carve_gru_ws(nullptr, T, B, R, nullptr); }
 

@@ -43,6 +43,35 @@ struct SeqLstmBwd {
   pchain::Ctl ctl;
 };
 
+// Both directions of a bidirectional LSTM layer in ONE launch: twice the tiles of one direction, workgroups [0, tiles) run the forward
+// chain and [tiles, 2 tiles) the reverse one (d[0] / d[1]); the two chains share nothing but `lens`, `out` and `dout`.  Recurrence
+// step j of row b works on time index seq_time_index(j, dir, lens, b) (pchain.h): everything ROW-MAJOR that a step saves or reads —
+// xg, the state entering the step (Hin, Cin), the cell state leaving it (Cout), the gates, the gate gradients DG and the halves of
+// out / dout — sits at that TIME index, so the weight-gradient GEMMs pair DG with the input frame and with Hin by one index.  The
+// T16 hand-off slabs stay STEP indexed.  Initial states are zero and live in registers, as does the running cell gradient.
+struct SeqLstmBidirFwdDir {
+  const float *H16, *Whh, *bhh, *xg;  // T+1 T16 state slabs (slab 0: zeros), T16 weights [4H,H], [4H], [T,B,4H]
+  float *Hin, *Cin, *Cout, *gates;    // [T,B,H] x3, [T,B,4H]
+};
+struct SeqLstmBidirFwd {
+  SeqLstmBidirFwdDir d[2];
+  const int32_t* lens;
+  float* out;  // [T,B,2H]: forward in columns [0,H), reverse in [H,2H), zeros past a row's length
+  int T, B, H, ot;
+  pchain::Ctl ctl;
+};
+struct SeqLstmBidirBwdDir {
+  const float *DG16, *WhhT, *gates, *Cin, *Cout;  // DG16: T+1 T16 slabs indexed by s (slab s written at step s)
+  float* DG;                                      // [T,B,4H] time indexed
+};
+struct SeqLstmBidirBwd {
+  SeqLstmBidirBwdDir d[2];
+  const int32_t* lens;
+  const float* dout;  // [T,B,2H]
+  int T, B, H, ot;
+  pchain::Ctl ctl;
+};
+
 // whether the register-resident kernels take a sequence: K a multiple of 128 (every wave the same number of k-chunks), at most one
 // tile per CU, and a chunk count that was instantiated
 bool seq_regs_applies(int K_fwd, int K_bwd, int hidden, int B, int gates);
@@ -52,5 +81,8 @@ int seq_gru_fwd(SeqGruFwd a, hipStream_t s);
 int seq_gru_bwd(SeqGruBwd a, hipStream_t s);
 int seq_lstm_fwd(SeqLstmFwd a, hipStream_t s);
 int seq_lstm_bwd(SeqLstmBwd a, hipStream_t s);
+// grid = 2 (H/16) ceil(B/16): the caller has checked that it fits the device (every workgroup of a polling launch must be resident)
+int seq_lstm_bidir_fwd(SeqLstmBidirFwd a, hipStream_t s);
+int seq_lstm_bidir_bwd(SeqLstmBidirBwd a, hipStream_t s);
 
 }  // namespace blvm

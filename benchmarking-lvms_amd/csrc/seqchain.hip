@@ -226,6 +226,123 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_bwd_kernel(SeqLstmBwd a) {
   if (own) a.DC[o] = dc;
 }
 
+// ---- both directions of a bidirectional LSTM layer in one launch (seqchain.h) ---------------------------------------------------
+// The workgroup's direction and tile, once at entry.  tiles = (H/16) rt is a multiple of 8 rt for the widths these kernels take, so
+// blockIdx % 8 still fixes the row tile (what the SHARED product of the backward kernel relies on) and every XCD serves both chains.
+struct BidirAt { int dir, r0, c0; };
+__device__ __forceinline__ BidirAt my_bidir_tile(int B, int H) {
+  const int rt = (B + 15) / 16, tiles = (H / 16) * rt;
+  const int dir = (int)blockIdx.x >= tiles ? 1 : 0, tile = (int)blockIdx.x - dir * tiles;
+  return BidirAt{dir, (tile % rt) * 16, (tile / rt) * 16};
+}
+// seq_time_index (pchain.h) with the row's length already in a register
+__device__ __forceinline__ int bidir_time_index(int j, int dir, int len) { return dir != 0 && j < len ? len - 1 - j : j; }
+
+// The arithmetic of lstm_fwd_kernel, product for product; h and c of this thread's element stay in registers for the whole sequence.
+template <int OT, int NCH>
+__global__ __launch_bounds__(NW * 64, 1) void lstm_bidir_fwd_kernel(SeqLstmBidirFwd a) {
+  __shared__ float red[2][4 * NW * 256];
+  const BidirAt tl = my_bidir_tile(a.B, a.H);
+  const SeqLstmBidirFwdDir q = a.d[tl.dir];
+  const int H = a.H, B = a.B, r0 = tl.r0, c0 = tl.c0, dir = tl.dir;
+  const int tt = threadIdx.x & 255, row = r0 + (tt >> 4), col = c0 + (tt & 15);
+  const bool own = threadIdx.x < 256 && row < B;
+  const int rowc = row < B ? row : r0;
+  const size_t o = (size_t)rowc * H + col, o4 = (size_t)rowc * 4 * H + col, sH = (size_t)B * H, xH = (size_t)((B + 15) / 16) * 16 * H;
+  const size_t oo2 = (size_t)rowc * 2 * H + (size_t)dir * H + col;
+  typename WFrag<OT>::type w[4][NCH];
+  {
+    const int cs[4] = {c0, H + c0, 2 * H + c0, 3 * H + c0};
+    load_w<OT, 4, NCH>(w, q.Whh, cs, H);
+  }
+  const float b0 = q.bhh[col], b1 = q.bhh[H + col], b2 = q.bhh[2 * H + col], b3 = q.bhh[3 * H + col];
+  const int len = min(max(a.lens[rowc], 0), a.T);
+  float cp = 0.f, hp = 0.f;
+  Poll pl{a.ctl, 0u, false, 1};
+  for (int t = 0; t < a.T; ++t) {
+    pl.code = ((unsigned)t << 4) | 5u;
+    const int idx = bidir_time_index(t, dir, len);
+    float x0 = 0.f, x1 = 0.f, x2 = 0.f, x3 = 0.f;
+    auto prefetch = [&]() {
+      const float* xg = q.xg + (size_t)idx * 4 * sH;
+      x0 = xg[o4] + b0; x1 = xg[o4 + H] + b1; x2 = xg[o4 + 2 * H] + b2; x3 = xg[o4 + 3 * H] + b3;
+    };
+    f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    product<OT, 4, NCH, false>(q.H16 + (size_t)t * xH, r0, B, H, w, acc, pl, prefetch);
+    float v[4];
+    reduce_tiles<4, NW>(acc, red[t & 1], v);
+    if (!own) continue;
+    const bool live = t < len;
+    const float i = sigmoidf_(v[0] + x0), f = sigmoidf_(v[1] + x1), g = tanhf(v[2] + x2), og = sigmoidf_(v[3] + x3);
+    const float c2 = f * cp + i * g;
+    const float h2 = og * tanhf(c2);
+    const float cn = live ? c2 : cp, hn = live ? h2 : hp;
+    const Out oo{nullptr, H, false, const_cast<float*>(q.H16) + (size_t)(t + 1) * xH, H / 16};
+    put_t16(oo, r0, c0, row, col, hn);  // the hand-off first; the saves below sit at the row's TIME index
+    const size_t os = (size_t)idx * sH + o;
+    q.Hin[os] = hp; q.Cin[os] = cp; q.Cout[os] = cn;
+    a.out[(size_t)idx * 2 * sH + oo2] = live ? h2 : 0.f;
+    float* gt = q.gates + (size_t)idx * 4 * sH;
+    gt[o4] = live ? i : 0.f; gt[o4 + H] = live ? f : 0.f; gt[o4 + 2 * H] = live ? g : 0.f; gt[o4 + 3 * H] = live ? og : 0.f;
+    cp = cn; hp = hn;
+  }
+}
+
+template <int OT, int NCH>
+__global__ __launch_bounds__(NW * 64, 1) void lstm_bidir_bwd_kernel(SeqLstmBidirBwd a) {
+  __shared__ float red[2][NW * 256];
+  const BidirAt tl = my_bidir_tile(a.B, a.H);
+  const SeqLstmBidirBwdDir q = a.d[tl.dir];
+  const int H = a.H, B = a.B, T = a.T, r0 = tl.r0, c0 = tl.c0, dir = tl.dir;
+  const int tt = threadIdx.x & 255, row = r0 + (tt >> 4), col = c0 + (tt & 15);
+  const bool own = threadIdx.x < 256 && row < B;
+  const int rowc = row < B ? row : r0;
+  const size_t o = (size_t)rowc * H + col, o4 = (size_t)rowc * 4 * H + col, sH = (size_t)B * H, x4H = (size_t)((B + 15) / 16) * 16 * 4 * H;
+  const size_t oo2 = (size_t)rowc * 2 * H + (size_t)dir * H + col;
+  typename WFrag<OT>::type w[1][NCH];
+  {
+    const int cs[1] = {c0};
+    load_w<OT, 1, NCH>(w, q.WhhT, cs, 4 * H);
+  }
+  const int len = min(max(a.lens[rowc], 0), T);
+  Poll pl{a.ctl, 0u, false, 1};
+  float dc = 0.f;  // running gradient wrt the cell state
+  for (int s = 0; s < T; ++s) {
+    const int j = T - 1 - s, idx = bidir_time_index(j, dir, len);
+    const bool has_gemm = s >= 1;
+    pl.code = ((unsigned)s << 4) | 6u;
+    float dh = 0.f, ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, cs = 0.f, cs1 = 0.f;
+    auto prefetch = [&]() {
+      dh = a.dout[(size_t)idx * 2 * sH + oo2];
+      const float* gt = q.gates + (size_t)idx * 4 * sH;
+      ig = gt[o4]; fg = gt[o4 + H]; gg = gt[o4 + 2 * H]; og = gt[o4 + 3 * H];
+      cs = q.Cin[(size_t)idx * sH + o]; cs1 = q.Cout[(size_t)idx * sH + o];
+    };
+    float v[1] = {0.f};
+    if (has_gemm) {  // uniform
+      f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
+      product<OT, 1, NCH, (NCH >= 12)>(q.DG16 + (size_t)(s - 1) * x4H, r0, B, 4 * H, w, acc, pl, prefetch);
+      reduce_tiles<1, NW>(acc, red[s & 1], v);
+    } else {
+      prefetch();
+    }
+    if (!own) continue;
+    dh += v[0];
+    const float tc = tanhf(cs1);
+    const float d_o = dh * tc;
+    const float dct = dc + dh * og * (1.f - tc * tc);
+    const float di = dct * gg * ig * (1.f - ig), df = dct * cs * fg * (1.f - fg), dg = dct * ig * (1.f - gg * gg), dog = d_o * og * (1.f - og);
+    const Out od{nullptr, 4 * H, false, const_cast<float*>(q.DG16) + (size_t)s * x4H, 4 * H / 16};
+    put_t16(od, r0, c0, row, col, di);
+    put_t16(od, r0, H + c0, row, H + col, df);
+    put_t16(od, r0, 2 * H + c0, row, 2 * H + col, dg);
+    put_t16(od, r0, 3 * H + c0, row, 3 * H + col, dog);
+    float* dgt = q.DG + (size_t)idx * 4 * sH;  // row-major at the row's TIME index: a per-row address, so not through put()
+    dgt[o4] = di; dgt[o4 + H] = df; dgt[o4 + 2 * H] = dg; dgt[o4 + 3 * H] = dog;
+    dc = dct * fg;
+  }
+}
+
 inline bool nch_ok(int nch) { return nch == 1 || nch == 2 || nch == 3 || nch == 4 || nch == 6 || nch == 8 || nch == 12; }
 
 #define SEQ_LAUNCH_OT(kernel, N, ot, grid, s, args)                                                                  \
@@ -286,6 +403,20 @@ int seq_lstm_bwd(SeqLstmBwd a, hipStream_t s) {
   const dim3 grid((unsigned)((a.H / 16) * ((a.B + 15) / 16)));
   SEQ_LAUNCH(lstm_bwd_kernel, 4 * a.H / (NW * 16), a.ot, grid, s, a);
   BLVM_CHECK_LAUNCH("seq_lstm_bwd");
+  return BLVM_OK;
+}
+int seq_lstm_bidir_fwd(SeqLstmBidirFwd a, hipStream_t s) {
+  BLVM_TRY(pchain_ctl(a.ctl));
+  const dim3 grid((unsigned)(2 * (a.H / 16) * ((a.B + 15) / 16)));
+  SEQ_LAUNCH(lstm_bidir_fwd_kernel, a.H / (NW * 16), a.ot, grid, s, a);
+  BLVM_CHECK_LAUNCH("seq_lstm_bidir_fwd");
+  return BLVM_OK;
+}
+int seq_lstm_bidir_bwd(SeqLstmBidirBwd a, hipStream_t s) {
+  BLVM_TRY(pchain_ctl(a.ctl));
+  const dim3 grid((unsigned)(2 * (a.H / 16) * ((a.B + 15) / 16)));
+  SEQ_LAUNCH(lstm_bidir_bwd_kernel, 4 * a.H / (NW * 16), a.ot, grid, s, a);
+  BLVM_CHECK_LAUNCH("seq_lstm_bidir_bwd");
   return BLVM_OK;
 }
 

@@ -392,6 +392,38 @@ int blvm_lstm_seq_bwd(const float* Wih, const float* Whh, const float* in, const
                       float* dbih, float* dbhh, float* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * K4b  one BIDIRECTIONAL LSTM layer over a sequence (forward + BPTT), both directions in ONE persistent launch.
+ *     Replaces the bidirectional `nn.LSTM` layer on a packed sequence inside `LSTMBlock.forward`,
+ *     `blvm/modules/lstm_block.py:60-82`.  The reverse direction is the per-row time reversal of K2: row b consumes
+ *     time index lens[b]-1-j at recurrence step j < lens[b] (index j in its right padding, where it is not live) and
+ *     writes its output at that time index.  Gate rows [i|f|g|o]; the two directions' parameters stay separate, in
+ *     their PyTorch layouts (`weight_ih_l0`, `weight_ih_l0_reverse`, ...: `_f` / `_r` below).  Initial states are
+ *     zero; no final states are returned and no initial-state gradient is computed.
+ *   in [T,B,I]; lens [B] int32 valid steps per row (required; any order, 0 allowed)
+ *   out [T,B,2H]: forward direction in columns [0,H), reverse in [H,2H), zeros past a row's length in both halves
+ *   The one-launch form takes T >= 4, B <= 128, H in {128, 256, 384} on a device of at least 32 CUs that holds all
+ *   2 (H/16) ceil(B/16) workgroups at once.  Any other shape returns BLVM_NOT_APPLICABLE before anything is
+ *   written or launched: run two K4 calls instead.  blvm_lstm_bidir_applies answers 1 / 0 for a shape on the
+ *   current device without touching it, so a caller need not allocate for a call that would be refused.  The
+ *   two size functions are host arithmetic for any shape (for B > 128 they omit, like K4's, the operand slabs).
+ *   blvm_lstm_bidir_path_counts: out[0] / out[1] = forward / backward calls so far that ran the one-launch
+ *   kernels; these calls never move the counters of blvm_rnn_path_counts.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t blvm_lstm_bidir_reserve_floats(int T, int B, int H);
+size_t blvm_lstm_bidir_bwd_workspace_floats(int T, int B, int H);
+int blvm_lstm_bidir_fwd(const float* Wih_f, const float* Whh_f, const float* bih_f, const float* bhh_f,
+                        const float* Wih_r, const float* Whh_r, const float* bih_r, const float* bhh_r, const float* in,
+                        const int32_t* lens, int T, int B, int I, int H, float* out, float* reserve, void* stream);
+/*   d_out [T,B,2H] (its values past a row's length are ignored); d_in [T,B,I] = the sum of both directions'
+ *   contributions (may be NULL); the eight weight / bias grads ACCUMULATED (each may be NULL). */
+int blvm_lstm_bidir_bwd(const float* Wih_f, const float* Whh_f, const float* Wih_r, const float* Whh_r, const float* in,
+                        const int32_t* lens, const float* reserve, const float* d_out, int T, int B, int I, int H,
+                        float* d_in, float* dWih_f, float* dWhh_f, float* dbih_f, float* dbhh_f, float* dWih_r,
+                        float* dWhh_r, float* dbih_r, float* dbhh_r, float* workspace, void* stream);
+int blvm_lstm_bidir_applies(int T, int B, int H);
+int blvm_lstm_bidir_path_counts(unsigned long long out[2]);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * K2  single-layer GRU over a sequence (forward + BPTT), optionally time-reversed PER ROW.  Replaces `nn.GRU` and
  *     the `reverse_sequences` gathers around it, `blvm/models/srnn.py:113-116,196,200-206` +
  *     `blvm/utils/operations.py:56-87`: with reverse != 0 row b consumes time index lens[b]-1-j at recurrence step

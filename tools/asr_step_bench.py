@@ -9,7 +9,10 @@ the tool alternately on each (A B A B: a drift of the box hits both alike) with 
 `--rounds` rounds of `--steps` steps, every step between two device synchronisations; the median and min..max over all steps are
 printed as one JSON line, with the hypothesis lengths the step met (the host path's cost grows with them).  Where the tree has
 `ops.ctc_error_totals`, that call alone, and the distance launch inside it, are also timed between device events, in rounds of
-`--calls` calls."""
+`--calls` calls.
+
+`--num_layers` and `--bidirectional True|False` build the deeper probes of the reference's `experiments/phoneme.txt`
+(`--hidden_size 256 --num_layers 3 --bidirectional True`); their defaults are the one-layer unidirectional step above."""
 import argparse
 import json
 import os
@@ -33,6 +36,8 @@ def main():
     ap.add_argument("--B", type=int, default=40)
     ap.add_argument("--input_size", type=int, default=80)
     ap.add_argument("--hidden_size", type=int, default=128)
+    ap.add_argument("--num_layers", type=int, default=1)
+    ap.add_argument("--bidirectional", type=lambda v: v.lower() in ("1", "true", "yes"), default=False, metavar="True|False")
     ap.add_argument("--classes", type=int, default=62)
     ap.add_argument("--L", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
@@ -51,7 +56,7 @@ def main():
     torch.manual_seed(0)
     gen = torch.Generator().manual_seed(0)
     tm = TokenMap([chr(97 + i % 26) + chr(97 + i // 26) for i in range(a.classes - 1)], add_blank=True)  # two-letter "phonemes"
-    model = SimpleLSTMASR(tm, a.input_size, a.hidden_size, num_layers=1).to(dev).train()
+    model = SimpleLSTMASR(tm, a.input_size, a.hidden_size, num_layers=a.num_layers, bidirectional=a.bidirectional).to(dev).train()
     # lr = 0: the optimiser does its work and the weights stay, so that every timed step meets the same transcripts (a few real
     # steps on one batch collapse the untrained model to blanks, and an empty hypothesis costs the host path nothing)
     opt = torch.optim.Adam(model.parameters(), lr=0.0)
@@ -90,7 +95,8 @@ def main():
     read_ms = (time.perf_counter() - t0) * 1e3
 
     res = dict(package=os.path.relpath(os.path.abspath(a.package), os.path.join(HERE, "..")),
-               shape=dict(T=a.T, B=a.B, input=a.input_size, hidden=a.hidden_size, classes=a.classes, L=a.L), steps=len(times),
+               shape=dict(T=a.T, B=a.B, input=a.input_size, hidden=a.hidden_size, layers=a.num_layers, bidirectional=a.bidirectional,
+                          classes=a.classes, L=a.L), steps=len(times),
                step_ms=spread(times), tracker_read_ms=round(read_ms, 3), wer=round(values["wer"], 4), cer=round(values["cer"], 4),
                hyp_tokens=dict(mean=round(statistics.mean(hyp_tokens), 1), max=max(hyp_tokens)))  # fmt: skip
     if hasattr(ops, "ctc_error_totals"):
