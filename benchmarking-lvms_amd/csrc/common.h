@@ -373,7 +373,8 @@ int pchain_ctl(unsigned** dev, unsigned** host_dev, unsigned* epoch);
 // kernels fit better.
 int pchain_max_batch();
 int pchain_tune();  // placement bits (env BLVM_PCHAIN_TUNE / blvm_pchain_tune): 4 XCD-aware tile placement, 16 canary polls of deferred tiles,
-                     // 32 / 64 placement of the static walks' launches (vrnn_static.h Place: plain / local where it applies)
+                     // 32 / 64 placement of the static walks' launches (vrnn_static.h Place: plain / local where it applies),
+                     // 128 no look-ahead arming in the static walks: the host fills every polled slab (vrnn_static.h kArmAhead)
 unsigned long long* pchain_profile_buffer();  // diagnostics: null unless blvm_pchain_profile() installed a device buffer
 
 // internal launchers shared between translation units (defined in gemm.hip)

@@ -22,6 +22,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdlib>
+#include <functional>
 
 #include "common.h"
 #include "decode_tiles.h"
@@ -1450,8 +1451,12 @@ inline int pchain_launch(pchain::Builder& bld, const char* who, hipStream_t stre
   return pchain_run(bld.p, stream);
 }
 // the VRNN forward / backward program on the static-walk kernels (vrnn_static.hip), or on the interpreter when it is not the shape they
-// were compiled for or after blvm_pchain_static(0)
-int vrnn_launch(pchain::Builder& bld, bool forward, const char* who, hipStream_t stream);
+// were compiled for or after blvm_pchain_static(0).  The launch decides how the polled buffers get their sentinels, because only
+// here is it known which of the two runs (vrnn_static.h ArmPlan): an armed static walk fills walk steps [0, kArmAhead) of the plan's
+// table and arms the rest itself, everything else fills the plan's full regions.  `pre` then enqueues the caller's writes into
+// polled memory (the initial state: step 0 only), behind the fill and in front of the launch.
+namespace pchain { struct ArmPlan; }
+int vrnn_launch(pchain::Builder& bld, bool forward, const char* who, hipStream_t stream, const pchain::ArmPlan& plan, const std::function<int()>& pre);
 // dst = T16 copy [ceil(B/16)*16, K] of the rows of src [B, K] (row stride ld; null: zeros); rows >= B are left alone (never read).
 // n16 > 0: dst is a slab of n16 blocks per row tile (a concatenation; dst points at this part's first block)
 // k_src > 0: src has only k_src < K columns, the columns k_src .. K-1 of dst are zeros (a padded frame stack)

@@ -382,8 +382,8 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   }
   BLVM_TRY(pack_scope.flush());  // all packs above in one launch
 
-  // initial state -> h-part of decin row 0
-  BLVM_HIP(copy_or_zero_2d(decin + H, sizeof(float) * ldd, h0, sizeof(float) * R, B, s));
+  // initial state -> h-part of decin row 0 (the persistent path writes it behind its sentinel fill of decin, below)
+  if (!(vrnn_persistent(B) && device_cus() >= 32)) BLVM_HIP(copy_or_zero_2d(decin + H, sizeof(float) * ldd, h0, sizeof(float) * R, B, s));
   // the phi-part of the extra row T' has no producer (there is no step T'): zeros, so that no word of decin keeps the caller's bytes
   BLVM_HIP(hipMemset2DAsync(decin + n * ldd, sizeof(float) * ldd, 0, sizeof(float) * H, B, s));
 
@@ -479,13 +479,28 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
         add_desc(bld, K_LIN, dl.dec[3].ct, dl.dec[3].wg0, dl.dec[3].nwg, H, DF_RELU | DF_GENTLE | canary, 0, Tp, o);
       }
     }
-    // sentinel-fill what the launch polls: the T16 copies, the hidden projection, and decin (the GRU link polls words of h)
-    BLVM_HIP(pchain_fill_sentinel(rs.H16, rs.x16_bytes, s));
-    BLVM_HIP(pchain_fill_sentinel(rs.GHb, sizeof(float) * n * 3 * R, s));
-    BLVM_HIP(pchain_fill_sentinel(decin, sizeof(float) * n * ldd, s));  // rows 0..T'-1; row T' only receives h_n
-    BLVM_HIP(copy_or_zero_2d(decin + H, sizeof(float) * ldd, h0, sizeof(float) * R, B, s));
-    BLVM_TRY(pchain_rows_to_t16(h0, R, B, R, rs.H16, s));
-    BLVM_TRY(vrnn_launch(bld, true, "vrnn_fwd", s));
+    // what the launch polls gets sentinels: the T16 copies, the hidden projection, and decin (the GRU link polls words of h).  Who
+    // stores them is the launch's decision (vrnn_static.h ArmPlan): the full regions, or the table's buffers slab by slab.
+    ArmPlan plan;
+    plan.fill(rs.H16, rs.x16_bytes);
+    plan.fill(rs.GHb, sizeof(float) * n * 3 * R);
+    plan.fill(decin, sizeof(float) * n * ldd);  // rows 0..T'-1; row T' only receives h_n
+    if (!groups) {
+      plan.add(arm_t16(rs.H16, R, rt, Tp + 1));
+      for (int i = 0; i < 3; ++i) { plan.add(arm_t16(rs.P16[i], H, rt, Tp)); plan.add(arm_t16(rs.Q16[i], H, rt, Tp)); plan.add(arm_t16(rs.FZ16[i], H, rt, Tp)); }
+      plan.add(arm_t16(rs.Z16, Z, rt, Tp));
+      plan.add(arm_t16(rs.PHI16, H, rt, Tp));
+      plan.add(arm_t16(rs.Y116, H, rt, Tp)); plan.add(arm_t16(rs.Y216, H, rt, Tp));  // (null without the decoder range: not added)
+      plan.add(arm_rm(rs.Y1P, H, B, Tp));
+      plan.add(arm_rm(rs.GHb, 3 * R, B, Tp));
+      plan.add(arm_rm(decin, ldd, B, Tp));
+    }
+    // the initial state is step 0's operand: both writes go behind the fill
+    auto pre = [&]() -> int {
+      BLVM_HIP(copy_or_zero_2d(decin + H, sizeof(float) * ldd, h0, sizeof(float) * R, B, s));
+      return pchain_rows_to_t16(h0, R, B, R, rs.H16, s);
+    };
+    BLVM_TRY(vrnn_launch(bld, true, "vrnn_fwd", s, plan, pre));
     if (fold) { ++g_dec_folded; if (folded) *folded = fold; }
     return BLVM_OK;
   }
@@ -743,9 +758,19 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       add_linseq(bld, ctH, dl.prior.wg0, dl.prior.nwg, H, false, true, 0, T, last(ws.DPH16, x2Z), 3, lp, -sH, -xH, ctH, 0.f, H, 2 * Z);
       add_linseq(bld, ctH, dl.post.wg0, dl.post.nwg, H, false, true, 0, T, last(ws.DQH16, x2Z), 3, lq, -sH, -xH, ctH, 0.f, H, 2 * Z);
     }
-    // sentinel-fill what the launch polls: GA, GB (single words) and the T16 copies
-    BLVM_HIP(pchain_fill_sentinel(ws.GA, ws.x16_bytes, s));
-    BLVM_TRY(vrnn_launch(bld, false, "vrnn_bwd", s));
+    // what the launch polls gets sentinels: GA, GB (single words) and the T16 copies, from the host or slab by slab from the walk
+    // (vrnn_static.h ArmPlan; the table's walk step j is time step T' - 1 - j)
+    ArmPlan plan;
+    plan.fill(ws.GA, ws.x16_bytes);
+    if (!groups) {
+      plan.add(arm_rm(ws.GA, R, B, T, true)); plan.add(arm_rm(ws.GB, R, B, T, true));
+      for (int i = 0; i < 3; ++i) { plan.add(arm_t16(ws.DP16[i], H, rt, T, true)); plan.add(arm_t16(ws.DQ16[i], H, rt, T, true)); }
+      plan.add(arm_t16(ws.DGI16, 3 * R, rt, T, true)); plan.add(arm_t16(ws.DGH16, 3 * R, rt, T, true));
+      for (int i = 0; i < 4; ++i) plan.add(arm_t16(ws.DPHI16[i], H, rt, T, true));
+      plan.add(arm_t16(ws.DPH16, 2 * Z, rt, T, true)); plan.add(arm_t16(ws.DQH16, 2 * Z, rt, T, true));
+      plan.add(arm_t16(ws.DPHI16b, H, rt, T, true)); plan.add(arm_t16(ws.DPHI16c, H, rt, T, true));
+    }
+    BLVM_TRY(vrnn_launch(bld, false, "vrnn_bwd", s, plan, []() -> int { return BLVM_OK; }));
     if (split3) {  // DPHI[3] += the two other partial sums
       const size_t n4 = n * H / 4;
       hipLaunchKernelGGL(add3_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, reinterpret_cast<float4*>(ws.DPHI[3]),

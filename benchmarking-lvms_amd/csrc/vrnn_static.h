@@ -1,6 +1,6 @@
 // vrnn_static.h — the host arithmetic the static walk (vrnn_static.hip) shares with its host test (tests/host/static_plan_test.hip):
 // the deal of the VRNN step programs, which of their links keep their weights in registers, and the placement of a static launch
-// (tests/host/static_place_test.hip).
+// (tests/host/static_place_test.hip), and the plan by which a static walk stores its own sentinels (tests/host/arm_plan_test.hip).
 #pragma once
 #include <algorithm>
 #include <initializer_list>
@@ -143,6 +143,125 @@ inline int grid_of(const Program& p) {
   int g = 0;
   for (int i = 0; i < p.ndesc; ++i) g = std::max(g, p.d[i].wg0 + p.d[i].nwg);
   return g;
+}
+
+// ---- look-ahead arming: the walk's idle workgroups store the sentinels of walk step s + kArmAhead ----------------------
+// The host fills the polled buffers of a persistent launch with sentinels.  Under a static walk only walk steps [0, kArmAhead) are
+// filled in front of the launch; the slabs of step s + kArmAhead are armed at step s by workgroups that wait anyway (forward: the
+// posterior half between its run and its GRU tile; backward: the spare range between its partial-sum tiles).  Three rules:
+//   1. a workgroup arms only words of the row tile its own tile of the role's link belongs to: row tiles are independent chains,
+//      and inside one every producer of step s + kArmAhead is causally behind this workgroup's next published tile;
+//   2. the stores are write-through (sc1) 16-byte stores and the wave drains them (vmcnt(0)) before its next tile publishes;
+//   3. only a program that arm_applies() has verified is armed; any other launch gets the full host fill.
+constexpr int kArmAhead = 4;
+constexpr int kArmMax = 24;        // entries of a table
+constexpr int kArmCandidates = 64;  // workgroups of an arming role (one wave ranks them with a ballot)
+// one polled buffer: walk step j's slab starts at base + j * step (floats; step < 0: the backward walks time in reverse), row tile r
+// of it at + r * tile and holds n4 16-byte words (the last row tile of a row-major buffer: n4_last); the buffer has nslabs slabs
+struct ArmEntry {
+  float* base;
+  int step, tile, n4, n4_last, nslabs;
+};
+struct ArmTable {
+  ArmEntry e[kArmMax];
+  int n;  // 0: the launch arms nothing
+};
+// a T16 slab [rt * 16, width] (1 KB blocks, a row tile is 16 * width contiguous floats) | a row-major slab [B, ld]
+// reversed: walk step j is time step nslabs - 1 - j
+inline ArmEntry arm_t16(float* buf, int width, int rt, int nslabs, bool reversed = false) {
+  const int step = rt * 16 * width;
+  return ArmEntry{reversed ? buf + (long)(nslabs - 1) * step : buf, reversed ? -step : step, 16 * width, 4 * width, 4 * width, nslabs};
+}
+inline ArmEntry arm_rm(float* buf, int ld, int B, int nslabs, bool reversed = false) {
+  const int step = B * ld, rt = (B + 15) / 16;
+  return ArmEntry{reversed ? buf + (long)(nslabs - 1) * step : buf, reversed ? -step : step, 16 * ld, 4 * ld, (B - 16 * (rt - 1)) * ld / 4, nslabs};
+}
+// what a launch's host code hands vrnn_launch: the table, and the regions of the full fill (the interpreter; unverified programs)
+struct ArmPlan {
+  ArmTable tab{};
+  struct Region { void* p; size_t bytes; } full[3] = {};
+  int nfull = 0;
+  void add(const ArmEntry& e) { if (e.base != nullptr && tab.n < kArmMax) tab.e[tab.n++] = e; else if (e.base != nullptr) tab.n = kArmMax + 1; }
+  void fill(void* p, size_t bytes) { full[nfull++] = Region{p, bytes}; }
+};
+// the armer's share of row tile r of an entry: 16-byte words [*first, *first + *count) of the row tile, armer k of n = 1 << log2n
+// (a power of two: the step loop of a walk divides by shifting)
+__host__ __device__ __forceinline__ void arm_share(const ArmEntry& e, int r, int rt, int k, int log2n, int* first, int* count) {
+  const int total = r == rt - 1 ? e.n4_last : e.n4, per = (total + (1 << log2n) - 1) >> log2n;
+  *first = k * per < total ? k * per : total;
+  *count = per < total - *first ? per : total - *first;
+}
+// the workgroups that arm: those of [cand0, cand0 + ncand) with a tile of `link`, ranked k of n among the ones of the same row tile
+// false: workgroup w does not arm
+inline bool arm_rank(const Program& p, int link, int cand0, int ncand, bool xcd, int w, int* r, int* k, int* n) {
+  const int rt = (p.B + 15) / 16;
+  const Desc& d = p.d[link];
+  TileIter mine(w, d.wg0, d.nwg, rt, d.ct, xcd);
+  if (w < cand0 || w >= cand0 + ncand || !mine.valid()) return false;
+  *r = mine.r0() / 16; *k = 0; *n = 0;
+  for (int c = cand0; c < cand0 + ncand; ++c) {
+    TileIter it(c, d.wg0, d.nwg, rt, d.ct, xcd);
+    if (!it.valid() || it.r0() != mine.r0()) continue;
+    ++*n;
+    if (c < w) ++*k;
+  }
+  return true;
+}
+// the descriptor slot of a link's polled activation operand (-1: a kind the static walks do not run)
+inline int arm_operand_slot(int kind) {
+  switch (kind) {
+    case K_LIN: return LIN_A;
+    case K_LINSEQ: return LINSEQ_A0;
+    case K_HEAD: return HEAD_P16;
+    case K_GRU: return GRU_X16;
+    case K_GRUB: return GRUB_D0_16;
+    case K_DZ: return DZ_D16;
+    default: return -1;
+  }
+}
+// Rule 3, next to one_tile_each: the converter's condition for arming a launch.  `link`: the arming role's link, whose tiles the
+// workgroups [cand0, cand0 + ncand) arm around; idle: the links those workgroups must own no tile of (they wait while others walk
+// them: the window the stores go into, and the registers — vrnn_static.hip fwd_post_arming); xcd: the launch's TileIter mode.
+//   - every link multiplies a stepped operand that lies in a buffer of the table: it polls, so nothing runs ahead of the chain;
+//   - every arming workgroup owns exactly one tile of the role's link, and every row tile has armers, a power of two of them;
+//   - every buffer of the table has the program's row-tile geometry: 16-byte aligned pieces, row tiles inside their slab.
+inline bool arm_applies(const Program& p, const ArmTable& t, int link, std::initializer_list<int> idle, int cand0, int ncand, bool xcd) {
+  const int rt = (p.B + 15) / 16;
+  if (t.n <= 0 || t.n > kArmMax || ncand <= 0 || ncand > kArmCandidates || p.S <= kArmAhead || p.rt_group != 1) return false;
+  for (int i = 0; i < t.n; ++i) {
+    const ArmEntry& e = t.e[i];
+    const long span = e.step < 0 ? -(long)e.step : e.step;
+    if (e.base == nullptr || (reinterpret_cast<unsigned long long>(e.base) & 15) != 0 || e.step % 4 != 0 || e.tile % 4 != 0) return false;
+    if (e.n4 <= 0 || e.n4_last <= 0 || e.n4_last > e.n4 || 4L * e.n4 > e.tile || (long)(rt - 1) * e.tile + 4L * e.n4_last > span) return false;
+    if (e.nslabs < p.S - 1 || e.nslabs > p.S + 1) return false;  // (a slab per step; the state's T16 copy has one more)
+  }
+  for (int i = 0; i < p.ndesc; ++i) {
+    const Desc& d = p.d[i];
+    const int slot = arm_operand_slot(d.kind);
+    if (slot < 0 || d.p[slot] == nullptr || p.stride[d.sidx[slot]] == 0) return false;
+    bool inside = false;
+    for (int k = 0; k < t.n && !inside; ++k) {
+      const ArmEntry& e = t.e[k];
+      const long span = e.step < 0 ? -(long)e.step : e.step;
+      const float* lo = e.step < 0 ? e.base - (long)(e.nslabs - 1) * span : e.base;
+      inside = d.p[slot] >= lo && d.p[slot] <= lo + (long)e.nslabs * span;  // (<=: a reversed operand may start one slab past the end)
+    }
+    if (!inside) return false;
+  }
+  const Desc& d = p.d[link];
+  int armers[4] = {0, 0, 0, 0};
+  if (rt > 4) return false;
+  for (int w = cand0; w < cand0 + ncand; ++w) {
+    int tiles = 0, r = 0;
+    for (TileIter it(w, d.wg0, d.nwg, rt, d.ct, xcd); it.valid(); it.next()) { ++tiles; r = it.r0() / 16; }
+    if (tiles > 1) return false;
+    if (tiles == 1) ++armers[r];
+    for (int i : idle)
+      if (TileIter(w, p.d[i].wg0, p.d[i].nwg, rt, p.d[i].ct, xcd).valid()) return false;
+  }
+  for (int r = 0; r < rt; ++r)
+    if (armers[r] == 0 || (armers[r] & (armers[r] - 1)) != 0) return false;
+  return true;
 }
 
 }  // namespace pchain

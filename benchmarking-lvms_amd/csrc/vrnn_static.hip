@@ -378,6 +378,38 @@ __device__ __forceinline__ void visit_grub(const GrubArgs& q, const Deal& d, int
   ANAT(anat_note(wk.anat, 4 * d.idx, wk.pl);)
 }
 
+// ---- look-ahead arming (vrnn_static.h: the table, the three rules, the host's mirror of the arithmetic below) --------------------
+// This workgroup's place among the armers of its row tile: the workgroups [cand0, cand0 + ncand) with a tile of the role's link in
+// that row tile, ranked in one ballot (ncand <= kArmCandidates: arm_applies).  `tiles`, nt: this workgroup's tile_lanes of the link.
+struct Armer {
+  int r, k, log2n;  // row tile, rank, armers of the row tile (a power of two: arm_applies; -1: this workgroup arms nothing)
+};
+__device__ __forceinline__ Armer arm_rank_dev(int w, const Deal& link, int cand0, int ncand, int rt, bool xcd, int tiles, int nt, int entries) {
+  if (entries == 0 || nt != 1 || w < cand0 || w >= cand0 + ncand) return Armer{0, 0, -1};
+  const int lane = threadIdx.x & 63, my_r0 = __builtin_amdgcn_readlane(tiles, 0) & 0xffff;
+  const TileIter it(cand0 + lane, link.wg0, link.nwg, rt, link.ct, xcd);
+  const unsigned long long same = __ballot(lane < ncand && it.valid() && it.r0() == my_r0);
+  const int n = (int)__popcll(same);  // (>= 1: this workgroup's own bit; a power of two: arm_applies)
+  return Armer{my_r0 >> 4, (int)__popcll(same & ((1ull << (w - cand0)) - 1ull)), __builtin_ctz((unsigned)n)};
+}
+// store the sentinels of walk step j into this workgroup's share of its row tile (rule 1), entry e on wave e % NW, as write-through
+// 16-byte stores that the wave drains before it goes on to its next tile (rule 2)
+template <int NW>
+__device__ __forceinline__ void arm_ahead(const ArmTable& t, int j, int rt, const Armer& a) {
+  if (a.log2n < 0) return;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const u32x4 ff = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
+  for (int e = wave; e < t.n; e += NW) {
+    const ArmEntry& en = t.e[e];
+    if (j >= en.nslabs) continue;
+    int first, count;
+    arm_share(en, a.r, rt, a.k, a.log2n, &first, &count);
+    const rsrc_t dst = make_rsrc(en.base + (long)j * en.step + (long)a.r * en.tile + 4L * first);
+    for (int i = lane; i < count; i += 64) __builtin_amdgcn_raw_buffer_store_b128(ff, dst, 16 * i, 0, PCHAIN_STORE_AUX);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 // The kernel's own argument block (offset 0 of the kernarg segment) through a pointer the compiler cannot see through: every visit
 // reads the fields it needs with s_load at its point of use.  Read through the by-value parameter instead, the compiler hoists every
 // pointer of a role's loop into SGPRs for the whole launch and, past 106 of them, parks them in VGPR lanes (forward 514 -> 34,
@@ -404,6 +436,7 @@ struct FwdArgs {
   int ndec;  // 0 | 3 | 4 (the last layer's Deal stays empty)
   int B, s0, S, xcd, place;  // place: vrnn_static.h Place
   Ctl ctl;
+  ArmTable arm;  // look-ahead arming by the posterior half (n = 0: off)
   ANAT(unsigned long long* prof;)
 };
 constexpr int kFwdProducts = 4, kBwdProducts = 2;
@@ -433,6 +466,27 @@ __device__ __forceinline__ void fwd_half(const FwdArgs& a, int w, int rt, bool x
     else visit_gru<NW>(kargs<FwdArgs>().gru, kargs<FwdArgs>().deal[5], s, t5, n5, wk, gru);
   }
   ANAT(anat_end(wk.anat, kargs<FwdArgs>().prof, HALF, w == kargs<FwdArgs>().deal[1 + HALF].wg0);)
+}
+
+// a workgroup of the posterior half that arms (vrnn_static.h): the deal gives it no tile of the heads or the phi_z run, so between its
+// run and its GRU tile it waits while the prior half walks those — and stores the sentinels of step s + kArmAhead in that window.
+// A role of its own, not a branch of fwd_half: without the heads' and the run's fragments it has the registers for the stores,
+// and the other workgroups' code stays what it was.
+template <int NW>
+__device__ __forceinline__ void fwd_post_arming(const FwdArgs& a, int w, int rt, bool xcd, Walk& wk) {
+  const int t1 = tile_lanes(w, a.deal[2].wg0, a.deal[2].nwg, rt, a.deal[2].ct, xcd), n1 = tile_count(t1);
+  const int t5 = tile_lanes(w, a.deal[5].wg0, a.deal[5].nwg, rt, a.deal[5].ct, xcd), n5 = tile_count(t5);
+  const Armer armer = arm_rank_dev(w, a.deal[5], a.deal[2].wg0, a.deal[0].wg0 - a.deal[2].wg0, rt, xcd, t5, n5, a.arm.n);
+  RunRes<3, kR, kH> run;
+  Res<kH, 3> gru;
+  load_run<NW>(run, kargs<FwdArgs>().run[1], t1, n1);
+  load_gru<NW>(gru, kargs<FwdArgs>().gru, t5, n5);
+  for (int s = a.s0; s < a.S; ++s) {
+    visit_run<NW, 3, kR, kH, false, Paced>(kargs<FwdArgs>().run[1], kargs<FwdArgs>().deal[2], s, t1, n1, wk, run);
+    arm_ahead<NW>(kargs<FwdArgs>().arm, s + kArmAhead, rt, armer);
+    visit_gru<NW>(kargs<FwdArgs>().gru, kargs<FwdArgs>().deal[5], s, t5, n5, wk, gru);  // (not paced: see fwd_half)
+  }
+  ANAT(anat_end(wk.anat, kargs<FwdArgs>().prof, 1, w == kargs<FwdArgs>().deal[2].wg0);)
 }
 
 // a workgroup of the decoder range: a follower of the chain.  Step t's decoder row needs [phi_t | h_t] only, so nothing the critical
@@ -479,6 +533,7 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_fwd_kernel(FwdArgs a) 
     return;
   }
   if (w < a.deal[2].wg0) fwd_half<NW, 0>(a, w, rt, xcd, wk);
+  else if (a.arm.n != 0) fwd_post_arming<NW>(a, w, rt, xcd, wk);  // (an armed launch: no workgroup of this half has a heads or phi_z tile, arm_applies)
   else fwd_half<NW, 1>(a, w, rt, xcd, wk);
 }
 
@@ -494,6 +549,7 @@ struct BwdArgs {
   Deal deal[10];
   int B, s0, S, xcd, place;  // place: vrnn_static.h Place
   Ctl ctl;
+  ArmTable arm;  // look-ahead arming by the spare range (n = 0: off)
   ANAT(unsigned long long* prof;)
 };
 
@@ -543,7 +599,11 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) 
     if (n == 0) return;
     Res<kR> part;
     load_lin<NW, kR>(part, kargs<BwdArgs>().part[2].W, kargs<BwdArgs>().part[2].w_width, t, n);
-    for (int s = a.s0; s < a.S; ++s) visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[2], kargs<BwdArgs>().deal[3], s, t, n, wk, part);
+    const Armer armer = arm_rank_dev(w, a.deal[3], a.deal[3].wg0, a.deal[3].nwg, rt, xcd, t, n, a.arm.n);
+    for (int s = a.s0; s < a.S; ++s) {
+      visit_lin<NW, kR, 0>(kargs<BwdArgs>().part[2], kargs<BwdArgs>().deal[3], s, t, n, wk, part);
+      arm_ahead<NW>(kargs<BwdArgs>().arm, s + kArmAhead, rt, armer);
+    }
     ANAT(anat_end(wk.anat, kargs<BwdArgs>().prof, 4, w == kargs<BwdArgs>().deal[3].wg0);)
     return;
   }
@@ -627,6 +687,7 @@ int static_lin_chain_launch(const Program& p, hipStream_t stream, bool resident,
 // the selector between the static walk and the interpreter for the VRNN programs (blvm_pchain_static)
 int g_static = 1;
 long g_static_launches = 0;  // VRNN programs launched on the static kernels (blvm_pchain_static(-2))
+long g_armed_launches = 0;   // ... of which armed their polled slabs themselves (blvm_pchain_static(-3))
 bool pchain_static_on() { return g_static != 0; }
 
 // ---- host: the interpreter's program -> the static kernels' arguments -------------------------------------------------------
@@ -656,6 +717,35 @@ SeqArgs seq_args(const Program& p, const Desc& d) {
   return q;
 }
 
+// ---- host: who stores the sentinels (vrnn_static.h) ----------------------------------------------------------------------------
+// walk steps [0, kArmAhead) of every buffer of the table, in one launch: block (x, e) strides over the 16-byte words of entry e
+__global__ __launch_bounds__(256) void arm_prefix_kernel(ArmTable t, int rt) {
+  const ArmEntry& en = t.e[blockIdx.y];
+  const uint4 ff = make_uint4(SENTINEL, SENTINEL, SENTINEL, SENTINEL);
+  const int slabs = en.nslabs < kArmAhead ? en.nslabs : kArmAhead;
+  for (int j = 0; j < slabs; ++j)
+    for (int r = 0; r < rt; ++r) {
+      uint4* const dst = reinterpret_cast<uint4*>(en.base + (long)j * en.step + (long)r * en.tile);
+      const int n4 = r == rt - 1 ? en.n4_last : en.n4;
+      for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) dst[i] = ff;
+    }
+}
+int full_fill(const ArmPlan& plan, hipStream_t stream) {
+  for (int i = 0; i < plan.nfull; ++i) BLVM_HIP(pchain_fill_sentinel(plan.full[i].p, plan.full[i].bytes, stream));
+  return BLVM_OK;
+}
+// An armed launch (bit 128 of pchain_tune clear and arm_applies: rule 3): *arm = the table, and the host fills only the steps in
+// front of the first armed one.  Any other launch: *arm stays empty and the host fills everything the launch polls.
+int arm_or_fill(const Program& p, const ArmPlan& plan, int link, std::initializer_list<int> idle, int cand0, int ncand, bool xcd, hipStream_t stream,
+                ArmTable* arm) {
+  arm->n = 0;
+  if ((pchain_tune() & 128) != 0 || !arm_applies(p, plan.tab, link, idle, cand0, ncand, xcd)) return full_fill(plan, stream);
+  *arm = plan.tab;
+  hipLaunchKernelGGL(arm_prefix_kernel, dim3(8, plan.tab.n), dim3(256), 0, stream, plan.tab, (p.B + 15) / 16);
+  BLVM_CHECK_LAUNCH("arm_prefix");
+  return BLVM_OK;
+}
+
 // 1: not the shape the static kernels were compiled for (vrnn_launch runs the interpreter).  *place: the launch's placement
 // (prior, post: the descriptors of the two halves' runs); every count of tiles is taken in the TileIter mode that placement deals with
 int vrnn_static_check(const Program& p, int ndesc, int products, int prior, int post, int* place) {
@@ -667,7 +757,7 @@ int vrnn_static_check(const Program& p, int ndesc, int products, int prior, int 
   return 0;
 }
 
-int vrnn_static_fwd(const Program& p, hipStream_t stream) {
+int vrnn_static_fwd(const Program& p, hipStream_t stream, const ArmPlan& plan, const std::function<int()>& pre) {
   int place = kPlaceProgram;
   const bool dec = p.ndesc == kFwdDecDesc || p.ndesc == kFwdDecDesc - 1;  // with the decoder range (all three layers | the first two)
   if (vrnn_static_check(p, dec ? p.ndesc : kFwdDesc, kFwdProducts, 1, 2, &place)) return 1;
@@ -716,15 +806,20 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream) {
   for (int i = 0; i < p.ndesc; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.place = place; a.ctl = p.ctl;
   ANAT(a.prof = pchain_profile_buffer();)
+  // the posterior half's workgroups [half, gentle) arm around their GRU tiles (descriptor 5) where none of them has a tile of the
+  // heads or the phi_z run (3, 4)
+  BLVM_TRY(arm_or_fill(p, plan, 5, {3, 4}, half, gentle - half, place_xcd(place, p), stream, &a.arm));
+  BLVM_TRY(pre());
   const size_t lds = sizeof(float) * 2 * kFwdProducts * 16 * 256;
   BLVM_TRY(static_go(&vrnn_static_fwd_kernel<16>, 0, grid, lds, "vrnn_static_fwd"));
   hipLaunchKernelGGL(vrnn_static_fwd_kernel<16>, dim3(grid), dim3(1024), lds, stream, a);
   BLVM_CHECK_LAUNCH("vrnn_static_fwd");
   ++g_static_launches;
+  if (a.arm.n != 0) ++g_armed_launches;
   return BLVM_OK;
 }
 
-int vrnn_static_bwd(const Program& p, hipStream_t stream) {
+int vrnn_static_bwd(const Program& p, hipStream_t stream, const ArmPlan& plan, const std::function<int()>& pre) {
   int place = kPlaceProgram;
   if (vrnn_static_check(p, 10, kBwdProducts, 8, 9, &place)) return 1;
   const Desc* d = p.d;
@@ -764,26 +859,34 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream) {
   for (int i = 0; i < 10; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.place = place; a.ctl = p.ctl;
   ANAT(a.prof = pchain_profile_buffer();)
+  // the spare range's workgroups arm around their partial-sum tiles (descriptor 3)
+  BLVM_TRY(arm_or_fill(p, plan, 3, {}, spare, d[3].nwg, place_xcd(place, p), stream, &a.arm));
+  BLVM_TRY(pre());
   const size_t lds = sizeof(float) * 2 * kBwdProducts * 16 * 256;
   BLVM_TRY(static_go(&vrnn_static_bwd_kernel<16>, 1, grid, lds, "vrnn_static_bwd"));
   hipLaunchKernelGGL(vrnn_static_bwd_kernel<16>, dim3(grid), dim3(1024), lds, stream, a);
   BLVM_CHECK_LAUNCH("vrnn_static_bwd");
   ++g_static_launches;
+  if (a.arm.n != 0) ++g_armed_launches;
   return BLVM_OK;
 }
 
 }  // namespace
 
-int vrnn_launch(pchain::Builder& bld, bool forward, const char* who, hipStream_t stream) {
+int vrnn_launch(pchain::Builder& bld, bool forward, const char* who, hipStream_t stream, const pchain::ArmPlan& plan, const std::function<int()>& pre) {
   BLVM_TRY(pchain_prepare(bld, who));
-  const int rc = forward ? vrnn_static_fwd(bld.p, stream) : vrnn_static_bwd(bld.p, stream);
-  return rc == 1 ? pchain_run(bld.p, stream) : rc;
+  const int rc = forward ? vrnn_static_fwd(bld.p, stream, plan, pre) : vrnn_static_bwd(bld.p, stream, plan, pre);
+  if (rc != 1) return rc;
+  BLVM_TRY(full_fill(plan, stream));  // (the static converters return 1 in front of any fill)
+  BLVM_TRY(pre());
+  return pchain_run(bld.p, stream);
 }
 
 }  // namespace blvm
 
 extern "C" int blvm_pchain_static(int mode) {
   if (mode == -2) return (int)std::min<long>(blvm::g_static_launches, 0x7fffffffL);
+  if (mode == -3) return (int)std::min<long>(blvm::g_armed_launches, 0x7fffffffL);
   const int was = blvm::g_static;
   if (mode >= 0) blvm::g_static = mode != 0;
   return was;

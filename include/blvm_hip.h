@@ -77,12 +77,15 @@ int blvm_pchain_profile(unsigned long long* device_buffer);
  * operand polls of tiles off the critical path.  Bits 32 and 64 place the static-walk launches only (the interpreter runs a program as
  * built): 32 deals their tiles without the column-tile placement of bit 4 (with four row tiles, row tile r on XCDs r and r + 4), 64
  * permutes the block index as well, so that the prior half of row tile r sits on XCD r and the posterior half on XCD r + 4; where
- * the deal is not the one the permutation was made for (it needs four row tiles on 256 CUs) a launch is placed as bit 32 says. */
+ * the deal is not the one the permutation was made for (it needs four row tiles on 256 CUs) a launch is placed as bit 32 says.
+ * Bit 128 turns the static walks' look-ahead arming off: by default a static-walk launch of more than four steps stores the
+ * sentinels of its polled slabs itself, four steps ahead, from workgroups that wait anyway, and the host fills only the first
+ * four steps; with the bit set the host fills every polled slab in front of the launch, as it does for every other launch. */
 int blvm_pchain_tune(int bits);
 /* The VRNN forward / backward programs at B <= 64 (16-row tiles, fp32, H = Z = 256, R = 512) run on static-walk kernels whose walk is
  * fixed at compile time (mode 1, the default; bit-identical results); mode 0 sends them to the program interpreter, a negative
  * mode only queries.  Returns the mode in effect before the call; mode -2 returns instead how many VRNN programs the process has
- * launched on the static kernels so far. */
+ * launched on the static kernels so far, mode -3 how many of those armed their polled slabs themselves (blvm_pchain_tune bit 128). */
 int blvm_pchain_static(int mode);
 /* Diagnostics: which implementation the single-layer sequence entry points (K4 / K2) took so far in this process.  Copies twelve
  * counters, out[op * 3 + path]: op 0 blvm_lstm_seq_fwd, 1 blvm_lstm_seq_bwd, 2 blvm_gru_seq_fwd, 3 blvm_gru_seq_bwd; path 0 the
