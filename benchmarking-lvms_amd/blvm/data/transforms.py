@@ -61,6 +61,29 @@ class MuLawDecode(Transform):
         return x.sign() * (torch.exp(x.abs() * self._divisor) - 1) / self.mu
 
 
+class Quantize(Transform):
+    """Values in [-1, 1] -> integer classes (transforms.py:216-260): `bucketize` against `linspace(-1, 1, bins)` with right=False, so
+    class k is the interval (boundaries[k-1], boundaries[k]] and a value above 1 gets class `bins` (callers that need a class below
+    `bins` clamp, as `WaveNet.forward` does).  Give one of `bits` (bins = 2**bits) and `bins` (pass bits=None).
+    `rescale=True` returns floats instead: `linspace(low, high, bins)[min(k, bins - 1)]`, the value that quantises back to class k —
+    `CategoricalDense.dequantize` for the default range (the reference names a class `Scale` there that does not exist)."""
+
+    def __init__(self, low: float = -1.0, high: float = 1.0, bits: Optional[int] = 8, bins: Optional[int] = None,
+                 force_out_int64: bool = True, rescale: bool = False):  # fmt: skip
+        super().__init__()
+        assert (bits is None) != (bins is None), "Must set one and only one of `bits` and `bins`"
+        self.low, self.high = low, high
+        self.bits = bins // 8 if bits is None else bits
+        self.bins = 2**bits if bins is None else bins
+        self.boundaries = torch.linspace(start=-1, end=1, steps=self.bins)
+        self.out_int32 = (self.bits <= 32) and (not force_out_int64)
+        self.rescale = torch.linspace(start=low, end=high, steps=self.bins) if rescale else None
+
+    def forward(self, x: torch.Tensor):
+        k = torch.bucketize(x, self.boundaries.to(x.device), out_int32=self.out_int32, right=False)
+        return self.rescale.to(x.device)[k.long().clamp(max=self.bins - 1)] if self.rescale is not None else k
+
+
 class Compose(Transform):
     """Apply transforms left to right (transforms.py:30-52)."""
 

@@ -1,7 +1,8 @@
 """WaveNet with the reference's construction API and state_dict layout (blvm/models/wavenet/wavenet.py:29-293).
 
 forward: left-pad by the receptive field -> causal conv -> in_transform -> 50 gated residual blocks (K10, one autograd
-node) -> sum of skips * variance_scale -> ReLU-Linear-ReLU -> likelihood Linear (K6) -> DMoL log-likelihood (K7).
+node) -> sum of skips * variance_scale -> ReLU-Linear-ReLU -> likelihood Linear (K6) -> DMoL log-likelihood (K7), or with a
+`CategoricalDense` head its Linear and the softmax log-likelihood in one (K7d: the logits are never stored).
 Loss in fp32 like the reference: -sum(ll * mask) / sum(x_sl) (wavenet.py:128-146).
 """
 import math
@@ -14,7 +15,7 @@ from blvm import ops
 from blvm.evaluation import BitsPerDimMetric, DeferredScalars, LLMetric, LossMetric
 from blvm.models.base_model import BaseModel
 from blvm.models.vrnn import LazyNamespace
-from blvm.modules.distributions import DiscretizedLogisticMixtureDense
+from blvm.modules.distributions import CategoricalDense, DiscretizedLogisticMixtureDense
 from blvm.utils.operations import split_sequence
 from blvm.utils.padding import get_modulo_length
 
@@ -63,8 +64,9 @@ class WaveNet(BaseModel):
 
     def forward(self, x, x_sl, y=None, pad_causal: bool = True, pad_receptive_field: bool = True):
         lik, nsf, rf = self.likelihood, self.n_stack_frames, self.receptive_field
-        if not isinstance(lik, DiscretizedLogisticMixtureDense):
-            raise NotImplementedError("libblvm_hip: WaveNet is built with the DMoL likelihood head")
+        cat = isinstance(lik, CategoricalDense)
+        if not cat and not isinstance(lik, DiscretizedLogisticMixtureDense):
+            raise NotImplementedError("libblvm_hip: WaveNet is built with the DMoL and the categorical likelihood heads")
         if x.ndim == 3:
             x = x.squeeze(-1)
         dev = x.device
@@ -72,8 +74,12 @@ class WaveNet(BaseModel):
         x_sl_host = x_sl.detach().cpu().to(torch.int64)
         if y is None:
             y = x.detach()
+            if cat:  # Quantize(bins=V) on the device: class V (a value above 1) joins the top class
+                y = torch.bucketize(y, lik.levels, right=False).clamp(max=lik.y_dim - 1)
             if not pad_receptive_field:
                 y = y[:, rf * nsf :]
+        elif cat and (y.is_floating_point() or y.is_complex()):
+            raise TypeError(f"WaveNet: the categorical head takes integer class targets y [B,T], got {y.dtype}")
         y = y.reshape(y.size(0), -1).contiguous()
         x_sl_strided = (x_sl_host / nsf).ceil().int()
         B = x.size(0)
@@ -97,10 +103,11 @@ class WaveNet(BaseModel):
         skip_sum = self.res_stack.forward_tm(out, skip_size)  # [skip_size,B,C]
         C = self.res_channels
         logits = self.out_transform.forward_rows(skip_sum.view(skip_size * B, C), self.variance_scale)  # [skip*B, C*nsf]
-        par = ops.linear(logits.view(skip_size * B * nsf, C), lik.params.weight, lik.params.bias)  # [skip*B*nsf, 3K]
-
         T_y = y.size(1)
         mask_len = ops.upload_i32(x_sl_host.clamp(min=0, max=T_y), dev)
+        if cat:
+            return self._categorical_outputs(logits, y, mask_len, x_sl_host, x_sl_strided, skip_sum, B, T_y, skip_size)
+        par = ops.linear(logits.view(skip_size * B * nsf, C), lik.params.weight, lik.params.bias)  # [skip*B*nsf, 3K]
         log_prob = ops.dmol_log_prob(par.view(skip_size * B, nsf * lik.out_features), None, None, y, mask_len,
                                      ops.LAYOUT_TIME_MAJOR, B, T_y, skip_size, nsf, lik.num_mix, lik.num_bins,
                                      lik.log_epsilon).to(torch.float32)  # fmt: skip
@@ -136,6 +143,45 @@ class WaveNet(BaseModel):
                                y=y.unsqueeze(-1))  # fmt: skip
         return loss, metrics, output
 
+    def _categorical_outputs(self, dec, y, mask_len, x_sl_host, x_sl_strided, skip_sum, B, T_y, skip_size):
+        """The categorical head on the output transform's activations `dec` [skip*B, C*nsf] (K7d: the head's Linear, the
+        log-softmax, the gather at y, the mask and the per-utterance sums without a [frames, V] tensor); the same loss, metrics and
+        lazy outputs as the DMoL head.  `output.parameters` are the materialised logits [B,T,V]: ask for them at small T * V only."""
+        lik, nsf, C = self.likelihood, self.n_stack_frames, self.res_channels
+        log_prob = lik.fused_log_prob(dec, y, mask_len, B, T_y, skip_size, nsf).to(torch.float32)
+        n_frames = float(x_sl_host.sum())
+        loss = -log_prob.sum() / n_frames
+        sums = DeferredScalars(torch.stack([loss.detach().double(), log_prob.detach().double().sum()]))
+        metrics = [
+            LossMetric(sums[0], weight_by=B),
+            LLMetric(sums[1], reduce_by=B),
+            BitsPerDimMetric(sums[1], reduce_by=n_frames),
+        ]
+        V = lik.y_dim
+
+        def parameters():
+            with torch.no_grad():
+                p = lik(dec.detach().view(skip_size * B * nsf, C))
+            return p.view(skip_size, B, nsf, V).permute(1, 0, 2, 3).reshape(B, skip_size * nsf, V)[:, :T_y]
+
+        lazy = dict(
+            parameters=parameters,
+            log_prob_twise=lambda: ops.categorical_ll_twise(dec, lik.logits.weight, lik.logits.bias, y, mask_len, B, T_y, skip_size, nsf),
+            predictions=lambda ns: lik.sample(ns.parameters),
+            predictions_mode=lambda ns: lik.mode(ns.parameters),
+        )
+        output = LazyNamespace(lazy, loss=loss, log_prob=log_prob, z=[skip_sum.detach().transpose(0, 1)], z_sl=x_sl_strided,
+                               y=y.unsqueeze(-1))  # fmt: skip
+        return loss, metrics, output
+
+    def _draw(self, parameters, u):
+        """One draw per head evaluation -> floats [B,nsf,1]; the categorical head's class k is fed back as `dequantize(k)`."""
+        lik = self.likelihood
+        if isinstance(lik, CategoricalDense):
+            k = lik.sample(parameters, uniforms=None if u is None else u.reshape(parameters.shape[:-1]))
+            return lik.dequantize(k).unsqueeze(-1)
+        return lik.sample(parameters) if u is None else lik.sample(parameters, uniforms=u)
+
     def split_sequence(self, x, x_sl, length: int):
         """Overlap = receptive field (wavenet.py:230-242)."""
         overlap = self.receptive_field * self.n_stack_frames
@@ -157,7 +203,8 @@ class WaveNet(BaseModel):
         whole residual stack over a receptive-field window (no cached sampling, as in the reference), takes the single skip
         output, DIVIDES it by variance_scale (the reference's generate divides where forward multiplies, :274 — kept), applies
         the output transform and the head, samples, and shifts the window (FIFO).  Returns x_hat [B, n_frames, 1].
-        `uniforms[t]` optionally supplies the head sampler's two uniform draws of frame t.
+        `uniforms[t]` optionally supplies the head sampler's draws of frame t: the DMoL head's two, the categorical head's one [B]
+        (its class k is fed back and returned as the float `dequantize(k)`).
         `cached=True` (the reference's TODO, arXiv:1611.09482): the same samples from per-block queues of past activations —
         one new frame per block per step instead of the whole window; with the DMoL head and widths the decode kernel takes
         (K10c: every frame in one launch) through `ops.wavenet_decode`, otherwise block by block (`_generate_cached`).
@@ -192,7 +239,7 @@ class WaveNet(BaseModel):
             skip = self.res_stack.forward_tm(out, 1)  # [1,B,C]
             logits = self.out_transform.forward_rows(skip.view(n_samples, C), 1.0 / self.variance_scale)  # [B, C * nsf]
             parameters = lik(logits.view(n_samples, nsf, C))  # unstack_tensor(logits, nsf) (wavenet.py:277-278): one head evaluation per stacked sample
-            pred = lik.sample(parameters) if uniforms is None else lik.sample(parameters, uniforms=uniforms[t])  # [B,nsf,1]
+            pred = self._draw(parameters, None if uniforms is None else uniforms[t])  # [B,nsf,1]
             x_hat.append(pred)
             # the nsf new samples are the channels of the next input frame (wavenet.py:290; nsf = 1: one sample, one channel)
             win = torch.cat([win[1:], pred.reshape(1, n_samples, nsf).to(torch.float32)], 0)
@@ -308,7 +355,7 @@ class WaveNet(BaseModel):
                 heads[i] = (heads[i] + 1) % d
             logits = self.out_transform.forward_rows(skip.view(B, C), 1.0 / self.variance_scale)
             parameters = lik(logits.view(B, 1, C))
-            pred = lik.sample(parameters) if uniforms is None else lik.sample(parameters, uniforms=uniforms[t])  # [B,1,1]
+            pred = self._draw(parameters, None if uniforms is None else uniforms[t])  # [B,1,1]
             x_hat.append(pred)
             x_prev, x_now = x_now, pred.view(B, 1).to(torch.float32)
         x_hat = torch.hstack(x_hat)

@@ -154,6 +154,52 @@ class DiagonalGaussianMixtureDense(ConditionalDistribution):
         return ops.mix_sample(DiscretizedLogisticMixtureDense._pack(params), u, nrm, 1, sd_beta=0.0).unsqueeze(-1)
 
 
+class CategoricalDense(ConditionalDistribution):
+    """Softmax over `y_dim` classes with the reference's constructor and parameter names (distributions.py:207-235: `logits` =
+    nn.Linear, so its state_dict loads unchanged).  Training goes through `fused_log_prob` (K7d: the [frames, y_dim] logits are never
+    stored); `forward` materialises logits for the few rows generation and the lazy outputs ask for."""
+
+    def __init__(self, x_dim, y_dim):
+        super().__init__()
+        ops.categorical_check_widths(x_dim, y_dim)
+        self.x_dim, self.y_dim = x_dim, y_dim
+        self.out_features = y_dim
+        self.logits = nn.Linear(x_dim, y_dim)
+        # the class values, computed where `Quantize` computes its boundaries (on the host) so that the two agree to the bit; not
+        # part of the state_dict
+        self.register_buffer("levels", torch.linspace(-1.0, 1.0, y_dim), persistent=False)
+        self.reset_parameters()
+
+    def forward(self, x):
+        lead = x.shape[:-1]
+        return ops.mlp(x.reshape(-1, x.shape[-1]), [self.logits], act=ops.ACT_NONE).view(*lead, -1)
+
+    def fused_log_prob(self, dec, y, x_sl_dev, B, T, Tp, S):
+        """Masked per-utterance log-likelihood sums [B] (float64) of integer targets y [B,T] straight from the activations `dec`
+        [B*T', S*x_dim] (time-major rows)."""
+        return ops.categorical_log_prob(dec, self.logits.weight, self.logits.bias, y, x_sl_dev, B, T, Tp, S)
+
+    def log_prob(self, y, logits, reduce_dim=None):
+        """`categorical_ll(y, logits, reduce_dim)` (log_likelihoods.py:63-80) per frame on materialised logits — a handful of rows,
+        element-wise torch off the hot path (training uses `fused_log_prob`)."""
+        ll = (logits - logits.logsumexp(dim=-1, keepdim=True)).gather(-1, y.long().unsqueeze(-1)).squeeze(-1)
+        return ll if reduce_dim is None else ll.sum(reduce_dim)
+
+    @torch.no_grad()
+    def mode(self, logits):
+        return ops.categorical_sample(logits)
+
+    @torch.no_grad()
+    def sample(self, logits, uniforms=None):
+        """Inverse-CDF draw, one uniform per row (`uniforms` [*] in [0,1) optionally supplies them)."""
+        u = torch.rand(logits.shape[:-1], device=logits.device) if uniforms is None else uniforms
+        return ops.categorical_sample(logits, u)
+
+    def dequantize(self, k):
+        """Class k -> linspace(-1, 1, y_dim)[k]: the value `Quantize(bins=y_dim)` maps back to class k."""
+        return self.levels.to(k.device)[k.long()]
+
+
 def mlp_log_prob(lik, x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given=None):
     """Decoder MLP + likelihood head `lik` on its output: (decoder activations DETACHED, masked per-utterance log-likelihood sums [B]).
     The DMoL head takes its fused form; the Gaussian heads run the MLP and `fused_log_prob` as separate nodes.

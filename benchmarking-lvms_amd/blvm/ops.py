@@ -483,6 +483,102 @@ def dmol_ll_twise(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix=10, num_b
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# K7d: categorical head fused with its Linear(C -> V) — the [frames, V] logits are never stored
+# ----------------------------------------------------------------------------------------------------------------------
+
+BLVM_ENOSUP = _hip.CONSTANTS["BLVM_ENOSUP"]
+
+
+def categorical_check_widths(C: int, V: int):
+    """The widths the fused categorical head is built for (host arithmetic: raises before any device work)."""
+    if C % 16 != 0 or not 16 <= C <= 512 or not 2 <= V <= 65536:
+        raise NotImplementedError(f"libblvm_hip: the categorical head takes C % 16 == 0, 16 <= C <= 512 and 2 <= V <= 65536, got C = {C}, V = {V}")
+
+
+def _cat_check(rc: int, what: str):
+    if rc == BLVM_ENOSUP:
+        raise NotImplementedError(f"libblvm_hip: {load().blvm_last_error().decode(errors='replace')}")
+    check(rc, what)
+
+
+def _cat_operands(dec, W, b, y, B, T, Tp, S):
+    if W.dim() != 2 or b.dim() != 1 or b.shape[0] != W.shape[0]:
+        raise _hip.BlvmHipError(f"categorical head: weight [V,C] and bias [V], got {tuple(W.shape)} and {tuple(b.shape)}")
+    V, C = W.shape
+    categorical_check_widths(C, V)
+    if dec.dim() != 2 or dec.shape[0] != B * Tp or dec.shape[1] != S * C:
+        raise _hip.BlvmHipError(f"categorical head: activations must be [B*T'={B * Tp}, S*C={S * C}], got {tuple(dec.shape)}")
+    if tuple(y.shape) != (B, T) or Tp * S < T:
+        raise _hip.BlvmHipError(f"categorical head: targets must be [B={B}, T={T}] with T <= T'*S={Tp * S}, got {tuple(y.shape)}")
+    if y.dtype not in (torch.int32, torch.int64):
+        raise _hip.BlvmHipError(f"categorical head: targets are integer classes, got {y.dtype}")
+    y32 = y if y.dtype == torch.int32 else y.to(torch.int32)  # a class beyond int32 is beyond V: it wraps to another wrong class
+    return _f32c(dec), _f32c(W), _f32c(b), y32.contiguous(), V, C
+
+
+def _cat_forward(dec, W, b, y32, x_sl_dev, B, T, Tp, S, C, V, want_sums: bool):
+    lse = torch.empty(B * Tp * S, device=dec.device, dtype=torch.float32)
+    ll = torch.empty(B, T, device=dec.device, dtype=torch.float32)
+    log_prob = torch.zeros(B, device=dec.device, dtype=torch.float64) if want_sums else None
+    _cat_check(load().blvm_cat_fwd(ptr(dec), ptr(W), ptr(b), ptr(y32), ptr(x_sl_dev), B, T, Tp, S, C, V, ptr(lse), ptr(ll), ptr(log_prob),
+                                   stream_ptr()), "blvm_cat_fwd")  # fmt: skip
+    return lse, ll, log_prob
+
+
+class _CategoricalFunction(torch.autograd.Function):
+    """Saves the activations, the targets and one log-sum-exp per frame; the backward recomputes the logits tile by tile."""
+
+    @staticmethod
+    def forward(ctx, dec, W, b, y, x_sl_dev, B, T, Tp, S):
+        dec, W, b, y32, V, C = _cat_operands(dec, W, b, y, B, T, Tp, S)
+        lse, _, log_prob = _cat_forward(dec, W, b, y32, x_sl_dev, B, T, Tp, S, C, V, True)
+        ctx.save_for_backward(dec, W, b, y32, x_sl_dev, lse)
+        ctx.cfg = (B, T, Tp, S, C, V)
+        return log_prob
+
+    @staticmethod
+    def backward(ctx, g):
+        dec, W, b, y32, x_sl_dev, lse = ctx.saved_tensors
+        B, T, Tp, S, C, V = ctx.cfg
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        g32 = _grad_f32(g)
+        lib = load()
+        d_dec = torch.empty_like(dec) if need_x else None
+        dW = torch.empty_like(W) if need_w else None
+        db = torch.empty_like(b) if need_b else None
+        ws_floats = lib.blvm_cat_bwd_workspace_floats(B * Tp * S, C, V) if (need_w or need_b) else 0
+        ws = torch.empty(ws_floats, device=dec.device, dtype=torch.float32) if ws_floats else None
+        _cat_check(lib.blvm_cat_bwd(ptr(dec), ptr(W), ptr(b), ptr(y32), ptr(x_sl_dev), ptr(lse), ptr(g32), B, T, Tp, S, C, V, ptr(d_dec),
+                                    ptr(dW), ptr(db), ptr(ws), stream_ptr()), "blvm_cat_bwd")  # fmt: skip
+        return (d_dec, dW, db) + (None,) * 6
+
+
+def categorical_log_prob(dec, W, b, y, x_sl_dev, B, T, Tp, S):
+    """Per-utterance masked categorical log-likelihood sums [B] (float64) of integer targets y [B,T] under softmax(dec W^T + b);
+    `dec` [B*T', S*C] time-major rows.  Gradients for dec, W and b, each only where it is needed."""
+    return _CategoricalFunction.apply(dec, W, b, y, x_sl_dev, B, T, Tp, S)
+
+
+def categorical_ll_twise(dec, W, b, y, x_sl_dev, B, T, Tp, S):
+    """Masked frame-wise log-likelihood [B,T] (no autograd)."""
+    dec, W, b, y32, V, C = _cat_operands(dec.detach(), W.detach(), b.detach(), y, B, T, Tp, S)
+    return _cat_forward(dec, W, b, y32, x_sl_dev, B, T, Tp, S, C, V, False)[1]
+
+
+def categorical_sample(logits, u=None):
+    """Classes [...] (int64) from logits [..., V] (no autograd): the arg-max (lowest index on a tie) without `u`, else the inverse
+    CDF at the uniforms u [...]."""
+    logits = _f32c(logits.detach())
+    V = logits.shape[-1]
+    lead = logits.shape[:-1]
+    n = logits.numel() // V
+    out = torch.empty(n, device=logits.device, dtype=torch.int32)
+    u = _f32c(u.to(device=logits.device, dtype=torch.float32).reshape(n)) if u is not None else None
+    _cat_check(load().blvm_cat_sample(ptr(logits), ptr(u), n, V, ptr(out), stream_ptr()), "blvm_cat_sample")
+    return out.view(*lead).to(torch.int64)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # K8: Gaussian KL + free nats + masked sums (stand-alone form; the VRNN path fuses the backward into K1)
 # ----------------------------------------------------------------------------------------------------------------------
 

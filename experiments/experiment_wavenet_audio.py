@@ -4,7 +4,7 @@ no gradient clipping in this loop (:206-209)."""
 from _common import run, wavenet_split_eval  # noqa: I001
 
 from blvm.models import WaveNet
-from blvm.modules.distributions import DiscretizedLogisticMixtureDense
+from blvm.modules.distributions import CategoricalDense, DiscretizedLogisticMixtureDense
 from blvm.utils.argparsers import parser, str2bool
 
 parser.set_defaults(lr=3e-4, epochs=3000, num_workers=8, save_checkpoints=True, optimizer="Adam")  # experiment_wavenet_audio.py:32-40
@@ -26,9 +26,14 @@ g.add_argument("--split_eval", default=False, type=str2bool)
 
 if __name__ == "__main__":
     args = parser.parse_args()
-    if args.likelihood != "DMoL":
-        raise NotImplementedError("libblvm_hip: WaveNet is built with the DMoL likelihood")
-    lik = DiscretizedLogisticMixtureDense(args.res_channels, 1, num_mix=args.num_mix, num_bins=2**args.num_bits)
+    if args.likelihood == "DMoL":
+        lik = DiscretizedLogisticMixtureDense(args.res_channels, 1, num_mix=args.num_mix, num_bins=2**args.num_bits)
+    elif args.likelihood == "Categorical":
+        # softmax over the 2**num_bits classes (experiment_wavenet_audio.py:154-155); the model quantises its float input into the
+        # targets itself ("WaveNet with the categorical head")
+        lik = CategoricalDense(args.res_channels, 2**args.num_bits)
+    else:
+        raise NotImplementedError("libblvm_hip: WaveNet is built with the DMoL and the Categorical likelihoods")
     model = WaveNet(likelihood=lik, n_layers=args.n_layers, n_stacks=args.n_stacks, res_channels=args.res_channels,
                     kernel_size=args.kernel_size, base_dilation=args.base_dilation, n_stack_frames=args.n_stack_frames)  # fmt: skip
     if args.split_eval and not args.random_segment_size:

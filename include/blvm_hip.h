@@ -236,6 +236,43 @@ int blvm_mix_sample(const float* par, const float* u, const float* v, long long 
                     float sd_beta, float sd_eps, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * K7d  categorical (softmax) head fused with its Linear(C -> V): `CategoricalDense.forward` + `.log_prob(..., reduce_dim=None)`
+ *      (`blvm/modules/distributions.py:207-235`, `categorical_ll` `blvm/utils/log_likelihoods.py:63-80`: logits - logsumexp, gather
+ *      at y) + the mask and per-utterance sum of `blvm/models/wavenet/wavenet.py:128-146`.  The [frames, V] logits are never
+ *      stored: tiles of them are recomputed on the exact-fp32 matrix pipe wherever they are needed.
+ *
+ *   dec   [rows, S*C] contiguous, rows TIME-MAJOR (row = t*B + b), rows = Tp*B; frame (b, tau = t*S + j) at dec + (row*S + j)*C
+ *   W [V, C], bias [V]: the head's Linear;  y [B, T] int32 classes;  x_sl [B] int32 on device
+ *   frame (b, tau) counts iff tau < min(x_sl[b], T).  A frame that does not count changes nothing, whatever its target (any
+ *   integer) and its activations (NaN included) hold.  A counted frame whose target lies outside [0, V) has ll = -inf: the target is
+ *   compared with the class index and never used as an address.
+ *   Shapes: C % 16 == 0, 16 <= C <= 512, 2 <= V <= 65536 (else BLVM_ENOSUP); dec, W, d_dec, dW 16-byte aligned.  Operands are fp32
+ *   whatever blvm_set_operand_dtype says, as for K7.
+ *   fwd: lse [rows*S] fp32 (log-sum-exp of the frame's logits, 0 where the frame does not count), ll [B, T] fp32 (l_y - lse, 0 where
+ *   the frame does not count; every element is written), log_prob [B] double ACCUMULATED (caller zeroes; may be NULL): the float64
+ *   sum of ll[b, :] in a fixed order. */
+int blvm_cat_fwd(const float* dec, const float* W, const float* bias, const int32_t* y, const int32_t* x_sl, int B, int T, int Tp, int S,
+                 int C, int V, float* lse, float* ll, double* log_prob, void* stream);
+
+/*   Backward of log_prob (autograd through `logits.logsumexp` / `.gather`, log_likelihoods.py:75-79, and nn.Linear): with
+ *   d = g_b[b] * mask * (onehot(y) - exp(l - lse)) per frame, recomputed tile by tile from dec, W and the forward's `lse`,
+ *   d_dec [rows, S*C] = d W (zero on frames that do not count), dW [V, C] = d^T dec, db [V] = column sums of d: all WRITTEN; any of
+ *   the three may be NULL.  d itself never reaches global memory.  No float atomics: repeated calls give identical bits.
+ *   `workspace`: blvm_cat_bwd_workspace_floats(rows*S, C, V) floats (may be uninitialised; NULL when that is 0, or when dW and db are
+ *   NULL): partial dW / db of the row splits that fill the chip when V is small (V >= 16384: none) — under
+ *   2^15 * (C + 1) floats whatever the number of frames. */
+size_t blvm_cat_bwd_workspace_floats(long long frames, int C, int V);
+int blvm_cat_bwd(const float* dec, const float* W, const float* bias, const int32_t* y, const int32_t* x_sl, const float* lse,
+                 const float* g_b, int B, int T, int Tp, int S, int C, int V, float* d_dec, float* dW, float* db, float* workspace,
+                 void* stream);
+
+/*   Draws / modes of the head on materialised logits [n, V] (`CategoricalDense.sample` / `.mode`, distributions.py:223-229:
+ *   `torch.distributions.Categorical(logits).sample()`, `torch.argmax`).  u NULL: the arg-max, the lowest index on a tie.  Otherwise
+ *   u [n] uniforms and the inverse CDF: with m = max l, e_k = exp(l_k - m), S = sum e, out = the smallest k whose running sum
+ *   e_0 + .. + e_k reaches u * S (V - 1 if none does).  out [n] int32.  The caller draws u, as for blvm_mix_sample. */
+int blvm_cat_sample(const float* logits, const float* u, long long n, int V, int32_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * K8  fused analytic Gaussian KL + free-nats + mask + per-utterance sums.  Replaces
  *     `blvm/utils/variational.py:67-70,86-122` + `blvm/models/vrnn.py:271-276`.
  *   mu_q, sd_q, mu_p, sd_p [rows=Tp*B, Z] (layout as above); step t of row b counts iff t*stride < x_sl[b]
