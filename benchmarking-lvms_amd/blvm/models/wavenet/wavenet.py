@@ -206,8 +206,9 @@ class WaveNet(BaseModel):
         `uniforms[t]` optionally supplies the head sampler's draws of frame t: the DMoL head's two, the categorical head's one [B]
         (its class k is fed back and returned as the float `dequantize(k)`).
         `cached=True` (the reference's TODO, arXiv:1611.09482): the same samples from per-block queues of past activations —
-        one new frame per block per step instead of the whole window; with the DMoL head and widths the decode kernel takes
-        (K10c: every frame in one launch) through `ops.wavenet_decode`, otherwise block by block (`_generate_cached`).
+        one new frame per block per step instead of the whole window; at the widths the decode kernel takes (K10c: every frame in
+        one launch) through `ops.wavenet_decode` (the DMoL head) or `ops.wavenet_cat_decode` (the categorical head with 16 <= V <=
+        1024 classes, V a multiple of 16), otherwise block by block (`_generate_cached`).
         With `cached=True`, `x` [B,P,1] is a prompt: the queues are primed from its last receptive-field samples (`_prime`) and
         frames P, P+1, ... are drawn.  `return_state=True` returns (x_hat, state); `state=` continues from one (generation in
         chunks; `uniforms` are indexed from 0 for every call)."""
@@ -223,12 +224,13 @@ class WaveNet(BaseModel):
                 if x.size(0) != n_samples:
                     raise ValueError(f"WaveNet.generate: prompt of {x.size(0)} rows for n_samples = {n_samples}")
                 state = self._prime(x)
-            one_launch = self._decode_kernel_applies()
+            run = self._generate_cached
+            if self._decode_kernel_applies():
+                run = self._generate_decode_kernel
+            elif self._cat_decode_kernel_applies():
+                run = self._generate_cat_decode_kernel
             if state is None and not return_state:
-                if one_launch:
-                    return self._generate_decode_kernel(n_samples, n_frames, uniforms)
-                return self._generate_cached(n_samples, n_frames, uniforms)
-            run = self._generate_decode_kernel if one_launch else self._generate_cached
+                return run(n_samples, n_frames, uniforms)
             x_hat, state = run(n_samples, n_frames, uniforms, state=state, want_state=True)
             return (x_hat, state) if return_state else x_hat
         dev = self.causal.conv.weight.device
@@ -249,6 +251,14 @@ class WaveNet(BaseModel):
         C, blk, lik = self.res_channels, self.res_stack.res_blocks[0], self.likelihood
         return (isinstance(lik, DiscretizedLogisticMixtureDense) and lik.y_dim == 1 and lik.out_features <= 32 and self.in_channels == 1
                 and C % 16 == 0 and blk.skip_channels % 16 == 0 and C <= 128 and blk.skip_channels <= 128 and len(self.res_stack.res_blocks) <= 64)  # fmt: skip
+
+    def _cat_decode_kernel_applies(self):
+        """The decode kernel's categorical head: 16 <= V <= 1024 in multiples of 16 (a larger softmax wants its head Linear split
+        across workgroups: block by block, `_generate_cached`), the widths of `_decode_kernel_applies`."""
+        C, blk, lik = self.res_channels, self.res_stack.res_blocks[0], self.likelihood
+        return (isinstance(lik, CategoricalDense) and 16 <= lik.y_dim <= 1024 and lik.y_dim % 16 == 0 and self.in_channels == 1
+                and self.n_stack_frames == 1 and C % 16 == 0 and blk.skip_channels % 16 == 0 and C <= 128 and blk.skip_channels <= 128
+                and len(self.res_stack.res_blocks) <= 64)  # fmt: skip
 
     @torch.no_grad()
     def _prime(self, x):
@@ -297,6 +307,33 @@ class WaveNet(BaseModel):
             raise ValueError("WaveNet.generate: the state does not come from the decode kernel's path at this batch size")
         # the kernel takes the phase of frame `state.n_frames` in every ring: any t0 equal to it modulo all dilations
         x, samples = ops.wavenet_decode_resume(*args, state.n_frames % math.lcm(*rs.dilations), state.samples, state.scratch)
+        return x.unsqueeze(-1), WaveNetDecodeState(state.scratch, state.rings, samples, state.n_frames + n_frames)
+
+    @torch.no_grad()
+    def _generate_cat_decode_kernel(self, n_samples: int, n_frames: int, uniforms=None, state=None, want_state: bool = False):
+        """The decode kernel with the categorical head: `uniforms[t]` [B] is the head's one draw of frame t (None: torch.rand on the
+        device); class k comes back as `likelihood.levels[k]`, the float `dequantize(k)` returns.  States as `_generate_decode_kernel`."""
+        lik, rs, B = self.likelihood, self.res_stack, n_samples
+        dev = self.causal.conv.weight.device
+        if uniforms is None:
+            u = torch.rand(n_frames, B, device=dev)
+        else:
+            u = torch.stack([a.reshape(B) for a in uniforms[:n_frames]]).to(device=dev, dtype=torch.float32)
+        t_in, blk = rs.in_transform, rs.res_blocks[0]
+        args = ((self.causal.conv.weight, self.causal.conv.bias), (t_in.weight.view(t_in.out_channels, -1), t_in.bias),
+                [b.kernel_params() for b in rs.res_blocks], rs.dilations,
+                (self.out_transform.linear.weight, self.out_transform.linear.bias), (lik.logits.weight, lik.logits.bias), lik.levels,
+                B, n_frames, blk.inv_std, 1.0 / self.variance_scale, u)  # fmt: skip
+        if state is None and not want_state:
+            return ops.wavenet_cat_decode(*args)[0].unsqueeze(-1)
+        if state is None:  # the zero start, keeping its scratch: the samples in front of frame 0 are zeros
+            x, _, scratch = ops.wavenet_cat_decode_start(*args)
+            samples = torch.cat([torch.zeros(B, 2, device=dev), x], 1)[:, -2:].contiguous()
+            state = WaveNetDecodeState(scratch, ops.wavenet_ring_views(scratch, rs.dilations, B, self.res_channels, blk.skip_channels), samples, n_frames)
+            return x.unsqueeze(-1), state
+        if state.scratch is None or tuple(state.samples.shape) != (B, 2):
+            raise ValueError("WaveNet.generate: the state does not come from the decode kernel's path at this batch size")
+        x, _, samples = ops.wavenet_cat_decode_resume(*args, state.n_frames % math.lcm(*rs.dilations), state.samples, state.scratch)
         return x.unsqueeze(-1), WaveNetDecodeState(state.scratch, state.rings, samples, state.n_frames + n_frames)
 
     @torch.no_grad()

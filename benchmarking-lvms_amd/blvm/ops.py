@@ -1504,6 +1504,81 @@ def wavenet_decode_resume(causal, in_transform, blocks_params, dilations, out_li
     return x, samples_out
 
 
+def _wavenet_cat_decode_pack(causal, in_transform, blocks_params, dilations, out_linear, head_linear, levels):
+    """The packed weight image of K10c with the categorical head (the head Linear [V,O] unpadded) and its sizes:
+    -> (lib, C, S, O, V, device, packed, dilations as a C array, levels [V] fp32 on the device)."""
+    lib = load()
+    C, S, O = in_transform[0].shape[0], blocks_params[0][2].shape[0] - in_transform[0].shape[0], out_linear[0].shape[0]
+    dev = causal[0].device
+    if causal[0].numel() != 2 * C:
+        raise NotImplementedError("libblvm_hip: wavenet_cat_decode is built for in_channels = n_stack_frames = 1")
+    hw, hb = head_linear
+    V = hw.shape[0]
+    if levels.numel() != V or hb.numel() != V:
+        raise ValueError(f"wavenet_cat_decode: a head of {V} classes with {hb.numel()} biases and {levels.numel()} levels")
+    parts = [*causal, *in_transform, *(p for blk in blocks_params for p in blk), *out_linear, hw, hb]
+    packed = torch.cat([_f32c(p).reshape(-1) for p in parts])
+    if packed.numel() != lib.blvm_wavenet_cat_decode_pack_floats(C, S, O, len(blocks_params), V):
+        raise ValueError("wavenet_cat_decode: parameter shapes do not match the packed layout")
+    return lib, C, S, O, V, dev, packed, _c_ints(dilations), _f32c(levels.to(dev)).reshape(V)
+
+
+def _wavenet_cat_decode_draws(u, n_frames: int, B: int):
+    if u is not None:
+        u = _f32c(u)
+        if tuple(u.shape) != (n_frames, B):
+            raise ValueError("wavenet_cat_decode: u must be [n_frames,B]")
+    return u
+
+
+@torch.no_grad()
+def wavenet_cat_decode_start(causal, in_transform, blocks_params, dilations, out_linear, head_linear, levels, B: int, n_frames: int,
+                             inv_std: float, skip_scale: float, u=None):
+    """`wavenet_cat_decode`, which also hands back its scratch buffer: -> (x [B,n_frames], k [B,n_frames] int32, scratch).  With the
+    last two samples the ring buffers in scratch (`wavenet_ring_views`) are the state after n_frames frames."""
+    lib, C, S, O, V, dev, packed, dil, levels = _wavenet_cat_decode_pack(causal, in_transform, blocks_params, dilations, out_linear,
+                                                                        head_linear, levels)  # fmt: skip
+    queues = torch.empty(lib.blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S), device=dev, dtype=torch.float32)
+    x = torch.empty(B, n_frames, device=dev, dtype=torch.float32)
+    k = torch.empty(B, n_frames, device=dev, dtype=torch.int32)
+    u = _wavenet_cat_decode_draws(u, n_frames, B)
+    check(lib.blvm_wavenet_cat_decode(ptr(packed), dil, len(dilations), B, C, S, O, V, n_frames, inv_std, skip_scale, ptr(levels), ptr(u),
+                                      ptr(queues), ptr(x), ptr(k), stream_ptr()), "blvm_wavenet_cat_decode")  # fmt: skip
+    return x, k, queues
+
+
+@torch.no_grad()
+def wavenet_cat_decode(causal, in_transform, blocks_params, dilations, out_linear, head_linear, levels, B: int, n_frames: int,
+                       inv_std: float, skip_scale: float, u=None):
+    """K10c with the categorical head: all frames of B utterances in one launch.  Weights as for `wavenet_decode`, head_linear the
+    [V,O] Linear of the softmax (16 <= V <= 1024, a multiple of 16), levels [V] the class values; u [n_frames,B] uniform draws (None:
+    the arg-max class).  -> (x [B,n_frames] = levels[k], k [B,n_frames] int32)."""
+    return wavenet_cat_decode_start(causal, in_transform, blocks_params, dilations, out_linear, head_linear, levels, B, n_frames, inv_std,
+                                    skip_scale, u)[:2]  # fmt: skip
+
+
+@torch.no_grad()
+def wavenet_cat_decode_resume(causal, in_transform, blocks_params, dilations, out_linear, head_linear, levels, B: int, n_frames: int,
+                              inv_std: float, skip_scale: float, u, t0: int, samples, scratch):
+    """`wavenet_cat_decode` from a state, as `wavenet_decode_resume` (the scratch buffer and the sample pair are the same for both
+    heads).  -> (x [B,n_frames], k [B,n_frames] int32, samples [B,2])."""
+    lib, C, S, O, V, dev, packed, dil, levels = _wavenet_cat_decode_pack(causal, in_transform, blocks_params, dilations, out_linear,
+                                                                        head_linear, levels)  # fmt: skip
+    if scratch.dtype != torch.float32 or scratch.numel() != lib.blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S):
+        raise ValueError("wavenet_cat_decode_resume: the scratch buffer does not belong to these shapes")
+    samples = _f32c(samples)
+    if tuple(samples.shape) != (B, 2):
+        raise ValueError("wavenet_cat_decode_resume: samples must be [B,2]")
+    x = torch.empty(B, n_frames, device=dev, dtype=torch.float32)
+    k = torch.empty(B, n_frames, device=dev, dtype=torch.int32)
+    samples_out = torch.empty(B, 2, device=dev, dtype=torch.float32)
+    u = _wavenet_cat_decode_draws(u, n_frames, B)
+    check(lib.blvm_wavenet_cat_decode_resume(ptr(packed), dil, len(dilations), B, C, S, O, V, n_frames, t0, inv_std, skip_scale,
+                                             ptr(levels), ptr(u), ptr(samples), ptr(scratch), ptr(x), ptr(k), ptr(samples_out),
+                                             stream_ptr()), "blvm_wavenet_cat_decode_resume")  # fmt: skip
+    return x, k, samples_out
+
+
 def stcn_generate_pack(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear,
                        head_linear, dense: bool, S: int, num_mix: int):
     """The packed weight image of K10d (`blvm_stcn_generate`) and the host arrays that travel with it.  causal / in_transform /

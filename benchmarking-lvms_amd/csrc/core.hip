@@ -181,7 +181,7 @@ extern "C" int blvm_async_errors_take(unsigned* last_code) {
   return (int)fresh;
 }
 
-extern "C" int blvm_version(void) { return 200; /* 0.2.0: blvm_cat_fwd / _bwd / _bwd_workspace_floats / _sample (K7d) */ }
+extern "C" int blvm_version(void) { return 201; /* 0.2.1: blvm_wavenet_cat_decode / _resume / _pack_floats (K10c with the categorical head) */ }
 
 extern "C" const char* blvm_last_error(void) { return blvm::g_err; }
 

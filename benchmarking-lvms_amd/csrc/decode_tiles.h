@@ -4,6 +4,7 @@
 // mix_sample_kernel (dmol.hip) all end in the same draw, and the two convolutional decoders walk the same gated residual block.
 // Each of these is written once here; a kernel supplies its buffers, its widths and the last line of an epilogue.
 //   mix_pick / logistic_draw   the DMoL draw
+//   cat_pick                   the categorical draw of K10c's softmax head
 //   tile16 / tile_layer        "16x16 tiles over the waves, product from an LDS operand, + bias, epilogue"
 //   gated_ring_block           one gated residual block on one new frame, with its ring buffer
 // Nothing here holds a barrier the caller does not see, except gated_ring_block, whose four are part of its contract.
@@ -46,6 +47,57 @@ __device__ __forceinline__ int mix_pick(const float* p, int K, const float* u) {
 __device__ __forceinline__ float logistic_draw(float loc, float raw, float v, float log_eps) {
   const float x = loc + expf(fmaxf(raw, log_eps)) * (logf(v) - logf(1.f - v));
   return fminf(fmaxf(x, -1.f), 1.f);
+}
+
+// ---- the categorical draw (the rule of tests/cat_cases.py::check_draws) ---------------------------------------------------------
+// One class from the V logits l[0..V) of a row in LDS, by the LANES consecutive lanes (a power of two <= 64, aligned) that call it
+// together; every lane returns the class.  Lane j owns the classes [j chunk, (j + 1) chunk), chunk = ceil(V / LANES).
+// !noisy: the arg-max, first maximum (as torch.argmax; 0 when no logit compares above -inf).
+// noisy: inverse CDF of e = exp(l - max l) at u — the first class whose prefix sum reaches u * total, V - 1 if none does (u next to
+// 1, or a non-finite logit: the class comes from comparisons only, never from arithmetic on a logit, so it is always in [0, V)).
+// The order of every sum is fixed — in a lane class after class, across lanes a Hillis-Steele scan — so two launches agree to the
+// bit; no atomics.  l is overwritten with e.  No barrier: a lane re-reads only what it wrote itself.
+template <int LANES>
+__device__ __forceinline__ int cat_pick(float* l, int V, bool noisy, float u) {
+  const int j = threadIdx.x & (LANES - 1);
+  const int chunk = (V + LANES - 1) / LANES;
+  const int lo = min(j * chunk, V), hi = min(lo + chunk, V);
+  float bv = -INFINITY;
+  int best = lo < V ? lo : V - 1;
+  for (int k = lo; k < hi; ++k) {
+    const float s = l[k];
+    if (s > bv) { bv = s; best = k; }
+  }
+#pragma unroll
+  for (int m = LANES / 2; m > 0; m >>= 1) {
+    const float ov = __shfl_xor(bv, m, LANES);
+    const int oi = __shfl_xor(best, m, LANES);
+    if (ov > bv || (ov == bv && oi < best)) { bv = ov; best = oi; }
+  }
+  if (!noisy) return best;
+  float part = 0.f;
+  for (int k = lo; k < hi; ++k) {
+    const float e = expf(l[k] - bv);
+    l[k] = e;
+    part += e;
+  }
+  float inc = part;  // -> the prefix sum up to and including this lane's classes
+#pragma unroll
+  for (int d = 1; d < LANES; d <<= 1) {
+    const float o = __shfl_up(inc, d, LANES);
+    if (j >= d) inc += o;
+  }
+  const float target = u * __shfl(inc, LANES - 1, LANES);
+  float cum = __shfl_up(inc, 1, LANES);
+  if (j == 0) cum = 0.f;
+  int found = V;
+  for (int k = lo; k < hi; ++k) {
+    cum += l[k];
+    if (found == V && cum >= target) found = k;
+  }
+#pragma unroll
+  for (int m = LANES / 2; m > 0; m >>= 1) found = min(found, __shfl_xor(found, m, LANES));
+  return found < V ? found : V - 1;
 }
 
 // ---- the tile layer ----------------------------------------------------------------------------------------------------------

@@ -17,6 +17,11 @@
 //
 // The any-width block, the tile layers and the draw are the ones K10d (stcn_decode.hip) uses: decode_tiles.h.  The compile-time-
 // width path below (block_fast) is this kernel's own.
+//
+// Two heads (a template parameter, so each keeps its own code): the DMoL head (3 * num_mix <= 32 outputs, Gumbel-max + logistic
+// draw) and the categorical head of the original paper (K7d's softmax over V classes, 16 <= V <= 1024): its Linear goes through the
+// same tile layer into an LDS logits buffer [16][V + 4], 32 lanes per row draw one class (cat_pick, decode_tiles.h), and the class
+// is fed back and written out as levels[k] — the model's table, copied to LDS once; no arithmetic on it.
 #include "common.h"
 #include "decode_tiles.h"
 
@@ -33,7 +38,7 @@ struct DecodeLayout {
   size_t conv_b, rs_w, rs_b;  // relative to a block's start (conv_w is at 0)
 };
 
-__host__ __device__ inline DecodeLayout decode_layout(int C, int S, int O, int n_blocks) {
+__host__ __device__ inline DecodeLayout decode_layout(int C, int S, int O, int n_blocks, int head_rows = DEC_HEAD_ROWS) {
   DecodeLayout L;
   size_t o = 0;
   L.causal_w = o; o += (size_t)C * 2;  // [C,1,2]
@@ -47,8 +52,8 @@ __host__ __device__ inline DecodeLayout decode_layout(int C, int S, int O, int n
   L.blocks = o; o += L.block_stride * n_blocks;
   L.out_w = o; o += (size_t)O * S;
   L.out_b = o; o += O;
-  L.head_w = o; o += (size_t)DEC_HEAD_ROWS * O;
-  L.head_b = o; o += DEC_HEAD_ROWS;
+  L.head_w = o; o += (size_t)head_rows * O;
+  L.head_b = o; o += head_rows;
   L.total = o;
   return L;
 }
@@ -68,6 +73,23 @@ struct DecodeArgs {
   const float* x_in;  // [B,2] (previous, newest) sample in front of frame t0
   float* x_state;     // [B,2] the same pair after the last frame
 };
+
+// The categorical head: u is [n_frames,B] (one draw per frame and row, NULL: the arg-max class); num_mix, log_eps and v are unused.
+struct CatDecodeArgs : DecodeArgs {
+  int V;                // classes: the head Linear is [V,O] in the packed image
+  const float* levels;  // [V] the value of class k, fed back and written to x_out as it stands
+  int* k_out;           // [B,n_frames] the classes, or NULL
+};
+
+struct DmolHead {
+  using Args = DecodeArgs;
+  static constexpr bool categorical = false;
+};
+struct CatHead {
+  using Args = CatDecodeArgs;
+  static constexpr bool categorical = true;
+};
+constexpr int CAT_MIN_V = 16, CAT_MAX_V = 1024, CAT_LOGIT_PAD = 4;
 
 // LDS-only barrier: waits for this wave's LDS traffic, not for its global loads.  No thread of the decoder ever reads
 // global memory another thread wrote (ring-buffer elements are read and rewritten by the same thread, weights and draws are
@@ -96,9 +118,9 @@ __device__ __forceinline__ f32x4 tile_from_regs(const float* __restrict__ A, int
 // the NEXT block in registers, loaded while the current block computes.  CC == 0: any width, loads where they are used.
 // RESUME: no steady-state prologue — rings and the last two samples are the caller's, frame t is absolute frame t0 + t, and
 // the sample pair is handed back; with the rings left in scratch that is the whole state.  A separate instantiation, so the
-// zero-start entry keeps its code.
-template <int NW, int CC, int SS, bool RESUME>
-__global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
+// zero-start entry keeps its code.  HEAD: DmolHead or CatHead, separate instantiations for the same reason.
+template <int NW, int CC, int SS, bool RESUME, class HEAD>
+__global__ __launch_bounds__(NW * 64) void wn_decode_kernel(typename HEAD::Args a) {
   extern __shared__ __align__(16) float smem[];
   constexpr int NT = NW * 64;
   const int C = CC > 0 ? CC : a.C, S = SS > 0 ? SS : a.S, O = a.O, B = a.B;
@@ -109,16 +131,24 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
   float* sAct = sPre + DEC_ROWS * ldP; // [16][max(C,O)+4]
   float* sH = sAct + DEC_ROWS * ldA;   // [16][C]     current block input
   float* sSkip = sH + DEC_ROWS * C;    // [16][S+4]
-  float* sPar = sSkip + DEC_ROWS * ldS;  // [16][32]  head outputs
-  float* sX = sPar + DEC_ROWS * DEC_HEAD_ROWS;  // [16][2] previous / newest sample
+  const int head_rows = [&] {
+    if constexpr (HEAD::categorical) return a.V;
+    else return DEC_HEAD_ROWS;
+  }();
+  const int ldL = HEAD::categorical ? head_rows + CAT_LOGIT_PAD : DEC_HEAD_ROWS;
+  float* sPar = sSkip + DEC_ROWS * ldS;  // [16][32]  head outputs; categorical: [16][V+4] the logits
+  float* sX = sPar + DEC_ROWS * ldL;     // [16][2] previous / newest sample
+  [[maybe_unused]] float* sLev = sX + DEC_ROWS * 2;  // categorical: [V] the class values
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, cc = lane & 15;
   const int b0 = blockIdx.x * DEC_ROWS;
-  const DecodeLayout L = decode_layout(C, S, O, a.n_blocks);
+  const DecodeLayout L = decode_layout(C, S, O, a.n_blocks, head_rows);
   const float* w = a.w;
 
   const int t0 = RESUME ? a.t0 : 0;
   for (int i = tid; i < DEC_ROWS * 2; i += NT) sX[i] = (RESUME && b0 + i / 2 < B) ? a.x_in[(size_t)2 * b0 + i] : 0.f;
+  if constexpr (HEAD::categorical)
+    for (int i = tid; i < head_rows; i += NT) sLev[i] = a.levels[i];
   __syncthreads();
 
   // causal conv on (previous, newest) sample -> 1x1 in_transform -> sH; clears the skip accumulators
@@ -303,19 +333,38 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(DecodeArgs a) {
     __syncthreads();
     tile_layer<NW, false>(sSkip, ldS, w + L.out_w, S, 0, O / 16, w + L.out_b, [&](int row, int o, float val) { sAct[row * ldA + o] = fmaxf(val, 0.f); });
     __syncthreads();
-    tile_layer<NW, false>(sAct, ldA, w + L.head_w, O, 0, DEC_HEAD_ROWS / 16, w + L.head_b, [&](int row, int o, float val) { sPar[row * DEC_HEAD_ROWS + o] = val; });
-    __syncthreads();
-    if (tid < DEC_ROWS && b0 + tid < B) {
-      // Gumbel-max component pick + clamped logistic draw (decode_tiles.h)
-      const float* p = sPar + tid * DEC_HEAD_ROWS;
-      const int K = a.num_mix;
-      const size_t f = (size_t)t * B + b0 + tid;
-      const int best = mix_pick(p, K, a.u != nullptr ? a.u + f * K : nullptr);
-      float x = p[K + best];
-      if (a.v != nullptr) x = logistic_draw(x, p[2 * K + best], a.v[f], a.log_eps);
-      a.x_out[(size_t)(b0 + tid) * a.n_frames + t] = x;
-      sX[2 * tid] = sX[2 * tid + 1];
-      sX[2 * tid + 1] = x;
+    if constexpr (HEAD::categorical) {
+      // logits -> one class per row, drawn by the row's 32 lanes (rows >= B draw too, from finite logits, and write nothing)
+      constexpr int LANES = NT / DEC_ROWS;
+      static_assert(LANES == 32, "the categorical draw gives each of the 16 rows half a wave");
+      const int row = tid / LANES;
+      const bool live = b0 + row < B, noisy = a.u != nullptr;
+      const float u = (noisy && live) ? a.u[(size_t)t * B + b0 + row] : 0.f;  // issued ahead of the head's product
+      tile_layer<NW, false>(sAct, ldA, w + L.head_w, O, 0, head_rows / 16, w + L.head_b, [&](int r, int o, float val) { sPar[r * ldL + o] = val; });
+      __syncthreads();
+      const int k = cat_pick<LANES>(sPar + row * ldL, head_rows, noisy, u);
+      if ((tid & (LANES - 1)) == 0 && live) {
+        const float x = sLev[k];
+        a.x_out[(size_t)(b0 + row) * a.n_frames + t] = x;
+        if (a.k_out != nullptr) a.k_out[(size_t)(b0 + row) * a.n_frames + t] = k;
+        sX[2 * row] = sX[2 * row + 1];
+        sX[2 * row + 1] = x;
+      }
+    } else {
+      tile_layer<NW, false>(sAct, ldA, w + L.head_w, O, 0, DEC_HEAD_ROWS / 16, w + L.head_b, [&](int row, int o, float val) { sPar[row * DEC_HEAD_ROWS + o] = val; });
+      __syncthreads();
+      if (tid < DEC_ROWS && b0 + tid < B) {
+        // Gumbel-max component pick + clamped logistic draw (decode_tiles.h)
+        const float* p = sPar + tid * DEC_HEAD_ROWS;
+        const int K = a.num_mix;
+        const size_t f = (size_t)t * B + b0 + tid;
+        const int best = mix_pick(p, K, a.u != nullptr ? a.u + f * K : nullptr);
+        float x = p[K + best];
+        if (a.v != nullptr) x = logistic_draw(x, p[2 * K + best], a.v[f], a.log_eps);
+        a.x_out[(size_t)(b0 + tid) * a.n_frames + t] = x;
+        sX[2 * tid] = sX[2 * tid + 1];
+        sX[2 * tid + 1] = x;
+      }
     }
     __syncthreads();
   }
@@ -341,9 +390,23 @@ __global__ __launch_bounds__(256) void wn_ring_fill_kernel(const float4* __restr
   ring[(size_t)slot * row4 + e] = src[idx];
 }
 
-inline size_t decode_lds_bytes(int C, int S, int O) {
+// V == 0: the DMoL head; else the categorical head's logits [16][V+4] in place of the 32 head outputs, and its V class values
+inline size_t decode_lds_bytes(int C, int S, int O, int V) {
   const int CA = C > O ? C : O;
-  return sizeof(float) * ((size_t)DEC_ROWS * ((2 * C + 4) + 2 * C + (CA + 4) + C + (S + 4) + DEC_HEAD_ROWS) + 2 * DEC_ROWS);
+  const size_t head = V > 0 ? (size_t)DEC_ROWS * (V + CAT_LOGIT_PAD) + V : (size_t)DEC_ROWS * DEC_HEAD_ROWS;
+  return sizeof(float) * ((size_t)DEC_ROWS * ((2 * C + 4) + 2 * C + (CA + 4) + C + (S + 4)) + head + 2 * DEC_ROWS);
+}
+
+template <class HEAD>
+int decode_launch(bool resume, bool even, const typename HEAD::Args& a, size_t lds, hipStream_t stream) {
+  constexpr int NW = 8;
+  auto kern = resume ? wn_decode_kernel<NW, 0, 0, true, HEAD> : wn_decode_kernel<NW, 0, 0, false, HEAD>;
+  if (even && a.C == 64 && a.S == 64) kern = resume ? wn_decode_kernel<NW, 64, 64, true, HEAD> : wn_decode_kernel<NW, 64, 64, false, HEAD>;
+  else if (even && a.C == 32 && a.S == 32) kern = resume ? wn_decode_kernel<NW, 32, 32, true, HEAD> : wn_decode_kernel<NW, 32, 32, false, HEAD>;
+  if (lds > 64 * 1024) BLVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)((a.B + DEC_ROWS - 1) / DEC_ROWS)), dim3(NW * 64), lds, stream, a);
+  BLVM_CHECK_LAUNCH("wavenet_decode");
+  return BLVM_OK;
 }
 
 }  // namespace
@@ -364,21 +427,30 @@ extern "C" size_t blvm_wavenet_decode_ring_offset_floats(int n_blocks, int C, in
   return (size_t)n_blocks * ((size_t)2 * C * 2 * C + (size_t)(C + S) * C);
 }
 
-// resume: the kernel starts from the rings in `scratch` and x_in at absolute frame t0 and hands the sample pair back
+// resume: the kernel starts from the rings in `scratch` and x_in at absolute frame t0 and hands the sample pair back.
+// V > 0: the categorical head (levels [V], u [n_frames,B], k_out or NULL; num_mix, log_eps and v unused), V == 0: the DMoL head.
 static int decode_run(bool resume, const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int num_mix,
                       int n_frames, int t0, float inv_std, float skip_scale, float log_eps, const float* u, const float* v,
-                      const float* x_in, float* scratch, float* x_out, float* x_state, void* stream) {
+                      const float* x_in, float* scratch, float* x_out, float* x_state, void* stream, int V = 0,
+                      const float* levels = nullptr, int32_t* k_out = nullptr) {
   using namespace blvm;
+  const bool cat = V > 0;
   BLVM_REQUIRE(packed && dilations && scratch && x_out && aligned16(packed) && aligned16(scratch), "wavenet_decode: NULL or misaligned argument");
   BLVM_REQUIRE(B > 0 && n_frames >= 0 && n_blocks > 0 && n_blocks <= DEC_MAX_BLOCKS, "wavenet_decode: need B > 0, 1 <= n_blocks <= %d", DEC_MAX_BLOCKS);
   BLVM_REQUIRE(C > 0 && S > 0 && O > 0 && C % 16 == 0 && S % 16 == 0 && O % 16 == 0, "wavenet_decode: C, S, O must be multiples of 16");
-  BLVM_REQUIRE(num_mix > 0 && 3 * num_mix <= DEC_HEAD_ROWS, "wavenet_decode: num_mix must be in [1, %d]", DEC_HEAD_ROWS / 3);
-  BLVM_REQUIRE((u == nullptr) == (v == nullptr), "wavenet_decode: u and v are given together (both NULL: the mode)");
+  if (cat) {
+    BLVM_REQUIRE(levels, "wavenet_cat_decode: NULL levels");
+  } else {
+    BLVM_REQUIRE(num_mix > 0 && 3 * num_mix <= DEC_HEAD_ROWS, "wavenet_decode: num_mix must be in [1, %d]", DEC_HEAD_ROWS / 3);
+    BLVM_REQUIRE((u == nullptr) == (v == nullptr), "wavenet_decode: u and v are given together (both NULL: the mode)");
+  }
   if (resume) BLVM_TRY(check_resume("wavenet_decode_resume", "sample", "n_frames", t0, n_frames, x_in, x_state));
-  const size_t lds = decode_lds_bytes(C, S, O);
+  const size_t lds = decode_lds_bytes(C, S, O, V);
+  if (cat) BLVM_REQUIRE(lds <= 160 * 1024, "wavenet_cat_decode: C=%d, S=%d, O=%d, V=%d need %zu bytes of LDS (> 160 KB)", C, S, O, V, lds);
   BLVM_REQUIRE(lds <= 160 * 1024, "wavenet_decode: C=%d, S=%d, O=%d need %zu bytes of LDS (> 160 KB)", C, S, O, lds);
   if (n_frames == 0) return resume ? hand_back_state(x_state, x_in, (size_t)2 * B, static_cast<hipStream_t>(stream)) : BLVM_OK;
-  DecodeArgs a;
+  CatDecodeArgs a;  // (the DMoL kernels take its base)
+  a.V = V; a.levels = levels; a.k_out = k_out;
   a.w = packed;
   for (int i = 0; i < n_blocks; ++i) {
     BLVM_REQUIRE(dilations[i] >= 1, "wavenet_decode: dilation %d of block %d", dilations[i], i);
@@ -390,7 +462,7 @@ static int decode_run(bool resume, const float* packed, const int* dilations, in
   a.u = u; a.v = v; a.x_out = x_out;
   a.t0 = t0; a.x_in = x_in; a.x_state = x_state;
   // scratch = [T16 operand copies of the blocks' matrices | ring buffers]
-  const DecodeLayout L = decode_layout(C, S, O, n_blocks);
+  const DecodeLayout L = decode_layout(C, S, O, n_blocks, cat ? V : DEC_HEAD_ROWS);
   const size_t wt_stride = (size_t)2 * C * 2 * C + (size_t)(C + S) * C;
   for (int i = 0; i < n_blocks; ++i) {
     const float* bw = packed + L.blocks + (size_t)i * L.block_stride;
@@ -400,15 +472,9 @@ static int decode_run(bool resume, const float* packed, const int* dilations, in
   }
   a.wt = scratch;
   a.queues = scratch + (size_t)n_blocks * wt_stride;
-  constexpr int NW = 8;
   const bool even = n_blocks % 2 == 0;
-  auto kern = resume ? wn_decode_kernel<NW, 0, 0, true> : wn_decode_kernel<NW, 0, 0, false>;
-  if (even && C == 64 && S == 64) kern = resume ? wn_decode_kernel<NW, 64, 64, true> : wn_decode_kernel<NW, 64, 64, false>;
-  else if (even && C == 32 && S == 32) kern = resume ? wn_decode_kernel<NW, 32, 32, true> : wn_decode_kernel<NW, 32, 32, false>;
-  if (lds > 64 * 1024) BLVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)((B + DEC_ROWS - 1) / DEC_ROWS)), dim3(NW * 64), lds, static_cast<hipStream_t>(stream), a);
-  BLVM_CHECK_LAUNCH("wavenet_decode");
-  return BLVM_OK;
+  if (cat) return decode_launch<CatHead>(resume, even, a, lds, static_cast<hipStream_t>(stream));
+  return decode_launch<DmolHead>(resume, even, a, lds, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int blvm_wavenet_decode(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O,
@@ -424,6 +490,39 @@ extern "C" int blvm_wavenet_decode_resume(const float* packed, const int* dilati
                                           float* x_state, void* stream) {
   return decode_run(true, packed, dilations, n_blocks, B, C, S, O, num_mix, n_frames, t0, inv_std, skip_scale, log_eps, u, v, x_in,
                     scratch, x_out, x_state, stream);
+}
+
+// The categorical head is built for 16 <= V <= 1024 in multiples of 16: one workgroup streams the whole head weight per frame, which
+// at V = 65 536 needs a head split across workgroups — another kernel.
+static int cat_widths_ok(int V) {
+  if (V < blvm::CAT_MIN_V || V > blvm::CAT_MAX_V || V % 16 != 0) {
+    blvm::set_error("wavenet_cat_decode: V = %d classes: the one-launch categorical head is built for %d <= V <= %d, V a multiple of 16",
+                    V, blvm::CAT_MIN_V, blvm::CAT_MAX_V);
+    return BLVM_ENOSUP;
+  }
+  return BLVM_OK;
+}
+
+extern "C" size_t blvm_wavenet_cat_decode_pack_floats(int C, int S, int O, int n_blocks, int V) {
+  if (C <= 0 || S <= 0 || O <= 0 || n_blocks <= 0 || V <= 0) return 0;
+  return blvm::decode_layout(C, S, O, n_blocks, V).total;
+}
+
+extern "C" int blvm_wavenet_cat_decode(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int V,
+                                       int n_frames, float inv_std, float skip_scale, const float* levels, const float* u,
+                                       float* scratch, float* x_out, int32_t* k_out, void* stream) {
+  BLVM_TRY(cat_widths_ok(V));
+  return decode_run(false, packed, dilations, n_blocks, B, C, S, O, 0, n_frames, 0, inv_std, skip_scale, 0.f, u, nullptr, nullptr, scratch,
+                    x_out, nullptr, stream, V, levels, k_out);
+}
+
+extern "C" int blvm_wavenet_cat_decode_resume(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int V,
+                                              int n_frames, int t0, float inv_std, float skip_scale, const float* levels,
+                                              const float* u, const float* x_in, float* scratch, float* x_out, int32_t* k_out,
+                                              float* x_state, void* stream) {
+  BLVM_TRY(cat_widths_ok(V));
+  return decode_run(true, packed, dilations, n_blocks, B, C, S, O, 0, n_frames, t0, inv_std, skip_scale, 0.f, u, nullptr, x_in, scratch,
+                    x_out, x_state, stream, V, levels, k_out);
 }
 
 extern "C" int blvm_wavenet_decode_ring_fill(const float* h, int L, int B, int C, int dilation, int t0, float* ring, void* stream) {

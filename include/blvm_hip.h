@@ -646,6 +646,26 @@ int blvm_wavenet_decode_resume(const float* packed, const int* dilations, int n_
                                int n_frames, int t0, float inv_std, float skip_scale, float log_eps, const float* u,
                                const float* v, const float* x_in, float* scratch, float* x_out, float* x_state, void* stream);
 
+/* K10c  The same one-launch sampling with the categorical head (the softmax over V classes of K7d), from an all-zero start and from
+ *   a state.  Arguments as for the DMoL pair above, except:
+ *   V, levels, u replace num_mix, log_eps, u, v.  16 <= V <= 1024, V a multiple of 16 (anything else: BLVM_ENOSUP before any
+ *     launch).  The packed image ends in the head Linear w [V,O], b [V] (no padding): blvm_wavenet_cat_decode_pack_floats floats.
+ *     levels [V]: the value of class k — it is fed back as the next input and written to x_out as it stands (no arithmetic).
+ *     u [n_frames,B]: one uniform draw per frame and row, or NULL.
+ *   Per frame: ... -> head Linear -> logits l [V] -> NULL u: the arg-max class, first maximum; else the inverse CDF of
+ *     e = exp(l - max l): the first class whose prefix sum reaches u * total, class V - 1 if none does.  The order of the sums is
+ *     fixed: two calls on the same inputs agree to the bit.
+ *   k_out [B,n_frames] int32 (=): the classes, or NULL.  x_out [B,n_frames] = levels[k].
+ *   scratch, the rings, blvm_wavenet_decode_ring_fill, x_in / x_state: shared with the DMoL pair unchanged, so a state primed for
+ *     one head serves the other. */
+size_t blvm_wavenet_cat_decode_pack_floats(int C, int S, int O, int n_blocks, int V);
+int blvm_wavenet_cat_decode(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int V, int n_frames,
+                            float inv_std, float skip_scale, const float* levels, const float* u, float* scratch, float* x_out,
+                            int32_t* k_out, void* stream);
+int blvm_wavenet_cat_decode_resume(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int V,
+                                   int n_frames, int t0, float inv_std, float skip_scale, const float* levels, const float* u,
+                                   const float* x_in, float* scratch, float* x_out, int32_t* k_out, float* x_state, void* stream);
+
 /* K10d  Ancestral sampling from the STCN: all T steps of all rows in ONE launch, from an all-zero past.  The reference leaves
  *   `STCN.generate` unimplemented (`blvm/models/stcn/stcn.py:435-442`); this is the generative model its `forward` / `infer` define
  *   (`stcn.py:299-326, 389-409`) with every latent drawn from its prior.  Per step t: causal conv (kernel 2) of the stacks x_{t-2},
