@@ -14,6 +14,7 @@
 
 #include <vector>
 
+#include "bf16_slice.h"
 #include "common.h"
 
 namespace blvm {
@@ -236,7 +237,20 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
 // (no __syncthreads: its fence would drain the DMAs still in flight) makes every wave's stage s visible and retires every read of
 // stage s - 1, then the DMAs of stage s + WST - 1 go into the slot of s - 1 and the MFMAs consume stage s.  Reads are conflict-free
 // ds_read_b32: lanes 0-31 read 32 consecutive floats of row k, lanes 32-63 row k + 1 (the other lane group of the instruction).
-// The MFMA chain per output runs the same k order as gemm_tile, so an unsplit launch matches it bit for bit.
+// Two bodies share everything but the fragment gather and the MFMA block:
+//  * SLICED = false: the exact fp32 chain on v_mfma_f32_32x32x2_f32 in gemm_tile's k order, so an unsplit launch matches gemm_tile
+//    bit for bit.  It serves the unsplit (split_k == 1, deterministic) launches of gemm_f32.
+//  * SLICED = true: every operand is split in registers into three bf16 slices (bf16_slice.h: x = hi + mid + lo exactly) and a
+//    16-row stage of a 32 x 32 output is six v_mfma_f32_32x32x16_bf16 with fp32 accumulation instead of eight fp32 MFMAs of twice
+//    the cycles each.  Term order per stage and output tile (0 = hi, 1 = mid, 2 = lo):
+//        a0 b0, a0 b1, a1 b0, a0 b2, a1 b1, a2 b0
+//    a1 b2, a2 b1, a2 b2 (each < 2^-22 of the product, 2^-24 in all on average) are dropped.  The six go into ONE accumulator that
+//    starts from zero in every stage, and the stage's sum is added to the running sum with fp32 VALU adds: every update of the
+//    bf16 MFMA's accumulator errs toward minus infinity by ~0.015 ulp of the accumulator, which on a running sum over the whole k
+//    range is a one-signed error that grows with it (measured) and on a 16-row sum is 3e-8 of the result.  The
+//    tiles of a wave go one after the other, so one stage sum (16 registers) is live beside the MFMAs of the next.  The k
+//    grouping differs from gemm_tile's, so results agree with it to rounding, not bit for bit; an infinite operand gives NaN.
+//    The grouped launch and gemm_f32 with split_k != 1 take this body.
 // Requirements (host-checked; others take gemm_tile): 16-byte aligned operands, M, N, ldd, lda multiples of 4.  Columns past M / N
 // are staged from a clamped (valid) column and never stored; rows past the k range are staged from a clamped row and zeroed at read.
 constexpr int WBM = 128, WBK = 16;         // square tile, k rows per stage
@@ -252,6 +266,10 @@ __device__ __forceinline__ void ring_barrier() {  // (the LDS reads of the stage
   asm volatile("" ::: "memory");
 }
 
+typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t wg_u32x4 __attribute__((ext_vector_type(4)));
+
+template <bool SLICED>
 __device__ __forceinline__ void wgrad_tile(const GemmArgs& g, const int bx, const int by, const int bz, const int nz) {
   constexpr int SLOT = 2 * WBK * WBM;  // floats per stage: D rows then Act rows
   __shared__ __attribute__((aligned(16))) float ring[WST * SLOT];
@@ -294,46 +312,6 @@ __device__ __forceinline__ void wgrad_tile(const GemmArgs& g, const int bx, cons
   const bool do_csum = g.colsum != nullptr && bx == 0;  // bias gradient: the first column block also sums its D tiles over k
   float csum = 0.f;
 
-  // one stage: 8 k-pairs x 2 x 2 MFMAs; the operands of pair p + 1 are requested before the MFMAs of pair p (as in gemm_tile).
-  // MASK: the last stage of a ragged k range — rows >= nv are clamped copies and enter as zeros
-  auto stage = [&](const float* sa, auto mask_tag, int nv) {
-    constexpr bool MASK = decltype(mask_tag)::value;
-    const float* sb = sa + WBK * WBM;
-    if (do_csum) {  // 2 threads per column, 8 rows each
-#pragma unroll
-      for (int kk = 0; kk < WBK / 2; ++kk) {
-        const int k = kk * 2 + (tid >> 7);
-        const float v = sa[k * WBM + (tid & 127)];
-        csum += (!MASK || k < nv) ? v : 0.f;
-      }
-    }
-    float a[2][2], b[2][2];
-    auto lds_ab = [&](int kk, float (&a_)[2], float (&b_)[2]) {
-      const bool ok = !MASK || kk + lh < nv;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const float v = sa[(kk + lh) * WBM + wm * 64 + i * 32 + li];
-        a_[i] = ok ? v : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const float v = sb[(kk + lh) * WBM + wn * 64 + j * 32 + li];
-        b_[j] = ok ? v : 0.f;
-      }
-    };
-    lds_ab(0, a[0], b[0]);
-#pragma unroll
-    for (int p = 0; p < WBK / 2; ++p) {
-      if (p + 1 < WBK / 2) lds_ab(2 * (p + 1), a[(p + 1) & 1], b[(p + 1) & 1]);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[p & 1][i], b[p & 1][j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    }
-  };
-
 #pragma unroll
   for (int s = 0; s < WST - 1; ++s)
     if (s < nst) issue(s);
@@ -345,11 +323,129 @@ __device__ __forceinline__ void wgrad_tile(const GemmArgs& g, const int bx, cons
     if (s + WST - 1 < nst) issue(s + WST - 1);  // into the slot of stage s - 1
     return ring + (s % WST) * SLOT;
   };
-  // the ragged last stage is peeled: a masked stage inside the loop makes the compiler shuttle the accumulators between register
-  // files on every k-step
   const int nfull = (kend - kbeg) / WBK;
-  for (int s = 0; s < nfull; ++s) stage(advance(s), std::false_type{}, WBK);
-  if (nfull < nst) stage(advance(nfull), std::true_type{}, kend - kbeg - nfull * WBK);
+  if constexpr (SLICED) {
+    // Lane l holds row l & 31 and the 8 consecutive k from 8 (l >> 5) of a 32x32x16 fragment: eight ds_read_b32 down one LDS column
+    // per fragment (32 lanes read 32 consecutive floats of a row: conflict-free), 32 per stage as in the exact body.  The raw
+    // values of stage s + 1 are requested BEFORE the MFMAs of stage s (its barrier, DMA issue and LDS round trip run under them)
+    // and sliced after them, over the fragments they have consumed: one set of fragment registers, no copies.
+    float ra[2][8], rb[2][8];
+    // MASK: the last stage of a ragged k range — rows >= nv are clamped copies and enter as zeros, before slicing
+    auto gather = [&](const float* sa, auto mask_tag, int nv) {
+      constexpr bool MASK = decltype(mask_tag)::value;
+      const float* sb = sa + WBK * WBM;
+      if (do_csum) {  // 2 threads per column, 8 rows each: the bias gradient stays an fp32 sum of the unsliced values
+#pragma unroll
+        for (int kk = 0; kk < WBK / 2; ++kk) {
+          const int k = kk * 2 + (tid >> 7);
+          const float v = sa[k * WBM + (tid & 127)];
+          csum += (!MASK || k < nv) ? v : 0.f;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int k = 8 * lh + q;
+        const bool ok = !MASK || k < nv;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const float va = sa[k * WBM + wm * 64 + i * 32 + li], vb = sb[k * WBM + wn * 64 + i * 32 + li];
+          ra[i][q] = ok ? va : 0.f;
+          rb[i][q] = ok ? vb : 0.f;
+        }
+      }
+    };
+    auto fetch = [&](int s) {
+      const float* sa = advance(s);
+      if (s < nfull) gather(sa, std::false_type{}, WBK);
+      else gather(sa, std::true_type{}, kend - kbeg - nfull * WBK);
+    };
+    auto slice = [&](const float (&r)[8], wg_bf16x8 (&f)[3]) {
+      Slices3 c[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) c[q] = slice3(r[q]);
+      wg_u32x4 h, m, l;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        h[q] = slice_pack(c[2 * q].hi, c[2 * q + 1].hi);
+        m[q] = slice_pack(c[2 * q].mid, c[2 * q + 1].mid);
+        l[q] = slice_pack(c[2 * q].lo, c[2 * q + 1].lo);
+      }
+      f[0] = __builtin_bit_cast(wg_bf16x8, h);
+      f[1] = __builtin_bit_cast(wg_bf16x8, m);
+      f[2] = __builtin_bit_cast(wg_bf16x8, l);
+    };
+    wg_bf16x8 fa[2][3], fb[2][3];
+    auto slice_all = [&]() {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        slice(ra[i], fa[i]);
+        slice(rb[i], fb[i]);
+      }
+    };
+    fetch(0);
+    slice_all();
+    for (int s = 0; s < nst; ++s) {
+      if (s + 1 < nst) fetch(s + 1);
+      constexpr int TA[6] = {0, 0, 1, 0, 1, 2}, TB[6] = {0, 1, 0, 2, 1, 0};  // a0 b0, a0 b1, a1 b0, a0 b2, a1 b1, a2 b0
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          f32x16 part;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) part[r] = 0.f;
+#pragma unroll
+          for (int t = 0; t < 6; ++t) part = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][TA[t]], fb[j][TB[t]], part, 0, 0, 0);
+          acc[i][j] += part;  // fp32 VALU adds, round to nearest even
+        }
+      if (s + 1 < nst) slice_all();  // the next stage's fragments over the ones just consumed
+    }
+  } else {
+    // one stage: 8 k-pairs x 2 x 2 MFMAs; the operands of pair p + 1 are requested before the MFMAs of pair p (as in gemm_tile).
+    // MASK: the last stage of a ragged k range — rows >= nv are clamped copies and enter as zeros
+    auto stage = [&](const float* sa, auto mask_tag, int nv) {
+      constexpr bool MASK = decltype(mask_tag)::value;
+      const float* sb = sa + WBK * WBM;
+      if (do_csum) {  // 2 threads per column, 8 rows each
+#pragma unroll
+        for (int kk = 0; kk < WBK / 2; ++kk) {
+          const int k = kk * 2 + (tid >> 7);
+          const float v = sa[k * WBM + (tid & 127)];
+          csum += (!MASK || k < nv) ? v : 0.f;
+        }
+      }
+      float a[2][2], b[2][2];
+      auto lds_ab = [&](int kk, float (&a_)[2], float (&b_)[2]) {
+        const bool ok = !MASK || kk + lh < nv;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const float v = sa[(kk + lh) * WBM + wm * 64 + i * 32 + li];
+          a_[i] = ok ? v : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const float v = sb[(kk + lh) * WBM + wn * 64 + j * 32 + li];
+          b_[j] = ok ? v : 0.f;
+        }
+      };
+      lds_ab(0, a[0], b[0]);
+#pragma unroll
+      for (int p = 0; p < WBK / 2; ++p) {
+        if (p + 1 < WBK / 2) lds_ab(2 * (p + 1), a[(p + 1) & 1], b[(p + 1) & 1]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[p & 1][i], b[p & 1][j], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+      }
+    };
+
+    // the ragged last stage is peeled: a masked stage inside the loop makes the compiler shuttle the accumulators between register
+    // files on every k-step
+    for (int s = 0; s < nfull; ++s) stage(advance(s), std::false_type{}, WBK);
+    if (nfull < nst) stage(advance(nfull), std::true_type{}, kend - kbeg - nfull * WBK);
+  }
 
   if (do_csum && m0 + (tid & 127) < g.M) atomicAdd(g.colsum + m0 + (tid & 127), csum);
   // epilogue: C/D layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5); rows / columns past M / N are dropped
@@ -384,7 +480,10 @@ struct GemmGroup {
   int first[kMaxGroup + 1];
   int n, split;
 };
-__global__ __launch_bounds__(256) void wgrad_group_kernel(GemmGroup gg) {
+// (amdgpu_waves_per_eu(2): the ring's 64 KiB allow two workgroups per CU; without the hint hipcc interleaves the four tiles' stage
+// sums and takes 234 VGPRs + 64 AGPRs, one workgroup per CU.  With it the sliced body takes 248 of the 256 registers two workgroups
+// allow: no headroom, one more live value spills or halves the occupancy)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void wgrad_group_kernel(GemmGroup gg) {
   const int item = blockIdx.x;
   int p = 0;
   while (p + 1 < gg.n && item >= gg.first[p + 1]) ++p;
@@ -392,7 +491,7 @@ __global__ __launch_bounds__(256) void wgrad_group_kernel(GemmGroup gg) {
   const int local = item - gg.first[p];
   const int tiles_n = (g.N + WBM - 1) / WBM, tiles = tiles_n * ((g.M + WBM - 1) / WBM);
   const int bz = local / tiles, t = local - bz * tiles;
-  wgrad_tile(g, t % tiles_n, t / tiles_n, bz, gg.split);
+  wgrad_tile<true>(g, t % tiles_n, t / tiles_n, bz, gg.split);
 }
 
 // the same work items on the register-staged 64 x 64 tile: groups whose outputs would leave much of a 128 x 128 tile as padding
@@ -407,7 +506,12 @@ __global__ __launch_bounds__(256) void gemm_group_kernel(GemmGroup gg) {
   gemm_tile<64, 64, 1, 1>(g, t % tiles_n, t / tiles_n, bz, gg.split);
 }
 
-__global__ __launch_bounds__(256) void wgrad_kernel(GemmArgs g) { wgrad_tile(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void wgrad_kernel(GemmArgs g) {
+  wgrad_tile<true>(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z);
+}
+__global__ __launch_bounds__(256) void wgrad_exact_kernel(GemmArgs g) {  // unsplit requests of gemm_f32
+  wgrad_tile<false>(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z);
+}
 
 // ---- 16-bit operand variant (operand_type() OP_BF16 / OP_F16: the reference's --use_amp regime) ----------------------------------
 // Same tiling, arguments and epilogue; the global -> LDS stage rounds both operands to bf16 / fp16 (OT; nearest even) and lays them
@@ -666,6 +770,10 @@ int wgrad_k_per_split(int K, int split) {
   const int ksteps = (K + WBK - 1) / WBK;
   return ((ksteps + split - 1) / split) * WBK;
 }
+// The sliced body is the faster one wherever both were measured (tools/wgrad_tile_bench.py on MI355X, us, exact -> sliced): the VRNN
+// chain group 704 -> 624 (ragged rows 705 -> 629), a 256 x 512 + 2 x 256 x 256 group 85.1 -> 76.2, 1536 x 512 x 16000 215 -> 182,
+// 384 x 192 x 49152 88.8 -> 77.3, 256 x 256 x 64000 83.0 -> 72.4, 768 x 192 x 393216 1194 -> 1061.  Only a request for NO split keeps
+// the exact body: it asks for a reproducible result, the 64 x 64 tile's bits.
 
 }  // namespace
 
@@ -701,7 +809,10 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
     const dim3 grid((N + WBM - 1) / WBM, (M + WBM - 1) / WBM, nz);
     if (nz > 1 && !accumulate)  // atomic accumulation needs a zeroed destination
       BLVM_HIP(hipMemset2DAsync(C, sizeof(float) * (size_t)ldc, 0, sizeof(float) * (size_t)N, (size_t)M, stream));
-    hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, stream, g);
+    // a request for no split asks for a reproducible result: the exact fp32 body, bit-identical to the 64 x 64 tile.  That includes
+    // the callers that pass gemm_pick_split() where it returns 1 (outputs of >= 768 64 x 64 tiles, e.g. 2048 x 2048)
+    if (split_k != 1) hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL(wgrad_exact_kernel, grid, dim3(256), 0, stream, g);
     BLVM_CHECK_LAUNCH("gemm_f32");
     return BLVM_OK;
   }

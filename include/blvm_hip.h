@@ -157,7 +157,9 @@ int blvm_act_bwd_f32(const float* dy, const float* y, float slope, float* dz, si
  *   dW[n*lddw + k] += sum_r D[r*ldd + n] X[r*ldx + k]   ;   db[n] += sum_r D[r*ldd + n]     (both ACCUMULATE; caller zeroes)
  * D [rows, N_out] pre-activation gradients, X [rows, K_in] the layer's input; dW or db may be NULL; split_k < 1: chosen here.
  * The workgroups of the GEMM's first column block sum the D tiles they stage anyway (fp32 operands; in the bf16-operand mode the
- * bias gradient stays an fp32 sum in its own launch). */
+ * bias gradient stays an fp32 sum in its own launch).  Large aligned problems with a split compute fp32-accurate products from three
+ * exact bf16 slices per operand; split_k == 1, requested or chosen here (outputs of >= 768 64 x 64 tiles), keeps the exact fp32
+ * chain. */
 int blvm_wgrad_f32(int N_out, int K_in, int rows, const float* D, int ldd, const float* X, int ldx, float* dW, int lddw, float* db,
                    int split_k, void* stream);
 
