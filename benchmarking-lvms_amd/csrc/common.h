@@ -388,6 +388,13 @@ int gemm_ws_min_rows();
 int gemm_ws_f32(int op_b, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias,
                 int act, float slope, const float* gate, int ldg, int accumulate, hipStream_t stream);
 void gemm_count_path(int path);  // 0: the staged tiles of gemm.hip, 1: gemm_ws.hip
+// The kernels K6 chooses among (the BLVM_GEMM_ARM_* numbers of include/blvm_hip.h).  ARM_STAGED + 3 * tile + operand with tile 0 the
+// 64 x 64, 1 the 128 x 128, 2 the 128 x 192, 3 the 192 x 128 register-staged tile and operand an OpType value; ARM_COUNT doubles as
+// "nothing is launched".  gemm_arm (gemm.hip) is gemm_f32's dispatch as host arithmetic; gemm_count_arm counts one launch.
+enum GemmArm { ARM_WS = 0, ARM_STAGED = 1, ARM_WGRAD_EXACT = 13, ARM_WGRAD_SLICED = 14, ARM_WGRAD_GROUP = 15, ARM_GEMM_GROUP = 16, ARM_COUNT = 17 };
+int gemm_arm(int op_a, int op_b, int M, int N, int K, uintptr_t a_addr, int lda, uintptr_t b_addr, int ldb, int split_k, bool has_bias,
+             int act, bool has_gate, bool has_colsum, int operand, int min_rows, int force_tile);
+void gemm_count_arm(int arm);
 int colsum_f32(int M, int N, const float* X, int ldx, float* out, int accumulate, hipStream_t stream);
 // Weight gradients of one reduction length as ONE launch: dW[M,N] += D^T[M,K] Act[K,N] and, with db, db[M] += column sums of D, for
 // every job with dW (a job without dW only sums its columns).  Jobs with 16-byte aligned operands, M, N and leading dimensions

@@ -10,6 +10,7 @@
 // f32-in MFMA is an exact fp32 fma chain (guide §3 'FP32-input MFMA'), so results are bit-reproducible except
 // for split-K (atomic) accumulation order.
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include <vector>
@@ -659,12 +660,19 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs g) {
     }
 }
 
+// launches per arm (blvm_gemm_arm_counts; numbering at GemmArm, common.h): counted beside every hipLaunchKernelGGL of K6, keyed by
+// the kernel that launch names, never by the routing's answer
+std::atomic<unsigned long long> g_arm_count[ARM_COUNT];
+constexpr int tile_index(int bm, int bn) { return bm == 64 ? 0 : (bn == 192 ? 2 : (bm == 192 ? 3 : 1)); }
+constexpr int staged_arm(int bm, int bn, int ot) { return ARM_STAGED + 3 * tile_index(bm, bn) + ot; }
+
 template <int BM, int BN, int OT>
 void launch_gemm16(const GemmArgs& g, int op_a, int op_b, dim3 grid, hipStream_t s) {
   if (op_a == 0 && op_b == 0) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 0, 0, OT>), grid, dim3(256), 0, s, g);
   else if (op_a == 0 && op_b == 1) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 0, 1, OT>), grid, dim3(256), 0, s, g);
   else if (op_a == 1 && op_b == 0) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 1, 0, OT>), grid, dim3(256), 0, s, g);
   else hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 1, 1, OT>), grid, dim3(256), 0, s, g);
+  gemm_count_arm(staged_arm(BM, BN, OT));
 }
 
 template <int BM, int BN>
@@ -675,6 +683,7 @@ void launch_gemm(const GemmArgs& g, int op_a, int op_b, dim3 grid, hipStream_t s
   else if (op_a == 0 && op_b == 1) hipLaunchKernelGGL((gemm_kernel<BM, BN, 0, 1>), grid, dim3(256), 0, s, g);
   else if (op_a == 1 && op_b == 0) hipLaunchKernelGGL((gemm_kernel<BM, BN, 1, 0>), grid, dim3(256), 0, s, g);
   else hipLaunchKernelGGL((gemm_kernel<BM, BN, 1, 1>), grid, dim3(256), 0, s, g);
+  gemm_count_arm(staged_arm(BM, BN, OP_F32));
 }
 
 __global__ __launch_bounds__(256) void colsum_kernel(int M, int N, const float* __restrict__ X, int ldx,
@@ -750,8 +759,8 @@ __global__ __launch_bounds__(256) void transpose_kernel(int M, int N, const floa
 
 // ---- wgrad_tile host side ----
 // operands it can stage by 16-byte DMA (and clamp inside a row), and reductions long enough to pipeline
-bool wgrad_fits(const float* D, int ldd, int M, const float* Act, int lda, int N, int K) {
-  return aligned16(D) && aligned16(Act) && ldd % 4 == 0 && lda % 4 == 0 && M % 4 == 0 && N % 4 == 0 && K >= 1024;
+bool wgrad_fits(uintptr_t d_addr, int ldd, int M, uintptr_t act_addr, int lda, int N, int K) {
+  return (d_addr & 15u) == 0 && (act_addr & 15u) == 0 && ldd % 4 == 0 && lda % 4 == 0 && M % 4 == 0 && N % 4 == 0 && K >= 1024;
 }
 int wgrad_tiles(int M, int N) { return ((M + WBM - 1) / WBM) * ((N + WBM - 1) / WBM); }
 // k splits over `tiles` output tiles: as many as keep every workgroup in the first wave (the workgroups per CU that the ring's LDS
@@ -777,6 +786,79 @@ int wgrad_k_per_split(int K, int split) {
 
 }  // namespace
 
+void gemm_count_arm(int arm) { g_arm_count[arm].fetch_add(1, std::memory_order_relaxed); }
+int gemm_force_tile() {  // BLVM_GEMM_TILE, experiments only: 1 the 64 x 64 tile, 2 no 128 x 192, 3 no weight-stationary path
+  static const int force_tile = [] { const char* e = getenv("BLVM_GEMM_TILE"); return e ? atoi(e) : 0; }();
+  return force_tile;
+}
+
+// Which kernel gemm_f32 launches for a request: host arithmetic only, and the ONE place where the choice is made -- gemm_f32 asks
+// this function and launches what it answers (exported as blvm_gemm_arm; tests/test_gemm_arms_cpu.py walks its conditions).
+int gemm_arm(int op_a, int op_b, int M, int N, int K, uintptr_t a_addr, int lda, uintptr_t b_addr, int ldb, int split_k, bool has_bias,
+             int act, bool has_gate, bool has_colsum, int operand, int min_rows, int force_tile) {
+  if (M <= 0 || N <= 0) return ARM_COUNT;  // nothing is launched
+  if (split_k < 1) split_k = 1;
+  // weight-gradient form (both operands [rows, features]) on wgrad_tile where it fits and measured faster than the 64 x 64 tile
+  // (tools/wgrad_tile_bench.py on MI355X, split as the callers request it; us, 64 x 64 -> wgrad_tile):
+  //   1536 x 512 x 16000  257 -> 215      768 x 192 x 393216  1451 -> 1203      384 x 192 x 49152  94.0 -> 88.9
+  //   256 x 256 x 64000  92.5 -> 83.5     256 x 256 x 16000   36.4 -> 44.1      768 x 256 x 16000  72.0 -> 75.7
+  //   192 x 192 x 98304  89.7 -> 108
+  // i.e. large outputs, or long reductions on outputs whose 128-wide tiles are not mostly padding.  split_k == 1 stays unsplit
+  // (deterministic); any other request takes the body's own split.
+  const bool wgrad_wins = (long)M * N >= 512L * 512 || (K >= 32768 && std::max(M, N) >= 256);
+  if (op_a == 1 && op_b == 1 && operand == OP_F32 && act == 0 && !has_gate && !has_bias && wgrad_wins &&
+      wgrad_fits(a_addr, lda, M, b_addr, ldb, N, K)) {
+    // a request for no split asks for a reproducible result: the exact fp32 body, bit-identical to the 64 x 64 tile.  That includes
+    // the callers that pass gemm_pick_split() where it returns 1 (outputs of >= 768 64 x 64 tiles, e.g. 2048 x 2048)
+    return split_k != 1 ? ARM_WGRAD_SLICED : ARM_WGRAD_EXACT;
+  }
+  // forward / data-gradient forms with a short reduction and many rows: the weight-stationary path (gemm_ws.hip; the routing
+  // table is at gemm_ws_route).  BLVM_GEMM_TILE=3 keeps them on the staged tiles (A/B runs of one library).
+  if (force_tile != 3 && gemm_ws_route(op_a, M, N, K, a_addr, lda, split_k, has_colsum, operand, min_rows)) return ARM_WS;
+  // (the tile count takes the split as requested, before gemm_f32 clamps it to the k-tiles there are)
+  bool big = (M >= 128 && N >= 128 && (size_t)((M + 127) / 128) * ((N + 127) / 128) * split_k >= 192);
+  // 192-wide tiles for the conv coders' channel counts (192 = 1.5 x 128 would waste a quarter of a 128-tile pair and
+  // re-read the other operand): N % 192 == 0 -> 128x192, else M % 192 == 0 -> 192x128
+  // Measured on MI355X (tools/gemm_bench.py, tools/gemm_cw.py with BLVM_GEMM_TILE forcing each variant): of the register-staged
+  // tiles the 64x64 one wins for every weight-gradient form (76 -> 91 TF/s at 768x192x4e5, 71 -> 91 at 1536x512x16000; those that
+  // wgrad_tile takes left above)
+  // and for short reductions on narrow outputs (K <= 256 and N <= 256: 43 -> 65 TF/s at K = 96, 53 -> 61 at 256x256); the
+  // 128-wide tiles win once N >= 512 or K >= 512 (84 vs 74 TF/s at N = 768, K = 192; 114 vs 95 at 4096^3).
+  if ((op_a == 1 && op_b == 1) || (K <= 256 && N <= 256)) big = false;
+  if (force_tile == 1) big = false;
+  const bool n192 = big && N % 192 == 0 && N % 128 != 0 && force_tile != 2;
+  const bool m192 = big && !n192 && M % 192 == 0 && M % 128 != 0;
+  // (128 x 64 tiles for narrow outputs whose 128 x 128 tiles are fewer than two per CU, measured r03: dec L1 forward 89 -> 85 us, dec L3
+  // dgrad unchanged, the VRNN step within noise: not worth a fourth tile shape)
+  return ARM_STAGED + 3 * (big ? (n192 ? 2 : (m192 ? 3 : 1)) : 0) + operand;
+}
+
+// The grouped entry point's choice, per job and for the group (host arithmetic only; exported as blvm_wgrad_group_route):
+// fits[i] = 1 for the jobs wgrad_tile can take (at most kMaxGroup of them); two or more of those run as ONE launch, on
+// wgrad_group_kernel or, where their 128 x 128 tiles would be mostly padding, on gemm_group_kernel -- the arm returned.  ARM_COUNT:
+// no grouped launch (fewer than two fit); then, as every job with fits[i] == 0, those jobs go through gemm_f32 one by one.
+int wgrad_group_route(const WgradJob* jobs, int njobs, int K, int operand, int* fits) {
+  int ntake = 0;
+  long tiles = 0, area = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const WgradJob& j = jobs[i];
+    fits[i] = 0;
+    if (!j.dW) continue;
+    if (operand == OP_F32 && wgrad_fits(reinterpret_cast<uintptr_t>(j.D), j.ldd, j.M, reinterpret_cast<uintptr_t>(j.Act), j.lda, j.N, K) &&
+        ntake < kMaxGroup) {
+      fits[i] = 1;
+      ++ntake;
+      tiles += wgrad_tiles(j.M, j.N);
+      area += (long)j.M * j.N;
+    }
+  }
+  if (ntake < 2) return ARM_COUNT;
+  // wgrad_tile unless its tiles would be mostly padding.  Measured (tools/wgrad_tile_bench.py, us, 64 x 64 group -> wgrad_tile): the
+  // VRNN chain (16 jobs, 164 full tiles) 920 -> 766, a 256 x 512 + 2 x 256 x 256 group 94.5 -> 85.6, but a 256 x 64 + 2 x 256 x 256
+  // group (90 % of its tile area used) 66.2 -> 79.5, and STCN's narrow latent MLPs 31.84 -> 32.32 ms/step
+  return area * 100 >= tiles * WBM * WBM * 95L ? ARM_WGRAD_GROUP : ARM_GEMM_GROUP;
+}
+
 int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
              int ldc, const float* bias, int act, float slope, const float* gate, int ldg, int accumulate,
              int split_k, hipStream_t stream, float* colsum) {
@@ -792,56 +874,36 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
   g.a_vec = aligned16(A) && (lda % 4 == 0);
   g.b_vec = aligned16(B) && (ldb % 4 == 0);
   if (split_k < 1) split_k = 1;
-  // weight-gradient form (both operands [rows, features]) on wgrad_tile where it fits and measured faster than the 64 x 64 tile
-  // (tools/wgrad_tile_bench.py on MI355X, split as the callers request it; us, 64 x 64 -> wgrad_tile):
-  //   1536 x 512 x 16000  257 -> 215      768 x 192 x 393216  1451 -> 1203      384 x 192 x 49152  94.0 -> 88.9
-  //   256 x 256 x 64000  92.5 -> 83.5     256 x 256 x 16000   36.4 -> 44.1      768 x 256 x 16000  72.0 -> 75.7
-  //   192 x 192 x 98304  89.7 -> 108
-  // i.e. large outputs, or long reductions on outputs whose 128-wide tiles are not mostly padding.  split_k == 1 stays unsplit
-  // (deterministic); any other request takes the body's own split.
-  const bool wgrad_wins = (long)M * N >= 512L * 512 || (K >= 32768 && std::max(M, N) >= 256);
-  if (op_a == 1 && op_b == 1 && operand_type() == OP_F32 && act == 0 && gate == nullptr && bias == nullptr && wgrad_wins &&
-      wgrad_fits(A, lda, M, B, ldb, N, K)) {
+  const OpType ot = operand_type();
+  const int arm = gemm_arm(op_a, op_b, M, N, K, reinterpret_cast<uintptr_t>(A), lda, reinterpret_cast<uintptr_t>(B), ldb, split_k,
+                           bias != nullptr, act, gate != nullptr, colsum != nullptr, ot, gemm_ws_min_rows(), gemm_force_tile());
+  if (arm == ARM_WGRAD_EXACT || arm == ARM_WGRAD_SLICED) {
     g.colsum = colsum;
-    const int split = split_k == 1 ? 1 : wgrad_split(wgrad_tiles(M, N), K);
+    const int split = arm == ARM_WGRAD_EXACT ? 1 : wgrad_split(wgrad_tiles(M, N), K);
     g.k_per_split = wgrad_k_per_split(K, split);
     const int nz = (K + g.k_per_split - 1) / g.k_per_split;
     const dim3 grid((N + WBM - 1) / WBM, (M + WBM - 1) / WBM, nz);
     if (nz > 1 && !accumulate)  // atomic accumulation needs a zeroed destination
       BLVM_HIP(hipMemset2DAsync(C, sizeof(float) * (size_t)ldc, 0, sizeof(float) * (size_t)N, (size_t)M, stream));
-    // a request for no split asks for a reproducible result: the exact fp32 body, bit-identical to the 64 x 64 tile.  That includes
-    // the callers that pass gemm_pick_split() where it returns 1 (outputs of >= 768 64 x 64 tiles, e.g. 2048 x 2048)
-    if (split_k != 1) hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL(wgrad_exact_kernel, grid, dim3(256), 0, stream, g);
+    if (arm == ARM_WGRAD_SLICED) {
+      hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, stream, g);
+      gemm_count_arm(ARM_WGRAD_SLICED);
+    } else {
+      hipLaunchKernelGGL(wgrad_exact_kernel, grid, dim3(256), 0, stream, g);
+      gemm_count_arm(ARM_WGRAD_EXACT);
+    }
     BLVM_CHECK_LAUNCH("gemm_f32");
     return BLVM_OK;
   }
-  static const int force_tile = [] { const char* e = getenv("BLVM_GEMM_TILE"); return e ? atoi(e) : 0; }();  // experiments only
-  // forward / data-gradient forms with a short reduction and many rows: the weight-stationary path (gemm_ws.hip; the routing
-  // table is at gemm_ws_route).  BLVM_GEMM_TILE=3 keeps them on the staged tiles (A/B runs of one library).
-  if (force_tile != 3 && gemm_ws_route(op_a, M, N, K, reinterpret_cast<uintptr_t>(A), lda, split_k, colsum != nullptr, operand_type(),
-                                       gemm_ws_min_rows())) {
+  if (arm == ARM_WS) {
     gemm_count_path(1);
     return gemm_ws_f32(op_b, M, N, K, A, lda, B, ldb, C, ldc, bias, act, slope, gate, ldg, accumulate, stream);
   }
   gemm_count_path(0);
-  bool big =(M >= 128 && N >= 128 && (size_t)((M + 127) / 128) * ((N + 127) / 128) * split_k >= 192);
-  // 192-wide tiles for the conv coders' channel counts (192 = 1.5 x 128 would waste a quarter of a 128-tile pair and
-  // re-read the other operand): N % 192 == 0 -> 128x192, else M % 192 == 0 -> 192x128
-  // Measured on MI355X (tools/gemm_bench.py, tools/gemm_cw.py with BLVM_GEMM_TILE forcing each variant): of the register-staged
-  // tiles the 64x64 one wins for every weight-gradient form (76 -> 91 TF/s at 768x192x4e5, 71 -> 91 at 1536x512x16000; those that
-  // wgrad_tile takes left above)
-  // and for short reductions on narrow outputs (K <= 256 and N <= 256: 43 -> 65 TF/s at K = 96, 53 -> 61 at 256x256); the
-  // 128-wide tiles win once N >= 512 or K >= 512 (84 vs 74 TF/s at N = 768, K = 192; 114 vs 95 at 4096^3).
-  if ((op_a == 1 && op_b == 1) || (K <= 256 && N <= 256)) big = false;
-  if (force_tile == 1) big = false;
-  const bool n192 = big && N % 192 == 0 && N % 128 != 0 && force_tile != 2;
-  const bool m192 = big && !n192 && M % 192 == 0 && M % 128 != 0;
-  // (128 x 64 tiles for narrow outputs whose 128 x 128 tiles are fewer than two per CU, measured r03: dec L1 forward 89 -> 85 us, dec L3
-  // dgrad unchanged, the VRNN step within noise: not worth a fourth tile shape)
+  const int tile = (arm - ARM_STAGED) / 3;  // 0: 64 x 64, 1: 128 x 128, 2: 128 x 192, 3: 192 x 128
+  const bool big = tile != 0, n192 = tile == 2, m192 = tile == 3;
   const int bm = big ? (m192 ? 192 : 128) : 64;
   const int bn = big ? (n192 ? 192 : 128) : 64;
-  const OpType ot = operand_type();
   const int bk = ot != OP_F32 ? BKB : tile_bk(bm, bn);
   if (colsum != nullptr && (ot != OP_F32 || op_a != 1 || K == 0)) {  // (the 16-bit kernel stages ROUNDED operands: the bias gradient stays an fp32 sum)
     BLVM_TRY(op_a == 1 ? colsum_f32(K, M, A, lda, colsum, 1, stream) : BLVM_EINVAL);
@@ -869,7 +931,8 @@ int gemm_f32(int op_a, int op_b, int M, int N, int K, const float* A, int lda, c
 
 int gemm_wgrad_group(const WgradJob* jobs, int njobs, int K, hipStream_t stream) {
   // the problems wgrad_tile takes, largest first; the others (unaligned, K < 1024, the 16-bit operand modes) one by one through gemm_f32
-  std::vector<int> take;
+  std::vector<int> take, fits((size_t)std::max(njobs, 0));
+  const int arm = wgrad_group_route(jobs, njobs, K, operand_type(), fits.data());
   for (int i = 0; i < njobs; ++i) {
     const WgradJob& j = jobs[i];
     if (!j.dW) {
@@ -877,13 +940,13 @@ int gemm_wgrad_group(const WgradJob* jobs, int njobs, int K, hipStream_t stream)
       continue;
     }
     BLVM_REQUIRE(j.D && j.Act && j.M > 0 && j.N > 0 && j.ldd >= j.M && j.lda >= j.N && j.ldw >= j.N, "gemm_wgrad_group: bad job %d", i);
-    if (!operand_16bit() && wgrad_fits(j.D, j.ldd, j.M, j.Act, j.lda, j.N, K) && (int)take.size() < kMaxGroup) {
+    if (fits[(size_t)i]) {
       take.push_back(i);
       continue;
     }
     BLVM_TRY(gemm_f32(1, 1, j.M, j.N, K, j.D, j.ldd, j.Act, j.lda, j.dW, j.ldw, nullptr, 0, 0.f, nullptr, 0, 1, gemm_pick_split(j.M, j.N, K), stream, j.db));
   }
-  if (take.size() < 2) {  // a group of one: gemm_f32 picks tile and split (measured: 256 x 256 x 16000 alone 40 us there, 47 in a group)
+  if (arm == ARM_COUNT) {  // a group of one: gemm_f32 picks tile and split (measured: 256 x 256 x 16000 alone 40 us there, 47 in a group)
     for (const int i : take) {
       const WgradJob& j = jobs[i];
       BLVM_TRY(gemm_f32(1, 1, j.M, j.N, K, j.D, j.ldd, j.Act, j.lda, j.dW, j.ldw, nullptr, 0, 0.f, nullptr, 0, 1, gemm_pick_split(j.M, j.N, K), stream, j.db));
@@ -904,12 +967,7 @@ int gemm_wgrad_group(const WgradJob* jobs, int njobs, int K, hipStream_t stream)
     g.colsum = j.db;
     tiles += wgrad_tiles(j.M, j.N);
   }
-  // wgrad_tile unless its tiles would be mostly padding.  Measured (tools/wgrad_tile_bench.py, us, 64 x 64 group -> wgrad_tile): the
-  // VRNN chain (16 jobs, 164 full tiles) 920 -> 766, a 256 x 512 + 2 x 256 x 256 group 94.5 -> 85.6, but a 256 x 64 + 2 x 256 x 256
-  // group (90 % of its tile area used) 66.2 -> 79.5, and STCN's narrow latent MLPs 31.84 -> 32.32 ms/step
-  long area = 0;
-  for (int p = 0; p < gg.n; ++p) area += (long)gg.p[p].M * gg.p[p].N;
-  const bool dma = area * 100 >= tiles * WBM * WBM * 95L;
+  const bool dma = arm == ARM_WGRAD_GROUP;  // (the tile-area rule is at wgrad_group_route)
   const int bk = dma ? WBK : tile_bk(64, 64);
   int split;
   if (dma) {
@@ -930,8 +988,13 @@ int gemm_wgrad_group(const WgradJob* jobs, int njobs, int K, hipStream_t stream)
     first += (dma ? wgrad_tiles(gg.p[p].M, gg.p[p].N) : ((gg.p[p].M + 63) / 64) * ((gg.p[p].N + 63) / 64)) * gg.split;
   }
   gg.first[gg.n] = first;
-  if (dma) hipLaunchKernelGGL(wgrad_group_kernel, dim3((unsigned)first), dim3(256), 0, stream, gg);
-  else hipLaunchKernelGGL(gemm_group_kernel, dim3((unsigned)first), dim3(256), 0, stream, gg);
+  if (dma) {
+    hipLaunchKernelGGL(wgrad_group_kernel, dim3((unsigned)first), dim3(256), 0, stream, gg);
+    gemm_count_arm(ARM_WGRAD_GROUP);
+  } else {
+    hipLaunchKernelGGL(gemm_group_kernel, dim3((unsigned)first), dim3(256), 0, stream, gg);
+    gemm_count_arm(ARM_GEMM_GROUP);
+  }
   BLVM_CHECK_LAUNCH("gemm_wgrad_group");
   return BLVM_OK;
 }
@@ -1151,4 +1214,31 @@ extern "C" int blvm_act_bwd_f32(const float* dy, const float* y, float slope, fl
 
 extern "C" int blvm_colsum_f32(int M, int N, const float* X, int ldx, float* out, int accumulate, void* stream) {
   return blvm::colsum_f32(M, N, X, ldx, out, accumulate, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int blvm_gemm_arm(int op_a, int op_b, int M, int N, int K, size_t a_addr, int lda, size_t b_addr, int ldb, int split_k, int has_bias,
+                             int act, int has_gate, int has_colsum, int operand, int min_rows) {
+  return blvm::gemm_arm(op_a, op_b, M, N, K, (uintptr_t)a_addr, lda, (uintptr_t)b_addr, ldb, split_k, has_bias != 0, act, has_gate != 0,
+                        has_colsum != 0, operand, min_rows, blvm::gemm_force_tile());
+}
+
+extern "C" int blvm_wgrad_group_route(int n, const int* N_out, const int* K_in, int rows, const size_t* d_addr, const int* ldd,
+                                      const size_t* x_addr, const int* ldx, const int* has_dw, int operand, int* joins) {
+  using namespace blvm;
+  if (n < 0 || (n > 0 && !(N_out && K_in && d_addr && ldd && x_addr && ldx && has_dw && joins))) return ARM_COUNT;
+  std::vector<WgradJob> jobs((size_t)n);
+  static float some_dw;  // (never dereferenced: a job's dW only has to be non-null)
+  for (int i = 0; i < n; ++i)
+    jobs[(size_t)i] = WgradJob{reinterpret_cast<const float*>((uintptr_t)d_addr[i]), ldd[i], N_out[i],
+                               reinterpret_cast<const float*>((uintptr_t)x_addr[i]), ldx[i], K_in[i], has_dw[i] ? &some_dw : nullptr, K_in[i], nullptr};
+  const int arm = wgrad_group_route(jobs.data(), n, rows, operand, joins);
+  for (int i = 0; i < n; ++i) joins[i] = !has_dw[i] ? -1 : (arm != ARM_COUNT && joins[i] ? 1 : 0);
+  return arm;
+}
+
+extern "C" int blvm_gemm_arm_counts(unsigned long long out[17]) {
+  static_assert(blvm::ARM_COUNT == 17, "the header's numbering");
+  BLVM_REQUIRE(out != nullptr, "blvm_gemm_arm_counts: null pointer");
+  for (int a = 0; a < blvm::ARM_COUNT; ++a) out[a] = blvm::g_arm_count[a].load(std::memory_order_relaxed);
+  return BLVM_OK;
 }

@@ -247,7 +247,7 @@ int cu_count() {
 
 template <int OPB>
 void launch_ws(int nc, const WsArgs& g, dim3 grid, hipStream_t s) {
-#define WS_CASE(n) case n: hipLaunchKernelGGL((gemm_ws_kernel<n, OPB>), grid, dim3(WS_THREADS), 0, s, g); break;
+#define WS_CASE(n) case n: hipLaunchKernelGGL((gemm_ws_kernel<n, OPB>), grid, dim3(WS_THREADS), 0, s, g); gemm_count_arm(ARM_WS); break;
   switch (nc) {
     WS_CASE(1) WS_CASE(2) WS_CASE(3) WS_CASE(4) WS_CASE(5) WS_CASE(6) WS_CASE(7) WS_CASE(8)
     WS_CASE(9) WS_CASE(10) WS_CASE(11) WS_CASE(12) WS_CASE(13) WS_CASE(14) WS_CASE(15) WS_CASE(16)

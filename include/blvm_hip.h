@@ -149,6 +149,42 @@ int blvm_gemm_ws_min_rows(int rows);
  * counters, no device needed; products that the weight-gradient ring takes are counted in neither). */
 int blvm_gemm_path_counts(unsigned long long* out);
 
+/* The kernels ("arms") K6 chooses among, one number per kernel family and tile shape:
+ *    0       weight-stationary (gemm_ws_kernel)
+ *    1 ..  3 register-staged  64 x  64 tile with fp32 / bf16 / fp16 operands (gemm_kernel / gemm_bf16_kernel)
+ *    4 ..  6 register-staged 128 x 128 tile, the same three operand types
+ *    7 ..  9 register-staged 128 x 192 tile
+ *   10 .. 12 register-staged 192 x 128 tile
+ *   13       weight-gradient ring, exact fp32 body (wgrad_exact_kernel: an unsplit request)
+ *   14       weight-gradient ring, sliced body (wgrad_kernel)
+ *   15       grouped weight gradients on the ring (wgrad_group_kernel)
+ *   16       grouped weight gradients on the 64 x 64 tile (gemm_group_kernel)
+ * i.e. a staged arm is BLVM_GEMM_ARM_STAGED + 3 * tile + BLVM_DTYPE_*.  BLVM_GEMM_ARMS (17) is the number of arms and, as an
+ * answer, "nothing is launched". */
+#define BLVM_GEMM_ARM_WS 0
+#define BLVM_GEMM_ARM_STAGED 1
+#define BLVM_GEMM_ARM_WGRAD_EXACT 13
+#define BLVM_GEMM_ARM_WGRAD_SLICED 14
+#define BLVM_GEMM_ARM_WGRAD_GROUP 15
+#define BLVM_GEMM_ARM_GEMM_GROUP 16
+#define BLVM_GEMM_ARMS 17
+/* The arm blvm_gemm_f32 launches for a request: pure host arithmetic, no device, and the function blvm_gemm_f32 itself dispatches
+ * through.  a_addr / b_addr are A and B as integers (only their low four bits matter), has_bias / has_gate whether the pointers are
+ * given, has_colsum whether a bias gradient rides on the product (blvm_wgrad_f32 with db), split_k as REQUESTED, operand a
+ * BLVM_DTYPE_* value, min_rows the weight-stationary row threshold to apply.  M == 0 or N == 0: BLVM_GEMM_ARMS. */
+int blvm_gemm_arm(int op_a, int op_b, int M, int N, int K, size_t a_addr, int lda, size_t b_addr, int ldb, int split_k, int has_bias,
+                  int act, int has_gate, int has_colsum, int operand, int min_rows);
+/* The same for blvm_wgrad_group_f32 (arguments as there, addresses as integers, has_dw[i] whether job i has a dW): joins[i] = 1 for
+ * the jobs that run together in the grouped launch, 0 for those that go through blvm_gemm_f32 one by one (op_a = op_b = 1, no
+ * epilogue, accumulating, the split blvm_wgrad_f32 would choose: blvm_gemm_arm says where), -1 for a job without dW (column sums
+ * only).  Returns the arm of the grouped launch, 15 or 16, or BLVM_GEMM_ARMS when there is none (fewer than two jobs fit). */
+int blvm_wgrad_group_route(int n, const int* N_out, const int* K_in, int rows, const size_t* d_addr, const int* ldd, const size_t* x_addr,
+                           const int* ldx, const int* has_dw, int operand, int* joins);
+/* Launches per arm since the library was loaded, out[arm], counted beside each kernel launch and keyed by the kernel launched, not
+ * by the answer of the two functions above: on a device the two are checked against each other (tests/test_gpu_gemm_arms.py).
+ * Host counters; never touches the device.  Launches that are no GEMM (memsets, column sums) are not counted. */
+int blvm_gemm_arm_counts(unsigned long long out[17]);
+
 /* dz[i] = dy[i] * (y[i] > 0 ? 1 : slope) over n contiguous floats: derivative of ReLU / LeakyReLU from its OUTPUT y
  * (used where no producing GEMM exists to fuse it into, e.g. behind the DMoL head).  dz may alias dy. */
 int blvm_act_bwd_f32(const float* dy, const float* y, float slope, float* dz, size_t n, void* stream);

@@ -23,7 +23,7 @@ def test_every_declared_entry_point_is_bound_with_its_parameter_count():
     header = open(os.path.join(ROOT, "include", "blvm_hip.h")).read()
     code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
     protos = dict(re.findall(r"\b(blvm_\w+)\s*\(([^()]*)\)\s*;", code))
-    assert len(protos) >= 108 and set(protos) == set(re.findall(r"\b(blvm_\w+)\s*\(", code)) == set(_hip.SIGNATURES)
+    assert len(protos) >= 111 and set(protos) == set(re.findall(r"\b(blvm_\w+)\s*\(", code)) == set(_hip.SIGNATURES)
     lib = _hip.load()
     for name, params in protos.items():
         n = 0 if params.strip() in ("", "void") else params.count(",") + 1
@@ -44,6 +44,9 @@ def test_one_entry_point_per_kind_of_type_is_pinned_literally():
         "blvm_dmol_bwd_fused_workspace_floats": (c_size_t, [c_int] * 3),
         "blvm_last_error": (c_char_p, []),
         "blvm_rnn_path_counts": (c_int, [c_void_p]),
+        "blvm_gemm_arm": (c_int, [c_int] * 5 + [c_size_t, c_int, c_size_t] + [c_int] * 8),
+        "blvm_wgrad_group_route": (c_int, [c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p]),
+        "blvm_gemm_arm_counts": (c_int, [c_void_p]),
         "blvm_async_errors_take": (c_int, [c_void_p]),
         "blvm_wgrad_group_f32": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),

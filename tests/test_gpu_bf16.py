@@ -73,6 +73,9 @@ def test_gemm_bf16_operands_fp32_accumulate(op_a, op_b, M, N, K):
 
 @pytest.mark.parametrize("op_a,op_b,M,N,K,split", [(1, 1, 192, 768, 30000, 40), (1, 0, 384, 130, 20001, 24), (0, 1, 16385, 576, 192, 1), (1, 1, 96, 80, 4096, 16)])
 def test_gemm_bf16_split_k_wide_tiles_accumulate(op_a, op_b, M, N, K, split):
+    """Split-K and accumulation with ldc > N.  Of the four shapes only (0, 1, 16385, 576, 192) runs on a wide tile today (128x192:
+    the 16-bit modes have no weight-stationary path); the weight-gradient forms and 384 x 130 (144 tiles < 192) run on 64x64
+    (`blvm_gemm_arm`).  Every wide tile of this mode, with the launch counters asserted: tests/test_gpu_gemm_arms.py."""
     g = torch.Generator().manual_seed(M + N + K)
     A = torch.randn(*((K, M) if op_a else (M, K)), generator=g)
     Bm = torch.randn(*((K, N) if op_b else (N, K)), generator=g)

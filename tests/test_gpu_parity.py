@@ -80,7 +80,11 @@ def test_gemm_split_k_gate_accumulate_and_strides():
 @pytest.mark.parametrize("op_a,op_b,M,N,K,split", [(0, 0, 16400, 192, 200, 1), (0, 1, 16385, 576, 192, 1), (1, 1, 192, 768, 30000, 40),
                                                     (1, 0, 384, 130, 20001, 24), (0, 0, 12290, 384, 100, 1)])
 def test_gemm_192_wide_tiles(op_a, op_b, M, N, K, split):
-    """Conv-coder channel counts (192 / 576 / 384 = odd multiples of 64...) take the 128x192 / 192x128 tile variants."""
+    """Conv-coder channel counts (192 / 576 / 384 = odd multiples of 64...) with accumulation onto a non-zero C.  Written for the
+    128x192 / 192x128 tiles, which today's routing (`blvm_gemm_arm`) gives none of these shapes: in the order of the list they
+    run on the 64x64 tile (K <= 256 and N <= 256), weight-stationary (K % 16 == 0, K <= 256), the 64x64 tile (the weight-gradient
+    form never goes wide and this output is too small for the ring), the 64x64 tile (3 x 2 x 24 = 144 tiles < 192) and the 128x128
+    tile (384 % 128 == 0).  The 192-wide tiles are run, arm by arm with the launch counters asserted, by tests/test_gpu_gemm_arms.py."""
     g = torch.Generator().manual_seed(M + N + K)
     A = torch.randn(*((K, M) if op_a else (M, K)), generator=g)
     Bm = torch.randn(*((K, N) if op_b else (N, K)), generator=g)
