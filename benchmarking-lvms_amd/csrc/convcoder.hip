@@ -107,7 +107,8 @@ __global__ __launch_bounds__(256) void finalize_stats_kernel(const double* __res
   }
 }
 
-// y = (x - mean) * rstd * gamma_c + beta_c, evaluated exactly in that order (bit-identical to the unfused form)
+// y = (x - mean) * rstd * gamma_c + beta_c, evaluated in that order (the compiler fuses the last multiply-add); a column
+// that is constant has x - mean == 0 exactly and normalises to exactly beta_c
 __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict__ x, const float* __restrict__ mr,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta, int L,
                                                          int N, int C, int rows_per_block, float* __restrict__ y) {
@@ -623,7 +624,8 @@ extern "C" int blvm_dwconv_bwd(const float* x, const float* in_scale, const floa
   BLVM_REQUIRE(x && w && dy && k > 0 && k <= 8 && stride > 0 && dilation > 0, "dwconv_bwd: bad arguments");
   BLVM_REQUIRE(!relu || y, "dwconv_bwd: the ReLU mask needs the forward output");
   BLVM_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "dwconv_bwd: in_scale and in_shift go together");
-  BLVM_REQUIRE(aligned16(x) && aligned16(dy) && (!dx || aligned16(dx)) && (!y || aligned16(y)), "dwconv_bwd: alignment");
+  BLVM_REQUIRE(aligned16(x) && aligned16(dy) && (!dx || aligned16(dx)) && (!y || aligned16(y)) &&
+               (!in_scale || (aligned16(in_scale) && aligned16(in_shift))), "dwconv_bwd: alignment");
   const int L_out = dw_len_out(L_in, k, stride, dilation, transposed);
   const float* mask = relu ? y : nullptr;
   if (dx) {  // data gradient (wrt the affine-transformed input): the other stencil form applied to the (masked) output gradient
@@ -661,6 +663,7 @@ extern "C" int blvm_dwconv_bwd(const float* x, const float* in_scale, const floa
 
 extern "C" int blvm_resample_add_fwd(const float* y, const float* x, int L_out, int L_in, int N, float* out, void* stream_) {
   BLVM_REQUIRE(y && x && out && L_out > 0 && L_in > 0 && N > 0 && N % 4 == 0, "resample_add_fwd: bad arguments");
+  BLVM_REQUIRE(aligned16(y) && aligned16(x) && aligned16(out), "resample_add_fwd: alignment");
   hipLaunchKernelGGL(resample_add_kernel, ew_grid((size_t)L_out * (N / 4)), dim3(256), 0, static_cast<hipStream_t>(stream_), y, x,
                      L_out, L_in, N, out);
   BLVM_CHECK_LAUNCH("resample_add_fwd");

@@ -822,6 +822,8 @@ int blvm_rssm_seq_bwd(const BlvmRssmWeights* w, const float* enc, const float* c
  *   dw/dbias ACCUMULATED (may be NULL).
  * resample_add: out[t] = y[t] + x[nearest(t)], nearest(t)=min(floor(t*float(L_in)/L_out), L_in-1) (F.interpolate
  *   mode='nearest');  bwd ACCUMULATES dout into dx [L_in,N] (dy is dout itself).
+ * Every [L,N] tensor and every [N] / [2,N] / [C] vector that a kernel reads or writes four columns at a time must be
+ *   16-byte aligned (resample_add_fwd's y, x and out and dwconv's in_scale / in_shift included): BLVM_EINVAL otherwise.
  * ------------------------------------------------------------------------------------------------------------- */
 size_t blvm_chan_norm_workspace_doubles(int N);
 int blvm_chan_norm_stats(const float* x, int L, int N, int C, const float* gamma, const float* beta, float eps, float* mr,
