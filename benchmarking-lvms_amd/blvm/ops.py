@@ -1362,6 +1362,44 @@ class _WaveNetStackFunction(torch.autograd.Function):
         return (d_x, None, None, None, None, None, *grads)
 
 
+def _conv1d_k2_bwd(x, W, d_out, dilation, need_dx, dW, db):
+    """`blvm_conv1d_k2_bwd` with caller-chosen outputs: dW [Cout,Cin,2] and db [Cout] are accumulated into (None: not computed)."""
+    L, B, Cin = x.shape
+    d_x = torch.empty_like(x) if need_dx else None
+    ws = torch.empty(load().blvm_conv1d_k2_workspace_floats(Cin, W.shape[0]), device=x.device, dtype=torch.float32)
+    check(load().blvm_conv1d_k2_bwd(ptr(x), ptr(W), ptr(d_out), L, B, Cin, W.shape[0], dilation, ptr(d_x), ptr(dW), ptr(db), ptr(ws),
+                                    stream_ptr()), "blvm_conv1d_k2_bwd")  # fmt: skip
+    return d_x
+
+
+def _wavenet_block_fwd(x, conv_w, conv_b, rs_w, rs_b, dilation, T_skip, inv_std, o, skip):
+    """ONE gated residual block: x [L,B,C], conv_w [2C,C,2], rs_w [C+S,C] -> (pre [L-dilation,B,2C], act [L-dilation,B,C], reserve),
+    pre and act being views of the reserve that `_wavenet_block_bwd` takes.  o [L-dilation,B,C] (None: no residual output) is written,
+    skip [T_skip,B,S] (None with S = 0) is accumulated into; both are handed to the kernel as they are, wherever they start."""
+    L, B, C = x.shape
+    S, rows = rs_w.shape[0] - C, (L - dilation) * B
+    lib = load()
+    f32 = dict(device=x.device, dtype=torch.float32)
+    reserve = torch.empty(lib.blvm_wavenet_block_reserve_floats(L, B, C, dilation), **f32)
+    ws = torch.empty(lib.blvm_wavenet_block_workspace_floats(L, B, C, S, dilation), **f32)
+    check(lib.blvm_wavenet_block_fwd(ptr(x), ptr(conv_w), ptr(conv_b), ptr(rs_w), ptr(rs_b), L, B, C, S, dilation, T_skip, inv_std, ptr(o),
+                                     ptr(skip), ptr(reserve), ptr(ws), stream_ptr()), "blvm_wavenet_block_fwd")  # fmt: skip
+    return reserve[: rows * 2 * C].view(L - dilation, B, 2 * C), reserve[rows * 2 * C : rows * 3 * C].view(L - dilation, B, C), reserve
+
+
+def _wavenet_block_bwd(x, conv_w, rs_w, reserve, d_o, d_skip, dilation, T_skip, inv_std, dconv_w, dconv_b, drs_w, drs_b, d_x=None):
+    """Backward of `_wavenet_block_fwd`: d_o [L-dilation,B,C] or None, d_skip [T_skip,B,S] (None with S = 0) -> d_x [L,B,C] (written
+    into the buffer given, whatever it held); the parameter gradients are accumulated into the buffers given (None: not computed)."""
+    L, B, C = x.shape
+    S = rs_w.shape[0] - C
+    d_x = torch.empty_like(x) if d_x is None else d_x
+    ws = torch.empty(load().blvm_wavenet_block_workspace_floats(L, B, C, S, dilation), device=x.device, dtype=torch.float32)
+    check(load().blvm_wavenet_block_bwd(ptr(x), ptr(conv_w), ptr(rs_w), ptr(reserve), ptr(d_o), ptr(d_skip), L, B, C, S, dilation, T_skip,
+                                        inv_std, ptr(d_x), ptr(dconv_w), ptr(dconv_b), ptr(drs_w), ptr(drs_b), ptr(ws), stream_ptr()),
+          "blvm_wavenet_block_bwd")  # fmt: skip
+    return d_x
+
+
 @torch.no_grad()
 def wavenet_block_step(x2, params, inv_std: float, S: int, skip_acc, want_output: bool = True):
     """One gated residual block on ONE new frame for cached generation: x2 [2,B,C] = (the block's input `dilation` frames ago,
