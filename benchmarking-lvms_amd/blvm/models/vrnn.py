@@ -201,13 +201,16 @@ class VRNN(nn.Module):
         # has them (`given`: its activations; None: not folded, the decoder runs as K6 below)
         widths = [(lin.in_features, lin.out_features) for lin in dec_lin]
         chained = len(dec_lin) == 3 and widths[0] == (H + R, widths[1][0]) and widths[1][1] == widths[1][0] == widths[2][0]
-        fold = ops.DecoderFold(dec_lin, ops.LEAKY_SLOPE) if chained and all(lin.bias is not None for lin in dec_lin) else None
+        # (head_gates: the DMoL head below returns the gradient of the decoder's last pre-activation, so the cell's node may take the
+        # decoder in and run its backward on the backward launch's spare workgroups: `fold.dec`)
+        gates = isinstance(lik, DiscretizedLogisticMixtureDense) and lik.params is not None
+        fold = ops.DecoderFold(dec_lin, ops.LEAKY_SLOPE, gates) if chained and all(lin.bias is not None for lin in dec_lin) else None
         decin, kld, kld_fn, mu_q, sd_q, mu_p, sd_p, z = self.vrnn_cell.sequence(enc, h0, eps, x_sl_dev, stride, free_nats, decoder=fold)
-        given = fold.given if fold is not None else None
+        given, dec_node = (fold.given, fold.dec) if fold is not None else (None, None)
 
         # decoder MLP (K6, or its node alone) + likelihood head (K7 / K7b / K7c); dec [T'*B, S*F] detached
         dec, log_prob = mlp_log_prob(lik, decin[:Tp].view(Tp * B, H + R), dec_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE, y, x_sl_dev,
-                                     ops.LAYOUT_TIME_MAJOR, B, T, Tp, S, given=given)  # fmt: skip
+                                     ops.LAYOUT_TIME_MAJOR, B, T, Tp, S, given=given, dec_node=dec_node)  # fmt: skip
 
         # ELBO assembly in float64 as the reference does (mask dtype `float`, vrnn.py:266-279), one kernel:
         # elbo = log_prob - kld, loss = -(log_prob - beta * kld_fn).sum() / n_frames

@@ -80,12 +80,13 @@ class DiscretizedLogisticMixtureDense(ConditionalDistribution):
         W, b = (self.params.weight, self.params.bias) if fused_linear else (None, None)
         return ops.dmol_log_prob(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, self.num_mix, self.num_bins, self.log_epsilon)
 
-    def fused_mlp_log_prob(self, x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given=None):
+    def fused_mlp_log_prob(self, x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given=None, dec_node=None):
         """The decoder MLP `layers` (activation after every layer) and this head on its output: (activations DETACHED, log_prob [B]).
         The head's backward hands the MLP the gradient of its last pre-activation and the head Linear's own gradients (K7 fused).
-        `given`: the MLP's activations where they were computed already (`ops.mlp_given`)."""
+        `given`: the MLP's activations where they were computed already (`ops.mlp_given`); `dec_node`: the MLP's output where another
+        node owns the MLP (`ops.DecoderFold.dec`)."""
         return ops.mlp_dmol_log_prob(x2d, layers, self.params.weight, self.params.bias, y, x_sl_dev, layout, B, T, Tp, S, act, slope,
-                                     self.num_mix, self.num_bins, self.log_epsilon, given)  # fmt: skip
+                                     self.num_mix, self.num_bins, self.log_epsilon, given, dec_node)  # fmt: skip
 
     @staticmethod
     def _pack(params):
@@ -200,11 +201,13 @@ class CategoricalDense(ConditionalDistribution):
         return self.levels.to(k.device)[k.long()]
 
 
-def mlp_log_prob(lik, x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given=None):
+def mlp_log_prob(lik, x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given=None, dec_node=None):
     """Decoder MLP + likelihood head `lik` on its output: (decoder activations DETACHED, masked per-utterance log-likelihood sums [B]).
     The DMoL head takes its fused form; the Gaussian heads run the MLP and `fused_log_prob` as separate nodes.
     `given`: the MLP's activations, one tensor per layer, where they were computed already (the VRNN forward launch)."""
     if isinstance(lik, DiscretizedLogisticMixtureDense):
-        return lik.fused_mlp_log_prob(x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given)
+        return lik.fused_mlp_log_prob(x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given, dec_node)
+    if dec_node is not None:
+        raise ops._hip.BlvmHipError("mlp_log_prob: only the fused DMoL head takes a decoder output with head gates")
     dec = ops.mlp(x2d, layers, act, slope) if given is None else ops.mlp_given(x2d, layers, given, act, slope)
     return dec.detach(), lik.fused_log_prob(dec, y, x_sl_dev, layout, B, T, Tp, S)

@@ -371,10 +371,16 @@ def mlp_given(x2d, layers, given, act: int = ACT_LEAKY, slope: float = LEAKY_SLO
 
 
 def mlp_dmol_log_prob(x2d, layers, W, b, y, x_sl_dev, layout, B, T, Tp, S, act: int = ACT_LEAKY, slope: float = LEAKY_SLOPE,
-                      num_mix=10, num_bins=256, log_eps=-7.0, given=None):  # fmt: skip
+                      num_mix=10, num_bins=256, log_eps=-7.0, given=None, dec_node=None):  # fmt: skip
     """`mlp(x2d, layers, act, slope)` feeding `dmol_log_prob(., W, b, ...)` as one pair of autograd nodes whose backward never writes
     d_par or d_dec: the head's backward kernel hands the MLP the gradient of its last pre-activation and accumulates dW / db itself.
     Returns (dec DETACHED — the activations [rows, S*3*num_mix] for samplers / modes —, log_prob [B] float64)."""
+    if dec_node is not None:
+        # `dec_node`: the MLP's output as an output of another node that takes the gradient of the last PRE-activation (the VRNN
+        # cell's node with its decoder, `DecoderFold(head_gates=True)`): only the head remains to be built
+        if act != ACT_LEAKY or W is None:
+            raise _hip.BlvmHipError("mlp_dmol_log_prob: a decoder output with head gates needs the leaky ReLU and the fused head Linear")
+        return dec_node.detach(), _DMoLFunction.apply(dec_node, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, num_bins, log_eps, slope)
     if act == ACT_NONE or W is None:
         dec = mlp(x2d, layers, act, slope) if given is None else mlp_given(x2d, layers, given, act, slope)
         return dec.detach(), dmol_log_prob(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, num_bins, log_eps)
@@ -811,7 +817,12 @@ def vrnn_decode(enc_lin, cell_params, dec_lin, lik_lin, x0, h0, eps, u, v, S, H,
 
 
 class _VRNNSeqFunction(torch.autograd.Function):
-    """(enc, h0, eps, 28 params) -> decin [T'+1,B,H+R], kld [B], kld_fn [B]  (+ non-differentiable mu/sd/z)."""
+    """(enc, h0, eps, 28 params) -> decin [T'+1,B,H+R], kld [B], kld_fn [B]  (+ non-differentiable mu/sd/z).
+    With the decoder's six parameters behind the 28 (`DecoderFold(head_gates=True)`, `blvm_vrnn_dec_bwd_fold` on) and a forward launch
+    that folded all three layers, the node is the cell AND its decoder: a ninth output `dec` [T'*B, S*F] whose incoming gradient is
+    that of the decoder's last pre-activation; the backward runs the decoder's data gradients inside the cell's backward launch
+    (`blvm_vrnn_seq_bwd_dec`) or, where that does not fold, as the K6 products `_MLPFunction` runs, and then the decoder's three
+    weight gradients.  (A node cannot return weight gradients that a later node's kernel will fill.)"""
 
     @staticmethod
     def forward(ctx, enc, h0, eps, x_sl_dev, cfg, dec, *params):
@@ -819,7 +830,7 @@ class _VRNNSeqFunction(torch.autograd.Function):
         three activations are left in `dec.given`."""
         Tp, B, X, H, Z, R, residual, sd_eps, stride, fn_floor = cfg
         enc, eps = _f32c(enc), _f32c(eps)
-        params = tuple(_f32c(p) for p in params)
+        params, dparams = tuple(_f32c(p) for p in params[:28]), tuple(_f32c(p) for p in params[28:])
         dev = enc.device
         lib = load()
         f32 = dict(device=dev, dtype=torch.float32)
@@ -851,6 +862,7 @@ class _VRNNSeqFunction(torch.autograd.Function):
                 "blvm_vrnn_seq_fwd_dec",
             )  # fmt: skip
             dec.given = tuple(ys[: folded.value]) if folded.value else None  # (2: the last layer is left to the caller)
+        joint = dec is not None and len(dparams) == 6 and dec.given is not None and len(dec.given) == 3
         _tick("fwd_end")
         kld = torch.zeros(B, device=dev, dtype=torch.float64)
         kld_fn = torch.zeros(B, device=dev, dtype=torch.float64)
@@ -861,21 +873,76 @@ class _VRNNSeqFunction(torch.autograd.Function):
         )  # fmt: skip
         ctx.cfg = cfg
         ctx.has_h0 = h0 is not None
-        ctx.save_for_backward(enc, eps, x_sl_dev, decin, mu_q, sd_q, mu_p, sd_p, z, reserve, *params)
+        ctx.joint, ctx.n_dpar, ctx.dec_slope = joint, len(dparams), dec.slope if joint else 0.0
+        ctx.save_for_backward(enc, eps, x_sl_dev, decin, mu_q, sd_q, mu_p, sd_p, z, reserve, *params, *((*dparams, ys[0], ys[1]) if joint else ()))
         ctx.mark_non_differentiable(mu_q, sd_q, mu_p, sd_p, z)
         ctx.set_materialize_grads(False)  # (else autograd fills a [T',B,Z] zero gradient per statistics output: 16 MB each at [64,16000])
-        return decin, kld, kld_fn, mu_q, sd_q, mu_p, sd_p, z
+        return decin, kld, kld_fn, mu_q, sd_q, mu_p, sd_p, z, (ys[2] if joint else None)
 
     @staticmethod
-    def backward(ctx, d_decin, g_kld, g_kld_fn, *_unused):
+    def backward(ctx, d_decin, g_kld, g_kld_fn, *rest):
         Tp, B, X, H, Z, R, residual, sd_eps, stride, fn_floor = ctx.cfg
         enc, eps, x_sl_dev, decin, mu_q, sd_q, mu_p, sd_p, z, reserve, *params = ctx.saved_tensors
         dev = enc.device
         lib = load()
         f32 = dict(device=dev, dtype=torch.float32)
-        d_decin = _f32c(d_decin) if d_decin is not None else torch.zeros_like(decin)
         c_raw = _grad_f32(g_kld) if g_kld is not None else None
         c_fn = _grad_f32(g_kld_fn) if g_kld_fn is not None else None
+        d_dec = rest[5] if ctx.joint else None
+        dgrads = (None,) * ctx.n_dpar
+        if d_dec is not None:
+            # the cell and its decoder: the decoder's data gradients inside the launch where it folds, else as K6 in front of it
+            params, (W1, b1, W2, b2, W3, b3, y1, y2) = params[:28], params[28:]
+            dz3, M, DH, SF, slope = _f32c(d_dec), Tp * B, W2.shape[0], W3.shape[0], ctx.dec_slope
+            dy2, dy1 = torch.empty(M, DH, **f32), torch.empty(M, DH, **f32)
+            grads = _zeros_like_many(params)
+            d_enc = torch.empty_like(enc)
+            d_h0 = torch.empty(B, R, **f32) if ctx.has_h0 else None
+            w, g = _pack_weights(params), _pack_weights(grads, _hip.VrnnGrads)
+            folded = ctypes.c_int(0)
+            if d_decin is None:
+                ws = torch.empty(lib.blvm_vrnn_bwd_dec_workspace_floats(Tp, B, X, H, Z, R, DH, SF), **f32)
+                dw = (ctypes.c_void_p * 3)(ptr(W1), ptr(W2), ptr(W3))
+                _tick("bwd_begin")
+                check(
+                    lib.blvm_vrnn_seq_bwd_dec(w, ptr(enc), ptr(eps), ptr(decin), ptr(mu_q), ptr(sd_q), ptr(mu_p), ptr(sd_p), ptr(z),
+                                              ptr(reserve), ptr(x_sl_dev), ptr(c_raw), ptr(c_fn), stride, fn_floor, Tp, B, X, H, Z, R,
+                                              int(residual), sd_eps, ptr(d_enc), ptr(d_h0), g, ptr(ws), ptr(dz3), ptr(y1), ptr(y2), dw,
+                                              ptr(dy2), ptr(dy1), DH, SF, slope, ctypes.byref(folded), stream_ptr()),
+                    "blvm_vrnn_seq_bwd_dec",
+                )  # fmt: skip
+            if not folded.value:  # nothing was done: the data gradients as `_MLPFunction._backward` runs them, then the cell
+                gemm(0, 1, M, DH, SF, dz3, SF, W3, DH, dy2, DH, slope=slope, gate=y2, ldg=DH)
+                gemm(0, 1, M, DH, DH, dy2, DH, W2, DH, dy1, DH, slope=slope, gate=y1, ldg=DH)
+                dx = torch.empty(M, H + R, **f32)
+                gemm(0, 1, M, H + R, DH, dy1, DH, W1, H + R, dx, H + R, slope=slope)
+                dd = torch.zeros_like(decin)
+                dd[:Tp] = dx.view(Tp, B, H + R)
+                if d_decin is not None:
+                    dd = dd + _f32c(d_decin)
+                ws = torch.empty(lib.blvm_vrnn_bwd_workspace_floats(Tp, B, X, H, Z, R), **f32)
+                _tick("bwd_begin")
+                check(
+                    lib.blvm_vrnn_seq_bwd(w, ptr(enc), ptr(eps), ptr(decin), ptr(mu_q), ptr(sd_q), ptr(mu_p), ptr(sd_p), ptr(z),
+                                          ptr(reserve), ptr(dd), ptr(x_sl_dev), ptr(c_raw), ptr(c_fn), stride, fn_floor, Tp, B,
+                                          X, H, Z, R, int(residual), sd_eps, ptr(d_enc), ptr(d_h0), g, ptr(ws), stream_ptr()),
+                    "blvm_vrnn_seq_bwd",
+                )  # fmt: skip
+            _tick("bwd_end")
+            # the decoder's weight and bias gradients: one grouped launch, as `_MLPFunction._backward` (views of one zero-filled buffer)
+            dpar = (W1, b1, W2, b2, W3, b3)
+            want = [ctx.needs_input_grad[6 + 28 + i] for i in range(6)]
+            sizes = [(dpar[i].numel() + 3) // 4 * 4 if want[i] else 0 for i in range(6)]
+            flat = torch.zeros(sum(sizes), **f32)
+            views, off = [], 0
+            for i in range(6):
+                views.append(flat[off : off + dpar[i].numel()].view(dpar[i].shape) if want[i] else None)
+                off += sizes[i]
+            x2d = decin[:Tp].view(M, H + R)
+            wgrad_group([(dz3, y2, views[4], views[5]), (dy2, y1, views[2], views[3]), (dy1, x2d, views[0], views[1])], M)
+            return (d_enc, d_h0, None, None, None, None, *grads, *views)
+        params = params[:28]  # (a decoder whose output went unused: no gradient)
+        d_decin = _f32c(d_decin) if d_decin is not None else torch.zeros_like(decin)
         grads = _zeros_like_many(params)
         d_enc = torch.empty_like(enc)
         d_h0 = torch.empty(B, R, **f32) if ctx.has_h0 else None
@@ -889,7 +956,7 @@ class _VRNNSeqFunction(torch.autograd.Function):
             "blvm_vrnn_seq_bwd",
         )  # fmt: skip
         _tick("bwd_end")
-        return (d_enc, d_h0, None, None, None, None, *grads)
+        return (d_enc, d_h0, None, None, None, None, *grads, *dgrads)
 
 
 def vrnn_sequence(enc, h0, eps, x_sl_dev, params: Sequence[torch.Tensor], X, H, Z, R, residual_posterior, stride,
@@ -902,18 +969,26 @@ def vrnn_sequence(enc, h0, eps, x_sl_dev, params: Sequence[torch.Tensor], X, H, 
     fn_floor = float(free_nats) / Z if free_nats else 0.0
     cfg = (Tp, B, X, H, Z, R, int(residual_posterior), float(sd_eps), int(stride), fn_floor)  # 0 plain, 1 residual, 3 generate
     if decoder is None:
-        return _VRNNSeqFunction.apply(enc, h0, eps, x_sl_dev, cfg, None, *params)
-    decoder.given = None
-    return _VRNNSeqFunction.apply(enc, h0, eps, x_sl_dev, cfg, decoder, *params)
+        return _VRNNSeqFunction.apply(enc, h0, eps, x_sl_dev, cfg, None, *params)[:8]
+    decoder.given = decoder.dec = None
+    dparams = ()
+    if decoder.head_gates and load().blvm_vrnn_dec_bwd_fold(-1):  # the cell's node takes the decoder in (where the forward folds it)
+        dparams = tuple(t for lin in decoder.layers for t in (lin.weight, lin.bias))
+    *out, decoder.dec = _VRNNSeqFunction.apply(enc, h0, eps, x_sl_dev, cfg, decoder, *params, *dparams)
+    return tuple(out)
 
 
 class DecoderFold:
     """The VRNN decoder MLP handed down to the cell's forward (`vrnn_sequence`): `layers` = its three nn.Linear, LeakyReLU(`slope`)
     after each.  After the call `given` holds the three activations (plain tensors outside the graph; `mlp_given` builds the decoder's
-    autograd node from them) where the launch computed them, else None."""
+    autograd node from them) where the launch computed them, else None.
+    `head_gates`: the caller will feed the decoder's output to a fused likelihood head whose backward returns the gradient of the
+    last PRE-activation (`mlp_dmol_log_prob(..., dec_node=)`).  Then, with `blvm_vrnn_dec_bwd_fold` on and a forward launch that
+    folded the whole decoder, `dec` holds that output as an output of the cell's own node (the decoder's backward then runs with the
+    cell's, `_VRNNSeqFunction`) and the caller builds no decoder node; else `dec` is None."""
 
-    def __init__(self, layers, slope: float = LEAKY_SLOPE):
-        self.layers, self.slope, self.given = list(layers), float(slope), None
+    def __init__(self, layers, slope: float = LEAKY_SLOPE, head_gates: bool = False):
+        self.layers, self.slope, self.given, self.head_gates, self.dec = list(layers), float(slope), None, bool(head_gates), None
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -574,6 +574,9 @@ struct LinLate {
   bool add_polled, relu;
   float slope;
   Out out;
+  bool add_early = false;       // DF_ADD_EARLY
+  const float* add2 = nullptr;  // DF_ADD2_POLLED: [B, ldadd2], polled
+  int ldadd2 = 0;
 };
 // (ws, here and in the tiles below: the weight source — WMem, the pointer arguments, or a WRegs loaded for this very tile)
 template <int NW, int OT, class Late, class WS = WMem, class PC = PaceOff>
@@ -595,6 +598,7 @@ __device__ __forceinline__ void tile_lin_late(const float* A, int lda, bool a_po
     if (L.bias) e_bias = L.bias[col];
     if (L.gate) e_gate = L.gate[(size_t)rowc * L.ldgate + col];
     if (L.add && !L.add_polled) e_add = L.add[(size_t)rowc * L.ldadd + col];
+    if (L.add && L.add_polled && L.add_early) e_add = ld_sc1(make_rsrc(L.add), 4u * ((unsigned)rowc * (unsigned)L.ldadd + (unsigned)col));
   };
   f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
   if (A2 != nullptr) {  // (uniform) the operand arrives as three partial-sum slabs
@@ -618,15 +622,24 @@ __device__ __forceinline__ void tile_lin_late(const float* A, int lda, bool a_po
   }
 #endif
   if (threadIdx.x >= 256) return;
-  if (L.add && L.add_polled) {
+  if (L.add && L.add_polled && (!L.add_early || __any(own && is_sentinel(e_add)))) {
     const rsrc_t rs[1] = {make_rsrc(L.add)};
     const unsigned os[1] = {4u * ((unsigned)rowc * (unsigned)L.ldadd + (unsigned)col)};
     float ws[1];
     poll_words<1>(rs, os, ws, own, pl);
     e_add = ws[0];
   }
+  float e_add2 = 0.f;
+  if (L.add2) {
+    const rsrc_t rs[1] = {make_rsrc(L.add2)};
+    const unsigned os[1] = {4u * ((unsigned)rowc * (unsigned)L.ldadd2 + (unsigned)col)};
+    float ws[1];
+    poll_words<1>(rs, os, ws, own, pl);
+    e_add2 = ws[0];
+  }
   if (!own) return;
   float x = v[0] + e_bias + e_add;
+  if (L.add2) x += e_add2;
   if (L.relu) x = x > 0.f ? x : x * L.slope;
   if (L.gate) x = e_gate > 0.f ? x : x * L.slope;
   put(L.out, r0, c0, row, col, x);
@@ -1274,6 +1287,9 @@ enum DescFlag : int {
   DF_CANARY = 32,      // one-word canary wait in front of the operand poll
   DF_A_SUM3 = 64,      // K_LIN: the polled operand is the sum of three slabs (LIN_A, LIN_A2, LIN_A3) of partial sums
   DF_SEQ_GATE = 128,   // K_LINSEQ: the per-link auxiliary pointer is the derivative gate (backward chains), not the bias
+  DF_ADD_EARLY = 256,  // K_LIN with DF_ADD_POLLED: the addend was stored steps ago — requested with the epilogue's operands under the operand
+                       // wait (as tile_grub reads g_in) and polled again only where it still holds the sentinel
+  DF_ADD2_POLLED = 512,  // K_LIN: a second addend (LIN_ADD2, row stride i[LIN_I_LD_ADD2]) produced inside the launch
 };
 // ---- what the slots of a descriptor hold, by tile kind: each enum lists the kind's pointer slots p[] in order, then the indices of
 // the fields it reads: <KIND>_LD_* into ld[], _N16_* into n16[], _I_* into i[], _F_* into f[].  Every kind but K_LINSEQ: ld[LD_OUT] =
@@ -1282,9 +1298,9 @@ enum DescFlag : int {
 enum : int { LD_OUT = 3, N16_OUT = 0, N16_OUTB = 1 };
 // K_LIN: A (T16, polled; ld[LIN_LD_A] = its width when wider than K | row-major when DF_A_PLAIN), W (T16), bias, add, gate, out
 // row-major | T16 | second T16, (DF_A_SUM3) two more slabs of A: the operand is the sum of the three.  i: width of W's packed rows
-// when the product covers a K-range of them.
-enum : int { LIN_A, LIN_W, LIN_BIAS, LIN_ADD, LIN_GATE, LIN_ORM, LIN_O16, LIN_O16B, LIN_A2, LIN_A3, LIN_LD_A = 0, LIN_LD_ADD = 1, LIN_LD_GATE = 2,
-             LIN_I_W_WIDTH = 0, LIN_F_SLOPE = 0 };
+// when the product covers a K-range of them; (DF_ADD2_POLLED) the second addend and its row stride.
+enum : int { LIN_A, LIN_W, LIN_BIAS, LIN_ADD, LIN_GATE, LIN_ORM, LIN_O16, LIN_O16B, LIN_A2, LIN_A3, LIN_ADD2, LIN_LD_A = 0, LIN_LD_ADD = 1, LIN_LD_GATE = 2,
+             LIN_I_W_WIDTH = 0, LIN_I_LD_ADD2 = 1, LIN_F_SLOPE = 0 };
 // K_LINSEQ (add_linseq): A_0, then for link l at base + l: W_l, bias_l | gate_l (DF_SEQ_GATE), out_l row-major (ld[LINSEQ_LD_ORM + l])
 // and T16; add0: the first link's row-major addend or null.  i: links in the run, the first link's K when it is not the run's (0: it is).
 enum : int { LINSEQ_A0 = 0, LINSEQ_W = 1, LINSEQ_AUX = 5, LINSEQ_ORM = 9, LINSEQ_O16 = 13, LINSEQ_ADD0 = 17, LINSEQ_LD_ORM = 0,

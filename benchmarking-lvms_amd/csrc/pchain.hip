@@ -200,9 +200,17 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             auto late = [&]() {
               __builtin_amdgcn_sched_barrier(0);
               nx.fetch(ltab, nx_i, nx_s);  // (per tile: the same lanes again — cheaper than a flag carried through the visit)
-              return LinLate{d.base<LIN_BIAS>(), d.p<LIN_ADD>(s), d.p<LIN_GATE>(s), d.w<RD_LD + LIN_LD_ADD>(), d.w<RD_LD + LIN_LD_GATE>(), (flags & DF_ADD_POLLED) != 0,
-                             (flags & DF_RELU) != 0, d.f<LIN_F_SLOPE>(), Out{d.m<LIN_ORM>(s), d.w<RD_LD + LD_OUT>(), (flags & DF_RM_SC1) != 0, d.m<LIN_O16>(s),
-                                                                             d.w<RD_N16 + N16_OUT>(), d.m<LIN_O16B>(s), d.w<RD_N16 + N16_OUTB>()}};
+              // (the early and the second addend: the fp32 training instantiation only — pchain_run refuses them elsewhere; in the 16-bit
+              // kernels the three extra fields cost 35 SGPR spills and 0.25 ms of a bf16 VRNN step, used or not)
+              if constexpr (OT == OP_F32 && !ROLL)
+                return LinLate{d.base<LIN_BIAS>(), d.p<LIN_ADD>(s), d.p<LIN_GATE>(s), d.w<RD_LD + LIN_LD_ADD>(), d.w<RD_LD + LIN_LD_GATE>(), (flags & DF_ADD_POLLED) != 0,
+                               (flags & DF_RELU) != 0, d.f<LIN_F_SLOPE>(), Out{d.m<LIN_ORM>(s), d.w<RD_LD + LD_OUT>(), (flags & DF_RM_SC1) != 0, d.m<LIN_O16>(s),
+                                                                               d.w<RD_N16 + N16_OUT>(), d.m<LIN_O16B>(s), d.w<RD_N16 + N16_OUTB>()},
+                               (flags & DF_ADD_EARLY) != 0, (flags & DF_ADD2_POLLED) ? d.p<LIN_ADD2>(s) : nullptr, d.w<RD_I + LIN_I_LD_ADD2>()};
+              else
+                return LinLate{d.base<LIN_BIAS>(), d.p<LIN_ADD>(s), d.p<LIN_GATE>(s), d.w<RD_LD + LIN_LD_ADD>(), d.w<RD_LD + LIN_LD_GATE>(), (flags & DF_ADD_POLLED) != 0,
+                               (flags & DF_RELU) != 0, d.f<LIN_F_SLOPE>(), Out{d.m<LIN_ORM>(s), d.w<RD_LD + LD_OUT>(), (flags & DF_RM_SC1) != 0, d.m<LIN_O16>(s),
+                                                                               d.w<RD_N16 + N16_OUT>(), d.m<LIN_O16B>(s), d.w<RD_N16 + N16_OUTB>()}};
             };
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
@@ -661,6 +669,8 @@ int pchain_run(const pchain::Program& prog, hipStream_t stream) {
       BLVM_REQUIRE(k == pchain::K_LIN || k == pchain::K_LINSEQ || k == pchain::K_HEAD || k == pchain::K_GRU || k == pchain::K_DZ || k == pchain::K_GRUB,
                    "pchain: tile kind %d has no row-group form", k);
       BLVM_REQUIRE(k != pchain::K_DZ || prog.d[i].p[2] == nullptr, "pchain: the row-group dz tile is the single-product form");
+      BLVM_REQUIRE(k != pchain::K_LIN || (prog.d[i].flags & (pchain::DF_ADD_EARLY | pchain::DF_ADD2_POLLED)) == 0,
+                   "pchain: the row-group linear tile has one addend, polled behind its product");
     }
     BLVM_REQUIRE(prog.ot == OP_F32, "pchain: row groups multiply fp32 operands only");
     BLVM_TRY(go(&pchain_rt_kernel<8, OP_F32, 2>, 2, 512));
@@ -669,6 +679,9 @@ int pchain_run(const pchain::Program& prog, hipStream_t stream) {
   }
   bool roll = false;
   for (int i = 0; i < prog.ndesc; ++i) roll |= prog.d[i].kind == pchain::K_LSTM;
+  for (int i = 0; i < prog.ndesc; ++i)
+    BLVM_REQUIRE(prog.d[i].kind != pchain::K_LIN || (prog.d[i].flags & (pchain::DF_ADD_EARLY | pchain::DF_ADD2_POLLED)) == 0 || (prog.ot == OP_F32 && !roll),
+                 "pchain: an early or a second polled addend runs in the fp32 training kernel only");
   if (roll) {  // the roll-out's own instantiation
     for (int i = 0; i < prog.ndesc; ++i) {
       const int k = prog.d[i].kind;

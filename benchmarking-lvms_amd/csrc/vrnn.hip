@@ -231,9 +231,13 @@ struct BwdWs {
   float *GA, *GB, *DP16[3], *DQ16[3], *DGI16, *DGH16, *DPHI16[4], *DPH16, *DQH16, *DPHI16b, *DPHI16c;
   size_t x16_bytes;  // from the first piece a launch polls to the end of the T16 copies: sentinel-filled in one go
   float *DPHI3b, *DPHI3c;  // row-major partial sums of DPHI[3] when its K = 3R product is split over three links (added up after the launch)
+  // decoder leader of the backward launch (SF > 0; vrnn_static.h): the hand-off slabs of the decoder's two hidden gradients, the polled
+  // row-major gradient of the decoder's input [T',B,H+R] (inside the sentinel-filled stretch), and the transposed T16 copies of the
+  // three weights (behind everything else)
+  float *DY216, *DY116, *DD, *dT[3];
 };
 
-size_t carve_ws(float* base, int Tp, int B, int X, int H, int Z, int R, BwdWs* w) {
+size_t carve_ws(float* base, int Tp, int B, int X, int H, int Z, int R, BwdWs* w, int SF = 0) {
   (void)X;
   const size_t n = (size_t)Tp * B;
   Arena ar{base};
@@ -261,8 +265,11 @@ size_t carve_ws(float* base, int Tp, int B, int X, int H, int Z, int R, BwdWs* w
     for (int i = 0; i < 4; ++i) t.DPHI16[i] = ar.take(m * H);
     t.DPH16 = ar.take(m * 2 * Z); t.DQH16 = ar.take(m * 2 * Z);
     t.DPHI16b = ar.take(m * H); t.DPHI16c = ar.take(m * H);
+    t.DY216 = t.DY116 = t.DD = nullptr;
+    if (SF > 0) { t.DY216 = ar.take(m * H); t.DY116 = ar.take(m * H); t.DD = ar.take(n * (H + R)); }
     t.x16_bytes = ar.bytes_from(t.GA);
     t.DPHI3b = ar.take(n * H); t.DPHI3c = ar.take(n * H);
+    if (SF > 0) { t.dT[0] = ar.take((size_t)(H + R) * H); t.dT[1] = ar.take((size_t)H * H); t.dT[2] = ar.take((size_t)H * SF); }
   }
   if (w) *w = t;
   return ar.floats();
@@ -307,6 +314,29 @@ int vrnn_dec_folds(int B, int H, int Z, int R, int DH, int SF) {
   return fits ? layers : 0;
 }
 
+// blvm_vrnn_seq_bwd_dec: the decoder's data gradients on the backward walk's spare range (vrnn_static.h "decoder leader")
+struct VrnnDecBwd {
+  const float *dz3, *y1, *y2, *w[3];  // gradient of the last pre-activation [T'B, SF]; the two hidden activations; the three weights
+  float *dy2, *dy1;                   // out: gradients of the hidden pre-activations [T'B, DH] (the caller's weight gradients read them)
+  int DH, SF;
+  float slope;
+};
+// blvm_vrnn_dec_bwd_fold; env BLVM_VRNN_DEC_BWD_FOLD=0: never
+int g_dec_bwd_fold = [] { const char* e = getenv("BLVM_VRNN_DEC_BWD_FOLD"); return e ? (atoi(e) != 0 ? 1 : 0) : 1; }();
+long g_dec_bwd_folded = 0;  // backward calls that computed the decoder's data gradients inside the launch
+// Whether a backward call folds: where the forward fold applies (vrnn_dec_folds' conditions) and in addition the walk has the
+// static kernels' widths, the backward program takes its split3 form on the own-range deal, the deal has a leader range, and the
+// walk is long enough to arm its slabs (vrnn_static.h kArmAhead) and to lead (kBdecAhead).
+bool vrnn_dec_bwd_folds(int Tp, int B, int H, int Z, int R, int DH, int SF) {
+  if (!g_dec_bwd_fold || !vrnn_persistent(B) || device_cus() < 32 || operand_16bit() || pchain_optype(B) != OP_F32) return false;
+  if (B > 64 || vrnn_row_groups(B) || Z != H || DH != H || H != 256 || R != 512 || SF <= 0 || SF % 16 != 0) return false;
+  if (Tp + 1 <= pchain::kArmAhead || Tp <= pchain::kBdecAhead) return false;
+  const int tl = (B + 15) / 16;
+  if (vrnn_shared_deal(false, tl)) return false;
+  const pchain::VrnnBwdDeal dl = pchain::vrnn_bwd_deal(H / 16, Z / 16, R / 16, tl, device_cus() & ~7, false, pchain_split3(), (H + R) / 16);
+  return dl.split3 && dl.bdec[0].nwg > 0;
+}
+
 int check_dims(int Tp, int B, int X, int H, int Z, int R) {
   BLVM_REQUIRE(Tp > 0 && B > 0, "vrnn: bad Tp=%d B=%d", Tp, B);
   BLVM_REQUIRE(X > 0 && H > 0 && Z > 0 && R > 0 && X % 16 == 0 && H % 16 == 0 && Z % 16 == 0 && R % 16 == 0,
@@ -337,6 +367,15 @@ extern "C" int blvm_vrnn_dec_fold(int mode) {
 
 extern "C" size_t blvm_vrnn_bwd_workspace_floats(int Tp, int B, int X, int H, int Z, int R) {
   return carve_ws(nullptr, Tp, B, X, H, Z, R, nullptr);
+}
+extern "C" size_t blvm_vrnn_bwd_dec_workspace_floats(int Tp, int B, int X, int H, int Z, int R, int DH, int SF) {
+  return carve_ws(nullptr, Tp, B, X, H, Z, R, nullptr, vrnn_dec_bwd_folds(Tp, B, H, Z, R, DH, SF) ? SF : 0);  // (grown only where the call folds)
+}
+extern "C" int blvm_vrnn_dec_bwd_fold(int mode) {
+  if (mode == -2) return (int)std::min<long>(g_dec_bwd_folded, 0x7fffffffL);
+  const int was = g_dec_bwd_fold;
+  if (mode >= 0) g_dec_bwd_fold = mode != 0;
+  return was;
 }
 
 static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const float* h0, const float* eps,
@@ -586,16 +625,17 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
                              const float* z, const float* reserve, const float* d_decin, const int32_t* x_sl,
                              const float* c_raw, const float* c_fn, int stride, float fn_floor, int Tp, int B, int X, int H, int Z,
                              int R, int residual_posterior, float sd_eps, float* d_enc, float* d_h0,
-                             const BlvmVrnnGrads* gr, float* workspace, hipStream_t s) {
+                             const BlvmVrnnGrads* gr, float* workspace, hipStream_t s, const VrnnDecBwd* dec = nullptr) {
+  // dec: the caller has checked vrnn_dec_bwd_folds — the decoder's data gradients run on the walk and d_decin is not read
   BLVM_TRY(check_dims(Tp, B, X, H, Z, R));
-  BLVM_REQUIRE(w && enc && eps && decin && mu_q && sd_q && mu_p && sd_p && z && reserve && d_decin && workspace && gr,
+  BLVM_REQUIRE(w && enc && eps && decin && mu_q && sd_q && mu_p && sd_p && z && reserve && (d_decin || dec) && workspace && gr,
                "vrnn_bwd: null pointer");
   BLVM_REQUIRE((c_fn == nullptr && c_raw == nullptr) || x_sl != nullptr, "vrnn_bwd: KL coefficients need x_sl");
   BLVM_REQUIRE(aligned16(workspace) && aligned16(reserve) && aligned16(d_decin), "vrnn_bwd: buffers must be 16-byte aligned");
   Reserve rs;
   carve_reserve(const_cast<float*>(reserve), Tp, B, H, Z, R, &rs);
   BwdWs ws;
-  carve_ws(workspace, Tp, B, X, H, Z, R, &ws);
+  carve_ws(workspace, Tp, B, X, H, Z, R, &ws, dec ? dec->SF : 0);
   const size_t n = (size_t)Tp * B;
   const int ldd = H + R;
   const float beta = softplus_beta_of(sd_eps);
@@ -614,6 +654,11 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   for (int i = 1; i < 4; ++i) BLVM_TRY(t16_pack_transposed(w->phi_w[i], H, H, H, ws.fT[i], s));
   BLVM_TRY(t16_pack_transposed(w->gru_wih + X, X + H, 3 * R, H, ws.wihT, s));
   BLVM_TRY(t16_pack_transposed(w->gru_whh, R, 3 * R, R, ws.whhT, s));
+  if (dec) {  // the decoder's three, in the same launch
+    BLVM_TRY(t16_pack_transposed(dec->w[0], H + R, H, H + R, ws.dT[0], s));
+    BLVM_TRY(t16_pack_transposed(dec->w[1], H, H, H, ws.dT[1], s));
+    BLVM_TRY(t16_pack_transposed(dec->w[2], H, dec->SF, H, ws.dT[2], s));
+  }
   BLVM_TRY(pack_scope.flush());  // all packs above in one launch
 
   BLVM_HIP(hipMemsetAsync(ws.G, 0, sizeof(float) * (size_t)B * R, s));
@@ -688,7 +733,8 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     // (shared deal: see vrnn_fwd -- here the gentle link is GB, which the posterior half runs while the prior half
     // takes the gradient back through the phi_z run and the heads)
     const bool shared = vrnn_shared_deal(groups, tl);
-    const VrnnBwdDeal dl = vrnn_bwd_deal(ctH, ctZ, ctR, tl, cus, shared, pchain_split3());  // (vrnn_static.h: the ranges of every link)
+    const VrnnBwdDeal dl = vrnn_bwd_deal(ctH, ctZ, ctR, tl, cus, shared, pchain_split3(), dec ? (H + R) / 16 : 0);  // (vrnn_static.h: the ranges of every link)
+    BLVM_REQUIRE(!dec || (dl.split3 && dl.bdec[0].nwg > 0 && !groups), "vrnn_bwd: the deal has no decoder leader range");
     Builder bld;
     bld.begin(pchain_optype(B), T + 1, B, groups ? 8 : 2, true, dl.g);
     bld.p.rt_group = RTG;
@@ -697,7 +743,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       Operands o;
       o.p[GRUB_D0_16] = rev(ws.DP16[0], xH, T); o.p[GRUB_D1_16] = rev(ws.DQ16[0], xH, T); o.p[GRUB_W0] = ws.pT[0]; o.p[GRUB_W1] = ws.qT[0];
       o.p[GRUB_G_IN] = rev(ws.GB, sR, T); o.p[GRUB_RG] = last(rs.RG, sR); o.p[GRUB_UG] = last(rs.UG, sR); o.p[GRUB_NG] = last(rs.NG, sR);
-      o.p[GRUB_GH] = last(rs.GHb, s3R); o.p[GRUB_HPREV] = last(decin + H, sD); o.p[GRUB_DD] = last(d_decin + H, sD); o.p[GRUB_DGI] = last(ws.DGI, s3R);
+      o.p[GRUB_GH] = last(rs.GHb, s3R); o.p[GRUB_HPREV] = last(decin + H, sD); o.p[GRUB_DD] = dec ? Ptr() : last(d_decin + H, sD); o.p[GRUB_DGI] = last(ws.DGI, s3R);
       o.p[GRUB_DGI16] = last(ws.DGI16, x3R); o.p[GRUB_DGH] = last(ws.DGH, s3R); o.p[GRUB_DGH16] = last(ws.DGH16, x3R); o.p[GRUB_GA] = last(ws.GA, sR);
       o.p[GRUB_G_OUT] = d_h0 ? d_h0 : ws.G; o.ld[GRUB_LD_H] = ldd; o.ld[LD_OUT] = 3 * R; o.n16[N16_OUT] = 3 * ctR; o.i[GRUB_I_R] = R; o.i[GRUB_I_GEMM_FROM] = 1;
       o.i[GRUB_I_GATES_TO] = T; o.i[GRUB_I_GIN_FROM] = 1;
@@ -717,9 +763,12 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       float* const o16[3] = {ws.DPHI16[3], ws.DPHI16b, ws.DPHI16c};
       o.ld[LIN_LD_A] = 3 * R; o.i[LIN_I_W_WIDTH] = 3 * R;
       for (int part = 0; part < 3; ++part) {
-        o.p[LIN_A] = last(ws.DGI16 + (size_t)part * ctR * 256, x3R); o.p[LIN_W] = ws.wihT + part * wthird; o.p[LIN_ADD] = part == 0 ? last(d_decin, sD) : Ptr();
+        // (the decoder's gradient: from outside the launch it joins the first partial sum; from the leader, which runs on the third
+        // part's range, the third — polled, stored kBdecAhead steps earlier)
+        o.p[LIN_A] = last(ws.DGI16 + (size_t)part * ctR * 256, x3R); o.p[LIN_W] = ws.wihT + part * wthird;
+        o.p[LIN_ADD] = dec ? (part == 2 ? last(ws.DD, sD) : Ptr()) : (part == 0 ? last(d_decin, sD) : Ptr());
         o.p[LIN_ORM] = last(orm[part], sH); o.p[LIN_O16] = last(o16[part], xH);
-        add_desc(bld, K_LIN, ctH, dl.part[part].wg0, dl.part[part].nwg, R, 0, 0, T, o);
+        add_desc(bld, K_LIN, ctH, dl.part[part].wg0, dl.part[part].nwg, R, dec && part == 2 ? DF_ADD_POLLED | DF_ADD_EARLY : 0, 0, T, o);
       }
     } else {
       o.p[LIN_A] = last(ws.DGI16, x3R); o.p[LIN_W] = ws.wihT; o.p[LIN_ADD] = last(d_decin, sD); o.p[LIN_ORM] = last(ws.DPHI[3], sH);
@@ -728,7 +777,9 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     }
     Operands gb;
     gb.p[LIN_A] = last(ws.DGH16, x3R); gb.p[LIN_W] = ws.whhT; gb.p[LIN_ADD] = last(ws.GA, sR); gb.ld[LIN_LD_ADD] = R; gb.p[LIN_ORM] = last(ws.GB, sR); gb.ld[LD_OUT] = R;
-    add_desc(bld, K_LIN, ctR, dl.gb.wg0, dl.gb.nwg, 3 * R, DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0), 0, T, gb);
+    if (dec) { gb.p[LIN_ADD2] = last(ws.DD + H, sD); gb.i[LIN_I_LD_ADD2] = ldd; }  // GB = GA + (the decoder's gradient wrt h) + DGH W_hh, GA = g u
+    add_desc(bld, K_LIN, ctR, dl.gb.wg0, dl.gb.nwg, 3 * R,
+             DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | ((pchain_tune() & 16) ? DF_CANARY : 0) | (dec ? DF_ADD2_POLLED : 0), 0, T, gb);
     // B3..B5: back through phi_z layers 3, 2, 1: runs of backward links (K_LINSEQ), D_{i+1} = (D_i W_i) masked by the saved activation
     auto blink = [&](const float* W, const float* gate, float* orm, float* o16) { return rev_link(W, gate, orm, o16, T - 1, sH, H, xH); };
     const SeqLink lf[3] = {blink(ws.fT[3], rs.FZ[2], ws.DPHI[2], ws.DPHI16[2]), blink(ws.fT[2], rs.FZ[1], ws.DPHI[1], ws.DPHI16[1]),
@@ -758,6 +809,22 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       add_linseq(bld, ctH, dl.prior.wg0, dl.prior.nwg, H, false, true, 0, T, last(ws.DPH16, x2Z), 3, lp, -sH, -xH, ctH, 0.f, H, 2 * Z);
       add_linseq(bld, ctH, dl.post.wg0, dl.post.nwg, H, false, true, 0, T, last(ws.DQH16, x2Z), 3, lq, -sH, -xH, ctH, 0.f, H, 2 * Z);
     }
+    if (dec) {
+      // the decoder leader (vrnn_static.h): walk step s runs the decoder's data gradients of walk step s + kBdecAhead — the pointers
+      // start there and the links end kBdecAhead steps early; the first kBdecAhead walk steps' rows come from K6 in front of the launch
+      const int L = kBdecAhead, SF = dec->SF;
+      const long sF = (long)B * SF;
+      auto lead = [&](const float* base, long step) { return rev(base, step, T - 1 - L); };
+      Operands b0, b1, b2;
+      b0.p[LIN_A] = lead(dec->dz3, sF); b0.ld[LIN_LD_A] = SF; b0.p[LIN_W] = ws.dT[2]; b0.p[LIN_GATE] = lead(dec->y2, sH); b0.ld[LIN_LD_GATE] = H;
+      b0.p[LIN_ORM] = lead(dec->dy2, sH); b0.ld[LD_OUT] = H; b0.p[LIN_O16] = lead(ws.DY216, xH); b0.n16[N16_OUT] = ctH; b0.f[LIN_F_SLOPE] = dec->slope;
+      add_desc(bld, K_LIN, ctH, dl.bdec[0].wg0, dl.bdec[0].nwg, SF, DF_A_PLAIN | DF_GENTLE, 0, T - L, b0);
+      b1.p[LIN_A] = lead(ws.DY216, xH); b1.p[LIN_W] = ws.dT[1]; b1.p[LIN_GATE] = lead(dec->y1, sH); b1.ld[LIN_LD_GATE] = H;
+      b1.p[LIN_ORM] = lead(dec->dy1, sH); b1.ld[LD_OUT] = H; b1.p[LIN_O16] = lead(ws.DY116, xH); b1.n16[N16_OUT] = ctH; b1.f[LIN_F_SLOPE] = dec->slope;
+      add_desc(bld, K_LIN, ctH, dl.bdec[1].wg0, dl.bdec[1].nwg, H, DF_GENTLE | DF_CANARY, 0, T - L, b1);
+      b2.p[LIN_A] = lead(ws.DY116, xH); b2.p[LIN_W] = ws.dT[0]; b2.p[LIN_ORM] = lead(ws.DD, sD); b2.ld[LD_OUT] = ldd;
+      add_desc(bld, K_LIN, (H + R) / 16, dl.bdec[2].wg0, dl.bdec[2].nwg, H, DF_RM_SC1 | DF_GENTLE | DF_CANARY, 0, T - L, b2);
+    }
     // what the launch polls gets sentinels: GA, GB (single words) and the T16 copies, from the host or slab by slab from the walk
     // (vrnn_static.h ArmPlan; the table's walk step j is time step T' - 1 - j)
     ArmPlan plan;
@@ -769,8 +836,19 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       for (int i = 0; i < 4; ++i) plan.add(arm_t16(ws.DPHI16[i], H, rt, T, true));
       plan.add(arm_t16(ws.DPH16, 2 * Z, rt, T, true)); plan.add(arm_t16(ws.DQH16, 2 * Z, rt, T, true));
       plan.add(arm_t16(ws.DPHI16b, H, rt, T, true)); plan.add(arm_t16(ws.DPHI16c, H, rt, T, true));
+      if (dec) { plan.add(arm_t16(ws.DY216, H, rt, T, true)); plan.add(arm_t16(ws.DY116, H, rt, T, true)); plan.add(arm_rm(ws.DD, ldd, B, T, true)); }
     }
-    BLVM_TRY(vrnn_launch(bld, false, "vrnn_bwd", s, plan, []() -> int { return BLVM_OK; }));
+    // the leader's first rows (time steps T' - kBdecAhead .. T' - 1) as K6 products, behind the fill: the walk polls their DD slabs
+    auto lead_rows = [&]() -> int {
+      if (!dec) return BLVM_OK;
+      const int L = kBdecAhead, M = L * B, SF = dec->SF;
+      const size_t r0 = (size_t)(T - L) * B;
+      BLVM_TRY(gemm_f32(0, 1, M, H, SF, dec->dz3 + r0 * SF, SF, dec->w[2], H, dec->dy2 + r0 * H, H, nullptr, 0, dec->slope, dec->y2 + r0 * H, H, 0, 1, s));
+      BLVM_TRY(gemm_f32(0, 1, M, H, H, dec->dy2 + r0 * H, H, dec->w[1], H, dec->dy1 + r0 * H, H, nullptr, 0, dec->slope, dec->y1 + r0 * H, H, 0, 1, s));
+      return gemm_f32(0, 1, M, H + R, H, dec->dy1 + r0 * H, H, dec->w[0], H + R, ws.DD + r0 * ldd, ldd, nullptr, 0, 0.f, nullptr, 0, 0, 1, s);
+    };
+    BLVM_TRY(vrnn_launch(bld, false, "vrnn_bwd", s, plan, lead_rows));
+    if (dec) ++g_dec_bwd_folded;
     if (split3) {  // DPHI[3] += the two other partial sums
       const size_t n4 = n * H / 4;
       hipLaunchKernelGGL(add3_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, reinterpret_cast<float4*>(ws.DPHI[3]),
@@ -779,6 +857,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     return batched();
   }
 
+  BLVM_REQUIRE(!dec, "vrnn_bwd: the decoder leader needs the persistent path");
   launch_dh(-1, Tp - 1);  // G(T') = 0: gate derivatives of the last step, G <- d_decin h-part of row T'-1
   for (int t = Tp - 1; t >= 0; --t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z, o3R = (size_t)t * B * 3 * R, o2Z = (size_t)t * B * 2 * Z;
@@ -835,4 +914,24 @@ extern "C" int blvm_vrnn_seq_bwd(const BlvmVrnnWeights* w, const float* enc, con
                                  const BlvmVrnnGrads* gr, float* workspace, void* stream_) {
   return vrnn_seq_bwd_impl(w, enc, eps, decin, mu_q, sd_q, mu_p, sd_p, z, reserve, d_decin, x_sl, c_raw, c_fn, stride, fn_floor, Tp, B, X,
                            H, Z, R, residual_posterior, sd_eps, d_enc, d_h0, gr, workspace, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int blvm_vrnn_seq_bwd_dec(const BlvmVrnnWeights* w, const float* enc, const float* eps, const float* decin,
+                                     const float* mu_q, const float* sd_q, const float* mu_p, const float* sd_p, const float* z,
+                                     const float* reserve, const int32_t* x_sl, const float* c_raw, const float* c_fn, int stride,
+                                     float fn_floor, int Tp, int B, int X, int H, int Z, int R, int residual_posterior, float sd_eps,
+                                     float* d_enc, float* d_h0, const BlvmVrnnGrads* gr, float* workspace, const float* dz3,
+                                     const float* dec_y1, const float* dec_y2, const float* const* dec_w, float* dy2, float* dy1, int DH,
+                                     int SF, float slope, int* folded, void* stream_) {
+  BLVM_REQUIRE(folded != nullptr, "vrnn_bwd_dec: null pointer");
+  *folded = 0;
+  BLVM_TRY(check_dims(Tp, B, X, H, Z, R));
+  if (!vrnn_dec_bwd_folds(Tp, B, H, Z, R, DH, SF)) return BLVM_OK;  // nothing done: the caller takes blvm_vrnn_seq_bwd's path
+  BLVM_REQUIRE(dz3 && dec_y1 && dec_y2 && dec_w && dec_w[0] && dec_w[1] && dec_w[2] && dy2 && dy1, "vrnn_bwd_dec: null pointer");
+  BLVM_REQUIRE(aligned16(dz3) && aligned16(dy2) && aligned16(dy1), "vrnn_bwd_dec: buffers must be 16-byte aligned");
+  const VrnnDecBwd dec{dz3, dec_y1, dec_y2, {dec_w[0], dec_w[1], dec_w[2]}, dy2, dy1, DH, SF, slope};
+  BLVM_TRY(vrnn_seq_bwd_impl(w, enc, eps, decin, mu_q, sd_q, mu_p, sd_p, z, reserve, nullptr, x_sl, c_raw, c_fn, stride, fn_floor, Tp, B, X,
+                             H, Z, R, residual_posterior, sd_eps, d_enc, d_h0, gr, workspace, static_cast<hipStream_t>(stream_), &dec));
+  *folded = 1;
+  return BLVM_OK;
 }

@@ -60,12 +60,22 @@ inline VrnnFwdDeal vrnn_fwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, boo
 }
 // backward: GRU backward; dphi as one link or (split3: a third range is free) three K = R partial-sum links side by side; GB
 // (gentle); the summing link, the phi_z run and dz on the wide range; the prior | posterior runs on a half each
+// backward, decoder leader (ctD > 0 = the column tiles of the decoder's input, (H + R) / 16; split3 only): the spare range, which
+// owns one partial-sum tile per workgroup and then waits for the rest of the step, runs the decoder MLP's data gradients of the
+// time step kBdecAhead walk steps ahead of the chain, three gentle links on the range of part[2]:
+//   bdec[0]  dY2 = gate_Y2(dZ3 Wd3)   (K = S F: dZ3 is complete before the launch, row-major, not polled)
+//   bdec[1]  dY1 = gate_Y1(dY2 Wd2)   (K = H, resident weights: one tile per workgroup)
+//   bdec[2]  dD  = dY1 Wd1            (K = H, ctD column tiles: the phi part | the h part)
+// dD's phi part is the polled addend of part[2], its h part the second polled addend of GB.  On the range of part[2] (16 tl
+// workgroups) TileIter gives the workgroup of part[2]'s tile (r, c) the tile (r, c) of bdec[2] too, in both modes: the addend a
+// partial-sum tile polls is the one its own workgroup stored.  Empty (nwg = 0 in all three) where a link does not fit.
+constexpr int kBdecAhead = 2;  // walk steps the leader runs ahead (at most kArmAhead - 2: see arm_applies)
 struct VrnnBwdDeal {
   int def_n, half, g, spare;
   bool split3;
-  LinkRange grub, part[3], dphi, gb, wide_h, dz, prior, post;
+  LinkRange grub, part[3], dphi, gb, wide_h, dz, prior, post, bdec[3];
 };
-inline VrnnBwdDeal vrnn_bwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, bool shared, bool allow_split3) {
+inline VrnnBwdDeal vrnn_bwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, bool shared, bool allow_split3, int ctD = 0) {
   VrnnBwdDeal d;
   d.def_n = shared ? 0 : range_for(ctR * tl, std::min(cus / 4, 64));  // GB link
   d.half = range_for(ctH * tl, (cus - d.def_n) / 2);
@@ -83,6 +93,17 @@ inline VrnnBwdDeal vrnn_bwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, boo
   d.dz = LinkRange{ctZ, 0, range_for(ctZ * tl, wide)};
   d.prior = LinkRange{ctH, 0, d.half};
   d.post = LinkRange{ctH, d.half, d.half};
+  for (LinkRange& r : d.bdec) r = LinkRange{0, 0, 0};
+  if (ctD > 0 && d.split3) {
+    const int w0 = d.part[2].wg0, n = d.part[2].nwg;
+    bool fits = n == ctH * tl;  // (one partial-sum tile on every workgroup of the range: the leader's tiles line up with them)
+    for (bool xcd : {false, true})
+      fits = fits && tiles_per_workgroup(tl, ctH, n, xcd) <= 1 && tiles_per_workgroup(tl, ctD, n, xcd) <= kMaxTiles;
+    if (fits) {
+      d.bdec[0] = d.bdec[1] = LinkRange{ctH, w0, n};
+      d.bdec[2] = LinkRange{ctD, w0, n};
+    }
+  }
   return d;
 }
 
@@ -93,6 +114,9 @@ constexpr std::initializer_list<int> kBwdResident = {0, 1, 2, 3, 5, 6, 7, 8, 9};
 // the forward program with the decoder range: descriptors 6 .. 9 are dec[0 .. 3] of the deal; the first three are resident too
 constexpr int kFwdDesc = 6, kFwdDecDesc = 10;
 constexpr std::initializer_list<int> kFwdDecResident = {6, 7, 8};
+// the backward program with the decoder leader: descriptors 10 .. 12 are bdec[0 .. 2] of the deal; bdec[1] is resident
+constexpr int kBwdDesc = 10, kBwdDecDesc = 13;
+constexpr std::initializer_list<int> kBwdDecResident = {11};
 // the converter's condition: every resident link deals a workgroup at most one tile (else the interpreter runs the program)
 // (xcd: the TileIter mode the kernel will deal with — the program's own, or plain under a placement of the launch, below)
 inline bool one_tile_each(const Program& p, std::initializer_list<int> links, bool xcd) {
@@ -223,6 +247,8 @@ inline int arm_operand_slot(int kind) {
 // workgroups [cand0, cand0 + ncand) arm around; idle: the links those workgroups must own no tile of (they wait while others walk
 // them: the window the stores go into, and the registers — vrnn_static.hip fwd_post_arming); xcd: the launch's TileIter mode.
 //   - every link multiplies a stepped operand that lies in a buffer of the table: it polls, so nothing runs ahead of the chain;
+//     the one exemption is a K_LIN whose operand is complete before the launch (DF_A_PLAIN: dZ3 of the decoder leader) — every
+//     workgroup with a tile of it must own a tile of the arming role's link, whose poll it runs behind in every step;
 //   - every arming workgroup owns exactly one tile of the role's link, and every row tile has armers, a power of two of them;
 //   - every buffer of the table has the program's row-tile geometry: 16-byte aligned pieces, row tiles inside their slab.
 inline bool arm_applies(const Program& p, const ArmTable& t, int link, std::initializer_list<int> idle, int cand0, int ncand, bool xcd) {
@@ -239,6 +265,12 @@ inline bool arm_applies(const Program& p, const ArmTable& t, int link, std::init
     const Desc& d = p.d[i];
     const int slot = arm_operand_slot(d.kind);
     if (slot < 0 || d.p[slot] == nullptr || p.stride[d.sidx[slot]] == 0) return false;
+    if (d.kind == K_LIN && (d.flags & DF_A_PLAIN) != 0) {
+      const Desc& role = p.d[link];
+      for (int w = d.wg0; w < d.wg0 + d.nwg; ++w)
+        if (TileIter(w, d.wg0, d.nwg, rt, d.ct, xcd).valid() && !TileIter(w, role.wg0, role.nwg, rt, role.ct, xcd).valid()) return false;
+      continue;
+    }
     bool inside = false;
     for (int k = 0; k < t.n && !inside; ++k) {
       const ArmEntry& e = t.e[k];

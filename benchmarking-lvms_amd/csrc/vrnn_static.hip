@@ -54,8 +54,10 @@ __device__ __forceinline__ int tile_count(int lanes) { return __popcll(__ballot(
 // the first issue to the successful poll, ticks from there to the tile's last T16 store (waves that store nothing: to the tile's
 // end)} to a table in LDS; the first workgroup of each role copies its table to the blvm_pchain_profile buffer when it is done:
 // words [kAnatBase + role * kAnatRole + (slot * 2 + class) * 4 + j].  Roles: 0 / 1 forward halves (or the chain probe), 2 / 3
-// backward halves, 4 the backward's spare range.  Slot = 4 * (index of the link in its program) + link of the run.
-constexpr int kAnatBase = 128, kAnatRole = 512, kAnatSlots = 48;
+// backward halves, 4 the backward's spare range.  Slot = 4 * (index of the link in its program) + link of the run.  (With the decoder
+// leader the spare role also leaves, in slots 13 and 14, its walk steps and the ticks it spent in the leader's links, in the arming
+// stores and in the whole loop: bwd_spare_leader.)
+constexpr int kAnatBase = 128, kAnatRole = 512, kAnatSlots = 56;
 #ifdef PCHAIN_TPROF
 __device__ __forceinline__ void anat_begin(unsigned* tab) {
   for (int i = threadIdx.x; i < kAnatSlots * 8; i += blockDim.x) tab[i] = 0u;
@@ -269,27 +271,34 @@ typedef PaceK<VRNN_PACE_EARLY, VRNN_PACE_EPI> Paced;
 // ROW_ONCE: the canary wait only in front of the first tile of a row tile.  A workgroup's tiles of a visit that share their row tile
 // read the same [16, K] slab (with four row tiles on a range of 8 k workgroups: all of them), and once its canary words have arrived
 // the later tiles' operand polls succeed at once; a canary per tile is a round trip and a barrier each for nothing.
-template <int NW, int K, int FLAGS, class PC = PaceOff, bool ROW_ONCE = false, class WS>
-__device__ __forceinline__ void visit_lin(const LinArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const WS& ws) {
+// KT: the link's K, or 0: the descriptor's, passed as kdyn (the weights are then read per tile).  DF_A_PLAIN: A is row-major and
+// complete before the launch.  add2, ldadd2: the second addend of a DF_ADD2_POLLED link (kept out of LinArgs: a launch's
+// arguments are 4 KB at most).
+template <int NW, int KT, int FLAGS, class PC = PaceOff, bool ROW_ONCE = false, class WS>
+__device__ __forceinline__ void visit_lin(const LinArgs& q, const Deal& d, int s, int tiles, int nt, Walk& wk, const WS& ws, int kdyn = 0,
+                                          const SPtr& add2 = SPtr{nullptr, 0}, int ldadd2 = 0) {
   if (nt == 0 || s < d.s_begin || s >= d.s_end) return;
-  constexpr bool sum3 = (FLAGS & DF_A_SUM3) != 0;
+  static_assert(KT != 0 || !WS::resident, "resident weights hold a K fixed at compile time");
+  const int K = KT != 0 ? KT : kdyn;
+  constexpr bool sum3 = (FLAGS & DF_A_SUM3) != 0, a_polled = (FLAGS & DF_A_PLAIN) == 0;
   wk.at(d, s, (FLAGS & DF_GENTLE) != 0);
   const float* A = q.a.at(s);
   const float* A2 = sum3 ? q.a2.at(s) : nullptr;
   const float* A3 = sum3 ? q.a3.at(s) : nullptr;
   auto late = [&]() {
     return LinLate{q.bias, q.add.at(s), q.gate.at(s), q.ld1, q.ld2, (FLAGS & DF_ADD_POLLED) != 0, (FLAGS & DF_RELU) != 0, q.slope,
-                   Out{q.orm.at(s), q.ld3, (FLAGS & DF_RM_SC1) != 0, q.o16.at(s), q.n16, q.o16b.at(s), q.n16b}};
+                   Out{q.orm.at(s), q.ld3, (FLAGS & DF_RM_SC1) != 0, q.o16.at(s), q.n16, q.o16b.at(s), q.n16b},
+                   (FLAGS & DF_ADD_EARLY) != 0, (FLAGS & DF_ADD2_POLLED) != 0 ? add2.at(s) : nullptr, ldadd2};
   };
   int seen_r0 = -1;  // (wave-uniform, as tr0: the branch around the canary's barrier is uniform)
   for (int tk = 0; tk < (WS::resident ? 1 : nt); ++tk) {
     const int trc = __builtin_amdgcn_readlane(tiles, tk), tr0 = trc & 0xffff, tc0 = (trc >> 16) * 16;
-    if constexpr ((FLAGS & DF_CANARY) != 0) {
+    if constexpr ((FLAGS & DF_CANARY) != 0 && a_polled) {
       if (!ROW_ONCE || tr0 != seen_r0) canary_wait(A, tr0, K, wk.pl, q.ld0);
       seen_r0 = tr0;
     }
     ANAT(anat_arm(wk.pl);)
-    tile_lin_late<NW, OP_F32>(A, q.ld0, true, q.W, K, late, tr0, tc0, wk.B, wk.red(), wk.pl, A2, A3, q.w_width, ws, PC());
+    tile_lin_late<NW, OP_F32>(A, q.ld0, a_polled, q.W, K, late, tr0, tc0, wk.B, wk.red(), wk.pl, A2, A3, q.w_width, ws, PC());
     ANAT(anat_note(wk.anat, 4 * d.idx, wk.pl);)
   }
 }
@@ -539,19 +548,26 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_fwd_kernel(FwdArgs a) 
 
 // Backward program (vrnn.hip vrnn_seq_bwd_impl, split3 form): 0 GRU backward (steps 0 .. T'), 1 .. 3 the K = 3R dphi product as
 // three K = R partial-sum links (prior half | posterior half | spare range), 4 GB (gentle, K = 3R), 5 the summing link, 6 phi_z
-// run of two, 7 dz, 8 prior run (K = 2Z, H, H), 9 posterior run.
+// run of two, 7 dz, 8 prior run (K = 2Z, H, H), 9 posterior run; with the decoder leader (nbdec = 3, vrnn_static.h) 10 .. 12 the
+// decoder MLP's three data-gradient links on the spare range.
 struct BwdArgs {
   GrubArgs grub;
   LinArgs part[3], gb, sum;
   SeqArgs phi;
   DzArgs dz;
   SeqArgs run[2];
-  Deal deal[10];
+  LinArgs bdec[3];
+  Deal deal[kBwdDecDesc];
+  int nbdec;  // 0 | 3: the decoder leader on the spare range
+  int bdec_k, gb_ldadd2;  // K of bdec[0] (the decoder's output width); GB's second addend, the h part of the decoder's gradient
+  SPtr gb_add2;
   int B, s0, S, xcd, place;  // place: vrnn_static.h Place
   Ctl ctl;
   ArmTable arm;  // look-ahead arming by the spare range (n = 0: off)
   ANAT(unsigned long long* prof;)
 };
+
+static_assert(sizeof(BwdArgs) <= 4096 && sizeof(FwdArgs) <= 4096, "kernel argument size");
 
 // a workgroup of the prior (HALF 0) or posterior (1) half: its half's partial sum and run of three and whatever tile of the GRU
 // backward, the summing link, the phi_z run and dz the deal gives it, all on resident weights
@@ -587,6 +603,52 @@ __device__ __forceinline__ void bwd_half(const BwdArgs& a, int w, int rt, bool x
   ANAT(anat_end(wk.anat, kargs<BwdArgs>().prof, 2 + HALF, w == kargs<BwdArgs>().deal[1 + HALF].wg0);)
 }
 
+// a workgroup of the spare range with the decoder leader (vrnn_static.h): per walk step its partial-sum tile, which is on the chain
+// and now takes the phi part of the decoder's gradient as its addend (stored kBdecAhead steps ago: requested under the operand wait),
+// then the decoder's three data-gradient links of the time step kBdecAhead walk steps ahead (their descriptors' pointers start
+// there: the interpreter walks the same descriptors in the same order), then the sentinels of step s + kArmAhead.
+// (the flags of GB, of the third partial sum under the leader, and of the leader's links: the converter checks the program against them)
+constexpr int kGbFlags = DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | DF_CANARY;
+constexpr int kPartLeadFlags = DF_ADD_POLLED | DF_ADD_EARLY;
+constexpr int kBdec0Flags = DF_A_PLAIN | DF_GENTLE, kBdec1Flags = DF_GENTLE | DF_CANARY, kBdec2Flags = DF_RM_SC1 | DF_GENTLE | DF_CANARY;
+template <int NW>
+__device__ __forceinline__ void bwd_spare_leader(const BwdArgs& a, int w, int rt, bool xcd, Walk& wk) {
+  const int t = tile_lanes(w, a.deal[3].wg0, a.deal[3].nwg, rt, a.deal[3].ct, xcd), n = tile_count(t);
+  const int t10 = tile_lanes(w, a.deal[10].wg0, a.deal[10].nwg, rt, a.deal[10].ct, xcd), n10 = tile_count(t10);
+  const int t11 = tile_lanes(w, a.deal[11].wg0, a.deal[11].nwg, rt, a.deal[11].ct, xcd), n11 = tile_count(t11);
+  const int t12 = tile_lanes(w, a.deal[12].wg0, a.deal[12].nwg, rt, a.deal[12].ct, xcd), n12 = tile_count(t12);
+  if ((n | n10 | n11 | n12) == 0) return;
+  Res<kR> part;
+  Res<kH> w2;
+  load_lin<NW, kR>(part, kargs<BwdArgs>().part[2].W, kargs<BwdArgs>().part[2].w_width, t, n);
+  load_lin<NW, kH>(w2, kargs<BwdArgs>().bdec[1].W, kH, t11, n11);
+  const Armer armer = arm_rank_dev(w, a.deal[3], a.deal[3].wg0, a.deal[3].nwg, rt, xcd, t, n, a.arm.n);
+#ifdef PCHAIN_TPROF
+  unsigned long long lead = 0, arming = 0;
+  const unsigned long long tb = wall_clock64();
+#endif
+  for (int s = a.s0; s < a.S; ++s) {
+    visit_lin<NW, kR, kPartLeadFlags>(kargs<BwdArgs>().part[2], kargs<BwdArgs>().deal[3], s, t, n, wk, part);
+    ANAT(const unsigned long long t0 = wall_clock64();)
+    visit_lin<NW, 0, kBdec0Flags>(kargs<BwdArgs>().bdec[0], kargs<BwdArgs>().deal[10], s, t10, n10, wk, WMem(), kargs<BwdArgs>().bdec_k);
+    visit_lin<NW, kH, kBdec1Flags>(kargs<BwdArgs>().bdec[1], kargs<BwdArgs>().deal[11], s, t11, n11, wk, w2);
+    visit_lin<NW, kH, kBdec2Flags, PaceOff, true>(kargs<BwdArgs>().bdec[2], kargs<BwdArgs>().deal[12], s, t12, n12, wk, WMem());
+    ANAT(const unsigned long long t1 = wall_clock64();)
+    arm_ahead<NW>(kargs<BwdArgs>().arm, s + kArmAhead, rt, armer);
+    ANAT(const unsigned long long t2 = wall_clock64(); lead += t1 - t0; arming += t2 - t1;)
+  }
+#ifdef PCHAIN_TPROF
+  // slot 13 of the role's table: {walk steps, -, ticks in the leader's links, ticks in the arming stores}; slot 14: {1, -, ticks of the whole loop, -}
+  const unsigned long long whole = wall_clock64() - tb;
+  if (threadIdx.x == 0) {
+    unsigned* q = wk.anat + 13 * 2 * 4;
+    q[0] = (unsigned)(a.S - a.s0); q[2] = (unsigned)lead; q[3] = (unsigned)arming;
+    q[8] = 1u; q[10] = (unsigned)whole;
+  }
+  anat_end(wk.anat, kargs<BwdArgs>().prof, 4, w == kargs<BwdArgs>().deal[3].wg0);
+#endif
+}
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds_red[];
@@ -594,6 +656,10 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) 
   const bool xcd = a.place == kPlaceProgram && a.xcd != 0;
   Walk wk{lds_red, lds_red + kBwdProducts * NW * 256, 0, a.B, Poll{a.ctl, 0u, false, 1}};
   ANAT(__shared__ unsigned anat[kAnatSlots * 8]; anat_begin(anat); wk.anat = anat;)
+  if (a.nbdec != 0 && w >= a.deal[3].wg0) {
+    bwd_spare_leader<NW>(a, w, rt, xcd, wk);
+    return;
+  }
   if (w >= a.deal[3].wg0) {  // spare range: the third partial sum alone
     const int t = tile_lanes(w, a.deal[3].wg0, a.deal[3].nwg, rt, a.deal[3].ct, xcd), n = tile_count(t);
     if (n == 0) return;
@@ -610,8 +676,14 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) 
   if (w >= a.deal[4].wg0) {  // gentle range: GB alone
     const int t = tile_lanes(w, a.deal[4].wg0, a.deal[4].nwg, rt, a.deal[4].ct, xcd), n = tile_count(t);
     if (n == 0) return;
+    if (a.nbdec != 0) {  // (with the leader: the h part of the decoder's gradient is GB's second polled addend)
+      for (int s = a.s0; s < a.S; ++s)
+        visit_lin<NW, 3 * kR, kGbFlags | DF_ADD2_POLLED>(kargs<BwdArgs>().gb, kargs<BwdArgs>().deal[4], s, t, n, wk, WMem(), 0, kargs<BwdArgs>().gb_add2,
+                                                         kargs<BwdArgs>().gb_ldadd2);
+      return;
+    }
     for (int s = a.s0; s < a.S; ++s)
-      visit_lin<NW, 3 * kR, DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | DF_CANARY>(kargs<BwdArgs>().gb, kargs<BwdArgs>().deal[4], s, t, n, wk, WMem());
+      visit_lin<NW, 3 * kR, kGbFlags>(kargs<BwdArgs>().gb, kargs<BwdArgs>().deal[4], s, t, n, wk, WMem());
     return;
   }
   if (w < a.deal[2].wg0) bwd_half<NW, 0>(a, w, rt, xcd, wk);
@@ -821,13 +893,14 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream, const ArmPlan& plan, c
 
 int vrnn_static_bwd(const Program& p, hipStream_t stream, const ArmPlan& plan, const std::function<int()>& pre) {
   int place = kPlaceProgram;
-  if (vrnn_static_check(p, 10, kBwdProducts, 8, 9, &place)) return 1;
+  const bool lead = p.ndesc == kBwdDecDesc;  // with the decoder leader on the spare range
+  if (vrnn_static_check(p, lead ? kBwdDecDesc : kBwdDesc, kBwdProducts, 8, 9, &place)) return 1;
   const Desc* d = p.d;
   const int S = p.S;  // T' + 1
-  for (int i = 0; i < 10; ++i)
+  for (int i = 0; i < kBwdDesc; ++i)
     if (d[i].s_begin != 0 || d[i].s_end != (i == 0 ? S : S - 1)) return 1;
-  if (!shaped(d[0], K_GRUB, 0, kH) || !shaped(d[1], K_LIN, 0, kR) || !shaped(d[2], K_LIN, 0, kR) || !shaped(d[3], K_LIN, 0, kR) ||
-      !shaped(d[4], K_LIN, DF_ADD_POLLED | DF_RM_SC1 | DF_GENTLE | DF_CANARY, 3 * kR) || !shaped(d[5], K_LIN, DF_A_SUM3, kH) ||
+  if (!shaped(d[0], K_GRUB, 0, kH) || !shaped(d[1], K_LIN, 0, kR) || !shaped(d[2], K_LIN, 0, kR) || !shaped(d[3], K_LIN, lead ? kPartLeadFlags : 0, kR) ||
+      !shaped(d[4], K_LIN, lead ? kGbFlags | DF_ADD2_POLLED : kGbFlags, 3 * kR) || !shaped(d[5], K_LIN, DF_A_SUM3, kH) ||
       !shaped(d[6], K_LINSEQ, DF_SEQ_GATE, kH) || !shaped(d[7], K_DZ, 0, kH) || !shaped(d[8], K_LINSEQ, DF_SEQ_GATE, kH) ||
       !shaped(d[9], K_LINSEQ, DF_SEQ_GATE, kH))
     return 1;
@@ -840,6 +913,18 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream, const ArmPlan& plan, c
     return 1;
   for (int i : {0, 5, 6, 7})
     if (!within(d[i], 0, gentle)) return 1;
+  if (lead) {
+    // the leader's links: on the range of the third partial sum, active while there is a time step kBdecAhead walk steps ahead; the
+    // first reads its row-major operand as it is (K: the descriptor's), the second is resident on one tile per workgroup
+    for (int i = kBwdDesc; i < kBwdDecDesc; ++i) {
+      if (d[i].s_begin != 0 || d[i].s_end != S - 1 - kBdecAhead || d[i].wg0 != spare || d[i].nwg != d[3].nwg) return 1;
+      if (d[i].p[LIN_A2] || d[i].p[LIN_A3] || d[i].p[LIN_O16B] || d[i].p[LIN_ADD] || d[i].p[LIN_ADD2] || d[i].p[LIN_BIAS] || d[i].i[LIN_I_W_WIDTH] != 0) return 1;
+    }
+    if (d[10].kind != K_LIN || d[10].flags != kBdec0Flags || d[10].K <= 0 || d[10].K % 16 != 0 || d[10].ld[LIN_LD_A] != d[10].K) return 1;
+    if (!shaped(d[11], K_LIN, kBdec1Flags, kH) || !shaped(d[12], K_LIN, kBdec2Flags, kH) || d[11].ld[LIN_LD_A] != 0 || d[12].ld[LIN_LD_A] != 0) return 1;
+    if (!one_tile_each(p, kBwdDecResident, place_xcd(place, p))) return 1;
+    if (d[3].p[LIN_ADD] == nullptr || d[4].p[LIN_ADD2] == nullptr || d[1].p[LIN_ADD] != nullptr || d[0].p[GRUB_DD] != nullptr) return 1;
+  }
   BwdArgs a{};
   const Desc& g = d[0];
   a.grub = GrubArgs{sp(p, g, GRUB_D0_16), sp(p, g, GRUB_D1_16), sp(p, g, GRUB_G_IN), sp(p, g, GRUB_RG), sp(p, g, GRUB_UG), sp(p, g, GRUB_NG), sp(p, g, GRUB_GH),
@@ -855,8 +940,11 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream, const ArmPlan& plan, c
                 sp(p, z, DZ_DPH16), z.p[DZ_WT], z.p[DZ_C_RAW], z.p[DZ_C_FN], reinterpret_cast<const int32_t*>(z.p[DZ_X_SL]), z.ld[DZ_LD_ADD],
                 z.ld[LD_OUT], z.n16[N16_OUT], z.i[DZ_I_Z], z.i[DZ_I_RESIDUAL], z.i[DZ_I_STRIDE], z.i[DZ_I_T0], (int)z.f[DZ_F_GEMM_FROM], z.f[DZ_F_FN_FLOOR],
                 z.f[DZ_F_BETA], z.f[DZ_F_SD_EPS]};
+  a.nbdec = lead ? 3 : 0;
+  if (lead) { a.bdec_k = d[kBwdDesc].K; a.gb_add2 = sp(p, d[4], LIN_ADD2); a.gb_ldadd2 = d[4].i[LIN_I_LD_ADD2]; }
+  for (int k = 0; k < a.nbdec; ++k) a.bdec[k] = lin_args(p, d[kBwdDesc + k]);
   int grid = 0;
-  for (int i = 0; i < 10; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
+  for (int i = 0; i < p.ndesc; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.place = place; a.ctl = p.ctl;
   ANAT(a.prof = pchain_profile_buffer();)
   // the spare range's workgroups arm around their partial-sum tiles (descriptor 3)

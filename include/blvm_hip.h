@@ -452,6 +452,29 @@ int blvm_vrnn_seq_bwd(const BlvmVrnnWeights* w, const float* enc, const float* e
                       int residual_posterior, float sd_eps, float* d_enc, float* d_h0, const BlvmVrnnGrads* grads,
                       float* workspace, void* stream);
 
+/* The same backward with the decoder MLP's data gradients handed down (the mirror image of blvm_vrnn_seq_fwd_dec): where the backward
+ * launch has a spare range (the conditions of the forward fold and in addition H == 256, R == 512, the split3 program on its own-range
+ * deal, Tp >= 4) the three products dY2 = gate(dZ3 Wd3), dY1 = gate(dY2 Wd2), d_decin = dY1 Wd1 run inside the persistent launch,
+ * a fixed number of steps ahead of the chain, and *folded = 1.  Otherwise *folded = 0 and NOTHING has been done: the caller runs the
+ * decoder's data gradients itself (K6) and calls blvm_vrnn_seq_bwd.  There is no d_decin argument: a gradient that reaches decin from
+ * anywhere but the decoder is the caller's reason to take that path.
+ *   dz3 [Tp*B,SF]: gradient of the decoder's last PRE-activation (what blvm_dmol_bwd_fused returns with act_slope >= 0);
+ *   dec_y1, dec_y2 [Tp*B,DH]: the decoder's hidden activations; dec_w: host array of the three weight pointers (as for the forward);
+ *   dy2, dy1 [Tp*B,DH] (out): gradients of the hidden pre-activations, every row written; the decoder's weight gradients are the
+ *   caller's (dW3 = dz3^T y2, dW2 = dy2^T y1, dW1 = dy1^T decin).
+ *   workspace: blvm_vrnn_bwd_dec_workspace_floats(..., DH, SF) floats, asked for under the same blvm_vrnn_dec_bwd_fold mode.
+ * blvm_vrnn_dec_bwd_fold(mode): 0 never folds, 1 (default; env BLVM_VRNN_DEC_BWD_FOLD) folds where it applies, negative only queries;
+ * returns the mode in effect before the call, mode -2 instead the number of backward calls that folded so far. */
+size_t blvm_vrnn_bwd_dec_workspace_floats(int Tp, int B, int X, int H, int Z, int R, int DH, int SF);
+int blvm_vrnn_seq_bwd_dec(const BlvmVrnnWeights* w, const float* enc, const float* eps, const float* decin,
+                          const float* mu_q, const float* sd_q, const float* mu_p, const float* sd_p, const float* z,
+                          const float* reserve, const int32_t* x_sl, const float* c_raw, const float* c_fn, int stride,
+                          float fn_floor, int Tp, int B, int X, int H, int Z, int R, int residual_posterior, float sd_eps,
+                          float* d_enc, float* d_h0, const BlvmVrnnGrads* grads, float* workspace, const float* dz3,
+                          const float* dec_y1, const float* dec_y2, const float* const* dec_w, float* dy2, float* dy1, int DH,
+                          int SF, float slope, int* folded, void* stream);
+int blvm_vrnn_dec_bwd_fold(int mode);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * K4  single-layer LSTM over a sequence (forward + BPTT).  Replaces `nn.LSTM` on a packed sequence,
  *     `blvm/models/lstm.py:46-55,96-98` (pack_padded_sequence / pad_packed_sequence semantics through `lens`:
