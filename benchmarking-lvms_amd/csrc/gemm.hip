@@ -484,7 +484,18 @@ struct GemmGroup {
 // (amdgpu_waves_per_eu(2): the ring's 64 KiB allow two workgroups per CU; without the hint hipcc interleaves the four tiles' stage
 // sums and takes 234 VGPRs + 64 AGPRs, one workgroup per CU.  With it the sliced body takes 248 of the 256 registers two workgroups
 // allow: no headroom, one more live value spills or halves the occupancy)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void wgrad_group_kernel(GemmGroup gg) {
+// WGRAD_SCALAR_ADDS: the two sliced kernels are compiled without packed fp32 VALU, so that `acc[i][j] += part` is 16 v_add_f32 per
+// tile and not 8 v_pk_add_f32, the form the backend gives a vector add by default: beside MFMAs a packed add costs the issue port
+// several plain ones.  Same add, same order, same bits; still 248 VGPRs, no scratch, two workgroups per CU, and no v_pk_add_f32
+// left in either kernel.  Measured (tools/wgrad_tile_bench.py groups, MI355X, packed -> scalar, three alternated rounds): the VRNN
+// chain group 614 .. 627 -> 551 .. 561 us, the decoder group 166 .. 172 -> 162 .. 163 us.  The attribute sits on the kernels whose
+// whole body is that loop; every other kernel of the file keeps the packed forms.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WGRAD_SCALAR_ADDS __attribute__((target("no-packed-fp32-ops")))
+#else
+#define WGRAD_SCALAR_ADDS  // (the host pass knows no such feature)
+#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) WGRAD_SCALAR_ADDS void wgrad_group_kernel(GemmGroup gg) {
   const int item = blockIdx.x;
   int p = 0;
   while (p + 1 < gg.n && item >= gg.first[p + 1]) ++p;
@@ -507,7 +518,7 @@ __global__ __launch_bounds__(256) void gemm_group_kernel(GemmGroup gg) {
   gemm_tile<64, 64, 1, 1>(g, t % tiles_n, t / tiles_n, bz, gg.split);
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void wgrad_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) WGRAD_SCALAR_ADDS void wgrad_kernel(GemmArgs g) {
   wgrad_tile<true>(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z);
 }
 __global__ __launch_bounds__(256) void wgrad_exact_kernel(GemmArgs g) {  // unsplit requests of gemm_f32
@@ -782,7 +793,10 @@ int wgrad_k_per_split(int K, int split) {
 // The sliced body is the faster one wherever both were measured (tools/wgrad_tile_bench.py on MI355X, us, exact -> sliced): the VRNN
 // chain group 704 -> 624 (ragged rows 705 -> 629), a 256 x 512 + 2 x 256 x 256 group 85.1 -> 76.2, 1536 x 512 x 16000 215 -> 182,
 // 384 x 192 x 49152 88.8 -> 77.3, 256 x 256 x 64000 83.0 -> 72.4, 768 x 192 x 393216 1194 -> 1061.  Only a request for NO split keeps
-// the exact body: it asks for a reproducible result, the 64 x 64 tile's bits.
+// the exact body: it asks for a reproducible result, the 64 x 64 tile's bits.  (Those figures are with packed accumulator adds; with
+// WGRAD_SCALAR_ADDS the sliced body gives: chain group 551 .. 561, ragged rows 566 .. 573, the decoder's 3-job group 162 .. 164,
+// 1536 x 512 x 16000 168, 256 x 256 x 64000 74.  A second sliced body on 64 x 128 wave tiles, one workgroup per CU, was built and
+// measured slower at all of these -- chain group 630 .. 641, 1536 x 512 x 16000 179 .. 188 -- and is not here: DESIGN.md §0.)
 
 }  // namespace
 

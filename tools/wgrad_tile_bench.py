@@ -3,17 +3,24 @@ tree this file sits in, on the shapes the models run.
 
   * the VRNN chain's weight gradients (vrnn.hip, the grouped launch of the batched part; X = H = Z = 256, R = 512 at the headline
     configuration, rows = 16 000) one by one and as ONE grouped launch (blvm_wgrad_group_f32), with their bias gradients;
+  * the VRNN decoder's three weight gradients (768 -> 256 -> 256 -> 1920) as the grouped launch the MLP's backward hands over;
   * MLP-like groups (three layers, as ops.py's _MLPFunction backward hands them over);
   * single weight-gradient GEMMs through blvm_gemm_f32 (op_a = op_b = 1) at the CW-VAE / STCN / VRNN shapes.
 
-Run it in the old and in the new tree on one box to compare.  Prints one line per case: microseconds and TF/s."""
+Run it in the old and in the new tree on one box to compare (BLVM_HIP_LIB=<other library> times another build of the library under
+this tree's Python, as long as both export the same entry points).  Prints one line per case: microseconds and TF/s.
+
+  (no argument)   every case once
+  chain           the chain group alone, full and ragged row counts interleaved (for counters / A-B)
+  groups          chain group, decoder group and the single shapes 1536 x 512 x 16000 and 256 x 256 x 64000, three rounds (A-B of two
+                  libraries: one process each, alternated by the caller)"""
 import os
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "benchmarking-lvms_amd"))
-from blvm import ops  # noqa: E402
+from blvm import _hip, ops  # noqa: E402
 
 dev = "cuda:0"
 ROWS = int(os.environ.get("ROWS", 16000))
@@ -30,6 +37,12 @@ def chain_jobs():
     j += [(H, H, True)] * 4
     j += [(H, R, True), (H, R, False), (H, X, True)]
     return j
+
+
+def decoder_jobs():
+    """(M, N, bias) of the headline decoder's weight gradients: Linear(H + R, H), Linear(H, H), Linear(H, 1920) (the DMoL head of a
+    64-sample frame stack with 10 mixture components)."""
+    return [(H, H + R, True), (H, H, True), (1920, H, True)]
 
 
 def timed(f):
@@ -66,6 +79,7 @@ def single_case(M, N, K):
     sk = max(1, min((768 + tiles - 1) // tiles, (K + 255) // 256))  # the callers' request (common.h gemm_pick_split)
     us = timed(lambda: ops.gemm(1, 1, M, N, K, D, M, A, N, C, N, accumulate=True, split_k=sk))
     print(f"gemm_f32 (1,1) M={M:5d} N={N:4d} K={K:6d}       {us:8.1f} us  {2 * M * N * K / us / 1e6:6.1f} TF/s", flush=True)
+    return us
 
 
 def main():
@@ -74,6 +88,14 @@ def main():
             group_case("chain group (one launch)", chain_jobs(), ROWS)
             group_case("chain group, ragged rows", chain_jobs(), ROWS - 5)
         return
+    if sys.argv[1:] == ["groups"]:
+        print(f"library: {os.path.basename(_hip.lib_path())}")
+        for _ in range(3):
+            group_case("chain group (one launch)", chain_jobs(), ROWS)
+            group_case("decoder group (one launch)", decoder_jobs(), ROWS)
+            single_case(1536, 512, 16000)
+            single_case(256, 256, 64000)
+        return
     print(f"tree: {os.path.dirname(os.path.abspath(__file__))}/..  device: {torch.cuda.get_device_name(0)}")
     total = 0.0
     for i, (M, N, bias) in enumerate(chain_jobs()):
@@ -81,6 +103,7 @@ def main():
     print(f"chain jobs one by one: {total:.1f} us in all")
     group_case("chain group (one launch)", chain_jobs(), ROWS)
     group_case("chain group, ragged rows", chain_jobs(), ROWS - 5)
+    group_case("decoder group (one launch)", decoder_jobs(), ROWS)
     group_case("encoder-like MLP group", [(256, 64, True), (256, 256, True), (256, 256, True)], ROWS)
     group_case("decoder-like MLP group", [(256, 512, True), (256, 256, True), (256, 256, True)], ROWS)
     for M, N, K in [(256, 256, 16000), (768, 256, 16000), (1536, 512, 16000), (768, 192, 393216), (192, 192, 98304),
