@@ -276,7 +276,7 @@ class STCN(BaseModel):
                 and len(self.res_stack.dilations) <= 64 and self.n_layers <= 64)  # fmt: skip
 
     def _one_launch_parts(self):
-        """The weight arguments of `ops.stcn_generate` / `ops.stcn_generate_pack`, up to and including `dense`."""
+        """The `weights` argument of `ops.stcn_generate` / `ops.stcn_generate_pack`."""
         rs, ot, up, lik, n = self.res_stack, self.out_transform, self.out_upsample[0], self.likelihood_module, self.n_latents
         conv1x1 = lambda c: (c.weight.view(c.out_channels, -1), c.bias)  # noqa: E731
         linears = lambda seq: [seq[0], seq[2], seq[4]]  # noqa: E731
@@ -389,7 +389,7 @@ class STCN(BaseModel):
         chunks; eps and uniforms are indexed from 0 for every call, and max_timesteps must then be a multiple of S.  A continued call
         updates the state's rings in place: a state is good for ONE continuation.
 
-        fused=None takes the one-launch kernel (`ops.stcn_generate`, K10d; from a state `ops.stcn_generate_resume`, its rings primed
+        fused=None takes the one-launch kernel (`ops.stcn_generate`, K10d; from a state through its `resume=`, the rings primed
         from the state's windows when it carries none) when it applies: the DMoL head, res_channels and every
         latent size multiples of 16, within the kernel's 160 KB of LDS.  fused=True insists.  fused=False, the GMM and Gaussian heads and
         other widths run step by step on the time-parallel operators over a receptive-field window — an independent second path,
@@ -419,7 +419,6 @@ class STCN(BaseModel):
                 raise ValueError(f"STCN.generate: prompt_eps must hold one [P',{B},z_l] tensor per level, z_l = {self.latent_size}")
             if x is None:
                 raise ValueError("STCN.generate: prompt_eps replays the latent draws over a prompt, and there is none (x is None)")
-        stateful = x is not None or state is not None or return_state
         if (state is not None or return_state) and N % S != 0:
             raise ValueError(f"STCN.generate: with a state, max_timesteps = {N} must be a multiple of n_stack_frames = {S}: a cut output "
                              "would lose samples between chunks")  # fmt: skip
@@ -487,17 +486,14 @@ class STCN(BaseModel):
                 raise BlvmHipError("STCN.generate: the one-launch kernel is built for the DMoL head")
             try:
                 p0 = self.prior[0]
-                args = (*self._one_launch_parts(), B, Tp, S, rs.res_blocks[0].inv_std, self.inv_std, p0.softplus_beta, p0.epsilon,
-                        p0.transform_mu[1].negative_slope, lik.num_mix, lik.log_epsilon, eps, u, v)  # fmt: skip
-                if not stateful:
-                    xs, z, mu, sd = ops.stcn_generate(*args)
-                elif st is None:  # the zero start, keeping its scratch
-                    xs, z, mu, sd, scratch = ops.stcn_generate_start(*args)
-                else:
-                    scratch = st.scratch if st.scratch is not None else self._prime_rings(st, lik.num_mix)
+                resume = None
+                if st is not None:
                     # the kernel takes the phase of step `n_steps` in every ring: any t0 equal to it modulo all dilations
-                    xs, z, mu, sd, _ = ops.stcn_generate_resume(*args, st.n_steps % math.lcm(*rs.dilations),
-                                                                st.x_window[-2:].transpose(0, 1).contiguous(), scratch)  # fmt: skip
+                    resume = (st.n_steps % math.lcm(*rs.dilations), st.x_window[-2:].transpose(0, 1).contiguous(),
+                              st.scratch if st.scratch is not None else self._prime_rings(st, lik.num_mix))  # fmt: skip
+                xs, z, mu, sd, scratch, _ = ops.stcn_generate(self._one_launch_parts(), B, Tp, S, rs.res_blocks[0].inv_std, self.inv_std,
+                                                              p0.softplus_beta, p0.epsilon, p0.transform_mu[1].negative_slope, lik.num_mix,
+                                                              lik.log_epsilon, eps, u, v, resume=resume)  # fmt: skip
                 if return_state:
                     x_old = st.x_window if st is not None else torch.zeros(rf, B, S, **f32)
                     z_old = st.z_window if st is not None else torch.zeros(n_out, B, Zin, **f32)

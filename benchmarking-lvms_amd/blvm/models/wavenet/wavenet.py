@@ -207,8 +207,8 @@ class WaveNet(BaseModel):
         (its class k is fed back and returned as the float `dequantize(k)`).
         `cached=True` (the reference's TODO, arXiv:1611.09482): the same samples from per-block queues of past activations —
         one new frame per block per step instead of the whole window; at the widths the decode kernel takes (K10c: every frame in
-        one launch) through `ops.wavenet_decode` (the DMoL head) or `ops.wavenet_cat_decode` (the categorical head with 16 <= V <=
-        1024 classes, V a multiple of 16), otherwise block by block (`_generate_cached`).
+        one launch) through `ops.wavenet_decode` (the DMoL head, or the categorical head with 16 <= V <= 1024 classes, V a multiple of
+        16), otherwise block by block (`_generate_cached`).
         With `cached=True`, `x` [B,P,1] is a prompt: the queues are primed from its last receptive-field samples (`_prime`) and
         frames P, P+1, ... are drawn.  `return_state=True` returns (x_hat, state); `state=` continues from one (generation in
         chunks; `uniforms` are indexed from 0 for every call)."""
@@ -224,11 +224,8 @@ class WaveNet(BaseModel):
                 if x.size(0) != n_samples:
                     raise ValueError(f"WaveNet.generate: prompt of {x.size(0)} rows for n_samples = {n_samples}")
                 state = self._prime(x)
-            run = self._generate_cached
-            if self._decode_kernel_applies():
-                run = self._generate_decode_kernel
-            elif self._cat_decode_kernel_applies():
-                run = self._generate_cat_decode_kernel
+            one_launch = self._decode_kernel_applies() or self._cat_decode_kernel_applies()
+            run = self._generate_one_launch if one_launch else self._generate_cached
             if state is None and not return_state:
                 return run(n_samples, n_frames, uniforms)
             x_hat, state = run(n_samples, n_frames, uniforms, state=state, want_state=True)
@@ -247,18 +244,22 @@ class WaveNet(BaseModel):
             win = torch.cat([win[1:], pred.reshape(1, n_samples, nsf).to(torch.float32)], 0)
         return torch.hstack(x_hat)
 
+    def _decode_widths_fit(self):
+        """The widths the decode kernel (K10c) takes, whatever the head."""
+        C, blk = self.res_channels, self.res_stack.res_blocks[0]
+        return (self.in_channels == 1 and C % 16 == 0 and blk.skip_channels % 16 == 0 and C <= 128 and blk.skip_channels <= 128
+                and len(self.res_stack.res_blocks) <= 64)  # fmt: skip
+
     def _decode_kernel_applies(self):
-        C, blk, lik = self.res_channels, self.res_stack.res_blocks[0], self.likelihood
-        return (isinstance(lik, DiscretizedLogisticMixtureDense) and lik.y_dim == 1 and lik.out_features <= 32 and self.in_channels == 1
-                and C % 16 == 0 and blk.skip_channels % 16 == 0 and C <= 128 and blk.skip_channels <= 128 and len(self.res_stack.res_blocks) <= 64)  # fmt: skip
+        lik = self.likelihood
+        return isinstance(lik, DiscretizedLogisticMixtureDense) and lik.y_dim == 1 and lik.out_features <= 32 and self._decode_widths_fit()
 
     def _cat_decode_kernel_applies(self):
         """The decode kernel's categorical head: 16 <= V <= 1024 in multiples of 16 (a larger softmax wants its head Linear split
         across workgroups: block by block, `_generate_cached`), the widths of `_decode_kernel_applies`."""
-        C, blk, lik = self.res_channels, self.res_stack.res_blocks[0], self.likelihood
-        return (isinstance(lik, CategoricalDense) and 16 <= lik.y_dim <= 1024 and lik.y_dim % 16 == 0 and self.in_channels == 1
-                and self.n_stack_frames == 1 and C % 16 == 0 and blk.skip_channels % 16 == 0 and C <= 128 and blk.skip_channels <= 128
-                and len(self.res_stack.res_blocks) <= 64)  # fmt: skip
+        lik = self.likelihood
+        return (isinstance(lik, CategoricalDense) and 16 <= lik.y_dim <= 1024 and lik.y_dim % 16 == 0 and self.n_stack_frames == 1
+                and self._decode_widths_fit())  # fmt: skip
 
     @torch.no_grad()
     def _prime(self, x):
@@ -281,60 +282,57 @@ class WaveNet(BaseModel):
         ops.wavenet_prime_rings(h0, [b.kernel_params() for b in rs.res_blocks], rs.dilations, blk.inv_std, blk.skip_channels, P, rings)
         return WaveNetDecodeState(scratch, rings, win[:, -2:].contiguous(), P)
 
-    @torch.no_grad()
-    def _generate_decode_kernel(self, n_samples: int, n_frames: int, uniforms=None, state=None, want_state: bool = False):
-        lik, rs, B = self.likelihood, self.res_stack, n_samples
-        dev = self.causal.conv.weight.device
+    def _one_launch_parts(self):
+        """The `weights` argument of `ops.wavenet_decode`; the head Linear is the DMoL head's `params`, the categorical head's `logits`."""
+        rs, lik = self.res_stack, self.likelihood
+        t_in = rs.in_transform
+        head = lik.logits if isinstance(lik, CategoricalDense) else lik.params
+        return ((self.causal.conv.weight, self.causal.conv.bias), (t_in.weight.view(t_in.out_channels, -1), t_in.bias),
+                [b.kernel_params() for b in rs.res_blocks], rs.dilations,
+                (self.out_transform.linear.weight, self.out_transform.linear.bias), (head.weight, head.bias))  # fmt: skip
+
+    def _one_launch_head(self, B: int, n_frames: int, uniforms):
+        """-> (the `head` argument of `ops.wavenet_decode`, its draws).  Categorical: `uniforms[t]` [B] is the head's one draw of frame
+        t (None: torch.rand on the device); class k comes back as `likelihood.levels[k]`, the float `dequantize(k)` returns."""
+        lik, dev = self.likelihood, self.causal.conv.weight.device
+        if isinstance(lik, CategoricalDense):
+            if uniforms is None:
+                u = torch.rand(n_frames, B, device=dev)
+            else:
+                u = torch.stack([a.reshape(B) for a in uniforms[:n_frames]]).to(device=dev, dtype=torch.float32)
+            return ops.CategoricalHead(lik.levels), u
         if uniforms is None:
             u = torch.empty(n_frames, B, lik.num_mix, device=dev).uniform_(1e-5, 1.0 - 1e-5)  # the reference's two draws (variational.py:309-349)
             v = torch.empty(n_frames, B, device=dev).uniform_(1e-8, 1.0 - 1e-8)
         else:
             u = torch.stack([a.reshape(B, lik.num_mix) for a, _ in uniforms[:n_frames]]).to(dev)
             v = torch.stack([b.reshape(B) for _, b in uniforms[:n_frames]]).to(dev)
-        t_in, blk = rs.in_transform, rs.res_blocks[0]
-        args = ((self.causal.conv.weight, self.causal.conv.bias), (t_in.weight.view(t_in.out_channels, -1), t_in.bias),
-                [b.kernel_params() for b in rs.res_blocks], rs.dilations,
-                (self.out_transform.linear.weight, self.out_transform.linear.bias), (lik.params.weight, lik.params.bias),
-                B, n_frames, blk.inv_std, 1.0 / self.variance_scale, lik.num_mix, lik.log_epsilon, u, v)  # fmt: skip
-        if state is None and not want_state:
-            return ops.wavenet_decode(*args).unsqueeze(-1)
-        if state is None:  # the zero start, keeping its scratch: the samples in front of frame 0 are zeros
-            x, scratch = ops.wavenet_decode_start(*args)
-            samples = torch.cat([torch.zeros(B, 2, device=dev), x], 1)[:, -2:].contiguous()
-            state = WaveNetDecodeState(scratch, ops.wavenet_ring_views(scratch, rs.dilations, B, self.res_channels, blk.skip_channels), samples, n_frames)
-            return x.unsqueeze(-1), state
-        if state.scratch is None or tuple(state.samples.shape) != (B, 2):
-            raise ValueError("WaveNet.generate: the state does not come from the decode kernel's path at this batch size")
-        # the kernel takes the phase of frame `state.n_frames` in every ring: any t0 equal to it modulo all dilations
-        x, samples = ops.wavenet_decode_resume(*args, state.n_frames % math.lcm(*rs.dilations), state.samples, state.scratch)
-        return x.unsqueeze(-1), WaveNetDecodeState(state.scratch, state.rings, samples, state.n_frames + n_frames)
+        return ops.DmolHead(lik.num_mix, lik.log_epsilon), (u, v)
 
     @torch.no_grad()
-    def _generate_cat_decode_kernel(self, n_samples: int, n_frames: int, uniforms=None, state=None, want_state: bool = False):
-        """The decode kernel with the categorical head: `uniforms[t]` [B] is the head's one draw of frame t (None: torch.rand on the
-        device); class k comes back as `likelihood.levels[k]`, the float `dequantize(k)` returns.  States as `_generate_decode_kernel`."""
-        lik, rs, B = self.likelihood, self.res_stack, n_samples
-        dev = self.causal.conv.weight.device
-        if uniforms is None:
-            u = torch.rand(n_frames, B, device=dev)
-        else:
-            u = torch.stack([a.reshape(B) for a in uniforms[:n_frames]]).to(device=dev, dtype=torch.float32)
-        t_in, blk = rs.in_transform, rs.res_blocks[0]
-        args = ((self.causal.conv.weight, self.causal.conv.bias), (t_in.weight.view(t_in.out_channels, -1), t_in.bias),
-                [b.kernel_params() for b in rs.res_blocks], rs.dilations,
-                (self.out_transform.linear.weight, self.out_transform.linear.bias), (lik.logits.weight, lik.logits.bias), lik.levels,
-                B, n_frames, blk.inv_std, 1.0 / self.variance_scale, u)  # fmt: skip
-        if state is None and not want_state:
-            return ops.wavenet_cat_decode(*args)[0].unsqueeze(-1)
+    def _generate_one_launch(self, n_samples: int, n_frames: int, uniforms=None, state=None, want_state: bool = False):
+        """The decode kernel (K10c), either head: every frame in one launch, from the zero start or from `state` (a prompt's, `_prime`,
+        or an earlier call's, whose scratch buffer is updated in place); `want_state` returns (x_hat, state)."""
+        rs, B = self.res_stack, n_samples
+        blk = rs.res_blocks[0]
+        head, draws = self._one_launch_head(B, n_frames, uniforms)
+        resume = None
+        if state is not None:
+            if state.scratch is None or tuple(state.samples.shape) != (B, 2):
+                raise ValueError("WaveNet.generate: the state does not come from the decode kernel's path at this batch size")
+            # the kernel takes the phase of frame `state.n_frames` in every ring: any t0 equal to it modulo all dilations
+            resume = (state.n_frames % math.lcm(*rs.dilations), state.samples, state.scratch)
+        out = ops.wavenet_decode(self._one_launch_parts(), head, B, n_frames, blk.inv_std, 1.0 / self.variance_scale, draws=draws,
+                                 resume=resume)  # fmt: skip
+        x_hat = out.x.unsqueeze(-1)
+        if not want_state:
+            return x_hat
         if state is None:  # the zero start, keeping its scratch: the samples in front of frame 0 are zeros
-            x, _, scratch = ops.wavenet_cat_decode_start(*args)
-            samples = torch.cat([torch.zeros(B, 2, device=dev), x], 1)[:, -2:].contiguous()
-            state = WaveNetDecodeState(scratch, ops.wavenet_ring_views(scratch, rs.dilations, B, self.res_channels, blk.skip_channels), samples, n_frames)
-            return x.unsqueeze(-1), state
-        if state.scratch is None or tuple(state.samples.shape) != (B, 2):
-            raise ValueError("WaveNet.generate: the state does not come from the decode kernel's path at this batch size")
-        x, _, samples = ops.wavenet_cat_decode_resume(*args, state.n_frames % math.lcm(*rs.dilations), state.samples, state.scratch)
-        return x.unsqueeze(-1), WaveNetDecodeState(state.scratch, state.rings, samples, state.n_frames + n_frames)
+            samples = torch.cat([torch.zeros(B, 2, device=out.x.device), out.x], 1)[:, -2:].contiguous()
+            rings, before = ops.wavenet_ring_views(out.scratch, rs.dilations, B, self.res_channels, blk.skip_channels), 0
+        else:
+            samples, rings, before = out.samples, state.rings, state.n_frames
+        return x_hat, WaveNetDecodeState(out.scratch, rings, samples, before + n_frames)
 
     @torch.no_grad()
     def _generate_cached(self, n_samples: int, n_frames: int, uniforms=None, state=None, want_state: bool = False):

@@ -5,7 +5,7 @@ hot path, and no CPU fallback (``_hip.ptr`` refuses CPU tensors).
 Layout convention: sequence tensors are time-major ``[T', B, F]``.
 """
 import ctypes
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -1493,62 +1493,114 @@ def wavenet_block_step(x2, params, inv_std: float, S: int, skip_acc, want_output
     return o
 
 
-def _wavenet_decode_pack(causal, in_transform, blocks_params, dilations, out_linear, head_linear, num_mix: int):
-    """The packed weight image of K10c and its sizes: -> (lib, C, S, O, device, packed, dilations as a C array)."""
+class DmolHead(NamedTuple):
+    """K10c's discretised-logistic-mixture head: the head Linear has 3 * num_mix <= 32 rows."""
+
+    num_mix: int
+    log_eps: float
+
+
+class CategoricalHead(NamedTuple):
+    """K10c's softmax head: levels [V] are the class values, the head Linear is [V,O] (16 <= V <= 1024, a multiple of 16)."""
+
+    levels: torch.Tensor
+
+
+class WaveNetDecodeOut(NamedTuple):
+    x: torch.Tensor  # [B,n_frames]
+    k: Optional[torch.Tensor]  # [B,n_frames] int32 classes (the categorical head)
+    scratch: torch.Tensor  # the buffer the call used; with the last two samples its rings (`wavenet_ring_views`) are the state
+    samples: Optional[torch.Tensor]  # [B,2], the last two samples (a resumed call)
+
+
+def _wavenet_decode_pack(weights, head):
+    """The packed weight image of K10c and its sizes: -> (lib, C, S, O, device, packed, dilations as a C array).  The image ends
+    in the head Linear: padded with zeros to 32 rows (`DmolHead`), as it stands (`CategoricalHead`)."""
+    causal, in_transform, blocks_params, dilations, out_linear, (hw, hb) = weights
     lib = load()
     C, S, O = in_transform[0].shape[0], blocks_params[0][2].shape[0] - in_transform[0].shape[0], out_linear[0].shape[0]
     dev = causal[0].device
     if causal[0].numel() != 2 * C:
         raise NotImplementedError("libblvm_hip: wavenet_decode is built for in_channels = n_stack_frames = 1")
-    hw, hb = head_linear
-    if hw.shape[0] > 32 or hw.shape[0] != 3 * num_mix:
-        raise NotImplementedError("libblvm_hip: wavenet_decode head must have 3 * num_mix <= 32 outputs")
-    pad_w = torch.zeros(32 - hw.shape[0], hw.shape[1], device=dev)
-    parts = [*causal, *in_transform, *(p for blk in blocks_params for p in blk), *out_linear, hw, pad_w, hb, pad_w.new_zeros(32 - hb.numel())]
+    if isinstance(head, DmolHead):
+        if hw.shape[0] > 32 or hw.shape[0] != 3 * head.num_mix:
+            raise NotImplementedError("libblvm_hip: wavenet_decode head must have 3 * num_mix <= 32 outputs")
+        pad_w = torch.zeros(32 - hw.shape[0], hw.shape[1], device=dev)
+        tail = [hw, pad_w, hb, pad_w.new_zeros(32 - hb.numel())]
+        want = lib.blvm_wavenet_decode_pack_floats(C, S, O, len(blocks_params))
+    else:
+        V = hw.shape[0]
+        if head.levels.numel() != V or hb.numel() != V:
+            raise ValueError(f"wavenet_decode: a head of {V} classes with {hb.numel()} biases and {head.levels.numel()} levels")
+        tail = [hw, hb]
+        want = lib.blvm_wavenet_cat_decode_pack_floats(C, S, O, len(blocks_params), V)
+    parts = [*causal, *in_transform, *(p for blk in blocks_params for p in blk), *out_linear, *tail]
     packed = torch.cat([_f32c(p).reshape(-1) for p in parts])
-    if packed.numel() != lib.blvm_wavenet_decode_pack_floats(C, S, O, len(blocks_params)):
+    if packed.numel() != want:
         raise ValueError("wavenet_decode: parameter shapes do not match the packed layout")
     return lib, C, S, O, dev, packed, _c_ints(dilations)
 
 
-def _wavenet_decode_draws(u, v, n_frames: int, B: int, num_mix: int):
-    if u is not None:
-        u, v = _f32c(u), _f32c(v)
-        if tuple(u.shape) != (n_frames, B, num_mix) or tuple(v.shape) != (n_frames, B):
-            raise ValueError("wavenet_decode: u must be [n_frames,B,num_mix] and v [n_frames,B]")
-    return u, v
-
-
 @torch.no_grad()
-def wavenet_decode_start(causal, in_transform, blocks_params, dilations, out_linear, head_linear, B: int, n_frames: int, inv_std: float,
-                         skip_scale: float, num_mix: int, log_eps: float, u=None, v=None):
-    """`wavenet_decode`, which also hands back its scratch buffer: -> (x [B,n_frames], scratch).  With the last two samples the
-    ring buffers in scratch (`wavenet_ring_views`) are the state after n_frames frames (`wavenet_decode_resume`)."""
-    lib, C, S, O, dev, packed, dil = _wavenet_decode_pack(causal, in_transform, blocks_params, dilations, out_linear, head_linear, num_mix)
-    queues = torch.empty(lib.blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S), device=dev, dtype=torch.float32)
-    x = torch.empty(B, n_frames, device=dev, dtype=torch.float32)
-    u, v = _wavenet_decode_draws(u, v, n_frames, B, num_mix)
-    check(lib.blvm_wavenet_decode(ptr(packed), dil, len(dilations), B, C, S, O, num_mix, n_frames, inv_std, skip_scale, log_eps,
-                                  ptr(u), ptr(v), ptr(queues), ptr(x), stream_ptr()), "blvm_wavenet_decode")  # fmt: skip
-    return x, queues
+def wavenet_decode(weights, head, B: int, n_frames: int, inv_std: float, skip_scale: float, draws=None, resume=None):
+    """K10c: all frames of B utterances in one launch.  weights = (causal, in_transform, blocks_params, dilations, out_linear,
+    head_linear): (weight, bias) pairs, blocks_params as for wavenet_stack.  head = `DmolHead` with draws = (u [n_frames,B,num_mix],
+    v [n_frames,B]), or `CategoricalHead` with draws = u [n_frames,B]: uniform draws indexed from 0 (None: the mode, the arg-max class).
+    resume = (t0, samples [B,2], scratch) continues from a state: `scratch` holds the ring buffers after absolute frame t0 - 1
+    (`wavenet_prime_rings` or an earlier call; updated in place), samples the last two samples.  -> `WaveNetDecodeOut`."""
+    lib, C, S, O, dev, packed, dil = _wavenet_decode_pack(weights, head)
+    dmol, n = isinstance(head, DmolHead), len(dil)
+    shapes = [(n_frames, B, head.num_mix), (n_frames, B)] if dmol else [(n_frames, B)]
+    if draws is None:
+        draws = [None] * len(shapes)
+    else:
+        draws = [_f32c(t) for t in (draws if dmol else (draws,))]
+        if [tuple(t.shape) for t in draws] != shapes:
+            raise ValueError("wavenet_decode: the draws must be (u [n_frames,B,num_mix], v [n_frames,B]) for the DMoL head and u [n_frames,B] "
+                             "for the categorical head")  # fmt: skip
+    n_scratch = lib.blvm_wavenet_decode_scratch_floats(dil, n, B, C, S)
+    f32 = dict(device=dev, dtype=torch.float32)
+    if resume is None:
+        scratch = torch.empty(n_scratch, **f32)
+    else:
+        t0, samples, scratch = resume
+        if scratch.dtype != torch.float32 or scratch.numel() != n_scratch:
+            raise ValueError("wavenet_decode: the scratch buffer does not belong to these shapes")
+        samples = _f32c(samples)
+        if tuple(samples.shape) != (B, 2):
+            raise ValueError("wavenet_decode: samples must be [B,2]")
+    x = torch.empty(B, n_frames, **f32)
+    k = None if dmol else torch.empty(B, n_frames, device=dev, dtype=torch.int32)
+    if dmol:
+        name, width, operands = "blvm_wavenet_decode", head.num_mix, (head.log_eps, *map(ptr, draws))
+    else:
+        name, width = "blvm_wavenet_cat_decode", head.levels.numel()
+        levels = _f32c(head.levels.to(dev)).reshape(width)  # (named: it must outlive the launch's enqueue)
+        operands = (ptr(levels), ptr(draws[0]))
+    sizes = (ptr(packed), dil, n, B, C, S, O, width, n_frames)
+    outs = (ptr(x),) if dmol else (ptr(x), ptr(k))
+    if resume is None:
+        check(getattr(lib, name)(*sizes, inv_std, skip_scale, *operands, ptr(scratch), *outs, stream_ptr()), name)
+        return WaveNetDecodeOut(x, k, scratch, None)
+    samples_out = torch.empty(B, 2, **f32)
+    name += "_resume"
+    check(getattr(lib, name)(*sizes, int(t0), inv_std, skip_scale, *operands, ptr(samples), ptr(scratch), *outs, ptr(samples_out),
+                             stream_ptr()), name)  # fmt: skip
+    return WaveNetDecodeOut(x, k, scratch, samples_out)
 
 
-@torch.no_grad()
-def wavenet_decode(causal, in_transform, blocks_params, dilations, out_linear, head_linear, B: int, n_frames: int, inv_std: float,
-                   skip_scale: float, num_mix: int, log_eps: float, u=None, v=None):
-    """K10c: all frames of B utterances in one launch.  causal / in_transform / out_linear / head_linear = (weight, bias);
-    blocks_params as for wavenet_stack; u [n_frames,B,num_mix], v [n_frames,B] uniform draws (None: the mode).  -> x [B,n_frames]."""
-    return wavenet_decode_start(causal, in_transform, blocks_params, dilations, out_linear, head_linear, B, n_frames, inv_std, skip_scale,
-                                num_mix, log_eps, u, v)[0]  # fmt: skip
-
-
-def wavenet_ring_views(scratch, dilations, B: int, C: int, S: int):
-    """The ring buffers inside a K10c scratch buffer: block i's input over its last dilation_i frames as a view [dilation_i,B,C]."""
-    off, views = load().blvm_wavenet_decode_ring_offset_floats(len(dilations), C, S), []
+def _ring_views(scratch, off: int, dilations, B: int, C: int):
+    """Consecutive views [dilation_i,B,C] of `scratch` from float offset `off`: block i's input over its last dilation_i frames."""
+    views = []
     for d in dilations:
         views.append(scratch[off : off + d * B * C].view(d, B, C))
         off += d * B * C
     return views
+
+
+def wavenet_ring_views(scratch, dilations, B: int, C: int, S: int):
+    """The ring buffers inside a K10c scratch buffer: block i's input over its last dilation_i frames as a view [dilation_i,B,C]."""
+    return _ring_views(scratch, load().blvm_wavenet_decode_ring_offset_floats(len(dilations), C, S), dilations, B, C)
 
 
 def wavenet_decode_scratch(dilations, B: int, C: int, S: int, device):
@@ -1597,109 +1649,15 @@ def wavenet_prime_rings(h0, blocks_params, dilations, inv_std: float, S: int, t0
         cur, L = o, L - d
 
 
-@torch.no_grad()
-def wavenet_decode_resume(causal, in_transform, blocks_params, dilations, out_linear, head_linear, B: int, n_frames: int, inv_std: float,
-                          skip_scale: float, num_mix: int, log_eps: float, u, v, t0: int, samples, scratch):
-    """K10c from a state: `scratch` holds the ring buffers after absolute frame t0 - 1 (`wavenet_prime_rings` or an earlier
-    call; updated in place), samples [B,2] the last two samples.  u, v are indexed from 0.  -> (x [B,n_frames], samples [B,2])."""
-    lib, C, S, O, dev, packed, dil = _wavenet_decode_pack(causal, in_transform, blocks_params, dilations, out_linear, head_linear, num_mix)
-    if scratch.dtype != torch.float32 or scratch.numel() != lib.blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S):
-        raise ValueError("wavenet_decode_resume: the scratch buffer does not belong to these shapes")
-    samples = _f32c(samples)
-    if tuple(samples.shape) != (B, 2):
-        raise ValueError("wavenet_decode_resume: samples must be [B,2]")
-    x = torch.empty(B, n_frames, device=dev, dtype=torch.float32)
-    samples_out = torch.empty(B, 2, device=dev, dtype=torch.float32)
-    u, v = _wavenet_decode_draws(u, v, n_frames, B, num_mix)
-    check(lib.blvm_wavenet_decode_resume(ptr(packed), dil, len(dilations), B, C, S, O, num_mix, n_frames, t0, inv_std, skip_scale,
-                                         log_eps, ptr(u), ptr(v), ptr(samples), ptr(scratch), ptr(x), ptr(samples_out), stream_ptr()),
-          "blvm_wavenet_decode_resume")  # fmt: skip
-    return x, samples_out
-
-
-def _wavenet_cat_decode_pack(causal, in_transform, blocks_params, dilations, out_linear, head_linear, levels):
-    """The packed weight image of K10c with the categorical head (the head Linear [V,O] unpadded) and its sizes:
-    -> (lib, C, S, O, V, device, packed, dilations as a C array, levels [V] fp32 on the device)."""
-    lib = load()
-    C, S, O = in_transform[0].shape[0], blocks_params[0][2].shape[0] - in_transform[0].shape[0], out_linear[0].shape[0]
-    dev = causal[0].device
-    if causal[0].numel() != 2 * C:
-        raise NotImplementedError("libblvm_hip: wavenet_cat_decode is built for in_channels = n_stack_frames = 1")
-    hw, hb = head_linear
-    V = hw.shape[0]
-    if levels.numel() != V or hb.numel() != V:
-        raise ValueError(f"wavenet_cat_decode: a head of {V} classes with {hb.numel()} biases and {levels.numel()} levels")
-    parts = [*causal, *in_transform, *(p for blk in blocks_params for p in blk), *out_linear, hw, hb]
-    packed = torch.cat([_f32c(p).reshape(-1) for p in parts])
-    if packed.numel() != lib.blvm_wavenet_cat_decode_pack_floats(C, S, O, len(blocks_params), V):
-        raise ValueError("wavenet_cat_decode: parameter shapes do not match the packed layout")
-    return lib, C, S, O, V, dev, packed, _c_ints(dilations), _f32c(levels.to(dev)).reshape(V)
-
-
-def _wavenet_cat_decode_draws(u, n_frames: int, B: int):
-    if u is not None:
-        u = _f32c(u)
-        if tuple(u.shape) != (n_frames, B):
-            raise ValueError("wavenet_cat_decode: u must be [n_frames,B]")
-    return u
-
-
-@torch.no_grad()
-def wavenet_cat_decode_start(causal, in_transform, blocks_params, dilations, out_linear, head_linear, levels, B: int, n_frames: int,
-                             inv_std: float, skip_scale: float, u=None):
-    """`wavenet_cat_decode`, which also hands back its scratch buffer: -> (x [B,n_frames], k [B,n_frames] int32, scratch).  With the
-    last two samples the ring buffers in scratch (`wavenet_ring_views`) are the state after n_frames frames."""
-    lib, C, S, O, V, dev, packed, dil, levels = _wavenet_cat_decode_pack(causal, in_transform, blocks_params, dilations, out_linear,
-                                                                        head_linear, levels)  # fmt: skip
-    queues = torch.empty(lib.blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S), device=dev, dtype=torch.float32)
-    x = torch.empty(B, n_frames, device=dev, dtype=torch.float32)
-    k = torch.empty(B, n_frames, device=dev, dtype=torch.int32)
-    u = _wavenet_cat_decode_draws(u, n_frames, B)
-    check(lib.blvm_wavenet_cat_decode(ptr(packed), dil, len(dilations), B, C, S, O, V, n_frames, inv_std, skip_scale, ptr(levels), ptr(u),
-                                      ptr(queues), ptr(x), ptr(k), stream_ptr()), "blvm_wavenet_cat_decode")  # fmt: skip
-    return x, k, queues
-
-
-@torch.no_grad()
-def wavenet_cat_decode(causal, in_transform, blocks_params, dilations, out_linear, head_linear, levels, B: int, n_frames: int,
-                       inv_std: float, skip_scale: float, u=None):
-    """K10c with the categorical head: all frames of B utterances in one launch.  Weights as for `wavenet_decode`, head_linear the
-    [V,O] Linear of the softmax (16 <= V <= 1024, a multiple of 16), levels [V] the class values; u [n_frames,B] uniform draws (None:
-    the arg-max class).  -> (x [B,n_frames] = levels[k], k [B,n_frames] int32)."""
-    return wavenet_cat_decode_start(causal, in_transform, blocks_params, dilations, out_linear, head_linear, levels, B, n_frames, inv_std,
-                                    skip_scale, u)[:2]  # fmt: skip
-
-
-@torch.no_grad()
-def wavenet_cat_decode_resume(causal, in_transform, blocks_params, dilations, out_linear, head_linear, levels, B: int, n_frames: int,
-                              inv_std: float, skip_scale: float, u, t0: int, samples, scratch):
-    """`wavenet_cat_decode` from a state, as `wavenet_decode_resume` (the scratch buffer and the sample pair are the same for both
-    heads).  -> (x [B,n_frames], k [B,n_frames] int32, samples [B,2])."""
-    lib, C, S, O, V, dev, packed, dil, levels = _wavenet_cat_decode_pack(causal, in_transform, blocks_params, dilations, out_linear,
-                                                                        head_linear, levels)  # fmt: skip
-    if scratch.dtype != torch.float32 or scratch.numel() != lib.blvm_wavenet_decode_scratch_floats(dil, len(dilations), B, C, S):
-        raise ValueError("wavenet_cat_decode_resume: the scratch buffer does not belong to these shapes")
-    samples = _f32c(samples)
-    if tuple(samples.shape) != (B, 2):
-        raise ValueError("wavenet_cat_decode_resume: samples must be [B,2]")
-    x = torch.empty(B, n_frames, device=dev, dtype=torch.float32)
-    k = torch.empty(B, n_frames, device=dev, dtype=torch.int32)
-    samples_out = torch.empty(B, 2, device=dev, dtype=torch.float32)
-    u = _wavenet_cat_decode_draws(u, n_frames, B)
-    check(lib.blvm_wavenet_cat_decode_resume(ptr(packed), dil, len(dilations), B, C, S, O, V, n_frames, t0, inv_std, skip_scale,
-                                             ptr(levels), ptr(u), ptr(samples), ptr(scratch), ptr(x), ptr(k), ptr(samples_out),
-                                             stream_ptr()), "blvm_wavenet_cat_decode_resume")  # fmt: skip
-    return x, k, samples_out
-
-
-def stcn_generate_pack(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear,
-                       head_linear, dense: bool, S: int, num_mix: int):
-    """The packed weight image of K10d (`blvm_stcn_generate`) and the host arrays that travel with it.  causal / in_transform /
-    out_in / up_linear / head_linear = (weight, bias); blocks_params as for wavenet_stack; groups[i] = the latent level that reads
-    block i's skip (or -1); priors[l] = (the three nn.Linear of the mean MLP, those of the sd MLP); order = the levels in visiting
-    order.  -> namespace(lib, packed, C, dil, groups, latent, order, n_blocks, n_out, n, dense, latent_sizes)."""
+def stcn_generate_pack(weights, S: int, num_mix: int):
+    """The packed weight image of K10d (`blvm_stcn_generate`) and the host arrays that travel with it.  weights = (causal,
+    in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear, dense): causal /
+    in_transform / out_in / up_linear / head_linear = (weight, bias); blocks_params as for wavenet_stack; groups[i] = the latent level
+    that reads block i's skip (or -1); priors[l] = (the three nn.Linear of the mean MLP, those of the sd MLP); order = the levels in
+    visiting order.  -> namespace(lib, packed, C, dil, groups, latent, order, n_blocks, n_out, n, dense, latent_sizes)."""
     from types import SimpleNamespace
 
+    causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear, dense = weights
     lib = load()
     C = in_transform[0].shape[0]
     dev = causal[0].device
@@ -1731,16 +1689,26 @@ def stcn_generate_pack(causal, in_transform, blocks_params, dilations, groups, p
     return ns
 
 
-def _stcn_scratch_floats(p, S: int, num_mix: int, B: int) -> int:
-    return max(int(p.lib.blvm_stcn_generate_scratch_floats(p.dil, p.C, S, p.n_blocks, p.n_out, p.latent, p.order, p.n, p.dense, num_mix, B)), 4)
+def stcn_generate_scratch_floats(dilations, n_out: int, latent_sizes, order, dense: bool, B: int, C: int, S: int, num_mix: int) -> int:
+    """Size of a K10d scratch buffer (a host computation: no device needed)."""
+    lib = load()
+    n = lib.blvm_stcn_generate_scratch_floats(_c_ints(dilations), C, S, len(dilations), n_out, _c_ints(latent_sizes), _c_ints(order),
+                                              len(latent_sizes), int(bool(dense)), num_mix, B)  # fmt: skip
+    if n == 0:
+        raise _hip.BlvmHipError("blvm_stcn_generate: " + lib.blvm_last_error().decode(errors="replace"))
+    return max(int(n), 4)
 
 
 @torch.no_grad()
-def _stcn_generate_call(weights, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float, slope: float,
-                        num_mix: int, log_eps: float, eps, u, v, resume=None):
-    """`blvm_stcn_generate`, or `blvm_stcn_generate_resume` with resume = (t0, x_in [B,2,S], scratch).
-    -> (x [B,T,S], z, mu, sd: lists of [T,B,Z_l], scratch, x_state [B,2,S] or None)."""
-    p = stcn_generate_pack(*weights, S, num_mix)
+def stcn_generate(weights, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float, slope: float,
+                  num_mix: int, log_eps: float, eps, u=None, v=None, resume=None):
+    """K10d: T steps of ancestral sampling from the STCN for B rows in one launch (weights as `stcn_generate_pack`).  eps[l]
+    [T,B,Z_l]; u [T,B,S,num_mix], v [T,B,S] uniform draws (None: the mode), all indexed from 0.  resume = (t0, x_in [B,2,S], scratch)
+    continues from a state: `scratch` holds the rings after absolute step t0 - 1 (primed through `stcn_ring_views`, or an earlier
+    call's; updated in place), x_in the two newest stacks.
+    -> (x [B,T,S], z, mu, sd: lists of [T,B,Z_l], scratch, x_state [B,2,S] or None).  With the last two stacks of x (zero stacks in
+    front of step 0) the rings in the scratch buffer a zero start hands back are the state after T steps."""
+    p = stcn_generate_pack(weights, S, num_mix)
     lib, dev = p.lib, p.packed.device
     f32 = dict(device=dev, dtype=torch.float32)
     eps = [_f32c(e) for e in eps]
@@ -1750,16 +1718,16 @@ def _stcn_generate_call(weights, B: int, T: int, S: int, inv_std: float, out_sca
         u, v = _f32c(u), _f32c(v)
         if tuple(u.shape) != (T, B, S, num_mix) or tuple(v.shape) != (T, B, S):
             raise ValueError("stcn_generate: u must be [T,B,S,num_mix] and v [T,B,S]")
-    n_scratch = _stcn_scratch_floats(p, S, num_mix, B)
+    n_scratch = stcn_generate_scratch_floats(p.dil, p.n_out, p.latent_sizes, p.order, p.dense, B, p.C, S, num_mix)
     if resume is None:
         scratch = torch.empty(n_scratch, **f32)
     else:
         t0, x_in, scratch = resume
         if scratch.dtype != torch.float32 or scratch.device != dev or scratch.numel() != n_scratch or not scratch.is_contiguous():
-            raise ValueError("stcn_generate_resume: the scratch buffer does not belong to these shapes")
+            raise ValueError("stcn_generate: the scratch buffer does not belong to these shapes")
         x_in = _f32c(x_in)
         if tuple(x_in.shape) != (B, 2, S):
-            raise ValueError("stcn_generate_resume: x_in must be [B,2,S]")
+            raise ValueError("stcn_generate: x_in must be [B,2,S]")
     x = torch.empty(B, T, S, **f32)
     zs, mus, sds = ([torch.empty(T, B, Z, **f32) for Z in p.latent_sizes] for _ in range(3))
     ptrs = lambda ts: (ctypes.c_void_p * len(ts))(*[ptr(t) for t in ts])  # noqa: E731
@@ -1773,36 +1741,6 @@ def _stcn_generate_call(weights, B: int, T: int, S: int, inv_std: float, out_sca
     return x, zs, mus, sds, scratch, x_state
 
 
-def stcn_generate(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear,
-                  dense: bool, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float, slope: float,
-                  num_mix: int, log_eps: float, eps, u=None, v=None):
-    """K10d: T steps of ancestral sampling from the STCN for B rows in one launch (arguments as `stcn_generate_pack`).  eps[l]
-    [T,B,Z_l]; u [T,B,S,num_mix], v [T,B,S] uniform draws (None: the mode).  -> (x [B,T,S], z, mu, sd: lists of [T,B,Z_l])."""
-    weights = (causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear, dense)
-    return _stcn_generate_call(weights, B, T, S, inv_std, out_scale, sd_beta, sd_eps, slope, num_mix, log_eps, eps, u, v)[:4]
-
-
-def stcn_generate_start(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear,
-                        head_linear, dense: bool, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float,
-                        slope: float, num_mix: int, log_eps: float, eps, u=None, v=None):
-    """`stcn_generate`, which also hands back its scratch buffer: -> (x, z, mu, sd, scratch).  With the last two stacks of x (zero
-    stacks in front of step 0) the rings in scratch (`stcn_ring_views`) are the state after T steps (`stcn_generate_resume`)."""
-    weights = (causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear, dense)
-    return _stcn_generate_call(weights, B, T, S, inv_std, out_scale, sd_beta, sd_eps, slope, num_mix, log_eps, eps, u, v)[:5]
-
-
-def stcn_generate_resume(causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear,
-                         head_linear, dense: bool, B: int, T: int, S: int, inv_std: float, out_scale: float, sd_beta: float, sd_eps: float,
-                         slope: float, num_mix: int, log_eps: float, eps, u, v, t0: int, x_in, scratch):
-    """K10d from a state: `scratch` holds the rings after absolute step t0 - 1 (primed through `stcn_ring_views`, or an earlier
-    call's; updated in place), x_in [B,2,S] the two newest stacks.  eps, u, v are indexed from 0.
-    -> (x [B,T,S], z, mu, sd: lists of [T,B,Z_l], x_state [B,2,S])."""
-    weights = (causal, in_transform, blocks_params, dilations, groups, priors, order, out_in, out_blocks_params, up_linear, head_linear, dense)
-    x, zs, mus, sds, _, x_state = _stcn_generate_call(weights, B, T, S, inv_std, out_scale, sd_beta, sd_eps, slope, num_mix, log_eps, eps,
-                                                      u, v, resume=(t0, x_in, scratch))  # fmt: skip
-    return x, zs, mus, sds, x_state
-
-
 def stcn_ring_views(scratch, dilations, n_out: int, latent_sizes, order, dense: bool, B: int, C: int, S: int, num_mix: int):
     """The state inside a K10d scratch buffer as views: (rings: dilated block i's input over its last dilation_i steps [dilation_i,B,C],
     orings: output block j's input at the last step [1,B,C])."""
@@ -1810,21 +1748,8 @@ def stcn_ring_views(scratch, dilations, n_out: int, latent_sizes, order, dense: 
                                                            len(latent_sizes), int(bool(dense)), num_mix))  # fmt: skip
     if off == 0:
         raise _hip.BlvmHipError("blvm_stcn_generate: " + load().blvm_last_error().decode(errors="replace"))
-    rings = []
-    for d in [*dilations, *([1] * n_out)]:
-        rings.append(scratch[off : off + d * B * C].view(d, B, C))
-        off += d * B * C
+    rings = _ring_views(scratch, off, [*dilations, *([1] * n_out)], B, C)
     return rings[: len(dilations)], rings[len(dilations) :]
-
-
-def stcn_generate_scratch_floats(dilations, n_out: int, latent_sizes, order, dense: bool, B: int, C: int, S: int, num_mix: int) -> int:
-    """Size of a K10d scratch buffer (a host computation: no device needed)."""
-    lib = load()
-    n = lib.blvm_stcn_generate_scratch_floats(_c_ints(dilations), C, S, len(dilations), n_out, _c_ints(latent_sizes), _c_ints(order),
-                                              len(latent_sizes), int(bool(dense)), num_mix, B)  # fmt: skip
-    if n == 0:
-        raise _hip.BlvmHipError("blvm_stcn_generate: " + lib.blvm_last_error().decode(errors="replace"))
-    return max(int(n), 4)
 
 
 def stcn_generate_scratch(dilations, n_out: int, latent_sizes, order, dense: bool, B: int, C: int, S: int, num_mix: int, device):

@@ -1053,8 +1053,8 @@ def test_wavenet_decode_kernel_with_a_skip_width_of_its_own():
     assert gap >= WP.MIN_GAP
     causal, in_transform, blocks, out_linear, head_linear = ([t.to(DEV) for t in p] if isinstance(p, tuple) else [tuple(t.to(DEV) for t in b) for b in p]
                                                              for p in params)  # fmt: skip
-    x = ops.wavenet_decode(causal, in_transform, blocks, list(c.dilations), out_linear, head_linear, c.B, c.n_frames, c.inv_std, c.skip_scale,
-                           c.num_mix, c.log_eps, u.to(DEV), v.to(DEV))  # fmt: skip
+    x = ops.wavenet_decode((causal, in_transform, blocks, list(c.dilations), out_linear, head_linear), ops.DmolHead(c.num_mix, c.log_eps), c.B,
+                           c.n_frames, c.inv_std, c.skip_scale, (u.to(DEV), v.to(DEV))).x  # fmt: skip
     _hip.check_async()
     assert tuple(x.shape) == (c.B, c.n_frames)
     err = (x.cpu().double() - x64).abs()

@@ -310,8 +310,6 @@ def test_wavenet_draw_site(loaded):
         x = m.generate(n_samples=B, n_frames=T_, uniforms=[(u[t, :, 0], v[t, :, 0]) for t in range(T_)], cached=True)
         judge_site("wavenet_decode", case, x.view(B, T_, 1))
         if i == 0:
-            t_in, blk = rs.in_transform, rs.res_blocks[0]
-            x = ops.wavenet_decode((m.causal.conv.weight, m.causal.conv.bias), (t_in.weight.view(t_in.out_channels, -1), t_in.bias),
-                                   [b.kernel_params() for b in rs.res_blocks], rs.dilations, (m.out_transform.linear.weight, m.out_transform.linear.bias),
-                                   (lik.params.weight, lik.params.bias), B, T_, blk.inv_std, 1.0 / m.variance_scale, lik.num_mix, lik.log_epsilon)  # fmt: skip
+            x = ops.wavenet_decode(m._one_launch_parts(), ops.DmolHead(lik.num_mix, lik.log_epsilon), B, T_, rs.res_blocks[0].inv_std,
+                                   1.0 / m.variance_scale).x  # fmt: skip
             judge_site("wavenet_decode", case, x.view(B, T_, 1), mode=True)

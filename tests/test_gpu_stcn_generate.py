@@ -95,12 +95,14 @@ def test_step_by_step_matches_float64_and_the_one_launch_path(name):
 
 
 def counting(monkeypatch):
-    """-> list that receives one entry per `ops.stcn_generate` call (the model calls it as `ops.stcn_generate`)."""
+    """-> list that receives one entry per `ops.stcn_generate` call from the zero start (the model calls it as `ops.stcn_generate`,
+    with `resume=` by keyword)."""
     seen, real = [], ops.stcn_generate
 
     def wrapped(*a, **k):
         out = real(*a, **k)
-        seen.append(out)
+        if k.get("resume") is None:
+            seen.append(out)
         return out
 
     monkeypatch.setattr(ops, "stcn_generate", wrapped)
@@ -173,7 +175,7 @@ def call_c_abi(name, fill, C=None, num_mix=NUM_MIX, n=None, out_fill=None):
     """`blvm_stcn_generate` called directly on a case's tensors with scratch and outputs prefilled.  -> (rc, x, z, mu, sd, scratch)."""
     case = CASES[name]
     m, eps, (u, v) = on_device(name)
-    p = ops.stcn_generate_pack(*m._one_launch_parts(), case.S, NUM_MIX)
+    p = ops.stcn_generate_pack(m._one_launch_parts(), case.S, NUM_MIX)
     lib, T, B, S = p.lib, case.T, case.B, case.S
     f32 = dict(device=DEV, dtype=torch.float32)
     n_scratch = int(lib.blvm_stcn_generate_scratch_floats(p.dil, p.C, S, p.n_blocks, p.n_out, p.latent, p.order, p.n, p.dense, NUM_MIX, B))

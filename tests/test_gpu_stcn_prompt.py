@@ -232,13 +232,15 @@ def test_prompt_then_chunks_is_prompt_then_all(name, Pp, chunks):
         assert all_equal([torch.cat([f(o)[l] for o in outs], 1) for l in range(len(case.latents))], f(out))
 
 
-def counting(monkeypatch, name):
-    """-> list that receives one entry per `ops.<name>` call (the model calls it as `ops.<name>`)."""
+def counting(monkeypatch, name, resumed=False):
+    """-> list that receives one entry per `ops.<name>` call (the model calls it as `ops.<name>`); resumed=True: per call that
+    continues from a state (the model gives `resume=` by keyword)."""
     seen, real = [], getattr(ops, name)
 
     def wrapped(*a, **k):
         out = real(*a, **k)
-        seen.append(out)
+        if not resumed or k.get("resume") is not None:
+            seen.append(out)
         return out
 
     monkeypatch.setattr(ops, name, wrapped)
@@ -250,7 +252,7 @@ def test_default_takes_the_resume_entry_with_a_prompt(monkeypatch):
     name, Pp = "c", 5
     case, r, m = CASES[name], prompt_reference(name, Pp, "posterior"), on_device(name)[0]
     assert m._one_launch_applies()
-    seen = counting(monkeypatch, "stcn_generate_resume")
+    seen = counting(monkeypatch, "stcn_generate", resumed=True)
     eps, uni = [e.to(DEV) for e in r["eps"]], tuple(t.to(DEV) for t in r["uniforms"])
     x, _ = gen(m, case, r["T"], eps, uni, fused=None, **prompt_kw(r, "posterior"))
     assert len(seen) == 1
@@ -264,7 +266,7 @@ def test_a_step_by_step_state_is_primed_for_the_one_launch_kernel(monkeypatch):
     m, eps, uni = on_device(name)
     _, first = gen(m, case, T1, *cut(eps, uni, 0, T1), fused=False, return_state=True)
     assert first.state.scratch is None
-    seen, primed = counting(monkeypatch, "stcn_generate_resume"), counting(monkeypatch, "wavenet_prime_rings")
+    seen, primed = counting(monkeypatch, "stcn_generate", resumed=True), counting(monkeypatch, "wavenet_prime_rings")
     x, out = gen(m, case, case.T - T1, *cut(eps, uni, T1, case.T), fused=True, state=first.state, return_state=True)
     assert len(seen) == 1 and len(primed) == 2  # the dilated stack's rings and the output stack's
     assert out.state.scratch is not None and out.state.n_steps == case.T
@@ -280,7 +282,7 @@ def test_another_head_continues_a_prompt_step_by_step(monkeypatch):
     B, S, latents = 3, 8, [16, 16, 32]
     torch.manual_seed(21)
     m = STCN(likelihood="GMM", n_layers=3, latent_size=latents, res_channels=16, n_stack_frames=S).to(DEV)
-    seen = counting(monkeypatch, "stcn_generate_resume")
+    seen = counting(monkeypatch, "stcn_generate", resumed=True)
     prompt = 0.5 * torch.tanh(torch.randn(B, 4 * S, device=DEV))
     (x, x_sl), out = m.generate(n_samples=B, max_timesteps=2 * S, x=prompt, return_state=True)
     (x2, _), out2 = m.generate(n_samples=B, max_timesteps=S, state=out.state)
@@ -296,7 +298,7 @@ def test_another_head_continues_a_prompt_step_by_step(monkeypatch):
 
 # ---- the C ABI of blvm_stcn_generate_resume
 def resume_abi(name, T1, fill=None, sentinel=None, t0=None, null_in=False, null_state=False, latent24=False, T=None):
-    """The state after T1 steps of the case (`ops.stcn_generate_start`), then `blvm_stcn_generate_resume` through ctypes for the
+    """The state after T1 steps of the case (`ops.stcn_generate` from the zero start), then `blvm_stcn_generate_resume` through ctypes for the
     remaining steps.  fill: what the outputs, the operand copies below the ring offset and the selected-skips tail hold before the
     call.  sentinel = (scratch, x_out, x_state) values planted everywhere instead (refusals).
     -> (rc, x, z, mu, sd, x_state, scratch, ring region bounds, x_in, error message)."""
@@ -306,10 +308,10 @@ def resume_abi(name, T1, fill=None, sentinel=None, t0=None, null_in=False, null_
     T2 = case.T - T1 if T is None else T
     p0, lik, blk = m.prior[0], m.likelihood_module, m.res_stack.res_blocks[0]
     f32 = dict(device=DEV, dtype=torch.float32)
-    x1, _, _, _, scratch = ops.stcn_generate_start(*m._one_launch_parts(), B, T1, S, blk.inv_std, m.inv_std, p0.softplus_beta, p0.epsilon,
-                                                   p0.transform_mu[1].negative_slope, NUM_MIX, lik.log_epsilon, [e[:T1] for e in eps],
-                                                   None if case.mode else u[:T1], None if case.mode else v[:T1])  # fmt: skip
-    p = ops.stcn_generate_pack(*m._one_launch_parts(), S, NUM_MIX)
+    x1, _, _, _, scratch, _ = ops.stcn_generate(m._one_launch_parts(), B, T1, S, blk.inv_std, m.inv_std, p0.softplus_beta, p0.epsilon,
+                                                p0.transform_mu[1].negative_slope, NUM_MIX, lik.log_epsilon, [e[:T1] for e in eps],
+                                                None if case.mode else u[:T1], None if case.mode else v[:T1])  # fmt: skip
+    p = ops.stcn_generate_pack(m._one_launch_parts(), S, NUM_MIX)
     lib = p.lib
     lo = int(lib.blvm_stcn_generate_ring_offset_floats(p.C, S, p.n_blocks, p.n_out, p.latent, p.order, p.n, p.dense, NUM_MIX))
     hi = lo + (sum(m.res_stack.dilations) + p.n_out) * B * p.C

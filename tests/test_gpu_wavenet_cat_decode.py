@@ -55,12 +55,13 @@ def _forbid_block_steps(monkeypatch):
     monkeypatch.setattr(ops, "wavenet_block_step", refuse)
 
 
-def _op_args(m, B, n, u):
-    rs, lik = m.res_stack, m.likelihood
-    t_in, blk = rs.in_transform, rs.res_blocks[0]
-    return ((m.causal.conv.weight, m.causal.conv.bias), (t_in.weight.view(t_in.out_channels, -1), t_in.bias),
-            [b.kernel_params() for b in rs.res_blocks], rs.dilations, (m.out_transform.linear.weight, m.out_transform.linear.bias),
-            (lik.logits.weight, lik.logits.bias), lik.levels, B, n, blk.inv_std, 1.0 / m.variance_scale, u)  # fmt: skip
+def _op_args(m, B, n, draws):
+    """The arguments of `ops.wavenet_decode` for a model of either head."""
+    from blvm import ops
+
+    lik = m.likelihood
+    head = ops.CategoricalHead(lik.levels) if hasattr(lik, "levels") else ops.DmolHead(lik.num_mix, lik.log_epsilon)
+    return m._one_launch_parts(), head, B, n, m.res_stack.res_blocks[0].inv_std, 1.0 / m.variance_scale, draws
 
 
 # ---- 1: one-launch generation ------------------------------------------------------------------------------------------------------
@@ -192,7 +193,7 @@ def test_without_uniforms_every_frame_is_the_first_arg_max_class(name):
     r = W.mode_reference(name)
     assert r["logit_gap"] >= W.MIN_LOGIT_GAP
     m = gpu_model(name)
-    x, k = ops.wavenet_cat_decode(*_op_args(m, case.B, case.n_frames, None))
+    x, k = ops.wavenet_decode(*_op_args(m, case.B, case.n_frames, None))[:2]
     assert k.dtype == torch.int32 and tuple(k.shape) == (case.B, case.n_frames)
     wrong = int((k.cpu().long() != r["k"]).sum())
     print(f"{name} mode: classes that differ {wrong} of {k.numel()}")
@@ -209,7 +210,7 @@ def test_the_class_output_and_sampling_without_given_uniforms():
     case = W.SHAPES["c32v256"]
     _, _, uni, r = W.reference("c32v256", 0)
     m = gpu_model("c32v256")
-    x, k = ops.wavenet_cat_decode(*_op_args(m, case.B, case.n_frames, torch.stack(_dev(uni))))
+    x, k = ops.wavenet_decode(*_op_args(m, case.B, case.n_frames, torch.stack(_dev(uni))))[:2]
     assert torch.equal(k.cpu().long(), r["k"]) and torch.equal(x, m.likelihood.dequantize(k))
     torch.manual_seed(3)
     free = m.generate(n_samples=case.B, n_frames=case.n_frames, cached=True)
@@ -223,32 +224,41 @@ def test_the_class_output_and_sampling_without_given_uniforms():
 @gpu
 @pytest.mark.parametrize("mode", ["nan", "noise"])
 def test_results_do_not_depend_on_what_the_buffers_held(mode, monkeypatch):
-    """The zero-start call and the resume call with every `torch.empty` of blvm.ops pre-filled (NaN words, noise): identical bits to
-    the unpoisoned run, no NaN, and the harness did poison buffers."""
+    """The zero-start call and the resume call of either head with every `torch.empty` of blvm.ops pre-filled (NaN words, noise):
+    identical bits to the unpoisoned run, no NaN, and the harness did poison buffers.  The categorical head at c32v256, the DMoL head
+    at the r32 shape of tests/test_wavenet_prompt.py; 7 frames per call."""
+    import test_wavenet_prompt as WP
     from blvm import ops
 
     _lib()
-    case = W.SHAPES["c32v256"]
-    B, n = case.B, 7
-    _, uni = W.draws(case, 0)
-    u = torch.stack(_dev(uni))
-    m = gpu_model("c32v256")
+    n = 7
+    cat, dmol = W.SHAPES["c32v256"], WP.SHAPES["r32"]
+    u_cat = torch.stack(_dev(W.draws(cat, 0)[1]))
+    uni = WP.draws(dmol, 0)[1]
+    u = torch.stack([a.reshape(dmol.B, dmol.num_mix) for a, _ in uni]).to(DEV)
+    v = torch.stack([b.reshape(dmol.B) for _, b in uni]).to(DEV)
+    sides = [(gpu_model("c32v256"), cat.B, lambda lo, hi: u_cat[lo:hi]), (WP.gpu_model("r32"), dmol.B, lambda lo, hi: (u[lo:hi], v[lo:hi]))]
 
-    def run():
-        x1, k1, scratch = ops.wavenet_cat_decode_start(*_op_args(m, B, n, u[:n]))
-        samples = x1[:, -2:].contiguous()
-        x2, k2, s2 = ops.wavenet_cat_decode_resume(*_op_args(m, B, n, u[n : 2 * n]), n, samples, scratch)
+    def run(m, B, draws):
+        a = ops.wavenet_decode(*_op_args(m, B, n, draws(0, n)))
+        b = ops.wavenet_decode(*_op_args(m, B, n, draws(n, 2 * n)), resume=(n, a.x[:, -2:].contiguous(), a.scratch))
         torch.cuda.synchronize()
-        return [t.clone() for t in (x1, k1, x2, k2, s2)]
+        return [t.clone() for t in (a.x, a.k, b.x, b.k, b.samples) if t is not None]
 
-    clean = run()
+    clean = [run(*side) for side in sides]
     with poisoned(monkeypatch, mode) as h:
-        dirty = run()
+        dirty, counts = [], []
+        for side in sides:
+            before = h.count
+            dirty.append(run(*side))
+            counts.append(h.count - before)
     assert h.count >= 6, "the harness poisoned fewer buffers than the two calls allocate"
-    for a, b in zip(clean, dirty):
+    # per head: scratch, x, k | x, k, samples; the DMoL head has no k
+    assert counts[0] >= 6 and counts[1] >= 4, counts
+    for a, b in zip(clean[0] + clean[1], dirty[0] + dirty[1]):
         assert not bool(torch.isnan(b.float()).any())
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
-    assert len(clean[1].unique()) >= 8
+    assert len(clean[0][1].unique()) >= 8 and len(clean[1][0].unique()) >= 8
 
 
 # ---- 6: refusals -----------------------------------------------------------------------------------------------------------------------

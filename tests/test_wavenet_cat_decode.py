@@ -108,3 +108,35 @@ def test_new_entry_points_are_declared_once():
     # the DMoL image with its head padded to 32 rows, the categorical one unpadded
     assert lib.blvm_wavenet_cat_decode_pack_floats(32, 32, 32, 4, 32) == lib.blvm_wavenet_decode_pack_floats(32, 32, 32, 4)
     assert lib.blvm_wavenet_cat_decode_pack_floats(32, 32, 32, 4, 256) - lib.blvm_wavenet_decode_pack_floats(32, 32, 32, 4) == 224 * 33
+
+
+def test_one_packer_builds_the_image_of_either_head():
+    """`ops._wavenet_decode_pack` on the smallest model (C = 16, two blocks): the size the library states for the head, and element
+    for element the image built part by part, whose tail is the DMoL head padded with zeros to 32 rows or the categorical head as it
+    stands.  Exact: the image is a copy of the parameters."""
+    from blvm import _hip, ops
+    from blvm.modules.distributions import CategoricalDense, DiscretizedLogisticMixtureDense
+
+    lib = _hip.load()
+    torch.manual_seed(5)
+    dmol, cat = _model(DiscretizedLogisticMixtureDense(16, 1, num_mix=10, num_bins=2**16)), _model(CategoricalDense(16, 48))
+    for m, head, lin, want in (
+        (dmol, ops.DmolHead(10, dmol.likelihood.log_epsilon), dmol.likelihood.params, lib.blvm_wavenet_decode_pack_floats(16, 16, 16, 2)),
+        (cat, ops.CategoricalHead(cat.likelihood.levels), cat.likelihood.logits, lib.blvm_wavenet_cat_decode_pack_floats(16, 16, 16, 2, 48)),
+    ):
+        rs, hw, hb = m.res_stack, lin.weight, lin.bias
+        assert len(rs.res_blocks) == 2 and m.res_channels == 16
+        parts = [m.causal.conv.weight, m.causal.conv.bias, rs.in_transform.weight, rs.in_transform.bias]
+        for b in rs.res_blocks:
+            parts += list(b.kernel_params())
+        parts += [m.out_transform.linear.weight, m.out_transform.linear.bias]
+        if isinstance(head, ops.DmolHead):
+            assert tuple(hw.shape) == (30, 16)
+            parts += [hw, hw.new_zeros(2, 16), hb, hb.new_zeros(2)]
+        else:
+            parts += [hw, hb]
+        image = torch.cat([p.detach().float().reshape(-1) for p in parts])
+        with torch.no_grad():
+            packed = ops._wavenet_decode_pack(m._one_launch_parts(), head)[5]
+        assert packed.dtype == torch.float32 and packed.numel() == want == image.numel()
+        assert torch.equal(packed, image)
