@@ -21,6 +21,7 @@ from blvm.models.base_model import BaseModel
 from blvm.models.vrnn import LIKELIHOOD_HEADS, LazyNamespace, _linears
 from blvm.modules.convenience import View
 from blvm.modules.distributions import (DiagonalGaussianDense, DiagonalGaussianMixtureDense, DiscretizedLogisticMixtureDense,
+                                        gauss_head_sample, gauss_rollout_draws, gauss_rollout_head, gauss_rollout_noise,
                                         mlp_log_prob)  # fmt: skip
 from blvm.utils.operations import split_sequence
 from blvm.utils.padding import get_modulo_length
@@ -183,10 +184,14 @@ class SRNN(nn.Module):
         (list of the head sampler's draws per step) optionally supply the randomness.  Every step runs K6 / K2 / K3 at T' = 1;
         `fused` (DMoL head, no stop value, at most `blvm_pchain_max_batch()` utterances, hidden / latent / recurrent sizes in multiples
         of 16, any frame-stack size S >= 1; default: whenever that holds) runs ALL steps in one persistent launch (K3c,
-        `ops.srnn_generate`)."""
+        `ops.srnn_generate`).  The GMM and Gaussian heads take the same paths under the same rules (`_generate_gauss`); their
+        `uniforms` = (u [T,B,S,K] in (1e-6, 1-1e-6), n [T,B,S] standard normals), u = None for the Gaussian head."""
         if u is not None or x.size(1) > 1:
             raise NotImplementedError("libblvm_hip: SRNN.generate is built for unconditional generation (x [B,1,S], u=None)")
         S, enc_lin, dec_lin, lik = self._plan()
+        head = gauss_rollout_head(lik)
+        if head is not None:
+            return self._generate_gauss(head, x, d_0, z_0, n_samples, max_timesteps, stop_value, use_mode, eps, uniforms, fused)
         dev = x.device
         H, Z, R = self.h_dim, self.z_dim, self.r_dim
         n = n_samples
@@ -254,6 +259,64 @@ class SRNN(nn.Module):
         return (xs.unsqueeze(-1), x_sl), SimpleNamespace(h_p=torch.cat([d_n, z_prev], -1))
 
 
+    @torch.no_grad()
+    def _generate_gauss(self, head, x, d_0, z_0, n, T, stop_value, use_mode, eps, uniforms, fused):
+        """`generate` for the GMM and Gaussian heads: the path is decided before any noise is drawn, the noise is drawn once in the
+        reference's per-step order (`gauss_rollout_noise`) and replayed by whichever path runs.  use_mode: zero prior noise, the
+        observation is still sampled (srnn.py:366-392)."""
+        S, enc_lin, dec_lin, lik = self._plan()
+        dev = x.device
+        H, Z, R = self.h_dim, self.z_dim, self.r_dim
+        gmm = isinstance(head, ops.GmmHead)
+        structure = stop_value is None and len(enc_lin) == 3 and len(dec_lin) == 3
+        if fused is None:
+            fused = (structure and T > 0 and 0 < n <= ops.load().blvm_pchain_max_batch() and all(v % 16 == 0 for v in (H, Z, R))
+                     and (not gmm or head.num_mix == 10))  # fmt: skip
+        elif fused and not structure:
+            raise NotImplementedError("libblvm_hip: the one-launch SRNN decoder needs the SRNNAudio structure and no stop value")
+        e_, u_s, n_s = gauss_rollout_noise(head, T, n, S, Z, dev, eps is None and not use_mode, uniforms is None)
+        if use_mode:
+            eps = torch.zeros(T, n, Z, device=dev)
+        else:
+            eps = e_ if eps is None else torch.as_tensor(eps)[:T].reshape(T, n, Z).to(dev, torch.float32)
+        if uniforms is not None:
+            u_s, n_s = gauss_rollout_draws(head, uniforms, T, n, S, dev)
+        d0 = None if d_0 is None else d_0.reshape(n, R)
+        if fused:
+            slope = next(m.negative_slope for m in self.encoder if isinstance(m, nn.LeakyReLU))
+            xs, d_n, zs = ops.srnn_generate(enc_lin, self.d_forward_recurrent, self._chain_params(), dec_lin, lik.params, x.reshape(n, S), d0, z_0,
+                                            eps, u_s, n_s, S, H, Z, R, head.num_mix if gmm else 0, self.prior[6].epsilon, slope, 0.0, head=head)  # fmt: skip
+            z_prev = zs[T - 2] if T > 1 else (torch.zeros(n, Z, device=dev) if z_0 is None else z_0)
+            return (xs.unsqueeze(-1), torch.zeros(n) + T), SimpleNamespace(h_p=torch.cat([d_n, z_prev], -1))
+        x_sl = torch.zeros(n)
+        d_t = torch.zeros(n, R, device=dev) if d0 is None else d0.contiguous()
+        z_t = torch.zeros(n, Z, device=dev) if z_0 is None else z_0.contiguous()
+        ones = torch.ones(n, dtype=torch.int32, device=dev)
+        gd = self.d_forward_recurrent
+        all_x, h_p = [], None
+        seq_active = torch.ones(n, dtype=torch.int)
+        t, all_ended = 0, False
+        while not all_ended and t < T:
+            enc = ops.mlp(x.reshape(n, S).to(torch.float32).contiguous(), enc_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE).view(1, n, -1)
+            d_seq, _ = ops.gru_sequence(enc, d_t, gd.weight_ih_l0, gd.weight_hh_l0, gd.bias_ih_l0, gd.bias_hh_l0)
+            d_t = d_seq[0].contiguous()
+            h_p = torch.cat([d_t, z_t], -1)
+            zs, *_ = ops.srnn_latent_chain(d_t.unsqueeze(0), torch.zeros(1, n, R, device=dev), z_t, eps[t].view(1, n, Z).contiguous(), ones,
+                                           self._chain_params(), H, Z, R, 3, 1, 0.0, self.prior[6].epsilon)  # mode 3: z ~ prior
+            z_t = zs[1].contiguous()
+            dec = ops.mlp(torch.cat([z_t, d_t], -1).contiguous(), dec_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE)
+            parameters = lik(dec.view(n, S, lik.out_features))
+            xs = gauss_head_sample(lik, head, parameters, None if u_s is None else u_s[t], n_s[t])  # [B,S,1]
+            all_x.append(xs)
+            x = xs.unsqueeze(1)
+            x_sl += seq_active
+            if stop_value is not None:
+                seq_active *= 1 - (xs == stop_value).flatten(1).all(1).to(torch.int).cpu()
+            t += 1
+            all_ended = bool(torch.all(1 - seq_active))
+        return (torch.stack(all_x, dim=1), x_sl), SimpleNamespace(h_p=h_p)
+
+
 class SRNNAudio(BaseModel):
     def __init__(self, likelihood: Union[str, nn.Module], input_size: int = 200, hidden_size: int = 256, latent_size: int = 64,
                  dropout: float = 0, residual_posterior: bool = False, smoothing: bool = True, num_mix: int = 10,
@@ -308,8 +371,8 @@ class SRNNAudio(BaseModel):
         return loss, metrics, outputs
 
     def generate(self, n_samples: int = 1, max_timesteps: int = 100, use_mode: bool = False, x=None, u=None, d_0=None, a_0=None,
-                 z_0=None, eps=None, uniforms=None):  # fmt: skip
-        """Same arguments as the reference (srnn.py:515-535)."""
+                 z_0=None, eps=None, uniforms=None, fused: Optional[bool] = None):  # fmt: skip
+        """Same arguments as the reference (srnn.py:515-535); `fused`: every step in one launch (K3c; default: when it applies)."""
         x = torch.zeros(n_samples, 1, self.input_size, device=self.device) if x is None else x
         return self.srnn.generate(x=x, u=u, d_0=d_0, a_0=a_0, z_0=z_0, n_samples=n_samples, max_timesteps=max_timesteps,
-                                  use_mode=use_mode, eps=eps, uniforms=uniforms)  # fmt: skip
+                                  use_mode=use_mode, eps=eps, uniforms=uniforms, fused=fused)  # fmt: skip

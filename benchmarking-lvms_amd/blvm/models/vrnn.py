@@ -19,8 +19,9 @@ from blvm.data.transforms import StackTensor
 from blvm.evaluation import BitsPerDimMetric, DeferredScalars, KLMetric, LatestMeanMetric, LLMetric, LossMetric
 from blvm.models.base_model import BaseModel
 from blvm.modules.convenience import View
-from blvm.modules.distributions import (DiagonalGaussianDense, DiagonalGaussianMixtureDense,
-                                        DiscretizedLogisticMixtureDense, mlp_log_prob)  # fmt: skip
+from blvm.modules.distributions import (DiagonalGaussianDense, DiagonalGaussianMixtureDense, DiscretizedLogisticMixtureDense,
+                                        gauss_head_sample, gauss_rollout_draws, gauss_rollout_head, gauss_rollout_noise,
+                                        mlp_log_prob)  # fmt: skip
 
 LIKELIHOOD_HEADS = (DiscretizedLogisticMixtureDense, DiagonalGaussianMixtureDense, DiagonalGaussianDense)
 
@@ -268,8 +269,13 @@ class VRNN(nn.Module):
         runs the K6 / K1 / K7-head kernels at T' = 1; `fused=True` (DMoL head, no stop value) runs ALL steps in one launch (K1c);
         the default (None) takes the one-launch path whenever the model has that structure: hidden, latent and recurrent sizes in
         multiples of 16, 10 mixture components, any frame-stack size S >= 1 (up to blvm_pchain_max_batch() utterances; beyond that
-        the per-CU form, which needs S % 16 == 0, or else the step-by-step path)."""
+        the per-CU form, which needs S % 16 == 0, or else the step-by-step path).
+        The GMM and Gaussian heads take the same paths under the same rules (`_generate_gauss`; the Gaussian head has no per-CU
+        form); their `uniforms` = (u [T,B,S,K] in (1e-6, 1-1e-6), n [T,B,S] standard normals), u = None for the Gaussian head."""
         S, enc_lin, dec_lin, lik = self._plan()
+        head = gauss_rollout_head(lik)
+        if head is not None:
+            return self._generate_gauss(head, x, h0, n_samples, max_timesteps, stop_value, use_mode, eps, uniforms, fused)
         auto = fused is None
         if auto:
             c = self.vrnn_cell
@@ -340,6 +346,57 @@ class VRNN(nn.Module):
                                 cell.z_dim, cell.r_dim, lik.num_mix, cell.prior[6].epsilon, slope, lik.log_epsilon)  # fmt: skip
         out = torch.cat([x.reshape(B, 1, S), xs], 1)  # [B,1+T,S] like the step-by-step path
         return (out, torch.full((B,), T + 1, dtype=torch.int)), SimpleNamespace()
+
+
+    @torch.no_grad()
+    def _generate_gauss(self, head, x, h0, n_samples, max_timesteps, stop_value, use_mode, eps, uniforms, fused):
+        """`generate` for the GMM and Gaussian heads.  The path is decided BEFORE any noise is drawn, from the structure and the
+        library's own limits (`blvm_pchain_max_batch`, `blvm_vrnn_decode_applies`), and the noise is drawn once, in the reference's
+        per-step order (`gauss_rollout_noise`), for whichever path replays it: a seeded call gives the same draws on either, and a
+        library error is an error, never a silent second run.  use_mode: the head's mode, z still sampled (as for the DMoL head)."""
+        S, enc_lin, dec_lin, lik = self._plan()
+        c = self.vrnn_cell
+        H, Z, R = c.h_dim, c.z_dim, c.r_dim
+        if x.size(0) == 1:
+            x = x.repeat(n_samples, *[1] * (x.ndim - 1))
+        assert x.size(0) == n_samples
+        dev, T, B = x.device, max_timesteps, n_samples
+        gmm = isinstance(head, ops.GmmHead)
+        structure = stop_value is None and T > 0 and len(enc_lin) == 3 and len(dec_lin) == 3
+        if fused is None:
+            lib = ops.load()
+            fused = (structure and all(v % 16 == 0 for v in (H, Z, R)) and (not gmm or head.num_mix == 10)
+                     and (B <= lib.blvm_pchain_max_batch() or (gmm and lib.blvm_vrnn_decode_applies(S, H, Z, R) == 1)))  # fmt: skip
+        elif fused and not structure:
+            raise NotImplementedError("libblvm_hip: the one-launch decoder is built for the VRNNAudio structure without a stop value")
+        want_draws = not use_mode and uniforms is None
+        e_, u, n = gauss_rollout_noise(head, T, B, S, Z, dev, eps is None, want_draws)
+        eps = e_ if eps is None else torch.as_tensor(eps)[:T].reshape(T, B, Z).to(dev, torch.float32)
+        if not use_mode and uniforms is not None:
+            u, n = gauss_rollout_draws(head, uniforms, T, B, S, dev)
+        if fused:
+            slope = next(m.negative_slope for m in self.encoder if isinstance(m, nn.LeakyReLU))
+            xs, _ = ops.vrnn_decode(enc_lin, c.kernel_params(), dec_lin, lik.params, x.reshape(B, S), h0, eps, u, n, S, H, Z, R,
+                                    head.num_mix if gmm else 0, c.prior[6].epsilon, slope, 0.0, head=head)  # fmt: skip
+            return (torch.cat([x.reshape(B, 1, S), xs], 1), torch.full((B,), T + 1, dtype=torch.int)), SimpleNamespace()
+        all_x = [x]
+        x_sl = torch.ones(B, dtype=torch.int)
+        h = c.get_initial_state(B, dev) if h0 is None else h0
+        seq_active = torch.ones(B, dtype=torch.int)
+        t, all_ended = 0, False
+        while not all_ended and t < T:
+            enc = ops.mlp(x.reshape(B, S).to(torch.float32).contiguous(), enc_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE)
+            h, out = c.generate(enc, h.contiguous(), use_mode=False, eps=eps[t])
+            dec = ops.mlp(torch.cat([out.phi_z, h], -1).contiguous(), dec_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE)  # [B, S*F]
+            parameters = lik(dec.view(B, S, lik.out_features))
+            x = lik.mode(parameters) if use_mode else gauss_head_sample(lik, head, parameters, None if u is None else u[t], n[t])  # [B,S,1]
+            all_x.append(x)
+            x_sl += seq_active
+            if stop_value is not None:
+                seq_active *= 1 - (x == stop_value).flatten(1).all(1).to(torch.int).cpu()
+            t += 1
+            all_ended = bool(torch.all(1 - seq_active))
+        return (torch.cat(all_x, dim=-1).permute(0, 2, 1), x_sl), SimpleNamespace()
 
 
 class VRNNAudio(BaseModel):

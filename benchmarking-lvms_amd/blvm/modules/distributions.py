@@ -38,8 +38,9 @@ class DiagonalGaussianDense(ConditionalDistribution):
         return params[0].contiguous()
 
     @torch.no_grad()
-    def sample(self, params):
-        return params[0] + params[1] * torch.randn_like(params[0])
+    def sample(self, params, noise=None):
+        """mu + sd n; `noise` (standard normals of params[0]'s shape) optionally supplies n, otherwise it comes from the device RNG."""
+        return params[0] + params[1] * (torch.randn_like(params[0]) if noise is None else noise.to(params[0]).reshape(params[0].shape))
 
     def forward(self, x: torch.Tensor):
         lead = x.shape[:-1]
@@ -199,6 +200,52 @@ class CategoricalDense(ConditionalDistribution):
     def dequantize(self, k):
         """Class k -> linspace(-1, 1, y_dim)[k]: the value `Quantize(bins=y_dim)` maps back to class k."""
         return self.levels.to(k.device)[k.long()]
+
+
+def gauss_rollout_head(lik):
+    """The head the one-launch VRNN / SRNN roll-outs draw for a Gaussian likelihood (`ops.GmmHead`, `ops.GaussHead`); None for any
+    other module (the DMoL head is those roll-outs' default and needs none)."""
+    if isinstance(lik, DiagonalGaussianMixtureDense) and lik.y_dim == 1:
+        return ops.GmmHead(lik.num_mix, lik.softplus_beta, lik.epsilon if lik.epsilon > 0 else 0.0)
+    if isinstance(lik, DiagonalGaussianDense) and lik.y_dim == 1:
+        return ops.GaussHead(lik.softplus_beta, lik.epsilon if lik.epsilon > 0 else 0.0)
+    return None
+
+
+def gauss_rollout_noise(head, T, B, S, Z, device, want_eps=True, want_draws=True):
+    """The device noise of a T-step roll-out with a Gaussian head, drawn in the reference's order and ranges — per step randn(B, Z)
+    for the prior, then (GMM) uniform(1e-6, 1 - 1e-6) over [B,S,K] for the component pick, then randn(B, S, 1) — so that a seeded
+    call draws the same numbers whichever path replays them.  -> (eps [T,B,Z], u [T,B,S,K] or None, n [T,B,S]); a part that is not
+    wanted is not drawn and None."""
+    K = head.num_mix if isinstance(head, ops.GmmHead) else 0
+    eps, u, n = [], [], []
+    for _ in range(T):
+        if want_eps:
+            eps.append(torch.randn(B, Z, device=device))
+        if want_draws:
+            if K:
+                u.append(torch.empty(B, S, K, device=device).uniform_(1e-6, 1.0 - 1e-6))
+            n.append(torch.randn(B, S, 1, device=device))
+    stack = lambda ts: torch.stack(ts) if ts else None  # noqa: E731
+    n = stack(n)
+    return stack(eps), stack(u), None if n is None else n.squeeze(-1)
+
+
+def gauss_rollout_draws(head, uniforms, T, B, S, device):
+    """A caller's `uniforms` = (u [T,B,S,K] or None, n [T,B,S]) for a Gaussian head -> (u, n) float32 on `device` in those shapes."""
+    K = head.num_mix if isinstance(head, ops.GmmHead) else 0
+    u, n = uniforms
+    if (u is None) != (K == 0):
+        raise ValueError("uniforms: (u [T,B,S,K], n [T,B,S]) for the GMM head, (None, n [T,B,S]) for the Gaussian head")
+    u = None if u is None else torch.as_tensor(u)[:T].reshape(T, B, S, K).to(device, torch.float32).contiguous()
+    return u, torch.as_tensor(n)[:T].reshape(T, B, S).to(device, torch.float32).contiguous()
+
+
+def gauss_head_sample(lik, head, parameters, u_t, n_t):
+    """One step of the step-by-step path with given draws: lik.sample with u_t [B,S,K] (GMM) and n_t [B,S] handed over as `noise=`."""
+    if isinstance(head, ops.GmmHead):
+        return lik.sample(parameters, noise=(u_t, n_t))
+    return lik.sample(parameters, noise=n_t.unsqueeze(-1))
 
 
 def mlp_log_prob(lik, x2d, layers, act, slope, y, x_sl_dev, layout, B, T, Tp, S, given=None, dec_node=None):

@@ -771,16 +771,31 @@ def _decode_weight_ptrs(w, first, first_lin, dec_lin, lik_lin):
     return keep
 
 
+def _head_scalars(head):
+    """A roll-out head (`DmolHead`, `GmmHead`, `GaussHead`) -> the five scalars the *_head entry points take in place of `num_mix,
+    log_eps`: (head_kind, num_mix, log_eps, head_sd_beta, head_sd_eps)."""
+    if isinstance(head, DmolHead):
+        return 0, int(head.num_mix), float(head.log_eps), 0.0, 0.0
+    if isinstance(head, GmmHead):
+        return 1, int(head.num_mix), 0.0, float(head.sd_beta), float(head.sd_eps)
+    if isinstance(head, GaussHead):
+        return 2, 0, 0.0, float(head.sd_beta), float(head.sd_eps)
+    raise TypeError(f"head: one of ops.DmolHead, ops.GmmHead, ops.GaussHead (got {type(head).__name__})")
+
+
 @torch.no_grad()
 def vrnn_decode(enc_lin, cell_params, dec_lin, lik_lin, x0, h0, eps, u, v, S, H, Z, R, num_mix, sd_eps, slope, log_eps, whole_chip=None,
-                max_scratch_floats=None):  # fmt: skip
+                max_scratch_floats=None, head=None):  # fmt: skip
     """K1c: T = eps.shape[0] steps of ancestral sampling for all B utterances in one launch.  enc_lin / dec_lin: 3 nn.Linear each;
     cell_params in `_VRNN_PARAM_ORDER`; lik_lin the DMoL head's Linear.  x0 [B,S], h0 [B,R] or None, eps [T,B,Z],
     u [T,B,S,num_mix] / v [T,B,S] uniforms (None: the mode).  -> (x [B,T,S], h_n [B,R]).
     whole_chip: True = `blvm_vrnn_generate` (every layer of a step dealt over all CUs, B <= 128, any S >= 1), False =
     `blvm_vrnn_decode` (16 utterances per CU, S a multiple of 16), None = the former whenever it applies.
     max_scratch_floats (whole chip; None: MAX_SCRATCH_FLOATS): a roll-out whose scratch would be larger runs as consecutive launches
-    of as many steps as fit — the same samples and state, bit for bit."""
+    of as many steps as fit — the same samples and state, bit for bit.
+    head (None: the DMoL head `num_mix, log_eps`, through the entry points above): `DmolHead`, `GmmHead` (lik_lin [30,30], u as for
+    DMoL, v standard normals) or `GaussHead` (lik_lin [2,2], u None, v [T,B,S] standard normals or None: the mean; whole chip only)
+    through `blvm_vrnn_generate_head` / `blvm_vrnn_decode_head`; num_mix and log_eps are then not read."""
     from ._hip import VrnnDecodeWeights
 
     lib = load()
@@ -797,22 +812,32 @@ def vrnn_decode(enc_lin, cell_params, dec_lin, lik_lin, x0, h0, eps, u, v, S, H,
     v = _f32c(v) if v is not None else None
     if whole_chip is None:
         whole_chip = B <= lib.blvm_pchain_max_batch()
+    hs5 = None if head is None else _head_scalars(head)
     x = torch.empty(B, T, S, device=dev, dtype=torch.float32)
     hn = torch.empty(B, R, device=dev, dtype=torch.float32)
     if whole_chip:
 
         def call(t0, t1, state, xc, scratch):
             xs, hs = (x0, h0) if state is None else state
-            uc, vc = (None, None) if u is None else (u[t0:t1], v[t0:t1])
-            check(lib.blvm_vrnn_generate(ctypes.byref(w), ptr(xs), ptr(hs), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, num_mix,
-                                         sd_eps, slope, log_eps, ptr(xc), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_generate")  # fmt: skip
+            uc, vc = (None if u is None else u[t0:t1]), (None if v is None else v[t0:t1])
+            if hs5 is None:
+                check(lib.blvm_vrnn_generate(ctypes.byref(w), ptr(xs), ptr(hs), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, num_mix,
+                                             sd_eps, slope, log_eps, ptr(xc), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_generate")  # fmt: skip
+            else:
+                check(lib.blvm_vrnn_generate_head(ctypes.byref(w), ptr(xs), ptr(hs), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, *hs5,
+                                                  sd_eps, slope, ptr(xc), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_generate_head")  # fmt: skip
 
-        _rollout(lambda n: lib.blvm_vrnn_generate_scratch_floats(n, B, S, H, Z, R), T, max_scratch_floats, "vrnn_decode", x, call,
-                 lambda xc, t1: (xc[:, -1].contiguous(), hn.clone()))  # fmt: skip
+        floats = ((lambda n: lib.blvm_vrnn_generate_scratch_floats(n, B, S, H, Z, R)) if hs5 is None
+                  else (lambda n: lib.blvm_vrnn_generate_scratch_floats_head(n, B, S, H, Z, R, hs5[0])))  # fmt: skip
+        _rollout(floats, T, max_scratch_floats, "vrnn_decode", x, call, lambda xc, t1: (xc[:, -1].contiguous(), hn.clone()))
         return x, hn
     scratch = torch.empty(lib.blvm_vrnn_decode_scratch_floats(S, H, Z, R), device=dev, dtype=torch.float32)
-    check(lib.blvm_vrnn_decode(ctypes.byref(w), ptr(x0), ptr(h0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, num_mix, sd_eps, slope,
-                               log_eps, ptr(x), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_decode")  # fmt: skip
+    if hs5 is None:
+        check(lib.blvm_vrnn_decode(ctypes.byref(w), ptr(x0), ptr(h0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, num_mix, sd_eps, slope,
+                                   log_eps, ptr(x), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_decode")  # fmt: skip
+    else:
+        check(lib.blvm_vrnn_decode_head(ctypes.byref(w), ptr(x0), ptr(h0), ptr(eps), ptr(u), ptr(v), T, B, S, H, Z, R, *hs5, sd_eps, slope,
+                                        ptr(x), ptr(hn), ptr(scratch), stream_ptr()), "blvm_vrnn_decode_head")  # fmt: skip
     return x, hn
 
 
@@ -1205,16 +1230,19 @@ _SRNN_PARAM_ORDER = (
 
 
 def srnn_generate(enc_lin, gru, chain_params, dec_lin, lik_lin, x0, d0, z0, eps, u, v, S, H, Z, R, num_mix, sd_eps, slope, log_eps,
-                  max_scratch_floats=None):  # fmt: skip
+                  max_scratch_floats=None, head=None):  # fmt: skip
     """K3c: T = eps.shape[0] steps of ancestral sampling from SRNNAudio for all B <= 128 utterances in one persistent launch.
     enc_lin / dec_lin: 3 nn.Linear each; gru: the forward nn.GRU (parameter container); chain_params in `_SRNN_PARAM_ORDER`;
     lik_lin the DMoL head's Linear.  x0 [B,S]; d0 [B,R], z0 [B,Z] or None; eps [T,B,Z]; u [T,B,S,num_mix] / v [T,B,S] (None: the
     mode).  Any S >= 1; H, Z, R multiples of 16.  -> (x [B,T,S], d_T [B,R], z [T,B,Z]).
     max_scratch_floats (None: MAX_SCRATCH_FLOATS): a roll-out whose scratch would be larger runs as consecutive launches of as many
-    steps as fit — the same samples, latents and state, bit for bit."""
+    steps as fit — the same samples, latents and state, bit for bit.
+    head (None: the DMoL head `num_mix, log_eps`, through `blvm_srnn_generate`): `DmolHead`, `GmmHead` or `GaussHead` as in
+    `vrnn_decode`, through `blvm_srnn_generate_head`."""
     lib = load()
     T, B = eps.shape[0], x0.shape[0]
     dev = x0.device
+    hs5 = None if head is None else _head_scalars(head)
     gk = [_f32c(t) for t in (gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)]
     cp = [_f32c(p) for p in chain_params]
     cw = _pack(_hip.SrnnWeights, _SRNN_PARAM_ORDER, cp)
@@ -1232,12 +1260,17 @@ def srnn_generate(enc_lin, gru, chain_params, dec_lin, lik_lin, x0, d0, z0, eps,
 
     def call(t0, t1, state, xc, scratch):
         xs, ds, z_prev = (x0, d0, z0) if state is None else state
-        uc, vc = (None, None) if u is None else (u[t0:t1], v[t0:t1])
-        check(lib.blvm_srnn_generate(ctypes.byref(w), ptr(xs), ptr(ds), ptr(z_prev), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, num_mix,
-                                     sd_eps, slope, log_eps, ptr(xc), ptr(dn), ptr(zs[t0:t1]), ptr(scratch), stream_ptr()), "blvm_srnn_generate")  # fmt: skip
+        uc, vc = (None if u is None else u[t0:t1]), (None if v is None else v[t0:t1])
+        if hs5 is None:
+            check(lib.blvm_srnn_generate(ctypes.byref(w), ptr(xs), ptr(ds), ptr(z_prev), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, num_mix,
+                                         sd_eps, slope, log_eps, ptr(xc), ptr(dn), ptr(zs[t0:t1]), ptr(scratch), stream_ptr()), "blvm_srnn_generate")  # fmt: skip
+        else:
+            check(lib.blvm_srnn_generate_head(ctypes.byref(w), ptr(xs), ptr(ds), ptr(z_prev), ptr(eps[t0:t1]), ptr(uc), ptr(vc), t1 - t0, B, S, H, Z, R, *hs5,
+                                              sd_eps, slope, ptr(xc), ptr(dn), ptr(zs[t0:t1]), ptr(scratch), stream_ptr()), "blvm_srnn_generate_head")  # fmt: skip
 
-    _rollout(lambda n: lib.blvm_srnn_generate_scratch_floats(n, B, S, H, Z, R), T, max_scratch_floats, "srnn_generate", x, call,
-             lambda xc, t1: (xc[:, -1].contiguous(), dn.clone(), zs[t1 - 1]))  # fmt: skip
+    floats = ((lambda n: lib.blvm_srnn_generate_scratch_floats(n, B, S, H, Z, R)) if hs5 is None
+              else (lambda n: lib.blvm_srnn_generate_scratch_floats_head(n, B, S, H, Z, R, hs5[0])))  # fmt: skip
+    _rollout(floats, T, max_scratch_floats, "srnn_generate", x, call, lambda xc, t1: (xc[:, -1].contiguous(), dn.clone(), zs[t1 - 1]))
     return x, dn, zs
 
 
@@ -1498,6 +1531,22 @@ class DmolHead(NamedTuple):
 
     num_mix: int
     log_eps: float
+
+
+class GmmHead(NamedTuple):
+    """The diagonal Gaussian-mixture head of the VRNN / SRNN roll-outs: the DMoL head's layout and component pick, then x = mu + sd n
+    with sd = softplus_beta(raw) + sd_eps (sd_beta == 0: raw is the sd)."""
+
+    num_mix: int
+    sd_beta: float
+    sd_eps: float
+
+
+class GaussHead(NamedTuple):
+    """The plain Gaussian head of the VRNN / SRNN roll-outs: the head Linear is [2,2] -> (mu, raw), x = mu + sd n as for `GmmHead`."""
+
+    sd_beta: float
+    sd_eps: float
 
 
 class CategoricalHead(NamedTuple):

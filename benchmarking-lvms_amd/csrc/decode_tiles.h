@@ -4,6 +4,7 @@
 // mix_sample_kernel (dmol.hip) all end in the same draw, and the two convolutional decoders walk the same gated residual block.
 // Each of these is written once here; a kernel supplies its buffers, its widths and the last line of an epilogue.
 //   mix_pick / logistic_draw   the DMoL draw
+//   gauss_draw                 the draw of the GMM head (behind the same pick) and of the plain Gaussian head
 //   cat_pick                   the categorical draw of K10c's softmax head
 //   tile16 / tile_layer        "16x16 tiles over the waves, product from an LDS operand, + bias, epilogue"
 //   gated_ring_block           one gated residual block on one new frame, with its ring buffer
@@ -47,6 +48,12 @@ __device__ __forceinline__ int mix_pick(const float* p, int K, const float* u) {
 __device__ __forceinline__ float logistic_draw(float loc, float raw, float v, float log_eps) {
   const float x = loc + expf(fmaxf(raw, log_eps)) * (logf(v) - logf(1.f - v));
   return fminf(fmaxf(x, -1.f), 1.f);
+}
+
+// x = mu + sd(raw) * n, n standard normal: sd = softplus_beta(raw) + sd_eps, or raw itself when sd_beta == 0 (the scales are
+// standard deviations already).  No clamp.  The draw of the GMM and Gaussian heads (variational.py:156-195).
+__device__ __forceinline__ float gauss_draw(float mu, float raw, float n, float sd_beta, float sd_eps) {
+  return mu + (sd_beta > 0.f ? softplus_beta(raw, sd_beta, 1.f / sd_beta) + sd_eps : raw) * n;
 }
 
 // ---- the categorical draw (the rule of tests/cat_cases.py::check_draws) ---------------------------------------------------------

@@ -886,7 +886,7 @@ __global__ __launch_bounds__(256) void mix_sample_kernel(const float* __restrict
     if (kind == 0) {
       x = logistic_draw(loc, raw, vv, log_eps);
     } else {
-      x = loc + (sd_beta > 0.f ? softplus_beta(raw, sd_beta, 1.f / sd_beta) + sd_eps : raw) * vv;  // sd_beta == 0: raw IS the sd
+      x = gauss_draw(loc, raw, vv, sd_beta, sd_eps);  // sd_beta == 0: raw IS the sd
     }
   }
   out[f] = x;

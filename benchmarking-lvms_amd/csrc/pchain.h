@@ -1192,6 +1192,21 @@ __device__ __forceinline__ void tile_lstm(const float* X, const float* Wih, int 
   put(hnew, r0, c0, row, col, og * tanhf(c2));
 }
 
+// The three heads of the draw tile (i[DMOLS_I_HEAD]; the head scalars of blvm_hip.h).  p: the head Linear's outputs of one sample.
+//   0 DMoL      p = logits | locations | raw log-scales (num_mix each): Gumbel-max pick with u, clamped logistic draw with v uniform
+//   1 GMM       p = logits | means | raw scales: the same pick, x = mu + sd(raw) n with v standard normal (gauss_draw), no clamp
+//   2 Gaussian  p = (mu, raw scale), no pick and no u: x = mu + sd(raw) n
+// u: the sample's num_mix pick draws (null: the arg-max-logit component); vf: its own draw (null: the location).
+enum : int { DRAW_DMOL = 0, DRAW_GMM = 1, DRAW_GAUSS = 2 };
+struct DrawFields { int kind; float log_eps, sd_beta, sd_eps; };
+__device__ __forceinline__ float dmols_draw(const DrawFields& h, const float* p, int num_mix, const float* u, const float* vf) {
+  if (h.kind == DRAW_GAUSS) return vf != nullptr ? gauss_draw(p[0], p[1], *vf, h.sd_beta, h.sd_eps) : p[0];
+  const int best = mix_pick(p, num_mix, u);
+  float x = p[num_mix + best];
+  if (vf != nullptr) x = h.kind == DRAW_DMOL ? logistic_draw(x, p[2 * num_mix + best], *vf, h.log_eps) : gauss_draw(x, p[2 * num_mix + best], *vf, h.sd_beta, h.sd_eps);
+  return x;
+}
+
 // Sampling from a DMoL head during generation (`VRNN.generate`, blvm/models/vrnn.py:371-434: likelihood(dec) -> sample): a tile =
 // 16 utterances x 4 samples of one frame stack.  dec [B, S*F] (F = 3 * num_mix = 30 head inputs per sample, row-major, polled words:
 // the last decoder layer of this step) -> per sample the head's Linear(F -> F) -> Gumbel-max component pick with u, clamped
@@ -1202,9 +1217,11 @@ __device__ __forceinline__ void tile_lstm(const float* X, const float* Wih, int 
 // multiple of 16 floats, so every 16-byte piece is aligned and lies wholly inside or outside a row).  A sample >= S reads no u, v or
 // head input that is checked, stores no x, and writes 0 into its column of the T16 slab — a consumer polls EVERY word of an operand
 // block, so a pad column left as a sentinel would be a spin until the poll bound.
-template <int NW>
+// fields() -> DrawFields: the head's descriptor fields, asked for by wave 0 in front of its draws (dmols_draw above) and not before, so
+// that none of them is live across the poll and the product.
+template <int NW, class Fields>
 __device__ __forceinline__ void tile_dmol_sample(const float* dec, int ldd, const float* Wl, const float* bl, const float* u, const float* v, int S, int F,
-                                                 int num_mix, float log_eps, const Out& xo, int r0, int s0, int B, float* lds, Poll& pl) {
+                                                 int num_mix, Fields fields, const Out& xo, int r0, int s0, int B, float* lds, Poll& pl) {
   static_assert(NW == 8 || NW == 16, "waves");
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   float* in = lds;               // [16 rows][4 * F]
@@ -1254,14 +1271,12 @@ __device__ __forceinline__ void tile_dmol_sample(const float* dec, int ldd, cons
   }
   __syncthreads();
   if (wave == 0) {
+    const DrawFields h = fields();
     const int rr = lane >> 2, ss = lane & 3, row = r0 + rr, smp = s0 + ss;
     if (row < B && smp < S) {
       const float* p = outp + lane * 32;
       const size_t f = (size_t)row * S + smp;
-      const int best = mix_pick(p, num_mix, u != nullptr ? u + f * num_mix : nullptr);
-      float x = p[num_mix + best];
-      if (v != nullptr) x = logistic_draw(x, p[2 * num_mix + best], v[f], log_eps);
-      put(xo, r0, s0 & ~15, row, smp, x);
+      put(xo, r0, s0 & ~15, row, smp, dmols_draw(h, p, num_mix, u != nullptr ? u + f * num_mix : nullptr, v != nullptr ? v + f : nullptr));
     } else if (row < B) {
       put_t16(xo, r0, s0 & ~15, row, smp, 0.f);  // a pad column of the operand slab: the next step's first link polls it
     }
@@ -1321,9 +1336,10 @@ enum : int { GRUB_D0_16, GRUB_D1_16, GRUB_W0, GRUB_W1, GRUB_G_IN, GRUB_RG, GRUB_
              GRUB_DGH, GRUB_DGH16, GRUB_GA, GRUB_G_OUT, GRUB_G_ADD, GRUB_LD_H = 0, GRUB_LD_GADD = 1, GRUB_I_R = 0, GRUB_I_GEMM_FROM = 1,
              GRUB_I_GATES_TO = 2, GRUB_I_GIN_FROM = 3 };
 // K_DMOLS (tile_dmol_sample; ct counts tiles of 4 samples, Sp / 4 of them): dec (row-major, polled words, ld[DMOLS_LD_DEC] = its padded
-// row length), head W [F,F], head b, u, v, x row-major | T16 (n16 = Sp / 16)
+// row length), head W [F,F], head b, u, v, x row-major | T16 (n16 = Sp / 16).  i: S, F, num_mix, the head kind (dmols_draw: 0 DMoL
+// F = 3 num_mix, 1 GMM F = 3 num_mix, 2 Gaussian F = 2, num_mix = 0 and no u); f: log_eps (kind 0), sd_beta and sd_eps (kinds 1, 2)
 enum : int { DMOLS_DEC, DMOLS_W, DMOLS_B, DMOLS_U, DMOLS_V, DMOLS_X, DMOLS_X16, DMOLS_LD_DEC = 0, DMOLS_I_S = 0, DMOLS_I_F = 1, DMOLS_I_NMIX = 2,
-             DMOLS_F_LOG_EPS = 0 };
+             DMOLS_I_HEAD = 3, DMOLS_F_LOG_EPS = 0, DMOLS_F_SD_BETA = 1, DMOLS_F_SD_EPS = 2 };
 // K_GRUS (tile_gru_seq; recurrence step j = s): H16 (state entering the step), Whh (T16), b_hh, xg [T,B,3R] (time indexed), lens, h_prev
 // row-major, h_next row-major | T16, out (time indexed), gates, ghn
 enum : int { GRUS_H16, GRUS_WHH, GRUS_BHH, GRUS_XG, GRUS_LENS, GRUS_HPREV, GRUS_HNEXT, GRUS_HNEXT16, GRUS_OUT, GRUS_RG, GRUS_UG, GRUS_NG, GRUS_GHN,

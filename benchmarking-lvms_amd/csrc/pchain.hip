@@ -379,8 +379,10 @@ __global__ __launch_bounds__(NW * 64, 1) void pchain_kernel(const int* __restric
             const int S = d.w<RD_I + DMOLS_I_S>(), F = d.w<RD_I + DMOLS_I_F>(), nmix = d.w<RD_I + DMOLS_I_NMIX>();
             for (int tk = 0; tk < nt; ++tk) {
               const int trc = d.tile(tk);
-              tile_dmol_sample<NW>(d.p<DMOLS_DEC>(s), ld0, d.base<DMOLS_W>(), d.base<DMOLS_B>(), d.p<DMOLS_U>(s), d.p<DMOLS_V>(s), S, F, nmix, d.f<DMOLS_F_LOG_EPS>(), o,
-                                   trc & 0xffff, (trc >> 16) * 4, B, red0, pl);
+              // the head's fields are read at the draw (wave 0, after the product): nothing of them is live before
+              tile_dmol_sample<NW>(d.p<DMOLS_DEC>(s), ld0, d.base<DMOLS_W>(), d.base<DMOLS_B>(), d.p<DMOLS_U>(s), d.p<DMOLS_V>(s), S, F, nmix,
+                                   [&] { return DrawFields{d.w<RD_I + DMOLS_I_HEAD>(), d.f<DMOLS_F_LOG_EPS>(), d.f<DMOLS_F_SD_BETA>(), d.f<DMOLS_F_SD_EPS>()}; },
+                                   o, trc & 0xffff, (trc >> 16) * 4, B, red0, pl);
             }
           } break;
           default: break;

@@ -14,6 +14,22 @@ namespace blvm {
 namespace pchain {
 
 constexpr int kDmolF = 30, kDmolK = 10;  // DMoL head: 3 * num_mix parameters per sample, num_mix
+// The head of the draw tile as the plans see it (pchain.h dmols_draw): F head inputs per sample (the last decoder layer is S F wide,
+// the head Linear [F,F]), K pick draws per sample (the u stream; 0: none).  The default is the DMoL head of every program so far.
+struct DrawPlan { int kind = DRAW_DMOL, F = kDmolF, K = kDmolK; float sd_beta = 0.f, sd_eps = 0.f; };
+// A caller's head (the five scalars of blvm_hip.h), checked: null and *dp unless it is one the tile does not draw — the kind
+// unknown, another count than 10 components where there is a pick, a negative sd_beta.
+inline const char* draw_plan(int kind, int num_mix, float sd_beta, float sd_eps, DrawPlan* dp) {
+  if (kind != DRAW_DMOL && kind != DRAW_GMM && kind != DRAW_GAUSS) return "unknown head kind (0 DMoL, 1 GMM, 2 Gaussian)";
+  if (kind != DRAW_GAUSS && num_mix != kDmolK) return "the mixture heads have 10 components";
+  if (!(sd_beta >= 0.f)) return "head_sd_beta must not be negative";
+  if (kind == DRAW_GAUSS) *dp = DrawPlan{DRAW_GAUSS, 2, 0, sd_beta, sd_eps};
+  else if (kind == DRAW_GMM) *dp = DrawPlan{DRAW_GMM, kDmolF, kDmolK, sd_beta, sd_eps};
+  else *dp = DrawPlan{};
+  return nullptr;
+}
+// the u and v streams a head takes: a pick's u comes with v (both null: the mode), the Gaussian head has no u
+inline bool draw_streams_ok(const DrawPlan& dp, const float* u, const float* v) { return dp.K > 0 ? (u == nullptr) == (v == nullptr) : u == nullptr; }
 
 // a piece of the scratch, in floats from its base, and an arena that records the pieces it hands out (in ascending order)
 struct Region { const char* name; size_t off, floats; };
@@ -108,6 +124,7 @@ struct Tail {
   const float* D16;  // the operand: T slabs [rows, H] T16
   int ld_a, n16;     // the last layer's ld[LIN_LD_A] and n16[N16_OUT], as each model states them (neither is read: A is H wide, no T16 output)
   const float *W, *bias; float slope; float *DEC, *X16; const float *lik_w, *lik_b, *u, *v; float* x_out; float log_eps;
+  DrawPlan head = {};  // (sp is stack_pad(S, head.F))
 };
 inline void add_tail(Builder& bld, const Deal& d, const StackPad& sp, const Tail& t) {
   const int S = sp.S, Sp = sp.Sp, Np = sp.Np;
@@ -115,9 +132,10 @@ inline void add_tail(Builder& bld, const Deal& d, const StackPad& sp, const Tail
   add_lin(bld, d.T, {.A = {t.D16, d.xH}, .ld_a = t.ld_a, .W = t.W, .bias = t.bias, .K = d.H, .ct = Np / 16, .flags = DF_RELU | DF_RM_SC1, .slope = t.slope,
                      .orm = {t.DEC, sF}, .ldo = Np, .n16 = t.n16, .nwg = range_for(Np / 16 * d.rt, d.cus)});
   Operands o;
-  o.p[DMOLS_DEC] = {t.DEC, sF}; o.p[DMOLS_W] = t.lik_w; o.p[DMOLS_B] = t.lik_b; o.p[DMOLS_U] = {t.u, (long)d.B * S * kDmolK}; o.p[DMOLS_V] = {t.v, (long)d.B * S};
+  o.p[DMOLS_DEC] = {t.DEC, sF}; o.p[DMOLS_W] = t.lik_w; o.p[DMOLS_B] = t.lik_b; o.p[DMOLS_U] = {t.u, (long)d.B * S * t.head.K}; o.p[DMOLS_V] = {t.v, (long)d.B * S};
   o.p[DMOLS_X] = {t.x_out, S}; o.p[DMOLS_X16] = {t.X16 + xS, xS}; o.ld[DMOLS_LD_DEC] = Np; o.ld[LD_OUT] = d.T * S; o.n16[N16_OUT] = Sp / 16; o.i[DMOLS_I_S] = S;
-  o.i[DMOLS_I_F] = kDmolF; o.i[DMOLS_I_NMIX] = kDmolK; o.f[DMOLS_F_LOG_EPS] = t.log_eps;
+  o.i[DMOLS_I_F] = t.head.F; o.i[DMOLS_I_NMIX] = t.head.K; o.i[DMOLS_I_HEAD] = t.head.kind; o.f[DMOLS_F_LOG_EPS] = t.log_eps;
+  o.f[DMOLS_F_SD_BETA] = t.head.sd_beta; o.f[DMOLS_F_SD_EPS] = t.head.sd_eps;
   add_desc(bld, K_DMOLS, Sp / 4, 0, range_for(Sp / 4 * d.rt, d.r_main), 16, 0, 0, d.T, o);
 }
 
@@ -149,8 +167,8 @@ inline void add_gru_cell(Builder& bld, const Deal& d, int R, const GruCell& g) {
 // =================================================================================================================================
 enum VrnnPack : int { VP_ENC0, VP_ENC1, VP_ENC2, VP_PRIOR0, VP_PRIOR1, VP_PRIOR2, VP_PRIOR_H, VP_PHI0, VP_PHI1, VP_PHI2, VP_PHI3, VP_WIH, VP_WHH, VP_DEC0, VP_DEC1, VP_DEC2 };
 // (both entry points: the per-CU blvm_vrnn_decode takes S % 16 == 0 only, where nothing is staged)
-inline PackTable vrnn_pack_table(const BlvmVrnnDecodeWeights& w, const BlvmVrnnWeights& c, int S, int H, int Z, int R) {
-  const StackPad sp = stack_pad(S, kDmolF);
+inline PackTable vrnn_pack_table(const BlvmVrnnDecodeWeights& w, const BlvmVrnnWeights& c, int S, int H, int Z, int R, int F = kDmolF) {
+  const StackPad sp = stack_pad(S, F);
   return pack_table(sp,
                     {{"enc0", w.enc_w[0], sp.Sp, H, sp.Sp}, {"enc1", w.enc_w[1], H, H, H}, {"enc2", w.enc_w[2], H, H, H},
                      {"prior0", c.prior_w[0], R, H, R}, {"prior1", c.prior_w[1], H, H, H}, {"prior2", c.prior_w[2], H, H, H},
@@ -174,11 +192,11 @@ struct VrnnBufs {
   size_t X16, E16[2], CAT16, H16, HS, P16[3], GHb, Z16, F16[3], DC16, D16[2], DEC, polled_end, dummyZ, dummyR, end;
   std::vector<Region> regions;
 };
-inline VrnnBufs vrnn_generate_layout(size_t base, int T, int B, int S, int H, int Z, int R) {
+inline VrnnBufs vrnn_generate_layout(size_t base, int T, int B, int S, int H, int Z, int R, int F = kDmolF) {
   VrnnBufs b{};
   RegionArena ar(base);
   const size_t rows = (size_t)((B + 15) / 16) * 16, m = (size_t)T * rows, X = H;
-  const StackPad sp = stack_pad(S, kDmolF);
+  const StackPad sp = stack_pad(S, F);
   b.X16 = ar.take("X16", (m + rows) * sp.Sp);
   b.E16[0] = ar.take("E16.0", m * H); b.E16[1] = ar.take("E16.1", m * H);
   b.CAT16 = ar.take("CAT16", m * (X + H));
@@ -211,7 +229,7 @@ inline std::vector<Prefill> vrnn_generate_prefills(const VrnnBufs& b, int S, int
 //   decoder and draw: K_LIN x2, the tail                                    DC16[s] -> D16[0..1][s] -> ...
 inline void vrnn_generate_program(Builder& bld, int ot, int cus_all, int tune, const BlvmVrnnDecodeWeights* w, const PackTable& p, const VrnnBufs& b, float* sc,
                                   const float* eps, const float* u, const float* v, float* x_out, int T, int B, int S, int H, int Z, int R, float sd_eps,
-                                  float slope, float log_eps) {
+                                  float slope, float log_eps, const DrawPlan& head = {}) {
   const BlvmVrnnWeights* c = w->cell;
   const int ctH = H / 16, ctR = R / 16, X = H;
   Deal d = deal(T, B, H, cus_all, 3 * ctR * ((B + 15) / 16));
@@ -260,7 +278,7 @@ inline void vrnn_generate_program(Builder& bld, int ot, int cus_all, int tune, c
   add_lin(bld, T, layer({sc + b.DC16, xD}, VP_DEC0, H + R, w->dec_b[0], slope, {sc + b.D16[0], xH}, ctH));
   add_lin(bld, T, layer({sc + b.D16[0], xH}, VP_DEC1, H, w->dec_b[1], slope, {sc + b.D16[1], xH}, ctH));
   add_tail(bld, d, p.sp, {.D16 = sc + b.D16[1], .ld_a = 0, .n16 = 0, .W = W(VP_DEC2), .bias = p.bias, .slope = slope, .DEC = sc + b.DEC, .X16 = sc + b.X16,
-                          .lik_w = w->lik_w, .lik_b = w->lik_b, .u = u, .v = v, .x_out = x_out, .log_eps = log_eps});
+                          .lik_w = w->lik_w, .lik_b = w->lik_b, .u = u, .v = v, .x_out = x_out, .log_eps = log_eps, .head = head});
 }
 
 // =================================================================================================================================
@@ -269,8 +287,8 @@ inline void vrnn_generate_program(Builder& bld, int ot, int cus_all, int tune, c
 //         writes into slab s+2; also the hidden projection's operand of step s+1);  DC16  cat[z_s | d_s] (head link, GRU link)
 // =================================================================================================================================
 enum SrnnPack : int { SP_ENC0, SP_ENC1, SP_ENC2, SP_WIH, SP_WHH, SP_PRIOR0, SP_PRIOR1, SP_PRIOR2, SP_PRIOR_H, SP_DEC0, SP_DEC1, SP_DEC2 };
-inline PackTable srnn_pack_table(const BlvmSrnnDecodeWeights& w, const BlvmSrnnWeights& c, int S, int H, int Z, int R) {
-  const StackPad sp = stack_pad(S, kDmolF);
+inline PackTable srnn_pack_table(const BlvmSrnnDecodeWeights& w, const BlvmSrnnWeights& c, int S, int H, int Z, int R, int F = kDmolF) {
+  const StackPad sp = stack_pad(S, F);
   return pack_table(sp,
                     {{"enc0", w.enc_w[0], sp.Sp, H, sp.Sp}, {"enc1", w.enc_w[1], H, H, H}, {"enc2", w.enc_w[2], H, H, H},
                      {"wih", w.gru_wih, H, 3 * R, H}, {"whh", w.gru_whh, R, 3 * R, R},
@@ -284,11 +302,11 @@ struct SrnnBufs {
   size_t X16, E16[2], ENC16, CP16, DS, GHb, P16[3], DC16, D16[2], DEC, polled_end, ZS, dummyZ, dummyR, end;
   std::vector<Region> regions;
 };
-inline SrnnBufs srnn_generate_layout(size_t base, int T, int B, int S, int H, int Z, int R) {
+inline SrnnBufs srnn_generate_layout(size_t base, int T, int B, int S, int H, int Z, int R, int F = kDmolF) {
   SrnnBufs b{};
   RegionArena ar(base);
   const size_t rows = (size_t)((B + 15) / 16) * 16, m = (size_t)T * rows;
-  const StackPad sp = stack_pad(S, kDmolF);
+  const StackPad sp = stack_pad(S, F);
   b.X16 = ar.take("X16", (m + rows) * sp.Sp);
   b.E16[0] = ar.take("E16.0", m * H); b.E16[1] = ar.take("E16.1", m * H); b.ENC16 = ar.take("ENC16", m * H);
   b.CP16 = ar.take("CP16", (m + 2 * rows) * (R + Z));
@@ -324,7 +342,7 @@ inline std::vector<Prefill> srnn_generate_prefills(const SrnnBufs& b, int B, int
 // Every link of this program carries the caller's slope and states its operand's width in ld[LIN_LD_A].
 inline void srnn_generate_program(Builder& bld, int ot, int cus_all, int tune, const BlvmSrnnDecodeWeights* w, const PackTable& p, const SrnnBufs& b, float* sc,
                                   const float* eps, const float* u, const float* v, float* x_out, int T, int B, int S, int H, int Z, int R, float sd_eps,
-                                  float slope, float log_eps) {
+                                  float slope, float log_eps, const DrawPlan& head = {}) {
   const BlvmSrnnWeights* c = w->chain;
   const int ctH = H / 16, ctZ = Z / 16, ctR = R / 16, nCP = (R + Z) / 16, nDC = (Z + R) / 16;
   const Deal d = deal(T, B, H, cus_all, 3 * ctR * ((B + 15) / 16));
@@ -350,7 +368,7 @@ inline void srnn_generate_program(Builder& bld, int ot, int cus_all, int tune, c
   add_lin(bld, T, {.A = {sc + b.D16[0], xH}, .ld_a = H, .W = W(SP_DEC1), .bias = w->dec_b[1], .K = H, .ct = ctH, .flags = DF_RELU, .slope = slope,
                    .o16 = {sc + b.D16[1], xH}, .n16 = ctH, .nwg = d.rH});
   add_tail(bld, d, p.sp, {.D16 = sc + b.D16[1], .ld_a = H, .n16 = 0, .W = W(SP_DEC2), .bias = p.bias, .slope = slope, .DEC = sc + b.DEC, .X16 = sc + b.X16,
-                          .lik_w = w->lik_w, .lik_b = w->lik_b, .u = u, .v = v, .x_out = x_out, .log_eps = log_eps});
+                          .lik_w = w->lik_w, .lik_b = w->lik_b, .u = u, .v = v, .x_out = x_out, .log_eps = log_eps, .head = head});
 }
 
 }  // namespace pchain

@@ -29,6 +29,8 @@ struct VDArgs {
   float *x_out, *h_out;
   int T, B, S, H, Z, R;
   float sd_eps, beta, slope, log_eps;
+  int head;                        // pchain::DRAW_DMOL | DRAW_GMM (pchain.h): what follows the component pick
+  float head_sd_beta, head_sd_eps;  // DRAW_GMM: sd = softplus_beta(raw) + eps of the picked component
 };
 
 __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : x * slope; }
@@ -382,14 +384,15 @@ __global__ __launch_bounds__(VD_NW * 64) void vrnn_decode_kernel(VDArgs a) {
           for (int r = 0; r < 4; ++r) sPar[((4 * q + r) * VD_CHUNK + sm) * 32 + ct * 16 + cc] = c[r] + bv;
         }
         __syncthreads();
-        if (tid < VD_ROWS * VD_CHUNK) {  // Gumbel-max component pick + clamped logistic draw (decode_tiles.h), the draws from registers
+        if (tid < VD_ROWS * VD_CHUNK) {  // Gumbel-max component pick + clamped logistic or Gaussian draw (decode_tiles.h), the draws from registers
           const int r = tid / VD_CHUNK, sm = tid - r * VD_CHUNK, s_idx = ch * VD_CHUNK + sm;
           if (b0 + r < B) {
             const float* p = sPar + tid * 32;
             const size_t f = ((size_t)t * B + b0 + r) * S + s_idx;
             const int best = mix_pick_from<VD_K>(p, VD_K, a.u != nullptr, [&](int m) { return uu[m]; });
             float x = p[VD_K + best];
-            if (a.v != nullptr) x = logistic_draw(x, p[2 * VD_K + best], vv, a.log_eps);
+            if (a.v != nullptr)
+              x = a.head == pchain::DRAW_GMM ? gauss_draw(x, p[2 * VD_K + best], vv, a.head_sd_beta, a.head_sd_eps) : logistic_draw(x, p[2 * VD_K + best], vv, a.log_eps);
             a.x_out[((size_t)(b0 + r) * a.T + t) * S + s_idx] = x;
             sX[r * ldS + s_idx] = x;
           }
@@ -420,9 +423,9 @@ size_t vd_lds_bytes(int S, int H, int Z, int R) {
 using namespace blvm;
 
 // sizes only: the pack table of no weights
-static pchain::PackTable vd_pack_sizes(int S, int H, int Z, int R) {
+static pchain::PackTable vd_pack_sizes(int S, int H, int Z, int R, int F = pchain::kDmolF) {
   const BlvmVrnnWeights c{};
-  return pchain::vrnn_pack_table(BlvmVrnnDecodeWeights{}, c, S, H, Z, R);
+  return pchain::vrnn_pack_table(BlvmVrnnDecodeWeights{}, c, S, H, Z, R, F);
 }
 
 extern "C" size_t blvm_vrnn_decode_scratch_floats(int S, int H, int Z, int R) {
@@ -430,21 +433,35 @@ extern "C" size_t blvm_vrnn_decode_scratch_floats(int S, int H, int Z, int R) {
   return vd_pack_sizes(S, H, Z, R).total;
 }
 
-extern "C" int blvm_vrnn_decode(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u,
-                                const float* v, int T, int B, int S, int H, int Z, int R, int num_mix, float sd_eps, float slope,
-                                float log_eps, float* x_out, float* h_out, float* scratch, void* stream_) {
+// the per-CU kernel's own limits: its op program has 32 slots, a wave keeps at most 4 tiles of the new state, the LDS plan 160 KB
+static bool vd_ops_fit(int S) { return 14 + 2 * (S / VD_CHUNK) <= 32; }
+static bool vd_state_fits(int R) { return (R / 16 + VD_NW - 1) / VD_NW <= 4; }
+constexpr size_t kVdLdsMax = 160 * 1024;
+
+extern "C" int blvm_vrnn_decode_applies(int S, int H, int Z, int R) {
+  return S > 0 && H > 0 && Z > 0 && R > 0 && S % 16 == 0 && H % 16 == 0 && Z % 16 == 0 && R % 16 == 0 && vd_ops_fit(S) && vd_state_fits(R) &&
+         vd_lds_bytes(S, H, Z, R) <= kVdLdsMax;
+}
+
+extern "C" int blvm_vrnn_decode_head(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u, const float* v, int T, int B,
+                                     int S, int H, int Z, int R, int head_kind, int num_mix, float log_eps, float head_sd_beta, float head_sd_eps, float sd_eps,
+                                     float slope, float* x_out, float* h_out, float* scratch, void* stream_) {
   hipStream_t s = static_cast<hipStream_t>(stream_);
   BLVM_REQUIRE(w && w->cell && x0 && eps && x_out && scratch, "vrnn_decode: null pointer");
   BLVM_REQUIRE(T >= 0 && B > 0, "vrnn_decode: bad T=%d B=%d", T, B);
   BLVM_REQUIRE(S % 16 == 0 && H % 16 == 0 && Z % 16 == 0 && R % 16 == 0 && S > 0 && H > 0 && Z > 0 && R > 0,
                "vrnn_decode: S, H, Z, R must be positive multiples of 16 (got %d, %d, %d, %d)", S, H, Z, R);
-  BLVM_REQUIRE(num_mix == VD_K, "vrnn_decode: the DMoL head has %d components", VD_K);
-  BLVM_REQUIRE(14 + 2 * (S / VD_CHUNK) <= 32, "vrnn_decode: frame stacks of more than %d samples are not supported", 9 * VD_CHUNK);
-  BLVM_REQUIRE((R / 16 + VD_NW - 1) / VD_NW <= 4, "vrnn_decode: recurrent size %d too large", R);
+  pchain::DrawPlan dp;
+  const char* const why = pchain::draw_plan(head_kind, num_mix, head_sd_beta, head_sd_eps, &dp);
+  BLVM_REQUIRE(why == nullptr, "vrnn_decode: %s (kind %d, num_mix %d, head_sd_beta %g)", why, head_kind, num_mix, (double)head_sd_beta);
+  BLVM_REQUIRE(dp.kind != pchain::DRAW_GAUSS, "vrnn_decode: the per-CU form draws the mixture heads only (kind 0 DMoL, 1 GMM), not the Gaussian head (kind 2)");
+  static_assert(VD_F == pchain::kDmolF && VD_K == pchain::kDmolK, "the per-CU kernel is built for the 10-component heads");
+  BLVM_REQUIRE(vd_ops_fit(S), "vrnn_decode: frame stacks of more than %d samples are not supported", 9 * VD_CHUNK);
+  BLVM_REQUIRE(vd_state_fits(R), "vrnn_decode: recurrent size %d too large", R);
   BLVM_REQUIRE((u == nullptr) == (v == nullptr), "vrnn_decode: u and v are given together (both NULL: the mode)");
   BLVM_REQUIRE(aligned16(scratch), "vrnn_decode: scratch must be 16-byte aligned");
   const size_t lds = vd_lds_bytes(S, H, Z, R);
-  BLVM_REQUIRE(lds <= 160 * 1024, "vrnn_decode: S=%d H=%d Z=%d R=%d need %zu bytes of LDS (> 160 KB)", S, H, Z, R, lds);
+  BLVM_REQUIRE(lds <= kVdLdsMax, "vrnn_decode: S=%d H=%d Z=%d R=%d need %zu bytes of LDS (> 160 KB)", S, H, Z, R, lds);
   if (T == 0) return BLVM_OK;
   const BlvmVrnnWeights* c = w->cell;
   using namespace pchain;
@@ -463,10 +480,17 @@ extern "C" int blvm_vrnn_decode(const BlvmVrnnDecodeWeights* w, const float* x0,
   a.x0 = x0; a.h0 = h0; a.eps = eps; a.u = u; a.v = v; a.x_out = x_out; a.h_out = h_out;
   a.T = T; a.B = B; a.S = S; a.H = H; a.Z = Z; a.R = R;
   a.sd_eps = sd_eps; a.beta = softplus_beta_of(sd_eps); a.slope = slope; a.log_eps = log_eps;
+  a.head = dp.kind; a.head_sd_beta = dp.sd_beta; a.head_sd_eps = dp.sd_eps;
   BLVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(vrnn_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(vrnn_decode_kernel, dim3((unsigned)((B + VD_ROWS - 1) / VD_ROWS)), dim3(VD_NW * 64), lds, s, a);
   BLVM_CHECK_LAUNCH("vrnn_decode");
   return BLVM_OK;
+}
+
+extern "C" int blvm_vrnn_decode(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u,
+                                const float* v, int T, int B, int S, int H, int Z, int R, int num_mix, float sd_eps, float slope,
+                                float log_eps, float* x_out, float* h_out, float* scratch, void* stream) {
+  return blvm_vrnn_decode_head(w, x0, h0, eps, u, v, T, B, S, H, Z, R, pchain::DRAW_DMOL, num_mix, log_eps, 0.f, 0.f, sd_eps, slope, x_out, h_out, scratch, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -476,35 +500,47 @@ extern "C" int blvm_vrnn_decode(const BlvmVrnnDecodeWeights* w, const float* x0,
 // The pack table (shared with the per-CU form), the layout of the scratch and the descriptor list are in rollout_plan.h, which
 // tests/host/vrnn_generate_plan_test.hip replays on the host.
 // ---------------------------------------------------------------------------------------------------------------------------------
+extern "C" size_t blvm_vrnn_generate_scratch_floats_head(int T, int B, int S, int H, int Z, int R, int head_kind) {
+  pchain::DrawPlan dp;
+  if (T <= 0 || B <= 0 || S <= 0 || H <= 0 || Z <= 0 || R <= 0 || pchain::draw_plan(head_kind, pchain::kDmolK, 0.f, 0.f, &dp) != nullptr) return 0;
+  return pchain::vrnn_generate_layout(vd_pack_sizes(S, H, Z, R, dp.F).total, T, B, S, H, Z, R, dp.F).end;
+}
 extern "C" size_t blvm_vrnn_generate_scratch_floats(int T, int B, int S, int H, int Z, int R) {
-  if (T <= 0 || B <= 0 || S <= 0 || H <= 0 || Z <= 0 || R <= 0) return 0;
-  return pchain::vrnn_generate_layout(vd_pack_sizes(S, H, Z, R).total, T, B, S, H, Z, R).end;
+  return blvm_vrnn_generate_scratch_floats_head(T, B, S, H, Z, R, pchain::DRAW_DMOL);
 }
 
-extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u,
-                                  const float* v, int T, int B, int S, int H, int Z, int R, int num_mix, float sd_eps, float slope,
-                                  float log_eps, float* x_out, float* h_out, float* scratch, void* stream_) {
+extern "C" int blvm_vrnn_generate_head(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u, const float* v, int T, int B,
+                                       int S, int H, int Z, int R, int head_kind, int num_mix, float log_eps, float head_sd_beta, float head_sd_eps, float sd_eps,
+                                       float slope, float* x_out, float* h_out, float* scratch, void* stream_) {
   using namespace pchain;
   hipStream_t s = static_cast<hipStream_t>(stream_);
   BLVM_REQUIRE(w && w->cell && x0 && eps && x_out && scratch, "vrnn_generate: null pointer");
   BLVM_REQUIRE(T >= 0 && B > 0 && B <= kPchainCarveMaxB, "vrnn_generate: bad T=%d B=%d (at most %d utterances)", T, B, kPchainCarveMaxB);
   BLVM_REQUIRE(H % 16 == 0 && Z % 16 == 0 && R % 16 == 0 && S > 0 && H > 0 && Z > 0 && R > 0,
                "vrnn_generate: S must be positive and H, Z, R positive multiples of 16 (got %d, %d, %d, %d)", S, H, Z, R);
-  BLVM_REQUIRE(num_mix == VD_K, "vrnn_generate: the DMoL head has %d components", VD_K);
-  BLVM_REQUIRE((u == nullptr) == (v == nullptr), "vrnn_generate: u and v are given together (both NULL: the mode)");
+  DrawPlan dp;
+  const char* const why = draw_plan(head_kind, num_mix, head_sd_beta, head_sd_eps, &dp);
+  BLVM_REQUIRE(why == nullptr, "vrnn_generate: %s (kind %d, num_mix %d, head_sd_beta %g)", why, head_kind, num_mix, (double)head_sd_beta);
+  BLVM_REQUIRE(draw_streams_ok(dp, u, v), "vrnn_generate: u and v are given together (both NULL: the mode); the Gaussian head takes no u");
   BLVM_REQUIRE(aligned16(scratch), "vrnn_generate: scratch must be 16-byte aligned");
   if (T == 0) return BLVM_OK;
   // (unlike the SRNN and LSTM roll-outs this entry point never required device_cus() >= 32: kept so)
-  PackTable p = vrnn_pack_table(*w, *w->cell, S, H, Z, R);
-  const VrnnBufs b = vrnn_generate_layout(p.total, T, B, S, H, Z, R);
+  PackTable p = vrnn_pack_table(*w, *w->cell, S, H, Z, R, dp.F);
+  const VrnnBufs b = vrnn_generate_layout(p.total, T, B, S, H, Z, R, dp.F);
   float* const sc = scratch;
   const OpType ot = pchain_optype(B);
   BLVM_TRY(stage_and_pack(p, ot, sc, s));
   Builder bld;
-  vrnn_generate_program(bld, ot, device_cus(), pchain_tune(), w, p, b, sc, eps, u, v, x_out, T, B, S, H, Z, R, sd_eps, slope, log_eps);
+  vrnn_generate_program(bld, ot, device_cus(), pchain_tune(), w, p, b, sc, eps, u, v, x_out, T, B, S, H, Z, R, sd_eps, slope, log_eps, dp);
   const float* const srcs[] = {x0, h0};
   BLVM_TRY(fill_and_prefill(b.X16, b.polled_end, vrnn_generate_prefills(b, S, R), srcs, B, sc, s));
   BLVM_TRY(pchain_launch(bld, "vrnn_generate", s));
   if (h_out) BLVM_HIP(hipMemcpyAsync(h_out, sc + b.HS + (size_t)T * B * R, sizeof(float) * (size_t)B * R, hipMemcpyDeviceToDevice, s));
   return BLVM_OK;
+}
+
+extern "C" int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u,
+                                  const float* v, int T, int B, int S, int H, int Z, int R, int num_mix, float sd_eps, float slope,
+                                  float log_eps, float* x_out, float* h_out, float* scratch, void* stream) {
+  return blvm_vrnn_generate_head(w, x0, h0, eps, u, v, T, B, S, H, Z, R, pchain::DRAW_DMOL, num_mix, log_eps, 0.f, 0.f, sd_eps, slope, x_out, h_out, scratch, stream);
 }

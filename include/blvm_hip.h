@@ -407,6 +407,40 @@ int blvm_vrnn_generate(const BlvmVrnnDecodeWeights* w, const float* x0, const fl
                        const float* v, int T, int B, int S, int H, int Z, int R, int num_mix, float sd_eps, float slope,
                        float log_eps, float* x_out, float* h_out, float* scratch, void* stream);
 
+/* The head of a roll-out's draw: what the last link of every step does with the head Linear's outputs of one sample.  The header's
+ * structs hold pointers only (the bindings are generated from them), so a head is five scalars, always in this order:
+ *   head_kind, num_mix, log_eps, head_sd_beta, head_sd_eps
+ *   kind 0  DMoL      outputs logits | locations | raw log-scales (num_mix each): the draw of blvm_mix_sample kind 0 (log_eps);
+ *                     the two head_sd_* are not read
+ *   kind 1  GMM       outputs logits | means | raw scales (num_mix each): the draw of blvm_mix_sample kind 1, sd = softplus_beta(raw)
+ *                     + head_sd_eps with beta = head_sd_beta (0: raw is the sd); u as for kind 0, v [T,B,S] STANDARD NORMALS; no clamp
+ *   kind 2  Gaussian  outputs (mean, raw scale): x = mean + sd v with the same sd, no component pick: u must be NULL, v [T,B,S]
+ *                     standard normals or NULL (x = the mean); num_mix and log_eps are not read
+ * Kinds 0 and 1 take u and v together (both NULL: the arg-max-logit component's location).  With F = 3 num_mix (kinds 0, 1) or F = 2
+ * (kind 2): the last decoder layer is [S*F, H], its bias [S*F], lik_w [F,F], lik_b [F], and where S is no multiple of 16 the padded
+ * row of the last layer is Np = 16 ceil(S F / 16) floats.  Refused with BLVM_EINVAL before any launch or write: a kind other than
+ * 0, 1, 2; num_mix != 10 for kinds 0 and 1; head_sd_beta < 0; u given for kind 2.
+ *
+ * K1c with a head: blvm_vrnn_decode and blvm_vrnn_generate are the kind-0 cases (0, num_mix, log_eps, 0, 0) of these calls, which
+ * take the same arguments in the same layouts with the head in place of `num_mix, log_eps` (sd_eps and slope stay the cell's and the
+ * MLPs').  The per-CU form blvm_vrnn_decode_head draws kinds 0 and 1 (kind 2 is refused, as every refusal before any launch or
+ * write); its scratch does not depend on the head: blvm_vrnn_decode_scratch_floats.  The whole-chip form draws all three; its scratch
+ * depends on F: blvm_vrnn_generate_scratch_floats_head (0 for a kind it does not draw).  Caller-owned buffers as for the calls above:
+ * every word of scratch that is read is written first by the same call, results do not depend on the prior contents of scratch or of
+ * the outputs, and nothing outside x_out, h_out and scratch is written. */
+size_t blvm_vrnn_generate_scratch_floats_head(int T, int B, int S, int H, int Z, int R, int head_kind);
+/* 1 when the per-CU form takes these widths (multiples of 16 within its op-program, state-tile and LDS limits), else 0: what a caller
+ * asks before it draws noise for a batch above blvm_pchain_max_batch().  Host arithmetic, no GPU call. */
+int blvm_vrnn_decode_applies(int S, int H, int Z, int R);
+int blvm_vrnn_generate_head(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u,
+                            const float* v, int T, int B, int S, int H, int Z, int R, int head_kind, int num_mix, float log_eps,
+                            float head_sd_beta, float head_sd_eps, float sd_eps, float slope, float* x_out, float* h_out,
+                            float* scratch, void* stream);
+int blvm_vrnn_decode_head(const BlvmVrnnDecodeWeights* w, const float* x0, const float* h0, const float* eps, const float* u,
+                          const float* v, int T, int B, int S, int H, int Z, int R, int head_kind, int num_mix, float log_eps,
+                          float head_sd_beta, float head_sd_eps, float sd_eps, float slope, float* x_out, float* h_out,
+                          float* scratch, void* stream);
+
 /* number of floats of `reserve` (activations kept for BPTT) / `workspace` (backward scratch). */
 size_t blvm_vrnn_reserve_floats(int Tp, int B, int X, int H, int Z, int R);
 size_t blvm_vrnn_bwd_workspace_floats(int Tp, int B, int X, int H, int Z, int R);
@@ -597,6 +631,15 @@ size_t blvm_srnn_generate_scratch_floats(int T, int B, int S, int H, int Z, int 
 int blvm_srnn_generate(const BlvmSrnnDecodeWeights* w, const float* x0, const float* d0, const float* z0, const float* eps,
                        const float* u, const float* v, int T, int B, int S, int H, int Z, int R, int num_mix, float sd_eps,
                        float slope, float log_eps, float* x_out, float* d_out, float* z_out, float* scratch, void* stream);
+/* K3c with a head (the five scalars described at blvm_vrnn_generate_head: all three kinds, the same refusals before any launch or
+ * write): blvm_srnn_generate is the kind-0 case (0, num_mix, log_eps, 0, 0).  The same arguments and layouts with the head in place
+ * of `num_mix, log_eps`; dec_w[2] [S*F,H], lik_w [F,F], lik_b [F]; the scratch depends on F (0 for a kind that is not drawn).
+ * Caller-owned buffers: results do not depend on the prior contents of scratch or of the outputs; nothing else is written. */
+size_t blvm_srnn_generate_scratch_floats_head(int T, int B, int S, int H, int Z, int R, int head_kind);
+int blvm_srnn_generate_head(const BlvmSrnnDecodeWeights* w, const float* x0, const float* d0, const float* z0, const float* eps,
+                            const float* u, const float* v, int T, int B, int S, int H, int Z, int R, int head_kind, int num_mix,
+                            float log_eps, float head_sd_beta, float head_sd_eps, float sd_eps, float slope, float* x_out,
+                            float* d_out, float* z_out, float* scratch, void* stream);
 
 /* K4c  Sampling from LSTMAudio: every step of every utterance in ONE persistent launch (B <= 128).  The loop of `LSTMAudio.generate`
  *   (`blvm/models/lstm.py`): emb = embedding(x_{t-1}) -> per layer (h, c) = LSTM cell(input, (h, c)) -> decoder(h of the last layer) ->

@@ -3,6 +3,9 @@
 // builds of the plan can be compared with diff.  Host only, no GPU call.
 //   hipcc --offload-arch=gfx950 -O1 -std=c++17 -w -Iinclude -Ibenchmarking-lvms_amd/csrc tools/dump_rollout_program.hip -o dump_rollout_program
 // Grid: S in {1, 5, 8, 16, 24, 64} x B in {1, 17, 64, 128} x CUs in {32, 256}, T = 3; VRNN with Z == H and Z != H, LSTM with 1 and 2 layers.
+// Without arguments: the DMoL programs (head kind 0), the output every earlier build of the plan can be compared with.  `--heads`: after
+// them the VRNN and SRNN programs of the GMM head (kind 1) and the Gaussian head (kind 2), each title with its `head <kind>`; in every
+// dump the draw link's head kind is i[3] and its sd_beta, sd_eps are f[1], f[2] of the last descriptor (pchain.h DMOLS_I_HEAD).
 #include "lstm_decode.h"
 
 #include <cstdio>
@@ -54,7 +57,15 @@ void dump(const char* title, const Builder& bld, const Arrays& a) {
 constexpr int T = 3;
 constexpr float kSdEps = 1e-6f, kSlope = 0.01f, kLogEps = -7.f;
 
-void vrnn(int S, int B, int H, int Z, int R, int cus, int tune) {
+// the head of kind `kind` as the entry points plan it (sd_beta ln 2, sd_eps 1e-4: the audio models' Gaussian heads)
+DrawPlan head_of(int kind) {
+  DrawPlan dp;
+  draw_plan(kind, kDmolK, 0.6931472f, 1e-4f, &dp);
+  return dp;
+}
+void vrnn(int S, int B, int H, int Z, int R, int cus, int tune, int kind = 0) {
+  const DrawPlan dp = head_of(kind);
+  const int kDmolF = dp.F, kDmolK = dp.K;  // (the head's widths under the names the sizes below use)
   Arrays a;
   BlvmVrnnWeights c{};
   BlvmVrnnDecodeWeights w{};
@@ -68,19 +79,22 @@ void vrnn(int S, int B, int H, int Z, int R, int cus, int tune) {
   c.prior_hw = a.add("prior_hw", big); c.prior_hb = a.add("prior_hb", 2 * Z); c.gru_wih = a.add("gru_wih", big); c.gru_whh = a.add("gru_whh", big);
   c.gru_bih = a.add("gru_bih", 3 * R); c.gru_bhh = a.add("gru_bhh", 3 * R); w.lik_w = a.add("lik_w", kDmolF * kDmolF); w.lik_b = a.add("lik_b", kDmolF);
   w.cell = &c;
-  auto p = vrnn_pack_table(w, c, S, H, Z, R);
-  const auto b = vrnn_generate_layout(p.total, T, B, S, H, Z, R);
+  auto p = vrnn_pack_table(w, c, S, H, Z, R, dp.F);
+  const auto b = vrnn_generate_layout(p.total, T, B, S, H, Z, R, dp.F);
   float* sc = a.add("scratch", b.end);
   p.use_staged(sc);
-  const float *eps = a.add("eps", (size_t)T * B * Z), *u = a.add("u", (size_t)T * B * S * kDmolK), *v = a.add("v", (size_t)T * B * S);
+  const float *eps = a.add("eps", (size_t)T * B * Z), *u = kDmolK ? a.add("u", (size_t)T * B * S * kDmolK) : nullptr, *v = a.add("v", (size_t)T * B * S);
   float* x_out = a.add("x_out", (size_t)B * T * S);
   Builder bld;
-  vrnn_generate_program(bld, blvm::OP_F32, cus, tune, &w, p, b, sc, eps, u, v, x_out, T, B, S, H, Z, R, kSdEps, kSlope, kLogEps);
-  char title[128];
-  snprintf(title, sizeof title, "vrnn S %d B %d H %d Z %d R %d cus %d tune %d scratch %zu", S, B, H, Z, R, cus, tune, (size_t)b.end);
+  vrnn_generate_program(bld, blvm::OP_F32, cus, tune, &w, p, b, sc, eps, u, v, x_out, T, B, S, H, Z, R, kSdEps, kSlope, kLogEps, dp);
+  char title[128], head[16] = "";
+  if (kind) snprintf(head, sizeof head, " head %d", kind);
+  snprintf(title, sizeof title, "vrnn S %d B %d H %d Z %d R %d cus %d tune %d scratch %zu%s", S, B, H, Z, R, cus, tune, (size_t)b.end, head);
   dump(title, bld, a);
 }
-void srnn(int S, int B, int H, int Z, int R, int cus, int tune) {
+void srnn(int S, int B, int H, int Z, int R, int cus, int tune, int kind = 0) {
+  const DrawPlan dp = head_of(kind);
+  const int kDmolF = dp.F, kDmolK = dp.K;
   Arrays a;
   BlvmSrnnWeights c{};
   BlvmSrnnDecodeWeights w{};
@@ -93,16 +107,17 @@ void srnn(int S, int B, int H, int Z, int R, int cus, int tune) {
   c.prior_hw = a.add("prior_hw", big); c.prior_hb = a.add("prior_hb", 2 * Z); w.gru_wih = a.add("gru_wih", big); w.gru_whh = a.add("gru_whh", big);
   w.gru_bih = a.add("gru_bih", 3 * R); w.gru_bhh = a.add("gru_bhh", 3 * R); w.lik_w = a.add("lik_w", kDmolF * kDmolF); w.lik_b = a.add("lik_b", kDmolF);
   w.chain = &c;
-  auto p = srnn_pack_table(w, c, S, H, Z, R);
-  const auto b = srnn_generate_layout(p.total, T, B, S, H, Z, R);
+  auto p = srnn_pack_table(w, c, S, H, Z, R, dp.F);
+  const auto b = srnn_generate_layout(p.total, T, B, S, H, Z, R, dp.F);
   float* sc = a.add("scratch", b.end);
   p.use_staged(sc);
-  const float *eps = a.add("eps", (size_t)T * B * Z), *u = a.add("u", (size_t)T * B * S * kDmolK), *v = a.add("v", (size_t)T * B * S);
+  const float *eps = a.add("eps", (size_t)T * B * Z), *u = kDmolK ? a.add("u", (size_t)T * B * S * kDmolK) : nullptr, *v = a.add("v", (size_t)T * B * S);
   float* x_out = a.add("x_out", (size_t)B * T * S);
   Builder bld;
-  srnn_generate_program(bld, blvm::OP_F32, cus, tune, &w, p, b, sc, eps, u, v, x_out, T, B, S, H, Z, R, kSdEps, kSlope, kLogEps);
-  char title[128];
-  snprintf(title, sizeof title, "srnn S %d B %d H %d Z %d R %d cus %d tune %d scratch %zu", S, B, H, Z, R, cus, tune, (size_t)b.end);
+  srnn_generate_program(bld, blvm::OP_F32, cus, tune, &w, p, b, sc, eps, u, v, x_out, T, B, S, H, Z, R, kSdEps, kSlope, kLogEps, dp);
+  char title[128], head[16] = "";
+  if (kind) snprintf(head, sizeof head, " head %d", kind);
+  snprintf(title, sizeof title, "srnn S %d B %d H %d Z %d R %d cus %d tune %d scratch %zu%s", S, B, H, Z, R, cus, tune, (size_t)b.end, head);
   dump(title, bld, a);
 }
 void lstm(int S, int B, int H, int L, int cus) {
@@ -133,7 +148,7 @@ void lstm(int S, int B, int H, int L, int cus) {
 }
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
   for (int S : {1, 5, 8, 16, 24, 64})
     for (int B : {1, 17, 64, 128})
       for (int cus : {32, 256}) {
@@ -143,5 +158,12 @@ int main() {
         srnn(S, B, 48, 16, 32, cus, 16);
         for (int L : {1, 2}) lstm(S, B, 48, L, cus);
       }
+  if (argc > 1 && !strcmp(argv[1], "--heads"))
+    for (int kind : {1, 2})
+      for (int S : {1, 6, 16, 24})
+        for (int B : {3, 17}) {
+          vrnn(S, B, 48, 16, 32, 256, 0, kind);
+          srnn(S, B, 48, 16, 32, 256, 0, kind);
+        }
   return 0;
 }
