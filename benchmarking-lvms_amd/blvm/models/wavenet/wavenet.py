@@ -4,6 +4,10 @@ forward: left-pad by the receptive field -> causal conv -> in_transform -> 50 ga
 node) -> sum of skips * variance_scale -> ReLU-Linear-ReLU -> likelihood Linear (K6) -> DMoL log-likelihood (K7), or with a
 `CategoricalDense` head its Linear and the softmax log-likelihood in one (K7d: the logits are never stored).
 Loss in fp32 like the reference: -sum(ll * mask) / sum(x_sl) (wavenet.py:128-146).
+
+`embedding_dim=E` is the class-in model of the original paper (wavenet.py:105-113,182): sample classes -> nn.Embedding(num_bins, E) ->
+a causal conv with groups = res_channels.  Embedding, padding and that convolution run as one gather from two lookup tables (K10e,
+`ops.wavenet_embed_front`); the rest of the network is the float model's.
 """
 import math
 from typing import Optional
@@ -33,7 +37,7 @@ class WaveNetDecodeState:
     """What cached generation needs to go on after `n_frames` samples (a prompt's included): every block's ring buffer of its
     own input over its last `dilation` frames ([d,B,C], frame tau in slot tau mod d) and the last two samples.
     `scratch`: the decode kernel's buffer the rings are views into (None on the block-by-block path).  A continued call updates
-    the rings in place: a state is good for ONE continuation."""
+    the rings in place: a state is good for ONE continuation.  An embedded model keeps the last two CLASSES (int32) as `samples`."""
 
     __slots__ = ("scratch", "rings", "samples", "n_frames")
 
@@ -47,15 +51,27 @@ class WaveNet(BaseModel):
                  gate_channels: Optional[int] = None, kernel_size: int = 2, base_dilation: int = 2, n_stack_frames: int = 1,
                  activation: nn.Module = nn.ReLU):  # fmt: skip
         super().__init__()
-        if embedding_dim is not None:
-            raise NotImplementedError("libblvm_hip: the embedding input variant of WaveNet is not built (audio runs feed floats)")
+        if embedding_dim is not None and n_stack_frames > 1:
+            raise ValueError("Cannot stack frames if using an embedding (which is what we do when in_channels>1)")
+        if embedding_dim is not None and in_channels > 1:
+            raise ValueError("Cannot use more than 1 input_channel if also wanting to use an embedding.")
+        if embedding_dim is not None and (embedding_dim % res_channels != 0 or kernel_size != 2 or res_channels % 4 != 0):
+            # (nn.Conv1d(groups=res_channels) itself refuses an embedding_dim that is no multiple of res_channels)
+            raise NotImplementedError("libblvm_hip: the embedding input variant of WaveNet is built for embedding_dim a multiple of "
+                                      "res_channels (its causal conv has groups=res_channels), res_channels a multiple of 4, kernel_size 2")  # fmt: skip
         self.n_layers, self.n_stacks, self.in_channels, self.embedding_dim = n_layers, n_stacks, in_channels, embedding_dim
         self.res_channels, self.skip_channels, self.gate_channels = res_channels, skip_channels, gate_channels
         self.kernel_size, self.base_dilation, self.num_bins = kernel_size, base_dilation, num_bins
         self.n_stack_frames, self.activation = n_stack_frames, activation
         self.variance_scale = math.sqrt(1 / self.n_stacks * self.n_layers)
-        self.embedding = None
-        self.causal = CausalConv1d(in_channels=in_channels * n_stack_frames, out_channels=res_channels, kernel_size=kernel_size)
+        if embedding_dim is None:
+            self.embedding = None
+            self.causal = CausalConv1d(in_channels=in_channels * n_stack_frames, out_channels=res_channels, kernel_size=kernel_size)
+        else:
+            self.embedding = nn.Embedding(num_embeddings=num_bins, embedding_dim=embedding_dim)
+            self.causal = CausalConv1d(in_channels=embedding_dim, out_channels=res_channels, kernel_size=kernel_size, groups=res_channels)
+            # the class values `Quantize(bins=num_bins)` maps back to the classes (as `CategoricalDense.levels`); not in the state_dict
+            self.register_buffer("levels", torch.linspace(-1.0, 1.0, num_bins), persistent=False)
         self.res_stack = ResidualStack(n_layers=n_layers, n_stacks=n_stacks, res_channels=res_channels, kernel_size=kernel_size,
                                        base_dilation=base_dilation)  # fmt: skip
         self.receptive_field = self.res_stack.receptive_field + self.causal.kernel_size - 1
@@ -70,9 +86,18 @@ class WaveNet(BaseModel):
         if x.ndim == 3:
             x = x.squeeze(-1)
         dev = x.device
-        x = x.to(torch.float32)
+        k = None
+        if self.embedding is not None:  # classes in: an integer x as it stands, a float x quantised by the categorical target's rule
+            k = self._classes(x)
+            if y is None and cat and lik.y_dim != self.num_bins:
+                raise ValueError(f"WaveNet: the {self.num_bins} input classes are no targets for a head of {lik.y_dim} classes: give y")
+            x = x.detach().to(torch.float32) if x.is_floating_point() else (self.levels[k] if y is None and not cat else k)
+        else:
+            x = x.to(torch.float32)
         x_sl_host = x_sl.detach().cpu().to(torch.int64)
-        if y is None:
+        if y is None and k is not None and cat:  # the classes are the targets
+            y = k if pad_receptive_field else k[:, rf:]
+        elif y is None:
             y = x.detach()
             if cat:  # Quantize(bins=V) on the device: class V (a value above 1) joins the top class
                 y = torch.bucketize(y, lik.levels, right=False).clamp(max=lik.y_dim - 1)
@@ -83,23 +108,29 @@ class WaveNet(BaseModel):
         y = y.reshape(y.size(0), -1).contiguous()
         x_sl_strided = (x_sl_host / nsf).ceil().int()
         B = x.size(0)
-        if nsf > 1:
+        if k is not None:
+            xt = k.t().to(torch.int32)  # time-major classes [T,B]
+        elif nsf > 1:
             T = x.size(1)
             Tp = (T + nsf - 1) // nsf
-            x = torch.nn.functional.pad(x, (0, Tp * nsf - T)).view(B, Tp, nsf)
+            xt = torch.nn.functional.pad(x, (0, Tp * nsf - T)).view(B, Tp, nsf).transpose(0, 1).contiguous()
         else:
-            x = x.unsqueeze(-1)
-        xt = x.transpose(0, 1).contiguous()  # time-major [T',B,C_in]
+            xt = x.unsqueeze(-1).transpose(0, 1).contiguous()  # time-major [T',B,C_in]
         if pad_receptive_field:
             skip_size = xt.size(0)
-            xt = torch.cat([torch.zeros(rf, B, xt.size(2), device=dev), xt], 0)
+            # zeros in front; of an embedded model index -1, the zero row: the reference pads AFTER embedding (wavenet.py:182-188)
+            pad = torch.zeros(rf, B, xt.size(2), device=dev) if k is None else torch.full((rf, B), -1, device=dev, dtype=torch.int32)
+            xt = torch.cat([pad, xt], 0)
         else:
             skip_size = xt.size(0) - rf
             x_sl_host = x_sl_host - rf
         if xt.size(0) - int(pad_causal) < rf:
             raise InputSizeError(xt.size(0), rf)
 
-        out = self.causal.forward_tm(xt, pad_causal=pad_causal)
+        if k is None:
+            out = self.causal.forward_tm(xt, pad_causal=pad_causal)
+        else:
+            out = ops.wavenet_embed_front(xt, self.embedding.weight, self.causal.conv.weight, self.causal.conv.bias, pad_causal)
         skip_sum = self.res_stack.forward_tm(out, skip_size)  # [skip_size,B,C]
         C = self.res_channels
         logits = self.out_transform.forward_rows(skip_sum.view(skip_size * B, C), self.variance_scale)  # [skip*B, C*nsf]
@@ -174,6 +205,15 @@ class WaveNet(BaseModel):
                                y=y.unsqueeze(-1))  # fmt: skip
         return loss, metrics, output
 
+    def _classes(self, x):
+        """x [B,T] of an embedded model -> its classes [B,T] int64: an integer x as it stands, a float x by `Quantize(bins=num_bins)`'s
+        rule (`bucketize` on linspace(-1, 1, V), a value above 1 joining the top class)."""
+        if x.ndim == 3:
+            x = x.squeeze(-1)
+        if x.is_floating_point():
+            return torch.bucketize(x.detach().to(torch.float32), self.levels, right=False).clamp(max=self.num_bins - 1)
+        return x.detach().long()
+
     def _draw(self, parameters, u):
         """One draw per head evaluation -> floats [B,nsf,1]; the categorical head's class k is fed back as `dequantize(k)`."""
         lik = self.likelihood
@@ -211,8 +251,16 @@ class WaveNet(BaseModel):
         16), otherwise block by block (`_generate_cached`).
         With `cached=True`, `x` [B,P,1] is a prompt: the queues are primed from its last receptive-field samples (`_prime`) and
         frames P, P+1, ... are drawn.  `return_state=True` returns (x_hat, state); `state=` continues from one (generation in
-        chunks; `uniforms` are indexed from 0 for every call)."""
+        chunks; `uniforms` are indexed from 0 for every call).
+        An embedded model generates with the categorical head (the drawn class is the next input class) on all three paths and returns
+        `dequantize(k)` floats like the float-input model; its zero start is a past of class 0 (the reference's `embedding(zeros)`
+        window, wavenet.py:264-266), a prompt is classes [B,P] or floats [B,P,1] (quantised), on either path."""
         lik, C, nsf = self.likelihood, self.res_channels, self.n_stack_frames
+        if self.embedding is not None:
+            if not isinstance(lik, CategoricalDense):
+                raise NotImplementedError("libblvm_hip: the embedded WaveNet generates with the categorical head (a drawn class is the next input)")
+            if lik.y_dim != self.num_bins:
+                raise ValueError(f"WaveNet.generate: a head of {lik.y_dim} classes cannot feed an embedding of {self.num_bins}")
         if nsf != 1 and (cached or self.in_channels != 1):
             raise NotImplementedError("libblvm_hip: WaveNet.generate on frame stacks is the window path with in_channels=1 (cached=False)")
         if not cached and (state is not None or return_state):
@@ -231,6 +279,8 @@ class WaveNet(BaseModel):
             x_hat, state = run(n_samples, n_frames, uniforms, state=state, want_state=True)
             return (x_hat, state) if return_state else x_hat
         dev = self.causal.conv.weight.device
+        if self.embedding is not None:
+            return self._generate_window_embedded(n_samples, n_frames, x, uniforms)
         win = torch.zeros(self.receptive_field, n_samples, self.in_channels * nsf, device=dev) if x is None else x.transpose(0, 1).contiguous()
         x_hat = []
         for t in range(n_frames):
@@ -244,6 +294,38 @@ class WaveNet(BaseModel):
             win = torch.cat([win[1:], pred.reshape(1, n_samples, nsf).to(torch.float32)], 0)
         return torch.hstack(x_hat)
 
+    def _class_window(self, x, n_samples: int, width: int):
+        """The last `width` classes of a prompt (classes [B,P] or floats [B,P,1]; None: no prompt), class 0 in front of a shorter
+        one (the zero start) -> int32 [B,width] on the model's device."""
+        dev = self.causal.conv.weight.device
+        if x is None:
+            return torch.zeros(n_samples, width, device=dev, dtype=torch.int32)
+        k = self._classes(x.to(dev))
+        if k.ndim != 2 or k.size(0) != n_samples:
+            raise ValueError(f"WaveNet.generate: a prompt of classes [B,P] or floats [B,P,1] with B = {n_samples}, got {tuple(x.shape)}")
+        k = k[:, -width:].to(torch.int32)
+        return torch.nn.functional.pad(k, (width - k.size(1), 0))
+
+    def _front_tables(self):
+        return ops.wavenet_embed_tables(self.embedding.weight, self.causal.conv.weight)
+
+    @torch.no_grad()
+    def _generate_window_embedded(self, n_samples: int, n_frames: int, x=None, uniforms=None):
+        """The window path of `generate` on classes: the window holds the last receptive_field classes, the front is the table
+        lookup (K10e), the drawn class shifts in."""
+        lik, C, B = self.likelihood, self.res_channels, n_samples
+        tables, bias = self._front_tables(), self.causal.conv.bias
+        win = self._class_window(x, B, self.receptive_field).t().contiguous()  # [rf,B]
+        ks = []
+        for t in range(n_frames):
+            out = ops.wavenet_embed_lookup(tables, bias, win, pad_causal=False)
+            skip = self.res_stack.forward_tm(out, 1)  # [1,B,C]
+            logits = self.out_transform.forward_rows(skip.view(B, C), 1.0 / self.variance_scale)
+            k = lik.sample(lik(logits.view(B, 1, C)), uniforms=None if uniforms is None else uniforms[t].reshape(B, 1))  # [B,1]
+            ks.append(k)
+            win = torch.cat([win[1:], k.view(1, B).to(torch.int32)], 0)
+        return lik.dequantize(torch.cat(ks, 1)).unsqueeze(-1)
+
     def _decode_widths_fit(self):
         """The widths the decode kernel (K10c) takes, whatever the head."""
         C, blk = self.res_channels, self.res_stack.res_blocks[0]
@@ -256,7 +338,8 @@ class WaveNet(BaseModel):
 
     def _cat_decode_kernel_applies(self):
         """The decode kernel's categorical head: 16 <= V <= 1024 in multiples of 16 (a larger softmax wants its head Linear split
-        across workgroups: block by block, `_generate_cached`), the widths of `_decode_kernel_applies`."""
+        across workgroups: block by block, `_generate_cached`), the widths of `_decode_kernel_applies`.  An embedded model (which
+        generates with this head only, y_dim == num_bins) runs the kernel's embedded arm at the same widths."""
         lik = self.likelihood
         return (isinstance(lik, CategoricalDense) and 16 <= lik.y_dim <= 1024 and lik.y_dim % 16 == 0 and self.n_stack_frames == 1
                 and self._decode_widths_fit())  # fmt: skip
@@ -267,15 +350,23 @@ class WaveNet(BaseModel):
         shorter prompt is left-padded with zeros, which is what the zero start means.  The frame the two newest samples give is
         the first one generation evaluates, so the window that fills the queues ends one sample earlier: the causal conv drops
         it (`pad_causal=True`), the in_transform and the time-parallel block kernels give every block's input over the window
-        (`ops.wavenet_prime_rings`), and each ring buffer takes the last `dilation` frames of its block's input."""
-        if self.in_channels != 1 or x.ndim != 3 or x.size(2) != 1 or x.size(1) < 1:
-            raise NotImplementedError("libblvm_hip: cached generation takes a prompt [B,P,1] with P >= 1 (in_channels = 1)")
+        (`ops.wavenet_prime_rings`), and each ring buffer takes the last `dilation` frames of its block's input.
+        An embedded model: the prompt is classes [B,P] (or floats, quantised), padded with class 0; the state keeps two classes."""
         rs, rf, C = self.res_stack, self.receptive_field, self.res_channels
         dev = self.causal.conv.weight.device
-        B, P = x.size(0), x.size(1)
-        win = x[:, -rf:, 0].to(device=dev, dtype=torch.float32)
-        win = torch.nn.functional.pad(win, (rf - win.size(1), 0))  # [B,rf]
-        out = self.causal.forward_tm(win.t().contiguous().unsqueeze(-1), pad_causal=True)  # [rf-2,B,C]: absolute frames P-rf+2 .. P-1
+        if self.embedding is not None:
+            if x.size(1) < 1:
+                raise NotImplementedError("libblvm_hip: cached generation takes a prompt of P >= 1 samples")
+            B, P = x.size(0), x.size(1)
+            win = self._class_window(x, B, rf)  # [B,rf]
+            out = ops.wavenet_embed_lookup(self._front_tables(), self.causal.conv.bias, win.t().contiguous(), pad_causal=True)  # [rf-2,B,C]
+        else:
+            if self.in_channels != 1 or x.ndim != 3 or x.size(2) != 1 or x.size(1) < 1:
+                raise NotImplementedError("libblvm_hip: cached generation takes a prompt [B,P,1] with P >= 1 (in_channels = 1)")
+            B, P = x.size(0), x.size(1)
+            win = x[:, -rf:, 0].to(device=dev, dtype=torch.float32)
+            win = torch.nn.functional.pad(win, (rf - win.size(1), 0))  # [B,rf]
+            out = self.causal.forward_tm(win.t().contiguous().unsqueeze(-1), pad_causal=True)  # [rf-2,B,C]: absolute frames P-rf+2 .. P-1
         L, t_in, blk = out.size(0), rs.in_transform, rs.res_blocks[0]
         h0 = ops.linear(out.reshape(L * B, C), t_in.weight.view(t_in.out_channels, C), t_in.bias).view(L, B, C)
         scratch, rings = ops.wavenet_decode_scratch(rs.dilations, B, C, blk.skip_channels, dev)
@@ -287,7 +378,8 @@ class WaveNet(BaseModel):
         rs, lik = self.res_stack, self.likelihood
         t_in = rs.in_transform
         head = lik.logits if isinstance(lik, CategoricalDense) else lik.params
-        return ((self.causal.conv.weight, self.causal.conv.bias), (t_in.weight.view(t_in.out_channels, -1), t_in.bias),
+        causal = self.causal.conv.weight if self.embedding is None else self._front_tables()  # (K10e: the tables in the weights' place)
+        return ((causal, self.causal.conv.bias), (t_in.weight.view(t_in.out_channels, -1), t_in.bias),
                 [b.kernel_params() for b in rs.res_blocks], rs.dilations,
                 (self.out_transform.linear.weight, self.out_transform.linear.bias), (head.weight, head.bias))  # fmt: skip
 
@@ -327,8 +419,9 @@ class WaveNet(BaseModel):
         x_hat = out.x.unsqueeze(-1)
         if not want_state:
             return x_hat
-        if state is None:  # the zero start, keeping its scratch: the samples in front of frame 0 are zeros
-            samples = torch.cat([torch.zeros(B, 2, device=out.x.device), out.x], 1)[:, -2:].contiguous()
+        if state is None:  # the zero start, keeping its scratch: the samples in front of frame 0 are zeros (embedded: class 0)
+            last = out.x if self.embedding is None else out.k
+            samples = torch.cat([last.new_zeros(B, 2), last], 1)[:, -2:].contiguous()
             rings, before = ops.wavenet_ring_views(out.scratch, rs.dilations, B, self.res_channels, blk.skip_channels), 0
         else:
             samples, rings, before = out.samples, state.rings, state.n_frames
@@ -348,8 +441,15 @@ class WaveNet(BaseModel):
         S, inv_std = blocks[0].skip_channels, blocks[0].inv_std
         t_in = rs.in_transform
 
+        emb = self.embedding is not None
+        if emb:
+            tables = self._front_tables()
+
         def causal_pair(x_prev, x_now):  # [B,Cin] each -> causal conv output for the newest position, then the 1x1 in_transform
-            c = self.causal.forward_tm(torch.stack([x_prev, x_now], 0), pad_causal=False)  # [1,B,C]
+            if emb:  # [B,1] classes each: two table rows (K10e)
+                c = ops.wavenet_embed_lookup(tables, self.causal.conv.bias, torch.cat([x_prev, x_now], 1).t().contiguous(), pad_causal=False)
+            else:
+                c = self.causal.forward_tm(torch.stack([x_prev, x_now], 0), pad_causal=False)  # [1,B,C]
             return ops.linear(c.view(B, C), t_in.weight.view(t_in.out_channels, C), t_in.bias)
 
         def through_blocks(h, taps0, skip):
@@ -362,7 +462,7 @@ class WaveNet(BaseModel):
                 h = o.view(B, C) if o is not None else None
             return inputs
 
-        zero_x = torch.zeros(B, self.in_channels, device=dev)
+        zero_x = torch.zeros(B, 1, device=dev, dtype=torch.int32) if emb else torch.zeros(B, self.in_channels, device=dev)
         if state is None:
             # steady state under an all-zero past: block i's delayed input equals its current input
             h, steady = causal_pair(zero_x, zero_x), []
@@ -390,6 +490,11 @@ class WaveNet(BaseModel):
                 heads[i] = (heads[i] + 1) % d
             logits = self.out_transform.forward_rows(skip.view(B, C), 1.0 / self.variance_scale)
             parameters = lik(logits.view(B, 1, C))
+            if emb:
+                k = lik.sample(parameters, uniforms=None if uniforms is None else uniforms[t].reshape(B, 1))  # [B,1]
+                x_hat.append(lik.dequantize(k).unsqueeze(-1))
+                x_prev, x_now = x_now, k.view(B, 1).to(torch.int32)
+                continue
             pred = self._draw(parameters, None if uniforms is None else uniforms[t])  # [B,1,1]
             x_hat.append(pred)
             x_prev, x_now = x_now, pred.view(B, 1).to(torch.float32)

@@ -14,13 +14,18 @@ from blvm.modules.activations import GatedTanhUnit
 
 
 class CausalConv1d(nn.Module):
-    """y[t] depends on x[:t] only: the last input is dropped before a kernel-size-k convolution (:14-50)."""
+    """y[t] depends on x[:t] only: the last input is dropped before a kernel-size-k convolution (:14-50).
+    `groups == out_channels` with kernel_size 2 is the front of the embedded WaveNet: a parameter container (the shapes are
+    nn.Conv1d's own), executed together with the embedding in front of it by `ops.wavenet_embed_front` (K10e)."""
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int = 1, activation: Optional[nn.Module] = None, **kwargs):
         super().__init__()
-        if kernel_size not in (1, 2) or kwargs.get("groups", 1) != 1 or activation is not None:
-            raise NotImplementedError("libblvm_hip: CausalConv1d is built for kernel_size in {1, 2}, groups=1, no activation")
-        self.kernel_size = kernel_size
+        groups = kwargs.get("groups", 1)
+        grouped = groups != 1 and groups == out_channels and kernel_size == 2
+        if kernel_size not in (1, 2) or (groups != 1 and not grouped) or activation is not None:
+            raise NotImplementedError("libblvm_hip: CausalConv1d is built for kernel_size in {1, 2}, groups=1 (kernel_size 2: or "
+                                      "groups=out_channels, the embedded WaveNet's front), no activation")  # fmt: skip
+        self.kernel_size, self.groups = kernel_size, groups
         self.conv = nn.Conv1d(in_channels, out_channels, kernel_size=kernel_size, **kwargs)
         self.activation = None
 
@@ -30,6 +35,9 @@ class CausalConv1d(nn.Module):
 
     def forward_tm(self, x: torch.Tensor, pad_causal: bool = True):
         """x [L,B,C_in] time-major -> [L - pad_causal - (k-1), B, C_out]."""
+        if self.groups != 1:
+            raise NotImplementedError("libblvm_hip: the grouped CausalConv1d runs fused with the embedding in front of it "
+                                      "(ops.wavenet_embed_front), not on an embedded tensor")  # fmt: skip
         if pad_causal:
             x = x[:-1]
         if self.kernel_size == 1:

@@ -1419,6 +1419,86 @@ def conv1d_k2(x, weight, bias, dilation: int = 1):
     return _Conv1dK2Function.apply(x, weight, bias, int(dilation))
 
 
+def _embed_dims(emb, cw):
+    """-> (V, E, C, m) of embedding.weight [V,E] and the grouped causal conv's weight [C,m,2] (groups = C)."""
+    V, E = emb.shape
+    C, m = cw.shape[0], cw.shape[1]
+    if cw.ndim != 3 or cw.shape[2] != 2 or C * m != E:
+        raise ValueError(f"wavenet_embed: embedding [{V},{E}] with a conv weight {tuple(cw.shape)}: need [C, E / C, 2]")
+    return V, E, C, m
+
+
+@torch.no_grad()
+def wavenet_embed_tables(emb, cw):
+    """K10e: embedding.weight [V,E] and the grouped causal conv's weight [C,E/C,2] -> the lookup tables P [2,V+1,C] (row V: zeros)."""
+    emb, cw = _f32c(emb), _f32c(cw)
+    V, _, C, m = _embed_dims(emb, cw)
+    P = torch.empty(2, V + 1, C, device=emb.device, dtype=torch.float32)
+    check(load().blvm_wavenet_embed_tables(ptr(emb), ptr(cw), V, C, m, ptr(P), stream_ptr()), "blvm_wavenet_embed_tables")
+    return P
+
+
+def _embed_classes(k, what="wavenet_embed_front"):
+    if k.ndim != 2 or k.is_floating_point() or k.is_complex():
+        raise TypeError(f"{what}: classes are an integer tensor [L,B] (time-major), got {k.dtype} {tuple(k.shape)}")
+    return k.to(torch.int32).contiguous()
+
+
+@torch.no_grad()
+def wavenet_embed_lookup(P, bias, k, pad_causal: bool = True):
+    """K10e forward on given tables: classes k [L,B] (integer, time-major; -1 = a zero-padded frame) ->
+    out [L - 1 - pad_causal, B, C] = (P[0][k[t]] + P[1][k[t+1]]) + bias."""
+    k, bias = _embed_classes(k), _f32c(bias)
+    L, B = k.shape
+    V, C = P.shape[1] - 1, P.shape[2]
+    out = torch.empty(max(L - 1 - int(pad_causal), 0), B, C, device=P.device, dtype=torch.float32)
+    check(load().blvm_wavenet_embed_fwd(ptr(P), ptr(bias), ptr(k), L, B, V, C, int(pad_causal), ptr(out), stream_ptr()), "blvm_wavenet_embed_fwd")
+    return out
+
+
+class _WaveNetEmbedFunction(torch.autograd.Function):
+    """nn.Embedding(V, E) -> zero left-padding -> the causal convolution of kernel size 2 with groups = C, as one gather of two table
+    rows per output frame (K10e); the gradients of all three parameters from per-class sums of d_out, without float atomics."""
+
+    @staticmethod
+    def forward(ctx, k, pad_causal, emb, cw, bias):
+        emb, cw = _f32c(emb), _f32c(cw)
+        k = _embed_classes(k)
+        out = wavenet_embed_lookup(wavenet_embed_tables(emb, cw), bias, k, pad_causal)
+        ctx.save_for_backward(k, emb, cw)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        k, emb, cw = ctx.saved_tensors
+        V, E, C, m = _embed_dims(emb, cw)
+        d_out = _f32c(d_out)
+        Lo, B = d_out.shape[0], d_out.shape[1]
+        lib = load()
+        f32 = dict(device=emb.device, dtype=torch.float32)
+        if Lo == 0:
+            return None, None, torch.zeros(V, E, **f32), torch.zeros(C, m, 2, **f32), torch.zeros(C, **f32)
+        # integer plumbing: the frames of every class, in frame order (a stable sort; padding sorts last, as class V)
+        keys = k[: Lo + 1].reshape(-1)
+        keys = torch.where((keys >= 0) & (keys < V), keys, torch.full_like(keys, V))
+        skeys, perm = torch.sort(keys, stable=True)
+        perm = perm.to(torch.int32)
+        starts = torch.searchsorted(skeys, torch.arange(V + 1, device=keys.device, dtype=torch.int32)).to(torch.int32)
+        n = keys.numel()
+        G = torch.empty(2, V, C, **f32)
+        ws = torch.empty(max(lib.blvm_wavenet_embed_bwd_workspace_floats(n, V, C, m), 1), **f32)
+        d_emb, d_cw, d_bias = torch.empty(V, E, **f32), torch.empty(C, m, 2, **f32), torch.empty(C, **f32)
+        check(lib.blvm_wavenet_embed_bwd(ptr(d_out), ptr(skeys), ptr(perm), ptr(starts), Lo, B, V, C, m, ptr(emb), ptr(cw), ptr(G), ptr(ws),
+                                         ptr(d_emb), ptr(d_cw), ptr(d_bias), stream_ptr()), "blvm_wavenet_embed_bwd")  # fmt: skip
+        return None, None, d_emb, d_cw, d_bias
+
+
+def wavenet_embed_front(k, emb, cw, bias, pad_causal: bool = True):
+    """K10e: classes k [L,B] (integer, time-major; -1 = a zero-padded frame), embedding.weight [V,E], the grouped causal conv's
+    weight [C,E/C,2] and bias [C] -> [L - 1 - pad_causal, B, C]: `causal(pad(embedding(k)))` of the reference's embedded WaveNet."""
+    return _WaveNetEmbedFunction.apply(k, bool(pad_causal), emb, cw, bias)
+
+
 class _WaveNetStackFunction(torch.autograd.Function):
     """All gated residual blocks of a residual stack in one autograd node: x [L,B,C] -> G skip tensors [T_skip,B,S].
     `groups[i]` names the output that block i's skip branch is accumulated into; -1 = the block's skip is not used at all
@@ -1563,12 +1643,17 @@ class WaveNetDecodeOut(NamedTuple):
 
 
 def _wavenet_decode_pack(weights, head):
-    """The packed weight image of K10c and its sizes: -> (lib, C, S, O, device, packed, dilations as a C array).  The image ends
-    in the head Linear: padded with zeros to 32 rows (`DmolHead`), as it stands (`CategoricalHead`)."""
+    """The packed weight image of K10c and its sizes: -> (lib, C, S, O, device, packed, dilations as a C array, tables).  The image ends
+    in the head Linear: padded with zeros to 32 rows (`DmolHead`), as it stands (`CategoricalHead`).  An embedded model (K10e) gives
+    (tables [2,V+1,C], bias) as `causal`: the tables travel beside the image, whose causal weights are zeros nobody reads."""
     causal, in_transform, blocks_params, dilations, out_linear, (hw, hb) = weights
     lib = load()
     C, S, O = in_transform[0].shape[0], blocks_params[0][2].shape[0] - in_transform[0].shape[0], out_linear[0].shape[0]
     dev = causal[0].device
+    tables = None
+    if isinstance(head, CategoricalHead) and tuple(causal[0].shape) == (2, hw.shape[0] + 1, C):
+        tables = _f32c(causal[0])
+        causal = (torch.zeros(2 * C, device=dev), causal[1])
     if causal[0].numel() != 2 * C:
         raise NotImplementedError("libblvm_hip: wavenet_decode is built for in_channels = n_stack_frames = 1")
     if isinstance(head, DmolHead):
@@ -1587,7 +1672,7 @@ def _wavenet_decode_pack(weights, head):
     packed = torch.cat([_f32c(p).reshape(-1) for p in parts])
     if packed.numel() != want:
         raise ValueError("wavenet_decode: parameter shapes do not match the packed layout")
-    return lib, C, S, O, dev, packed, _c_ints(dilations)
+    return lib, C, S, O, dev, packed, _c_ints(dilations), tables
 
 
 @torch.no_grad()
@@ -1596,8 +1681,10 @@ def wavenet_decode(weights, head, B: int, n_frames: int, inv_std: float, skip_sc
     head_linear): (weight, bias) pairs, blocks_params as for wavenet_stack.  head = `DmolHead` with draws = (u [n_frames,B,num_mix],
     v [n_frames,B]), or `CategoricalHead` with draws = u [n_frames,B]: uniform draws indexed from 0 (None: the mode, the arg-max class).
     resume = (t0, samples [B,2], scratch) continues from a state: `scratch` holds the ring buffers after absolute frame t0 - 1
-    (`wavenet_prime_rings` or an earlier call; updated in place), samples the last two samples.  -> `WaveNetDecodeOut`."""
-    lib, C, S, O, dev, packed, dil = _wavenet_decode_pack(weights, head)
+    (`wavenet_prime_rings` or an earlier call; updated in place), samples the last two samples.  -> `WaveNetDecodeOut`.
+    An embedded model (K10e) with the categorical head: `causal` = (tables [2,V+1,C] of `wavenet_embed_tables`, bias); the class is fed
+    back as a class, the zero start is a past of class 0, and samples (in and out) are the last two CLASSES, int32 [B,2]."""
+    lib, C, S, O, dev, packed, dil, tables = _wavenet_decode_pack(weights, head)
     dmol, n = isinstance(head, DmolHead), len(dil)
     shapes = [(n_frames, B, head.num_mix), (n_frames, B)] if dmol else [(n_frames, B)]
     if draws is None:
@@ -1615,7 +1702,9 @@ def wavenet_decode(weights, head, B: int, n_frames: int, inv_std: float, skip_sc
         t0, samples, scratch = resume
         if scratch.dtype != torch.float32 or scratch.numel() != n_scratch:
             raise ValueError("wavenet_decode: the scratch buffer does not belong to these shapes")
-        samples = _f32c(samples)
+        if tables is not None and samples.dtype != torch.int32:
+            raise ValueError("wavenet_decode: an embedded model continues from the last two classes, int32 [B,2]")
+        samples = samples.contiguous() if tables is not None else _f32c(samples)
         if tuple(samples.shape) != (B, 2):
             raise ValueError("wavenet_decode: samples must be [B,2]")
     x = torch.empty(B, n_frames, **f32)
@@ -1627,11 +1716,13 @@ def wavenet_decode(weights, head, B: int, n_frames: int, inv_std: float, skip_sc
         levels = _f32c(head.levels.to(dev)).reshape(width)  # (named: it must outlive the launch's enqueue)
         operands = (ptr(levels), ptr(draws[0]))
     sizes = (ptr(packed), dil, n, B, C, S, O, width, n_frames)
+    if tables is not None:
+        name, sizes = "blvm_wavenet_embed_cat_decode", (ptr(packed), ptr(tables), *sizes[1:])
     outs = (ptr(x),) if dmol else (ptr(x), ptr(k))
     if resume is None:
         check(getattr(lib, name)(*sizes, inv_std, skip_scale, *operands, ptr(scratch), *outs, stream_ptr()), name)
         return WaveNetDecodeOut(x, k, scratch, None)
-    samples_out = torch.empty(B, 2, **f32)
+    samples_out = torch.empty(B, 2, device=dev, dtype=samples.dtype)
     name += "_resume"
     check(getattr(lib, name)(*sizes, int(t0), inv_std, skip_scale, *operands, ptr(samples), ptr(scratch), *outs, ptr(samples_out),
                              stream_ptr()), name)  # fmt: skip

@@ -181,7 +181,7 @@ extern "C" int blvm_async_errors_take(unsigned* last_code) {
   return (int)fresh;
 }
 
-extern "C" int blvm_version(void) { return 202; /* 0.2.2: blvm_gemm_arm / blvm_wgrad_group_route / blvm_gemm_arm_counts (K6's dispatch, arm by arm) */ }
+extern "C" int blvm_version(void) { return 203; /* 0.2.3: blvm_wavenet_embed_* (K10e: WaveNet with embedded class input) */ }
 
 extern "C" const char* blvm_last_error(void) { return blvm::g_err; }
 

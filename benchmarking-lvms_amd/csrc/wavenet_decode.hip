@@ -22,6 +22,8 @@
 // draw) and the categorical head of the original paper (K7d's softmax over V classes, 16 <= V <= 1024): its Linear goes through the
 // same tile layer into an LDS logits buffer [16][V + 4], 32 lanes per row draw one class (cat_pick, decode_tiles.h), and the class
 // is fed back and written out as levels[k] — the model's table, copied to LDS once; no arithmetic on it.
+// On an embedded model (K10e, wavenet_embed.hip) the categorical head feeds the class back as a CLASS: sX holds the two newest classes
+// and the front reads two rows of the lookup tables from global memory; a third HEAD, so the arms above keep their code.
 #include "common.h"
 #include "decode_tiles.h"
 
@@ -81,13 +83,22 @@ struct CatDecodeArgs : DecodeArgs {
   int* k_out;           // [B,n_frames] the classes, or NULL
 };
 
+// The embedded model: x_in / x_state hold int32 classes; the zero start is a past of class 0.
+struct EmbCatDecodeArgs : CatDecodeArgs {
+  const float* tab;  // [2,V+1,C] the lookup tables of wavenet_embed.hip
+};
+
 struct DmolHead {
   using Args = DecodeArgs;
-  static constexpr bool categorical = false;
+  static constexpr bool categorical = false, embedded = false;
 };
 struct CatHead {
   using Args = CatDecodeArgs;
-  static constexpr bool categorical = true;
+  static constexpr bool categorical = true, embedded = false;
+};
+struct EmbCatHead {
+  using Args = EmbCatDecodeArgs;
+  static constexpr bool categorical = true, embedded = true;
 };
 constexpr int CAT_MIN_V = 16, CAT_MAX_V = 1024, CAT_LOGIT_PAD = 4;
 
@@ -146,7 +157,13 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(typename HEAD::Args 
   const float* w = a.w;
 
   const int t0 = RESUME ? a.t0 : 0;
-  for (int i = tid; i < DEC_ROWS * 2; i += NT) sX[i] = (RESUME && b0 + i / 2 < B) ? a.x_in[(size_t)2 * b0 + i] : 0.f;
+  [[maybe_unused]] int* sK = reinterpret_cast<int*>(sX);  // embedded: the pair as classes
+  if constexpr (HEAD::embedded) {
+    const int* k_in = reinterpret_cast<const int*>(a.x_in);
+    for (int i = tid; i < DEC_ROWS * 2; i += NT) sK[i] = (RESUME && b0 + i / 2 < B) ? min(max(k_in[(size_t)2 * b0 + i], 0), a.V - 1) : 0;
+  } else {
+    for (int i = tid; i < DEC_ROWS * 2; i += NT) sX[i] = (RESUME && b0 + i / 2 < B) ? a.x_in[(size_t)2 * b0 + i] : 0.f;
+  }
   if constexpr (HEAD::categorical)
     for (int i = tid; i < head_rows; i += NT) sLev[i] = a.levels[i];
   __syncthreads();
@@ -155,9 +172,18 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(typename HEAD::Args 
   auto front = [&]() {
     const float* cw = w + L.causal_w;
     const float* cb = w + L.causal_b;
-    for (int idx = tid; idx < DEC_ROWS * C; idx += NT) {
-      const int r = idx / C, o = idx - r * C;
-      sAct[r * ldA + o] = cw[2 * o] * sX[2 * r] + cw[2 * o + 1] * sX[2 * r + 1] + cb[o];
+    if constexpr (HEAD::embedded) {
+      const float* p0 = a.tab;
+      const float* p1 = a.tab + (size_t)(a.V + 1) * C;
+      for (int idx = tid; idx < DEC_ROWS * C; idx += NT) {
+        const int r = idx / C, o = idx - r * C;
+        sAct[r * ldA + o] = (p0[(size_t)sK[2 * r] * C + o] + p1[(size_t)sK[2 * r + 1] * C + o]) + cb[o];
+      }
+    } else {
+      for (int idx = tid; idx < DEC_ROWS * C; idx += NT) {
+        const int r = idx / C, o = idx - r * C;
+        sAct[r * ldA + o] = cw[2 * o] * sX[2 * r] + cw[2 * o + 1] * sX[2 * r + 1] + cb[o];
+      }
     }
     for (int idx = tid; idx < DEC_ROWS * S; idx += NT) {
       const int r = idx / S;
@@ -347,8 +373,13 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(typename HEAD::Args 
         const float x = sLev[k];
         a.x_out[(size_t)(b0 + row) * a.n_frames + t] = x;
         if (a.k_out != nullptr) a.k_out[(size_t)(b0 + row) * a.n_frames + t] = k;
-        sX[2 * row] = sX[2 * row + 1];
-        sX[2 * row + 1] = x;
+        if constexpr (HEAD::embedded) {
+          sK[2 * row] = sK[2 * row + 1];
+          sK[2 * row + 1] = k;
+        } else {
+          sX[2 * row] = sX[2 * row + 1];
+          sX[2 * row + 1] = x;
+        }
       }
     } else {
       tile_layer<NW, false>(sAct, ldA, w + L.head_w, O, 0, DEC_HEAD_ROWS / 16, w + L.head_b, [&](int row, int o, float val) { sPar[row * DEC_HEAD_ROWS + o] = val; });
@@ -370,7 +401,10 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(typename HEAD::Args 
   }
   if constexpr (RESUME)
     for (int i = tid; i < DEC_ROWS * 2; i += NT)
-      if (b0 + i / 2 < B) a.x_state[(size_t)2 * b0 + i] = sX[i];
+      if (b0 + i / 2 < B) {
+        if constexpr (HEAD::embedded) reinterpret_cast<int*>(a.x_state)[(size_t)2 * b0 + i] = sK[i];
+        else a.x_state[(size_t)2 * b0 + i] = sX[i];
+      }
 #ifdef DEC_PROF
   if (blockIdx.x == 0 && (tid == 0 || tid == NT - 1))
     for (int k = 0; k < 6; ++k) a.x_out[(size_t)B * a.n_frames + (tid ? 6 : 0) + k] = (float)(prof[k] / 1000);
@@ -432,7 +466,7 @@ extern "C" size_t blvm_wavenet_decode_ring_offset_floats(int n_blocks, int C, in
 static int decode_run(bool resume, const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int num_mix,
                       int n_frames, int t0, float inv_std, float skip_scale, float log_eps, const float* u, const float* v,
                       const float* x_in, float* scratch, float* x_out, float* x_state, void* stream, int V = 0,
-                      const float* levels = nullptr, int32_t* k_out = nullptr) {
+                      const float* levels = nullptr, int32_t* k_out = nullptr, const float* tables = nullptr) {
   using namespace blvm;
   const bool cat = V > 0;
   BLVM_REQUIRE(packed && dilations && scratch && x_out && aligned16(packed) && aligned16(scratch), "wavenet_decode: NULL or misaligned argument");
@@ -449,8 +483,8 @@ static int decode_run(bool resume, const float* packed, const int* dilations, in
   if (cat) BLVM_REQUIRE(lds <= 160 * 1024, "wavenet_cat_decode: C=%d, S=%d, O=%d, V=%d need %zu bytes of LDS (> 160 KB)", C, S, O, V, lds);
   BLVM_REQUIRE(lds <= 160 * 1024, "wavenet_decode: C=%d, S=%d, O=%d need %zu bytes of LDS (> 160 KB)", C, S, O, lds);
   if (n_frames == 0) return resume ? hand_back_state(x_state, x_in, (size_t)2 * B, static_cast<hipStream_t>(stream)) : BLVM_OK;
-  CatDecodeArgs a;  // (the DMoL kernels take its base)
-  a.V = V; a.levels = levels; a.k_out = k_out;
+  EmbCatDecodeArgs a;  // (the other kernels take its bases)
+  a.V = V; a.levels = levels; a.k_out = k_out; a.tab = tables;
   a.w = packed;
   for (int i = 0; i < n_blocks; ++i) {
     BLVM_REQUIRE(dilations[i] >= 1, "wavenet_decode: dilation %d of block %d", dilations[i], i);
@@ -473,6 +507,7 @@ static int decode_run(bool resume, const float* packed, const int* dilations, in
   a.wt = scratch;
   a.queues = scratch + (size_t)n_blocks * wt_stride;
   const bool even = n_blocks % 2 == 0;
+  if (tables) return decode_launch<EmbCatHead>(resume, even, a, lds, static_cast<hipStream_t>(stream));
   if (cat) return decode_launch<CatHead>(resume, even, a, lds, static_cast<hipStream_t>(stream));
   return decode_launch<DmolHead>(resume, even, a, lds, static_cast<hipStream_t>(stream));
 }
@@ -523,6 +558,26 @@ extern "C" int blvm_wavenet_cat_decode_resume(const float* packed, const int* di
   BLVM_TRY(cat_widths_ok(V));
   return decode_run(true, packed, dilations, n_blocks, B, C, S, O, 0, n_frames, t0, inv_std, skip_scale, 0.f, u, nullptr, x_in, scratch,
                     x_out, x_state, stream, V, levels, k_out);
+}
+
+// The embedded model: the class pair travels through x_in / x_state as int32 words; the kernel clamps what it reads to [0, V).
+extern "C" int blvm_wavenet_embed_cat_decode(const float* packed, const float* tables, const int* dilations, int n_blocks, int B, int C, int S,
+                                             int O, int V, int n_frames, float inv_std, float skip_scale, const float* levels, const float* u,
+                                             float* scratch, float* x_out, int32_t* k_out, void* stream) {
+  BLVM_TRY(cat_widths_ok(V));
+  BLVM_REQUIRE(tables && blvm::aligned16(tables), "wavenet_embed_cat_decode: NULL or misaligned tables");
+  return decode_run(false, packed, dilations, n_blocks, B, C, S, O, 0, n_frames, 0, inv_std, skip_scale, 0.f, u, nullptr, nullptr, scratch,
+                    x_out, nullptr, stream, V, levels, k_out, tables);
+}
+
+extern "C" int blvm_wavenet_embed_cat_decode_resume(const float* packed, const float* tables, const int* dilations, int n_blocks, int B, int C,
+                                                    int S, int O, int V, int n_frames, int t0, float inv_std, float skip_scale,
+                                                    const float* levels, const float* u, const int32_t* k_in, float* scratch, float* x_out,
+                                                    int32_t* k_out, int32_t* k_state, void* stream) {
+  BLVM_TRY(cat_widths_ok(V));
+  BLVM_REQUIRE(tables && blvm::aligned16(tables), "wavenet_embed_cat_decode_resume: NULL or misaligned tables");
+  return decode_run(true, packed, dilations, n_blocks, B, C, S, O, 0, n_frames, t0, inv_std, skip_scale, 0.f, u, nullptr,
+                    reinterpret_cast<const float*>(k_in), scratch, x_out, reinterpret_cast<float*>(k_state), stream, V, levels, k_out, tables);
 }
 
 extern "C" int blvm_wavenet_decode_ring_fill(const float* h, int L, int B, int C, int dilation, int t0, float* ring, void* stream) {

@@ -17,6 +17,7 @@ g.add_argument("--base_dilation", default=2, type=int)
 g.add_argument("--input_embedding_dim", default=1, type=int)
 g.add_argument("--n_stack_frames", default=1, type=int)
 g.add_argument("--generate_every", default=25, type=int)
+g.add_argument("--generate_frames", default=0, type=int, help="after training: draw this many samples from a zero start (cached generation)")
 g.add_argument("--input_coding", default="mu_law", type=str, choices=["mu_law", "linear"])
 g.add_argument("--num_bits", default=16, type=int)
 g.add_argument("--num_mix", default=10, type=int)
@@ -24,8 +25,7 @@ g.add_argument("--likelihood", default="DMoL", type=str)
 g.add_argument("--random_segment_size", default=None, type=int)
 g.add_argument("--split_eval", default=False, type=str2bool)
 
-if __name__ == "__main__":
-    args = parser.parse_args()
+def build_model(args):
     if args.likelihood == "DMoL":
         lik = DiscretizedLogisticMixtureDense(args.res_channels, 1, num_mix=args.num_mix, num_bins=2**args.num_bits)
     elif args.likelihood == "Categorical":
@@ -34,8 +34,17 @@ if __name__ == "__main__":
         lik = CategoricalDense(args.res_channels, 2**args.num_bits)
     else:
         raise NotImplementedError("libblvm_hip: WaveNet is built with the DMoL and the Categorical likelihoods")
-    model = WaveNet(likelihood=lik, n_layers=args.n_layers, n_stacks=args.n_stacks, res_channels=args.res_channels,
-                    kernel_size=args.kernel_size, base_dilation=args.base_dilation, n_stack_frames=args.n_stack_frames)  # fmt: skip
+    # --input_embedding_dim E > 1: the class-in model, nn.Embedding(2**num_bits, E) in front of a grouped causal conv.  The reference
+    # passes E as `in_channels` (:168), which its model cannot run; here it is `embedding_dim` ("WaveNet with embedded
+    # input").  The float input is quantised into the classes by the model.
+    embedded = dict(embedding_dim=args.input_embedding_dim, num_bins=2**args.num_bits) if args.input_embedding_dim > 1 else {}
+    return WaveNet(likelihood=lik, n_layers=args.n_layers, n_stacks=args.n_stacks, res_channels=args.res_channels,
+                   kernel_size=args.kernel_size, base_dilation=args.base_dilation, n_stack_frames=args.n_stack_frames, **embedded)  # fmt: skip
+
+
+if __name__ == "__main__":
+    args = parser.parse_args()
+    model = build_model(args)
     if args.split_eval and not args.random_segment_size:
         raise SystemExit("--split_eval True needs --random_segment_size (the split length, experiment_wavenet_audio.py:226)")
 
@@ -44,3 +53,8 @@ if __name__ == "__main__":
 
     run(args, model, lambda m, x, sl: m(x, sl), lambda m, x, sl: m(x, sl), "loss", args.num_bits, split_eval if args.split_eval else None,
         clip=False)  # fmt: skip
+    if args.generate_frames > 0:
+        model.eval()
+        x_hat = model.generate(n_samples=1, n_frames=args.generate_frames, cached=True)
+        print(f"generated {tuple(x_hat.shape)}: mean {float(x_hat.mean()):.4f}, std {float(x_hat.std()):.4f}, "
+              f"{len(x_hat.unique())} distinct values", flush=True)

@@ -770,6 +770,38 @@ int blvm_wavenet_cat_decode_resume(const float* packed, const int* dilations, in
                                    int n_frames, int t0, float inv_std, float skip_scale, const float* levels, const float* u,
                                    const float* x_in, float* scratch, float* x_out, int32_t* k_out, float* x_state, void* stream);
 
+/* K10e  WaveNet with embedded class input (`WaveNet(embedding_dim=E, num_bins=V)`, `blvm/models/wavenet/wavenet.py:105-113,182`):
+ *   nn.Embedding(V, E) and the causal convolution with groups = C, kernel size 2 (m = E / C inputs per output channel) as two lookup
+ *   tables.  emb [V,E], cw [C,m,2], bias [C]; C a multiple of 4, C <= 1024.
+ *   blvm_wavenet_embed_tables: P [2,V+1,C] (=), P[tap][k][o] = sum_j cw[o,j,tap] emb[k, o m + j] in index order; row V is zeros.
+ *   blvm_wavenet_embed_fwd: k [L_in,B] int32 time-major classes, any value outside [0,V) (-1 by convention) a zero-padded frame ->
+ *     out [L_out,B,C] (=), out[t,b] = (P[0][k[t,b]] + P[1][k[t+1,b]]) + bias, L_out = L_in - 1 - pad_causal (pad_causal: the last
+ *     input is dropped, as in `CausalConv1d.forward`).
+ *   blvm_wavenet_embed_bwd: d_out [L_out,B,C]; the caller sorts the n = (L_out + 1) B flattened classes of k[:L_out + 1] (padding
+ *     mapped to V) with a stable sort: sorted_keys [n] ascending, perm [n] = the frame index tau B + b of every sorted entry,
+ *     starts [V+1] = the first sorted position with a key >= k.  -> G [2,V,C] (=) the per-class sums of d_out by tap (an exact zero
+ *     for a class without frames), d_emb [V,E] (=), d_cw [C,m,2] (=), d_bias [C] (=).  No float atomics: two calls agree to the bit.
+ *     workspace: blvm_wavenet_embed_bwd_workspace_floats(n, V, C, m) floats (contents need no initialisation). */
+int blvm_wavenet_embed_tables(const float* emb, const float* cw, int V, int C, int m, float* P, void* stream);
+int blvm_wavenet_embed_fwd(const float* P, const float* bias, const int32_t* k, int L_in, int B, int V, int C, int pad_causal,
+                           float* out, void* stream);
+size_t blvm_wavenet_embed_bwd_workspace_floats(int n, int V, int C, int m);
+int blvm_wavenet_embed_bwd(const float* d_out, const int32_t* sorted_keys, const int32_t* perm, const int32_t* starts, int L_out,
+                           int B, int V, int C, int m, const float* emb, const float* cw, float* G, float* workspace, float* d_emb,
+                           float* d_cw, float* d_bias, void* stream);
+
+/* K10c  on the embedded model: the categorical pair above with the class fed back as a class.  tables = P [2,V+1,C] of
+ *   blvm_wavenet_embed_tables replaces the causal convolution's weights (that region of the packed image is not read; its bias is):
+ *   frame input = (P[0][k_prev] + P[1][k_new]) + bias.  The zero start is a past of class 0 (the reference's `embedding(zeros)`
+ *   window, `wavenet.py:264-266`).  k_in / k_state [B,2] int32: the (previous, newest) class in place of x_in / x_state. */
+int blvm_wavenet_embed_cat_decode(const float* packed, const float* tables, const int* dilations, int n_blocks, int B, int C, int S,
+                                  int O, int V, int n_frames, float inv_std, float skip_scale, const float* levels, const float* u,
+                                  float* scratch, float* x_out, int32_t* k_out, void* stream);
+int blvm_wavenet_embed_cat_decode_resume(const float* packed, const float* tables, const int* dilations, int n_blocks, int B, int C,
+                                         int S, int O, int V, int n_frames, int t0, float inv_std, float skip_scale,
+                                         const float* levels, const float* u, const int32_t* k_in, float* scratch, float* x_out,
+                                         int32_t* k_out, int32_t* k_state, void* stream);
+
 /* K10d  Ancestral sampling from the STCN: all T steps of all rows in ONE launch, from an all-zero past.  The reference leaves
  *   `STCN.generate` unimplemented (`blvm/models/stcn/stcn.py:435-442`); this is the generative model its `forward` / `infer` define
  *   (`stcn.py:299-326, 389-409`) with every latent drawn from its prior.  Per step t: causal conv (kernel 2) of the stacks x_{t-2},
