@@ -7,6 +7,8 @@
 // into one MFMA GEMM each before the loop, so a step is 4 dependent links (first layers | second | third | heads +
 // sample) forward and 4 backward, every element-wise piece fused into an epilogue (stages.h).  The KL(+free nats)
 // gradient is folded into the backward chain exactly as for the VRNN cell.
+#include <atomic>
+
 #include "common.h"
 #include "pchain.h"
 
@@ -69,6 +71,13 @@ size_t carve_srnn_ws(float* base, int Tp, int B, int H, int Z, SrnnWs* w) {
   return ar.floats();
 }
 
+// which implementation the entry points took and which tiles their per-link loops ran on (blvm_srnn_path_counts): host-side
+// counts, [0..3] one per call, [4..5] one per launch_lin of the launch-per-link loops
+enum { SRNN_FWD_PROGRAM = 0, SRNN_FWD_PER_LINK = 1, SRNN_BWD_PROGRAM = 2, SRNN_BWD_PER_LINK = 3, SRNN_LIN16 = 4, SRNN_LIN32 = 5 };
+std::atomic<unsigned long long> g_srnn_counts[6];
+inline void count_srnn(int k) { g_srnn_counts[k].fetch_add(1, std::memory_order_relaxed); }
+inline void count_lin(int tile_width) { count_srnn(tile_width == 32 ? SRNN_LIN32 : SRNN_LIN16); }
+
 int check_srnn(int Tp, int B, int H, int Z, int R) {
   BLVM_REQUIRE(Tp > 0 && B > 0, "srnn: bad Tp=%d B=%d", Tp, B);
   BLVM_REQUIRE(H > 0 && Z > 0 && R > 0 && H % 16 == 0 && Z % 16 == 0 && R % 16 == 0,
@@ -81,6 +90,12 @@ int check_srnn(int Tp, int B, int H, int Z, int R) {
 }  // namespace blvm
 
 using namespace blvm;
+
+extern "C" int blvm_srnn_path_counts(unsigned long long out[6]) {
+  BLVM_REQUIRE(out, "srnn_path_counts: null pointer");
+  for (int k = 0; k < 6; ++k) out[k] = g_srnn_counts[k].load(std::memory_order_relaxed);
+  return BLVM_OK;
+}
 
 extern "C" size_t blvm_srnn_reserve_floats(int Tp, int B, int H, int Z, int R) {
   (void)R;
@@ -123,6 +138,7 @@ extern "C" int blvm_srnn_latent_fwd(const BlvmSrnnWeights* w, const float* d, co
   if (pchain_applies(B) && device_cus() >= 32) {
     // Persistent path (pchain.h / pchain.hip): the four links of a step as a program of 7 descriptors, one launch per sequence
     using namespace pchain;
+    count_srnn(SRNN_FWD_PROGRAM);
     const int ctH = H / 16, ctZ = Z / 16, cus = device_cus() & ~7;
     const long sH = (long)B * H, sZ = (long)B * Z, xH = (long)rt * 16 * H, xZ = (long)rt * 16 * Z;
     const int half = range_for(ctH * rt, cus / 2);
@@ -147,6 +163,7 @@ extern "C" int blvm_srnn_latent_fwd(const BlvmSrnnWeights* w, const float* d, co
     BLVM_TRY(pchain_rows_to_t16(zs, Z, B, Z, rs.Z16, s));
     return pchain_launch(bld, "srnn_fwd", s);
   }
+  count_srnn(SRNN_FWD_PER_LINK);
   for (int t = 0; t < Tp; ++t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z;
     const float* zprev = zs + oZ;
@@ -154,11 +171,11 @@ extern "C" int blvm_srnn_latent_fwd(const BlvmSrnnWeights* w, const float* d, co
     l.B = B; l.slope = slope; l.nseg = 2;
     l.seg[0] = seg(zprev, Z, rs.Wp[0], Z, nullptr, rs.XP + oH, H, nullptr, 0, rs.P[0] + oH, H, H, Z, 1);
     l.seg[1] = seg(zprev, Z, rs.Wq[0], Z, nullptr, rs.XQ + oH, H, nullptr, 0, rs.Q[0] + oH, H, H, Z, 1);
-    launch_lin(l, s);
+    count_lin(launch_lin(l, s));
     for (int k = 1; k < 3; ++k) {
       l.seg[0] = seg(rs.P[k - 1] + oH, H, rs.Wp[k], H, w->prior_b[k], nullptr, 0, nullptr, 0, rs.P[k] + oH, H, H, H, 1);
       l.seg[1] = seg(rs.Q[k - 1] + oH, H, rs.Wq[k], H, w->post_b[k], nullptr, 0, nullptr, 0, rs.Q[k] + oH, H, H, H, 1);
-      launch_lin(l, s);
+      count_lin(launch_lin(l, s));
     }
     HeadArgs h;
     h.P = rs.P[2] + oH; h.Q = rs.Q[2] + oH;
@@ -205,6 +222,7 @@ extern "C" int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, co
   BLVM_TRY(pack_scope.flush());
   const int rt = (B + 15) / 16;
   const bool persistent = pchain_applies(B) && device_cus() >= 32;
+  count_srnn(persistent ? SRNN_BWD_PROGRAM : SRNN_BWD_PER_LINK);
   if (persistent) {
     // Persistent path: the BPTT chain as a program of 9 descriptors walked for s = 0 .. T' (t = T'-1-s; s = T': the gradient wrt z_0)
     using namespace pchain;
@@ -263,11 +281,11 @@ extern "C" int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, co
     l.B = B; l.slope = slope; l.nseg = 2;
     l.seg[0] = seg(ws.DPH + o2Z, 2 * Z, ws.phT, 2 * Z, nullptr, nullptr, 0, rs.P[2] + oH, H, ws.DP[2] + oH, H, H, 2 * Z, 0);
     l.seg[1] = seg(ws.DQH + o2Z, 2 * Z, ws.qhT, 2 * Z, nullptr, nullptr, 0, rs.Q[2] + oH, H, ws.DQ[2] + oH, H, H, 2 * Z, 0);
-    launch_lin(l, s);
+    count_lin(launch_lin(l, s));
     for (int k = 2; k >= 1; --k) {
       l.seg[0] = seg(ws.DP[k] + oH, H, ws.pT[k], H, nullptr, nullptr, 0, rs.P[k - 1] + oH, H, ws.DP[k - 1] + oH, H, H, H, 0);
       l.seg[1] = seg(ws.DQ[k] + oH, H, ws.qT[k], H, nullptr, nullptr, 0, rs.Q[k - 1] + oH, H, ws.DQ[k - 1] + oH, H, H, H, 0);
-      launch_lin(l, s);
+      count_lin(launch_lin(l, s));
     }
   }
   BLVM_CHECK_LAUNCH("srnn_latent_bwd");
@@ -275,9 +293,9 @@ extern "C" int blvm_srnn_latent_bwd(const BlvmSrnnWeights* w, const float* d, co
     LinLaunch l;
     l.B = B; l.slope = 0.f; l.nseg = 1;
     l.seg[0] = seg(ws.DP[0], H, ws.pzT, H, nullptr, nullptr, 0, nullptr, 0, d_z0, Z, Z, H, 0);
-    launch_lin(l, s);
+    count_lin(launch_lin(l, s));
     l.seg[0] = seg(ws.DQ[0], H, ws.qzT, H, nullptr, d_z0, Z, nullptr, 0, d_z0, Z, Z, H, 0);
-    launch_lin(l, s);
+    count_lin(launch_lin(l, s));
   }
   // batched, state-independent part
   if (d_d) BLVM_TRY(gemm_f32(0, 1, (int)n, R, H, ws.DP[0], H, w->prior_w[0], ldw0, d_d, R, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include "common.h"
 #include "pchain.h"
@@ -337,6 +338,13 @@ bool vrnn_dec_bwd_folds(int Tp, int B, int H, int Z, int R, int DH, int SF) {
   return dl.split3 && dl.bdec[0].nwg > 0;
 }
 
+// which implementation the sequence entry points took and which tiles their per-link loops ran on (blvm_vrnn_path_counts):
+// host-side counts, [0..4] one per call ([4]: the calls of [0] and [2] whose program ran on row groups), [5..6] one per launch_lin
+enum { VRNN_FWD_PROGRAM = 0, VRNN_FWD_PER_LINK = 1, VRNN_BWD_PROGRAM = 2, VRNN_BWD_PER_LINK = 3, VRNN_ROW_GROUPS = 4, VRNN_LIN16 = 5, VRNN_LIN32 = 6 };
+std::atomic<unsigned long long> g_vrnn_counts[7];
+inline void count_vrnn(int k) { g_vrnn_counts[k].fetch_add(1, std::memory_order_relaxed); }
+inline void count_lin(int tile_width) { count_vrnn(tile_width == 32 ? VRNN_LIN32 : VRNN_LIN16); }
+
 int check_dims(int Tp, int B, int X, int H, int Z, int R) {
   BLVM_REQUIRE(Tp > 0 && B > 0, "vrnn: bad Tp=%d B=%d", Tp, B);
   BLVM_REQUIRE(X > 0 && H > 0 && Z > 0 && R > 0 && X % 16 == 0 && H % 16 == 0 && Z % 16 == 0 && R % 16 == 0,
@@ -349,6 +357,12 @@ int check_dims(int Tp, int B, int X, int H, int Z, int R) {
 }  // namespace blvm
 
 using namespace blvm;
+
+extern "C" int blvm_vrnn_path_counts(unsigned long long out[7]) {
+  BLVM_REQUIRE(out, "vrnn_path_counts: null pointer");
+  for (int k = 0; k < 7; ++k) out[k] = g_vrnn_counts[k].load(std::memory_order_relaxed);
+  return BLVM_OK;
+}
 
 extern "C" size_t blvm_vrnn_reserve_floats(int Tp, int B, int X, int H, int Z, int R) {
   (void)X;
@@ -437,6 +451,8 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     const long xH = (long)rt * 16 * H, xZ = (long)rt * 16 * Z, xR = (long)rt * 16 * R;
     // tiles of a link per column tile: row tiles, or (65 <= B <= 256) groups of row tiles (pchain_rt.h)
     const bool groups = vrnn_row_groups(B);
+    count_vrnn(VRNN_FWD_PROGRAM);
+    if (groups) count_vrnn(VRNN_ROW_GROUPS);
     const int RTG = groups ? vrnn_rt(B) : 1;
     const int tl = (rt + RTG - 1) / RTG;
     // hidden projection: up to a quarter of the chip
@@ -543,6 +559,7 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     if (fold) { ++g_dec_folded; if (folded) *folded = fold; }
     return BLVM_OK;
   }
+  count_vrnn(VRNN_FWD_PER_LINK);
   for (int t = 0; t < Tp; ++t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z, oR = (size_t)t * B * R, o3R = (size_t)t * B * 3 * R;
     const float* dec_t = decin + (size_t)t * B * ldd;
@@ -555,13 +572,13 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     a.seg[0] = seg(hprev, ldd, rs.Wp[0], R, w->prior_b[0], nullptr, 0, nullptr, 0, rs.P[0] + oH, H, H, R, 1);
     a.seg[1] = seg(hprev, ldd, rs.Wq[0], R, nullptr, rs.XQ + oH, H, nullptr, 0, rs.Q[0] + oH, H, H, R, 1);
     a.seg[2] = seg(hprev, ldd, rs.Whh, R, w->gru_bhh, nullptr, 0, nullptr, 0, rs.GHb + o3R, 3 * R, 3 * R, R, 0);
-    launch_lin(a, s);
+    count_lin(launch_lin(a, s));
     // F2, F3
     a.nseg = 2;
     for (int l = 1; l < 3; ++l) {
       a.seg[0] = seg(rs.P[l - 1] + oH, H, rs.Wp[l], H, w->prior_b[l], nullptr, 0, nullptr, 0, rs.P[l] + oH, H, H, H, 1);
       a.seg[1] = seg(rs.Q[l - 1] + oH, H, rs.Wq[l], H, w->post_b[l], nullptr, 0, nullptr, 0, rs.Q[l] + oH, H, H, H, 1);
-      launch_lin(a, s);
+      count_lin(launch_lin(a, s));
     }
     // F4: heads + sample
     HeadArgs h;
@@ -576,13 +593,13 @@ static int vrnn_seq_fwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     // F5..F8: phi_z MLP (last layer writes phi into decin row t)
     a.nseg = 1;
     a.seg[0] = seg(z + oZ, Z, rs.Wf[0], Z, w->phi_b[0], nullptr, 0, nullptr, 0, rs.FZ[0] + oH, H, H, Z, 1);
-    launch_lin(a, s);
+    count_lin(launch_lin(a, s));
     a.seg[0] = seg(rs.FZ[0] + oH, H, rs.Wf[1], H, w->phi_b[1], nullptr, 0, nullptr, 0, rs.FZ[1] + oH, H, H, H, 1);
-    launch_lin(a, s);
+    count_lin(launch_lin(a, s));
     a.seg[0] = seg(rs.FZ[1] + oH, H, rs.Wf[2], H, w->phi_b[2], nullptr, 0, nullptr, 0, rs.FZ[2] + oH, H, H, H, 1);
-    launch_lin(a, s);
+    count_lin(launch_lin(a, s));
     a.seg[0] = seg(rs.FZ[2] + oH, H, rs.Wf[3], H, w->phi_b[3], nullptr, 0, nullptr, 0, decin + (size_t)t * B * ldd, ldd, H, H, 1);
-    launch_lin(a, s);
+    count_lin(launch_lin(a, s));
     // F9: GRU
     {
       const int nw = pick_nw(H, 3);
@@ -728,6 +745,8 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     const long sH = (long)B * H, sZ = (long)B * Z, sR = (long)B * R, s3R = 3 * sR, s2Z = 2 * sZ, sD = (long)B * ldd;
     const long xH = (long)rt * 16 * H, x2Z = (long)rt * 16 * 2 * Z, x3R = (long)rt * 16 * 3 * R;
     const bool groups = vrnn_row_groups(B);
+    count_vrnn(VRNN_BWD_PROGRAM);
+    if (groups) count_vrnn(VRNN_ROW_GROUPS);
     const int RTG = groups ? vrnn_rt(B) : 1;
     const int tl = (rt + RTG - 1) / RTG;  // tiles of a link per column tile: row tiles, or groups of them (pchain_rt.h)
     // (shared deal: see vrnn_fwd -- here the gentle link is GB, which the posterior half runs while the prior half
@@ -858,6 +877,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   }
 
   BLVM_REQUIRE(!dec, "vrnn_bwd: the decoder leader needs the persistent path");
+  count_vrnn(VRNN_BWD_PER_LINK);
   launch_dh(-1, Tp - 1);  // G(T') = 0: gate derivatives of the last step, G <- d_decin h-part of row T'-1
   for (int t = Tp - 1; t >= 0; --t) {
     const size_t oH = (size_t)t * B * H, oZ = (size_t)t * B * Z, o3R = (size_t)t * B * 3 * R, o2Z = (size_t)t * B * 2 * Z;
@@ -869,12 +889,12 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     a.nseg = 2;
     a.seg[0] = seg(ws.DGI + o3R, 3 * R, ws.wihT, 3 * R, nullptr, ddec_t, ldd, dec_t, ldd, ws.DPHI[3] + oH, H, H, 3 * R, 0);
     a.seg[1] = seg(ws.DGH + o3R, 3 * R, ws.whhT, 3 * R, nullptr, ws.G, R, nullptr, 0, ws.G, R, R, 3 * R, 0);
-    launch_lin(a, s);
+    count_lin(launch_lin(a, s));
     // B3..B5: back through phi_z layers 3,2,1
     a.nseg = 1;
     for (int l = 3; l >= 1; --l) {
       a.seg[0] = seg(ws.DPHI[l] + oH, H, ws.fT[l], H, nullptr, nullptr, 0, rs.FZ[l - 1] + oH, H, ws.DPHI[l - 1] + oH, H, H, H, 0);
-      launch_lin(a, s);
+      count_lin(launch_lin(a, s));
     }
     // B6: dz and the heads
     DzArgs d;
@@ -890,12 +910,12 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     a.nseg = 2;
     a.seg[0] = seg(ws.DPH + o2Z, 2 * Z, ws.phT, 2 * Z, nullptr, nullptr, 0, rs.P[2] + oH, H, ws.DP[2] + oH, H, H, 2 * Z, 0);
     a.seg[1] = seg(ws.DQH + o2Z, 2 * Z, ws.qhT, 2 * Z, nullptr, nullptr, 0, rs.Q[2] + oH, H, ws.DQ[2] + oH, H, H, 2 * Z, 0);
-    launch_lin(a, s);
+    count_lin(launch_lin(a, s));
     // B8, B9
     for (int l = 2; l >= 1; --l) {
       a.seg[0] = seg(ws.DP[l] + oH, H, ws.pT[l], H, nullptr, nullptr, 0, rs.P[l - 1] + oH, H, ws.DP[l - 1] + oH, H, H, H, 0);
       a.seg[1] = seg(ws.DQ[l] + oH, H, ws.qT[l], H, nullptr, nullptr, 0, rs.Q[l - 1] + oH, H, ws.DQ[l - 1] + oH, H, H, H, 0);
-      launch_lin(a, s);
+      count_lin(launch_lin(a, s));
     }
     // B10 (+ gate derivatives of step t-1)
     launch_dh(t, t - 1);

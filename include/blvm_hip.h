@@ -97,6 +97,16 @@ int blvm_rnn_path_counts(unsigned long long out[12]);
  * (one count per call); out[4] / out[5] the linear-link launches of the launch-per-link loops (the backward's initial-state links
  * included) that ran on 16x16 / on 32x32 tiles (one count per launch).  Host-side; never touches the device. */
 int blvm_rssm_path_counts(unsigned long long out[6]);
+/* The same for the VRNN sequence entry points (K1; blvm_vrnn_seq_fwd / _fwd_dec / _bwd / _bwd_dec).  Copies seven counters: out[0]
+ * forward calls that ran as one persistent program (static walk, interpreter or row groups; blvm_pchain_static(-2) tells the static
+ * walks apart), out[1] those that ran one launch per link and step, out[2] / out[3] the same for the backward, out[4] the calls of
+ * out[0] and out[2] whose program ran on row groups (one count per call); out[5] / out[6] the linear-link launches of the
+ * launch-per-link loops that ran on 16x16 / on 32x32 tiles (one count per launch).  Host-side; never touches the device. */
+int blvm_vrnn_path_counts(unsigned long long out[7]);
+/* The same for the SRNN latent chain (K3; blvm_srnn_latent_fwd / _bwd), laid out as blvm_rssm_path_counts: out[0] / out[1] forward
+ * calls on the persistent program / on launch-per-link, out[2] / out[3] the backward, out[4] / out[5] the linear-link launches of
+ * the launch-per-link loops (the backward's initial-latent links included) on 16x16 / on 32x32 tiles. */
+int blvm_srnn_path_counts(unsigned long long out[6]);
 /* Diagnostics / unit test of the persistent-chain engine on its own: L dependent links x_{s+1} = relu(x_s W^T + b), [B,N] x [N,N],
  * as ONE launch.  W16: W [N,N] in the T16 operand layout (blvm_pchain_rows_to_t16 of W: a weight's rows are the "batch");
  * x16: L+1 T16 slabs of ceil(B/16)*16 x N floats, slab 0 = x_0 in T16 (blvm_pchain_rows_to_t16); xs: L row-major [B,N] outputs.

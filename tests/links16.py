@@ -262,12 +262,11 @@ def srnn_id(c):
 
 
 @functools.lru_cache(maxsize=None)
-def srnn_inputs(case, seed=0, Tp=None):
+def srnn_inputs(case, seed=0, Tp=None, R=SRNN_R):
     """fp32: d, a, z0, eps of unit scale; nn.Linear-style parameters; lengths in steps (row 0 full, one row of length 1); the
     upstream gradient `w` of zs[1:]."""
     T_, B, H, Z, has_z0, _, _ = case
     Tp = T_ if Tp is None else Tp
-    R = SRNN_R
     g = torch.Generator().manual_seed(100000 * seed + 1000 * H + 10 * B + Tp + 7 * int(has_z0))
     p = {}
     for c in ("prior", "post"):
@@ -281,31 +280,32 @@ def srnn_inputs(case, seed=0, Tp=None):
                 eps=torch.randn(Tp, B, Z, generator=g), w=torch.randn(Tp, B, Z, generator=g), lens=lens, **p)
 
 
-def _kl_terms(out, forced, lens, dtype):
-    """kld, kld_fn [B] over the rows' lengths (stride 1).  Which elements sit on the free-nats floor is decided from the FORCED
-    statistics where there are any (they are stored fp32 values too): max(kl, floor) has a kink, and an element within a flip of the
+def _kl_terms(out, forced, lens, dtype, stride=1, free_nats=SRNN_FREE_NATS):
+    """kld, kld_fn [B] over the rows' lengths: step t of row b is live where t * stride < lens[b].  Which elements sit on the
+    free-nats floor (free_nats / Z per element) is decided from the FORCED statistics where there are any (they are stored fp32 values too): max(kl, floor) has a kink, and an element within a flip of the
     floor would otherwise switch its whole gradient on or off between two evaluations."""
     Tp = out["mu_q"].shape[0]
-    mask = (torch.arange(Tp).unsqueeze(1) < lens.unsqueeze(0)).to(dtype).unsqueeze(-1)  # [T',B,1]
+    mask = (torch.arange(Tp).unsqueeze(1) * stride < lens.unsqueeze(0)).to(dtype).unsqueeze(-1)  # [T',B,1]
     kl = O.kl_gaussian(out["mu_q"], out["sd_q"], out["mu_p"], out["sd_p"])
-    floor = SRNN_FREE_NATS / kl.shape[-1]
+    floor = free_nats / kl.shape[-1]
     decide = kl if forced is None else O.kl_gaussian(*(forced[k].detach().cpu().to(dtype) for k in ("mu_q", "sd_q", "mu_p", "sd_p")))
     kl_fn = torch.where(decide > floor, kl, torch.full_like(kl, floor))
     return (kl * mask).sum((0, 2)), (kl_fn * mask).sum((0, 2))
 
 
-def srnn_oracle(inp, mode, case, dtype=torch.float64, forced_zs=None, backward=False, forced_stats=None):
+def srnn_oracle(inp, mode, case, dtype=torch.float64, forced_zs=None, backward=False, forced_stats=None, stride=1, free_nats=SRNN_FREE_NATS, pre_out=None,
+                coef=(SRNN_C_RAW, SRNN_C_FN)):
     """-> dict over SRNN_STATS (+ kld, kld_fn [B]; with `backward`: d_d, d_a, d_z0, d_<param>) of `O.srnn_latent_rounded_ref`; the
     loss of the backward is (zs[1:] * w).sum() + (SRNN_C_RAW * kld + SRNN_C_FN * kld_fn).sum()."""
     Z, residual, rec = case[3], case[5], case[6]
     names = ("d", "a") + (("z0",) if inp["z0"] is not None else ()) + O.SRNN_CHAIN_PARAMS
     lv = {n: inp[n].clone().to(dtype).requires_grad_(backward) for n in names}
     forced = None if forced_zs is None else forced_zs.detach().cpu().to(dtype)
-    res = O.srnn_latent_rounded_ref(lv["d"], lv["a"], lv.get("z0"), inp["eps"].to(dtype), lv, residual, O.operand_rounding(mode), rec, forced)
+    res = O.srnn_latent_rounded_ref(lv["d"], lv["a"], lv.get("z0"), inp["eps"].to(dtype), lv, residual, O.operand_rounding(mode), rec, forced, pre_out=pre_out)
     out = dict(zip(SRNN_STATS, res))
-    out["kld"], out["kld_fn"] = _kl_terms(out, forced_stats, inp["lens"], dtype)
+    out["kld"], out["kld_fn"] = _kl_terms(out, forced_stats, inp["lens"], dtype, stride, free_nats)
     if backward:
-        ((out["zs"][1:] * inp["w"].to(dtype)).sum() + (SRNN_C_RAW * out["kld"] + SRNN_C_FN * out["kld_fn"]).sum()).backward()
+        ((out["zs"][1:] * inp["w"].to(dtype)).sum() + (coef[0] * out["kld"] + coef[1] * out["kld_fn"]).sum()).backward()
         out.update({"d_" + n: lv[n].grad for n in names})
     return {k: v.detach() for k, v in out.items()}
 
@@ -341,10 +341,9 @@ def vrnn_id(c):
 
 
 @functools.lru_cache(maxsize=None)
-def vrnn_inputs(case, seed=0, Tp=None):
+def vrnn_inputs(case, seed=0, Tp=None, X=VRNN_X, R=VRNN_R):
     T_, B, H, Z, has_h0 = case
     Tp = T_ if Tp is None else Tp
-    X, R = VRNN_X, VRNN_R
     g = torch.Generator().manual_seed(100000 * seed + 1000 * H + 10 * B + Tp + 3 * int(has_h0) + 1)
     shapes = dict(prior_w0=(H, R), prior_w1=(H, H), prior_w2=(H, H), prior_hw=(2 * Z, H), post_w0=(H, R + X), post_w1=(H, H), post_w2=(H, H), post_hw=(2 * Z, H),
                   phi_w0=(H, Z), phi_w1=(H, H), phi_w2=(H, H), phi_w3=(H, H), gru_wih=(3 * R, X + H), gru_whh=(3 * R, R))
@@ -362,19 +361,23 @@ def vrnn_inputs(case, seed=0, Tp=None):
     return inp
 
 
-def vrnn_oracle(inp, mode, case, dtype=torch.float64, forced=None, backward=False):
+def vrnn_oracle(inp, mode, case, dtype=torch.float64, forced=None, backward=False, residual=True, stride=1, free_nats=SRNN_FREE_NATS, forced_stats=None,
+                kl=False, pre_out=None, coef=(SRNN_C_RAW, SRNN_C_FN)):
     """-> dict(decin, mu_q, sd_q, mu_p, sd_p, z) of `O.vrnn_sequence_rounded_ref`; forced: dict(decin, z), the kernel's stores.
     backward: also kld, kld_fn [B] over the rows' lengths (stride 1) and d_enc, d_h0, d_<param> of the loss
-    (decin * w).sum() + (SRNN_C_RAW * kld + SRNN_C_FN * kld_fn).sum()."""
+    (decin * w).sum() + (SRNN_C_RAW * kld + SRNN_C_FN * kld_fn).sum().
+    residual: the posterior's mean is added to the prior's.  kl: kld, kld_fn also without `backward`.  forced_stats: a result dict whose
+    statistics decide the free-nats branch (`_kl_terms`) where nothing is teacher forced (default: `forced`)."""
     names = ("enc",) + (("h0",) if inp["h0"] is not None else ()) + O.VRNN_SEQ_PARAMS
     lv = {n: inp[n].clone().to(dtype).requires_grad_(backward) for n in names}
     f = None if forced is None else {k: forced[k].detach().cpu().to(dtype) for k in ("decin", "z")}
     with torch.set_grad_enabled(backward):
-        res = O.vrnn_sequence_rounded_ref(lv["enc"], lv.get("h0"), inp["eps"].to(dtype), lv, True, O.operand_rounding(mode), True, f)
+        res = O.vrnn_sequence_rounded_ref(lv["enc"], lv.get("h0"), inp["eps"].to(dtype), lv, residual, O.operand_rounding(mode), True, f, pre_out=pre_out)
         out = dict(zip(("decin",) + VRNN_STATS, res))
+        if backward or kl:
+            out["kld"], out["kld_fn"] = _kl_terms(out, forced if forced_stats is None else forced_stats, inp["lens"], dtype, stride, free_nats)
         if backward:
-            out["kld"], out["kld_fn"] = _kl_terms(out, forced, inp["lens"], dtype)
-            ((out["decin"] * inp["w"].to(dtype)).sum() + (SRNN_C_RAW * out["kld"] + SRNN_C_FN * out["kld_fn"]).sum()).backward()
+            ((out["decin"] * inp["w"].to(dtype)).sum() + (coef[0] * out["kld"] + coef[1] * out["kld_fn"]).sum()).backward()
             out.update({"d_" + n: lv[n].grad for n in names})
     return {k: v.detach() for k, v in out.items()}
 
@@ -404,7 +407,7 @@ KINK = 2e-5  # what ONE flipped fp16 operand moves a hidden pre-activation by: 2
 
 
 @functools.lru_cache(maxsize=None)
-def bwd_inputs(family, case, seed=0):
+def bwd_inputs(family, case, seed=0, kink=KINK):
     """The inputs at T' = BWD_T.  A batch row in which a hidden pre-activation lies within KINK of zero (float64, either mode)
     carries no loss: its upstream gradient is zero and its length 0.  One flipped operand puts such a unit on the other branch of its
     (Leaky)ReLU, the kernel's saved activation and the oracle's then disagree about the derivative (1 against 0.01 or 0), and the
@@ -423,7 +426,7 @@ def bwd_inputs(family, case, seed=0):
                 O.srnn_latent_rounded_ref(lv["d"], lv["a"], lv.get("z0"), lv["eps"], lv, case[5], O.operand_rounding(mode), case[6], pre_out=pre)
             else:
                 O.vrnn_sequence_rounded_ref(lv["enc"], lv.get("h0"), lv["eps"], lv, True, O.operand_rounding(mode), True, pre_out=pre)
-        near |= torch.stack([p.abs().min(1).values for p in pre]).min(0).values < KINK
+        near |= torch.stack([p.abs().min(1).values for p in pre]).min(0).values < kink
     inp["w"][:, near] = 0
     inp["lens"][near] = 0
     inp["near_kink"] = near

@@ -49,6 +49,17 @@ def test_rssm_path_counts_is_a_host_side_read():
     assert lib.blvm_rssm_path_counts(None) != 0 and b"null" in lib.blvm_last_error()
 
 
+@pytest.mark.parametrize("entry,words", [("blvm_vrnn_path_counts", 7), ("blvm_srnn_path_counts", 6)])
+def test_chain_path_counts_are_host_side_reads(entry, words):
+    """`blvm_vrnn_path_counts` / `blvm_srnn_path_counts` copy seven / six host counters (no device needed): every word is written
+    (two buffers with different prefills come back equal), reading does not change them, and a null pointer is refused."""
+    fn = getattr(_hip.load(), entry)
+    a, b = (ctypes.c_ulonglong * words)(*([2**63 + 7] * words)), (ctypes.c_ulonglong * words)(*([2**63 + 9] * words))
+    assert fn(a) == 0 and fn(b) == 0
+    assert list(a) == list(b) and max(a) < 2**63
+    assert fn(None) != 0 and b"null" in _hip.load().blvm_last_error()
+
+
 def test_pchain_configure_accepts_only_the_built_wave_count():
     """The persistent kernels exist for 16 waves per workgroup only: `waves` <= 0 or 16 leaves the configuration as it is, any other
     count is refused with a message instead of being ignored."""
