@@ -921,7 +921,7 @@ class _VRNNSeqFunction(torch.autograd.Function):
             dz3, M, DH, SF, slope = _f32c(d_dec), Tp * B, W2.shape[0], W3.shape[0], ctx.dec_slope
             dy2, dy1 = torch.empty(M, DH, **f32), torch.empty(M, DH, **f32)
             grads = _zeros_like_many(params)
-            d_enc = torch.empty_like(enc)
+            d_enc = torch.empty_like(enc) if ctx.needs_input_grad[0] else None  # (not asked for: the library skips its products)
             d_h0 = torch.empty(B, R, **f32) if ctx.has_h0 else None
             w, g = _pack_weights(params), _pack_weights(grads, _hip.VrnnGrads)
             folded = ctypes.c_int(0)
@@ -969,7 +969,7 @@ class _VRNNSeqFunction(torch.autograd.Function):
         params = params[:28]  # (a decoder whose output went unused: no gradient)
         d_decin = _f32c(d_decin) if d_decin is not None else torch.zeros_like(decin)
         grads = _zeros_like_many(params)
-        d_enc = torch.empty_like(enc)
+        d_enc = torch.empty_like(enc) if ctx.needs_input_grad[0] else None  # (not asked for: the library skips its products)
         d_h0 = torch.empty(B, R, **f32) if ctx.has_h0 else None
         ws = torch.empty(lib.blvm_vrnn_bwd_workspace_floats(Tp, B, X, H, Z, R), **f32)
         w, g = _pack_weights(params), _pack_weights(grads, _hip.VrnnGrads)

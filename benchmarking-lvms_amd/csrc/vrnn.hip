@@ -236,10 +236,13 @@ struct BwdWs {
   // row-major gradient of the decoder's input [T',B,H+R] (inside the sentinel-filled stretch), and the transposed T16 copies of the
   // three weights (behind everything else)
   float *DY216, *DY116, *DD, *dT[3];
+  // d_enc follower of the backward launch (enc; vrnn_static.h): the transposed T16 copies of the encoding's columns of the GRU input
+  // weight and of the posterior's first layer, and the polled row-major product EP = DGI W_ih[:, :X] [T',B,X] — behind everything
+  // else, so the pieces above sit where a call that does not fold looks for them
+  float *wixT, *qxT, *EP;
 };
 
-size_t carve_ws(float* base, int Tp, int B, int X, int H, int Z, int R, BwdWs* w, int SF = 0) {
-  (void)X;
+size_t carve_ws(float* base, int Tp, int B, int X, int H, int Z, int R, BwdWs* w, int SF = 0, bool enc = false) {
   const size_t n = (size_t)Tp * B;
   Arena ar{base};
   BwdWs t;
@@ -272,6 +275,8 @@ size_t carve_ws(float* base, int Tp, int B, int X, int H, int Z, int R, BwdWs* w
     t.DPHI3b = ar.take(n * H); t.DPHI3c = ar.take(n * H);
     if (SF > 0) { t.dT[0] = ar.take((size_t)(H + R) * H); t.dT[1] = ar.take((size_t)H * H); t.dT[2] = ar.take((size_t)H * SF); }
   }
+  t.wixT = t.qxT = t.EP = nullptr;
+  if (enc) { t.wixT = ar.take((size_t)3 * R * X); t.qxT = ar.take((size_t)H * X); t.EP = ar.take(n * X); }
   if (w) *w = t;
   return ar.floats();
 }
@@ -338,6 +343,22 @@ bool vrnn_dec_bwd_folds(int Tp, int B, int H, int Z, int R, int DH, int SF) {
   return dl.split3 && dl.bdec[0].nwg > 0;
 }
 
+// d_enc = DQ0 Wq0[:, R:] + DGI W_ih[:, :X] on the backward walk's posterior half (vrnn_static.h "d_enc follower") instead of two K6
+// launches behind the walk.  blvm_vrnn_enc_bwd_fold; env BLVM_VRNN_ENC_BWD_FOLD=0: never
+int g_enc_bwd_fold = [] { const char* e = getenv("BLVM_VRNN_ENC_BWD_FOLD"); return e ? (atoi(e) != 0 ? 1 : 0) : 1; }();
+long g_enc_bwd_folded = 0;  // backward calls that computed d_enc inside the launch
+// Whether a backward call that asks for d_enc folds it: fp32 operands on 16-row tiles without row groups, the static walk's widths
+// with X = H, the split3 program on its own-range deal, a deal that gives every workgroup of the posterior half one follower tile,
+// and a walk long enough to arm its slabs (vrnn_static.h kArmAhead).  The workspace is grown under the same conditions.
+bool vrnn_enc_bwd_folds(int Tp, int B, int X, int H, int Z, int R) {
+  if (!g_enc_bwd_fold || !vrnn_persistent(B) || device_cus() < 32 || operand_16bit() || pchain_optype(B) != OP_F32) return false;
+  if (B > 64 || vrnn_row_groups(B) || Z != H || X != H || H != 256 || R != 512 || Tp <= pchain::kArmAhead) return false;
+  const int tl = (B + 15) / 16;
+  if (vrnn_shared_deal(false, tl)) return false;
+  const pchain::VrnnBwdDeal dl = pchain::vrnn_bwd_deal(H / 16, Z / 16, R / 16, tl, device_cus() & ~7, false, pchain_split3(), 0, X / 16);
+  return dl.split3 && dl.benc[0].nwg > 0;
+}
+
 // which implementation the sequence entry points took and which tiles their per-link loops ran on (blvm_vrnn_path_counts):
 // host-side counts, [0..4] one per call ([4]: the calls of [0] and [2] whose program ran on row groups), [5..6] one per launch_lin
 enum { VRNN_FWD_PROGRAM = 0, VRNN_FWD_PER_LINK = 1, VRNN_BWD_PROGRAM = 2, VRNN_BWD_PER_LINK = 3, VRNN_ROW_GROUPS = 4, VRNN_LIN16 = 5, VRNN_LIN32 = 6 };
@@ -380,10 +401,17 @@ extern "C" int blvm_vrnn_dec_fold(int mode) {
 }
 
 extern "C" size_t blvm_vrnn_bwd_workspace_floats(int Tp, int B, int X, int H, int Z, int R) {
-  return carve_ws(nullptr, Tp, B, X, H, Z, R, nullptr);
+  return carve_ws(nullptr, Tp, B, X, H, Z, R, nullptr, 0, vrnn_enc_bwd_folds(Tp, B, X, H, Z, R));  // (grown only where d_enc folds)
 }
 extern "C" size_t blvm_vrnn_bwd_dec_workspace_floats(int Tp, int B, int X, int H, int Z, int R, int DH, int SF) {
-  return carve_ws(nullptr, Tp, B, X, H, Z, R, nullptr, vrnn_dec_bwd_folds(Tp, B, H, Z, R, DH, SF) ? SF : 0);  // (grown only where the call folds)
+  return carve_ws(nullptr, Tp, B, X, H, Z, R, nullptr, vrnn_dec_bwd_folds(Tp, B, H, Z, R, DH, SF) ? SF : 0,  // (grown only where the call folds)
+                  vrnn_enc_bwd_folds(Tp, B, X, H, Z, R));
+}
+extern "C" int blvm_vrnn_enc_bwd_fold(int mode) {
+  if (mode == -2) return (int)std::min<long>(g_enc_bwd_folded, 0x7fffffffL);
+  const int was = g_enc_bwd_fold;
+  if (mode >= 0) g_enc_bwd_fold = mode != 0;
+  return was;
 }
 extern "C" int blvm_vrnn_dec_bwd_fold(int mode) {
   if (mode == -2) return (int)std::min<long>(g_dec_bwd_folded, 0x7fffffffL);
@@ -651,8 +679,11 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   BLVM_REQUIRE(aligned16(workspace) && aligned16(reserve) && aligned16(d_decin), "vrnn_bwd: buffers must be 16-byte aligned");
   Reserve rs;
   carve_reserve(const_cast<float*>(reserve), Tp, B, H, Z, R, &rs);
+  // d_enc inside the launch: the workspace is blvm_vrnn_bwd_workspace_floats' under the same blvm_vrnn_enc_bwd_fold mode
+  const bool encf = d_enc != nullptr && vrnn_enc_bwd_folds(Tp, B, X, H, Z, R);
+  BLVM_REQUIRE(!encf || aligned16(d_enc), "vrnn_bwd: d_enc must be 16-byte aligned");
   BwdWs ws;
-  carve_ws(workspace, Tp, B, X, H, Z, R, &ws, dec ? dec->SF : 0);
+  carve_ws(workspace, Tp, B, X, H, Z, R, &ws, dec ? dec->SF : 0, encf);
   const size_t n = (size_t)Tp * B;
   const int ldd = H + R;
   const float beta = softplus_beta_of(sd_eps);
@@ -675,6 +706,10 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     BLVM_TRY(t16_pack_transposed(dec->w[0], H + R, H, H + R, ws.dT[0], s));
     BLVM_TRY(t16_pack_transposed(dec->w[1], H, H, H, ws.dT[1], s));
     BLVM_TRY(t16_pack_transposed(dec->w[2], H, dec->SF, H, ws.dT[2], s));
+  }
+  if (encf) {  // the follower's two: the encoding's columns of the GRU input weight and of the posterior's first layer
+    BLVM_TRY(t16_pack_transposed(w->gru_wih, X + H, 3 * R, X, ws.wixT, s));
+    BLVM_TRY(t16_pack_transposed(w->post_w[0] + R, R + X, H, X, ws.qxT, s));
   }
   BLVM_TRY(pack_scope.flush());  // all packs above in one launch
 
@@ -707,7 +742,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
   // CU slots and memory-pipeline share from the chain's links; removed.)
   const float* hprev_all = decin + H;  // [n rows, ld = H+R]
   auto batched = [&]() -> int {
-    if (d_enc) {
+    if (d_enc && !encf) {
       BLVM_TRY(gemm_f32(0, 1, (int)n, X, H, ws.DQ[0], H, w->post_w[0] + R, R + X, d_enc, X, nullptr, 0, 0.f, nullptr, 0, 0, 1, s));
       BLVM_TRY(gemm_f32(0, 1, (int)n, X, 3 * R, ws.DGI, 3 * R, w->gru_wih, X + H, d_enc, X, nullptr, 0, 0.f, nullptr, 0, 1, 1, s));
     }
@@ -752,8 +787,9 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     // (shared deal: see vrnn_fwd -- here the gentle link is GB, which the posterior half runs while the prior half
     // takes the gradient back through the phi_z run and the heads)
     const bool shared = vrnn_shared_deal(groups, tl);
-    const VrnnBwdDeal dl = vrnn_bwd_deal(ctH, ctZ, ctR, tl, cus, shared, pchain_split3(), dec ? (H + R) / 16 : 0);  // (vrnn_static.h: the ranges of every link)
+    const VrnnBwdDeal dl = vrnn_bwd_deal(ctH, ctZ, ctR, tl, cus, shared, pchain_split3(), dec ? (H + R) / 16 : 0, encf ? X / 16 : 0);  // (vrnn_static.h: the ranges of every link)
     BLVM_REQUIRE(!dec || (dl.split3 && dl.bdec[0].nwg > 0 && !groups), "vrnn_bwd: the deal has no decoder leader range");
+    BLVM_REQUIRE(!encf || (dl.split3 && dl.benc[0].nwg > 0 && !groups), "vrnn_bwd: the deal has no range for the d_enc follower");
     Builder bld;
     bld.begin(pchain_optype(B), T + 1, B, groups ? 8 : 2, true, dl.g);
     bld.p.rt_group = RTG;
@@ -844,10 +880,24 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       b2.p[LIN_A] = lead(ws.DY116, xH); b2.p[LIN_W] = ws.dT[0]; b2.p[LIN_ORM] = lead(ws.DD, sD); b2.ld[LD_OUT] = ldd;
       add_desc(bld, K_LIN, (H + R) / 16, dl.bdec[2].wg0, dl.bdec[2].nwg, H, DF_RM_SC1 | DF_GENTLE | DF_CANARY, 0, T - L, b2);
     }
+    if (encf) {
+      // the d_enc follower (vrnn_static.h): walk step s computes the rows of the time step of walk step s - kBencLag, whose DQ0 the
+      // posterior run published at the end of that step — the pointers start a slab back, the links begin a step late and use the
+      // walk's last step.  EP: the K = 3R product, polled by the K = H link of the same tile on the same workgroup.
+      const long sX = (long)B * X;
+      auto lag = [&](const float* base, long step) { return rev(base, step, T - 1 + kBencLag); };
+      Operands e0, e1;
+      e0.p[LIN_A] = lag(ws.DGI16, x3R); e0.p[LIN_W] = ws.wixT; e0.p[LIN_ORM] = lag(ws.EP, sX); e0.ld[LD_OUT] = X;
+      add_desc(bld, K_LIN, X / 16, dl.benc[0].wg0, dl.benc[0].nwg, 3 * R, DF_RM_SC1 | DF_GENTLE | DF_CANARY, kBencLag, T + 1, e0);
+      e1.p[LIN_A] = lag(ws.DQ16[0], xH); e1.p[LIN_W] = ws.qxT; e1.p[LIN_ADD] = lag(ws.EP, sX); e1.ld[LIN_LD_ADD] = X;
+      e1.p[LIN_ORM] = lag(d_enc, sX); e1.ld[LD_OUT] = X;
+      add_desc(bld, K_LIN, X / 16, dl.benc[1].wg0, dl.benc[1].nwg, H, DF_ADD_POLLED | DF_GENTLE | DF_CANARY, kBencLag, T + 1, e1);
+    }
     // what the launch polls gets sentinels: GA, GB (single words) and the T16 copies, from the host or slab by slab from the walk
     // (vrnn_static.h ArmPlan; the table's walk step j is time step T' - 1 - j)
     ArmPlan plan;
     plan.fill(ws.GA, ws.x16_bytes);
+    if (encf) plan.fill(ws.EP, sizeof(float) * n * X);
     if (!groups) {
       plan.add(arm_rm(ws.GA, R, B, T, true)); plan.add(arm_rm(ws.GB, R, B, T, true));
       for (int i = 0; i < 3; ++i) { plan.add(arm_t16(ws.DP16[i], H, rt, T, true)); plan.add(arm_t16(ws.DQ16[i], H, rt, T, true)); }
@@ -856,6 +906,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
       plan.add(arm_t16(ws.DPH16, 2 * Z, rt, T, true)); plan.add(arm_t16(ws.DQH16, 2 * Z, rt, T, true));
       plan.add(arm_t16(ws.DPHI16b, H, rt, T, true)); plan.add(arm_t16(ws.DPHI16c, H, rt, T, true));
       if (dec) { plan.add(arm_t16(ws.DY216, H, rt, T, true)); plan.add(arm_t16(ws.DY116, H, rt, T, true)); plan.add(arm_rm(ws.DD, ldd, B, T, true)); }
+      if (encf) plan.add(arm_rm(ws.EP, X, B, T, true));  // (the slab of the table's walk step j is stored at walk step j + kBencLag)
     }
     // the leader's first rows (time steps T' - kBdecAhead .. T' - 1) as K6 products, behind the fill: the walk polls their DD slabs
     auto lead_rows = [&]() -> int {
@@ -868,6 +919,7 @@ static int vrnn_seq_bwd_impl(const BlvmVrnnWeights* w, const float* enc, const f
     };
     BLVM_TRY(vrnn_launch(bld, false, "vrnn_bwd", s, plan, lead_rows));
     if (dec) ++g_dec_bwd_folded;
+    if (encf) ++g_enc_bwd_folded;
     if (split3) {  // DPHI[3] += the two other partial sums
       const size_t n4 = n * H / 4;
       hipLaunchKernelGGL(add3_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, reinterpret_cast<float4*>(ws.DPHI[3]),

@@ -70,12 +70,22 @@ inline VrnnFwdDeal vrnn_fwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, boo
 // workgroups) TileIter gives the workgroup of part[2]'s tile (r, c) the tile (r, c) of bdec[2] too, in both modes: the addend a
 // partial-sum tile polls is the one its own workgroup stored.  Empty (nwg = 0 in all three) where a link does not fit.
 constexpr int kBdecAhead = 2;  // walk steps the leader runs ahead (at most kArmAhead - 2: see arm_applies)
+// backward, d_enc follower (ctX > 0 = the column tiles of the encoding, X / 16; split3 only): the posterior half, which owns no tile
+// of the summing link, the phi_z run or dz and waits between its partial-sum tile and its run, computes the gradient wrt the
+// encoding of the time step one walk step BEHIND the chain (DQ0[t] is published at the end of its own walk step), two gentle links
+// on the range of `post`:
+//   benc[0]  EP    = DGI W_ih[:, :X]          (K = 3R, weights read per tile; row-major, write-through, polled by benc[1])
+//   benc[1]  d_enc = DQ0 Wq0[:, R:] + EP      (K = H, resident weights; plain stores into the caller's buffer)
+// Both deal ctX tl tiles over the same range, so TileIter gives a workgroup the same tile (r, c) of both, in both modes: the addend
+// a tile polls is the one its own workgroup stored, and every word of EP and d_enc is written once (no atomics: the sum has one
+// order).  Empty (nwg = 0 in both) unless every workgroup of the half gets exactly one tile and none of the wide links reaches it.
+constexpr int kBencLag = 1;  // walk steps the follower runs behind: active on s in [kBencLag, T' + 1), the walk's existing last step
 struct VrnnBwdDeal {
   int def_n, half, g, spare;
   bool split3;
-  LinkRange grub, part[3], dphi, gb, wide_h, dz, prior, post, bdec[3];
+  LinkRange grub, part[3], dphi, gb, wide_h, dz, prior, post, bdec[3], benc[2];
 };
-inline VrnnBwdDeal vrnn_bwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, bool shared, bool allow_split3, int ctD = 0) {
+inline VrnnBwdDeal vrnn_bwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, bool shared, bool allow_split3, int ctD = 0, int ctX = 0) {
   VrnnBwdDeal d;
   d.def_n = shared ? 0 : range_for(ctR * tl, std::min(cus / 4, 64));  // GB link
   d.half = range_for(ctH * tl, (cus - d.def_n) / 2);
@@ -104,6 +114,12 @@ inline VrnnBwdDeal vrnn_bwd_deal(int ctH, int ctZ, int ctR, int tl, int cus, boo
       d.bdec[2] = LinkRange{ctD, w0, n};
     }
   }
+  for (LinkRange& r : d.benc) r = LinkRange{0, 0, 0};
+  if (ctX > 0 && d.split3) {
+    bool fits = ctX * tl == d.post.nwg && d.wide_h.wg0 + d.wide_h.nwg <= d.post.wg0 && d.dz.wg0 + d.dz.nwg <= d.post.wg0;
+    for (bool xcd : {false, true}) fits = fits && tiles_per_workgroup(tl, ctX, d.post.nwg, xcd) <= 1;
+    if (fits) d.benc[0] = d.benc[1] = LinkRange{ctX, d.post.wg0, d.post.nwg};
+  }
   return d;
 }
 
@@ -117,6 +133,9 @@ constexpr std::initializer_list<int> kFwdDecResident = {6, 7, 8};
 // the backward program with the decoder leader: descriptors 10 .. 12 are bdec[0 .. 2] of the deal; bdec[1] is resident
 constexpr int kBwdDesc = 10, kBwdDecDesc = 13;
 constexpr std::initializer_list<int> kBwdDecResident = {11};
+// the backward program with the d_enc follower: benc[0 .. 1] of the deal are the program's LAST two descriptors (10, 11 | behind the
+// decoder leader 13, 14), both on one tile per workgroup; benc[1] is resident
+constexpr int kBwdEncLinks = 2, kBwdEncDesc = kBwdDesc + kBwdEncLinks, kBwdDecEncDesc = kBwdDecDesc + kBwdEncLinks;
 // the converter's condition: every resident link deals a workgroup at most one tile (else the interpreter runs the program)
 // (xcd: the TileIter mode the kernel will deal with — the program's own, or plain under a placement of the launch, below)
 inline bool one_tile_each(const Program& p, std::initializer_list<int> links, bool xcd) {

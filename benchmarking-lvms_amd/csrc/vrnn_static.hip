@@ -56,8 +56,9 @@ __device__ __forceinline__ int tile_count(int lanes) { return __popcll(__ballot(
 // words [kAnatBase + role * kAnatRole + (slot * 2 + class) * 4 + j].  Roles: 0 / 1 forward halves (or the chain probe), 2 / 3
 // backward halves, 4 the backward's spare range.  Slot = 4 * (index of the link in its program) + link of the run.  (With the decoder
 // leader the spare role also leaves, in slots 13 and 14, its walk steps and the ticks it spent in the leader's links, in the arming
-// stores and in the whole loop: bwd_spare_leader.)
-constexpr int kAnatBase = 128, kAnatRole = 512, kAnatSlots = 56;
+// stores and in the whole loop: bwd_spare_leader; with the d_enc follower the backward's posterior half does the same for the
+// follower's links: bwd_post_follower.)
+constexpr int kAnatBase = 128, kAnatRole = 512, kAnatSlots = 64;  // (slots: 4 per descriptor of the longest program, 8 words each: a role's whole stretch)
 #ifdef PCHAIN_TPROF
 __device__ __forceinline__ void anat_begin(unsigned* tab) {
   for (int i = threadIdx.x; i < kAnatSlots * 8; i += blockDim.x) tab[i] = 0u;
@@ -546,10 +547,20 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_fwd_kernel(FwdArgs a) 
   else fwd_half<NW, 1>(a, w, rt, xcd, wk);
 }
 
+// The d_enc follower's two links (vrnn_static.h benc) in a compact form — a launch's arguments are 4 KB at most and BwdArgs is
+// close to it: only what an empty LinArgs and the rest of BwdArgs do not say already.  The links' operands are the GRU backward's
+// DGI16 and the posterior run's last output DQ16[0], a walk step back; their range is the posterior run's (the converter checks both).
+struct EncArgs {
+  float *ep, *out;       // benc[0]: EP = DGI16 W0;  benc[1]: out = DQ16[0] W1 + EP  (at walk step 0: a slab behind the chain's)
+  const float *W0, *W1;
+  int stride;            // of both, per walk step (floats)
+};
+
 // Backward program (vrnn.hip vrnn_seq_bwd_impl, split3 form): 0 GRU backward (steps 0 .. T'), 1 .. 3 the K = 3R dphi product as
 // three K = R partial-sum links (prior half | posterior half | spare range), 4 GB (gentle, K = 3R), 5 the summing link, 6 phi_z
 // run of two, 7 dz, 8 prior run (K = 2Z, H, H), 9 posterior run; with the decoder leader (nbdec = 3, vrnn_static.h) 10 .. 12 the
-// decoder MLP's three data-gradient links on the spare range.
+// decoder MLP's three data-gradient links on the spare range; with the d_enc follower (nenc = 2) the program's last two descriptors
+// are its links on the posterior half.
 struct BwdArgs {
   GrubArgs grub;
   LinArgs part[3], gb, sum;
@@ -558,6 +569,8 @@ struct BwdArgs {
   SeqArgs run[2];
   LinArgs bdec[3];
   Deal deal[kBwdDecDesc];
+  EncArgs enc;
+  int nenc;   // 0 | 2: the d_enc follower on the posterior half
   int nbdec;  // 0 | 3: the decoder leader on the spare range
   int bdec_k, gb_ldadd2;  // K of bdec[0] (the decoder's output width); GB's second addend, the h part of the decoder's gradient
   SPtr gb_add2;
@@ -568,6 +581,19 @@ struct BwdArgs {
 };
 
 static_assert(sizeof(BwdArgs) <= 4096 && sizeof(FwdArgs) <= 4096, "kernel argument size");
+__device__ __forceinline__ SPtr lagged(const SPtr& p) { return SPtr{p.base - (long)kBencLag * p.stride, p.stride}; }  // walk step s -> the slab of step s - kBencLag
+__device__ __forceinline__ LinArgs enc_lin(const BwdArgs& a, int k) {
+  LinArgs q{};
+  q.a = lagged(k == 0 ? a.grub.dgi16 : a.run[1].o16[2]);
+  q.orm = SPtr{k == 0 ? a.enc.ep : a.enc.out, a.enc.stride};
+  if (k == 1) { q.add = SPtr{a.enc.ep, a.enc.stride}; q.ld1 = kH; }
+  q.W = k == 0 ? a.enc.W0 : a.enc.W1;
+  q.ld3 = kH;  // (X = H: the converter checks it)
+  return q;
+}
+__device__ __forceinline__ Deal enc_deal(const BwdArgs& a, int k) {
+  return Deal{a.deal[9].wg0, a.deal[9].nwg, kH / 16, kBencLag, a.S, (a.nbdec != 0 ? kBwdDecDesc : kBwdDesc) + k};
+}
 
 // a workgroup of the prior (HALF 0) or posterior (1) half: its half's partial sum and run of three and whatever tile of the GRU
 // backward, the summing link, the phi_z run and dz the deal gives it, all on resident weights
@@ -649,7 +675,56 @@ __device__ __forceinline__ void bwd_spare_leader(const BwdArgs& a, int w, int rt
 #endif
 }
 
+// a workgroup of the posterior half with the d_enc follower (vrnn_static.h): the deal gives it no tile of the summing link, the phi_z
+// run or dz, so between its partial-sum tile and its run it waits while the prior half walks those — and computes its tile of the
+// gradient wrt the encoding of the previous walk step's time step in that window: EP = DGI W_ih[:, :X] (weights read per tile), then
+// d_enc = DQ0 Wq0[:, R:] + EP on resident weights, the addend polled where its own threads stored it.  Both operands were published
+// a walk step ago, so neither link waits.  A role of its own, as fwd_post_arming: without the fragments of the links it never runs
+// it has the registers, and the other workgroups' code stays what it was.
+constexpr int kBenc0Flags = DF_RM_SC1 | DF_GENTLE | DF_CANARY, kBenc1Flags = DF_ADD_POLLED | DF_GENTLE | DF_CANARY;
 template <int NW>
+__device__ __forceinline__ void bwd_post_follower(const BwdArgs& a, int w, int rt, bool xcd, Walk& wk) {
+  const int t0 = tile_lanes(w, a.deal[0].wg0, a.deal[0].nwg, rt, a.deal[0].ct, xcd), n0 = tile_count(t0);
+  const int t1 = tile_lanes(w, a.deal[2].wg0, a.deal[2].nwg, rt, a.deal[2].ct, xcd), n1 = tile_count(t1);
+  const int t8 = tile_lanes(w, a.deal[9].wg0, a.deal[9].nwg, rt, a.deal[9].ct, xcd), n8 = tile_count(t8);
+  const int te = tile_lanes(w, a.deal[9].wg0, a.deal[9].nwg, rt, kH / 16, xcd), ne = tile_count(te);
+  Res<kH, 2> grub;
+  Res<kR> part;
+  RunRes<3, 2 * kH, kH> run;
+  Res<kH> wq;
+  load_grub<NW>(grub, kargs<BwdArgs>().grub, t0, n0);
+  load_lin<NW, kR>(part, kargs<BwdArgs>().part[1].W, kargs<BwdArgs>().part[1].w_width, t1, n1);
+  load_run<NW>(run, kargs<BwdArgs>().run[1], t8, n8);
+  load_lin<NW, kH>(wq, kargs<BwdArgs>().enc.W1, kH, te, ne);
+#ifdef PCHAIN_TPROF
+  unsigned long long follow = 0;
+  const unsigned long long tb = wall_clock64();
+#endif
+  for (int s = a.s0; s < a.S; ++s) {
+    visit_grub<NW, Paced>(kargs<BwdArgs>().grub, kargs<BwdArgs>().deal[0], s, t0, n0, wk, grub);
+    visit_lin<NW, kR, 0, Paced>(kargs<BwdArgs>().part[1], kargs<BwdArgs>().deal[2], s, t1, n1, wk, part);
+    ANAT(const unsigned long long f0 = wall_clock64();)
+    visit_lin<NW, 3 * kR, kBenc0Flags>(enc_lin(kargs<BwdArgs>(), 0), enc_deal(kargs<BwdArgs>(), 0), s, te, ne, wk, WMem());
+    visit_lin<NW, kH, kBenc1Flags>(enc_lin(kargs<BwdArgs>(), 1), enc_deal(kargs<BwdArgs>(), 1), s, te, ne, wk, wq);
+    ANAT(follow += wall_clock64() - f0;)
+    visit_run<NW, 3, 2 * kH, kH, true>(kargs<BwdArgs>().run[1], kargs<BwdArgs>().deal[9], s, t8, n8, wk, run);  // (not paced: see bwd_half)
+  }
+#ifdef PCHAIN_TPROF
+  // slot 13 of the role's table: {walk steps, -, ticks in the follower's links, -}; slot 14: {1, -, ticks of the whole loop, -}
+  const unsigned long long whole = wall_clock64() - tb;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned* q = wk.anat + 13 * 2 * 4;
+    q[0] = (unsigned)(a.S - a.s0); q[2] = (unsigned)follow;
+    q[8] = 1u; q[10] = (unsigned)whole;
+  }
+  anat_end(wk.anat, kargs<BwdArgs>().prof, 3, w == kargs<BwdArgs>().deal[2].wg0);
+#endif
+}
+
+// ENC: the launch runs the d_enc follower (a.nenc != 0).  An instantiation of its own, so that the kernel of every other launch is
+// the code it was: with the role as a run-time branch of one kernel the unfolded step measured 0.05 ms slower than before it existed.
+template <int NW, bool ENC = false>
 __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds_red[];
   const int w = placed_wg(a.place), rt = (a.B + 15) / 16;
@@ -687,6 +762,7 @@ __global__ __launch_bounds__(NW * 64, 1) void vrnn_static_bwd_kernel(BwdArgs a) 
     return;
   }
   if (w < a.deal[2].wg0) bwd_half<NW, 0>(a, w, rt, xcd, wk);
+  else if constexpr (ENC) bwd_post_follower<NW>(a, w, rt, xcd, wk);  // (no workgroup of this half has a tile of the summing link, the phi_z run or dz: the converter)
   else bwd_half<NW, 1>(a, w, rt, xcd, wk);
 }
 
@@ -705,11 +781,12 @@ bool int_strides(const Program& p) {  // SPtr keeps 32-bit strides
 SPtr sptr(const Program& p, const Desc& d, int k) { return SPtr{const_cast<float*>(d.p[k]), (int)p.stride[d.sidx[k]]}; }
 
 // every workgroup of `grid` resident at once (one 16-wave workgroup per CU with `lds` bytes of dynamic LDS), as pchain_run
-// checks it; the dynamic-LDS limit is raised once per process and device.  slot: 0 forward, 1 backward, 2 the probe's chain
+// checks it; the dynamic-LDS limit is raised once per process and device.  slot: 0 forward, 1 backward, 2 the probe's chain,
+// 3 the backward with the d_enc follower
 template <class Kern>
 int static_go(Kern kernel, int slot, int grid, size_t lds, const char* what) {
   static std::mutex mu;
-  static int attr_dev[3] = {-1, -1, -1}, occ[3] = {0, 0, 0};
+  static int attr_dev[4] = {-1, -1, -1, -1}, occ[4] = {0, 0, 0, 0};
   int dev = 0, cus = 0;
   BLVM_HIP(hipGetDevice(&dev));
   BLVM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -893,8 +970,10 @@ int vrnn_static_fwd(const Program& p, hipStream_t stream, const ArmPlan& plan, c
 
 int vrnn_static_bwd(const Program& p, hipStream_t stream, const ArmPlan& plan, const std::function<int()>& pre) {
   int place = kPlaceProgram;
-  const bool lead = p.ndesc == kBwdDecDesc;  // with the decoder leader on the spare range
-  if (vrnn_static_check(p, lead ? kBwdDecDesc : kBwdDesc, kBwdProducts, 8, 9, &place)) return 1;
+  const bool enc = p.ndesc == kBwdEncDesc || p.ndesc == kBwdDecEncDesc;  // with the d_enc follower on the posterior half (the last two descriptors)
+  const bool lead = p.ndesc - (enc ? kBwdEncLinks : 0) == kBwdDecDesc;    // with the decoder leader on the spare range
+  const int nbase = lead ? kBwdDecDesc : kBwdDesc;
+  if (vrnn_static_check(p, nbase + (enc ? kBwdEncLinks : 0), kBwdProducts, 8, 9, &place)) return 1;
   const Desc* d = p.d;
   const int S = p.S;  // T' + 1
   for (int i = 0; i < kBwdDesc; ++i)
@@ -925,6 +1004,25 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream, const ArmPlan& plan, c
     if (!one_tile_each(p, kBwdDecResident, place_xcd(place, p))) return 1;
     if (d[3].p[LIN_ADD] == nullptr || d[4].p[LIN_ADD2] == nullptr || d[1].p[LIN_ADD] != nullptr || d[0].p[GRUB_DD] != nullptr) return 1;
   }
+  if (enc) {
+    // the follower's links: one tile of each on every workgroup of the posterior half, which owns no tile of the links between the
+    // partial sum and the run; a walk step behind the chain from step kBencLag to the walk's last; X = H; the second link's addend
+    // is the first one's output; their operands are the GRU backward's DGI16 and the posterior run's last output, a step back
+    const Desc &e0 = d[nbase], &e1 = d[nbase + 1];
+    const long st_dgi = p.stride[d[0].sidx[GRUB_DGI16]], st_dq = p.stride[d[9].sidx[LINSEQ_O16 + 2]], st_ep = p.stride[e0.sidx[LIN_ORM]];
+    if (e0.p[LIN_A] != d[0].p[GRUB_DGI16] - kBencLag * st_dgi || p.stride[e0.sidx[LIN_A]] != st_dgi) return 1;
+    if (e1.p[LIN_A] != d[9].p[LINSEQ_O16 + 2] - kBencLag * st_dq || p.stride[e1.sidx[LIN_A]] != st_dq || p.stride[e1.sidx[LIN_ORM]] != st_ep) return 1;
+    for (const Desc* e : {&e0, &e1}) {
+      if (e->s_begin != kBencLag || e->s_end != S || e->wg0 != d[9].wg0 || e->nwg != d[9].nwg || e->wg0 != half || e->nwg != gentle - half || e->ct != kH / 16 || e->ct * ((p.B + 15) / 16) != e->nwg) return 1;
+      if (e->p[LIN_A2] || e->p[LIN_A3] || e->p[LIN_O16] || e->p[LIN_O16B] || e->p[LIN_GATE] || e->p[LIN_BIAS] || e->p[LIN_ADD2] || !e->p[LIN_ORM]) return 1;
+      if (e->i[LIN_I_W_WIDTH] != 0 || e->ld[LIN_LD_A] != 0 || e->ld[LD_OUT] != kH) return 1;
+    }
+    if (!shaped(e0, K_LIN, kBenc0Flags, 3 * kR) || !shaped(e1, K_LIN, kBenc1Flags, kH) || e0.p[LIN_ADD] != nullptr) return 1;
+    if (e1.p[LIN_ADD] != e0.p[LIN_ORM] || p.stride[e1.sidx[LIN_ADD]] != st_ep || e1.ld[LIN_LD_ADD] != kH) return 1;
+    if (!one_tile_each(p, {nbase, nbase + 1}, place_xcd(place, p))) return 1;
+    for (int i : {5, 6, 7})
+      if (!within(d[i], 0, half)) return 1;
+  }
   BwdArgs a{};
   const Desc& g = d[0];
   a.grub = GrubArgs{sp(p, g, GRUB_D0_16), sp(p, g, GRUB_D1_16), sp(p, g, GRUB_G_IN), sp(p, g, GRUB_RG), sp(p, g, GRUB_UG), sp(p, g, GRUB_NG), sp(p, g, GRUB_GH),
@@ -943,16 +1041,29 @@ int vrnn_static_bwd(const Program& p, hipStream_t stream, const ArmPlan& plan, c
   a.nbdec = lead ? 3 : 0;
   if (lead) { a.bdec_k = d[kBwdDesc].K; a.gb_add2 = sp(p, d[4], LIN_ADD2); a.gb_ldadd2 = d[4].i[LIN_I_LD_ADD2]; }
   for (int k = 0; k < a.nbdec; ++k) a.bdec[k] = lin_args(p, d[kBwdDesc + k]);
+  a.nenc = enc ? kBwdEncLinks : 0;
+  if (enc) {
+    const Desc &e0 = d[nbase], &e1 = d[nbase + 1];
+    a.enc = EncArgs{const_cast<float*>(e0.p[LIN_ORM]), const_cast<float*>(e1.p[LIN_ORM]), e0.p[LIN_W], e1.p[LIN_W], (int)p.stride[e0.sidx[LIN_ORM]]};
+  }
   int grid = 0;
-  for (int i = 0; i < p.ndesc; ++i) { a.deal[i] = deal_of(d[i], i); grid = std::max(grid, d[i].wg0 + d[i].nwg); }
+  for (int i = 0; i < p.ndesc; ++i) {
+    if (i < nbase) a.deal[i] = deal_of(d[i], i);
+    grid = std::max(grid, d[i].wg0 + d[i].nwg);
+  }
   a.B = p.B; a.s0 = p.s_first; a.S = S; a.xcd = p.xcd; a.place = place; a.ctl = p.ctl;
   ANAT(a.prof = pchain_profile_buffer();)
   // the spare range's workgroups arm around their partial-sum tiles (descriptor 3)
   BLVM_TRY(arm_or_fill(p, plan, 3, {}, spare, d[3].nwg, place_xcd(place, p), stream, &a.arm));
   BLVM_TRY(pre());
   const size_t lds = sizeof(float) * 2 * kBwdProducts * 16 * 256;
-  BLVM_TRY(static_go(&vrnn_static_bwd_kernel<16>, 1, grid, lds, "vrnn_static_bwd"));
-  hipLaunchKernelGGL(vrnn_static_bwd_kernel<16>, dim3(grid), dim3(1024), lds, stream, a);
+  if (enc) {
+    BLVM_TRY(static_go(&vrnn_static_bwd_kernel<16, true>, 3, grid, lds, "vrnn_static_bwd"));
+    hipLaunchKernelGGL((vrnn_static_bwd_kernel<16, true>), dim3(grid), dim3(1024), lds, stream, a);
+  } else {
+    BLVM_TRY(static_go(&vrnn_static_bwd_kernel<16, false>, 1, grid, lds, "vrnn_static_bwd"));
+    hipLaunchKernelGGL((vrnn_static_bwd_kernel<16, false>), dim3(grid), dim3(1024), lds, stream, a);
+  }
   BLVM_CHECK_LAUNCH("vrnn_static_bwd");
   ++g_static_launches;
   if (a.arm.n != 0) ++g_armed_launches;

@@ -519,6 +519,16 @@ int blvm_vrnn_seq_bwd_dec(const BlvmVrnnWeights* w, const float* enc, const floa
                           int SF, float slope, int* folded, void* stream);
 int blvm_vrnn_dec_bwd_fold(int mode);
 
+/* d_enc inside the backward launch: where blvm_vrnn_seq_bwd / blvm_vrnn_seq_bwd_dec are asked for d_enc and the walk is the static
+ * split3 one (fp32 operands, B <= 64 on 16-row tiles, X == H == Z == 256, R == 512, the own-range deal with one tile of [B, X] for
+ * every workgroup of the posterior half, Tp >= 5), d_enc = DQ0 Wq0[:, R:] + DGI W_ih[:, :X] is computed on the walk's posterior half,
+ * one walk step behind the chain, every word written once; otherwise as two K6 products behind the launch, the second accumulating
+ * into the first.  blvm_vrnn_bwd_workspace_floats and blvm_vrnn_bwd_dec_workspace_floats grow where a call would fold: ask for the
+ * workspace under the same mode as the call.
+ * blvm_vrnn_enc_bwd_fold(mode): 0 never folds, 1 (default; env BLVM_VRNN_ENC_BWD_FOLD) folds where it applies, negative only queries;
+ * returns the mode in effect before the call, mode -2 instead the number of backward calls that folded so far. */
+int blvm_vrnn_enc_bwd_fold(int mode);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * K4  single-layer LSTM over a sequence (forward + BPTT).  Replaces `nn.LSTM` on a packed sequence,
  *     `blvm/models/lstm.py:46-55,96-98` (pack_padded_sequence / pad_packed_sequence semantics through `lens`:

@@ -9,7 +9,10 @@ VRNN forward and backward programs of bench.py's shape ([64, T' = 250], H = Z = 
 With the decoder leader on the backward walk's spare range (blvm_vrnn_dec_bwd_fold, the default) the spare role also prints its
 resident leader link and, per walk step, the time it spends in the leader's three links and in the arming stores against the
 whole step; --no-leader runs the same steps with the switch off.  The decoder's gradient dZ3 is the DMoL head's on random
-audio: what the leader costs does not depend on its values."""
+audio: what the leader costs does not depend on its values.
+With the d_enc follower on the backward walk's posterior half (blvm_vrnn_enc_bwd_fold, the default) that role also prints the
+follower's resident link and, per walk step, the time it spends in the follower's two links against the whole step and the wait
+that is left in front of its next critical poll (link 0 of its run); --no-enc-fold runs the same steps with the switch off."""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "benchmarking-lvms_amd"))
@@ -26,7 +29,7 @@ FWD = {4: "prior run, link 0 (K=512, after the GRU)", 5: "prior run, link 1", 6:
 BWD = {0: "GRU backward", 4: "partial sum, prior half (K=512)", 8: "partial sum, posterior half (K=512)", 12: "partial sum, spare range (K=512)",
        20: "summing link", 24: "phi_z run, link 0", 25: "phi_z run, link 1", 28: "dz", 32: "prior run, link 0 (K=512, after dz)",
        33: "prior run, link 1", 34: "prior run, link 2", 36: "posterior run, link 0 (K=512, after dz)", 37: "posterior run, link 1", 38: "posterior run, link 2",
-       44: "decoder leader, dY1 (K=256, resident)"}
+       44: "decoder leader, dY1 (K=256, resident)", 56: "d_enc follower, d_enc (K=256, resident)"}
 
 
 def rows(h, role, names):
@@ -69,11 +72,15 @@ if __name__ == "__main__":
     ap.add_argument("--paced", default="", help="first-poll delays EARLY:EPI for a second pass over the chain probe, comma separated")
     ap.add_argument("--steps", type=int, default=3, help="profiled VRNN train steps")
     ap.add_argument("--no-leader", action="store_true", help="blvm_vrnn_dec_bwd_fold(0): the decoder's data gradients as K6 launches")
+    ap.add_argument("--no-enc-fold", action="store_true", help="blvm_vrnn_enc_bwd_fold(0): d_enc as two K6 launches behind the walk")
     ap.add_argument("--no-chain", action="store_true", help="skip the chain probe rows")
     args = ap.parse_args()
     settings = [(0, 0)] + [tuple(int(v) for v in item.split(":")) for item in args.paced.split(",") if item]
     if args.no_leader:
         lib.blvm_vrnn_dec_bwd_fold(0)
+    enc_fold = getattr(lib, "blvm_vrnn_enc_bwd_fold", None)  # (a library from before the follower: none)
+    if args.no_enc_fold and enc_fold:
+        enc_fold(0)
     for B, N in () if args.no_chain else ((64, 256), (8, 256), (64, 512), (8, 512)):
         for st in settings:
             chain(B, N, args.links, *st)
@@ -87,14 +94,20 @@ if __name__ == "__main__":
 
     for _ in range(2):
         step()
-    n0, f0 = lib.blvm_pchain_static(-2), lib.blvm_vrnn_dec_bwd_fold(-2)
+    n0, f0, e0 = lib.blvm_pchain_static(-2), lib.blvm_vrnn_dec_bwd_fold(-2), enc_fold(-2) if enc_fold else 0
     h = profiled(lambda: [step() for _ in range(args.steps)])
     print(f"VRNN [64, T'=250], {args.steps} train steps, static launches {lib.blvm_pchain_static(-2) - n0}, "
-          f"backward launches with the decoder leader {lib.blvm_vrnn_dec_bwd_fold(-2) - f0}:", flush=True)
+          f"backward launches with the decoder leader {lib.blvm_vrnn_dec_bwd_fold(-2) - f0}, with the d_enc follower "
+          f"{(enc_fold(-2) if enc_fold else 0) - e0}:", flush=True)
     for title, role, names in (("forward, prior half (workgroup 0)", 0, FWD), ("forward, posterior half", 1, FWD), ("backward, prior half (workgroup 0)", 2, BWD),
                                ("backward, posterior half", 3, BWD), ("backward, spare range", 4, BWD)):
         print(f" {title}:", flush=True)
         rows(h, role, names)
+        if role == 3:  # (the last profiled launch: csrc/vrnn_static.hip bwd_post_follower)
+            q, w, nxt = h[BASE + 3 * ROLE + 13 * 8:][:4], h[BASE + 3 * ROLE + 14 * 8:][:4], h[BASE + 3 * ROLE + 36 * 8:][:4]
+            if q[0] and w[0] == 1:
+                print(f"   per walk step ({q[0]} steps): follower links {q[2] * TICK / q[0]:6.2f} us, whole step {w[2] * TICK / q[0]:6.2f} us; "
+                      f"wait left in front of the run's link 0 (waves 0-3, issue->ok): {nxt[2] * TICK / max(nxt[0], 1):6.3f} us", flush=True)
     q, w = h[BASE + 4 * ROLE + 13 * 8:][:4], h[BASE + 4 * ROLE + 14 * 8:][:4]  # (the last profiled launch: csrc/vrnn_static.hip bwd_spare_leader)
     if q[0]:
         print(f"   per walk step ({q[0]} steps): leader links {q[2] * TICK / q[0]:6.2f} us, arming stores {q[3] * TICK / q[0]:6.2f} us, "
