@@ -18,6 +18,7 @@ from blvm import ops
 from blvm._hip import BlvmHipError
 from blvm.evaluation import (BitsPerDimMetric, DeferredScalars, EMAMetric, KLMetric, LatestMeanMetric, LLMetric,
                              LossMetric)  # fmt: skip
+from blvm.models import importance
 from blvm.models.base_model import BaseModel
 from blvm.models.clockwork_vae.convolutional_coders import ConvCoder1d
 from blvm.models.vrnn import LazyNamespace
@@ -105,6 +106,23 @@ class CWVAE(nn.Module):
                 eps: Optional[List[torch.Tensor]] = None):  # fmt: skip
         """x [B,T] or [B,T,1]; x_sl [B] (host ints).  `eps[l]` [T_l,B,z_l] optionally supplies the reparameterisation
         noise of level l (otherwise drawn on the device, top level first as in the reference)."""
+        y, x_sl, x_sl_dev, level_sl, same_paddings, encodings = self._front(x, x_sl, y, pad_strideable, pad_same)
+        dev, NL = y.device, self.num_levels
+        B, T = y.shape
+
+        def eps_of(l, T_l):
+            Z = self.z_size[l]
+            if eps is not None:
+                return eps[l].to(device=dev, dtype=torch.float32)
+            return torch.zeros(T_l, B, Z, device=dev) if use_mode_global else torch.randn(T_l, B, Z, device=dev)
+
+        kld_l, kld_fn_l, latents, enc_mus, prior_mus, state_n, context = self._levels(
+            encodings, [None] * NL if state0 is None else state0, eps_of, x_sl_dev, level_sl, same_paddings, pad_same, B, free_nats)  # fmt: skip
+        return self._finish(context, y, x_sl, x_sl_dev, kld_l, kld_fn_l, latents, enc_mus, prior_mus, state_n, level_sl, beta, free_nats)
+
+    def _front(self, x, x_sl, y, pad_strideable: bool, pad_same: bool):
+        """The deterministic front of `forward` and `iw_bound`: target, lengths, paddings and the conv encoder ->
+        (y [B,T], x_sl on the host, x_sl on the device, level_sl, same_paddings, encodings[l] [T_l,B,E_l])."""
         if x.ndim == 3:
             x = x.squeeze(-1)
         if not x.is_cuda:
@@ -136,8 +154,16 @@ class CWVAE(nn.Module):
 
         x_tm = x.t().contiguous().unsqueeze(-1)  # [T,B,1]
         encodings = self.encoder.forward_tm(x_tm, pad_right=same_paddings if pad_same else [0] * NL)
+        return y, x_sl, x_sl_dev, level_sl, same_paddings, encodings
 
-        states0 = [None] * NL if state0 is None else state0
+    def _levels(self, encodings, states0, eps_of, x_sl_dev, level_sl, same_paddings, pad_same: bool, B: int, free_nats: float,
+                log_ratio: bool = False):  # fmt: skip
+        """The stochastic part, top level first: one cell sequence per level on B rows and the context decoder below it.
+        `eps_of(l, T_l)` -> the level's noise [T_l,B,z_l].  Returns (kld_l, kld_fn_l, latents, enc_mus, prior_mus, state_n, the
+        bottom context).  `log_ratio` (`iw_bound`): kld_l (= kld_fn_l) are the sums of log q(z) - log p(z) at the drawn z (K8m),
+        folded over segments exactly as the KL is, and no state is gathered."""
+        dev = x_sl_dev.device
+        NL, os_ = self.num_levels, [int(s) for s in self.overall_strides]
         kld_l, kld_fn_l, latents, enc_mus, prior_mus, state_n = ([None] * NL for _ in range(6))
         context = None
         for l in range(NL - 1, -1, -1):
@@ -154,12 +180,7 @@ class CWVAE(nn.Module):
                 raise IndexError(f"list index out of range (level {l}: state of step {int(level_sl[l].max()) - 1} wanted, the level has {T_l} "
                                  f"steps{'' if pad_same else '; pad_same=False never completes in the reference either'})")  # fmt: skip
             Z = self.z_size[l]
-            if eps is not None:
-                eps_l = eps[l].to(device=dev, dtype=torch.float32)
-            elif use_mode_global:
-                eps_l = torch.zeros(T_l, B, Z, device=dev)
-            else:
-                eps_l = torch.randn(T_l, B, Z, device=dev)
+            eps_l = eps_of(l, T_l)
             fn_l = free_nats * os_[l] / os_[0]  # free nats scale with the level's stride (clockwork_vae.py:151)
             k = self._resets(l)
             if k:
@@ -169,32 +190,50 @@ class CWVAE(nn.Module):
                 seg_sl = ops.upload_i32((steps * os_[l]).reshape(-1), dev)
                 f = lambda t: self._fold(t, k, nseg)  # noqa: E731
                 u = lambda t: self._unfold(t, k, nseg, T_l)  # noqa: E731
-                zs_f, hs_f, kld_f, kld_fn_f, mu_q, _, mu_p, _ = self.cells[l].sequence(
-                    f(enc_l[:T_l]), f(None if context is None else context[:T_l]), None, f(eps_l), seg_sl, os_[l], fn_l)  # fmt: skip
+                eps_f = f(eps_l)
+                zs_f, hs_f, kld_f, kld_fn_f, mu_q, sd_q, mu_p, sd_p = self.cells[l].sequence(
+                    f(enc_l[:T_l]), f(None if context is None else context[:T_l]), None, eps_f, seg_sl, os_[l], fn_l)  # fmt: skip
+                if log_ratio:
+                    kld_f = kld_fn_f = ops.gauss_log_ratio_sums(mu_q, sd_q, mu_p, sd_p, zs_f[1:], eps_f, seg_sl, ops.LAYOUT_TIME_MAJOR,
+                                                                nseg * B, k, Z, os_[l])  # fmt: skip
                 zs = torch.cat([zs_f.new_zeros(1, B, Z), u(zs_f[1:])], 0)
                 hs = torch.cat([hs_f.new_zeros(1, B, hs_f.shape[-1]), u(hs_f[1:])], 0)
                 kld, kld_fn = kld_f.view(nseg, B).sum(0), kld_fn_f.view(nseg, B).sum(0)
                 mu_q, mu_p = u(mu_q), u(mu_p)
             else:
-                zs, hs, kld, kld_fn, mu_q, _, mu_p, _ = self.cells[l].sequence(
+                zs, hs, kld, kld_fn, mu_q, sd_q, mu_p, sd_p = self.cells[l].sequence(
                     enc_l[:T_l], None if context is None else context[:T_l], states0[l], eps_l, x_sl_dev, os_[l], fn_l)  # fmt: skip
+                if log_ratio:
+                    kld = kld_fn = ops.gauss_log_ratio_sums(mu_q, sd_q, mu_p, sd_p, zs[1:], eps_l, x_sl_dev, ops.LAYOUT_TIME_MAJOR, B,
+                                                            T_l, Z, os_[l])  # fmt: skip
             kld_l[l], kld_fn_l[l] = kld, kld_fn
             latents[l], enc_mus[l], prior_mus[l] = zs[1:].transpose(0, 1), mu_q.transpose(0, 1), mu_p.transpose(0, 1)
 
-            # state to carry into the next split: the one at each example's last valid step (clockwork_vae.py:283-290)
-            stop = ops.upload_i32((level_sl[l] - 1).clamp(0) + 1, dev).long()
-            rows = torch.arange(B, device=dev)
-            state_n[l] = (zs[stop, rows], hs[stop, rows])
+            if not log_ratio:
+                # state to carry into the next split: the one at each example's last valid step (clockwork_vae.py:283-290)
+                stop = ops.upload_i32((level_sl[l] - 1).clamp(0) + 1, dev).long()
+                rows = torch.arange(B, device=dev)
+                state_n[l] = (zs[stop, rows], hs[stop, rows])
 
             # context for the level below: decode cat(z, h) up to its rate (clockwork_vae.py:292-297)
             _, context = self.decoder.forward_level_tm(torch.cat([zs[1:], hs[1:]], dim=-1), l, pad_right=same_paddings[l])
 
+        return kld_l, kld_fn_l, latents, enc_mus, prior_mus, state_n, context
+
+    def _log_prob(self, context, y, x_sl_dev):
+        """The head on the bottom context [T,B,h] -> log_prob [B] float64."""
+        B, T = y.shape
         if context.shape[0] != T:
             raise BlvmHipError(f"decoded length {context.shape[0]} != target length {T}")
         lik = self.likelihood
         # head: Linear h -> 3*num_mix as a K6 GEMM, then K7 without its fused [F,F] Linear
         par = ops.linear(context.reshape(T * B, -1), lik.params.weight, lik.params.bias)
-        log_prob = lik.fused_log_prob(par, y, x_sl_dev, ops.LAYOUT_TIME_MAJOR, B, T, T, 1, fused_linear=False)
+        return lik.fused_log_prob(par, y, x_sl_dev, ops.LAYOUT_TIME_MAJOR, B, T, T, 1, fused_linear=False)
+
+    def _finish(self, context, y, x_sl, x_sl_dev, kld_l, kld_fn_l, latents, enc_mus, prior_mus, state_n, level_sl, beta, free_nats):
+        """The head, the ELBO, the metrics and the outputs of `forward`."""
+        dev, lik = y.device, self.likelihood
+        log_prob = self._log_prob(context, y, x_sl_dev)
 
         kld, kld_fn = sum(kld_l), sum(kld_fn_l)
         n_frames = float(x_sl.sum())
@@ -215,6 +254,28 @@ class CWVAE(nn.Module):
         outputs = LazyNamespace(lazy, elbo=elbo, log_prob=log_prob, kld=kld, y=y.unsqueeze(-1), z=latents, z_sl=level_sl,
                                 enc_mus=enc_mus, prior_mus=prior_mus, state_n=state_n)  # fmt: skip
         return loss, metrics, outputs
+
+    @torch.no_grad()
+    def iw_bound(self, x, x_sl, num_samples: int, eps: Optional[List[torch.Tensor]] = None, max_rows: Optional[int] = None):
+        """K-sample importance-weighted bound per utterance -> (bound [B] float64, metrics, outputs(log_w [K,B], ess, elbo_mc)).
+        The conv encoder runs once on the B utterances; the cell sequences of every level, the context decoders and the head run on
+        passes of c * B rows (row k * B + b), c * B <= `max_rows` (default max(B, blvm_pchain_max_batch())).  `eps[l]`
+        [K,T_l,B,z_l] optionally supplies the noise.  Same padding, as `forward`'s default; no free nats, no beta; always fp32
+        operands.  With `with_resets` the log-ratio sums fold over segments as `forward` folds the KL."""
+        K = importance.check_samples(num_samples)
+        with importance.fp32_operands():
+            y, x_sl, x_sl_dev, level_sl, same_paddings, encodings = self._front(x, x_sl, None, False, True)
+            B = y.shape[0]
+            parts = []
+            for k0, c in importance.passes(K, B, max_rows):
+                n = c * B
+                sl, yy = x_sl_dev.repeat(c), importance.tile_rows(y, c, 0)
+                eps_of = lambda l, T_l: importance.pass_eps(None if eps is None else eps[l], k0, c, T_l, B, self.z_size[l], y.device)  # noqa: E731, B023
+                ratios, _, _, _, _, _, context = self._levels([importance.tile_rows(e, c) for e in encodings], [None] * self.num_levels,
+                                                              eps_of, sl, [s.repeat(c) for s in level_sl], same_paddings, True, n, 0.0,
+                                                              log_ratio=True)  # fmt: skip
+                parts.append(self._log_prob(context, yy, sl) - sum(ratios))
+            return importance.finish(parts, K, B, float(x_sl.sum()))
 
     def build_metrics(self, loss, elbo, log_prob, kld, kld_l, x_sl, beta, free_nats):
         """Metric names / reductions of clockwork_vae.py:106-130; all sums leave the device in one deferred transfer."""
@@ -321,6 +382,10 @@ class CWVAEAudio(BaseModel):
     def forward(self, x, x_sl, state0=None, beta: float = 1, free_nats: float = 0, pad_strideable: bool = True,
                 pad_same: bool = True, y=None, eps=None):  # fmt: skip
         return self.cwvae(x, x_sl, state0, beta, free_nats, y, pad_strideable, pad_same, eps=eps)
+
+    @torch.no_grad()
+    def iw_bound(self, x, x_sl, num_samples: int, eps=None, max_rows=None):
+        return self.cwvae.iw_bound(x, x_sl, num_samples, eps, max_rows)
 
     def generate(self, *args, **kwargs):
         return self.cwvae.generate(*args, **kwargs)

@@ -17,6 +17,7 @@ import torch.nn.init as init
 from blvm import ops
 from blvm.data.transforms import StackTensor
 from blvm.evaluation import BitsPerDimMetric, DeferredScalars, KLMetric, LatestMeanMetric, LLMetric, LossMetric
+from blvm.models import importance
 from blvm.models.base_model import BaseModel
 from blvm.models.vrnn import LIKELIHOOD_HEADS, LazyNamespace, _linears
 from blvm.modules.convenience import View
@@ -87,11 +88,9 @@ class SRNN(nn.Module):
             raise NotImplementedError("libblvm_hip accelerates the SRNNAudio(likelihood='DMoL') structure")
         return stack.n_frames, _linears(enc), _linears(dec), lik
 
-    def forward(self, x, x_sl, u=None, d_0=None, a_0=None, z_0=None, h_p_0=None, h_q_0=None, beta: float = 1,
-                free_nats: float = 0, eps: Optional[torch.Tensor] = None):  # fmt: skip
-        if u is not None:
-            raise NotImplementedError("libblvm_hip: external control input u is not supported (SRNNAudio never passes it)")
-        S, enc_lin, dec_lin, lik = self._plan()
+    def _deterministic(self, x, x_sl, d_0, a_0, S, enc_lin):
+        """The deterministic part of `forward` and `iw_bound`: encoder, forward GRU d, smoothing GRU (or MLP) a ->
+        (y [B,T] fp32, x_sl host, x_sl device, strided lengths, T', stride, d [T',B,R], a [T',B,R], d_n, a_n)."""
         if x.ndim == 3:
             x = x.squeeze(-1)
         dev = x.device
@@ -103,7 +102,7 @@ class SRNN(nn.Module):
         stride = math.ceil(T / Tp)
         x_sl_strided = (x_sl_host / stride).ceil().int()
         lens_dev = ops.upload_i32(x_sl_strided, dev)
-        H, Z, R = self.h_dim, self.z_dim, self.r_dim
+        R = self.r_dim
 
         xs = torch.nn.functional.pad(y, (0, Tp * S - T)) if Tp * S != T else y
         xs = xs.view(B, Tp, S).transpose(0, 1).contiguous().view(Tp * B, S)
@@ -126,6 +125,17 @@ class SRNN(nn.Module):
         else:
             a = ops.mlp(cat_xd.view(Tp * B, -1), _linears(self.a_mlp), ops.ACT_LEAKY, ops.LEAKY_SLOPE).view(Tp, B, R)
             a_n = None
+        return y, x_sl_host, x_sl_dev, x_sl_strided, Tp, stride, d, a, d_n, a_n
+
+    def forward(self, x, x_sl, u=None, d_0=None, a_0=None, z_0=None, h_p_0=None, h_q_0=None, beta: float = 1,
+                free_nats: float = 0, eps: Optional[torch.Tensor] = None):  # fmt: skip
+        if u is not None:
+            raise NotImplementedError("libblvm_hip: external control input u is not supported (SRNNAudio never passes it)")
+        S, enc_lin, dec_lin, lik = self._plan()
+        y, x_sl_host, x_sl_dev, x_sl_strided, Tp, stride, d, a, d_n, a_n = self._deterministic(x, x_sl, d_0, a_0, S, enc_lin)
+        dev = y.device
+        B, T = y.shape
+        H, Z, R = self.h_dim, self.z_dim, self.r_dim
 
         if eps is None:
             eps = torch.randn(Tp, B, Z, device=dev, dtype=torch.float32)
@@ -174,6 +184,33 @@ class SRNN(nn.Module):
         )  # fmt: skip
         return loss, metrics, outputs
 
+    @torch.no_grad()
+    def iw_bound(self, x, x_sl, num_samples: int, eps: Optional[torch.Tensor] = None, max_rows: Optional[int] = None):
+        """K-sample importance-weighted bound per utterance -> (bound [B] float64, metrics, outputs(log_w [K,B], ess, elbo_mc)).
+        The encoder and the two GRUs (d, a) run once on the B utterances; the latent chain, the decoder and the head run on passes
+        of c * B rows (row k * B + b), c * B <= `max_rows` (default max(B, blvm_pchain_max_batch())).  `eps` [K,T',B,z] optionally
+        supplies the noise.  No free nats, no beta; always fp32 operands."""
+        K = importance.check_samples(num_samples)
+        S, enc_lin, dec_lin, lik = self._plan()
+        H, Z, R = self.h_dim, self.z_dim, self.r_dim
+        with importance.fp32_operands():
+            y, x_sl_host, x_sl_dev, _, Tp, stride, d, a, _, _ = self._deterministic(x, x_sl, None, None, S, enc_lin)
+            B, T = y.shape
+            parts = []
+            for k0, c in importance.passes(K, B, max_rows):
+                n = c * B
+                e = importance.pass_eps(eps, k0, c, Tp, B, Z, y.device)
+                sl, yy, dd = x_sl_dev.repeat(c), importance.tile_rows(y, c, 0), importance.tile_rows(d, c)
+                zs, _, _, mu_q, sd_q, mu_p, sd_p = ops.srnn_latent_chain(
+                    dd, importance.tile_rows(a, c), None, e, sl, self._chain_params(), H, Z, R, self.residual_posterior, stride, 0.0,
+                    self.prior[6].epsilon
+                )
+                z = zs[1:]
+                _, log_prob = mlp_log_prob(lik, torch.cat([z, dd], -1).view(Tp * n, Z + R), dec_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE, yy, sl,
+                                           ops.LAYOUT_TIME_MAJOR, n, T, Tp, S)  # fmt: skip
+                ratio = ops.gauss_log_ratio_sums(mu_q, sd_q, mu_p, sd_p, z, e, sl, ops.LAYOUT_TIME_MAJOR, n, Tp, Z, stride)
+                parts.append(log_prob - ratio)
+            return importance.finish(parts, K, B, float(x_sl_host.sum()))
 
     @torch.no_grad()
     def generate(self, x, u=None, d_0=None, a_0=None, z_0=None, h_p_0=None, n_samples: int = 1, max_timesteps: int = 100,
@@ -369,6 +406,10 @@ class SRNNAudio(BaseModel):
         loss, metrics, outputs = self.srnn(x=x, x_sl=x_sl, d_0=d_0, a_0=a_0, z_0=z_0, beta=beta, free_nats=free_nats, eps=eps)
         outputs._lazy["x_hat"] = lambda ns: self.srnn.likelihood.sample(ns.parameters)
         return loss, metrics, outputs
+
+    @torch.no_grad()
+    def iw_bound(self, x, x_sl, num_samples: int, eps=None, max_rows=None):
+        return self.srnn.iw_bound(x, x_sl, num_samples, eps, max_rows)
 
     def generate(self, n_samples: int = 1, max_timesteps: int = 100, use_mode: bool = False, x=None, u=None, d_0=None, a_0=None,
                  z_0=None, eps=None, uniforms=None, fused: Optional[bool] = None):  # fmt: skip

@@ -16,6 +16,7 @@ import torch.nn as nn
 from blvm import ops
 from blvm._hip import BlvmHipError
 from blvm.evaluation import BitsPerDimMetric, DeferredScalars, KLMetric, LatestMeanMetric, LLMetric, LossMetric
+from blvm.models import importance
 from blvm.models.base_model import BaseModel
 from blvm.models.vrnn import LazyNamespace
 from blvm.models.wavenet.wavenet_modules import CausalConv1d, ResidualStack
@@ -124,8 +125,9 @@ class STCN(BaseModel):
         self.likelihood_module = likelihood_module
 
     # ---- inference over the latent hierarchy (stcn.py:296-327) -------------------------------------------------------
-    def infer(self, skips, eps, x_sl_dev, B: int, T: int, free_nats: float):
-        """skips[l] [T+1,B,C] time-major.  Returns per level (mu_p, sd_p, mu_q, sd_q, z) [T,B,Z_l] and the KL sums."""
+    def infer(self, skips, eps, x_sl_dev, B: int, T: int, free_nats: float, log_ratio: bool = False):
+        """skips[l] [T+1,B,C] time-major.  Returns per level (mu_p, sd_p, mu_q, sd_q, z) [T,B,Z_l] and the KL sums.
+        `log_ratio` (`iw_bound`): the sums are those of log q(z) - log p(z) at the drawn z (K8m), for either direction."""
         n, S = self.n_latents, self.n_stack_frames
         mu_p, sd_p, mu_q, sd_q, z = ([None] * n for _ in range(5))
         klds, klds_fn = [None] * n, [None] * n
@@ -142,7 +144,9 @@ class STCN(BaseModel):
             sp, mq_c, sq_c, z_l = ops.gauss_latent(mp, sp_raw, mq, sq_raw, e, self.prior[l].softplus_beta,
                                                    self.posterior[l].softplus_beta, self.prior[l].epsilon,
                                                    ops.RSSM_PRECISION if self.precision_posterior else ops.RSSM_PLAIN)  # fmt: skip
-            if self.top_down:
+            if log_ratio:
+                klds[l] = klds_fn[l] = ops.gauss_log_ratio_sums(mq_c, sq_c, mp, sp, z_l, e, x_sl_dev, ops.LAYOUT_TIME_MAJOR, B, T, Z, S)
+            elif self.top_down:
                 klds[l], klds_fn[l] = ops.gaussian_kl_sums(mq_c, sq_c, mp, sp, x_sl_dev, ops.LAYOUT_TIME_MAJOR, B, T, Z, S, free_nats)
             else:
                 # Monte-Carlo KL at the drawn z (stcn.py:286-287, variational.py:73-83): log q(z) - log p(z) per element, masked to the
@@ -164,16 +168,14 @@ class STCN(BaseModel):
         """Receptive-field padding on the first split only (stcn.py:332-342); `eps` as in `forward`."""
         return self.forward(x, x_sl, y=y, pad_receptive_field=(i_split == 0), eps=eps)
 
-    def forward(self, x, x_sl, y=None, pad_receptive_field: bool = True, free_nats: float = 0, beta: float = 1,
-                eps: Optional[List[torch.Tensor]] = None):  # fmt: skip
-        """x [B,T] in [-1,1]; x_sl [B] (host ints).  `eps[l]` [T',B,z_l] optionally supplies the reparameterisation noise
-        (otherwise drawn on the device, top level first as in the reference)."""
+    def _front(self, x, x_sl, y, pad_receptive_field: bool):
+        """The deterministic front of `forward` and `iw_bound`: the target, the lengths and the encoder stacks' skip outputs ->
+        (y [B,T_y], x_sl on the host, mask lengths on the device, B, T, T_y, skips[l] [T+1,B,C])."""
         if x.ndim == 3:
             x = x.squeeze(-1)
         if not x.is_cuda:
             raise BlvmHipError("blvm HIP kernels were handed a CPU tensor (no CPU fallback)")
         dev, S, rf, C = x.device, self.n_stack_frames, self.receptive_field, self.res_channels
-        lik = self.likelihood_module
         x = x.to(torch.float32)
         x_sl_host = x_sl.detach().cpu().to(torch.int64)
         if y is None:
@@ -204,6 +206,27 @@ class STCN(BaseModel):
         # used — with n_layers == n_latents (the default) that is the last block of every stack
         groups = self._skip_groups()
         skips = self.res_stack.forward_tm(out, T + 1, groups=groups)
+        return y, x_sl_host, mask_len, B, T, T_y, skips
+
+    def _observe(self, z, y, mask_len, B: int, T: int, T_y: int):
+        """The observation model on the latents z[l] [T,B,Z_l]: output stack, upsampling Linear and likelihood head ->
+        (dec [T*B, S*F] detached, log_prob [B] float64)."""
+        dev, S, C, lik = y.device, self.n_stack_frames, self.res_channels, self.likelihood_module
+        logits_in = torch.cat(z, -1) if self.dense else z[0]
+        ot = self.out_transform
+        logits_in = torch.cat([torch.zeros(ot.receptive_field - 1, B, logits_in.size(-1), device=dev), logits_in], 0)
+        skip_sum = ot.forward_tm(logits_in, T)  # [T,B,C]: sum of the output blocks' skips
+        h = ops.scale_act(skip_sum.view(T * B, C), self.inv_std, 1.0)  # * inv_std (slope 1: no activation)
+        up = self.out_upsample[0]
+        return mlp_log_prob(lik, h, [up], ops.ACT_RELU, 0.0, y, mask_len, ops.LAYOUT_TIME_MAJOR, B, T_y, T, S)  # dec [T*B, S*F]
+
+    def forward(self, x, x_sl, y=None, pad_receptive_field: bool = True, free_nats: float = 0, beta: float = 1,
+                eps: Optional[List[torch.Tensor]] = None):  # fmt: skip
+        """x [B,T] in [-1,1]; x_sl [B] (host ints).  `eps[l]` [T',B,z_l] optionally supplies the reparameterisation noise
+        (otherwise drawn on the device, top level first as in the reference)."""
+        y, x_sl_host, mask_len, B, T, T_y, skips = self._front(x, x_sl, y, pad_receptive_field)
+        dev, S, n = y.device, self.n_stack_frames, self.n_latents
+        lik = self.likelihood_module
 
         if eps is None:
             eps = [None] * n
@@ -212,13 +235,7 @@ class STCN(BaseModel):
         mu_p, sd_p, mu_q, sd_q, z, klds, klds_fn = self.infer(skips, [e.to(device=dev, dtype=torch.float32).contiguous() for e in eps],
                                                               mask_len, B, T, free_nats)  # fmt: skip
 
-        logits_in = torch.cat(z, -1) if self.dense else z[0]
-        ot = self.out_transform
-        logits_in = torch.cat([torch.zeros(ot.receptive_field - 1, B, logits_in.size(-1), device=dev), logits_in], 0)
-        skip_sum = ot.forward_tm(logits_in, T)  # [T,B,C]: sum of the output blocks' skips
-        h = ops.scale_act(skip_sum.view(T * B, C), self.inv_std, 1.0)  # * inv_std (slope 1: no activation)
-        up = self.out_upsample[0]
-        dec, log_prob = mlp_log_prob(lik, h, [up], ops.ACT_RELU, 0.0, y, mask_len, ops.LAYOUT_TIME_MAJOR, B, T_y, T, S)  # dec [T*B, S*F]
+        dec, log_prob = self._observe(z, y, mask_len, B, T, T_y)
 
         kld, kld_fn = sum(klds), sum(klds_fn)
         n_frames = float(x_sl_host.sum())
@@ -238,6 +255,28 @@ class STCN(BaseModel):
                                z_sl=[torch.ceil(x_sl_host / S).long()] * self.n_stacks, enc_mus=bt(mu_q), prior_mus=bt(mu_p),
                                y=y.unsqueeze(-1))  # fmt: skip
         return loss, metrics, output
+
+    @torch.no_grad()
+    def iw_bound(self, x, x_sl, num_samples: int, eps: Optional[List[torch.Tensor]] = None, max_rows: Optional[int] = None):
+        """K-sample importance-weighted bound per utterance -> (bound [B] float64, metrics, outputs(log_w [K,B], ess, elbo_mc)).
+        The deterministic encoder stacks run once on the B utterances; the latent hierarchy and the observation model run on passes
+        of c * B rows (row k * B + b), c * B <= `max_rows` (default max(B, blvm_pchain_max_batch())).  `eps[l]` [K,T',B,z_l]
+        optionally supplies the noise.  No free nats, no beta; always fp32 operands."""
+        K = importance.check_samples(num_samples)
+        with importance.fp32_operands():
+            y, x_sl_host, mask_len, B, T, T_y, skips = self._front(x, x_sl, None, True)
+            parts = []
+            for k0, c in importance.passes(K, B, max_rows):
+                n = c * B
+                order = reversed(range(self.n_latents)) if self.top_down else range(self.n_latents)  # the reference's draw order
+                e = [None] * self.n_latents
+                for l in order:
+                    e[l] = importance.pass_eps(None if eps is None else eps[l], k0, c, T, B, self.latent_size[l], y.device)
+                sl, yy = mask_len.repeat(c), importance.tile_rows(y, c, 0)
+                *_, z, ratios, _ = self.infer([importance.tile_rows(s, c) for s in skips], e, sl, n, T, 0, log_ratio=True)
+                _, log_prob = self._observe(z, yy, sl, n, T, T_y)
+                parts.append(log_prob - sum(ratios))
+            return importance.finish(parts, K, B, float(x_sl_host.sum()))
 
     def build_metrics(self, loss, elbo, log_prob, kld, klds, x_sl, beta, free_nats):
         """Metric names / reductions of stcn.py:208-245."""

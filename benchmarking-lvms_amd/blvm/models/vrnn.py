@@ -17,6 +17,7 @@ import torch.nn.init as init
 from blvm import _hip, ops
 from blvm.data.transforms import StackTensor
 from blvm.evaluation import BitsPerDimMetric, DeferredScalars, KLMetric, LatestMeanMetric, LLMetric, LossMetric
+from blvm.models import importance
 from blvm.models.base_model import BaseModel
 from blvm.modules.convenience import View
 from blvm.modules.distributions import (DiagonalGaussianDense, DiagonalGaussianMixtureDense, DiscretizedLogisticMixtureDense,
@@ -175,11 +176,9 @@ class VRNN(nn.Module):
             )
         return stack.n_frames, _linears(enc), _linears(dec), lik
 
-    def forward(self, x: torch.Tensor, x_sl: torch.Tensor, beta: float = 1, free_nats: float = 0,
-                h0: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None):  # fmt: skip
-        """x [B,T] or [B,T,1] in [-1,1]; x_sl [B] lengths (host int tensor, as the reference's loaders give it).
-        `eps` [T',B,z] optionally supplies the reparameterisation noise (otherwise drawn on the device)."""
-        S, enc_lin, dec_lin, lik = self._plan()
+    def _encode(self, x, x_sl, S, enc_lin):
+        """The deterministic front of `forward` and `iw_bound`: (y [B,T] fp32, x_sl on the host, x_sl on the device, T', stride,
+        enc [T',B,X])."""
         if x.ndim == 3:
             x = x.squeeze(-1)
         dev = x.device
@@ -189,23 +188,38 @@ class VRNN(nn.Module):
         y = x.detach().to(torch.float32).contiguous()
         Tp = (T + S - 1) // S
         stride = math.ceil(T / Tp)
-        H, Z, R = self.h_dim, self.z_dim, self.r_dim
 
         # frames stacked time-major: [T', B, S]   (StackTensor, operations.py:14-32: right zero-pad)
         xs = torch.nn.functional.pad(y, (0, Tp * S - T)) if Tp * S != T else y
         xs = xs.view(B, Tp, S).transpose(0, 1).contiguous().view(Tp * B, S)
         enc = ops.mlp(xs, enc_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE).view(Tp, B, -1)
+        return y, x_sl_host, x_sl_dev, Tp, stride, enc
 
-        if eps is None:
-            eps = torch.randn(Tp, B, Z, device=dev, dtype=torch.float32)
-        # a decoder of three Linear + LeakyReLU goes down with the cell: the forward launch runs it on its spare workgroups where it
-        # has them (`given`: its activations; None: not folded, the decoder runs as K6 below)
+    def _decoder_fold(self, dec_lin, lik):
+        """The decoder handed down with the cell where it is three chained Linear + LeakyReLU (else None: it runs as K6)."""
+        H, R = self.h_dim, self.r_dim
         widths = [(lin.in_features, lin.out_features) for lin in dec_lin]
         chained = len(dec_lin) == 3 and widths[0] == (H + R, widths[1][0]) and widths[1][1] == widths[1][0] == widths[2][0]
         # (head_gates: the DMoL head below returns the gradient of the decoder's last pre-activation, so the cell's node may take the
         # decoder in and run its backward on the backward launch's spare workgroups: `fold.dec`)
         gates = isinstance(lik, DiscretizedLogisticMixtureDense) and lik.params is not None
-        fold = ops.DecoderFold(dec_lin, ops.LEAKY_SLOPE, gates) if chained and all(lin.bias is not None for lin in dec_lin) else None
+        return ops.DecoderFold(dec_lin, ops.LEAKY_SLOPE, gates) if chained and all(lin.bias is not None for lin in dec_lin) else None
+
+    def forward(self, x: torch.Tensor, x_sl: torch.Tensor, beta: float = 1, free_nats: float = 0,
+                h0: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None):  # fmt: skip
+        """x [B,T] or [B,T,1] in [-1,1]; x_sl [B] lengths (host int tensor, as the reference's loaders give it).
+        `eps` [T',B,z] optionally supplies the reparameterisation noise (otherwise drawn on the device)."""
+        S, enc_lin, dec_lin, lik = self._plan()
+        y, x_sl_host, x_sl_dev, Tp, stride, enc = self._encode(x, x_sl, S, enc_lin)
+        dev = y.device
+        B, T = y.shape
+        H, Z, R = self.h_dim, self.z_dim, self.r_dim
+
+        if eps is None:
+            eps = torch.randn(Tp, B, Z, device=dev, dtype=torch.float32)
+        # a decoder of three Linear + LeakyReLU goes down with the cell: the forward launch runs it on its spare workgroups where it
+        # has them (`given`: its activations; None: not folded, the decoder runs as K6 below)
+        fold = self._decoder_fold(dec_lin, lik)
         decin, kld, kld_fn, mu_q, sd_q, mu_p, sd_p, z = self.vrnn_cell.sequence(enc, h0, eps, x_sl_dev, stride, free_nats, decoder=fold)
         given, dec_node = (fold.given, fold.dec) if fold is not None else (None, None)
 
@@ -257,6 +271,33 @@ class VRNN(nn.Module):
         )
         return loss, metrics, outputs
 
+    @torch.no_grad()
+    def iw_bound(self, x: torch.Tensor, x_sl: torch.Tensor, num_samples: int, eps: Optional[torch.Tensor] = None,
+                 max_rows: Optional[int] = None):  # fmt: skip
+        """K-sample importance-weighted bound per utterance -> (bound [B] float64, metrics, outputs(log_w [K,B], ess, elbo_mc)).
+        The encoder runs once on the B utterances; the cell, the decoder and the head run on passes of c * B rows (row k * B + b),
+        c * B <= `max_rows` (default max(B, blvm_pchain_max_batch())).  `eps` [K,T',B,z] optionally supplies the noise.  No free
+        nats, no beta; always fp32 operands."""
+        K = importance.check_samples(num_samples)
+        S, enc_lin, dec_lin, lik = self._plan()
+        H, Z, R = self.h_dim, self.z_dim, self.r_dim
+        with importance.fp32_operands():
+            y, x_sl_host, x_sl_dev, Tp, stride, enc = self._encode(x, x_sl, S, enc_lin)
+            B, T = y.shape
+            parts = []
+            for k0, c in importance.passes(K, B, max_rows):
+                n = c * B
+                e = importance.pass_eps(eps, k0, c, Tp, B, Z, y.device)
+                sl, yy = x_sl_dev.repeat(c), importance.tile_rows(y, c, 0)
+                fold = self._decoder_fold(dec_lin, lik)
+                decin, _, _, mu_q, sd_q, mu_p, sd_p, z = self.vrnn_cell.sequence(importance.tile_rows(enc, c), None, e, sl, stride, 0.0,
+                                                                                 decoder=fold)  # fmt: skip
+                given, dec_node = (fold.given, fold.dec) if fold is not None else (None, None)
+                _, log_prob = mlp_log_prob(lik, decin[:Tp].view(Tp * n, H + R), dec_lin, ops.ACT_LEAKY, ops.LEAKY_SLOPE, yy, sl,
+                                           ops.LAYOUT_TIME_MAJOR, n, T, Tp, S, given=given, dec_node=dec_node)  # fmt: skip
+                ratio = ops.gauss_log_ratio_sums(mu_q, sd_q, mu_p, sd_p, z, e, sl, ops.LAYOUT_TIME_MAJOR, n, Tp, Z, stride)
+                parts.append(log_prob - ratio)
+            return importance.finish(parts, K, B, float(x_sl_host.sum()))
 
     @torch.no_grad()
     def generate(self, x: torch.Tensor, h0: Optional[torch.Tensor] = None, n_samples: int = 1, max_timesteps: int = 100,
@@ -451,6 +492,10 @@ class VRNNAudio(BaseModel):
 
     def forward(self, x, x_sl, beta: float = 1, free_nats: float = 0, h0=None, eps=None):
         return self.vrnn(x, x_sl, beta, free_nats, h0, eps)
+
+    @torch.no_grad()
+    def iw_bound(self, x, x_sl, num_samples: int, eps=None, max_rows=None):
+        return self.vrnn.iw_bound(x, x_sl, num_samples, eps, max_rows)
 
     def generate(self, n_samples: int = 1, max_timesteps: int = 100, use_mode: bool = False, x=None, h0=None, eps=None, uniforms=None,
                  fused: Optional[bool] = None):  # fmt: skip

@@ -625,6 +625,56 @@ def gaussian_kl_sums(mu_q, sd_q, mu_p, sd_p, x_sl_dev, layout, B, Tp, Z, stride,
     return _KLFunction.apply(mu_q, sd_q, mu_p, sd_p, x_sl_dev, layout, B, Tp, Z, stride, fn_floor)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# K8m: the importance-weighted bound's reductions (evaluation only: none of these builds an autograd graph)
+# ----------------------------------------------------------------------------------------------------------------------
+
+
+def gauss_log_ratio_sums(mu_q, sd_q, mu_p, sd_p, z, eps, x_sl_dev, layout, B, Tp, Z, stride):
+    """[B] float64: masked per-utterance sums of log q(z) - log p(z) at the drawn z = mu_q + sd_q eps (`blvm_gauss_logratio_fwd`).
+    The six operands are [Tp*B, Z] fp32 in `layout`; step t of row b counts iff t * stride < x_sl_dev[b]."""
+    ts = [_f32c(t.detach()) for t in (mu_q, sd_q, mu_p, sd_p, z, eps)]
+    n = int(B) * int(Tp) * int(Z)
+    if any(t.numel() != n for t in ts):
+        raise _hip.BlvmHipError(f"gauss_log_ratio_sums: operands must hold B*Tp*Z = {n} elements, got {[t.numel() for t in ts]}")
+    if x_sl_dev.dtype != torch.int32 or x_sl_dev.numel() != B:
+        raise _hip.BlvmHipError("gauss_log_ratio_sums: x_sl_dev must be int32 [B]")
+    ptrs = [ptr(t) for t in ts]  # (refuses CPU tensors before anything is allocated)
+    out = torch.empty(B, device=ts[0].device, dtype=torch.float64)
+    check(load().blvm_gauss_logratio_fwd(*ptrs, int(layout), ptr(x_sl_dev), int(B), int(Tp), int(Z), int(stride), ptr(out),
+                                         stream_ptr()), "blvm_gauss_logratio_fwd")  # fmt: skip
+    return out
+
+
+def iw_reduce(log_w):
+    """log_w [K, B] float64 -> (bound [B], ess [B]) float64: bound = logsumexp_k(log_w) - log K, ess = (sum w)^2 / sum w^2 with the
+    weights normalised by the column's maximum (`blvm_iw_reduce`)."""
+    if log_w.dtype != torch.float64 or log_w.ndim != 2:
+        raise _hip.BlvmHipError("iw_reduce: log_w must be float64 [K, B]")
+    log_w = log_w.detach().contiguous()
+    K, B = log_w.shape
+    p = ptr(log_w)  # (refuses a CPU tensor before anything is allocated)
+    bound, ess = (torch.empty(B, device=log_w.device, dtype=torch.float64) for _ in range(2))
+    check(load().blvm_iw_reduce(p, K, B, ptr(bound), ptr(ess), stream_ptr()), "blvm_iw_reduce")
+    return bound, ess
+
+
+def iw_chunks(K: int, B: int, max_rows: int) -> List[int]:
+    """Particle counts per pass for K particles of B utterances: every pass carries c particles with c * B <= max_rows (c = 1 where
+    B alone exceeds max_rows), as many as fit, the remainder last; the counts sum to K.  Host arithmetic."""
+    K, B, max_rows = int(K), int(B), int(max_rows)
+    if K < 1 or B < 1 or max_rows < 1:
+        raise ValueError(f"iw_chunks: K, B and max_rows must be positive, got {K}, {B}, {max_rows}")
+    c = max(1, max_rows // B)
+    return [c] * (K // c) + ([K % c] if K % c else [])
+
+
+def iw_max_rows(B: int, max_rows: Optional[int] = None) -> int:
+    """The rows of one `iw_bound` pass: `max_rows`, or by default max(B, blvm_pchain_max_batch()), which keeps the recurrent chains
+    on their persistent path."""
+    return int(max_rows) if max_rows is not None else max(int(B), int(load().blvm_pchain_max_batch()))
+
+
 class _ELBOFunction(torch.autograd.Function):
     """(log_prob, kld, kld_fn [B] float64) -> (loss scalar, elbo [B], sums [4]) in one launch; backward one launch (`blvm_elbo_bwd`)."""
 

@@ -152,6 +152,37 @@ def cwvae_split_eval(model, x, x_sl, tracker, length):
     return out
 
 
+IW_SPLIT_MESSAGE = ("--iw_samples with --split_eval True: the importance-weighted bound is not computed over evaluation splits (it would "
+                    "need particle states carried from split to split); evaluate whole utterances, or leave --iw_samples at 0")  # fmt: skip
+
+
+def add_iw_flag(group):
+    group.add_argument("--iw_samples", default=0, type=int, help="K > 0: the test pass also reports the K-sample importance-weighted "
+                       "bound (model.iw_bound: iw-K (nats), iw-K (bpt), iw-K ess); 0: off")  # fmt: skip
+
+
+def check_iw_flags(parser, args):
+    """--iw_samples is refused, not ignored, where the test pass runs on splits."""
+    if args.iw_samples < 0:
+        parser.error("--iw_samples must be 0 (off) or a positive number of particles")
+    if args.iw_samples and args.split_eval:
+        parser.error(IW_SPLIT_MESSAGE)
+
+
+def with_iw_bound(forward_eval, iw_samples: int, prepare=None):
+    """`forward_eval` whose metrics are joined by those of `model.iw_bound(x, x_sl, iw_samples)`; itself when iw_samples is 0.
+    `prepare(x)`: what the script does to a batch before the model sees it."""
+    if not iw_samples:
+        return forward_eval
+
+    def forward_eval_iw(model, x, x_sl):
+        loss, metrics, out = forward_eval(model, x, x_sl)
+        _, iw_metrics, _ = model.iw_bound(prepare(x) if prepare is not None else x, x_sl, iw_samples)
+        return loss, list(metrics) + iw_metrics, out
+
+    return forward_eval_iw
+
+
 def clip_and_step(params, optimizer, max_grad_value, max_grad_norm, skip_nonfinite=False, scaler=None):
     """clip by value -> clip by norm -> optimizer step (experiment_vrnn_audio.py:224-228).  With `skip_nonfinite` a step whose
     gradient norm is NaN / inf is NOT taken (experiment_srnn_audio.py:236-240): parameters and optimizer state stay as they are.

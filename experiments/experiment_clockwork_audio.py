@@ -2,7 +2,7 @@
 """Clockwork VAE on audio waveforms — entry point with the reference's flags (experiments/experiment_clockwork_audio.py:
 flags :31-66, model :84-96, train loop :213-232, split evaluation with carried per-level state :247-262, checkpoint
 criterion "elbo (bpt)" :288)."""
-from _common import cwvae_split_eval, run  # noqa: I001
+from _common import add_iw_flag, check_iw_flags, cwvae_split_eval, run, with_iw_bound  # noqa: I001
 
 import torch
 
@@ -34,6 +34,7 @@ g.add_argument("--beta_start_value", default=0, type=float)
 g.add_argument("--free_nats_steps", default=0, type=int)
 g.add_argument("--free_nats_start_value", default=4, type=float)
 g.add_argument("--split_eval", default=False, type=str2bool)
+add_iw_flag(g)
 
 
 def _one_or_list(v):
@@ -42,6 +43,7 @@ def _one_or_list(v):
 
 if __name__ == "__main__":
     args = parser.parse_args()
+    check_iw_flags(parser, args)
     model = CWVAEAudio(z_size=_one_or_list(args.latent_size), h_size=_one_or_list(args.hidden_size), g_size=args.global_size,
                        strides=args.strides, num_level_layers=args.num_level_layers, stride_per_layer=args.stride_per_layer,
                        num_mix=args.num_mix, num_bins=2**args.num_bits, residual_posterior=args.residual_posterior,
@@ -62,5 +64,5 @@ if __name__ == "__main__":
         cwvae_split_eval(model, x, x_sl, tracker, args.random_segment_size)
 
     run(args, model, lambda m, x, sl: m(strideable(x), sl, beta=beta.step(), free_nats=fn.step(), pad_strideable=True),
-        lambda m, x, sl: m(strideable(x), sl, pad_strideable=True), "elbo (bpt)", args.num_bits,
+        with_iw_bound(lambda m, x, sl: m(strideable(x), sl, pad_strideable=True), args.iw_samples, strideable), "elbo (bpt)", args.num_bits,
         split_eval if args.split_eval and args.random_segment_size else None)  # fmt: skip

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """SRNN on audio waveforms — entry point with the reference's flags (experiments/experiment_srnn_audio.py)."""
-from _common import run  # noqa: I001
+from _common import add_iw_flag, check_iw_flags, run, with_iw_bound  # noqa: I001
 
 from blvm.models import SRNNAudio
 from blvm.training.annealers import CosineAnnealer
@@ -26,9 +26,11 @@ g.add_argument("--beta_start_value", default=0, type=float)
 g.add_argument("--free_nats_steps", default=0, type=int)
 g.add_argument("--free_nats_start_value", default=0.0625, type=float)
 g.add_argument("--split_eval", default=False, type=str2bool)
+add_iw_flag(g)
 
 if __name__ == "__main__":
     args = parser.parse_args()
+    check_iw_flags(parser, args)
     model = SRNNAudio(likelihood=args.likelihood, input_size=args.stack_frames, hidden_size=args.hidden_size,
                       latent_size=args.latent_size, num_mix=args.num_mix, num_bins=2**args.num_bits,
                       residual_posterior=args.residual_posterior, smoothing=args.smoothing, dropout=args.dropout)  # fmt: skip
@@ -43,5 +45,5 @@ if __name__ == "__main__":
             tracker.update(metrics)
             state = dict(d_0=out.d_n, a_0=out.a_n, z_0=out.z_n)
 
-    run(args, model, lambda m, x, sl: m(x, sl, beta=beta.step(), free_nats=fn.step()), lambda m, x, sl: m(x, sl), "elbo",
-        args.num_bits, split_eval if args.split_eval and args.random_segment_size else None, skip_nonfinite=True)  # fmt: skip
+    run(args, model, lambda m, x, sl: m(x, sl, beta=beta.step(), free_nats=fn.step()), with_iw_bound(lambda m, x, sl: m(x, sl), args.iw_samples),
+        "elbo", args.num_bits, split_eval if args.split_eval and args.random_segment_size else None, skip_nonfinite=True)  # fmt: skip

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """STCN on audio waveforms — entry point with the reference's flags (experiments/experiment_stcn_audio.py: flags :29-67,
 model :84-96, train loop :222-241, checkpoint criterion "elbo (bpx)" :286-287)."""
-from _common import run  # noqa: I001
+from _common import add_iw_flag, check_iw_flags, run, with_iw_bound  # noqa: I001
 
 from blvm.models import STCN
 from blvm.training.annealers import CosineAnnealer
@@ -29,9 +29,11 @@ g.add_argument("--beta_start_value", default=0, type=float)
 g.add_argument("--free_nats_steps", default=0, type=int)
 g.add_argument("--free_nats_start_value", default=4, type=float)
 g.add_argument("--split_eval", default=False, type=str2bool)
+add_iw_flag(g)
 
 if __name__ == "__main__":
     args = parser.parse_args()
+    check_iw_flags(parser, args)
     if args.split_eval:
         # experiment_stcn_audio.py:258 calls model.split_sequence, which raises NotImplementedError (stcn.py:328-330)
         raise SystemExit("--split_eval True: STCN.split_sequence is not implemented in the reference (stcn.py:328-330: raises "
@@ -42,5 +44,5 @@ if __name__ == "__main__":
     beta = CosineAnnealer(anneal_steps=args.beta_anneal_steps, start_value=args.beta_start_value, end_value=1)
     fn = CosineAnnealer(anneal_steps=args.free_nats_steps // 2, constant_steps=args.free_nats_steps // 2,
                         start_value=args.free_nats_start_value, end_value=0)  # fmt: skip
-    run(args, model, lambda m, x, sl: m(x, sl, beta=beta.step(), free_nats=fn.step()), lambda m, x, sl: m(x, sl), "elbo (bpx)",
-        args.num_bits)  # fmt: skip
+    run(args, model, lambda m, x, sl: m(x, sl, beta=beta.step(), free_nats=fn.step()), with_iw_bound(lambda m, x, sl: m(x, sl), args.iw_samples),
+        "elbo (bpx)", args.num_bits)  # fmt: skip

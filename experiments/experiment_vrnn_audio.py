@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """VRNN on audio waveforms — entry point with the reference's flags (experiments/experiment_vrnn_audio.py:33-72)."""
-from _common import run  # noqa: I001  (sets sys.path)
+from _common import add_iw_flag, check_iw_flags, run, with_iw_bound  # noqa: I001  (sets sys.path)
 
 from blvm.models import VRNNAudio
 from blvm.training.annealers import CosineAnnealer
@@ -29,9 +29,11 @@ g.add_argument("--beta_start_value", default=0, type=float)
 g.add_argument("--free_nats_steps", default=0, type=int)
 g.add_argument("--free_nats_start_value", default=0.0625, type=float)
 g.add_argument("--split_eval", default=False, type=str2bool)
+add_iw_flag(g)
 
 if __name__ == "__main__":
     args = parser.parse_args()
+    check_iw_flags(parser, args)
     if args.dropout:  # the reference's VRNNAudio takes no dropout either (blvm/models/vrnn.py:437-447): the flag exists for CLI parity
         parser.error("--dropout: VRNNAudio has no dropout; leave it at 0")
     model = VRNNAudio(likelihood=args.likelihood, input_size=args.stack_frames, hidden_size=args.hidden_size,
@@ -50,5 +52,5 @@ if __name__ == "__main__":
             tracker.update(metrics)
             h0 = out.h_n
 
-    run(args, model, lambda m, x, sl: m(x, sl, beta=beta.step(), free_nats=fn.step()), lambda m, x, sl: m(x, sl), "elbo",
-        args.num_bits, split_eval if args.split_eval and args.random_segment_size else None)  # fmt: skip
+    run(args, model, lambda m, x, sl: m(x, sl, beta=beta.step(), free_nats=fn.step()), with_iw_bound(lambda m, x, sl: m(x, sl), args.iw_samples),
+        "elbo", args.num_bits, split_eval if args.split_eval and args.random_segment_size else None)  # fmt: skip

@@ -345,6 +345,28 @@ int blvm_elbo_fwd(const double* log_prob, const double* kld, const double* kld_f
 int blvm_elbo_bwd(const double* g_loss, const double* g_elbo, double beta, double n_frames, int B, double* g64, float* g32,
                   void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * K8m  the reductions of the K-sample importance-weighted bound L_K = log (1/K) sum_k p(x, z_k) / q(z_k | x), z_k ~ q (evaluation
+ *      only, no backward; an addition beyond the reference, which reports the single-sample ELBO).
+ * blvm_gauss_logratio_fwd: the Monte-Carlo log-density ratio at the drawn z.  All six inputs [rows=Tp*B, Z] fp32 in the layouts and
+ *   with the mask of blvm_kl_fwd (step t of row b counts iff t*stride < x_sl[b]).  Per element
+ *     r = log(sd_p) - log(sd_q) - eps^2 / 2 + ((z - mu_p) / sd_p)^2 / 2
+ *   (the q-term from eps: z - mu_q = sd_q eps is how z was drawn, so mu_q is not read; the p-term from the stored z, the value the
+ *   decoder saw).  out[b] = the float64 sum of r over the live steps and all Z elements of row b, WRITTEN (not accumulated): every
+ *   word of out is written (a row with x_sl[b] = 0 gets 0), the result does not depend on the prior contents of out, masked steps
+ *   are not read, and calls are bit-identical (fixed reduction order, no floating-point atomics).  Any Z >= 1 and any alignment:
+ *   16-byte loads where Z % 4 == 0 and the bases are aligned, a scalar path otherwise.  BLVM_EINVAL before any launch on a null
+ *   pointer, B, Tp, Z or stride < 1, a layout other than 0 or 1.
+ * blvm_iw_reduce: log_w [K,B] float64 -> with m = max_k log_w[k,b] and w = exp(log_w - m):
+ *     bound[b] = m + log sum_k w - log K,   ess[b] = (sum_k w)^2 / sum_k w^2   (ess may be NULL)
+ *   summed over k in ascending order (calls are bit-identical).  A column of all -inf gives bound = -inf, ess = 0; a NaN anywhere in
+ *   a column gives NaN in that column only.  K = 1 returns log_w itself, K equal weights return that weight and ess = K, exactly.
+ * ------------------------------------------------------------------------------------------------------------- */
+int blvm_gauss_logratio_fwd(const float* mu_q, const float* sd_q, const float* mu_p, const float* sd_p, const float* z,
+                            const float* eps, int layout, const int32_t* x_sl, int B, int Tp, int Z, int stride, double* out,
+                            void* stream);
+int blvm_iw_reduce(const double* log_w, int K, int B, double* bound, double* ess, void* stream);
+
 /* K8b  Gaussian latent head, elementwise over n = rows*Z: sd = softplus_beta(raw) + sd_eps for prior and posterior
  * (`DiagonalGaussianDenseSTCN.forward`, `blvm/models/stcn/stcn.py:32-76`), posterior combination (mode 0 plain, 1 residual
  * mu_q += mu_p, 2 precision-weighted `variational.py:125-138`) and the reparameterised sample z = mu_q + sd_q*eps
