@@ -141,6 +141,33 @@ class LogMelSpectrogram(Transform):
         return features[0] if waveform.dim() == 1 else features
 
 
+class LatentRepresentation(Transform):
+    """Fresh latents z ~ q(z | x) of a frozen latent-variable model as the probe's features, drawn anew on every call (the
+    reference's `get_representation`, experiments/experiment_asr_ctc_resampling.py:184-199): `forward(x [B,L] on the device, x_sl)`
+    -> (features [B, D, T], lengths [B]) from `model.represent(x, x_sl, level, num_samples)`, which runs only what the latents need.
+    `features` is the VIEW `z.permute(1, 2, 0)` of the time-major result z [T,B,D]: `SimpleLSTMASR.forward` turns its input back with
+    `x.permute(2, 0, 1).contiguous()`, which on this view is z itself, so the hand-off to the LSTM kernels copies nothing.
+    The model is put in `eval()` and its parameters are frozen (`requires_grad_(False)`); frames past an utterance's length are zero."""
+
+    def __init__(self, model: nn.Module, level: int = 0, num_samples: int = 1):
+        super().__init__()
+        if not callable(getattr(model, "represent", None)):
+            raise TypeError(f"LatentRepresentation: {type(model).__name__} has no represent() (the latent-variable models have)")
+        self.model = model.eval()
+        for p in self.model.parameters():
+            p.requires_grad_(False)
+        self.level, self.num_samples = level, num_samples
+
+    def train(self, mode: bool = True):
+        """The extractor stays in `eval()` whatever mode the modules around it are put in."""
+        return super().train(False)
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor, lengths):
+        z, z_sl = self.model.represent(x, lengths, level=self.level, num_samples=self.num_samples)
+        return z.permute(1, 2, 0), z_sl
+
+
 class Normalize(Transform):
     """(x - mean) / std with fixed statistics, or the example's own over `dim` (transforms.py:169-179)."""
 

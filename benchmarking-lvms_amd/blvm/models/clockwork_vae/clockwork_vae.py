@@ -92,6 +92,11 @@ class CWVAE(nn.Module):
         B = t.shape[1] // nseg
         return t.view(k, nseg, B, -1).transpose(0, 1).reshape(nseg * k, B, -1)[:T_l]
 
+    @staticmethod
+    def represent_levels(num_levels: int, level: Optional[int]):
+        """The levels `represent(level=...)` computes, in order: the hierarchy is top-down, z[l] needs levels NL-1 .. l."""
+        return importance.levels_upto(range(num_levels - 1, -1, -1), level)
+
     def _resets(self, l: int) -> int:
         return int(self.strides[l + 1]) if (self.with_resets and l < self.num_levels - 1) else 0
 
@@ -157,16 +162,17 @@ class CWVAE(nn.Module):
         return y, x_sl, x_sl_dev, level_sl, same_paddings, encodings
 
     def _levels(self, encodings, states0, eps_of, x_sl_dev, level_sl, same_paddings, pad_same: bool, B: int, free_nats: float,
-                log_ratio: bool = False):  # fmt: skip
+                log_ratio: bool = False, latents_to: Optional[int] = None):  # fmt: skip
         """The stochastic part, top level first: one cell sequence per level on B rows and the context decoder below it.
         `eps_of(l, T_l)` -> the level's noise [T_l,B,z_l].  Returns (kld_l, kld_fn_l, latents, enc_mus, prior_mus, state_n, the
         bottom context).  `log_ratio` (`iw_bound`): kld_l (= kld_fn_l) are the sums of log q(z) - log p(z) at the drawn z (K8m),
-        folded over segments exactly as the KL is, and no state is gathered."""
+        folded over segments exactly as the KL is, and no state is gathered.  `latents_to` = l (`represent`): the levels
+        `represent_levels` names only, no state is gathered and level l's context decoder does not run (context: None)."""
         dev = x_sl_dev.device
         NL, os_ = self.num_levels, [int(s) for s in self.overall_strides]
         kld_l, kld_fn_l, latents, enc_mus, prior_mus, state_n = ([None] * NL for _ in range(6))
         context = None
-        for l in range(NL - 1, -1, -1):
+        for l in range(NL - 1, -1, -1) if latents_to is None else self.represent_levels(NL, latents_to):
             enc_l = encodings[l]
             T_l = enc_l.shape[0] if (pad_same or context is None) else context.shape[0]
             if enc_l.shape[0] < T_l or (context is not None and context.shape[0] < T_l):
@@ -209,7 +215,10 @@ class CWVAE(nn.Module):
             kld_l[l], kld_fn_l[l] = kld, kld_fn
             latents[l], enc_mus[l], prior_mus[l] = zs[1:].transpose(0, 1), mu_q.transpose(0, 1), mu_p.transpose(0, 1)
 
-            if not log_ratio:
+            if latents_to is not None:
+                if l == latents_to:
+                    return kld_l, kld_fn_l, latents, enc_mus, prior_mus, state_n, None
+            elif not log_ratio:
                 # state to carry into the next split: the one at each example's last valid step (clockwork_vae.py:283-290)
                 stop = ops.upload_i32((level_sl[l] - 1).clamp(0) + 1, dev).long()
                 rows = torch.arange(B, device=dev)
@@ -276,6 +285,38 @@ class CWVAE(nn.Module):
                                                               log_ratio=True)  # fmt: skip
                 parts.append(self._log_prob(context, yy, sl) - sum(ratios))
             return importance.finish(parts, K, B, float(x_sl.sum()))
+
+    @torch.no_grad()
+    def represent(self, x, x_sl, level: Optional[int] = None, num_samples: int = 1, eps: Optional[List[torch.Tensor]] = None,
+                  max_rows: Optional[int] = None):  # fmt: skip
+        """Latents z_l ~ q(z_l | x, context) of a frozen model -> (z, z_sl): per level z [T_l,B,z_l] fp32 TIME-MAJOR and z_sl [B] as
+        `forward`'s `output.z_sl[l]` — the lists over levels for `level=None`, one entry for `level=l`; frames t >= z_sl[b] are
+        exactly zero.  Only what z needs runs: the conv encoder once on the B utterances, the cell sequences of levels NL-1 .. l
+        (`represent_levels`) and the context decoders of the levels ABOVE l — never level 0's decoder, the head, the state gather,
+        the ELBO or the metrics, and for l >= 1 not the level-0 cell sequence.  `num_samples` = K: the mean over K draws, on passes
+        of c * B rows as `iw_bound` lays them (c * B <= `max_rows`), summed in particle order by K8r (`ops.particle_mean`):
+        bit-identical for every `max_rows`.  `eps[l]` [T_l,B,z_l] ([K,T_l,B,z_l] for K > 1) supplies the noise, else it is drawn top
+        level first as `forward` draws it (K = 1: the same seed gives `forward`'s latents).  Same padding, as `forward`'s default.
+        Operand mode: the process's current one."""
+        K = importance.check_samples(num_samples)
+        NL = self.num_levels
+        levels = self.represent_levels(NL, level)
+        y, _, x_sl_dev, level_sl, same_paddings, encodings = self._front(x, x_sl, None, False, True)
+        B, dev = y.shape[0], y.device
+        lens = {l: ops.upload_i32(level_sl[l], dev) for l in levels}
+        eps_k = None if eps is None else {l: importance.particle_axis(eps[l], K) for l in levels}
+        outs = dict.fromkeys(levels)
+        for k0, c in importance.passes(K, B, max_rows):
+            sl = x_sl_dev if c == 1 else x_sl_dev.repeat(c)
+            eps_of = lambda l, T_l: importance.pass_eps(None if eps_k is None else eps_k[l], k0, c, T_l, B, self.z_size[l], dev)  # noqa: E731, B023
+            latents = self._levels([importance.tile_rows(e, c) for e in encodings], [None] * NL, eps_of, sl,
+                                   [s if c == 1 else s.repeat(c) for s in level_sl], same_paddings, True, c * B, 0.0,
+                                   latents_to=levels[-1])[2]  # fmt: skip
+            for l in levels:
+                outs[l] = importance.mean_pass(outs[l], latents[l].transpose(0, 1), lens[l], B, k0, c, K)
+        if level is not None:
+            return outs[level], level_sl[level]
+        return [outs[l] for l in range(NL)], level_sl
 
     def build_metrics(self, loss, elbo, log_prob, kld, kld_l, x_sl, beta, free_nats):
         """Metric names / reductions of clockwork_vae.py:106-130; all sums leave the device in one deferred transfer."""
@@ -386,6 +427,10 @@ class CWVAEAudio(BaseModel):
     @torch.no_grad()
     def iw_bound(self, x, x_sl, num_samples: int, eps=None, max_rows=None):
         return self.cwvae.iw_bound(x, x_sl, num_samples, eps, max_rows)
+
+    @torch.no_grad()
+    def represent(self, x, x_sl, level=None, num_samples: int = 1, eps=None, max_rows=None):
+        return self.cwvae.represent(x, x_sl, level, num_samples, eps, max_rows)
 
     def generate(self, *args, **kwargs):
         return self.cwvae.generate(*args, **kwargs)

@@ -5,7 +5,10 @@
 an evaluation quantity beyond the reference, which reports the single-sample ELBO.  Each model runs its deterministic part once on
 the B utterances, tiles it along the batch axis for a pass of c particles (rows particle-major: row k * B + b) and runs its
 stochastic part and its head on the c * B rows through the kernels `forward` uses; the Monte-Carlo log-ratio and the reduction over
-particles are K8m (`ops.gauss_log_ratio_sums`, `ops.iw_reduce`)."""
+particles are K8m (`ops.gauss_log_ratio_sums`, `ops.iw_reduce`).
+
+The models' `represent` methods lay their particles out the same way (`passes`, `tile_rows`, `pass_eps`) but stop at the latents:
+the level dependency rule (`levels_upto`) and the mean over particles with the padding zeroed, K8r (`mean_pass`), are below."""
 import contextlib
 from types import SimpleNamespace
 
@@ -58,6 +61,32 @@ def pass_eps(eps, k0: int, c: int, T: int, B: int, Z: int, dev):
     if e.shape != (c, T, B, Z):
         raise ValueError(f"iw_bound: eps must be [K, {T}, {B}, {Z}] per level, got {tuple(eps.shape)}")
     return e.permute(1, 0, 2, 3).reshape(T, c * B, Z).contiguous()
+
+
+# ---- `represent()`: the latents alone, K particles averaged (K8r) -------------------------------------------------------------------
+def levels_upto(order, level):
+    """The dependency rule of a latent hierarchy visited in `order` (each level conditions on the one visited before it): the
+    levels `z[level]` needs, in visiting order; all of them for None.  A level outside the hierarchy raises IndexError."""
+    order = list(order)
+    if level is None:
+        return order
+    if isinstance(level, bool) or not isinstance(level, int) or level not in order:
+        raise IndexError(f"represent: level {level!r} is outside the hierarchy of {len(order)} level(s)")
+    return order[: order.index(level) + 1]
+
+
+def particle_axis(eps, K: int):
+    """`represent`'s noise with the particle axis in front: a single particle's noise may come in `forward`'s shape [T, B, Z]."""
+    if eps is None:
+        return None
+    eps = torch.as_tensor(eps)
+    return eps.unsqueeze(0) if (K == 1 and eps.ndim == 3) else eps
+
+
+def mean_pass(out, z, lens_dev, B: int, k0: int, c: int, K: int):
+    """Particles k0 .. k0 + c - 1 (z [T, c * B, Z], row k * B + b) join the running sum `out` [T, B, Z] (None on the first pass); the
+    last pass scales by 1 / K and zeroes the frames past `lens_dev`.  One K8r launch; K = 1 is z with its padding zeroed."""
+    return ops.particle_mean(z, lens_dev, B, out=out, first=k0 == 0, last=k0 + c == K, scale=1.0 / K)
 
 
 def finish(parts, K: int, B: int, n_frames: float):

@@ -213,6 +213,30 @@ class SRNN(nn.Module):
             return importance.finish(parts, K, B, float(x_sl_host.sum()))
 
     @torch.no_grad()
+    def represent(self, x, x_sl, level: Optional[int] = None, num_samples: int = 1, eps: Optional[torch.Tensor] = None,
+                  max_rows: Optional[int] = None):  # fmt: skip
+        """Latents z ~ q(z | x) of a frozen model -> (z [T',B,z] fp32 TIME-MAJOR, z_sl [B] as `forward`'s `output.z_sl`); frames
+        t >= z_sl[b] are exactly zero.  Only what z needs runs: the encoder and the two GRUs (d, a) once on the B utterances and the
+        latent chain (no decoder, no head, no ELBO, no metrics).  `num_samples` = K: the mean over K draws, the chain on passes of
+        c * B rows as `iw_bound` lays them (c * B <= `max_rows`), summed in particle order by K8r (`ops.particle_mean`):
+        bit-identical for every `max_rows`.  `eps` [T',B,z] ([K,T',B,z] for K > 1) supplies the noise, else it is drawn as `forward`
+        draws it (K = 1: the same seed gives `forward`'s latents).  `level`: None or 0.  Operand mode: the process's current one."""
+        K = importance.check_samples(num_samples)
+        importance.levels_upto([0], level)
+        S, enc_lin, _, _ = self._plan()
+        y, _, x_sl_dev, z_sl, Tp, stride, d, a, _, _ = self._deterministic(x, x_sl, None, None, S, enc_lin)
+        B, H, Z, R = y.shape[0], self.h_dim, self.z_dim, self.r_dim
+        lens = ops.upload_i32(z_sl, y.device)
+        eps, out = importance.particle_axis(eps, K), None
+        for k0, c in importance.passes(K, B, max_rows):
+            e = importance.pass_eps(eps, k0, c, Tp, B, Z, y.device)
+            sl = x_sl_dev if c == 1 else x_sl_dev.repeat(c)
+            zs = ops.srnn_latent_chain(importance.tile_rows(d, c), importance.tile_rows(a, c), None, e, sl, self._chain_params(), H, Z, R,
+                                       self.residual_posterior, stride, 0.0, self.prior[6].epsilon)[0]  # fmt: skip
+            out = importance.mean_pass(out, zs[1:], lens, B, k0, c, K)
+        return out, z_sl
+
+    @torch.no_grad()
     def generate(self, x, u=None, d_0=None, a_0=None, z_0=None, h_p_0=None, n_samples: int = 1, max_timesteps: int = 100,
                  stop_value: float = None, use_mode: bool = False, eps=None, uniforms=None, fused: Optional[bool] = None):  # fmt: skip
         """Unconditional autoregressive sampling (srnn.py:304-403): encode the previous frame stack, one GRU step for d_t, draw
@@ -410,6 +434,10 @@ class SRNNAudio(BaseModel):
     @torch.no_grad()
     def iw_bound(self, x, x_sl, num_samples: int, eps=None, max_rows=None):
         return self.srnn.iw_bound(x, x_sl, num_samples, eps, max_rows)
+
+    @torch.no_grad()
+    def represent(self, x, x_sl, level=None, num_samples: int = 1, eps=None, max_rows=None):
+        return self.srnn.represent(x, x_sl, level, num_samples, eps, max_rows)
 
     def generate(self, n_samples: int = 1, max_timesteps: int = 100, use_mode: bool = False, x=None, u=None, d_0=None, a_0=None,
                  z_0=None, eps=None, uniforms=None, fused: Optional[bool] = None):  # fmt: skip

@@ -125,13 +125,21 @@ class STCN(BaseModel):
         self.likelihood_module = likelihood_module
 
     # ---- inference over the latent hierarchy (stcn.py:296-327) -------------------------------------------------------
-    def infer(self, skips, eps, x_sl_dev, B: int, T: int, free_nats: float, log_ratio: bool = False):
+    @staticmethod
+    def represent_levels(n_latents: int, top_down: bool, level: Optional[int]):
+        """The levels `represent(level=...)` computes, in `infer`'s order: top-down z[l] needs levels n-1 .. l, bottom-up 0 .. l."""
+        return importance.levels_upto(reversed(range(n_latents)) if top_down else range(n_latents), level)
+
+    def infer(self, skips, eps, x_sl_dev, B: int, T: int, free_nats: float, log_ratio: bool = False, latents_to: Optional[int] = None):
         """skips[l] [T+1,B,C] time-major.  Returns per level (mu_p, sd_p, mu_q, sd_q, z) [T,B,Z_l] and the KL sums.
-        `log_ratio` (`iw_bound`): the sums are those of log q(z) - log p(z) at the drawn z (K8m), for either direction."""
+        `log_ratio` (`iw_bound`): the sums are those of log q(z) - log p(z) at the drawn z (K8m), for either direction.
+        `latents_to` = l (`represent`): only the levels `represent_levels` names are visited, and no sums are made."""
         n, S = self.n_latents, self.n_stack_frames
         mu_p, sd_p, mu_q, sd_q, z = ([None] * n for _ in range(5))
         klds, klds_fn = [None] * n, [None] * n
         order = list(reversed(range(n))) if self.top_down else list(range(n))  # bottom-up: each latent conditions on the one below
+        if latents_to is not None:
+            order = self.represent_levels(n, self.top_down, latents_to)  # (a prefix of the full order)
         for i, l in enumerate(order):
             d_p, d_q = skips[l][:-1], skips[l][1:]  # prior sees frame t-1's features, the posterior frame t's (stcn.py:300-302)
             if i > 0:
@@ -144,7 +152,9 @@ class STCN(BaseModel):
             sp, mq_c, sq_c, z_l = ops.gauss_latent(mp, sp_raw, mq, sq_raw, e, self.prior[l].softplus_beta,
                                                    self.posterior[l].softplus_beta, self.prior[l].epsilon,
                                                    ops.RSSM_PRECISION if self.precision_posterior else ops.RSSM_PLAIN)  # fmt: skip
-            if log_ratio:
+            if latents_to is not None:
+                pass  # the latents alone: no sums of either kind
+            elif log_ratio:
                 klds[l] = klds_fn[l] = ops.gauss_log_ratio_sums(mq_c, sq_c, mp, sp, z_l, e, x_sl_dev, ops.LAYOUT_TIME_MAJOR, B, T, Z, S)
             elif self.top_down:
                 klds[l], klds_fn[l] = ops.gaussian_kl_sums(mq_c, sq_c, mp, sp, x_sl_dev, ops.LAYOUT_TIME_MAJOR, B, T, Z, S, free_nats)
@@ -277,6 +287,38 @@ class STCN(BaseModel):
                 _, log_prob = self._observe(z, yy, sl, n, T, T_y)
                 parts.append(log_prob - sum(ratios))
             return importance.finish(parts, K, B, float(x_sl_host.sum()))
+
+    @torch.no_grad()
+    def represent(self, x, x_sl, level: Optional[int] = None, num_samples: int = 1, eps: Optional[List[torch.Tensor]] = None,
+                  max_rows: Optional[int] = None):  # fmt: skip
+        """Latents z_l ~ q(z_l | x, z of the level visited before) of a frozen model -> (z, z_sl): per level z [T',B,z_l] fp32
+        TIME-MAJOR and z_sl [B] as `forward`'s `output.z_sl[l]` — the lists over levels for `level=None`, one entry for `level=l`;
+        frames t >= z_sl[b] are exactly zero.  Only what z needs runs: the encoder stacks once on the B utterances and the prior /
+        posterior MLPs and latent heads of the levels `represent_levels` names (top-down n-1 .. l, bottom-up 0 .. l) — never the
+        observation model (`_observe`), the KL sums, the ELBO or the metrics.  `num_samples` = K: the mean over K draws, on passes of
+        c * B rows as `iw_bound` lays them (c * B <= `max_rows`), summed in particle order by K8r (`ops.particle_mean`):
+        bit-identical for every `max_rows`.  `eps[l]` [T',B,z_l] ([K,T',B,z_l] for K > 1) supplies the noise, else it is drawn in
+        `forward`'s order (K = 1: the same seed gives `forward`'s latents).  Receptive-field padding, as `forward`'s default.
+        Operand mode: the process's current one."""
+        K = importance.check_samples(num_samples)
+        n, S = self.n_latents, self.n_stack_frames
+        levels = self.represent_levels(n, self.top_down, level)
+        y, x_sl_host, mask_len, B, T, _, skips = self._front(x, x_sl, None, True)
+        z_sl = torch.ceil(x_sl_host / S).long()
+        lens = ops.upload_i32(z_sl, y.device)
+        outs = dict.fromkeys(levels)
+        for k0, c in importance.passes(K, B, max_rows):
+            e = [None] * n
+            for l in levels:  # the reference's draw order
+                e[l] = importance.pass_eps(None if eps is None else importance.particle_axis(eps[l], K), k0, c, T, B, self.latent_size[l],
+                                           y.device)  # fmt: skip
+            sl = mask_len if c == 1 else mask_len.repeat(c)
+            z = self.infer([importance.tile_rows(s, c) for s in skips], e, sl, c * B, T, 0, latents_to=levels[-1])[4]
+            for l in levels:
+                outs[l] = importance.mean_pass(outs[l], z[l], lens, B, k0, c, K)
+        if level is not None:
+            return outs[level], z_sl
+        return [outs[l] for l in range(n)], [z_sl] * self.n_stacks
 
     def build_metrics(self, loss, elbo, log_prob, kld, klds, x_sl, beta, free_nats):
         """Metric names / reductions of stcn.py:208-245."""

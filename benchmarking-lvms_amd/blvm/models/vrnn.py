@@ -300,6 +300,31 @@ class VRNN(nn.Module):
             return importance.finish(parts, K, B, float(x_sl_host.sum()))
 
     @torch.no_grad()
+    def represent(self, x: torch.Tensor, x_sl: torch.Tensor, level: Optional[int] = None, num_samples: int = 1,
+                  eps: Optional[torch.Tensor] = None, max_rows: Optional[int] = None):  # fmt: skip
+        """Latents z ~ q(z | x) of a frozen model -> (z [T',B,z] fp32 TIME-MAJOR, z_sl [B] as `forward`'s `output.z_sl`); frames
+        t >= z_sl[b] are exactly zero.  Only what z needs runs: the encoder once on the B utterances and the cell (no decoder, in the
+        cell's launch or after it, no head, no KL sums, no ELBO, no metrics).  `num_samples` = K: the mean over K draws, the particles
+        on passes of c * B rows as `iw_bound` lays them (c * B <= `max_rows`), summed in particle order by K8r
+        (`ops.particle_mean`): bit-identical for every `max_rows`.  `eps` [T',B,z] ([K,T',B,z] for K > 1) supplies the noise, else
+        it is drawn as `forward` draws it (K = 1: the same seed gives `forward`'s latents).  `level`: None or 0.  Operand mode: the
+        process's current one."""
+        K = importance.check_samples(num_samples)
+        importance.levels_upto([0], level)
+        S, enc_lin, _, _ = self._plan()
+        y, x_sl_host, x_sl_dev, Tp, stride, enc = self._encode(x, x_sl, S, enc_lin)
+        B, Z = y.shape[0], self.z_dim
+        z_sl = (x_sl_host / stride).ceil().int()
+        lens = ops.upload_i32(z_sl, y.device)
+        eps, out = importance.particle_axis(eps, K), None
+        for k0, c in importance.passes(K, B, max_rows):
+            e = importance.pass_eps(eps, k0, c, Tp, B, Z, y.device)
+            sl = x_sl_dev if c == 1 else x_sl_dev.repeat(c)
+            z = self.vrnn_cell.sequence(importance.tile_rows(enc, c), None, e, sl, stride, 0.0, decoder=None)[7]
+            out = importance.mean_pass(out, z, lens, B, k0, c, K)
+        return out, z_sl
+
+    @torch.no_grad()
     def generate(self, x: torch.Tensor, h0: Optional[torch.Tensor] = None, n_samples: int = 1, max_timesteps: int = 100,
                  stop_value: float = None, use_mode: bool = False, eps: Optional[torch.Tensor] = None, uniforms=None,
                  fused: Optional[bool] = None):  # fmt: skip
@@ -496,6 +521,10 @@ class VRNNAudio(BaseModel):
     @torch.no_grad()
     def iw_bound(self, x, x_sl, num_samples: int, eps=None, max_rows=None):
         return self.vrnn.iw_bound(x, x_sl, num_samples, eps, max_rows)
+
+    @torch.no_grad()
+    def represent(self, x, x_sl, level=None, num_samples: int = 1, eps=None, max_rows=None):
+        return self.vrnn.represent(x, x_sl, level, num_samples, eps, max_rows)
 
     def generate(self, n_samples: int = 1, max_timesteps: int = 100, use_mode: bool = False, x=None, h0=None, eps=None, uniforms=None,
                  fused: Optional[bool] = None):  # fmt: skip

@@ -675,6 +675,33 @@ def iw_max_rows(B: int, max_rows: Optional[int] = None) -> int:
     return int(max_rows) if max_rows is not None else max(int(B), int(load().blvm_pchain_max_batch()))
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# K8r: the mean over particles with the padding zeroed, the last launch of every `represent()` level (evaluation only)
+# ----------------------------------------------------------------------------------------------------------------------
+
+
+def particle_mean(z, lens_dev, B: int, out=None, first: bool = True, last: bool = True, scale: float = 1.0):
+    """z [T, c*B, Z] fp32 time-major (row k * B + b) -> out [T, B, Z] (`blvm_particle_mean`): out = (0 if `first` else out) + the c
+    particles in ascending order, one fp32 add each; with `last`, times `scale` on frames t < lens_dev[b] and +0 beyond.  `out` is
+    allocated where None (then `first` must hold: there is nothing to add to).  c = 1, scale = 1: z with the padding zeroed."""
+    if z.ndim != 3 or z.shape[1] % int(B) or z.shape[1] < int(B):
+        raise _hip.BlvmHipError(f"particle_mean: z must be [T, c*B, Z] with B = {B}, got {tuple(z.shape)}")
+    z = _f32c(z.detach())
+    T, rows, Z = z.shape
+    if lens_dev.dtype != torch.int32 or lens_dev.numel() != B:
+        raise _hip.BlvmHipError("particle_mean: lens_dev must be int32 [B]")
+    pz = ptr(z)  # (refuses a CPU tensor before anything is allocated)
+    if out is None:
+        if not first:
+            raise _hip.BlvmHipError("particle_mean: a pass that is not the first needs the `out` of the passes before it")
+        out = torch.empty(T, B, Z, device=z.device, dtype=torch.float32)
+    elif out.shape != (T, B, Z) or out.dtype != torch.float32:
+        raise _hip.BlvmHipError(f"particle_mean: out must be fp32 [{T}, {B}, {Z}], got {out.dtype} {tuple(out.shape)}")
+    check(load().blvm_particle_mean(pz, ptr(lens_dev), T, rows // int(B), int(B), Z, int(bool(first)), int(bool(last)), float(scale),
+                                    ptr(out), stream_ptr()), "blvm_particle_mean")  # fmt: skip
+    return out
+
+
 class _ELBOFunction(torch.autograd.Function):
     """(log_prob, kld, kld_fn [B] float64) -> (loss scalar, elbo [B], sums [4]) in one launch; backward one launch (`blvm_elbo_bwd`)."""
 

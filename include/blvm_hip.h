@@ -367,6 +367,21 @@ int blvm_gauss_logratio_fwd(const float* mu_q, const float* sd_q, const float* m
                             void* stream);
 int blvm_iw_reduce(const double* log_w, int K, int B, double* bound, double* ess, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * K8r  the last launch of every `represent()` level (evaluation only, no backward): the mean of the latents over particles with the
+ *      frames past each utterance's length zeroed.  z [T, c*B, Z] fp32 time-major with row k*B + b (particle k of utterance b, as the
+ *      iw_bound passes lay their rows), lens [B] in frames of this level, out [T, B, Z].  Per element
+ *        acc = first ? 0 : out;   acc += z[t, k*B+b, :] for k = 0 .. c-1, one fp32 add each;
+ *        out = last ? (t < lens[b] ? acc * scale : 0) : acc
+ *      so K particles split over any passes (first on the first, last and scale = 1/K on the last) are ONE chain of fp32 adds in
+ *      particle order: bit-identical for every split and from call to call.  c = 1, first = last = 1, scale = 1 is z itself with the
+ *      dead frames +0, whatever z held there.  With first = 1 no word of out depends on its previous contents and every word is
+ *      written.  Streaming: 16-byte loads and stores, grid-stride, no LDS, no atomics.  BLVM_EINVAL before any launch on a null
+ *      pointer, T, B or Z < 1, c < 1, Z % 4 != 0, z or out not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------------------- */
+int blvm_particle_mean(const float* z, const int32_t* lens, int T, int c, int B, int Z, int first, int last, float scale,
+                       float* out, void* stream);
+
 /* K8b  Gaussian latent head, elementwise over n = rows*Z: sd = softplus_beta(raw) + sd_eps for prior and posterior
  * (`DiagonalGaussianDenseSTCN.forward`, `blvm/models/stcn/stcn.py:32-76`), posterior combination (mode 0 plain, 1 residual
  * mu_q += mu_p, 2 precision-weighted `variational.py:125-138`) and the reparameterised sample z = mu_q + sd_q*eps
