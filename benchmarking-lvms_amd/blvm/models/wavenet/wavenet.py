@@ -1,8 +1,9 @@
 """WaveNet with the reference's construction API and state_dict layout (blvm/models/wavenet/wavenet.py:29-293).
 
 forward: left-pad by the receptive field -> causal conv -> in_transform -> 50 gated residual blocks (K10, one autograd
-node) -> sum of skips * variance_scale -> ReLU-Linear-ReLU -> likelihood Linear (K6) -> DMoL log-likelihood (K7), or with a
-`CategoricalDense` head its Linear and the softmax log-likelihood in one (K7d: the logits are never stored).
+node) -> sum of skips * variance_scale -> ReLU-Linear-ReLU -> likelihood Linear (K6) -> DMoL log-likelihood (K7), the Gaussian-mixture
+(K7b, 1..16 components) or Gaussian one (K7c), or with a `CategoricalDense` head its Linear and the softmax log-likelihood in one (K7d:
+the logits are never stored).
 Loss in fp32 like the reference: -sum(ll * mask) / sum(x_sl) (wavenet.py:128-146).
 
 `embedding_dim=E` is the class-in model of the original paper (wavenet.py:105-113,182): sample classes -> nn.Embedding(num_bins, E) ->
@@ -19,7 +20,8 @@ from blvm import ops
 from blvm.evaluation import BitsPerDimMetric, DeferredScalars, LLMetric, LossMetric
 from blvm.models.base_model import BaseModel
 from blvm.models.vrnn import LazyNamespace
-from blvm.modules.distributions import CategoricalDense, DiscretizedLogisticMixtureDense
+from blvm.modules.distributions import (CategoricalDense, DiagonalGaussianDense, DiagonalGaussianMixtureDense,
+                                        DiscretizedLogisticMixtureDense, gauss_rollout_head)  # fmt: skip
 from blvm.utils.operations import split_sequence
 from blvm.utils.padding import get_modulo_length
 
@@ -81,8 +83,8 @@ class WaveNet(BaseModel):
     def forward(self, x, x_sl, y=None, pad_causal: bool = True, pad_receptive_field: bool = True):
         lik, nsf, rf = self.likelihood, self.n_stack_frames, self.receptive_field
         cat = isinstance(lik, CategoricalDense)
-        if not cat and not isinstance(lik, DiscretizedLogisticMixtureDense):
-            raise NotImplementedError("libblvm_hip: WaveNet is built with the DMoL and the categorical likelihood heads")
+        if not cat and not isinstance(lik, (DiscretizedLogisticMixtureDense, DiagonalGaussianMixtureDense, DiagonalGaussianDense)):
+            raise NotImplementedError("libblvm_hip: WaveNet is built with the DMoL, the categorical, the Gaussian and the Gaussian-mixture likelihood heads")
         if x.ndim == 3:
             x = x.squeeze(-1)
         dev = x.device
@@ -138,10 +140,40 @@ class WaveNet(BaseModel):
         mask_len = ops.upload_i32(x_sl_host.clamp(min=0, max=T_y), dev)
         if cat:
             return self._categorical_outputs(logits, y, mask_len, x_sl_host, x_sl_strided, skip_sum, B, T_y, skip_size)
-        par = ops.linear(logits.view(skip_size * B * nsf, C), lik.params.weight, lik.params.bias)  # [skip*B*nsf, 3K]
-        log_prob = ops.dmol_log_prob(par.view(skip_size * B, nsf * lik.out_features), None, None, y, mask_len,
-                                     ops.LAYOUT_TIME_MAJOR, B, T_y, skip_size, nsf, lik.num_mix, lik.num_bins,
-                                     lik.log_epsilon).to(torch.float32)  # fmt: skip
+        return self._float_head_outputs(logits, y, mask_len, x_sl_host, x_sl_strided, skip_sum, B, T_y, skip_size)
+
+    def _head_parameters(self, p):
+        """Head outputs p [B,T,F] -> `likelihood.forward`'s tuple in the reference's shapes: DMoL (logits [B,T,K], locs [B,T,1,K],
+        log_scales [B,T,1,K] clamped), the mixture (logits, mu [B,T,1,K], sd [B,T,1,K]), the Gaussian (mu [B,T,1], sd [B,T,1])."""
+        lik = self.likelihood
+        if isinstance(lik, DiagonalGaussianDense):
+            mu, raw = p.chunk(2, dim=-1)
+            return mu, lik.sd_activation(raw)
+        K = lik.num_mix
+        logits_, rest = p[..., :K], p[..., K:].reshape(*p.shape[:-1], 1, 2 * K)
+        locs, scales = rest.chunk(2, dim=-1)
+        if isinstance(lik, DiagonalGaussianMixtureDense):
+            return logits_, locs, lik.sd_activation(scales)
+        return logits_, locs, scales.clamp(min=lik.log_epsilon)
+
+    def _head_ll_twise(self, par2d, y, mask_len, B, T_y, skip_size):
+        """Masked frame-wise log-likelihood [B,T_y] of a float head from its outputs par2d [skip*B, nsf*F] (K7 / K7b / K7c)."""
+        lik, nsf = self.likelihood, self.n_stack_frames
+        tm = (par2d, None, None, y, mask_len, ops.LAYOUT_TIME_MAJOR, B, T_y, skip_size, nsf)
+        if isinstance(lik, DiagonalGaussianMixtureDense):
+            return ops.gmm_ll_twise(*tm, lik.num_mix, lik.softplus_beta, lik.epsilon if lik.epsilon > 0 else 0.0)[0]
+        if isinstance(lik, DiagonalGaussianDense):
+            return ops.gauss_ll_twise(*tm, lik.softplus_beta, lik.epsilon)[0]
+        return ops.dmol_ll_twise(*tm, lik.num_mix, lik.num_bins, lik.log_epsilon)[0]
+
+    def _float_head_outputs(self, dec, y, mask_len, x_sl_host, x_sl_strided, skip_sum, B, T_y, skip_size):
+        """A head on float targets — DMoL, Gaussian mixture, Gaussian — on the output transform's activations `dec` [skip*B, C*nsf]:
+        the head Linear C -> F as a K6 GEMM, then the head's fused log-likelihood on its F outputs per frame (F = 3 num_mix, or 2)."""
+        lik, nsf, C = self.likelihood, self.n_stack_frames, self.res_channels
+        F = lik.out_features
+        par = ops.linear(dec.view(skip_size * B * nsf, C), lik.params.weight, lik.params.bias)  # [skip*B*nsf, F]
+        log_prob = lik.fused_log_prob(par.view(skip_size * B, nsf * F), y, mask_len, ops.LAYOUT_TIME_MAJOR, B, T_y, skip_size, nsf,
+                                      fused_linear=False).to(torch.float32)  # fmt: skip
         n_frames = float(x_sl_host.sum())
         loss = -log_prob.sum() / n_frames
 
@@ -151,22 +183,14 @@ class WaveNet(BaseModel):
             LLMetric(sums[1], reduce_by=B),
             BitsPerDimMetric(sums[1], reduce_by=n_frames),
         ]
-        F = lik.out_features
 
         def parameters():
             p = par.detach().view(skip_size, B, nsf, F).permute(1, 0, 2, 3).reshape(B, skip_size * nsf, F)[:, :T_y]
-            logits_, rest = p[..., : lik.num_mix], p[..., lik.num_mix :].reshape(B, -1, 1, 2 * lik.num_mix)
-            locs, log_scales = rest.chunk(2, dim=-1)
-            return logits_, locs, log_scales.clamp(min=lik.log_epsilon)
-
-        def ll_twise():
-            ll, _ = ops.dmol_ll_twise(par.detach().view(skip_size * B, nsf * F), None, None, y, mask_len, ops.LAYOUT_TIME_MAJOR, B,
-                                      T_y, skip_size, nsf, lik.num_mix, lik.num_bins, lik.log_epsilon)  # fmt: skip
-            return ll
+            return self._head_parameters(p)
 
         lazy = dict(
             parameters=parameters,
-            log_prob_twise=ll_twise,
+            log_prob_twise=lambda: self._head_ll_twise(par.detach().view(skip_size * B, nsf * F), y, mask_len, B, T_y, skip_size),
             predictions=lambda ns: lik.sample(ns.parameters),
             predictions_mode=lambda ns: lik.mode(ns.parameters),
         )
@@ -220,6 +244,15 @@ class WaveNet(BaseModel):
         if isinstance(lik, CategoricalDense):
             k = lik.sample(parameters, uniforms=None if u is None else u.reshape(parameters.shape[:-1]))
             return lik.dequantize(k).unsqueeze(-1)
+        if isinstance(lik, DiagonalGaussianMixtureDense):  # u = (u [B,nsf,n], n [B,nsf]); None: uniform(1e-6, 1 - 1e-6), then randn
+            if u is None:
+                return lik.sample(parameters)
+            lead = parameters[0].shape[:-1]
+            return lik.sample(parameters, noise=(u[0].reshape(*lead, lik.num_mix), u[1].reshape(lead)))
+        if isinstance(lik, DiagonalGaussianDense):  # u = (None, n [B,nsf]) or n; None: randn
+            if u is None:
+                return lik.sample(parameters)
+            return lik.sample(parameters, noise=u[1] if isinstance(u, (tuple, list)) else u)
         return lik.sample(parameters) if u is None else lik.sample(parameters, uniforms=u)
 
     def split_sequence(self, x, x_sl, length: int):
@@ -244,11 +277,12 @@ class WaveNet(BaseModel):
         output, DIVIDES it by variance_scale (the reference's generate divides where forward multiplies, :274 — kept), applies
         the output transform and the head, samples, and shifts the window (FIFO).  Returns x_hat [B, n_frames, 1].
         `uniforms[t]` optionally supplies the head sampler's draws of frame t: the DMoL head's two, the categorical head's one [B]
-        (its class k is fed back and returned as the float `dequantize(k)`).
+        (its class k is fed back and returned as the float `dequantize(k)`), the Gaussian mixture's (u [B,nsf,num_mix] uniforms,
+        n [B,nsf] standard normals), the Gaussian head's (None, n [B,nsf]) or n; the Gaussian draws are not clamped.
         `cached=True` (the reference's TODO, arXiv:1611.09482): the same samples from per-block queues of past activations —
         one new frame per block per step instead of the whole window; at the widths the decode kernel takes (K10c: every frame in
-        one launch) through `ops.wavenet_decode` (the DMoL head, or the categorical head with 16 <= V <= 1024 classes, V a multiple of
-        16), otherwise block by block (`_generate_cached`).
+        one launch) through `ops.wavenet_decode` (the DMoL head, the Gaussian head, the Gaussian mixture of up to 10 components, or the
+        categorical head with 16 <= V <= 1024 classes, V a multiple of 16), otherwise block by block (`_generate_cached`).
         With `cached=True`, `x` [B,P,1] is a prompt: the queues are primed from its last receptive-field samples (`_prime`) and
         frames P, P+1, ... are drawn.  `return_state=True` returns (x_hat, state); `state=` continues from one (generation in
         chunks; `uniforms` are indexed from 0 for every call).
@@ -272,7 +306,7 @@ class WaveNet(BaseModel):
                 if x.size(0) != n_samples:
                     raise ValueError(f"WaveNet.generate: prompt of {x.size(0)} rows for n_samples = {n_samples}")
                 state = self._prime(x)
-            one_launch = self._decode_kernel_applies() or self._cat_decode_kernel_applies()
+            one_launch = self._decode_kernel_applies() or self._cat_decode_kernel_applies() or self._gauss_decode_kernel_applies()
             run = self._generate_one_launch if one_launch else self._generate_cached
             if state is None and not return_state:
                 return run(n_samples, n_frames, uniforms)
@@ -344,6 +378,14 @@ class WaveNet(BaseModel):
         return (isinstance(lik, CategoricalDense) and 16 <= lik.y_dim <= 1024 and lik.y_dim % 16 == 0 and self.n_stack_frames == 1
                 and self._decode_widths_fit())  # fmt: skip
 
+    def _gauss_decode_kernel_applies(self):
+        """The decode kernel's Gaussian heads: one output dimension, a mixture of 3 * num_mix <= 32 head rows (the DMoL head's padded
+        image; 11 or more components generate block by block), the widths of `_decode_kernel_applies`."""
+        lik = self.likelihood
+        if isinstance(lik, DiagonalGaussianMixtureDense):
+            return lik.y_dim == 1 and 3 * lik.num_mix <= 32 and self._decode_widths_fit()
+        return isinstance(lik, DiagonalGaussianDense) and lik.y_dim == 1 and self._decode_widths_fit()
+
     @torch.no_grad()
     def _prime(self, x):
         """Prompt x [B,P,1] (P >= 1) -> the decode state after its P samples.  Only the last receptive_field samples matter; a
@@ -374,7 +416,7 @@ class WaveNet(BaseModel):
         return WaveNetDecodeState(scratch, rings, win[:, -2:].contiguous(), P)
 
     def _one_launch_parts(self):
-        """The `weights` argument of `ops.wavenet_decode`; the head Linear is the DMoL head's `params`, the categorical head's `logits`."""
+        """The `weights` argument of `ops.wavenet_decode`; the head Linear is the categorical head's `logits`, any other head's `params`."""
         rs, lik = self.res_stack, self.likelihood
         t_in = rs.in_transform
         head = lik.logits if isinstance(lik, CategoricalDense) else lik.params
@@ -393,6 +435,17 @@ class WaveNet(BaseModel):
             else:
                 u = torch.stack([a.reshape(B) for a in uniforms[:n_frames]]).to(device=dev, dtype=torch.float32)
             return ops.CategoricalHead(lik.levels), u
+        head = gauss_rollout_head(lik)
+        if head is not None:  # the Gaussian heads: (u [n_frames,B,num_mix], n [n_frames,B]) for the mixture, n alone otherwise
+            mix = isinstance(head, ops.GmmHead)
+            if uniforms is None:  # the ranges `gauss_rollout_noise` documents
+                u = torch.empty(n_frames, B, lik.num_mix, device=dev).uniform_(1e-6, 1.0 - 1e-6) if mix else None
+                nrm = torch.randn(n_frames, B, device=dev)
+            else:
+                draws = [a if isinstance(a, (tuple, list)) else (None, a) for a in uniforms[:n_frames]]
+                u = torch.stack([torch.as_tensor(a).reshape(B, lik.num_mix) for a, _ in draws]).to(device=dev, dtype=torch.float32) if mix else None
+                nrm = torch.stack([torch.as_tensor(b).reshape(B) for _, b in draws]).to(device=dev, dtype=torch.float32)
+            return head, ((u, nrm) if mix else nrm)
         if uniforms is None:
             u = torch.empty(n_frames, B, lik.num_mix, device=dev).uniform_(1e-5, 1.0 - 1e-5)  # the reference's two draws (variational.py:309-349)
             v = torch.empty(n_frames, B, device=dev).uniform_(1e-8, 1.0 - 1e-8)

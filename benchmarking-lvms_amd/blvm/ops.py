@@ -449,8 +449,19 @@ class _GaussHeadFunction(torch.autograd.Function):
         return (d_dec if ctx.needs_input_grad[0] else None, dW, db) + (None,) * 11
 
 
+GMM_MAX_MIX = 16  # blvm_gmm_fwd / blvm_gmm_bwd: 1 <= num_mix <= 16 (csrc/dmol.hip)
+
+
+def _gmm_check_count(num_mix: int):
+    """The library refuses a count outside 1..16 before any launch; here that refusal is a NotImplementedError."""
+    if not 1 <= int(num_mix) <= GMM_MAX_MIX:
+        raise NotImplementedError(f"libblvm_hip: the Gaussian-mixture head is built for 1 <= num_mix <= {GMM_MAX_MIX}, got num_mix = {num_mix}")
+
+
 def gmm_log_prob(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, sd_beta, sd_eps):
-    """Per-utterance masked Gaussian-mixture log-likelihood sums [B] (float64); dec [rows, S*3*num_mix]."""
+    """Per-utterance masked Gaussian-mixture log-likelihood sums [B] (float64); dec [rows, S*3*num_mix], 1 <= num_mix <= 16 (K7b: ten
+    components on the path of the audio models, any other count on the general arm)."""
+    _gmm_check_count(num_mix)
     return _GaussHeadFunction.apply(dec, W, b, y, x_sl_dev, 1, layout, B, T, Tp, S, num_mix, float(sd_beta), float(sd_eps))
 
 
@@ -486,6 +497,39 @@ def dmol_ll_twise(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix=10, num_b
         "blvm_dmol_fwd",
     )  # fmt: skip
     return ll, lp
+
+
+def _gauss_ll_twise(kind, dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, sd_beta, sd_eps):
+    dec, y = _f32c(dec), _f32c(y)
+    W, b = (_f32c(W), _f32c(b)) if W is not None else (None, None)
+    F = 3 * num_mix if kind == 1 else 2
+    if dec.dim() != 2 or dec.shape[0] != B * Tp or dec.shape[1] != S * F:
+        raise _hip.BlvmHipError(f"Gaussian head: activations must be [B*T'={B * Tp}, S*F={S * F}], got {tuple(dec.shape)}")
+    if W is not None and tuple(W.shape) != (F, F):
+        raise _hip.BlvmHipError(f"Gaussian head: fused head weight must be [{F},{F}], got {tuple(W.shape)}")
+    if tuple(y.shape) != (B, T) or Tp * S < T:
+        raise _hip.BlvmHipError(f"Gaussian head: targets must be [B={B}, T={T}] with T <= T'*S={Tp * S}, got {tuple(y.shape)}")
+    lp = torch.zeros(B, device=dec.device, dtype=torch.float64)
+    ll = torch.zeros(B, T, device=dec.device, dtype=torch.float32)  # (caller zeroes: the kernel writes the unmasked frames only)
+    lib = load()
+    if kind == 1:
+        check(lib.blvm_gmm_fwd(ptr(dec), layout, ptr(W), ptr(b), ptr(y), ptr(x_sl_dev), B, T, Tp, S, num_mix, float(sd_beta), float(sd_eps),
+                               ptr(lp), ptr(ll), stream_ptr()), "blvm_gmm_fwd")  # fmt: skip
+    else:
+        check(lib.blvm_gauss_head_fwd(ptr(dec), layout, ptr(W), ptr(b), ptr(y), ptr(x_sl_dev), B, T, Tp, S, float(sd_beta), float(sd_eps),
+                                      ptr(lp), ptr(ll), stream_ptr()), "blvm_gauss_head_fwd")  # fmt: skip
+    return ll, lp
+
+
+def gmm_ll_twise(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, sd_beta, sd_eps):
+    """Masked frame-wise Gaussian-mixture log-likelihood [B,T] and its sums [B] float64 (no autograd); arguments as `gmm_log_prob`."""
+    _gmm_check_count(num_mix)
+    return _gauss_ll_twise(1, dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, num_mix, sd_beta, sd_eps)
+
+
+def gauss_ll_twise(dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, sd_beta, sd_eps):
+    """Masked frame-wise Gaussian log-likelihood [B,T] and its sums [B] float64 (no autograd); arguments as `gauss_log_prob`."""
+    return _gauss_ll_twise(2, dec, W, b, y, x_sl_dev, layout, B, T, Tp, S, 0, sd_beta, sd_eps)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1721,7 +1765,7 @@ class WaveNetDecodeOut(NamedTuple):
 
 def _wavenet_decode_pack(weights, head):
     """The packed weight image of K10c and its sizes: -> (lib, C, S, O, device, packed, dilations as a C array, tables).  The image ends
-    in the head Linear: padded with zeros to 32 rows (`DmolHead`), as it stands (`CategoricalHead`).  An embedded model (K10e) gives
+    in the head Linear: padded with zeros to 32 rows (`DmolHead`, `GmmHead`, and `GaussHead`'s [2,O]), as it stands (`CategoricalHead`).  An embedded model (K10e) gives
     (tables [2,V+1,C], bias) as `causal`: the tables travel beside the image, whose causal weights are zeros nobody reads."""
     causal, in_transform, blocks_params, dilations, out_linear, (hw, hb) = weights
     lib = load()
@@ -1733,9 +1777,10 @@ def _wavenet_decode_pack(weights, head):
         causal = (torch.zeros(2 * C, device=dev), causal[1])
     if causal[0].numel() != 2 * C:
         raise NotImplementedError("libblvm_hip: wavenet_decode is built for in_channels = n_stack_frames = 1")
-    if isinstance(head, DmolHead):
-        if hw.shape[0] > 32 or hw.shape[0] != 3 * head.num_mix:
-            raise NotImplementedError("libblvm_hip: wavenet_decode head must have 3 * num_mix <= 32 outputs")
+    if isinstance(head, (DmolHead, GmmHead, GaussHead)):
+        rows = 2 if isinstance(head, GaussHead) else 3 * head.num_mix
+        if hw.shape[0] > 32 or hw.shape[0] != rows:
+            raise NotImplementedError("libblvm_hip: wavenet_decode head must have 3 * num_mix <= 32 outputs (2 for the Gaussian head)")
         pad_w = torch.zeros(32 - hw.shape[0], hw.shape[1], device=dev)
         tail = [hw, pad_w, hb, pad_w.new_zeros(32 - hb.numel())]
         want = lib.blvm_wavenet_decode_pack_floats(C, S, O, len(blocks_params))
@@ -1756,21 +1801,25 @@ def _wavenet_decode_pack(weights, head):
 def wavenet_decode(weights, head, B: int, n_frames: int, inv_std: float, skip_scale: float, draws=None, resume=None):
     """K10c: all frames of B utterances in one launch.  weights = (causal, in_transform, blocks_params, dilations, out_linear,
     head_linear): (weight, bias) pairs, blocks_params as for wavenet_stack.  head = `DmolHead` with draws = (u [n_frames,B,num_mix],
-    v [n_frames,B]), or `CategoricalHead` with draws = u [n_frames,B]: uniform draws indexed from 0 (None: the mode, the arg-max class).
+    v [n_frames,B]), or `CategoricalHead` with draws = u [n_frames,B]: uniform draws indexed from 0 (None: the mode, the arg-max class);
+    `GmmHead` with draws = (u [n_frames,B,num_mix] uniforms, n [n_frames,B] standard normals) or `GaussHead` with draws = n [n_frames,B]
+    (None: the arg-max component's mean / the mean; these two draws are not clamped).
     resume = (t0, samples [B,2], scratch) continues from a state: `scratch` holds the ring buffers after absolute frame t0 - 1
     (`wavenet_prime_rings` or an earlier call; updated in place), samples the last two samples.  -> `WaveNetDecodeOut`.
     An embedded model (K10e) with the categorical head: `causal` = (tables [2,V+1,C] of `wavenet_embed_tables`, bias); the class is fed
     back as a class, the zero start is a past of class 0, and samples (in and out) are the last two CLASSES, int32 [B,2]."""
     lib, C, S, O, dev, packed, dil, tables = _wavenet_decode_pack(weights, head)
-    dmol, n = isinstance(head, DmolHead), len(dil)
-    shapes = [(n_frames, B, head.num_mix), (n_frames, B)] if dmol else [(n_frames, B)]
+    gauss = 1 if isinstance(head, GmmHead) else 2 if isinstance(head, GaussHead) else 0
+    pair = isinstance(head, (DmolHead, GmmHead))  # two draws per frame
+    dmol, n = pair or gauss == 2, len(dil)  # the float heads: one output x, no classes
+    shapes = [(n_frames, B, head.num_mix), (n_frames, B)] if pair else [(n_frames, B)]
     if draws is None:
         draws = [None] * len(shapes)
     else:
-        draws = [_f32c(t) for t in (draws if dmol else (draws,))]
+        draws = [_f32c(t) for t in (draws if pair else (draws,))]
         if [tuple(t.shape) for t in draws] != shapes:
-            raise ValueError("wavenet_decode: the draws must be (u [n_frames,B,num_mix], v [n_frames,B]) for the DMoL head and u [n_frames,B] "
-                             "for the categorical head")  # fmt: skip
+            raise ValueError("wavenet_decode: the draws must be (u [n_frames,B,num_mix], v [n_frames,B]) for the DMoL and the Gaussian-mixture "
+                             "head and u [n_frames,B] for the categorical head, n [n_frames,B] for the Gaussian head")  # fmt: skip
     n_scratch = lib.blvm_wavenet_decode_scratch_floats(dil, n, B, C, S)
     f32 = dict(device=dev, dtype=torch.float32)
     if resume is None:
@@ -1786,13 +1835,20 @@ def wavenet_decode(weights, head, B: int, n_frames: int, inv_std: float, skip_sc
             raise ValueError("wavenet_decode: samples must be [B,2]")
     x = torch.empty(B, n_frames, **f32)
     k = None if dmol else torch.empty(B, n_frames, device=dev, dtype=torch.int32)
-    if dmol:
+    width2 = ()
+    if gauss:
+        if not (head.sd_beta > 0.0 and head.sd_eps >= 0.0):
+            raise ValueError("wavenet_decode: the Gaussian heads need sd_beta > 0 (the raw scales go through the softplus) and sd_eps >= 0")
+        u_n = draws if gauss == 1 else (None, draws[0])
+        name, width, width2 = "blvm_wavenet_gauss_decode", gauss, (head.num_mix if gauss == 1 else 0,)
+        operands = (float(head.sd_beta), float(head.sd_eps), *map(ptr, u_n))
+    elif dmol:
         name, width, operands = "blvm_wavenet_decode", head.num_mix, (head.log_eps, *map(ptr, draws))
     else:
         name, width = "blvm_wavenet_cat_decode", head.levels.numel()
         levels = _f32c(head.levels.to(dev)).reshape(width)  # (named: it must outlive the launch's enqueue)
         operands = (ptr(levels), ptr(draws[0]))
-    sizes = (ptr(packed), dil, n, B, C, S, O, width, n_frames)
+    sizes = (ptr(packed), dil, n, B, C, S, O, width, *width2, n_frames)
     if tables is not None:
         name, sizes = "blvm_wavenet_embed_cat_decode", (ptr(packed), ptr(tables), *sizes[1:])
     outs = (ptr(x),) if dmol else (ptr(x), ptr(k))

@@ -23,6 +23,7 @@ namespace {
 constexpr int F_MAX = 30;   // 3 * num_mix, num_mix = 10
 constexpr int NMIX = 10;
 constexpr int FPB = 256;    // frames per block
+constexpr int GMM_MAX_MIX = 16;  // K7b's general arm (gmm_any_kernel): 1 <= num_mix <= 16
 
 // The 30x30 head weights are read-only for the whole launch and wave-uniform: reading them through the CONSTANT
 // address space makes hipcc keep them on the scalar path (s_load -> SGPR operands of v_pk_fma) even inside loops that
@@ -719,10 +720,11 @@ long long fused_grid(int B, int Tp, int S, bool wgrad, int* nchunks_out) {
 size_t fused_ws_floats(long long grid) { return DW_TICKETS + (size_t)(grid + (grid + DW_GROUP - 1) / DW_GROUP) * DW_TILE; }
 
 int check_common(const float* dec, const float* W, const float* bias, const float* y, const int32_t* x_sl, int B,
-                 int T, int Tp, int S, int num_mix, int num_bins, int layout) {
+                 int T, int Tp, int S, int num_mix, int num_bins, int layout, bool any_count = false) {
   BLVM_REQUIRE(dec && y && x_sl, "dmol: null pointer");
   BLVM_REQUIRE((W == nullptr) == (bias == nullptr), "dmol: W and bias must both be given or both be NULL");
-  BLVM_REQUIRE(num_mix == NMIX, "dmol: this build supports num_mix == 10 (got %d)", num_mix);
+  if (any_count) BLVM_REQUIRE(num_mix >= 1 && num_mix <= GMM_MAX_MIX, "gmm: num_mix must be in 1..%d (got %d)", GMM_MAX_MIX, num_mix);
+  else BLVM_REQUIRE(num_mix == NMIX, "dmol: this build supports num_mix == 10 (got %d)", num_mix);
   BLVM_REQUIRE(B > 0 && T > 0 && Tp > 0 && S > 0 && num_bins > 1, "dmol: bad shape B=%d T=%d Tp=%d S=%d", B, T, Tp, S);
   BLVM_REQUIRE((long long)Tp * S >= T, "dmol: Tp*S (%d*%d) < T (%d)", Tp, S, T);
   BLVM_REQUIRE(layout == 0 || layout == 1, "dmol: layout must be 0 or 1");
@@ -939,17 +941,240 @@ extern "C" int blvm_gauss_head_bwd(const float* dec, int layout, const float* W,
   return BLVM_OK;
 }
 
+namespace blvm {
+namespace {
+
+// ---- K7b at any component count (1 <= K <= 16, K != 10: ten components keep dmol_kernel / dmol_rows_kernel above) ----------
+// dmol_kernel's mapping — one lane per frame, 256 frames per workgroup, staged through LDS with 16-byte accesses — with the frame
+// width F = 3 K a template argument: every index into the frame's register arrays is a compile-time constant (an array indexed by
+// a runtime component count would live in scratch), the [F,F] head Linear stays on the scalar path, and each count is its own
+// instantiation.  LDS rows are F | 1 floats: an odd dword stride is invertible mod the 64 banks, so the 64 lanes of a wave reading
+// column i of their own frames fall on 64 distinct banks for every F (F + 1 would be even for the odd counts).  Every stack size
+// takes this kernel: the rows kernel's verbatim 64 x 30 image and 15 k-pair MFMA product are written for F = 30.
+template <int K>
+struct GmmK {
+  static constexpr int F = 3 * K;
+  static constexpr int LD = F | 1;  // LDS row stride in floats
+};
+
+template <int K>
+__device__ __forceinline__ void stage_frames_k(const float* __restrict__ src, long long f0, long long n_frames, float* __restrict__ lds) {
+  constexpr int F = GmmK<K>::F, LD = GmmK<K>::LD;
+  const long long base = f0 * F;
+  const long long total = min((long long)FPB, n_frames - f0) * F;  // floats available
+  const bool vec = ((reinterpret_cast<uintptr_t>(src + base)) & 15u) == 0;
+  for (int i = threadIdx.x * 4; i < FPB * F; i += 256 * 4) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i + 3 < total && vec) {
+      v = *reinterpret_cast<const float4*>(src + base + i);
+    } else {
+      if (i + 0 < total) v.x = src[base + i + 0];
+      if (i + 1 < total) v.y = src[base + i + 1];
+      if (i + 2 < total) v.z = src[base + i + 2];
+      if (i + 3 < total) v.w = src[base + i + 3];
+    }
+    const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int idx = i + k, fr = idx / F, c = idx - fr * F;
+      lds[fr * LD + c] = e[k];
+    }
+  }
+}
+
+template <int K>
+__device__ __forceinline__ void unstage_frames_k(float* __restrict__ dst, long long f0, long long n_frames, const float* __restrict__ lds) {
+  constexpr int F = GmmK<K>::F, LD = GmmK<K>::LD;
+  const long long base = f0 * F;
+  const long long total = min((long long)FPB, n_frames - f0) * F;
+  const bool vec = ((reinterpret_cast<uintptr_t>(dst + base)) & 15u) == 0;
+  for (int i = threadIdx.x * 4; i < FPB * F; i += 256 * 4) {
+    float e[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int idx = i + k, fr = idx / F, c = idx - fr * F;
+      e[k] = lds[fr * LD + c];
+    }
+    if (i + 3 < total && vec) {
+      *reinterpret_cast<float4*>(dst + base + i) = make_float4(e[0], e[1], e[2], e[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (i + k < total) dst[base + i + k] = e[k];
+    }
+  }
+}
+
+// gmm_frame's math over K components: p[0..K) logits, p[K..2K) means, p[2K..3K) pre-softplus standard deviations.
+template <bool BWD, int K>
+__device__ __forceinline__ float gmm_frame_k(const DmolArgs& a, float yv, float (&p)[3 * K]) {
+  float mx = p[0];
+#pragma unroll
+  for (int m = 1; m < K; ++m) mx = fmaxf(mx, p[m]);
+  float se = 0.f;
+#pragma unroll
+  for (int m = 0; m < K; ++m) se += fexp(p[m] - mx);
+  const float lse_logits = mx + flog(se);
+  float lp[K], dmu[K], dsd[K];
+  float tmax = -INFINITY;
+  const float inv_beta = 1.f / a.sd_beta;
+#pragma unroll
+  for (int m = 0; m < K; ++m) {
+    const float mu = p[K + m], raw = p[2 * K + m];
+    const float sd = softplus_beta(raw, a.sd_beta, inv_beta) + a.sd_eps;
+    const float isd = frcp(sd), d = (yv - mu) * isd;
+    lp[m] = -0.5f * d * d - flog(sd) - 0.91893853320467274f + (p[m] - lse_logits);
+    tmax = fmaxf(tmax, lp[m]);
+    if (BWD) {
+      dmu[m] = d * isd;
+      dsd[m] = (d * d - 1.f) * isd * sigmoidf_(a.sd_beta * raw);
+    }
+  }
+  float s = 0.f, e[K];
+#pragma unroll
+  for (int m = 0; m < K; ++m) { e[m] = fexp(lp[m] - tmax); s += e[m]; }
+  const float ll = tmax + flog(s);
+  if (BWD) {
+    const float rs = frcp(s), rse = frcp(se);
+#pragma unroll
+    for (int m = 0; m < K; ++m) {
+      const float wgt = e[m] * rs;
+      const float pm = fexp(p[m] - mx) * rse;
+      p[m] = wgt - pm;
+      p[K + m] = wgt * dmu[m];
+      p[2 * K + m] = wgt * dsd[m];
+    }
+  }
+  return ll;
+}
+
+template <bool BWD, int K>
+__global__ __launch_bounds__(256) void gmm_any_kernel(DmolArgs a) {
+  constexpr int F = GmmK<K>::F, LD = GmmK<K>::LD;
+  __shared__ __attribute__((aligned(16))) float lds[FPB * LD];
+  const long long f0 = (long long)blockIdx.x * FPB;
+  const long long f = f0 + threadIdx.x;
+  stage_frames_k<K>(a.dec, f0, a.n_frames, lds);
+  __syncthreads();
+
+  const FrameCoord fc = frame_coord(a, f);
+  float d[F];
+#pragma unroll
+  for (int i = 0; i < F; ++i) d[i] = lds[threadIdx.x * LD + i];
+
+  cfloat* Wc = as_const(a.W);
+  cfloat* bc = as_const(a.bias);
+  float p[F];
+  if (a.W != nullptr) {
+#pragma unroll
+    for (int o = 0; o < F; ++o) {
+      float s = bc[o];
+#pragma unroll
+      for (int i = 0; i < F; ++i) s = fmaf(Wc[o * F + i], d[i], s);
+      p[o] = s;
+    }
+  } else {
+#pragma unroll
+    for (int o = 0; o < F; ++o) p[o] = d[o];
+  }
+  const float yv = fc.valid ? a.y[(size_t)fc.b * a.T + fc.tau] : 0.f;
+  const float ll = gmm_frame_k<BWD, K>(a, yv, p);
+
+  if (!BWD) {
+    const float llm = fc.valid ? ll : 0.f;
+    if (a.ll_twise != nullptr && fc.valid) a.ll_twise[(size_t)fc.b * a.T + fc.tau] = llm;
+    // per-utterance fp64 sums as in dmol_kernel: one LDS partial per utterance, then one global atomic per (workgroup, utterance)
+    __shared__ double part[256];
+    const bool lds_path = a.B <= 256;
+    if (lds_path) {
+      part[threadIdx.x] = 0.0;
+      __syncthreads();
+    }
+    const int b0 = __builtin_amdgcn_readfirstlane(fc.b);
+    const bool uniform = __all((fc.b == b0) || !fc.valid);
+    if (uniform) {
+      double v = (double)llm;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+      const unsigned long long vm = __ballot(fc.valid);
+      if (vm != 0ull) {
+        const int src = __ffsll((long long)vm) - 1;
+        const int bb = __shfl(fc.b, src, 64);
+        if ((threadIdx.x & 63) == 0) {
+          if (lds_path) atomicAdd(&part[bb], v);
+          else atomicAdd(a.log_prob + bb, v);
+        }
+      }
+    } else if (fc.valid) {
+      if (lds_path) atomicAdd(&part[fc.b], (double)llm);
+      else atomicAdd(a.log_prob + fc.b, (double)llm);
+    }
+    if (lds_path) {
+      __syncthreads();
+      if ((int)threadIdx.x < a.B && part[threadIdx.x] != 0.0) atomicAdd(a.log_prob + threadIdx.x, part[threadIdx.x]);
+    }
+  } else {
+    const float g = fc.valid ? a.g_b[fc.b] : 0.f;
+#pragma unroll
+    for (int o = 0; o < F; ++o) p[o] *= g;
+    float dd[F];
+    if (a.W != nullptr) {
+#pragma unroll
+      for (int i = 0; i < F; ++i) dd[i] = 0.f;
+#pragma unroll
+      for (int o = 0; o < F; ++o) {
+#pragma unroll
+        for (int i = 0; i < F; ++i) dd[i] = fmaf(Wc[o * F + i], p[o], dd[i]);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < F; ++i) dd[i] = p[i];
+    }
+    __syncthreads();  // everyone has read its frame from lds
+#pragma unroll
+    for (int i = 0; i < F; ++i) lds[threadIdx.x * LD + i] = dd[i];
+    __syncthreads();
+    unstage_frames_k<K>(a.d_dec, f0, a.n_frames, lds);
+    if (a.d_par != nullptr) {
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < F; ++i) lds[threadIdx.x * LD + i] = p[i];
+      __syncthreads();
+      unstage_frames_k<K>(a.d_par, f0, a.n_frames, lds);
+    }
+  }
+}
+
+template <bool BWD>
+int launch_gmm(DmolArgs& a, int num_mix, hipStream_t s) {
+  if (num_mix == NMIX) return launch_dmol<BWD>(a, s);  // ten components: the code they ran before the general arm existed
+  const long long blocks = (a.n_frames + FPB - 1) / FPB;
+  BLVM_REQUIRE(blocks < (1ll << 31), "gmm: too many frames");
+#define GMM_CASE(k) \
+  case k: hipLaunchKernelGGL((gmm_any_kernel<BWD, k>), dim3((unsigned)blocks), dim3(256), 0, s, a); break;
+  switch (num_mix) {
+    GMM_CASE(1) GMM_CASE(2) GMM_CASE(3) GMM_CASE(4) GMM_CASE(5) GMM_CASE(6) GMM_CASE(7) GMM_CASE(8) GMM_CASE(9)
+    GMM_CASE(11) GMM_CASE(12) GMM_CASE(13) GMM_CASE(14) GMM_CASE(15) GMM_CASE(16)
+    default: BLVM_REQUIRE(false, "gmm: num_mix must be in 1..%d (got %d)", GMM_MAX_MIX, num_mix);
+  }
+#undef GMM_CASE
+  return BLVM_OK;
+}
+
+}  // namespace
+}  // namespace blvm
+
 extern "C" int blvm_gmm_fwd(const float* dec, int layout, const float* W, const float* bias, const float* y,
                             const int32_t* x_sl, int B, int T, int Tp, int S, int num_mix, float sd_beta, float sd_eps,
                             double* log_prob, float* ll_twise, void* stream) {
   using namespace blvm;
-  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, 2, layout));
+  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, 2, layout, true));
   BLVM_REQUIRE(log_prob != nullptr && sd_beta > 0.f, "gmm_fwd: bad arguments");
   DmolArgs a = make_args(dec, layout, W, bias, y, x_sl, B, T, Tp, S, 2, 0.f);
   a.kind = 1; a.sd_beta = sd_beta; a.sd_eps = sd_eps;
   a.log_prob = log_prob;
   a.ll_twise = ll_twise;
-  BLVM_TRY(launch_dmol<false>(a, static_cast<hipStream_t>(stream)));
+  BLVM_TRY(launch_gmm<false>(a, num_mix, static_cast<hipStream_t>(stream)));
   BLVM_CHECK_LAUNCH("gmm_fwd");
   return BLVM_OK;
 }
@@ -958,14 +1183,14 @@ extern "C" int blvm_gmm_bwd(const float* dec, int layout, const float* W, const 
                             const int32_t* x_sl, const float* g_b, int B, int T, int Tp, int S, int num_mix, float sd_beta,
                             float sd_eps, float* d_dec, float* d_par, void* stream) {
   using namespace blvm;
-  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, 2, layout));
+  BLVM_TRY(check_common(dec, W, bias, y, x_sl, B, T, Tp, S, num_mix, 2, layout, true));
   BLVM_REQUIRE(g_b && d_dec && (d_par || !W) && sd_beta > 0.f, "gmm_bwd: bad arguments");
   DmolArgs a = make_args(dec, layout, W, bias, y, x_sl, B, T, Tp, S, 2, 0.f);
   a.kind = 1; a.sd_beta = sd_beta; a.sd_eps = sd_eps;
   a.g_b = g_b;
   a.d_dec = d_dec;
   a.d_par = d_par;
-  BLVM_TRY(launch_dmol<true>(a, static_cast<hipStream_t>(stream)));
+  BLVM_TRY(launch_gmm<true>(a, num_mix, static_cast<hipStream_t>(stream)));
   BLVM_CHECK_LAUNCH("gmm_bwd");
   return BLVM_OK;
 }

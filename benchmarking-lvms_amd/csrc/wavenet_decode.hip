@@ -18,7 +18,8 @@
 // The any-width block, the tile layers and the draw are the ones K10d (stcn_decode.hip) uses: decode_tiles.h.  The compile-time-
 // width path below (block_fast) is this kernel's own.
 //
-// Two heads (a template parameter, so each keeps its own code): the DMoL head (3 * num_mix <= 32 outputs, Gumbel-max + logistic
+// Heads (a template parameter, so each keeps its own code): the Gaussian-mixture and Gaussian heads (the DMoL head's padded 32 head
+// rows; mix_pick then gauss_draw, or gauss_draw on (mu, raw); unclamped), the DMoL head (3 * num_mix <= 32 outputs, Gumbel-max + logistic
 // draw) and the categorical head of the original paper (K7d's softmax over V classes, 16 <= V <= 1024): its Linear goes through the
 // same tile layer into an LDS logits buffer [16][V + 4], 32 lanes per row draw one class (cat_pick, decode_tiles.h), and the class
 // is fed back and written out as levels[k] — the model's table, copied to LDS once; no arithmetic on it.
@@ -88,17 +89,37 @@ struct EmbCatDecodeArgs : CatDecodeArgs {
   const float* tab;  // [2,V+1,C] the lookup tables of wavenet_embed.hip
 };
 
+// The Gaussian heads: v is [n_frames,B] standard normals (NULL: the mean); the mixture keeps u and num_mix, the plain Gaussian
+// head's two outputs are (mu, raw) and u is unused.  log_eps is unused.
+struct GaussDecodeArgs : DecodeArgs {
+  float sd_beta, sd_eps;  // sd = softplus_beta(raw) + sd_eps
+};
+
+// `gauss`: 0 none, 1 the Gaussian mixture (the DMoL head's layout and pick, gauss_draw), 2 the plain Gaussian (mu, raw)
 struct DmolHead {
   using Args = DecodeArgs;
   static constexpr bool categorical = false, embedded = false;
+  static constexpr int gauss = 0;
 };
 struct CatHead {
   using Args = CatDecodeArgs;
   static constexpr bool categorical = true, embedded = false;
+  static constexpr int gauss = 0;
 };
 struct EmbCatHead {
   using Args = EmbCatDecodeArgs;
   static constexpr bool categorical = true, embedded = true;
+  static constexpr int gauss = 0;
+};
+struct GmmHead {
+  using Args = GaussDecodeArgs;
+  static constexpr bool categorical = false, embedded = false;
+  static constexpr int gauss = 1;
+};
+struct GaussHead {
+  using Args = GaussDecodeArgs;
+  static constexpr bool categorical = false, embedded = false;
+  static constexpr int gauss = 2;
 };
 constexpr int CAT_MIN_V = 16, CAT_MAX_V = 1024, CAT_LOGIT_PAD = 4;
 
@@ -129,7 +150,7 @@ __device__ __forceinline__ f32x4 tile_from_regs(const float* __restrict__ A, int
 // the NEXT block in registers, loaded while the current block computes.  CC == 0: any width, loads where they are used.
 // RESUME: no steady-state prologue — rings and the last two samples are the caller's, frame t is absolute frame t0 + t, and
 // the sample pair is handed back; with the rings left in scratch that is the whole state.  A separate instantiation, so the
-// zero-start entry keeps its code.  HEAD: DmolHead or CatHead, separate instantiations for the same reason.
+// zero-start entry keeps its code.  HEAD: one of the head types above, separate instantiations for the same reason.
 template <int NW, int CC, int SS, bool RESUME, class HEAD>
 __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(typename HEAD::Args a) {
   extern __shared__ __align__(16) float smem[];
@@ -385,13 +406,26 @@ __global__ __launch_bounds__(NW * 64) void wn_decode_kernel(typename HEAD::Args 
       tile_layer<NW, false>(sAct, ldA, w + L.head_w, O, 0, DEC_HEAD_ROWS / 16, w + L.head_b, [&](int row, int o, float val) { sPar[row * DEC_HEAD_ROWS + o] = val; });
       __syncthreads();
       if (tid < DEC_ROWS && b0 + tid < B) {
-        // Gumbel-max component pick + clamped logistic draw (decode_tiles.h)
         const float* p = sPar + tid * DEC_HEAD_ROWS;
-        const int K = a.num_mix;
         const size_t f = (size_t)t * B + b0 + tid;
-        const int best = mix_pick(p, K, a.u != nullptr ? a.u + f * K : nullptr);
-        float x = p[K + best];
-        if (a.v != nullptr) x = logistic_draw(x, p[2 * K + best], a.v[f], a.log_eps);
+        float x;
+        if constexpr (HEAD::gauss == 2) {
+          // (mu, raw): the unclamped Gaussian draw (decode_tiles.h); no n: the mean
+          x = p[0];
+          if (a.v != nullptr) x = gauss_draw(x, p[1], a.v[f], a.sd_beta, a.sd_eps);
+        } else if constexpr (HEAD::gauss == 1) {
+          // Gumbel-max component pick + the component's unclamped Gaussian draw; no u, no n: the arg-max component's mean
+          const int K = a.num_mix;
+          const int best = mix_pick(p, K, a.u != nullptr ? a.u + f * K : nullptr);
+          x = p[K + best];
+          if (a.v != nullptr) x = gauss_draw(x, p[2 * K + best], a.v[f], a.sd_beta, a.sd_eps);
+        } else {
+          // Gumbel-max component pick + clamped logistic draw (decode_tiles.h)
+          const int K = a.num_mix;
+          const int best = mix_pick(p, K, a.u != nullptr ? a.u + f * K : nullptr);
+          x = p[K + best];
+          if (a.v != nullptr) x = logistic_draw(x, p[2 * K + best], a.v[f], a.log_eps);
+        }
         a.x_out[(size_t)(b0 + tid) * a.n_frames + t] = x;
         sX[2 * tid] = sX[2 * tid + 1];
         sX[2 * tid + 1] = x;
@@ -466,7 +500,8 @@ extern "C" size_t blvm_wavenet_decode_ring_offset_floats(int n_blocks, int C, in
 static int decode_run(bool resume, const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int num_mix,
                       int n_frames, int t0, float inv_std, float skip_scale, float log_eps, const float* u, const float* v,
                       const float* x_in, float* scratch, float* x_out, float* x_state, void* stream, int V = 0,
-                      const float* levels = nullptr, int32_t* k_out = nullptr, const float* tables = nullptr) {
+                      const float* levels = nullptr, int32_t* k_out = nullptr, const float* tables = nullptr, int gauss = 0,
+                      float sd_beta = 0.f, float sd_eps = 0.f) {
   using namespace blvm;
   const bool cat = V > 0;
   BLVM_REQUIRE(packed && dilations && scratch && x_out && aligned16(packed) && aligned16(scratch), "wavenet_decode: NULL or misaligned argument");
@@ -474,10 +509,13 @@ static int decode_run(bool resume, const float* packed, const int* dilations, in
   BLVM_REQUIRE(C > 0 && S > 0 && O > 0 && C % 16 == 0 && S % 16 == 0 && O % 16 == 0, "wavenet_decode: C, S, O must be multiples of 16");
   if (cat) {
     BLVM_REQUIRE(levels, "wavenet_cat_decode: NULL levels");
+  } else if (gauss == 2) {
+    BLVM_REQUIRE(u == nullptr, "wavenet_gauss_decode: the Gaussian head (head_kind 2) takes no component draws u");
   } else {
-    BLVM_REQUIRE(num_mix > 0 && 3 * num_mix <= DEC_HEAD_ROWS, "wavenet_decode: num_mix must be in [1, %d]", DEC_HEAD_ROWS / 3);
+    BLVM_REQUIRE(num_mix > 0 && 3 * num_mix <= DEC_HEAD_ROWS, "wavenet_decode: num_mix must be in [1, %d] (got %d)", DEC_HEAD_ROWS / 3, num_mix);
     BLVM_REQUIRE((u == nullptr) == (v == nullptr), "wavenet_decode: u and v are given together (both NULL: the mode)");
   }
+  if (gauss) BLVM_REQUIRE(sd_beta > 0.f && sd_eps >= 0.f, "wavenet_gauss_decode: need sd_beta > 0, sd_eps >= 0");
   if (resume) BLVM_TRY(check_resume("wavenet_decode_resume", "sample", "n_frames", t0, n_frames, x_in, x_state));
   const size_t lds = decode_lds_bytes(C, S, O, V);
   if (cat) BLVM_REQUIRE(lds <= 160 * 1024, "wavenet_cat_decode: C=%d, S=%d, O=%d, V=%d need %zu bytes of LDS (> 160 KB)", C, S, O, V, lds);
@@ -509,6 +547,13 @@ static int decode_run(bool resume, const float* packed, const int* dilations, in
   const bool even = n_blocks % 2 == 0;
   if (tables) return decode_launch<EmbCatHead>(resume, even, a, lds, static_cast<hipStream_t>(stream));
   if (cat) return decode_launch<CatHead>(resume, even, a, lds, static_cast<hipStream_t>(stream));
+  if (gauss) {
+    GaussDecodeArgs g;
+    static_cast<DecodeArgs&>(g) = a;
+    g.sd_beta = sd_beta; g.sd_eps = sd_eps;
+    if (gauss == 1) return decode_launch<GmmHead>(resume, even, g, lds, static_cast<hipStream_t>(stream));
+    return decode_launch<GaussHead>(resume, even, g, lds, static_cast<hipStream_t>(stream));
+  }
   return decode_launch<DmolHead>(resume, even, a, lds, static_cast<hipStream_t>(stream));
 }
 
@@ -525,6 +570,29 @@ extern "C" int blvm_wavenet_decode_resume(const float* packed, const int* dilati
                                           float* x_state, void* stream) {
   return decode_run(true, packed, dilations, n_blocks, B, C, S, O, num_mix, n_frames, t0, inv_std, skip_scale, log_eps, u, v, x_in,
                     scratch, x_out, x_state, stream);
+}
+
+// The Gaussian heads: head_kind 1 the mixture (num_mix components, 3 * num_mix <= 32 head rows), 2 the plain Gaussian (2 head rows).
+static int gauss_kind_ok(int head_kind) {
+  BLVM_REQUIRE(head_kind == 1 || head_kind == 2, "wavenet_gauss_decode: head_kind must be 1 (Gaussian mixture) or 2 (Gaussian), got %d", head_kind);
+  return BLVM_OK;
+}
+
+extern "C" int blvm_wavenet_gauss_decode(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int head_kind,
+                                         int num_mix, int n_frames, float inv_std, float skip_scale, float sd_beta, float sd_eps,
+                                         const float* u, const float* n, float* scratch, float* x_out, void* stream) {
+  BLVM_TRY(gauss_kind_ok(head_kind));
+  return decode_run(false, packed, dilations, n_blocks, B, C, S, O, num_mix, n_frames, 0, inv_std, skip_scale, 0.f, u, n, nullptr, scratch,
+                    x_out, nullptr, stream, 0, nullptr, nullptr, nullptr, head_kind, sd_beta, sd_eps);
+}
+
+extern "C" int blvm_wavenet_gauss_decode_resume(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O,
+                                                int head_kind, int num_mix, int n_frames, int t0, float inv_std, float skip_scale,
+                                                float sd_beta, float sd_eps, const float* u, const float* n, const float* x_in,
+                                                float* scratch, float* x_out, float* x_state, void* stream) {
+  BLVM_TRY(gauss_kind_ok(head_kind));
+  return decode_run(true, packed, dilations, n_blocks, B, C, S, O, num_mix, n_frames, t0, inv_std, skip_scale, 0.f, u, n, x_in, scratch,
+                    x_out, x_state, stream, 0, nullptr, nullptr, nullptr, head_kind, sd_beta, sd_eps);
 }
 
 // The categorical head is built for 16 <= V <= 1024 in multiples of 16: one workgroup streams the whole head weight per frame, which

@@ -4,7 +4,7 @@ no gradient clipping in this loop (:206-209)."""
 from _common import run, wavenet_split_eval  # noqa: I001
 
 from blvm.models import WaveNet
-from blvm.modules.distributions import CategoricalDense, DiscretizedLogisticMixtureDense
+from blvm.modules.distributions import CategoricalDense, DiagonalGaussianDense, DiagonalGaussianMixtureDense, DiscretizedLogisticMixtureDense
 from blvm.utils.argparsers import parser, str2bool
 
 parser.set_defaults(lr=3e-4, epochs=3000, num_workers=8, save_checkpoints=True, optimizer="Adam")  # experiment_wavenet_audio.py:32-40
@@ -32,8 +32,14 @@ def build_model(args):
         # softmax over the 2**num_bits classes (experiment_wavenet_audio.py:154-155); the model quantises its float input into the
         # targets itself ("WaveNet with the categorical head")
         lik = CategoricalDense(args.res_channels, 2**args.num_bits)
+    elif args.likelihood == "Gaussian":
+        lik = DiagonalGaussianDense(args.res_channels, 1, initial_sd=1, epsilon=1e-4)  # experiment_wavenet_audio.py:156-157
+    elif args.likelihood[:4] == "GMM-":
+        # GMM-<n> (:158-160); no input normalisation: the reference's gate for it tests "gaussian" / "gmm-" (:79), spellings its own
+        # model construction rejects, so its runs never normalise ("WaveNet with the Gaussian heads")
+        lik = DiagonalGaussianMixtureDense(args.res_channels, 1, num_mix=int(args.likelihood.split("-")[-1]), initial_sd=1, epsilon=1e-4)
     else:
-        raise NotImplementedError("libblvm_hip: WaveNet is built with the DMoL and the Categorical likelihoods")
+        raise ValueError(f"Unknown likelihood: {args.likelihood}")
     # --input_embedding_dim E > 1: the class-in model, nn.Embedding(2**num_bits, E) in front of a grouped causal conv.  The reference
     # passes E as `in_channels` (:168), which its model cannot run; here it is `embedding_dim` ("WaveNet with embedded
     # input").  The float input is quantised into the classes by the model.

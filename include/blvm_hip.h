@@ -257,8 +257,10 @@ int blvm_dmol_bwd_fused(const float* dec, int layout, const float* W, const floa
 
 /* K7b / K7c  Gaussian output heads, same calling convention, frame layout, masks and float64 per-utterance sums as K7:
  *   gmm: `DiagonalGaussianMixtureDense.forward` + `.log_prob` (`blvm/modules/distributions.py:153-206`,
- *        `gaussian_mixture_ll` `blvm/utils/log_likelihoods.py:42-60`): dec [rows, S*3*num_mix] -> Linear(30->30) (W NULL:
- *        dec ARE the parameters) -> logits | means | pre-softplus sds, sd = softplus_beta(raw) + sd_eps.
+ *        `gaussian_mixture_ll` `blvm/utils/log_likelihoods.py:42-60`): dec [rows, S*3*num_mix] -> Linear(3 num_mix -> 3 num_mix) (W
+ *        NULL: dec ARE the parameters) -> logits | means | pre-softplus sds, sd = softplus_beta(raw) + sd_eps.  1 <= num_mix <= 16
+ *        (anything else: an error before any launch); ten components run the kernels of the audio models, any other count a
+ *        general arm at frame width 3 num_mix.
  *   gauss_head: `DiagonalGaussianDense.forward` + `.log_prob` (`distributions.py:105-150`, `gaussian_ll`
  *        `log_likelihoods.py:17-39`): dec [rows, S*2] -> Linear(2->2) (W NULL: none) -> mean | pre-softplus sd.
  *   bwd: d_dec (gradient wrt dec) and d_par (gradient wrt the Linear's output; dW = d_par^T dec, db = colsum(d_par)). */
@@ -826,6 +828,25 @@ int blvm_wavenet_cat_decode(const float* packed, const int* dilations, int n_blo
 int blvm_wavenet_cat_decode_resume(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int V,
                                    int n_frames, int t0, float inv_std, float skip_scale, const float* levels, const float* u,
                                    const float* x_in, float* scratch, float* x_out, int32_t* k_out, float* x_state, void* stream);
+
+/* K10c  The same one-launch sampling with the Gaussian heads, from an all-zero start and from a state.  Arguments as for the DMoL
+ *   pair above, except: head_kind, num_mix, sd_beta, sd_eps, u, n replace num_mix, log_eps, u, v.
+ *   head_kind 1: the diagonal Gaussian mixture.  The head Linear is [3 num_mix, O] -> (logits, means, raw sds), zero-padded to [32,O]
+ *     as the DMoL head's (3 num_mix <= 32).  Gumbel-max component pick with u [n_frames,B,num_mix], then x = mu + (softplus_beta(raw)
+ *     + sd_eps) n with n [n_frames,B] standard normals (as blvm_mix_sample kind 1).  u and n are given together; both NULL: the
+ *     arg-max component's mean.
+ *   head_kind 2: the diagonal Gaussian.  The head Linear is [2,O] -> (mu, raw), zero-padded to [32,O]; num_mix is ignored, u must be
+ *     NULL; x = mu + (softplus_beta(raw) + sd_eps) n, n NULL: the mean.
+ *   Neither draw is clamped.  Any other head_kind, sd_beta <= 0 or sd_eps < 0: an error before any launch.
+ *   packed: blvm_wavenet_decode_pack_floats floats.  scratch, the rings, blvm_wavenet_decode_ring_fill, x_in / x_state: shared with
+ *     the DMoL pair unchanged. */
+int blvm_wavenet_gauss_decode(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int head_kind,
+                              int num_mix, int n_frames, float inv_std, float skip_scale, float sd_beta, float sd_eps, const float* u,
+                              const float* n, float* scratch, float* x_out, void* stream);
+int blvm_wavenet_gauss_decode_resume(const float* packed, const int* dilations, int n_blocks, int B, int C, int S, int O, int head_kind,
+                                     int num_mix, int n_frames, int t0, float inv_std, float skip_scale, float sd_beta, float sd_eps,
+                                     const float* u, const float* n, const float* x_in, float* scratch, float* x_out, float* x_state,
+                                     void* stream);
 
 /* K10e  WaveNet with embedded class input (`WaveNet(embedding_dim=E, num_bins=V)`, `blvm/models/wavenet/wavenet.py:105-113,182`):
  *   nn.Embedding(V, E) and the causal convolution with groups = C, kernel size 2 (m = E / C inputs per output channel) as two lookup
